@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s + achieved algorithmic GB/s of the ray-march hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one frame: one pass of the ray-march over every pixel of the viewport
 (BASELINE.json: bonsai 256^3 uint8 @ 1920x1080, benchmark parameters of src/main.rs:180-190
 with step 0.01, the reference's effective camera eye (0.5,0.5,1.5)).  The real .raw is not in
 the repository (.MISSING_LARGE_BLOBS), so the volume is volym_amd.synth.synth_bonsai(256).
+
+--dump-outputs DIR writes, after the timed steps, the frame the timed loop's last step produced (what a caller of the
+path reads back: RGBA8 of the whole viewport, assembled on rank 0 when N > 1) as DIR/frame_rgba8.npy in float32, so that
+two builds can be compared output for output (the inputs are seeded: the same arguments give the same inputs).
+bench_outputs/ is the directory git ignores for it.
 
 N > 1 (one process per GPU, launched by torch.distributed.run): the framebuffer is sharded by interleaved
 16x16 screen tiles over the ranks, the volume is replicated, and every frame's PACKED shards (only the tiles
@@ -31,6 +36,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_MAX_BYTES = 64 * 1000 * 1000     # --dump-outputs: at most this many bytes in all
+DUMP_SAMPLE_SEED = 20261015           # --dump-outputs: the fixed pixel sample of a frame above the limit
 
 
 def build_scene(args):
@@ -100,6 +107,24 @@ def frame_check(args, dims, volume, importances, lut, state, got_u8, n_rows=68):
     if int(d.max()) <= 1:
         return "ok"
     return "MISMATCH: %d of %d sampled pixels differ from the oracle by more than 1 LSB (max %d)" % (int((d.max(axis=-1) > 1).sum()), len(rows) * W, int(d.max()))
+
+
+def dump_outputs(out_dir, frame_u8):
+    """--dump-outputs: the last timed frame as out_dir/frame_rgba8.npy, float32 of shape (H, W, 4).  A frame above
+    DUMP_MAX_BYTES (3840x2160 and up) is written as a fixed, seeded sample of its pixels instead: frame_rgba8.npy of
+    shape (K, 4) and frame_rgba8_index.npy, the row-major pixel indices of the sample (float64, sorted).  Returns the
+    file names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    H, W, _ = frame_u8.shape
+    pixels = frame_u8.reshape(H * W, 4).astype(np.float32)
+    if pixels.nbytes + 4096 <= DUMP_MAX_BYTES:
+        np.save(os.path.join(out_dir, "frame_rgba8.npy"), pixels.reshape(H, W, 4))
+        return ["frame_rgba8.npy"]
+    k = (DUMP_MAX_BYTES - 4096) // (4 * 4 + 8)          # float32 RGBA + float64 index per sampled pixel; room for the .npy headers
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(H * W, size=k, replace=False))
+    np.save(os.path.join(out_dir, "frame_rgba8.npy"), pixels[idx])
+    np.save(os.path.join(out_dir, "frame_rgba8_index.npy"), idx.astype(np.float64))
+    return ["frame_rgba8.npy", "frame_rgba8_index.npy"]
 
 
 def make_context(args, demo, _lib, W, H, device, dims, volume, importances, lut, state, frames_in_flight=1):
@@ -204,10 +229,15 @@ def main():
     ap.add_argument("--turntable-degrees", type=float, default=0.25, help="rotation between consecutive views of the turntable")
     ap.add_argument("--no-frame-check", action="store_true", help="skip the untimed check of the frame against the oracle")
     ap.add_argument("--scene", choices=["bonsai", "ball", "vessels"], default="bonsai", help="synthetic volume of the scheduling rows (the metric is quoted on bonsai)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step to DIR/frame_rgba8.npy (float32; a seeded "
+                         "pixel sample above 64 MB)")
     ap.add_argument("--workload", choices=["c1", "c2", "c3", "c4", "c5"],
                     help="BASELINE.json configs[0..4] presets (default = c3, the configuration the metric is quoted on): "
                          "c1 teapot 512x512, c2 bonsai 1080p direct kernel, c3 bonsai 1080p, c4 bonsai 4K, c5 synthetic 1024^3 + labels 4K importance")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "c1":
         args.width = args.height = 512
         args.teapot = True
@@ -245,6 +275,7 @@ def main():
     W, H = args.width, args.height
     exit_code = 0
     gather_check = frame_check_result = None
+    last_frame = None               # --dump-outputs: the frame of the last timed step (rank 0)
     first_frame_ms = moving_view_ms = static_views_ms = ray_pool_ms = None
     mg_info = None
 
@@ -318,6 +349,8 @@ def main():
         ctx.sync()
         torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
+        if args.dump_outputs:
+            last_frame = ctx.read_rgba8()          # the frame of the latest pass, whichever frame context ran it
         local = ctx
     else:
         # ---------------------------------------------- N GPUs (or N virtual ranks) ---------------------------------
@@ -366,6 +399,7 @@ def main():
                        "host_enqueue_us_per_frame": None, "per_stage_ms_rank0": None}
             if rank == 0:
                 assembled = fb_ctx.read_rgba8()
+                last_frame = assembled
             fb_ctx.set_shard(0, 1)                               # the reference frame of the self-check is the whole frame
             fb_ctx.update(state.camera_uniforms(), state.parameter_uniforms())
             if rank == 0:
@@ -410,6 +444,8 @@ def main():
                 dist.barrier()
             torch.cuda.synchronize(dev)
             dt = time.perf_counter() - t0
+            if rank == 0 and args.dump_outputs:
+                last_frame = mg.read_rgba8()               # before mg.profile below renders more frames
             over = tim["overflowed"]
             if procs > 1:
                 t = torch.tensor([dt, float(over)], dtype=torch.float64)
@@ -553,6 +589,9 @@ def main():
             out["cpu_baseline"] = cb
         else:
             out["cpu_baseline"] = None
+        out["dump_outputs"] = None
+        if args.dump_outputs and last_frame is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, last_frame)}
         failed = [c for c in (gather_check, frame_check_result) if c is not None and c != "ok"]
         if failed:                       # a wrong frame is not a benchmark result
             out["value"] = None
