@@ -339,6 +339,7 @@ def test_frames_in_flight(oracle, volym_lib, bonsai64):
         ctx.set_option(_lib.OPT_FRAMES_IN_FLIGHT, 2)
         _setup_ctx(ctx, raw, labels, common.BONSAI_SEGMENTS, dims, 0)
         n = 0
+        ptrs = []
         for par in pars:
             pu = _lib.ParameterUniforms.from_buffer_copy(bytes(par))
             for pose in poses:                       # 5 views per parameter set: the parity of the frame counter keeps changing sides
@@ -352,7 +353,9 @@ def test_frames_in_flight(oracle, volym_lib, bonsai64):
                 err, over, du8, _ = common.compare_images(gf, gu, ref[0], ref[1], TOL)
                 assert over == 0 and err <= TOL and du8 <= 1, (n, pose, err, over, du8)
                 assert np.array_equal(ctx.read_blit(), gu), (n, pose)
+                ptrs.append(ctx.frame_device_ptr())      # the buffer of the latest pass: the context's and the twin's in turn
                 n += 1
+        assert ptrs[0] != ptrs[1] and all(p == ptrs[i & 1] for i, p in enumerate(ptrs)), ptrs
         # a standing view: frames back to back on both streams, settled lists, then the two latest frames
         cam = oracle.benchmark_camera_uniforms(W / H, 35.0, 20.0, 0.5)
         par = pars[0]

@@ -891,6 +891,9 @@ int volym_set_option(volym_ctx* c, int key, int value)
             if (c->twin) {
                 int rc = volym_sync(c);
                 if (rc != VOLYM_OK) return rc;
+                // (nothing of ours may keep pointing at the twin's buffers: a caller may have bound what volym_frame_device_ptr gave)
+                if (c->d_frame == c->twin->d_frame_own) c->d_frame = c->d_frame_own;
+                if (c->d_shard == c->twin->d_shard_own) c->d_shard = c->d_shard_own;
                 volym_destroy(c->twin);
                 c->twin = nullptr; c->last = c->last_blit = nullptr; c->flight_parity = 0;
             }
@@ -911,6 +914,9 @@ int volym_set_option(volym_ctx* c, int key, int value)
             rc = volym_set_shard(t, c->rank, c->world);
             if (rc != VOLYM_OK) { const std::string m = t->err; volym_destroy(t); return fail(c, rc, "second frame context: " + m); }
         }
+        // output buffers the caller bound before: the twin renders into them too (volym_bind_output)
+        if (c->d_frame != c->d_frame_own) t->d_frame = c->d_frame;
+        if (c->d_shard != c->d_shard_own) t->d_shard = c->d_shard;
         c->twin = t;
         return VOLYM_OK;
     }
@@ -1599,15 +1605,18 @@ int volym_read_blit(volym_ctx* c, uint8_t* out)
 
 uint32_t volym_local_tiles(const volym_ctx* c) { return c ? c->n_local : 0u; }
 size_t volym_shard_bytes(const volym_ctx* c) { return c ? static_cast<size_t>(c->shard_tiles) * 1024u : 0u; }
-void* volym_shard_device_ptr(volym_ctx* c) { return c ? c->d_shard : nullptr; }
-void* volym_frame_device_ptr(volym_ctx* c) { return c ? c->d_frame : nullptr; }
+// with a twin: the buffers of the latest pass, as volym_read_rgba8 reads them
+void* volym_shard_device_ptr(volym_ctx* c) { return c ? ((c->twin && c->last) ? c->last : c)->d_shard : nullptr; }
+void* volym_frame_device_ptr(volym_ctx* c) { return c ? ((c->twin && c->last) ? c->last : c)->d_frame : nullptr; }
 
 int volym_bind_output(volym_ctx* c, void* shard_rgba8, void* frame_rgba8)
 {
     if (!c) return VOLYM_E_INVALID;
-    // takes effect for launches enqueued after this call; earlier launches keep their pointers
+    // takes effect for launches enqueued after this call; earlier launches keep their pointers.  The twin renders into the
+    // same buffers (NULL: each context its own)
     c->d_shard = shard_rgba8 ? static_cast<uint32_t*>(shard_rgba8) : c->d_shard_own;
     c->d_frame = frame_rgba8 ? static_cast<uint32_t*>(frame_rgba8) : c->d_frame_own;
+    TWIN_FORWARD(c, volym_bind_output(c->twin, shard_rgba8, frame_rgba8));
     return VOLYM_OK;
 }
 
