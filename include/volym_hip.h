@@ -78,16 +78,17 @@ enum {
     VOLYM_OPT_REBALANCE_ROUNDS = 9, /* kernel 2: after a standing view's list is dealt, re-balance it this many times (0..8) from
                                     the times its workgroups took (measured: the list then depends on the weather).  Default 0. */
     VOLYM_OPT_FRAMES_IN_FLIGHT = 11, /* 1 (default) = one frame after the other on the context's stream.  2 = the context keeps a
-                                  second complete context on the same device (stream, frame buffer, copy of the volume, lists,
-                                  feedback) and volym_compute_pass alternates between the two: a frame of the persistent kernel
+                                  second frame slot (stream, frame buffer, tables, distance field, lists, feedback) that marches
+                                  the same scene, and volym_compute_pass alternates between the two: a frame of the persistent kernel
                                   ends on its longest chains, and the next frame's workgroups take the CUs it leaves idle
                                   (1920x1080: 31.9 -> 27.6 us per frame; 3840x2160: 74.7 -> 70.7).  Set it before the volume,
-                                  the importances and the transfer function (they go to both), and not with a caller's stream.
-                                  volym_update / _settle / _sync / _set_* and volym_bind_output act on both; volym_read_rgba8 /
+                                  the importances and the transfer function, and not with a caller's stream.
+                                  volym_update / _settle / _sync / _set_* and volym_bind_output act on both slots; volym_read_rgba8 /
                                   _rgba32f / volym_blit and volym_frame_device_ptr / _shard_device_ptr take the frame of the
                                   latest pass; volym_throttle marks it; volym_stats_pass, volym_time_*
-                                  and volym_selftest_ray_setup use the first context alone (one frame at a time); the shard /
-                                  pack / assemble calls and volym_set_stream return VOLYM_E_STATE.  Memory: everything twice. */
+                                  and volym_selftest_ray_setup use the first slot alone (one frame at a time); the shard /
+                                  pack / assemble calls and volym_set_stream return VOLYM_E_STATE.  Memory: the volume,
+                                  importances and macro cells once; the frame buffers, tables and work lists twice. */
     VOLYM_OPT_SETUP_IEEE = 10  /* 1 = the ray set-up (wgsl:221-241) runs its 14 divisions as 14 plain IEEE divisions; default 0: the
                                   divisions that share a denominator share its refined reciprocal -- the same instructions on the
                                   same values, so the same bits (raymarch_device.h make_ray; volym_selftest_ray_setup).  Takes
@@ -202,18 +203,18 @@ int volym_read_blit(volym_ctx* ctx, uint8_t* out);
 uint32_t volym_local_tiles(const volym_ctx* ctx);
 size_t volym_shard_bytes(const volym_ctx* ctx);
 /* The buffers the latest volym_compute_pass renders into (bound or the context's own); with two frames in flight, those of
- * the frame context that ran it, so that volym_frame_device_ptr holds what volym_read_rgba8 reads. */
+ * the frame slot that ran it, so that volym_frame_device_ptr holds what volym_read_rgba8 reads. */
 void* volym_shard_device_ptr(volym_ctx* ctx);
 void* volym_frame_device_ptr(volym_ctx* ctx);
 /* Let the caller own the device buffers (e.g. torch tensors handed to RCCL):
  * shard_rgba8 = volym_shard_bytes() bytes, frame_rgba8 = W*H*4 bytes; NULL gives the context its own back.  Takes effect for
  * passes enqueued after the call; a pass already enqueued keeps the buffers it was launched with.
- * With VOLYM_OPT_FRAMES_IN_FLIGHT = 2 both frame contexts render into the bound buffers (NULL: each into its own again), so
+ * With VOLYM_OPT_FRAMES_IN_FLIGHT = 2 both frame slots render into the bound buffers (NULL: each into its own again), so
  * consecutive passes may write one buffer at the same time.  Frames of the same view write the same pixels, and a buffer that
  * receives them is well defined.  A caller that moves the camera with two frames in flight binds a different buffer before
  * each volym_compute_pass, as a swap chain does: a ring of two or more buffers, rebound before each pass, gives every frame
- * its own.  Back to VOLYM_OPT_FRAMES_IN_FLIGHT = 1, the bound buffers stay bound (a buffer of the twin itself excepted: the
- * context takes its own back). */
+ * its own.  Back to VOLYM_OPT_FRAMES_IN_FLIGHT = 1, the bound buffers stay bound (a buffer of the second slot itself excepted:
+ * the context takes its own back). */
 int volym_bind_output(volym_ctx* ctx, void* shard_rgba8, void* frame_rgba8);
 /* Root side of the image gather: `gathered` = world shards back to back in rank order
  * (device memory, world * volym_shard_bytes() bytes) -> raster W*H*4 in the frame buffer. */

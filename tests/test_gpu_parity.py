@@ -324,7 +324,7 @@ def test_ray_setup_selftest(oracle, volym_lib, bonsai64):
 
 
 def test_frames_in_flight(oracle, volym_lib, bonsai64):
-    """VOLYM_OPT_FRAMES_IN_FLIGHT = 2: compute passes alternate between the context and its twin (own stream and frame buffer).
+    """VOLYM_OPT_FRAMES_IN_FLIGHT = 2: compute passes alternate between the context's two frame slots (own stream and frame buffer).
     Every frame of a sequence of views -- i.e. frames of BOTH contexts -- against the oracle (floats, rgba8, and the blit of the
     latest frame), frames enqueued back to back without a sync in between, standing views through settle, the calls that are
     refused, and the way back to one frame at a time."""
@@ -353,7 +353,7 @@ def test_frames_in_flight(oracle, volym_lib, bonsai64):
                 err, over, du8, _ = common.compare_images(gf, gu, ref[0], ref[1], TOL)
                 assert over == 0 and err <= TOL and du8 <= 1, (n, pose, err, over, du8)
                 assert np.array_equal(ctx.read_blit(), gu), (n, pose)
-                ptrs.append(ctx.frame_device_ptr())      # the buffer of the latest pass: the context's and the twin's in turn
+                ptrs.append(ctx.frame_device_ptr())      # the buffer of the latest pass: slot 0's and slot 1's in turn
                 n += 1
         assert ptrs[0] != ptrs[1] and all(p == ptrs[i & 1] for i, p in enumerate(ptrs)), ptrs
         # a standing view: frames back to back on both streams, settled lists, then the two latest frames
@@ -383,7 +383,7 @@ def test_frames_in_flight(oracle, volym_lib, bonsai64):
         ctx.sync()
         err, over, du8, _ = common.compare_images(ctx.read_rgba32f(), ctx.read_rgba8(), ref[0], ref[1], TOL)
         assert over == 0 and err <= TOL and du8 <= 1
-        with pytest.raises(_lib.VolymError) as e:   # a twin needs the scene from the start
+        with pytest.raises(_lib.VolymError) as e:   # a second frame slot needs the scene from the start
             ctx.set_option(_lib.OPT_FRAMES_IN_FLIGHT, 2)
         assert e.value.code == _lib.E_STATE
 

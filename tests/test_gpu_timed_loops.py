@@ -1,7 +1,7 @@
 """The frame loops bench.py times, frame by frame against the CPU oracle.
 
 bench.py's timed loop keeps two frames in flight (VOLYM_OPT_FRAMES_IN_FLIGHT = 2: compute passes alternate between the
-context and its twin), renders into a caller-owned buffer bound with volym_bind_output, writes no float side buffer (the
+two frame slots of the context), renders into a caller-owned buffer bound with volym_bind_output, writes no float side buffer (the
 16-byte super-fill stores) and runs work lists dealt by the cost feedback.  Its turntable runs up to three frames ahead of
 the device, each frame on lists dealt on earlier views.  These tests check every frame of such loops -- frames of both
 frame contexts -- against the oracle (rgba8 within 1 LSB), on rows sampled every 8th row and shifted by the frame's index,
@@ -142,7 +142,7 @@ def _run_ahead(ctx, views, kernels=None):
     return bufs
 
 
-# ---- 1. volym_bind_output and volym_frame_device_ptr with a twin -------------------------------------------------------
+# ---- 1. volym_bind_output and volym_frame_device_ptr with a second frame slot ------------------------------------------
 
 def test_bind_output_with_twin(oracle, volym_lib):
     """Both frame contexts render into the bound buffer; NULL gives each its own back; the binding survives the way back
@@ -154,7 +154,7 @@ def test_bind_output_with_twin(oracle, volym_lib):
     with _context(oracle, W, H, n, 2, _params_state(W, H)) as ctx:
         buf = _buffer(W, H)
         ctx.bind_output(None, buf.data_ptr())
-        for k in range(4):                           # passes 0 and 2 on the context, 1 and 3 on the twin
+        for k in range(4):                           # passes 0 and 2 on slot 0, 1 and 3 on slot 1
             cu, pu = views[k]
             buf.fill_(SENTINEL)
             torch.cuda.synchronize()
@@ -196,8 +196,8 @@ def test_bind_output_with_twin(oracle, volym_lib):
 
 
 def test_bind_output_before_twin_and_twin_buffer(oracle, volym_lib):
-    """A buffer bound before VOLYM_OPT_FRAMES_IN_FLIGHT = 2 is the twin's too; a context that had the twin's own buffer
-    bound takes its own back when the twin goes (nothing points at the freed buffer)."""
+    """A buffer bound before VOLYM_OPT_FRAMES_IN_FLIGHT = 2 is the second frame slot's too; a context that had that slot's own
+    buffer bound takes its own back when the slot goes (nothing points at the freed buffer)."""
     from volym_amd import _lib, demo
     W, H, n = 200, 120, 64
     dims, (volume, importances, lut), _ = _scene(oracle, n)
@@ -223,7 +223,7 @@ def test_bind_output_before_twin_and_twin_buffer(oracle, volym_lib):
             ctx.update(*views[k])
             ctx.compute_pass()
         ctx.sync()
-        twin_own = ctx.frame_device_ptr()            # the twin ran the latest pass: its own buffer
+        twin_own = ctx.frame_device_ptr()            # slot 1 ran the latest pass: its own buffer
         ctx.bind_output(None, twin_own)
         ctx.set_option(_lib.OPT_FRAMES_IN_FLIGHT, 1)
         assert ctx.frame_device_ptr() != twin_own
@@ -255,7 +255,7 @@ def test_timed_path_two_in_flight(oracle, volym_lib, kw):
             ctx.compute_pass()
         ctx.sync()
         ctx.settle()
-        for k in range(4):                           # two pairs: context, twin, context, twin
+        for k in range(4):                           # two pairs: slot 0, slot 1, slot 0, slot 1
             buf.fill_(SENTINEL)
             torch.cuda.synchronize()
             ctx.compute_pass()
@@ -300,7 +300,7 @@ def test_turntable_runs_ahead(oracle, volym_lib, flight, kw):
     _turntable_case(oracle, 1920, 1080, 256, flight, kw, TURNTABLE)
 
 
-# ---- 4. kernel switches under a twin -------------------------------------------------------------------------------------
+# ---- 4. kernel switches with a second frame slot ------------------------------------------------------------------------
 
 def test_kernel_switches_under_twin(oracle, volym_lib):
     """VOLYM_OPT_KERNEL 2 and 3 alternate between passes of a moving view with two frames in flight; the pattern 2, 3, 3, 2

@@ -40,7 +40,7 @@ def test_virtual_ranks_native_loop(volym_lib, world):
     dims, vol, imp, lut, state = _scene(W, H)
     full = _solo(W, H, dims, vol, imp, lut, state)
     with mgpu.MultiGpu(W, H, devices=[0] * world, transport=mgpu.COPY) as mg:
-        with pytest.raises(_lib.VolymError) as e:        # frame twins are a single-context option (include/volym_hip.h)
+        with pytest.raises(_lib.VolymError) as e:        # frame slots are a single-context option (include/volym_hip.h)
             mg.set_option(_lib.OPT_FRAMES_IN_FLIGHT, 2)
         assert e.value.code == _lib.E_STATE
         mg.set_volume(vol, dims, 0)

@@ -1,4 +1,4 @@
-// Internal: the context behind include/volym_hip.h (one device, one stream, one W x H output) and the pieces of host
+// Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: C ABI; mgpu.hip: the native multi-GPU loop).
 #pragma once
 
@@ -7,6 +7,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -31,49 +32,57 @@ struct WorkList {
 
 }  // namespace volym
 
-struct volym_ctx {
-    int device = 0;
+namespace volym {
+
+// What a capture hands the feedback thread: written by the caller before FB_CAPTURED, by the worker before FB_READY.
+struct FbJob {
+    int list = 0;                            // which of lists[] the captured launch ran
+    uint32_t n_entries = 0;
+    uint64_t view_serial = 0;
+    bool captured_has_dp = false;
+    bool continuous = false;
+    bool plain = false;                      // table mode, no importance mode (the common instantiation)
+    uint32_t max_grid = 0, waves = 16;
+    int dp_min_cost = -1;
+    uint32_t dp_share_pct = 60, fill_cost = 2;
+    bool super_fill = true, only_quarters = false;
+    int dilate = -1;
+    uint32_t grid = 0;                       // workgroups of the captured launch
+    uint32_t dev_drop_tenths = 0;            // dev
+    uint32_t dp_floor = 64;
+    uint32_t trim_rounds = 0;
+    double t_us[6] = {};                     // dev: wall-clock stamps of the job's stages
+    uint32_t prio_tenths[3] = {3, 6, 10};
+    std::string error;                       // worker -> caller
+};
+
+// One frame in flight: everything a launch writes or rewrites in stream order, and the work lists and cost feedback that
+// schedule its launches.  A context has one (slot 0) or, with VOLYM_OPT_FRAMES_IN_FLIGHT = 2, two; the scene they march is
+// the context's (raymarch.hip "frames in flight").
+struct FrameSlot {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     hipStream_t copy_stream = nullptr;      // cost read-backs and work-list uploads of the feedback thread
-    uint32_t W = 0, H = 0, tiles_x = 0, tiles_y = 0, n_tiles = 0;
-    uint32_t rank = 0, world = 1, n_local = 0, shard_tiles = 0;
-
-    uint8_t* d_vol = nullptr;
-    uint8_t* d_imp = nullptr;
-    uint32_t nx = 0, ny = 0, nz = 0;
-    uint32_t inx = 0, iny = 0, inz = 0;
-    int imp_box_lo[3] = {1, 1, 1}, imp_box_hi[3] = {0, 0, 0};   // texel AABB of the importances >= 128 (lo > hi: none)
-    int filter = VOLYM_FILTER_NEAREST;
-    uint8_t lut[256 * 4] = {};
-    uint32_t tf_n = 0;
-    bool have_vol = false, have_imp = false, have_tf = false, have_frame = false;
 
     // per-(transfer function, step) tables: one device copy, refreshed in stream order from a ring of pinned stagings
     static constexpr int TABLE_RING = 8;
-    volym::FrameTables* d_tables = nullptr;
-    volym::FrameTables* h_tables[TABLE_RING] = {};
+    FrameTables* d_tables = nullptr;
+    FrameTables* h_tables[TABLE_RING] = {};
     hipEvent_t tables_ev[TABLE_RING] = {};
     int tables_slot = 0;
-    volym::FrameTables tables_now;           // what d_tables holds (or will, in stream order)
+    FrameTables tables_now;                  // what d_tables holds (or will, in stream order)
     bool tables_dirty = true;
     float tables_alpha_y = -1.0f;
 
-    uint8_t* d_mc = nullptr;                 // per-macro-cell density maxima
     uint8_t* d_df = nullptr;                 // packed 4-bit distance field for (d_mc, thr_byte)
-    std::vector<uint8_t> h_mc;               // host copy of d_mc
-    int aabb_tab[257][6];                    // occupied-cell AABB per threshold byte {x0,y0,z0,x1,y1,z1}; x1 < x0: none
-    uint32_t mc_n = 32;
     uint32_t df_thr_byte = 0xffffffffu;
     uint32_t thr_byte_cull = 256;
+    bool hull_dirty = true;
     uint32_t* d_tile_mask = nullptr;         // one bit per 8x8 pixel tile: some occupied macro cell projects onto it (per view); two
                                              // buffers of tile_mask_words: the one in use and the one being kept zeroed for the next view
     int mask_cur = 0;
-    uint32_t tile_mask_words = 0;            // 0: the frame has more tiles than the mask kernel holds in LDS -- no mask
-    bool tile_mask = true;                   // dev switch
     bool mask_wanted = false;                // compute_culling: this view gets a mask
     bool mask_pending = false;               // ... and has not got it yet
-    bool mask_eager = false;                 // dev
     uint32_t view_launches = 0;              // launches since the view last changed
     float mask_clip[16] = {};                // world -> clip of the view (f32 copy for the mask kernel)
     float mask_margin = 0.0f;
@@ -81,8 +90,6 @@ struct volym_ctx {
 
     uint32_t* d_shard_own = nullptr;
     uint32_t* d_frame_own = nullptr;
-    uint32_t* d_shard = nullptr;
-    uint32_t* d_frame = nullptr;
     float4* d_f32 = nullptr;
     uint32_t* d_blit = nullptr;              // volym_blit target when the caller passes none
     size_t blit_bytes = 0;
@@ -91,7 +98,7 @@ struct volym_ctx {
     uint32_t* d_pack_counters = nullptr;
     uint32_t pack_parity = 0;
     size_t gather_tmp_bytes = 0;
-    volym::Counters* d_counters = nullptr;
+    Counters* d_counters = nullptr;
     uint4* d_trace = nullptr;
 
     // ---- work lists + cost feedback (variant 2) ----
@@ -101,12 +108,10 @@ struct volym_ctx {
     uint16_t* h_cost_pinned = nullptr;          // wave and the start time of every workgroup of that launch (raymarch_pq.h)
     size_t list_capacity = 0;                   // entries each of the above can hold
     int cur = 0;
-    volym::WorkList lists[2];
-    std::vector<uint32_t> geometric;            // centre-first list of this shard (rebuilt by the setup calls)
+    WorkList lists[2];
     std::vector<uint16_t> item_cost;            // last measured / estimated cost per 8x8 item (4 * n_local), carried across views
     std::vector<uint8_t> item_is_dp;            // hysteresis of the depth-parallel split
     std::atomic<uint64_t> view_serial{1};       // bumped by every volym_update that changes the uniforms (read by the feedback thread)
-    bool lists_ready = false;
     // ---- variant 3 (ray pool): {-, -, error bits of the frames so far}
     uint32_t* d_pool_sync = nullptr;
     bool pool_launched = false;
@@ -119,26 +124,41 @@ struct volym_ctx {
     std::condition_variable fb_cv;
     std::atomic<int> fb_state{FB_IDLE};
     hipEvent_t ev_march = nullptr, ev_cost = nullptr, ev_list = nullptr;
-    struct FbJob {                               // written by the caller before FB_CAPTURED, by the worker before FB_READY
-        int list = 0;                            // which of lists[] the captured launch ran
-        uint32_t n_entries = 0;
-        uint64_t view_serial = 0;
-        bool captured_has_dp = false;
-        bool continuous = false;
-        bool plain = false;                      // table mode, no importance mode (the common instantiation)
-        uint32_t max_grid = 0, waves = 16;
-        int dp_min_cost = -1;
-        uint32_t dp_share_pct = 60, fill_cost = 2;
-        bool super_fill = true, only_quarters = false;
-        int dilate = -1;
-        uint32_t grid = 0;                       // workgroups of the captured launch
-        uint32_t dev_drop_tenths = 0;            // dev
-        uint32_t dp_floor = 64;
-        uint32_t trim_rounds = 0;
-        double t_us[6] = {};                     // dev: wall-clock stamps of the job's stages
-        uint32_t prio_tenths[3] = {3, 6, 10};
-        std::string error;                       // worker -> caller
-    } fb_job;
+    FbJob fb_job;
+
+    FrameParams fp;
+};
+
+}  // namespace volym
+
+// The scene and the settings: what the set-up calls write and every frame slot only reads.
+struct volym_ctx {
+    int device = 0;
+    uint32_t W = 0, H = 0, tiles_x = 0, tiles_y = 0, n_tiles = 0;
+    uint32_t rank = 0, world = 1, n_local = 0, shard_tiles = 0;
+    std::vector<uint32_t> geometric;            // centre-first list of this shard (rebuilt by the setup calls)
+
+    uint8_t* d_vol = nullptr;
+    uint8_t* d_imp = nullptr;
+    uint32_t nx = 0, ny = 0, nz = 0;
+    uint32_t inx = 0, iny = 0, inz = 0;
+    int imp_box_lo[3] = {1, 1, 1}, imp_box_hi[3] = {0, 0, 0};   // texel AABB of the importances >= 128 (lo > hi: none)
+    int filter = VOLYM_FILTER_NEAREST;
+    uint8_t lut[256 * 4] = {};
+    uint32_t tf_n = 0;
+    bool have_vol = false, have_imp = false, have_tf = false, have_frame = false;
+
+    uint8_t* d_mc = nullptr;                 // per-macro-cell density maxima
+    std::vector<uint8_t> h_mc;               // host copy of d_mc
+    int aabb_tab[257][6];                    // occupied-cell AABB per threshold byte {x0,y0,z0,x1,y1,z1}; x1 < x0: none
+    uint32_t mc_n = 32;
+    uint32_t tile_mask_words = 0;            // 0: the frame has more tiles than the mask kernel holds in LDS -- no mask
+    bool tile_mask = true;                   // dev switch
+    bool mask_eager = false;                 // dev
+
+    // bound by volym_bind_output (NULL: each slot renders into its own)
+    uint32_t* bound_shard = nullptr;
+    uint32_t* bound_frame = nullptr;
 
     static constexpr uint32_t THROTTLE_RING = 9;          // one more than the deepest wait volym_throttle accepts (8)
     hipEvent_t throttle_ev[THROTTLE_RING] = {};
@@ -162,33 +182,33 @@ struct volym_ctx {
     int dp_min_cost = -1;
     int n_cus = 256;
     uint32_t wgs_per_cu = 1;
-    int kspec = 4;
     bool culling = true;
-    // VOLYM_OPT_FRAMES_IN_FLIGHT = 2: a second context on the same device (own stream, frame buffer, lists and feedback) that renders
-    // every other frame, so that a frame's workgroups take the CUs the previous frame's tail leaves idle (raymarch.hip "frames in flight")
-    volym_ctx* twin = nullptr;
-    volym_ctx* last = nullptr;                  // the context the latest volym_compute_pass went to (this one or the twin)
-    volym_ctx* last_blit = nullptr;
-    uint32_t flight_parity = 0;
-    std::vector<std::pair<int, int>> option_log;    // options set so far: replayed into a twin created later
     bool setup_ieee = false;                    // VOLYM_OPT_SETUP_IEEE: make_ray with plain divisions (FrameParams::setup_lo = +inf)
     bool straight_jobs = false;                 // dev switch (option 121): CJ = 2 instantiation for the straight look-ahead
     bool lds_bricks = false;        // dev option 122: LDS-staged bricks in the common instantiation (bricked layout)
-    bool hull_dirty = true;
     volym_camera_uniforms cam_copy;
     volym_parameter_uniforms par_copy;
-
-    volym::FrameParams fp;
     int kernel_variant = 2;
     bool write_f32 = false;
     uint32_t xcd_bands = 0;
+
+    // slot 0 always exists; slot 1 while VOLYM_OPT_FRAMES_IN_FLIGHT = 2, and then volym_compute_pass alternates between them
+    std::unique_ptr<volym::FrameSlot> slots[2];
+    int last = 0;                               // the slot the latest volym_compute_pass went to
+    int last_blit = 0;                          // ... and the latest volym_blit
+    uint32_t flight_parity = 0;
     std::string err;
+
+    int n_slots() const { return slots[1] ? 2 : 1; }
+    volym::FrameSlot& slot0() { return *slots[0]; }
+    uint32_t* frame_buf(const volym::FrameSlot& s) const { return bound_frame ? bound_frame : s.d_frame_own; }
+    uint32_t* shard_buf(const volym::FrameSlot& s) const { return bound_shard ? bound_shard : s.d_shard_own; }
 };
 
 namespace volym {
 
 int ctx_fail(volym_ctx* c, int code, const std::string& msg);
-// one plain ray-march launch on the context's stream (what volym_compute_pass enqueues); used by the multi-GPU loop
+// one plain ray-march launch of slot 0 on its stream (what volym_compute_pass enqueues); used by the multi-GPU loop
 int ctx_launch_march(volym_ctx* c);
 
 }  // namespace volym

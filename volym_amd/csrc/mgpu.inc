@@ -173,7 +173,7 @@ int mg_enqueue_frame(volym_mgpu* m, uint64_t i, bool capturing, bool fresh_cycle
     }
     for (MgLocal& L : m->loc) {
         MG_HIP(m, hipSetDevice(L.device));
-        hipStream_t s_march = L.ctx->stream;
+        hipStream_t s_march = L.ctx->slot0().stream;
         if (L.free_pending[b] && !(capturing && fresh_cycle)) MG_HIP(m, hipStreamWaitEvent(s_march, L.ev_free[b], 0));
         MG_CTX(m, L, ctx_launch_march(L.ctx));
         MG_CTX(m, L, volym_pack_shard(L.ctx, L.packed[b], msg));
@@ -212,7 +212,7 @@ int mg_enqueue_frame(volym_mgpu* m, uint64_t i, bool capturing, bool fresh_cycle
     if (R) {
         MG_HIP(m, hipSetDevice(R->device));
         volym_ctx* c = R->ctx;
-        hipLaunchKernelGGL(volym_assemble_packed_kernel, dim3(c->n_tiles), dim3(256), 0, R->s_comm, m->gathered[b], msg, c->d_frame, c->W, c->H,
+        hipLaunchKernelGGL(volym_assemble_packed_kernel, dim3(c->n_tiles), dim3(256), 0, R->s_comm, m->gathered[b], msg, c->frame_buf(c->slot0()), c->W, c->H,
                            c->tiles_x, c->n_tiles, c->world, c->shard_tiles);
         MG_HIP(m, hipGetLastError());
     }
@@ -234,7 +234,7 @@ int mg_drain(volym_mgpu* m)
 {
     for (MgLocal& L : m->loc) {
         MG_HIP(m, hipSetDevice(L.device));
-        MG_HIP(m, hipStreamSynchronize(L.ctx->stream));
+        MG_HIP(m, hipStreamSynchronize(L.ctx->slot0().stream));
         MG_HIP(m, hipStreamSynchronize(L.s_comm));
     }
     return VOLYM_OK;
@@ -382,7 +382,7 @@ int volym_mgpu_set_transfer_function(volym_mgpu* m, const uint8_t* rgba8, uint32
 int volym_mgpu_set_option(volym_mgpu* m, int key, int value)
 {
     if (!m) return VOLYM_E_INVALID;
-    // the loop marches a rank's frames on one stream and packs from one shard buffer (DESIGN.md 12.5a): no frame twins here yet
+    // the loop marches a rank's frames on one stream and packs from one shard buffer (DESIGN.md 12.5a): one frame slot per rank here
     if (key == VOLYM_OPT_FRAMES_IN_FLIGHT && value != 1) return mg_fail(m, VOLYM_E_STATE, "volym_mgpu_set_option: VOLYM_OPT_FRAMES_IN_FLIGHT > 1 is not available in the multi-GPU loop");
     for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_option(L.ctx, key, value));
     return VOLYM_OK;
@@ -428,7 +428,7 @@ int volym_mgpu_prepare(volym_mgpu* m, uint32_t slack_percent)
         const size_t cap = volym_packed_shard_bytes(L.ctx, 1u << 30);
         if (rc == VOLYM_OK && hipMalloc(&probe, cap) != hipSuccess) { rc = VOLYM_E_NOMEM; probe_err = "volym_mgpu_prepare: hipMalloc(probe)"; }
         // the overflow flag of an earlier preparation must not outlive it (the slots are sized anew below)
-        if (rc == VOLYM_OK && hipMemsetAsync(L.ctx->d_pack_counters + 2, 0, sizeof(uint32_t), L.ctx->stream) != hipSuccess) rc = VOLYM_E_HIP;
+        if (rc == VOLYM_OK && hipMemsetAsync(L.ctx->slot0().d_pack_counters + 2, 0, sizeof(uint32_t), L.ctx->slot0().stream) != hipSuccess) rc = VOLYM_E_HIP;
         if (rc == VOLYM_OK) rc = volym_compute_pass(L.ctx);
         if (rc == VOLYM_OK) rc = volym_pack_shard(L.ctx, probe, cap);
         uint32_t used = 0, over = 0;
@@ -489,10 +489,10 @@ int volym_mgpu_run(volym_mgpu* m, uint32_t frames, int use_graph, volym_mgpu_tim
     if (use_graph && graphable && frames >= 2u * MG_NBUF) {
         MgLocal& L0 = m->loc[0];
         MG_HIP(m, hipSetDevice(L0.device));
-        hipStream_t s0 = L0.ctx->stream;
-        const uint64_t view = L0.ctx->view_serial.load(std::memory_order_relaxed);
+        hipStream_t s0 = L0.ctx->slot0().stream;
+        const uint64_t view = L0.ctx->slot0().view_serial.load(std::memory_order_relaxed);
         std::vector<hipStream_t> others;                 // every stream but the origin
-        for (MgLocal& L : m->loc) { if (&L != &L0) others.push_back(L.ctx->stream); if (m->world > 1) others.push_back(L.s_comm); }
+        for (MgLocal& L : m->loc) { if (&L != &L0) others.push_back(L.ctx->slot0().stream); if (m->world > 1) others.push_back(L.s_comm); }
         if (!m->graph_exec || m->graph_view != view) {
             if (m->graph_exec) { (void)hipGraphExecDestroy(m->graph_exec); m->graph_exec = nullptr; }
             if (m->graph) { (void)hipGraphDestroy(m->graph); m->graph = nullptr; }
@@ -605,12 +605,12 @@ int volym_mgpu_profile(volym_mgpu* m, uint32_t frames, volym_mgpu_split* split)
             MG_HIP(m, hipSetDevice(L.device));
             hipEvent_t e[3];
             for (auto& x : e) MG_HIP(m, hipEventCreate(&x));
-            MG_HIP(m, hipEventRecord(e[0], L.ctx->stream));
+            MG_HIP(m, hipEventRecord(e[0], L.ctx->slot0().stream));
             MG_CTX(m, L, ctx_launch_march(L.ctx));
-            MG_HIP(m, hipEventRecord(e[1], L.ctx->stream));
+            MG_HIP(m, hipEventRecord(e[1], L.ctx->slot0().stream));
             if (m->world > 1) MG_CTX(m, L, volym_pack_shard(L.ctx, L.packed[0], msg));
-            MG_HIP(m, hipEventRecord(e[2], L.ctx->stream));
-            MG_HIP(m, hipStreamSynchronize(L.ctx->stream));
+            MG_HIP(m, hipEventRecord(e[2], L.ctx->slot0().stream));
+            MG_HIP(m, hipStreamSynchronize(L.ctx->slot0().stream));
             float a = 0, b2 = 0;
             (void)hipEventElapsedTime(&a, e[0], e[1]);
             (void)hipEventElapsedTime(&b2, e[1], e[2]);
@@ -643,7 +643,7 @@ int volym_mgpu_profile(volym_mgpu* m, uint32_t frames, volym_mgpu_split* split)
             MG_HIP(m, hipEventCreate(&e0)); MG_HIP(m, hipEventCreate(&e1));
             volym_ctx* c = R->ctx;
             MG_HIP(m, hipEventRecord(e0, R->s_comm));
-            hipLaunchKernelGGL(volym_assemble_packed_kernel, dim3(c->n_tiles), dim3(256), 0, R->s_comm, m->gathered[0], msg, c->d_frame, c->W, c->H,
+            hipLaunchKernelGGL(volym_assemble_packed_kernel, dim3(c->n_tiles), dim3(256), 0, R->s_comm, m->gathered[0], msg, c->frame_buf(c->slot0()), c->W, c->H,
                                c->tiles_x, c->n_tiles, c->world, c->shard_tiles);
             MG_HIP(m, hipEventRecord(e1, R->s_comm));
             MG_HIP(m, hipStreamSynchronize(R->s_comm));
@@ -668,7 +668,7 @@ int volym_mgpu_read_rgba8(volym_mgpu* m, uint8_t* out)
     if (rc != VOLYM_OK) return rc;
     MgLocal& R = m->loc[m->root];
     MG_HIP(m, hipSetDevice(R.device));
-    MG_HIP(m, hipMemcpy(out, R.ctx->d_frame, static_cast<size_t>(m->W) * m->H * 4, hipMemcpyDeviceToHost));
+    MG_HIP(m, hipMemcpy(out, R.ctx->frame_buf(R.ctx->slot0()), static_cast<size_t>(m->W) * m->H * 4, hipMemcpyDeviceToHost));
     return VOLYM_OK;
 }
 

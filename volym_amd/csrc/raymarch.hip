@@ -154,20 +154,20 @@ bool hull_edges(const P2* pts, int n, float out[8][4])
 }
 }  // namespace
 
-static void compute_culling(volym_ctx* c)
+static void compute_culling(const volym_ctx* c, FrameSlot& s)
 {
-    FrameParams& fp = c->fp;
+    FrameParams& fp = s.fp;
     fp.cull = 0;
     std::memset(fp.hull, 0, sizeof fp.hull);
     // variant 3's lattice rectangle: the whole frame unless the hull of the occupied cells says less (below)
     fp.rect[0] = 0; fp.rect[1] = 0;
     fp.rect[2] = (c->W + PL_SBW - 1u) / PL_SBW * PL_SBW; fp.rect[3] = (c->H + PL_SBH - 1u) / PL_SBH * PL_SBH;
-    c->hull_dirty = false;
-    c->mask_wanted = false;
+    s.hull_dirty = false;
+    s.mask_wanted = false;
     if (!c->culling) return;
     // AABB of the occupied cells (per threshold byte, computed when the volume was set), grown by what a sample may
     // reach beyond its own position
-    const int* h_aabb = c->aabb_tab[std::min(c->thr_byte_cull, 256u)];
+    const int* h_aabb = c->aabb_tab[std::min(s.thr_byte_cull, 256u)];
     const bool none = h_aabb[3] < h_aabb[0];
     if (none) fp.cull |= CULL_NOTHING_DENSE;
     double lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
@@ -223,9 +223,9 @@ static void compute_culling(volym_ctx* c)
     // the per-tile mask of the occupied cells' projections (volym_tile_mask_kernel): its cells lie inside the AABB whose
     // corners were all found in front of the eye, so their corners are too
     fp.mask_t8x = c->tiles_x * 2u;
-    c->mask_margin = static_cast<float>(margin);
-    for (int i = 0; i < 16; ++i) c->mask_clip[i] = static_cast<float>(M[i]);
-    c->mask_wanted = (fp.cull & CULL_OBJ_HULL) != 0u && c->tile_mask && c->tile_mask_words != 0u;
+    s.mask_margin = static_cast<float>(margin);
+    for (int i = 0; i < 16; ++i) s.mask_clip[i] = static_cast<float>(M[i]);
+    s.mask_wanted = (fp.cull & CULL_OBJ_HULL) != 0u && c->tile_mask && c->tile_mask_words != 0u;
 }
 // ================================================================================================================
 // Work lists and their cost feedback (variant 2).
@@ -271,7 +271,7 @@ static void build_geometric(volym_ctx* c)
 }
 
 // Deal `item_cost` into a list (feedback thread; also the caller's thread inside blocking set-up calls).
-static void deal_list(const volym_ctx* c, const volym_ctx::FbJob& job, const std::vector<uint16_t>& measured_cost, std::vector<uint8_t>& item_is_dp,
+static void deal_list(const volym_ctx* c, const FrameSlot& s, const FbJob& job, const std::vector<uint16_t>& measured_cost, std::vector<uint8_t>& item_is_dp,
                       const std::vector<uint32_t>& geometric, uint32_t n_local, WorkList& out)
 {
     const uint32_t waves = job.waves;
@@ -283,7 +283,7 @@ static void deal_list(const volym_ctx* c, const volym_ctx::FbJob& job, const std
     // keep split tiles split (hysteresis).  A view that stands still gets exactly what its own costs say -- but only costs
     // MEASURED on whole 8x8 entries say it well (a split tile reports an estimate).  So when the captured list held split
     // tiles, the first deal for a standing view is a measuring list without any split, and the deal after it is final.
-    const bool moving = c->view_serial.load(std::memory_order_relaxed) != job.view_serial;
+    const bool moving = s.view_serial.load(std::memory_order_relaxed) != job.view_serial;
     const bool measuring = !moving && job.captured_has_dp && job.dp_min_cost < 0;
     const int dilate = job.dilate >= 0 ? job.dilate : (moving ? 1 : 0);
     if (dilate > 0) {
@@ -418,7 +418,7 @@ static void deal_list(const volym_ctx* c, const volym_ctx::FbJob& job, const std
 // builds the gain is 0.1 us (33.17 -> 33.07), and one run in six came out at 33.85: a list trimmed from a capture that caught a
 // hiccup is final, and wrong, for as long as the view stands.  A deterministic list is worth more than 0.3 %: OFF by default
 // (FbJob::trim_rounds = 0; VOLYM_OPT_REBALANCE_ROUNDS turns it on).
-static bool trim_list(const volym_ctx* c, const volym_ctx::FbJob& job, const WorkList& in, const uint32_t* times, WorkList& out)
+static bool trim_list(const FrameSlot& s, const FbJob& job, const WorkList& in, const uint32_t* times, WorkList& out)
 {
     const uint32_t G = in.grid, waves = job.waves;
     if (G == 0 || G != job.grid || in.entries.size() % G != 0 || in.shares.size() != in.entries.size()) return false;
@@ -491,7 +491,7 @@ static bool trim_list(const volym_ctx* c, const volym_ctx::FbJob& job, const Wor
         std::stable_sort(wg[b].begin(), wg[b].end(), [](const Ent& a, const Ent& b2) { return a.w > b2.w; });
         rows_out = std::max(rows_out, wg[b].size());
     }
-    if (static_cast<size_t>(G) * rows_out > c->list_capacity) return false;
+    if (static_cast<size_t>(G) * rows_out > s.list_capacity) return false;
     out.entries.assign(static_cast<size_t>(G) * rows_out, PQ_NO_ITEM);
     out.shares.assign(static_cast<size_t>(G) * rows_out, 0);
     for (uint32_t b = 0; b < G; ++b)
@@ -550,45 +550,46 @@ static void costs_to_items(const WorkList& list, const uint16_t* cost, uint32_t 
         if (q_seen[i]) item_cost[i] = static_cast<uint16_t>(std::min(65535u, 5u + q_max[i]));
 }
 
-static void feedback_thread(volym_ctx* c)
+static void feedback_thread(const volym_ctx* c, FrameSlot* sp)
 {
+    FrameSlot& s = *sp;
     (void)hipSetDevice(c->device);
     for (;;) {
         {
-            std::unique_lock<std::mutex> lk(c->fb_mu);
-            c->fb_cv.wait(lk, [&] { const int s = c->fb_state.load(std::memory_order_acquire); return s == volym_ctx::FB_CAPTURED || s == volym_ctx::FB_QUIT; });
+            std::unique_lock<std::mutex> lk(s.fb_mu);
+            s.fb_cv.wait(lk, [&] { const int st = s.fb_state.load(std::memory_order_acquire); return st == FrameSlot::FB_CAPTURED || st == FrameSlot::FB_QUIT; });
         }
-        if (c->fb_state.load(std::memory_order_acquire) == volym_ctx::FB_QUIT) return;
-        volym_ctx::FbJob& job = c->fb_job;
+        if (s.fb_state.load(std::memory_order_acquire) == FrameSlot::FB_QUIT) return;
+        FbJob& job = s.fb_job;
         job.error.clear();
         auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         job.t_us[1] = now_us();
-        hipError_t e = hipEventSynchronize(c->ev_cost);            // the captured launch and its cost copy are done
+        hipError_t e = hipEventSynchronize(s.ev_cost);            // the captured launch and its cost copy are done
         job.t_us[2] = now_us();
         const int next = job.list ^ 1;
         if (e == hipSuccess) {
             // A list dealt for this very view from whole-entry costs is not dealt again (its split tiles report estimates): it is
             // re-balanced from the workgroups' measured times, job.trim_rounds times.
-            const WorkList& ran = c->lists[job.list];
-            const bool same_view = c->view_serial.load(std::memory_order_relaxed) == job.view_serial && ran.view_serial == job.view_serial;
+            const WorkList& ran = s.lists[job.list];
+            const bool same_view = s.view_serial.load(std::memory_order_relaxed) == job.view_serial && ran.view_serial == job.view_serial;
             bool trimmed = false;
             if (same_view && ran.trimmable && ran.trim_round < job.trim_rounds)
-                trimmed = trim_list(c, job, ran, reinterpret_cast<const uint32_t*>(c->h_cost_pinned + ((job.n_entries + 1u) & ~1u)), c->lists[next]);
+                trimmed = trim_list(s, job, ran, reinterpret_cast<const uint32_t*>(s.h_cost_pinned + ((job.n_entries + 1u) & ~1u)), s.lists[next]);
             job.t_us[3] = now_us();
             if (!trimmed) {
-                costs_to_items(ran, c->h_cost_pinned, job.n_entries, c->item_cost);
+                costs_to_items(ran, s.h_cost_pinned, job.n_entries, s.item_cost);
                 job.t_us[3] = now_us();
-                deal_list(c, job, c->item_cost, c->item_is_dp, c->geometric, c->n_local, c->lists[next]);
+                deal_list(c, s, job, s.item_cost, s.item_is_dp, c->geometric, c->n_local, s.lists[next]);
             }
             job.t_us[4] = now_us();
-            if (c->lists[next].entries.size() > c->list_capacity) {
+            if (s.lists[next].entries.size() > s.list_capacity) {
                 job.error = "work list larger than its buffers";    // cannot happen: capacity is the worst case
             } else {
-                list_to_device_form(c, c->lists[next].entries, c->h_list_pinned);
+                list_to_device_form(c, s.lists[next].entries, s.h_list_pinned);
                 // every launch that read d_list[next] finished before the captured launch did (same stream, in order)
-                e = hipMemcpyAsync(c->d_list[next], c->h_list_pinned, c->lists[next].entries.size() * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, c->copy_stream);
-                if (e == hipSuccess) e = hipEventRecord(c->ev_list, c->copy_stream);
-                if (e == hipSuccess) e = hipEventSynchronize(c->ev_list);
+                e = hipMemcpyAsync(s.d_list[next], s.h_list_pinned, s.lists[next].entries.size() * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, s.copy_stream);
+                if (e == hipSuccess) e = hipEventRecord(s.ev_list, s.copy_stream);
+                if (e == hipSuccess) e = hipEventSynchronize(s.ev_list);
             }
         }
         if (e != hipSuccess) job.error = std::string("cost feedback: ") + hipGetErrorString(e);
@@ -596,93 +597,115 @@ static void feedback_thread(volym_ctx* c)
         {
             // under the mutex: a caller in feedback_quiesce that has just found the state CAPTURED must be inside wait() before this
             // store and its notification happen, or it would sleep through them
-            std::lock_guard<std::mutex> lk(c->fb_mu);
-            c->fb_state.store(volym_ctx::FB_READY, std::memory_order_release);
+            std::lock_guard<std::mutex> lk(s.fb_mu);
+            s.fb_state.store(FrameSlot::FB_READY, std::memory_order_release);
         }
-        c->fb_cv.notify_all();
+        s.fb_cv.notify_all();
     }
 }
 
 // caller side: adopt a finished list (never blocks)
-static void feedback_poll(volym_ctx* c)
+static void feedback_poll(FrameSlot& s)
 {
-    if (c->fb_state.load(std::memory_order_acquire) != volym_ctx::FB_READY) return;
-    if (c->fb_job.error.empty()) c->cur = c->fb_job.list ^ 1;
-    c->fb_state.store(volym_ctx::FB_IDLE, std::memory_order_release);
+    if (s.fb_state.load(std::memory_order_acquire) != FrameSlot::FB_READY) return;
+    if (s.fb_job.error.empty()) s.cur = s.fb_job.list ^ 1;
+    s.fb_state.store(FrameSlot::FB_IDLE, std::memory_order_release);
 }
 
 // caller side, blocking (set-up calls, volym_settle): wait for a job in flight and adopt its list
-static void feedback_quiesce(volym_ctx* c)
+static void feedback_quiesce(FrameSlot& s)
 {
-    if (c->fb_state.load(std::memory_order_acquire) == volym_ctx::FB_CAPTURED) {
-        std::unique_lock<std::mutex> lk(c->fb_mu);
-        c->fb_cv.wait(lk, [&] { return c->fb_state.load(std::memory_order_acquire) != volym_ctx::FB_CAPTURED; });
+    if (s.fb_state.load(std::memory_order_acquire) == FrameSlot::FB_CAPTURED) {
+        std::unique_lock<std::mutex> lk(s.fb_mu);
+        s.fb_cv.wait(lk, [&] { return s.fb_state.load(std::memory_order_acquire) != FrameSlot::FB_CAPTURED; });
     }
-    feedback_poll(c);
+    feedback_poll(s);
 }
 
-// (Re)build the lists of this shard: geometric order, no costs.  Blocking set-up path (create, set_shard, options).
-static int rebuild_lists(volym_ctx* c)
+// Before a set-up call rewrites or frees what the slots share (the volume, the importances, the macro cells, the shard and its
+// geometric list): the feedback of EVERY slot at rest, and EVERY slot's stream idle -- with two frames in flight, the frames
+// of either slot may still read it.
+static int quiesce_slots(volym_ctx* c)
 {
-    feedback_quiesce(c);
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    build_geometric(c);
-    // worst case: every 8x8 item split into four quarters, plus padding to a multiple of the grid
-    const size_t need = static_cast<size_t>(c->n_local) * 16u + 2u * static_cast<size_t>(c->n_cus) * 8u + 64u;
-    if (need > c->list_capacity) {
-        for (int i = 0; i < 2; ++i) { if (c->d_list[i]) (void)hipFree(c->d_list[i]); c->d_list[i] = nullptr; }
-        if (c->d_cost) (void)hipFree(c->d_cost);
-        if (c->h_list_pinned) (void)hipHostFree(c->h_list_pinned);
-        if (c->h_cost_pinned) (void)hipHostFree(c->h_cost_pinned);
-        c->d_cost = nullptr; c->h_list_pinned = nullptr; c->h_cost_pinned = nullptr; c->list_capacity = 0;
-        hipError_t e = hipMalloc(&c->d_list[0], need * 2u * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&c->d_list[1], need * 2u * sizeof(uint32_t));
-        // + the times of the captured launch: a u32 per wave and per workgroup (raymarch_pq.h wg_time)
-        const size_t cost_bytes = (need + 2u) * sizeof(uint16_t) + (static_cast<size_t>(c->n_cus) * 8u * (PQ_WAVES + 1u) + 64u) * sizeof(uint32_t);
-        if (e == hipSuccess) e = hipMalloc(&c->d_cost, cost_bytes);
-        if (e == hipSuccess) e = hipHostMalloc(&c->h_list_pinned, need * 2u * sizeof(uint32_t), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipHostMalloc(&c->h_cost_pinned, cost_bytes, hipHostMallocDefault);
-        if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("work lists: ") + hipGetErrorString(e));
-        c->list_capacity = need;
+    for (int i = 0; i < c->n_slots(); ++i) {
+        feedback_quiesce(*c->slots[i]);
+        HIPCHK(c, hipStreamSynchronize(c->slots[i]->stream));
     }
-    c->item_cost.assign(static_cast<size_t>(c->n_local) * 4, 0);
-    c->item_is_dp.assign(static_cast<size_t>(c->n_local) * 4, 0);
-    c->cur = 0;
-    c->lists[0] = WorkList();                 // (no split entries, not final, dealt for no view)
-    c->lists[0].entries = c->geometric;
-    c->lists[1] = WorkList();
-    if (!c->geometric.empty()) {
-        list_to_device_form(c, c->geometric, c->h_list_pinned);
-        HIPCHK(c, hipMemcpy(c->d_list[0], c->h_list_pinned, c->geometric.size() * 2u * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    c->lists_ready = true;
     return VOLYM_OK;
 }
 
-// costs no longer describe the scene (new volume, transfer function, threshold grid...): back to the geometric order
-static int forget_costs(volym_ctx* c)
+// The slot's lists in geometric order, no costs (the context's geometric list is current; the slot is at rest).
+static int reset_slot_lists(volym_ctx* c, FrameSlot& s)
 {
-    if (!c->lists_ready) return VOLYM_OK;
-    return rebuild_lists(c);
+    // worst case: every 8x8 item split into four quarters, plus padding to a multiple of the grid
+    const size_t need = static_cast<size_t>(c->n_local) * 16u + 2u * static_cast<size_t>(c->n_cus) * 8u + 64u;
+    if (need > s.list_capacity) {
+        for (int i = 0; i < 2; ++i) { if (s.d_list[i]) (void)hipFree(s.d_list[i]); s.d_list[i] = nullptr; }
+        if (s.d_cost) (void)hipFree(s.d_cost);
+        if (s.h_list_pinned) (void)hipHostFree(s.h_list_pinned);
+        if (s.h_cost_pinned) (void)hipHostFree(s.h_cost_pinned);
+        s.d_cost = nullptr; s.h_list_pinned = nullptr; s.h_cost_pinned = nullptr; s.list_capacity = 0;
+        hipError_t e = hipMalloc(&s.d_list[0], need * 2u * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&s.d_list[1], need * 2u * sizeof(uint32_t));
+        // + the times of the captured launch: a u32 per wave and per workgroup (raymarch_pq.h wg_time)
+        const size_t cost_bytes = (need + 2u) * sizeof(uint16_t) + (static_cast<size_t>(c->n_cus) * 8u * (PQ_WAVES + 1u) + 64u) * sizeof(uint32_t);
+        if (e == hipSuccess) e = hipMalloc(&s.d_cost, cost_bytes);
+        if (e == hipSuccess) e = hipHostMalloc(&s.h_list_pinned, need * 2u * sizeof(uint32_t), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc(&s.h_cost_pinned, cost_bytes, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("work lists: ") + hipGetErrorString(e));
+        s.list_capacity = need;
+    }
+    s.item_cost.assign(static_cast<size_t>(c->n_local) * 4, 0);
+    s.item_is_dp.assign(static_cast<size_t>(c->n_local) * 4, 0);
+    s.cur = 0;
+    s.lists[0] = WorkList();                 // (no split entries, not final, dealt for no view)
+    s.lists[0].entries = c->geometric;
+    s.lists[1] = WorkList();
+    if (!c->geometric.empty()) {
+        list_to_device_form(c, c->geometric, s.h_list_pinned);
+        HIPCHK(c, hipMemcpy(s.d_list[0], s.h_list_pinned, c->geometric.size() * 2u * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    return VOLYM_OK;
+}
+
+// (Re)build the lists of this shard in every slot: geometric order, no costs.  Blocking set-up path (set_shard, options, uploads):
+// costs no longer describe the scene (new volume, transfer function, threshold grid...).
+static int rebuild_lists(volym_ctx* c)
+{
+    int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
+    build_geometric(c);
+    for (int i = 0; i < c->n_slots() && rc == VOLYM_OK; ++i) rc = reset_slot_lists(c, *c->slots[i]);
+    return rc;
 }
 
 // Macro-cell maxima, their host copy and the occupied-cell AABB for every threshold byte (set-up path: blocks).
 static int build_macro_cells(volym_ctx* c)
 {
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
+    // (every slot is idle: nothing reads the shared maxima or a slot's distance field).  Until every buffer below is rebuilt
+    // there is no volume to march: a failure leaves the context asking for volym_set_volume and volym_update again
+    const bool had_frame = c->have_frame;
+    c->have_vol = c->have_frame = false;
     if (c->d_mc) { HIPCHK(c, hipFree(c->d_mc)); c->d_mc = nullptr; }
-    if (c->d_df) { HIPCHK(c, hipFree(c->d_df)); c->d_df = nullptr; }
     const uint32_t n = c->mc_n, cells = n * n * n;
     hipError_t e = hipMalloc(&c->d_mc, cells);
-    if (e == hipSuccess) e = hipMalloc(&c->d_df, (cells / 2u + 15u) / 16u * 16u);
+    for (int i = 0; i < c->n_slots(); ++i) {
+        FrameSlot& s = *c->slots[i];
+        if (s.d_df) { HIPCHK(c, hipFree(s.d_df)); s.d_df = nullptr; }
+        if (e == hipSuccess) e = hipMalloc(&s.d_df, (cells / 2u + 15u) / 16u * 16u);
+        s.df_thr_byte = 0xffffffffu;
+        s.hull_dirty = true;
+    }
     if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(macro cells): ") + hipGetErrorString(e));
-    hipLaunchKernelGGL(volym_macrocell_kernel, dim3(cells), dim3(256), 0, c->stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n, c->bricked ? 1u : 0u);
+    const hipStream_t stream = c->slot0().stream;
+    hipLaunchKernelGGL(volym_macrocell_kernel, dim3(cells), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n, c->bricked ? 1u : 0u);
     HIPCHK(c, hipGetLastError());
     c->h_mc.resize(cells);
-    HIPCHK(c, hipMemcpyAsync(c->h_mc.data(), c->d_mc, cells, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_mc.data(), c->d_mc, cells, hipMemcpyDeviceToHost, stream));
+    HIPCHK(c, hipStreamSynchronize(stream));
     // AABB of the cells whose maximum reaches b, for every b: boxes of the cells with maximum exactly v, then a suffix union
     int box[257][6];
     for (int v = 0; v <= 256; ++v) { box[v][0] = box[v][1] = box[v][2] = 1 << 30; box[v][3] = box[v][4] = box[v][5] = -1; }
@@ -699,8 +722,8 @@ static int build_macro_cells(volym_ctx* c)
         for (int i = 0; i < 3; ++i) { run[i] = std::min(run[i], box[v][i]); run[3 + i] = std::max(run[3 + i], box[v][3 + i]); }
         for (int i = 0; i < 6; ++i) c->aabb_tab[v][i] = run[3] < 0 ? (i < 3 ? 0 : -1) : run[i];
     }
-    c->df_thr_byte = 0xffffffffu;
-    c->hull_dirty = true;
+    c->have_vol = true;
+    c->have_frame = had_frame;
     return VOLYM_OK;
 }
 
@@ -712,21 +735,94 @@ const char* volym_last_error(const volym_ctx* ctx) { return ctx ? ctx->err.c_str
 
 // ---- frames in flight ------------------------------------------------------------------------------------------------
 // A frame of the persistent kernel ends on its longest chains: for the last fifth of its time the CUs empty one by one
-// (DESIGN.md 5).  With VOLYM_OPT_FRAMES_IN_FLIGHT = 2 the context owns a twin -- a complete second context on the same device:
-// stream, frame buffer, volume copy, work lists, feedback thread -- and volym_compute_pass alternates between the two, so the
-// next frame's workgroups start on every CU the previous frame has left (measured: 31.9 -> 27.6 us per frame at 1920x1080).
-// Everything that describes the scene goes to both; the reading calls take the frame of the latest pass.
-#define TWIN_FORWARD(c, call)                                                                              \
-    do {                                                                                                   \
-        if ((c) && (c)->twin) {                                                                            \
-            const int rt_ = (call);                                                                        \
-            if (rt_ != VOLYM_OK) return fail((c), rt_, std::string("second frame context: ") + (c)->twin->err); \
-        }                                                                                                  \
-    } while (0)
-#define TWIN_REFUSE(c, what)                                                                               \
-    do {                                                                                                   \
-        if ((c) && (c)->twin) return fail((c), VOLYM_E_STATE, what ": not with VOLYM_OPT_FRAMES_IN_FLIGHT = 2"); \
-    } while (0)
+// (DESIGN.md 5).  With VOLYM_OPT_FRAMES_IN_FLIGHT = 2 the context has a second frame slot (context.hpp FrameSlot: stream,
+// frame buffer, tables, distance field, work lists, feedback thread) that marches the same scene, and volym_compute_pass
+// alternates between the two slots, so that the next frame's workgroups start on every CU the previous frame has left
+// (measured: 31.9 -> 27.6 us per frame at 1920x1080).  The set-up calls act once on the scene and then on every slot's own
+// state; the reading calls take the frame of the latest pass.
+
+// Streams, buffers, lists and feedback thread of a new slot (set-up path).  On failure the caller frees the slot.
+static int init_slot(volym_ctx* c, FrameSlot& s)
+{
+    auto bad = [&](hipError_t e, const char* what) {
+        return fail(c, e == hipErrorOutOfMemory ? VOLYM_E_NOMEM : VOLYM_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    };
+    // the caller's current device may be another one: a slot's streams and buffers belong on the context's device
+    HIPCHK(c, hipSetDevice(c->device));
+    std::memset(&s.fp, 0, sizeof s.fp);
+    std::memset(&s.tables_now, 0, sizeof s.tables_now);
+    hipError_t e;
+    if ((e = hipStreamCreateWithFlags(&s.own_stream, hipStreamNonBlocking)) != hipSuccess) return bad(e, "hipStreamCreate");
+    if ((e = hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking)) != hipSuccess) return bad(e, "hipStreamCreate");
+    s.stream = s.own_stream;
+    const size_t frame_bytes = static_cast<size_t>(c->W) * c->H * 4;
+    if ((e = hipMalloc(&s.d_frame_own, frame_bytes)) != hipSuccess) return bad(e, "hipMalloc(frame)");
+    if ((e = hipMalloc(&s.d_shard_own, static_cast<size_t>(c->n_tiles) * 1024)) != hipSuccess) return bad(e, "hipMalloc(shard)");
+    if ((e = hipMalloc(&s.d_tables, sizeof(FrameTables))) != hipSuccess) return bad(e, "hipMalloc(tables)");
+    if ((e = hipMalloc(&s.d_counters, sizeof(Counters))) != hipSuccess) return bad(e, "hipMalloc(counters)");
+    if ((e = hipMemset(s.d_frame_own, 0, frame_bytes)) != hipSuccess) return bad(e, "hipMemset(frame)");
+    if ((e = hipMalloc(&s.d_aabb, 6 * sizeof(int))) != hipSuccess) return bad(e, "hipMalloc(aabb)");
+    if (c->tile_mask_words && (e = hipMalloc(&s.d_tile_mask, 2u * c->tile_mask_words * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(tile mask)");
+    if (c->tile_mask_words && (e = hipMemset(s.d_tile_mask, 0, 2u * c->tile_mask_words * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMemset(tile mask)");
+    if ((e = hipMalloc(&s.d_pack_counters, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(pack counters)");
+    if ((e = hipMemset(s.d_pack_counters, 0, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMemset(pack counters)");
+    if ((e = hipMalloc(&s.d_pool_sync, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(pool sync)");
+    if ((e = hipMemset(s.d_pool_sync, 0, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMemset(pool sync)");
+    if ((e = hipMalloc(&s.d_pool_dbg, static_cast<size_t>(c->n_cus) * 8u * PL_WAVES * 24u * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(pool timeline)");
+    for (int i = 0; i < FrameSlot::TABLE_RING; ++i) {
+        if ((e = hipHostMalloc(reinterpret_cast<void**>(&s.h_tables[i]), sizeof(FrameTables), hipHostMallocDefault)) != hipSuccess) return bad(e, "hipHostMalloc(tables)");
+        if ((e = hipEventCreateWithFlags(&s.tables_ev[i], hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+    }
+    if ((e = hipEventCreateWithFlags(&s.ev_march, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+    if ((e = hipEventCreateWithFlags(&s.ev_cost, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+    if ((e = hipEventCreateWithFlags(&s.ev_list, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
+    if (c->write_f32 && (e = hipMalloc(&s.d_f32, static_cast<size_t>(c->W) * c->H * sizeof(float4))) != hipSuccess) return bad(e, "hipMalloc(f32 frame)");
+    const int rc = reset_slot_lists(c, s);
+    if (rc != VOLYM_OK) return rc;
+    try {
+        s.fb_thread = std::thread(feedback_thread, c, &s);
+    } catch (...) {
+        return fail(c, VOLYM_E_NOMEM, "cannot start the feedback thread");
+    }
+    return VOLYM_OK;
+}
+
+static void free_slot(FrameSlot& s)
+{
+    if (s.fb_thread.joinable()) {
+        feedback_quiesce(s);
+        {
+            std::lock_guard<std::mutex> lk(s.fb_mu);
+            s.fb_state.store(FrameSlot::FB_QUIT, std::memory_order_release);
+        }
+        s.fb_cv.notify_all();
+        s.fb_thread.join();
+    }
+    if (s.stream) (void)hipStreamSynchronize(s.stream);
+    if (s.copy_stream) (void)hipStreamSynchronize(s.copy_stream);
+    (void)hipFree(s.d_tables); (void)hipFree(s.d_df);
+    (void)hipFree(s.d_shard_own); (void)hipFree(s.d_frame_own); (void)hipFree(s.d_f32); (void)hipFree(s.d_blit);
+    (void)hipFree(s.d_gather_tmp); (void)hipFree(s.d_pack_counters); (void)hipFree(s.d_counters); (void)hipFree(s.d_aabb); (void)hipFree(s.d_tile_mask);
+    (void)hipFree(s.d_list[0]); (void)hipFree(s.d_list[1]); (void)hipFree(s.d_cost);
+    (void)hipFree(s.d_pool_sync); (void)hipFree(s.d_pool_dbg);
+    if (s.h_list_pinned) (void)hipHostFree(s.h_list_pinned);
+    if (s.h_cost_pinned) (void)hipHostFree(s.h_cost_pinned);
+    for (int i = 0; i < FrameSlot::TABLE_RING; ++i) {
+        if (s.h_tables[i]) (void)hipHostFree(s.h_tables[i]);
+        if (s.tables_ev[i]) (void)hipEventDestroy(s.tables_ev[i]);
+    }
+    if (s.ev_march) (void)hipEventDestroy(s.ev_march);
+    if (s.ev_cost) (void)hipEventDestroy(s.ev_cost);
+    if (s.ev_list) (void)hipEventDestroy(s.ev_list);
+    if (s.own_stream) (void)hipStreamDestroy(s.own_stream);
+    if (s.copy_stream) (void)hipStreamDestroy(s.copy_stream);
+}
+
+// the calls that address one stream or one shard buffer
+static int refuse_two_slots(volym_ctx* c, const char* what)
+{
+    return fail(c, VOLYM_E_STATE, std::string(what) + ": not with VOLYM_OPT_FRAMES_IN_FLIGHT = 2");
+}
 
 int volym_create(volym_ctx** out, uint32_t width, uint32_t height, int device_id)
 {
@@ -756,56 +852,15 @@ int volym_create(volym_ctx** out, uint32_t width, uint32_t height, int device_id
     c->tiles_y = (height + 15u) / 16u;
     c->n_tiles = c->tiles_x * c->tiles_y;
     recompute_shard(c);
-    std::memset(&c->fp, 0, sizeof c->fp);
-    std::memset(&c->tables_now, 0, sizeof c->tables_now);
     std::memset(c->aabb_tab, 0, sizeof c->aabb_tab);
+    const uint64_t tiles8 = static_cast<uint64_t>(c->tiles_x) * 2u * c->tiles_y * 2u;
+    const uint64_t words = (tiles8 + 31u) / 32u;
+    c->tile_mask_words = words <= VOLYM_TILE_MASK_MAX_WORDS ? static_cast<uint32_t>(words) : 0u;
+    build_geometric(c);
 
-    auto bail = [&](hipError_t e, const char* what) {
-        std::string m = std::string(what) + ": " + hipGetErrorString(e);
-        volym_destroy(c);
-        return fail(nullptr, e == hipErrorOutOfMemory ? VOLYM_E_NOMEM : VOLYM_E_HIP, m);
-    };
-    hipError_t e;
-    if ((e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    if ((e = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "hipStreamCreate");
-    c->stream = c->own_stream;
-    const size_t frame_bytes = static_cast<size_t>(width) * height * 4;
-    if ((e = hipMalloc(&c->d_frame_own, frame_bytes)) != hipSuccess) return bail(e, "hipMalloc(frame)");
-    if ((e = hipMalloc(&c->d_shard_own, static_cast<size_t>(c->n_tiles) * 1024)) != hipSuccess) return bail(e, "hipMalloc(shard)");
-    if ((e = hipMalloc(&c->d_tables, sizeof(FrameTables))) != hipSuccess) return bail(e, "hipMalloc(tables)");
-    if ((e = hipMalloc(&c->d_counters, sizeof(Counters))) != hipSuccess) return bail(e, "hipMalloc(counters)");
-    if ((e = hipMemset(c->d_frame_own, 0, frame_bytes)) != hipSuccess) return bail(e, "hipMemset(frame)");
-    if ((e = hipMalloc(&c->d_aabb, 6 * sizeof(int))) != hipSuccess) return bail(e, "hipMalloc(aabb)");
-    {
-        const uint64_t tiles8 = static_cast<uint64_t>(c->tiles_x) * 2u * c->tiles_y * 2u;
-        const uint64_t words = (tiles8 + 31u) / 32u;
-        c->tile_mask_words = words <= VOLYM_TILE_MASK_MAX_WORDS ? static_cast<uint32_t>(words) : 0u;
-        if (c->tile_mask_words && (e = hipMalloc(&c->d_tile_mask, 2u * c->tile_mask_words * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc(tile mask)");
-        if (c->tile_mask_words && (e = hipMemset(c->d_tile_mask, 0, 2u * c->tile_mask_words * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMemset(tile mask)");
-    }
-    if ((e = hipMalloc(&c->d_pack_counters, 4 * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc(pack counters)");
-    if ((e = hipMemset(c->d_pack_counters, 0, 4 * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMemset(pack counters)");
-    if ((e = hipMalloc(&c->d_pool_sync, 4 * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc(pool sync)");
-    if ((e = hipMemset(c->d_pool_sync, 0, 4 * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMemset(pool sync)");
-    if ((e = hipMalloc(&c->d_pool_dbg, static_cast<size_t>(c->n_cus) * 8u * PL_WAVES * 24u * sizeof(uint32_t))) != hipSuccess) return bail(e, "hipMalloc(pool timeline)");
-    for (int i = 0; i < volym_ctx::TABLE_RING; ++i) {
-        if ((e = hipHostMalloc(reinterpret_cast<void**>(&c->h_tables[i]), sizeof(FrameTables), hipHostMallocDefault)) != hipSuccess) return bail(e, "hipHostMalloc(tables)");
-        if ((e = hipEventCreateWithFlags(&c->tables_ev[i], hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    }
-    if ((e = hipEventCreateWithFlags(&c->ev_march, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&c->ev_cost, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&c->ev_list, hipEventDisableTiming)) != hipSuccess) return bail(e, "hipEventCreate");
-
-    c->d_frame = c->d_frame_own;
-    c->d_shard = c->d_shard_own;
-    int rc = rebuild_lists(c);
+    c->slots[0].reset(new (std::nothrow) FrameSlot());
+    const int rc = c->slots[0] ? init_slot(c, c->slot0()) : fail(c, VOLYM_E_NOMEM, "out of host memory");
     if (rc != VOLYM_OK) { const std::string m = c->err; volym_destroy(c); return fail(nullptr, rc, m); }
-    try {
-        c->fb_thread = std::thread(feedback_thread, c);
-    } catch (...) {
-        volym_destroy(c);
-        return fail(nullptr, VOLYM_E_NOMEM, "volym_create: cannot start the feedback thread");
-    }
     *out = c;
     return VOLYM_OK;
 }
@@ -813,134 +868,80 @@ int volym_create(volym_ctx** out, uint32_t width, uint32_t height, int device_id
 void volym_destroy(volym_ctx* c)
 {
     if (!c) return;
-    if (c->twin) { volym_destroy(c->twin); c->twin = nullptr; }
     (void)hipSetDevice(c->device);
-    if (c->fb_thread.joinable()) {
-        feedback_quiesce(c);
-        {
-            std::lock_guard<std::mutex> lk(c->fb_mu);
-            c->fb_state.store(volym_ctx::FB_QUIT, std::memory_order_release);
-        }
-        c->fb_cv.notify_all();
-        c->fb_thread.join();
-    }
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-    (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_tables); (void)hipFree(c->d_mc); (void)hipFree(c->d_df);
-    (void)hipFree(c->d_shard_own); (void)hipFree(c->d_frame_own); (void)hipFree(c->d_f32); (void)hipFree(c->d_blit);
-    (void)hipFree(c->d_gather_tmp); (void)hipFree(c->d_pack_counters); (void)hipFree(c->d_counters); (void)hipFree(c->d_aabb); (void)hipFree(c->d_tile_mask);
-    (void)hipFree(c->d_list[0]); (void)hipFree(c->d_list[1]); (void)hipFree(c->d_cost);
-    (void)hipFree(c->d_pool_sync); (void)hipFree(c->d_pool_dbg);
-    if (c->h_list_pinned) (void)hipHostFree(c->h_list_pinned);
-    if (c->h_cost_pinned) (void)hipHostFree(c->h_cost_pinned);
-    for (int i = 0; i < volym_ctx::TABLE_RING; ++i) {
-        if (c->h_tables[i]) (void)hipHostFree(c->h_tables[i]);
-        if (c->tables_ev[i]) (void)hipEventDestroy(c->tables_ev[i]);
-    }
+    for (int i = 1; i >= 0; --i)
+        if (c->slots[i]) free_slot(*c->slots[i]);
+    // (every slot's stream is idle now: nothing reads the scene any more)
+    (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_mc);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
-    if (c->ev_march) (void)hipEventDestroy(c->ev_march);
-    if (c->ev_cost) (void)hipEventDestroy(c->ev_cost);
-    if (c->ev_list) (void)hipEventDestroy(c->ev_list);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     delete c;
 }
 
 int volym_set_stream(volym_ctx* c, void* hip_stream)
 {
     if (!c) return VOLYM_E_INVALID;
-    TWIN_REFUSE(c, "volym_set_stream");
+    if (c->slots[1]) return refuse_two_slots(c, "volym_set_stream");
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
-    feedback_quiesce(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->own_stream;
-    return VOLYM_OK;
-}
-
-int volym_settle(volym_ctx* c)
-{
-    if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_settle(c->twin));
-    feedback_quiesce(c);
-    if (!c->fb_job.error.empty()) { const std::string m = c->fb_job.error; c->fb_job.error.clear(); return fail(c, VOLYM_E_HIP, m); }
-    // ... and run the feedback to its fixed point for the current view: frames of this view (what volym_compute_pass
-    // enqueues) until the list in use is final -- measuring list, deal, re-balancing rounds (raymarch.hip, "cost feedback")
-    if (c->have_frame && c->kernel_variant >= 2 && !frame_uses_pool(c, c->fp.flags) && c->feedback && !c->feedback_frozen && c->lists_ready) {
-        for (int round = 0; round < 12; ++round) {
-            const WorkList& wl = c->lists[c->cur];
-            if (wl.entries.empty() || (wl.view_serial == c->view_serial.load(std::memory_order_relaxed) && wl.final_for_view)) break;
-            int rc = volym::ctx_launch_march(c);
-            if (rc != VOLYM_OK) return rc;
-            feedback_quiesce(c);
-            if (!c->fb_job.error.empty()) { const std::string m = c->fb_job.error; c->fb_job.error.clear(); return fail(c, VOLYM_E_HIP, m); }
-        }
-    }
+    feedback_quiesce(s);
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    s.stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : s.own_stream;
     return VOLYM_OK;
 }
 
 static bool want_bricked(const volym_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz);
 
-static int set_option_one(volym_ctx* c, int key, int value);
+static int set_frames_in_flight(volym_ctx* c, int value)
+{
+    if (value != 1 && value != 2) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_FRAMES_IN_FLIGHT: 1 or 2");
+    if (value == 1) {
+        if (c->slots[1]) {
+            int rc = volym_sync(c);
+            if (rc != VOLYM_OK) return rc;
+            // (a buffer of slot 1 itself does not stay bound: a caller may have bound what volym_frame_device_ptr gave)
+            if (c->bound_frame == c->slots[1]->d_frame_own) c->bound_frame = nullptr;
+            if (c->bound_shard == c->slots[1]->d_shard_own) c->bound_shard = nullptr;
+            free_slot(*c->slots[1]);
+            c->slots[1].reset();
+            c->last = c->last_blit = 0; c->flight_parity = 0;
+        }
+        return VOLYM_OK;
+    }
+    if (c->slots[1]) return VOLYM_OK;
+    if (c->have_vol || c->have_imp || c->have_tf)
+        return fail(c, VOLYM_E_STATE, "VOLYM_OPT_FRAMES_IN_FLIGHT = 2: set it before the volume, the importances and the transfer function");
+    if (c->slot0().stream != c->slot0().own_stream) return fail(c, VOLYM_E_STATE, "VOLYM_OPT_FRAMES_IN_FLIGHT = 2: not with a caller's stream (volym_set_stream)");
+    // (slot 0's own buffer, bound by the caller, stays slot 0's alone: slot 1 renders into its own)
+    if (c->bound_frame == c->slot0().d_frame_own) c->bound_frame = nullptr;
+    if (c->bound_shard == c->slot0().d_shard_own) c->bound_shard = nullptr;
+    c->slots[1].reset(new (std::nothrow) FrameSlot());
+    const int rc = c->slots[1] ? init_slot(c, *c->slots[1]) : fail(c, VOLYM_E_NOMEM, "out of host memory");
+    if (rc != VOLYM_OK) {
+        if (c->slots[1]) free_slot(*c->slots[1]);
+        c->slots[1].reset();
+        return fail(c, rc, "second frame slot: " + c->err);
+    }
+    c->slots[1]->fp.dev = c->slot0().fp.dev;    // (dev option 110)
+    return VOLYM_OK;
+}
 
 int volym_set_option(volym_ctx* c, int key, int value)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (key == VOLYM_OPT_FRAMES_IN_FLIGHT) {
-        if (value != 1 && value != 2) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_FRAMES_IN_FLIGHT: 1 or 2");
-        if (value == 1) {
-            if (c->twin) {
-                int rc = volym_sync(c);
-                if (rc != VOLYM_OK) return rc;
-                // (nothing of ours may keep pointing at the twin's buffers: a caller may have bound what volym_frame_device_ptr gave)
-                if (c->d_frame == c->twin->d_frame_own) c->d_frame = c->d_frame_own;
-                if (c->d_shard == c->twin->d_shard_own) c->d_shard = c->d_shard_own;
-                volym_destroy(c->twin);
-                c->twin = nullptr; c->last = c->last_blit = nullptr; c->flight_parity = 0;
-            }
-            return VOLYM_OK;
-        }
-        if (c->twin) return VOLYM_OK;
-        if (c->have_vol || c->have_imp || c->have_tf)
-            return fail(c, VOLYM_E_STATE, "VOLYM_OPT_FRAMES_IN_FLIGHT = 2: set it before the volume, the importances and the transfer function");
-        if (c->stream != c->own_stream) return fail(c, VOLYM_E_STATE, "VOLYM_OPT_FRAMES_IN_FLIGHT = 2: not with a caller's stream (volym_set_stream)");
-        volym_ctx* t = nullptr;
-        int rc = volym_create(&t, c->W, c->H, c->device);
-        if (rc != VOLYM_OK) return fail(c, rc, std::string("second frame context: ") + volym_last_error(nullptr));
-        for (const auto& kv : c->option_log) {
-            rc = set_option_one(t, kv.first, kv.second);
-            if (rc != VOLYM_OK) { const std::string m = t->err; volym_destroy(t); return fail(c, rc, "second frame context: " + m); }
-        }
-        if (c->world != 1u) {
-            rc = volym_set_shard(t, c->rank, c->world);
-            if (rc != VOLYM_OK) { const std::string m = t->err; volym_destroy(t); return fail(c, rc, "second frame context: " + m); }
-        }
-        // output buffers the caller bound before: the twin renders into them too (volym_bind_output)
-        if (c->d_frame != c->d_frame_own) t->d_frame = c->d_frame;
-        if (c->d_shard != c->d_shard_own) t->d_shard = c->d_shard;
-        c->twin = t;
-        return VOLYM_OK;
-    }
-    const int rc = set_option_one(c, key, value);
-    if (rc != VOLYM_OK) return rc;
-    // (the log is what a twin created later starts from: it can only be created before the scene is set)
-    if (!c->twin && !(c->have_vol || c->have_imp || c->have_tf)) c->option_log.emplace_back(key, value);
-    TWIN_FORWARD(c, set_option_one(c->twin, key, value));
-    return VOLYM_OK;
-}
-
-static int set_option_one(volym_ctx* c, int key, int value)
-{
-    if (!c) return VOLYM_E_INVALID;
     switch (key) {
+    case VOLYM_OPT_FRAMES_IN_FLIGHT:
+        return set_frames_in_flight(c, value);
     case VOLYM_OPT_KERNEL:
         if (value < 0 || value > 3) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_KERNEL: 0 (direct), 1 (macro-cell), 2 (persistent tiles + shading queue) or 3 (ray pool)");
         c->kernel_variant = value;
         return VOLYM_OK;
     case VOLYM_OPT_WRITE_F32:
         c->write_f32 = value != 0;
-        if (c->write_f32 && !c->d_f32) {
+        for (int i = 0; i < c->n_slots() && c->write_f32; ++i) {
+            FrameSlot& s = *c->slots[i];
+            if (s.d_f32) continue;
             HIPCHK(c, hipSetDevice(c->device));
-            hipError_t e = hipMalloc(&c->d_f32, static_cast<size_t>(c->W) * c->H * sizeof(float4));
+            hipError_t e = hipMalloc(&s.d_f32, static_cast<size_t>(c->W) * c->H * sizeof(float4));
             if (e != hipSuccess) { c->write_f32 = false; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(f32 frame): ") + hipGetErrorString(e)); }
         }
         return VOLYM_OK;
@@ -950,22 +951,22 @@ static int set_option_one(volym_ctx* c, int key, int value)
             return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_MACRO_CELLS: power of two in 4..32");
         c->mc_n = static_cast<uint32_t>(value);
         if (c->have_vol) { int rc = build_macro_cells(c); if (rc != VOLYM_OK) return rc; }
-        return forget_costs(c);
+        return rebuild_lists(c);
     case VOLYM_OPT_VOLUME_LAYOUT:
         if (value < -1 || value > 1) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_VOLUME_LAYOUT: -1 (by size), 0 (linear) or 1 (4x4x4 bricks)");
         c->layout_choice = value;
         return VOLYM_OK;
     case VOLYM_OPT_CULLING:
         c->culling = value != 0;
-        c->hull_dirty = true;
+        for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->hull_dirty = true;
         return VOLYM_OK;
     case VOLYM_OPT_COST_FEEDBACK:
         c->feedback = value != 0;
-        return forget_costs(c);
+        return rebuild_lists(c);
     case VOLYM_OPT_DEPTH_PARALLEL:
         if (value < -100 || value > 65535) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_DEPTH_PARALLEL: < 0 adaptive (-N = N/10 x fair share), 0 off, else explicit cost");
         c->dp_min_cost = value;
-        return forget_costs(c);
+        return rebuild_lists(c);
     case VOLYM_OPT_REBALANCE_ROUNDS:   // 0: the dealt list is final
         if (value < 0 || value > 8) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_REBALANCE_ROUNDS: 0..8");
         c->trim_rounds = static_cast<uint32_t>(value);
@@ -983,24 +984,24 @@ static int set_option_one(volym_ctx* c, int key, int value)
     case 101:   // persistent workgroups per CU (variant 2)
         if (value < 1 || value > 8) return fail(c, VOLYM_E_INVALID, "workgroups per CU: 1..8");
         c->wgs_per_cu = static_cast<uint32_t>(value);
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 107:   // 0 disables the 16x16 super fill items
         c->super_fill = value != 0;
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 108:   // issue-priority thresholds t1 + 100*t2 + 10000*t3 in tenths of the fair share (0 = no priorities)
         if (value < 0) return fail(c, VOLYM_E_INVALID, "priority thresholds: t1 + 100*t2 + 10000*t3, tenths of the fair share");
         c->prio_tenths[0] = static_cast<uint32_t>(value % 100);
         c->prio_tenths[1] = static_cast<uint32_t>((value / 100) % 100);
         c->prio_tenths[2] = static_cast<uint32_t>(value / 10000);
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 109:   // keep only the depth-parallel items in the work list (the frame is then incomplete)
         c->dev_only_quarters = value != 0;
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 110:   // FrameParams::dev
-        c->fp.dev = static_cast<uint32_t>(value);
+        for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->fp.dev = static_cast<uint32_t>(value);
         return VOLYM_OK;
     case 113:   // 1 freezes the cost feedback: no more captures, the current list stays (how fast do lists go stale?)
-        feedback_quiesce(c);
+        for (int i = 0; i < c->n_slots(); ++i) feedback_quiesce(*c->slots[i]);
         c->feedback_frozen = value != 0;
         return VOLYM_OK;
     case 114:   // dilation radius (in 8x8 items) of the cost map when a list is dealt
@@ -1009,13 +1010,13 @@ static int set_option_one(volym_ctx* c, int key, int value)
     case 115:   // waves per workgroup of the instantiations that need more than 128 VGPRs: 0 default, 12 or 16
         if (value != 0 && value != 12 && value != 16) return fail(c, VOLYM_E_INVALID, "wide waves: 0, 12 or 16");
         c->wide_waves = value;
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 119:   // floor of the adaptive split threshold (cost units)
         c->dp_floor = static_cast<uint32_t>(std::max(value, 1));
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 118:   // drop the tiles of >= value/10 x the fair share from the lists (the frame is then incomplete): how much do they cost?
         c->dev_drop_tenths = static_cast<uint32_t>(std::max(value, 0));
-        return forget_costs(c);
+        return rebuild_lists(c);
     case 121:   // 1: the straight look-ahead as jobs shared by the workgroup (raymarch_pq.h CJ = 2)
         c->straight_jobs = value != 0;
         return VOLYM_OK;
@@ -1025,12 +1026,12 @@ static int set_option_one(volym_ctx* c, int key, int value)
     case 117:   // 0: no per-view tile mask (the hulls and the AABB clip stay); 2: a mask for every view, on its first frame
         c->tile_mask = value != 0;
         c->mask_eager = value == 2;
-        c->hull_dirty = true;
-        return forget_costs(c);
+        for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->hull_dirty = true;
+        return rebuild_lists(c);
     case 111:   // balancing estimates, dp_share_pct + 1000 * fill_cost
         c->dp_share_pct = static_cast<uint32_t>(value % 1000);
         c->fill_cost = static_cast<uint32_t>(value / 1000);
-        return forget_costs(c);
+        return rebuild_lists(c);
 #endif
     default:
         return fail(c, VOLYM_E_INVALID, "volym_set_option: unknown key");
@@ -1040,13 +1041,11 @@ static int set_option_one(volym_ctx* c, int key, int value)
 int volym_set_shard(volym_ctx* c, uint32_t rank, uint32_t world)
 {
     if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_set_shard(c->twin, rank, world));
     if (world == 0 || rank >= world || world > 4096) return fail(c, VOLYM_E_INVALID, "volym_set_shard: need rank < world <= 4096");
-    // the feedback thread reads rank / world / n_local while it deals a list: let a job in flight finish (and the frames that
+    // the feedback threads read rank / world / n_local while they deal a list: let the jobs in flight finish (and the frames that
     // read the current lists) before any of them changes
-    feedback_quiesce(c);
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
     c->rank = rank; c->world = world;
     recompute_shard(c);
     return rebuild_lists(c);
@@ -1060,9 +1059,8 @@ static int upload_volume(volym_ctx* c, uint8_t** dst, const uint8_t* src, uint32
     const uint64_t nb = bricked ? static_cast<uint64_t>(brick_count(nx)) * brick_count(ny) * brick_count(nz) * 64u : n;
     if (nx > 4096 || ny > 4096 || nz > 4096 || nb > 0xffffffffull)
         return fail(c, VOLYM_E_INVALID, "volume: each dimension <= 4096 and the brick-padded size < 2^32");
-    HIPCHK(c, hipSetDevice(c->device));
-    feedback_quiesce(c);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
     if (*dst) { HIPCHK(c, hipFree(*dst)); *dst = nullptr; }
     uint8_t* staging = nullptr;
     hipError_t e = hipMalloc(dst, nb + 16);      // the trilinear fetch reads voxel pairs: one byte past the last voxel is touched
@@ -1071,9 +1069,10 @@ static int upload_volume(volym_ctx* c, uint8_t** dst, const uint8_t* src, uint32
     if (e != hipSuccess) { (void)hipFree(staging); return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(volume): ") + hipGetErrorString(e)); }
     e = hipMemcpy(bricked ? staging : *dst, src, n, hipMemcpyHostToDevice);
     if (e == hipSuccess && bricked) {
-        hipLaunchKernelGGL(volym_rebrick_kernel, dim3(static_cast<uint32_t>((nb + 255u) / 256u)), dim3(256), 0, c->stream, staging, *dst, nx, ny, nz);
+        const hipStream_t stream = c->slot0().stream;
+        hipLaunchKernelGGL(volym_rebrick_kernel, dim3(static_cast<uint32_t>((nb + 255u) / 256u)), dim3(256), 0, stream, staging, *dst, nx, ny, nz);
         e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
     }
     (void)hipFree(staging);
     if (e != hipSuccess) return fail(c, VOLYM_E_HIP, std::string("volume upload: ") + hipGetErrorString(e));
@@ -1091,17 +1090,15 @@ static bool want_bricked(const volym_ctx* c, uint32_t nx, uint32_t ny, uint32_t 
 int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t ny, uint32_t nz, int filter)
 {
     if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_set_volume(c->twin, voxels, nx, ny, nz, filter));
     if (filter != VOLYM_FILTER_NEAREST && filter != VOLYM_FILTER_LINEAR)
         return fail(c, VOLYM_E_INVALID, "volym_set_volume: filter must be VOLYM_FILTER_NEAREST or VOLYM_FILTER_LINEAR");
     int rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;
     c->bricked = want_bricked(c, nx, ny, nz);
-    c->have_vol = true;
-    rc = build_macro_cells(c);
+    rc = build_macro_cells(c);             // (sets have_vol)
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
-    return forget_costs(c);
+    return rebuild_lists(c);
 }
 
 // AABB (texel indices) of the importances a look-ahead probe counts as important (byte >= 128, wgsl:133, :155).  Host scan,
@@ -1136,25 +1133,23 @@ static void important_texel_box(const uint8_t* imp, uint32_t nx, uint32_t ny, ui
 int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_set_importances(c->twin, importances, nx, ny, nz));
     int rc = upload_volume(c, &c->d_imp, importances, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_imp = false; return rc; }
     important_texel_box(importances, nx, ny, nz, c->imp_box_lo, c->imp_box_hi);
     c->inx = nx; c->iny = ny; c->inz = nz;
     c->have_imp = true;
-    return forget_costs(c);
+    return rebuild_lists(c);
 }
 
 int volym_set_transfer_function(volym_ctx* c, const uint8_t* rgba8, uint32_t n)
 {
     if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_set_transfer_function(c->twin, rgba8, n));
     if (!rgba8 || n < 1 || n > 256) return fail(c, VOLYM_E_INVALID, "volym_set_transfer_function: 1..256 RGBA8 texels");
     std::memset(c->lut, 0, sizeof c->lut);
     std::memcpy(c->lut, rgba8, static_cast<size_t>(n) * 4);
     c->tf_n = n;
     c->have_tf = true;
-    c->tables_dirty = true;
+    for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->tables_dirty = true;
     return VOLYM_OK;
 }
 
@@ -1162,82 +1157,63 @@ int volym_set_transfer_function(volym_ctx* c, const uint8_t* rgba8, uint32_t n)
 
 // Per-frame resources that depend on the uniforms: distance field for the threshold byte (a launch, in stream order) and
 // the culling hulls (host arithmetic).  Nothing here allocates or waits.
-static int ensure_frame_resources(volym_ctx* c)
+static int ensure_frame_resources(volym_ctx* c, FrameSlot& s)
 {
-    if (c->df_thr_byte != c->thr_byte_cull) {
+    if (s.df_thr_byte != s.thr_byte_cull) {
         // stream order: earlier frames finish reading d_df before this kernel rewrites it
-        if (c->mc_n <= 32u) hipLaunchKernelGGL(volym_distance_field_kernel<1>, dim3(1), dim3(1024), 0, c->stream, c->d_mc, c->d_df, c->d_aabb, c->mc_n, c->thr_byte_cull);
-        else hipLaunchKernelGGL(volym_distance_field_kernel<4>, dim3(1), dim3(1024), 0, c->stream, c->d_mc, c->d_df, c->d_aabb, c->mc_n, c->thr_byte_cull);
+        if (c->mc_n <= 32u) hipLaunchKernelGGL(volym_distance_field_kernel<1>, dim3(1), dim3(1024), 0, s.stream, c->d_mc, s.d_df, s.d_aabb, c->mc_n, s.thr_byte_cull);
+        else hipLaunchKernelGGL(volym_distance_field_kernel<4>, dim3(1), dim3(1024), 0, s.stream, c->d_mc, s.d_df, s.d_aabb, c->mc_n, s.thr_byte_cull);
         HIPCHK(c, hipGetLastError());
-        c->df_thr_byte = c->thr_byte_cull;
-        c->hull_dirty = true;
+        s.df_thr_byte = s.thr_byte_cull;
+        s.hull_dirty = true;
     }
-    if (c->hull_dirty) {
-        compute_culling(c);
-        c->fp.tile_mask = nullptr;
-        c->fp.mask_words = c->tile_mask_words;
-        c->fp.tile_mask_spare = c->d_tile_mask ? c->d_tile_mask + static_cast<size_t>(c->mask_cur ^ 1) * c->tile_mask_words : nullptr;
-        c->mask_pending = c->mask_wanted;
-        c->view_launches = 0;
+    if (s.hull_dirty) {
+        compute_culling(c, s);
+        s.fp.tile_mask = nullptr;
+        s.fp.mask_words = c->tile_mask_words;
+        s.fp.tile_mask_spare = s.d_tile_mask ? s.d_tile_mask + static_cast<size_t>(s.mask_cur ^ 1) * c->tile_mask_words : nullptr;
+        s.mask_pending = s.mask_wanted;
+        s.view_launches = 0;
     }
     // The tile mask costs a kernel per view (~13 us: device-scope atomics) and changes which tiles are constant from view to view.
     // It is built when a view is rendered a SECOND time: a standing view has it from its second frame on; a moving camera
     // never pays for it -- and does not want it: the lists it runs were dealt for earlier views, and a 16x16 entry that was
     // constant under that view's mask is four marched tiles on one wave under this one's (turntable at 3840x2160, 1 degree per
     // frame: 130 us per frame without a mask per view, 164 with; at 1080p, 0.25 degrees: 52 and 62).
-    if (c->mask_pending && (c->view_launches >= 1u || c->mask_eager)) {
+    if (s.mask_pending && (s.view_launches >= 1u || c->mask_eager)) {
         ClipMatrix M;
-        std::memcpy(M.m, c->mask_clip, sizeof M.m);
+        std::memcpy(M.m, s.mask_clip, sizeof M.m);
         // into the buffer the launches so far have kept zeroed; the launches from here on read it and zero the other one
-        c->mask_cur ^= 1;
-        uint32_t* cur = c->d_tile_mask + static_cast<size_t>(c->mask_cur) * c->tile_mask_words;
+        s.mask_cur ^= 1;
+        uint32_t* cur = s.d_tile_mask + static_cast<size_t>(s.mask_cur) * c->tile_mask_words;
         const uint32_t cells = c->mc_n * c->mc_n * c->mc_n;
         if (static_cast<size_t>(c->tile_mask_words) * sizeof(uint32_t) <= 48u * 1024u) {
             // the mask fits LDS: aggregated per block of cells, only the words that are not zero travel
             const uint32_t nb = (c->mc_n + 7u) / 8u;
-            hipLaunchKernelGGL(volym_tile_mask_lds_kernel, dim3(nb * nb * ((c->mc_n + 3u) / 4u)), dim3(256), c->tile_mask_words * sizeof(uint32_t), c->stream, c->d_mc, c->mc_n,
-                               c->thr_byte_cull, M, c->mask_margin, c->W, c->H, c->tiles_x * 2u, c->tile_mask_words, cur);
+            hipLaunchKernelGGL(volym_tile_mask_lds_kernel, dim3(nb * nb * ((c->mc_n + 3u) / 4u)), dim3(256), c->tile_mask_words * sizeof(uint32_t), s.stream, c->d_mc, c->mc_n,
+                               s.thr_byte_cull, M, s.mask_margin, c->W, c->H, c->tiles_x * 2u, c->tile_mask_words, cur);
         } else {
-            hipLaunchKernelGGL(volym_tile_mask_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, c->stream, c->d_mc, c->mc_n, c->thr_byte_cull, M, c->mask_margin,
+            hipLaunchKernelGGL(volym_tile_mask_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, s.stream, c->d_mc, c->mc_n, s.thr_byte_cull, M, s.mask_margin,
                                c->W, c->H, c->tiles_x * 2u, c->tile_mask_words, cur);
         }
         HIPCHK(c, hipGetLastError());
-        c->fp.tile_mask = cur;
-        c->fp.cull |= CULL_TILE_MASK;
-        c->fp.tile_mask_spare = c->d_tile_mask + static_cast<size_t>(c->mask_cur ^ 1) * c->tile_mask_words;
-        c->mask_pending = false;
+        s.fp.tile_mask = cur;
+        s.fp.cull |= CULL_TILE_MASK;
+        s.fp.tile_mask_spare = s.d_tile_mask + static_cast<size_t>(s.mask_cur ^ 1) * c->tile_mask_words;
+        s.mask_pending = false;
         // costs measured before the mask existed describe tiles that are constant from here on: for the cost feedback this is a
         // new view (a list dealt from the old costs would balance work that is no longer there: 33.2 instead of 32.3 us)
-        if (c->view_launches >= 1u) c->view_serial.fetch_add(1, std::memory_order_relaxed);
+        if (s.view_launches >= 1u) s.view_serial.fetch_add(1, std::memory_order_relaxed);
     }
-    c->view_launches++;
+    s.view_launches++;
     return VOLYM_OK;
 }
 
-extern "C" {
-
-int volym_update(volym_ctx* c, const volym_camera_uniforms* cam, const volym_parameter_uniforms* par)
+// volym_update's part in one slot; view_changed: the uniforms differ from the last update's
+static int update_slot(volym_ctx* c, FrameSlot& s, const volym_camera_uniforms* cam, const volym_parameter_uniforms* par, bool view_changed)
 {
-    if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_update(c->twin, cam, par));
-    if (!cam || !par) return fail(c, VOLYM_E_INVALID, "volym_update: NULL uniforms");
-    if (!c->have_vol || !c->have_imp || !c->have_tf)
-        return fail(c, VOLYM_E_STATE, "volym_update: set volume, importances and transfer function first");
-    if (c->nx != c->inx || c->ny != c->iny || c->nz != c->inz)
-        return fail(c, VOLYM_E_STATE, "volym_update: volume and importances differ in size");
-    // The reference loops `while t < exit` with t += step on the GPU; a step that cannot advance t
-    // would never terminate there.  Refuse such inputs instead of hanging the device.
     const float step = par->raymarching_step_size;
-    if (!(step >= 1.0e-4f && step <= 1.0f)) return fail(c, VOLYM_E_INVALID, "volym_update: raymarching_step_size must be in [1e-4, 1]");
-    if (!std::isfinite(par->density_threshold)) return fail(c, VOLYM_E_INVALID, "volym_update: density_threshold is not finite");
-    if (par->importance_check_ahead_steps > 4096u) return fail(c, VOLYM_E_INVALID, "volym_update: importance_check_ahead_steps > 4096");
-    for (int i = 0; i < 16; ++i)
-        if (!std::isfinite((&cam->inverse_view_proj[0][0])[i])) return fail(c, VOLYM_E_INVALID, "volym_update: inverse_view_proj is not finite");
-    for (int i = 0; i < 3; ++i)
-        if (!(std::fabs(cam->camera_position[i]) <= 64.0f)) return fail(c, VOLYM_E_INVALID, "volym_update: |camera_position| must be <= 64 per axis");
-
-    HIPCHK(c, hipSetDevice(c->device));
-    FrameParams& fp = c->fp;
+    FrameParams& fp = s.fp;
     std::memcpy(fp.ivp, cam->inverse_view_proj, sizeof fp.ivp);
     fp.eye[0] = cam->camera_position[0]; fp.eye[1] = cam->camera_position[1]; fp.eye[2] = cam->camera_position[2];
     fp.thr = par->density_threshold;
@@ -1282,38 +1258,68 @@ int volym_update(volym_ctx* c, const volym_camera_uniforms* cam, const volym_par
     std::memcpy(fp.cone_cos, k_cone_cos, sizeof k_cone_cos);
     std::memcpy(fp.cone_sin, k_cone_sin, sizeof k_cone_sin);
 
-    if (c->tables_dirty || c->tables_alpha_y != fp.alpha_y) {
+    if (s.tables_dirty || s.tables_alpha_y != fp.alpha_y) {
         // New tables travel in stream order behind the frames that read the old ones.  The pinned staging slot must not be
         // rewritten before its copy has run: a ring of TABLE_RING slots, each with the event of its last copy.  Only a
         // caller that changes the step size or the transfer function TABLE_RING times while the device is that many frames
         // behind ever waits here.
-        const int slot = c->tables_slot;
-        c->tables_slot = (slot + 1) % volym_ctx::TABLE_RING;
-        if (hipEventQuery(c->tables_ev[slot]) != hipSuccess) HIPCHK(c, hipEventSynchronize(c->tables_ev[slot]));
-        build_tables(c, *c->h_tables[slot], fp.alpha_y);
-        c->tables_now = *c->h_tables[slot];
-        HIPCHK(c, hipMemcpyAsync(c->d_tables, c->h_tables[slot], sizeof(FrameTables), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->tables_ev[slot], c->stream));
-        c->tables_dirty = false;
-        c->tables_alpha_y = fp.alpha_y;
+        const int slot = s.tables_slot;
+        s.tables_slot = (slot + 1) % FrameSlot::TABLE_RING;
+        if (hipEventQuery(s.tables_ev[slot]) != hipSuccess) HIPCHK(c, hipEventSynchronize(s.tables_ev[slot]));
+        build_tables(c, *s.h_tables[slot], fp.alpha_y);
+        s.tables_now = *s.h_tables[slot];
+        HIPCHK(c, hipMemcpyAsync(s.d_tables, s.h_tables[slot], sizeof(FrameTables), hipMemcpyHostToDevice, s.stream));
+        HIPCHK(c, hipEventRecord(s.tables_ev[slot], s.stream));
+        s.tables_dirty = false;
+        s.tables_alpha_y = fp.alpha_y;
     }
     uint32_t tb = 256;
     for (int b = 255; b >= 0; --b)
-        if (c->tables_now.rho[b] >= fp.thr) tb = static_cast<uint32_t>(b); else break;
+        if (s.tables_now.rho[b] >= fp.thr) tb = static_cast<uint32_t>(b); else break;
     fp.thr_byte = tb;
     // continuous-rho modes (trilinear / smoothed) compare an interpolated value: give its rounding some room
     if (fp.flags & (F_LINEAR | F_GAUSSIAN)) {
         const float cons = fp.thr - std::fabs(fp.thr) * 1.0e-5f - 1.0e-7f;
         uint32_t tc = 256;
         for (int b = 255; b >= 0; --b)
-            if (c->tables_now.rho[b] >= cons) tc = static_cast<uint32_t>(b); else break;
-        c->thr_byte_cull = tc;
+            if (s.tables_now.rho[b] >= cons) tc = static_cast<uint32_t>(b); else break;
+        s.thr_byte_cull = tc;
     } else {
-        c->thr_byte_cull = tb;
+        s.thr_byte_cull = tb;
     }
-    if (!c->have_frame || std::memcmp(&c->cam_copy, cam, sizeof *cam) != 0 || std::memcmp(&c->par_copy, par, sizeof *par) != 0) {
-        c->view_serial.fetch_add(1, std::memory_order_relaxed);   // the lists stay valid (they are scheduling only); the feedback follows the view
-        c->hull_dirty = true;                                     // hulls, AABB clip and tile mask belong to the view
+    if (view_changed) {
+        s.view_serial.fetch_add(1, std::memory_order_relaxed);    // the lists stay valid (they are scheduling only); the feedback follows the view
+        s.hull_dirty = true;                                      // hulls, AABB clip and tile mask belong to the view
+    }
+    return VOLYM_OK;
+}
+
+extern "C" {
+
+int volym_update(volym_ctx* c, const volym_camera_uniforms* cam, const volym_parameter_uniforms* par)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!cam || !par) return fail(c, VOLYM_E_INVALID, "volym_update: NULL uniforms");
+    if (!c->have_vol || !c->have_imp || !c->have_tf)
+        return fail(c, VOLYM_E_STATE, "volym_update: set volume, importances and transfer function first");
+    if (c->nx != c->inx || c->ny != c->iny || c->nz != c->inz)
+        return fail(c, VOLYM_E_STATE, "volym_update: volume and importances differ in size");
+    // The reference loops `while t < exit` with t += step on the GPU; a step that cannot advance t
+    // would never terminate there.  Refuse such inputs instead of hanging the device.
+    const float step = par->raymarching_step_size;
+    if (!(step >= 1.0e-4f && step <= 1.0f)) return fail(c, VOLYM_E_INVALID, "volym_update: raymarching_step_size must be in [1e-4, 1]");
+    if (!std::isfinite(par->density_threshold)) return fail(c, VOLYM_E_INVALID, "volym_update: density_threshold is not finite");
+    if (par->importance_check_ahead_steps > 4096u) return fail(c, VOLYM_E_INVALID, "volym_update: importance_check_ahead_steps > 4096");
+    for (int i = 0; i < 16; ++i)
+        if (!std::isfinite((&cam->inverse_view_proj[0][0])[i])) return fail(c, VOLYM_E_INVALID, "volym_update: inverse_view_proj is not finite");
+    for (int i = 0; i < 3; ++i)
+        if (!(std::fabs(cam->camera_position[i]) <= 64.0f)) return fail(c, VOLYM_E_INVALID, "volym_update: |camera_position| must be <= 64 per axis");
+
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool view_changed = !c->have_frame || std::memcmp(&c->cam_copy, cam, sizeof *cam) != 0 || std::memcmp(&c->par_copy, par, sizeof *par) != 0;
+    for (int i = 0; i < c->n_slots(); ++i) {
+        const int rc = update_slot(c, *c->slots[i], cam, par, view_changed);
+        if (rc != VOLYM_OK) return rc;
     }
     c->cam_copy = *cam;
     c->par_copy = *par;
@@ -1324,11 +1330,11 @@ int volym_update(volym_ctx* c, const volym_camera_uniforms* cam, const volym_par
 }  // extern "C"
 
 template <bool COUNT, bool TRACE = false>
-static int launch_march(volym_ctx* c)
+static int launch_march(volym_ctx* c, FrameSlot& s)
 {
-    int rc = ensure_frame_resources(c);
+    int rc = ensure_frame_resources(c, s);
     if (rc != VOLYM_OK) return rc;
-    FrameParams fp = c->fp;
+    FrameParams fp = s.fp;
     fp.rank = c->rank; fp.world = c->world; fp.n_local = c->n_local;
     fp.mc_n = c->mc_n;
     fp.xcd_bands = c->xcd_bands;
@@ -1341,32 +1347,34 @@ static int launch_march(volym_ctx* c)
         const uint32_t per_chunk = (c->n_local + chunks - 1u) / chunks;
         grid = per_chunk * chunks;
     }
-    Counters* cnt = (COUNT || (VOLYM_DEV_SWITCHES && (c->fp.dev & 512u))) ? c->d_counters : nullptr;
-    uint4* trace = TRACE ? c->d_trace : nullptr;
+    uint32_t* const d_shard = c->shard_buf(s);
+    uint32_t* const d_frame = c->frame_buf(s);
+    Counters* cnt = (COUNT || (VOLYM_DEV_SWITCHES && (s.fp.dev & 512u))) ? s.d_counters : nullptr;
+    uint4* trace = TRACE ? s.d_trace : nullptr;
     if (!COUNT && !TRACE && frame_uses_pool(c, fp.flags)) {
         // the ray pool (raymarch_pool.h): the common instantiation; every other flag set runs variant 2 below
         const uint32_t pgrid = std::min(256u, max_grid(c));         // (the lattice has 256 cells per superblock)
-        uint32_t* dbg = c->pool_dbg ? c->d_pool_dbg : nullptr;
+        uint32_t* dbg = s.pool_dbg ? s.d_pool_dbg : nullptr;
         if (c->bricked)
-            hipLaunchKernelGGL((volym_raymarch_pool_kernel<true>), dim3(pgrid), dim3(PL_WAVES * 64), 0, c->stream, c->d_vol, c->d_tables, c->d_df, c->d_pool_sync, c->d_shard,
-                               c->d_frame, c->d_f32, dbg, fp);
+            hipLaunchKernelGGL((volym_raymarch_pool_kernel<true>), dim3(pgrid), dim3(PL_WAVES * 64), 0, s.stream, c->d_vol, s.d_tables, s.d_df, s.d_pool_sync, d_shard,
+                               d_frame, s.d_f32, dbg, fp);
         else
-            hipLaunchKernelGGL((volym_raymarch_pool_kernel<false>), dim3(pgrid), dim3(PL_WAVES * 64), 0, c->stream, c->d_vol, c->d_tables, c->d_df, c->d_pool_sync, c->d_shard,
-                               c->d_frame, c->d_f32, dbg, fp);
+            hipLaunchKernelGGL((volym_raymarch_pool_kernel<false>), dim3(pgrid), dim3(PL_WAVES * 64), 0, s.stream, c->d_vol, s.d_tables, s.d_df, s.d_pool_sync, d_shard,
+                               d_frame, s.d_f32, dbg, fp);
         HIPCHK(c, hipGetLastError());
-        c->pool_launched = true;
+        s.pool_launched = true;
         return VOLYM_OK;
     }
     if (c->kernel_variant >= 2) {
         const bool plain = !COUNT && !TRACE;
-        if (plain) feedback_poll(c);                      // adopt a list the feedback thread has finished
-        const WorkList& wl = c->lists[c->cur];
+        if (plain) feedback_poll(s);                      // adopt a list the feedback thread has finished
+        const WorkList& wl = s.lists[s.cur];
         const uint32_t n_items = static_cast<uint32_t>(wl.entries.size());
         if (n_items == 0) return VOLYM_OK;
         // capture this launch's costs?  Only one capture is in flight; a list dealt from costs measured on this very view, on
         // whole 8x8 entries, is final
-        const bool capture = plain && c->feedback && !c->feedback_frozen && c->fb_state.load(std::memory_order_acquire) == volym_ctx::FB_IDLE && (wl.view_serial != c->view_serial.load(std::memory_order_relaxed) || !wl.final_for_view);
-        uint16_t* cost_out = capture ? c->d_cost : nullptr;
+        const bool capture = plain && c->feedback && !c->feedback_frozen && s.fb_state.load(std::memory_order_acquire) == FrameSlot::FB_IDLE && (wl.view_serial != s.view_serial.load(std::memory_order_relaxed) || !wl.final_for_view);
+        uint16_t* cost_out = capture ? s.d_cost : nullptr;
         const bool table = !(fp.flags & (F_LINEAR | F_GAUSSIAN));
         // IMP = false: opacity on and no importance colouring (the common cases), without (IR = false) or with (IR = true)
         // importance rendering; the instrumented launch always takes the general form
@@ -1383,8 +1391,8 @@ static int launch_march(volym_ctx* c)
         const uint32_t want = (n_items + waves - 1) / waves;
         const uint32_t pgrid = wl.grid ? wl.grid : std::max(1u, std::min(want, max_grid(c)));
 #define VOLYM_PQ_LAUNCH_J(T, KS, I, B, R, WV, J)                                                                                 \
-    hipLaunchKernelGGL((volym_raymarch_pq_kernel<T, COUNT && I, TRACE, KS, I, B, R, WV, J>), dim3(pgrid), dim3(WV * 64), 0, c->stream, c->d_vol,  \
-                       c->d_imp, c->d_tables, c->d_df, reinterpret_cast<const uint2*>(c->d_list[c->cur]), n_items, cost_out, c->d_shard, c->d_frame, c->d_f32, cnt, trace, fp)
+    hipLaunchKernelGGL((volym_raymarch_pq_kernel<T, COUNT && I, TRACE, KS, I, B, R, WV, J>), dim3(pgrid), dim3(WV * 64), 0, s.stream, c->d_vol,  \
+                       c->d_imp, s.d_tables, s.d_df, reinterpret_cast<const uint2*>(s.d_list[s.cur]), n_items, cost_out, d_shard, d_frame, s.d_f32, cnt, trace, fp)
 #define VOLYM_PQ_LAUNCH(T, KS, I, B, R, WV) VOLYM_PQ_LAUNCH_J(T, KS, I, B, R, WV, 0)
 #if VOLYM_DEV_SWITCHES
 #define VOLYM_PQ_LAUNCH_W(T, KS, I, B, R) do { if (wide12) VOLYM_PQ_LAUNCH(T, KS, I, B, R, PQ_WAVES_WIDE); else VOLYM_PQ_LAUNCH(T, KS, I, B, R, PQ_WAVES); } while (0)
@@ -1401,8 +1409,8 @@ static int launch_march(volym_ctx* c)
 #if VOLYM_DEV_SWITCHES
             // (dev, option 122: north_star's LDS-staged bricks, measured in profiles/r03_lds_bricks_ab.txt; not in the product library)
             if (table && no_imp && c->lds_bricks && !COUNT && !TRACE)
-                hipLaunchKernelGGL((volym_raymarch_pq_kernel<true, false, false, 4, false, true, false, PQ_WAVES, 0, true>), dim3(pgrid), dim3(PQ_WAVES * 64), 0, c->stream, c->d_vol,
-                                   c->d_imp, c->d_tables, c->d_df, reinterpret_cast<const uint2*>(c->d_list[c->cur]), n_items, cost_out, c->d_shard, c->d_frame, c->d_f32, cnt, trace, fp);
+                hipLaunchKernelGGL((volym_raymarch_pq_kernel<true, false, false, 4, false, true, false, PQ_WAVES, 0, true>), dim3(pgrid), dim3(PQ_WAVES * 64), 0, s.stream, c->d_vol,
+                                   c->d_imp, s.d_tables, s.d_df, reinterpret_cast<const uint2*>(s.d_list[s.cur]), n_items, cost_out, d_shard, d_frame, s.d_f32, cnt, trace, fp);
             else
 #endif
             if (table && no_imp) VOLYM_PQ_LAUNCH(true, 4, false, true, false, PQ_WAVES);
@@ -1429,15 +1437,15 @@ static int launch_march(volym_ctx* c)
         HIPCHK(c, hipGetLastError());
         if (capture) {
             // costs -> pinned host memory on the copy stream, behind this launch; the feedback thread takes it from there
-            HIPCHK(c, hipEventRecord(c->ev_march, c->stream));
-            HIPCHK(c, hipStreamWaitEvent(c->copy_stream, c->ev_march, 0));
+            HIPCHK(c, hipEventRecord(s.ev_march, s.stream));
+            HIPCHK(c, hipStreamWaitEvent(s.copy_stream, s.ev_march, 0));
             const size_t cost_bytes = static_cast<size_t>((n_items + 1u) & ~1u) * sizeof(uint16_t) + static_cast<size_t>(pgrid) * (waves + 1u) * sizeof(uint32_t);
-            HIPCHK(c, hipMemcpyAsync(c->h_cost_pinned, c->d_cost, cost_bytes, hipMemcpyDeviceToHost, c->copy_stream));
-            HIPCHK(c, hipEventRecord(c->ev_cost, c->copy_stream));
-            volym_ctx::FbJob& job = c->fb_job;
-            job.list = c->cur;
+            HIPCHK(c, hipMemcpyAsync(s.h_cost_pinned, s.d_cost, cost_bytes, hipMemcpyDeviceToHost, s.copy_stream));
+            HIPCHK(c, hipEventRecord(s.ev_cost, s.copy_stream));
+            FbJob& job = s.fb_job;
+            job.list = s.cur;
             job.n_entries = n_items;
-            job.view_serial = c->view_serial.load(std::memory_order_relaxed);
+            job.view_serial = s.view_serial.load(std::memory_order_relaxed);
             job.captured_has_dp = wl.has_dp;
             job.continuous = (fp.flags & (F_LINEAR | F_GAUSSIAN)) != 0u;
             job.plain = table && no_imp;                  // the common instantiation: the split threshold's floor was measured for it
@@ -1456,16 +1464,16 @@ static int launch_march(volym_ctx* c)
             job.t_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
             for (int i = 0; i < 3; ++i) job.prio_tenths[i] = c->prio_tenths[i];
             {
-                std::lock_guard<std::mutex> lk(c->fb_mu);
-                c->fb_state.store(volym_ctx::FB_CAPTURED, std::memory_order_release);
+                std::lock_guard<std::mutex> lk(s.fb_mu);
+                s.fb_state.store(FrameSlot::FB_CAPTURED, std::memory_order_release);
             }
-            c->fb_cv.notify_all();
+            s.fb_cv.notify_all();
         }
         return VOLYM_OK;
     }
 #define VOLYM_DIRECT_LAUNCH(V, B)                                                                                                \
-    hipLaunchKernelGGL((volym_raymarch_kernel<V, COUNT, TRACE, B>), dim3(grid), dim3(256), 0, c->stream, c->d_vol, c->d_imp, c->d_tables, \
-                       c->d_df, c->d_shard, c->d_frame, c->d_f32, cnt, trace, fp)
+    hipLaunchKernelGGL((volym_raymarch_kernel<V, COUNT, TRACE, B>), dim3(grid), dim3(256), 0, s.stream, c->d_vol, c->d_imp, s.d_tables, \
+                       s.d_df, d_shard, d_frame, s.d_f32, cnt, trace, fp)
     if (c->kernel_variant >= 1) { if (c->bricked) VOLYM_DIRECT_LAUNCH(1, true); else VOLYM_DIRECT_LAUNCH(1, false); }
     else { if (c->bricked) VOLYM_DIRECT_LAUNCH(0, true); else VOLYM_DIRECT_LAUNCH(0, false); }
 #undef VOLYM_DIRECT_LAUNCH
@@ -1473,7 +1481,7 @@ static int launch_march(volym_ctx* c)
     return VOLYM_OK;
 }
 
-int volym::ctx_launch_march(volym_ctx* c) { return launch_march<false>(c); }
+int volym::ctx_launch_march(volym_ctx* c) { return launch_march<false>(c, c->slot0()); }
 
 extern "C" {
 
@@ -1482,12 +1490,8 @@ int volym_compute_pass(volym_ctx* c)
     if (!c) return VOLYM_E_INVALID;
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_compute_pass: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
-    if (c->twin) {                                  // frames in flight: every other frame goes to the twin's stream and frame buffer
-        volym_ctx* const t = (c->flight_parity++ & 1u) ? c->twin : c;
-        c->last = t;
-        if (t != c) { TWIN_FORWARD(c, launch_march<false>(t)); return VOLYM_OK; }
-    }
-    return launch_march<false>(c);
+    c->last = c->slots[1] ? static_cast<int>(c->flight_parity++ & 1u) : 0;    // frames in flight: the slots take turns
+    return launch_march<false>(c, *c->slots[c->last]);
 }
 
 // Back-pressure of a frame loop: the reference's loop cannot run ahead of the device by more than its swap chain holds
@@ -1509,7 +1513,7 @@ int volym_throttle(volym_ctx* c, uint32_t max_in_flight)
         c->throttle_ev[slot] = nullptr;
         HIPCHK(c, hipEventCreateWithFlags(&c->throttle_ev[slot], hipEventDisableTiming));
     }
-    HIPCHK(c, hipEventRecord(c->throttle_ev[slot], (c->twin && c->last) ? c->last->stream : c->stream));   // the frame just enqueued
+    HIPCHK(c, hipEventRecord(c->throttle_ev[slot], c->slots[c->last]->stream));   // the frame just enqueued
     c->throttle_head++;
     if (c->throttle_head > max_in_flight) {
         const uint32_t old = (c->throttle_head - 1u - max_in_flight) % volym_ctx::THROTTLE_RING;
@@ -1520,13 +1524,13 @@ int volym_throttle(volym_ctx* c, uint32_t max_in_flight)
 
 // The ray-pool kernel (variant 3) bounds every wait it contains and reports a wait that ran out (a bug, never an input) in
 // d_pool_sync[2]; the blocking calls look at it, so that a broken frame is an error and not a picture.  Stream is idle here.
-static int check_pool_error(volym_ctx* c)
+static int check_pool_error(volym_ctx* c, FrameSlot& s)
 {
-    if (!c->pool_launched) return VOLYM_OK;
+    if (!s.pool_launched) return VOLYM_OK;
     uint32_t bits = 0;
-    HIPCHK(c, hipMemcpy(&bits, c->d_pool_sync + 2, sizeof bits, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&bits, s.d_pool_sync + 2, sizeof bits, hipMemcpyDeviceToHost));
     if (bits != 0u) {
-        (void)hipMemset(c->d_pool_sync, 0, 4 * sizeof(uint32_t));
+        (void)hipMemset(s.d_pool_sync, 0, 4 * sizeof(uint32_t));
         return fail(c, VOLYM_E_HIP, "ray-pool kernel gave up waiting (error bits " + std::to_string(bits) + "): the frame is incomplete");
     }
     return VOLYM_OK;
@@ -1535,31 +1539,56 @@ static int check_pool_error(volym_ctx* c)
 int volym_sync(volym_ctx* c)
 {
     if (!c) return VOLYM_E_INVALID;
-    TWIN_FORWARD(c, volym_sync(c->twin));
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return check_pool_error(c);
+    for (int i = c->n_slots() - 1; i >= 0; --i) {
+        HIPCHK(c, hipStreamSynchronize(c->slots[i]->stream));
+        const int rc = check_pool_error(c, *c->slots[i]);
+        if (rc != VOLYM_OK) return rc;
+    }
+    return VOLYM_OK;
+}
+
+int volym_settle(volym_ctx* c)
+{
+    if (!c) return VOLYM_E_INVALID;
+    for (int i = c->n_slots() - 1; i >= 0; --i) {
+        FrameSlot& s = *c->slots[i];
+        feedback_quiesce(s);
+        if (!s.fb_job.error.empty()) { const std::string m = s.fb_job.error; s.fb_job.error.clear(); return fail(c, VOLYM_E_HIP, m); }
+        // ... and run the feedback to its fixed point for the current view: frames of this view (what volym_compute_pass
+        // enqueues) until the list in use is final -- measuring list, deal, re-balancing rounds (raymarch.hip, "cost feedback")
+        if (!c->have_frame || c->kernel_variant < 2 || frame_uses_pool(c, s.fp.flags) || !c->feedback || c->feedback_frozen) continue;
+        for (int round = 0; round < 12; ++round) {
+            const WorkList& wl = s.lists[s.cur];
+            if (wl.entries.empty() || (wl.view_serial == s.view_serial.load(std::memory_order_relaxed) && wl.final_for_view)) break;
+            int rc = launch_march<false>(c, s);
+            if (rc != VOLYM_OK) return rc;
+            feedback_quiesce(s);
+            if (!s.fb_job.error.empty()) { const std::string m = s.fb_job.error; s.fb_job.error.clear(); return fail(c, VOLYM_E_HIP, m); }
+        }
+    }
+    return VOLYM_OK;
 }
 
 int volym_read_rgba8(volym_ctx* c, uint8_t* out)
 {
     if (!c || !out) return VOLYM_E_INVALID;
-    if (c->twin && c->last == c->twin) { TWIN_FORWARD(c, volym_read_rgba8(c->twin, out)); return VOLYM_OK; }
+    FrameSlot& s = *c->slots[c->last];
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_frame, static_cast<size_t>(c->W) * c->H * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return check_pool_error(c);
+    HIPCHK(c, hipMemcpyAsync(out, c->frame_buf(s), static_cast<size_t>(c->W) * c->H * 4, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    return check_pool_error(c, s);
 }
 
 int volym_read_rgba32f(volym_ctx* c, float* out)
 {
     if (!c || !out) return VOLYM_E_INVALID;
-    if (c->twin && c->last == c->twin) { TWIN_FORWARD(c, volym_read_rgba32f(c->twin, out)); return VOLYM_OK; }
-    if (!c->write_f32 || !c->d_f32 || c->world != 1)
+    FrameSlot& s = *c->slots[c->last];
+    if (!c->write_f32 || !s.d_f32 || c->world != 1)
         return fail(c, VOLYM_E_STATE, "volym_read_rgba32f: needs VOLYM_OPT_WRITE_F32 = 1, world == 1 and a rendered frame");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_f32, static_cast<size_t>(c->W) * c->H * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, s.d_f32, static_cast<size_t>(c->W) * c->H * sizeof(float4), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
     return VOLYM_OK;
 }
 
@@ -1567,27 +1596,25 @@ int volym_read_rgba32f(volym_ctx* c, float* out)
 int volym_blit(volym_ctx* c, void* target_rgba8, uint32_t out_w, uint32_t out_h)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (c->twin) {
-        c->last_blit = (c->last == c->twin) ? c->twin : c;
-        if (c->last_blit == c->twin) { TWIN_FORWARD(c, volym_blit(c->twin, target_rgba8, out_w, out_h)); return VOLYM_OK; }
-    }
+    c->last_blit = c->last;
+    FrameSlot& s = *c->slots[c->last_blit];
     if (out_w == 0 || out_h == 0 || out_w > 32768 || out_h > 32768) return fail(c, VOLYM_E_INVALID, "volym_blit: target must be 1..32768 in each dimension");
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t* dst = static_cast<uint32_t*>(target_rgba8);
     if (!dst) {
         // our own target: sized on first use / on a size change (a set-up step: this is the one blocking path of the call)
         const size_t need = static_cast<size_t>(out_w) * out_h * 4;
-        if (need > c->blit_bytes) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->d_blit) { HIPCHK(c, hipFree(c->d_blit)); c->d_blit = nullptr; c->blit_bytes = 0; }
-            hipError_t e = hipMalloc(&c->d_blit, need);
+        if (need > s.blit_bytes) {
+            HIPCHK(c, hipStreamSynchronize(s.stream));
+            if (s.d_blit) { HIPCHK(c, hipFree(s.d_blit)); s.d_blit = nullptr; s.blit_bytes = 0; }
+            hipError_t e = hipMalloc(&s.d_blit, need);
             if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(blit target): ") + hipGetErrorString(e));
-            c->blit_bytes = need;
+            s.blit_bytes = need;
         }
-        dst = c->d_blit;
-        c->blit_w = out_w; c->blit_h = out_h;
+        dst = s.d_blit;
+        s.blit_w = out_w; s.blit_h = out_h;
     }
-    hipLaunchKernelGGL(volym_blit_kernel, dim3((out_w + 63u) / 64u, (out_h + 3u) / 4u), dim3(64, 4), 0, c->stream, c->d_frame, c->W, c->H, dst, out_w, out_h);
+    hipLaunchKernelGGL(volym_blit_kernel, dim3((out_w + 63u) / 64u, (out_h + 3u) / 4u), dim3(64, 4), 0, s.stream, c->frame_buf(s), c->W, c->H, dst, out_w, out_h);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
 }
@@ -1595,40 +1622,40 @@ int volym_blit(volym_ctx* c, void* target_rgba8, uint32_t out_w, uint32_t out_h)
 int volym_read_blit(volym_ctx* c, uint8_t* out)
 {
     if (!c || !out) return VOLYM_E_INVALID;
-    if (c->twin && c->last_blit == c->twin) { TWIN_FORWARD(c, volym_read_blit(c->twin, out)); return VOLYM_OK; }
-    if (!c->d_blit || c->blit_w == 0) return fail(c, VOLYM_E_STATE, "volym_read_blit: no volym_blit into the context's own target yet");
+    FrameSlot& s = *c->slots[c->last_blit];
+    if (!s.d_blit || s.blit_w == 0) return fail(c, VOLYM_E_STATE, "volym_read_blit: no volym_blit into the context's own target yet");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_blit, static_cast<size_t>(c->blit_w) * c->blit_h * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, s.d_blit, static_cast<size_t>(s.blit_w) * s.blit_h * 4, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
     return VOLYM_OK;
 }
 
 uint32_t volym_local_tiles(const volym_ctx* c) { return c ? c->n_local : 0u; }
 size_t volym_shard_bytes(const volym_ctx* c) { return c ? static_cast<size_t>(c->shard_tiles) * 1024u : 0u; }
-// with a twin: the buffers of the latest pass, as volym_read_rgba8 reads them
-void* volym_shard_device_ptr(volym_ctx* c) { return c ? ((c->twin && c->last) ? c->last : c)->d_shard : nullptr; }
-void* volym_frame_device_ptr(volym_ctx* c) { return c ? ((c->twin && c->last) ? c->last : c)->d_frame : nullptr; }
+// the buffers of the latest pass, as volym_read_rgba8 reads them
+void* volym_shard_device_ptr(volym_ctx* c) { return c ? c->shard_buf(*c->slots[c->last]) : nullptr; }
+void* volym_frame_device_ptr(volym_ctx* c) { return c ? c->frame_buf(*c->slots[c->last]) : nullptr; }
 
 int volym_bind_output(volym_ctx* c, void* shard_rgba8, void* frame_rgba8)
 {
     if (!c) return VOLYM_E_INVALID;
-    // takes effect for launches enqueued after this call; earlier launches keep their pointers.  The twin renders into the
-    // same buffers (NULL: each context its own)
-    c->d_shard = shard_rgba8 ? static_cast<uint32_t*>(shard_rgba8) : c->d_shard_own;
-    c->d_frame = frame_rgba8 ? static_cast<uint32_t*>(frame_rgba8) : c->d_frame_own;
-    TWIN_FORWARD(c, volym_bind_output(c->twin, shard_rgba8, frame_rgba8));
+    // takes effect for launches enqueued after this call; earlier launches keep their pointers.  Every slot renders into the
+    // same buffers (NULL: each slot its own)
+    c->bound_shard = static_cast<uint32_t*>(shard_rgba8);
+    c->bound_frame = static_cast<uint32_t*>(frame_rgba8);
     return VOLYM_OK;
 }
 
 int volym_read_shard(volym_ctx* c, uint8_t* out)
 {
-    TWIN_REFUSE(c, "volym_read_shard");
+    if (c && c->slots[1]) return refuse_two_slots(c, "volym_read_shard");
     if (!c || !out) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
     // the padding tile of a short shard is never written by the kernel: define it
     const size_t used = static_cast<size_t>(c->n_local) * 1024u, total = volym_shard_bytes(c);
-    HIPCHK(c, hipMemcpyAsync(out, c->d_shard, used, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->shard_buf(s), used, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
     if (total > used) std::memset(out + used, 0, total - used);
     return VOLYM_OK;
 }
@@ -1641,85 +1668,91 @@ size_t volym_packed_shard_bytes(const volym_ctx* c, uint32_t tiles)
 
 int volym_pack_shard(volym_ctx* c, void* packed, size_t capacity_bytes)
 {
-    TWIN_REFUSE(c, "volym_pack_shard");
+    if (c && c->slots[1]) return refuse_two_slots(c, "volym_pack_shard");
     if (!c || !packed) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     const size_t header = pack_header_bytes(c->shard_tiles);
     if (capacity_bytes < header) return fail(c, VOLYM_E_INVALID, "volym_pack_shard: the buffer does not even hold the header (volym_packed_shard_bytes)");
     HIPCHK(c, hipSetDevice(c->device));
     if (c->n_local == 0) return VOLYM_OK;
     const uint32_t max_slots = static_cast<uint32_t>(std::min<size_t>((capacity_bytes - header) / 1024u, c->shard_tiles));
-    hipLaunchKernelGGL(volym_pack_shard_kernel, dim3(c->n_local), dim3(64), 0, c->stream, c->d_shard, static_cast<uint8_t*>(packed), c->n_local,
-                       c->shard_tiles, max_slots, c->d_pack_counters, c->pack_parity);
+    hipLaunchKernelGGL(volym_pack_shard_kernel, dim3(c->n_local), dim3(64), 0, s.stream, c->shard_buf(s), static_cast<uint8_t*>(packed), c->n_local,
+                       c->shard_tiles, max_slots, s.d_pack_counters, s.pack_parity);
     HIPCHK(c, hipGetLastError());
-    c->pack_parity ^= 1u;
+    s.pack_parity ^= 1u;
     return VOLYM_OK;
 }
 
 int volym_packed_tiles(volym_ctx* c, uint32_t* tiles_used, uint32_t* overflowed)
 {
-    TWIN_REFUSE(c, "volym_packed_tiles");
+    if (c && c->slots[1]) return refuse_two_slots(c, "volym_packed_tiles");
     if (!c || !tiles_used) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
     uint32_t h[4] = {0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(h, c->d_pack_counters, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *tiles_used = h[c->pack_parity ^ 1u];        // the counter the last launch used
+    HIPCHK(c, hipMemcpyAsync(h, s.d_pack_counters, sizeof(h), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    *tiles_used = h[s.pack_parity ^ 1u];        // the counter the last launch used
     if (overflowed) *overflowed = h[2];
     return VOLYM_OK;
 }
 
 int volym_assemble_packed(volym_ctx* c, const void* gathered, size_t stride_bytes)
 {
-    TWIN_REFUSE(c, "volym_assemble_packed");
+    if (c && c->slots[1]) return refuse_two_slots(c, "volym_assemble_packed");
     if (!c || !gathered) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     if (stride_bytes < pack_header_bytes(c->shard_tiles)) return fail(c, VOLYM_E_INVALID, "volym_assemble_packed: stride smaller than the header");
     HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(volym_assemble_packed_kernel, dim3(c->n_tiles), dim3(256), 0, c->stream, static_cast<const uint8_t*>(gathered), stride_bytes,
-                       c->d_frame, c->W, c->H, c->tiles_x, c->n_tiles, c->world, c->shard_tiles);
+    hipLaunchKernelGGL(volym_assemble_packed_kernel, dim3(c->n_tiles), dim3(256), 0, s.stream, static_cast<const uint8_t*>(gathered), stride_bytes,
+                       c->frame_buf(s), c->W, c->H, c->tiles_x, c->n_tiles, c->world, c->shard_tiles);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
 }
 
 int volym_assemble(volym_ctx* c, const void* gathered)
 {
-    TWIN_REFUSE(c, "volym_assemble");
+    if (c && c->slots[1]) return refuse_two_slots(c, "volym_assemble");
     if (!c || !gathered) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(volym_assemble_kernel, dim3(c->n_tiles), dim3(256), 0, c->stream, static_cast<const uint32_t*>(gathered),
-                       c->d_frame, c->W, c->H, c->tiles_x, c->n_tiles, c->world, c->shard_tiles);
+    hipLaunchKernelGGL(volym_assemble_kernel, dim3(c->n_tiles), dim3(256), 0, s.stream, static_cast<const uint32_t*>(gathered),
+                       c->frame_buf(s), c->W, c->H, c->tiles_x, c->n_tiles, c->world, c->shard_tiles);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
 }
 
 int volym_assemble_host(volym_ctx* c, const uint8_t* gathered_host)
 {
-    TWIN_REFUSE(c, "volym_assemble_host");
+    if (c && c->slots[1]) return refuse_two_slots(c, "volym_assemble_host");
     if (!c || !gathered_host) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = volym_shard_bytes(c) * c->world;
-    if (c->gather_tmp_bytes < bytes) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_gather_tmp) { HIPCHK(c, hipFree(c->d_gather_tmp)); c->d_gather_tmp = nullptr; c->gather_tmp_bytes = 0; }
-        hipError_t e = hipMalloc(&c->d_gather_tmp, bytes);
+    if (s.gather_tmp_bytes < bytes) {
+        HIPCHK(c, hipStreamSynchronize(s.stream));
+        if (s.d_gather_tmp) { HIPCHK(c, hipFree(s.d_gather_tmp)); s.d_gather_tmp = nullptr; s.gather_tmp_bytes = 0; }
+        hipError_t e = hipMalloc(&s.d_gather_tmp, bytes);
         if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(gather): ") + hipGetErrorString(e));
-        c->gather_tmp_bytes = bytes;
+        s.gather_tmp_bytes = bytes;
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_gather_tmp, gathered_host, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return volym_assemble(c, c->d_gather_tmp);
+    HIPCHK(c, hipMemcpyAsync(s.d_gather_tmp, gathered_host, bytes, hipMemcpyHostToDevice, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    return volym_assemble(c, s.d_gather_tmp);
 }
 
 int volym_stats_pass(volym_ctx* c, volym_stats* out)
 {
     if (!c || !out) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_stats_pass: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
-    int rc = launch_march<true>(c);
+    HIPCHK(c, hipMemsetAsync(s.d_counters, 0, sizeof(Counters), s.stream));
+    int rc = launch_march<true>(c, s);
     if (rc != VOLYM_OK) return rc;
     Counters h;
-    HIPCHK(c, hipMemcpyAsync(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h, s.d_counters, sizeof h, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
     out->n_vol = h.n_vol; out->n_imp = h.n_imp; out->n_steps = h.n_steps; out->n_dense = h.n_dense; out->n_hit = h.n_hit;
     // every pixel of an owned tile that lies inside the frame launches a ray (wgsl:217-219)
     uint64_t rays = 0;
@@ -1738,16 +1771,17 @@ int volym_stats_pass(volym_ctx* c, volym_stats* out)
 int volym_selftest_ray_setup(volym_ctx* c, unsigned long long out[3])
 {
     if (!c || !out) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_selftest_ray_setup: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
     static_assert(sizeof(Counters) >= 3 * sizeof(unsigned long long), "counters");
-    HIPCHK(c, hipMemsetAsync(c->d_counters, 0, sizeof(Counters), c->stream));
+    HIPCHK(c, hipMemsetAsync(s.d_counters, 0, sizeof(Counters), s.stream));
     const dim3 grid((c->W + 63u) / 64u, (c->H + 3u) / 4u);
-    volym_ray_setup_selftest_kernel<<<grid, 256, 0, c->stream>>>(c->fp, reinterpret_cast<unsigned long long*>(c->d_counters));
+    volym_ray_setup_selftest_kernel<<<grid, 256, 0, s.stream>>>(s.fp, reinterpret_cast<unsigned long long*>(s.d_counters));
     HIPCHK(c, hipGetLastError());
     Counters h;
-    HIPCHK(c, hipMemcpyAsync(&h, c->d_counters, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&h, s.d_counters, sizeof h, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
     out[0] = h.n_vol; out[1] = h.n_imp; out[2] = h.n_steps;
     return VOLYM_OK;
 }
@@ -1755,16 +1789,17 @@ int volym_selftest_ray_setup(volym_ctx* c, unsigned long long out[3])
 int volym_time_batch(volym_ctx* c, uint32_t n, float* ms_total)
 {
     if (!c || !ms_total || n == 0 || n > 1000000) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_time_batch: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { if (e0) (void)hipEventDestroy(e0); return fail(c, VOLYM_E_HIP, "hipEventCreate failed"); }
-    int rc = ensure_frame_resources(c);
+    int rc = ensure_frame_resources(c, s);
     if (rc == VOLYM_OK) {
-        (void)hipEventRecord(e0, c->stream);
-        for (uint32_t i = 0; i < n && rc == VOLYM_OK; ++i) rc = launch_march<false>(c);
-        (void)hipEventRecord(e1, c->stream);
-        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == VOLYM_OK) rc = fail(c, VOLYM_E_HIP, "hipStreamSynchronize failed");
+        (void)hipEventRecord(e0, s.stream);
+        for (uint32_t i = 0; i < n && rc == VOLYM_OK; ++i) rc = launch_march<false>(c, s);
+        (void)hipEventRecord(e1, s.stream);
+        if (hipStreamSynchronize(s.stream) != hipSuccess && rc == VOLYM_OK) rc = fail(c, VOLYM_E_HIP, "hipStreamSynchronize failed");
         if (rc == VOLYM_OK && hipEventElapsedTime(ms_total, e0, e1) != hipSuccess) rc = fail(c, VOLYM_E_HIP, "hipEventElapsedTime failed");
     }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
@@ -1774,20 +1809,21 @@ int volym_time_batch(volym_ctx* c, uint32_t n, float* ms_total)
 int volym_time_passes(volym_ctx* c, uint32_t n, float* ms_each)
 {
     if (!c || !ms_each || n == 0 || n > 100000) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_time_passes: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<hipEvent_t> ev(n + 1, nullptr);
     int rc = VOLYM_OK;
     for (uint32_t i = 0; i <= n && rc == VOLYM_OK; ++i)
         if (hipEventCreate(&ev[i]) != hipSuccess) rc = fail(c, VOLYM_E_HIP, "hipEventCreate failed");
-    if (rc == VOLYM_OK) rc = ensure_frame_resources(c);
+    if (rc == VOLYM_OK) rc = ensure_frame_resources(c, s);
     if (rc == VOLYM_OK) {
-        (void)hipEventRecord(ev[0], c->stream);
+        (void)hipEventRecord(ev[0], s.stream);
         for (uint32_t i = 0; i < n && rc == VOLYM_OK; ++i) {
-            rc = launch_march<false>(c);
-            if (hipEventRecord(ev[i + 1], c->stream) != hipSuccess && rc == VOLYM_OK) rc = fail(c, VOLYM_E_HIP, "hipEventRecord failed");
+            rc = launch_march<false>(c, s);
+            if (hipEventRecord(ev[i + 1], s.stream) != hipSuccess && rc == VOLYM_OK) rc = fail(c, VOLYM_E_HIP, "hipEventRecord failed");
         }
-        if (hipStreamSynchronize(c->stream) != hipSuccess && rc == VOLYM_OK) rc = fail(c, VOLYM_E_HIP, "hipStreamSynchronize failed");
+        if (hipStreamSynchronize(s.stream) != hipSuccess && rc == VOLYM_OK) rc = fail(c, VOLYM_E_HIP, "hipStreamSynchronize failed");
         if (rc == VOLYM_OK)
             for (uint32_t i = 0; i < n; ++i)
                 if (hipEventElapsedTime(&ms_each[i], ev[i], ev[i + 1]) != hipSuccess) { rc = fail(c, VOLYM_E_HIP, "hipEventElapsedTime failed"); break; }
@@ -1803,11 +1839,12 @@ int volym_time_passes(volym_ctx* c, uint32_t n, float* ms_each)
 int volym_dev_pool_timeline(volym_ctx* c, int on, uint32_t* out, uint32_t max_words)
 {
     if (!c) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
     const uint32_t words = std::min(max_words, static_cast<uint32_t>(max_grid(c)) * PL_WAVES * 24u);
-    if (out && words) HIPCHK(c, hipMemcpy(out, c->d_pool_dbg, static_cast<size_t>(words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    c->pool_dbg = on != 0;
+    if (out && words) HIPCHK(c, hipMemcpy(out, s.d_pool_dbg, static_cast<size_t>(words) * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    s.pool_dbg = on != 0;
     return static_cast<int>(words);
 }
 
@@ -1815,20 +1852,22 @@ int volym_dev_pool_timeline(volym_ctx* c, int on, uint32_t* out, uint32_t max_wo
 int volym_dev_counters(volym_ctx* c, unsigned long long out[5], int reset)
 {
     if (!c) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (out) HIPCHK(c, hipMemcpy(out, c->d_counters, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(c, hipMemset(c->d_counters, 0, sizeof(Counters)));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    if (out) HIPCHK(c, hipMemcpy(out, s.d_counters, 5 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(c, hipMemset(s.d_counters, 0, sizeof(Counters)));
     return VOLYM_OK;
 }
 
 int volym_dev_read_costs(volym_ctx* c, uint16_t* out, uint32_t max_items)
 {
     if (!c || !out) return VOLYM_E_INVALID;
-    feedback_quiesce(c);
+    FrameSlot& s = c->slot0();
+    feedback_quiesce(s);
     const uint32_t n = c->n_local * 4u;
-    if (max_items < n || c->item_cost.size() < n) return VOLYM_E_INVALID;
-    std::memcpy(out, c->item_cost.data(), n * sizeof(uint16_t));
+    if (max_items < n || s.item_cost.size() < n) return VOLYM_E_INVALID;
+    std::memcpy(out, s.item_cost.data(), n * sizeof(uint16_t));
     return static_cast<int>(n);
 }
 
@@ -1837,8 +1876,9 @@ int volym_dev_read_costs(volym_ctx* c, uint16_t* out, uint32_t max_items)
 int volym_dev_feedback_timing(volym_ctx* c, double out[6])
 {
     if (!c || !out) return VOLYM_E_INVALID;
-    feedback_quiesce(c);
-    for (int i = 0; i < 6; ++i) out[i] = c->fb_job.t_us[i];
+    FrameSlot& s = c->slot0();
+    feedback_quiesce(s);
+    for (int i = 0; i < 6; ++i) out[i] = s.fb_job.t_us[i];
     return VOLYM_OK;
 }
 
@@ -1846,8 +1886,9 @@ int volym_dev_feedback_timing(volym_ctx* c, double out[6])
 int volym_dev_read_order(volym_ctx* c, uint32_t* out, uint32_t max_items)
 {
     if (!c || !out) return VOLYM_E_INVALID;
-    feedback_quiesce(c);
-    const WorkList& wl = c->lists[c->cur];
+    FrameSlot& s = c->slot0();
+    feedback_quiesce(s);
+    const WorkList& wl = s.lists[s.cur];
     if (max_items < wl.entries.size()) return VOLYM_E_INVALID;
     std::memcpy(out, wl.entries.data(), wl.entries.size() * sizeof(uint32_t));
     return static_cast<int>(wl.entries.size());
@@ -1858,31 +1899,32 @@ int volym_dev_read_order(volym_ctx* c, uint32_t* out, uint32_t max_items)
 int volym_dev_wave_trace(volym_ctx* c, uint32_t* out, uint32_t max_records)
 {
     if (!c || !out) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_dev_wave_trace: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
     // a lone launch on an idle GPU runs at idle clocks: trace the 31st of 31 back-to-back passes
     int rc = VOLYM_OK;
-    for (int i = 0; i < 30 && rc == VOLYM_OK; ++i) rc = launch_march<false, false>(c);
+    for (int i = 0; i < 30 && rc == VOLYM_OK; ++i) rc = launch_march<false, false>(c, s);
     if (rc != VOLYM_OK) return rc;
-    feedback_quiesce(c);
+    feedback_quiesce(s);
     // records: two per wave of the grid that is really launched (variant 2: the list's grid; variants 0/1: 4 waves per tile)
-    const WorkList& wl = c->lists[c->cur];
+    const WorkList& wl = s.lists[s.cur];
     const uint32_t n_items = static_cast<uint32_t>(wl.entries.size());
     const uint32_t pgrid = wl.grid ? wl.grid : std::max(1u, std::min((n_items + PQ_WAVES - 1) / PQ_WAVES, max_grid(c)));
     const uint32_t waves = c->kernel_variant >= 2 ? pgrid * PQ_WAVES : (c->n_local + 64u * 8u) * 4u;   // PQ_WAVES >= every instantiation's WAVES
     const uint32_t records = waves * 2u;
     if (max_records < records) return fail(c, VOLYM_E_INVALID, "volym_dev_wave_trace: buffer too small");
-    HIPCHK(c, hipMalloc(&c->d_trace, static_cast<size_t>(records) * sizeof(uint4)));
-    HIPCHK(c, hipMemsetAsync(c->d_trace, 0, static_cast<size_t>(records) * sizeof(uint4), c->stream));
-    rc = launch_march<false, true>(c);
+    HIPCHK(c, hipMalloc(&s.d_trace, static_cast<size_t>(records) * sizeof(uint4)));
+    HIPCHK(c, hipMemsetAsync(s.d_trace, 0, static_cast<size_t>(records) * sizeof(uint4), s.stream));
+    rc = launch_march<false, true>(c, s);
     if (rc == VOLYM_OK) {
-        hipError_t e = hipMemcpyAsync(out, c->d_trace, static_cast<size_t>(records) * sizeof(uint4), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        hipError_t e = hipMemcpyAsync(out, s.d_trace, static_cast<size_t>(records) * sizeof(uint4), hipMemcpyDeviceToHost, s.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(s.stream);
         if (e != hipSuccess) rc = fail(c, VOLYM_E_HIP, hipGetErrorString(e));
     }
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(c->d_trace);
-    c->d_trace = nullptr;
+    (void)hipStreamSynchronize(s.stream);
+    (void)hipFree(s.d_trace);
+    s.d_trace = nullptr;
     return rc == VOLYM_OK ? static_cast<int>(records) : rc;
 }
 #endif
