@@ -156,6 +156,22 @@ int volym_set_volume(volym_ctx* ctx, const uint8_t* voxels, uint32_t nx, uint32_
 /* GpuImportances::init upload (src/demos/simple/importance.rs:93-131); same dims. */
 int volym_set_importances(volym_ctx* ctx, const uint8_t* importances, uint32_t nx,
                           uint32_t ny, uint32_t nz);
+/* Segment importances on the device (new; the reference maps labels on the host, importance.rs:148-158, and uploads the result).
+ * volym_set_labels: nx*ny*nz label bytes, prepared like the volume (volym_prepare_volume: padded, flipped).  Kept on the device in
+ * the layout the importances get (VOLYM_OPT_VOLUME_LAYOUT / the size rule); one pass counts, per label value, its voxels and
+ * their texel AABB.  Leaves the importances (and whether there are any) as they were.  Label dims must match the volume's
+ * exactly as importances must: volym_update refuses a mismatch.  Blocking set-up call, like volym_set_importances. */
+int volym_set_labels(volym_ctx* ctx, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz);
+/* importance(voxel) = table[label(voxel)] for every voxel, computed on the device into the importance volume the march reads:
+ * the same state as volym_set_importances with the host-mapped bytes (device bytes, important-texel box, work lists).  The box
+ * is the union of the boxes of the labels with table[l] >= 128: no pass over the voxels on the host.  The frames enqueued after
+ * the call use the new importances, with or without a volym_update in between; those enqueued before it the old ones (it waits
+ * for them, in every frame slot).  VOLYM_E_STATE without labels; volym_set_importances drops the labels, so a table after it is
+ * VOLYM_E_STATE as well.  Blocking set-up call, but no upload. */
+int volym_set_segment_importances(volym_ctx* ctx, const uint8_t table[256]);
+/* Voxel count per label value, from the volym_set_labels pass (the reference logs such a histogram, importance.rs:83-91).
+ * VOLYM_E_STATE without labels. */
+int volym_label_counts(volym_ctx* ctx, uint64_t counts[256]);
 /* GPUTransferFunction::new_texture_1d_rgbt upload (src/gpu_resources/transfer_function.rs:36-90):
  * n RGBA8 texels (the reference uses n = 256), Linear/ClampToEdge sampler. */
 int volym_set_transfer_function(volym_ctx* ctx, const uint8_t* rgba8, uint32_t n);

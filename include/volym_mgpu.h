@@ -71,6 +71,8 @@ int volym_mgpu_local_rank(const volym_mgpu* mg, int i);
 /* the volym_set_* / volym_update of volym_hip.h, applied to every local context (the volume is replicated) */
 int volym_mgpu_set_volume(volym_mgpu* mg, const uint8_t* voxels, uint32_t nx, uint32_t ny, uint32_t nz, int filter);
 int volym_mgpu_set_importances(volym_mgpu* mg, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz);
+int volym_mgpu_set_labels(volym_mgpu* mg, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz);
+int volym_mgpu_set_segment_importances(volym_mgpu* mg, const uint8_t table[256]);
 int volym_mgpu_set_transfer_function(volym_mgpu* mg, const uint8_t* rgba8, uint32_t n);
 int volym_mgpu_set_option(volym_mgpu* mg, int key, int value);
 int volym_mgpu_update(volym_mgpu* mg, const volym_camera_uniforms* camera, const volym_parameter_uniforms* parameters);

@@ -143,6 +143,13 @@ struct volym_ctx {
     uint32_t nx = 0, ny = 0, nz = 0;
     uint32_t inx = 0, iny = 0, inz = 0;
     int imp_box_lo[3] = {1, 1, 1}, imp_box_hi[3] = {0, 0, 0};   // texel AABB of the importances >= 128 (lo > hi: none)
+    uint64_t imp_bytes = 0;                  // size of the d_imp allocation
+    // label volume (volym_set_labels): kept in the layout d_imp gets; volym_set_segment_importances maps it into d_imp
+    uint8_t* d_labels = nullptr;
+    uint32_t lnx = 0, lny = 0, lnz = 0;
+    bool labels_bricked = false;
+    uint64_t label_count[256] = {};
+    int label_box[256][6] = {};              // texel AABB {x0, y0, z0, x1, y1, z1} of every label value (count 0: none)
     int filter = VOLYM_FILTER_NEAREST;
     uint8_t lut[256 * 4] = {};
     uint32_t tf_n = 0;

@@ -83,6 +83,44 @@ public:
         ctx.check(volym_update(ctx.handle(), &cam, &par));
     }
     void compute_pass(const GpuContext& ctx) override { ctx.check(volym_compute_pass(ctx.handle())); }   // src/demos/pipeline.rs:62-102
+
+    // New: the label map stays on the device, and set_segments changes segment importances without a host map or an upload.
+    void set_labels(const GpuContext& ctx, const SimpleAssets& a)
+    {
+        std::vector<uint8_t> labels(static_cast<size_t>(a.nx) * a.ny * a.nz);
+        prepare_volume(a.labels_raw.data(), a.labels_raw.size(), a.nx, a.ny, a.nz, true, labels.data());
+        ctx.check(volym_set_labels(ctx.handle(), labels.data(), a.nx, a.ny, a.nz));
+        labels_on_device_ = true;
+    }
+    // The reference maps labels before padding them (importance.rs:148-158), so padding has importance 0 there and table[0]
+    // here: with padding and table[0] != 0 this falls back to the host map (which drops the labels from the device).
+    void set_segments(const GpuContext& ctx, const SimpleAssets& a, const std::vector<SegmentInfo>& segments)
+    {
+        const std::vector<uint8_t> table = segment_table(segments);
+        const size_t n = static_cast<size_t>(a.nx) * a.ny * a.nz;
+        if (a.labels_raw.size() < n && table[0] != 0) {
+            std::vector<uint8_t> mapped(a.labels_raw), imp(n);
+            std::vector<uint8_t> lv, im;
+            for (const SegmentInfo& s : segments) { lv.push_back(s.label_value); im.push_back(s.importance); }
+            map_segments_to_importance(mapped.data(), mapped.size(), lv.data(), im.data(), lv.size());
+            prepare_volume(mapped.data(), mapped.size(), a.nx, a.ny, a.nz, true, imp.data());
+            ctx.check(volym_set_importances(ctx.handle(), imp.data(), a.nx, a.ny, a.nz));
+            labels_on_device_ = false;
+            return;
+        }
+        if (!labels_on_device_) set_labels(ctx, a);
+        ctx.check(volym_set_segment_importances(ctx.handle(), table.data()));
+    }
+    // src/demos/simple/importance.rs:148-158 as a table: the first segment whose label_value matches wins, the default is 0
+    static std::vector<uint8_t> segment_table(const std::vector<SegmentInfo>& segments)
+    {
+        std::vector<uint8_t> t(256, 0);
+        for (size_t i = segments.size(); i-- > 0;) t[segments[i].label_value] = segments[i].importance;
+        return t;
+    }
+
+private:
+    bool labels_on_device_ = false;
 };
 
 }  // namespace volym

@@ -372,6 +372,20 @@ int volym_mgpu_set_importances(volym_mgpu* m, const uint8_t* importances, uint32
     return VOLYM_OK;
 }
 
+int volym_mgpu_set_labels(volym_mgpu* m, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    if (!m) return VOLYM_E_INVALID;
+    for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_labels(L.ctx, labels, nx, ny, nz));
+    return VOLYM_OK;
+}
+
+int volym_mgpu_set_segment_importances(volym_mgpu* m, const uint8_t table[256])
+{
+    if (!m) return VOLYM_E_INVALID;
+    for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_segment_importances(L.ctx, table));
+    return VOLYM_OK;
+}
+
 int volym_mgpu_set_transfer_function(volym_mgpu* m, const uint8_t* rgba8, uint32_t n)
 {
     if (!m) return VOLYM_E_INVALID;

@@ -727,6 +727,18 @@ static int build_macro_cells(volym_ctx* c)
     return VOLYM_OK;
 }
 
+// the look-ahead's reject box (raymarch_device.h ahead_cannot_hit): positions u with clamp(floor(u * n), 0, n - 1) inside the
+// texel AABB of the important voxels, open-ended where the AABB touches the border; 2e-6 covers the rounding of u * n
+static void set_reject_box(const volym_ctx* c, FrameParams& fp)
+{
+    const uint32_t dims[3] = {c->inx, c->iny, c->inz};
+    for (int a = 0; a < 3; ++a) {
+        if (c->imp_box_lo[a] > c->imp_box_hi[a]) { fp.imp_lo[a] = INFINITY; fp.imp_hi[a] = -INFINITY; continue; }
+        fp.imp_lo[a] = c->imp_box_lo[a] <= 0 ? -INFINITY : static_cast<float>(c->imp_box_lo[a]) / static_cast<float>(dims[a]) - 2.0e-6f;
+        fp.imp_hi[a] = c->imp_box_hi[a] >= static_cast<int>(dims[a]) - 1 ? INFINITY : static_cast<float>(c->imp_box_hi[a] + 1) / static_cast<float>(dims[a]) + 2.0e-6f;
+    }
+}
+
 extern "C" {
 
 int volym_abi_version(void) { return VOLYM_ABI_VERSION; }
@@ -872,7 +884,7 @@ void volym_destroy(volym_ctx* c)
     for (int i = 1; i >= 0; --i)
         if (c->slots[i]) free_slot(*c->slots[i]);
     // (every slot's stream is idle now: nothing reads the scene any more)
-    (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_mc);
+    (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }
@@ -1051,12 +1063,18 @@ int volym_set_shard(volym_ctx* c, uint32_t rank, uint32_t world)
     return rebuild_lists(c);
 }
 
+// bytes of a volume in the device layout (without the 16 bytes every allocation of one adds)
+static uint64_t layout_bytes(bool bricked, uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    return bricked ? static_cast<uint64_t>(brick_count(nx)) * brick_count(ny) * brick_count(nz) * 64u : static_cast<uint64_t>(nx) * ny * nz;
+}
+
 static int upload_volume(volym_ctx* c, uint8_t** dst, const uint8_t* src, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     const bool bricked = want_bricked(c, nx, ny, nz);
     if (!src || nx == 0 || ny == 0 || nz == 0) return fail(c, VOLYM_E_INVALID, "volume: NULL data or zero dimension");
     const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
-    const uint64_t nb = bricked ? static_cast<uint64_t>(brick_count(nx)) * brick_count(ny) * brick_count(nz) * 64u : n;
+    const uint64_t nb = layout_bytes(bricked, nx, ny, nz);
     if (nx > 4096 || ny > 4096 || nz > 4096 || nb > 0xffffffffull)
         return fail(c, VOLYM_E_INVALID, "volume: each dimension <= 4096 and the brick-padded size < 2^32");
     const int rc = quiesce_slots(c);
@@ -1134,11 +1152,113 @@ int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx,
 {
     if (!c) return VOLYM_E_INVALID;
     int rc = upload_volume(c, &c->d_imp, importances, nx, ny, nz);
-    if (rc != VOLYM_OK) { c->have_imp = false; return rc; }
+    if (rc != VOLYM_OK) { c->have_imp = false; c->imp_bytes = 0; return rc; }
+    c->imp_bytes = layout_bytes(want_bricked(c, nx, ny, nz), nx, ny, nz) + 16u;
+    // the importances are the caller's now: a segment table has no labels to map any more
+    if (c->d_labels) { HIPCHK(c, hipFree(c->d_labels)); c->d_labels = nullptr; }
     important_texel_box(importances, nx, ny, nz, c->imp_box_lo, c->imp_box_hi);
     c->inx = nx; c->iny = ny; c->inz = nz;
     c->have_imp = true;
     return rebuild_lists(c);
+}
+
+// ---- segment importances on the device ---------------------------------------------------------------------------------
+// The reference maps labels to importances on the host once (importance.rs:148-158) and uploads the result; an edit of one
+// segment's importance would pay that again (a host pass, an upload and a host scan of the whole volume).  Here the labels stay
+// on the device: volym_set_labels uploads them once and counts, per label value, its voxels and their texel AABB;
+// volym_set_segment_importances maps them through a 256-byte table into d_imp (one HBM stream) and takes the important-texel
+// box as the union of the boxes of the labels the table makes important -- exactly what important_texel_box would find.
+
+static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks)
+{
+    const uint64_t g = std::min<uint64_t>((n_chunks + 255u) / 256u, static_cast<uint64_t>(c->n_cus) * 8u);
+    return static_cast<uint32_t>(std::max<uint64_t>(g, 1u));
+}
+
+int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz)
+{
+    if (!c) return VOLYM_E_INVALID;
+    int rc = upload_volume(c, &c->d_labels, labels, nx, ny, nz);      // (quiesces the slots first)
+    if (rc != VOLYM_OK) { if (c->d_labels) (void)hipFree(c->d_labels); c->d_labels = nullptr; return rc; }
+    c->lnx = nx; c->lny = ny; c->lnz = nz;
+    c->labels_bricked = want_bricked(c, nx, ny, nz);
+    const uint64_t n_chunks = (layout_bytes(c->labels_bricked, nx, ny, nz) + 15u) / 16u;
+    // counts, then boxes: lo = INT_MAX, hi = -1 until a voxel says otherwise
+    std::vector<unsigned char> init(256 * sizeof(unsigned long long) + 256 * 6 * sizeof(int));
+    int* boxes = reinterpret_cast<int*>(init.data() + 256 * sizeof(unsigned long long));
+    for (int l = 0; l < 256; ++l)
+        for (int i = 0; i < 6; ++i) boxes[l * 6 + i] = i < 3 ? INT32_MAX : -1;
+    unsigned char* d_stats = nullptr;
+    const hipStream_t stream = c->slot0().stream;
+    hipError_t e = hipMalloc(&d_stats, init.size());
+    if (e == hipSuccess) e = hipMemcpy(d_stats, init.data(), init.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(volym_label_stats_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels),
+                           reinterpret_cast<unsigned long long*>(d_stats), reinterpret_cast<int*>(d_stats + 256 * sizeof(unsigned long long)),
+                           nx, ny, nz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(init.data(), d_stats, init.size(), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d_stats);
+    if (e != hipSuccess) {
+        (void)hipFree(c->d_labels); c->d_labels = nullptr;
+        return fail(c, VOLYM_E_HIP, std::string("volym_set_labels: ") + hipGetErrorString(e));
+    }
+    std::memcpy(c->label_count, init.data(), sizeof c->label_count);
+    std::memcpy(c->label_box, boxes, sizeof c->label_box);
+    return VOLYM_OK;
+}
+
+int volym_set_segment_importances(volym_ctx* c, const uint8_t table[256])
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!table) return fail(c, VOLYM_E_INVALID, "volym_set_segment_importances: NULL table");
+    if (!c->d_labels) return fail(c, VOLYM_E_STATE, "volym_set_segment_importances: no labels (volym_set_labels first; volym_set_importances drops them)");
+    int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
+    const uint64_t nb = layout_bytes(c->labels_bricked, c->lnx, c->lny, c->lnz);
+    if (c->imp_bytes != nb + 16u) {
+        // the importances take the labels' dimensions and layout: a new allocation, whose 16 bytes past the layout stay zero
+        c->have_imp = false;
+        if (c->d_imp) { HIPCHK(c, hipFree(c->d_imp)); c->d_imp = nullptr; }
+        c->imp_bytes = 0;
+        hipError_t e = hipMalloc(&c->d_imp, nb + 16u);
+        if (e == hipSuccess) e = hipMemset(c->d_imp + nb, 0, 16);
+        if (e != hipSuccess) { (void)hipFree(c->d_imp); c->d_imp = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(importances): ") + hipGetErrorString(e)); }
+        c->imp_bytes = nb + 16u;
+    }
+    LabelTable t;
+    std::memcpy(t.v, table, 256);
+    const uint64_t n_chunks = (nb + 15u) / 16u;
+    const hipStream_t stream = c->slot0().stream;
+    hipLaunchKernelGGL(volym_segment_map_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels),
+                       reinterpret_cast<uint4*>(c->d_imp), t, c->lnx, c->lny, c->lnz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(stream));       // every slot's next frame reads the new bytes
+    int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+    for (int l = 0; l < 256; ++l) {
+        if (table[l] < 128u || c->label_count[l] == 0u) continue;
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c->label_box[l][a]); hi[a] = std::max(hi[a], c->label_box[l][3 + a]); }
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (hi[0] < 0) { c->imp_box_lo[a] = 1; c->imp_box_hi[a] = 0; continue; }
+        c->imp_box_lo[a] = lo[a]; c->imp_box_hi[a] = hi[a];
+    }
+    c->inx = c->lnx; c->iny = c->lny; c->inz = c->lnz;
+    c->have_imp = true;
+    // the frames enqueued from here on march the new box, with or without a volym_update in between
+    for (int i = 0; i < c->n_slots(); ++i) set_reject_box(c, c->slots[i]->fp);
+    return rebuild_lists(c);
+}
+
+int volym_label_counts(volym_ctx* c, uint64_t counts[256])
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!counts) return fail(c, VOLYM_E_INVALID, "volym_label_counts: NULL output");
+    if (!c->d_labels) return fail(c, VOLYM_E_STATE, "volym_label_counts: no labels");
+    std::memcpy(counts, c->label_count, sizeof c->label_count);
+    return VOLYM_OK;
 }
 
 int volym_set_transfer_function(volym_ctx* c, const uint8_t* rgba8, uint32_t n)
@@ -1240,16 +1360,7 @@ static int update_slot(volym_ctx* c, FrameSlot& s, const volym_camera_uniforms* 
     fp.nx = c->nx; fp.ny = c->ny; fp.nz = c->nz;
     fp.tiles_x = c->tiles_x; fp.n_tiles = c->n_tiles;
     fp.tf_n = c->tf_n;
-    {
-        // the look-ahead's reject box (raymarch_device.h ahead_cannot_hit): positions u with clamp(floor(u * n), 0, n - 1) inside the
-        // texel AABB of the important voxels, open-ended where the AABB touches the border; 2e-6 covers the rounding of u * n
-        const uint32_t dims[3] = {c->inx, c->iny, c->inz};
-        for (int a = 0; a < 3; ++a) {
-            if (c->imp_box_lo[a] > c->imp_box_hi[a]) { fp.imp_lo[a] = INFINITY; fp.imp_hi[a] = -INFINITY; continue; }
-            fp.imp_lo[a] = c->imp_box_lo[a] <= 0 ? -INFINITY : static_cast<float>(c->imp_box_lo[a]) / static_cast<float>(dims[a]) - 2.0e-6f;
-            fp.imp_hi[a] = c->imp_box_hi[a] >= static_cast<int>(dims[a]) - 1 ? INFINITY : static_cast<float>(c->imp_box_hi[a] + 1) / static_cast<float>(dims[a]) + 2.0e-6f;
-        }
-    }
+    set_reject_box(c, fp);
     const float sigma = 1.5f;            // wgsl:255
     for (int i = -2; i <= 2; ++i) {
         const float x = static_cast<float>(i) * 0.005f;

@@ -590,6 +590,127 @@ __global__ __launch_bounds__(256) void volym_rebrick_kernel(const uint8_t* __res
     bricked[o] = v;
 }
 
+// ---- segment importances from a label volume on the device (volym_set_labels / volym_set_segment_importances) ----
+// Both kernels walk the device layout of the labels (linear, or the 4x4x4 bricks of volym_rebrick_kernel) in 16-byte chunks,
+// one chunk per lane and step.  Byte b of chunk k is a voxel of the volume or padding: linear, bytes past the last voxel;
+// bricked, the bytes of a brick outside nx x ny x nz.  In a bricked chunk z is fixed and (x, y) is a 4x4 patch.
+struct LabelTable { uint8_t v[256]; };
+
+__device__ __forceinline__ void label_chunk_origin(bool bricked, uint32_t k, uint32_t nx, uint32_t ny, uint32_t& x, uint32_t& y, uint32_t& z)
+{
+    if (bricked) {
+        const uint32_t bx = brick_count(nx), by = brick_count(ny), brick = k >> 2;
+        x = (brick % bx) * 4u; y = ((brick / bx) % by) * 4u; z = (brick / (bx * by)) * 4u + (k & 3u);
+    } else {
+        const uint32_t o = k * 16u, slab = nx * ny;
+        z = o / slab; y = (o - z * slab) / nx; x = o - z * slab - y * nx;
+    }
+}
+
+// bit b set: byte b of chunk k is a voxel of the volume
+__device__ __forceinline__ uint32_t label_chunk_inside(bool bricked, uint32_t k, uint32_t nx, uint32_t ny, uint32_t nz, uint64_t n)
+{
+    if (!bricked) {
+        const uint64_t o = static_cast<uint64_t>(k) * 16u;
+        return o + 16u <= n ? 0xffffu : (1u << static_cast<uint32_t>(n - o)) - 1u;
+    }
+    uint32_t x, y, z;
+    label_chunk_origin(true, k, nx, ny, x, y, z);
+    if (z >= nz) return 0u;
+    const uint32_t wx = nx - x < 4u ? nx - x : 4u, wy = ny - y < 4u ? ny - y : 4u;
+    const uint32_t row = (1u << wx) - 1u;
+    uint32_t m = 0;
+    for (uint32_t r = 0; r < wy; ++r) m |= row << (4u * r);
+    return m;
+}
+
+// imp[i] = table[labels[i]] for the voxels, 0 for the padding (what volym_rebrick_kernel leaves there): 16 bytes in, 16 out per
+// lane, the table in LDS.  n_chunks = ceil(layout bytes / 16); both buffers hold n_chunks * 16 bytes (the allocations end 16
+// bytes past the layout).  Grid-stride, two chunks in flight per lane.
+__global__ __launch_bounds__(256) void volym_segment_map_kernel(const uint4* __restrict__ labels, uint4* __restrict__ imp, LabelTable table,
+                                                                uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_chunks)
+{
+    __shared__ uint8_t s_tab[256];
+    s_tab[threadIdx.x] = table.v[threadIdx.x];
+    __syncthreads();
+    const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
+    const uint32_t stride = gridDim.x * 256u;
+    auto map = [&](uint4 v, uint32_t inside) {
+        uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            uint32_t o = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (inside & (1u << (4 * j + b))) o |= static_cast<uint32_t>(s_tab[(w[j] >> (8 * b)) & 0xffu]) << (8 * b);
+            w[j] = o;
+        }
+        return make_uint4(w[0], w[1], w[2], w[3]);
+    };
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += 2u * stride) {
+        const uint32_t k2 = k + stride;
+        const uint4 a = labels[k];
+        const uint4 b = k2 < n_chunks ? labels[k2] : make_uint4(0u, 0u, 0u, 0u);
+        imp[k] = map(a, label_chunk_inside(bricked != 0u, k, nx, ny, nz, n));
+        if (k2 < n_chunks) imp[k2] = map(b, label_chunk_inside(bricked != 0u, k2, nx, ny, nz, n));
+    }
+}
+
+// Voxel count and texel AABB of every label value, in the coordinates of the volume (x fastest), whatever the layout.
+// stats: 256 u64 counts, then 256 x {x0, y0, z0, x1, y1, z1} (the caller initialises lo = INT_MAX, hi = -1).
+// A lane carries one run of equal labels through its voxels and flushes it to LDS when the label changes; most voxels carry
+// one or two labels, so the flushes are few.  Each workgroup then adds its LDS totals to the global ones once per label.
+__global__ __launch_bounds__(256) void volym_label_stats_kernel(const uint4* __restrict__ labels, unsigned long long* __restrict__ counts,
+                                                                int* __restrict__ boxes, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                                uint32_t bricked, uint32_t n_chunks)
+{
+    __shared__ uint32_t s_cnt[256];
+    __shared__ int s_box[256 * 6];
+    s_cnt[threadIdx.x] = 0u;
+    for (int i = 0; i < 6; ++i) s_box[threadIdx.x * 6 + i] = i < 3 ? INT32_MAX : -1;
+    __syncthreads();
+    const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
+    uint32_t cur = 256u, cnt = 0;                 // 256: no run yet
+    int bx0 = 0, by0 = 0, bz0 = 0, bx1 = 0, by1 = 0, bz1 = 0;
+    auto flush = [&]() {
+        if (cur > 255u) return;
+        atomicAdd(&s_cnt[cur], cnt);
+        int* b = &s_box[cur * 6];
+        atomicMin(&b[0], bx0); atomicMin(&b[1], by0); atomicMin(&b[2], bz0);
+        atomicMax(&b[3], bx1); atomicMax(&b[4], by1); atomicMax(&b[5], bz1);
+    };
+    for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n_chunks; k += gridDim.x * 256u) {
+        const uint4 v = labels[k];
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t inside = label_chunk_inside(bricked != 0u, k, nx, ny, nz, n);
+        uint32_t x0, y0, z0;
+        label_chunk_origin(bricked != 0u, k, nx, ny, x0, y0, z0);
+        int x = static_cast<int>(x0), y = static_cast<int>(y0), z = static_cast<int>(z0);
+        for (uint32_t i = 0; i < 16u; ++i) {
+            if (bricked) { x = static_cast<int>(x0 + (i & 3u)); y = static_cast<int>(y0 + (i >> 2)); }
+            if (inside & (1u << i)) {
+                const uint32_t l = (w[i >> 2] >> (8u * (i & 3u))) & 0xffu;
+                if (l != cur) {
+                    flush();
+                    cur = l; cnt = 0;
+                    bx0 = bx1 = x; by0 = by1 = y; bz0 = bz1 = z;
+                }
+                ++cnt;
+                bx0 = min(bx0, x); bx1 = max(bx1, x); by0 = min(by0, y); by1 = max(by1, y); bz0 = min(bz0, z); bz1 = max(bz1, z);
+            }
+            if (!bricked && ++x == static_cast<int>(nx)) { x = 0; if (++y == static_cast<int>(ny)) { y = 0; ++z; } }
+        }
+    }
+    flush();
+    __syncthreads();
+    const uint32_t l = threadIdx.x;
+    if (s_cnt[l] != 0u) {
+        atomicAdd(&counts[l], static_cast<unsigned long long>(s_cnt[l]));
+        for (int i = 0; i < 3; ++i) atomicMin(&boxes[l * 6 + i], s_box[l * 6 + i]);
+        for (int i = 3; i < 6; ++i) atomicMax(&boxes[l * 6 + i], s_box[l * 6 + i]);
+    }
+}
+
 // root side of the image gather: world shards of 16x16 tiles -> W x H raster
 __global__ __launch_bounds__(256) void volym_assemble_kernel(const uint32_t* __restrict__ gathered, uint32_t* __restrict__ raster,
                                                              uint32_t W, uint32_t H, uint32_t tiles_x, uint32_t n_tiles,

@@ -93,6 +93,25 @@ class GpuContext:
         t = np.ascontiguousarray(rgba8, np.uint8).ravel()
         self._ck(_lib.lib().volym_set_transfer_function(self.handle, scene._u8p(t), t.size // 4))
 
+    def set_labels(self, labels, dims):
+        """Prepared label bytes (scene.prepare_volume), kept on the device for set_segment_importances."""
+        v = np.ascontiguousarray(labels, np.uint8).ravel()
+        nx, ny, nz = dims
+        if v.size != nx * ny * nz:
+            raise ValueError("labels have %d bytes, dims say %d" % (v.size, nx * ny * nz))
+        self._ck(_lib.lib().volym_set_labels(self.handle, scene._u8p(v), nx, ny, nz))
+
+    def set_segment_importances(self, table):
+        """importance = table[label] for every voxel, on the device (table: 256 bytes, scene.segment_table)."""
+        t = scene.check_segment_table(table)
+        self._ck(_lib.lib().volym_set_segment_importances(self.handle, scene._u8p(t)))
+
+    def label_counts(self):
+        """Voxels per label value of the labels on the device (np.uint64[256])."""
+        out = np.zeros(256, np.uint64)
+        self._ck(_lib.lib().volym_label_counts(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return out
+
     # ---- per frame --------------------------------------------------------------------------
     def update(self, camera_uniforms, parameter_uniforms):
         self._ck(_lib.lib().volym_update(self.handle, C.byref(camera_uniforms), C.byref(parameter_uniforms)))
@@ -247,3 +266,28 @@ class Simple(ComputeDemo):
     def compute_pass(self, ctx):
         """BaseDemo::compute_pass -> DemoPipeline::compute_pass (src/demos/pipeline.rs:62-102, :214-225)"""
         ctx.compute_pass()
+
+    def set_labels(self, ctx, labels_raw):
+        """Keep the label map on the device (new; the reference maps it once on the host), so that set_segments can change
+        segment importances without mapping or uploading the volume again."""
+        labels_raw = np.ascontiguousarray(labels_raw, np.uint8).ravel()
+        ctx.set_labels(scene.prepare_volume(labels_raw, self.dims, flip_y=True), self.dims)
+        self._labels_raw = labels_raw
+        self._labels_on_device = True
+
+    def set_segments(self, ctx, segments):
+        """New segment importances for the labels of set_labels (an editor's "show me the lobster instead of the cup").
+        The table runs on the device.  One case differs from the reference's flow: it maps labels BEFORE padding them to the
+        volume (importance.rs:148-158, then volume.rs:38-61), so the padding of a label file shorter than the volume has
+        importance 0 there, table[0] here.  When that matters (table[0] != 0 and padding exists) the host map runs instead."""
+        segments = scene.load_segments(segments)
+        table = scene.segment_table(segments)
+        padded = self._labels_raw.size < self.dims[0] * self.dims[1] * self.dims[2]
+        if padded and table[0] != 0:
+            importances = scene.map_segments_to_importance(self._labels_raw, segments)
+            ctx.set_importances(scene.prepare_volume(importances, self.dims, flip_y=True), self.dims)   # (drops the labels)
+            self._labels_on_device = False
+            return
+        if not self._labels_on_device:
+            self.set_labels(ctx, self._labels_raw)
+        ctx.set_segment_importances(table)

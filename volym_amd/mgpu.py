@@ -38,6 +38,8 @@ SIGNATURES = {
     "volym_mgpu_local_rank": (C.c_int, [_mg, C.c_int]),
     "volym_mgpu_set_volume": (C.c_int, [_mg, _u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]),
     "volym_mgpu_set_importances": (C.c_int, [_mg, _u8p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "volym_mgpu_set_labels": (C.c_int, [_mg, _u8p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "volym_mgpu_set_segment_importances": (C.c_int, [_mg, _u8p]),
     "volym_mgpu_set_transfer_function": (C.c_int, [_mg, _u8p, C.c_uint32]),
     "volym_mgpu_set_option": (C.c_int, [_mg, C.c_int, C.c_int]),
     "volym_mgpu_update": (C.c_int, [_mg, C.POINTER(_lib.CameraUniforms), C.POINTER(_lib.ParameterUniforms)]),
@@ -127,6 +129,16 @@ class MultiGpu:
     def set_importances(self, importances, dims):
         v = np.ascontiguousarray(importances, np.uint8).ravel()
         self._ck(lib().volym_mgpu_set_importances(self._h, scene._u8p(v), dims[0], dims[1], dims[2]))
+
+    def set_labels(self, labels, dims):
+        v = np.ascontiguousarray(labels, np.uint8).ravel()
+        if v.size != dims[0] * dims[1] * dims[2]:
+            raise ValueError("labels have %d bytes, dims say %d" % (v.size, dims[0] * dims[1] * dims[2]))
+        self._ck(lib().volym_mgpu_set_labels(self._h, scene._u8p(v), dims[0], dims[1], dims[2]))
+
+    def set_segment_importances(self, table):
+        t = scene.check_segment_table(table)
+        self._ck(lib().volym_mgpu_set_segment_importances(self._h, scene._u8p(t)))
 
     def set_transfer_function(self, rgba8):
         t = np.ascontiguousarray(rgba8, np.uint8).ravel()

@@ -179,6 +179,22 @@ def load_segments(path_or_list):
     return segs
 
 
+def segment_table(segments):
+    """The 256-byte label -> importance table of map_segments_to_importance (src/demos/simple/importance.rs:148-158): the
+    first segment whose label_value matches wins, labels no segment names get 0."""
+    table = np.zeros(256, np.uint8)
+    for s in reversed(list(segments)):
+        table[s["label_value"]] = s["importance"]
+    return table
+
+
+def check_segment_table(table):
+    t = np.ascontiguousarray(table, np.uint8).ravel()
+    if t.size != 256:
+        raise ValueError("a segment table has 256 entries, not %d" % t.size)
+    return t
+
+
 def map_segments_to_importance(labels, segments):
     """src/demos/simple/importance.rs:148-158"""
     data = np.array(labels, np.uint8, copy=True).ravel()
