@@ -86,6 +86,8 @@ struct FrameSlot {
     uint32_t view_launches = 0;              // launches since the view last changed
     float mask_clip[16] = {};                // world -> clip of the view (f32 copy for the mask kernel)
     float mask_margin = 0.0f;
+    uint32_t* d_tile_depth = nullptr;        // per 8x8 tile: the depth range of its occupied cells (FrameParams::tile_depth), 64 words per
+                                             // mask word; zeroed and rebuilt in stream order with each view's mask
     int* d_aabb = nullptr;                   // written by the distance-field kernel (kept for the dev tools)
 
     uint32_t* d_shard_own = nullptr;
@@ -161,6 +163,7 @@ struct volym_ctx {
     uint32_t mc_n = 32;
     uint32_t tile_mask_words = 0;            // 0: the frame has more tiles than the mask kernel holds in LDS -- no mask
     bool tile_mask = true;                   // dev switch
+    bool tile_depth = true;                  // dev switch: per-tile depth bounds with the mask
     bool mask_eager = false;                 // dev
 
     // bound by volym_bind_output (NULL: each slot renders into its own)

@@ -776,6 +776,7 @@ static int init_slot(volym_ctx* c, FrameSlot& s)
     if ((e = hipMalloc(&s.d_aabb, 6 * sizeof(int))) != hipSuccess) return bad(e, "hipMalloc(aabb)");
     if (c->tile_mask_words && (e = hipMalloc(&s.d_tile_mask, 2u * c->tile_mask_words * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(tile mask)");
     if (c->tile_mask_words && (e = hipMemset(s.d_tile_mask, 0, 2u * c->tile_mask_words * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMemset(tile mask)");
+    if (c->tile_mask_words && (e = hipMalloc(&s.d_tile_depth, 64u * static_cast<size_t>(c->tile_mask_words) * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(tile depth)");
     if ((e = hipMalloc(&s.d_pack_counters, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(pack counters)");
     if ((e = hipMemset(s.d_pack_counters, 0, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMemset(pack counters)");
     if ((e = hipMalloc(&s.d_pool_sync, 4 * sizeof(uint32_t))) != hipSuccess) return bad(e, "hipMalloc(pool sync)");
@@ -815,6 +816,7 @@ static void free_slot(FrameSlot& s)
     (void)hipFree(s.d_tables); (void)hipFree(s.d_df);
     (void)hipFree(s.d_shard_own); (void)hipFree(s.d_frame_own); (void)hipFree(s.d_f32); (void)hipFree(s.d_blit);
     (void)hipFree(s.d_gather_tmp); (void)hipFree(s.d_pack_counters); (void)hipFree(s.d_counters); (void)hipFree(s.d_aabb); (void)hipFree(s.d_tile_mask);
+    (void)hipFree(s.d_tile_depth);
     (void)hipFree(s.d_list[0]); (void)hipFree(s.d_list[1]); (void)hipFree(s.d_cost);
     (void)hipFree(s.d_pool_sync); (void)hipFree(s.d_pool_dbg);
     if (s.h_list_pinned) (void)hipHostFree(s.h_list_pinned);
@@ -1035,6 +1037,10 @@ int volym_set_option(volym_ctx* c, int key, int value)
     case 122:   // 1: the speculative voxel fetches of the common instantiation through LDS-staged bricks (raymarch_pq.h LB; bricked layout)
         c->lds_bricks = value != 0;
         return VOLYM_OK;
+    case 123:   // 0: no per-tile depth bounds with the mask (raymarch_pq.h), 1 (default): bounds
+        c->tile_depth = value != 0;
+        for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->hull_dirty = true;
+        return rebuild_lists(c);
     case 117:   // 0: no per-view tile mask (the hulls and the AABB clip stay); 2: a mask for every view, on its first frame
         c->tile_mask = value != 0;
         c->mask_eager = value == 2;
@@ -1290,6 +1296,7 @@ static int ensure_frame_resources(volym_ctx* c, FrameSlot& s)
     if (s.hull_dirty) {
         compute_culling(c, s);
         s.fp.tile_mask = nullptr;
+        s.fp.tile_depth = nullptr;
         s.fp.mask_words = c->tile_mask_words;
         s.fp.tile_mask_spare = s.d_tile_mask ? s.d_tile_mask + static_cast<size_t>(s.mask_cur ^ 1) * c->tile_mask_words : nullptr;
         s.mask_pending = s.mask_wanted;
@@ -1319,6 +1326,18 @@ static int ensure_frame_resources(volym_ctx* c, FrameSlot& s)
         HIPCHK(c, hipGetLastError());
         s.fp.tile_mask = cur;
         s.fp.cull |= CULL_TILE_MASK;
+        if (c->tile_depth && s.d_tile_depth) {
+            // the same cells' depth ranges per tile (raymarch_kernels.h volym_tile_depth_kernel): one buffer per slot, rewritten in stream
+            // order behind the launches that read the last view's
+            const uint32_t n_t8 = 32u * c->tile_mask_words;
+            HIPCHK(c, hipMemsetAsync(s.d_tile_depth, 0, 2u * static_cast<size_t>(n_t8) * sizeof(uint32_t), s.stream));
+            const uint32_t nb = (c->mc_n + 7u) / 8u;
+            hipLaunchKernelGGL(volym_tile_depth_kernel, dim3(nb * nb * ((c->mc_n + 3u) / 4u)), dim3(256), 0, s.stream, c->d_mc, c->mc_n, s.thr_byte_cull, M,
+                               s.mask_margin, s.fp.eye[0], s.fp.eye[1], s.fp.eye[2], c->W, c->H, c->tiles_x * 2u, n_t8, s.d_tile_depth);
+            HIPCHK(c, hipGetLastError());
+            s.fp.tile_depth = s.d_tile_depth;
+            s.fp.cull |= CULL_TILE_DEPTH;
+        }
         s.fp.tile_mask_spare = s.d_tile_mask + static_cast<size_t>(s.mask_cur ^ 1) * c->tile_mask_words;
         s.mask_pending = false;
         // costs measured before the mask existed describe tiles that are constant from here on: for the cost feedback this is a

@@ -63,6 +63,9 @@ struct FrameParams {
                                  // meet anything dense
     uint32_t* tile_mask_spare;   // the mask buffer this view does not use: every launch zeroes it for the next view's mask kernel
     uint32_t mask_words;
+    const uint32_t* tile_depth;  // CULL_TILE_DEPTH: per 8x8 tile (index as tile_mask), words [0, 32 * mask_words): ~bits(near), then
+                                 // [32 * mask_words, 64 * mask_words): bits(far) -- no sample of the tile's rays outside [near, far] can be
+                                 // dense (volym_tile_depth_kernel, with the mask); both words 0: no occupied cell projects onto the tile
     float rcp_w, rcp_h;          // RN(1 / W), RN(1 / H): make_ray's pixel quotients (raymarch_device.h div_pixel)
     float setup_lo;              // 2^-40 when make_ray may share reciprocals between its divisions, +inf when it must not (volym_update)
     uint32_t rect[4];            // variant 3: the screen rectangle {x0, y0, x1, y1} (pixels, whole 64x32 superblocks, x1/y1 may pass the frame) outside of
@@ -85,6 +88,7 @@ enum : uint32_t {
     CULL_AABB = 1u << 2,        // aabb_lo/hi are valid: no sample outside it can reach the threshold
     CULL_NOTHING_DENSE = 1u << 3,   // no macro cell can reach the threshold at all
     CULL_TILE_MASK = 1u << 4,   // tile_mask is valid for this view
+    CULL_TILE_DEPTH = 1u << 5,  // tile_depth is valid for this view (only together with CULL_TILE_MASK)
 };
 
 // Per-(transfer function, parameters) tables, built on the host with the same wgsl_math.h

@@ -404,6 +404,47 @@ __global__ __launch_bounds__(1024) void volym_distance_field_kernel(const uint8_
 // its corners in front of the eye: CULL_OBJ_HULL); a cell with a corner that is not sets every bit.
 struct ClipMatrix { float m[16]; };   // world -> clip, column-major
 constexpr uint32_t VOLYM_TILE_MASK_MAX_WORDS = 1u << 20;     // 32 M tiles of 8x8 pixels
+// The 8x8 tiles [tx0, tx1] x [ty0, ty1] with a pixel inside the projection of macro cell (cx, cy, cz): its box grown by `margin` in
+// texture space, the bounding rectangle of its eight corners grown by 1.5 pixels.  on: some pixel of the frame is inside; bad: a corner
+// is not in front of the eye (or projects to NaN).  The mask kernels and volym_tile_depth_kernel share it: same cells, same tiles.
+struct CellRect { uint32_t tx0, ty0, tx1, ty1; bool on, bad; };
+__device__ __forceinline__ void cell_box(uint32_t cx, uint32_t cy, uint32_t cz, uint32_t mc_n, float margin, float lo[3], float hi[3])
+{
+    const float inv = 1.0f / static_cast<float>(mc_n);
+    lo[0] = static_cast<float>(cx) * inv - margin; lo[1] = static_cast<float>(cy) * inv - margin; lo[2] = static_cast<float>(cz) * inv - margin;
+    hi[0] = static_cast<float>(cx + 1u) * inv + margin; hi[1] = static_cast<float>(cy + 1u) * inv + margin; hi[2] = static_cast<float>(cz + 1u) * inv + margin;
+}
+__device__ __forceinline__ CellRect cell_tile_rect(const ClipMatrix& M, uint32_t cx, uint32_t cy, uint32_t cz, uint32_t mc_n, float margin, uint32_t W, uint32_t H)
+{
+    const float fw = static_cast<float>(W), fh = static_cast<float>(H);
+    float lo[3], hi[3];
+    cell_box(cx, cy, cz, mc_n, margin, lo, hi);
+    float px0 = 3.0e38f, px1 = -3.0e38f, py0 = 3.0e38f, py1 = -3.0e38f;
+    CellRect r = {0u, 0u, 0u, 0u, false, false};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
+        const float qx = M.m[0] * x + M.m[4] * y + M.m[8] * z + M.m[12];
+        const float qy = M.m[1] * x + M.m[5] * y + M.m[9] * z + M.m[13];
+        const float qw = M.m[3] * x + M.m[7] * y + M.m[11] * z + M.m[15];
+        if (!(qw > 0.0f)) r.bad = true;
+        const float iw = 1.0f / qw;
+        const float sx = (qx * iw + 1.0f) * 0.5f * fw, sy = (1.0f - qy * iw) * 0.5f * fh;
+        if (!(sx == sx) || !(sy == sy)) r.bad = true;
+        px0 = fminf(px0, sx); px1 = fmaxf(px1, sx); py0 = fminf(py0, sy); py1 = fmaxf(py1, sy);
+    }
+    if (r.bad) return r;
+    // pixels (integer points) inside the grown rectangle; a relative 1e-5 for the f32 projection
+    const float gx = 1.5f + 1.0e-5f * fw, gy = 1.5f + 1.0e-5f * fh;
+    const float fx0 = fmaxf(ceilf(px0 - gx), 0.0f), fx1 = fminf(floorf(px1 + gx), fw - 1.0f);
+    const float fy0 = fmaxf(ceilf(py0 - gy), 0.0f), fy1 = fminf(floorf(py1 + gy), fh - 1.0f);
+    r.on = fx0 <= fx1 && fy0 <= fy1;
+    if (r.on) {
+        r.tx0 = static_cast<uint32_t>(fx0) >> 3; r.tx1 = static_cast<uint32_t>(fx1) >> 3;
+        r.ty0 = static_cast<uint32_t>(fy0) >> 3; r.ty1 = static_cast<uint32_t>(fy1) >> 3;
+    }
+    return r;
+}
 // volym_selftest_ray_setup: one pixel per thread (64 x 4 pixels per workgroup, a wave = 64 pixels of a row)
 __global__ __launch_bounds__(256) void volym_ray_setup_selftest_kernel(FrameParams fp, unsigned long long* __restrict__ out)
 {
@@ -435,36 +476,14 @@ __global__ __launch_bounds__(256) void volym_tile_mask_kernel(const uint8_t* __r
     const uint32_t cell = blockIdx.x * 256u + threadIdx.x;
     const uint32_t cells = mc_n * mc_n * mc_n;
     if (cell >= cells || mc_max[cell] < thr_byte) return;
-    const float inv = 1.0f / static_cast<float>(mc_n);
-    const float fw = static_cast<float>(W), fh = static_cast<float>(H);
     const uint32_t cx = cell % mc_n, cy = (cell / mc_n) % mc_n, cz = cell / (mc_n * mc_n);
-    const float lo[3] = {static_cast<float>(cx) * inv - margin, static_cast<float>(cy) * inv - margin, static_cast<float>(cz) * inv - margin};
-    const float hi[3] = {static_cast<float>(cx + 1u) * inv + margin, static_cast<float>(cy + 1u) * inv + margin, static_cast<float>(cz + 1u) * inv + margin};
-    float px0 = 3.0e38f, px1 = -3.0e38f, py0 = 3.0e38f, py1 = -3.0e38f;
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
-        const float qx = M.m[0] * x + M.m[4] * y + M.m[8] * z + M.m[12];
-        const float qy = M.m[1] * x + M.m[5] * y + M.m[9] * z + M.m[13];
-        const float qw = M.m[3] * x + M.m[7] * y + M.m[11] * z + M.m[15];
-        if (!(qw > 0.0f)) bad = true;
-        const float iw = 1.0f / qw;
-        const float sx = (qx * iw + 1.0f) * 0.5f * fw, sy = (1.0f - qy * iw) * 0.5f * fh;
-        if (!(sx == sx) || !(sy == sy)) bad = true;
-        px0 = fminf(px0, sx); px1 = fmaxf(px1, sx); py0 = fminf(py0, sy); py1 = fmaxf(py1, sy);
-    }
-    if (bad) {                                   // cannot happen under CULL_OBJ_HULL; be safe: everything is marched
+    const CellRect r = cell_tile_rect(M, cx, cy, cz, mc_n, margin, W, H);
+    if (r.bad) {                                 // cannot happen under CULL_OBJ_HULL; be safe: everything is marched
         for (uint32_t i = 0; i < n_words; ++i) atomicOr(&out[i], 0xffffffffu);
         return;
     }
-    // pixels (integer points) inside the grown rectangle; a relative 1e-5 for the f32 projection
-    const float gx = 1.5f + 1.0e-5f * fw, gy = 1.5f + 1.0e-5f * fh;
-    const float fx0 = fmaxf(ceilf(px0 - gx), 0.0f), fx1 = fminf(floorf(px1 + gx), fw - 1.0f);
-    const float fy0 = fmaxf(ceilf(py0 - gy), 0.0f), fy1 = fminf(floorf(py1 + gy), fh - 1.0f);
-    if (!(fx0 <= fx1) || !(fy0 <= fy1)) return;          // off screen
-    const uint32_t tx0 = static_cast<uint32_t>(fx0) >> 3, tx1 = static_cast<uint32_t>(fx1) >> 3;
-    const uint32_t ty0 = static_cast<uint32_t>(fy0) >> 3, ty1 = static_cast<uint32_t>(fy1) >> 3;
+    if (!r.on) return;                           // off screen
+    const uint32_t tx0 = r.tx0, tx1 = r.tx1, ty0 = r.ty0, ty1 = r.ty1;
     for (uint32_t ty = ty0; ty <= ty1; ++ty) {
         // the bits tx0..tx1 of row ty, word by word
         uint32_t bit = ty * t8x + tx0;
@@ -497,33 +516,12 @@ __global__ __launch_bounds__(256) void volym_tile_mask_lds_kernel(const uint8_t*
     const uint32_t cx = bx * 8u + (threadIdx.x & 7u), cy = by * 8u + ((threadIdx.x >> 3) & 7u), cz = bz * 4u + (threadIdx.x >> 6);
     bool all_bits = false;
     if (cx < mc_n && cy < mc_n && cz < mc_n && mc_max[cx + mc_n * (cy + mc_n * cz)] >= thr_byte) {
-        const float inv = 1.0f / static_cast<float>(mc_n);
-        const float fw = static_cast<float>(W), fh = static_cast<float>(H);
-        const float lo[3] = {static_cast<float>(cx) * inv - margin, static_cast<float>(cy) * inv - margin, static_cast<float>(cz) * inv - margin};
-        const float hi[3] = {static_cast<float>(cx + 1u) * inv + margin, static_cast<float>(cy + 1u) * inv + margin, static_cast<float>(cz + 1u) * inv + margin};
-        float px0 = 3.0e38f, px1 = -3.0e38f, py0 = 3.0e38f, py1 = -3.0e38f;
-        bool bad = false;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
-            const float qx = M.m[0] * x + M.m[4] * y + M.m[8] * z + M.m[12];
-            const float qy = M.m[1] * x + M.m[5] * y + M.m[9] * z + M.m[13];
-            const float qw = M.m[3] * x + M.m[7] * y + M.m[11] * z + M.m[15];
-            if (!(qw > 0.0f)) bad = true;
-            const float iw = 1.0f / qw;
-            const float sx = (qx * iw + 1.0f) * 0.5f * fw, sy = (1.0f - qy * iw) * 0.5f * fh;
-            if (!(sx == sx) || !(sy == sy)) bad = true;
-            px0 = fminf(px0, sx); px1 = fmaxf(px1, sx); py0 = fminf(py0, sy); py1 = fmaxf(py1, sy);
-        }
-        if (bad) {
+        const CellRect r = cell_tile_rect(M, cx, cy, cz, mc_n, margin, W, H);
+        if (r.bad) {
             all_bits = true;                         // cannot happen under CULL_OBJ_HULL; be safe: everything is marched
         } else {
-            const float gx = 1.5f + 1.0e-5f * fw, gy = 1.5f + 1.0e-5f * fh;
-            const float fx0 = fmaxf(ceilf(px0 - gx), 0.0f), fx1 = fminf(floorf(px1 + gx), fw - 1.0f);
-            const float fy0 = fmaxf(ceilf(py0 - gy), 0.0f), fy1 = fminf(floorf(py1 + gy), fh - 1.0f);
-            if (fx0 <= fx1 && fy0 <= fy1) {
-                const uint32_t tx0 = static_cast<uint32_t>(fx0) >> 3, tx1 = static_cast<uint32_t>(fx1) >> 3;
-                const uint32_t ty0 = static_cast<uint32_t>(fy0) >> 3, ty1 = static_cast<uint32_t>(fy1) >> 3;
+            if (r.on) {
+                const uint32_t tx0 = r.tx0, tx1 = r.tx1, ty0 = r.ty0, ty1 = r.ty1;
                 for (uint32_t ty = ty0; ty <= ty1; ++ty) {
                     uint32_t bit = ty * t8x + tx0;
                     const uint32_t last = ty * t8x + tx1;
@@ -542,6 +540,82 @@ __global__ __launch_bounds__(256) void volym_tile_mask_lds_kernel(const uint8_t*
     for (uint32_t i = threadIdx.x; i < n_words; i += 256u) {
         const uint32_t v = any_all ? 0xffffffffu : s_mask[i];
         if (v) atomicOr(&out[i], v);
+    }
+}
+
+// Per 8x8 tile, the depth range along its rays in which a sample can be dense: every macro cell that sets mask bits (same cells, same
+// grown boxes, same tile rectangles: cell_tile_rect) folds [near, far] of its box into each tile of its rectangle -- near the distance
+// from the eye to the box's nearest point, far to its farthest corner, both widened by 2e-5 relative + 1e-5 for the f32 rounding of
+// o + d * t and of the unit direction (t is the distance along the ray: |d| = 1 up to rounding).  A dense sample of pixel (gx, gy) lies in
+// a grown occupied cell whose rectangle holds the pixel, so its t is inside the tile's range (raymarch_pq.h clips the rays to it).
+// Encoding, so that a zeroed buffer means "no cell" and both folds are atomicMax: near as ~bits(near) in words [0, n_t8), far as
+// bits(far) in [n_t8, 2 n_t8) (non-negative floats order as their bits).  One workgroup per block of 8 x 8 x 4 cells, as
+// volym_tile_mask_lds_kernel: the block's tiles are folded in LDS and only tiles some cell touched go to global memory (a block whose
+// rectangle exceeds VOLYM_TILE_DEPTH_LDS tiles folds straight into global memory).  The caller zeroes `out` in stream order before.
+constexpr uint32_t VOLYM_TILE_DEPTH_LDS = 4096;      // tiles of a block's rectangle folded in LDS (32 KB)
+__global__ __launch_bounds__(256) void volym_tile_depth_kernel(const uint8_t* __restrict__ mc_max, uint32_t mc_n, uint32_t thr_byte, ClipMatrix M,
+                                                               float margin, float ex, float ey, float ez, uint32_t W, uint32_t H, uint32_t t8x,
+                                                               uint32_t n_t8, uint32_t* __restrict__ out)
+{
+    __shared__ uint32_t s_near[VOLYM_TILE_DEPTH_LDS], s_far[VOLYM_TILE_DEPTH_LDS];
+    __shared__ uint32_t s_rect[4];                       // union of the block's rectangles: min tx0, min ty0, max tx1, max ty1
+    if (threadIdx.x == 0u) { s_rect[0] = 0xffffffffu; s_rect[1] = 0xffffffffu; s_rect[2] = 0u; s_rect[3] = 0u; }
+    __syncthreads();
+    const uint32_t nbx = (mc_n + 7u) / 8u, nby = (mc_n + 7u) / 8u;
+    const uint32_t bx = blockIdx.x % nbx, by = (blockIdx.x / nbx) % nby, bz = blockIdx.x / (nbx * nby);
+    const uint32_t cx = bx * 8u + (threadIdx.x & 7u), cy = by * 8u + ((threadIdx.x >> 3) & 7u), cz = bz * 4u + (threadIdx.x >> 6);
+    CellRect r = {0u, 0u, 0u, 0u, false, false};
+    uint32_t ne = 0u, fe = 0u;
+    if (cx < mc_n && cy < mc_n && cz < mc_n && mc_max[cx + mc_n * (cy + mc_n * cz)] >= thr_byte) {
+        r = cell_tile_rect(M, cx, cy, cz, mc_n, margin, W, H);
+        if (r.on && !r.bad) {
+            float lo[3], hi[3];
+            cell_box(cx, cy, cz, mc_n, margin, lo, hi);
+            const float e[3] = {ex, ey, ez};
+            float dn = 0.0f, df = 0.0f;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float a = e[k] - fminf(fmaxf(e[k], lo[k]), hi[k]);               // to the nearest point of the box
+                const float b = fmaxf(fabsf(e[k] - lo[k]), fabsf(e[k] - hi[k]));       // to the farthest corner
+                dn += a * a; df += b * b;
+            }
+            const float near = fmaxf(sqrtf(dn) * (1.0f - 2.0e-5f) - 1.0e-5f, 0.0f);
+            const float far = sqrtf(df) * (1.0f + 2.0e-5f) + 1.0e-5f;
+            ne = ~__float_as_uint(near); fe = __float_as_uint(far);
+            atomicMin(&s_rect[0], r.tx0); atomicMin(&s_rect[1], r.ty0);
+            atomicMax(&s_rect[2], r.tx1); atomicMax(&s_rect[3], r.ty1);
+        }
+    }
+    if (__syncthreads_or(r.bad ? 1 : 0)) {               // cannot happen under CULL_OBJ_HULL (the mask sets every bit): no bounds anywhere
+        for (uint32_t i = threadIdx.x; i < n_t8; i += 256u) { atomicMax(&out[i], 0xffffffffu); atomicMax(&out[n_t8 + i], 0x7f800000u); }
+        return;
+    }
+    const uint32_t rx0 = s_rect[0], ry0 = s_rect[1], rx1 = s_rect[2], ry1 = s_rect[3];
+    if (rx0 > rx1) return;                               // no cell of the block on screen
+    const uint32_t rw = rx1 - rx0 + 1u, area = rw * (ry1 - ry0 + 1u);
+    const bool lds = area <= VOLYM_TILE_DEPTH_LDS;
+    if (lds) {
+        for (uint32_t i = threadIdx.x; i < area; i += 256u) { s_near[i] = 0u; s_far[i] = 0u; }
+        __syncthreads();
+    }
+    if (fe != 0u) {
+        for (uint32_t ty = r.ty0; ty <= r.ty1; ++ty)
+            for (uint32_t tx = r.tx0; tx <= r.tx1; ++tx) {
+                if (lds) {
+                    const uint32_t i = (ty - ry0) * rw + (tx - rx0);
+                    atomicMax(&s_near[i], ne); atomicMax(&s_far[i], fe);
+                } else {
+                    const uint32_t i = ty * t8x + tx;
+                    if (i < n_t8) { atomicMax(&out[i], ne); atomicMax(&out[n_t8 + i], fe); }
+                }
+            }
+    }
+    if (!lds) return;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < area; i += 256u) {      // row by row: neighbouring lanes, neighbouring words
+        const uint32_t f = s_far[i];
+        const uint32_t t = (ry0 + i / rw) * t8x + rx0 + i % rw;
+        if (f != 0u && t < n_t8) { atomicMax(&out[t], s_near[i]); atomicMax(&out[n_t8 + t], f); }
     }
 }
 

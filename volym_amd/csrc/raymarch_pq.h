@@ -38,7 +38,8 @@
 // Exact culling (results unchanged, DESIGN.md "Culling"):
 //   * no sample outside the AABB of the occupied macro cells can reach the threshold, so a ray is
 //     replayed (t += cur in f32, no fetches) up to the AABB entry and abandoned at its exit; a ray that
-//     misses the AABB is final at (0,0,0,0);
+//     misses the AABB is final at (0,0,0,0).  With the tile mask, the entry and exit are also clipped to
+//     the depth range of the occupied cells that project onto the ray's 8x8 tile (CULL_TILE_DEPTH);
 //   * a wave tile whose 8x8 pixel rectangle lies outside the projected cube stores (0,0,0,1) and one
 //     inside the cube but outside the projected AABB stores (0,0,0,0) without any per-ray work.  Both
 //     tests use hulls projected on the host and a 1.5 pixel safety margin; tiles that straddle an
@@ -579,6 +580,15 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax0, ax1), __builtin_fmaxf(ay0, ay1)), __builtin_fmaxf(az0, az1));
             tn = tn - 2.0e-5f * __builtin_fabsf(tn) - 1.0e-6f;
             tf = tf + 2.0e-5f * __builtin_fabsf(tf) + 1.0e-6f;
+            if (fp.cull & CULL_TILE_DEPTH) {
+                // ... and to the depth range of the occupied cells that project onto this 8x8 tile (volym_tile_depth_kernel, margins
+                // included; a quarter item reads its parent tile's).  Wave-uniform: two scalar loads.  No cell: near is NaN (fmax
+                // keeps tn) and far 0, which leaves no sample
+                const auto* td = (const __attribute__((address_space(4))) uint32_t*)fp.tile_depth;
+                const uint32_t t8 = (ty * 2u + (sub >> 1)) * fp.mask_t8x + tx * 2u + (sub & 1u);
+                tn = __builtin_fmaxf(tn, __uint_as_float(~td[t8]));
+                tf = __builtin_fminf(tf, __uint_as_float(td[32u * fp.mask_words + t8]));
+            }
             // a zero direction component makes its slab pair NaN/inf: fmin/fmax drop NaN, so test the origin there
             const bool outside_static = (ray.d.x == 0.0f && (ray.o.x < fp.aabb_lo[0] || ray.o.x > fp.aabb_hi[0])) ||
                                         (ray.d.y == 0.0f && (ray.o.y < fp.aabb_lo[1] || ray.o.y > fp.aabb_hi[1])) ||
