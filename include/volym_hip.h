@@ -170,8 +170,28 @@ int volym_set_labels(volym_ctx* ctx, const uint8_t* labels, uint32_t nx, uint32_
  * VOLYM_E_STATE as well.  Blocking set-up call, but no upload. */
 int volym_set_segment_importances(volym_ctx* ctx, const uint8_t table[256]);
 /* Voxel count per label value, from the volym_set_labels pass (the reference logs such a histogram, importance.rs:83-91).
- * VOLYM_E_STATE without labels. */
+ * Counts the whole label volume, whatever the crop box.  VOLYM_E_STATE without labels. */
 int volym_label_counts(volym_ctx* ctx, uint64_t counts[256]);
+/* Axis-aligned crop box on the device (new; the reference has none).  The frames enqueued after the call are the frames of the
+ * same scene in which every density byte AND every importance byte of a texel outside the box is 0 (an important structure
+ * that is cut away stops suppressing what lies in front of it).  lo inclusive, hi exclusive, in texels of the volume as
+ * volym_set_volume received it (prepared: padded, Y-flipped), x first.  Valid: lo[a] <= hi[a] <= n[a] on every axis; an empty
+ * box (lo == hi on some axis) renders the background everywhere; anything else is VOLYM_E_INVALID, a call without a volume
+ * VOLYM_E_STATE.  The whole volume [0, n) means "no crop" and is the state after volym_set_volume, which resets the box.
+ * The box belongs to the scene: volym_set_importances and volym_set_labels + volym_set_segment_importances made after a crop
+ * give cropped importances.  Blocking set-up call with the semantics of volym_set_segment_importances: it waits for the frames
+ * in flight in every frame slot (they show the old box), and needs no volym_update before the next volym_compute_pass.  No
+ * pass over voxels on the host and no upload: the first crop makes a device copy of the uncropped density (and of uploaded
+ * importances; labels on the device serve as their own source), and every edit rewrites only the slabs of texels between the
+ * old faces and the new ones, then the macro cells those slabs touch.  Memory: one more volume (two with uploaded
+ * importances) from the first crop until the next volym_set_volume; nothing in a context that never crops. */
+int volym_set_crop_box(volym_ctx* ctx, const uint32_t lo[3], const uint32_t hi[3]);
+int volym_get_crop_box(volym_ctx* ctx, uint32_t lo[3], uint32_t hi[3]);
+/* The slabs volym_set_crop_box rewrites when the box goes from [old_lo, old_hi) to [new_lo, new_hi): at most six boxes
+ * {x0, y0, z0, x1, y1, z1} whose union holds every texel that is in exactly one of the two boxes; *n_slabs of them are written
+ * (0 when the boxes are equal).  Pure host arithmetic, no context.  VOLYM_E_INVALID for NULL or lo > hi. */
+int volym_crop_slabs(const uint32_t old_lo[3], const uint32_t old_hi[3], const uint32_t new_lo[3], const uint32_t new_hi[3],
+                     uint32_t slabs[6][6], uint32_t* n_slabs);
 /* GPUTransferFunction::new_texture_1d_rgbt upload (src/gpu_resources/transfer_function.rs:36-90):
  * n RGBA8 texels (the reference uses n = 256), Linear/ClampToEdge sampler. */
 int volym_set_transfer_function(volym_ctx* ctx, const uint8_t* rgba8, uint32_t n);

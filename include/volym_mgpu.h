@@ -73,6 +73,10 @@ int volym_mgpu_set_volume(volym_mgpu* mg, const uint8_t* voxels, uint32_t nx, ui
 int volym_mgpu_set_importances(volym_mgpu* mg, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz);
 int volym_mgpu_set_labels(volym_mgpu* mg, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz);
 int volym_mgpu_set_segment_importances(volym_mgpu* mg, const uint8_t table[256]);
+int volym_mgpu_set_crop_box(volym_mgpu* mg, const uint32_t lo[3], const uint32_t hi[3]);
+/* (The set-up calls that change the scene -- volume, importances, segment importances, crop box, transfer function -- also drop
+ * the HIP graph volym_mgpu_run may hold: it was captured for the scene before the call, and the next run with use_graph captures
+ * again, at a standing view too.) */
 int volym_mgpu_set_transfer_function(volym_mgpu* mg, const uint8_t* rgba8, uint32_t n);
 int volym_mgpu_set_option(volym_mgpu* mg, int key, int value);
 int volym_mgpu_update(volym_mgpu* mg, const volym_camera_uniforms* camera, const volym_parameter_uniforms* parameters);

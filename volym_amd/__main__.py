@@ -116,6 +116,14 @@ def benchmark(args):
     return 0
 
 
+def _crop_arg(text):
+    """--crop x0,y0,z0,x1,y1,z1 (unit-cube coordinates) -> (lo01, hi01)"""
+    v = [float(t) for t in text.split(",")]
+    if len(v) != 6:
+        raise SystemExit("--crop: x0,y0,z0,x1,y1,z1 in [0, 1]")
+    return tuple(v[:3]), tuple(v[3:])
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -123,6 +131,8 @@ def run_simple(args):
     state.update()
     with demo.GpuContext(W, H, args.device) as ctx:
         d = demo.Simple.init(ctx, state, volume_raw=raw, labels_raw=labels, segments=segments, dims=(256, 256, 256))
+        if args.crop:
+            d.set_crop(ctx, *_crop_arg(args.crop))
         d.update_gpu_state(ctx, state)
         d.compute_pass(ctx)
         ctx.sync()
@@ -137,7 +147,9 @@ def flythrough(args):
     """Scripted fly-through (volym_amd/flythrough.py): mouse orbit, scroll zoom and every
     widget of the reference's panel over its range (src/gui.rs:198-277), one event + update + compute pass per frame
     (src/event_loop.rs:100-119).  --out DIR keeps every --keep-every-th frame as PNG and writes frames.json: the uniforms
-    each kept frame was rendered with (what a test needs to render the same frames with the oracle)."""
+    each kept frame was rendered with (what a test needs to render the same frames with the oracle) and, as metadata only, the
+    crop box in texels it was rendered with (the whole volume unless --crop or --crop-sweep is given; the frames of a run
+    without them are what they were before the crop box existed)."""
     import json
     import os
     from . import flythrough as ft
@@ -148,9 +160,14 @@ def flythrough(args):
     kept, times = [], []
     with demo.GpuContext(W, H, args.device) as ctx:
         d = demo.Simple.init(ctx, state, volume_raw=raw, labels_raw=labels, segments=segments, dims=(256, 256, 256))
+        if args.crop:
+            d.set_crop(ctx, *_crop_arg(args.crop))
+        sweep = ft.crop_sweep(args.frames) if args.crop_sweep else None    # our widget: a crop face dragged over its range
         for i, ev in enumerate(ft.script(args.frames)):
             ft.apply(state, ev)
             state.update()
+            if sweep:
+                d.set_crop(ctx, *sweep[i])
             d.update_gpu_state(ctx, state)
             t0 = time.perf_counter()
             d.compute_pass(ctx)
@@ -160,7 +177,7 @@ def flythrough(args):
                 ctx.sync()
                 name = "fly_%04d.png" % i
                 image.write_png(os.path.join(args.out, name), ctx.read_rgba8())
-                kept.append({"frame": i, "event": list(ev), "png": name,
+                kept.append({"frame": i, "event": list(ev), "png": name, "crop_box": [list(b) for b in ctx.crop_box()],
                              "camera_uniforms": bytes(state.camera_uniforms()).hex(),
                              "parameter_uniforms": bytes(state.parameter_uniforms()).hex()})
         ctx.sync()
@@ -210,6 +227,7 @@ def main(argv=None):
     run.add_argument("demo", nargs="?", default="simple", choices=["simple"])
     run.add_argument("--width", type=int, default=1280); run.add_argument("--height", type=int, default=720)
     run.add_argument("--screenshot")
+    run.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359
     b.add_argument("--secs", type=float, default=0.25, help="GPU seconds per trial (the reference uses 2 s of wall clock)")
@@ -223,6 +241,8 @@ def main(argv=None):
     fl = sub.add_parser("flythrough", help="scripted fly-through: orbit, zoom and every GUI widget over its range")
     fl.add_argument("--width", type=int, default=1280); fl.add_argument("--height", type=int, default=720)
     fl.add_argument("--frames", type=int, default=120); fl.add_argument("--out"); fl.add_argument("--keep-every", type=int, default=10)
+    fl.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
+    fl.add_argument("--crop-sweep", action="store_true", help="drag the far z crop face over its range while flying (not a widget of the reference)")
     dv = sub.add_parser("devtools", help="3D-Slicer .seg.nrrd -> segments.json + label .raw (volym_devtools)")
     dv.add_argument("nrrd"); dv.add_argument("segments_json"); dv.add_argument("binary_data")
     args = ap.parse_args(argv)

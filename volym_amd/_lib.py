@@ -129,6 +129,10 @@ SIGNATURES = {
     "volym_set_labels": (C.c_int, [_ctx, _u8p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "volym_set_segment_importances": (C.c_int, [_ctx, _u8p]),
     "volym_label_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint64)]),
+    "volym_set_crop_box": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_get_crop_box": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_crop_slabs": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                   C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "volym_update": (C.c_int, [_ctx, C.POINTER(CameraUniforms), C.POINTER(ParameterUniforms)]),
     "volym_compute_pass": (C.c_int, [_ctx]),
     "volym_sync": (C.c_int, [_ctx]),

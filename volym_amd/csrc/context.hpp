@@ -152,6 +152,17 @@ struct volym_ctx {
     bool labels_bricked = false;
     uint64_t label_count[256] = {};
     int label_box[256][6] = {};              // texel AABB {x0, y0, z0, x1, y1, z1} of every label value (count 0: none)
+    // crop box (volym_set_crop_box), texels of the volume; [0, n) after volym_set_volume.  From the first crop on d_vol0 holds the
+    // uncropped density and d_vol is "d_vol0 inside the box, 0 elsewhere".  The importances likewise: their uncropped source is
+    // the labels through seg_table when a table has been set since the labels, else d_imp0 (NULL: d_imp is uncropped).  They are
+    // cropped only while their dimensions are the volume's (volym_update refuses any other).
+    uint32_t crop_lo[3] = {0, 0, 0}, crop_hi[3] = {0, 0, 0};
+    uint8_t* d_vol0 = nullptr;
+    uint8_t* d_imp0 = nullptr;
+    bool imp_bricked = false;                // layout of d_imp (and d_imp0)
+    uint8_t seg_table[256] = {};
+    bool have_seg_table = false;
+    int imp_box0_lo[3] = {1, 1, 1}, imp_box0_hi[3] = {0, 0, 0};   // imp_box_* of the uncropped importances
     int filter = VOLYM_FILTER_NEAREST;
     uint8_t lut[256 * 4] = {};
     uint32_t tf_n = 0;

@@ -7,6 +7,7 @@
 // GpuContext stands where src/gpu_context.rs + GpuWriteTexture2D stood: a device and a W x H rgba8 output.
 #pragma once
 
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -110,6 +111,20 @@ public:
         }
         if (!labels_on_device_) set_labels(ctx, a);
         ctx.check(volym_set_segment_importances(ctx.handle(), table.data()));
+    }
+    // New: axis-aligned crop box in unit-cube coordinates in [0, 1] (the cube the camera orbits; y as the prepared, flipped volume
+    // has it): texel = floor(p * n + 0.5) clamped to [0, n].  Density and importances outside it count as 0 (volym_set_crop_box).
+    void set_crop(const GpuContext& ctx, const SimpleAssets& a, const float lo01[3], const float hi01[3])
+    {
+        const uint32_t n[3] = {a.nx, a.ny, a.nz};
+        uint32_t lo[3], hi[3];
+        for (int i = 0; i < 3; ++i) { lo[i] = crop_texel(lo01[i], n[i]); hi[i] = crop_texel(hi01[i], n[i]); }
+        ctx.check(volym_set_crop_box(ctx.handle(), lo, hi));
+    }
+    static uint32_t crop_texel(float p, uint32_t n)
+    {
+        const double t = std::floor(static_cast<double>(p) * n + 0.5);
+        return t <= 0.0 ? 0u : t >= static_cast<double>(n) ? n : static_cast<uint32_t>(t);
     }
     // src/demos/simple/importance.rs:148-158 as a table: the first segment whose label_value matches wins, the default is 0
     static std::vector<uint8_t> segment_table(const std::vector<SegmentInfo>& segments)

@@ -358,9 +358,14 @@ int volym_mgpu_local_count(const volym_mgpu* m) { return m ? static_cast<int>(m-
 volym_ctx* volym_mgpu_context(volym_mgpu* m, int i) { return (m && i >= 0 && i < static_cast<int>(m->loc.size())) ? m->loc[static_cast<size_t>(i)].ctx : nullptr; }
 int volym_mgpu_local_rank(const volym_mgpu* m, int i) { return (m && i >= 0 && i < static_cast<int>(m->loc.size())) ? m->loc[static_cast<size_t>(i)].rank : -1; }
 
+// A captured loop carries the frame parameters, culling buffers and distance fields of the scene it was captured for, and is
+// keyed on the view alone: a set-up call that changes the scene (at a standing view too) makes the next volym_mgpu_run capture again.
+static void mg_drop_graph(volym_mgpu* m) { m->graph_view = 0; }
+
 int volym_mgpu_set_volume(volym_mgpu* m, const uint8_t* voxels, uint32_t nx, uint32_t ny, uint32_t nz, int filter)
 {
     if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
     for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_volume(L.ctx, voxels, nx, ny, nz, filter));
     return VOLYM_OK;
 }
@@ -368,6 +373,7 @@ int volym_mgpu_set_volume(volym_mgpu* m, const uint8_t* voxels, uint32_t nx, uin
 int volym_mgpu_set_importances(volym_mgpu* m, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
     for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_importances(L.ctx, importances, nx, ny, nz));
     return VOLYM_OK;
 }
@@ -382,13 +388,23 @@ int volym_mgpu_set_labels(volym_mgpu* m, const uint8_t* labels, uint32_t nx, uin
 int volym_mgpu_set_segment_importances(volym_mgpu* m, const uint8_t table[256])
 {
     if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
     for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_segment_importances(L.ctx, table));
+    return VOLYM_OK;
+}
+
+int volym_mgpu_set_crop_box(volym_mgpu* m, const uint32_t lo[3], const uint32_t hi[3])
+{
+    if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
+    for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_crop_box(L.ctx, lo, hi));
     return VOLYM_OK;
 }
 
 int volym_mgpu_set_transfer_function(volym_mgpu* m, const uint8_t* rgba8, uint32_t n)
 {
     if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
     for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_transfer_function(L.ctx, rgba8, n));
     return VOLYM_OK;
 }

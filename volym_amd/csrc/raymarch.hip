@@ -680,6 +680,8 @@ static int rebuild_lists(volym_ctx* c)
     return rc;
 }
 
+static int read_macro_cells(volym_ctx* c);
+
 // Macro-cell maxima, their host copy and the occupied-cell AABB for every threshold byte (set-up path: blocks).
 static int build_macro_cells(volym_ctx* c)
 {
@@ -701,8 +703,22 @@ static int build_macro_cells(volym_ctx* c)
     }
     if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(macro cells): ") + hipGetErrorString(e));
     const hipStream_t stream = c->slot0().stream;
-    hipLaunchKernelGGL(volym_macrocell_kernel, dim3(cells), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n, c->bricked ? 1u : 0u);
+    const CellRange all = {{0u, 0u, 0u}, {n, n, n}};
+    hipLaunchKernelGGL(volym_macrocell_kernel, dim3(cells), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n, c->bricked ? 1u : 0u, all);
     HIPCHK(c, hipGetLastError());
+    rc = read_macro_cells(c);
+    if (rc != VOLYM_OK) return rc;
+    c->have_vol = true;
+    c->have_frame = had_frame;
+    return VOLYM_OK;
+}
+
+// The host's copy of the maxima (behind the launches on slot 0's stream that wrote them) and the occupied-cell AABB for every
+// threshold byte.  Blocks.
+static int read_macro_cells(volym_ctx* c)
+{
+    const uint32_t n = c->mc_n, cells = n * n * n;
+    const hipStream_t stream = c->slot0().stream;
     c->h_mc.resize(cells);
     HIPCHK(c, hipMemcpyAsync(c->h_mc.data(), c->d_mc, cells, hipMemcpyDeviceToHost, stream));
     HIPCHK(c, hipStreamSynchronize(stream));
@@ -722,8 +738,6 @@ static int build_macro_cells(volym_ctx* c)
         for (int i = 0; i < 3; ++i) { run[i] = std::min(run[i], box[v][i]); run[3 + i] = std::max(run[3 + i], box[v][3 + i]); }
         for (int i = 0; i < 6; ++i) c->aabb_tab[v][i] = run[3] < 0 ? (i < 3 ? 0 : -1) : run[i];
     }
-    c->have_vol = true;
-    c->have_frame = had_frame;
     return VOLYM_OK;
 }
 
@@ -887,6 +901,7 @@ void volym_destroy(volym_ctx* c)
         if (c->slots[i]) free_slot(*c->slots[i]);
     // (every slot's stream is idle now: nothing reads the scene any more)
     (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc);
+    (void)hipFree(c->d_vol0); (void)hipFree(c->d_imp0);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }
@@ -1111,14 +1126,260 @@ static bool want_bricked(const volym_ctx* c, uint32_t nx, uint32_t ny, uint32_t 
     return static_cast<uint64_t>(nx) * ny * nz > c->brick_from_bytes;
 }
 
+// ---- crop box on the device ---------------------------------------------------------------------------------------------
+// A frame with crop box B is the frame of the scene whose density and importance bytes outside B are 0.  The march kernels know
+// nothing of it: they read d_vol and d_imp, and volym_set_crop_box rewrites those from an uncropped source (context.hpp) --
+// only the texels whose side of the box changes, which at most six slabs cover (volym_crop_slabs), one per face that moved.
+// Everything derived from the bytes follows: the macro cells the slabs touch, the occupied-cell boxes, every slot's distance
+// field, hulls, tile mask and depth bounds (rebuilt by the next launch), the look-ahead's reject box, the work lists.
+
+static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks);
+
+int volym_crop_slabs(const uint32_t old_lo[3], const uint32_t old_hi[3], const uint32_t new_lo[3], const uint32_t new_hi[3], uint32_t slabs[6][6],
+                     uint32_t* n_slabs)
+{
+    if (!old_lo || !old_hi || !new_lo || !new_hi || !slabs || !n_slabs) return VOLYM_E_INVALID;
+    bool old_empty = false, new_empty = false;
+    for (int a = 0; a < 3; ++a) {
+        if (old_lo[a] > old_hi[a] || new_lo[a] > new_hi[a]) return VOLYM_E_INVALID;
+        old_empty = old_empty || old_lo[a] == old_hi[a];
+        new_empty = new_empty || new_lo[a] == new_hi[a];
+    }
+    uint32_t n = 0;
+    auto push = [&](const uint32_t lo[3], const uint32_t hi[3]) {
+        for (int a = 0; a < 3; ++a) if (lo[a] >= hi[a]) return;
+        for (int a = 0; a < 3; ++a) { slabs[n][a] = lo[a]; slabs[n][3 + a] = hi[a]; }
+        ++n;
+    };
+    if (old_empty || new_empty) {
+        // to or from nothing: the other box is the whole difference
+        if (!new_empty) push(new_lo, new_hi);
+        if (!old_empty) push(old_lo, old_hi);
+    } else {
+        // a texel of one box that is not in the other lies, on some axis, between the two positions of a face; on the other axes
+        // it lies within its own box, so within the union of the two extents
+        uint32_t ulo[3], uhi[3];
+        for (int a = 0; a < 3; ++a) { ulo[a] = std::min(old_lo[a], new_lo[a]); uhi[a] = std::max(old_hi[a], new_hi[a]); }
+        for (int a = 0; a < 3; ++a) {
+            uint32_t lo[3] = {ulo[0], ulo[1], ulo[2]}, hi[3] = {uhi[0], uhi[1], uhi[2]};
+            lo[a] = std::min(old_lo[a], new_lo[a]); hi[a] = std::max(old_lo[a], new_lo[a]);
+            push(lo, hi);
+            lo[a] = std::min(old_hi[a], new_hi[a]); hi[a] = std::max(old_hi[a], new_hi[a]);
+            push(lo, hi);
+        }
+    }
+    *n_slabs = n;
+    return VOLYM_OK;
+}
+
+static bool crop_active(const volym_ctx* c)
+{
+    return c->crop_lo[0] != 0u || c->crop_lo[1] != 0u || c->crop_lo[2] != 0u || c->crop_hi[0] != c->nx || c->crop_hi[1] != c->ny || c->crop_hi[2] != c->nz;
+}
+
+static bool imp_croppable(const volym_ctx* c)
+{
+    return c->have_vol && c->have_imp && c->d_imp && c->inx == c->nx && c->iny == c->ny && c->inz == c->nz;
+}
+
+static bool imp_from_labels(const volym_ctx* c) { return c->d_labels && c->have_seg_table; }
+
+// dst = inside(c->crop) ? source : 0 over one slab, on slot 0's stream (table: the source holds labels)
+static int launch_crop_slab(volym_ctx* c, const uint8_t* src, uint8_t* dst, const uint8_t* table, bool bricked, const uint32_t slab[6])
+{
+    CropSlab s = {};
+    for (int a = 0; a < 3; ++a) { s.lo[a] = slab[a]; s.hi[a] = slab[3 + a]; s.box_lo[a] = c->crop_lo[a]; s.box_hi[a] = c->crop_hi[a]; }
+    uint64_t items;
+    if (bricked) {
+        for (int a = 0; a < 3; ++a) { s.b_lo[a] = s.lo[a] >> 2; s.b_n[a] = ((s.hi[a] + 3u) >> 2) - s.b_lo[a]; }
+        items = 4ull * s.b_n[0] * s.b_n[1] * s.b_n[2];
+    } else {
+        const bool rows = s.lo[0] == 0u && s.hi[0] == c->nx, slices = rows && s.lo[1] == 0u && s.hi[1] == c->ny;
+        uint64_t run = s.hi[0] - s.lo[0];
+        s.runs_y = s.hi[1] - s.lo[1]; s.runs_z = s.hi[2] - s.lo[2];
+        if (rows) { run *= s.runs_y; s.runs_y = 1u; }
+        if (slices) { run *= s.runs_z; s.runs_z = 1u; }
+        s.run_len = static_cast<uint32_t>(run);                       // (a volume has fewer than 2^32 bytes: upload_volume)
+        s.chunks_per_run = static_cast<uint32_t>((run + 15u) / 16u) + 1u;
+        items = static_cast<uint64_t>(s.chunks_per_run) * s.runs_y * s.runs_z;
+    }
+    if (items == 0u) return VOLYM_OK;
+    LabelTable t = {};
+    if (table) std::memcpy(t.v, table, 256);
+    const hipStream_t stream = c->slot0().stream;
+    const dim3 grid(stream_grid(c, items));
+    if (table)
+        hipLaunchKernelGGL(volym_crop_slab_kernel<true>, grid, dim3(256), 0, stream, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), t, s, c->nx, c->ny,
+                           c->nz, bricked ? 1u : 0u, static_cast<uint32_t>(items));
+    else
+        hipLaunchKernelGGL(volym_crop_slab_kernel<false>, grid, dim3(256), 0, stream, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), t, s, c->nx, c->ny,
+                           c->nz, bricked ? 1u : 0u, static_cast<uint32_t>(items));
+    HIPCHK(c, hipGetLastError());
+    return VOLYM_OK;
+}
+
+// The uncropped copies a crop needs and the context does not hold yet.  Only called while the bytes they are copied from are
+// uncropped (the box is the whole volume, or the buffer has just been uploaded).  Device-to-device on slot 0's stream (the
+// slots are at rest): a device-to-device copy is not waited for by the host and the slots' streams do not wait for the NULL
+// stream, so only stream order puts the copy before the slab kernels that rewrite its source, and the hipStreamSynchronize
+// that ends every caller covers it.
+static int ensure_uncropped_copies(volym_ctx* c, bool vol, bool imp)
+{
+    if (vol && !c->d_vol0) {
+        const uint64_t nb = layout_bytes(c->bricked, c->nx, c->ny, c->nz) + 16u;
+        hipError_t e = hipMalloc(&c->d_vol0, nb);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_vol0, c->d_vol, nb, hipMemcpyDeviceToDevice, c->slot0().stream);
+        if (e != hipSuccess) { (void)hipFree(c->d_vol0); c->d_vol0 = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("crop box (density copy): ") + hipGetErrorString(e)); }
+    }
+    if (imp && imp_croppable(c) && !imp_from_labels(c) && !c->d_imp0) {
+        hipError_t e = hipMalloc(&c->d_imp0, c->imp_bytes);
+        if (e == hipSuccess) e = hipMemcpyAsync(c->d_imp0, c->d_imp, c->imp_bytes, hipMemcpyDeviceToDevice, c->slot0().stream);
+        if (e != hipSuccess) { (void)hipFree(c->d_imp0); c->d_imp0 = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("crop box (importance copy): ") + hipGetErrorString(e)); }
+    }
+    return VOLYM_OK;
+}
+
+// imp_box_* = the uncropped importances' box cut to the crop box: the cropped importances have nothing important outside it
+static void crop_important_box(volym_ctx* c)
+{
+    bool none = c->imp_box0_lo[0] > c->imp_box0_hi[0];
+    for (int a = 0; a < 3; ++a) {
+        c->imp_box_lo[a] = c->imp_box0_lo[a]; c->imp_box_hi[a] = c->imp_box0_hi[a];
+        if (none || !imp_croppable(c)) continue;
+        c->imp_box_lo[a] = std::max(c->imp_box_lo[a], static_cast<int>(c->crop_lo[a]));
+        c->imp_box_hi[a] = std::min(c->imp_box_hi[a], static_cast<int>(c->crop_hi[a]) - 1);
+        none = c->imp_box_lo[a] > c->imp_box_hi[a];
+    }
+    if (none) for (int a = 0; a < 3; ++a) { c->imp_box_lo[a] = 1; c->imp_box_hi[a] = 0; }
+    // the frames enqueued from here on march the new box, with or without a volym_update in between
+    for (int i = 0; i < c->n_slots(); ++i) set_reject_box(c, c->slots[i]->fp);
+}
+
+// Rewrite the importances (which hold their uncropped bytes everywhere) to the crop box: zero what lies outside.
+static int crop_fresh_importances(volym_ctx* c)
+{
+    crop_important_box(c);
+    if (!crop_active(c) || !imp_croppable(c)) return VOLYM_OK;
+    int rc = ensure_uncropped_copies(c, false, true);
+    if (rc != VOLYM_OK) return rc;
+    const uint32_t zero[3] = {0u, 0u, 0u}, dims[3] = {c->nx, c->ny, c->nz};
+    uint32_t slabs[6][6], n = 0;
+    (void)volym_crop_slabs(zero, dims, c->crop_lo, c->crop_hi, slabs, &n);
+    for (uint32_t i = 0; i < n && rc == VOLYM_OK; ++i)
+        rc = imp_from_labels(c) ? launch_crop_slab(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, slabs[i])
+                                : launch_crop_slab(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, slabs[i]);
+    if (rc != VOLYM_OK) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));
+    return VOLYM_OK;
+}
+
+// The box becomes [lo, hi) (valid): density (do_vol) and importances rewritten over the slabs between the old box and the new one,
+// and what is derived from them brought up to date.  Blocking set-up path.  A failure before the first launch leaves the context
+// as it was; one after it leaves bytes that belong to neither box, and the context then asks for volym_set_volume again, as it
+// does when volym_set_volume itself fails.
+static int apply_crop_work(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol);
+
+static int apply_crop(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol)
+{
+    int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
+    rc = ensure_uncropped_copies(c, do_vol, true);
+    if (rc != VOLYM_OK) return rc;
+    rc = apply_crop_work(c, lo, hi, do_vol);
+    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
+    return rc;
+}
+
+static int apply_crop_work(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol)
+{
+    int rc = VOLYM_OK;
+    uint32_t old_lo[3], old_hi[3], slabs[6][6], n = 0;
+    for (int a = 0; a < 3; ++a) { old_lo[a] = c->crop_lo[a]; old_hi[a] = c->crop_hi[a]; c->crop_lo[a] = lo[a]; c->crop_hi[a] = hi[a]; }
+    (void)volym_crop_slabs(old_lo, old_hi, lo, hi, slabs, &n);
+    const bool imp = imp_croppable(c);
+    for (uint32_t i = 0; i < n; ++i) {
+        if (do_vol) rc = launch_crop_slab(c, c->d_vol0, c->d_vol, nullptr, c->bricked, slabs[i]);
+        if (rc == VOLYM_OK && imp)
+            rc = imp_from_labels(c) ? launch_crop_slab(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, slabs[i])
+                                    : launch_crop_slab(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, slabs[i]);
+        if (rc != VOLYM_OK) return rc;
+    }
+    const hipStream_t stream = c->slot0().stream;
+    if (do_vol) {
+        // the maxima of the cells whose voxel range (slack included) meets a slab; the others cover no texel that changed
+        const uint32_t dims[3] = {c->nx, c->ny, c->nz};
+        for (uint32_t i = 0; i < n; ++i) {
+            CellRange r;
+            bool any = true;
+            for (int a = 0; a < 3; ++a) {
+                uint32_t c0 = c->mc_n, c1 = 0;
+                for (uint32_t k = 0; k < c->mc_n; ++k)
+                    if (mc_voxel_lo(k, dims[a], c->mc_n) < slabs[i][3 + a] && mc_voxel_hi(k, dims[a], c->mc_n) > slabs[i][a]) { c0 = std::min(c0, k); c1 = k + 1u; }
+                any = any && c0 < c1;
+                r.c0[a] = c0; r.cn[a] = any ? c1 - c0 : 0u;
+            }
+            if (!any) continue;
+            hipLaunchKernelGGL(volym_macrocell_kernel, dim3(r.cn[0] * r.cn[1] * r.cn[2]), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n,
+                               c->bricked ? 1u : 0u, r);
+            HIPCHK(c, hipGetLastError());
+        }
+        rc = read_macro_cells(c);
+        if (rc != VOLYM_OK) return rc;
+        for (int i = 0; i < c->n_slots(); ++i) { c->slots[i]->df_thr_byte = 0xffffffffu; c->slots[i]->hull_dirty = true; }
+    }
+    HIPCHK(c, hipStreamSynchronize(stream));       // every slot's next frame reads the new bytes
+    crop_important_box(c);
+    return rebuild_lists(c);
+}
+
+int volym_set_crop_box(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3])
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!lo || !hi) return fail(c, VOLYM_E_INVALID, "volym_set_crop_box: NULL box");
+    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_set_crop_box: no volume (volym_set_volume first)");
+    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
+    bool same = true;
+    for (int a = 0; a < 3; ++a) {
+        if (lo[a] > hi[a] || hi[a] > dims[a]) return fail(c, VOLYM_E_INVALID, "volym_set_crop_box: need lo <= hi <= volume size on every axis");
+        same = same && lo[a] == c->crop_lo[a] && hi[a] == c->crop_hi[a];
+    }
+    if (same) return VOLYM_OK;
+    return apply_crop(c, lo, hi, true);
+}
+
+int volym_get_crop_box(volym_ctx* c, uint32_t lo[3], uint32_t hi[3])
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!lo || !hi) return fail(c, VOLYM_E_INVALID, "volym_get_crop_box: NULL output");
+    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_get_crop_box: no volume");
+    for (int a = 0; a < 3; ++a) { lo[a] = c->crop_lo[a]; hi[a] = c->crop_hi[a]; }
+    return VOLYM_OK;
+}
+
 int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t ny, uint32_t nz, int filter)
 {
     if (!c) return VOLYM_E_INVALID;
     if (filter != VOLYM_FILTER_NEAREST && filter != VOLYM_FILTER_LINEAR)
         return fail(c, VOLYM_E_INVALID, "volym_set_volume: filter must be VOLYM_FILTER_NEAREST or VOLYM_FILTER_LINEAR");
-    int rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
+    int rc;
+    if (c->have_vol && crop_active(c)) {
+        // the box goes back to the whole volume: the importances get their cropped texels back (the density is replaced below).
+        // This runs before upload_volume has looked at its arguments: a call that then fails leaves the box reset and no volume
+        // (have_vol false), which is what a failed volym_set_volume leaves in any case.
+        const uint32_t zero[3] = {0u, 0u, 0u}, dims[3] = {c->nx, c->ny, c->nz};
+        rc = apply_crop(c, zero, dims, false);
+        if (rc != VOLYM_OK) return rc;
+    }
+    rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
+    // (d_imp is uncropped now, and the copies are made again by the next crop: a context that does not crop holds none)
+    if (c->d_vol0) { HIPCHK(c, hipFree(c->d_vol0)); c->d_vol0 = nullptr; }
+    if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
+    rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;
+    for (int a = 0; a < 3; ++a) c->crop_lo[a] = 0u;
+    c->crop_hi[0] = nx; c->crop_hi[1] = ny; c->crop_hi[2] = nz;
     c->bricked = want_bricked(c, nx, ny, nz);
     rc = build_macro_cells(c);             // (sets have_vol)
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
@@ -1162,9 +1423,14 @@ int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx,
     c->imp_bytes = layout_bytes(want_bricked(c, nx, ny, nz), nx, ny, nz) + 16u;
     // the importances are the caller's now: a segment table has no labels to map any more
     if (c->d_labels) { HIPCHK(c, hipFree(c->d_labels)); c->d_labels = nullptr; }
-    important_texel_box(importances, nx, ny, nz, c->imp_box_lo, c->imp_box_hi);
+    c->have_seg_table = false;
+    if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }      // (of the importances this call replaced)
+    c->imp_bricked = want_bricked(c, nx, ny, nz);
+    important_texel_box(importances, nx, ny, nz, c->imp_box0_lo, c->imp_box0_hi);
     c->inx = nx; c->iny = ny; c->inz = nz;
     c->have_imp = true;
+    rc = crop_fresh_importances(c);          // the crop box belongs to the scene: these importances are cropped like the last
+    if (rc != VOLYM_OK) { c->have_imp = false; return rc; }
     return rebuild_lists(c);
 }
 
@@ -1184,7 +1450,24 @@ static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks)
 int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!c) return VOLYM_E_INVALID;
-    int rc = upload_volume(c, &c->d_labels, labels, nx, ny, nz);      // (quiesces the slots first)
+    int rc;
+    if (imp_from_labels(c) && crop_active(c) && imp_croppable(c) && !c->d_imp0) {
+        // the importances stay as they are, cropped, and the labels they were mapped from go: keep their uncropped bytes
+        rc = quiesce_slots(c);
+        if (rc != VOLYM_OK) return rc;
+        hipError_t e = hipMalloc(&c->d_imp0, c->imp_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(c->d_imp0 + c->imp_bytes - 16u, 0, 16, c->slot0().stream);
+        if (e != hipSuccess) { (void)hipFree(c->d_imp0); c->d_imp0 = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(importances): ") + hipGetErrorString(e)); }
+        LabelTable t;
+        std::memcpy(t.v, c->seg_table, 256);
+        const uint64_t n_chunks = (c->imp_bytes - 16u + 15u) / 16u;
+        hipLaunchKernelGGL(volym_segment_map_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, c->slot0().stream, reinterpret_cast<const uint4*>(c->d_labels),
+                           reinterpret_cast<uint4*>(c->d_imp0), t, c->lnx, c->lny, c->lnz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->slot0().stream));
+    }
+    c->have_seg_table = false;
+    rc = upload_volume(c, &c->d_labels, labels, nx, ny, nz);      // (quiesces the slots first)
     if (rc != VOLYM_OK) { if (c->d_labels) (void)hipFree(c->d_labels); c->d_labels = nullptr; return rc; }
     c->lnx = nx; c->lny = ny; c->lnz = nz;
     c->labels_bricked = want_bricked(c, nx, ny, nz);
@@ -1248,13 +1531,20 @@ int volym_set_segment_importances(volym_ctx* c, const uint8_t table[256])
         for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c->label_box[l][a]); hi[a] = std::max(hi[a], c->label_box[l][3 + a]); }
     }
     for (int a = 0; a < 3; ++a) {
-        if (hi[0] < 0) { c->imp_box_lo[a] = 1; c->imp_box_hi[a] = 0; continue; }
-        c->imp_box_lo[a] = lo[a]; c->imp_box_hi[a] = hi[a];
+        if (hi[0] < 0) { c->imp_box0_lo[a] = 1; c->imp_box0_hi[a] = 0; continue; }
+        c->imp_box0_lo[a] = lo[a]; c->imp_box0_hi[a] = hi[a];
     }
     c->inx = c->lnx; c->iny = c->lny; c->inz = c->lnz;
     c->have_imp = true;
-    // the frames enqueued from here on march the new box, with or without a volym_update in between
-    for (int i = 0; i < c->n_slots(); ++i) set_reject_box(c, c->slots[i]->fp);
+    // from here on the labels and this table are the uncropped importances
+    std::memcpy(c->seg_table, table, 256);
+    c->have_seg_table = true;
+    c->imp_bricked = c->labels_bricked;
+    if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
+    // the crop box (if any) cuts the new importances, and the frames enqueued from here on march the new reject box, with or
+    // without a volym_update in between
+    rc = crop_fresh_importances(c);
+    if (rc != VOLYM_OK) { c->have_imp = false; return rc; }
     return rebuild_lists(c);
 }
 

@@ -621,15 +621,28 @@ __global__ __launch_bounds__(256) void volym_tile_depth_kernel(const uint8_t* __
 
 // per-cell maxima of the density volume: cell (cx,cy,cz) of the mc_n^3 grid covers the voxels a
 // nearest-filter sample with pos in [c/mc_n, (c+1)/mc_n) can select, i.e. floor(pos*n) for those pos.
-__global__ __launch_bounds__(256) void volym_macrocell_kernel(const uint8_t* __restrict__ vol, uint8_t* __restrict__ mc_max,
-                                                              uint32_t nx, uint32_t ny, uint32_t nz, uint32_t mc_n, uint32_t bricked)
+// One workgroup per cell of the range of cells `cells` = {x0, y0, z0, nx, ny, nz} (the whole grid, or the cells a crop edit touched).
+struct CellRange { uint32_t c0[3], cn[3]; };
+// voxel range [lo, hi) of cell c on an axis of n voxels, one voxel of slack on both sides (float rounding of pos*n)
+__host__ __device__ inline uint32_t mc_voxel_lo(uint32_t c, uint32_t n, uint32_t mc_n)
 {
-    const uint32_t cell = blockIdx.x;
-    const uint32_t cx = cell % mc_n, cy = (cell / mc_n) % mc_n, cz = cell / (mc_n * mc_n);
-    // voxel range [lo, hi) per axis, one voxel of slack on both sides (float rounding of pos*n)
-    auto lo = [&](uint32_t c, uint32_t n) { uint32_t v = static_cast<uint32_t>((static_cast<uint64_t>(c) * n) / mc_n); return v > 0u ? v - 1u : 0u; };
-    auto hi = [&](uint32_t c, uint32_t n) { uint32_t v = static_cast<uint32_t>((static_cast<uint64_t>(c + 1u) * n + mc_n - 1u) / mc_n) + 1u; return v < n ? v : n; };
-    const uint32_t x0 = lo(cx, nx), x1 = hi(cx, nx), y0 = lo(cy, ny), y1 = hi(cy, ny), z0 = lo(cz, nz), z1 = hi(cz, nz);
+    const uint32_t v = static_cast<uint32_t>((static_cast<uint64_t>(c) * n) / mc_n);
+    return v > 0u ? v - 1u : 0u;
+}
+__host__ __device__ inline uint32_t mc_voxel_hi(uint32_t c, uint32_t n, uint32_t mc_n)
+{
+    const uint32_t v = static_cast<uint32_t>((static_cast<uint64_t>(c + 1u) * n + mc_n - 1u) / mc_n) + 1u;
+    return v < n ? v : n;
+}
+
+__global__ __launch_bounds__(256) void volym_macrocell_kernel(const uint8_t* __restrict__ vol, uint8_t* __restrict__ mc_max,
+                                                              uint32_t nx, uint32_t ny, uint32_t nz, uint32_t mc_n, uint32_t bricked, CellRange cells)
+{
+    const uint32_t cx = cells.c0[0] + blockIdx.x % cells.cn[0], cy = cells.c0[1] + (blockIdx.x / cells.cn[0]) % cells.cn[1],
+                   cz = cells.c0[2] + blockIdx.x / (cells.cn[0] * cells.cn[1]);
+    const uint32_t cell = (cz * mc_n + cy) * mc_n + cx;
+    const uint32_t x0 = mc_voxel_lo(cx, nx, mc_n), x1 = mc_voxel_hi(cx, nx, mc_n), y0 = mc_voxel_lo(cy, ny, mc_n), y1 = mc_voxel_hi(cy, ny, mc_n),
+                   z0 = mc_voxel_lo(cz, nz, mc_n), z1 = mc_voxel_hi(cz, nz, mc_n);
     const uint32_t wx = x1 - x0, wy = y1 - y0, wz = z1 - z0;
     const uint32_t total = wx * wy * wz;
     uint32_t m = 0;
@@ -782,6 +795,84 @@ __global__ __launch_bounds__(256) void volym_label_stats_kernel(const uint4* __r
         atomicAdd(&counts[l], static_cast<unsigned long long>(s_cnt[l]));
         for (int i = 0; i < 3; ++i) atomicMin(&boxes[l * 6 + i], s_box[l * 6 + i]);
         for (int i = 3; i < 6; ++i) atomicMax(&boxes[l * 6 + i], s_box[l * 6 + i]);
+    }
+}
+
+// ---- crop box on the device (volym_set_crop_box) -------------------------------------------------------------------------
+// dst = inside(box) ? value(src) : 0 over one slab of texels, where value is the byte itself (density, uploaded importances) or
+// table[byte] (src = the label volume).  16 bytes in, 16 out per lane and step, in either layout; a chunk that sticks out of the
+// slab rewrites its other bytes by the same rule, which leaves them as they are (the host only hands slabs that cover every
+// texel whose side of the box changes).  Padding stays 0: the box lies inside the volume.
+//   bricked: the slab widened to whole bricks; item i is chunk (i & 3) of brick (i >> 2) of that brick range (chunks whose z is
+//            outside the slab are skipped), so neighbouring lanes write neighbouring chunks;
+//   linear:  the slab as runs of consecutive bytes (a row of the slab; whole rows merge into one run per z, whole slices into a
+//            single run -- the host decides), each covered by the aligned chunks it touches.  Two runs may share a chunk: both
+//            lanes store the same 16 bytes.
+struct CropSlab {
+    uint32_t lo[3], hi[3];          // the slab, texels
+    uint32_t box_lo[3], box_hi[3];  // the box the bytes are cropped to
+    uint32_t run_len, runs_y, runs_z, chunks_per_run;   // linear walk: runs_y * runs_z runs of run_len bytes
+    uint32_t b_lo[3], b_n[3];       // bricked walk: first brick and bricks per axis
+};
+
+template <bool TABLE>
+__global__ __launch_bounds__(256) void volym_crop_slab_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, LabelTable table, CropSlab s,
+                                                              uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
+{
+    __shared__ uint8_t s_tab[TABLE ? 256 : 1];      // (only the instantiation that maps labels holds the table)
+    if (TABLE) {
+        s_tab[threadIdx.x] = table.v[threadIdx.x];
+        __syncthreads();
+    }
+    const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
+    const uint32_t bx = brick_count(nx), by = brick_count(ny);
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
+        uint64_t k;                  // chunk
+        uint32_t keep = 0;           // bit b: byte b of the chunk is a texel inside the box
+        if (bricked) {
+            const uint32_t zz = i & 3u, b = i >> 2;
+            const uint32_t bxi = s.b_lo[0] + b % s.b_n[0], byi = s.b_lo[1] + (b / s.b_n[0]) % s.b_n[1], bzi = s.b_lo[2] + b / (s.b_n[0] * s.b_n[1]);
+            const uint32_t z = bzi * 4u + zz;
+            if (z < s.lo[2] || z >= s.hi[2]) continue;
+            k = (static_cast<uint64_t>(bzi) * by + byi) * bx + bxi;
+            k = k * 4u + zz;
+            if (z >= s.box_lo[2] && z < s.box_hi[2]) {
+                uint32_t row = 0;
+                for (uint32_t j = 0; j < 4u; ++j) { const uint32_t x = bxi * 4u + j; if (x >= s.box_lo[0] && x < s.box_hi[0]) row |= 1u << j; }
+                for (uint32_t r = 0; r < 4u; ++r) { const uint32_t y = byi * 4u + r; if (y >= s.box_lo[1] && y < s.box_hi[1]) keep |= row << (4u * r); }
+            }
+        } else {
+            const uint32_t ci = i % s.chunks_per_run, r = i / s.chunks_per_run;
+            const uint32_t ry = r % s.runs_y, rz = r / s.runs_y;
+            const uint64_t start = s.lo[0] + static_cast<uint64_t>(nx) * ((s.lo[1] + ry) + static_cast<uint64_t>(ny) * (s.lo[2] + rz));
+            k = (start >> 4) + ci;
+            if ((k << 4) >= start + s.run_len) continue;
+            const uint64_t o = k << 4, slice = static_cast<uint64_t>(nx) * ny;
+            uint32_t z = static_cast<uint32_t>(o / slice);
+            const uint32_t rem = static_cast<uint32_t>(o - z * slice);
+            uint32_t y = rem / nx, x = rem - y * nx;
+            for (uint32_t j = 0; j < 16u; ++j) {
+                if (o + j < n && x >= s.box_lo[0] && x < s.box_hi[0] && y >= s.box_lo[1] && y < s.box_hi[1] && z >= s.box_lo[2] && z < s.box_hi[2]) keep |= 1u << j;
+                if (++x == nx) { x = 0; if (++y == ny) { y = 0; ++z; } }
+            }
+        }
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        if (keep) {
+            const uint4 v = src[k];
+            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t o = 0;
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    if (!(keep & (1u << (4 * j + b)))) continue;
+                    const uint32_t byte = (w[j] >> (8 * b)) & 0xffu;
+                    o |= (TABLE ? static_cast<uint32_t>(s_tab[byte & (TABLE ? 255u : 0u)]) : byte) << (8 * b);
+                }
+                w[j] = o;
+            }
+        }
+        dst[k] = make_uint4(w[0], w[1], w[2], w[3]);
     }
 }
 

@@ -40,6 +40,8 @@ struct Options {
     int device = 0;
     int frames_in_flight = 1;      // 2: VOLYM_OPT_FRAMES_IN_FLIGHT (benchmark: frames per wall clock)
     bool debug = false;
+    bool crop = false;             // --crop x0,y0,z0,x1,y1,z1: crop box in unit-cube coordinates (run simple)
+    float crop_lo[3] = {0.0f, 0.0f, 0.0f}, crop_hi[3] = {1.0f, 1.0f, 1.0f};
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -157,6 +159,7 @@ int run_simple(const Options& o)
     State state = State::with_parameters(static_cast<float>(W) / static_cast<float>(H), StateParameters());   // src/state.rs:41-55
     state.update();
     Simple demo = Simple::init(ctx, state, assets);
+    if (o.crop) demo.set_crop(ctx, assets, o.crop_lo, o.crop_hi);
     demo.update_gpu_state(ctx, state);
     demo.compute_pass(ctx);
     ctx.check(volym_sync(ctx.handle()));
@@ -191,7 +194,14 @@ int main(int argc, char** argv)
             else if (a == "--secs") o.secs = std::stod(next());
             else if (a == "--device") o.device = std::stoi(next());
             else if (a == "--frames-in-flight") { o.frames_in_flight = std::stoi(next()); if (o.frames_in_flight != 1 && o.frames_in_flight != 2) throw Error(VOLYM_E_INVALID, "--frames-in-flight: 1 or 2"); }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2]\n"); return 2; }
+            else if (a == "--crop") {
+                const std::string v = next();
+                float f[6];
+                if (std::sscanf(v.c_str(), "%f,%f,%f,%f,%f,%f", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5]) != 6) throw Error(VOLYM_E_INVALID, "--crop: x0,y0,z0,x1,y1,z1 in [0, 1]");
+                for (int k = 0; k < 3; ++k) { o.crop_lo[k] = f[k]; o.crop_hi[k] = f[3 + k]; }
+                o.crop = true;
+            }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

@@ -112,6 +112,18 @@ class GpuContext:
         self._ck(_lib.lib().volym_label_counts(self.handle, out.ctypes.data_as(C.POINTER(C.c_uint64))))
         return out
 
+    def set_crop_box(self, lo, hi):
+        """Crop box in texels of the prepared volume (lo inclusive, hi exclusive, x first): density and importances outside
+        it count as 0 from the next compute pass on.  No upload; the device rewrites the slabs between the old and new faces."""
+        lo3, hi3 = (C.c_uint32 * 3)(*[int(v) for v in lo]), (C.c_uint32 * 3)(*[int(v) for v in hi])
+        self._ck(_lib.lib().volym_set_crop_box(self.handle, lo3, hi3))
+
+    def crop_box(self):
+        """(lo, hi) of the current crop box in texels; the whole volume when nothing is cropped."""
+        lo3, hi3 = (C.c_uint32 * 3)(), (C.c_uint32 * 3)()
+        self._ck(_lib.lib().volym_get_crop_box(self.handle, lo3, hi3))
+        return tuple(int(v) for v in lo3), tuple(int(v) for v in hi3)
+
     # ---- per frame --------------------------------------------------------------------------
     def update(self, camera_uniforms, parameter_uniforms):
         self._ck(_lib.lib().volym_update(self.handle, C.byref(camera_uniforms), C.byref(parameter_uniforms)))
@@ -266,6 +278,13 @@ class Simple(ComputeDemo):
     def compute_pass(self, ctx):
         """BaseDemo::compute_pass -> DemoPipeline::compute_pass (src/demos/pipeline.rs:62-102, :214-225)"""
         ctx.compute_pass()
+
+    def set_crop(self, ctx, lo01, hi01):
+        """Crop box in unit-cube coordinates in [0, 1] (the cube the camera orbits; y as the prepared, flipped volume has it):
+        texel = floor(p * n + 0.5) clamped to [0, n] (scene.crop_box_texels).  Returns the texel box."""
+        lo, hi = scene.crop_box_texels(lo01, hi01, self.dims)
+        ctx.set_crop_box(lo, hi)
+        return lo, hi
 
     def set_labels(self, ctx, labels_raw):
         """Keep the label map on the device (new; the reference maps it once on the host), so that set_segments can change

@@ -7,7 +7,9 @@ scripted input event:
   * the egui panel's widgets (src/gui.rs:198-277) with their rules and ranges: "Importance Rendering" on forces "Opacity" on
     (:228-236) and the opacity box is disabled while it is on (:211-222); "Cone Importance Check" and "Look Ahead Steps"
     (2..=25) are enabled only with importance rendering (:242-262); "Raymarching Step Size" 0.001..=0.1 logarithmic
-    (:264-269); "Density Threshold" 0.005..=1.0 (:271-275).
+    (:264-269); "Density Threshold" 0.005..=1.0 (:271-275);
+  * one widget of ours, which the reference's panel does not have: a crop face (volym_set_crop_box) dragged over its range
+    (`crop_sweep`; opt-in, so the frames of `script` stay what they were).
 """
 import numpy as np
 
@@ -87,3 +89,18 @@ def apply(state, event):
         state.process_scroll(event[1])
     else:
         getattr(Gui(state), kind)(event[1])
+
+
+CROP_FACE_RANGE = (0.25, 1.0)       # ours: how far the swept crop face travels, unit-cube z
+
+
+def crop_sweep(n_frames):
+    """Ours (no counterpart in src/gui.rs): per frame, the crop box (lo01, hi01) in unit-cube coordinates while the far z face
+    is dragged from the end of its range to the start and back, a step every frame, as a slider under the mouse moves."""
+    lo, hi = CROP_FACE_RANGE
+    half = max(1, n_frames // 2)
+    out = []
+    for i in range(n_frames):
+        t = i / half if i < half else (n_frames - 1 - i) / max(1, n_frames - 1 - half)
+        out.append(((0.0, 0.0, 0.0), (1.0, 1.0, hi + (lo - hi) * min(max(t, 0.0), 1.0))))
+    return out

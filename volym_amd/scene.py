@@ -195,6 +195,44 @@ def check_segment_table(table):
     return t
 
 
+def check_crop_box(lo, hi, dims):
+    """A crop box in texels of the prepared volume (lo inclusive, hi exclusive, x first): lo <= hi <= n on every axis."""
+    try:
+        lo, hi, dims = [int(v) for v in lo], [int(v) for v in hi], [int(v) for v in dims]
+    except TypeError:
+        raise ValueError("a crop box is two triples of texel indices")
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("a crop box is two triples of texel indices, got %d and %d values" % (len(lo), len(hi)))
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("crop box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    return tuple(lo), tuple(hi)
+
+
+def crop_box_texels(lo01, hi01, dims):
+    """Unit-cube coordinates in [0, 1] (the space the camera orbits, target (.5, .5, .5)) -> texels of the prepared volume:
+    texel = floor(p * n + 0.5), clamped to [0, n].  A face at p cuts between the texels whose centres lie on either side."""
+    if len(lo01) != 3 or len(hi01) != 3 or len(dims) != 3:
+        raise ValueError("a crop box is two triples of unit-cube coordinates")
+
+    def texel(p, n):
+        return int(min(max(np.floor(float(p) * n + 0.5), 0), n))
+    lo = [texel(p, n) for p, n in zip(lo01, dims)]
+    hi = [texel(p, n) for p, n in zip(hi01, dims)]
+    return check_crop_box(lo, hi, dims)
+
+
+def crop_volume(prepared, dims, lo, hi):
+    """The definition of the crop box: a copy of the prepared bytes (density or importances) with every texel outside
+    [lo, hi) set to 0."""
+    lo, hi = check_crop_box(lo, hi, dims)
+    nx, ny, nz = dims
+    src = np.ascontiguousarray(prepared, np.uint8).reshape(nz, ny, nx)
+    out = np.zeros_like(src)
+    out[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]] = src[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+    return out.ravel()
+
+
 def map_segments_to_importance(labels, segments):
     """src/demos/simple/importance.rs:148-158"""
     data = np.array(labels, np.uint8, copy=True).ravel()
