@@ -192,6 +192,48 @@ int volym_get_crop_box(volym_ctx* ctx, uint32_t lo[3], uint32_t hi[3]);
  * (0 when the boxes are equal).  Pure host arithmetic, no context.  VOLYM_E_INVALID for NULL or lo > hi. */
 int volym_crop_slabs(const uint32_t old_lo[3], const uint32_t old_hi[3], const uint32_t new_lo[3], const uint32_t new_hi[3],
                      uint32_t slabs[6][6], uint32_t* n_slabs);
+/* Segment visibility on the device (new; the reference has none): switch segments off without touching the volume on the host.
+ * visible[l] != 0 shows label value l.  The frames enqueued after the call are the frames of the same scene in which every
+ * density byte AND every importance byte of a texel whose label is hidden, or that lies outside the crop box, is 0 (a hidden
+ * structure stops suppressing what lies in front of it, as a cropped one does).  Crop box and mask commute: any interleaving of
+ * volym_set_crop_box and this call that ends at the same (box, mask) leaves the same bytes, and a box that grows over hidden
+ * texels leaves them 0.
+ *   Call order: needs a volume and labels on the device whose dimensions equal the volume's, else VOLYM_E_STATE; NULL context or
+ * table VOLYM_E_INVALID.  Volume, labels (and importances) held in different device layouts -- VOLYM_OPT_VOLUME_LAYOUT changed
+ * between their uploads -- are refused with VOLYM_E_STATE as well.
+ *   Blocking set-up call with the semantics of volym_set_segment_importances: it waits for the frames in flight in every frame
+ * slot (they show the old mask), and needs no volym_update before the next volym_compute_pass.  A mask equal to the current one
+ * returns at once.  A label value without voxels is accepted and toggling it changes nothing; label 0 (which covers the padding)
+ * can be hidden like any other.
+ *   The mask belongs to the labels.  Initially all visible; volym_set_labels resets it to all visible (new labels, new
+ * segments), volym_set_importances drops the labels and with them the mask, volym_set_volume resets it as it resets the box:
+ * after any of the three the scene is that of the crop box alone, the hidden texels have their bytes back (where a call of the
+ * three then fails on its arguments, the mask is reset all the same).  volym_set_segment_importances called while segments are
+ * hidden gives importances with those segments hidden, and the look-ahead's reject box is then that of the labels with
+ * table[l] >= 128 that are visible, cut to the crop box (with uploaded importances: their box, cut to the crop box).
+ * volym_label_counts keeps counting the whole label volume.
+ *   No pass over voxels on the host, no upload: an edit rewrites the texels inside the boxes of the labels that flipped, cut to
+ * the crop box (volym_visibility_boxes), skipping every 16-byte chunk without a texel of such a label, then the macro cells
+ * those boxes touch.  Memory: the uncropped copies of the crop box (volym_set_crop_box), made by the first hide or the first
+ * crop, whichever comes first; the copy of the importances only when they were uploaded rather than mapped from the labels;
+ * nothing in a context that never hides or crops.  A failure after the first kernel of an edit leaves bytes that belong to
+ * neither mask, and the context then asks for volym_set_volume again. */
+int volym_set_segment_visibility(volym_ctx* ctx, const uint8_t visible[256]);
+/* The current mask as 0 / 1 per label value (all 1 without labels). */
+int volym_get_segment_visibility(volym_ctx* ctx, uint8_t visible[256]);
+/* The boxes of texels volym_set_segment_visibility rewrites when the labels with flipped[l] != 0 change visibility: at most
+ * VOLYM_VISIBILITY_MAX_BOXES boxes {x0, y0, z0, x1, y1, z1} (hi exclusive) inside the crop box [crop_lo, crop_hi) whose union
+ * holds every texel of a flipped label inside the crop box; *n_boxes of them are written.  counts[l] and label_boxes[l]
+ * ({x0, y0, z0, x1, y1, z1}, hi INCLUSIVE) are the voxel count and texel AABB of label l, as the volym_set_labels pass finds
+ * them; a label without voxels is skipped.  The rule: every flipped label's box, cut to the crop box, joins the first box so far
+ * whose hull with it holds no more texels than the two apart (overlapping and nested boxes: nothing is read twice); else it
+ * becomes a box of its own while there is room; else it joins the box that grows least.  At the end, boxes are joined while a
+ * hull holds no more texels than its two boxes.  So one label costs one launch over its own box, and 200 labels at most
+ * VOLYM_VISIBILITY_MAX_BOXES launches.  Pure host arithmetic, no context.  VOLYM_E_INVALID for NULL, crop_lo > crop_hi or a
+ * counted label with a negative or inverted box. */
+#define VOLYM_VISIBILITY_MAX_BOXES 8
+int volym_visibility_boxes(const uint8_t flipped[256], const uint64_t counts[256], const int32_t label_boxes[256][6], const uint32_t crop_lo[3],
+                           const uint32_t crop_hi[3], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6], uint32_t* n_boxes);
 /* GPUTransferFunction::new_texture_1d_rgbt upload (src/gpu_resources/transfer_function.rs:36-90):
  * n RGBA8 texels (the reference uses n = 256), Linear/ClampToEdge sampler. */
 int volym_set_transfer_function(volym_ctx* ctx, const uint8_t* rgba8, uint32_t n);

@@ -124,6 +124,17 @@ def _crop_arg(text):
     return tuple(v[:3]), tuple(v[3:])
 
 
+def _hide_arg(text):
+    """--hide 3,4 (label values) -> [3, 4]"""
+    try:
+        v = [int(t) for t in text.split(",") if t.strip() != ""]
+    except ValueError:
+        raise SystemExit("--hide: label values 0..255, comma separated")
+    if not v or any(not 0 <= l <= 255 for l in v):
+        raise SystemExit("--hide: label values 0..255, comma separated")
+    return v
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -133,6 +144,8 @@ def run_simple(args):
         d = demo.Simple.init(ctx, state, volume_raw=raw, labels_raw=labels, segments=segments, dims=(256, 256, 256))
         if args.crop:
             d.set_crop(ctx, *_crop_arg(args.crop))
+        if args.hide:
+            d.set_hidden(ctx, _hide_arg(args.hide))
         d.update_gpu_state(ctx, state)
         d.compute_pass(ctx)
         ctx.sync()
@@ -149,7 +162,7 @@ def flythrough(args):
     (src/event_loop.rs:100-119).  --out DIR keeps every --keep-every-th frame as PNG and writes frames.json: the uniforms
     each kept frame was rendered with (what a test needs to render the same frames with the oracle) and, as metadata only, the
     crop box in texels it was rendered with (the whole volume unless --crop or --crop-sweep is given; the frames of a run
-    without them are what they were before the crop box existed)."""
+    without them are what they were before the crop box existed) and, with --hide only, the hidden label values ("hidden_labels")."""
     import json
     import os
     from . import flythrough as ft
@@ -162,6 +175,7 @@ def flythrough(args):
         d = demo.Simple.init(ctx, state, volume_raw=raw, labels_raw=labels, segments=segments, dims=(256, 256, 256))
         if args.crop:
             d.set_crop(ctx, *_crop_arg(args.crop))
+        hidden = d.set_hidden(ctx, _hide_arg(args.hide)) if args.hide else None
         sweep = ft.crop_sweep(args.frames) if args.crop_sweep else None    # our widget: a crop face dragged over its range
         for i, ev in enumerate(ft.script(args.frames)):
             ft.apply(state, ev)
@@ -180,6 +194,8 @@ def flythrough(args):
                 kept.append({"frame": i, "event": list(ev), "png": name, "crop_box": [list(b) for b in ctx.crop_box()],
                              "camera_uniforms": bytes(state.camera_uniforms()).hex(),
                              "parameter_uniforms": bytes(state.parameter_uniforms()).hex()})
+                if hidden is not None:       # (a run without --hide writes the keys it always wrote)
+                    kept[-1]["hidden_labels"] = hidden
         ctx.sync()
     if args.out:
         with open(os.path.join(args.out, "frames.json"), "w") as f:
@@ -228,6 +244,7 @@ def main(argv=None):
     run.add_argument("--width", type=int, default=1280); run.add_argument("--height", type=int, default=720)
     run.add_argument("--screenshot")
     run.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
+    run.add_argument("--hide", help="label values of the segments to hide, e.g. 3,4")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359
     b.add_argument("--secs", type=float, default=0.25, help="GPU seconds per trial (the reference uses 2 s of wall clock)")
@@ -242,6 +259,7 @@ def main(argv=None):
     fl.add_argument("--width", type=int, default=1280); fl.add_argument("--height", type=int, default=720)
     fl.add_argument("--frames", type=int, default=120); fl.add_argument("--out"); fl.add_argument("--keep-every", type=int, default=10)
     fl.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
+    fl.add_argument("--hide", help="label values of the segments to hide, e.g. 3,4")
     fl.add_argument("--crop-sweep", action="store_true", help="drag the far z crop face over its range while flying (not a widget of the reference)")
     dv = sub.add_parser("devtools", help="3D-Slicer .seg.nrrd -> segments.json + label .raw (volym_devtools)")
     dv.add_argument("nrrd"); dv.add_argument("segments_json"); dv.add_argument("binary_data")

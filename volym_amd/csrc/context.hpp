@@ -162,7 +162,14 @@ struct volym_ctx {
     bool imp_bricked = false;                // layout of d_imp (and d_imp0)
     uint8_t seg_table[256] = {};
     bool have_seg_table = false;
-    int imp_box0_lo[3] = {1, 1, 1}, imp_box0_hi[3] = {0, 0, 0};   // imp_box_* of the uncropped importances
+    int imp_box0_lo[3] = {1, 1, 1}, imp_box0_hi[3] = {0, 0, 0};   // imp_box_* of the uncropped importances (of the visible segments)
+    // segment visibility (volym_set_segment_visibility): seg_hidden[l] != 0 hides label l; all 0 after volym_set_labels,
+    // volym_set_importances and volym_set_volume.  The invariant every edit of box or mask keeps, and relies on to rewrite only
+    // the texels whose state changes:  d_vol[t] = (t inside the crop box && !seg_hidden[label(t)]) ? d_vol0[t] : 0  for every
+    // texel t, and the same for d_imp with its uncropped source (above).  An edit that fails after its first launch breaks it,
+    // and the context then asks for volym_set_volume again (have_vol false).  While a segment is hidden the labels have the
+    // volume's dimensions and layout (the call refuses anything else).
+    uint8_t seg_hidden[256] = {};
     int filter = VOLYM_FILTER_NEAREST;
     uint8_t lut[256 * 4] = {};
     uint32_t tf_n = 0;

@@ -121,6 +121,19 @@ public:
         for (int i = 0; i < 3; ++i) { lo[i] = crop_texel(lo01[i], n[i]); hi[i] = crop_texel(hi01[i], n[i]); }
         ctx.check(volym_set_crop_box(ctx.handle(), lo, hi));
     }
+    // New: hide the segments with the given label values and show all others (volym_set_segment_visibility).  The labels go to the
+    // device first if they are not there yet; the importances stay what they were.
+    void set_hidden(const GpuContext& ctx, const SimpleAssets& a, const std::vector<uint8_t>& hidden_label_values)
+    {
+        uint8_t visible[256];
+        for (int l = 0; l < 256; ++l) visible[l] = 1;
+        for (uint8_t l : hidden_label_values) visible[l] = 0;
+        if (!labels_on_device_) {
+            if (hidden_label_values.empty()) return;
+            set_labels(ctx, a);
+        }
+        ctx.check(volym_set_segment_visibility(ctx.handle(), visible));
+    }
     static uint32_t crop_texel(float p, uint32_t n)
     {
         const double t = std::floor(static_cast<double>(p) * n + 0.5);

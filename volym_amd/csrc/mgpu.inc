@@ -401,6 +401,14 @@ int volym_mgpu_set_crop_box(volym_mgpu* m, const uint32_t lo[3], const uint32_t 
     return VOLYM_OK;
 }
 
+int volym_mgpu_set_segment_visibility(volym_mgpu* m, const uint8_t visible[256])
+{
+    if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
+    for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_segment_visibility(L.ctx, visible));
+    return VOLYM_OK;
+}
+
 int volym_mgpu_set_transfer_function(volym_mgpu* m, const uint8_t* rgba8, uint32_t n)
 {
     if (!m) return VOLYM_E_INVALID;

@@ -1184,10 +1184,17 @@ static bool imp_croppable(const volym_ctx* c)
 
 static bool imp_from_labels(const volym_ctx* c) { return c->d_labels && c->have_seg_table; }
 
-// dst = inside(c->crop) ? source : 0 over one slab, on slot 0's stream (table: the source holds labels)
-static int launch_crop_slab(volym_ctx* c, const uint8_t* src, uint8_t* dst, const uint8_t* table, bool bricked, const uint32_t slab[6])
+// a hidden label that has voxels (hiding label values no voxel carries changes no byte)
+static bool mask_active(const volym_ctx* c)
 {
-    CropSlab s = {};
+    for (int l = 0; l < 256; ++l) if (c->seg_hidden[l] && c->label_count[l] != 0u) return true;
+    return false;
+}
+
+// the walk of the slab kernels over one slab [slab[0..2], slab[3..5]) of a volume in the given layout; returns its items
+static uint64_t make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t slab[6], CropSlab& s)
+{
+    s = CropSlab{};
     for (int a = 0; a < 3; ++a) { s.lo[a] = slab[a]; s.hi[a] = slab[3 + a]; s.box_lo[a] = c->crop_lo[a]; s.box_hi[a] = c->crop_hi[a]; }
     uint64_t items;
     if (bricked) {
@@ -1203,6 +1210,39 @@ static int launch_crop_slab(volym_ctx* c, const uint8_t* src, uint8_t* dst, cons
         s.chunks_per_run = static_cast<uint32_t>((run + 15u) / 16u) + 1u;
         items = static_cast<uint64_t>(s.chunks_per_run) * s.runs_y * s.runs_z;
     }
+    return items;
+}
+
+// dst = (inside(c->crop) && visible(label)) ? source : 0 over one box of texels, on slot 0's stream, by volym_visibility_kernel:
+// only the chunks that hold a texel of a label in `flipped` are rewritten (NULL: every chunk).  table: the labels are the source.
+static int launch_visibility(volym_ctx* c, const uint8_t* src, uint8_t* dst, const uint8_t* table, bool bricked, const uint32_t box[6], const uint8_t* flipped)
+{
+    CropSlab s;
+    const uint64_t items = make_crop_slab(c, bricked, box, s);
+    if (items == 0u) return VOLYM_OK;
+    LabelTable t = {}, m = {};
+    if (table) std::memcpy(t.v, table, 256);
+    for (int l = 0; l < 256; ++l) m.v[l] = static_cast<uint8_t>((c->seg_hidden[l] ? 0u : 1u) | ((!flipped || flipped[l]) ? 2u : 0u));
+    const hipStream_t stream = c->slot0().stream;
+    const dim3 grid(stream_grid(c, items));
+    const uint4* labels = reinterpret_cast<const uint4*>(c->d_labels);
+    if (table)
+        hipLaunchKernelGGL(volym_visibility_kernel<true>, grid, dim3(256), 0, stream, labels, labels, reinterpret_cast<uint4*>(dst), t, m, s, c->nx, c->ny, c->nz,
+                           bricked ? 1u : 0u, static_cast<uint32_t>(items));
+    else
+        hipLaunchKernelGGL(volym_visibility_kernel<false>, grid, dim3(256), 0, stream, labels, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), t, m, s,
+                           c->nx, c->ny, c->nz, bricked ? 1u : 0u, static_cast<uint32_t>(items));
+    HIPCHK(c, hipGetLastError());
+    return VOLYM_OK;
+}
+
+// dst = inside(c->crop) ? source : 0 over one slab, on slot 0's stream (table: the source holds labels).  While a segment is
+// hidden the slab goes through the kernel that reads the labels as well; a context that hides nothing runs what it always ran.
+static int launch_crop_slab(volym_ctx* c, const uint8_t* src, uint8_t* dst, const uint8_t* table, bool bricked, const uint32_t slab[6])
+{
+    if (mask_active(c)) return launch_visibility(c, src, dst, table, bricked, slab, nullptr);
+    CropSlab s;
+    const uint64_t items = make_crop_slab(c, bricked, slab, s);
     if (items == 0u) return VOLYM_OK;
     LabelTable t = {};
     if (table) std::memcpy(t.v, table, 256);
@@ -1255,11 +1295,15 @@ static void crop_important_box(volym_ctx* c)
     for (int i = 0; i < c->n_slots(); ++i) set_reject_box(c, c->slots[i]->fp);
 }
 
-// Rewrite the importances (which hold their uncropped bytes everywhere) to the crop box: zero what lies outside.
+static uint32_t visibility_boxes(const volym_ctx* c, const uint8_t flipped[256], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6]);
+
+// Rewrite the importances (which hold their uncropped bytes everywhere, hidden segments included) to the crop box and the
+// visibility mask: zero what lies outside the box, then the hidden segments inside it.
 static int crop_fresh_importances(volym_ctx* c)
 {
     crop_important_box(c);
-    if (!crop_active(c) || !imp_croppable(c)) return VOLYM_OK;
+    const bool masked = mask_active(c);
+    if ((!crop_active(c) && !masked) || !imp_croppable(c)) return VOLYM_OK;
     int rc = ensure_uncropped_copies(c, false, true);
     if (rc != VOLYM_OK) return rc;
     const uint32_t zero[3] = {0u, 0u, 0u}, dims[3] = {c->nx, c->ny, c->nz};
@@ -1268,6 +1312,14 @@ static int crop_fresh_importances(volym_ctx* c)
     for (uint32_t i = 0; i < n && rc == VOLYM_OK; ++i)
         rc = imp_from_labels(c) ? launch_crop_slab(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, slabs[i])
                                 : launch_crop_slab(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, slabs[i]);
+    if (masked && rc == VOLYM_OK) {
+        // inside the box the bytes are those of "all visible": the hidden labels are the ones that flip
+        uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6];
+        const uint32_t nb = visibility_boxes(c, c->seg_hidden, boxes);
+        for (uint32_t i = 0; i < nb && rc == VOLYM_OK; ++i)
+            rc = imp_from_labels(c) ? launch_visibility(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, boxes[i], c->seg_hidden)
+                                    : launch_visibility(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, boxes[i], c->seg_hidden);
+    }
     if (rc != VOLYM_OK) return rc;
     HIPCHK(c, hipStreamSynchronize(c->slot0().stream));
     return VOLYM_OK;
@@ -1278,6 +1330,33 @@ static int crop_fresh_importances(volym_ctx* c)
 // as it was; one after it leaves bytes that belong to neither box, and the context then asks for volym_set_volume again, as it
 // does when volym_set_volume itself fails.
 static int apply_crop_work(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol);
+
+// The maxima of the macro cells whose voxel range (slack included) meets one of n boxes of rewritten texels (the others cover no
+// texel that changed), their host copy and the occupied-cell boxes; every slot's distance field and hulls become stale.
+static int refresh_macro_cells(volym_ctx* c, const uint32_t (*boxes)[6], uint32_t n)
+{
+    const hipStream_t stream = c->slot0().stream;
+    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
+    for (uint32_t i = 0; i < n; ++i) {
+        CellRange r;
+        bool any = true;
+        for (int a = 0; a < 3; ++a) {
+            uint32_t c0 = c->mc_n, c1 = 0;
+            for (uint32_t k = 0; k < c->mc_n; ++k)
+                if (mc_voxel_lo(k, dims[a], c->mc_n) < boxes[i][3 + a] && mc_voxel_hi(k, dims[a], c->mc_n) > boxes[i][a]) { c0 = std::min(c0, k); c1 = k + 1u; }
+            any = any && c0 < c1;
+            r.c0[a] = c0; r.cn[a] = any ? c1 - c0 : 0u;
+        }
+        if (!any) continue;
+        hipLaunchKernelGGL(volym_macrocell_kernel, dim3(r.cn[0] * r.cn[1] * r.cn[2]), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n,
+                           c->bricked ? 1u : 0u, r);
+        HIPCHK(c, hipGetLastError());
+    }
+    const int rc = read_macro_cells(c);
+    if (rc != VOLYM_OK) return rc;
+    for (int i = 0; i < c->n_slots(); ++i) { c->slots[i]->df_thr_byte = 0xffffffffu; c->slots[i]->hull_dirty = true; }
+    return VOLYM_OK;
+}
 
 static int apply_crop(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol)
 {
@@ -1306,26 +1385,8 @@ static int apply_crop_work(volym_ctx* c, const uint32_t lo[3], const uint32_t hi
     }
     const hipStream_t stream = c->slot0().stream;
     if (do_vol) {
-        // the maxima of the cells whose voxel range (slack included) meets a slab; the others cover no texel that changed
-        const uint32_t dims[3] = {c->nx, c->ny, c->nz};
-        for (uint32_t i = 0; i < n; ++i) {
-            CellRange r;
-            bool any = true;
-            for (int a = 0; a < 3; ++a) {
-                uint32_t c0 = c->mc_n, c1 = 0;
-                for (uint32_t k = 0; k < c->mc_n; ++k)
-                    if (mc_voxel_lo(k, dims[a], c->mc_n) < slabs[i][3 + a] && mc_voxel_hi(k, dims[a], c->mc_n) > slabs[i][a]) { c0 = std::min(c0, k); c1 = k + 1u; }
-                any = any && c0 < c1;
-                r.c0[a] = c0; r.cn[a] = any ? c1 - c0 : 0u;
-            }
-            if (!any) continue;
-            hipLaunchKernelGGL(volym_macrocell_kernel, dim3(r.cn[0] * r.cn[1] * r.cn[2]), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n,
-                               c->bricked ? 1u : 0u, r);
-            HIPCHK(c, hipGetLastError());
-        }
-        rc = read_macro_cells(c);
+        rc = refresh_macro_cells(c, slabs, n);
         if (rc != VOLYM_OK) return rc;
-        for (int i = 0; i < c->n_slots(); ++i) { c->slots[i]->df_thr_byte = 0xffffffffu; c->slots[i]->hull_dirty = true; }
     }
     HIPCHK(c, hipStreamSynchronize(stream));       // every slot's next frame reads the new bytes
     crop_important_box(c);
@@ -1356,12 +1417,175 @@ int volym_get_crop_box(volym_ctx* c, uint32_t lo[3], uint32_t hi[3])
     return VOLYM_OK;
 }
 
+// ---- segment visibility on the device ------------------------------------------------------------------------------------
+// A frame with mask `visible` is the frame of the scene whose density and importance bytes are 0 in every texel of a hidden
+// label (and outside the crop box).  As with the crop box the march kernels know nothing of it: volym_set_segment_visibility
+// rewrites d_vol and d_imp from their uncropped sources, over the texels an edit can change -- those inside the label boxes
+// (volym_set_labels) of the labels that flipped, cut to the crop box -- and volym_visibility_kernel skips every chunk in there
+// that holds no texel of such a label.  Which boxes: volym_visibility_boxes.
+
+int volym_visibility_boxes(const uint8_t flipped[256], const uint64_t counts[256], const int32_t label_boxes[256][6], const uint32_t crop_lo[3],
+                           const uint32_t crop_hi[3], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6], uint32_t* n_boxes)
+{
+    if (!flipped || !counts || !label_boxes || !crop_lo || !crop_hi || !boxes || !n_boxes) return VOLYM_E_INVALID;
+    for (int a = 0; a < 3; ++a) if (crop_lo[a] > crop_hi[a]) return VOLYM_E_INVALID;
+    auto volume = [](const uint32_t b[6]) { return static_cast<uint64_t>(b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]); };
+    auto hull = [](const uint32_t p[6], const uint32_t q[6], uint32_t out[6]) {
+        for (int a = 0; a < 3; ++a) { out[a] = std::min(p[a], q[a]); out[3 + a] = std::max(p[3 + a], q[3 + a]); }
+    };
+    uint32_t n = 0;
+    for (int l = 0; l < 256; ++l) {
+        if (!flipped[l] || counts[l] == 0u) continue;
+        uint32_t b[6];
+        bool empty = false;
+        for (int a = 0; a < 3; ++a) {
+            if (label_boxes[l][a] < 0 || label_boxes[l][3 + a] < label_boxes[l][a]) return VOLYM_E_INVALID;
+            b[a] = std::max(static_cast<uint32_t>(label_boxes[l][a]), crop_lo[a]);
+            b[3 + a] = std::min(static_cast<uint32_t>(label_boxes[l][3 + a]) + 1u, crop_hi[a]);
+            empty = empty || b[a] >= b[3 + a];
+        }
+        if (empty) continue;
+        // into the first box whose hull with this one holds no more texels than the two apart; else a box of its own while there
+        // is room; else into the box that grows least
+        uint32_t h[6], best = n;
+        uint64_t best_growth = ~0ull;
+        for (uint32_t i = 0; i < n; ++i) {
+            hull(boxes[i], b, h);
+            const uint64_t hv = volume(h), vi = volume(boxes[i]);
+            if (hv <= vi + volume(b)) { best = i; break; }
+            if (n == VOLYM_VISIBILITY_MAX_BOXES && hv - vi < best_growth) { best_growth = hv - vi; best = i; }
+        }
+        if (best == n) { std::memcpy(boxes[n++], b, sizeof b); continue; }
+        hull(boxes[best], b, h);
+        std::memcpy(boxes[best], h, sizeof h);
+    }
+    // boxes that grew may now pay to merge with each other
+    for (bool merged = true; merged;) {
+        merged = false;
+        for (uint32_t i = 0; i < n && !merged; ++i)
+            for (uint32_t j = i + 1u; j < n && !merged; ++j) {
+                uint32_t h[6];
+                hull(boxes[i], boxes[j], h);
+                if (volume(h) > volume(boxes[i]) + volume(boxes[j])) continue;
+                std::memcpy(boxes[i], h, sizeof h);
+                std::memcpy(boxes[j], boxes[n - 1u], sizeof h);
+                --n;
+                merged = true;
+            }
+    }
+    *n_boxes = n;
+    return VOLYM_OK;
+}
+
+static uint32_t visibility_boxes(const volym_ctx* c, const uint8_t flipped[256], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6])
+{
+    uint32_t n = 0;
+    (void)volym_visibility_boxes(flipped, c->label_count, c->label_box, c->crop_lo, c->crop_hi, boxes, &n);
+    return n;
+}
+
+// imp_box0_* of importances mapped from the labels: the union of the boxes of the labels the table makes important and the
+// mask shows -- what important_texel_box would find in the mapped bytes, or a box around it
+static void segment_important_box(volym_ctx* c)
+{
+    int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+    for (int l = 0; l < 256; ++l) {
+        if (c->seg_table[l] < 128u || c->seg_hidden[l] || c->label_count[l] == 0u) continue;
+        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c->label_box[l][a]); hi[a] = std::max(hi[a], c->label_box[l][3 + a]); }
+    }
+    for (int a = 0; a < 3; ++a) {
+        if (hi[0] < 0) { c->imp_box0_lo[a] = 1; c->imp_box0_hi[a] = 0; continue; }
+        c->imp_box0_lo[a] = lo[a]; c->imp_box0_hi[a] = hi[a];
+    }
+}
+
+static int apply_visibility_work(volym_ctx* c, const uint8_t hidden[256], bool do_vol)
+{
+    uint8_t flipped[256];
+    for (int l = 0; l < 256; ++l) { flipped[l] = c->seg_hidden[l] != hidden[l]; c->seg_hidden[l] = hidden[l]; }
+    uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6];
+    const uint32_t n = visibility_boxes(c, flipped, boxes);
+    const bool imp = imp_croppable(c);
+    int rc = VOLYM_OK;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (do_vol) rc = launch_visibility(c, c->d_vol0, c->d_vol, nullptr, c->bricked, boxes[i], flipped);
+        if (rc == VOLYM_OK && imp)
+            rc = imp_from_labels(c) ? launch_visibility(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, boxes[i], flipped)
+                                    : launch_visibility(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, boxes[i], flipped);
+        if (rc != VOLYM_OK) return rc;
+    }
+    if (do_vol && n != 0u) {
+        rc = refresh_macro_cells(c, boxes, n);
+        if (rc != VOLYM_OK) return rc;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));       // every slot's next frame reads the new bytes
+    if (imp_from_labels(c)) segment_important_box(c);          // (uploaded importances keep their box: it is conservative)
+    crop_important_box(c);
+    return rebuild_lists(c);
+}
+
+// The mask becomes `hidden` (0 / 1 per label; the caller has checked that the labels fit the volume).  Blocking set-up path with
+// the failure rule of apply_crop.
+static int apply_visibility(volym_ctx* c, const uint8_t hidden[256], bool do_vol)
+{
+    int rc = quiesce_slots(c);
+    if (rc != VOLYM_OK) return rc;
+    rc = ensure_uncropped_copies(c, do_vol, true);
+    if (rc != VOLYM_OK) return rc;
+    rc = apply_visibility_work(c, hidden, do_vol);
+    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
+    return rc;
+}
+
+// volym_set_labels, volym_set_importances and volym_set_volume start from "all visible": the hidden texels get their bytes back
+// (those of the density only where it stays, do_vol)
+static int show_all_segments(volym_ctx* c, bool do_vol)
+{
+    if (!c->have_vol || !mask_active(c)) {
+        std::memset(c->seg_hidden, 0, sizeof c->seg_hidden);
+        return VOLYM_OK;
+    }
+    const uint8_t none[256] = {};
+    return apply_visibility(c, none, do_vol);
+}
+
+int volym_set_segment_visibility(volym_ctx* c, const uint8_t visible[256])
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!visible) return fail(c, VOLYM_E_INVALID, "volym_set_segment_visibility: NULL table");
+    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: no volume (volym_set_volume first)");
+    if (!c->d_labels) return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: no labels (volym_set_labels first; volym_set_importances drops them)");
+    if (c->lnx != c->nx || c->lny != c->ny || c->lnz != c->nz)
+        return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: the labels' dimensions are not the volume's");
+    if (c->labels_bricked != c->bricked || (imp_croppable(c) && c->imp_bricked != c->labels_bricked))
+        return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: volume, importances and labels were uploaded under different VOLYM_OPT_VOLUME_LAYOUT settings");
+    uint8_t hidden[256];
+    bool changes = false;                  // a flipped label that has voxels: anything else changes no byte
+    for (int l = 0; l < 256; ++l) { hidden[l] = visible[l] ? 0u : 1u; changes = changes || (hidden[l] != c->seg_hidden[l] && c->label_count[l] != 0u); }
+    if (!changes) {
+        std::memcpy(c->seg_hidden, hidden, sizeof hidden);
+        return VOLYM_OK;
+    }
+    return apply_visibility(c, hidden, true);
+}
+
+int volym_get_segment_visibility(volym_ctx* c, uint8_t visible[256])
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!visible) return fail(c, VOLYM_E_INVALID, "volym_get_segment_visibility: NULL output");
+    for (int l = 0; l < 256; ++l) visible[l] = c->seg_hidden[l] ? 0u : 1u;
+    return VOLYM_OK;
+}
+
 int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t ny, uint32_t nz, int filter)
 {
     if (!c) return VOLYM_E_INVALID;
     if (filter != VOLYM_FILTER_NEAREST && filter != VOLYM_FILTER_LINEAR)
         return fail(c, VOLYM_E_INVALID, "volym_set_volume: filter must be VOLYM_FILTER_NEAREST or VOLYM_FILTER_LINEAR");
-    int rc;
+    // the mask goes back to all visible and the importances get their hidden texels back (like the box below, before
+    // upload_volume has looked at the arguments)
+    int rc = show_all_segments(c, false);
+    if (rc != VOLYM_OK) return rc;
     if (c->have_vol && crop_active(c)) {
         // the box goes back to the whole volume: the importances get their cropped texels back (the density is replaced below).
         // This runs before upload_volume has looked at its arguments: a call that then fails leaves the box reset and no volume
@@ -1418,7 +1642,11 @@ static void important_texel_box(const uint8_t* imp, uint32_t nx, uint32_t ny, ui
 int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!c) return VOLYM_E_INVALID;
-    int rc = upload_volume(c, &c->d_imp, importances, nx, ny, nz);
+    // the labels go, and the mask with them: the density gets its hidden texels back (the importances are replaced below).  A
+    // call that then fails on its arguments leaves the mask reset.
+    int rc = show_all_segments(c, true);
+    if (rc != VOLYM_OK) return rc;
+    rc = upload_volume(c, &c->d_imp, importances, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_imp = false; c->imp_bytes = 0; return rc; }
     c->imp_bytes = layout_bytes(want_bricked(c, nx, ny, nz), nx, ny, nz) + 16u;
     // the importances are the caller's now: a segment table has no labels to map any more
@@ -1450,7 +1678,10 @@ static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks)
 int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!c) return VOLYM_E_INVALID;
-    int rc;
+    // new labels mean new segments: all visible, and density and importances get their hidden texels back while the labels
+    // that say which they are still exist
+    int rc = show_all_segments(c, true);
+    if (rc != VOLYM_OK) return rc;
     if (imp_from_labels(c) && crop_active(c) && imp_croppable(c) && !c->d_imp0) {
         // the importances stay as they are, cropped, and the labels they were mapped from go: keep their uncropped bytes
         rc = quiesce_slots(c);
@@ -1525,23 +1756,15 @@ int volym_set_segment_importances(volym_ctx* c, const uint8_t table[256])
                        reinterpret_cast<uint4*>(c->d_imp), t, c->lnx, c->lny, c->lnz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(stream));       // every slot's next frame reads the new bytes
-    int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
-    for (int l = 0; l < 256; ++l) {
-        if (table[l] < 128u || c->label_count[l] == 0u) continue;
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c->label_box[l][a]); hi[a] = std::max(hi[a], c->label_box[l][3 + a]); }
-    }
-    for (int a = 0; a < 3; ++a) {
-        if (hi[0] < 0) { c->imp_box0_lo[a] = 1; c->imp_box0_hi[a] = 0; continue; }
-        c->imp_box0_lo[a] = lo[a]; c->imp_box0_hi[a] = hi[a];
-    }
     c->inx = c->lnx; c->iny = c->lny; c->inz = c->lnz;
     c->have_imp = true;
     // from here on the labels and this table are the uncropped importances
     std::memcpy(c->seg_table, table, 256);
     c->have_seg_table = true;
+    segment_important_box(c);                // (of the visible segments)
     c->imp_bricked = c->labels_bricked;
     if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
-    // the crop box (if any) cuts the new importances, and the frames enqueued from here on march the new reject box, with or
+    // the crop box and the mask (if any) cut the new importances, and the frames enqueued from here on march the new reject box, with or
     // without a volym_update in between
     rc = crop_fresh_importances(c);
     if (rc != VOLYM_OK) { c->have_imp = false; return rc; }

@@ -815,6 +815,61 @@ struct CropSlab {
     uint32_t b_lo[3], b_n[3];       // bricked walk: first brick and bricks per axis
 };
 
+// Item i of the walk over slab s: its chunk k and `keep` (bit b: byte b of the chunk is a texel inside the box).  False: the item
+// has no chunk (a bricked chunk whose z is outside the slab, the spare chunk of a linear run).
+__device__ inline bool crop_chunk(const CropSlab& s, uint32_t i, uint32_t nx, uint32_t ny, uint64_t n, uint32_t bricked, uint32_t bx, uint32_t by,
+                                  uint64_t& k, uint32_t& keep)
+{
+    keep = 0;
+    if (bricked) {
+        const uint32_t zz = i & 3u, b = i >> 2;
+        const uint32_t bxi = s.b_lo[0] + b % s.b_n[0], byi = s.b_lo[1] + (b / s.b_n[0]) % s.b_n[1], bzi = s.b_lo[2] + b / (s.b_n[0] * s.b_n[1]);
+        const uint32_t z = bzi * 4u + zz;
+        if (z < s.lo[2] || z >= s.hi[2]) return false;
+        k = (static_cast<uint64_t>(bzi) * by + byi) * bx + bxi;
+        k = k * 4u + zz;
+        if (z >= s.box_lo[2] && z < s.box_hi[2]) {
+            uint32_t row = 0;
+            for (uint32_t j = 0; j < 4u; ++j) { const uint32_t x = bxi * 4u + j; if (x >= s.box_lo[0] && x < s.box_hi[0]) row |= 1u << j; }
+            for (uint32_t r = 0; r < 4u; ++r) { const uint32_t y = byi * 4u + r; if (y >= s.box_lo[1] && y < s.box_hi[1]) keep |= row << (4u * r); }
+        }
+    } else {
+        const uint32_t ci = i % s.chunks_per_run, r = i / s.chunks_per_run;
+        const uint32_t ry = r % s.runs_y, rz = r / s.runs_y;
+        const uint64_t start = s.lo[0] + static_cast<uint64_t>(nx) * ((s.lo[1] + ry) + static_cast<uint64_t>(ny) * (s.lo[2] + rz));
+        k = (start >> 4) + ci;
+        if ((k << 4) >= start + s.run_len) return false;
+        const uint64_t o = k << 4, slice = static_cast<uint64_t>(nx) * ny;
+        uint32_t z = static_cast<uint32_t>(o / slice);
+        const uint32_t rem = static_cast<uint32_t>(o - z * slice);
+        uint32_t y = rem / nx, x = rem - y * nx;
+        for (uint32_t j = 0; j < 16u; ++j) {
+            if (o + j < n && x >= s.box_lo[0] && x < s.box_hi[0] && y >= s.box_lo[1] && y < s.box_hi[1] && z >= s.box_lo[2] && z < s.box_hi[2]) keep |= 1u << j;
+            if (++x == nx) { x = 0; if (++y == ny) { y = 0; ++z; } }
+        }
+    }
+    return true;
+}
+
+// the bytes of chunk v that `keep` names, each through the table (TABLE) or as it is; the others 0
+template <bool TABLE>
+__device__ inline uint4 crop_chunk_value(uint4 v, uint32_t keep, const uint8_t* s_tab)
+{
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t o = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            if (!(keep & (1u << (4 * j + b)))) continue;
+            const uint32_t byte = (w[j] >> (8 * b)) & 0xffu;
+            o |= (TABLE ? static_cast<uint32_t>(s_tab[byte & (TABLE ? 255u : 0u)]) : byte) << (8 * b);
+        }
+        w[j] = o;
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
 template <bool TABLE>
 __global__ __launch_bounds__(256) void volym_crop_slab_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, LabelTable table, CropSlab s,
                                                               uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
@@ -827,52 +882,50 @@ __global__ __launch_bounds__(256) void volym_crop_slab_kernel(const uint4* __res
     const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
-        uint64_t k;                  // chunk
-        uint32_t keep = 0;           // bit b: byte b of the chunk is a texel inside the box
-        if (bricked) {
-            const uint32_t zz = i & 3u, b = i >> 2;
-            const uint32_t bxi = s.b_lo[0] + b % s.b_n[0], byi = s.b_lo[1] + (b / s.b_n[0]) % s.b_n[1], bzi = s.b_lo[2] + b / (s.b_n[0] * s.b_n[1]);
-            const uint32_t z = bzi * 4u + zz;
-            if (z < s.lo[2] || z >= s.hi[2]) continue;
-            k = (static_cast<uint64_t>(bzi) * by + byi) * bx + bxi;
-            k = k * 4u + zz;
-            if (z >= s.box_lo[2] && z < s.box_hi[2]) {
-                uint32_t row = 0;
-                for (uint32_t j = 0; j < 4u; ++j) { const uint32_t x = bxi * 4u + j; if (x >= s.box_lo[0] && x < s.box_hi[0]) row |= 1u << j; }
-                for (uint32_t r = 0; r < 4u; ++r) { const uint32_t y = byi * 4u + r; if (y >= s.box_lo[1] && y < s.box_hi[1]) keep |= row << (4u * r); }
-            }
-        } else {
-            const uint32_t ci = i % s.chunks_per_run, r = i / s.chunks_per_run;
-            const uint32_t ry = r % s.runs_y, rz = r / s.runs_y;
-            const uint64_t start = s.lo[0] + static_cast<uint64_t>(nx) * ((s.lo[1] + ry) + static_cast<uint64_t>(ny) * (s.lo[2] + rz));
-            k = (start >> 4) + ci;
-            if ((k << 4) >= start + s.run_len) continue;
-            const uint64_t o = k << 4, slice = static_cast<uint64_t>(nx) * ny;
-            uint32_t z = static_cast<uint32_t>(o / slice);
-            const uint32_t rem = static_cast<uint32_t>(o - z * slice);
-            uint32_t y = rem / nx, x = rem - y * nx;
-            for (uint32_t j = 0; j < 16u; ++j) {
-                if (o + j < n && x >= s.box_lo[0] && x < s.box_hi[0] && y >= s.box_lo[1] && y < s.box_hi[1] && z >= s.box_lo[2] && z < s.box_hi[2]) keep |= 1u << j;
-                if (++x == nx) { x = 0; if (++y == ny) { y = 0; ++z; } }
-            }
-        }
-        uint32_t w[4] = {0u, 0u, 0u, 0u};
-        if (keep) {
-            const uint4 v = src[k];
-            w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+        uint64_t k;
+        uint32_t keep;
+        if (!crop_chunk(s, i, nx, ny, n, bricked, bx, by, k, keep)) continue;
+        dst[k] = keep ? crop_chunk_value<TABLE>(src[k], keep, s_tab) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// ---- segment visibility on the device (volym_set_segment_visibility) ------------------------------------------------------
+// dst = (inside(box) && visible[label]) ? value(src) : 0 over one box of texels, walked as volym_crop_slab_kernel walks a slab (same
+// CropSlab, same items, both layouts).  `labels` has the dimensions and layout of src and dst.  TABLE: the labels are the source
+// themselves (value = table[label], src is not read).  mask.v[l]: bit 0 = label l is visible, bit 1 = its visibility flipped in
+// this edit.  The label chunk is read first; a chunk with no texel of a flipped label is neither loaded from src nor stored:
+// dst already holds there what the rule gives (the host keeps it so, context.hpp).  A chunk that is stored is stored whole by the
+// new rule, which leaves its other bytes as they are.  A crop edit under a mask runs this kernel over its slabs with every
+// label marked flipped.  Both tables are a byte per label in LDS: a lane indexes them with its own label, which a mask held as
+// eight dwords of kernel arguments (SGPRs) cannot serve without a select chain per byte.
+template <bool TABLE>
+__global__ __launch_bounds__(256) void volym_visibility_kernel(const uint4* __restrict__ labels, const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                               LabelTable table, LabelTable mask, CropSlab s, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                               uint32_t bricked, uint32_t n_items)
+{
+    __shared__ uint8_t s_mask[256];
+    __shared__ uint8_t s_tab[TABLE ? 256 : 1];
+    s_mask[threadIdx.x] = mask.v[threadIdx.x];
+    if (TABLE) s_tab[threadIdx.x] = table.v[threadIdx.x];
+    __syncthreads();
+    const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
+    const uint32_t bx = brick_count(nx), by = brick_count(ny);
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
+        uint64_t k;
+        uint32_t keep;
+        if (!crop_chunk(s, i, nx, ny, n, bricked, bx, by, k, keep)) continue;
+        const uint4 lv = labels[k];
+        const uint32_t l[4] = {lv.x, lv.y, lv.z, lv.w};
+        uint32_t flipped = 0, visible = 0;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                uint32_t o = 0;
-#pragma unroll
-                for (int b = 0; b < 4; ++b) {
-                    if (!(keep & (1u << (4 * j + b)))) continue;
-                    const uint32_t byte = (w[j] >> (8 * b)) & 0xffu;
-                    o |= (TABLE ? static_cast<uint32_t>(s_tab[byte & (TABLE ? 255u : 0u)]) : byte) << (8 * b);
-                }
-                w[j] = o;
-            }
+        for (int j = 0; j < 16; ++j) {
+            const uint32_t m = s_mask[(l[j >> 2] >> (8 * (j & 3))) & 0xffu];
+            flipped |= m;
+            visible |= (m & 1u) << j;
         }
-        dst[k] = make_uint4(w[0], w[1], w[2], w[3]);
+        if (!(flipped & 2u)) continue;
+        keep &= visible;
+        dst[k] = keep ? crop_chunk_value<TABLE>(TABLE ? lv : src[k], keep, s_tab) : make_uint4(0u, 0u, 0u, 0u);
     }
 }
 

@@ -42,6 +42,7 @@ struct Options {
     bool debug = false;
     bool crop = false;             // --crop x0,y0,z0,x1,y1,z1: crop box in unit-cube coordinates (run simple)
     float crop_lo[3] = {0.0f, 0.0f, 0.0f}, crop_hi[3] = {1.0f, 1.0f, 1.0f};
+    std::vector<uint8_t> hide;     // --hide 3,4: label values of the segments to hide (run simple)
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -160,6 +161,7 @@ int run_simple(const Options& o)
     state.update();
     Simple demo = Simple::init(ctx, state, assets);
     if (o.crop) demo.set_crop(ctx, assets, o.crop_lo, o.crop_hi);
+    if (!o.hide.empty()) demo.set_hidden(ctx, assets, o.hide);
     demo.update_gpu_state(ctx, state);
     demo.compute_pass(ctx);
     ctx.check(volym_sync(ctx.handle()));
@@ -201,7 +203,21 @@ int main(int argc, char** argv)
                 for (int k = 0; k < 3; ++k) { o.crop_lo[k] = f[k]; o.crop_hi[k] = f[3 + k]; }
                 o.crop = true;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1]\n"); return 2; }
+            else if (a == "--hide") {
+                const std::string v = next();
+                size_t pos = 0;
+                while (pos <= v.size()) {
+                    const size_t comma = std::min(v.find(',', pos), v.size());
+                    size_t used = 0;
+                    const std::string item = v.substr(pos, comma - pos);
+                    int l = -1;
+                    try { l = std::stoi(item, &used); } catch (const std::exception&) { used = 0; }
+                    if (item.empty() || used != item.size() || l < 0 || l > 255) throw Error(VOLYM_E_INVALID, "--hide: label values 0..255, comma separated");
+                    o.hide.push_back(static_cast<uint8_t>(l));
+                    pos = comma + 1u;
+                }
+            }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--hide l,l,...]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

@@ -124,6 +124,19 @@ class GpuContext:
         self._ck(_lib.lib().volym_get_crop_box(self.handle, lo3, hi3))
         return tuple(int(v) for v in lo3), tuple(int(v) for v in hi3)
 
+    def set_segment_visibility(self, visible):
+        """256 flags, one per label value (nonzero = visible): density and importances of the hidden segments count as 0 from
+        the next compute pass on.  Needs the labels on the device (set_labels).  No upload; the device rewrites the texels
+        inside the boxes of the labels that flipped."""
+        v = scene.check_segment_visibility(visible)
+        self._ck(_lib.lib().volym_set_segment_visibility(self.handle, scene._u8p(v)))
+
+    def segment_visibility(self):
+        """The current mask (np.uint8[256] of 0 / 1); all 1 when nothing is hidden."""
+        out = np.zeros(256, np.uint8)
+        self._ck(_lib.lib().volym_get_segment_visibility(self.handle, scene._u8p(out)))
+        return out
+
     # ---- per frame --------------------------------------------------------------------------
     def update(self, camera_uniforms, parameter_uniforms):
         self._ck(_lib.lib().volym_update(self.handle, C.byref(camera_uniforms), C.byref(parameter_uniforms)))
@@ -268,6 +281,9 @@ class Simple(ComputeDemo):
         tf = transfer_function if transfer_function is not None else scene.TransferFunction.default()
         ctx.set_transfer_function(tf.bake_rgba8())
         self = cls(dims)
+        self._labels_raw = np.ascontiguousarray(labels_raw, np.uint8).ravel()
+        self._labels_on_device = False
+        self._segments = segments
         self.update_gpu_state(ctx, state)   # GpuCamera::new / GpuParameters::new upload initial state
         return self
 
@@ -285,6 +301,27 @@ class Simple(ComputeDemo):
         lo, hi = scene.crop_box_texels(lo01, hi01, self.dims)
         ctx.set_crop_box(lo, hi)
         return lo, hi
+
+    def set_hidden(self, ctx, hidden):
+        """Hide the given segments and show all others (an editor's "hide the cup so that I can see the lobster").  `hidden`:
+        ids of the segments JSON ("Segment_4") or raw label values (3), mixed freely.  The labels go to the device first if
+        they are not there yet; the importances stay what they were.  Returns the hidden label values, sorted."""
+        by_id = {s["id"]: s["label_value"] for s in getattr(self, "_segments", []) if "id" in s}
+        values = set()
+        for h in hidden:
+            if isinstance(h, str):
+                if h not in by_id:
+                    raise ValueError("no segment with id %r" % h)
+                values.add(by_id[h])
+            else:
+                values.add(int(h))
+        mask = scene.visibility_mask(values)
+        if not self._labels_on_device:
+            if not values:
+                return []
+            self.set_labels(ctx, self._labels_raw)
+        ctx.set_segment_visibility(mask)
+        return sorted(values)
 
     def set_labels(self, ctx, labels_raw):
         """Keep the label map on the device (new; the reference maps it once on the host), so that set_segments can change

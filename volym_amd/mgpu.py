@@ -41,6 +41,7 @@ SIGNATURES = {
     "volym_mgpu_set_labels": (C.c_int, [_mg, _u8p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "volym_mgpu_set_segment_importances": (C.c_int, [_mg, _u8p]),
     "volym_mgpu_set_crop_box": (C.c_int, [_mg, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_mgpu_set_segment_visibility": (C.c_int, [_mg, _u8p]),
     "volym_mgpu_set_transfer_function": (C.c_int, [_mg, _u8p, C.c_uint32]),
     "volym_mgpu_set_option": (C.c_int, [_mg, C.c_int, C.c_int]),
     "volym_mgpu_update": (C.c_int, [_mg, C.POINTER(_lib.CameraUniforms), C.POINTER(_lib.ParameterUniforms)]),
@@ -145,6 +146,11 @@ class MultiGpu:
         """Crop box in texels of the prepared volume (lo inclusive, hi exclusive), on every local rank."""
         lo3, hi3 = (C.c_uint32 * 3)(*[int(v) for v in lo]), (C.c_uint32 * 3)(*[int(v) for v in hi])
         self._ck(lib().volym_mgpu_set_crop_box(self._h, lo3, hi3))
+
+    def set_segment_visibility(self, visible):
+        """256 flags, one per label value (nonzero = visible), on every local rank."""
+        v = scene.check_segment_visibility(visible)
+        self._ck(lib().volym_mgpu_set_segment_visibility(self._h, scene._u8p(v)))
 
     def set_transfer_function(self, rgba8):
         t = np.ascontiguousarray(rgba8, np.uint8).ravel()

@@ -195,6 +195,52 @@ def check_segment_table(table):
     return t
 
 
+def check_segment_visibility(visible):
+    """A visibility mask: 256 flags, one per label value, nonzero = visible.  Returns np.uint8[256] of 0 / 1."""
+    if isinstance(visible, (str, bytes, bytearray)) and len(visible) != 256:
+        raise ValueError("a visibility mask has 256 entries, not %d" % len(visible))
+    try:
+        v = np.asarray(visible)
+    except Exception:
+        raise ValueError("a visibility mask is 256 flags, one per label value")
+    if v.dtype == object or v.dtype.kind not in "buif":
+        raise ValueError("a visibility mask is 256 flags (bool or numbers), not %s" % v.dtype)
+    if v.ndim != 1 or v.size != 256:
+        raise ValueError("a visibility mask has 256 entries, not %s" % (v.shape,))
+    return (v != 0).astype(np.uint8)
+
+
+def visibility_mask(hidden_label_values):
+    """All visible except the given label values."""
+    v = np.ones(256, np.uint8)
+    for l in hidden_label_values:
+        if not 0 <= int(l) <= 255:
+            raise ValueError("a label value is a u8, got %r" % (l,))
+        v[int(l)] = 0
+    return v
+
+
+def hide_segments(prepared, labels, visible):
+    """The definition of segment visibility: a copy of the prepared bytes (density or importances) with every texel whose
+    label is hidden set to 0.  `labels`: the prepared label bytes, as many as `prepared`.  Composes with crop_volume."""
+    v = check_segment_visibility(visible)
+    src = np.ascontiguousarray(prepared, np.uint8).ravel()
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != src.size:
+        raise ValueError("labels have %d bytes, the volume %d" % (lab.size, src.size))
+    hidden = np.flatnonzero(v == 0)
+    if hidden.size <= 16:
+        # a compare per hidden label: a gather through the table would widen every label to an index first
+        gone = np.zeros(lab.shape, bool)
+        for l in hidden:
+            gone |= lab == l
+    else:
+        gone = (v == 0)[lab]
+    out = src.copy()
+    out[gone] = 0
+    return out
+
+
 def check_crop_box(lo, hi, dims):
     """A crop box in texels of the prepared volume (lo inclusive, hi exclusive, x first): lo <= hi <= n on every axis."""
     try:
