@@ -244,6 +244,80 @@ def test_lifetime(oracle, volym_lib, layout):
         _same("hide after set_volume", _three(dev, "hide after set_volume"), twin_frame(*_hide(vol, imp2, labels, (4,))))
 
 
+@pytest.mark.parametrize("layout", [0, 1], ids=["linear", "bricked"])
+@pytest.mark.parametrize("source", ["labels", "uploaded"])
+@pytest.mark.parametrize("call", ["set_volume", "set_labels", "set_importances", "set_segment_importances"])
+def test_lifetime_cropped_and_masked(oracle, volym_lib, call, source, layout):
+    """The set-up calls on a context that has BOTH a crop box and a mask.  volym_set_volume resets both and gives the importances
+    all their bytes back; volym_set_labels and volym_set_importances reset the mask and keep the box; volym_set_segment_importances
+    keeps both.  Every state bit-equal to a twin that is handed the host-zeroed bytes, and near the oracle."""
+    from volym_amd import scene
+    dims, vol, labels = _bonsai()
+    lut = scene.default_lut()
+    cam, par, cu, pu = _uniforms(oracle, W, H, (0.0, -80.0, 0.0), **PARAMS["straight"])     # the pot in front: its importance matters
+    box, hidden, full = ((5, 7, 9), (50, 61, 43)), (2, 4), ((0, 0, 0), dims)
+    first, second = _table(l2=255, l3=255), _table(l3=255, l4=255)
+    imp = first[labels]
+
+    def crop(a):
+        return scene.crop_volume(a, dims, *box)
+
+    with _ctx(layout) as dev, _ctx(layout) as twin:
+        dev.set_volume(vol, dims, 0)
+        dev.set_transfer_function(lut)
+        if source == "labels":
+            dev.set_labels(labels, dims)
+            dev.set_segment_importances(first)
+        else:
+            dev.set_importances(imp, dims)
+            dev.set_labels(labels, dims)
+        twin.set_transfer_function(lut)
+        dev.update(cu, pu)
+        _frame(dev)
+        dev.set_crop_box(*box)
+        dev.set_segment_visibility(_mask(hidden))
+        hvol, himp = _hide(vol, imp, labels, hidden)
+        tvol, timp = crop(hvol), crop(himp)
+        twin.set_volume(tvol, dims, 0)
+        twin.set_importances(timp, dims)
+        what = (call, source, layout, "cropped and masked")
+        cut = _three(dev, what)
+        _same(what + ("twin",), cut, _frame(twin, cu, pu))
+        _near(what, cut, _ref(oracle, ("both", "cut"), tvol, timp, dims, cam, par))
+        if call == "set_volume":
+            dev.set_volume(vol, dims, 0)
+            want_box, want_hidden, tvol, timp = full, ALL, vol, imp
+        elif call == "set_labels":
+            dev.set_labels(labels, dims)
+            want_box, want_hidden, tvol, timp = box, ALL, crop(vol), crop(imp)
+        elif call == "set_importances":
+            dev.set_importances(POT[labels], dims)
+            want_box, want_hidden, tvol, timp = box, ALL, crop(vol), crop(POT[labels])
+        else:
+            dev.set_segment_importances(second)
+            want_box, want_hidden = box, hidden
+            tvol, timp = (crop(a) for a in _hide(vol, second[labels], labels, hidden))
+        assert dev.crop_box() == want_box and np.array_equal(dev.segment_visibility(), _mask(want_hidden))
+        twin.set_volume(tvol, dims, 0)
+        twin.set_importances(timp, dims)
+        what = (call, source, layout, "after the call")
+        got = _three(dev, what, cu, pu)
+        _same(what + ("twin",), got, _frame(twin, cu, pu))
+        _near(what, got, _ref(oracle, ("both", call), tvol, timp, dims, cam, par))
+        if call != "set_segment_importances":               # (density comes back: the canopy and the pot, or all of the volume)
+            assert _changed(got[1], cut[1]) > 0.0, what
+        if call != "set_importances":
+            # the labels are still there, and the context edits on: the pot hidden inside the (kept or new) box
+            dev.set_crop_box(*box)
+            dev.set_segment_visibility(_mask((4,)))
+            src = second[labels] if call == "set_segment_importances" else imp
+            tvol, timp = (crop(a) for a in _hide(vol, src, labels, (4,)))
+            twin.set_volume(tvol, dims, 0)
+            twin.set_importances(timp, dims)
+            what = (call, source, layout, "edited on")
+            _same(what + ("twin",), _three(dev, what), _frame(twin, cu, pu))
+
+
 @pytest.mark.parametrize("slots", [1, 2], ids=["one slot", "two in flight"])
 def test_edit_between_enqueued_passes(oracle, volym_lib, slots):
     """A pass enqueued before the edit shows the old mask, the two enqueued after it the new one, with no volym_update and no

@@ -1,5 +1,6 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
-// logic that more than one translation unit needs (raymarch.hip: C ABI; mgpu.hip: the native multi-GPU loop).
+// logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, with mgpu.inc, the native
+// multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and their C ABI).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -168,7 +169,8 @@ struct volym_ctx {
     // the texels whose state changes:  d_vol[t] = (t inside the crop box && !seg_hidden[label(t)]) ? d_vol0[t] : 0  for every
     // texel t, and the same for d_imp with its uncropped source (above).  An edit that fails after its first launch breaks it,
     // and the context then asks for volym_set_volume again (have_vol false).  While a segment is hidden the labels have the
-    // volume's dimensions and layout (the call refuses anything else).
+    // volume's dimensions and layout (the call refuses anything else).  One function keeps it: retarget (scene_bytes.hip), which
+    // every set-up call that changes box, mask or bytes goes through.
     uint8_t seg_hidden[256] = {};
     int filter = VOLYM_FILTER_NEAREST;
     uint8_t lut[256 * 4] = {};
@@ -238,6 +240,16 @@ namespace volym {
 int ctx_fail(volym_ctx* c, int code, const std::string& msg);
 // one plain ray-march launch of slot 0 on its stream (what volym_compute_pass enqueues); used by the multi-GPU loop
 int ctx_launch_march(volym_ctx* c);
+
+// the seam between the frame loop (raymarch.hip) and the scene's bytes (scene_bytes.hip); all blocking set-up path
+// raymarch.hip: every slot's feedback at rest and stream idle, before what the slots share is rewritten or freed
+int quiesce_slots(volym_ctx* c);
+// raymarch.hip: the work lists of every slot in geometric order, no costs (the costs no longer describe the scene)
+int rebuild_lists(volym_ctx* c);
+// raymarch.hip: the look-ahead's reject box of a frame from imp_box_*
+void set_reject_box(const volym_ctx* c, FrameParams& fp);
+// scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes (sets have_vol)
+int build_macro_cells(volym_ctx* c);
 
 }  // namespace volym
 

@@ -1,4 +1,5 @@
-// libvolym_hip.so: context + C ABI (include/volym_hip.h) over the gfx950 kernels.
+// libvolym_hip.so: context, frame loop and their C ABI (include/volym_hip.h) over the gfx950 kernels.  The bytes of the scene
+// (volume, labels, importances, crop box, segment visibility, macro cells) and their C ABI are scene_bytes.hip.
 // Replaces the reference's gpu_context.rs / gpu_resources/* / demos/pipeline.rs for the
 // ray-march path; citations are file:line under /root/reference/.
 //
@@ -625,7 +626,7 @@ static void feedback_quiesce(FrameSlot& s)
 // Before a set-up call rewrites or frees what the slots share (the volume, the importances, the macro cells, the shard and its
 // geometric list): the feedback of EVERY slot at rest, and EVERY slot's stream idle -- with two frames in flight, the frames
 // of either slot may still read it.
-static int quiesce_slots(volym_ctx* c)
+int volym::quiesce_slots(volym_ctx* c)
 {
     HIPCHK(c, hipSetDevice(c->device));
     for (int i = 0; i < c->n_slots(); ++i) {
@@ -671,7 +672,7 @@ static int reset_slot_lists(volym_ctx* c, FrameSlot& s)
 
 // (Re)build the lists of this shard in every slot: geometric order, no costs.  Blocking set-up path (set_shard, options, uploads):
 // costs no longer describe the scene (new volume, transfer function, threshold grid...).
-static int rebuild_lists(volym_ctx* c)
+int volym::rebuild_lists(volym_ctx* c)
 {
     int rc = quiesce_slots(c);
     if (rc != VOLYM_OK) return rc;
@@ -680,70 +681,9 @@ static int rebuild_lists(volym_ctx* c)
     return rc;
 }
 
-static int read_macro_cells(volym_ctx* c);
-
-// Macro-cell maxima, their host copy and the occupied-cell AABB for every threshold byte (set-up path: blocks).
-static int build_macro_cells(volym_ctx* c)
-{
-    int rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
-    // (every slot is idle: nothing reads the shared maxima or a slot's distance field).  Until every buffer below is rebuilt
-    // there is no volume to march: a failure leaves the context asking for volym_set_volume and volym_update again
-    const bool had_frame = c->have_frame;
-    c->have_vol = c->have_frame = false;
-    if (c->d_mc) { HIPCHK(c, hipFree(c->d_mc)); c->d_mc = nullptr; }
-    const uint32_t n = c->mc_n, cells = n * n * n;
-    hipError_t e = hipMalloc(&c->d_mc, cells);
-    for (int i = 0; i < c->n_slots(); ++i) {
-        FrameSlot& s = *c->slots[i];
-        if (s.d_df) { HIPCHK(c, hipFree(s.d_df)); s.d_df = nullptr; }
-        if (e == hipSuccess) e = hipMalloc(&s.d_df, (cells / 2u + 15u) / 16u * 16u);
-        s.df_thr_byte = 0xffffffffu;
-        s.hull_dirty = true;
-    }
-    if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(macro cells): ") + hipGetErrorString(e));
-    const hipStream_t stream = c->slot0().stream;
-    const CellRange all = {{0u, 0u, 0u}, {n, n, n}};
-    hipLaunchKernelGGL(volym_macrocell_kernel, dim3(cells), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n, c->bricked ? 1u : 0u, all);
-    HIPCHK(c, hipGetLastError());
-    rc = read_macro_cells(c);
-    if (rc != VOLYM_OK) return rc;
-    c->have_vol = true;
-    c->have_frame = had_frame;
-    return VOLYM_OK;
-}
-
-// The host's copy of the maxima (behind the launches on slot 0's stream that wrote them) and the occupied-cell AABB for every
-// threshold byte.  Blocks.
-static int read_macro_cells(volym_ctx* c)
-{
-    const uint32_t n = c->mc_n, cells = n * n * n;
-    const hipStream_t stream = c->slot0().stream;
-    c->h_mc.resize(cells);
-    HIPCHK(c, hipMemcpyAsync(c->h_mc.data(), c->d_mc, cells, hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    // AABB of the cells whose maximum reaches b, for every b: boxes of the cells with maximum exactly v, then a suffix union
-    int box[257][6];
-    for (int v = 0; v <= 256; ++v) { box[v][0] = box[v][1] = box[v][2] = 1 << 30; box[v][3] = box[v][4] = box[v][5] = -1; }
-    for (uint32_t z = 0; z < n; ++z)
-        for (uint32_t y = 0; y < n; ++y)
-            for (uint32_t x = 0; x < n; ++x) {
-                int* b = box[c->h_mc[(z * n + y) * n + x]];
-                const int p[3] = {static_cast<int>(x), static_cast<int>(y), static_cast<int>(z)};
-                for (int i = 0; i < 3; ++i) { b[i] = std::min(b[i], p[i]); b[3 + i] = std::max(b[3 + i], p[i]); }
-            }
-    int run[6] = {1 << 30, 1 << 30, 1 << 30, -1, -1, -1};
-    for (int i = 0; i < 6; ++i) c->aabb_tab[256][i] = i < 3 ? 0 : -1;         // threshold byte 256: nothing is dense
-    for (int v = 255; v >= 0; --v) {
-        for (int i = 0; i < 3; ++i) { run[i] = std::min(run[i], box[v][i]); run[3 + i] = std::max(run[3 + i], box[v][3 + i]); }
-        for (int i = 0; i < 6; ++i) c->aabb_tab[v][i] = run[3] < 0 ? (i < 3 ? 0 : -1) : run[i];
-    }
-    return VOLYM_OK;
-}
-
 // the look-ahead's reject box (raymarch_device.h ahead_cannot_hit): positions u with clamp(floor(u * n), 0, n - 1) inside the
 // texel AABB of the important voxels, open-ended where the AABB touches the border; 2e-6 covers the rounding of u * n
-static void set_reject_box(const volym_ctx* c, FrameParams& fp)
+void volym::set_reject_box(const volym_ctx* c, FrameParams& fp)
 {
     const uint32_t dims[3] = {c->inx, c->iny, c->inz};
     for (int a = 0; a < 3; ++a) {
@@ -918,8 +858,6 @@ int volym_set_stream(volym_ctx* c, void* hip_stream)
     return VOLYM_OK;
 }
 
-static bool want_bricked(const volym_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz);
-
 static int set_frames_in_flight(volym_ctx* c, int value)
 {
     if (value != 1 && value != 2) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_FRAMES_IN_FLIGHT: 1 or 2");
@@ -1082,702 +1020,6 @@ int volym_set_shard(volym_ctx* c, uint32_t rank, uint32_t world)
     c->rank = rank; c->world = world;
     recompute_shard(c);
     return rebuild_lists(c);
-}
-
-// bytes of a volume in the device layout (without the 16 bytes every allocation of one adds)
-static uint64_t layout_bytes(bool bricked, uint32_t nx, uint32_t ny, uint32_t nz)
-{
-    return bricked ? static_cast<uint64_t>(brick_count(nx)) * brick_count(ny) * brick_count(nz) * 64u : static_cast<uint64_t>(nx) * ny * nz;
-}
-
-static int upload_volume(volym_ctx* c, uint8_t** dst, const uint8_t* src, uint32_t nx, uint32_t ny, uint32_t nz)
-{
-    const bool bricked = want_bricked(c, nx, ny, nz);
-    if (!src || nx == 0 || ny == 0 || nz == 0) return fail(c, VOLYM_E_INVALID, "volume: NULL data or zero dimension");
-    const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
-    const uint64_t nb = layout_bytes(bricked, nx, ny, nz);
-    if (nx > 4096 || ny > 4096 || nz > 4096 || nb > 0xffffffffull)
-        return fail(c, VOLYM_E_INVALID, "volume: each dimension <= 4096 and the brick-padded size < 2^32");
-    const int rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
-    if (*dst) { HIPCHK(c, hipFree(*dst)); *dst = nullptr; }
-    uint8_t* staging = nullptr;
-    hipError_t e = hipMalloc(dst, nb + 16);      // the trilinear fetch reads voxel pairs: one byte past the last voxel is touched
-    if (e == hipSuccess) e = hipMemset(*dst + nb, 0, 16);
-    if (e == hipSuccess && bricked) e = hipMalloc(&staging, n);
-    if (e != hipSuccess) { (void)hipFree(staging); return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(volume): ") + hipGetErrorString(e)); }
-    e = hipMemcpy(bricked ? staging : *dst, src, n, hipMemcpyHostToDevice);
-    if (e == hipSuccess && bricked) {
-        const hipStream_t stream = c->slot0().stream;
-        hipLaunchKernelGGL(volym_rebrick_kernel, dim3(static_cast<uint32_t>((nb + 255u) / 256u)), dim3(256), 0, stream, staging, *dst, nx, ny, nz);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    }
-    (void)hipFree(staging);
-    if (e != hipSuccess) return fail(c, VOLYM_E_HIP, std::string("volume upload: ") + hipGetErrorString(e));
-    return VOLYM_OK;
-}
-
-// Bricks pay once the volume outgrows the L2s (measured: from 512^3 on; see raymarch_device.h); volume and importances of
-// the same dimensions get the same answer.
-static bool want_bricked(const volym_ctx* c, uint32_t nx, uint32_t ny, uint32_t nz)
-{
-    if (c->layout_choice >= 0) return c->layout_choice == 1;
-    return static_cast<uint64_t>(nx) * ny * nz > c->brick_from_bytes;
-}
-
-// ---- crop box on the device ---------------------------------------------------------------------------------------------
-// A frame with crop box B is the frame of the scene whose density and importance bytes outside B are 0.  The march kernels know
-// nothing of it: they read d_vol and d_imp, and volym_set_crop_box rewrites those from an uncropped source (context.hpp) --
-// only the texels whose side of the box changes, which at most six slabs cover (volym_crop_slabs), one per face that moved.
-// Everything derived from the bytes follows: the macro cells the slabs touch, the occupied-cell boxes, every slot's distance
-// field, hulls, tile mask and depth bounds (rebuilt by the next launch), the look-ahead's reject box, the work lists.
-
-static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks);
-
-int volym_crop_slabs(const uint32_t old_lo[3], const uint32_t old_hi[3], const uint32_t new_lo[3], const uint32_t new_hi[3], uint32_t slabs[6][6],
-                     uint32_t* n_slabs)
-{
-    if (!old_lo || !old_hi || !new_lo || !new_hi || !slabs || !n_slabs) return VOLYM_E_INVALID;
-    bool old_empty = false, new_empty = false;
-    for (int a = 0; a < 3; ++a) {
-        if (old_lo[a] > old_hi[a] || new_lo[a] > new_hi[a]) return VOLYM_E_INVALID;
-        old_empty = old_empty || old_lo[a] == old_hi[a];
-        new_empty = new_empty || new_lo[a] == new_hi[a];
-    }
-    uint32_t n = 0;
-    auto push = [&](const uint32_t lo[3], const uint32_t hi[3]) {
-        for (int a = 0; a < 3; ++a) if (lo[a] >= hi[a]) return;
-        for (int a = 0; a < 3; ++a) { slabs[n][a] = lo[a]; slabs[n][3 + a] = hi[a]; }
-        ++n;
-    };
-    if (old_empty || new_empty) {
-        // to or from nothing: the other box is the whole difference
-        if (!new_empty) push(new_lo, new_hi);
-        if (!old_empty) push(old_lo, old_hi);
-    } else {
-        // a texel of one box that is not in the other lies, on some axis, between the two positions of a face; on the other axes
-        // it lies within its own box, so within the union of the two extents
-        uint32_t ulo[3], uhi[3];
-        for (int a = 0; a < 3; ++a) { ulo[a] = std::min(old_lo[a], new_lo[a]); uhi[a] = std::max(old_hi[a], new_hi[a]); }
-        for (int a = 0; a < 3; ++a) {
-            uint32_t lo[3] = {ulo[0], ulo[1], ulo[2]}, hi[3] = {uhi[0], uhi[1], uhi[2]};
-            lo[a] = std::min(old_lo[a], new_lo[a]); hi[a] = std::max(old_lo[a], new_lo[a]);
-            push(lo, hi);
-            lo[a] = std::min(old_hi[a], new_hi[a]); hi[a] = std::max(old_hi[a], new_hi[a]);
-            push(lo, hi);
-        }
-    }
-    *n_slabs = n;
-    return VOLYM_OK;
-}
-
-static bool crop_active(const volym_ctx* c)
-{
-    return c->crop_lo[0] != 0u || c->crop_lo[1] != 0u || c->crop_lo[2] != 0u || c->crop_hi[0] != c->nx || c->crop_hi[1] != c->ny || c->crop_hi[2] != c->nz;
-}
-
-static bool imp_croppable(const volym_ctx* c)
-{
-    return c->have_vol && c->have_imp && c->d_imp && c->inx == c->nx && c->iny == c->ny && c->inz == c->nz;
-}
-
-static bool imp_from_labels(const volym_ctx* c) { return c->d_labels && c->have_seg_table; }
-
-// a hidden label that has voxels (hiding label values no voxel carries changes no byte)
-static bool mask_active(const volym_ctx* c)
-{
-    for (int l = 0; l < 256; ++l) if (c->seg_hidden[l] && c->label_count[l] != 0u) return true;
-    return false;
-}
-
-// the walk of the slab kernels over one slab [slab[0..2], slab[3..5]) of a volume in the given layout; returns its items
-static uint64_t make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t slab[6], CropSlab& s)
-{
-    s = CropSlab{};
-    for (int a = 0; a < 3; ++a) { s.lo[a] = slab[a]; s.hi[a] = slab[3 + a]; s.box_lo[a] = c->crop_lo[a]; s.box_hi[a] = c->crop_hi[a]; }
-    uint64_t items;
-    if (bricked) {
-        for (int a = 0; a < 3; ++a) { s.b_lo[a] = s.lo[a] >> 2; s.b_n[a] = ((s.hi[a] + 3u) >> 2) - s.b_lo[a]; }
-        items = 4ull * s.b_n[0] * s.b_n[1] * s.b_n[2];
-    } else {
-        const bool rows = s.lo[0] == 0u && s.hi[0] == c->nx, slices = rows && s.lo[1] == 0u && s.hi[1] == c->ny;
-        uint64_t run = s.hi[0] - s.lo[0];
-        s.runs_y = s.hi[1] - s.lo[1]; s.runs_z = s.hi[2] - s.lo[2];
-        if (rows) { run *= s.runs_y; s.runs_y = 1u; }
-        if (slices) { run *= s.runs_z; s.runs_z = 1u; }
-        s.run_len = static_cast<uint32_t>(run);                       // (a volume has fewer than 2^32 bytes: upload_volume)
-        s.chunks_per_run = static_cast<uint32_t>((run + 15u) / 16u) + 1u;
-        items = static_cast<uint64_t>(s.chunks_per_run) * s.runs_y * s.runs_z;
-    }
-    return items;
-}
-
-// dst = (inside(c->crop) && visible(label)) ? source : 0 over one box of texels, on slot 0's stream, by volym_visibility_kernel:
-// only the chunks that hold a texel of a label in `flipped` are rewritten (NULL: every chunk).  table: the labels are the source.
-static int launch_visibility(volym_ctx* c, const uint8_t* src, uint8_t* dst, const uint8_t* table, bool bricked, const uint32_t box[6], const uint8_t* flipped)
-{
-    CropSlab s;
-    const uint64_t items = make_crop_slab(c, bricked, box, s);
-    if (items == 0u) return VOLYM_OK;
-    LabelTable t = {}, m = {};
-    if (table) std::memcpy(t.v, table, 256);
-    for (int l = 0; l < 256; ++l) m.v[l] = static_cast<uint8_t>((c->seg_hidden[l] ? 0u : 1u) | ((!flipped || flipped[l]) ? 2u : 0u));
-    const hipStream_t stream = c->slot0().stream;
-    const dim3 grid(stream_grid(c, items));
-    const uint4* labels = reinterpret_cast<const uint4*>(c->d_labels);
-    if (table)
-        hipLaunchKernelGGL(volym_visibility_kernel<true>, grid, dim3(256), 0, stream, labels, labels, reinterpret_cast<uint4*>(dst), t, m, s, c->nx, c->ny, c->nz,
-                           bricked ? 1u : 0u, static_cast<uint32_t>(items));
-    else
-        hipLaunchKernelGGL(volym_visibility_kernel<false>, grid, dim3(256), 0, stream, labels, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), t, m, s,
-                           c->nx, c->ny, c->nz, bricked ? 1u : 0u, static_cast<uint32_t>(items));
-    HIPCHK(c, hipGetLastError());
-    return VOLYM_OK;
-}
-
-// dst = inside(c->crop) ? source : 0 over one slab, on slot 0's stream (table: the source holds labels).  While a segment is
-// hidden the slab goes through the kernel that reads the labels as well; a context that hides nothing runs what it always ran.
-static int launch_crop_slab(volym_ctx* c, const uint8_t* src, uint8_t* dst, const uint8_t* table, bool bricked, const uint32_t slab[6])
-{
-    if (mask_active(c)) return launch_visibility(c, src, dst, table, bricked, slab, nullptr);
-    CropSlab s;
-    const uint64_t items = make_crop_slab(c, bricked, slab, s);
-    if (items == 0u) return VOLYM_OK;
-    LabelTable t = {};
-    if (table) std::memcpy(t.v, table, 256);
-    const hipStream_t stream = c->slot0().stream;
-    const dim3 grid(stream_grid(c, items));
-    if (table)
-        hipLaunchKernelGGL(volym_crop_slab_kernel<true>, grid, dim3(256), 0, stream, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), t, s, c->nx, c->ny,
-                           c->nz, bricked ? 1u : 0u, static_cast<uint32_t>(items));
-    else
-        hipLaunchKernelGGL(volym_crop_slab_kernel<false>, grid, dim3(256), 0, stream, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), t, s, c->nx, c->ny,
-                           c->nz, bricked ? 1u : 0u, static_cast<uint32_t>(items));
-    HIPCHK(c, hipGetLastError());
-    return VOLYM_OK;
-}
-
-// The uncropped copies a crop needs and the context does not hold yet.  Only called while the bytes they are copied from are
-// uncropped (the box is the whole volume, or the buffer has just been uploaded).  Device-to-device on slot 0's stream (the
-// slots are at rest): a device-to-device copy is not waited for by the host and the slots' streams do not wait for the NULL
-// stream, so only stream order puts the copy before the slab kernels that rewrite its source, and the hipStreamSynchronize
-// that ends every caller covers it.
-static int ensure_uncropped_copies(volym_ctx* c, bool vol, bool imp)
-{
-    if (vol && !c->d_vol0) {
-        const uint64_t nb = layout_bytes(c->bricked, c->nx, c->ny, c->nz) + 16u;
-        hipError_t e = hipMalloc(&c->d_vol0, nb);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->d_vol0, c->d_vol, nb, hipMemcpyDeviceToDevice, c->slot0().stream);
-        if (e != hipSuccess) { (void)hipFree(c->d_vol0); c->d_vol0 = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("crop box (density copy): ") + hipGetErrorString(e)); }
-    }
-    if (imp && imp_croppable(c) && !imp_from_labels(c) && !c->d_imp0) {
-        hipError_t e = hipMalloc(&c->d_imp0, c->imp_bytes);
-        if (e == hipSuccess) e = hipMemcpyAsync(c->d_imp0, c->d_imp, c->imp_bytes, hipMemcpyDeviceToDevice, c->slot0().stream);
-        if (e != hipSuccess) { (void)hipFree(c->d_imp0); c->d_imp0 = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("crop box (importance copy): ") + hipGetErrorString(e)); }
-    }
-    return VOLYM_OK;
-}
-
-// imp_box_* = the uncropped importances' box cut to the crop box: the cropped importances have nothing important outside it
-static void crop_important_box(volym_ctx* c)
-{
-    bool none = c->imp_box0_lo[0] > c->imp_box0_hi[0];
-    for (int a = 0; a < 3; ++a) {
-        c->imp_box_lo[a] = c->imp_box0_lo[a]; c->imp_box_hi[a] = c->imp_box0_hi[a];
-        if (none || !imp_croppable(c)) continue;
-        c->imp_box_lo[a] = std::max(c->imp_box_lo[a], static_cast<int>(c->crop_lo[a]));
-        c->imp_box_hi[a] = std::min(c->imp_box_hi[a], static_cast<int>(c->crop_hi[a]) - 1);
-        none = c->imp_box_lo[a] > c->imp_box_hi[a];
-    }
-    if (none) for (int a = 0; a < 3; ++a) { c->imp_box_lo[a] = 1; c->imp_box_hi[a] = 0; }
-    // the frames enqueued from here on march the new box, with or without a volym_update in between
-    for (int i = 0; i < c->n_slots(); ++i) set_reject_box(c, c->slots[i]->fp);
-}
-
-static uint32_t visibility_boxes(const volym_ctx* c, const uint8_t flipped[256], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6]);
-
-// Rewrite the importances (which hold their uncropped bytes everywhere, hidden segments included) to the crop box and the
-// visibility mask: zero what lies outside the box, then the hidden segments inside it.
-static int crop_fresh_importances(volym_ctx* c)
-{
-    crop_important_box(c);
-    const bool masked = mask_active(c);
-    if ((!crop_active(c) && !masked) || !imp_croppable(c)) return VOLYM_OK;
-    int rc = ensure_uncropped_copies(c, false, true);
-    if (rc != VOLYM_OK) return rc;
-    const uint32_t zero[3] = {0u, 0u, 0u}, dims[3] = {c->nx, c->ny, c->nz};
-    uint32_t slabs[6][6], n = 0;
-    (void)volym_crop_slabs(zero, dims, c->crop_lo, c->crop_hi, slabs, &n);
-    for (uint32_t i = 0; i < n && rc == VOLYM_OK; ++i)
-        rc = imp_from_labels(c) ? launch_crop_slab(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, slabs[i])
-                                : launch_crop_slab(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, slabs[i]);
-    if (masked && rc == VOLYM_OK) {
-        // inside the box the bytes are those of "all visible": the hidden labels are the ones that flip
-        uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6];
-        const uint32_t nb = visibility_boxes(c, c->seg_hidden, boxes);
-        for (uint32_t i = 0; i < nb && rc == VOLYM_OK; ++i)
-            rc = imp_from_labels(c) ? launch_visibility(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, boxes[i], c->seg_hidden)
-                                    : launch_visibility(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, boxes[i], c->seg_hidden);
-    }
-    if (rc != VOLYM_OK) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));
-    return VOLYM_OK;
-}
-
-// The box becomes [lo, hi) (valid): density (do_vol) and importances rewritten over the slabs between the old box and the new one,
-// and what is derived from them brought up to date.  Blocking set-up path.  A failure before the first launch leaves the context
-// as it was; one after it leaves bytes that belong to neither box, and the context then asks for volym_set_volume again, as it
-// does when volym_set_volume itself fails.
-static int apply_crop_work(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol);
-
-// The maxima of the macro cells whose voxel range (slack included) meets one of n boxes of rewritten texels (the others cover no
-// texel that changed), their host copy and the occupied-cell boxes; every slot's distance field and hulls become stale.
-static int refresh_macro_cells(volym_ctx* c, const uint32_t (*boxes)[6], uint32_t n)
-{
-    const hipStream_t stream = c->slot0().stream;
-    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
-    for (uint32_t i = 0; i < n; ++i) {
-        CellRange r;
-        bool any = true;
-        for (int a = 0; a < 3; ++a) {
-            uint32_t c0 = c->mc_n, c1 = 0;
-            for (uint32_t k = 0; k < c->mc_n; ++k)
-                if (mc_voxel_lo(k, dims[a], c->mc_n) < boxes[i][3 + a] && mc_voxel_hi(k, dims[a], c->mc_n) > boxes[i][a]) { c0 = std::min(c0, k); c1 = k + 1u; }
-            any = any && c0 < c1;
-            r.c0[a] = c0; r.cn[a] = any ? c1 - c0 : 0u;
-        }
-        if (!any) continue;
-        hipLaunchKernelGGL(volym_macrocell_kernel, dim3(r.cn[0] * r.cn[1] * r.cn[2]), dim3(256), 0, stream, c->d_vol, c->d_mc, c->nx, c->ny, c->nz, c->mc_n,
-                           c->bricked ? 1u : 0u, r);
-        HIPCHK(c, hipGetLastError());
-    }
-    const int rc = read_macro_cells(c);
-    if (rc != VOLYM_OK) return rc;
-    for (int i = 0; i < c->n_slots(); ++i) { c->slots[i]->df_thr_byte = 0xffffffffu; c->slots[i]->hull_dirty = true; }
-    return VOLYM_OK;
-}
-
-static int apply_crop(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol)
-{
-    int rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
-    rc = ensure_uncropped_copies(c, do_vol, true);
-    if (rc != VOLYM_OK) return rc;
-    rc = apply_crop_work(c, lo, hi, do_vol);
-    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
-    return rc;
-}
-
-static int apply_crop_work(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3], bool do_vol)
-{
-    int rc = VOLYM_OK;
-    uint32_t old_lo[3], old_hi[3], slabs[6][6], n = 0;
-    for (int a = 0; a < 3; ++a) { old_lo[a] = c->crop_lo[a]; old_hi[a] = c->crop_hi[a]; c->crop_lo[a] = lo[a]; c->crop_hi[a] = hi[a]; }
-    (void)volym_crop_slabs(old_lo, old_hi, lo, hi, slabs, &n);
-    const bool imp = imp_croppable(c);
-    for (uint32_t i = 0; i < n; ++i) {
-        if (do_vol) rc = launch_crop_slab(c, c->d_vol0, c->d_vol, nullptr, c->bricked, slabs[i]);
-        if (rc == VOLYM_OK && imp)
-            rc = imp_from_labels(c) ? launch_crop_slab(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, slabs[i])
-                                    : launch_crop_slab(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, slabs[i]);
-        if (rc != VOLYM_OK) return rc;
-    }
-    const hipStream_t stream = c->slot0().stream;
-    if (do_vol) {
-        rc = refresh_macro_cells(c, slabs, n);
-        if (rc != VOLYM_OK) return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(stream));       // every slot's next frame reads the new bytes
-    crop_important_box(c);
-    return rebuild_lists(c);
-}
-
-int volym_set_crop_box(volym_ctx* c, const uint32_t lo[3], const uint32_t hi[3])
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!lo || !hi) return fail(c, VOLYM_E_INVALID, "volym_set_crop_box: NULL box");
-    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_set_crop_box: no volume (volym_set_volume first)");
-    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
-    bool same = true;
-    for (int a = 0; a < 3; ++a) {
-        if (lo[a] > hi[a] || hi[a] > dims[a]) return fail(c, VOLYM_E_INVALID, "volym_set_crop_box: need lo <= hi <= volume size on every axis");
-        same = same && lo[a] == c->crop_lo[a] && hi[a] == c->crop_hi[a];
-    }
-    if (same) return VOLYM_OK;
-    return apply_crop(c, lo, hi, true);
-}
-
-int volym_get_crop_box(volym_ctx* c, uint32_t lo[3], uint32_t hi[3])
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!lo || !hi) return fail(c, VOLYM_E_INVALID, "volym_get_crop_box: NULL output");
-    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_get_crop_box: no volume");
-    for (int a = 0; a < 3; ++a) { lo[a] = c->crop_lo[a]; hi[a] = c->crop_hi[a]; }
-    return VOLYM_OK;
-}
-
-// ---- segment visibility on the device ------------------------------------------------------------------------------------
-// A frame with mask `visible` is the frame of the scene whose density and importance bytes are 0 in every texel of a hidden
-// label (and outside the crop box).  As with the crop box the march kernels know nothing of it: volym_set_segment_visibility
-// rewrites d_vol and d_imp from their uncropped sources, over the texels an edit can change -- those inside the label boxes
-// (volym_set_labels) of the labels that flipped, cut to the crop box -- and volym_visibility_kernel skips every chunk in there
-// that holds no texel of such a label.  Which boxes: volym_visibility_boxes.
-
-int volym_visibility_boxes(const uint8_t flipped[256], const uint64_t counts[256], const int32_t label_boxes[256][6], const uint32_t crop_lo[3],
-                           const uint32_t crop_hi[3], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6], uint32_t* n_boxes)
-{
-    if (!flipped || !counts || !label_boxes || !crop_lo || !crop_hi || !boxes || !n_boxes) return VOLYM_E_INVALID;
-    for (int a = 0; a < 3; ++a) if (crop_lo[a] > crop_hi[a]) return VOLYM_E_INVALID;
-    auto volume = [](const uint32_t b[6]) { return static_cast<uint64_t>(b[3] - b[0]) * (b[4] - b[1]) * (b[5] - b[2]); };
-    auto hull = [](const uint32_t p[6], const uint32_t q[6], uint32_t out[6]) {
-        for (int a = 0; a < 3; ++a) { out[a] = std::min(p[a], q[a]); out[3 + a] = std::max(p[3 + a], q[3 + a]); }
-    };
-    uint32_t n = 0;
-    for (int l = 0; l < 256; ++l) {
-        if (!flipped[l] || counts[l] == 0u) continue;
-        uint32_t b[6];
-        bool empty = false;
-        for (int a = 0; a < 3; ++a) {
-            if (label_boxes[l][a] < 0 || label_boxes[l][3 + a] < label_boxes[l][a]) return VOLYM_E_INVALID;
-            b[a] = std::max(static_cast<uint32_t>(label_boxes[l][a]), crop_lo[a]);
-            b[3 + a] = std::min(static_cast<uint32_t>(label_boxes[l][3 + a]) + 1u, crop_hi[a]);
-            empty = empty || b[a] >= b[3 + a];
-        }
-        if (empty) continue;
-        // into the first box whose hull with this one holds no more texels than the two apart; else a box of its own while there
-        // is room; else into the box that grows least
-        uint32_t h[6], best = n;
-        uint64_t best_growth = ~0ull;
-        for (uint32_t i = 0; i < n; ++i) {
-            hull(boxes[i], b, h);
-            const uint64_t hv = volume(h), vi = volume(boxes[i]);
-            if (hv <= vi + volume(b)) { best = i; break; }
-            if (n == VOLYM_VISIBILITY_MAX_BOXES && hv - vi < best_growth) { best_growth = hv - vi; best = i; }
-        }
-        if (best == n) { std::memcpy(boxes[n++], b, sizeof b); continue; }
-        hull(boxes[best], b, h);
-        std::memcpy(boxes[best], h, sizeof h);
-    }
-    // boxes that grew may now pay to merge with each other
-    for (bool merged = true; merged;) {
-        merged = false;
-        for (uint32_t i = 0; i < n && !merged; ++i)
-            for (uint32_t j = i + 1u; j < n && !merged; ++j) {
-                uint32_t h[6];
-                hull(boxes[i], boxes[j], h);
-                if (volume(h) > volume(boxes[i]) + volume(boxes[j])) continue;
-                std::memcpy(boxes[i], h, sizeof h);
-                std::memcpy(boxes[j], boxes[n - 1u], sizeof h);
-                --n;
-                merged = true;
-            }
-    }
-    *n_boxes = n;
-    return VOLYM_OK;
-}
-
-static uint32_t visibility_boxes(const volym_ctx* c, const uint8_t flipped[256], uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6])
-{
-    uint32_t n = 0;
-    (void)volym_visibility_boxes(flipped, c->label_count, c->label_box, c->crop_lo, c->crop_hi, boxes, &n);
-    return n;
-}
-
-// imp_box0_* of importances mapped from the labels: the union of the boxes of the labels the table makes important and the
-// mask shows -- what important_texel_box would find in the mapped bytes, or a box around it
-static void segment_important_box(volym_ctx* c)
-{
-    int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
-    for (int l = 0; l < 256; ++l) {
-        if (c->seg_table[l] < 128u || c->seg_hidden[l] || c->label_count[l] == 0u) continue;
-        for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], c->label_box[l][a]); hi[a] = std::max(hi[a], c->label_box[l][3 + a]); }
-    }
-    for (int a = 0; a < 3; ++a) {
-        if (hi[0] < 0) { c->imp_box0_lo[a] = 1; c->imp_box0_hi[a] = 0; continue; }
-        c->imp_box0_lo[a] = lo[a]; c->imp_box0_hi[a] = hi[a];
-    }
-}
-
-static int apply_visibility_work(volym_ctx* c, const uint8_t hidden[256], bool do_vol)
-{
-    uint8_t flipped[256];
-    for (int l = 0; l < 256; ++l) { flipped[l] = c->seg_hidden[l] != hidden[l]; c->seg_hidden[l] = hidden[l]; }
-    uint32_t boxes[VOLYM_VISIBILITY_MAX_BOXES][6];
-    const uint32_t n = visibility_boxes(c, flipped, boxes);
-    const bool imp = imp_croppable(c);
-    int rc = VOLYM_OK;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (do_vol) rc = launch_visibility(c, c->d_vol0, c->d_vol, nullptr, c->bricked, boxes[i], flipped);
-        if (rc == VOLYM_OK && imp)
-            rc = imp_from_labels(c) ? launch_visibility(c, c->d_labels, c->d_imp, c->seg_table, c->imp_bricked, boxes[i], flipped)
-                                    : launch_visibility(c, c->d_imp0, c->d_imp, nullptr, c->imp_bricked, boxes[i], flipped);
-        if (rc != VOLYM_OK) return rc;
-    }
-    if (do_vol && n != 0u) {
-        rc = refresh_macro_cells(c, boxes, n);
-        if (rc != VOLYM_OK) return rc;
-    }
-    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));       // every slot's next frame reads the new bytes
-    if (imp_from_labels(c)) segment_important_box(c);          // (uploaded importances keep their box: it is conservative)
-    crop_important_box(c);
-    return rebuild_lists(c);
-}
-
-// The mask becomes `hidden` (0 / 1 per label; the caller has checked that the labels fit the volume).  Blocking set-up path with
-// the failure rule of apply_crop.
-static int apply_visibility(volym_ctx* c, const uint8_t hidden[256], bool do_vol)
-{
-    int rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
-    rc = ensure_uncropped_copies(c, do_vol, true);
-    if (rc != VOLYM_OK) return rc;
-    rc = apply_visibility_work(c, hidden, do_vol);
-    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
-    return rc;
-}
-
-// volym_set_labels, volym_set_importances and volym_set_volume start from "all visible": the hidden texels get their bytes back
-// (those of the density only where it stays, do_vol)
-static int show_all_segments(volym_ctx* c, bool do_vol)
-{
-    if (!c->have_vol || !mask_active(c)) {
-        std::memset(c->seg_hidden, 0, sizeof c->seg_hidden);
-        return VOLYM_OK;
-    }
-    const uint8_t none[256] = {};
-    return apply_visibility(c, none, do_vol);
-}
-
-int volym_set_segment_visibility(volym_ctx* c, const uint8_t visible[256])
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!visible) return fail(c, VOLYM_E_INVALID, "volym_set_segment_visibility: NULL table");
-    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: no volume (volym_set_volume first)");
-    if (!c->d_labels) return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: no labels (volym_set_labels first; volym_set_importances drops them)");
-    if (c->lnx != c->nx || c->lny != c->ny || c->lnz != c->nz)
-        return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: the labels' dimensions are not the volume's");
-    if (c->labels_bricked != c->bricked || (imp_croppable(c) && c->imp_bricked != c->labels_bricked))
-        return fail(c, VOLYM_E_STATE, "volym_set_segment_visibility: volume, importances and labels were uploaded under different VOLYM_OPT_VOLUME_LAYOUT settings");
-    uint8_t hidden[256];
-    bool changes = false;                  // a flipped label that has voxels: anything else changes no byte
-    for (int l = 0; l < 256; ++l) { hidden[l] = visible[l] ? 0u : 1u; changes = changes || (hidden[l] != c->seg_hidden[l] && c->label_count[l] != 0u); }
-    if (!changes) {
-        std::memcpy(c->seg_hidden, hidden, sizeof hidden);
-        return VOLYM_OK;
-    }
-    return apply_visibility(c, hidden, true);
-}
-
-int volym_get_segment_visibility(volym_ctx* c, uint8_t visible[256])
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!visible) return fail(c, VOLYM_E_INVALID, "volym_get_segment_visibility: NULL output");
-    for (int l = 0; l < 256; ++l) visible[l] = c->seg_hidden[l] ? 0u : 1u;
-    return VOLYM_OK;
-}
-
-int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t ny, uint32_t nz, int filter)
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (filter != VOLYM_FILTER_NEAREST && filter != VOLYM_FILTER_LINEAR)
-        return fail(c, VOLYM_E_INVALID, "volym_set_volume: filter must be VOLYM_FILTER_NEAREST or VOLYM_FILTER_LINEAR");
-    // the mask goes back to all visible and the importances get their hidden texels back (like the box below, before
-    // upload_volume has looked at the arguments)
-    int rc = show_all_segments(c, false);
-    if (rc != VOLYM_OK) return rc;
-    if (c->have_vol && crop_active(c)) {
-        // the box goes back to the whole volume: the importances get their cropped texels back (the density is replaced below).
-        // This runs before upload_volume has looked at its arguments: a call that then fails leaves the box reset and no volume
-        // (have_vol false), which is what a failed volym_set_volume leaves in any case.
-        const uint32_t zero[3] = {0u, 0u, 0u}, dims[3] = {c->nx, c->ny, c->nz};
-        rc = apply_crop(c, zero, dims, false);
-        if (rc != VOLYM_OK) return rc;
-    }
-    rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
-    // (d_imp is uncropped now, and the copies are made again by the next crop: a context that does not crop holds none)
-    if (c->d_vol0) { HIPCHK(c, hipFree(c->d_vol0)); c->d_vol0 = nullptr; }
-    if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
-    rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
-    if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
-    c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;
-    for (int a = 0; a < 3; ++a) c->crop_lo[a] = 0u;
-    c->crop_hi[0] = nx; c->crop_hi[1] = ny; c->crop_hi[2] = nz;
-    c->bricked = want_bricked(c, nx, ny, nz);
-    rc = build_macro_cells(c);             // (sets have_vol)
-    if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
-    return rebuild_lists(c);
-}
-
-// AABB (texel indices) of the importances a look-ahead probe counts as important (byte >= 128, wgsl:133, :155).  Host scan,
-// eight bytes at a time (bit 7 of a byte <=> the byte is >= 128); set-up path.
-static void important_texel_box(const uint8_t* imp, uint32_t nx, uint32_t ny, uint32_t nz, int (&lo)[3], int (&hi)[3])
-{
-    int x0 = INT32_MAX, y0 = INT32_MAX, z0 = INT32_MAX, x1 = -1, y1 = -1, z1 = -1;
-    for (uint32_t z = 0; z < nz; ++z)
-        for (uint32_t y = 0; y < ny; ++y) {
-            const uint8_t* row = imp + (static_cast<size_t>(z) * ny + y) * nx;
-            int first = -1, last = -1;
-            uint32_t x = 0;
-            for (; x + 8u <= nx; x += 8u) {
-                uint64_t w;
-                std::memcpy(&w, row + x, 8);
-                w &= 0x8080808080808080ull;
-                if (!w) continue;
-                if (first < 0) first = static_cast<int>(x) + (__builtin_ctzll(w) >> 3);
-                last = static_cast<int>(x) + 7 - (__builtin_clzll(w) >> 3);
-            }
-            for (; x < nx; ++x)
-                if (row[x] & 0x80u) { if (first < 0) first = static_cast<int>(x); last = static_cast<int>(x); }
-            if (first < 0) continue;
-            x0 = std::min(x0, first); x1 = std::max(x1, last);
-            y0 = std::min(y0, static_cast<int>(y)); y1 = std::max(y1, static_cast<int>(y));
-            z0 = std::min(z0, static_cast<int>(z)); z1 = std::max(z1, static_cast<int>(z));
-        }
-    if (x1 < 0) { lo[0] = lo[1] = lo[2] = 1; hi[0] = hi[1] = hi[2] = 0; return; }
-    lo[0] = x0; lo[1] = y0; lo[2] = z0; hi[0] = x1; hi[1] = y1; hi[2] = z1;
-}
-
-int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz)
-{
-    if (!c) return VOLYM_E_INVALID;
-    // the labels go, and the mask with them: the density gets its hidden texels back (the importances are replaced below).  A
-    // call that then fails on its arguments leaves the mask reset.
-    int rc = show_all_segments(c, true);
-    if (rc != VOLYM_OK) return rc;
-    rc = upload_volume(c, &c->d_imp, importances, nx, ny, nz);
-    if (rc != VOLYM_OK) { c->have_imp = false; c->imp_bytes = 0; return rc; }
-    c->imp_bytes = layout_bytes(want_bricked(c, nx, ny, nz), nx, ny, nz) + 16u;
-    // the importances are the caller's now: a segment table has no labels to map any more
-    if (c->d_labels) { HIPCHK(c, hipFree(c->d_labels)); c->d_labels = nullptr; }
-    c->have_seg_table = false;
-    if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }      // (of the importances this call replaced)
-    c->imp_bricked = want_bricked(c, nx, ny, nz);
-    important_texel_box(importances, nx, ny, nz, c->imp_box0_lo, c->imp_box0_hi);
-    c->inx = nx; c->iny = ny; c->inz = nz;
-    c->have_imp = true;
-    rc = crop_fresh_importances(c);          // the crop box belongs to the scene: these importances are cropped like the last
-    if (rc != VOLYM_OK) { c->have_imp = false; return rc; }
-    return rebuild_lists(c);
-}
-
-// ---- segment importances on the device ---------------------------------------------------------------------------------
-// The reference maps labels to importances on the host once (importance.rs:148-158) and uploads the result; an edit of one
-// segment's importance would pay that again (a host pass, an upload and a host scan of the whole volume).  Here the labels stay
-// on the device: volym_set_labels uploads them once and counts, per label value, its voxels and their texel AABB;
-// volym_set_segment_importances maps them through a 256-byte table into d_imp (one HBM stream) and takes the important-texel
-// box as the union of the boxes of the labels the table makes important -- exactly what important_texel_box would find.
-
-static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks)
-{
-    const uint64_t g = std::min<uint64_t>((n_chunks + 255u) / 256u, static_cast<uint64_t>(c->n_cus) * 8u);
-    return static_cast<uint32_t>(std::max<uint64_t>(g, 1u));
-}
-
-int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz)
-{
-    if (!c) return VOLYM_E_INVALID;
-    // new labels mean new segments: all visible, and density and importances get their hidden texels back while the labels
-    // that say which they are still exist
-    int rc = show_all_segments(c, true);
-    if (rc != VOLYM_OK) return rc;
-    if (imp_from_labels(c) && crop_active(c) && imp_croppable(c) && !c->d_imp0) {
-        // the importances stay as they are, cropped, and the labels they were mapped from go: keep their uncropped bytes
-        rc = quiesce_slots(c);
-        if (rc != VOLYM_OK) return rc;
-        hipError_t e = hipMalloc(&c->d_imp0, c->imp_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(c->d_imp0 + c->imp_bytes - 16u, 0, 16, c->slot0().stream);
-        if (e != hipSuccess) { (void)hipFree(c->d_imp0); c->d_imp0 = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(importances): ") + hipGetErrorString(e)); }
-        LabelTable t;
-        std::memcpy(t.v, c->seg_table, 256);
-        const uint64_t n_chunks = (c->imp_bytes - 16u + 15u) / 16u;
-        hipLaunchKernelGGL(volym_segment_map_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, c->slot0().stream, reinterpret_cast<const uint4*>(c->d_labels),
-                           reinterpret_cast<uint4*>(c->d_imp0), t, c->lnx, c->lny, c->lnz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipStreamSynchronize(c->slot0().stream));
-    }
-    c->have_seg_table = false;
-    rc = upload_volume(c, &c->d_labels, labels, nx, ny, nz);      // (quiesces the slots first)
-    if (rc != VOLYM_OK) { if (c->d_labels) (void)hipFree(c->d_labels); c->d_labels = nullptr; return rc; }
-    c->lnx = nx; c->lny = ny; c->lnz = nz;
-    c->labels_bricked = want_bricked(c, nx, ny, nz);
-    const uint64_t n_chunks = (layout_bytes(c->labels_bricked, nx, ny, nz) + 15u) / 16u;
-    // counts, then boxes: lo = INT_MAX, hi = -1 until a voxel says otherwise
-    std::vector<unsigned char> init(256 * sizeof(unsigned long long) + 256 * 6 * sizeof(int));
-    int* boxes = reinterpret_cast<int*>(init.data() + 256 * sizeof(unsigned long long));
-    for (int l = 0; l < 256; ++l)
-        for (int i = 0; i < 6; ++i) boxes[l * 6 + i] = i < 3 ? INT32_MAX : -1;
-    unsigned char* d_stats = nullptr;
-    const hipStream_t stream = c->slot0().stream;
-    hipError_t e = hipMalloc(&d_stats, init.size());
-    if (e == hipSuccess) e = hipMemcpy(d_stats, init.data(), init.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(volym_label_stats_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels),
-                           reinterpret_cast<unsigned long long*>(d_stats), reinterpret_cast<int*>(d_stats + 256 * sizeof(unsigned long long)),
-                           nx, ny, nz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(init.data(), d_stats, init.size(), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_stats);
-    if (e != hipSuccess) {
-        (void)hipFree(c->d_labels); c->d_labels = nullptr;
-        return fail(c, VOLYM_E_HIP, std::string("volym_set_labels: ") + hipGetErrorString(e));
-    }
-    std::memcpy(c->label_count, init.data(), sizeof c->label_count);
-    std::memcpy(c->label_box, boxes, sizeof c->label_box);
-    return VOLYM_OK;
-}
-
-int volym_set_segment_importances(volym_ctx* c, const uint8_t table[256])
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!table) return fail(c, VOLYM_E_INVALID, "volym_set_segment_importances: NULL table");
-    if (!c->d_labels) return fail(c, VOLYM_E_STATE, "volym_set_segment_importances: no labels (volym_set_labels first; volym_set_importances drops them)");
-    int rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
-    const uint64_t nb = layout_bytes(c->labels_bricked, c->lnx, c->lny, c->lnz);
-    if (c->imp_bytes != nb + 16u) {
-        // the importances take the labels' dimensions and layout: a new allocation, whose 16 bytes past the layout stay zero
-        c->have_imp = false;
-        if (c->d_imp) { HIPCHK(c, hipFree(c->d_imp)); c->d_imp = nullptr; }
-        c->imp_bytes = 0;
-        hipError_t e = hipMalloc(&c->d_imp, nb + 16u);
-        if (e == hipSuccess) e = hipMemset(c->d_imp + nb, 0, 16);
-        if (e != hipSuccess) { (void)hipFree(c->d_imp); c->d_imp = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(importances): ") + hipGetErrorString(e)); }
-        c->imp_bytes = nb + 16u;
-    }
-    LabelTable t;
-    std::memcpy(t.v, table, 256);
-    const uint64_t n_chunks = (nb + 15u) / 16u;
-    const hipStream_t stream = c->slot0().stream;
-    hipLaunchKernelGGL(volym_segment_map_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels),
-                       reinterpret_cast<uint4*>(c->d_imp), t, c->lnx, c->lny, c->lnz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(stream));       // every slot's next frame reads the new bytes
-    c->inx = c->lnx; c->iny = c->lny; c->inz = c->lnz;
-    c->have_imp = true;
-    // from here on the labels and this table are the uncropped importances
-    std::memcpy(c->seg_table, table, 256);
-    c->have_seg_table = true;
-    segment_important_box(c);                // (of the visible segments)
-    c->imp_bricked = c->labels_bricked;
-    if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
-    // the crop box and the mask (if any) cut the new importances, and the frames enqueued from here on march the new reject box, with or
-    // without a volym_update in between
-    rc = crop_fresh_importances(c);
-    if (rc != VOLYM_OK) { c->have_imp = false; return rc; }
-    return rebuild_lists(c);
-}
-
-int volym_label_counts(volym_ctx* c, uint64_t counts[256])
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!counts) return fail(c, VOLYM_E_INVALID, "volym_label_counts: NULL output");
-    if (!c->d_labels) return fail(c, VOLYM_E_STATE, "volym_label_counts: no labels");
-    std::memcpy(counts, c->label_count, sizeof c->label_count);
-    return VOLYM_OK;
 }
 
 int volym_set_transfer_function(volym_ctx* c, const uint8_t* rgba8, uint32_t n)
