@@ -72,8 +72,25 @@ struct FrameParams {
                                  // which no ray can meet anything dense; x1 <= x0: no such pixel at all
 };
 
+// The kernel's FrameParams argument, read afresh from the kernel-argument segment at the place of the call (OFFSET: the argument's
+// place in the segment; raymarch_pq.h computes and checks it).  The by-value argument is ~900 bytes that the compiler otherwise
+// keeps in scalar registers from the kernel's first instruction to its last: there are not that many, so it spilled them into
+// VGPR lanes (and those VGPRs into scratch) and read them back with v_readlane in front of every use.  The pointer is laundered
+// through an asm that holds no instruction, so what is read through the reference belongs to the place of the call: nothing is hoisted out of the
+// loop around it and nothing stays live from one call to the next.  Constant address space and a uniform address: every field
+// comes out as an s_load where it is used, hits the scalar cache after the first call, and costs no VALU slot.
+// Lane-dependent indices (the hull edge gather) would be vector loads: those read the argument itself, once per kernel.
+template <size_t OFFSET>
+__device__ __forceinline__ const FrameParams& frame_params_here()
+{
+    typedef const __attribute__((address_space(4))) char* kernarg_ptr;
+    kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr() + OFFSET;
+    asm volatile("; frame_params_here: kernarg offset %1" : "+s"(p) : "n"(OFFSET));     // (the comment is what the listing test reads)
+    return *(const FrameParams*)(const char*)p;     // (the address space is inferred back through the cast: s_load, not global_load)
+}
+
 #ifndef VOLYM_DEV_SWITCHES
-#define VOLYM_DEV_SWITCHES 0     // make DEV=1 compiles the FrameParams::dev timing experiments in (scripts/ablate.py --dev)
+#define VOLYM_DEV_SWITCHES 0    // make DEV=1 compiles the FrameParams::dev timing experiments in (scripts/ablate.py --dev)
 #endif
 // The distance field is read from LDS: 32^3 cells of 4 bits are the 16 KB it has there.  A finer grid (64^3, read from global memory
 // through L1 / L2) was measured slower and exists in the development build only: in the product kernels the test

@@ -47,6 +47,7 @@
 // The instrumented (COUNT) launch disables culling: it counts what the reference would fetch.
 #pragma once
 
+#include <cstddef>
 #include <type_traits>
 
 #include "raymarch_device.h"
@@ -113,6 +114,16 @@ __device__ __forceinline__ bool tile_mask_bit(const FrameParams& fp, uint32_t t8
     const uint32_t bit = t8y * fp.mask_t8x + t8x;
     return ((fp.tile_mask[bit >> 5] >> (bit & 31u)) & 1u) != 0u;
 }
+// The arguments of volym_raymarch_pq_kernel as the kernel-argument segment lays them out (every argument at its natural alignment, in
+// order: the layout of this struct), for the one thing the kernel needs to know about its own segment: where `fp` sits.
+// tests/test_kernel_resources.py compares the figure with the .offset the compiler writes into the code object's metadata.
+struct PqKernelArgs {
+    const uint8_t* vol; const uint8_t* imp; const FrameTables* tables; const uint8_t* df4; const uint2* order; uint32_t n_items; uint16_t* cost;
+    uint32_t* out_shard; uint32_t* out_raster; float4* out_f32; Counters* counters; uint4* trace; FrameParams fp;
+};
+constexpr size_t PQ_FP_KERNARG_OFFSET = offsetof(PqKernelArgs, fp);
+static_assert(PQ_FP_KERNARG_OFFSET % 8 == 0 && alignof(FrameParams) == 8, "FrameParams holds pointers: 8-byte aligned in the segment");
+
 // WAVES: waves per workgroup.  16 (four per SIMD, a budget of 128 VGPRs) for the common instantiation, which fits; the
 // importance / continuous-rho instantiations need ~150 registers and run 12 waves (three per SIMD, 168 VGPRs) instead of
 // spilling 64-100 bytes per lane to scratch (profiles/r02_kernel_resources.txt).
@@ -121,7 +132,10 @@ __device__ __forceinline__ bool tile_mask_bit(const FrameParams& fp, uint32_t t8
 // LB (development build only, north_star "LDS-staged voxel bricks"): the K speculative voxel fetches of an iteration go through a
 // per-wave cache of 4x4x4 bricks in LDS, filled with one coalesced 64-byte read per brick (16 lanes x 4 bytes) -- the A/B of
 // profiles/r03_lds_bricks_ab.txt.  Bricked layout, common instantiation only.
-template <bool TABLE, bool COUNT, bool TRACE = false, int KSPEC = 1, bool IMP = true, bool BRICK = false, bool IR = false, int WAVES = PQ_WAVES, int CJ = 0, bool LB = false>
+// RELOAD: every list entry reads the frame parameters of its set-up afresh from the kernel-argument segment (below, at the top of the
+// ticket loop) instead of holding them in scalar registers for the whole launch
+template <bool TABLE, bool COUNT, bool TRACE = false, int KSPEC = 1, bool IMP = true, bool BRICK = false, bool IR = false, int WAVES = PQ_WAVES, int CJ = 0, bool LB = false,
+          bool RELOAD = true>
 __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     const uint8_t* __restrict__ vol, const uint8_t* __restrict__ imp, const FrameTables* __restrict__ tables,
     const uint8_t* __restrict__ df4, const uint2* __restrict__ order, uint32_t n_items, uint16_t* __restrict__ cost,
@@ -256,6 +270,12 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     // wave serves jobs itself while it waits, and a wave that has run out of tiles serves until every wave has: no wave ever
     // waits for anything but a job that some wave -- if need be itself -- is free to run.  Same positions and f32 operations per
     // direction as ahead_cone; every wait is bounded.
+    // the look-aheads' own uniforms (ahead_steps, the box of the important texels) are read where a look-ahead starts, not held
+    // across the march loop around it
+    auto fp_here = [&]() __attribute__((always_inline)) -> const FrameParams& {
+        if constexpr (RELOAD) return frame_params_here<PQ_FP_KERNARG_OFFSET>();
+        else return fp;
+    };
     uint32_t cj_count = 0;          // samples this wave has asked about (wave-uniform): part of a tile's counted cost
     uint32_t la_rounds = 0;         // rounds of 64 straight look-ahead chains this wave has walked (wave-uniform): likewise
     auto cj_serve = [&]() __attribute__((always_inline)) -> bool {
@@ -304,7 +324,8 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         const V3 p0 = v3(r0.x, r0.y, r0.z), d0 = v3(r1.x, r1.y, r1.z);
         const float step = r0.w;
         const uint32_t meta = __float_as_uint(r1.w);
-        const int nprobe = static_cast<int>(fp.ahead_steps);
+        const FrameParams& fa = fp_here();
+        const int nprobe = static_cast<int>(fa.ahead_steps);
         bool hit = false;
         if constexpr (CJ != 2) {
             const float cone_xo = fp.cone_cos[lane & 7u] * 0.2f, cone_yo = fp.cone_sin[lane & 7u] * 0.2f;
@@ -346,7 +367,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 for (int b = 0; b < VOLYM_PROBE_BATCH; ++b) {
                     pos = pos + ds;
                     pb[b] = pos;
-                    inside = inside || probe_may_hit(fp, pos);
+                    inside = inside || probe_may_hit(fa, pos);
                 }
                 if (__ballot(live && inside) == 0ull) continue;             // no live chain where an important texel can be read
                 uint32_t ib[VOLYM_PROBE_BATCH];
@@ -373,9 +394,10 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
 #pragma unroll
         for (int k = 0; k < NK; ++k) { found[k] = false; any = any || need_in[k]; }
         if (__ballot(any) == 0ull) return;
+        const FrameParams& fa = fp_here();
 #pragma unroll
         for (int k = 0; k < NK; ++k) {
-            const bool nd = need_in[k] && !ahead_cannot_hit(fp, org + dir * tsk[k], dir, t_exit, CJ == 1);   // cannot reach an important voxel: false, unwalked
+            const bool nd = need_in[k] && !ahead_cannot_hit(fa, org + dir * tsk[k], dir, t_exit, CJ == 1);   // cannot reach an important voxel: false, unwalked
             need_bits |= nd ? 1u << k : 0u;
             if (nd) *reinterpret_cast<volatile uint8_t*>(&s_cres[wave][k * 64 + lane]) = 0;
         }
@@ -406,7 +428,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         for (int q = 1; q < NK; ++q) tk = k == static_cast<uint32_t>(q) ? tsk[q] : tk;
                         const V3 start = org + dir * tk;                          // the sample position, as its owner computes it (wgsl:251)
                         const uint32_t idx = (first_pos + rank) & (CJ_CAP - 1u);
-                        const float step = (t_exit - length_exact(start)) / static_cast<float>(static_cast<int>(fp.ahead_steps));   // wgsl:111
+                        const float step = (t_exit - length_exact(start)) / static_cast<float>(static_cast<int>(fa.ahead_steps));   // wgsl:111
                         // Take the place (0 free -> 2 being written -> 1 written): a place can be reserved a lap apart by two waves while its
                         // last taker still reads it, and only one of them may write next.  Every lane writes in the very turn it gets its
                         // place -- a lane that waited for its siblings' places would close a circle of waits (a server holds back a place
@@ -449,6 +471,11 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     // this lane's cone direction (lane & 7) for the wave-wide cone look-ahead, computed where it is used (two gathers
     // from the kernel-argument segment and two multiplies per call: nothing kept live across the march)
     for (uint32_t ticket = grab(); ticket < n_mine; ticket = grab()) {
+      // RELOAD: what this entry's set-up and store read of the frame parameters -- the matrix, the eye, the frame size and its
+      // reciprocals, the AABB, the culling flags, the mask and tile-depth pointers -- is fetched here, by scalar loads, and is live
+      // from its load to its last use in this entry, not across the kernel (raymarch_device.h, frame_params_here).  What the march
+      // loops read in every iteration (thr_byte, the steps, mc_n) stays in the argument's registers.
+      const FrameParams& fe = RELOAD ? frame_params_here<PQ_FP_KERNARG_OFFSET>() : fp;
       {
         // item = local_tile*4 + sub (an 8x8 wave tile, one lane per ray), or, for tiles the cost feedback
         // found expensive, bit 31 | (that id << 2) | quarter: a 4x4 quarter tile marched DEPTH-PARALLEL,
@@ -481,22 +508,22 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             const uint32_t lt = raw0 & 0x3fffffffu;
             const uint32_t tx16 = tx, ty16 = ty;
             bool masked16 = false;
-            if (culling && (fp.cull & CULL_TILE_MASK))
-                masked16 = !(tile_mask_bit(fp, tx16 * 2u, ty16 * 2u) || tile_mask_bit(fp, tx16 * 2u + 1u, ty16 * 2u) ||
-                             tile_mask_bit(fp, tx16 * 2u, ty16 * 2u + 1u) || tile_mask_bit(fp, tx16 * 2u + 1u, ty16 * 2u + 1u));
-            const uint32_t cls = culling ? classify_tile(fp, hull_edge, lane, static_cast<float>(tx16 * 16u), static_cast<float>(ty16 * 16u), 15.0f, masked16) : TILE_MARCH;
+            if (culling && (fe.cull & CULL_TILE_MASK))
+                masked16 = !(tile_mask_bit(fe, tx16 * 2u, ty16 * 2u) || tile_mask_bit(fe, tx16 * 2u + 1u, ty16 * 2u) ||
+                             tile_mask_bit(fe, tx16 * 2u, ty16 * 2u + 1u) || tile_mask_bit(fe, tx16 * 2u + 1u, ty16 * 2u + 1u));
+            const uint32_t cls = culling ? classify_tile(fe, hull_edge, lane, static_cast<float>(tx16 * 16u), static_cast<float>(ty16 * 16u), 15.0f, masked16) : TILE_MARCH;
             if (cls >= TILE_FILL_EMPTY) {
                 const uint32_t packed = cls == TILE_FILL_MISS ? 0xff000000u : 0u;
                 if (flags & F_RASTER) {
                     const uint32_t gx4 = tx16 * 16u + (lane & 3u) * 4u, gy4 = ty16 * 16u + (lane >> 2);
-                    if (gy4 < fp.H && (fp.W & 3u) == 0u && (reinterpret_cast<uintptr_t>(out_raster) & 15u) == 0u && gx4 < fp.W && !(flags & F_WRITE_F32)) {
+                    if (gy4 < fe.H && (fe.W & 3u) == 0u && (reinterpret_cast<uintptr_t>(out_raster) & 15u) == 0u && gx4 < fe.W && !(flags & F_WRITE_F32)) {
                         // rows are 16-byte aligned: one store per lane
-                        *reinterpret_cast<uint4*>(out_raster + static_cast<size_t>(gy4) * fp.W + gx4) = make_uint4(packed, packed, packed, packed);
-                    } else if (gy4 < fp.H) {
+                        *reinterpret_cast<uint4*>(out_raster + static_cast<size_t>(gy4) * fe.W + gx4) = make_uint4(packed, packed, packed, packed);
+                    } else if (gy4 < fe.H) {
                         for (uint32_t i = 0; i < 4u; ++i)
-                            if (gx4 + i < fp.W) {
-                                out_raster[static_cast<size_t>(gy4) * fp.W + gx4 + i] = packed;
-                                if (flags & F_WRITE_F32) out_f32[static_cast<size_t>(gy4) * fp.W + gx4 + i] = make_float4(0.0f, 0.0f, 0.0f, cls == TILE_FILL_MISS ? 1.0f : 0.0f);
+                            if (gx4 + i < fe.W) {
+                                out_raster[static_cast<size_t>(gy4) * fe.W + gx4 + i] = packed;
+                                if (flags & F_WRITE_F32) out_f32[static_cast<size_t>(gy4) * fe.W + gx4 + i] = make_float4(0.0f, 0.0f, 0.0f, cls == TILE_FILL_MISS ? 1.0f : 0.0f);
                             }
                     }
                 } else {
@@ -504,7 +531,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     for (uint32_t i = 0; i < 4u; ++i) {
                         const uint32_t sl = lane * 4u + i, sub4 = sl >> 6, in = sl & 63u;
                         const uint32_t gxx = tx16 * 16u + ((sub4 & 1u) << 3) + (in & 7u), gyy = ty16 * 16u + ((sub4 >> 1) << 3) + (in >> 3);
-                        out_shard[static_cast<size_t>(lt) * 256u + sl] = (gxx < fp.W && gyy < fp.H) ? packed : 0u;
+                        out_shard[static_cast<size_t>(lt) * 256u + sl] = (gxx < fe.W && gyy < fe.H) ? packed : 0u;
                     }
                 }
                 if (cost && lane == 0) cost[list_pos] = 0;
@@ -526,7 +553,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         const uint32_t own = dp ? (lane & ~3u) : lane;              // lane whose accumulators this ray uses
         const uint32_t gx = tx * 16u + ((sub & 1u) << 3) + px_in_sub;
         const uint32_t gy = ty * 16u + ((sub >> 1) << 3) + py_in_sub;
-        const bool in_frame = gx < fp.W && gy < fp.H;   // wgsl:217-219
+        const bool in_frame = gx < fe.W && gy < fe.H;   // wgsl:217-219
 
         if (TRACE) { trace_tiles++; tm_mark = PQ_TICK(); }
         uint32_t tile_iters = 0, tile_flushes = 0, tile_trips = 0;   // deterministic cost of this tile, fed back to the scheduler
@@ -534,13 +561,13 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         uint32_t trace_ray_iters = 0;                                // TRACE: iterations this lane's ray was active in
         uint32_t tclass = TILE_MARCH;
         if (culling && !dp) {
-            const bool masked8 = (fp.cull & CULL_TILE_MASK) != 0u && !tile_mask_bit(fp, tx * 2u + (sub & 1u), ty * 2u + (sub >> 1));
-            tclass = classify_tile(fp, hull_edge, lane, static_cast<float>(tx * 16u + ((sub & 1u) << 3)), static_cast<float>(ty * 16u + ((sub >> 1) << 3)), 7.0f, masked8);
+            const bool masked8 = (fe.cull & CULL_TILE_MASK) != 0u && !tile_mask_bit(fe, tx * 2u + (sub & 1u), ty * 2u + (sub >> 1));
+            tclass = classify_tile(fe, hull_edge, lane, static_cast<float>(tx * 16u + ((sub & 1u) << 3)), static_cast<float>(ty * 16u + ((sub >> 1) << 3)), 7.0f, masked8);
             if (tclass >= TILE_FILL_EMPTY) {            // no ray of this tile can differ from the constant
                 const uint32_t packed = tclass == TILE_FILL_MISS ? 0xff000000u : 0u;     // (0,0,0,1) wgsl:239 / (0,0,0,0) wgsl:328
                 if (flags & F_RASTER) {
                     if (in_frame) {
-                        const size_t o = static_cast<size_t>(gy) * fp.W + gx;
+                        const size_t o = static_cast<size_t>(gy) * fe.W + gx;
                         out_raster[o] = packed;
                         if (flags & F_WRITE_F32) out_f32[o] = make_float4(0.0f, 0.0f, 0.0f, tclass == TILE_FILL_MISS ? 1.0f : 0.0f);
                     }
@@ -558,7 +585,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         Ray ray;
         ray.o = v3(0.0f, 0.0f, 0.0f); ray.d = v3(0.0f, 0.0f, 0.0f); ray.t_entry = 0.0f; ray.t_exit = 0.0f;
         ray.hit = false;
-        if (in_frame) ray = make_ray<TABLE && !IMP && !IR>(fp, gx, gy);     // shared reciprocals where the registers allow (raymarch_device.h)
+        if (in_frame) ray = make_ray<TABLE && !IMP && !IR>(fe, gx, gy);     // shared reciprocals where the registers allow (raymarch_device.h)
         {
             const V3 hvec = ray_half_vector(ray.d);
             hh[lane] = make_float4(hvec.x, hvec.y, hvec.z, 0.0f);     // (a depth-parallel quad: four equal entries, owner = the first)
@@ -569,30 +596,30 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         bool last_dense = false;
         if (culling && tclass == TILE_HIT_TEST) active = false;     // hit rays of this tile see nothing dense: (0,0,0,0)
         float t_end = ray.t_exit;                        // samples at t >= t_end cannot be dense
-        if (culling && (fp.cull & CULL_AABB) && active) {
+        if (culling && (fe.cull & CULL_AABB) && active) {
             // slab test against the AABB of the occupied macro cells (conservative arithmetic)
             // v_rcp_f32 (1 ulp) instead of a division: the slab distances carry a 2e-5 margin
             const float rx = __builtin_amdgcn_rcpf(ray.d.x), ry = __builtin_amdgcn_rcpf(ray.d.y), rz = __builtin_amdgcn_rcpf(ray.d.z);
-            const float ax0 = (fp.aabb_lo[0] - ray.o.x) * rx, ax1 = (fp.aabb_hi[0] - ray.o.x) * rx;
-            const float ay0 = (fp.aabb_lo[1] - ray.o.y) * ry, ay1 = (fp.aabb_hi[1] - ray.o.y) * ry;
-            const float az0 = (fp.aabb_lo[2] - ray.o.z) * rz, az1 = (fp.aabb_hi[2] - ray.o.z) * rz;
+            const float ax0 = (fe.aabb_lo[0] - ray.o.x) * rx, ax1 = (fe.aabb_hi[0] - ray.o.x) * rx;
+            const float ay0 = (fe.aabb_lo[1] - ray.o.y) * ry, ay1 = (fe.aabb_hi[1] - ray.o.y) * ry;
+            const float az0 = (fe.aabb_lo[2] - ray.o.z) * rz, az1 = (fe.aabb_hi[2] - ray.o.z) * rz;
             float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax0, ax1), __builtin_fminf(ay0, ay1)), __builtin_fminf(az0, az1));
             float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax0, ax1), __builtin_fmaxf(ay0, ay1)), __builtin_fmaxf(az0, az1));
             tn = tn - 2.0e-5f * __builtin_fabsf(tn) - 1.0e-6f;
             tf = tf + 2.0e-5f * __builtin_fabsf(tf) + 1.0e-6f;
-            if (fp.cull & CULL_TILE_DEPTH) {
+            if (fe.cull & CULL_TILE_DEPTH) {
                 // ... and to the depth range of the occupied cells that project onto this 8x8 tile (volym_tile_depth_kernel, margins
                 // included; a quarter item reads its parent tile's).  Wave-uniform: two scalar loads.  No cell: near is NaN (fmax
                 // keeps tn) and far 0, which leaves no sample
-                const auto* td = (const __attribute__((address_space(4))) uint32_t*)fp.tile_depth;
-                const uint32_t t8 = (ty * 2u + (sub >> 1)) * fp.mask_t8x + tx * 2u + (sub & 1u);
+                const auto* td = (const __attribute__((address_space(4))) uint32_t*)fe.tile_depth;
+                const uint32_t t8 = (ty * 2u + (sub >> 1)) * fe.mask_t8x + tx * 2u + (sub & 1u);
                 tn = __builtin_fmaxf(tn, __uint_as_float(~td[t8]));
-                tf = __builtin_fminf(tf, __uint_as_float(td[32u * fp.mask_words + t8]));
+                tf = __builtin_fminf(tf, __uint_as_float(td[32u * fe.mask_words + t8]));
             }
             // a zero direction component makes its slab pair NaN/inf: fmin/fmax drop NaN, so test the origin there
-            const bool outside_static = (ray.d.x == 0.0f && (ray.o.x < fp.aabb_lo[0] || ray.o.x > fp.aabb_hi[0])) ||
-                                        (ray.d.y == 0.0f && (ray.o.y < fp.aabb_lo[1] || ray.o.y > fp.aabb_hi[1])) ||
-                                        (ray.d.z == 0.0f && (ray.o.z < fp.aabb_lo[2] || ray.o.z > fp.aabb_hi[2]));
+            const bool outside_static = (ray.d.x == 0.0f && (ray.o.x < fe.aabb_lo[0] || ray.o.x > fe.aabb_hi[0])) ||
+                                        (ray.d.y == 0.0f && (ray.o.y < fe.aabb_lo[1] || ray.o.y > fe.aabb_hi[1])) ||
+                                        (ray.d.z == 0.0f && (ray.o.z < fe.aabb_lo[2] || ray.o.z > fe.aabb_hi[2]));
             if (outside_static || !(tn <= tf)) {
                 active = false;                          // never inside the AABB: nothing dense on this ray
             } else {
@@ -825,14 +852,14 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         } else if (flags & F_CONE) {
 #pragma unroll
                             for (int j = 0; j < J; ++j)
-                                ahead[j] = ahead_cone_wave(g, fp, need[j], my_pos[j], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
+                                ahead[j] = ahead_cone_wave(g, fp_here(), need[j], my_pos[j], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
                         } else {
                             // (the straight look-ahead through the job ring was measured: 104 us against 66 -- one chain is one lane's work
                             // here, eight lanes' there, and the ring is a window of 32 samples)
                             bool any_need = false;
 #pragma unroll
                             for (int j = 0; j < J; ++j) any_need = any_need || need[j];
-                            if (__ballot(any_need) != 0ull) ahead_straight_wave<J>(g, fp, need, my_t, ray.o, ray.d, ray.t_exit, lane, mail, ahead, &la_rounds);
+                            if (__ballot(any_need) != 0ull) ahead_straight_wave<J>(g, fp_here(), need, my_t, ray.o, ray.d, ray.t_exit, lane, mail, ahead, &la_rounds);
                         }
 #pragma unroll
                         for (int j = 0; j < J; ++j) sm |= (static_cast<uint32_t>(__ballot(need[j] && ahead[j]) >> qsh) & 15u) << (4 * j);
@@ -932,12 +959,12 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     const bool need_k = active && dense_k && ib < 255u;
                     bool ahead_k;
                     if (flags & F_CONE) {
-                        ahead_k = ahead_cone_wave(g, fp, need_k, pos, ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
+                        ahead_k = ahead_cone_wave(g, fp_here(), need_k, pos, ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
                     } else {
                         const float tks[1] = {tk};
                         const bool needs[1] = {need_k};
                         bool founds[1];
-                        ahead_straight_wave<1>(g, fp, needs, tks, ray.o, ray.d, ray.t_exit, lane, mail, founds);
+                        ahead_straight_wave<1>(g, fp_here(), needs, tks, ray.o, ray.d, ray.t_exit, lane, mail, founds);
                         ahead_k = founds[0];
                     }
                     quad_s = static_cast<uint32_t>(__ballot(need_k && ahead_k) >> qsh) & 15u;
@@ -1143,12 +1170,12 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     } else if (flags & F_CONE) {
 #pragma unroll
                         for (int k = 0; k < K; ++k)
-                            supp[k] = ahead_cone_wave(g, fp, need[k], ray.o + ray.d * ts[k], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
+                            supp[k] = ahead_cone_wave(g, fp_here(), need[k], ray.o + ray.d * ts[k], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
                     } else {
                         bool any_need = false;
 #pragma unroll
                         for (int k = 0; k < K; ++k) any_need = any_need || need[k];
-                        if (__ballot(any_need) != 0ull) ahead_straight_wave<K>(g, fp, need, ts, ray.o, ray.d, ray.t_exit, lane, mail, supp, &la_rounds);
+                        if (__ballot(any_need) != 0ull) ahead_straight_wave<K>(g, fp_here(), need, ts, ray.o, ray.d, ray.t_exit, lane, mail, supp, &la_rounds);
                     }
 #pragma unroll
                     for (int k = 0; k < K; ++k) supp[k] = supp[k] && need[k];
@@ -1188,7 +1215,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     const bool dense_k = TABLE ? bs[k] >= fp.thr_byte : rhos[k] >= thr;
                     const bool need_k = chain && dense_k && ibs[k] < 255u;
                     chain = chain && dense_k == last_dense;
-                    ahead_pre[k] = ahead_cone_wave(g, fp, need_k, ray.o + ray.d * ts[k], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
+                    ahead_pre[k] = ahead_cone_wave(g, fp_here(), need_k, ray.o + ray.d * ts[k], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
                 }
             } else if (PRE_AHEAD && pre_ahead) {
                 bool need[K];
@@ -1199,7 +1226,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     need[k] = chain && dense_k && ibs[k] < 255u;
                     chain = chain && dense_k == last_dense;
                 }
-                ahead_straight_wave<K>(g, fp, need, ts, ray.o, ray.d, ray.t_exit, lane, mail, ahead_pre);
+                ahead_straight_wave<K>(g, fp_here(), need, ts, ray.o, ray.d, ray.t_exit, lane, mail, ahead_pre);
             }
             bool valid = active;
 #pragma unroll
@@ -1275,7 +1302,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         out_b = static_cast<float>(acc_b[own]) * PQ_FIX_INV;
             const uint32_t packed = pack_rgba8(out_r, out_g, out_b, acc_a);
             if (flags & F_RASTER) {
-                const size_t o = static_cast<size_t>(gy) * fp.W + gx;
+                const size_t o = static_cast<size_t>(gy) * fe.W + gx;
                 out_raster[o] = packed;
                 // (traced launch: the f32 frame carries the ray's and the tile's iteration counts instead, scripts/ray_lengths.py)
                 if (flags & F_WRITE_F32) out_f32[o] = TRACE ? make_float4(static_cast<float>(trace_ray_iters), static_cast<float>(tile_iters), out_b, acc_a) : make_float4(out_r, out_g, out_b, acc_a);
