@@ -57,3 +57,60 @@ def compare_images(got_f32, got_u8, ref_f32, ref_u8, tol=1e-4):
     over = int((d.max(axis=-1) > tol).sum())
     du8 = np.abs(got_u8.astype(np.int32) - ref_u8.astype(np.int32))
     return float(d.max()), over, int(du8.max()), float((du8 > 0).mean())
+
+
+# ---- the transfer-function and threshold axes (test_oracle_tf_threshold.py, test_gpu_tf_threshold.py) ----------------------
+
+def tf_family(rng):
+    """Named RGBA8 transfer-function tables (flat uint8, 4 * n bytes): the default one; random ones of n = 1, 2, 3, 7, 100, 255 and
+    256 texels; an opaque, a transparent, a comb (alpha 0 / 255 in turn) and a step table (alpha 0 below texel 96, 255 from
+    there on); and one baked from a handful of control points the way a user of scene.TransferFunction gets one."""
+    from volym_amd import scene
+    out = [("default", scene.default_lut())]
+    for n in (1, 2, 3, 7, 100, 255, 256):
+        out.append(("random %d" % n, rng.integers(0, 256, 4 * n, dtype=np.uint8)))
+
+    def with_alpha(alpha):
+        t = rng.integers(0, 256, (256, 4), dtype=np.uint8)
+        t[:, 3] = alpha
+        return t.ravel()
+
+    out.append(("opaque", with_alpha(255)))
+    out.append(("transparent", with_alpha(0)))
+    out.append(("comb", with_alpha(np.where(np.arange(256) % 2 == 0, 0, 255))))
+    out.append(("step", with_alpha(np.where(np.arange(256) < 96, 0, 255))))
+    tf = scene.TransferFunction()
+    for p in ((0.0, 0.1, 0.1, 0.4), (0.25, 0.9, 0.6, 0.1), (0.3, 1.0, 1.0, 1.0), (0.7, 0.2, 0.8, 0.3), (1.0, 1.0, 0.0, 0.0)):
+        tf.add_rgb_control_point(*p)
+    for p in ((0.0, 0.0), (0.2, 0.0), (0.35, 0.6), (0.5, 0.05), (0.8, 1.0), (1.0, 1.0)):
+        tf.add_alpha_control_point(*p)
+    out.append(("baked", tf.bake_rgba8()))
+    return out
+
+
+def terraced_volume(dims, levels):
+    """Prepared volume bytes (x fastest) of nested box-shaped terraces around the centre: 0 outside, then a plateau of each byte of
+    `levels` in turn, the last one in the middle.  Inside a plateau every trilinear or Gaussian sum is a sum of equal values
+    under weights that add up to about 1, so an interpolated density lands within an ulp of b/255, on either side."""
+    nx, ny, nz = dims
+    zz, yy, xx = np.meshgrid(*((np.arange(d) + 0.5) / d for d in (nz, ny, nx)), indexing="ij")
+    r = np.maximum(np.maximum(np.abs(xx - 0.5), np.abs(yy - 0.5)), np.abs(zz - 0.5)) / 0.5     # 0 in the centre, 1 on the faces
+    values = np.array([0] + list(levels), np.uint8)
+    band = np.clip(np.floor((1.0 - r) * 1.15 * len(values)).astype(np.int64), 0, len(values) - 1)
+    return values[band].ravel()
+
+
+def byte_thresholds(bs):
+    """float32 thresholds: prev(b/255), b/255 and next(b/255) for every byte b of `bs` (b/255 as float32 division, the value a
+    nearest-filter sample of byte b has), then 0, -1, 1, next(1) and 1.5; no value twice."""
+    out = []
+    for b in bs:
+        v = np.float32(b) / np.float32(255)
+        out += [np.nextafter(v, np.float32(-np.inf)), v, np.nextafter(v, np.float32(np.inf))]
+    out += [np.float32(0), np.float32(-1), np.float32(1), np.nextafter(np.float32(1), np.float32(2)), np.float32(1.5)]
+    seen, uniq = set(), []
+    for v in out:
+        if float(v) not in seen:
+            seen.add(float(v))
+            uniq.append(float(np.float32(v)))
+    return uniq
