@@ -315,6 +315,56 @@ int volym_assemble_packed(volym_ctx* ctx, const void* gathered_device, size_t st
 int volym_read_shard(volym_ctx* ctx, uint8_t* out);
 int volym_assemble_host(volym_ctx* ctx, const uint8_t* gathered_host);
 
+/* --- pick (new; the reference has none: its GUI has sliders only) --------------------------------------------------- */
+/* Segment, texel and depth under a pixel, by the rule the picture was made by.  For pixel (gx, gy) of the W x H frame take the
+ * ray of the last volym_update (camera and parameters) and march it exactly as wgsl:243-326 does through the scene as it
+ * stands, crop box and hidden segments included: the same positions, step state machine, threshold test, look-ahead suppression
+ * and alpha chain (w = (1 - alpha) * a; alpha += w, f32, in that order).  A composited sample is an iteration that reaches
+ * wgsl:313.  The pick is the first composited sample after whose compositing alpha >= alpha_min; the march ends there.  So
+ * alpha_min == 0 picks the first composited sample whatever its opacity; in first-hit mode (use_opacity == 0 without importance
+ * colouring) alpha becomes 1 at the first composited sample, which is then the pick for every valid alpha_min; importance
+ * colouring follows the same rule with its own alpha source.  A ray that leaves the loop without a pick has none.
+ * Valid: 0 <= alpha_min <= 0.95 (the loop's own exit); NaN or anything else is VOLYM_E_INVALID. */
+struct volym_pick {
+    float    t;          /* ray parameter of the picked sample (pos = eye + d*t); -1 unless status == 2 */
+    uint16_t x, y, z;    /* its nearest texel, clamp(floor(pos*n), 0, n-1), in the volume as volym_set_volume received it
+                            (the coordinates volym_set_crop_box takes) */
+    uint8_t  label;      /* label byte of that texel; 0 when has_labels == 0 */
+    uint8_t  density;    /* density byte of that texel as the march sees it */
+    uint8_t  status;     /* 0 = the ray misses the cube, 1 = hits it, nothing picked, 2 = picked */
+    uint8_t  alpha8;     /* unorm8 of alpha after the picked sample; status 1: the ray's final alpha; status 0: 255 */
+    uint8_t  has_labels; /* 1 = labels with the volume's dimensions are on the device */
+    uint8_t  reserved;   /* 0 */
+};                       /* 16 bytes; records of status 0 or 1 have x = y = z = label = density = 0 */
+/* The call volym_pick below shares the record's name, and C keeps typedef names and functions in one name space: the record is
+ * `struct volym_pick` (a tag, which may share it), or volym_pick_record for short. */
+typedef struct volym_pick volym_pick_record;
+#if defined(__cplusplus)
+static_assert(sizeof(struct volym_pick) == 16, "volym_pick is 16 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(struct volym_pick) == 16, "volym_pick is 16 bytes");
+#endif
+/* Enqueue only: one pick march of the rect {x0, y0, w, h} (NULL = the whole frame) goes behind what is already enqueued, into a
+ * device buffer the context owns: w*h records, row-major within the rect.  The buffer grows to the largest rect asked for so far;
+ * the call blocks only when it has to grow, as volym_blit does for its target.  An empty rect, or one not inside the frame, is
+ * VOLYM_E_INVALID; a call without volume, importances, transfer function or a volym_update is VOLYM_E_STATE.
+ *   A pick pass only reads the scene and writes no frame buffer: a frame enqueued before or after it is byte for byte the frame
+ * without it.  With VOLYM_OPT_FRAMES_IN_FLIGHT = 2 it runs on the first slot alone, like volym_stats_pass; with a caller's stream
+ * (volym_set_stream) it goes on that stream.  On a sharded context it ignores the shard: any pixel of the W x H frame may be
+ * picked, since every rank holds the whole volume (the native multi-GPU loop has no forward for it).
+ *   It works with uploaded importances, with labels + table, or with no labels at all (has_labels = 0); labels whose dimensions
+ * differ from the volume's count as absent.  The labels may sit in a different device layout than the volume: there is one label
+ * fetch per ray, and it takes the labels' own layout.  Cost: a subset of a frame's work per ray -- no gradient taps, no shading,
+ * and the march stops at the pick. */
+int volym_pick_pass(volym_ctx* ctx, const uint32_t rect[4], float alpha_min);
+/* Blocks; copies the w*h records of the latest pick pass.  VOLYM_E_STATE before any pass. */
+int volym_read_picks(volym_ctx* ctx, struct volym_pick* out);
+/* The device buffer of the latest pick pass (for a highlight or outline pass on the same stream), or NULL before any.  A later
+ * pass with a larger rect may move it. */
+void* volym_pick_device_ptr(volym_ctx* ctx);
+/* A pick pass over the one pixel (x, y) plus the read.  Blocks. */
+int volym_pick(volym_ctx* ctx, uint32_t x, uint32_t y, float alpha_min, struct volym_pick* out);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

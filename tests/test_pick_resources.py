@@ -1,0 +1,94 @@
+"""What the compiler made of the pick kernels (no GPU: any machine with hipcc).
+
+pick.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
+tests/test_kernel_resources.py compiles the march units.  The table-mode, linear-layout instantiation -- what a pick of the common
+frame runs -- must have no scratch and at most 128 VGPRs: volym_raymarch_kernel<1, false, false, false>, whose launch shape and
+leaps it shares, does strictly more per ray (gradient taps, shading, colour) in 96 VGPRs and no scratch
+(profiles/r02_kernel_resources.txt).  The figures of every instantiation go to profiles/pick_kernel_resources.txt; the general ones
+(look-ahead, smoothing, trilinear, colouring) have no bar.
+"""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "volym_amd", "csrc")
+HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+OUT = os.path.join(ROOT, "profiles", "pick_kernel_resources.txt")
+
+pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
+
+
+def makefile_flags():
+    """ARCH and CXXFLAGS as volym_amd/csrc/Makefile states them (the product build, no DEV), warnings dropped"""
+    text = open(os.path.join(CSRC, "Makefile")).read()
+    var = lambda name: re.search(r"^%s\s*[:?]?=\s*(.*)$" % name, text, re.M).group(1).split()
+    return ["--offload-arch=" + var("ARCH")[0]] + [f for f in var("CXXFLAGS") if not f.startswith("-W")]
+
+
+def remarks(stderr):
+    """{mangled kernel name: {figure: value}} from the kernel-resource-usage remarks"""
+    out = {}
+    for blk in stderr.split("Function Name: ")[1:]:
+        name = blk.split(" [")[0].strip()
+        g = lambda k: int(re.search(k + r": (\d+)", blk).group(1))
+        out[name] = {"vgpr": g("VGPRs"), "sgpr": g("SGPRs"), "scratch": g(r"ScratchSize \[bytes/lane\]"), "occ": g(r"Occupancy \[waves/SIMD\]"),
+                     "lds": g(r"LDS Size \[bytes/block\]")}
+    return out
+
+
+@pytest.fixture(scope="module")
+def pick_unit(tmp_path_factory):
+    out = os.path.join(str(tmp_path_factory.mktemp("pick")), "pick.s")
+    cmd = [HIPCC] + makefile_flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", os.path.join(CSRC, "pick.hip"), "-o", out]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return open(out).read(), remarks(p.stderr)
+
+
+def instantiations(res):
+    """{(bricked, general): figures} of the volym_pick_kernel<BRICK, GENERAL> instantiations"""
+    out = {}
+    for name, r in res.items():
+        m = re.search(r"volym_pick_kernelILb([01])ELb([01])E", name)
+        if m:
+            out[(m.group(1) == "1", m.group(2) == "1")] = r
+    return out
+
+
+def test_the_makefile_builds_and_links_the_unit():
+    text = open(os.path.join(CSRC, "Makefile")).read()
+    assert re.search(r"pick\$\(SFX\)\.o:.*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c", text)
+    assert re.search(r"^\$\(OUT\):.*pick\$\(SFX\)\.o", text, re.M)
+
+
+def test_common_instantiation_has_no_scratch_and_fits_four_waves(pick_unit):
+    inst = instantiations(pick_unit[1])
+    assert set(inst) == {(False, False), (False, True), (True, False), (True, True)}, list(pick_unit[1])
+    lines = ["volym_pick_kernel<BRICK, GENERAL> (pick.hip), hipcc with the Makefile's flags, -Rpass-analysis=kernel-resource-usage",
+             "written by tests/test_pick_resources.py; bar: <false, false> scratch 0, VGPRs <= 128; none for the others", ""]
+    for (brick, general), r in sorted(inst.items()):
+        lines.append("pick_kernel<%-5s, %-5s>  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (
+            str(brick).lower(), str(general).lower(), r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
+    print("\n".join(lines))
+    try:
+        with open(OUT, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    except OSError:
+        pass                                  # a read-only checkout still checks the bar
+    common = inst[(False, False)]
+    assert common["scratch"] == 0, common
+    assert common["vgpr"] <= 128, common
+
+
+def test_the_unit_holds_no_frame_kernel_and_no_scalar_memory_write(pick_unit):
+    listing, res = pick_unit
+    assert not [n for n in res if "volym_raymarch" in n], "pick.hip must not instantiate the frame kernels"
+    # records leave through vector stores: exactly the 16-byte store per lane
+    body = [l.strip() for l in listing.split("\n")]
+    stores = [l for l in body if l.startswith(("global_store", "flat_store", "buffer_store"))]
+    assert stores and all(l.startswith("global_store_dwordx4") for l in stores), sorted(set(s.split()[0] for s in stores))
+    assert not [l for l in body if re.match(r"s_(buffer_|scratch_)?(store|atomic)", l)]

@@ -10,7 +10,8 @@ HIP events.  The reference's teapot .raw files are not distributed (.MISSING_LAR
 --volume/--labels/--segments for real data, otherwise the synthetic stand-in of volym_amd.synth is used.
 
 run simple: renders the interactive default view (src/state.rs:41-55) once and writes screenshot_<unix time>.png
-like the reference's `P` key (src/state.rs:85-113).
+like the reference's `P` key (src/state.rs:85-113).  --pick X,Y[,ALPHA] then prints what that pixel shows (segment, texel,
+depth) as one JSON line.
 """
 import argparse
 import csv
@@ -135,6 +136,19 @@ def _hide_arg(text):
     return v
 
 
+def _pick_arg(text):
+    """--pick X,Y[,ALPHA] (pixel of the frame, alpha_min) -> (x, y, alpha_min)"""
+    try:
+        v = text.split(",")
+        x, y = int(v[0]), int(v[1])
+        alpha = float(v[2]) if len(v) == 3 else 0.5
+    except (ValueError, IndexError):
+        raise SystemExit("--pick: X,Y[,ALPHA] -- a pixel of the frame and alpha_min in [0, 0.95] (default 0.5)")
+    if len(v) > 3 or x < 0 or y < 0:
+        raise SystemExit("--pick: X,Y[,ALPHA] -- a pixel of the frame and alpha_min in [0, 0.95] (default 0.5)")
+    return x, y, alpha
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -150,9 +164,13 @@ def run_simple(args):
         d.compute_pass(ctx)
         ctx.sync()
         frame = ctx.read_rgba8()
+        picked = d.pick(ctx, *_pick_arg(args.pick)) if getattr(args, "pick", None) else None
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    if picked is not None:
+        import json
+        print(json.dumps(picked))      # one line: what the pixel shows (demo.Simple.pick)
     return 0
 
 
@@ -245,6 +263,7 @@ def main(argv=None):
     run.add_argument("--screenshot")
     run.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
     run.add_argument("--hide", help="label values of the segments to hide, e.g. 3,4")
+    run.add_argument("--pick", help="X,Y[,ALPHA]: after the frame, print what pixel (X, Y) shows as one JSON line (segment, texel, depth)")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359
     b.add_argument("--secs", type=float, default=0.25, help="GPU seconds per trial (the reference uses 2 s of wall clock)")

@@ -5,6 +5,8 @@ There is no CPU fallback: if the shared library is missing or a call fails, this
 import ctypes as C
 import os
 
+import numpy as np
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VOLYM_HIP_LIB") or os.path.join(_HERE, "libvolym_hip.so")   # the override is for A/B builds during development
 
@@ -52,6 +54,22 @@ class Stats(C.Structure):
 
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+class Pick(C.Structure):
+    """volym_pick (include/volym_hip.h): the record of one picked pixel, 16 bytes"""
+    _fields_ = [
+        ("t", C.c_float),
+        ("x", C.c_uint16), ("y", C.c_uint16), ("z", C.c_uint16),
+        ("label", C.c_uint8), ("density", C.c_uint8), ("status", C.c_uint8), ("alpha8", C.c_uint8),
+        ("has_labels", C.c_uint8), ("reserved", C.c_uint8),
+    ]
+
+
+# the same record as a NumPy structured dtype (GpuContext.read_picks)
+PICK_DTYPE = np.dtype([("t", "<f4"), ("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("label", "u1"), ("density", "u1"), ("status", "u1"),
+                       ("alpha8", "u1"), ("has_labels", "u1"), ("reserved", "u1")])
+PICK_MISS, PICK_NONE, PICK_HIT = 0, 1, 2      # volym_pick.status
 
 
 class CCamera(C.Structure):
@@ -158,6 +176,10 @@ SIGNATURES = {
     "volym_assemble_packed": (C.c_int, [_ctx, C.c_void_p, C.c_size_t]),
     "volym_read_shard": (C.c_int, [_ctx, _u8p]),
     "volym_assemble_host": (C.c_int, [_ctx, _u8p]),
+    "volym_pick_pass": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.c_float]),
+    "volym_read_picks": (C.c_int, [_ctx, C.POINTER(Pick)]),
+    "volym_pick_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_pick": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(Pick)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -1,6 +1,6 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, with mgpu.inc, the native
-// multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and their C ABI).
+// multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and their C ABI; pick.hip: the pick march).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -194,6 +194,12 @@ struct volym_ctx {
     hipEvent_t throttle_ev[THROTTLE_RING] = {};
     uint32_t throttle_head = 0;
 
+    // pick passes (volym_pick_pass): the records of the latest pass, in a buffer that grows to the largest rect asked for so far.
+    // Always written on slot 0's stream.
+    volym_pick_record* d_picks = nullptr;
+    size_t pick_capacity = 0;                // records d_picks holds
+    uint32_t pick_w = 0, pick_h = 0;         // rect size of the latest pass (0: none yet)
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -248,6 +254,9 @@ int quiesce_slots(volym_ctx* c);
 int rebuild_lists(volym_ctx* c);
 // raymarch.hip: the look-ahead's reject box of a frame from imp_box_*
 void set_reject_box(const volym_ctx* c, FrameParams& fp);
+// pick.hip: one pick march of rect {x0, y0, w, h} (inside the frame, not empty) into `out` (w * h records), enqueued on the slot's
+// stream with the slot's frame parameters, tables and -- when it is the one of the current threshold and scene -- distance field
+int launch_pick(volym_ctx* c, FrameSlot& s, const uint32_t rect[4], float alpha_min, void* out);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 

@@ -134,6 +134,40 @@ public:
         }
         ctx.check(volym_set_segment_visibility(ctx.handle(), visible));
     }
+    // New: what pixel (x, y) of the frame shows -- the first sample of its ray after which alpha >= alpha_min (volym_pick): the
+    // record, the name of the segment with its label (empty: none, or no labels) and the texel's centre in the unit-cube
+    // coordinates set_crop takes.  The labels go to the device first if they are not there yet.
+    struct Picked {
+        volym_pick_record record;
+        std::string segment;
+        float pos[3];
+    };
+    Picked pick(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, float alpha_min = 0.5f)
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        Picked p{};
+        ctx.check(volym_pick(ctx.handle(), x, y, alpha_min, &p.record));
+        const uint32_t n[3] = {a.nx, a.ny, a.nz}, t[3] = {p.record.x, p.record.y, p.record.z};
+        for (int i = 0; i < 3; ++i) p.pos[i] = (static_cast<float>(t[i]) + 0.5f) / static_cast<float>(n[i]);
+        if (p.record.status == 2 && p.record.has_labels)
+            for (const SegmentInfo& s : a.segments)
+                if (s.label_value == p.record.label) { p.segment = s.name; break; }
+        return p;
+    }
+    // New: click to hide -- a pick, then set_hidden with that label added to the hidden ones.  Nothing changes when the pixel shows
+    // no labelled sample.
+    Picked hide_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, float alpha_min = 0.5f)
+    {
+        const Picked p = pick(ctx, a, x, y, alpha_min);
+        if (p.record.status != 2 || !p.record.has_labels) return p;
+        uint8_t visible[256];
+        ctx.check(volym_get_segment_visibility(ctx.handle(), visible));
+        std::vector<uint8_t> hidden;
+        for (int l = 0; l < 256; ++l)
+            if (!visible[l] || l == p.record.label) hidden.push_back(static_cast<uint8_t>(l));
+        set_hidden(ctx, a, hidden);
+        return p;
+    }
     static uint32_t crop_texel(float p, uint32_t n)
     {
         const double t = std::floor(static_cast<double>(p) * n + 0.5);

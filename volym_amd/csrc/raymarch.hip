@@ -842,6 +842,7 @@ void volym_destroy(volym_ctx* c)
     // (every slot's stream is idle now: nothing reads the scene any more)
     (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc);
     (void)hipFree(c->d_vol0); (void)hipFree(c->d_imp0);
+    (void)hipFree(c->d_picks);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }
@@ -1624,6 +1625,59 @@ int volym_assemble_host(volym_ctx* c, const uint8_t* gathered_host)
     HIPCHK(c, hipMemcpyAsync(s.d_gather_tmp, gathered_host, bytes, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipStreamSynchronize(s.stream));
     return volym_assemble(c, s.d_gather_tmp);
+}
+
+// ---- pick: segment, texel and depth under a pixel (the march itself: pick.hip) -----------------------------------------
+int volym_pick_pass(volym_ctx* c, const uint32_t rect[4], float alpha_min)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!(alpha_min >= 0.0f && alpha_min <= 0.95f)) return fail(c, VOLYM_E_INVALID, "volym_pick_pass: alpha_min must be in [0, 0.95]");
+    const uint32_t whole[4] = {0u, 0u, c->W, c->H};
+    const uint32_t* r = rect ? rect : whole;
+    if (r[2] == 0u || r[3] == 0u || r[0] >= c->W || r[1] >= c->H || r[2] > c->W - r[0] || r[3] > c->H - r[1])
+        return fail(c, VOLYM_E_INVALID, "volym_pick_pass: the rect must be non-empty and inside the frame");
+    if (!c->have_vol || !c->have_imp || !c->have_tf) return fail(c, VOLYM_E_STATE, "volym_pick_pass: set volume, importances and transfer function first");
+    if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_pick_pass: call volym_update first");
+    FrameSlot& s = c->slot0();
+    if (s.fp.nx != c->nx || s.fp.ny != c->ny || s.fp.nz != c->nz || c->inx != c->nx || c->iny != c->ny || c->inz != c->nz)
+        return fail(c, VOLYM_E_STATE, "volym_pick_pass: the volume changed since the last volym_update");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t need = static_cast<size_t>(r[2]) * r[3];
+    if (need > c->pick_capacity) {
+        // grown on demand (a set-up step: the one blocking path of the call); earlier passes ran on this stream
+        HIPCHK(c, hipStreamSynchronize(s.stream));
+        if (c->d_picks) { HIPCHK(c, hipFree(c->d_picks)); c->d_picks = nullptr; c->pick_capacity = 0; c->pick_w = c->pick_h = 0; }
+        hipError_t e = hipMalloc(&c->d_picks, need * sizeof(volym_pick_record));
+        if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(pick records): ") + hipGetErrorString(e));
+        c->pick_capacity = need;
+    }
+    const int rc = launch_pick(c, s, r, alpha_min, c->d_picks);
+    if (rc != VOLYM_OK) return rc;
+    c->pick_w = r[2]; c->pick_h = r[3];
+    return VOLYM_OK;
+}
+
+int volym_read_picks(volym_ctx* c, volym_pick_record* out)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_picks: NULL output");
+    if (!c->d_picks || c->pick_w == 0u) return fail(c, VOLYM_E_STATE, "volym_read_picks: no volym_pick_pass yet");
+    FrameSlot& s = c->slot0();
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_picks, static_cast<size_t>(c->pick_w) * c->pick_h * sizeof(volym_pick_record), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    return VOLYM_OK;
+}
+
+void* volym_pick_device_ptr(volym_ctx* c) { return (c && c->pick_w != 0u) ? c->d_picks : nullptr; }
+
+int volym_pick(volym_ctx* c, uint32_t x, uint32_t y, float alpha_min, volym_pick_record* out)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!out) return fail(c, VOLYM_E_INVALID, "volym_pick: NULL output");
+    const uint32_t rect[4] = {x, y, 1u, 1u};
+    const int rc = volym_pick_pass(c, rect, alpha_min);
+    return rc != VOLYM_OK ? rc : volym_read_picks(c, out);
 }
 
 int volym_stats_pass(volym_ctx* c, volym_stats* out)

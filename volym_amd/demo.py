@@ -216,6 +216,36 @@ class GpuContext:
         g = np.ascontiguousarray(gathered, np.uint8).ravel()
         self._ck(_lib.lib().volym_assemble_host(self.handle, scene._u8p(g)))
 
+    # ---- pick ---------------------------------------------------------------------------------
+    def pick_pass(self, rect=None, alpha_min=0.0):
+        """Enqueue one pick march of rect = (x0, y0, w, h) (None: the whole frame) behind what is enqueued: per pixel the first
+        composited sample after which alpha >= alpha_min (include/volym_hip.h volym_pick_pass)."""
+        r = None
+        if rect is not None:
+            if len(rect) != 4:
+                raise ValueError("a pick rect is (x0, y0, w, h)")
+            r = (C.c_uint32 * 4)(*[int(v) for v in rect])
+        self._ck(_lib.lib().volym_pick_pass(self.handle, r, float(alpha_min)))
+        self._pick_size = (int(rect[3]), int(rect[2])) if rect is not None else (self.height, self.width)
+
+    def read_picks(self):
+        """The records of the latest pick pass: a structured array (_lib.PICK_DTYPE) of shape (h, w).  Blocks."""
+        size = getattr(self, "_pick_size", None)
+        out = np.zeros(size if size else (1, 1), _lib.PICK_DTYPE)
+        self._ck(_lib.lib().volym_read_picks(self.handle, out.ctypes.data_as(C.POINTER(_lib.Pick))))
+        return out
+
+    def pick_device_ptr(self):
+        """Device buffer of the latest pick pass (None before any)."""
+        return _lib.lib().volym_pick_device_ptr(self.handle)
+
+    def pick(self, x, y, alpha_min=0.0):
+        """The record of pixel (x, y): a pass over one pixel plus the read (np.void of _lib.PICK_DTYPE).  Blocks."""
+        out = np.zeros(1, _lib.PICK_DTYPE)
+        self._ck(_lib.lib().volym_pick(self.handle, int(x), int(y), float(alpha_min), out.ctypes.data_as(C.POINTER(_lib.Pick))))
+        self._pick_size = (1, 1)
+        return out[0]
+
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
         s = _lib.Stats()
@@ -322,6 +352,38 @@ class Simple(ComputeDemo):
             self.set_labels(ctx, self._labels_raw)
         ctx.set_segment_visibility(mask)
         return sorted(values)
+
+    def pick(self, ctx, x, y, alpha_min=0.5):
+        """What pixel (x, y) of the frame shows: the first sample of its ray after which alpha >= alpha_min (GpuContext.pick), as
+        a dict: status ("miss" / "none" / "hit"), label (None without labels), segment and segment_id (name and id of the segments
+        JSON entry with that label value, else None), texel (x, y, z) in the prepared volume, pos (the texel's centre in the unit-cube coordinates
+        set_crop takes), t (along the ray from the eye), alpha and density.  The labels go to the device first if they are not
+        there yet (the importances stay what they were)."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        r = ctx.pick(x, y, alpha_min)
+        status = ("miss", "none", "hit")[int(r["status"])]
+        out = {"x": int(x), "y": int(y), "status": status, "label": None, "segment": None, "segment_id": None, "texel": None, "pos": None, "t": None,
+               "alpha": int(r["alpha8"]) / 255.0, "density": None}
+        if status == "hit":
+            texel = (int(r["x"]), int(r["y"]), int(r["z"]))
+            out.update(texel=texel, pos=tuple((i + 0.5) / n for i, n in zip(texel, self.dims)), t=float(r["t"]), density=int(r["density"]))
+            if int(r["has_labels"]):
+                out["label"] = int(r["label"])
+                seg = next((s for s in getattr(self, "_segments", []) if s["label_value"] == out["label"]), None)
+                if seg is not None:
+                    out["segment"], out["segment_id"] = seg.get("name"), seg.get("id")
+        return out
+
+    def hide_at(self, ctx, x, y, alpha_min=0.5):
+        """Click to hide: pick pixel (x, y), then set_hidden with that label added to the hidden ones.  Returns the pick (its
+        "hidden" entry: the label values hidden now); nothing changes when the pixel shows no labelled sample."""
+        p = self.pick(ctx, x, y, alpha_min)
+        hidden = [int(l) for l in np.flatnonzero(ctx.segment_visibility() == 0)] if self._labels_on_device else []
+        if p["status"] == "hit" and p["label"] is not None:
+            hidden = self.set_hidden(ctx, sorted(set(hidden) | {p["label"]}))
+        p["hidden"] = hidden
+        return p
 
     def set_labels(self, ctx, labels_raw):
         """Keep the label map on the device (new; the reference maps it once on the host), so that set_segments can change
