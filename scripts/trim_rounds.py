@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Re-balancing rounds of a standing view's work list (raymarch.hip trim_list): sustained frame time by number of rounds.
+"""Re-balancing rounds of a standing view's work list (worklist.cpp trim_list): sustained frame time by number of rounds.
 Development aid; needs the DEV build (make -C volym_amd/csrc DEV=1, VOLYM_HIP_LIB=volym_amd/libvolym_hip_dev.so).
 VOLYM_TRIM_LOG=1 prints what every round measured."""
 import os

@@ -129,6 +129,7 @@ def main():
             [round(float(x) / 100, 1) for x in end[sl]], [round(float(x) / 100, 1) for x in dur[sl]], iters[sl].tolist(), dp_iters[sl].tolist(), flushes[sl].tolist(), tiles[sl].tolist()))
         # what the host predicted: cost share of every item of the list, dealt b, b+G, ...
         G = 256
+        # (the code of an entry is defined in volym_amd/csrc/worklist_entry.h; this is its NumPy decode)
         pad = order == 0xFFFFFFFF
         raw = np.where(pad, 0, order & ~np.uint32(0x30000000)).astype(np.uint32)
         is_q = (raw >> 31) != 0

@@ -1,6 +1,8 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
-// logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, with mgpu.inc, the native
-// multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and their C ABI; pick.hip: the pick march).
+// logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
+// capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
+// their C ABI; pick.hip: the pick march).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// host only, it knows nothing of this header.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,22 +18,7 @@
 
 #include "../../include/volym_hip.h"
 #include "raymarch_device.h"
-
-namespace volym {
-
-// One work list as the kernel reads it: workgroup b takes entries b, b + grid, ... (raymarch_pq.h).
-struct WorkList {
-    std::vector<uint32_t> entries;   // host copy (the feedback thread maps list positions back to tiles)
-    uint32_t grid = 0;               // workgroups the list was dealt to (0: the geometric list, any grid)
-    uint64_t view_serial = 0;        // the view whose measured costs produced it (0: none, geometric order)
-    bool has_dp = false;             // holds depth-parallel entries (their costs come back as estimates)
-    bool trimmable = false;          // dealt for a standing view from costs measured on whole entries
-    uint32_t trim_round = 0;         // times the list was re-balanced from measured workgroup times since it was dealt
-    bool final_for_view = false;     // trimmable and trimmed as often as asked: no more captures
-    std::vector<uint16_t> shares;    // by list position: the cost share the entry was dealt with (trimmable lists)
-};
-
-}  // namespace volym
+#include "worklist.hpp"
 
 namespace volym {
 
@@ -39,21 +26,9 @@ namespace volym {
 struct FbJob {
     int list = 0;                            // which of lists[] the captured launch ran
     uint32_t n_entries = 0;
-    uint64_t view_serial = 0;
-    bool captured_has_dp = false;
-    bool continuous = false;
-    bool plain = false;                      // table mode, no importance mode (the common instantiation)
-    uint32_t max_grid = 0, waves = 16;
-    int dp_min_cost = -1;
-    uint32_t dp_share_pct = 60, fill_cost = 2;
-    bool super_fill = true, only_quarters = false;
-    int dilate = -1;
-    uint32_t grid = 0;                       // workgroups of the captured launch
-    uint32_t dev_drop_tenths = 0;            // dev
-    uint32_t dp_floor = 64;
-    uint32_t trim_rounds = 0;
+    CapturedLaunch launch;                   // the facts of that launch the scheduler reads
+    ListSettings set;                        // the context's settings at the capture
     double t_us[6] = {};                     // dev: wall-clock stamps of the job's stages
-    uint32_t prio_tenths[3] = {3, 6, 10};
     std::string error;                       // worker -> caller
 };
 
@@ -203,19 +178,10 @@ struct volym_ctx {
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
-    uint32_t trim_rounds = 0;                   // re-balancing rounds from measured workgroup times after a standing view's list is dealt (VOLYM_OPT_REBALANCE_ROUNDS; off: see trim_list)
-    int cost_dilate = -1;                       // radius (8x8 items) of the max-filter over the cost map before dealing; -1: 1 while the view moves, else 0
-    bool super_fill = true;
-    uint32_t prio_tenths[3] = {3, 6, 10};
-    bool dev_only_quarters = false;
-    uint32_t dev_drop_tenths = 0;
-    uint32_t dp_floor = 64;                      // floor of the adaptive split threshold, cost units (deal_list)
+    volym::ListSettings list_settings;          // how the work lists are dealt (worklist.hpp)
     bool bricked = false;
     uint64_t brick_from_bytes = 64ull << 20;
     int layout_choice = -1;
-    uint32_t dp_share_pct = 60;
-    uint32_t fill_cost = 2;
-    int dp_min_cost = -1;
     int n_cus = 256;
     uint32_t wgs_per_cu = 1;
     bool culling = true;

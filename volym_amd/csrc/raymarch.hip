@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "context.hpp"
+#include "worklist.hpp"
 #include "raymarch_kernels.h"
 #include "raymarch_pq.h"
 #include "raymarch_pool.h"
@@ -58,6 +59,8 @@ static void recompute_shard(volym_ctx* c)
     c->n_local = c->n_tiles > c->rank ? (c->n_tiles - c->rank + c->world - 1) / c->world : 0;
     c->shard_tiles = (c->n_tiles + c->world - 1) / c->world;   // equal-sized shards, padded
 }
+
+static ShardGrid shard_grid(const volym_ctx* c) { return ShardGrid{c->W, c->H, c->tiles_x, c->tiles_y, c->rank, c->world, c->n_local}; }
 
 static uint32_t max_grid(const volym_ctx* c) { return static_cast<uint32_t>(c->n_cus) * c->wgs_per_cu; }
 
@@ -229,327 +232,15 @@ static void compute_culling(const volym_ctx* c, FrameSlot& s)
     s.mask_wanted = (fp.cull & CULL_OBJ_HULL) != 0u && c->tile_mask && c->tile_mask_words != 0u;
 }
 // ================================================================================================================
-// Work lists and their cost feedback (variant 2).
+// Work lists and their cost feedback (variant 2): the thread and the capture.  What list is dealt from what costs is the
+// scheduler's business (worklist.hpp); this unit runs it.
 //
-// The kernel's persistent workgroups read a list of items; the frame time is set by how well that list balances the few
-// hundred tiles whose rays take ~10x the average number of dependent samples.  Only a rendered frame knows which they
-// are, so a launch can be asked to report a counted cost per list entry ("capture"): the costs are copied to pinned host
-// memory on a second stream, and a feedback THREAD -- never the caller -- turns them into the next list: most expensive
-// entries first and dealt longest-processing-time first to the workgroups, the most expensive tiles split into four
-// depth-parallel quarter items, constant 16x16 tiles merged into super-fill items.  The caller's volym_compute_pass only
-// looks at an atomic flag: when a new list is ready it switches to it between two launches.  Lists are scheduling only:
-// every list renders the same pixels, so a list measured on a neighbouring view is a good list for this one, and a
-// moving camera simply keeps the feedback running (one capture in flight at a time).
+// A launch can be asked to report a counted cost per list entry ("capture"): the costs are copied to pinned host
+// memory on a second stream, and a feedback THREAD -- never the caller -- turns them into the next list (deal_list, or
+// trim_list for a standing view) and uploads it.  The caller's volym_compute_pass only looks at an atomic flag: when a new
+// list is ready it switches to it between two launches.  A moving camera simply keeps the feedback running (one capture
+// in flight at a time).
 // ================================================================================================================
-
-// geometric list: the 8x8-pixel wave tiles of this rank's 16x16 tiles (item = local_tile*4 + sub), by Chebyshev
-// distance of the tile centre from the screen centre.  The orbit camera always targets the volume centre
-// (src/camera.rs:23), so the long rays are the central ones: they start first.
-static void build_geometric(volym_ctx* c)
-{
-    std::vector<std::pair<uint32_t, uint32_t>> keyed;
-    keyed.reserve(static_cast<size_t>(c->n_local) * 4);
-    for (uint32_t lt = 0; lt < c->n_local; ++lt) {
-        const uint32_t tile = lt * c->world + c->rank;
-        const uint32_t tx = tile % c->tiles_x, ty = tile / c->tiles_x;
-        for (uint32_t sub = 0; sub < 4; ++sub) {
-            const int x0 = static_cast<int>(tx * 16u + (sub & 1u) * 8u), y0 = static_cast<int>(ty * 16u + (sub >> 1) * 8u);
-            if (x0 >= static_cast<int>(c->W) || y0 >= static_cast<int>(c->H)) {
-                if (c->world == 1) continue;          // wholly outside the frame: nothing to store in raster mode
-            }
-            const int dx = std::abs(2 * x0 + 8 - static_cast<int>(c->W)), dy = std::abs(2 * y0 + 8 - static_cast<int>(c->H));
-            // rings of 16 pixels; inside a ring a hash decides, so that a workgroup (which takes every G-th item)
-            // does not sit at the same angular position on every ring
-            const uint32_t item = lt * 4u + sub;
-            uint32_t h = item * 0x9E3779B1u;
-            h ^= h >> 15; h *= 0x85EBCA77u; h ^= h >> 13;
-            keyed.emplace_back((static_cast<uint32_t>(std::max(dx, dy)) / 32u) << 20 | (h & 0xfffffu), item);
-        }
-    }
-    std::sort(keyed.begin(), keyed.end());
-    c->geometric.resize(keyed.size());
-    for (size_t i = 0; i < keyed.size(); ++i) c->geometric[i] = keyed[i].second;
-}
-
-// Deal `item_cost` into a list (feedback thread; also the caller's thread inside blocking set-up calls).
-static void deal_list(const volym_ctx* c, const FrameSlot& s, const FbJob& job, const std::vector<uint16_t>& measured_cost, std::vector<uint8_t>& item_is_dp,
-                      const std::vector<uint32_t>& geometric, uint32_t n_local, WorkList& out)
-{
-    const uint32_t waves = job.waves;
-    // The costs were measured on an earlier frame; when the camera moves, what was expensive there is expensive a tile or two
-    // further on here.  A maximum filter over the neighbouring 8x8 items (radius job.dilate) makes the list hold for a
-    // while: the price is a few tiles split or started early that did not need it.
-    std::vector<uint16_t> item_cost(measured_cost);
-    // Has the camera moved since the captured frame?  Then the list will be read on yet another view: dilate the costs and
-    // keep split tiles split (hysteresis).  A view that stands still gets exactly what its own costs say -- but only costs
-    // MEASURED on whole 8x8 entries say it well (a split tile reports an estimate).  So when the captured list held split
-    // tiles, the first deal for a standing view is a measuring list without any split, and the deal after it is final.
-    const bool moving = s.view_serial.load(std::memory_order_relaxed) != job.view_serial;
-    const bool measuring = !moving && job.captured_has_dp && job.dp_min_cost < 0;
-    const int dilate = job.dilate >= 0 ? job.dilate : (moving ? 1 : 0);
-    if (dilate > 0) {
-        const uint32_t gw = c->tiles_x * 2u, gh = c->tiles_y * 2u;
-        std::vector<uint16_t> grid(static_cast<size_t>(gw) * gh, 0), tmp(static_cast<size_t>(gw) * gh, 0);
-        auto cell_of = [&](uint32_t item) {
-            const uint32_t tile = (item >> 2) * c->world + c->rank, sub = item & 3u;
-            return static_cast<size_t>((tile / c->tiles_x) * 2u + (sub >> 1)) * gw + (tile % c->tiles_x) * 2u + (sub & 1u);
-        };
-        for (uint32_t item : geometric) grid[cell_of(item)] = measured_cost[item];
-        const int r = dilate;
-        for (uint32_t y = 0; y < gh; ++y)
-            for (uint32_t x = 0; x < gw; ++x) {
-                uint16_t m = 0;
-                for (int d = -r; d <= r; ++d) { const int xx = static_cast<int>(x) + d; if (xx >= 0 && xx < static_cast<int>(gw)) m = std::max(m, grid[static_cast<size_t>(y) * gw + xx]); }
-                tmp[static_cast<size_t>(y) * gw + x] = m;
-            }
-        for (uint32_t y = 0; y < gh; ++y)
-            for (uint32_t x = 0; x < gw; ++x) {
-                uint16_t m = 0;
-                for (int d = -r; d <= r; ++d) { const int yy = static_cast<int>(y) + d; if (yy >= 0 && yy < static_cast<int>(gh)) m = std::max(m, tmp[static_cast<size_t>(yy) * gw + x]); }
-                grid[static_cast<size_t>(y) * gw + x] = m;
-            }
-        for (uint32_t item : geometric) item_cost[item] = grid[cell_of(item)];
-    }
-    // Tiles above the threshold are split into four 4x4 quarter tiles marched depth-parallel (raymarch_pq.h): their cost is
-    // a long chain of dependent samples, which four lanes per ray walk ~4x faster, on four waves.  Which tiles?  Those that
-    // would keep one wave busy for more than ~1.5x a wave's fair share of the frame (sum of costs / resident waves): below
-    // that they hide in the bulk and splitting only adds work.  A tile that is split stays split until its estimated cost
-    // falls below 0.7x the threshold (its cost is an estimate while it is split).
-    uint64_t total_cost = 0;
-    for (uint32_t item : geometric) total_cost += item_cost[item];
-    const uint32_t resident_waves = std::max(1u, job.max_grid * waves);
-    // Measured over four scenes (profiles/r03_dp_scene_sweep.txt: bonsai, teapot, a dense ball, thin vessels; 1080p, where the
-    // split matters -- at 3840x2160 every setting gives the same frame time): the common instantiation wants 1.7-1.9x (bonsai
-    // 33.9 us at 1.9x against 34.3 with r02's rule, teapot 44.9 against 51.9, ball 54.1 against 60.9; the vessels do not
-    // care); r02's 1.5x with an absolute floor of 104 units was the optimum of the bonsai alone and cost the other scenes
-    // 10-17 %.  The look-ahead instantiations keep 1.5x, the continuous-rho modes 1.2x (their classic loop speculates only
-    // two samples deep, a depth-parallel item four), as measured in r01 / r02.  A list dealt for a moving camera is read on later
-    // views: there the lower threshold (more tiles split than the captured view needed) is the better one (turntable at 0.25
-    // degrees per frame: 53.4 us at 1.5x, 57.0 at 1.9x).
-    const uint64_t tenths = job.dp_min_cost < -1 ? static_cast<uint64_t>(-job.dp_min_cost) : (job.continuous ? 12u : (job.plain && !moving) ? 19u : 15u);
-    const uint64_t floor_cost = job.dp_floor;                                   // 64 units: a tile below that is never worth four waves
-    const uint32_t adaptive = static_cast<uint32_t>(std::max<uint64_t>(floor_cost, tenths * total_cost / (10u * resident_waves) + 16));
-    const uint32_t dp_thr = job.dp_min_cost < 0 ? adaptive : static_cast<uint32_t>(job.dp_min_cost);
-#if VOLYM_DEV_SWITCHES
-    if (std::getenv("VOLYM_TRIM_LOG"))
-        std::fprintf(stderr, "deal: total cost %llu, fair share %llu, floor %llu, split threshold %u (moving %d measuring %d)\n", static_cast<unsigned long long>(total_cost),
-                     static_cast<unsigned long long>(total_cost / resident_waves), static_cast<unsigned long long>(floor_cost), dp_thr, moving ? 1 : 0, measuring ? 1 : 0);
-#endif
-    const bool dp_ok = job.dp_min_cost != 0 && !measuring;
-    std::vector<std::pair<uint32_t, uint32_t>> keyed;      // (cost share, entry)
-    keyed.reserve(geometric.size() * 2);
-    bool has_dp = false;
-    // 16x16 tiles whose four sub-tiles were all constant become one "super" fill item (bit 30)
-    std::vector<uint8_t> all_fill(n_local, 1), seen(n_local, 0), cnt(n_local, 0);
-    for (uint32_t item : geometric) { if (item_cost[item] != 0) all_fill[item >> 2] = 0; cnt[item >> 2]++; }
-    for (uint32_t lt = 0; lt < n_local; ++lt) if (cnt[lt] != 4) all_fill[lt] = 0;   // sub-tiles outside the frame are not listed
-    for (uint32_t item : geometric) {
-        const uint32_t k = item_cost[item];
-        if (job.super_fill && all_fill[item >> 2]) {
-            if (!seen[item >> 2]) { seen[item >> 2] = 1; keyed.emplace_back(0u, 0x40000000u | (item >> 2)); }
-            item_is_dp[item] = 0;
-            continue;
-        }
-        if (job.dev_drop_tenths && static_cast<uint64_t>(k) * 10u * resident_waves >= static_cast<uint64_t>(job.dev_drop_tenths) * total_cost) { item_is_dp[item] = 0; continue; }   // dev: what if the longest tiles were not there?
-        const bool split = dp_ok && (k >= dp_thr || (moving && item_is_dp[item] && job.dp_min_cost < 0 && 10u * k >= 7u * dp_thr));
-        has_dp = has_dp || split;
-        item_is_dp[item] = split ? 1 : 0;
-        if (split)
-            for (uint32_t qd = 0; qd < 4; ++qd) keyed.emplace_back((k * job.dp_share_pct + 99u) / 100u, 0x80000000u | (item << 2) | qd);
-        else
-            keyed.emplace_back(k, item);
-    }
-    {
-        // stable counting sort by decreasing cost share (shares are small integers): the feedback thread's latency is what
-        // a moving camera sees as the age of its list
-        uint32_t kmax = 0;
-        for (const auto& kv : keyed) kmax = std::max(kmax, kv.first);
-        std::vector<uint32_t> start(static_cast<size_t>(kmax) + 2u, 0);
-        for (const auto& kv : keyed) start[kmax - kv.first + 1u]++;
-        for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
-        std::vector<std::pair<uint32_t, uint32_t>> sorted(keyed.size());
-        for (const auto& kv : keyed) sorted[start[kmax - kv.first]++] = kv;
-        keyed.swap(sorted);
-    }
-    if (job.only_quarters) {     // dev experiment: how long do the depth-parallel items take with the machine to themselves?
-        std::vector<std::pair<uint32_t, uint32_t>> q;
-        for (const auto& kv : keyed) if (kv.second >> 31) q.push_back(kv);
-        keyed.swap(q);
-    }
-    // issue priority (bits 28-29) from the entry's cost relative to a wave's fair share of the frame
-    const uint64_t fair = std::max<uint64_t>(1, total_cost / resident_waves);
-    const bool prio_ok = job.prio_tenths[0] > 0 && static_cast<uint64_t>(n_local) * 16u < (1u << 28);
-    const uint32_t n_keyed = static_cast<uint32_t>(keyed.size());
-    const uint32_t G = std::max(1u, std::min((n_keyed + waves - 1) / waves, job.max_grid));
-    // Workgroup b reads entries b, b + G, ... of the list.  The entries, in order of decreasing cost, are dealt in
-    // boustrophedon order over the workgroups (0..G-1, G-1..0, ...): the sums differ by about one entry of the current size,
-    // as with a longest-processing-time heap, in one pass (the feedback thread's latency is the age of a moving camera's
-    // list).  Rounds are list rows: entry i sits in row i / G.
-    const size_t rows = (static_cast<size_t>(n_keyed) + G - 1) / G;
-    out.entries.assign(static_cast<size_t>(G) * rows, PQ_NO_ITEM);
-    out.shares.assign(static_cast<size_t>(G) * rows, 0);
-    for (uint32_t i = 0; i < n_keyed; ++i) {
-        const std::pair<uint32_t, uint32_t>& kv = keyed[i];
-        uint32_t prio = 0;
-        if (prio_ok && kv.first) {
-            const uint64_t k10 = static_cast<uint64_t>(kv.first) * 10u;
-            prio = k10 >= job.prio_tenths[2] * fair ? 3u : k10 >= job.prio_tenths[1] * fair ? 2u : k10 >= job.prio_tenths[0] * fair ? 1u : 0u;
-        }
-        const uint32_t row = i / G, j = i - row * G;
-        const size_t pos = static_cast<size_t>(row) * G + ((row & 1u) ? G - 1u - j : j);
-        out.entries[pos] = kv.second | (prio << 28);
-        out.shares[pos] = static_cast<uint16_t>(std::min(65535u, kv.first));
-    }
-    out.grid = G;
-    out.view_serial = job.view_serial;
-    out.has_dp = has_dp;
-    out.trimmable = !moving && !measuring;
-    out.trim_round = 0;
-    out.final_for_view = out.trimmable && job.trim_rounds == 0;
-}
-
-// Re-balance a standing view's list from the times its workgroups took (feedback thread).  The counted costs predict a
-// workgroup's time to within a few percent (profiles/r02_wave_trace.txt: end times spread over ~4 us of 33, and the spread
-// repeats from frame to frame); the frame ends with the LAST workgroup.  So: every workgroup's measured duration gives its
-// own rate (time per unit of cost, for the entries it holds); workgroups that ended after the mean hand entries worth
-// `damp` x their excess to a pool, and the pool goes, largest first, to whichever workgroup is predicted to end first.
-// Scheduling only: the pixels do not change.  Measured (scripts/trim_rounds.py, 1080p bonsai): 33.95 us without, 33.6-33.7 us
-// with 1..8 rounds -- the spread of the end times halves (28.0..34.1 -> 29.7..32.3 us) but their MEAN rises as it does: the
-// workgroups that used to finish early no longer leave the others a quieter machine.  In alternating 20 000-frame runs of two
-// builds the gain is 0.1 us (33.17 -> 33.07), and one run in six came out at 33.85: a list trimmed from a capture that caught a
-// hiccup is final, and wrong, for as long as the view stands.  A deterministic list is worth more than 0.3 %: OFF by default
-// (FbJob::trim_rounds = 0; VOLYM_OPT_REBALANCE_ROUNDS turns it on).
-static bool trim_list(const FrameSlot& s, const FbJob& job, const WorkList& in, const uint32_t* times, WorkList& out)
-{
-    const uint32_t G = in.grid, waves = job.waves;
-    if (G == 0 || G != job.grid || in.entries.size() % G != 0 || in.shares.size() != in.entries.size()) return false;
-    const size_t rows = in.entries.size() / G;
-    const uint32_t* starts = times + static_cast<size_t>(G) * waves;
-    const uint32_t ref = starts[0];
-    int32_t t0 = 0;
-    for (uint32_t b = 0; b < G; ++b) t0 = std::min(t0, static_cast<int32_t>(starts[b] - ref));
-    struct Ent { uint32_t w, code; };
-    std::vector<std::vector<Ent>> wg(G);
-    std::vector<double> dur(G), weight(G, 0.0), rate(G), pred(G);
-    double mean = 0.0;
-    for (uint32_t b = 0; b < G; ++b) {
-        int32_t end = 0;
-        for (uint32_t w = 0; w < waves; ++w) end = std::max(end, static_cast<int32_t>(times[static_cast<size_t>(b) * waves + w] - ref));
-        dur[b] = std::max(1.0, static_cast<double>(end - t0));
-        wg[b].reserve(rows + 8);
-        for (size_t r = 0; r < rows; ++r) {
-            const size_t pos = r * G + b;
-            if (in.entries[pos] == PQ_NO_ITEM) continue;
-            wg[b].push_back(Ent{in.shares[pos] + 1u, in.entries[pos]});
-            weight[b] += in.shares[pos] + 1u;
-        }
-        mean += dur[b];
-    }
-    mean /= G;
-    if (mean > 1.0e6) return false;                        // a second: not a frame's times (counter wrap, garbage)
-    const double damp = 0.8;
-    std::vector<Ent> pool;
-    for (uint32_t b = 0; b < G; ++b) {
-        rate[b] = dur[b] / std::max(1.0, weight[b]);
-        pred[b] = dur[b];
-        double excess = damp * (dur[b] - mean);
-        if (excess <= 0.0) continue;
-        // largest entries that fit first (the list of a workgroup is in order of decreasing share); constant tiles stay
-        std::vector<Ent> keep;
-        keep.reserve(wg[b].size());
-        for (const Ent& e : wg[b]) {
-            const double t = e.w * rate[b];
-            if (e.w > 1u && t <= excess) { pool.push_back(e); excess -= t; pred[b] -= t; }
-            else keep.push_back(e);
-        }
-        wg[b].swap(keep);
-    }
-    std::stable_sort(pool.begin(), pool.end(), [](const Ent& a, const Ent& b) { return a.w > b.w; });
-    for (const Ent& e : pool) {
-        uint32_t best = 0;
-        double best_t = 1.0e300;
-        for (uint32_t b = 0; b < G; ++b) { const double t = pred[b] + e.w * rate[b]; if (t < best_t) { best_t = t; best = b; } }
-        pred[best] = best_t;
-        wg[best].push_back(e);
-    }
-#if VOLYM_DEV_SWITCHES
-    if (std::getenv("VOLYM_TRIM_LOG")) {
-        double mx = 0, mn = 1e300, pmx = 0, pmn = 1e300;
-        for (uint32_t b = 0; b < G; ++b) { mx = std::max(mx, dur[b]); mn = std::min(mn, dur[b]); pmx = std::max(pmx, pred[b]); pmn = std::min(pmn, pred[b]); }
-        std::fprintf(stderr, "trim round %u: workgroup durations min %.2f mean %.2f max %.2f us; %zu entries moved; predicted min %.2f max %.2f\n", in.trim_round + 1, mn / 100, mean / 100,
-                     mx / 100, pool.size(), pmn / 100, pmx / 100);
-        double xs[8] = {}, xw[8] = {}; uint32_t xn[8] = {};
-        for (uint32_t b = 0; b < G; ++b) { xs[b & 7u] += dur[b]; xw[b & 7u] += weight[b]; xn[b & 7u]++; }
-        std::fprintf(stderr, "   by XCD (workgroup %% 8): mean duration");
-        for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %.2f", xs[k] / std::max(1u, xn[k]) / 100);
-        std::fprintf(stderr, " ; mean weight");
-        for (int k = 0; k < 8; ++k) std::fprintf(stderr, " %.0f", xw[k] / std::max(1u, xn[k]));
-        std::fprintf(stderr, "\n");
-    }
-#endif
-    size_t rows_out = 0;
-    for (uint32_t b = 0; b < G; ++b) {
-        std::stable_sort(wg[b].begin(), wg[b].end(), [](const Ent& a, const Ent& b2) { return a.w > b2.w; });
-        rows_out = std::max(rows_out, wg[b].size());
-    }
-    if (static_cast<size_t>(G) * rows_out > s.list_capacity) return false;
-    out.entries.assign(static_cast<size_t>(G) * rows_out, PQ_NO_ITEM);
-    out.shares.assign(static_cast<size_t>(G) * rows_out, 0);
-    for (uint32_t b = 0; b < G; ++b)
-        for (size_t r = 0; r < wg[b].size(); ++r) {
-            out.entries[r * G + b] = wg[b][r].code;
-            out.shares[r * G + b] = static_cast<uint16_t>(wg[b][r].w - 1u);
-        }
-    out.grid = G;
-    out.view_serial = in.view_serial;
-    out.has_dp = in.has_dp;
-    out.trimmable = true;
-    out.trim_round = in.trim_round + 1;
-    out.final_for_view = out.trim_round >= job.trim_rounds;
-    return true;
-}
-
-// device form of a list: {entry, x | y << 16 of the entry's 16x16 tile} (the kernel does no integer division)
-static void list_to_device_form(const volym_ctx* c, const std::vector<uint32_t>& entries, uint32_t* out)
-{
-    for (size_t i = 0; i < entries.size(); ++i) {
-        const uint32_t raw_p = entries[i];
-        uint32_t xy = 0;
-        if (raw_p != PQ_NO_ITEM) {
-            const uint32_t raw = raw_p & ~0x30000000u;
-            const uint32_t lt = (raw >> 31) ? ((raw & 0x7fffffffu) >> 4) : ((raw >> 30) == 1u ? (raw & 0x3fffffffu) : (raw >> 2));
-            const uint32_t tile = lt * c->world + c->rank;
-            xy = (tile % c->tiles_x) | ((tile / c->tiles_x) << 16);
-        }
-        out[2 * i] = raw_p;
-        out[2 * i + 1] = xy;
-    }
-}
-
-// costs by list position -> costs by item
-static void costs_to_items(const WorkList& list, const uint16_t* cost, uint32_t n_entries, std::vector<uint16_t>& item_cost)
-{
-    std::vector<uint32_t> q_max(item_cost.size(), 0);
-    std::vector<uint8_t> q_seen(item_cost.size(), 0);
-    for (uint32_t p = 0; p < n_entries && p < list.entries.size(); ++p) {
-        const uint32_t raw_p = list.entries[p];
-        if (raw_p == PQ_NO_ITEM) continue;
-        const uint32_t raw = raw_p & ~0x30000000u;
-        const uint32_t k = cost[p];
-        if (raw >> 31) {                                   // depth-parallel quarter: the tile's cost is 5 + the slowest quarter
-            const uint32_t item = (raw & 0x7fffffffu) >> 2;
-            if (item < item_cost.size()) { q_max[item] = std::max(q_max[item], k); q_seen[item] = 1; }
-        } else if ((raw >> 30) == 1u) {                    // super fill: zero, or the sum of four marched sub-tiles
-            const uint32_t lt = raw & 0x3fffffffu;
-            for (uint32_t sub = 0; sub < 4; ++sub)
-                if (lt * 4u + sub < item_cost.size()) item_cost[lt * 4u + sub] = static_cast<uint16_t>(k == 0 ? 0u : std::max(1u, k / 4u));
-        } else if (raw < item_cost.size()) {
-            item_cost[raw] = static_cast<uint16_t>(k);
-        }
-    }
-    for (size_t i = 0; i < item_cost.size(); ++i)
-        if (q_seen[i]) item_cost[i] = static_cast<uint16_t>(std::min(65535u, 5u + q_max[i]));
-}
 
 static void feedback_thread(const volym_ctx* c, FrameSlot* sp)
 {
@@ -570,23 +261,24 @@ static void feedback_thread(const volym_ctx* c, FrameSlot* sp)
         const int next = job.list ^ 1;
         if (e == hipSuccess) {
             // A list dealt for this very view from whole-entry costs is not dealt again (its split tiles report estimates): it is
-            // re-balanced from the workgroups' measured times, job.trim_rounds times.
+            // re-balanced from the workgroups' measured times, job.set.trim_rounds times.
             const WorkList& ran = s.lists[job.list];
-            const bool same_view = s.view_serial.load(std::memory_order_relaxed) == job.view_serial && ran.view_serial == job.view_serial;
+            const bool same_view = s.view_serial.load(std::memory_order_relaxed) == job.launch.view_serial && ran.view_serial == job.launch.view_serial;
             bool trimmed = false;
-            if (same_view && ran.trimmable && ran.trim_round < job.trim_rounds)
-                trimmed = trim_list(s, job, ran, reinterpret_cast<const uint32_t*>(s.h_cost_pinned + ((job.n_entries + 1u) & ~1u)), s.lists[next]);
+            if (same_view && ran.trimmable && ran.trim_round < job.set.trim_rounds)
+                trimmed = trim_list(job.set, job.launch, s.list_capacity, ran, reinterpret_cast<const uint32_t*>(s.h_cost_pinned + ((job.n_entries + 1u) & ~1u)), s.lists[next]);
             job.t_us[3] = now_us();
             if (!trimmed) {
                 costs_to_items(ran, s.h_cost_pinned, job.n_entries, s.item_cost);
                 job.t_us[3] = now_us();
-                deal_list(c, s, job, s.item_cost, s.item_is_dp, c->geometric, c->n_local, s.lists[next]);
+                const bool moving = s.view_serial.load(std::memory_order_relaxed) != job.launch.view_serial;    // (a second load: has it moved by now?)
+                deal_list(shard_grid(c), job.set, job.launch, moving, s.item_cost, s.item_is_dp, c->geometric, s.lists[next]);
             }
             job.t_us[4] = now_us();
             if (s.lists[next].entries.size() > s.list_capacity) {
                 job.error = "work list larger than its buffers";    // cannot happen: capacity is the worst case
             } else {
-                list_to_device_form(c, s.lists[next].entries, s.h_list_pinned);
+                list_to_device_form(shard_grid(c), s.lists[next].entries, s.h_list_pinned);
                 // every launch that read d_list[next] finished before the captured launch did (same stream, in order)
                 e = hipMemcpyAsync(s.d_list[next], s.h_list_pinned, s.lists[next].entries.size() * 2u * sizeof(uint32_t), hipMemcpyHostToDevice, s.copy_stream);
                 if (e == hipSuccess) e = hipEventRecord(s.ev_list, s.copy_stream);
@@ -664,7 +356,7 @@ static int reset_slot_lists(volym_ctx* c, FrameSlot& s)
     s.lists[0].entries = c->geometric;
     s.lists[1] = WorkList();
     if (!c->geometric.empty()) {
-        list_to_device_form(c, c->geometric, s.h_list_pinned);
+        list_to_device_form(shard_grid(c), c->geometric, s.h_list_pinned);
         HIPCHK(c, hipMemcpy(s.d_list[0], s.h_list_pinned, c->geometric.size() * 2u * sizeof(uint32_t), hipMemcpyHostToDevice));
     }
     return VOLYM_OK;
@@ -676,7 +368,7 @@ int volym::rebuild_lists(volym_ctx* c)
 {
     int rc = quiesce_slots(c);
     if (rc != VOLYM_OK) return rc;
-    build_geometric(c);
+    c->geometric = build_geometric(shard_grid(c));
     for (int i = 0; i < c->n_slots() && rc == VOLYM_OK; ++i) rc = reset_slot_lists(c, *c->slots[i]);
     return rc;
 }
@@ -824,7 +516,7 @@ int volym_create(volym_ctx** out, uint32_t width, uint32_t height, int device_id
     const uint64_t tiles8 = static_cast<uint64_t>(c->tiles_x) * 2u * c->tiles_y * 2u;
     const uint64_t words = (tiles8 + 31u) / 32u;
     c->tile_mask_words = words <= VOLYM_TILE_MASK_MAX_WORDS ? static_cast<uint32_t>(words) : 0u;
-    build_geometric(c);
+    c->geometric = build_geometric(shard_grid(c));
 
     c->slots[0].reset(new (std::nothrow) FrameSlot());
     const int rc = c->slots[0] ? init_slot(c, c->slot0()) : fail(c, VOLYM_E_NOMEM, "out of host memory");
@@ -933,11 +625,11 @@ int volym_set_option(volym_ctx* c, int key, int value)
         return rebuild_lists(c);
     case VOLYM_OPT_DEPTH_PARALLEL:
         if (value < -100 || value > 65535) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_DEPTH_PARALLEL: < 0 adaptive (-N = N/10 x fair share), 0 off, else explicit cost");
-        c->dp_min_cost = value;
+        c->list_settings.dp_min_cost = value;
         return rebuild_lists(c);
     case VOLYM_OPT_REBALANCE_ROUNDS:   // 0: the dealt list is final
         if (value < 0 || value > 8) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_REBALANCE_ROUNDS: 0..8");
-        c->trim_rounds = static_cast<uint32_t>(value);
+        c->list_settings.trim_rounds = static_cast<uint32_t>(value);
         return VOLYM_OK;
     case VOLYM_OPT_SETUP_IEEE:
         if (value != 0 && value != 1) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_SETUP_IEEE: 0 or 1");
@@ -954,16 +646,16 @@ int volym_set_option(volym_ctx* c, int key, int value)
         c->wgs_per_cu = static_cast<uint32_t>(value);
         return rebuild_lists(c);
     case 107:   // 0 disables the 16x16 super fill items
-        c->super_fill = value != 0;
+        c->list_settings.super_fill = value != 0;
         return rebuild_lists(c);
     case 108:   // issue-priority thresholds t1 + 100*t2 + 10000*t3 in tenths of the fair share (0 = no priorities)
         if (value < 0) return fail(c, VOLYM_E_INVALID, "priority thresholds: t1 + 100*t2 + 10000*t3, tenths of the fair share");
-        c->prio_tenths[0] = static_cast<uint32_t>(value % 100);
-        c->prio_tenths[1] = static_cast<uint32_t>((value / 100) % 100);
-        c->prio_tenths[2] = static_cast<uint32_t>(value / 10000);
+        c->list_settings.prio_tenths[0] = static_cast<uint32_t>(value % 100);
+        c->list_settings.prio_tenths[1] = static_cast<uint32_t>((value / 100) % 100);
+        c->list_settings.prio_tenths[2] = static_cast<uint32_t>(value / 10000);
         return rebuild_lists(c);
     case 109:   // keep only the depth-parallel items in the work list (the frame is then incomplete)
-        c->dev_only_quarters = value != 0;
+        c->list_settings.only_quarters = value != 0;
         return rebuild_lists(c);
     case 110:   // FrameParams::dev
         for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->fp.dev = static_cast<uint32_t>(value);
@@ -973,17 +665,17 @@ int volym_set_option(volym_ctx* c, int key, int value)
         c->feedback_frozen = value != 0;
         return VOLYM_OK;
     case 114:   // dilation radius (in 8x8 items) of the cost map when a list is dealt
-        c->cost_dilate = std::max(-1, std::min(value, 4));
+        c->list_settings.dilate = std::max(-1, std::min(value, 4));
         return VOLYM_OK;
     case 115:   // waves per workgroup of the instantiations that need more than 128 VGPRs: 0 default, 12 or 16
         if (value != 0 && value != 12 && value != 16) return fail(c, VOLYM_E_INVALID, "wide waves: 0, 12 or 16");
         c->wide_waves = value;
         return rebuild_lists(c);
     case 119:   // floor of the adaptive split threshold (cost units)
-        c->dp_floor = static_cast<uint32_t>(std::max(value, 1));
+        c->list_settings.dp_floor = static_cast<uint32_t>(std::max(value, 1));
         return rebuild_lists(c);
     case 118:   // drop the tiles of >= value/10 x the fair share from the lists (the frame is then incomplete): how much do they cost?
-        c->dev_drop_tenths = static_cast<uint32_t>(std::max(value, 0));
+        c->list_settings.dev_drop_tenths = static_cast<uint32_t>(std::max(value, 0));
         return rebuild_lists(c);
     case 121:   // 1: the straight look-ahead as jobs shared by the workgroup (raymarch_pq.h CJ = 2)
         c->straight_jobs = value != 0;
@@ -1000,9 +692,8 @@ int volym_set_option(volym_ctx* c, int key, int value)
         c->mask_eager = value == 2;
         for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->hull_dirty = true;
         return rebuild_lists(c);
-    case 111:   // balancing estimates, dp_share_pct + 1000 * fill_cost
-        c->dp_share_pct = static_cast<uint32_t>(value % 1000);
-        c->fill_cost = static_cast<uint32_t>(value / 1000);
+    case 111:   // cost share of a depth-parallel quarter, percent of its tile's cost: value % 1000 (scripts still pass a combined value whose thousands nothing reads)
+        c->list_settings.dp_share_pct = static_cast<uint32_t>(value % 1000);
         return rebuild_lists(c);
 #endif
     default:
@@ -1331,24 +1022,15 @@ static int launch_march(volym_ctx* c, FrameSlot& s)
             FbJob& job = s.fb_job;
             job.list = s.cur;
             job.n_entries = n_items;
-            job.view_serial = s.view_serial.load(std::memory_order_relaxed);
-            job.captured_has_dp = wl.has_dp;
-            job.continuous = (fp.flags & (F_LINEAR | F_GAUSSIAN)) != 0u;
-            job.plain = table && no_imp;                  // the common instantiation: the split threshold's floor was measured for it
-            job.max_grid = max_grid(c);
-            job.waves = waves;
-            job.dp_min_cost = c->dp_min_cost;
-            job.dp_share_pct = c->dp_share_pct;
-            job.fill_cost = c->fill_cost;
-            job.super_fill = c->super_fill;
-            job.only_quarters = c->dev_only_quarters;
-            job.dilate = c->cost_dilate;
-            job.grid = pgrid;
-            job.dev_drop_tenths = c->dev_drop_tenths;
-            job.dp_floor = c->dp_floor;
-            job.trim_rounds = c->trim_rounds;
+            job.launch.view_serial = s.view_serial.load(std::memory_order_relaxed);
+            job.launch.captured_has_dp = wl.has_dp;
+            job.launch.continuous = (fp.flags & (F_LINEAR | F_GAUSSIAN)) != 0u;
+            job.launch.plain = table && no_imp;           // the common instantiation: the split threshold's floor was measured for it
+            job.launch.max_grid = max_grid(c);
+            job.launch.waves = waves;
+            job.launch.grid = pgrid;
+            job.set = c->list_settings;
             job.t_us[0] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
-            for (int i = 0; i < 3; ++i) job.prio_tenths[i] = c->prio_tenths[i];
             {
                 std::lock_guard<std::mutex> lk(s.fb_mu);
                 s.fb_state.store(FrameSlot::FB_CAPTURED, std::memory_order_release);

@@ -25,8 +25,8 @@
 // in LDS: dynamic balance inside the workgroup, no global atomics, nothing to reset between launches.  The first frame of
 // a context runs the host's centre-first list (the orbit camera targets the volume centre, src/camera.rs:23); a launch can be
 // asked to record a counted cost per list entry, from which a feedback thread on the host deals the next list (raymarch.hip,
-// "cost feedback"): most expensive entries first, the most expensive tiles as depth-parallel quarter items (bit 31),
-// constant 16x16 tiles as super fill items (bit 30).  Entries are {item code, x | y << 16 of the entry's 16x16 tile}.
+// "cost feedback"; the policy is worklist.hpp): most expensive entries first, the most expensive tiles as depth-parallel quarter
+// items, constant 16x16 tiles as super fill items.  Entries are {item code (worklist_entry.h), x | y << 16 of the entry's 16x16 tile}.
 //
 // Item kinds and their loops (all bit-identical to the sequential march):
 //   * 8x8 tile, one lane per ray, K speculative samples per iteration ("classic");
@@ -51,6 +51,7 @@
 #include <type_traits>
 
 #include "raymarch_device.h"
+#include "worklist_entry.h"
 
 namespace volym {
 
@@ -58,7 +59,6 @@ constexpr int PQ_WAVES = 16;             // waves per workgroup of the common in
 constexpr int PQ_WAVES_WIDE = 12;        // ... of the instantiations that need more than 128 VGPRs
 constexpr uint32_t PQ_MIN_LEAP_D = 2;    // smallest distance-field value worth a leap
 constexpr int PQ_DP_DEPTH = 2;           // depth-parallel items: samples per lane and iteration (4 lanes per ray)
-constexpr uint32_t PQ_NO_ITEM = 0xffffffffu;   // padding of the work list
 constexpr int PQ_ITEMS_LDS = 512;       // work-list entries staged in LDS per workgroup (the rest stay in global memory)
 // ring entries per wave: < 64 left over from the last iteration + 64 per speculative sample of this one.  One workgroup
 // per CU owns the whole 160 KB of LDS, so the queue is sized for the shading to run at ONE point of the loop.
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         for (uint32_t wrd = blockIdx.x * (WAVES * 64u) + threadIdx.x; wrd < fp.mask_words; wrd += gridDim.x * (WAVES * 64u)) fp.tile_mask_spare[wrd] = 0u;
     if (VOLYM_DEV_SWITCHES && (fp.dev & 16u)) return;                    // launch + dispatch only
     // A launch whose costs are captured also reports when it ran: behind the costs, the end time of every wave and the start
-    // time of every workgroup (100 MHz counter).  The host evens out what the counted costs mispredict (raymarch.hip, trim_list).
+    // time of every workgroup (100 MHz counter).  The host evens out what the counted costs mispredict (worklist.cpp, trim_list).
     uint32_t* const wg_time = reinterpret_cast<uint32_t*>(cost + ((n_items + 1u) & ~1u));
     if (cost && threadIdx.x == 0u) wg_time[gridDim.x * WAVES + blockIdx.x] = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
     {
@@ -477,9 +477,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
       // loops read in every iteration (thr_byte, the steps, mc_n) stays in the argument's registers.
       const FrameParams& fe = RELOAD ? frame_params_here<PQ_FP_KERNARG_OFFSET>() : fp;
       {
-        // item = local_tile*4 + sub (an 8x8 wave tile, one lane per ray), or, for tiles the cost feedback
-        // found expensive, bit 31 | (that id << 2) | quarter: a 4x4 quarter tile marched DEPTH-PARALLEL,
-        // four lanes per ray, lane k of a quad taking the k-th speculative sample (see "dp" below)
+        // (the entry's code: worklist_entry.h)
         const size_t list_pos = blockIdx.x + static_cast<size_t>(gridDim.x) * ticket;     // this entry's place in the work list
         const uint2 entry = ticket < static_cast<uint32_t>(ITEMS_LDS) ? s_items[ticket] : order[list_pos];
         const uint32_t raw_p = __builtin_amdgcn_readfirstlane(entry.x);
@@ -490,22 +488,17 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         // counted cost of this list entry, reported by list position (one writer per entry: no atomics, nothing to reset); the
         // host's feedback thread maps positions back to tiles (raymarch.hip, "cost feedback")
         uint32_t entry_cost = 0;
-        // bits 28-29: issue priority the host derived from the measured cost.  The frame ends with its longest chains of
-        // dependent samples; a wave that carries one gets the SIMD's issue slots first, the cheap items fill the gaps.
-        switch ((raw_p >> 28) & 3u) {
+        switch (wl_prio(raw_p)) {
             case 0: __builtin_amdgcn_s_setprio(0); break;
             case 1: __builtin_amdgcn_s_setprio(1); break;
             case 2: __builtin_amdgcn_s_setprio(2); break;
             default: __builtin_amdgcn_s_setprio(3); break;
         }
-        const uint32_t raw0 = raw_p & ~0x30000000u;
-        // bit 30 (bit 31 clear): a whole 16x16 tile that was constant in the frame the costs were measured on.  One
-        // classification of the 16x16 rectangle and, if it still says "constant", 16-byte stores; otherwise its four
-        // sub-tiles are processed here one after the other.
-        const bool is_super = (raw0 >> 30) == 1u;
+        const uint32_t raw0 = wl_code(raw_p);
+        const bool is_super = wl_is_super(raw0);
         uint32_t n_sub = 1;
         if (is_super) {
-            const uint32_t lt = raw0 & 0x3fffffffu;
+            const uint32_t lt = wl_super_tile(raw0);
             const uint32_t tx16 = tx, ty16 = ty;
             bool masked16 = false;
             if (culling && (fe.cull & CULL_TILE_MASK))
@@ -540,11 +533,11 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             n_sub = 4;
         }
       for (uint32_t sub_iter = 0; sub_iter < n_sub; ++sub_iter) {
-        const uint32_t raw = is_super ? ((raw0 & 0x3fffffffu) * 4u + sub_iter) : raw0;
-        const bool is_quarter = (raw >> 31) != 0u;
+        const uint32_t raw = is_super ? (wl_super_tile(raw0) * 4u + sub_iter) : raw0;
+        const bool is_quarter = wl_is_quarter(raw);
         const bool dp = is_quarter && !COUNT;
-        const uint32_t item = is_quarter ? ((raw & 0x7fffffffu) >> 2) : raw;
-        const uint32_t quarter = raw & 3u;
+        const uint32_t item = is_quarter ? wl_quarter_item(raw) : raw;
+        const uint32_t quarter = wl_quarter_index(raw);
         if (is_quarter && !dp && quarter != 0u) continue;   // instrumented launch: quarter 0 stands for the whole tile
         const uint32_t local_tile = item >> 2, sub = item & 3u;
         const uint32_t px_in_sub = dp ? (((quarter & 1u) << 2) + ((lane >> 2) & 3u)) : (lane & 7u);
