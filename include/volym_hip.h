@@ -365,6 +365,52 @@ void* volym_pick_device_ptr(volym_ctx* ctx);
 /* A pick pass over the one pixel (x, y) plus the read.  Blocks. */
 int volym_pick(volym_ctx* ctx, uint32_t x, uint32_t y, float alpha_min, struct volym_pick* out);
 
+/* --- outline (new; the reference has none) ---------------------------------------------------------------------------- */
+/* Ring and tint of the selected segments, in screen space, from pick records that are already there: no march.  It reads the
+ * frame of the latest volym_compute_pass, a set of pick records and a selection, and writes an annotated W x H rgba8 image; it
+ * never changes the scene or the records, nor the frame unless the frame is the target.  While the view stands the records of
+ * one whole-frame pick pass stay valid, and hovering over another segment changes only `selected`.
+ *   The rule (integers only; scene.outline_frame of the Python package is its host twin, equal in every byte).  rect =
+ * {x0, y0, w, h} is the part of the frame the records cover, row-major within it.  A pixel of the frame is SELECTED when it lies
+ * inside rect, its record has status == 2 and selected[record.label] != 0; nothing else is (not a pixel outside rect, not a
+ * record of status 0 or 1 whose label byte happens to be selected).  has_labels == 0 records carry label 0, so selected[0] then
+ * selects every picked pixel.  A pixel is on the RING when it is not selected and some selected pixel q of the frame has
+ * max(|px - qx|, |py - qy|) <= radius; pixels beyond the frame do not exist, and a ring pixel may lie outside rect.  With src
+ * the frame's texel, ring pixels take col = ring_rgba, selected pixels col = fill_rgba, every other pixel copies src; with
+ * A = col[3]:  out[c] = (src[c] * (255 - A) + col[c] * A + 127) / 255 for r, g, b and out[3] = (src[3] * (255 - A) + 255 * A +
+ * 127) / 255, integer division.  A = 0 is the identity; A = 255 replaces rgb and makes alpha 255. */
+typedef struct volym_outline {
+    uint8_t  selected[256];     /* per label value: != 0 selects it */
+    uint8_t  ring_rgba[4];
+    uint8_t  fill_rgba[4];
+    uint32_t radius;            /* 1..8 */
+} volym_outline;                /* 268 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_outline) == 268, "volym_outline is 268 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_outline) == 268, "volym_outline is 268 bytes");
+#endif
+/* Enqueue only: two kernels (records -> a bit plane of the selected pixels; ring and blend) behind the frame and the pick pass.
+ *   records_device == NULL and rect == NULL: the records and the rect of the latest volym_pick_pass (VOLYM_E_STATE before any).
+ * Otherwise records_device is device memory holding rect[2] * rect[3] records and rect is required; one without the other is
+ * VOLYM_E_INVALID.  The records are not checked for staleness: records of an older view or scene outline that older view.
+ *   target_rgba8 == NULL: a W x H target the context owns (volym_read_outline, volym_outline_device_ptr).  Otherwise caller
+ * device memory of W * H * 4 bytes; it may be the frame buffer itself (a pixel reads only its own frame texel), and the frame
+ * then holds the annotated image.
+ *   VOLYM_E_INVALID: NULL ctx, NULL o, radius outside 1..8, a rect that is empty or not inside the frame.  VOLYM_E_STATE: before
+ * any volym_compute_pass, and on a sharded context (world > 1): its frame buffer holds a picture only on the root after
+ * assembly, and the native multi-GPU loop has no forward for this call.
+ *   No allocation and no synchronisation, except on first use: the first pass of a context allocates the bit plane (about 1 MB
+ * at 3840 x 2160), the first pass into the context's own target that target; that is the one blocking path, as with volym_blit.
+ *   Streams: the pass goes on the first slot's stream, where the pick passes go (a caller's stream when one is set).  With
+ * VOLYM_OPT_FRAMES_IN_FLIGHT = 2 events order it, without a host wait: it starts behind the frame it reads and behind the pick
+ * pass, and neither a later compute pass into that frame buffer nor a later pick pass into those records starts before it ends. */
+int   volym_outline_pass(volym_ctx* ctx, const volym_outline* o, const void* records_device, const uint32_t rect[4], void* target_rgba8);
+/* Blocks; W * H * 4 bytes of the context's own target.  VOLYM_E_STATE before any pass into it. */
+int   volym_read_outline(volym_ctx* ctx, uint8_t* out);
+/* The context's own target after the latest pass into it, NULL before any. */
+void* volym_outline_device_ptr(volym_ctx* ctx);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

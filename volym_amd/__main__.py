@@ -11,7 +11,8 @@ HIP events.  The reference's teapot .raw files are not distributed (.MISSING_LAR
 
 run simple: renders the interactive default view (src/state.rs:41-55) once and writes screenshot_<unix time>.png
 like the reference's `P` key (src/state.rs:85-113).  --pick X,Y[,ALPHA] then prints what that pixel shows (segment, texel,
-depth) as one JSON line.
+depth) as one JSON line.  --outline NAME[,NAME...] (segment names, ids or label values) and --outline-at X,Y (the segment under that
+pixel) write the annotated image instead: a ring round the segments and a tint over them (demo.Simple.highlight).
 """
 import argparse
 import csv
@@ -149,6 +150,25 @@ def _pick_arg(text):
     return x, y, alpha
 
 
+def _outline_arg(text):
+    """--outline Canopy,3 (names or ids of the segments JSON, or label values) -> ["Canopy", 3]"""
+    v = [t.strip() for t in text.split(",") if t.strip() != ""]
+    if not v:
+        raise SystemExit("--outline: segment names, ids or label values, comma separated")
+    return [int(t) if t.isdigit() else t for t in v]
+
+
+def _outline_at_arg(text):
+    """--outline-at X,Y (pixel of the frame) -> (x, y)"""
+    try:
+        x, y = (int(t) for t in text.split(","))
+    except ValueError:
+        raise SystemExit("--outline-at: X,Y -- a pixel of the frame")
+    if x < 0 or y < 0:
+        raise SystemExit("--outline-at: X,Y -- a pixel of the frame")
+    return x, y
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -165,12 +185,25 @@ def run_simple(args):
         ctx.sync()
         frame = ctx.read_rgba8()
         picked = d.pick(ctx, *_pick_arg(args.pick)) if getattr(args, "pick", None) else None
+        outlined = None
+        try:
+            if getattr(args, "outline", None):
+                outlined = {"outlined_labels": d.highlight(ctx, _outline_arg(args.outline))}
+            if getattr(args, "outline_at", None):
+                outlined = d.highlight_at(ctx, *_outline_at_arg(args.outline_at))
+        except ValueError as e:
+            raise SystemExit("--outline: %s" % e)
+        if outlined is not None:
+            frame = ctx.read_outline()      # the PNG is the annotated image
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
     if picked is not None:
         import json
         print(json.dumps(picked))      # one line: what the pixel shows (demo.Simple.pick)
+    if outlined is not None:
+        import json
+        print(json.dumps(outlined))    # one line: the label values outlined, or the pick under --outline-at
     return 0
 
 
@@ -264,6 +297,8 @@ def main(argv=None):
     run.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
     run.add_argument("--hide", help="label values of the segments to hide, e.g. 3,4")
     run.add_argument("--pick", help="X,Y[,ALPHA]: after the frame, print what pixel (X, Y) shows as one JSON line (segment, texel, depth)")
+    run.add_argument("--outline", help="NAME[,NAME...]: segment names, ids or label values to outline and tint; the PNG is the annotated image")
+    run.add_argument("--outline-at", help="X,Y: outline the segment pixel (X, Y) shows; the PNG is the annotated image")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359
     b.add_argument("--secs", type=float, default=0.25, help="GPU seconds per trial (the reference uses 2 s of wall clock)")

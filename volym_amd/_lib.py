@@ -72,6 +72,16 @@ PICK_DTYPE = np.dtype([("t", "<f4"), ("x", "<u2"), ("y", "<u2"), ("z", "<u2"), (
 PICK_MISS, PICK_NONE, PICK_HIT = 0, 1, 2      # volym_pick.status
 
 
+class Outline(C.Structure):
+    """volym_outline (include/volym_hip.h): selection, colours and radius of one outline pass, 268 bytes"""
+    _fields_ = [
+        ("selected", C.c_uint8 * 256),
+        ("ring_rgba", C.c_uint8 * 4),
+        ("fill_rgba", C.c_uint8 * 4),
+        ("radius", C.c_uint32),
+    ]
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -180,6 +190,9 @@ SIGNATURES = {
     "volym_read_picks": (C.c_int, [_ctx, C.POINTER(Pick)]),
     "volym_pick_device_ptr": (C.c_void_p, [_ctx]),
     "volym_pick": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(Pick)]),
+    "volym_outline_pass": (C.c_int, [_ctx, C.POINTER(Outline), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "volym_read_outline": (C.c_int, [_ctx, _u8p]),
+    "volym_outline_device_ptr": (C.c_void_p, [_ctx]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI; pick.hip: the pick march).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI; pick.hip: the pick march; outline.hip: the outline pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -174,6 +174,15 @@ struct volym_ctx {
     volym_pick_record* d_picks = nullptr;
     size_t pick_capacity = 0;                // records d_picks holds
     uint32_t pick_w = 0, pick_h = 0;         // rect size of the latest pass (0: none yet)
+    uint32_t pick_x0 = 0, pick_y0 = 0;       // ... and its origin in the frame (the outline pass places the records by it)
+
+    // outline passes (volym_outline_pass, outline.hip): all allocated on first use, all used on slot 0's stream
+    uint64_t* d_outline_plane = nullptr;     // one bit per frame pixel plus zeroed guards (outline_kernels.h)
+    uint32_t outline_stride = 0;             // words per plane row
+    uint32_t* d_outline = nullptr;           // W x H target when the caller passes none
+    bool outline_own_valid = false;          // a pass has written d_outline
+    hipEvent_t outline_ev[2] = {};           // frame of the other slot -> pass, pass -> the other slot's next work
+    bool frame_rendered = false;             // some volym_compute_pass has been enqueued
 
     bool feedback = true;
     bool feedback_frozen = false;               // dev
@@ -223,6 +232,8 @@ void set_reject_box(const volym_ctx* c, FrameParams& fp);
 // pick.hip: one pick march of rect {x0, y0, w, h} (inside the frame, not empty) into `out` (w * h records), enqueued on the slot's
 // stream with the slot's frame parameters, tables and -- when it is the one of the current threshold and scene -- distance field
 int launch_pick(volym_ctx* c, FrameSlot& s, const uint32_t rect[4], float alpha_min, void* out);
+// outline.hip: what the context keeps for the outline pass (every stream idle)
+void free_outline(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 

@@ -56,6 +56,15 @@ struct SimpleAssets {
     int filter = VOLYM_FILTER_NEAREST;           // src/gpu_resources/volume.rs:92-95
 };
 
+// How Simple::highlight draws: colours, ring width, the alpha_min of the pick pass behind it, and where the image goes.
+struct Highlight {
+    uint8_t ring_rgba[4] = {255, 255, 0, 255};
+    uint8_t fill_rgba[4] = {255, 255, 0, 48};
+    uint32_t radius = 2;                     // 1..8
+    float alpha_min = 0.5f;
+    void* target_rgba8 = nullptr;            // device memory of W * H * 4 bytes; NULL: the context's own target (volym_read_outline)
+};
+
 class Simple : public ComputeDemo {
 public:
     static Simple init(const GpuContext& ctx, const volym_state& state, const SimpleAssets& a)
@@ -82,6 +91,7 @@ public:
         if (!camera_uniforms_from(state.camera, cam)) throw Error(VOLYM_E_INVALID, "inverse_view_proj inversion failed");
         parameter_uniforms_from(state, par);
         ctx.check(volym_update(ctx.handle(), &cam, &par));
+        records_current_ = false;      // (highlight: the pick records of the old view are stale)
     }
     void compute_pass(const GpuContext& ctx) override { ctx.check(volym_compute_pass(ctx.handle())); }   // src/demos/pipeline.rs:62-102
 
@@ -92,6 +102,7 @@ public:
         prepare_volume(a.labels_raw.data(), a.labels_raw.size(), a.nx, a.ny, a.nz, true, labels.data());
         ctx.check(volym_set_labels(ctx.handle(), labels.data(), a.nx, a.ny, a.nz));
         labels_on_device_ = true;
+        records_current_ = false;
     }
     // The reference maps labels before padding them (importance.rs:148-158), so padding has importance 0 there and table[0]
     // here: with padding and table[0] != 0 this falls back to the host map (which drops the labels from the device).
@@ -99,6 +110,7 @@ public:
     {
         const std::vector<uint8_t> table = segment_table(segments);
         const size_t n = static_cast<size_t>(a.nx) * a.ny * a.nz;
+        records_current_ = false;
         if (a.labels_raw.size() < n && table[0] != 0) {
             std::vector<uint8_t> mapped(a.labels_raw), imp(n);
             std::vector<uint8_t> lv, im;
@@ -120,6 +132,7 @@ public:
         uint32_t lo[3], hi[3];
         for (int i = 0; i < 3; ++i) { lo[i] = crop_texel(lo01[i], n[i]); hi[i] = crop_texel(hi01[i], n[i]); }
         ctx.check(volym_set_crop_box(ctx.handle(), lo, hi));
+        records_current_ = false;
     }
     // New: hide the segments with the given label values and show all others (volym_set_segment_visibility).  The labels go to the
     // device first if they are not there yet; the importances stay what they were.
@@ -133,6 +146,7 @@ public:
             set_labels(ctx, a);
         }
         ctx.check(volym_set_segment_visibility(ctx.handle(), visible));
+        records_current_ = false;
     }
     // New: what pixel (x, y) of the frame shows -- the first sample of its ray after which alpha >= alpha_min (volym_pick): the
     // record, the name of the segment with its label (empty: none, or no labels) and the texel's centre in the unit-cube
@@ -147,13 +161,83 @@ public:
         if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
         Picked p{};
         ctx.check(volym_pick(ctx.handle(), x, y, alpha_min, &p.record));
+        records_current_ = false;      // (the one-pixel pass took the place of a whole frame's records)
+        describe(a, p);
+        return p;
+    }
+    // New: outline and tint segments in the frame of the latest compute pass (volym_outline_pass) -- one outline pass over the
+    // records of a whole-frame pick pass, which runs only if the demo has none for the current view and scene (update_gpu_state,
+    // set_crop, set_hidden, set_segments and set_labels make the records stale).  `segments`: names or ids of the segments table, or
+    // label values written as numbers ("3").  The image goes to target_rgba8 (device memory), or with NULL to the context's own
+    // target (volym_read_outline).  Returns the selected label values.
+    std::vector<uint8_t> highlight(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments, const Highlight& h = Highlight())
+    {
+        std::vector<uint8_t> values;
+        for (const std::string& s : segments) values.push_back(label_value_of(a, s));
+        highlight_labels(ctx, a, values, h);
+        return values;
+    }
+    // New: hover -- outline the segment pixel (x, y) shows (nothing when it shows no labelled sample: the image is then the frame).
+    // The label comes from the current records, which are read back once per view and scene: the hovers after the first cost the
+    // outline pass alone.  Returns what pick returns.
+    Picked highlight_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, const Highlight& h = Highlight())
+    {
+        if (x >= ctx.width || y >= ctx.height) throw Error(VOLYM_E_INVALID, "highlight_at: the pixel is not inside the frame");
+        current_records(ctx, a, h.alpha_min);
+        if (records_host_.empty()) {
+            records_host_.resize(static_cast<size_t>(ctx.width) * ctx.height);
+            ctx.check(volym_read_picks(ctx.handle(), records_host_.data()));
+        }
+        Picked p{};
+        p.record = records_host_[static_cast<size_t>(y) * ctx.width + x];
+        describe(a, p);
+        std::vector<uint8_t> values;
+        if (p.record.status == 2 && p.record.has_labels) values.push_back(p.record.label);
+        highlight_labels(ctx, a, values, h);
+        return p;
+    }
+
+private:
+    // a whole-frame pick pass, unless the records of one for the current view, scene and alpha_min are there already
+    void current_records(const GpuContext& ctx, const SimpleAssets& a, float alpha_min)
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        if (records_current_ && records_alpha_min_ == alpha_min) return;
+        ctx.check(volym_pick_pass(ctx.handle(), nullptr, alpha_min));
+        records_current_ = true;
+        records_alpha_min_ = alpha_min;
+        records_host_.clear();
+    }
+    void highlight_labels(const GpuContext& ctx, const SimpleAssets& a, const std::vector<uint8_t>& values, const Highlight& h)
+    {
+        current_records(ctx, a, h.alpha_min);
+        volym_outline o{};
+        for (uint8_t l : values) o.selected[l] = 1;
+        for (int i = 0; i < 4; ++i) { o.ring_rgba[i] = h.ring_rgba[i]; o.fill_rgba[i] = h.fill_rgba[i]; }
+        o.radius = h.radius;
+        ctx.check(volym_outline_pass(ctx.handle(), &o, nullptr, nullptr, h.target_rgba8));
+    }
+    static uint8_t label_value_of(const SimpleAssets& a, const std::string& s)
+    {
+        for (const SegmentInfo& seg : a.segments)
+            if (seg.name == s || seg.id == s) return seg.label_value;
+        size_t used = 0;
+        int l = -1;
+        try { l = std::stoi(s, &used); } catch (...) { used = 0; }
+        if (s.empty() || used != s.size() || l < 0 || l > 255) throw Error(VOLYM_E_INVALID, "no segment with name or id '" + s + "'");
+        return static_cast<uint8_t>(l);
+    }
+    // segment name and unit-cube position of a record
+    static void describe(const SimpleAssets& a, Picked& p)
+    {
         const uint32_t n[3] = {a.nx, a.ny, a.nz}, t[3] = {p.record.x, p.record.y, p.record.z};
         for (int i = 0; i < 3; ++i) p.pos[i] = (static_cast<float>(t[i]) + 0.5f) / static_cast<float>(n[i]);
         if (p.record.status == 2 && p.record.has_labels)
             for (const SegmentInfo& s : a.segments)
                 if (s.label_value == p.record.label) { p.segment = s.name; break; }
-        return p;
     }
+
+public:
     // New: click to hide -- a pick, then set_hidden with that label added to the hidden ones.  Nothing changes when the pixel shows
     // no labelled sample.
     Picked hide_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, float alpha_min = 0.5f)
@@ -183,6 +267,9 @@ public:
 
 private:
     bool labels_on_device_ = false;
+    bool records_current_ = false;             // the device holds the records of a whole-frame pick pass of the current view and scene
+    float records_alpha_min_ = 0.0f;
+    std::vector<volym_pick_record> records_host_;   // their host copy, read back by the first highlight_at
 };
 
 }  // namespace volym

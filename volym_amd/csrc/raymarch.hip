@@ -535,6 +535,7 @@ void volym_destroy(volym_ctx* c)
     (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc);
     (void)hipFree(c->d_vol0); (void)hipFree(c->d_imp0);
     (void)hipFree(c->d_picks);
+    free_outline(c);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }
@@ -1059,6 +1060,7 @@ int volym_compute_pass(volym_ctx* c)
     if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_compute_pass: call volym_update first");
     HIPCHK(c, hipSetDevice(c->device));
     c->last = c->slots[1] ? static_cast<int>(c->flight_parity++ & 1u) : 0;    // frames in flight: the slots take turns
+    c->frame_rendered = true;
     return launch_march<false>(c, *c->slots[c->last]);
 }
 
@@ -1335,6 +1337,7 @@ int volym_pick_pass(volym_ctx* c, const uint32_t rect[4], float alpha_min)
     }
     const int rc = launch_pick(c, s, r, alpha_min, c->d_picks);
     if (rc != VOLYM_OK) return rc;
+    c->pick_x0 = r[0]; c->pick_y0 = r[1];
     c->pick_w = r[2]; c->pick_h = r[3];
     return VOLYM_OK;
 }

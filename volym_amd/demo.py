@@ -246,6 +246,40 @@ class GpuContext:
         self._pick_size = (1, 1)
         return out[0]
 
+    # ---- outline ------------------------------------------------------------------------------
+    def outline_pass(self, selected, ring_rgba, fill_rgba=(0, 0, 0, 0), radius=2, records_ptr=None, rect=None, target_ptr=None):
+        """Enqueue one outline pass (include/volym_hip.h volym_outline_pass; scene.outline_frame is its definition): the frame of the
+        latest compute pass with a ring of `radius` pixels in ring_rgba round the pixels whose pick record shows a label with
+        selected[label] != 0, and those pixels tinted with fill_rgba.  records_ptr / rect: device memory of w * h records covering
+        rect = (x0, y0, w, h); both None: the records of the latest pick pass.  target_ptr: device memory of W * H * 4 bytes (it may
+        be frame_device_ptr()); None: a target the context owns (read_outline)."""
+        o = _lib.Outline()
+        C.memmove(o.selected, scene._u8p(scene.check_selection(selected)), 256)
+        for name, c in (("ring_rgba", ring_rgba), ("fill_rgba", fill_rgba)):
+            v = [int(x) for x in c]
+            if len(v) != 4 or not all(0 <= x <= 255 for x in v):
+                raise ValueError("%s is four bytes (r, g, b, a)" % name)
+            setattr(o, name, (C.c_uint8 * 4)(*v))
+        if not 0 <= int(radius) < 2 ** 32:
+            raise ValueError("the radius is 1..8")
+        o.radius = int(radius)
+        r = None
+        if rect is not None:
+            if len(rect) != 4:
+                raise ValueError("a rect is (x0, y0, w, h)")
+            r = (C.c_uint32 * 4)(*[int(v) for v in rect])
+        self._ck(_lib.lib().volym_outline_pass(self.handle, C.byref(o), C.c_void_p(records_ptr), r, C.c_void_p(target_ptr)))
+
+    def read_outline(self):
+        """The context's own outline target: (H, W, 4) uint8.  Blocks."""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._ck(_lib.lib().volym_read_outline(self.handle, scene._u8p(out)))
+        return out
+
+    def outline_device_ptr(self):
+        """The context's own outline target after the latest pass into it (None before any)."""
+        return _lib.lib().volym_outline_device_ptr(self.handle)
+
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
         s = _lib.Stats()
@@ -320,6 +354,7 @@ class Simple(ComputeDemo):
     def update_gpu_state(self, ctx, state):
         """BaseDemo::update_gpu_state (src/demos/pipeline.rs:208-212)"""
         ctx.update(state.camera_uniforms(), state.parameter_uniforms())
+        self._records_for = None        # (highlight: the pick records of the old view are stale)
 
     def compute_pass(self, ctx):
         """BaseDemo::compute_pass -> DemoPipeline::compute_pass (src/demos/pipeline.rs:62-102, :214-225)"""
@@ -330,6 +365,7 @@ class Simple(ComputeDemo):
         texel = floor(p * n + 0.5) clamped to [0, n] (scene.crop_box_texels).  Returns the texel box."""
         lo, hi = scene.crop_box_texels(lo01, hi01, self.dims)
         ctx.set_crop_box(lo, hi)
+        self._records_for = None
         return lo, hi
 
     def set_hidden(self, ctx, hidden):
@@ -351,7 +387,58 @@ class Simple(ComputeDemo):
                 return []
             self.set_labels(ctx, self._labels_raw)
         ctx.set_segment_visibility(mask)
+        self._records_for = None
         return sorted(values)
+
+    def _label_values(self, segments):
+        """Label values of `segments`: names or ids of the segments JSON ("Canopy", "canopy") or raw label values, mixed freely"""
+        by_key = {}
+        for s in reversed(getattr(self, "_segments", [])):
+            for k in ("name", "id"):
+                if k in s:
+                    by_key[s[k]] = s["label_value"]
+        values = set()
+        for h in segments:
+            if isinstance(h, str):
+                if h not in by_key:
+                    raise ValueError("no segment with name or id %r" % h)
+                values.add(by_key[h])
+            else:
+                values.add(int(h))
+        return sorted(values)
+
+    def _current_records(self, ctx, alpha_min):
+        """A whole-frame pick pass, unless the records of one for the current view, scene and alpha_min are there already"""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        if getattr(self, "_records_for", None) != (id(ctx), float(alpha_min)):
+            ctx.pick_pass(None, alpha_min)
+            self._records_for = (id(ctx), float(alpha_min))
+            self._records_host = None
+
+    def highlight(self, ctx, segments, ring_rgba=(255, 255, 0, 255), fill_rgba=(255, 255, 0, 48), radius=2, alpha_min=0.5, target_ptr=None):
+        """Outline and tint the given segments (names, ids or label values) in the frame of the latest compute pass: one outline
+        pass over the records of a whole-frame pick pass, which runs only if the demo has none for the current view and scene
+        (update_gpu_state, set_crop, set_hidden, set_segments and set_labels make the records stale).  A hover that moves to
+        another segment costs the outline pass alone.  The image goes to target_ptr, or to the context's own target
+        (ctx.read_outline()).  Returns the selected label values."""
+        values = self._label_values(segments)
+        self._current_records(ctx, alpha_min)
+        ctx.outline_pass(scene.selection_mask(values), ring_rgba, fill_rgba, radius, target_ptr=target_ptr)
+        return values
+
+    def highlight_at(self, ctx, x, y, alpha_min=0.5, **kw):
+        """Hover: outline the segment pixel (x, y) shows (nothing when it shows no labelled sample: the image is then the
+        frame).  The label comes from the current records, which are read back once per view and scene: the hovers after
+        the first cost the outline pass alone.  Returns what pick returns."""
+        if not (0 <= int(x) < ctx.width and 0 <= int(y) < ctx.height):
+            raise ValueError("pixel (%r, %r) is not inside the %d x %d frame" % (x, y, ctx.width, ctx.height))
+        self._current_records(ctx, alpha_min)
+        if self._records_host is None:
+            self._records_host = ctx.read_picks()
+        p = self._describe_pick(x, y, self._records_host[int(y), int(x)])
+        self.highlight(ctx, [p["label"]] if p["status"] == "hit" and p["label"] is not None else [], alpha_min=alpha_min, **kw)
+        return p
 
     def pick(self, ctx, x, y, alpha_min=0.5):
         """What pixel (x, y) of the frame shows: the first sample of its ray after which alpha >= alpha_min (GpuContext.pick), as
@@ -362,6 +449,11 @@ class Simple(ComputeDemo):
         if not self._labels_on_device and self._labels_raw.size:
             self.set_labels(ctx, self._labels_raw)
         r = ctx.pick(x, y, alpha_min)
+        self._records_for = None        # (the one-pixel pass took the place of a whole frame's records)
+        return self._describe_pick(x, y, r)
+
+    def _describe_pick(self, x, y, r):
+        """the dict of pick for the record r of pixel (x, y)"""
         status = ("miss", "none", "hit")[int(r["status"])]
         out = {"x": int(x), "y": int(y), "status": status, "label": None, "segment": None, "segment_id": None, "texel": None, "pos": None, "t": None,
                "alpha": int(r["alpha8"]) / 255.0, "density": None}
@@ -392,6 +484,7 @@ class Simple(ComputeDemo):
         ctx.set_labels(scene.prepare_volume(labels_raw, self.dims, flip_y=True), self.dims)
         self._labels_raw = labels_raw
         self._labels_on_device = True
+        self._records_for = None
 
     def set_segments(self, ctx, segments):
         """New segment importances for the labels of set_labels (an editor's "show me the lobster instead of the cup").
@@ -400,6 +493,7 @@ class Simple(ComputeDemo):
         importance 0 there, table[0] here.  When that matters (table[0] != 0 and padding exists) the host map runs instead."""
         segments = scene.load_segments(segments)
         table = scene.segment_table(segments)
+        self._records_for = None
         padded = self._labels_raw.size < self.dims[0] * self.dims[1] * self.dims[2]
         if padded and table[0] != 0:
             importances = scene.map_segments_to_importance(self._labels_raw, segments)

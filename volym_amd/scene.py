@@ -279,6 +279,72 @@ def crop_volume(prepared, dims, lo, hi):
     return out.ravel()
 
 
+def check_selection(selected):
+    """An outline selection: 256 flags, one per label value, nonzero = selected.  Returns np.uint8[256] of 0 / 1."""
+    return check_segment_visibility(selected)
+
+
+def selection_mask(label_values):
+    """Nothing selected except the given label values."""
+    return (1 - visibility_mask(label_values)).astype(np.uint8)
+
+
+def _rgba(c, what):
+    v = [int(x) for x in c]
+    if len(v) != 4 or not all(0 <= x <= 255 for x in v):
+        raise ValueError("%s is four bytes (r, g, b, a)" % what)
+    return np.array(v, np.uint32)
+
+
+def outline_blend(src, col):
+    """The blend of the outline pass on uint8 arrays (..., 4): out[c] = (src[c] * (255 - A) + col[c] * A + 127) // 255 for r, g, b
+    and the same with 255 for col in the alpha byte, A = col[3]."""
+    col = _rgba(col, "a colour")
+    a = col[3]
+    v = np.array([col[0], col[1], col[2], 255], np.uint32)
+    return ((np.asarray(src, np.uint8).astype(np.uint32) * (255 - a) + v * a + 127) // 255).astype(np.uint8)
+
+
+def outline_frame(frame, picks, rect, selected, ring_rgba, fill_rgba=(0, 0, 0, 0), radius=2):
+    """The definition of the outline pass (include/volym_hip.h volym_outline_pass), integers only: `frame` (H, W, 4) uint8, `picks`
+    an (h, w) array of _lib.PICK_DTYPE covering rect = (x0, y0, w, h) of it.  A pixel is selected when it lies inside rect, its
+    record has status 2 and selected[label] != 0; it is on the ring when it is not selected and a selected pixel of the frame lies
+    within `radius` (1..8) of it in the Chebyshev metric.  Ring pixels are blended with ring_rgba, selected ones with fill_rgba
+    (outline_blend), every other pixel is the frame's.  Returns a new (H, W, 4) uint8 image."""
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 4:
+        raise ValueError("the frame is (H, W, 4) uint8")
+    H, W = frame.shape[:2]
+    r = int(radius)
+    if not 1 <= r <= 8:
+        raise ValueError("the radius is 1..8, got %r" % (radius,))
+    if len(rect) != 4:
+        raise ValueError("a rect is (x0, y0, w, h)")
+    x0, y0, w, h = (int(v) for v in rect)
+    if w <= 0 or h <= 0 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError("the rect must be non-empty and inside the frame")
+    picks = np.asarray(picks)
+    if picks.dtype != _lib.PICK_DTYPE or picks.shape != (h, w):
+        raise ValueError("the records are an (h, w) = (%d, %d) array of PICK_DTYPE" % (h, w))
+    sel = check_selection(selected)
+    mask = np.zeros((H, W), bool)
+    mask[y0:y0 + h, x0:x0 + w] = (picks["status"] == 2) & (sel[picks["label"]] != 0)
+    # Chebyshev dilation: along x, then along y, on a plane padded with `r` unselected pixels (pixels beyond the frame do not exist)
+    pad = np.zeros((H + 2 * r, W + 2 * r), bool)
+    pad[r:r + H, r:r + W] = mask
+    rows = np.zeros((H + 2 * r, W), bool)
+    for s in range(2 * r + 1):
+        rows |= pad[:, s:s + W]
+    near = np.zeros((H, W), bool)
+    for s in range(2 * r + 1):
+        near |= rows[s:s + H]
+    ring = near & ~mask
+    out = frame.copy()
+    out[ring] = outline_blend(frame[ring], ring_rgba)
+    out[mask] = outline_blend(frame[mask], fill_rgba)
+    return out
+
+
 def map_segments_to_importance(labels, segments):
     """src/demos/simple/importance.rs:148-158"""
     data = np.array(labels, np.uint8, copy=True).ravel()
