@@ -192,6 +192,34 @@ int volym_get_crop_box(volym_ctx* ctx, uint32_t lo[3], uint32_t hi[3]);
  * (0 when the boxes are equal).  Pure host arithmetic, no context.  VOLYM_E_INVALID for NULL or lo > hi. */
 int volym_crop_slabs(const uint32_t old_lo[3], const uint32_t old_hi[3], const uint32_t new_lo[3], const uint32_t new_hi[3],
                      uint32_t slabs[6][6], uint32_t* n_slabs);
+/* Oblique clip plane on the device (new; the reference has none): the cut the box cannot make.  A plane is an integer normal n
+ * and an integer offset d; texel (x, y, z) -- the coordinates volym_set_crop_box and the pick records use -- is KEPT iff
+ * n[0]*x + n[1]*y + n[2]*z <= d.  The frames enqueued after the call are the frames of the same scene in which every density
+ * byte AND every importance byte of a texel that is not kept is 0.  Valid: |n[a]| <= VOLYM_CLIP_PLANE_MAX on every axis, and
+ * n == (0, 0, 0) only with d == 0, which means "no plane" and is the state after volym_set_volume (to keep nothing use e.g.
+ * n = (1, 0, 0), d = -1); anything else is VOLYM_E_INVALID, a call without a volume VOLYM_E_STATE.  With these bounds and the
+ * 4096 texels per axis volym_set_volume admits, |n . t| <= 3 * 4096 * 4099 < 2^31 (4099: the walk also evaluates a brick's padding texels): the test is exact in 32-bit integers on host
+ * and device, for every volume the library holds.
+ *   Box, plane and mask commute: any interleaving of volym_set_crop_box, volym_set_clip_plane and
+ * volym_set_segment_visibility that ends at the same (box, plane, mask) leaves the same bytes, and a box that grows over clipped
+ * texels leaves them 0.  The plane belongs to the scene as the box does: volym_set_volume resets it, and volym_set_importances,
+ * volym_set_labels and volym_set_segment_importances made under a plane give clipped importances.  Blocking set-up call with the
+ * semantics of volym_set_crop_box: it waits for the frames in flight in every frame slot (they show the old plane), needs no
+ * volym_update before the next volym_compute_pass, makes no pass over voxels on the host and no upload.  The first cut of any
+ * kind (box, plane, mask) makes the uncut device copies; an edit walks the box of volym_clip_plane_box and stores only the
+ * 16-byte chunks in which a texel changes side, then refreshes the macro cells that box touches.  A plane equal to the current
+ * one returns at once.  A failure after the first kernel of an edit leaves the context asking for volym_set_volume again. */
+#define VOLYM_CLIP_PLANE_MAX 4096
+int volym_set_clip_plane(volym_ctx* ctx, const int32_t n[3], int32_t d);
+int volym_get_clip_plane(volym_ctx* ctx, int32_t n[3], int32_t* d);
+/* The box of texels volym_set_clip_plane walks when the plane goes from (old_n, old_d) to (new_n, new_d) inside [lo, hi): 0 or 1
+ * boxes {x0, y0, z0, x1, y1, z1} (hi exclusive) inside [lo, hi) that hold every texel of [lo, hi) the two planes classify
+ * differently; *n_boxes is 0 when there is no such texel, in particular when the planes are equal.  The box is tight in this
+ * sense: over an outer slice of it, normal to an axis, the two predicates are not both constant and equal (the extremes of n . t
+ * over a slice are exact).  Pure host arithmetic, no context.  VOLYM_E_INVALID for NULL, an invalid plane, lo > hi or
+ * hi > 65536. */
+int volym_clip_plane_box(const int32_t old_n[3], int32_t old_d, const int32_t new_n[3], int32_t new_d, const uint32_t lo[3],
+                         const uint32_t hi[3], uint32_t box[6], uint32_t* n_boxes);
 /* Segment visibility on the device (new; the reference has none): switch segments off without touching the volume on the host.
  * visible[l] != 0 shows label value l.  The frames enqueued after the call are the frames of the same scene in which every
  * density byte AND every importance byte of a texel whose label is hidden, or that lies outside the crop box, is 0 (a hidden

@@ -74,8 +74,9 @@ int volym_mgpu_set_importances(volym_mgpu* mg, const uint8_t* importances, uint3
 int volym_mgpu_set_labels(volym_mgpu* mg, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz);
 int volym_mgpu_set_segment_importances(volym_mgpu* mg, const uint8_t table[256]);
 int volym_mgpu_set_crop_box(volym_mgpu* mg, const uint32_t lo[3], const uint32_t hi[3]);
+int volym_mgpu_set_clip_plane(volym_mgpu* mg, const int32_t n[3], int32_t d);
 int volym_mgpu_set_segment_visibility(volym_mgpu* mg, const uint8_t visible[256]);
-/* (The set-up calls that change the scene -- volume, importances, segment importances, crop box, segment visibility, transfer function -- also drop
+/* (The set-up calls that change the scene -- volume, importances, segment importances, crop box, clip plane, segment visibility, transfer function -- also drop
  * the HIP graph volym_mgpu_run may hold: it was captured for the scene before the call, and the next run with use_graph captures
  * again, at a standing view too.) */
 int volym_mgpu_set_transfer_function(volym_mgpu* mg, const uint8_t* rgba8, uint32_t n);

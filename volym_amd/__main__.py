@@ -16,6 +16,7 @@ pixel) write the annotated image instead: a ring round the segments and a tint o
 """
 import argparse
 import csv
+import math
 import sys
 import time
 
@@ -126,6 +127,17 @@ def _crop_arg(text):
     return tuple(v[:3]), tuple(v[3:])
 
 
+def _clip_plane_arg(text):
+    """--clip-plane NX,NY,NZ,PX,PY,PZ (normal and a point of the plane, unit-cube coordinates) -> (normal, point)"""
+    try:
+        v = [float(t) for t in text.split(",")]
+    except ValueError:
+        v = []
+    if len(v) != 6 or not all(math.isfinite(t) for t in v) or not any(v[:3]):
+        raise SystemExit("--clip-plane: NX,NY,NZ,PX,PY,PZ -- a normal (not zero) and a point of the plane, unit-cube coordinates")
+    return tuple(v[:3]), tuple(v[3:])
+
+
 def _hide_arg(text):
     """--hide 3,4 (label values) -> [3, 4]"""
     try:
@@ -158,14 +170,14 @@ def _outline_arg(text):
     return [int(t) if t.isdigit() else t for t in v]
 
 
-def _outline_at_arg(text):
-    """--outline-at X,Y (pixel of the frame) -> (x, y)"""
+def _outline_at_arg(text, flag="--outline-at"):
+    """--outline-at X,Y, --clip-at X,Y (pixel of the frame) -> (x, y)"""
     try:
         x, y = (int(t) for t in text.split(","))
     except ValueError:
-        raise SystemExit("--outline-at: X,Y -- a pixel of the frame")
+        raise SystemExit("%s: X,Y -- a pixel of the frame" % flag)
     if x < 0 or y < 0:
-        raise SystemExit("--outline-at: X,Y -- a pixel of the frame")
+        raise SystemExit("%s: X,Y -- a pixel of the frame" % flag)
     return x, y
 
 
@@ -178,11 +190,20 @@ def run_simple(args):
         d = demo.Simple.init(ctx, state, volume_raw=raw, labels_raw=labels, segments=segments, dims=(256, 256, 256))
         if args.crop:
             d.set_crop(ctx, *_crop_arg(args.crop))
+        if args.clip_plane:
+            d.set_clip_plane(ctx, *_clip_plane_arg(args.clip_plane))
         if args.hide:
             d.set_hidden(ctx, _hide_arg(args.hide))
         d.update_gpu_state(ctx, state)
         d.compute_pass(ctx)
         ctx.sync()
+        clipped = None
+        if args.clip_at:
+            # click to cut: the plane through what the pixel shows, facing the eye; the PNG is the frame after the cut
+            plane = d.clip_at(ctx, *_outline_at_arg(args.clip_at, "--clip-at"))
+            clipped = {"clip_plane": None if plane is None else {"n": list(plane[0]), "d": plane[1]}}
+            d.compute_pass(ctx)
+            ctx.sync()
         frame = ctx.read_rgba8()
         picked = d.pick(ctx, *_pick_arg(args.pick)) if getattr(args, "pick", None) else None
         outlined = None
@@ -198,6 +219,9 @@ def run_simple(args):
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    if clipped is not None:
+        import json
+        print(json.dumps(clipped))     # one line: the plane --clip-at set (null: the pixel shows nothing)
     if picked is not None:
         import json
         print(json.dumps(picked))      # one line: what the pixel shows (demo.Simple.pick)
@@ -226,6 +250,7 @@ def flythrough(args):
         d = demo.Simple.init(ctx, state, volume_raw=raw, labels_raw=labels, segments=segments, dims=(256, 256, 256))
         if args.crop:
             d.set_crop(ctx, *_crop_arg(args.crop))
+        plane = d.set_clip_plane(ctx, *_clip_plane_arg(args.clip_plane)) if args.clip_plane else None
         hidden = d.set_hidden(ctx, _hide_arg(args.hide)) if args.hide else None
         sweep = ft.crop_sweep(args.frames) if args.crop_sweep else None    # our widget: a crop face dragged over its range
         for i, ev in enumerate(ft.script(args.frames)):
@@ -247,6 +272,8 @@ def flythrough(args):
                              "parameter_uniforms": bytes(state.parameter_uniforms()).hex()})
                 if hidden is not None:       # (a run without --hide writes the keys it always wrote)
                     kept[-1]["hidden_labels"] = hidden
+                if plane is not None:        # (likewise --clip-plane)
+                    kept[-1]["clip_plane"] = {"n": list(plane[0]), "d": plane[1]}
         ctx.sync()
     if args.out:
         with open(os.path.join(args.out, "frames.json"), "w") as f:
@@ -296,6 +323,8 @@ def main(argv=None):
     run.add_argument("--screenshot")
     run.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
     run.add_argument("--hide", help="label values of the segments to hide, e.g. 3,4")
+    run.add_argument("--clip-plane", help="NX,NY,NZ,PX,PY,PZ: oblique clip plane, normal and point in unit-cube coordinates; the side the normal points to is cut away")
+    run.add_argument("--clip-at", help="X,Y: after the frame, cut along the plane through what pixel (X, Y) shows, facing the eye; the PNG is the frame after the cut")
     run.add_argument("--pick", help="X,Y[,ALPHA]: after the frame, print what pixel (X, Y) shows as one JSON line (segment, texel, depth)")
     run.add_argument("--outline", help="NAME[,NAME...]: segment names, ids or label values to outline and tint; the PNG is the annotated image")
     run.add_argument("--outline-at", help="X,Y: outline the segment pixel (X, Y) shows; the PNG is the annotated image")
@@ -314,6 +343,7 @@ def main(argv=None):
     fl.add_argument("--frames", type=int, default=120); fl.add_argument("--out"); fl.add_argument("--keep-every", type=int, default=10)
     fl.add_argument("--crop", help="crop box x0,y0,z0,x1,y1,z1 in unit-cube coordinates")
     fl.add_argument("--hide", help="label values of the segments to hide, e.g. 3,4")
+    fl.add_argument("--clip-plane", help="NX,NY,NZ,PX,PY,PZ: oblique clip plane, normal and point in unit-cube coordinates")
     fl.add_argument("--crop-sweep", action="store_true", help="drag the far z crop face over its range while flying (not a widget of the reference)")
     dv = sub.add_parser("devtools", help="3D-Slicer .seg.nrrd -> segments.json + label .raw (volym_devtools)")
     dv.add_argument("nrrd"); dv.add_argument("segments_json"); dv.add_argument("binary_data")

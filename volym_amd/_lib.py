@@ -159,6 +159,10 @@ SIGNATURES = {
     "volym_label_counts": (C.c_int, [_ctx, C.POINTER(C.c_uint64)]),
     "volym_set_crop_box": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "volym_get_crop_box": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_set_clip_plane": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.c_int32]),
+    "volym_get_clip_plane": (C.c_int, [_ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "volym_clip_plane_box": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "volym_set_segment_visibility": (C.c_int, [_ctx, _u8p]),
     "volym_get_segment_visibility": (C.c_int, [_ctx, _u8p]),
     "volym_visibility_boxes": (C.c_int, [_u8p, C.POINTER(C.c_uint64), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),

@@ -133,6 +133,9 @@ struct volym_ctx {
     // the labels through seg_table when a table has been set since the labels, else d_imp0 (NULL: d_imp is uncropped).  They are
     // cropped only while their dimensions are the volume's (volym_update refuses any other).
     uint32_t crop_lo[3] = {0, 0, 0}, crop_hi[3] = {0, 0, 0};
+    // clip plane (volym_set_clip_plane): texel (x, y, z) is kept iff clip_n . (x, y, z) <= clip_d; (0, 0, 0), 0 = no plane, the
+    // state after volym_set_volume.  A third term of the invariant below, cut from the same uncut sources as the box.
+    int32_t clip_n[3] = {0, 0, 0}, clip_d = 0;
     uint8_t* d_vol0 = nullptr;
     uint8_t* d_imp0 = nullptr;
     bool imp_bricked = false;                // layout of d_imp (and d_imp0)
@@ -141,11 +144,11 @@ struct volym_ctx {
     int imp_box0_lo[3] = {1, 1, 1}, imp_box0_hi[3] = {0, 0, 0};   // imp_box_* of the uncropped importances (of the visible segments)
     // segment visibility (volym_set_segment_visibility): seg_hidden[l] != 0 hides label l; all 0 after volym_set_labels,
     // volym_set_importances and volym_set_volume.  The invariant every edit of box or mask keeps, and relies on to rewrite only
-    // the texels whose state changes:  d_vol[t] = (t inside the crop box && !seg_hidden[label(t)]) ? d_vol0[t] : 0  for every
-    // texel t, and the same for d_imp with its uncropped source (above).  An edit that fails after its first launch breaks it,
+    // the texels whose state changes:  d_vol[t] = (t inside the crop box && t kept by the clip plane && !seg_hidden[label(t)]) ?
+    // d_vol0[t] : 0  for every texel t, and the same for d_imp with its uncropped source (above).  An edit that fails after its first launch breaks it,
     // and the context then asks for volym_set_volume again (have_vol false).  While a segment is hidden the labels have the
     // volume's dimensions and layout (the call refuses anything else).  One function keeps it: retarget (scene_bytes.hip), which
-    // every set-up call that changes box, mask or bytes goes through.
+    // every set-up call that changes box, plane, mask or bytes goes through.
     uint8_t seg_hidden[256] = {};
     int filter = VOLYM_FILTER_NEAREST;
     uint8_t lut[256 * 4] = {};

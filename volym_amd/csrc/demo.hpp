@@ -7,6 +7,7 @@
 // GpuContext stands where src/gpu_context.rs + GpuWriteTexture2D stood: a device and a W x H rgba8 output.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <stdexcept>
@@ -92,6 +93,7 @@ public:
         parameter_uniforms_from(state, par);
         ctx.check(volym_update(ctx.handle(), &cam, &par));
         records_current_ = false;      // (highlight: the pick records of the old view are stale)
+        for (int i = 0; i < 3; ++i) eye_[i] = state.camera.position[i];      // (clip_at: the plane faces the eye)
     }
     void compute_pass(const GpuContext& ctx) override { ctx.check(volym_compute_pass(ctx.handle())); }   // src/demos/pipeline.rs:62-102
 
@@ -134,6 +136,35 @@ public:
         ctx.check(volym_set_crop_box(ctx.handle(), lo, hi));
         records_current_ = false;
     }
+    // New: oblique clip plane through `point` with the given normal, both in the unit-cube coordinates set_crop takes: what lies on
+    // the side the normal points to is cut away (volym_set_clip_plane).  The integers, in double: g_i = normal_i / n_i,
+    // k = 4096 / max|g_i|, a_i = floor(g_i * k + 0.5), d = floor(sum a_i * (point_i * n_i - 0.5)).  normal == NULL lifts the plane.
+    struct ClipPlane { int32_t n[3]; int32_t d; };
+    ClipPlane set_clip_plane(const GpuContext& ctx, const SimpleAssets& a, const float normal[3], const float point[3])
+    {
+        ClipPlane p{{0, 0, 0}, 0};
+        if (normal) p = clip_plane_texels(a, normal, point);
+        ctx.check(volym_set_clip_plane(ctx.handle(), p.n, p.d));
+        records_current_ = false;
+        return p;
+    }
+    static ClipPlane clip_plane_texels(const SimpleAssets& a, const float normal[3], const float point[3])
+    {
+        const double dims[3] = {static_cast<double>(a.nx), static_cast<double>(a.ny), static_cast<double>(a.nz)};
+        double g[3], top = 0.0, sum = 0.0;
+        for (int i = 0; i < 3; ++i) { g[i] = static_cast<double>(normal[i]) / dims[i]; top = std::max(top, std::fabs(g[i])); }
+        if (!(top > 0.0) || !std::isfinite(top)) throw Error(VOLYM_E_INVALID, "clip plane: the normal must be finite and not zero");
+        ClipPlane p{};
+        for (int i = 0; i < 3; ++i) {
+            const double c = std::floor(g[i] * (4096.0 / top) + 0.5);
+            p.n[i] = static_cast<int32_t>(c);
+            sum += c * (static_cast<double>(point[i]) * dims[i] - 0.5);
+        }
+        sum = std::floor(sum);
+        if (!(sum >= -2147483648.0 && sum <= 2147483647.0)) throw Error(VOLYM_E_INVALID, "clip plane: the point is too far from the volume");
+        p.d = static_cast<int32_t>(sum);
+        return p;
+    }
     // New: hide the segments with the given label values and show all others (volym_set_segment_visibility).  The labels go to the
     // device first if they are not there yet; the importances stay what they were.
     void set_hidden(const GpuContext& ctx, const SimpleAssets& a, const std::vector<uint8_t>& hidden_label_values)
@@ -167,7 +198,7 @@ public:
     }
     // New: outline and tint segments in the frame of the latest compute pass (volym_outline_pass) -- one outline pass over the
     // records of a whole-frame pick pass, which runs only if the demo has none for the current view and scene (update_gpu_state,
-    // set_crop, set_hidden, set_segments and set_labels make the records stale).  `segments`: names or ids of the segments table, or
+    // set_crop, set_clip_plane, set_hidden, set_segments and set_labels make the records stale).  `segments`: names or ids of the segments table, or
     // label values written as numbers ("3").  The image goes to target_rgba8 (device memory), or with NULL to the context's own
     // target (volym_read_outline).  Returns the selected label values.
     std::vector<uint8_t> highlight(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments, const Highlight& h = Highlight())
@@ -252,6 +283,20 @@ public:
         set_hidden(ctx, a, hidden);
         return p;
     }
+    // New: click to cut -- a pick, then the clip plane through the picked texel's centre with the normal pointing from there to the
+    // eye: everything between the eye and the clicked point is cut away, the texel itself stays.  False: the pixel shows nothing, and
+    // the plane stays as it is.
+    bool clip_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, ClipPlane& plane, float alpha_min = 0.5f)
+    {
+        const Picked p = pick(ctx, a, x, y, alpha_min);
+        if (p.record.status != 2) return false;
+        const float normal[3] = {eye_[0] - p.pos[0], eye_[1] - p.pos[1], eye_[2] - p.pos[2]};
+        plane = clip_plane_texels(a, normal, p.pos);
+        plane.d = plane.n[0] * p.record.x + plane.n[1] * p.record.y + plane.n[2] * p.record.z;      // exactly through the texel
+        ctx.check(volym_set_clip_plane(ctx.handle(), plane.n, plane.d));
+        records_current_ = false;
+        return true;
+    }
     static uint32_t crop_texel(float p, uint32_t n)
     {
         const double t = std::floor(static_cast<double>(p) * n + 0.5);
@@ -266,6 +311,7 @@ public:
     }
 
 private:
+    float eye_[3] = {0.0f, 0.0f, 0.0f};
     bool labels_on_device_ = false;
     bool records_current_ = false;             // the device holds the records of a whole-frame pick pass of the current view and scene
     float records_alpha_min_ = 0.0f;

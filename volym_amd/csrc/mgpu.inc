@@ -401,6 +401,14 @@ int volym_mgpu_set_crop_box(volym_mgpu* m, const uint32_t lo[3], const uint32_t 
     return VOLYM_OK;
 }
 
+int volym_mgpu_set_clip_plane(volym_mgpu* m, const int32_t n[3], int32_t d)
+{
+    if (!m) return VOLYM_E_INVALID;
+    mg_drop_graph(m);
+    for (MgLocal& L : m->loc) MG_CTX(m, L, volym_set_clip_plane(L.ctx, n, d));
+    return VOLYM_OK;
+}
+
 int volym_mgpu_set_segment_visibility(volym_mgpu* m, const uint8_t visible[256])
 {
     if (!m) return VOLYM_E_INVALID;

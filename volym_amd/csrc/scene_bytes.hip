@@ -1,5 +1,5 @@
 // libvolym_hip.so: the bytes of the scene.  Volume, label and importance uploads, the device layout, the macro cells, and the
-// one transition (retarget) that keeps density and importances cut to the crop box and the segment mask; the C ABI entry
+// one transition (retarget) that keeps density and importances cut to the crop box, the clip plane and the segment mask; the C ABI entry
 // points of all of these.  The frame loop (raymarch.hip) reads what this unit writes; what the two need from each other is
 // declared in context.hpp.  Everything here is blocking set-up path.
 #include <hip/hip_runtime.h>
@@ -169,14 +169,16 @@ static int refresh_macro_cells(volym_ctx* c, const uint32_t (*boxes)[6], uint32_
     return VOLYM_OK;
 }
 
-// ---- crop box and segment visibility on the device --------------------------------------------------------------------
-// A frame with crop box B and mask `visible` is the frame of the scene whose density and importance bytes are 0 outside B and
-// in every texel of a hidden label.  The march kernels know nothing of either: they read d_vol and d_imp, and the set-up calls
-// rewrite those from an uncropped source so that the invariant of context.hpp holds for the scene's (box, mask).  One function
-// does that, retarget: it moves the buffers from the invariant of one (box, mask) to that of another and rewrites only the
-// texels whose state can differ between the two -- the slabs between the boxes (volym_crop_slabs: at most six, one per face
-// that moved) and the boxes of the labels whose flag flipped (volym_visibility_boxes; volym_visibility_kernel skips every
-// chunk in there that holds no texel of such a label).  Everything derived from the bytes follows: the macro cells the
+// ---- crop box, clip plane and segment visibility on the device --------------------------------------------------------
+// A frame with crop box B, clip plane P and mask `visible` is the frame of the scene whose density and importance bytes are 0
+// outside B, on the cut side of P and in every texel of a hidden label.  The march kernels know nothing of any of them: they
+// read d_vol and d_imp, and the set-up calls rewrite those from an uncropped source so that the invariant of context.hpp holds
+// for the scene's (box, plane, mask).  One function does that, retarget: it moves the buffers from the invariant of one
+// (box, plane, mask) to that of another and rewrites only the texels whose state can differ between the two -- the slabs
+// between the boxes (volym_crop_slabs: at most six, one per face that moved), the boxes of the labels whose flag flipped
+// (volym_visibility_boxes; volym_visibility_kernel skips every chunk in there that holds no texel of such a label) and the box
+// of the texels the two planes classify differently (volym_clip_plane_box; volym_clip_plane_kernel skips every chunk in there
+// in which no texel changes side).  Everything derived from the bytes follows: the macro cells the
 // rewritten boxes touch, the occupied-cell boxes, every slot's distance field, hulls, tile mask and depth bounds (rebuilt by
 // the next launch), the look-ahead's reject box, the work lists.
 
@@ -272,12 +274,87 @@ int volym_visibility_boxes(const uint8_t flipped[256], const uint64_t counts[256
     return VOLYM_OK;
 }
 
+static bool valid_plane(const int32_t n[3], int32_t d)
+{
+    for (int a = 0; a < 3; ++a) if (n[a] < -VOLYM_CLIP_PLANE_MAX || n[a] > VOLYM_CLIP_PLANE_MAX) return false;
+    return n[0] != 0 || n[1] != 0 || n[2] != 0 || d == 0;
+}
+
+static int64_t floor_div(int64_t a, int64_t b) { const int64_t q = a / b; return (a % b != 0 && ((a < 0) != (b < 0))) ? q - 1 : q; }
+
+// the texels x of [lo, hi) with n0 * x <= r, as an interval [x0, x1) (x0 == x1 == lo: none)
+static void kept_run(int64_t n0, int64_t r, int64_t lo, int64_t hi, int64_t& x0, int64_t& x1)
+{
+    x0 = lo; x1 = hi;
+    if (n0 > 0) x1 = std::min(hi, floor_div(r, n0) + 1);
+    else if (n0 < 0) x0 = std::max(lo, -floor_div(r, -n0));        // x >= ceil(r / n0) = -floor(r / -n0)
+    else if (r < 0) x1 = lo;
+    if (x1 <= x0) x0 = x1 = lo;
+}
+
+int volym_clip_plane_box(const int32_t old_n[3], int32_t old_d, const int32_t new_n[3], int32_t new_d, const uint32_t lo[3], const uint32_t hi[3],
+                         uint32_t box[6], uint32_t* n_boxes)
+{
+    if (!old_n || !new_n || !lo || !hi || !box || !n_boxes) return VOLYM_E_INVALID;
+    if (!valid_plane(old_n, old_d) || !valid_plane(new_n, new_d)) return VOLYM_E_INVALID;
+    for (int a = 0; a < 3; ++a) if (lo[a] > hi[a] || hi[a] > 65536u) return VOLYM_E_INVALID;
+    *n_boxes = 0;
+    const bool equal = old_d == new_d && old_n[0] == new_n[0] && old_n[1] == new_n[1] && old_n[2] == new_n[2];
+    if (equal || lo[0] == hi[0] || lo[1] == hi[1] || lo[2] == hi[2]) return VOLYM_OK;
+    // Shrink [lo, hi) from every face while the outer slice there is one over which both predicates are constant and equal: a
+    // texel the planes classify differently lies in no such slice, so it stays inside.  n . t over a slice is linear, so its
+    // extremes are exact: the predicate is true throughout when the maximum is <= d, false throughout when the minimum is > d.
+    // A slice of a narrower box may be clean where that of the wider one was not: repeat until no face moves.
+    uint32_t b[6] = {lo[0], lo[1], lo[2], hi[0], hi[1], hi[2]};
+    const auto state = [&](const int32_t n[3], int32_t d, int a, uint32_t i) {
+        int64_t mn = static_cast<int64_t>(n[a]) * i, mx = mn;
+        for (int o = 0; o < 3; ++o) {
+            if (o == a) continue;
+            const int64_t p = static_cast<int64_t>(n[o]) * b[o], q = static_cast<int64_t>(n[o]) * (b[3 + o] - 1u);
+            mn += std::min(p, q); mx += std::max(p, q);
+        }
+        return mx <= d ? 1 : mn > d ? 0 : 2;
+    };
+    const auto clean = [&](int a, uint32_t i) {
+        const int so = state(old_n, old_d, a, i);
+        return so != 2 && so == state(new_n, new_d, a, i);
+    };
+    for (bool moved = true; moved;) {
+        moved = false;
+        for (int a = 0; a < 3; ++a) {
+            while (b[a] < b[3 + a] && clean(a, b[a])) { ++b[a]; moved = true; }
+            while (b[a] < b[3 + a] && clean(a, b[3 + a] - 1u)) { --b[3 + a]; moved = true; }
+            if (b[a] == b[3 + a]) return VOLYM_OK;
+        }
+    }
+    // Two planes may still keep the same texels there (3x <= 2 and x <= 0): no box then.  Exact, a row at a time along the longest
+    // axis, where each plane keeps an interval; it ends at the first row whose two intervals differ.
+    int ax = 0;
+    for (int a = 1; a < 3; ++a) if (b[3 + a] - b[a] > b[3 + ax] - b[ax]) ax = a;
+    const int u = (ax + 1) % 3, v = (ax + 2) % 3;
+    for (uint32_t j = b[v]; j < b[3 + v]; ++j)
+        for (uint32_t i = b[u]; i < b[3 + u]; ++i) {
+            const int64_t ro = static_cast<int64_t>(old_d) - static_cast<int64_t>(old_n[u]) * i - static_cast<int64_t>(old_n[v]) * j;
+            const int64_t rn = static_cast<int64_t>(new_d) - static_cast<int64_t>(new_n[u]) * i - static_cast<int64_t>(new_n[v]) * j;
+            int64_t o0, o1, n0, n1;
+            kept_run(old_n[ax], ro, b[ax], b[3 + ax], o0, o1);
+            kept_run(new_n[ax], rn, b[ax], b[3 + ax], n0, n1);
+            if (o0 == n0 && o1 == n1) continue;
+            std::memcpy(box, b, sizeof b);
+            *n_boxes = 1;
+            return VOLYM_OK;
+        }
+    return VOLYM_OK;
+}
+
 }  // extern "C"
 
 static bool crop_active(const volym_ctx* c)
 {
     return c->crop_lo[0] != 0u || c->crop_lo[1] != 0u || c->crop_lo[2] != 0u || c->crop_hi[0] != c->nx || c->crop_hi[1] != c->ny || c->crop_hi[2] != c->nz;
 }
+
+static bool plane_active(const volym_ctx* c) { return c->clip_n[0] != 0 || c->clip_n[1] != 0 || c->clip_n[2] != 0; }
 
 static bool imp_croppable(const volym_ctx* c)
 {
@@ -305,11 +382,21 @@ static Derived importances_of(const volym_ctx* c)
     return {c->d_imp, c->d_imp0, nullptr, c->imp_bricked};
 }
 
-// the walk of the rewrite kernels over one box [box[0..2], box[3..5]) of a volume in the given layout; returns its items
-static uint64_t make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t box[6], CropSlab& s)
+// The part of the scene state the invariant depends on: crop box [lo, hi), clip plane (kept: n . t <= d) and mask (hidden[l] is
+// 0 or 1).
+struct SceneCut { uint32_t lo[3], hi[3]; int32_t n[3], d; uint8_t hidden[256]; };
+
+static bool same_plane(const SceneCut& a, const SceneCut& b) { return a.d == b.d && a.n[0] == b.n[0] && a.n[1] == b.n[1] && a.n[2] == b.n[2]; }
+
+// the walk of the rewrite kernels over one box [box[0..2], box[3..5]) of a volume in the given layout; returns its items.
+// moved_from: the box is that of a plane edit, and the walk also carries the plane the bytes were clipped to before.
+static uint64_t make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t box[6], const SceneCut* moved_from, CropSlab& s)
 {
     s = CropSlab{};
     for (int a = 0; a < 3; ++a) { s.lo[a] = box[a]; s.hi[a] = box[3 + a]; s.box_lo[a] = c->crop_lo[a]; s.box_hi[a] = c->crop_hi[a]; }
+    for (int a = 0; a < 3; ++a) { s.pn[a] = c->clip_n[a]; s.qn[a] = moved_from ? moved_from->n[a] : 0; }
+    s.pd = c->clip_d; s.qd = moved_from ? moved_from->d : 0;
+    s.planes = plane_active(c) || moved_from ? 1u : 0u;
     uint64_t items;
     if (bricked) {
         for (int a = 0; a < 3; ++a) { s.b_lo[a] = s.lo[a] >> 2; s.b_n[a] = ((s.hi[a] + 3u) >> 2) - s.b_lo[a]; }
@@ -327,14 +414,15 @@ static uint64_t make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t 
     return items;
 }
 
-// d.dst = (inside(c->crop) && !c->seg_hidden[label]) ? value(d.src) : 0 over one box of texels, on slot 0's stream.  flipped:
-// only the chunks that hold a texel of such a label are rewritten.  NULL: every chunk, by volym_crop_slab_kernel while no
-// segment is hidden (a context that hides nothing runs what it always ran), else by the kernel that reads the labels as well,
-// with every label marked flipped.
-static int rewrite(volym_ctx* c, const Derived& d, const uint32_t box[6], const uint8_t* flipped)
+// d.dst = (inside(c->crop) && kept by c->clip && !c->seg_hidden[label]) ? value(d.src) : 0 over one box of texels, on slot 0's
+// stream.  flipped: only the chunks that hold a texel of such a label are rewritten.  moved_from: only the chunks in which a
+// texel lies on different sides of that cut's plane and the context's.  Both NULL: every chunk, by volym_crop_slab_kernel while
+// no segment is hidden (a context that hides nothing runs what it always ran), else by the kernel that reads the labels as
+// well, with every label marked flipped.
+static int rewrite(volym_ctx* c, const Derived& d, const uint32_t box[6], const uint8_t* flipped, const SceneCut* moved_from)
 {
     CropSlab s;
-    const uint64_t items = make_crop_slab(c, d.bricked, box, s);
+    const uint64_t items = make_crop_slab(c, d.bricked, box, moved_from, s);
     if (items == 0u) return VOLYM_OK;
     LabelTable t = {}, m = {};
     if (d.table) std::memcpy(t.v, d.table, 256);
@@ -343,7 +431,13 @@ static int rewrite(volym_ctx* c, const Derived& d, const uint32_t box[6], const 
     const uint4* src = reinterpret_cast<const uint4*>(d.src);
     uint4* dst = reinterpret_cast<uint4*>(d.dst);
     const uint32_t bricked = d.bricked ? 1u : 0u, n_items = static_cast<uint32_t>(items);
-    if (!flipped && !mask_active(c)) {
+    if (moved_from) {
+        const bool masked = mask_active(c);
+        for (int l = 0; l < 256; ++l) m.v[l] = c->seg_hidden[l] ? 0u : 1u;
+        const auto kernel = d.table ? (masked ? volym_clip_plane_kernel<true, true> : volym_clip_plane_kernel<true, false>)
+                                    : (masked ? volym_clip_plane_kernel<false, true> : volym_clip_plane_kernel<false, false>);
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels), src, dst, t, m, s, c->nx, c->ny, c->nz, bricked, n_items);
+    } else if (!flipped && !mask_active(c)) {
         const auto kernel = d.table ? volym_crop_slab_kernel<true> : volym_crop_slab_kernel<false>;
         hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, src, dst, t, s, c->nx, c->ny, c->nz, bricked, n_items);
     } else {
@@ -408,13 +502,11 @@ static void crop_important_box(volym_ctx* c)
     for (int i = 0; i < c->n_slots(); ++i) set_reject_box(c, c->slots[i]->fp);
 }
 
-// The part of the scene state the invariant depends on: crop box [lo, hi) and mask (hidden[l] is 0 or 1).
-struct SceneCut { uint32_t lo[3], hi[3]; uint8_t hidden[256]; };
-
 static SceneCut current_cut(const volym_ctx* c)
 {
     SceneCut s;
-    for (int a = 0; a < 3; ++a) { s.lo[a] = c->crop_lo[a]; s.hi[a] = c->crop_hi[a]; }
+    for (int a = 0; a < 3; ++a) { s.lo[a] = c->crop_lo[a]; s.hi[a] = c->crop_hi[a]; s.n[a] = c->clip_n[a]; }
+    s.d = c->clip_d;
     std::memcpy(s.hidden, c->seg_hidden, sizeof s.hidden);
     return s;
 }
@@ -425,42 +517,64 @@ static SceneCut all_visible(SceneCut s)
     return s;
 }
 
-// the whole volume, nothing hidden: the bytes as they were uploaded
+// the whole volume, no plane, nothing hidden: the bytes as they were uploaded
 static SceneCut uncut(const volym_ctx* c)
 {
     SceneCut s = all_visible(current_cut(c));
     s.lo[0] = s.lo[1] = s.lo[2] = 0u;
     s.hi[0] = c->nx; s.hi[1] = c->ny; s.hi[2] = c->nz;
+    s.n[0] = s.n[1] = s.n[2] = s.d = 0;
     return s;
+}
+
+// The box inside both cuts' crop boxes that holds every texel their planes classify differently (outside `from`'s box a texel
+// of `to`'s lies in a slab).  moved false: there is no such texel.  A transition works it out once (two planes that keep the
+// same texels cost volym_clip_plane_box a pass over the rows of the box).
+struct PlaneMove { bool moved; uint32_t box[6]; };
+
+static PlaneMove plane_move(const SceneCut& from, const SceneCut& to)
+{
+    PlaneMove m = {};
+    if (same_plane(from, to)) return m;
+    uint32_t lo[3], hi[3], n = 0;
+    for (int a = 0; a < 3; ++a) { lo[a] = std::max(from.lo[a], to.lo[a]); hi[a] = std::max(std::min(from.hi[a], to.hi[a]), lo[a]); }
+    (void)volym_clip_plane_box(from.n, from.d, to.n, to.d, lo, hi, m.box, &n);
+    m.moved = n != 0u;
+    return m;
 }
 
 // Does some texel of a buffer that takes part (the importances; with vol the density too) differ between the two?  Not without
 // a volume (after a failed edit the bytes belong to no state and only volym_set_volume mends them), not for importances of other
-// dimensions than the volume's (they are never cut), not for the same box and flags that differ only in labels without voxels.
-static bool cuts_differ(const volym_ctx* c, const SceneCut& from, const SceneCut& to, bool vol)
+// dimensions than the volume's (they are never cut), not for the same box, planes that keep the same texels of it and flags that
+// differ only in labels without voxels.
+static bool cuts_differ(const volym_ctx* c, const SceneCut& from, const SceneCut& to, const PlaneMove& plane, bool vol)
 {
     if (!c->have_vol || !(vol || imp_croppable(c))) return false;
     for (int a = 0; a < 3; ++a) if (from.lo[a] != to.lo[a] || from.hi[a] != to.hi[a]) return true;
+    if (plane.moved) return true;
     for (int l = 0; l < 256; ++l) if (from.hidden[l] != to.hidden[l] && c->label_count[l] != 0u) return true;
     return false;
 }
 
 // The one function that keeps the invariant of context.hpp.  Precondition: the importances (with vol: and the density) hold it
-// for `from`.  Postcondition: they hold it for `to`, which is the context's crop box and mask, and everything derived from the
-// bytes is up to date.  Blocking set-up path; while `to` hides a label the caller has checked that the labels fit the volume.
-// Every chunk that is stored is stored by the full rule of `to`, so the two groups of boxes may overlap and their order does
-// not matter.  A failure before the first launch leaves the context as it was; one after it leaves bytes that belong to
+// for `from`.  Postcondition: they hold it for `to`, which is the context's crop box, clip plane and mask, and everything derived
+// from the bytes is up to date.  Blocking set-up path; while `to` hides a label the caller has checked that the labels fit the
+// volume.  Every chunk that is stored is stored by the full rule of `to`, so the three groups of boxes may overlap and their order
+// does not matter.  A failure before the first launch leaves the context as it was; one after it leaves bytes that belong to
 // neither state: the context then asks for volym_set_volume again (have_vol false), or, where only the importances were being
-// rewritten, for the importances.
-static int retarget(volym_ctx* c, const SceneCut& from, const SceneCut& to, bool vol)
+// rewritten, for the importances.  rewrote (if not NULL): whether any byte could differ, i.e. whether the transition ran.
+static int retarget(volym_ctx* c, const SceneCut& from, const SceneCut& to, bool vol, bool* rewrote = nullptr)
 {
-    const bool idle = !cuts_differ(c, from, to, vol);
+    const PlaneMove plane = plane_move(from, to);
+    const bool idle = !cuts_differ(c, from, to, plane, vol);
+    if (rewrote) *rewrote = !idle;
     if (!idle) {
         int rc = quiesce_slots(c);
         if (rc == VOLYM_OK) rc = ensure_uncropped_copies(c, vol);      // in stream order in front of the rewrites
         if (rc != VOLYM_OK) return rc;
     }
-    for (int a = 0; a < 3; ++a) { c->crop_lo[a] = to.lo[a]; c->crop_hi[a] = to.hi[a]; }
+    for (int a = 0; a < 3; ++a) { c->crop_lo[a] = to.lo[a]; c->crop_hi[a] = to.hi[a]; c->clip_n[a] = to.n[a]; }
+    c->clip_d = to.d;
     std::memcpy(c->seg_hidden, to.hidden, sizeof c->seg_hidden);
     if (idle) {
         crop_important_box(c);       // (host arithmetic: fresh importances on a plain context get their box and reject boxes here)
@@ -468,20 +582,23 @@ static int retarget(volym_ctx* c, const SceneCut& from, const SceneCut& to, bool
     }
     const auto work = [&]() -> int {
         // the slabs between the two boxes, then the boxes of the flipped labels inside both (outside `from`'s box a texel of
-        // `to`'s lies in a slab and has its final bytes already)
-        uint32_t boxes[6 + VOLYM_VISIBILITY_MAX_BOXES][6], n_slabs = 0, n_flipped = 0, lo[3], hi[3];
+        // `to`'s lies in a slab and has its final bytes already), then the box of the texels that change side of the plane
+        uint32_t boxes[6 + VOLYM_VISIBILITY_MAX_BOXES + 1][6], n_slabs = 0, n_flipped = 0, lo[3], hi[3];
         uint8_t flipped[256];
         (void)volym_crop_slabs(from.lo, from.hi, to.lo, to.hi, boxes, &n_slabs);
         for (int l = 0; l < 256; ++l) flipped[l] = from.hidden[l] != to.hidden[l];
         for (int a = 0; a < 3; ++a) { lo[a] = std::max(from.lo[a], to.lo[a]); hi[a] = std::max(std::min(from.hi[a], to.hi[a]), lo[a]); }
         (void)volym_visibility_boxes(flipped, c->label_count, c->label_box, lo, hi, boxes + n_slabs, &n_flipped);
-        const uint32_t n = n_slabs + n_flipped;
+        const uint32_t n_cut = n_slabs + n_flipped;
+        const uint32_t n = n_cut + (plane.moved ? 1u : 0u);
+        if (plane.moved) std::memcpy(boxes[n_cut], plane.box, sizeof plane.box);
         const bool imp = imp_croppable(c);
         int rc = VOLYM_OK;
         for (uint32_t i = 0; i < n; ++i) {
-            const uint8_t* f = i < n_slabs ? nullptr : flipped;
-            if (vol) rc = rewrite(c, density_of(c), boxes[i], f);
-            if (rc == VOLYM_OK && imp) rc = rewrite(c, importances_of(c), boxes[i], f);
+            const uint8_t* f = i < n_slabs || i >= n_cut ? nullptr : flipped;
+            const SceneCut* moved_from = i < n_cut ? nullptr : &from;
+            if (vol) rc = rewrite(c, density_of(c), boxes[i], f, moved_from);
+            if (rc == VOLYM_OK && imp) rc = rewrite(c, importances_of(c), boxes[i], f, moved_from);
             if (rc != VOLYM_OK) return rc;
         }
         if (vol && n != 0u) {
@@ -501,14 +618,13 @@ static int retarget(volym_ctx* c, const SceneCut& from, const SceneCut& to, bool
     return rc;
 }
 
-// d_imp has just been filled with complete importances: cut them to the scene's box and mask.  The work lists start over in
-// any case (the costs describe the old importances).
+// d_imp has just been filled with complete importances: cut them to the scene's box, plane and mask.  The work lists start over
+// in any case (the costs describe the old importances; a transition that ran has rebuilt them).
 static int cut_fresh_importances(volym_ctx* c)
 {
-    const SceneCut from = uncut(c), to = current_cut(c);
-    const bool idle = !cuts_differ(c, from, to, false);
-    int rc = retarget(c, from, to, false);
-    if (rc == VOLYM_OK && idle) rc = rebuild_lists(c);
+    bool rewrote = false;
+    int rc = retarget(c, uncut(c), current_cut(c), false, &rewrote);
+    if (rc == VOLYM_OK && !rewrote) rc = rebuild_lists(c);
     if (rc != VOLYM_OK) c->have_imp = false;
     return rc;
 }
@@ -563,15 +679,16 @@ static void important_texel_box(const uint8_t* imp, uint32_t nx, uint32_t ny, ui
     lo[0] = x0; lo[1] = y0; lo[2] = z0; hi[0] = x1; hi[1] = y1; hi[2] = z1;
 }
 
-// ---- C ABI: what each call makes of the scene's (box, mask) -----------------------------------------------------------
-//   volym_set_crop_box(lo, hi)                  current -> (lo, hi), current mask           density and importances
-//   volym_set_segment_visibility(v)             current -> current box, ~v                  density and importances
-//   volym_set_volume, before the upload         current -> whole volume, nothing hidden     importances (the density is replaced)
+// ---- C ABI: what each call makes of the scene's (box, plane, mask) ----------------------------------------------------
+//   volym_set_crop_box(lo, hi)                  current -> (lo, hi), current plane and mask density and importances
+//   volym_set_clip_plane(n, d)                  current -> current box and mask, (n, d)     density and importances
+//   volym_set_segment_visibility(v)             current -> current box and plane, ~v        density and importances
+//   volym_set_volume, before the upload         current -> whole volume, no plane, no mask  importances (the density is replaced)
 //   volym_set_labels, volym_set_importances,
-//     before they replace anything              current -> current box, nothing hidden      density and importances
+//     before they replace anything              current -> current box and plane, no mask   density and importances
 //   volym_set_importances and
 //     volym_set_segment_importances, after
-//     the new bytes are in d_imp                whole volume, nothing hidden -> current     importances
+//     the new bytes are in d_imp                whole volume, no plane, no mask -> current  importances
 
 extern "C" {
 
@@ -595,6 +712,28 @@ int volym_get_crop_box(volym_ctx* c, uint32_t lo[3], uint32_t hi[3])
     if (!lo || !hi) return fail(c, VOLYM_E_INVALID, "volym_get_crop_box: NULL output");
     if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_get_crop_box: no volume");
     for (int a = 0; a < 3; ++a) { lo[a] = c->crop_lo[a]; hi[a] = c->crop_hi[a]; }
+    return VOLYM_OK;
+}
+
+int volym_set_clip_plane(volym_ctx* c, const int32_t n[3], int32_t d)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!n) return fail(c, VOLYM_E_INVALID, "volym_set_clip_plane: NULL normal");
+    if (!valid_plane(n, d)) return fail(c, VOLYM_E_INVALID, "volym_set_clip_plane: need |n[a]| <= 4096 on every axis, and d == 0 with n == (0, 0, 0)");
+    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_set_clip_plane: no volume (volym_set_volume first)");
+    SceneCut to = current_cut(c);
+    for (int a = 0; a < 3; ++a) to.n[a] = n[a];
+    to.d = d;
+    return retarget(c, current_cut(c), to, true);
+}
+
+int volym_get_clip_plane(volym_ctx* c, int32_t n[3], int32_t* d)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!n || !d) return fail(c, VOLYM_E_INVALID, "volym_get_clip_plane: NULL output");
+    if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_get_clip_plane: no volume");
+    for (int a = 0; a < 3; ++a) n[a] = c->clip_n[a];
+    *d = c->clip_d;
     return VOLYM_OK;
 }
 
@@ -638,7 +777,8 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;
-    for (int a = 0; a < 3; ++a) c->crop_lo[a] = 0u;
+    for (int a = 0; a < 3; ++a) { c->crop_lo[a] = 0u; c->clip_n[a] = 0; }
+    c->clip_d = 0;
     c->crop_hi[0] = nx; c->crop_hi[1] = ny; c->crop_hi[2] = nz;
     c->bricked = want_bricked(c, nx, ny, nz);
     rc = build_macro_cells(c);             // (sets have_vol)
@@ -674,8 +814,8 @@ int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t 
     // that say which they are still exist
     int rc = retarget(c, current_cut(c), all_visible(current_cut(c)), true);
     if (rc != VOLYM_OK) return rc;
-    if (imp_from_labels(c) && crop_active(c) && imp_croppable(c) && !c->d_imp0) {
-        // the importances stay as they are, cropped, and the labels they were mapped from go: keep their uncropped bytes.  (A change
+    if (imp_from_labels(c) && (crop_active(c) || plane_active(c)) && imp_croppable(c) && !c->d_imp0) {
+        // the importances stay as they are, cropped and clipped, and the labels they were mapped from go: keep their uncropped bytes.  (A change
         // of the source, not of box or mask: it stands beside the transition, not in it.)
         rc = quiesce_slots(c);
         if (rc != VOLYM_OK) return rc;

@@ -1,6 +1,6 @@
 // The kernels of the scene-byte set-up path (scene_bytes.hip, the only unit that includes this header: a non-template
 // __global__ function is defined in exactly one unit): macro-cell maxima, the bricked layout, importances mapped from a
-// label volume, label statistics, and the crop box and segment visibility rewrites of density and importances.
+// label volume, label statistics, and the crop box, clip plane and segment visibility rewrites of density and importances.
 #pragma once
 
 #include "raymarch_device.h"
@@ -201,14 +201,43 @@ struct CropSlab {
     uint32_t box_lo[3], box_hi[3];  // the box the bytes are cropped to
     uint32_t run_len, runs_y, runs_z, chunks_per_run;   // linear walk: runs_y * runs_z runs of run_len bytes
     uint32_t b_lo[3], b_n[3];       // bricked walk: first brick and bricks per axis
+    // clip plane: texel (x, y, z) is kept iff pn . (x, y, z) <= pd; n = (0, 0, 0), d = 0 keeps every texel.  |n| <= 4096 and
+    // coordinates <= 4099 (a brick's padding; a linear chunk past the last voxel reaches z = nz <= 4096), so
+    // |n . t| <= 3 * 4096 * 4099 < 2^31: the sum is exact in 32 bits.
+    int32_t pn[3], pd;              // the plane the bytes are clipped to
+    int32_t qn[3], qd;              // the plane they were clipped to before (volym_clip_plane_kernel only)
+    uint32_t planes;                // 0: neither plane cuts, and the term is not evaluated
 };
 
-// Item i of the walk over slab s: its chunk k and `keep` (bit b: byte b of the chunk is a texel inside the box).  False: the item
-// has no chunk (a bricked chunk whose z is outside the slab, the spare chunk of a linear run).
-__device__ inline bool crop_chunk(const CropSlab& s, uint32_t i, uint32_t nx, uint32_t ny, uint64_t n, uint32_t bricked, uint32_t bx, uint32_t by,
-                                  uint64_t& k, uint32_t& keep)
+__device__ __forceinline__ int32_t plane_sum(const int32_t n[3], uint32_t x, uint32_t y, uint32_t z)
 {
-    keep = 0;
+    return n[0] * static_cast<int32_t>(x) + n[1] * static_cast<int32_t>(y) + n[2] * static_cast<int32_t>(z);
+}
+
+// bit 4 * r + j: texel (x0 + j, y0 + r, z) is kept by plane (n, d)
+__device__ __forceinline__ uint32_t plane_side_4x4(const int32_t n[3], int32_t d, uint32_t x0, uint32_t y0, uint32_t z)
+{
+    int32_t row = plane_sum(n, x0, y0, z);
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < 4u; ++r) {
+        int32_t t = row;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) { if (t <= d) m |= 1u << (4u * r + j); t += n[0]; }
+        row += n[1];
+    }
+    return m;
+}
+
+// Item i of the walk over slab s: its chunk k and `keep` (bit b: byte b of the chunk is a texel inside the box and on the kept
+// side of plane p).  MOVED: also `moved` (bit b: byte b is a texel inside the box that planes p and q classify differently).
+// False: the item has no chunk (a bricked chunk whose z is outside the slab, the spare chunk of a linear run).
+template <bool MOVED>
+__device__ inline bool crop_chunk(const CropSlab& s, uint32_t i, uint32_t nx, uint32_t ny, uint64_t n, uint32_t bricked, uint32_t bx, uint32_t by,
+                                  uint64_t& k, uint32_t& keep, uint32_t& moved)
+{
+    uint32_t inbox = 0, side_p = 0xffffu, side_q = 0xffffu;
+    keep = moved = 0;
     if (bricked) {
         const uint32_t zz = i & 3u, b = i >> 2;
         const uint32_t bxi = s.b_lo[0] + b % s.b_n[0], byi = s.b_lo[1] + (b / s.b_n[0]) % s.b_n[1], bzi = s.b_lo[2] + b / (s.b_n[0] * s.b_n[1]);
@@ -219,7 +248,11 @@ __device__ inline bool crop_chunk(const CropSlab& s, uint32_t i, uint32_t nx, ui
         if (z >= s.box_lo[2] && z < s.box_hi[2]) {
             uint32_t row = 0;
             for (uint32_t j = 0; j < 4u; ++j) { const uint32_t x = bxi * 4u + j; if (x >= s.box_lo[0] && x < s.box_hi[0]) row |= 1u << j; }
-            for (uint32_t r = 0; r < 4u; ++r) { const uint32_t y = byi * 4u + r; if (y >= s.box_lo[1] && y < s.box_hi[1]) keep |= row << (4u * r); }
+            for (uint32_t r = 0; r < 4u; ++r) { const uint32_t y = byi * 4u + r; if (y >= s.box_lo[1] && y < s.box_hi[1]) inbox |= row << (4u * r); }
+            if (s.planes && inbox) {
+                side_p = plane_side_4x4(s.pn, s.pd, bxi * 4u, byi * 4u, z);
+                if (MOVED) side_q = plane_side_4x4(s.qn, s.qd, bxi * 4u, byi * 4u, z);
+            }
         }
     } else {
         const uint32_t ci = i % s.chunks_per_run, r = i / s.chunks_per_run;
@@ -231,11 +264,32 @@ __device__ inline bool crop_chunk(const CropSlab& s, uint32_t i, uint32_t nx, ui
         uint32_t z = static_cast<uint32_t>(o / slice);
         const uint32_t rem = static_cast<uint32_t>(o - z * slice);
         uint32_t y = rem / nx, x = rem - y * nx;
-        for (uint32_t j = 0; j < 16u; ++j) {
-            if (o + j < n && x >= s.box_lo[0] && x < s.box_hi[0] && y >= s.box_lo[1] && y < s.box_hi[1] && z >= s.box_lo[2] && z < s.box_hi[2]) keep |= 1u << j;
-            if (++x == nx) { x = 0; if (++y == ny) { y = 0; ++z; } }
+        if (!s.planes) {
+            for (uint32_t j = 0; j < 16u; ++j) {
+                if (o + j < n && x >= s.box_lo[0] && x < s.box_hi[0] && y >= s.box_lo[1] && y < s.box_hi[1] && z >= s.box_lo[2] && z < s.box_hi[2]) inbox |= 1u << j;
+                if (++x == nx) { x = 0; if (++y == ny) { y = 0; ++z; } }
+            }
+        } else {
+            // the chunk may wrap a row (and a slice): the running sums step by n[0] with x and start over with the row
+            int32_t tp = plane_sum(s.pn, x, y, z), tq = MOVED ? plane_sum(s.qn, x, y, z) : 0;
+            side_p = side_q = 0;
+            for (uint32_t j = 0; j < 16u; ++j) {
+                if (o + j < n && x >= s.box_lo[0] && x < s.box_hi[0] && y >= s.box_lo[1] && y < s.box_hi[1] && z >= s.box_lo[2] && z < s.box_hi[2]) inbox |= 1u << j;
+                if (tp <= s.pd) side_p |= 1u << j;
+                if (MOVED && tq <= s.qd) side_q |= 1u << j;
+                tp += s.pn[0];
+                if (MOVED) tq += s.qn[0];
+                if (++x == nx) {
+                    x = 0;
+                    if (++y == ny) { y = 0; ++z; }
+                    tp = plane_sum(s.pn, x, y, z);
+                    if (MOVED) tq = plane_sum(s.qn, x, y, z);
+                }
+            }
         }
     }
+    keep = inbox & side_p;
+    if (MOVED) moved = inbox & (side_p ^ side_q);
     return true;
 }
 
@@ -271,8 +325,8 @@ __global__ __launch_bounds__(256) void volym_crop_slab_kernel(const uint4* __res
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
         uint64_t k;
-        uint32_t keep;
-        if (!crop_chunk(s, i, nx, ny, n, bricked, bx, by, k, keep)) continue;
+        uint32_t keep, moved;
+        if (!crop_chunk<false>(s, i, nx, ny, n, bricked, bx, by, k, keep, moved)) continue;
         dst[k] = keep ? crop_chunk_value<TABLE>(src[k], keep, s_tab) : make_uint4(0u, 0u, 0u, 0u);
     }
 }
@@ -300,8 +354,8 @@ __global__ __launch_bounds__(256) void volym_visibility_kernel(const uint4* __re
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
         uint64_t k;
-        uint32_t keep;
-        if (!crop_chunk(s, i, nx, ny, n, bricked, bx, by, k, keep)) continue;
+        uint32_t keep, moved;
+        if (!crop_chunk<false>(s, i, nx, ny, n, bricked, bx, by, k, keep, moved)) continue;
         const uint4 lv = labels[k];
         const uint32_t l[4] = {lv.x, lv.y, lv.z, lv.w};
         uint32_t flipped = 0, visible = 0;
@@ -313,6 +367,43 @@ __global__ __launch_bounds__(256) void volym_visibility_kernel(const uint4* __re
         }
         if (!(flipped & 2u)) continue;
         keep &= visible;
+        dst[k] = keep ? crop_chunk_value<TABLE>(TABLE ? lv : src[k], keep, s_tab) : make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// ---- clip plane on the device (volym_set_clip_plane) ------------------------------------------------------------------------
+// dst = (inside(box) && kept by plane p && visible[label]) ? value(src) : 0 over the box of texels that planes q (before) and p
+// (now) classify differently (volym_clip_plane_box), walked as the two kernels above walk theirs.  A chunk in which no texel
+// inside the box changes side is neither loaded nor stored: dst already holds there what the rule gives -- the analogue of the
+// visibility kernel's chunk without a flipped label.  A chunk that is stored is stored whole by the new rule.  MASKED: a segment
+// is hidden, and the labels are read as volym_visibility_kernel reads them (mask.v[l] bit 0 = label l is visible).  TABLE: the
+// labels are the source themselves (src == labels, value = table[label]).
+template <bool TABLE, bool MASKED>
+__global__ __launch_bounds__(256) void volym_clip_plane_kernel(const uint4* __restrict__ labels, const uint4* __restrict__ src, uint4* __restrict__ dst,
+                                                               LabelTable table, LabelTable mask, CropSlab s, uint32_t nx, uint32_t ny, uint32_t nz,
+                                                               uint32_t bricked, uint32_t n_items)
+{
+    __shared__ uint8_t s_mask[MASKED ? 256 : 1];
+    __shared__ uint8_t s_tab[TABLE ? 256 : 1];
+    if (MASKED) s_mask[threadIdx.x] = mask.v[threadIdx.x];
+    if (TABLE) s_tab[threadIdx.x] = table.v[threadIdx.x];
+    if (MASKED || TABLE) __syncthreads();
+    const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
+    const uint32_t bx = brick_count(nx), by = brick_count(ny);
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
+        uint64_t k;
+        uint32_t keep, moved;
+        if (!crop_chunk<true>(s, i, nx, ny, n, bricked, bx, by, k, keep, moved)) continue;
+        if (!moved) continue;
+        uint4 lv = make_uint4(0u, 0u, 0u, 0u);
+        if (keep && (MASKED || TABLE)) lv = labels[k];
+        if (MASKED) {
+            const uint32_t l[4] = {lv.x, lv.y, lv.z, lv.w};
+            uint32_t visible = 0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) visible |= (s_mask[(l[j >> 2] >> (8 * (j & 3))) & 0xffu] & 1u) << j;
+            keep &= visible;
+        }
         dst[k] = keep ? crop_chunk_value<TABLE>(TABLE ? lv : src[k], keep, s_tab) : make_uint4(0u, 0u, 0u, 0u);
     }
 }

@@ -42,6 +42,8 @@ struct Options {
     bool debug = false;
     bool crop = false;             // --crop x0,y0,z0,x1,y1,z1: crop box in unit-cube coordinates (run simple)
     float crop_lo[3] = {0.0f, 0.0f, 0.0f}, crop_hi[3] = {1.0f, 1.0f, 1.0f};
+    bool clip = false;             // --clip-plane nx,ny,nz,px,py,pz: clip plane in unit-cube coordinates (run simple)
+    float clip_normal[3] = {0.0f, 0.0f, 0.0f}, clip_point[3] = {0.5f, 0.5f, 0.5f};
     std::vector<uint8_t> hide;     // --hide 3,4: label values of the segments to hide (run simple)
 };
 
@@ -161,6 +163,7 @@ int run_simple(const Options& o)
     state.update();
     Simple demo = Simple::init(ctx, state, assets);
     if (o.crop) demo.set_crop(ctx, assets, o.crop_lo, o.crop_hi);
+    if (o.clip) demo.set_clip_plane(ctx, assets, o.clip_normal, o.clip_point);
     if (!o.hide.empty()) demo.set_hidden(ctx, assets, o.hide);
     demo.update_gpu_state(ctx, state);
     demo.compute_pass(ctx);
@@ -203,6 +206,13 @@ int main(int argc, char** argv)
                 for (int k = 0; k < 3; ++k) { o.crop_lo[k] = f[k]; o.crop_hi[k] = f[3 + k]; }
                 o.crop = true;
             }
+            else if (a == "--clip-plane") {
+                const std::string v = next();
+                float f[6];
+                if (std::sscanf(v.c_str(), "%f,%f,%f,%f,%f,%f", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5]) != 6) throw Error(VOLYM_E_INVALID, "--clip-plane: nx,ny,nz,px,py,pz (normal and point, unit-cube coordinates)");
+                for (int k = 0; k < 3; ++k) { o.clip_normal[k] = f[k]; o.clip_point[k] = f[3 + k]; }
+                o.clip = true;
+            }
             else if (a == "--hide") {
                 const std::string v = next();
                 size_t pos = 0;
@@ -217,7 +227,7 @@ int main(int argc, char** argv)
                     pos = comma + 1u;
                 }
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--hide l,l,...]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

@@ -124,6 +124,19 @@ class GpuContext:
         self._ck(_lib.lib().volym_get_crop_box(self.handle, lo3, hi3))
         return tuple(int(v) for v in lo3), tuple(int(v) for v in hi3)
 
+    def set_clip_plane(self, n, d):
+        """Clip plane in texels of the prepared volume: texel (x, y, z) is kept iff n . (x, y, z) <= d, and density and
+        importances of the others count as 0 from the next compute pass on; ((0, 0, 0), 0) lifts the plane.  No upload; the
+        device rewrites the chunks in which a texel changes side."""
+        n, d = scene.check_clip_plane(n, d)
+        self._ck(_lib.lib().volym_set_clip_plane(self.handle, (C.c_int32 * 3)(*n), d))
+
+    def clip_plane(self):
+        """(n, d) of the current clip plane; ((0, 0, 0), 0) when there is none."""
+        n3, d = (C.c_int32 * 3)(), C.c_int32(0)
+        self._ck(_lib.lib().volym_get_clip_plane(self.handle, n3, C.byref(d)))
+        return tuple(int(v) for v in n3), int(d.value)
+
     def set_segment_visibility(self, visible):
         """256 flags, one per label value (nonzero = visible): density and importances of the hidden segments count as 0 from
         the next compute pass on.  Needs the labels on the device (set_labels).  No upload; the device rewrites the texels
@@ -355,6 +368,7 @@ class Simple(ComputeDemo):
         """BaseDemo::update_gpu_state (src/demos/pipeline.rs:208-212)"""
         ctx.update(state.camera_uniforms(), state.parameter_uniforms())
         self._records_for = None        # (highlight: the pick records of the old view are stale)
+        self._eye = tuple(float(v) for v in state.camera.position)      # (clip_at: the plane faces the eye)
 
     def compute_pass(self, ctx):
         """BaseDemo::compute_pass -> DemoPipeline::compute_pass (src/demos/pipeline.rs:62-102, :214-225)"""
@@ -367,6 +381,28 @@ class Simple(ComputeDemo):
         ctx.set_crop_box(lo, hi)
         self._records_for = None
         return lo, hi
+
+    def set_clip_plane(self, ctx, normal, point):
+        """Oblique clip plane through `point` with the given normal, both in the unit-cube coordinates set_crop takes: what lies
+        on the side the normal points to is cut away (scene.clip_plane_texels).  normal=None lifts the plane.  Returns the
+        integer plane (n, d)."""
+        n, d = ((0, 0, 0), 0) if normal is None else scene.clip_plane_texels(normal, point, self.dims)
+        ctx.set_clip_plane(n, d)
+        self._records_for = None
+        return n, d
+
+    def clip_at(self, ctx, x, y, alpha_min=0.5):
+        """Click to cut: pick pixel (x, y), then set the clip plane through the picked texel's centre with the normal pointing
+        from there to the eye, so that everything between the eye and the clicked point is cut away and the texel itself stays.
+        Returns the plane (n, d), or None when the pixel shows nothing (the plane then stays as it is)."""
+        p = self.pick(ctx, x, y, alpha_min)
+        if p["status"] != "hit":
+            return None
+        n, _ = scene.clip_plane_texels([e - q for e, q in zip(self._eye, p["pos"])], p["pos"], self.dims)
+        d = sum(a * t for a, t in zip(n, p["texel"]))       # exactly through the texel: it is kept
+        ctx.set_clip_plane(n, d)
+        self._records_for = None
+        return n, d
 
     def set_hidden(self, ctx, hidden):
         """Hide the given segments and show all others (an editor's "hide the cup so that I can see the lobster").  `hidden`:
@@ -419,7 +455,7 @@ class Simple(ComputeDemo):
     def highlight(self, ctx, segments, ring_rgba=(255, 255, 0, 255), fill_rgba=(255, 255, 0, 48), radius=2, alpha_min=0.5, target_ptr=None):
         """Outline and tint the given segments (names, ids or label values) in the frame of the latest compute pass: one outline
         pass over the records of a whole-frame pick pass, which runs only if the demo has none for the current view and scene
-        (update_gpu_state, set_crop, set_hidden, set_segments and set_labels make the records stale).  A hover that moves to
+        (update_gpu_state, set_crop, set_clip_plane, set_hidden, set_segments and set_labels make the records stale).  A hover that moves to
         another segment costs the outline pass alone.  The image goes to target_ptr, or to the context's own target
         (ctx.read_outline()).  Returns the selected label values."""
         values = self._label_values(segments)

@@ -41,6 +41,7 @@ SIGNATURES = {
     "volym_mgpu_set_labels": (C.c_int, [_mg, _u8p, C.c_uint32, C.c_uint32, C.c_uint32]),
     "volym_mgpu_set_segment_importances": (C.c_int, [_mg, _u8p]),
     "volym_mgpu_set_crop_box": (C.c_int, [_mg, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_mgpu_set_clip_plane": (C.c_int, [_mg, C.POINTER(C.c_int32), C.c_int32]),
     "volym_mgpu_set_segment_visibility": (C.c_int, [_mg, _u8p]),
     "volym_mgpu_set_transfer_function": (C.c_int, [_mg, _u8p, C.c_uint32]),
     "volym_mgpu_set_option": (C.c_int, [_mg, C.c_int, C.c_int]),
@@ -146,6 +147,11 @@ class MultiGpu:
         """Crop box in texels of the prepared volume (lo inclusive, hi exclusive), on every local rank."""
         lo3, hi3 = (C.c_uint32 * 3)(*[int(v) for v in lo]), (C.c_uint32 * 3)(*[int(v) for v in hi])
         self._ck(lib().volym_mgpu_set_crop_box(self._h, lo3, hi3))
+
+    def set_clip_plane(self, n, d):
+        """Clip plane in texels of the prepared volume (kept: n . (x, y, z) <= d; (0, 0, 0), 0 lifts it), on every local rank."""
+        n, d = scene.check_clip_plane(n, d)
+        self._ck(lib().volym_mgpu_set_clip_plane(self._h, (C.c_int32 * 3)(*n), d))
 
     def set_segment_visibility(self, visible):
         """256 flags, one per label value (nonzero = visible), on every local rank."""

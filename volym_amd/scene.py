@@ -279,6 +279,59 @@ def crop_volume(prepared, dims, lo, hi):
     return out.ravel()
 
 
+CLIP_PLANE_MAX = 4096              # VOLYM_CLIP_PLANE_MAX: largest |coefficient| of a clip plane's normal
+
+
+def check_clip_plane(n, d):
+    """A clip plane in texels of the prepared volume: texel (x, y, z) is kept iff n[0]*x + n[1]*y + n[2]*z <= d.  Integers with
+    |n[a]| <= 4096 and d in int32; n == (0, 0, 0) only with d == 0 ("no plane").  Returns ((n0, n1, n2), d)."""
+    try:
+        given = list(n)
+        n, offset = [int(v) for v in given], int(d)
+        if len(n) != 3 or any(v != i for v, i in zip(given, n)) or offset != d:
+            raise TypeError
+        d = offset
+    except (TypeError, ValueError):
+        raise ValueError("a clip plane is a triple of integer coefficients and an integer offset")
+    if any(abs(v) > CLIP_PLANE_MAX for v in n):
+        raise ValueError("clip plane: need |n| <= %d on every axis, got %r" % (CLIP_PLANE_MAX, tuple(n)))
+    if not -2 ** 31 <= d < 2 ** 31:
+        raise ValueError("clip plane: d = %d is not a 32-bit integer" % d)
+    if n == [0, 0, 0] and d != 0:
+        raise ValueError("clip plane: the zero normal means no plane and goes with d == 0 only (to keep nothing: n = (1, 0, 0), d = -1)")
+    return tuple(n), d
+
+
+def clip_plane_texels(normal, point, dims):
+    """A plane of the unit cube (the cube the camera orbits; y as the prepared, flipped volume has it) -> integers for
+    check_clip_plane.  The kept side is normal . (centre - point) <= 0 with texel centres at (x + 0.5) / n.  In float64:
+    g_i = normal_i / dims_i, k = 4096 / max|g_i|, n_i = floor(g_i * k + 0.5), d = floor(sum n_i * (point_i * dims_i - 0.5)).
+    A zero normal raises ValueError."""
+    if len(normal) != 3 or len(point) != 3 or len(dims) != 3:
+        raise ValueError("a clip plane is a normal and a point of the unit cube, three coordinates each")
+    g = np.array([float(v) for v in normal], np.float64) / np.array([float(v) for v in dims], np.float64)
+    top = float(np.abs(g).max())
+    if not np.isfinite(g).all() or top == 0.0:
+        raise ValueError("clip plane: the normal must be finite and not zero")
+    a = np.floor(g * (CLIP_PLANE_MAX / top) + 0.5)
+    p = np.array([float(v) for v in point], np.float64) * np.array([float(v) for v in dims], np.float64) - 0.5
+    return check_clip_plane([int(v) for v in a], int(np.floor(float((a * p).sum()))))
+
+
+def clip_volume(prepared, dims, n, d):
+    """The definition of the clip plane: a copy of the prepared bytes (density or importances) with every texel that is not
+    kept (n . (x, y, z) > d) set to 0.  Composes with crop_volume and hide_segments."""
+    n, d = check_clip_plane(n, d)
+    nx, ny, nz = (int(v) for v in dims)
+    out = np.array(prepared, np.uint8).reshape(nz, ny, nx)            # (a copy)
+    xy = n[0] * np.arange(nx, dtype=np.int64)[None, :] + n[1] * np.arange(ny, dtype=np.int64)[:, None]
+    kept = np.empty((ny, nx), bool)
+    for z in range(nz):                                               # a slice at a time: the sums of a whole 1024^3 are 8 GiB
+        np.less_equal(xy, d - n[2] * z, out=kept)
+        np.multiply(out[z], kept, out=out[z])
+    return out.ravel()
+
+
 def check_selection(selected):
     """An outline selection: 256 flags, one per label value, nonzero = selected.  Returns np.uint8[256] of 0 / 1."""
     return check_segment_visibility(selected)
