@@ -439,6 +439,71 @@ int   volym_read_outline(volym_ctx* ctx, uint8_t* out);
 /* The context's own target after the latest pass into it, NULL before any. */
 void* volym_outline_device_ptr(volym_ctx* ctx);
 
+/* --- slice (new; the reference has none) ------------------------------------------------------------------------------ */
+/* A plane through the volume that shows the bytes of the scene themselves, with the segments as a colour overlay and the texels
+ * the cuts remove marked: the view beside the 3-D picture.  It reads only the bytes of the scene and writes only its target.
+ *   The rule (integers only; scene.slice_frame of the Python package is its host twin, equal in every byte).  A slice is an affine
+ * map from output pixels to 16.16 fixed-point texel coordinates, the texel coordinates volym_set_crop_box, volym_set_clip_plane
+ * and the pick records use; texel x covers [x, x + 1), so its centre is (x << 16) + 0x8000.  For output pixel (i, j):
+ * p[a] = origin[a] + i * du[a] + j * dv[a] over the integers, t[a] = floor(p[a] / 65536) (an arithmetic shift).  The pixel is INSIDE
+ * iff 0 <= t[a] < n[a] on every axis; nothing is clamped, and an outside pixel is `background`, unchanged.  A slice is VALID only
+ * if its four corner positions (i = 0 | width - 1, j = 0 | height - 1), over the integers, have every component in [-2^30, 2^30);
+ * p is affine, so every pixel of a valid slice is in that range as well.
+ *   An inside pixel is composed in this order.  (1) base, from byte b of texel t: DENSITY (b, b, b, 255) with b the density; TF the
+ * r, g, b of texel (b * tf_n) >> 8 of the table volym_set_transfer_function received (its RGBA8 bytes, no filtering) with alpha
+ * 255, b the density; IMPORTANCE (m, m, m, 255) with m the importance byte as the march reads it.  The density is the scene's as
+ * it stands (box, plane and mask applied); with UNCUT it is the uncut copy when the context holds one (from the first cut on),
+ * else the same bytes.  IMPORTANCE with UNCUT is invalid: the importances' uncut source is not one buffer.  (2) LABELS: with
+ * l = label(t) and col = palette[l], col is blended over the base with A = col[3] by the outline's formula (at volym_outline);
+ * A = 0 leaves the base.  (3) MARK_CUT: cut_rgba is blended, by the same formula, over every texel the context's current cut
+ * state removes: a texel outside the crop box, or with clip_n . t > clip_d under a plane, or with a hidden label while labels of
+ * the volume's dimensions are on the device.  The predicate decides, not the bytes: a removed texel needs no non-zero byte. */
+enum { VOLYM_SLICE_DENSITY = 0, VOLYM_SLICE_TF = 1, VOLYM_SLICE_IMPORTANCE = 2 };          /* mode */
+enum { VOLYM_SLICE_UNCUT = 1, VOLYM_SLICE_LABELS = 2, VOLYM_SLICE_MARK_CUT = 4 };          /* flags */
+typedef struct volym_slice {
+    int32_t  origin[3];         /* 16.16: position of output pixel (0, 0) */
+    int32_t  du[3], dv[3];      /* 16.16: step per pixel to the right / per row down */
+    uint32_t width, height;     /* 1..8192 each */
+    uint32_t mode, flags;
+    uint8_t  background[4];     /* pixels whose texel lies outside the volume */
+    uint8_t  cut_rgba[4];       /* MARK_CUT */
+    uint8_t  palette[256][4];   /* LABELS: colour per label value, alpha = strength */
+} volym_slice;                  /* 1084 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_slice) == 1084, "volym_slice is 1084 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_slice) == 1084, "volym_slice is 1084 bytes");
+#endif
+/* Enqueue only: one kernel on the first slot's stream, where the pick passes go (a caller's stream when one is set).  The output
+ * is width * height * 4 bytes, row-major.  target_rgba8 == NULL: a target the context owns (volym_read_slice,
+ * volym_slice_device_ptr); it grows to the largest slice asked for so far, and the call blocks only when it has to grow, as
+ * volym_pick_pass does for its records.  Apart from that growth there is no allocation, no synchronisation and no copy: palette
+ * and transfer function travel with the launch as kernel arguments.
+ *   It needs no volym_update and no frame: it reads only the bytes of the scene, which only blocking set-up calls change, and
+ * those idle every slot's stream first.  So with VOLYM_OPT_FRAMES_IN_FLIGHT = 2 it needs no events, and a frame enqueued before
+ * or after it is byte for byte the frame without it.  It works on a sharded context, since every rank holds the whole volume; the
+ * native multi-GPU loop has no forward for it.  The labels may sit in a different device layout than the volume.
+ *   VOLYM_E_INVALID: NULL ctx or slice, an unknown mode or flag bit, IMPORTANCE with UNCUT, a size outside 1..8192, an invalid
+ * corner (volym_slice_check).  VOLYM_E_STATE: no volume; LABELS without labels of the volume's dimensions on the device;
+ * IMPORTANCE without importances of the volume's dimensions; TF without a transfer function. */
+int   volym_slice_pass(volym_ctx* ctx, const volym_slice* slice, void* target_rgba8);
+/* Blocks; width * height * 4 bytes of the latest pass into the context's own target.  VOLYM_E_STATE before any such pass. */
+int   volym_read_slice(volym_ctx* ctx, uint8_t* out);
+/* The context's own target after the latest pass into it, NULL before any.  A later, larger slice may move it. */
+void* volym_slice_device_ptr(volym_ctx* ctx);
+/* The validity rules above, without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, an unknown mode or flag bit, IMPORTANCE
+ * with UNCUT, a size outside 1..8192 or a corner outside [-2^30, 2^30).  Pure host arithmetic. */
+int volym_slice_check(const volym_slice* slice);
+/* Geometry and size of the slice normal to `axis` (0 = x, 1 = y, 2 = z) through texel `index` of a dims[0] x dims[1] x dims[2]
+ * volume: one texel per pixel, through texel centres.  z: u = +x, v = +y.  y: u = +x, v = +z.  x: u = +y, v = +z.  It writes
+ * origin, du, dv, width and height and leaves mode, flags and colours alone.  VOLYM_E_INVALID for NULL, an axis outside 0..2,
+ * index >= dims[axis], an in-plane dimension outside 1..8192 or an index of 16384 or more (its centre lies beyond 2^30).  Pure
+ * host arithmetic. */
+int volym_slice_axis(int axis, uint32_t index, const uint32_t dims[3], volym_slice* out);
+/* The map itself, for click-on-slice: the texel t of output pixel (i, j), inside the volume or not.  VOLYM_E_INVALID for NULL
+ * or a pixel outside width x height.  Pure host arithmetic. */
+int volym_slice_texel(const volym_slice* slice, uint32_t i, uint32_t j, int32_t t[3]);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

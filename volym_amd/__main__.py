@@ -13,6 +13,9 @@ run simple: renders the interactive default view (src/state.rs:41-55) once and w
 like the reference's `P` key (src/state.rs:85-113).  --pick X,Y[,ALPHA] then prints what that pixel shows (segment, texel,
 depth) as one JSON line.  --outline NAME[,NAME...] (segment names, ids or label values) and --outline-at X,Y (the segment under that
 pixel) write the annotated image instead: a ring round the segments and a tint over them (demo.Simple.highlight).
+--slice AXIS,INDEX writes the slice view beside the frame -- the plane normal to x, y or z through texel INDEX, transfer-function
+colours, segments overlaid, cut texels tinted (demo.Simple.slice) -- as <screenshot>_slice_<axis>.png; --slice-at X,Y the three
+orthogonal slices through the texel pixel (X, Y) shows.
 """
 import argparse
 import csv
@@ -181,6 +184,19 @@ def _outline_at_arg(text, flag="--outline-at"):
     return x, y
 
 
+def _slice_arg(text):
+    """--slice z,128 -> ("z", 128)"""
+    v = [t.strip() for t in text.split(",")]
+    if len(v) != 2 or v[0] not in ("x", "y", "z") or not v[1].isdigit():
+        raise SystemExit("--slice: AXIS,INDEX -- x, y or z and a texel index along it")
+    return v[0], int(v[1])
+
+
+def _slice_path(path, axis):
+    stem = path[:-4] if path.lower().endswith(".png") else path
+    return "%s_slice_%s.png" % (stem, axis)
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -216,9 +232,26 @@ def run_simple(args):
             raise SystemExit("--outline: %s" % e)
         if outlined is not None:
             frame = ctx.read_outline()      # the PNG is the annotated image
+        slices, sliced_at = {}, None
+        try:
+            if getattr(args, "slice", None):
+                axis, index = _slice_arg(args.slice)
+                d.slice(ctx, axis, index, mode=_lib.SLICE_TF)
+                slices[axis] = ctx.read_slice()
+            if getattr(args, "slice_at", None):
+                sliced_at = d.slices_at(ctx, *_outline_at_arg(args.slice_at, "--slice-at"), mode=_lib.SLICE_TF)
+                slices.update(sliced_at.pop("slices") or {})
+        except ValueError as e:
+            raise SystemExit("--slice: %s" % e)
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    for axis, img in sorted(slices.items()):
+        image.write_png(_slice_path(path, axis), img)
+        print("slice %s: %dx%d -> %s" % (axis, img.shape[1], img.shape[0], _slice_path(path, axis)))
+    if sliced_at is not None:
+        import json
+        print(json.dumps(sliced_at))   # one line: the pick the three slices of --slice-at go through
     if clipped is not None:
         import json
         print(json.dumps(clipped))     # one line: the plane --clip-at set (null: the pixel shows nothing)
@@ -328,6 +361,8 @@ def main(argv=None):
     run.add_argument("--pick", help="X,Y[,ALPHA]: after the frame, print what pixel (X, Y) shows as one JSON line (segment, texel, depth)")
     run.add_argument("--outline", help="NAME[,NAME...]: segment names, ids or label values to outline and tint; the PNG is the annotated image")
     run.add_argument("--outline-at", help="X,Y: outline the segment pixel (X, Y) shows; the PNG is the annotated image")
+    run.add_argument("--slice", help="AXIS,INDEX: also write the slice normal to x, y or z through texel INDEX as <screenshot>_slice_<axis>.png")
+    run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359
     b.add_argument("--secs", type=float, default=0.25, help="GPU seconds per trial (the reference uses 2 s of wall clock)")

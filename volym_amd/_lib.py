@@ -82,6 +82,24 @@ class Outline(C.Structure):
     ]
 
 
+SLICE_DENSITY, SLICE_TF, SLICE_IMPORTANCE = 0, 1, 2           # volym_slice.mode
+SLICE_UNCUT, SLICE_LABELS, SLICE_MARK_CUT = 1, 2, 4            # volym_slice.flags
+
+
+class Slice(C.Structure):
+    """volym_slice (include/volym_hip.h): geometry, mode, flags and colours of one slice pass, 1084 bytes"""
+    _fields_ = [
+        ("origin", C.c_int32 * 3),
+        ("du", C.c_int32 * 3),
+        ("dv", C.c_int32 * 3),
+        ("width", C.c_uint32), ("height", C.c_uint32),
+        ("mode", C.c_uint32), ("flags", C.c_uint32),
+        ("background", C.c_uint8 * 4),
+        ("cut_rgba", C.c_uint8 * 4),
+        ("palette", (C.c_uint8 * 4) * 256),
+    ]
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -197,6 +215,12 @@ SIGNATURES = {
     "volym_outline_pass": (C.c_int, [_ctx, C.POINTER(Outline), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
     "volym_read_outline": (C.c_int, [_ctx, _u8p]),
     "volym_outline_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_slice_pass": (C.c_int, [_ctx, C.POINTER(Slice), C.c_void_p]),
+    "volym_read_slice": (C.c_int, [_ctx, _u8p]),
+    "volym_slice_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_slice_check": (C.c_int, [C.POINTER(Slice)]),
+    "volym_slice_axis": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(Slice)]),
+    "volym_slice_texel": (C.c_int, [C.POINTER(Slice), C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

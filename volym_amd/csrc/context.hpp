@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI; pick.hip: the pick march; outline.hip: the outline pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -187,6 +187,12 @@ struct volym_ctx {
     hipEvent_t outline_ev[2] = {};           // frame of the other slot -> pass, pass -> the other slot's next work
     bool frame_rendered = false;             // some volym_compute_pass has been enqueued
 
+    // slice passes (volym_slice_pass, slice.hip): the context's own target, grown to the largest slice asked for so far; written on
+    // slot 0's stream
+    uint32_t* d_slice = nullptr;
+    size_t slice_capacity = 0;               // pixels d_slice holds
+    uint32_t slice_w = 0, slice_h = 0;       // size of the latest pass into d_slice (0: none yet)
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -237,6 +243,8 @@ void set_reject_box(const volym_ctx* c, FrameParams& fp);
 int launch_pick(volym_ctx* c, FrameSlot& s, const uint32_t rect[4], float alpha_min, void* out);
 // outline.hip: what the context keeps for the outline pass (every stream idle)
 void free_outline(volym_ctx* c);
+// slice.hip: what the context keeps for the slice pass (every stream idle)
+void free_slice(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 

@@ -66,6 +66,18 @@ struct Highlight {
     void* target_rgba8 = nullptr;            // device memory of W * H * 4 bytes; NULL: the context's own target (volym_read_outline)
 };
 
+// How Simple::slice draws: what the plane shows, the overlays, their colours, and where the image goes.
+struct SliceView {
+    uint32_t mode = VOLYM_SLICE_DENSITY;     // VOLYM_SLICE_DENSITY, VOLYM_SLICE_TF or VOLYM_SLICE_IMPORTANCE
+    bool labels = true;                      // the segments as a colour overlay (needs label bytes in the assets)
+    bool mark_cut = true;                    // tint the texels the crop box, the clip plane and the hidden segments remove
+    bool uncut = false;                      // show the density before the cuts
+    uint8_t strength = 96;                   // alpha of the overlay's colours
+    uint8_t cut_rgba[4] = {255, 0, 0, 96};
+    uint8_t background[4] = {0, 0, 0, 255};
+    void* target_rgba8 = nullptr;            // device memory of width * height * 4 bytes; NULL: the context's own target (volym_read_slice)
+};
+
 class Simple : public ComputeDemo {
 public:
     static Simple init(const GpuContext& ctx, const volym_state& state, const SimpleAssets& a)
@@ -296,6 +308,63 @@ public:
         ctx.check(volym_set_clip_plane(ctx.handle(), plane.n, plane.d));
         records_current_ = false;
         return true;
+    }
+    // New: the slice view beside the 3-D picture -- the plane normal to `axis` (0 = x, 1 = y, 2 = z) through texel `index` of the
+    // prepared volume, one texel per pixel (volym_slice_axis, volym_slice_pass).  One kernel; no update and no frame needed.  The
+    // labels go to the device first if the overlay is wanted and they are not there yet.  Returns the slice, whose map
+    // volym_slice_texel inverts a click with; the image goes to v.target_rgba8 or the context's own target (volym_read_slice).
+    volym_slice slice(const GpuContext& ctx, const SimpleAssets& a, int axis, uint32_t index, const SliceView& v = SliceView())
+    {
+        volym_slice s{};
+        const uint32_t dims[3] = {a.nx, a.ny, a.nz};
+        ctx.check(volym_slice_axis(axis, index, dims, &s));
+        s.mode = v.mode;
+        s.flags = (v.mark_cut ? VOLYM_SLICE_MARK_CUT : 0u) | (v.uncut ? VOLYM_SLICE_UNCUT : 0u);
+        if (v.labels && (labels_on_device_ || !a.labels_raw.empty())) {
+            if (!labels_on_device_) set_labels(ctx, a);
+            s.flags |= VOLYM_SLICE_LABELS;
+        }
+        for (int i = 0; i < 4; ++i) { s.cut_rgba[i] = v.cut_rgba[i]; s.background[i] = v.background[i]; }
+        segment_palette(a, v.strength, s.palette);
+        ctx.check(volym_slice_pass(ctx.handle(), &s, v.target_rgba8));
+        return s;
+    }
+    // New: click to look inside -- the three orthogonal slices through the texel pixel (x, y) of the frame shows, read back as
+    // width * height * 4 bytes each (images[axis], sizes in slices[axis]).  False: the pixel shows nothing.
+    struct Slices {
+        Picked picked;
+        volym_slice slices[3];
+        std::vector<uint8_t> images[3];
+    };
+    bool slices_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, Slices& out, const SliceView& v = SliceView(), float alpha_min = 0.5f)
+    {
+        out.picked = pick(ctx, a, x, y, alpha_min);
+        if (out.picked.record.status != 2) return false;
+        const uint32_t t[3] = {out.picked.record.x, out.picked.record.y, out.picked.record.z};
+        SliceView own = v;
+        own.target_rgba8 = nullptr;
+        for (int axis = 0; axis < 3; ++axis) {
+            out.slices[axis] = slice(ctx, a, axis, t[axis], own);
+            out.images[axis].resize(static_cast<size_t>(out.slices[axis].width) * out.slices[axis].height * 4);
+            ctx.check(volym_read_slice(ctx.handle(), out.images[axis].data()));
+        }
+        return true;
+    }
+    // a colour per label value of the segments table for the slice overlay: hues spread by the golden angle over the label values,
+    // saturation 0.85, value 1; every other label, 0 included, stays transparent
+    static void segment_palette(const SimpleAssets& a, uint8_t strength, uint8_t palette[256][4])
+    {
+        for (int l = 0; l < 256; ++l) for (int c = 0; c < 4; ++c) palette[l][c] = 0;
+        for (const SegmentInfo& seg : a.segments) {
+            const uint32_t l = seg.label_value;
+            if (l == 0u) continue;
+            const double h6 = std::fmod(l * 0.61803398875, 1.0) * 6.0, sat = 0.85;
+            const int sector = static_cast<int>(h6) % 6;
+            const double f = h6 - std::floor(h6), p = 1.0 - sat, q = 1.0 - sat * f, t = 1.0 - sat * (1.0 - f);
+            const double rgb[6][3] = {{1, t, p}, {q, 1, p}, {p, 1, t}, {p, q, 1}, {t, p, 1}, {1, p, q}};
+            for (int c = 0; c < 3; ++c) palette[l][c] = static_cast<uint8_t>(rgb[sector][c] * 255.0 + 0.5);
+            palette[l][3] = strength;
+        }
     }
     static uint32_t crop_texel(float p, uint32_t n)
     {

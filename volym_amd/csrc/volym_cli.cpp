@@ -6,7 +6,8 @@
 //               reference's columns (src/main.rs:71-85) + Mrays/s, algorithmic bytes, GB/s, roofline fraction.
 //               A trial is --secs of back-to-back compute passes timed with HIP events (the reference counts
 //               presented frames over 2 s of wall clock, blit/GUI/vsync included).
-//   run simple: one frame of the interactive default view (src/state.rs:41-55) to frame.ppm.
+//   run simple: one frame of the interactive default view (src/state.rs:41-55) to frame.ppm; --slice AXIS,INDEX also writes the
+//   slice normal to x, y or z through that texel (Simple::slice) to frame_slice_<axis>.ppm.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -45,6 +46,8 @@ struct Options {
     bool clip = false;             // --clip-plane nx,ny,nz,px,py,pz: clip plane in unit-cube coordinates (run simple)
     float clip_normal[3] = {0.0f, 0.0f, 0.0f}, clip_point[3] = {0.5f, 0.5f, 0.5f};
     std::vector<uint8_t> hide;     // --hide 3,4: label values of the segments to hide (run simple)
+    int slice_axis = -1;           // --slice z,128: also write the slice normal to that axis through that texel (run simple)
+    uint32_t slice_index = 0;
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -175,6 +178,21 @@ int run_simple(const Options& o)
     f << "P6\n" << W << ' ' << H << "\n255\n";
     for (size_t i = 0; i < static_cast<size_t>(W) * H; ++i) f.write(reinterpret_cast<const char*>(&rgba[4 * i]), 3);
     std::printf("run simple: %s, %ux%u -> %s\n", what.c_str(), W, H, path.c_str());
+    if (o.slice_axis >= 0) {
+        // the slice view beside the frame: transfer-function colours, segments overlaid, cut texels tinted
+        SliceView view;
+        view.mode = VOLYM_SLICE_TF;
+        const volym_slice s = demo.slice(ctx, assets, o.slice_axis, o.slice_index, view);
+        std::vector<uint8_t> img(static_cast<size_t>(s.width) * s.height * 4);
+        ctx.check(volym_read_slice(ctx.handle(), img.data()));
+        const size_t dot = path.rfind('.');
+        const std::string stem = dot == std::string::npos ? path : path.substr(0, dot), ext = dot == std::string::npos ? std::string(".ppm") : path.substr(dot);
+        const std::string spath = stem + "_slice_" + "xyz"[o.slice_axis] + ext;
+        std::ofstream sf(spath, std::ios::binary);
+        sf << "P6\n" << s.width << ' ' << s.height << "\n255\n";
+        for (size_t i = 0; i < static_cast<size_t>(s.width) * s.height; ++i) sf.write(reinterpret_cast<const char*>(&img[4 * i]), 3);
+        std::printf("slice %c: %ux%u -> %s\n", "xyz"[o.slice_axis], s.width, s.height, spath.c_str());
+    }
     return 0;
 }
 
@@ -227,7 +245,17 @@ int main(int argc, char** argv)
                     pos = comma + 1u;
                 }
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...]\n"); return 2; }
+            else if (a == "--slice") {
+                const std::string v = next();
+                size_t used = 0;
+                unsigned long index = 0;
+                const size_t axis = v.size() >= 3 && v[1] == ',' ? std::string("xyz").find(v[0]) : std::string::npos;
+                try { index = std::stoul(v.substr(2), &used); } catch (const std::exception&) { used = 0; }
+                if (axis == std::string::npos || used == 0 || used != v.size() - 2 || index > 0xffffffffUL) throw Error(VOLYM_E_INVALID, "--slice: AXIS,INDEX -- x, y or z and a texel index along it");
+                o.slice_axis = static_cast<int>(axis);
+                o.slice_index = static_cast<uint32_t>(index);
+            }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

@@ -293,6 +293,27 @@ class GpuContext:
         """The context's own outline target after the latest pass into it (None before any)."""
         return _lib.lib().volym_outline_device_ptr(self.handle)
 
+    # ---- slice --------------------------------------------------------------------------------
+    def slice_pass(self, slice, target_ptr=None):
+        """Enqueue one slice pass (include/volym_hip.h volym_slice_pass; scene.slice_frame is its definition): `slice` is a
+        scene.Slice (scene.slice_axis, scene.slice_through).  target_ptr: device memory of width * height * 4 bytes; None: a
+        target the context owns (read_slice).  Needs a volume, nothing else: no update, no frame."""
+        c = slice.to_c()
+        self._ck(_lib.lib().volym_slice_pass(self.handle, C.byref(c), C.c_void_p(target_ptr)))
+        if target_ptr is None:
+            self._slice_size = (slice.height, slice.width)
+
+    def read_slice(self):
+        """The latest slice into the context's own target: (height, width, 4) uint8.  Blocks."""
+        h, w = getattr(self, "_slice_size", None) or (1, 1)
+        out = np.empty((h, w, 4), np.uint8)
+        self._ck(_lib.lib().volym_read_slice(self.handle, scene._u8p(out)))
+        return out
+
+    def slice_device_ptr(self):
+        """The context's own slice target after the latest pass into it (None before any)."""
+        return _lib.lib().volym_slice_device_ptr(self.handle)
+
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
         s = _lib.Stats()
@@ -502,6 +523,51 @@ class Simple(ComputeDemo):
                 if seg is not None:
                     out["segment"], out["segment_id"] = seg.get("name"), seg.get("id")
         return out
+
+    def segment_palette(self, strength=96):
+        """A colour per label value of the segments JSON for the slice overlay (alpha = strength); every other label, 0 included,
+        is left transparent.  The hues are spread by the golden angle over the label values, so that they do not depend on the
+        order of the JSON."""
+        import colorsys
+        pal = np.zeros((256, 4), np.uint8)
+        for s in getattr(self, "_segments", []):
+            l = int(s["label_value"])
+            if l:
+                r, g, b = colorsys.hsv_to_rgb((l * 0.61803398875) % 1.0, 0.85, 1.0)
+                pal[l] = (int(r * 255.0 + 0.5), int(g * 255.0 + 0.5), int(b * 255.0 + 0.5), int(strength))
+        return pal
+
+    def slice(self, ctx, axis, index, mode=_lib.SLICE_DENSITY, labels=True, mark_cut=True, uncut=False, palette=None,
+              cut_rgba=(255, 0, 0, 96), background=(0, 0, 0, 255), target_ptr=None):
+        """The slice view beside the 3-D picture: the plane normal to `axis` ("x", "y", "z") through texel `index` of the prepared
+        volume, one texel per pixel (scene.slice_axis).  mode: the density bytes, the transfer function's colours (_lib.SLICE_TF)
+        or the importances; labels: the segments as a colour overlay (segment_palette, or `palette`) -- the labels go to the device
+        first if they are not there yet; mark_cut: the texels the crop box, the clip plane and the hidden segments remove are
+        tinted with cut_rgba; uncut: show the density before the cuts, so that the tint lies over what was cut away.  One kernel,
+        no update and no frame needed.  The image goes to target_ptr, or to the context's own target (ctx.read_slice()).
+        Returns the scene.Slice, whose map scene.slice_texel inverts a click with."""
+        flags = (_lib.SLICE_MARK_CUT if mark_cut else 0) | (_lib.SLICE_UNCUT if uncut else 0)
+        if labels and (self._labels_on_device or self._labels_raw.size):
+            if not self._labels_on_device:
+                self.set_labels(ctx, self._labels_raw)
+            flags |= _lib.SLICE_LABELS
+        s = scene.slice_axis(axis, index, self.dims, mode=mode, flags=flags, palette=self.segment_palette() if palette is None else palette,
+                             cut_rgba=cut_rgba, background=background)
+        ctx.slice_pass(s, target_ptr)
+        return s
+
+    def slices_at(self, ctx, x, y, alpha_min=0.5, **kw):
+        """Click to look inside: the three orthogonal slices through the texel pixel (x, y) of the frame shows.  Returns the pick
+        (its "slices" entry: {"x": image, "y": image, "z": image}, each (height, width, 4) uint8, read back), or the pick alone
+        with "slices" None when the pixel shows nothing.  Keywords go to slice."""
+        p = self.pick(ctx, x, y, alpha_min)
+        p["slices"] = None
+        if p["status"] == "hit":
+            p["slices"] = {}
+            for a, axis in enumerate("xyz"):
+                self.slice(ctx, axis, p["texel"][a], **kw)
+                p["slices"][axis] = ctx.read_slice()
+        return p
 
     def hide_at(self, ctx, x, y, alpha_min=0.5):
         """Click to hide: pick pixel (x, y), then set_hidden with that label added to the hidden ones.  Returns the pick (its

@@ -398,6 +398,211 @@ def outline_frame(frame, picks, rect, selected, ring_rgba, fill_rgba=(0, 0, 0, 0
     return out
 
 
+SLICE_MAX = 8192                   # largest width and height of a slice
+SLICE_LIMIT = 1 << 30              # every corner position of a slice lies in [-2^30, 2^30), 16.16
+_SLICE_AXES = {"x": 0, "y": 1, "z": 2, 0: 0, 1: 1, 2: 2}
+
+
+class Slice:
+    """volym_slice (include/volym_hip.h): an affine map from output pixels to 16.16 texel coordinates -- pixel (i, j) shows texel
+    floor((origin + i * du + j * dv) / 65536) -- with what to show there.  mode: _lib.SLICE_DENSITY / SLICE_TF / SLICE_IMPORTANCE;
+    flags: SLICE_UNCUT | SLICE_LABELS | SLICE_MARK_CUT; palette: (256, 4) uint8, colour per label value with alpha = strength."""
+
+    def __init__(self, origin, du, dv, width, height, mode=_lib.SLICE_DENSITY, flags=0, background=(0, 0, 0, 255), cut_rgba=(255, 0, 0, 96),
+                 palette=None):
+        self.origin, self.du, self.dv = (tuple(int(v) for v in t) for t in (origin, du, dv))
+        self.width, self.height, self.mode, self.flags = int(width), int(height), int(mode), int(flags)
+        self.background, self.cut_rgba = tuple(int(v) for v in background), tuple(int(v) for v in cut_rgba)
+        self.palette = np.zeros((256, 4), np.uint8) if palette is None else np.array(palette, np.uint8).reshape(256, 4)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        fields = {k: getattr(self, k) for k in ("origin", "du", "dv", "width", "height", "mode", "flags", "background", "cut_rgba", "palette")}
+        for k in kw:
+            if k not in fields:
+                raise TypeError("a slice has no field %r" % k)
+        fields.update(kw)
+        return Slice(**fields)
+
+    def to_c(self):
+        """The _lib.Slice of this slice.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Slice()
+        for name in ("origin", "du", "dv"):
+            v = getattr(self, name)
+            if len(v) != 3 or not all(-2 ** 31 <= x < 2 ** 31 for x in v):
+                raise ValueError("slice: %s is three 32-bit integers (16.16)" % name)
+            setattr(c, name, (C.c_int32 * 3)(*v))
+        for name in ("width", "height", "mode", "flags"):
+            v = getattr(self, name)
+            if not 0 <= v < 2 ** 32:
+                raise ValueError("slice: %s = %d is not a u32" % (name, v))
+            setattr(c, name, v)
+        c.background = (C.c_uint8 * 4)(*[int(v) for v in _rgba(self.background, "background")])
+        c.cut_rgba = (C.c_uint8 * 4)(*[int(v) for v in _rgba(self.cut_rgba, "cut_rgba")])
+        C.memmove(c.palette, _u8p(np.ascontiguousarray(self.palette, np.uint8)), 1024)
+        return c
+
+    @classmethod
+    def from_c(cls, c):
+        return cls(tuple(c.origin), tuple(c.du), tuple(c.dv), c.width, c.height, c.mode, c.flags, tuple(c.background), tuple(c.cut_rgba),
+                   np.ctypeslib.as_array(c.palette).copy())
+
+
+def _slice_pos(s, a, i, j):
+    return s.origin[a] + i * s.du[a] + j * s.dv[a]          # Python integers: exact
+
+
+def check_slice(s):
+    """The validity rules of volym_slice_check: a known mode, known flag bits, no IMPORTANCE with UNCUT, width and height in
+    1..8192, and the four corner positions in [-2^30, 2^30) on every axis.  Returns the slice; raises ValueError."""
+    if s.mode not in (_lib.SLICE_DENSITY, _lib.SLICE_TF, _lib.SLICE_IMPORTANCE):
+        raise ValueError("slice: unknown mode %r" % (s.mode,))
+    if s.flags & ~(_lib.SLICE_UNCUT | _lib.SLICE_LABELS | _lib.SLICE_MARK_CUT) or s.flags < 0:
+        raise ValueError("slice: unknown flag bits in %#x" % s.flags)
+    if s.mode == _lib.SLICE_IMPORTANCE and s.flags & _lib.SLICE_UNCUT:
+        raise ValueError("slice: IMPORTANCE with UNCUT (the importances' uncut source is not one buffer)")
+    if not (1 <= s.width <= SLICE_MAX and 1 <= s.height <= SLICE_MAX):
+        raise ValueError("slice: width and height are 1..%d, got %d x %d" % (SLICE_MAX, s.width, s.height))
+    for a in range(3):
+        for i in (0, s.width - 1):
+            for j in (0, s.height - 1):
+                if not -SLICE_LIMIT <= _slice_pos(s, a, i, j) < SLICE_LIMIT:
+                    raise ValueError("slice: corner (%d, %d) is at %d on axis %d, outside [-2^30, 2^30)" % (i, j, _slice_pos(s, a, i, j), a))
+    return s
+
+
+def slice_axis(axis, index, dims, **kw):
+    """The slice normal to `axis` ("x", "y", "z" or 0, 1, 2) through texel `index` (volym_slice_axis): one texel per pixel through
+    texel centres.  z: u = +x, v = +y.  y: u = +x, v = +z.  x: u = +y, v = +z.  Keywords go to Slice (mode, flags, colours)."""
+    if axis not in _SLICE_AXES:
+        raise ValueError("a slice axis is x, y or z (0, 1, 2), got %r" % (axis,))
+    a = _SLICE_AXES[axis]
+    dims = [int(v) for v in dims]
+    if len(dims) != 3 or not 0 <= int(index) < dims[a]:
+        raise ValueError("slice index %r is not inside axis %d of %r" % (index, a, dims))
+    u, v = (1 if a == 0 else 0), (1 if a == 2 else 2)
+    origin, du, dv = [0x8000] * 3, [0] * 3, [0] * 3
+    origin[a] = (int(index) << 16) + 0x8000
+    du[u] = dv[v] = 1 << 16
+    return check_slice(Slice(origin, du, dv, dims[u], dims[v], **kw))
+
+
+def slice_texel(s, i, j):
+    """The texel (x, y, z) output pixel (i, j) of the slice shows (volym_slice_texel), inside the volume or not: floor, not
+    truncation."""
+    if not (0 <= int(i) < s.width and 0 <= int(j) < s.height):
+        raise ValueError("pixel (%r, %r) is not inside the %d x %d slice" % (i, j, s.width, s.height))
+    return tuple(_slice_pos(s, a, int(i), int(j)) >> 16 for a in range(3))
+
+
+def slice_through(point_texel, normal, up_hint, size, texels_per_pixel=1.0, **kw):
+    """An oblique slice: the plane through `point_texel` (texel coordinates, a texel's centre is at index + 0.5) with the given
+    normal (texel space; scene.clip_plane_texels gives a clip plane's n, so the cut surface can be shown).  `point_texel` is the
+    centre of the size = (width, height) output, rows run against the part of up_hint that lies in the plane, columns along
+    up x normal, and a pixel is texels_per_pixel texels wide.  The steps are rounded to 16.16 (float64, round half up), so the
+    plane shown is the one of the rounded steps.  Keywords go to Slice."""
+    n = np.array([float(v) for v in normal], np.float64)
+    up = np.array([float(v) for v in up_hint], np.float64)
+    pt = np.array([float(v) for v in point_texel], np.float64)
+    w, h = int(size[0]), int(size[1])
+    if n.shape != (3,) or up.shape != (3,) or pt.shape != (3,) or not np.isfinite(np.concatenate([n, up, pt])).all() or not (n != 0).any():
+        raise ValueError("an oblique slice is a point, a non-zero normal and an up hint, three finite coordinates each")
+    n /= np.sqrt((n * n).sum())
+    up = up - (up * n).sum() * n
+    if np.sqrt((up * up).sum()) < 1e-9:
+        raise ValueError("slice_through: the up hint is parallel to the normal")
+    up /= np.sqrt((up * up).sum())
+    right = np.cross(up, n)
+    k = float(texels_per_pixel) * 65536.0
+    if not np.isfinite(k) or k <= 0.0:
+        raise ValueError("slice_through: texels_per_pixel must be positive")
+    du = [int(v) for v in np.floor(right * k + 0.5)]
+    dv = [int(v) for v in np.floor(-up * k + 0.5)]
+    # twice the centre offset is an integer: origin = round(point * 65536) - ((w - 1) * du + (h - 1) * dv) / 2, floored
+    origin = [int(np.floor(pt[a] * 65536.0 + 0.5)) - (((w - 1) * du[a] + (h - 1) * dv[a]) >> 1) for a in range(3)]
+    return check_slice(Slice(origin, du, dv, w, h, **kw))
+
+
+def cut_volume(prepared, dims, cut, labels=None):
+    """Box, plane and mask of a cut state applied to prepared bytes (density or importances): crop_volume, clip_volume and
+    hide_segments in one.  `cut`: a dict with any of "box": (lo, hi), "plane": (n, d), "visible": 256 flags; None cuts nothing."""
+    out = np.ascontiguousarray(prepared, np.uint8).ravel()
+    cut = cut or {}
+    if cut.get("box") is not None:
+        out = crop_volume(out, dims, *cut["box"])
+    if cut.get("plane") is not None:
+        out = clip_volume(out, dims, *cut["plane"])
+    if cut.get("visible") is not None and labels is not None:
+        out = hide_segments(out, labels, cut["visible"])
+    return out
+
+
+def slice_frame(prepared, dims, slice, lut=None, labels=None, importances=None, cut=None, uncut=None):
+    """The definition of the slice pass (include/volym_hip.h volym_slice_pass), integers only; equal to the device in every byte.
+    `prepared`: the density bytes of the scene as it stands (box, plane and mask applied: cut_volume); `uncut`: the density before
+    any cut, shown under SLICE_UNCUT (None: the context never cut, `prepared` is shown); `lut`: the RGBA8 bytes
+    set_transfer_function received (SLICE_TF); `labels`: prepared label bytes of the volume's dimensions (SLICE_LABELS, and the
+    mask of SLICE_MARK_CUT); `importances`: the importance bytes as the march reads them (SLICE_IMPORTANCE); `cut`: the cut state
+    SLICE_MARK_CUT marks, as cut_volume takes it.  Returns (height, width, 4) uint8."""
+    s = check_slice(slice)
+    nx, ny, nz = (int(v) for v in dims)
+    n = (nx, ny, nz)
+    i = np.arange(s.width, dtype=np.int64)[None, :]
+    j = np.arange(s.height, dtype=np.int64)[:, None]
+    t = [(s.origin[a] + i * s.du[a] + j * s.dv[a]) >> 16 for a in range(3)]         # floor: an arithmetic shift
+    inside = np.ones((s.height, s.width), bool)
+    for a in range(3):
+        inside &= (t[a] >= 0) & (t[a] < n[a])
+    x, y, z = (v[inside] for v in t)
+    at = (z * ny + y) * nx + x
+
+    def fetch(arr, what):
+        if arr is None:
+            raise ValueError("slice_frame: this slice needs %s" % what)
+        arr = np.ascontiguousarray(arr, np.uint8).ravel()
+        if arr.size != nx * ny * nz:
+            raise ValueError("slice_frame: %s have %d bytes, the volume %d" % (what, arr.size, nx * ny * nz))
+        return arr[at]
+
+    if s.mode == _lib.SLICE_IMPORTANCE:
+        b = fetch(importances, "importances")
+    else:
+        b = fetch(uncut if (s.flags & _lib.SLICE_UNCUT and uncut is not None) else prepared, "density bytes")
+    base = np.empty((b.size, 4), np.uint8)
+    if s.mode == _lib.SLICE_TF:
+        if lut is None:
+            raise ValueError("slice_frame: SLICE_TF needs the transfer function's RGBA8 bytes")
+        table = np.ascontiguousarray(lut, np.uint8).reshape(-1, 4)
+        base[:] = table[(b.astype(np.int64) * table.shape[0]) >> 8]
+    else:
+        base[:, 0] = base[:, 1] = base[:, 2] = b
+    base[:, 3] = 255
+    need_labels = s.flags & _lib.SLICE_LABELS or (s.flags & _lib.SLICE_MARK_CUT and labels is not None)
+    lab = fetch(labels, "labels") if need_labels else None
+    if s.flags & _lib.SLICE_LABELS:
+        # outline_blend with a colour per pixel
+        col = np.ascontiguousarray(s.palette, np.uint8).reshape(256, 4)[lab].astype(np.uint32)
+        a8 = col[:, 3:4].copy()
+        col[:, 3] = 255
+        base = ((base.astype(np.uint32) * (255 - a8) + col * a8 + 127) // 255).astype(np.uint8)
+    if s.flags & _lib.SLICE_MARK_CUT and cut:
+        removed = np.zeros(b.size, bool)
+        if cut.get("box") is not None:
+            lo, hi = check_crop_box(cut["box"][0], cut["box"][1], dims)
+            for a, v in enumerate((x, y, z)):
+                removed |= (v < lo[a]) | (v >= hi[a])
+        if cut.get("plane") is not None:
+            pn, pd = check_clip_plane(*cut["plane"])
+            removed |= pn[0] * x + pn[1] * y + pn[2] * z > pd
+        if cut.get("visible") is not None and lab is not None:
+            removed |= check_segment_visibility(cut["visible"])[lab] == 0
+        base[removed] = outline_blend(base[removed], s.cut_rgba)
+    out = np.empty((s.height, s.width, 4), np.uint8)
+    out[:] = np.array(_rgba(s.background, "background"), np.uint8)
+    out[inside] = base
+    return out
+
+
 def map_segments_to_importance(labels, segments):
     """src/demos/simple/importance.rs:148-158"""
     data = np.array(labels, np.uint8, copy=True).ravel()
