@@ -89,6 +89,14 @@ enum {
                                   and volym_selftest_ray_setup use the first slot alone (one frame at a time); the shard /
                                   pack / assemble calls and volym_set_stream return VOLYM_E_STATE.  Memory: the volume,
                                   importances and macro cells once; the frame buffers, tables and work lists twice. */
+    VOLYM_OPT_BOUNDS_CELLS = 12, /* cells per axis of the grid of density maxima that a standing view's tile mask and per-tile depth
+                                  bounds are built from, once per view: -1 (default) = by the volume's size (volym_bounds_cells_for:
+                                  cells of two voxels on the longest axis, at most VOLYM_BOUNDS_CELLS_DEFAULT_MAX, never fewer than the
+                                  macro cells), 0 = the macro cells themselves, else a power of two from VOLYM_OPT_MACRO_CELLS to
+                                  VOLYM_BOUNDS_CELLS_MAX.  Same pixels for every value: a finer grid only trims more constant tiles
+                                  and more of the empty ends of the rays.  The march loop does not read the grid.  A view with the
+                                  cone look-ahead (use_importance_rendering and use_cone_importance_check) keeps the macro cells.  Blocking; with a
+                                  volume on the device it rebuilds the grid, and every view gets a new mask. */
     VOLYM_OPT_SETUP_IEEE = 10  /* 1 = the ray set-up (wgsl:221-241) runs its 14 divisions as 14 plain IEEE divisions; default 0: the
                                   divisions that share a denominator share its refined reciprocal -- the same instructions on the
                                   same values, so the same bits (raymarch_device.h make_ray; volym_selftest_ray_setup).  Takes
@@ -172,6 +180,16 @@ int volym_set_segment_importances(volym_ctx* ctx, const uint8_t table[256]);
 /* Voxel count per label value, from the volym_set_labels pass (the reference logs such a histogram, importance.rs:83-91).
  * Counts the whole label volume, whatever the crop box.  VOLYM_E_STATE without labels. */
 int volym_label_counts(volym_ctx* ctx, uint64_t counts[256]);
+/* The grids of density maxima (macro cells, and the finer grid of VOLYM_OPT_BOUNDS_CELLS) divide an axis of `dim` voxels into
+ * n_cells cells; cell k covers the voxels a nearest-filter sample at a position in [k / n_cells, (k + 1) / n_cells) can select,
+ * and one more voxel on either side.  volym_cells_meeting_box: the cells whose voxels meet [lo, hi), as [*c0, *c1); none, and
+ * lo >= hi, give *c0 == *c1 == 0.  An edit that rewrites a box of texels refreshes exactly these cells of each grid.  Pure host
+ * arithmetic, no context.  VOLYM_E_INVALID for NULL, n_cells outside 1..4096 or dim outside 1..65536. */
+int volym_cells_meeting_box(uint32_t n_cells, uint32_t dim, uint32_t lo, uint32_t hi, uint32_t* c0, uint32_t* c1);
+/* The default of VOLYM_OPT_BOUNDS_CELLS for a volume of dims[0] x dims[1] x dims[2] voxels and that many macro cells per axis. */
+#define VOLYM_BOUNDS_CELLS_MAX 128u         /* the largest grid the option takes */
+#define VOLYM_BOUNDS_CELLS_DEFAULT_MAX 64u  /* the largest the default takes: 128 costs a view more to build than it gives back */
+uint32_t volym_bounds_cells_for(const uint32_t dims[3], uint32_t macro_cells);
 /* Axis-aligned crop box on the device (new; the reference has none).  The frames enqueued after the call are the frames of the
  * same scene in which every density byte AND every importance byte of a texel outside the box is 0 (an important structure
  * that is cut away stops suppressing what lies in front of it).  lo inclusive, hi exclusive, in texels of the volume as
@@ -294,6 +312,15 @@ int volym_settle(volym_ctx* ctx);
  * (the latter needs VOLYM_OPT_WRITE_F32 = 1). */
 int volym_read_rgba8(volym_ctx* ctx, uint8_t* out);
 int volym_read_rgba32f(volym_ctx* ctx, float* out);
+/* The tile mask and the per-tile depth bounds of the view of the latest pass, as the march reads them (for tests and tools).
+ * volym_tile_bounds_size: the frame's 8x8 tiles per row and per column and the 32-bit words of its mask.  volym_read_tile_bounds
+ * blocks and addresses the frame slot of the latest pass: mask_bits receives mask_words words, bit (i & 31) of word (i >> 5)
+ * for tile i = ty * tiles_x8 + tx; near and far receive 32 * mask_words floats each, indexed by i: the range of the ray
+ * parameter outside which no sample of the tile's pixels can be dense.  A tile no occupied cell projects onto has near = +inf
+ * and far = 0; a view without depth bounds has near = 0 and far = +inf everywhere.  VOLYM_E_STATE while the view has no mask:
+ * a standing view gets it with its second frame, a view whose scene or options changed since loses it. */
+int volym_tile_bounds_size(volym_ctx* ctx, uint32_t* tiles_x8, uint32_t* tiles_y8, uint32_t* mask_words);
+int volym_read_tile_bounds(volym_ctx* ctx, uint32_t* mask_bits, float* near, float* far);
 
 /* The step after the path: RenderPipeline::render_pass (src/render_pipeline.rs:88-130) with shaders/render.wgsl:39-43 --
  * every pixel (x, y) of an out_w x out_h rgba8 target samples the frame at uv = (x + 0.5, y + 0.5) / (W, H) through a

@@ -100,12 +100,19 @@ def main():
         lanes = (ph[:, 3] & 0xFFFF).astype(np.float64)
         accepted = (ph[:, 3] >> 16).astype(np.float64)
         ph = ph.copy(); ph[:, 3] = 0
+        # a phase sum is a sum of differences of two clock reads; where one of them came out negative (the clock is read by a scalar
+        # instruction that a wave's neighbour on the SIMD can delay past the next read) the unsigned sum wraps to ~2^32.  No wave runs
+        # for 2^28 x 16 ticks: leave such waves out of the shares, and say how many.
+        wrapped = (ph[:, :3] >= (1 << 28)).any(axis=1)
+        if wrapped.any():
+            print("phase counters wrapped in %d of %d waves: left out of the shares below" % (int(wrapped.sum()), len(ph)))
+        ph[wrapped] = 0
         tick = ph.astype(np.float64) * 16.0          # shader clock ticks
         print("lane utilisation at the loop top %.1f%% ; samples accepted per active lane-iteration %.2f ; per wave-iteration %.1f (of %d slots)" % (
             100.0 * lanes.sum() / (64.0 * iters.sum()), accepted.sum() / lanes.sum(), accepted.sum() / iters.sum(), 256))
         tot = tick.sum(axis=0)
         print("phase shares over all waves (shader ticks): leap %.1f%%  sample %.1f%%  flush %.1f%%  setup+store %.1f%%  ; ticks per us of wave time: %.0f" % (
-            *(100.0 * tot / tot.sum()), tot.sum() / (dur.sum() / 100.0)))
+            *(100.0 * tot / tot.sum()), tot.sum() / (dur[~wrapped].sum() / 100.0)))
         slow = np.argsort(dur)[-16:]
         ts = tick[slow].sum(axis=0)
         print("slowest 16 waves: leap %.1f%% sample %.1f%% flush %.1f%% setup %.1f%% ; iterations %s ; dur us %s" % (

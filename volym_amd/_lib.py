@@ -16,6 +16,7 @@ OPT_KERNEL, OPT_WRITE_F32, OPT_MACRO_CELLS = 1, 2, 3
 OPT_VOLUME_LAYOUT, OPT_CULLING, OPT_COST_FEEDBACK, OPT_DEPTH_PARALLEL, OPT_XCD_BANDS, OPT_REBALANCE_ROUNDS = 4, 5, 6, 7, 8, 9
 OPT_SETUP_IEEE = 10
 OPT_FRAMES_IN_FLIGHT = 11
+OPT_BOUNDS_CELLS = 12
 
 
 class VolymError(RuntimeError):
@@ -213,6 +214,10 @@ SIGNATURES = {
     "volym_pick_device_ptr": (C.c_void_p, [_ctx]),
     "volym_pick": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(Pick)]),
     "volym_outline_pass": (C.c_int, [_ctx, C.POINTER(Outline), C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]),
+    "volym_cells_meeting_box": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_bounds_cells_for": (C.c_uint32, [C.POINTER(C.c_uint32), C.c_uint32]),
+    "volym_tile_bounds_size": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_read_tile_bounds": (C.c_int, [_ctx, C.POINTER(C.c_uint32), _f32p, _f32p]),
     "volym_read_outline": (C.c_int, [_ctx, _u8p]),
     "volym_outline_device_ptr": (C.c_void_p, [_ctx]),
     "volym_slice_pass": (C.c_int, [_ctx, C.POINTER(Slice), C.c_void_p]),

@@ -159,6 +159,13 @@ struct volym_ctx {
     std::vector<uint8_t> h_mc;               // host copy of d_mc
     int aabb_tab[257][6];                    // occupied-cell AABB per threshold byte {x0,y0,z0,x1,y1,z1}; x1 < x0: none
     uint32_t mc_n = 32;
+    // The grid the per-view tile mask and depth bounds are built from (raymarch.hip ensure_frame_resources): maxima of fine_n^3 cells
+    // defined as the macro cells are (scene_kernels.h volym_fine_cell_kernel), shared by the frame slots as d_mc is, device only.
+    // NULL with fine_n == mc_n: the macro cells themselves.  bounds_cells is VOLYM_OPT_BOUNDS_CELLS: -1 the rule
+    // (volym_bounds_cells_for), 0 the macro-cell grid, else an explicit power of two.
+    uint8_t* d_mc_fine = nullptr;
+    uint32_t fine_n = 32;
+    int bounds_cells = -1;
     uint32_t tile_mask_words = 0;            // 0: the frame has more tiles than the mask kernel holds in LDS -- no mask
     bool tile_mask = true;                   // dev switch
     bool tile_depth = true;                  // dev switch: per-tile depth bounds with the mask
@@ -245,8 +252,10 @@ int launch_pick(volym_ctx* c, FrameSlot& s, const uint32_t rect[4], float alpha_
 void free_outline(volym_ctx* c);
 // slice.hip: what the context keeps for the slice pass (every stream idle)
 void free_slice(volym_ctx* c);
-// scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes (sets have_vol)
+// scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
+// scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume
+int build_fine_cells(volym_ctx* c);
 
 }  // namespace volym
 

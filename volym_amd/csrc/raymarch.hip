@@ -532,7 +532,7 @@ void volym_destroy(volym_ctx* c)
     for (int i = 1; i >= 0; --i)
         if (c->slots[i]) free_slot(*c->slots[i]);
     // (every slot's stream is idle now: nothing reads the scene any more)
-    (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc);
+    (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc); (void)hipFree(c->d_mc_fine);
     (void)hipFree(c->d_vol0); (void)hipFree(c->d_imp0);
     (void)hipFree(c->d_picks);
     free_outline(c);
@@ -614,6 +614,12 @@ int volym_set_option(volym_ctx* c, int key, int value)
         c->mc_n = static_cast<uint32_t>(value);
         if (c->have_vol) { int rc = build_macro_cells(c); if (rc != VOLYM_OK) return rc; }
         return rebuild_lists(c);
+    case VOLYM_OPT_BOUNDS_CELLS:
+        if (value != -1 && value != 0 && (value < static_cast<int>(c->mc_n) || value > static_cast<int>(VOLYM_BOUNDS_CELLS_MAX) || (value & (value - 1)) != 0))
+            return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_BOUNDS_CELLS: -1 (by the volume's size), 0 (the macro cells) or a power of two from VOLYM_OPT_MACRO_CELLS to 128");
+        c->bounds_cells = value;
+        for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->hull_dirty = true;
+        return c->have_vol ? build_fine_cells(c) : VOLYM_OK;
     case VOLYM_OPT_VOLUME_LAYOUT:
         if (value < -1 || value > 1) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_VOLUME_LAYOUT: -1 (by size), 0 (linear) or 1 (4x4x4 bricks)");
         c->layout_choice = value;
@@ -762,14 +768,22 @@ static int ensure_frame_resources(volym_ctx* c, FrameSlot& s)
         // into the buffer the launches so far have kept zeroed; the launches from here on read it and zero the other one
         s.mask_cur ^= 1;
         uint32_t* cur = s.d_tile_mask + static_cast<size_t>(s.mask_cur) * c->tile_mask_words;
-        const uint32_t cells = c->mc_n * c->mc_n * c->mc_n;
+        // the cells of both kernels: the fine grid where the context holds one (the same criterion, the same margin, cells that nest
+        // in the occupied macro cells, so inside the AABB whose corners compute_culling found in front of the eye)
+        // A view with the cone look-ahead keeps the macro cells: its frame is the look-ahead jobs, not the march chains the finer grid
+        // shortens, and with the 64 grid it was measured 1.7 % slower, reproducibly and for a reason not found (profiles/fine_bounds_ab.txt
+        // point 2).  The flags belong to the view: a change of them makes the hulls dirty and the mask is built again.
+        const bool cone_view = (s.fp.flags & F_IMP_RENDERING) != 0u && (s.fp.flags & F_CONE) != 0u;
+        const bool fine = c->d_mc_fine != nullptr && !cone_view;
+        const uint8_t* grid = fine ? c->d_mc_fine : c->d_mc;
+        const uint32_t gn = fine ? c->fine_n : c->mc_n;
+        const uint32_t cells = gn * gn * gn, nb = (gn + 7u) / 8u;
         if (static_cast<size_t>(c->tile_mask_words) * sizeof(uint32_t) <= 48u * 1024u) {
             // the mask fits LDS: aggregated per block of cells, only the words that are not zero travel
-            const uint32_t nb = (c->mc_n + 7u) / 8u;
-            hipLaunchKernelGGL(volym_tile_mask_lds_kernel, dim3(nb * nb * ((c->mc_n + 3u) / 4u)), dim3(256), c->tile_mask_words * sizeof(uint32_t), s.stream, c->d_mc, c->mc_n,
+            hipLaunchKernelGGL(volym_tile_mask_lds_kernel, dim3(nb * nb * ((gn + 3u) / 4u)), dim3(256), c->tile_mask_words * sizeof(uint32_t), s.stream, grid, gn,
                                s.thr_byte_cull, M, s.mask_margin, c->W, c->H, c->tiles_x * 2u, c->tile_mask_words, cur);
         } else {
-            hipLaunchKernelGGL(volym_tile_mask_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, s.stream, c->d_mc, c->mc_n, s.thr_byte_cull, M, s.mask_margin,
+            hipLaunchKernelGGL(volym_tile_mask_kernel, dim3((cells + 255u) / 256u), dim3(256), 0, s.stream, grid, gn, s.thr_byte_cull, M, s.mask_margin,
                                c->W, c->H, c->tiles_x * 2u, c->tile_mask_words, cur);
         }
         HIPCHK(c, hipGetLastError());
@@ -780,8 +794,7 @@ static int ensure_frame_resources(volym_ctx* c, FrameSlot& s)
             // order behind the launches that read the last view's
             const uint32_t n_t8 = 32u * c->tile_mask_words;
             HIPCHK(c, hipMemsetAsync(s.d_tile_depth, 0, 2u * static_cast<size_t>(n_t8) * sizeof(uint32_t), s.stream));
-            const uint32_t nb = (c->mc_n + 7u) / 8u;
-            hipLaunchKernelGGL(volym_tile_depth_kernel, dim3(nb * nb * ((c->mc_n + 3u) / 4u)), dim3(256), 0, s.stream, c->d_mc, c->mc_n, s.thr_byte_cull, M,
+            hipLaunchKernelGGL(volym_tile_depth_kernel, dim3(nb * nb * ((gn + 3u) / 4u)), dim3(256), 0, s.stream, grid, gn, s.thr_byte_cull, M,
                                s.mask_margin, s.fp.eye[0], s.fp.eye[1], s.fp.eye[2], c->W, c->H, c->tiles_x * 2u, n_t8, s.d_tile_depth);
             HIPCHK(c, hipGetLastError());
             s.fp.tile_depth = s.d_tile_depth;
@@ -1149,6 +1162,41 @@ int volym_read_rgba8(volym_ctx* c, uint8_t* out)
     HIPCHK(c, hipMemcpyAsync(out, c->frame_buf(s), static_cast<size_t>(c->W) * c->H * 4, hipMemcpyDeviceToHost, s.stream));
     HIPCHK(c, hipStreamSynchronize(s.stream));
     return check_pool_error(c, s);
+}
+
+int volym_tile_bounds_size(volym_ctx* c, uint32_t* tiles_x8, uint32_t* tiles_y8, uint32_t* mask_words)
+{
+    if (!c || !tiles_x8 || !tiles_y8 || !mask_words) return VOLYM_E_INVALID;
+    *tiles_x8 = c->tiles_x * 2u; *tiles_y8 = c->tiles_y * 2u; *mask_words = c->tile_mask_words;
+    return VOLYM_OK;
+}
+
+int volym_read_tile_bounds(volym_ctx* c, uint32_t* mask_bits, float* near, float* far)
+{
+    if (!c) return VOLYM_E_INVALID;
+    if (!mask_bits || !near || !far) return fail(c, VOLYM_E_INVALID, "volym_read_tile_bounds: NULL output");
+    FrameSlot& s = *c->slots[c->last];
+    if (!(s.fp.cull & CULL_TILE_MASK) || !s.fp.tile_mask || s.mask_pending || s.hull_dirty)
+        return fail(c, VOLYM_E_STATE, "volym_read_tile_bounds: the view of the latest pass has no tile mask (it gets one with its second frame)");
+    const uint32_t words = c->tile_mask_words, n_t8 = 32u * words;
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<uint32_t> enc;
+    const bool depth = (s.fp.cull & CULL_TILE_DEPTH) != 0u && s.fp.tile_depth;
+    // (the launches of this view read the mask and keep the other buffer zeroed: the words are the mask kernel's)
+    HIPCHK(c, hipMemcpyAsync(mask_bits, s.fp.tile_mask, static_cast<size_t>(words) * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    if (depth) {
+        enc.resize(2u * static_cast<size_t>(n_t8));
+        HIPCHK(c, hipMemcpyAsync(enc.data(), s.fp.tile_depth, enc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s.stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    for (uint32_t t = 0; t < n_t8; ++t) {
+        near[t] = 0.0f; far[t] = INFINITY;                              // no bounds: the rays keep their whole length
+        if (!depth) continue;
+        const uint32_t ne = ~enc[t], fe = enc[n_t8 + t];
+        if (fe == 0u) { near[t] = INFINITY; far[t] = 0.0f; continue; }  // no cell projects onto the tile: no sample is left
+        std::memcpy(&near[t], &ne, 4); std::memcpy(&far[t], &fe, 4);
+    }
+    return VOLYM_OK;
 }
 
 int volym_read_rgba32f(volym_ctx* c, float* out)

@@ -498,47 +498,62 @@ __global__ __launch_bounds__(256) void volym_tile_mask_kernel(const uint8_t* __r
     }
 }
 
-// The same mask, aggregated in LDS first: one workgroup per block of 8 x 8 x 4 macro cells (a compact piece of the volume: its
-// cells project onto neighbouring tiles), the bits ORed into a copy of the mask in LDS, and only the words that are not zero go
-// to global memory -- a few thousand device-scope atomics per view instead of one per (cell, tile row, word): ~13 us -> ~3 us
-// at 1920 x 1080.  Same rectangles, same bits.  n_words * 4 bytes of dynamic LDS (the caller falls back to the kernel above
-// for frames whose mask does not fit).
+// The same mask, aggregated in LDS first: one workgroup per block of 8 x 8 x 4 cells (a compact piece of the volume: its cells
+// project onto neighbouring tiles).  The bits are ORed into a copy of the mask in LDS -- of the run of words the block touches --
+// and only the words that are not zero go to global memory: a few thousand device-scope atomics per view instead of one per
+// (cell, tile row, word).  Same rectangles, same bits.  At 1920 x 1080: 5 us over the 32^3 macro cells (13 us for the kernel
+// above), 11 us over a 64^3 grid, 27 us over 128^3 (profiles/fine_bounds_ab.txt, point 5).  n_words * 4 bytes of dynamic LDS
+// (the caller falls back to the kernel above for frames whose mask does not fit).
 __global__ __launch_bounds__(256) void volym_tile_mask_lds_kernel(const uint8_t* __restrict__ mc_max, uint32_t mc_n, uint32_t thr_byte, ClipMatrix M,
                                                                   float margin, uint32_t W, uint32_t H, uint32_t t8x, uint32_t n_words,
                                                                   uint32_t* __restrict__ out)
 {
     extern __shared__ uint32_t s_mask[];
-    for (uint32_t i = threadIdx.x; i < n_words; i += 256u) s_mask[i] = 0u;
-    __syncthreads();
+    __shared__ uint32_t s_words[2];                      // the words the block's cells touch: first, last
     // block -> cell: blocks of 8 x 8 x 4 cells, x fastest
     const uint32_t nbx = (mc_n + 7u) / 8u, nby = (mc_n + 7u) / 8u;
     const uint32_t bx = blockIdx.x % nbx, by = (blockIdx.x / nbx) % nby, bz = blockIdx.x / (nbx * nby);
     const uint32_t cx = bx * 8u + (threadIdx.x & 7u), cy = by * 8u + ((threadIdx.x >> 3) & 7u), cz = bz * 4u + (threadIdx.x >> 6);
-    bool all_bits = false;
-    if (cx < mc_n && cy < mc_n && cz < mc_n && mc_max[cx + mc_n * (cy + mc_n * cz)] >= thr_byte) {
-        const CellRect r = cell_tile_rect(M, cx, cy, cz, mc_n, margin, W, H);
-        if (r.bad) {
-            all_bits = true;                         // cannot happen under CULL_OBJ_HULL; be safe: everything is marched
-        } else {
-            if (r.on) {
-                const uint32_t tx0 = r.tx0, tx1 = r.tx1, ty0 = r.ty0, ty1 = r.ty1;
-                for (uint32_t ty = ty0; ty <= ty1; ++ty) {
-                    uint32_t bit = ty * t8x + tx0;
-                    const uint32_t last = ty * t8x + tx1;
-                    while (bit <= last) {
-                        const uint32_t word = bit >> 5, first_in = bit & 31u;
-                        const uint32_t end_in = (last >> 5) == word ? (last & 31u) : 31u;
-                        const uint32_t m = (end_in == 31u ? 0xffffffffu : ((1u << (end_in + 1u)) - 1u)) & ~((1u << first_in) - 1u);
-                        if (word < n_words) atomicOr(&s_mask[word], m);
-                        bit = (word + 1u) << 5;
-                    }
-                }
+    const bool occupied = cx < mc_n && cy < mc_n && cz < mc_n && mc_max[cx + mc_n * (cy + mc_n * cz)] >= thr_byte;
+    // most blocks of a fine grid hold no occupied cell: they end here, before the mask in LDS
+    if (!__syncthreads_or(occupied ? 1 : 0)) return;
+    if (threadIdx.x == 0u) { s_words[0] = 0xffffffffu; s_words[1] = 0u; }
+    __syncthreads();
+    CellRect r = {0u, 0u, 0u, 0u, false, false};
+    if (occupied) {
+        r = cell_tile_rect(M, cx, cy, cz, mc_n, margin, W, H);
+        if (r.on && !r.bad) {
+            atomicMin(&s_words[0], (r.ty0 * t8x + r.tx0) >> 5);
+            atomicMax(&s_words[1], (r.ty1 * t8x + r.tx1) >> 5);
+        }
+    }
+    if (__syncthreads_or(r.bad ? 1 : 0)) {               // cannot happen under CULL_OBJ_HULL; be safe: everything is marched
+        for (uint32_t i = threadIdx.x; i < n_words; i += 256u) atomicOr(&out[i], 0xffffffffu);
+        return;
+    }
+    // only the words between the first and the last the block touches are cleared, ORed and flushed: a block of small cells
+    // projects onto a small piece of the frame
+    const uint32_t w0 = s_words[0], w1 = s_words[1] < n_words ? s_words[1] : n_words - 1u;
+    if (w0 > w1) return;                                 // no cell of the block on screen
+    for (uint32_t i = w0 + threadIdx.x; i <= w1; i += 256u) s_mask[i] = 0u;
+    __syncthreads();
+    if (r.on) {
+        const uint32_t tx0 = r.tx0, tx1 = r.tx1, ty0 = r.ty0, ty1 = r.ty1;
+        for (uint32_t ty = ty0; ty <= ty1; ++ty) {
+            uint32_t bit = ty * t8x + tx0;
+            const uint32_t last = ty * t8x + tx1;
+            while (bit <= last) {
+                const uint32_t word = bit >> 5, first_in = bit & 31u;
+                const uint32_t end_in = (last >> 5) == word ? (last & 31u) : 31u;
+                const uint32_t m = (end_in == 31u ? 0xffffffffu : ((1u << (end_in + 1u)) - 1u)) & ~((1u << first_in) - 1u);
+                if (word <= w1) atomicOr(&s_mask[word], m);
+                bit = (word + 1u) << 5;
             }
         }
     }
-    const bool any_all = __syncthreads_or(all_bits ? 1 : 0) != 0;
-    for (uint32_t i = threadIdx.x; i < n_words; i += 256u) {
-        const uint32_t v = any_all ? 0xffffffffu : s_mask[i];
+    __syncthreads();
+    for (uint32_t i = w0 + threadIdx.x; i <= w1; i += 256u) {
+        const uint32_t v = s_mask[i];
         if (v) atomicOr(&out[i], v);
     }
 }
@@ -559,14 +574,16 @@ __global__ __launch_bounds__(256) void volym_tile_depth_kernel(const uint8_t* __
 {
     __shared__ uint32_t s_near[VOLYM_TILE_DEPTH_LDS], s_far[VOLYM_TILE_DEPTH_LDS];
     __shared__ uint32_t s_rect[4];                       // union of the block's rectangles: min tx0, min ty0, max tx1, max ty1
-    if (threadIdx.x == 0u) { s_rect[0] = 0xffffffffu; s_rect[1] = 0xffffffffu; s_rect[2] = 0u; s_rect[3] = 0u; }
-    __syncthreads();
     const uint32_t nbx = (mc_n + 7u) / 8u, nby = (mc_n + 7u) / 8u;
     const uint32_t bx = blockIdx.x % nbx, by = (blockIdx.x / nbx) % nby, bz = blockIdx.x / (nbx * nby);
     const uint32_t cx = bx * 8u + (threadIdx.x & 7u), cy = by * 8u + ((threadIdx.x >> 3) & 7u), cz = bz * 4u + (threadIdx.x >> 6);
+    const bool occupied = cx < mc_n && cy < mc_n && cz < mc_n && mc_max[cx + mc_n * (cy + mc_n * cz)] >= thr_byte;
+    if (!__syncthreads_or(occupied ? 1 : 0)) return;     // a block without an occupied cell folds nothing (as in the mask kernel)
+    if (threadIdx.x == 0u) { s_rect[0] = 0xffffffffu; s_rect[1] = 0xffffffffu; s_rect[2] = 0u; s_rect[3] = 0u; }
+    __syncthreads();
     CellRect r = {0u, 0u, 0u, 0u, false, false};
     uint32_t ne = 0u, fe = 0u;
-    if (cx < mc_n && cy < mc_n && cz < mc_n && mc_max[cx + mc_n * (cy + mc_n * cz)] >= thr_byte) {
+    if (occupied) {
         r = cell_tile_rect(M, cx, cy, cz, mc_n, margin, W, H);
         if (r.on && !r.bad) {
             float lo[3], hi[3];

@@ -79,6 +79,33 @@ static int upload_volume(volym_ctx* c, uint8_t** dst, const uint8_t* src, uint32
 
 // ---- macro cells ------------------------------------------------------------------------------------------------------
 
+extern "C" {
+
+int volym_cells_meeting_box(uint32_t n_cells, uint32_t dim, uint32_t lo, uint32_t hi, uint32_t* c0, uint32_t* c1)
+{
+    if (!c0 || !c1 || n_cells == 0u || n_cells > 4096u || dim == 0u || dim > 65536u) return VOLYM_E_INVALID;
+    // mc_voxel_lo and mc_voxel_hi do not decrease with the cell: the cells that meet [lo, hi) are consecutive
+    uint32_t a = n_cells, b = 0;
+    if (lo < hi)
+        for (uint32_t k = 0; k < n_cells; ++k)
+            if (mc_voxel_lo(k, dim, n_cells) < hi && mc_voxel_hi(k, dim, n_cells) > lo) { a = std::min(a, k); b = k + 1u; }
+    *c0 = a < b ? a : 0u; *c1 = a < b ? b : 0u;
+    return VOLYM_OK;
+}
+
+uint32_t volym_bounds_cells_for(const uint32_t dims[3], uint32_t macro_cells)
+{
+    if (!dims) return macro_cells;
+    const uint32_t longest = std::max(dims[0], std::max(dims[1], dims[2]));
+    uint32_t n = 1;
+    while (n < VOLYM_BOUNDS_CELLS_DEFAULT_MAX && 4u * n <= longest) n *= 2u;         // the largest power of two with 2 * n <= longest, at most the cap
+    return std::max(n, macro_cells);
+}
+
+}  // extern "C"
+
+static int launch_fine_grid(volym_ctx* c);
+
 // the maxima of one range of cells, on slot 0's stream
 static int launch_macro_cells(volym_ctx* c, const CellRange& r)
 {
@@ -86,6 +113,29 @@ static int launch_macro_cells(volym_ctx* c, const CellRange& r)
                        c->bricked ? 1u : 0u, r);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
+}
+
+// the fine maxima (the grid of the tile mask and the depth bounds) of one range of fine cells, on slot 0's stream
+static int launch_fine_cells(volym_ctx* c, const CellRange& r)
+{
+    const uint32_t total = r.cn[0] * r.cn[1] * r.cn[2];
+    hipLaunchKernelGGL(volym_fine_cell_kernel, dim3((total + 255u) / 256u), dim3(256), 0, c->slot0().stream, c->d_vol, c->d_mc_fine, c->nx, c->ny, c->nz, c->fine_n,
+                       c->bricked ? 1u : 0u, r);
+    HIPCHK(c, hipGetLastError());
+    return VOLYM_OK;
+}
+
+// The cells of a grid of n_cells per axis whose voxel range (slack included) meets box {x0, y0, z0, x1, y1, z1}; false: none
+static bool cells_meeting_box(const volym_ctx* c, uint32_t n_cells, const uint32_t box[6], CellRange& r)
+{
+    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
+    for (int a = 0; a < 3; ++a) {
+        uint32_t c0 = 0, c1 = 0;
+        (void)volym_cells_meeting_box(n_cells, dims[a], box[a], box[3 + a], &c0, &c1);
+        if (c0 >= c1) return false;
+        r.c0[a] = c0; r.cn[a] = c1 - c0;
+    }
+    return true;
 }
 
 // The host's copy of the maxima (behind the launches on slot 0's stream that wrote them) and the occupied-cell AABB for every
@@ -137,30 +187,51 @@ int volym::build_macro_cells(volym_ctx* c)
     }
     if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(macro cells): ") + hipGetErrorString(e));
     rc = launch_macro_cells(c, CellRange{{0u, 0u, 0u}, {n, n, n}});
-    if (rc == VOLYM_OK) rc = read_macro_cells(c);
+    if (rc == VOLYM_OK) rc = launch_fine_grid(c);
+    if (rc == VOLYM_OK) rc = read_macro_cells(c);         // (waits for the stream: the fine maxima are there too)
     if (rc != VOLYM_OK) return rc;
     c->have_vol = true;
     c->have_frame = had_frame;
     return VOLYM_OK;
 }
 
-// The maxima of the macro cells whose voxel range (slack included) meets one of n boxes of rewritten texels (the others cover no
-// texel that changed), their host copy and the occupied-cell boxes; every slot's distance field and hulls become stale.
+// The grid of the per-view tile mask and depth bounds for the volume's dimensions, mc_n and VOLYM_OPT_BOUNDS_CELLS: d_mc_fine and
+// fine_n, or no grid of its own (d_mc_fine NULL, fine_n = mc_n) where the two coincide.  Every slot is idle.  Enqueues on slot
+// 0's stream and does not wait.
+static int launch_fine_grid(volym_ctx* c)
+{
+    if (c->d_mc_fine) { HIPCHK(c, hipFree(c->d_mc_fine)); c->d_mc_fine = nullptr; }
+    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
+    uint32_t n = c->bounds_cells < 0 ? volym_bounds_cells_for(dims, c->mc_n) : static_cast<uint32_t>(c->bounds_cells);
+    n = std::max(n, c->mc_n);                        // (0, the macro-cell grid; an explicit value from before mc_n grew)
+    c->fine_n = n;
+    for (int i = 0; i < c->n_slots(); ++i) c->slots[i]->hull_dirty = true;
+    if (n == c->mc_n) return VOLYM_OK;
+    const hipError_t e = hipMalloc(&c->d_mc_fine, static_cast<size_t>(n) * n * n);
+    if (e != hipSuccess) { c->d_mc_fine = nullptr; c->fine_n = c->mc_n; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(fine cells): ") + hipGetErrorString(e)); }
+    return launch_fine_cells(c, CellRange{{0u, 0u, 0u}, {n, n, n}});
+}
+
+// VOLYM_OPT_BOUNDS_CELLS changed: the fine grid alone, for the volume the context holds (set-up path: blocks)
+int volym::build_fine_cells(volym_ctx* c)
+{
+    int rc = quiesce_slots(c);
+    if (rc == VOLYM_OK) rc = launch_fine_grid(c);
+    if (rc != VOLYM_OK) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));       // every slot's next view reads the new grid
+    return VOLYM_OK;
+}
+
+// The maxima of the macro cells and of the fine cells whose voxel range (slack included) meets one of n boxes of rewritten texels
+// (the others cover no texel that changed), the macro cells' host copy and the occupied-cell boxes; every slot's distance field and hulls become stale.
 static int refresh_macro_cells(volym_ctx* c, const uint32_t (*boxes)[6], uint32_t n)
 {
-    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
     for (uint32_t i = 0; i < n; ++i) {
         CellRange r;
-        bool any = true;
-        for (int a = 0; a < 3; ++a) {
-            uint32_t c0 = c->mc_n, c1 = 0;
-            for (uint32_t k = 0; k < c->mc_n; ++k)
-                if (mc_voxel_lo(k, dims[a], c->mc_n) < boxes[i][3 + a] && mc_voxel_hi(k, dims[a], c->mc_n) > boxes[i][a]) { c0 = std::min(c0, k); c1 = k + 1u; }
-            any = any && c0 < c1;
-            r.c0[a] = c0; r.cn[a] = any ? c1 - c0 : 0u;
-        }
-        if (!any) continue;
-        const int rc = launch_macro_cells(c, r);
+        // (the fine cells nest in the macro cells, voxel ranges included: where no macro cell meets the box, no fine cell does)
+        if (!cells_meeting_box(c, c->mc_n, boxes[i], r)) continue;
+        int rc = launch_macro_cells(c, r);
+        if (rc == VOLYM_OK && c->d_mc_fine && cells_meeting_box(c, c->fine_n, boxes[i], r)) rc = launch_fine_cells(c, r);
         if (rc != VOLYM_OK) return rc;
     }
     const int rc = read_macro_cells(c);

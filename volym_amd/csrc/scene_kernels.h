@@ -50,6 +50,29 @@ __global__ __launch_bounds__(256) void volym_macrocell_kernel(const uint8_t* __r
     }
 }
 
+// The same maxima for the finer grid of the per-view tile mask and depth bounds (volym_ctx::d_mc_fine): a cell of the fine_n^3 grid
+// is defined as a macro cell is, by mc_voxel_lo / mc_voxel_hi with fine_n.  Its voxel range is a few voxels per axis (2 + 2 of
+// slack at 256^3 and 128 cells), so one thread per cell of the range `cells`, x fastest: neighbouring lanes read neighbouring
+// runs of a row.  An axis shorter than fine_n gives cells that share voxels, never an empty range (the loops would leave 0).
+__global__ __launch_bounds__(256) void volym_fine_cell_kernel(const uint8_t* __restrict__ vol, uint8_t* __restrict__ fine_max,
+                                                              uint32_t nx, uint32_t ny, uint32_t nz, uint32_t fine_n, uint32_t bricked, CellRange cells)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cells.cn[0] * cells.cn[1] * cells.cn[2]) return;
+    const uint32_t cx = cells.c0[0] + i % cells.cn[0], cy = cells.c0[1] + (i / cells.cn[0]) % cells.cn[1], cz = cells.c0[2] + i / (cells.cn[0] * cells.cn[1]);
+    const uint32_t x0 = mc_voxel_lo(cx, nx, fine_n), x1 = mc_voxel_hi(cx, nx, fine_n), y0 = mc_voxel_lo(cy, ny, fine_n), y1 = mc_voxel_hi(cy, ny, fine_n),
+                   z0 = mc_voxel_lo(cz, nz, fine_n), z1 = mc_voxel_hi(cz, nz, fine_n);
+    const uint32_t bx = layout_bx(bricked != 0u, nx), bxy = layout_bxy(bricked != 0u, nx, ny);
+    uint32_t m = 0;
+    for (uint32_t z = z0; z < z1; ++z)
+        for (uint32_t y = y0; y < y1; ++y)
+            for (uint32_t x = x0; x < x1; ++x) {
+                const uint32_t v = vol[layout_offset(bricked != 0u, bx, bxy, x, y, z)];
+                m = v > m ? v : m;
+            }
+    fine_max[(cz * fine_n + cy) * fine_n + cx] = static_cast<uint8_t>(m);
+}
+
 // linear (x fastest) staging copy -> 4x4x4 bricks; one thread per voxel of the padded grid
 __global__ __launch_bounds__(256) void volym_rebrick_kernel(const uint8_t* __restrict__ linear, uint8_t* __restrict__ bricked,
                                                             uint32_t nx, uint32_t ny, uint32_t nz)

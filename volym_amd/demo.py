@@ -190,6 +190,21 @@ class GpuContext:
         self._ck(_lib.lib().volym_read_rgba32f(self.handle, scene._f32p(out)))
         return out
 
+    def read_tile_bounds(self):
+        """The tile mask and depth bounds of the latest pass's view (volym_read_tile_bounds): (mask, near, far), each of shape
+        (8x8 tiles per column, per row); mask is bool.  VolymError E_STATE while the view has no mask."""
+        L = _lib.lib()
+        tx, ty, words = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(L.volym_tile_bounds_size(self.handle, C.byref(tx), C.byref(ty), C.byref(words)))
+        bits = np.zeros(max(words.value, 1), np.uint32)
+        near = np.zeros(32 * max(words.value, 1), np.float32)
+        far = np.zeros_like(near)
+        self._ck(L.volym_read_tile_bounds(self.handle, bits.ctypes.data_as(C.POINTER(C.c_uint32)), scene._f32p(near), scene._f32p(far)))
+        n = tx.value * ty.value
+        mask = ((bits[np.arange(n) >> 5] >> (np.arange(n) & 31).astype(np.uint32)) & 1).astype(bool)
+        shape = (ty.value, tx.value)
+        return mask.reshape(shape), near[:n].reshape(shape), far[:n].reshape(shape)
+
     def local_tiles(self):
         return int(_lib.lib().volym_local_tiles(self.handle))
 
