@@ -531,6 +531,86 @@ int volym_slice_axis(int axis, uint32_t index, const uint32_t dims[3], volym_sli
  * or a pixel outside width x height.  Pure host arithmetic. */
 int volym_slice_texel(const volym_slice* slice, uint32_t i, uint32_t j, int32_t t[3]);
 
+/* --- projection (new; the reference has none) ------------------------------------------------------------------------- */
+/* Maximum and mean intensity along the view rays: the brightest sample of every ray (where it is, what segment it lies in) and
+ * the mean of all its samples ("X-ray").  It reads the bytes of the scene as they stand -- box, plane and mask are in them -- and
+ * writes only its records and its image.
+ *   The rule (integers wherever something is decided; scene.project_frame of the Python package is its host twin, equal in every
+ * byte).  Pixel (gx, gy) of the W x H frame has the ray of the last volym_update: o, d, t_entry, t_exit, hit (wgsl:221-241).  With
+ * `step` from the call, sample k = 0, 1, 2, ... lies at t_k = t_entry + (float)k * step -- f32, one multiply, one add, not fused --
+ * and exists while t_k < t_exit; t_k does not decrease with k, so the samples are a prefix and n_samples is their count (at least
+ * 1 on a hit ray, at most 65535: the path through the cube is at most sqrt(3)).  Positions are not accumulated: a sample depends on
+ * k alone.  Sample k reads the density byte b_k of texel clamp(floor(pos * n), 0, n - 1), pos = o + d * t_k: the march's nearest
+ * fetch, whatever filter the volume was given.  max is the largest b_k and k* the SMALLEST k that attains it: the running maximum
+ * starts at 0 and only a strictly greater byte replaces it, so a ray of zeros has max 0 and no position.  mean =
+ * (2 * sum + n_samples) / (2 * n_samples) over the integers, sum the sum of all b_k.  A record holds both, whatever the mode.
+ *   The image: a miss is `background`; otherwise v = max (MAX) or mean (MEAN) and the base is (v, v, v, 255), or with TF the r, g,
+ * b of texel (v * tf_n) >> 8 of the table volym_set_transfer_function received with alpha 255 (the slice pass's rule); with LABELS
+ * (MAX only) and status 2, palette[label] is blended over the base by the outline's formula (at volym_outline). */
+enum { VOLYM_PROJECT_MAX = 0, VOLYM_PROJECT_MEAN = 1 };                                    /* mode */
+enum { VOLYM_PROJECT_TF = 1, VOLYM_PROJECT_LABELS = 2, VOLYM_PROJECT_NO_SKIP = 4 };        /* flags */
+typedef struct volym_project {
+    float    step;              /* distance between samples along the ray, [1e-4, 1]: volym_update's range for the march step */
+    uint32_t mode, flags;
+    uint8_t  background[4];     /* image: pixels whose ray misses the cube */
+    uint8_t  palette[256][4];   /* LABELS: colour per label value, alpha = strength */
+} volym_project;                /* 1040 bytes */
+struct volym_projection {
+    float    t;          /* t_{k*}: ray parameter of the first sample that attains the maximum; -1 when status < 2 */
+    uint16_t x, y, z;    /* texel of that sample, the coordinates volym_set_crop_box takes; 0 when status < 2 */
+    uint8_t  max;        /* the largest density byte among the ray's samples */
+    uint8_t  mean;       /* (2 * sum + n_samples) / (2 * n_samples); 0 on a miss */
+    uint8_t  label;      /* label byte of that texel; 0 when status < 2 or without labels of the volume's dimensions on the device */
+    uint8_t  status;     /* 0 = the ray misses the cube, 1 = hit with max == 0, 2 = hit with max > 0 */
+    uint16_t n_samples;  /* 0 on a miss */
+};
+#if defined(__cplusplus)
+static_assert(sizeof(volym_project) == 1040, "volym_project is 1040 bytes");
+static_assert(sizeof(struct volym_projection) == 16, "volym_projection is 16 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_project) == 1040, "volym_project is 1040 bytes");
+_Static_assert(sizeof(struct volym_projection) == 16, "volym_projection is 16 bytes");
+#endif
+/* Enqueue only: one kernel over the rect {x0, y0, w, h} (NULL = the whole frame) on the first slot's stream, where the pick passes
+ * go (a caller's stream when one is set); with VOLYM_OPT_FRAMES_IN_FLIGHT = 2 it uses the first slot alone.  It ignores the shard:
+ * every rank holds the whole volume.  It only reads the scene and writes no frame buffer: a frame enqueued before or after it is
+ * byte for byte the frame without it.
+ *   records_device: caller device memory of w * h records, row-major within the rect, or NULL for records the context owns
+ * (volym_read_projection, volym_projection_device_ptr); those grow to the largest rect asked for so far, and the call blocks only
+ * when they have to grow.  image_rgba8: caller device memory of w * h * 4 bytes, row-major within the rect, or NULL for no image.
+ * volym_project_image_pass is the same pass with records and image both in buffers the context owns (volym_read_projection_image,
+ * volym_projection_image_device_ptr): two plain calls instead of a sentinel pointer.  Records and image leave the same launch.
+ *   By default the march skips samples that cannot change the record: those inside a macro cell (VOLYM_OPT_MACRO_CELLS) whose
+ * maximum is 0, which add nothing to the sum and never exceed the running maximum.  A record holds max and mean of the same
+ * ray, so a cell whose maximum is merely not above the running maximum still has to be read for the sum.  NO_SKIP reads every
+ * sample; both paths give the same records for every ray.
+ *   VOLYM_E_INVALID: NULL ctx or volym_project, what volym_project_check refuses, an empty rect or one outside the frame.
+ * VOLYM_E_STATE: no volume, no volym_update yet or the volume changed since; LABELS without labels of the volume's dimensions on
+ * the device; TF without a transfer function. */
+int   volym_project_pass(volym_ctx* ctx, const volym_project* p, const uint32_t rect[4], void* records_device, void* image_rgba8);
+int   volym_project_image_pass(volym_ctx* ctx, const volym_project* p, const uint32_t rect[4]);
+/* Blocks; the w * h records of the latest pass into the context's own records.  VOLYM_E_STATE before any such pass. */
+int   volym_read_projection(volym_ctx* ctx, struct volym_projection* out);
+/* Blocks; w * h * 4 bytes of the latest volym_project_image_pass.  VOLYM_E_STATE before any. */
+int   volym_read_projection_image(volym_ctx* ctx, uint8_t* out);
+/* The context's own buffers after the latest pass into them, NULL before any.  A later, larger rect may move them. */
+void* volym_projection_device_ptr(volym_ctx* ctx);
+void* volym_projection_image_device_ptr(volym_ctx* ctx);
+/* Rect size {w, h} of the latest pass into the context's own records / own image, {0, 0} before any: what the two reads copy,
+ * so that a caller sizes its buffer from the context and not from a note of its own. */
+int   volym_projection_size(volym_ctx* ctx, uint32_t size[2]);
+int   volym_projection_image_size(volym_ctx* ctx, uint32_t size[2]);
+/* A MAX pass without flags over the one pixel (x, y) plus the read.  Blocks.  The record goes through a 16-byte buffer of the
+ * call's own: the context's own records, their size and volym_projection_device_ptr stay what the latest pass made them. */
+int   volym_project_at(volym_ctx* ctx, uint32_t x, uint32_t y, float step, struct volym_projection* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a step that is not finite or outside [1e-4, 1], an unknown
+ * mode or flag bit, LABELS with MEAN.  Pure host arithmetic. */
+int   volym_project_check(const volym_project* p);
+/* The count rule: *n = the number of k >= 0 with t_entry + (float)k * step < t_exit in f32 (0 when t_exit <= t_entry).
+ * VOLYM_E_INVALID for NULL, a step outside [1e-4, 1] or a t that is not finite or outside [0, 128] (up to there t_k grows with
+ * every k).  Pure host arithmetic; the kernel's count agrees with it on every ray. */
+int   volym_project_samples(float t_entry, float t_exit, float step, uint32_t* n);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

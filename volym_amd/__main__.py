@@ -15,7 +15,9 @@ depth) as one JSON line.  --outline NAME[,NAME...] (segment names, ids or label 
 pixel) write the annotated image instead: a ring round the segments and a tint over them (demo.Simple.highlight).
 --slice AXIS,INDEX writes the slice view beside the frame -- the plane normal to x, y or z through texel INDEX, transfer-function
 colours, segments overlaid, cut texels tinted (demo.Simple.slice) -- as <screenshot>_slice_<axis>.png; --slice-at X,Y the three
-orthogonal slices through the texel pixel (X, Y) shows.
+orthogonal slices through the texel pixel (X, Y) shows.  --project MAX|MEAN[,STEP] writes the projection view -- maximum or mean
+intensity along the rays of the same view, STEP apart (default: a quarter of the march step) -- as <screenshot>_project_<mode>.png
+(demo.Simple.project).
 """
 import argparse
 import csv
@@ -192,6 +194,17 @@ def _slice_arg(text):
     return v[0], int(v[1])
 
 
+def _project_arg(text):
+    """--project MAX,0.002 -> ("MAX", 0.002); --project mean -> ("MEAN", None)"""
+    v = [t.strip() for t in text.split(",")]
+    try:
+        if len(v) not in (1, 2) or v[0].upper() not in ("MAX", "MEAN"):
+            raise ValueError
+        return v[0].upper(), (float(v[1]) if len(v) == 2 else None)
+    except ValueError:
+        raise SystemExit("--project: MAX or MEAN, then optionally the distance between samples")
+
+
 def _slice_path(path, axis):
     stem = path[:-4] if path.lower().endswith(".png") else path
     return "%s_slice_%s.png" % (stem, axis)
@@ -243,12 +256,24 @@ def run_simple(args):
                 slices.update(sliced_at.pop("slices") or {})
         except ValueError as e:
             raise SystemExit("--slice: %s" % e)
+        projection = None
+        if getattr(args, "project", None):
+            mode, step = _project_arg(args.project)
+            try:
+                d.project(ctx, mode, step, tf=True)
+            except ValueError as e:
+                raise SystemExit("--project: %s" % e)
+            projection = (mode.lower(), ctx.read_projection_image())
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
     for axis, img in sorted(slices.items()):
         image.write_png(_slice_path(path, axis), img)
         print("slice %s: %dx%d -> %s" % (axis, img.shape[1], img.shape[0], _slice_path(path, axis)))
+    if projection is not None:
+        stem = path[:-4] if path.lower().endswith(".png") else path
+        image.write_png("%s_project_%s.png" % (stem, projection[0]), projection[1])
+        print("project %s: %dx%d -> %s_project_%s.png" % (projection[0], W, H, stem, projection[0]))
     if sliced_at is not None:
         import json
         print(json.dumps(sliced_at))   # one line: the pick the three slices of --slice-at go through
@@ -362,6 +387,7 @@ def main(argv=None):
     run.add_argument("--outline", help="NAME[,NAME...]: segment names, ids or label values to outline and tint; the PNG is the annotated image")
     run.add_argument("--outline-at", help="X,Y: outline the segment pixel (X, Y) shows; the PNG is the annotated image")
     run.add_argument("--slice", help="AXIS,INDEX: also write the slice normal to x, y or z through texel INDEX as <screenshot>_slice_<axis>.png")
+    run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359

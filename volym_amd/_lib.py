@@ -101,6 +101,36 @@ class Slice(C.Structure):
     ]
 
 
+PROJECT_MAX, PROJECT_MEAN = 0, 1                               # volym_project.mode
+PROJECT_TF, PROJECT_LABELS, PROJECT_NO_SKIP = 1, 2, 4          # volym_project.flags
+
+
+class Project(C.Structure):
+    """volym_project (include/volym_hip.h): step, mode, flags and colours of one projection pass, 1040 bytes"""
+    _fields_ = [
+        ("step", C.c_float),
+        ("mode", C.c_uint32), ("flags", C.c_uint32),
+        ("background", C.c_uint8 * 4),
+        ("palette", (C.c_uint8 * 4) * 256),
+    ]
+
+
+class Projection(C.Structure):
+    """volym_projection (include/volym_hip.h): the record of one projected ray, 16 bytes"""
+    _fields_ = [
+        ("t", C.c_float),
+        ("x", C.c_uint16), ("y", C.c_uint16), ("z", C.c_uint16),
+        ("max", C.c_uint8), ("mean", C.c_uint8), ("label", C.c_uint8), ("status", C.c_uint8),
+        ("n_samples", C.c_uint16),
+    ]
+
+
+# the same record as a NumPy structured dtype (GpuContext.read_projection)
+PROJECTION_DTYPE = np.dtype([("t", "<f4"), ("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("max", "u1"), ("mean", "u1"), ("label", "u1"),
+                             ("status", "u1"), ("n_samples", "<u2")])
+PROJECTION_MISS, PROJECTION_EMPTY, PROJECTION_HIT = 0, 1, 2   # volym_projection.status
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -226,6 +256,17 @@ SIGNATURES = {
     "volym_slice_check": (C.c_int, [C.POINTER(Slice)]),
     "volym_slice_axis": (C.c_int, [C.c_int, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(Slice)]),
     "volym_slice_texel": (C.c_int, [C.POINTER(Slice), C.c_uint32, C.c_uint32, C.POINTER(C.c_int32)]),
+    "volym_project_pass": (C.c_int, [_ctx, C.POINTER(Project), C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p]),
+    "volym_project_image_pass": (C.c_int, [_ctx, C.POINTER(Project), C.POINTER(C.c_uint32)]),
+    "volym_read_projection": (C.c_int, [_ctx, C.POINTER(Projection)]),
+    "volym_read_projection_image": (C.c_int, [_ctx, _u8p]),
+    "volym_projection_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_projection_image_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_projection_size": (C.c_int, [_ctx, C.POINTER(C.c_uint32)]),
+    "volym_projection_image_size": (C.c_int, [_ctx, C.POINTER(C.c_uint32)]),
+    "volym_project_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(Projection)]),
+    "volym_project_check": (C.c_int, [C.POINTER(Project)]),
+    "volym_project_samples": (C.c_int, [C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

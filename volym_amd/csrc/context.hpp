@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -200,6 +200,15 @@ struct volym_ctx {
     size_t slice_capacity = 0;               // pixels d_slice holds
     uint32_t slice_w = 0, slice_h = 0;       // size of the latest pass into d_slice (0: none yet)
 
+    // projection passes (volym_project_pass, project.hip): the context's own records and image, each grown to the largest rect asked
+    // for so far; written on slot 0's stream
+    volym_projection* d_projection = nullptr;
+    uint32_t* d_projection_image = nullptr;
+    size_t projection_capacity = 0, projection_image_capacity = 0;      // records / pixels they hold
+    uint32_t projection_w = 0, projection_h = 0;                        // rect size of the latest pass into d_projection (0: none yet)
+    uint32_t projection_image_w = 0, projection_image_h = 0;            // ... and into d_projection_image
+    volym_projection* d_projection_at = nullptr;                        // the one record of volym_project_at, allocated on first use
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -252,6 +261,8 @@ int launch_pick(volym_ctx* c, FrameSlot& s, const uint32_t rect[4], float alpha_
 void free_outline(volym_ctx* c);
 // slice.hip: what the context keeps for the slice pass (every stream idle)
 void free_slice(volym_ctx* c);
+// project.hip: what the context keeps for the projection pass (every stream idle)
+void free_projection(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume

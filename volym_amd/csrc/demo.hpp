@@ -78,6 +78,17 @@ struct SliceView {
     void* target_rgba8 = nullptr;            // device memory of width * height * 4 bytes; NULL: the context's own target (volym_read_slice)
 };
 
+// How Simple::project draws: what the image shows, the overlays, and the rect.  Records and image go to the context's own buffers.
+struct ProjectView {
+    float step = 0.0f;                       // distance between samples; 0: the march's dense step, 0.25 * raymarching_step_size
+    bool tf = false;                         // colour through the transfer function
+    bool labels = true;                      // MAX: the segment of the brightest sample as a colour overlay
+    bool no_skip = false;                    // read every sample (the A/B partner of the default path)
+    uint8_t strength = 96;                   // alpha of the overlay's colours
+    uint8_t background[4] = {0, 0, 0, 255};
+    const uint32_t* rect = nullptr;          // {x0, y0, w, h}; NULL: the whole frame
+};
+
 class Simple : public ComputeDemo {
 public:
     static Simple init(const GpuContext& ctx, const volym_state& state, const SimpleAssets& a)
@@ -106,6 +117,7 @@ public:
         ctx.check(volym_update(ctx.handle(), &cam, &par));
         records_current_ = false;      // (highlight: the pick records of the old view are stale)
         for (int i = 0; i < 3; ++i) eye_[i] = state.camera.position[i];      // (clip_at: the plane faces the eye)
+        dense_step_ = 0.25f * par.raymarching_step_size;                     // (project: the march's dense step)
     }
     void compute_pass(const GpuContext& ctx) override { ctx.check(volym_compute_pass(ctx.handle())); }   // src/demos/pipeline.rs:62-102
 
@@ -341,6 +353,12 @@ public:
         out.picked = pick(ctx, a, x, y, alpha_min);
         if (out.picked.record.status != 2) return false;
         const uint32_t t[3] = {out.picked.record.x, out.picked.record.y, out.picked.record.z};
+        slices_through(ctx, a, t, out, v);
+        return true;
+    }
+    // the three orthogonal slices through texel t, read back into out.slices / out.images
+    void slices_through(const GpuContext& ctx, const SimpleAssets& a, const uint32_t t[3], Slices& out, const SliceView& v)
+    {
         SliceView own = v;
         own.target_rgba8 = nullptr;
         for (int axis = 0; axis < 3; ++axis) {
@@ -348,6 +366,53 @@ public:
             out.images[axis].resize(static_cast<size_t>(out.slices[axis].width) * out.slices[axis].height * 4);
             ctx.check(volym_read_slice(ctx.handle(), out.images[axis].data()));
         }
+    }
+    // New: the projection view -- maximum (VOLYM_PROJECT_MAX) or mean (VOLYM_PROJECT_MEAN, the X-ray) intensity along the rays of the
+    // current view, through the scene as it stands (volym_project_image_pass).  The labels go to the device first if they are not
+    // there yet.  Records and image go to the context's own buffers (volym_read_projection, volym_read_projection_image).
+    // Returns the request.
+    volym_project project(const GpuContext& ctx, const SimpleAssets& a, uint32_t mode, const ProjectView& v = ProjectView())
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);      // (the records name the segment either way)
+        volym_project p{};
+        p.step = v.step > 0.0f ? v.step : dense_step_;
+        p.mode = mode;
+        p.flags = (v.tf ? VOLYM_PROJECT_TF : 0u) | (v.no_skip ? VOLYM_PROJECT_NO_SKIP : 0u);
+        if (v.labels && mode == VOLYM_PROJECT_MAX && labels_on_device_) p.flags |= VOLYM_PROJECT_LABELS;
+        for (int i = 0; i < 4; ++i) p.background[i] = v.background[i];
+        segment_palette(a, v.strength, p.palette);
+        ctx.check(volym_project_image_pass(ctx.handle(), &p, v.rect));
+        return p;
+    }
+    // New: the brightest sample of the ray of pixel (x, y) (volym_project_at): the record, the name of the segment with its label
+    // (empty: none, or no labels) and the texel's centre in the unit-cube coordinates set_crop takes.  step 0: the dense step.
+    struct Projected {
+        struct volym_projection record;
+        std::string segment;
+        float pos[3];
+    };
+    Projected project_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, float step = 0.0f)
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        Projected p{};
+        ctx.check(volym_project_at(ctx.handle(), x, y, step > 0.0f ? step : dense_step_, &p.record));
+        if (p.record.status == 2) {
+            p.pos[0] = (p.record.x + 0.5f) / a.nx; p.pos[1] = (p.record.y + 0.5f) / a.ny; p.pos[2] = (p.record.z + 0.5f) / a.nz;
+            if (labels_on_device_)
+                for (const SegmentInfo& s : a.segments)
+                    if (s.label_value == p.record.label) { p.segment = s.name; break; }
+        }
+        return p;
+    }
+    // New: click the bright spot -- the three orthogonal slices through the texel of the maximum along the ray of pixel (x, y), read
+    // back as slices_at reads them (out.picked stays empty).  False: the ray shows nothing.
+    bool brightest_slices_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, Projected& at, Slices& out, const SliceView& v = SliceView(),
+                             float step = 0.0f)
+    {
+        at = project_at(ctx, a, x, y, step);
+        if (at.record.status != 2) return false;
+        const uint32_t t[3] = {at.record.x, at.record.y, at.record.z};
+        slices_through(ctx, a, t, out, v);
         return true;
     }
     // a colour per label value of the segments table for the slice overlay: hues spread by the golden angle over the label values,
@@ -381,6 +446,7 @@ public:
 
 private:
     float eye_[3] = {0.0f, 0.0f, 0.0f};
+    float dense_step_ = 0.0025f;
     bool labels_on_device_ = false;
     bool records_current_ = false;             // the device holds the records of a whole-frame pick pass of the current view and scene
     float records_alpha_min_ = 0.0f;

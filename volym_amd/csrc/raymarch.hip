@@ -537,6 +537,7 @@ void volym_destroy(volym_ctx* c)
     (void)hipFree(c->d_picks);
     free_outline(c);
     free_slice(c);
+    free_projection(c);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }

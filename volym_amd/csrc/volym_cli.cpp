@@ -7,8 +7,10 @@
 //               A trial is --secs of back-to-back compute passes timed with HIP events (the reference counts
 //               presented frames over 2 s of wall clock, blit/GUI/vsync included).
 //   run simple: one frame of the interactive default view (src/state.rs:41-55) to frame.ppm; --slice AXIS,INDEX also writes the
-//   slice normal to x, y or z through that texel (Simple::slice) to frame_slice_<axis>.ppm.
+//   slice normal to x, y or z through that texel (Simple::slice) to frame_slice_<axis>.ppm; --project MAX|MEAN[,STEP] the
+//   maximum or mean intensity projection of the view (Simple::project) to frame_project_<mode>.ppm.
 #include <algorithm>
+#include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -48,6 +50,8 @@ struct Options {
     std::vector<uint8_t> hide;     // --hide 3,4: label values of the segments to hide (run simple)
     int slice_axis = -1;           // --slice z,128: also write the slice normal to that axis through that texel (run simple)
     uint32_t slice_index = 0;
+    int project_mode = -1;         // --project MAX|MEAN[,STEP]: also write the projection view (run simple)
+    float project_step = 0.0f;     // 0: the march's dense step
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -193,6 +197,23 @@ int run_simple(const Options& o)
         for (size_t i = 0; i < static_cast<size_t>(s.width) * s.height; ++i) sf.write(reinterpret_cast<const char*>(&img[4 * i]), 3);
         std::printf("slice %c: %ux%u -> %s\n", "xyz"[o.slice_axis], s.width, s.height, spath.c_str());
     }
+    if (o.project_mode >= 0) {
+        // the projection view of the same camera: transfer-function colours, over MAX the brightest sample's segment
+        ProjectView view;
+        view.step = o.project_step;
+        view.tf = true;
+        demo.project(ctx, assets, static_cast<uint32_t>(o.project_mode), view);
+        std::vector<uint8_t> img(static_cast<size_t>(W) * H * 4);
+        ctx.check(volym_read_projection_image(ctx.handle(), img.data()));
+        const size_t dot = path.rfind('.');
+        const std::string stem = dot == std::string::npos ? path : path.substr(0, dot), ext = dot == std::string::npos ? std::string(".ppm") : path.substr(dot);
+        const char* mode = o.project_mode == VOLYM_PROJECT_MEAN ? "mean" : "max";
+        const std::string ppath = stem + "_project_" + mode + ext;
+        std::ofstream pf(ppath, std::ios::binary);
+        pf << "P6\n" << W << ' ' << H << "\n255\n";
+        for (size_t i = 0; i < static_cast<size_t>(W) * H; ++i) pf.write(reinterpret_cast<const char*>(&img[4 * i]), 3);
+        std::printf("project %s: %ux%u -> %s\n", mode, W, H, ppath.c_str());
+    }
     return 0;
 }
 
@@ -255,7 +276,20 @@ int main(int argc, char** argv)
                 o.slice_axis = static_cast<int>(axis);
                 o.slice_index = static_cast<uint32_t>(index);
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index]\n"); return 2; }
+            else if (a == "--project") {
+                const std::string v = next();
+                const size_t comma = v.find(',');
+                std::string mode = v.substr(0, comma);
+                for (char& ch : mode) ch = static_cast<char>(std::toupper(static_cast<unsigned char>(ch)));
+                size_t used = 0;
+                float step = 0.0f;
+                if (comma != std::string::npos) { try { step = std::stof(v.substr(comma + 1), &used); } catch (const std::exception&) { used = 0; } }
+                if ((mode != "MAX" && mode != "MEAN") || (comma != std::string::npos && (used == 0 || used != v.size() - comma - 1 || !(step > 0.0f))))
+                    throw Error(VOLYM_E_INVALID, "--project: MAX or MEAN, then optionally the distance between samples");
+                o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
+                o.project_step = step;
+            }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

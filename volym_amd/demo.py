@@ -329,6 +329,62 @@ class GpuContext:
         """The context's own slice target after the latest pass into it (None before any)."""
         return _lib.lib().volym_slice_device_ptr(self.handle)
 
+    # ---- projection ---------------------------------------------------------------------------
+    def project_pass(self, projection, rect=None, records_ptr=None, image_ptr=None, own_image=False):
+        """Enqueue one projection pass (include/volym_hip.h volym_project_pass; scene.project_frame is its definition): maximum and
+        mean intensity along the rays of rect = (x0, y0, w, h) (None: the whole frame) of the last update's view.  `projection`
+        is a scene.Projection.  records_ptr: device memory of w * h records; None: records the context owns (read_projection).
+        image_ptr: device memory of w * h * 4 bytes; None: no image -- unless own_image, which puts records and image both into
+        buffers the context owns (volym_project_image_pass; read_projection_image)."""
+        c = projection.to_c()
+        r = None
+        if rect is not None:
+            if len(rect) != 4:
+                raise ValueError("a projection rect is (x0, y0, w, h)")
+            r = (C.c_uint32 * 4)(*[int(v) for v in rect])
+        if own_image:
+            if records_ptr is not None or image_ptr is not None:
+                raise ValueError("own_image puts records and image into the context's own buffers")
+            self._ck(_lib.lib().volym_project_image_pass(self.handle, C.byref(c), r))
+        else:
+            self._ck(_lib.lib().volym_project_pass(self.handle, C.byref(c), r, C.c_void_p(records_ptr), C.c_void_p(image_ptr)))
+
+    def _projection_shape(self, fn):
+        """(h, w) of the latest pass into one of the context's own buffers, asked of the context"""
+        size = (C.c_uint32 * 2)()
+        self._ck(fn(self.handle, size))
+        return int(size[1]), int(size[0])
+
+    def read_projection(self):
+        """The records of the latest projection pass into the context's own records: a structured array (_lib.PROJECTION_DTYPE) of
+        shape (h, w).  Blocks."""
+        h, w = self._projection_shape(_lib.lib().volym_projection_size)
+        out = np.zeros((max(h, 1), max(w, 1)), _lib.PROJECTION_DTYPE)       # (before any pass the read refuses)
+        self._ck(_lib.lib().volym_read_projection(self.handle, out.ctypes.data_as(C.POINTER(_lib.Projection))))
+        return out
+
+    def read_projection_image(self):
+        """The image of the latest projection pass with own_image: (h, w, 4) uint8.  Blocks."""
+        h, w = self._projection_shape(_lib.lib().volym_projection_image_size)
+        out = np.empty((max(h, 1), max(w, 1), 4), np.uint8)
+        self._ck(_lib.lib().volym_read_projection_image(self.handle, scene._u8p(out)))
+        return out
+
+    def projection_device_ptr(self):
+        """The context's own projection records after the latest pass into them (None before any)."""
+        return _lib.lib().volym_projection_device_ptr(self.handle)
+
+    def projection_image_device_ptr(self):
+        """The context's own projection image after the latest pass into it (None before any)."""
+        return _lib.lib().volym_projection_image_device_ptr(self.handle)
+
+    def project_at(self, x, y, step):
+        """The record of pixel (x, y): a pass over one pixel plus the read (np.void of _lib.PROJECTION_DTYPE).  Blocks.  The
+        context's own records stay what the latest project_pass made them."""
+        out = np.zeros(1, _lib.PROJECTION_DTYPE)
+        self._ck(_lib.lib().volym_project_at(self.handle, int(x), int(y), float(step), out.ctypes.data_as(C.POINTER(_lib.Projection))))
+        return out[0]
+
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
         s = _lib.Stats()
@@ -405,6 +461,7 @@ class Simple(ComputeDemo):
         ctx.update(state.camera_uniforms(), state.parameter_uniforms())
         self._records_for = None        # (highlight: the pick records of the old view are stale)
         self._eye = tuple(float(v) for v in state.camera.position)      # (clip_at: the plane faces the eye)
+        self._dense_step = 0.25 * float(state.parameter_uniforms().raymarching_step_size)      # (project: the march's dense step)
 
     def compute_pass(self, ctx):
         """BaseDemo::compute_pass -> DemoPipeline::compute_pass (src/demos/pipeline.rs:62-102, :214-225)"""
@@ -576,12 +633,66 @@ class Simple(ComputeDemo):
         (its "slices" entry: {"x": image, "y": image, "z": image}, each (height, width, 4) uint8, read back), or the pick alone
         with "slices" None when the pixel shows nothing.  Keywords go to slice."""
         p = self.pick(ctx, x, y, alpha_min)
-        p["slices"] = None
-        if p["status"] == "hit":
-            p["slices"] = {}
-            for a, axis in enumerate("xyz"):
-                self.slice(ctx, axis, p["texel"][a], **kw)
-                p["slices"][axis] = ctx.read_slice()
+        p["slices"] = self._slices_through(ctx, p["texel"], **kw) if p["status"] == "hit" else None
+        return p
+
+    def _slices_through(self, ctx, texel, **kw):
+        """the three orthogonal slices through `texel`, read back: {"x": image, "y": image, "z": image}"""
+        out = {}
+        for a, axis in enumerate("xyz"):
+            self.slice(ctx, axis, texel[a], **kw)
+            out[axis] = ctx.read_slice()
+        return out
+
+    def project(self, ctx, mode, step=None, tf=False, labels=True, no_skip=False, palette=None, background=(0, 0, 0, 255), rect=None):
+        """The projection view: maximum (_lib.PROJECT_MAX, or "MAX") or mean ("MEAN", the X-ray) intensity along the rays of the
+        current view, through the scene as it stands.  step: the distance between samples, by default the march's dense step,
+        0.25 * raymarching_step_size; tf: colour through the transfer function; labels (MAX only): the segment of the brightest
+        sample as a colour overlay (segment_palette, or `palette`) -- the labels go to the device first if they are not there yet.
+        Records and image go to the context's own buffers (ctx.read_projection(), ctx.read_projection_image()).  Returns the
+        scene.Projection."""
+        if isinstance(mode, str):
+            if mode.upper() not in ("MAX", "MEAN"):
+                raise ValueError("a projection mode is MAX or MEAN, got %r" % (mode,))
+            mode = _lib.PROJECT_MEAN if mode.upper() == "MEAN" else _lib.PROJECT_MAX
+        flags = (_lib.PROJECT_TF if tf else 0) | (_lib.PROJECT_NO_SKIP if no_skip else 0)
+        if self._labels_raw.size and not self._labels_on_device:
+            self.set_labels(ctx, self._labels_raw)              # (the records name the segment either way)
+        if labels and mode == _lib.PROJECT_MAX and self._labels_on_device:
+            flags |= _lib.PROJECT_LABELS
+        p = scene.check_projection(scene.Projection(self._dense_step if step is None else step, mode, flags, background,
+                                                    self.segment_palette() if palette is None else palette))
+        ctx.project_pass(p, rect, own_image=True)
+        return p
+
+    def project_at(self, ctx, x, y, step=None):
+        """The brightest sample of the ray of pixel (x, y) (GpuContext.project_at), as a dict: status ("miss" / "empty" / "hit"),
+        max, mean, n_samples, and on a hit label (None without labels), segment and segment_id (name and id of the segments JSON
+        entry with that label value, else None), texel (x, y, z) in the prepared volume, pos (the texel's centre in the unit-cube
+        coordinates set_crop takes) and t (along the ray from the eye).  The labels go to the device first if they are not there
+        yet."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        r = ctx.project_at(x, y, self._dense_step if step is None else step)
+        status = ("miss", "empty", "hit")[int(r["status"])]
+        out = {"x": int(x), "y": int(y), "status": status, "max": int(r["max"]), "mean": int(r["mean"]), "n_samples": int(r["n_samples"]),
+               "label": None, "segment": None, "segment_id": None, "texel": None, "pos": None, "t": None}
+        if status == "hit":
+            texel = (int(r["x"]), int(r["y"]), int(r["z"]))
+            out.update(texel=texel, pos=tuple((i + 0.5) / n for i, n in zip(texel, self.dims)), t=float(r["t"]))
+            if self._labels_on_device:
+                out["label"] = int(r["label"])
+                seg = next((s for s in getattr(self, "_segments", []) if s["label_value"] == out["label"]), None)
+                if seg is not None:
+                    out["segment"], out["segment_id"] = seg.get("name"), seg.get("id")
+        return out
+
+    def brightest_slices_at(self, ctx, x, y, step=None, **kw):
+        """Click the bright spot: the three orthogonal slices through the texel of the maximum along the ray of pixel (x, y).
+        Returns what project_at returns with a "slices" entry as slices_at's; None when the ray shows nothing.  Keywords go to
+        slice."""
+        p = self.project_at(ctx, x, y, step)
+        p["slices"] = self._slices_through(ctx, p["texel"], **kw) if p["status"] == "hit" else None
         return p
 
     def hide_at(self, ctx, x, y, alpha_min=0.5):

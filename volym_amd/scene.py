@@ -603,6 +603,217 @@ def slice_frame(prepared, dims, slice, lut=None, labels=None, importances=None, 
     return out
 
 
+PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0      # volym_update's range for the march step
+
+
+class Projection:
+    """volym_project (include/volym_hip.h): what one projection pass computes and shows.  step: the distance between the samples
+    of a ray; mode: _lib.PROJECT_MAX / PROJECT_MEAN (what the image shows; a record holds both); flags: PROJECT_TF | PROJECT_LABELS
+    | PROJECT_NO_SKIP; background: the image's colour where a ray misses the cube; palette: (256, 4) uint8, colour per label
+    value with alpha = strength (PROJECT_LABELS)."""
+
+    def __init__(self, step, mode=_lib.PROJECT_MAX, flags=0, background=(0, 0, 0, 255), palette=None):
+        self.step, self.mode, self.flags = float(step), int(mode), int(flags)
+        self.background = tuple(int(v) for v in background)
+        self.palette = np.zeros((256, 4), np.uint8) if palette is None else np.array(palette, np.uint8).reshape(256, 4)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        fields = {k: getattr(self, k) for k in ("step", "mode", "flags", "background", "palette")}
+        for k in kw:
+            if k not in fields:
+                raise TypeError("a projection has no field %r" % k)
+        fields.update(kw)
+        return Projection(**fields)
+
+    def to_c(self):
+        """The _lib.Project of this projection.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Project()
+        c.step = self.step
+        for name in ("mode", "flags"):
+            v = getattr(self, name)
+            if not 0 <= v < 2 ** 32:
+                raise ValueError("projection: %s = %d is not a u32" % (name, v))
+            setattr(c, name, v)
+        c.background = (C.c_uint8 * 4)(*[int(v) for v in _rgba(self.background, "background")])
+        C.memmove(c.palette, _u8p(np.ascontiguousarray(self.palette, np.uint8)), 1024)
+        return c
+
+    @classmethod
+    def from_c(cls, c):
+        return cls(c.step, c.mode, c.flags, tuple(c.background), np.ctypeslib.as_array(c.palette).copy())
+
+
+def check_projection(p):
+    """The validity rules of volym_project_check: a finite step in [1e-4, 1] (as float32), a known mode, known flag bits, no
+    LABELS with MEAN.  Returns the projection; raises ValueError."""
+    step = np.float32(p.step)
+    if not (np.isfinite(step) and np.float32(PROJECT_STEP_MIN) <= step <= np.float32(PROJECT_STEP_MAX)):
+        raise ValueError("projection: the step must be in [1e-4, 1], got %r" % (p.step,))
+    if p.mode not in (_lib.PROJECT_MAX, _lib.PROJECT_MEAN):
+        raise ValueError("projection: unknown mode %r" % (p.mode,))
+    if p.flags & ~(_lib.PROJECT_TF | _lib.PROJECT_LABELS | _lib.PROJECT_NO_SKIP) or p.flags < 0:
+        raise ValueError("projection: unknown flag bits in %#x" % p.flags)
+    if p.mode == _lib.PROJECT_MEAN and p.flags & _lib.PROJECT_LABELS:
+        raise ValueError("projection: LABELS with MEAN (a mean has no texel to take a label from)")
+    return p
+
+
+def project_samples(t_entry, t_exit, step):
+    """The count rule of the projection (volym_project_samples), as the loop it is defined by: the number of k = 0, 1, 2, ... with
+    t_entry + float32(k) * step < t_exit in float32.  Arrays or scalars (broadcast); returns int64 of their common shape."""
+    F = np.float32
+    te, tx, st = np.broadcast_arrays(np.asarray(t_entry, F), np.asarray(t_exit, F), np.asarray(step, F))
+    shape = te.shape
+    te, tx, st = te.ravel(), tx.ravel(), st.ravel()
+    n = np.zeros(te.size, np.int64)
+    idx = np.arange(te.size)
+    k = 0
+    while idx.size:
+        idx = idx[te[idx] + F(k) * st[idx] < tx[idx]]
+        n[idx] += 1
+        k += 1
+    return n.reshape(shape)
+
+
+def project_rays(camera_uniforms, W, H, gx, gy):
+    """The rays of the pixels (gx[i], gy[i]) of the W x H frame (wgsl:221-241), restated in float32 operation for operation.
+    -> (o[3], d[n, 3], t_entry[n], t_exit[n], hit[n])"""
+    F = np.float32
+    zero, one = F(0.0), F(1.0)
+    ivp = np.array(camera_uniforms.inverse_view_proj, F)          # [col][row]
+    o = np.array(list(camera_uniforms.camera_position), F)
+    gx = np.asarray(gx).ravel().astype(F)
+    gy = np.asarray(gy).ravel().astype(F)
+    ndx = (gx / F(W)) * F(2.0) - one
+    ndy = one - (gy / F(H)) * F(2.0)
+    wp = [((ivp[0][r] * ndx + ivp[1][r] * ndy) + ivp[2][r] * zero) + ivp[3][r] * one for r in range(4)]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        v = [wp[a] / wp[3] - o[a] for a in range(3)]
+        ln = np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
+        d = [c / ln for c in v]
+        t1 = [(zero - o[a]) / d[a] for a in range(3)]
+        t2 = [(one - o[a]) / d[a] for a in range(3)]
+    lo = [np.fmin(a, b) for a, b in zip(t1, t2)]
+    hi = [np.fmax(a, b) for a, b in zip(t1, t2)]
+    t_entry = np.fmax(np.fmax(np.fmax(lo[0], lo[1]), lo[2]), zero).astype(F)
+    t_exit = np.fmax(np.fmin(np.fmin(hi[0], hi[1]), hi[2]), zero).astype(F)
+    with np.errstate(invalid="ignore"):
+        hit = ~(t_exit <= t_entry)
+    return o, np.stack(d, 1).astype(F), t_entry, t_exit, hit
+
+
+def _project_texels(o, d, t, dims):
+    """clamp(floor(pos * n), 0, n - 1) of pos = o + d * t, per axis (the march's nearest fetch)"""
+    F = np.float32
+    out = []
+    for a in range(3):
+        f = np.floor((o[a] + d[:, a] * t) * F(dims[a]))
+        f = np.where(f >= F(0.0), f, F(0.0))                       # also NaN -> 0
+        out.append(np.minimum(f, F(dims[a] - 1)).astype(np.int64))
+    return out
+
+
+def project_frame(prepared, dims, camera_uniforms, W, H, projection, rect=None, lut=None, labels=None):
+    """The definition of the projection pass (include/volym_hip.h volym_project_pass); equal to the device in every byte.
+    `prepared`: the density bytes of the scene as it stands (box, plane and mask applied: cut_volume); camera_uniforms: those of
+    the last update; rect = (x0, y0, w, h), None: the whole frame; `lut`: the RGBA8 bytes set_transfer_function received
+    (PROJECT_TF); `labels`: prepared label bytes of the volume's dimensions, None: none on the device (PROJECT_LABELS needs them).
+    Every sample of every ray is read: PROJECT_NO_SKIP changes nothing here.  Returns (records, image): (h, w) of
+    _lib.PROJECTION_DTYPE and (h, w, 4) uint8."""
+    F = np.float32
+    p = check_projection(projection)
+    nx, ny, nz = (int(v) for v in dims)
+    x0, y0, w, h = (0, 0, int(W), int(H)) if rect is None else (int(v) for v in rect)
+    if w < 1 or h < 1 or x0 < 0 or y0 < 0 or x0 + w > W or y0 + h > H:
+        raise ValueError("project_frame: the rect must be non-empty and inside the frame")
+    vol = np.ascontiguousarray(prepared, np.uint8).ravel()
+    if vol.size != nx * ny * nz:
+        raise ValueError("project_frame: the density has %d bytes, the volume %d" % (vol.size, nx * ny * nz))
+    gy, gx = np.meshgrid(np.arange(y0, y0 + h), np.arange(x0, x0 + w), indexing="ij")
+    o, d, t_entry, t_exit, hit = project_rays(camera_uniforms, W, H, gx.ravel(), gy.ravel())
+    n = hit.size
+    step = F(p.step)
+    best = np.zeros(n, np.int64)
+    best_k = np.zeros(n, np.int64)
+    total = np.zeros(n, np.int64)
+    count = np.zeros(n, np.int64)
+    idx = np.flatnonzero(hit)
+    k = 0
+    while idx.size:
+        t = t_entry[idx] + F(k) * step
+        keep = t < t_exit[idx]
+        idx, t = idx[keep], t[keep]
+        ix, iy, iz = _project_texels(o, d[idx], t, (nx, ny, nz))
+        b = vol[ix + nx * (iy + ny * iz)].astype(np.int64)
+        total[idx] += b
+        count[idx] += 1
+        up = b > best[idx]                                          # strictly greater: the smallest k keeps the maximum
+        best[idx[up]] = b[up]
+        best_k[idx[up]] = k
+        k += 1
+
+    rec = np.zeros(n, _lib.PROJECTION_DTYPE)
+    found = hit & (best > 0)
+    rec["status"] = np.where(found, 2, np.where(hit, 1, 0))
+    rec["max"] = best
+    rec["n_samples"] = count
+    rec["mean"] = np.where(hit, (2 * total + count) // np.maximum(2 * count, 1), 0)
+    rec["t"] = F(-1.0)
+    f = np.flatnonzero(found)
+    tb = t_entry[f] + best_k[f].astype(F) * step
+    rec["t"][f] = tb
+    ix, iy, iz = _project_texels(o, d[f], tb, (nx, ny, nz))
+    rec["x"][f], rec["y"][f], rec["z"][f] = ix, iy, iz
+    if labels is not None:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != nx * ny * nz:
+            raise ValueError("project_frame: the labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+        rec["label"][f] = lab[ix + nx * (iy + ny * iz)]
+    elif p.flags & _lib.PROJECT_LABELS:
+        raise ValueError("project_frame: PROJECT_LABELS needs labels")
+
+    rec = rec.reshape(h, w)
+    return rec, project_image(rec, p, lut)
+
+
+def project_image(records, projection, lut=None):
+    """The image rules of the projection pass (include/volym_hip.h at volym_project), from the records of the same rays: a miss
+    is `background`; otherwise v = max or mean by the mode, the base (v, v, v, 255) or, with PROJECT_TF, the r, g, b of texel
+    (v * tf_n) >> 8 of `lut` with alpha 255; with PROJECT_LABELS and status 2, palette[label] blended over it by the outline's
+    formula.  Returns uint8 of the records' shape + (4,)."""
+    p = check_projection(projection)
+    rec = np.asarray(records)
+    if rec.dtype != _lib.PROJECTION_DTYPE:
+        raise ValueError("the records are an array of PROJECTION_DTYPE")
+    v = (rec["mean"] if p.mode == _lib.PROJECT_MEAN else rec["max"]).astype(np.int64)
+    base = np.empty(rec.shape + (4,), np.uint8)
+    if p.flags & _lib.PROJECT_TF:
+        if lut is None:
+            raise ValueError("project_image: PROJECT_TF needs the transfer function's RGBA8 bytes")
+        table = np.ascontiguousarray(lut, np.uint8).reshape(-1, 4)
+        base[:] = table[(v * table.shape[0]) >> 8]
+    else:
+        base[..., 0] = base[..., 1] = base[..., 2] = v
+    base[..., 3] = 255
+    if p.flags & _lib.PROJECT_LABELS:
+        f = rec["status"] == 2
+        base[f] = outline_blend_each(base[f], np.ascontiguousarray(p.palette, np.uint8).reshape(256, 4)[rec["label"][f]])
+    hit = rec["status"] != 0
+    image = np.empty(rec.shape + (4,), np.uint8)
+    image[:] = np.array(_rgba(p.background, "background"), np.uint8)
+    image[hit] = base[hit]
+    return image
+
+
+def outline_blend_each(src, col):
+    """outline_blend with a colour per pixel: src and col are (n, 4) uint8, col's alpha byte is the strength"""
+    col = np.asarray(col, np.uint8).astype(np.uint32)
+    a8 = col[:, 3:4].copy()
+    col[:, 3] = 255
+    return ((np.asarray(src, np.uint8).astype(np.uint32) * (255 - a8) + col * a8 + 127) // 255).astype(np.uint8)
+
+
 def map_segments_to_importance(labels, segments):
     """src/demos/simple/importance.rs:148-158"""
     data = np.array(labels, np.uint8, copy=True).ravel()
