@@ -611,6 +611,68 @@ int   volym_project_check(const volym_project* p);
  * every k).  Pure host arithmetic; the kernel's count agrees with it on every ray. */
 int   volym_project_samples(float t_entry, float t_exit, float step, uint32_t* n);
 
+/* --- measuring segments (new; the reference has none) ----------------------------------------------------------------- */
+/* How large a segment is, where it lies and how its density is distributed, and the density histogram of the visible scene: one
+ * pass over the bytes of the scene that writes one 36 KB result.  It reads the bytes as they stand and writes nothing else.
+ *   The rule (integers only; scene.measure_volume of the Python package is its host twin, equal in every byte).  A request is a box
+ * [lo, hi) of texels (box = {x0, y0, z0, x1, y1, z1}, the coordinates volym_set_crop_box takes), flags, and a table group[256] that
+ * maps a label value to one of VOLYM_MEASURE_GROUPS histogram groups or to VOLYM_MEASURE_NO_GROUP.  Texel t of the box is IN iff it
+ * lies inside the crop box, is kept by the clip plane (n . t <= d) and its label is not hidden; with UNCUT every texel of the box is
+ * in.  Its density byte is that of the scene as it stands; with UNCUT that of the uncut copy when the context holds one (from the
+ * first cut on), else the same bytes.  Its label is the byte of the label volume, or 0 for every texel while the context holds no
+ * labels of the volume's dimensions (the mask term then removes nothing).
+ *   seg[l] sums over the in-texels with label l: their number, the density byte, its square and the three texel coordinates, with
+ * the smallest and largest byte and the texel box {x0, y0, z0, x1, y1, z1}, hi inclusive (the convention of the label boxes).  A
+ * label without an in-texel has the empty record: zeros, min = 255, max = 0, box = {INT32_MAX x 3, -1 x 3}.  hist[g][b] is the number
+ * of in-texels with density byte b whose label maps to group g.  Mean, deviation, centroid and physical volume are floats the host
+ * derives from the record (scene.segment_summary); the device computes none of them. */
+enum { VOLYM_MEASURE_UNCUT = 1 };                                                            /* flags */
+#define VOLYM_MEASURE_GROUPS 8
+#define VOLYM_MEASURE_NO_GROUP 255
+typedef struct volym_measure {
+    uint32_t box[6];            /* {x0, y0, z0, x1, y1, z1}: lo inclusive, hi exclusive, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint8_t  group[256];        /* label value -> histogram group 0..7, or VOLYM_MEASURE_NO_GROUP */
+} volym_measure;                /* 284 bytes */
+struct volym_segment_stats {
+    uint64_t count, sum, sum_sq;        /* in-texels, their density bytes, the squares of those */
+    uint64_t sum_x, sum_y, sum_z;       /* their texel coordinates */
+    int32_t  box[6];                    /* {x0, y0, z0, x1, y1, z1}, hi inclusive */
+    uint32_t min, max;                  /* smallest and largest density byte */
+};                                      /* 80 bytes */
+struct volym_measurement {
+    struct volym_segment_stats seg[256];
+    uint64_t hist[VOLYM_MEASURE_GROUPS][256];
+};                                      /* 36864 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_measure) == 284, "volym_measure is 284 bytes");
+static_assert(sizeof(struct volym_segment_stats) == 80, "volym_segment_stats is 80 bytes");
+static_assert(sizeof(struct volym_measurement) == 36864, "volym_measurement is 36864 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_measure) == 284, "volym_measure is 284 bytes");
+_Static_assert(sizeof(struct volym_segment_stats) == 80, "volym_segment_stats is 80 bytes");
+_Static_assert(sizeof(struct volym_measurement) == 36864, "volym_measurement is 36864 bytes");
+#endif
+/* Enqueue only, on the first slot's stream, where pick, slice and projection passes go (a caller's stream when one is set): one small
+ * kernel that puts the context's own result back to 256 empty records and zeroed histograms, then the pass.  m == NULL: the whole
+ * volume, every label in group 0, no flags.  The one blocking path is the first allocation of the result.  It needs a volume, but no
+ * volym_update, no frame and no transfer function; it ignores the shard (every rank holds the whole volume) and writes no frame
+ * buffer.  The bytes of the scene change only in blocking set-up calls that idle every stream, so with
+ * VOLYM_OPT_FRAMES_IN_FLIGHT = 2 it needs no events, and a frame enqueued before or after it is byte for byte the frame without it.
+ * The sums are integers, so the result does not depend on the order in which workgroups arrive.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_measure_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions held
+ * in the other device layout than the volume (the walk reads label chunk k beside density chunk k; volym_set_segment_visibility
+ * refuses the same). */
+int   volym_measure_pass(volym_ctx* ctx, const volym_measure* m);
+/* Blocks; the result of the latest pass.  VOLYM_E_STATE before any pass, and after volym_set_volume until the next one. */
+int   volym_read_measure(volym_ctx* ctx, struct volym_measurement* out);
+/* The context's own result (a struct volym_measurement in device memory) after a pass, NULL before any. */
+void* volym_measure_device_ptr(volym_ctx* ctx);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, a group entry that is neither below VOLYM_MEASURE_GROUPS nor VOLYM_MEASURE_NO_GROUP.  An empty box is valid: it yields 256
+ * empty records.  Pure host arithmetic. */
+int   volym_measure_check(const volym_measure* m, const uint32_t dims[3]);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

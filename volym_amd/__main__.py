@@ -17,7 +17,9 @@ pixel) write the annotated image instead: a ring round the segments and a tint o
 colours, segments overlaid, cut texels tinted (demo.Simple.slice) -- as <screenshot>_slice_<axis>.png; --slice-at X,Y the three
 orthogonal slices through the texel pixel (X, Y) shows.  --project MAX|MEAN[,STEP] writes the projection view -- maximum or mean
 intensity along the rays of the same view, STEP apart (default: a quarter of the march step) -- as <screenshot>_project_<mode>.png
-(demo.Simple.project).
+(demo.Simple.project).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
+mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
+and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
 """
 import argparse
 import csv
@@ -210,6 +212,18 @@ def _slice_path(path, axis):
     return "%s_slice_%s.png" % (stem, axis)
 
 
+def _measure_table(rows):
+    """the table --measure prints: one line per segment of demo.Simple.measure's dict"""
+    lines = ["%-16s %5s %12s %8s %8s %8s %4s %4s  %-22s %s" % ("segment", "label", "texels", "in view", "mean", "std", "min", "max", "centroid", "box")]
+    for name, s in rows.items():
+        if s is None:
+            lines.append("%-16s %5s %12s" % (name, "", "-"))
+            continue
+        lines.append("%-16s %5d %12d %7.1f%% %8.2f %8.2f %4d %4d  (%6.1f,%6.1f,%6.1f) [%d,%d,%d]..[%d,%d,%d]" % (
+            (name, s["label"], s["count"], 100.0 * s["in_view"], s["mean"], s["std"], s["min"], s["max"]) + s["centroid"] + s["box"][0] + s["box"][1]))
+    return "\n".join(lines)
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -264,6 +278,14 @@ def run_simple(args):
             except ValueError as e:
                 raise SystemExit("--project: %s" % e)
             projection = (mode.lower(), ctx.read_projection_image())
+        measured = None
+        if getattr(args, "measure", None) is not None:
+            names = [v for v in args.measure.split(",") if v]
+            try:
+                measured = (d.measure(ctx, [int(v) if v.isdigit() else v for v in names] or None),
+                            {"visible": d.histogram(ctx), **{v: d.histogram(ctx, [int(v) if v.isdigit() else v]) for v in names}})
+            except ValueError as e:
+                raise SystemExit("--measure: %s" % e)
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
@@ -274,6 +296,13 @@ def run_simple(args):
         stem = path[:-4] if path.lower().endswith(".png") else path
         image.write_png("%s_project_%s.png" % (stem, projection[0]), projection[1])
         print("project %s: %dx%d -> %s_project_%s.png" % (projection[0], W, H, stem, projection[0]))
+    if measured is not None:
+        import json
+        print(_measure_table(measured[0]))
+        stem = path[:-4] if path.lower().endswith(".png") else path
+        with open(stem + "_histogram.json", "w") as f:
+            json.dump({k: [int(c) for c in v] for k, v in measured[1].items()}, f)
+        print("histogram: %s -> %s_histogram.json" % (", ".join(measured[1]), stem))
     if sliced_at is not None:
         import json
         print(json.dumps(sliced_at))   # one line: the pick the three slices of --slice-at go through
@@ -387,6 +416,9 @@ def main(argv=None):
     run.add_argument("--outline", help="NAME[,NAME...]: segment names, ids or label values to outline and tint; the PNG is the annotated image")
     run.add_argument("--outline-at", help="X,Y: outline the segment pixel (X, Y) shows; the PNG is the annotated image")
     run.add_argument("--slice", help="AXIS,INDEX: also write the slice normal to x, y or z through texel INDEX as <screenshot>_slice_<axis>.png")
+    run.add_argument("--measure", nargs="?", const="", metavar="NAME,...",
+                     help="also print the table of segment statistics of the scene in view (all segments, or the named ones) and write the density "
+                          "histograms as <screenshot>_histogram.json")
     run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")

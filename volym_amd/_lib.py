@@ -131,6 +131,42 @@ PROJECTION_DTYPE = np.dtype([("t", "<f4"), ("x", "<u2"), ("y", "<u2"), ("z", "<u
 PROJECTION_MISS, PROJECTION_EMPTY, PROJECTION_HIT = 0, 1, 2   # volym_projection.status
 
 
+MEASURE_UNCUT = 1                                              # volym_measure.flags
+MEASURE_GROUPS, MEASURE_NO_GROUP = 8, 255
+
+
+class Measure(C.Structure):
+    """volym_measure (include/volym_hip.h): box, flags and group table of one measure pass, 284 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("group", C.c_uint8 * 256),
+    ]
+
+
+class SegmentStats(C.Structure):
+    """volym_segment_stats (include/volym_hip.h): the record of one label value, 80 bytes"""
+    _fields_ = [
+        ("count", C.c_uint64), ("sum", C.c_uint64), ("sum_sq", C.c_uint64),
+        ("sum_x", C.c_uint64), ("sum_y", C.c_uint64), ("sum_z", C.c_uint64),
+        ("box", C.c_int32 * 6),
+        ("min", C.c_uint32), ("max", C.c_uint32),
+    ]
+
+
+class Measurement(C.Structure):
+    """volym_measurement (include/volym_hip.h): 256 records and 8 histograms of 256 bins, 36864 bytes"""
+    _fields_ = [
+        ("seg", SegmentStats * 256),
+        ("hist", (C.c_uint64 * 256) * 8),
+    ]
+
+
+# the record as a NumPy structured dtype (GpuContext.read_measure, scene.measure_volume)
+SEGMENT_STATS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<u8"), ("sum_sq", "<u8"), ("sum_x", "<u8"), ("sum_y", "<u8"), ("sum_z", "<u8"),
+                                ("box", "<i4", (6,)), ("min", "<u4"), ("max", "<u4")])
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -267,6 +303,10 @@ SIGNATURES = {
     "volym_project_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_float, C.POINTER(Projection)]),
     "volym_project_check": (C.c_int, [C.POINTER(Project)]),
     "volym_project_samples": (C.c_int, [C.c_float, C.c_float, C.c_float, C.POINTER(C.c_uint32)]),
+    "volym_measure_pass": (C.c_int, [_ctx, C.POINTER(Measure)]),
+    "volym_read_measure": (C.c_int, [_ctx, C.POINTER(Measurement)]),
+    "volym_measure_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_measure_check": (C.c_int, [C.POINTER(Measure), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

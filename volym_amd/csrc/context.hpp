@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI, and the measure pass over them; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -209,6 +209,10 @@ struct volym_ctx {
     uint32_t projection_image_w = 0, projection_image_h = 0;            // ... and into d_projection_image
     volym_projection* d_projection_at = nullptr;                        // the one record of volym_project_at, allocated on first use
 
+    // measure passes (volym_measure_pass, scene_bytes.hip): the context's own result, allocated on first use; written on slot 0's stream
+    volym_measurement* d_measure = nullptr;
+    bool measure_valid = false;              // a pass has written d_measure since the latest volym_set_volume
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -263,6 +267,8 @@ void free_outline(volym_ctx* c);
 void free_slice(volym_ctx* c);
 // project.hip: what the context keeps for the projection pass (every stream idle)
 void free_projection(volym_ctx* c);
+// scene_bytes.hip: what the context keeps for the measure pass (every stream idle)
+void free_measure(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume

@@ -415,6 +415,87 @@ public:
         slices_through(ctx, a, t, out, v);
         return true;
     }
+    // New: measuring segments (volym_measure_pass) -- what a user reads off one record of a measurement, derived on the host in
+    // double from the record's exact integers: mean and population deviation of the density byte, centroid (mean texel index, x
+    // first), physical volume (count * the volume of a texel) and in_view, the share of the segment's texels that were counted
+    // (from volym_label_counts; of the whole volume without labels).
+    struct Measured {
+        uint8_t label;
+        std::string segment;                 // name in the segments table ("label N" for a value it does not list)
+        struct volym_segment_stats stats;
+        double mean, std_dev, centroid[3], volume, in_view;
+    };
+    static Measured segment_summary(const struct volym_segment_stats& r, const double spacing[3] = nullptr)
+    {
+        Measured m{};
+        m.stats = r;
+        if (r.count == 0u) return m;
+        const long double n = static_cast<long double>(r.count), s = static_cast<long double>(r.sum);
+        m.mean = static_cast<double>(s / n);
+        // count * sum_sq - sum^2 in 128 bits: exact, so a constant segment has deviation 0
+        const unsigned __int128 num = static_cast<unsigned __int128>(r.count) * r.sum_sq - static_cast<unsigned __int128>(r.sum) * r.sum;
+        m.std_dev = static_cast<double>(std::sqrt(static_cast<long double>(num)) / n);
+        m.centroid[0] = static_cast<double>(r.sum_x / n); m.centroid[1] = static_cast<double>(r.sum_y / n); m.centroid[2] = static_cast<double>(r.sum_z / n);
+        m.volume = static_cast<double>(r.count) * (spacing ? spacing[0] * spacing[1] * spacing[2] : 1.0);
+        return m;
+    }
+    // One measure pass plus the read over the scene as it stands (uncut: as it was uploaded), inside box01 = {x0, y0, z0, x1, y1, z1}
+    // in the unit-cube coordinates set_crop takes (NULL: the whole volume).  `segments`: names, ids or label values written as
+    // numbers; empty: every label value with a texel in view.  The labels go to the device first if they are not there yet; without
+    // labels everything is label 0.
+    std::vector<Measured> measure(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {}, const float* box01 = nullptr,
+                                  bool uncut = false, const double spacing[3] = nullptr)
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        volym_measure m{};
+        const uint32_t n[3] = {a.nx, a.ny, a.nz};
+        for (int i = 0; i < 3; ++i) { m.box[i] = box01 ? crop_texel(box01[i], n[i]) : 0u; m.box[3 + i] = box01 ? crop_texel(box01[3 + i], n[i]) : n[i]; }
+        m.flags = uncut ? VOLYM_MEASURE_UNCUT : 0u;
+        ctx.check(volym_measure_pass(ctx.handle(), &m));
+        std::vector<struct volym_measurement> r(1);
+        ctx.check(volym_read_measure(ctx.handle(), r.data()));
+        uint64_t totals[256];
+        for (int l = 0; l < 256; ++l) totals[l] = static_cast<uint64_t>(a.nx) * a.ny * a.nz;
+        if (labels_on_device_) ctx.check(volym_label_counts(ctx.handle(), totals));
+        std::vector<uint8_t> values;
+        for (const std::string& s : segments) values.push_back(label_value_of(a, s));
+        if (segments.empty())
+            for (int l = 0; l < 256; ++l) if (r[0].seg[l].count != 0u) values.push_back(static_cast<uint8_t>(l));
+        std::vector<Measured> out;
+        for (uint8_t l : values) {
+            Measured s = segment_summary(r[0].seg[l], spacing);
+            s.label = l;
+            s.segment = "label " + std::to_string(l);
+            for (const SegmentInfo& seg : a.segments) if (seg.label_value == l) { s.segment = seg.name.empty() ? seg.id : seg.name; break; }
+            s.in_view = totals[l] ? static_cast<double>(s.stats.count) / static_cast<double>(totals[l]) : 0.0;
+            out.push_back(s);
+        }
+        return out;
+    }
+    // New: the density histogram of the visible scene (no segments), or of the given segments as far as they are visible: 256 counts,
+    // the curve a transfer-function editor draws behind its control points.
+    std::vector<uint64_t> histogram(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {})
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        volym_measure m{};
+        m.box[3] = a.nx; m.box[4] = a.ny; m.box[5] = a.nz;
+        if (!segments.empty()) {
+            for (int l = 0; l < 256; ++l) m.group[l] = VOLYM_MEASURE_NO_GROUP;
+            for (const std::string& s : segments) m.group[label_value_of(a, s)] = 0;
+        }
+        ctx.check(volym_measure_pass(ctx.handle(), &m));
+        std::vector<struct volym_measurement> r(1);
+        ctx.check(volym_read_measure(ctx.handle(), r.data()));
+        return std::vector<uint64_t>(r[0].hist[0], r[0].hist[0] + 256);
+    }
+    // New: click to measure -- a pick, then the summary of the segment the pixel shows.  False: it shows no labelled sample.
+    bool measure_at(const GpuContext& ctx, const SimpleAssets& a, uint32_t x, uint32_t y, Measured& out, float alpha_min = 0.5f)
+    {
+        const Picked p = pick(ctx, a, x, y, alpha_min);
+        if (p.record.status != 2 || !p.record.has_labels) return false;
+        out = measure(ctx, a, {std::to_string(p.record.label)}).front();
+        return true;
+    }
     // a colour per label value of the segments table for the slice overlay: hues spread by the golden angle over the label values,
     // saturation 0.85, value 1; every other label, 0 included, stays transparent
     static void segment_palette(const SimpleAssets& a, uint8_t strength, uint8_t palette[256][4])

@@ -538,6 +538,7 @@ void volym_destroy(volym_ctx* c)
     free_outline(c);
     free_slice(c);
     free_projection(c);
+    free_measure(c);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }

@@ -1,7 +1,8 @@
 // libvolym_hip.so: the bytes of the scene.  Volume, label and importance uploads, the device layout, the macro cells, and the
 // one transition (retarget) that keeps density and importances cut to the crop box, the clip plane and the segment mask; the C ABI entry
 // points of all of these.  The frame loop (raymarch.hip) reads what this unit writes; what the two need from each other is
-// declared in context.hpp.  Everything here is blocking set-up path.
+// declared in context.hpp.  Everything here is blocking set-up path, except the measure pass at the end (measure.inc, measure_kernels.h),
+// which only reads these bytes and is enqueue-only.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 
 #include "context.hpp"
 #include "scene_kernels.h"
+#include "measure_kernels.h"
 
 using namespace volym;
 
@@ -845,6 +847,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     // (d_imp is uncropped now, and the copies are made again by the next cut: a context that does not cut holds none)
     if (c->d_vol0) { HIPCHK(c, hipFree(c->d_vol0)); c->d_vol0 = nullptr; }
     if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
+    c->measure_valid = false;               // (a result describes the volume it was measured in)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;
@@ -970,3 +973,6 @@ int volym_label_counts(volym_ctx* c, uint64_t counts[256])
 }
 
 }  // extern "C"
+
+// ---- measuring segments ---------------------------------------------------------------------------------------------------
+#include "measure.inc"

@@ -8,7 +8,8 @@
 //               presented frames over 2 s of wall clock, blit/GUI/vsync included).
 //   run simple: one frame of the interactive default view (src/state.rs:41-55) to frame.ppm; --slice AXIS,INDEX also writes the
 //   slice normal to x, y or z through that texel (Simple::slice) to frame_slice_<axis>.ppm; --project MAX|MEAN[,STEP] the
-//   maximum or mean intensity projection of the view (Simple::project) to frame_project_<mode>.ppm.
+//   maximum or mean intensity projection of the view (Simple::project) to frame_project_<mode>.ppm; --measure [NAME,...] prints
+//   the table of segment statistics of the scene in view (Simple::measure).
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -52,6 +53,8 @@ struct Options {
     uint32_t slice_index = 0;
     int project_mode = -1;         // --project MAX|MEAN[,STEP]: also write the projection view (run simple)
     float project_step = 0.0f;     // 0: the march's dense step
+    bool measure = false;          // --measure [NAME,...]: also print the table of segment statistics (run simple)
+    std::vector<std::string> measure_names;
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -214,6 +217,17 @@ int run_simple(const Options& o)
         for (size_t i = 0; i < static_cast<size_t>(W) * H; ++i) pf.write(reinterpret_cast<const char*>(&img[4 * i]), 3);
         std::printf("project %s: %ux%u -> %s\n", mode, W, H, ppath.c_str());
     }
+    if (o.measure) {
+        // what is in view, per segment: the scene under the cuts of this run
+        const std::vector<Simple::Measured> rows = demo.measure(ctx, assets, o.measure_names);
+        std::printf("%-16s %5s %12s %8s %8s %8s %4s %4s  %-22s %s\n", "segment", "label", "texels", "in view", "mean", "std", "min", "max", "centroid", "box");
+        for (const Simple::Measured& r : rows) {
+            if (r.stats.count == 0u) { std::printf("%-16s %5u %12s\n", r.segment.c_str(), r.label, "-"); continue; }
+            std::printf("%-16s %5u %12llu %7.1f%% %8.2f %8.2f %4u %4u  (%6.1f,%6.1f,%6.1f) [%d,%d,%d]..[%d,%d,%d]\n", r.segment.c_str(), r.label,
+                        static_cast<unsigned long long>(r.stats.count), 100.0 * r.in_view, r.mean, r.std_dev, r.stats.min, r.stats.max, r.centroid[0], r.centroid[1],
+                        r.centroid[2], r.stats.box[0], r.stats.box[1], r.stats.box[2], r.stats.box[3], r.stats.box[4], r.stats.box[5]);
+        }
+    }
     return 0;
 }
 
@@ -276,6 +290,18 @@ int main(int argc, char** argv)
                 o.slice_axis = static_cast<int>(axis);
                 o.slice_index = static_cast<uint32_t>(index);
             }
+            else if (a == "--measure") {
+                o.measure = true;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") {
+                    const std::string v = next();
+                    size_t pos = 0;
+                    while (pos <= v.size()) {
+                        const size_t comma = std::min(v.find(',', pos), v.size());
+                        if (comma > pos) o.measure_names.push_back(v.substr(pos, comma - pos));
+                        pos = comma + 1u;
+                    }
+                }
+            }
             else if (a == "--project") {
                 const std::string v = next();
                 const size_t comma = v.find(',');
@@ -289,7 +315,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

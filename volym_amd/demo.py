@@ -385,6 +385,26 @@ class GpuContext:
         self._ck(_lib.lib().volym_project_at(self.handle, int(x), int(y), float(step), out.ctypes.data_as(C.POINTER(_lib.Projection))))
         return out[0]
 
+    # ---- measuring segments -----------------------------------------------------------------
+    def measure_pass(self, measure=None):
+        """Enqueue one measure pass (include/volym_hip.h volym_measure_pass; scene.measure_volume is its definition): per-label
+        statistics and grouped density histograms of the scene under its cuts.  `measure` is a scene.Measure; None: the whole
+        volume, every label in group 0.  Needs a volume, nothing else: no update, no frame."""
+        c = None if measure is None else C.byref(measure.to_c())
+        self._ck(_lib.lib().volym_measure_pass(self.handle, c))
+
+    def read_measure(self):
+        """The result of the latest measure pass: (records, hist) -- a structured array of 256 _lib.SEGMENT_STATS_DTYPE records, one
+        per label value, and a uint64[8, 256] array of histograms.  Blocks."""
+        out = np.zeros(C.sizeof(_lib.Measurement), np.uint8)
+        self._ck(_lib.lib().volym_read_measure(self.handle, out.ctypes.data_as(C.POINTER(_lib.Measurement))))
+        n = 256 * _lib.SEGMENT_STATS_DTYPE.itemsize
+        return out[:n].view(_lib.SEGMENT_STATS_DTYPE).copy(), out[n:].view(np.uint64).reshape(_lib.MEASURE_GROUPS, 256).copy()
+
+    def measure_device_ptr(self):
+        """The context's own result (a volym_measurement in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_measure_device_ptr(self.handle)
+
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
         s = _lib.Stats()
@@ -693,6 +713,54 @@ class Simple(ComputeDemo):
         slice."""
         p = self.project_at(ctx, x, y, step)
         p["slices"] = self._slices_through(ctx, p["texel"], **kw) if p["status"] == "hit" else None
+        return p
+
+    def _segment_name(self, label):
+        seg = next((s for s in getattr(self, "_segments", []) if s["label_value"] == label), None)
+        return (seg.get("name") or seg.get("id")) if seg is not None else None
+
+    def measure(self, ctx, segments=None, box01=None, uncut=False, spacing=(1, 1, 1)):
+        """Measure segments of the scene as it stands (crop box, clip plane and hidden segments applied; uncut=True: as it was
+        uploaded): one measure pass plus the read.  segments: names, ids or label values (None: every label value that has texels
+        in view); box01: (lo, hi) in the unit-cube coordinates set_crop takes (None: the whole volume).  Returns {name: summary}
+        in label order, the name being the segments JSON's, or "label N" for a value it does not list; a summary is
+        scene.segment_summary's dict with "label" and "in_view" (the share of the segment's texels that were counted, from the
+        label counts of the device) added, or None for a segment with no texel in view.  The labels go to the device first if they
+        are not there yet; without labels everything is label 0."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        box = None if box01 is None else scene.crop_box_texels(box01[0], box01[1], self.dims)
+        m = scene.check_measure(scene.Measure(box, _lib.MEASURE_UNCUT if uncut else 0, dims=self.dims), self.dims)
+        ctx.measure_pass(m)
+        rec, _ = ctx.read_measure()
+        totals = ctx.label_counts() if self._labels_on_device else None
+        values = self._label_values(segments) if segments is not None else [int(l) for l in np.flatnonzero(rec["count"])]
+        out = {}
+        for l in values:
+            s = scene.segment_summary(rec[l], spacing)
+            if s is not None:
+                total = int(totals[l]) if totals is not None else self.dims[0] * self.dims[1] * self.dims[2]
+                s.update(label=l, in_view=s["count"] / total if total else 0.0)
+            out[self._segment_name(l) or "label %d" % l] = s
+        return out
+
+    def histogram(self, ctx, segments=None):
+        """The density histogram of the visible scene (segments=None), or of the given segments (names, ids or label values) as far
+        as they are visible: np.uint64[256], the curve a transfer-function editor draws behind its control points.  One measure
+        pass plus the read."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        group = None if segments is None else scene.measure_groups(self._label_values(segments))
+        ctx.measure_pass(scene.check_measure(scene.Measure(None, 0, group, dims=self.dims), self.dims))
+        return ctx.read_measure()[1][0]
+
+    def measure_at(self, ctx, x, y, alpha_min=0.5, **kw):
+        """Click to measure: pick pixel (x, y), then measure the segment it shows.  Returns the pick with a "measure" entry (the
+        summary of that segment, as measure gives it), None when the pixel shows no labelled sample.  Keywords go to measure."""
+        p = self.pick(ctx, x, y, alpha_min)
+        p["measure"] = None
+        if p["status"] == "hit" and p["label"] is not None:
+            p["measure"] = next(iter(self.measure(ctx, [p["label"]], **kw).values()))
         return p
 
     def hide_at(self, ctx, x, y, alpha_min=0.5):

@@ -603,7 +603,173 @@ def slice_frame(prepared, dims, slice, lut=None, labels=None, importances=None, 
     return out
 
 
-PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0      # volym_update's range for the march step
+class Measure:
+    """volym_measure (include/volym_hip.h): what one measure pass counts.  box: (lo, hi) in texels of the prepared volume, lo
+    inclusive, hi exclusive (None: the whole volume, which needs `dims`); flags: _lib.MEASURE_UNCUT; group: 256 entries, label value
+    -> histogram group 0..7 or _lib.MEASURE_NO_GROUP (None: every label in group 0)."""
+
+    def __init__(self, box=None, flags=0, group=None, dims=None):
+        if box is None:
+            if dims is None:
+                raise ValueError("a measure without a box needs the volume's dims")
+            box = ((0, 0, 0), tuple(int(v) for v in dims))
+        lo, hi = box
+        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.flags = int(flags)
+        self.group = np.zeros(256, np.int64) if group is None else np.array(group, np.int64).ravel()
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        fields = {k: getattr(self, k) for k in ("box", "flags", "group")}
+        for k in kw:
+            if k not in fields:
+                raise TypeError("a measure has no field %r" % k)
+        fields.update(kw)
+        return Measure(**fields)
+
+    def to_c(self):
+        """The _lib.Measure of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Measure()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("measure: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        if not 0 <= self.flags < 2 ** 32:
+            raise ValueError("measure: flags = %d is not a u32" % self.flags)
+        c.flags = self.flags
+        if self.group.size != 256 or not ((self.group >= 0) & (self.group <= 255)).all():
+            raise ValueError("measure: the group table is 256 bytes")
+        c.group = (C.c_uint8 * 256)(*[int(g) for g in self.group])
+        return c
+
+
+def measure_groups(*label_sets):
+    """A group table: the label values of the k-th argument go to histogram group k, every other label to no group."""
+    if len(label_sets) > _lib.MEASURE_GROUPS:
+        raise ValueError("at most %d histogram groups" % _lib.MEASURE_GROUPS)
+    g = np.full(256, _lib.MEASURE_NO_GROUP, np.int64)
+    for k, values in enumerate(label_sets):
+        for l in values:
+            if not 0 <= int(l) <= 255:
+                raise ValueError("a label value is a u8, got %r" % (l,))
+            g[int(l)] = k
+    return g
+
+
+def check_measure(measure, dims):
+    """The validity rules of volym_measure_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits, every
+    group entry below 8 or 255.  Returns the measure; raises ValueError."""
+    m = measure
+    dims = [int(v) for v in dims]
+    lo, hi = m.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("measure: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("measure box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    if m.flags & ~_lib.MEASURE_UNCUT or m.flags < 0:
+        raise ValueError("measure: unknown flag bits in %#x" % m.flags)
+    g = np.asarray(m.group)
+    if g.size != 256 or not (((g >= 0) & (g < _lib.MEASURE_GROUPS)) | (g == _lib.MEASURE_NO_GROUP)).all():
+        raise ValueError("measure: every group entry is 0..%d or %d" % (_lib.MEASURE_GROUPS - 1, _lib.MEASURE_NO_GROUP))
+    return m
+
+
+def empty_measurement():
+    """(records, hist) of a pass that counts nothing: 256 empty records (zeros, min 255, max 0, box INT32_MAX x 3, -1 x 3)."""
+    rec = np.zeros(256, _lib.SEGMENT_STATS_DTYPE)
+    rec["min"] = 255
+    rec["box"][:, :3] = 2 ** 31 - 1
+    rec["box"][:, 3:] = -1
+    return rec, np.zeros((_lib.MEASURE_GROUPS, 256), np.uint64)
+
+
+def measure_volume(prepared, dims, measure, labels=None, cut=None, uncut=None):
+    """The definition of the measure pass (include/volym_hip.h volym_measure_pass), NumPy integers only; equal to the device in every
+    byte.  `prepared`: the density bytes of the scene as it stands (box, plane and mask applied: cut_volume); `uncut`: the density
+    before any cut, read under MEASURE_UNCUT (None: the context never cut, `prepared` is read); `labels`: prepared label bytes of the
+    volume's dimensions (None: every texel has label 0 and the mask removes nothing); `cut`: the cut state, as cut_volume takes it.
+    Returns (records, hist): 256 records of _lib.SEGMENT_STATS_DTYPE and uint64[8, 256]."""
+    m = check_measure(measure, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    n = (nx, ny, nz)
+    whole = bool(m.flags & _lib.MEASURE_UNCUT)
+    cut = {} if whole else (cut or {})
+    lo, hi = list(m.box[0]), list(m.box[1])
+    if cut.get("box") is not None:
+        blo, bhi = check_crop_box(cut["box"][0], cut["box"][1], dims)
+        lo = [max(a, b) for a, b in zip(lo, blo)]
+        hi = [min(a, b) for a, b in zip(hi, bhi)]
+    rec, hist = empty_measurement()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return rec, hist
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("measure_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub].astype(np.int64)
+    if labels is None:
+        l = np.zeros_like(b)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("measure_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub].astype(np.int64)
+    z, y, x = np.meshgrid(*[np.arange(lo[a], hi[a], dtype=np.int64) for a in (2, 1, 0)], indexing="ij")
+    inside = np.ones(b.shape, bool)
+    if cut.get("plane") is not None:
+        pn, pd = check_clip_plane(*cut["plane"])
+        inside &= pn[0] * x + pn[1] * y + pn[2] * z <= pd
+    if cut.get("visible") is not None and labels is not None:
+        inside &= check_segment_visibility(cut["visible"])[l] != 0
+    b, l, pos = b[inside], l[inside], [v[inside] for v in (x, y, z)]
+    if b.size == 0:
+        return rec, hist
+    # counts per (label, byte) and per (label, coordinate): everything else is an integer sum over those tables
+    per_byte = np.bincount(l * 256 + b, minlength=65536).reshape(256, 256).astype(np.int64)
+    values = np.arange(256, dtype=np.int64)
+    count = per_byte.sum(axis=1)
+    rec["count"] = count
+    rec["sum"] = per_byte @ values
+    rec["sum_sq"] = per_byte @ (values * values)
+    present = np.flatnonzero(count)
+    for k in present:
+        nz_b = np.flatnonzero(per_byte[k])
+        rec["min"][k], rec["max"][k] = nz_b[0], nz_b[-1]
+    for a, name in enumerate(("sum_x", "sum_y", "sum_z")):
+        per_pos = np.bincount(l * n[a] + pos[a], minlength=256 * n[a]).reshape(256, n[a]).astype(np.int64)
+        rec[name] = per_pos @ np.arange(n[a], dtype=np.int64)
+        for k in present:
+            nz_p = np.flatnonzero(per_pos[k])
+            rec["box"][k, a], rec["box"][k, 3 + a] = nz_p[0], nz_p[-1]
+    group = np.asarray(m.group)
+    for g in range(_lib.MEASURE_GROUPS):
+        hist[g] = per_byte[group == g].sum(axis=0)
+    return rec, hist
+
+
+def segment_summary(stats, spacing=(1, 1, 1)):
+    """What a user reads off one record of a measurement (np.void of _lib.SEGMENT_STATS_DTYPE, or a _lib.SegmentStats): count, mean
+    and population standard deviation of the density byte, min, max, centroid (texel indices, x first: the mean coordinate),
+    centre (the centroid's position in physical units: (centroid + 0.5) * spacing, a texel's centre being at index + 0.5), box
+    ((x0, y0, z0), (x1, y1, z1), hi inclusive) and volume (count * the volume of a texel).  Python ints and floats, derived in
+    double from exact integers.  None for an empty record."""
+    import math
+    get = (lambda k: stats[k]) if isinstance(stats, (np.void, dict)) else (lambda k: getattr(stats, k))
+    count = int(get("count"))
+    if count == 0:
+        return None
+    s, sq = int(get("sum")), int(get("sum_sq"))
+    sums = [int(get(k)) for k in ("sum_x", "sum_y", "sum_z")]
+    box = [int(v) for v in get("box")]
+    sp = [float(v) for v in spacing]
+    centroid = tuple(v / count for v in sums)
+    return {"count": count, "mean": s / count, "std": math.sqrt(count * sq - s * s) / count, "min": int(get("min")), "max": int(get("max")),
+            "centroid": centroid, "centre": tuple((c + 0.5) * h for c, h in zip(centroid, sp)),
+            "box": (tuple(box[:3]), tuple(box[3:])), "volume": count * sp[0] * sp[1] * sp[2]}
+
+
+PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0     # volym_update's range for the march step
 
 
 class Projection:
