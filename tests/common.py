@@ -114,3 +114,39 @@ def byte_thresholds(bs):
             seen.add(float(v))
             uniq.append(float(np.float32(v)))
     return uniq
+
+
+# ---- the step-size and look-ahead axes (test_oracle_step_lookahead.py, test_gpu_step_lookahead.py) --------------------------
+
+def _f32_up(v):
+    return float(np.nextafter(np.float32(v), np.float32(np.inf)))
+
+
+def _f32_down(v):
+    return float(np.nextafter(np.float32(v), np.float32(-np.inf)))
+
+
+def step_axis():
+    """raymarching_step_size from one end of volym_update's range to the other: f32(1e-4) and the float above it, the ends of the
+    GUI's slider (0.001, 0.1), 0.25 and 0.5, the float below 1 and 1; every value as the float32 it is stored as."""
+    lo = float(np.float32(1e-4))
+    return [lo, _f32_up(lo), float(np.float32(0.001)), float(np.float32(0.1)), 0.25, 0.5, _f32_down(1.0), 1.0]
+
+
+def ahead_axis():
+    """importance_check_ahead_steps over volym_update's range: none, the GUI's ends and their neighbours, both sides of a wave of
+    64 and of 256, and the top of the range with its neighbour."""
+    return [0, 1, 2, 3, 25, 26, 63, 65, 255, 256, 1000, 4095, 4096]
+
+
+def noise_scene(rng, dims):
+    """(volume, importances), prepared bytes: uniform random densities; importance 255 for one voxel in four, 0 for the rest"""
+    n = dims[0] * dims[1] * dims[2]
+    vol = rng.integers(0, 256, n, dtype=np.uint8)
+    imp = np.where(rng.integers(0, 4, n) == 0, 255, 0).astype(np.uint8)
+    return vol, imp
+
+
+def refused_steps():
+    """step sizes volym_update refuses: one float outside either end of [f32(1e-4), 1], zero, a negative one, NaN, +inf"""
+    return [_f32_down(np.float32(1e-4)), _f32_up(1.0), 0.0, -0.01, float("nan"), float("inf")]
