@@ -23,7 +23,8 @@
  *     no stream synchronisation on their path.  The one exception is spelled out at volym_update.
  *     Blocking calls: volym_create / volym_destroy, volym_set_* (uploads; they also wait for the frames in flight),
  *     volym_set_option, volym_set_shard, volym_set_stream, volym_sync, volym_settle, volym_read_*, volym_packed_tiles,
- *     volym_assemble_host, volym_stats_pass, volym_time_*; volym_blit blocks only when it has to (re)size its own target.
+ *     volym_assemble_host, volym_stats_pass, volym_time_*; volym_blit blocks only when it has to (re)size its own target, and
+ *     volym_surface_faces_pass when it has to learn the face total of its surface pass or grow the context's own face buffer.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -672,6 +673,92 @@ void* volym_measure_device_ptr(volym_ctx* ctx);
  * bit, a group entry that is neither below VOLYM_MEASURE_GROUPS nor VOLYM_MEASURE_NO_GROUP.  An empty box is valid: it yields 256
  * empty records.  Pure host arithmetic. */
 int   volym_measure_check(const volym_measure* m, const uint32_t dims[3]);
+
+/* --- segment surfaces (new; the reference has none) -------------------------------------------------------------------- */
+/* The boundary faces of a segment, or of the isosurface density >= threshold: how many there are per label and direction (the
+ * surface area), the divergence sums that give the enclosed texel count back, and the faces themselves as one list a mesh is
+ * written from.  Two read-only passes over the bytes of the scene as they stand; nothing else is written.
+ *   The rule (integers only; scene.surface_volume of the Python package is its host twin, equal in every byte).  A request is a box
+ * [lo, hi) of texels (volym_measure's conventions), flags, min_byte in 1..255 and a table select[256].  Texel t is SOLID iff it
+ * lies in the request's box, its density byte is >= min_byte and select[label(t)] != 0.  The byte is that of the scene as it
+ * stands; with UNCUT that of the uncut copy when the context holds one (from the first cut on), else the same bytes.  The label is
+ * the byte of the label volume, or 0 for every texel while the context holds no labels of the volume's dimensions.
+ *   The cuts are in the predicate for free.  The scene keeps byte(t) = (t inside the crop box, kept by the clip plane, label not
+ * hidden) ? uncut byte : 0, and min_byte >= 1: a texel a cut removes has byte 0 and is never solid, so the pass evaluates no box,
+ * plane or mask arithmetic of its own.  The same holds for a texel of a selected label whose own byte is below min_byte: it is not
+ * solid, and the surface runs between it and its neighbours of the same label.
+ *   A FACE is a pair (t, dir) with t solid and its neighbour in direction dir not solid; dir 0..5 = -x, +x, -y, +y, -z, +z.  A
+ * neighbour outside the request's box, or outside the volume, is not solid, whatever its bytes: the surface of a box that cuts
+ * through a segment is closed along the box.
+ *   The summary: faces[l][dir] counts the faces of texels with label l; total counts all; for axis a, pos[l][a] is the sum of
+ * t[a] + 1 over the +a faces of label l and neg[l][a] the sum of t[a] over its -a faces, both stored as they are.  Summed over
+ * the labels, pos - neg is the number of solid texels, on every axis (the divergence theorem on unit cubes: every run of solid
+ * texels along a starts with a -a face at t[a] and ends with a +a face at t[a] + 1).  Two solid texels of different labels have
+ * no face between them, so per label the identity holds where the label's own surface is closed: always with that label selected
+ * alone, and then, with min_byte = 1 and no byte of the segment 0 inside the cuts, pos[l][a] - neg[l][a] is
+ * volym_measurement.seg[l].count.  Areas in physical units, the enclosed volume and sphericity are floats the host derives
+ * (scene.surface_summary).
+ *   The face list: one 8-byte record per face, in ONE order whatever the device layout: ascending (z, y, x, dir).  The same request
+ * on the same scene gives the same bytes, every time. */
+enum { VOLYM_SURFACE_UNCUT = 1 };                                                            /* flags */
+#define VOLYM_SURFACE_SCAN_ROWS 256     /* rows of the request's box (fixed y, z) that one workgroup of the offset scan covers */
+typedef struct volym_surface {
+    uint32_t box[6];            /* {x0, y0, z0, x1, y1, z1}: lo inclusive, hi exclusive, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint32_t min_byte;          /* 1..255 */
+    uint8_t  select[256];       /* label value -> != 0: its texels can be solid */
+} volym_surface;                /* 288 bytes */
+struct volym_surface_summary {
+    uint64_t faces[256][6];     /* per label of the solid texel and direction */
+    uint64_t total;
+    uint64_t pos[256][3];       /* sum of t[a] + 1 over the +a faces */
+    uint64_t neg[256][3];       /* sum of t[a] over the -a faces */
+};                              /* 24584 bytes */
+struct volym_surface_face {
+    uint16_t x, y, z;           /* the solid texel, the coordinates volym_set_crop_box takes */
+    uint8_t  dir;               /* 0..5 = -x, +x, -y, +y, -z, +z: the side of the texel the face is on */
+    uint8_t  label;             /* label byte of the texel; 0 without labels of the volume's dimensions on the device */
+};                              /* 8 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_surface) == 288, "volym_surface is 288 bytes");
+static_assert(sizeof(struct volym_surface_summary) == 24584, "volym_surface_summary is 24584 bytes");
+static_assert(sizeof(struct volym_surface_face) == 8, "volym_surface_face is 8 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_surface) == 288, "volym_surface is 288 bytes");
+_Static_assert(sizeof(struct volym_surface_summary) == 24584, "volym_surface_summary is 24584 bytes");
+_Static_assert(sizeof(struct volym_surface_face) == 8, "volym_surface_face is 8 bytes");
+#endif
+/* Enqueue only, on the first slot's stream, where pick, slice, projection and measure passes go (a caller's stream when one is
+ * set): a kernel that zeroes the context's own summary, the count pass (the summary, and the face count of every row of the
+ * request's box: fixed y, z) and the scan that turns the counts into the offset of every row's first face.  s == NULL: the whole
+ * volume, min_byte 1, every label selected, no flags.  The one blocking path is the first allocation of the summary and the first
+ * allocation, or a growth, of the row-offset array (4 bytes per row of the largest box asked for so far).  It needs a volume, but
+ * no volym_update, no frame and no transfer function; it ignores the shard (every rank holds the whole volume), writes no frame
+ * buffer and needs no events with VOLYM_OPT_FRAMES_IN_FLIGHT = 2: a frame enqueued before or after it is byte for byte the frame
+ * without it.  An empty box launches only the zeroing kernel.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_surface_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions held
+ * in the other device layout than the volume (as volym_measure_pass). */
+int   volym_surface_pass(volym_ctx* ctx, const volym_surface* s);
+/* Blocks; the summary of the latest pass.  VOLYM_E_STATE before any pass, and after volym_set_volume until the next one. */
+int   volym_read_surface(volym_ctx* ctx, struct volym_surface_summary* out);
+/* The context's own summary (a struct volym_surface_summary in device memory) after a pass, NULL before any. */
+void* volym_surface_device_ptr(volym_ctx* ctx);
+/* The emit pass of the latest surface pass: its faces, in canonical order, into target_device (device memory of capacity_faces
+ * records, 8-byte aligned), or with target_device == NULL into a buffer the context owns and sizes to the total
+ * (volym_read_surface_faces; capacity_faces is then ignored).  The first call after a surface pass blocks to learn the total; the
+ * context's own buffer blocks when it has to grow.  The kernel itself is enqueued on the first slot's stream.
+ *   VOLYM_E_INVALID: NULL ctx; a caller's capacity_faces below the total, or a misaligned target; a total above UINT32_MAX (the row
+ * offsets are 32-bit) -- pure host arithmetic on the summary, nothing is written.  VOLYM_E_STATE: before any surface pass, and
+ * after volym_set_volume or any set-up call that changed the bytes the pass read (volym_set_crop_box, volym_set_clip_plane,
+ * volym_set_segment_visibility with a change, volym_set_labels, volym_set_importances, which drops the labels): the offsets no
+ * longer describe the scene.  volym_set_segment_importances rewrites the importances alone and leaves a surface pass valid. */
+int   volym_surface_faces_pass(volym_ctx* ctx, void* target_device, uint64_t capacity_faces);
+/* Blocks; copies the faces of the latest volym_surface_faces_pass into the context's own buffer (`total` records of that pass).
+ * VOLYM_E_STATE before any such pass; VOLYM_E_INVALID for NULL or capacity_faces below that count. */
+int   volym_read_surface_faces(volym_ctx* ctx, struct volym_surface_face* out, uint64_t capacity_faces);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, min_byte outside 1..255.  An empty box is valid: a zero summary and no faces.  Pure host arithmetic. */
+int   volym_surface_check(const volym_surface* s, const uint32_t dims[3]);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

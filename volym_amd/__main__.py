@@ -17,7 +17,9 @@ pixel) write the annotated image instead: a ring round the segments and a tint o
 colours, segments overlaid, cut texels tinted (demo.Simple.slice) -- as <screenshot>_slice_<axis>.png; --slice-at X,Y the three
 orthogonal slices through the texel pixel (X, Y) shows.  --project MAX|MEAN[,STEP] writes the projection view -- maximum or mean
 intensity along the rays of the same view, STEP apart (default: a quarter of the march step) -- as <screenshot>_project_<mode>.png
-(demo.Simple.project).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
+(demo.Simple.project).  --surface [NAME,...][:MIN_BYTE] prints the surface table of the scene in view -- faces per axis, area, enclosed
+texels beside the measured count and sphericity per segment (demo.Simple.surface) -- and --surface-out FILE.stl|.obj writes the mesh of
+those segments together (demo.Simple.export_surface).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
 """
@@ -224,6 +226,24 @@ def _measure_table(rows):
     return "\n".join(lines)
 
 
+def _surface_arg(text):
+    """NAME[,NAME...][:MIN_BYTE] -> (names or label values, None for every segment in view; min_byte)"""
+    names, _, m = text.rpartition(":") if ":" in text else (text, "", "")
+    try:
+        min_byte = int(m) if m else 1
+    except ValueError:
+        raise SystemExit("--surface: NAME[,NAME...][:MIN_BYTE], MIN_BYTE an integer in 1..255")
+    return [int(v) if v.isdigit() else v for v in names.split(",") if v] or None, min_byte
+
+
+def _surface_table(rows):
+    """the table --surface prints: one line per segment of demo.Simple.surface's dict"""
+    lines = ["%-16s %5s %10s %10s %10s %12s %12s %12s %10s" % ("segment", "label", "faces x", "faces y", "faces z", "area", "enclosed", "measured", "sphericity")]
+    for name, s in rows.items():
+        lines.append("%-16s %5d %10d %10d %10d %12.1f %12d %12d %10.3f" % ((name, s["label"]) + tuple(s["pairs"]) + (s["area"], s["enclosed"], s["measured"], s["sphericity"])))
+    return "\n".join(lines)
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -286,9 +306,22 @@ def run_simple(args):
                             {"visible": d.histogram(ctx), **{v: d.histogram(ctx, [int(v) if v.isdigit() else v]) for v in names}})
             except ValueError as e:
                 raise SystemExit("--measure: %s" % e)
+        surfaced = None
+        if getattr(args, "surface", None) is not None or getattr(args, "surface_out", None):
+            names, min_byte = _surface_arg(args.surface or "")
+            try:
+                surfaced = d.surface(ctx, names, min_byte)
+                if args.surface_out:
+                    d.export_surface(ctx, args.surface_out, names, min_byte)
+            except ValueError as e:
+                raise SystemExit("--surface: %s" % e)
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    if surfaced is not None:
+        print(_surface_table(surfaced))
+        if args.surface_out:
+            print("surface: %s -> %s" % (", ".join(surfaced) or "no faces", args.surface_out))
     for axis, img in sorted(slices.items()):
         image.write_png(_slice_path(path, axis), img)
         print("slice %s: %dx%d -> %s" % (axis, img.shape[1], img.shape[0], _slice_path(path, axis)))
@@ -419,6 +452,10 @@ def main(argv=None):
     run.add_argument("--measure", nargs="?", const="", metavar="NAME,...",
                      help="also print the table of segment statistics of the scene in view (all segments, or the named ones) and write the density "
                           "histograms as <screenshot>_histogram.json")
+    run.add_argument("--surface", nargs="?", const="", metavar="NAME,...[:MIN_BYTE]",
+                     help="also print the surface table of the scene in view (all segments, or the named ones; texels with a density byte of at "
+                          "least MIN_BYTE, default 1, are solid): faces per axis, area, enclosed texels beside the measured count, sphericity")
+    run.add_argument("--surface-out", metavar="FILE.stl|.obj", help="also write the surface of those segments together as a binary STL or an OBJ mesh")
     run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")

@@ -167,6 +167,40 @@ SEGMENT_STATS_DTYPE = np.dtype([("count", "<u8"), ("sum", "<u8"), ("sum_sq", "<u
                                 ("box", "<i4", (6,)), ("min", "<u4"), ("max", "<u4")])
 
 
+SURFACE_UNCUT = 1                                              # volym_surface.flags
+SURFACE_SCAN_ROWS = 256                                        # rows of a request's box per workgroup of the offset scan
+
+
+class Surface(C.Structure):
+    """volym_surface (include/volym_hip.h): box, flags, min_byte and select table of one surface pass, 288 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("select", C.c_uint8 * 256),
+    ]
+
+
+class SurfaceSummary(C.Structure):
+    """volym_surface_summary (include/volym_hip.h): faces per label and direction, their total and the divergence sums, 24584 bytes"""
+    _fields_ = [
+        ("faces", (C.c_uint64 * 6) * 256),
+        ("total", C.c_uint64),
+        ("pos", (C.c_uint64 * 3) * 256),
+        ("neg", (C.c_uint64 * 3) * 256),
+    ]
+
+
+class SurfaceFace(C.Structure):
+    """volym_surface_face (include/volym_hip.h): one boundary face, 8 bytes"""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("z", C.c_uint16), ("dir", C.c_uint8), ("label", C.c_uint8)]
+
+
+# the summary and the face record as NumPy structured dtypes (GpuContext.read_surface / read_surface_faces, scene.surface_volume)
+SURFACE_SUMMARY_DTYPE = np.dtype([("faces", "<u8", (256, 6)), ("total", "<u8"), ("pos", "<u8", (256, 3)), ("neg", "<u8", (256, 3))])
+SURFACE_FACE_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("dir", "u1"), ("label", "u1")])
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -307,6 +341,12 @@ SIGNATURES = {
     "volym_read_measure": (C.c_int, [_ctx, C.POINTER(Measurement)]),
     "volym_measure_device_ptr": (C.c_void_p, [_ctx]),
     "volym_measure_check": (C.c_int, [C.POINTER(Measure), C.POINTER(C.c_uint32)]),
+    "volym_surface_pass": (C.c_int, [_ctx, C.POINTER(Surface)]),
+    "volym_read_surface": (C.c_int, [_ctx, C.POINTER(SurfaceSummary)]),
+    "volym_surface_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_surface_faces_pass": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
+    "volym_read_surface_faces": (C.c_int, [_ctx, C.POINTER(SurfaceFace), C.c_uint64]),
+    "volym_surface_check": (C.c_int, [C.POINTER(Surface), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

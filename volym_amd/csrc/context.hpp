@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI, and the measure pass over them; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI, and the measure pass over them; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -213,6 +213,24 @@ struct volym_ctx {
     volym_measurement* d_measure = nullptr;
     bool measure_valid = false;              // a pass has written d_measure since the latest volym_set_volume
 
+    // surface passes (volym_surface_pass / volym_surface_faces_pass, surface.hip): all allocated on first use, all used on slot 0's stream
+    uint64_t scene_serial = 0;               // bumped by every set-up call that changes a byte the surface pass reads (density, labels)
+    volym_surface_summary* d_surface = nullptr;
+    uint32_t* d_surface_rows = nullptr;      // per row of the request's box: its face count, scanned in place into the offset of its first face
+    uint32_t* d_surface_sums = nullptr;      // the scan's block sums: one per VOLYM_SURFACE_SCAN_ROWS rows
+    size_t surface_rows_capacity = 0;        // rows d_surface_rows holds
+    bool surface_valid = false;              // a pass has written d_surface since the latest volym_set_volume
+    uint64_t surface_serial = 0;             // scene_serial at that pass: the offsets describe the scene while it is the current one
+    volym_surface surface_request = {};      // what that pass was asked (the emit pass walks it again)
+    const uint8_t* surface_vol = nullptr;    // ... and the density it read (d_vol, or d_vol0 under UNCUT)
+    bool surface_labels = false;             // ... and whether it read labels
+    bool surface_total_known = false;        // surface_total is the pass's total (read back once)
+    uint64_t surface_total = 0;
+    volym_surface_face* d_surface_faces = nullptr;   // the context's own face list, grown to the largest total asked for so far
+    size_t surface_faces_capacity = 0;
+    bool surface_faces_valid = false;        // a faces pass has written d_surface_faces since the latest surface pass
+    uint64_t surface_faces_count = 0;        // ... that many records
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -269,6 +287,8 @@ void free_slice(volym_ctx* c);
 void free_projection(volym_ctx* c);
 // scene_bytes.hip: what the context keeps for the measure pass (every stream idle)
 void free_measure(volym_ctx* c);
+// surface.hip: what the context keeps for the surface passes (every stream idle)
+void free_surface(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume

@@ -10,6 +10,8 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
+#include <fstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -495,6 +497,98 @@ public:
         if (p.record.status != 2 || !p.record.has_labels) return false;
         out = measure(ctx, a, {std::to_string(p.record.label)}).front();
         return true;
+    }
+    // New: segment surfaces (volym_surface_pass) -- what a user reads off the summary for one label: faces per direction and per
+    // axis, area in physical units, the enclosed texel count from the divergence sums (pos - neg, equal on the three axes when the
+    // label was selected alone) beside the measured count, and sphericity pi^(1/3) (6 V)^(2/3) / A with V from the measured count.
+    struct Surfaced {
+        uint8_t label;
+        std::string segment;
+        uint64_t faces[6], pairs[3], enclosed, measured;
+        double area, volume, sphericity;
+    };
+    // One surface pass per segment -- each selected alone, so that its surface is closed and includes the faces it shares with other
+    // segments -- and one measure pass, over the scene as it stands (uncut: as it was uploaded).  `segments` as measure takes them;
+    // min_byte: the density byte from which a texel is solid.  Segments without faces are left out.
+    std::vector<Surfaced> surface(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {}, uint32_t min_byte = 1u,
+                                  bool uncut = false, const double spacing[3] = nullptr)
+    {
+        const double one[3] = {1.0, 1.0, 1.0};
+        const double* sp = spacing ? spacing : one;
+        std::vector<Surfaced> out;
+        std::vector<struct volym_surface_summary> r(1);
+        for (const Measured& m : measure(ctx, a, segments, nullptr, uncut, spacing)) {
+            volym_surface s{};
+            s.box[3] = a.nx; s.box[4] = a.ny; s.box[5] = a.nz;
+            s.flags = uncut ? VOLYM_SURFACE_UNCUT : 0u;
+            s.min_byte = min_byte;
+            s.select[m.label] = 1;
+            ctx.check(volym_surface_pass(ctx.handle(), &s));
+            ctx.check(volym_read_surface(ctx.handle(), r.data()));
+            Surfaced f{};
+            f.label = m.label; f.segment = m.segment; f.measured = m.stats.count;
+            uint64_t all = 0;
+            for (int d = 0; d < 6; ++d) { f.faces[d] = r[0].faces[m.label][d]; f.pairs[d >> 1] += f.faces[d]; all += f.faces[d]; }
+            if (all == 0u) continue;
+            f.enclosed = r[0].pos[m.label][0] - r[0].neg[m.label][0];
+            f.area = static_cast<double>(f.pairs[0]) * sp[1] * sp[2] + static_cast<double>(f.pairs[1]) * sp[0] * sp[2] + static_cast<double>(f.pairs[2]) * sp[0] * sp[1];
+            f.volume = static_cast<double>(f.measured) * sp[0] * sp[1] * sp[2];
+            f.sphericity = std::cbrt(3.14159265358979323846) * std::pow(6.0 * f.volume, 2.0 / 3.0) / f.area;
+            out.push_back(f);
+        }
+        return out;
+    }
+    // The boundary of the union of `segments` (empty: of every label) as face records in ascending (z, y, x, dir): one surface pass with
+    // all of them selected, one emit pass into the context's own buffer, and the read.
+    std::vector<struct volym_surface_face> surface_faces(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {},
+                                                         uint32_t min_byte = 1u, bool uncut = false)
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        volym_surface s{};
+        s.box[3] = a.nx; s.box[4] = a.ny; s.box[5] = a.nz;
+        s.flags = uncut ? VOLYM_SURFACE_UNCUT : 0u;
+        s.min_byte = min_byte;
+        for (int l = 0; l < 256; ++l) s.select[l] = segments.empty() ? 1 : 0;
+        for (const std::string& name : segments) s.select[label_value_of(a, name)] = 1;
+        ctx.check(volym_surface_pass(ctx.handle(), &s));
+        ctx.check(volym_surface_faces_pass(ctx.handle(), nullptr, 0));
+        std::vector<struct volym_surface_summary> r(1);
+        ctx.check(volym_read_surface(ctx.handle(), r.data()));
+        std::vector<struct volym_surface_face> faces(static_cast<size_t>(r[0].total));
+        ctx.check(volym_read_surface_faces(ctx.handle(), faces.data(), faces.size()));
+        return faces;
+    }
+    // Binary STL of a face list: 84 + 100 * faces bytes, two triangles per face (corners 0, 1, 2 and 0, 2, 3 of its quad, wound
+    // counter-clockwise seen from outside), the normal taken from the face's direction; vertices at origin + texel corner * spacing.
+    static void write_stl(const std::string& path, const std::vector<struct volym_surface_face>& faces, const double spacing[3] = nullptr,
+                          const double origin[3] = nullptr)
+    {
+        static const uint8_t corner[6][4][3] = {{{0, 0, 0}, {0, 0, 1}, {0, 1, 1}, {0, 1, 0}}, {{1, 0, 0}, {1, 1, 0}, {1, 1, 1}, {1, 0, 1}},
+                                                {{0, 0, 0}, {1, 0, 0}, {1, 0, 1}, {0, 0, 1}}, {{0, 1, 0}, {0, 1, 1}, {1, 1, 1}, {1, 1, 0}},
+                                                {{0, 0, 0}, {0, 1, 0}, {1, 1, 0}, {1, 0, 0}}, {{0, 0, 1}, {1, 0, 1}, {1, 1, 1}, {0, 1, 1}}};
+        std::ofstream f(path, std::ios::binary);
+        char header[80];
+        std::memset(header, ' ', sizeof header);
+        std::memcpy(header, "volym segment surface (binary STL)", 34);
+        f.write(header, sizeof header);
+        const uint32_t n = static_cast<uint32_t>(2u * faces.size());
+        f.write(reinterpret_cast<const char*>(&n), 4);
+        for (const struct volym_surface_face& face : faces) {
+            const uint16_t t[3] = {face.x, face.y, face.z};
+            float v[4][3];
+            for (int k = 0; k < 4; ++k)
+                for (int c = 0; c < 3; ++c)
+                    v[k][c] = static_cast<float>((origin ? origin[c] : 0.0) + static_cast<double>(t[c] + corner[face.dir][k][c]) * (spacing ? spacing[c] : 1.0));
+            float normal[3] = {0.0f, 0.0f, 0.0f};
+            normal[face.dir >> 1] = (face.dir & 1u) ? 1.0f : -1.0f;
+            const uint16_t attr = 0;
+            static const int triangle[2][3] = {{0, 1, 2}, {0, 2, 3}};
+            for (const auto& tri : triangle) {
+                f.write(reinterpret_cast<const char*>(normal), 12);
+                for (int k = 0; k < 3; ++k) f.write(reinterpret_cast<const char*>(v[tri[k]]), 12);
+                f.write(reinterpret_cast<const char*>(&attr), 2);
+            }
+        }
     }
     // a colour per label value of the segments table for the slice overlay: hues spread by the golden angle over the label values,
     // saturation 0.85, value 1; every other label, 0 included, stays transparent

@@ -539,6 +539,7 @@ void volym_destroy(volym_ctx* c)
     free_slice(c);
     free_projection(c);
     free_measure(c);
+    free_surface(c);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }

@@ -62,6 +62,7 @@ static int upload_volume(volym_ctx* c, uint8_t** dst, const uint8_t* src, uint32
         return fail(c, VOLYM_E_INVALID, "volume: each dimension <= 4096 and the brick-padded size < 2^32");
     const int rc = quiesce_slots(c);
     if (rc != VOLYM_OK) return rc;
+    ++c->scene_serial;          // density or labels are replaced, or (importances) the labels are about to go: a surface pass is stale
     if (*dst) { HIPCHK(c, hipFree(*dst)); *dst = nullptr; }
     uint8_t* staging = nullptr;
     hipError_t e = alloc_layout(dst, nb);
@@ -645,6 +646,7 @@ static int retarget(volym_ctx* c, const SceneCut& from, const SceneCut& to, bool
         int rc = quiesce_slots(c);
         if (rc == VOLYM_OK) rc = ensure_uncropped_copies(c, vol);      // in stream order in front of the rewrites
         if (rc != VOLYM_OK) return rc;
+        if (vol) ++c->scene_serial;                                    // density bytes change: a surface pass is stale
     }
     for (int a = 0; a < 3; ++a) { c->crop_lo[a] = to.lo[a]; c->crop_hi[a] = to.hi[a]; c->clip_n[a] = to.n[a]; }
     c->clip_d = to.d;
@@ -848,6 +850,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     if (c->d_vol0) { HIPCHK(c, hipFree(c->d_vol0)); c->d_vol0 = nullptr; }
     if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
     c->measure_valid = false;               // (a result describes the volume it was measured in)
+    free_surface(c);                        // (and so do a surface's summary, row offsets and faces, which are sized by it)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;

@@ -9,7 +9,8 @@
 //   run simple: one frame of the interactive default view (src/state.rs:41-55) to frame.ppm; --slice AXIS,INDEX also writes the
 //   slice normal to x, y or z through that texel (Simple::slice) to frame_slice_<axis>.ppm; --project MAX|MEAN[,STEP] the
 //   maximum or mean intensity projection of the view (Simple::project) to frame_project_<mode>.ppm; --measure [NAME,...] prints
-//   the table of segment statistics of the scene in view (Simple::measure).
+//   the table of segment statistics of the scene in view (Simple::measure); --surface [NAME,...][:MIN_BYTE] prints the surface
+//   table (Simple::surface) and --surface-out FILE.stl writes the mesh of those segments together.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -55,6 +56,10 @@ struct Options {
     float project_step = 0.0f;     // 0: the march's dense step
     bool measure = false;          // --measure [NAME,...]: also print the table of segment statistics (run simple)
     std::vector<std::string> measure_names;
+    bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
+    std::vector<std::string> surface_names;
+    uint32_t surface_min_byte = 1;
+    std::string surface_out;       // --surface-out FILE.stl: also write the mesh of those segments together
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -228,6 +233,20 @@ int run_simple(const Options& o)
                         r.centroid[2], r.stats.box[0], r.stats.box[1], r.stats.box[2], r.stats.box[3], r.stats.box[4], r.stats.box[5]);
         }
     }
+    if (o.surface || !o.surface_out.empty()) {
+        // the surface of each segment in view, selected alone; the file holds the boundary of all of them together
+        const std::vector<Simple::Surfaced> rows = demo.surface(ctx, assets, o.surface_names, o.surface_min_byte);
+        std::printf("%-16s %5s %10s %10s %10s %12s %12s %12s %10s\n", "segment", "label", "faces x", "faces y", "faces z", "area", "enclosed", "measured", "sphericity");
+        for (const Simple::Surfaced& r : rows)
+            std::printf("%-16s %5u %10llu %10llu %10llu %12.1f %12llu %12llu %10.3f\n", r.segment.c_str(), r.label, static_cast<unsigned long long>(r.pairs[0]),
+                        static_cast<unsigned long long>(r.pairs[1]), static_cast<unsigned long long>(r.pairs[2]), r.area, static_cast<unsigned long long>(r.enclosed),
+                        static_cast<unsigned long long>(r.measured), r.sphericity);
+        if (!o.surface_out.empty()) {
+            const std::vector<struct volym_surface_face> faces = demo.surface_faces(ctx, assets, o.surface_names, o.surface_min_byte);
+            Simple::write_stl(o.surface_out, faces);
+            std::printf("surface: %zu faces -> %s\n", faces.size(), o.surface_out.c_str());
+        }
+    }
     return 0;
 }
 
@@ -302,6 +321,34 @@ int main(int argc, char** argv)
                     }
                 }
             }
+            else if (a == "--surface") {
+                o.surface = true;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") {
+                    std::string v = next();
+                    const size_t colon = v.rfind(':');
+                    if (colon != std::string::npos) {
+                        size_t used = 0;
+                        unsigned long m = 0;
+                        try { m = std::stoul(v.substr(colon + 1), &used); } catch (const std::exception&) { used = 0; }
+                        if (used == 0 || used != v.size() - colon - 1 || m < 1 || m > 255) throw Error(VOLYM_E_INVALID, "--surface: NAME[,NAME...][:MIN_BYTE], MIN_BYTE in 1..255");
+                        o.surface_min_byte = static_cast<uint32_t>(m);
+                        v = v.substr(0, colon);
+                    }
+                    size_t pos = 0;
+                    while (pos <= v.size()) {
+                        const size_t comma = std::min(v.find(',', pos), v.size());
+                        if (comma > pos) o.surface_names.push_back(v.substr(pos, comma - pos));
+                        pos = comma + 1u;
+                    }
+                }
+            }
+            else if (a == "--surface-out") {
+                o.surface_out = next();
+                const size_t n = o.surface_out.size();
+                std::string ext = n >= 4 ? o.surface_out.substr(n - 4) : std::string();
+                for (char& ch : ext) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
+                if (ext != ".stl") throw Error(VOLYM_E_INVALID, "--surface-out: a file ending in .stl (the Python CLI also writes .obj)");
+            }
             else if (a == "--project") {
                 const std::string v = next();
                 const size_t comma = v.find(',');
@@ -315,7 +362,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

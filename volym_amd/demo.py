@@ -405,6 +405,37 @@ class GpuContext:
         """The context's own result (a volym_measurement in device memory) after a pass (None before any)."""
         return _lib.lib().volym_measure_device_ptr(self.handle)
 
+    # ---- segment surfaces ----------------------------------------------------------------------
+    def surface_pass(self, surface=None):
+        """Enqueue one surface pass (include/volym_hip.h volym_surface_pass; scene.surface_volume is its definition): the boundary
+        faces of the solid texels of the scene as it stands, counted per label and direction, and the offset of every row's first
+        face.  `surface` is a scene.Surface; None: the whole volume, min_byte 1, every label."""
+        c = None if surface is None else C.byref(surface.to_c())
+        self._ck(_lib.lib().volym_surface_pass(self.handle, c))
+
+    def read_surface(self):
+        """The summary of the latest surface pass: an np.void of _lib.SURFACE_SUMMARY_DTYPE (faces, total, pos, neg).  Blocks."""
+        out = np.zeros(1, _lib.SURFACE_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_surface(self.handle, out.ctypes.data_as(C.POINTER(_lib.SurfaceSummary))))
+        return out[0]
+
+    def surface_device_ptr(self):
+        """The context's own summary (a volym_surface_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_surface_device_ptr(self.handle)
+
+    def surface_faces_pass(self, target_ptr=None, capacity_faces=0):
+        """The emit pass of the latest surface pass (volym_surface_faces_pass): its faces in ascending (z, y, x, dir) into device
+        memory of capacity_faces 8-byte records at target_ptr, or (None) into a buffer the context owns (read_surface_faces)."""
+        self._ck(_lib.lib().volym_surface_faces_pass(self.handle, target_ptr, int(capacity_faces)))
+
+    def read_surface_faces(self, total=None):
+        """The face records of the latest surface_faces_pass into the context's own buffer (_lib.SURFACE_FACE_DTYPE).  total: how
+        many the pass wrote, when the caller has read the summary already (None: it is read here).  Blocks."""
+        n = int(self.read_surface()["total"]) if total is None else int(total)
+        out = np.zeros(n, _lib.SURFACE_FACE_DTYPE)
+        self._ck(_lib.lib().volym_read_surface_faces(self.handle, out.ctypes.data_as(C.POINTER(_lib.SurfaceFace)), n))
+        return out
+
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
         s = _lib.Stats()
@@ -743,6 +774,64 @@ class Simple(ComputeDemo):
                 s.update(label=l, in_view=s["count"] / total if total else 0.0)
             out[self._segment_name(l) or "label %d" % l] = s
         return out
+
+    def _surface_request(self, ctx, values, min_byte, box01, uncut):
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        box = None if box01 is None else scene.crop_box_texels(box01[0], box01[1], self.dims)
+        select = None if values is None else scene.surface_select(values)
+        return scene.check_surface(scene.Surface(box, _lib.SURFACE_UNCUT if uncut else 0, min_byte, select, dims=self.dims), self.dims)
+
+    def surface(self, ctx, segments=None, min_byte=1, box01=None, uncut=False, spacing=(1, 1, 1)):
+        """The surface of each of `segments` in the scene as it stands (crop box, clip plane and hidden segments applied; uncut=True:
+        as it was uploaded): one surface pass per segment -- each selected alone, so that its surface is closed and includes the
+        faces it shares with other segments -- one measure pass over the same box, and the reads.  segments: names, ids or label
+        values (None: every label value that has texels in view); min_byte: 1..255, the density byte from which a texel is solid;
+        box01: (lo, hi) in the unit-cube coordinates set_crop takes (None: the whole volume).  Returns {name: summary} in label
+        order for every segment that has faces: scene.surface_summary's dict (faces, pairs, area, enclosed, volume, sphericity)
+        with "measured", the measure pass's count of the segment's texels in the box -- equal to "enclosed" when min_byte is 1 and
+        no texel of the segment in view has density 0.  The labels go to the device first if they are not there yet; without
+        labels everything is label 0, the isosurface density >= min_byte."""
+        s = self._surface_request(ctx, None, min_byte, box01, uncut)
+        ctx.measure_pass(scene.Measure(s.box, _lib.MEASURE_UNCUT if uncut else 0, dims=self.dims))
+        rec, _ = ctx.read_measure()
+        values = self._label_values(segments) if segments is not None else [int(l) for l in np.flatnonzero(rec["count"])]
+        out = {}
+        for l in values:
+            ctx.surface_pass(s.replace(select=scene.surface_select([l])))
+            one = scene.surface_summary(ctx.read_surface(), l, spacing, rec[l])
+            if one is not None:
+                out[self._segment_name(l) or "label %d" % l] = one
+        return out
+
+    def surface_faces(self, ctx, segments=None, min_byte=1, box01=None, uncut=False):
+        """The boundary of the union of `segments` (None: of every label) as face records in ascending (z, y, x, dir): one surface
+        pass with all of them selected, one emit pass into the context's own buffer, and the reads.  Returns (summary, faces):
+        the np.void of _lib.SURFACE_SUMMARY_DTYPE and the records of _lib.SURFACE_FACE_DTYPE (scene.surface_mesh makes the mesh)."""
+        s = self._surface_request(ctx, None if segments is None else self._label_values(segments), min_byte, box01, uncut)
+        ctx.surface_pass(s)
+        ctx.surface_faces_pass()
+        summary = ctx.read_surface()
+        return summary, ctx.read_surface_faces(summary["total"])
+
+    def surface_at(self, ctx, x, y, alpha_min=0.5, **kw):
+        """Click for the surface: pick pixel (x, y), then the surface of the segment it shows.  Returns the pick with a "surface"
+        entry (the summary of that segment, as surface gives it), None when the pixel shows no labelled sample or the segment has
+        no face.  Keywords go to surface."""
+        p = self.pick(ctx, x, y, alpha_min)
+        p["surface"] = None
+        if p["status"] == "hit" and p["label"] is not None:
+            p["surface"] = next(iter(self.surface(ctx, [p["label"]], **kw).values()), None)
+        return p
+
+    def export_surface(self, ctx, path, segments=None, min_byte=1, box01=None, uncut=False, spacing=(1, 1, 1), origin=(0, 0, 0)):
+        """Write the boundary of the union of `segments` (surface_faces) to `path`: binary STL or OBJ by the name's ending
+        (mesh.write).  Vertices are at origin + texel corner * spacing.  Returns scene.surface_summary of all the selected labels
+        together (None, and an empty mesh, without faces)."""
+        from . import mesh
+        summary, faces = self.surface_faces(ctx, segments, min_byte, box01, uncut)
+        mesh.write(path, faces, spacing, origin)
+        return scene.surface_summary(summary, None, spacing)
 
     def histogram(self, ctx, segments=None):
         """The density histogram of the visible scene (segments=None), or of the given segments (names, ids or label values) as far

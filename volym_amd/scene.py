@@ -769,6 +769,195 @@ def segment_summary(stats, spacing=(1, 1, 1)):
             "box": (tuple(box[:3]), tuple(box[3:])), "volume": count * sp[0] * sp[1] * sp[2]}
 
 
+class Surface:
+    """volym_surface (include/volym_hip.h): what one surface pass takes the boundary of.  box: (lo, hi) in texels of the prepared
+    volume, lo inclusive, hi exclusive (None: the whole volume, which needs `dims`); flags: _lib.SURFACE_UNCUT; min_byte: 1..255, a
+    texel is solid only with a density byte of at least this; select: 256 entries, label value -> non-zero when its texels can be
+    solid (None: every label)."""
+
+    def __init__(self, box=None, flags=0, min_byte=1, select=None, dims=None):
+        if box is None:
+            if dims is None:
+                raise ValueError("a surface without a box needs the volume's dims")
+            box = ((0, 0, 0), tuple(int(v) for v in dims))
+        lo, hi = box
+        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.flags = int(flags)
+        self.min_byte = int(min_byte)
+        self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        fields = {k: getattr(self, k) for k in ("box", "flags", "min_byte", "select")}
+        for k in kw:
+            if k not in fields:
+                raise TypeError("a surface has no field %r" % k)
+        fields.update(kw)
+        return Surface(**fields)
+
+    def to_c(self):
+        """The _lib.Surface of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Surface()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("surface: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        if not 0 <= self.flags < 2 ** 32 or not 0 <= self.min_byte < 2 ** 32:
+            raise ValueError("surface: flags = %d and min_byte = %d must be u32" % (self.flags, self.min_byte))
+        c.flags, c.min_byte = self.flags, self.min_byte
+        if self.select.size != 256 or not ((self.select >= 0) & (self.select <= 255)).all():
+            raise ValueError("surface: the select table is 256 bytes")
+        c.select = (C.c_uint8 * 256)(*[int(g) for g in self.select])
+        return c
+
+
+def surface_select(label_values):
+    """A select table: 1 for the given label values, 0 for every other."""
+    s = np.zeros(256, np.int64)
+    for l in label_values:
+        if not 0 <= int(l) <= 255:
+            raise ValueError("a label value is a u8, got %r" % (l,))
+        s[int(l)] = 1
+    return s
+
+
+def check_surface(surface, dims):
+    """The validity rules of volym_surface_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits, min_byte
+    in 1..255.  Returns the surface; raises ValueError."""
+    s = surface
+    dims = [int(v) for v in dims]
+    lo, hi = s.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("surface: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("surface box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    if s.flags & ~_lib.SURFACE_UNCUT or s.flags < 0:
+        raise ValueError("surface: unknown flag bits in %#x" % s.flags)
+    if not 1 <= s.min_byte <= 255:
+        raise ValueError("surface: min_byte is 1..255, got %d" % s.min_byte)
+    if np.asarray(s.select).size != 256:
+        raise ValueError("surface: the select table has 256 entries")
+    return s
+
+
+def empty_surface():
+    """(summary, faces) of a pass that finds nothing: a zero summary (np.void of _lib.SURFACE_SUMMARY_DTYPE) and no face records."""
+    return np.zeros(1, _lib.SURFACE_SUMMARY_DTYPE)[0], np.zeros(0, _lib.SURFACE_FACE_DTYPE)
+
+
+def surface_volume(prepared, dims, surface, labels=None, cut=None, uncut=None):
+    """The definition of the surface passes (include/volym_hip.h volym_surface_pass / volym_surface_faces_pass), NumPy integers only;
+    equal to the device in every byte.  `prepared`: the density bytes of the scene as it stands (box, plane and mask applied:
+    cut_volume); `uncut`: the density before any cut, read under SURFACE_UNCUT (None: the context never cut, `prepared` is read);
+    `labels`: prepared label bytes of the volume's dimensions (None: every texel has label 0).  `cut` is what measure_volume takes in
+    this place and is not read: a cut texel has byte 0 in `prepared` and min_byte >= 1, so the cuts are in the bytes.
+    Returns (summary, faces): an np.void of _lib.SURFACE_SUMMARY_DTYPE and the records (_lib.SURFACE_FACE_DTYPE) in ascending
+    (z, y, x, dir)."""
+    s = check_surface(surface, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    n = (nx, ny, nz)
+    lo, hi = s.box
+    summary, none = empty_surface()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, none
+    whole = bool(s.flags & _lib.SURFACE_UNCUT)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("surface_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("surface_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    solid = (b >= s.min_byte) & (np.asarray(s.select)[l] != 0)
+    p = np.pad(solid, 1)                                    # a neighbour outside the request's box is not solid
+    mask = np.empty(solid.shape + (6,), bool)               # [z, y, x, dir]
+    mask[..., 0] = solid & ~p[1:-1, 1:-1, :-2]
+    mask[..., 1] = solid & ~p[1:-1, 1:-1, 2:]
+    mask[..., 2] = solid & ~p[1:-1, :-2, 1:-1]
+    mask[..., 3] = solid & ~p[1:-1, 2:, 1:-1]
+    mask[..., 4] = solid & ~p[:-2, 1:-1, 1:-1]
+    mask[..., 5] = solid & ~p[2:, 1:-1, 1:-1]
+    at = np.argwhere(mask)                                  # rows in ascending (z, y, x, dir): the canonical order
+    faces = np.zeros(len(at), _lib.SURFACE_FACE_DTYPE)
+    label = l[at[:, 0], at[:, 1], at[:, 2]].astype(np.int64)
+    t = [at[:, 2] + lo[0], at[:, 1] + lo[1], at[:, 0] + lo[2]]
+    d = at[:, 3]
+    faces["x"], faces["y"], faces["z"], faces["dir"], faces["label"] = t[0], t[1], t[2], d, label
+    summary["faces"][...] = np.bincount(label * 6 + d, minlength=256 * 6).reshape(256, 6)
+    summary["total"] = len(at)
+    for a in range(3):
+        for name, side, add in (("neg", 2 * a, 0), ("pos", 2 * a + 1, 1)):
+            sel = d == side
+            per = np.bincount(label[sel] * (n[a] + 1) + t[a][sel] + add, minlength=256 * (n[a] + 1)).reshape(256, n[a] + 1).astype(np.int64)
+            summary[name][:, a] = per @ np.arange(n[a] + 1, dtype=np.int64)
+    return summary, faces
+
+
+def surface_summary(summary, label=None, spacing=(1, 1, 1), stats=None):
+    """What a user reads off the summary of a surface pass, for one label value or (label None) for all selected labels together:
+    faces (per direction, -x +x -y +y -z +z), pairs (faces per axis: normal to x, y, z), area (sum over the axes of pairs[a] * the
+    area of a texel's face normal to a), enclosed (the number of solid texels, from the divergence sums pos - neg), volume
+    (enclosed * the volume of a texel) and sphericity (pi^(1/3) * (6 * volume)^(2/3) / area: 1 for a sphere, (pi / 6)^(1/3) ~ 0.81
+    for a cube, and a sphere made of texels tends to 2 / 3 because its staircase has 1.5 times the area).  The sums of all labels
+    together always close; those of one label do when it was selected alone (two solid texels of different labels have no face
+    between them), and where the three axes disagree enclosed, volume and sphericity are None.  With `stats`, the record of the
+    same label from a measure pass, "measured" is its count and sphericity takes the volume from it.  Python ints and floats.
+    None without faces."""
+    import math
+    pick = (lambda k: summary[k].astype(np.int64).sum(axis=0)) if label is None else (lambda k: summary[k][label])
+    faces = [int(v) for v in pick("faces")]
+    if not sum(faces):
+        return None
+    sp = [float(v) for v in spacing]
+    texel = sp[0] * sp[1] * sp[2]
+    pairs = [faces[2 * a] + faces[2 * a + 1] for a in range(3)]
+    enclosed = {int(p) - int(n) for p, n in zip(pick("pos"), pick("neg"))}
+    enclosed = enclosed.pop() if len(enclosed) == 1 else None
+    area = pairs[0] * sp[1] * sp[2] + pairs[1] * sp[0] * sp[2] + pairs[2] * sp[0] * sp[1]
+    out = {"label": None if label is None else int(label), "faces": faces, "pairs": pairs, "area": area, "enclosed": enclosed,
+           "volume": None if enclosed is None else enclosed * texel}
+    volume = out["volume"]
+    if stats is not None:
+        get = (lambda k: stats[k]) if isinstance(stats, (np.void, dict)) else (lambda k: getattr(stats, k))
+        out["measured"] = int(get("count"))
+        volume = out["measured"] * texel
+    out["sphericity"] = None if volume is None else math.pi ** (1.0 / 3.0) * (6.0 * volume) ** (2.0 / 3.0) / area
+    return out
+
+
+# corners of the face on side dir of the unit texel, counter-clockwise seen from outside: (v1 - v0) x (v2 - v0) points along dir
+SURFACE_FACE_CORNERS = np.array([
+    [(0, 0, 0), (0, 0, 1), (0, 1, 1), (0, 1, 0)],      # -x
+    [(1, 0, 0), (1, 1, 0), (1, 1, 1), (1, 0, 1)],      # +x
+    [(0, 0, 0), (1, 0, 0), (1, 0, 1), (0, 0, 1)],      # -y
+    [(0, 1, 0), (0, 1, 1), (1, 1, 1), (1, 1, 0)],      # +y
+    [(0, 0, 0), (0, 1, 0), (1, 1, 0), (1, 0, 0)],      # -z
+    [(0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 1, 1)],      # +z
+], np.int64)
+SURFACE_FACE_NORMALS = np.array([(-1, 0, 0), (1, 0, 0), (0, -1, 0), (0, 1, 0), (0, 0, -1), (0, 0, 1)], np.float32)
+
+
+def surface_mesh(faces, spacing=(1, 1, 1), origin=(0, 0, 0)):
+    """The quad mesh of a face list (records of _lib.SURFACE_FACE_DTYPE): (vertices, quads).  A texel covers [t, t + 1) on every
+    axis, so its corners are integer points; corners that several faces share become one vertex (sorted by z, y, x), at origin +
+    corner * spacing, float64 [n, 3].  quads: int64 [faces, 4], one per record in the records' order, wound counter-clockwise seen
+    from outside the solid."""
+    f = np.asarray(faces)
+    t = np.stack([f["x"], f["y"], f["z"]], axis=1).astype(np.int64)
+    corners = (t[:, None, :] + SURFACE_FACE_CORNERS[f["dir"].astype(np.int64)]).reshape(-1, 3)          # coordinates 0..4096
+    key = (corners[:, 2] * 4097 + corners[:, 1]) * 4097 + corners[:, 0]
+    unique, inverse = np.unique(key, return_inverse=True)
+    points = np.stack([unique % 4097, (unique // 4097) % 4097, unique // (4097 * 4097)], axis=1)
+    vertices = np.asarray(origin, np.float64) + points * np.asarray(spacing, np.float64)
+    return vertices, inverse.reshape(-1, 4).astype(np.int64)
+
+
 PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0     # volym_update's range for the march step
 
 
