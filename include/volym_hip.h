@@ -289,9 +289,27 @@ int volym_set_transfer_function(volym_ctx* ctx, const uint8_t* rgba8, uint32_t n
 /* ComputeDemo::update_gpu_state (src/demos/pipeline.rs:208-212): GpuCamera::update +
  * GpuParameters::update.  Fails with VOLYM_E_INVALID on out-of-range parameters.  Enqueue only; a change of the step size
  * or of the transfer function uploads 10 KiB of tables in stream order from a ring of 8 staging buffers, and only a caller
- * that makes 8 such changes while the device is still 8 frames behind waits for a slot. */
+ * that makes 8 such changes while the device is still 8 frames behind waits for a slot.
+ *
+ * The camera: inverse_view_proj and camera_position are taken verbatim, and any finite pair is rendered by the shader's rule
+ * (wgsl:221-234): the ray of a pixel starts at camera_position and passes through the pixel's point of the plane ndc z = 0,
+ * unprojected by inverse_view_proj -- with the eye inside the volume, the volume off screen or behind the eye, any roll, field
+ * of view, aspect and near plane.  The culling devices (projected hulls, the ray pool's rectangle, tile mask, tile depth
+ * bounds) describe the rays only for a CONSISTENT pair, one whose camera_position is the centre of projection of the matrix, as
+ * every pair from volym_camera_uniforms_from is: they are used while no point of a ray beyond the near plane projects further
+ * than VOLYM_VIEW_EYE_SLACK_PIXELS from the ray's own pixel (volym_view_eye_displacement), which f32 rounding of a consistent
+ * pair stays far below.  Any other pair is rendered without them: the same pixels, more time.  view_matrix and
+ * projection_matrix are not read. */
 int volym_update(volym_ctx* ctx, const volym_camera_uniforms* camera,
                  const volym_parameter_uniforms* parameters);
+/* How far camera_position is from the centre of projection of inverse_view_proj, in pixels of a W x H frame: the largest
+ * distance between the pixel of a ray and the projection, under the matrix, of a point of that ray whose clip w is at least
+ * w_min (w_min <= 0: any point beyond the near plane).  0 for the exact centre; +inf where the bound fails (camera_position at
+ * or beyond the near plane's w, or w_min not above its own).  Pure host arithmetic in double precision, no context (DESIGN.md
+ * 4, "a consistent eye").  VOLYM_E_INVALID for NULL, an empty frame, a matrix that is singular or not finite, or one whose near
+ * plane is not in front of its centre. */
+#define VOLYM_VIEW_EYE_SLACK_PIXELS 0.375     /* a quarter of the 1.5 pixels by which hulls and tile rectangles are grown */
+int volym_view_eye_displacement(const volym_camera_uniforms* camera, uint32_t W, uint32_t H, double w_min, double* pixels);
 /* ComputeDemo::compute_pass (src/demos/pipeline.rs:62-102, :214-225): enqueue one
  * ray-march of every owned tile on the context's stream; returns immediately. */
 int volym_compute_pass(volym_ctx* ctx);

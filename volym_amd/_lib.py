@@ -289,6 +289,7 @@ SIGNATURES = {
     "volym_crop_slabs": (C.c_int, [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                    C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "volym_update": (C.c_int, [_ctx, C.POINTER(CameraUniforms), C.POINTER(ParameterUniforms)]),
+    "volym_view_eye_displacement": (C.c_int, [C.POINTER(CameraUniforms), C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
     "volym_compute_pass": (C.c_int, [_ctx]),
     "volym_sync": (C.c_int, [_ctx]),
     "volym_settle": (C.c_int, [_ctx]),

@@ -156,7 +156,64 @@ bool hull_edges(const P2* pts, int n, float out[8][4])
     }
     return true;
 }
+
+// Is camera_position the centre of projection of inverse_view_proj?  ("a consistent eye".)  The shader's ray of pixel n
+// (in NDC) starts at the eye E and passes through N = unproject(n, z = 0), so its points are X = (1 - s) E + s N, and in clip space
+// (M = inverse_view_proj^-1, affine in X) clip(X) = (1 - s) e + s w_N (n, z, 1) with e = clip(E), w_N = clip(N).w.  The hulls and the
+// cells' rectangles say where X projects: ndc(X) - n = (1 - s) (e.xy - n e.w) / w_X, and with s = (w_X - e.w) / (w_N - e.w)
+//     |ndc(X) - n| <= (|e.xy| + |e.w|) |w_N / w_X - 1| / (w_N - |e.w|)      for |n| <= 1.
+// For a box whose corners all have w >= w_min > |e.w| the middle factor is at most max(1, w_N / w_min - 1): 1 for everything beyond
+// the near plane, more only for a box between the eye and that plane.  e = 0 for the centre of projection itself.
+struct ViewCheck {
+    double M[16];            // world -> clip, column-major
+    double e[4];             // clip(camera_position)
+    double wn_lo, wn_hi;     // range of w_N over the frame
+    double scale;            // |M's w row|_1: what a clip w is small against
+};
+
+bool view_check(const float (*ivp_f)[4], const float eye[3], ViewCheck& v)
+{
+    double ivp[16];
+    for (int i = 0; i < 16; ++i) ivp[i] = (&ivp_f[0][0])[i];
+    for (int i = 0; i < 16; ++i) if (!std::isfinite(ivp[i])) return false;
+    if (!std::isfinite(eye[0]) || !std::isfinite(eye[1]) || !std::isfinite(eye[2])) return false;
+    if (!invert4d(ivp, v.M)) return false;
+    for (int r = 0; r < 4; ++r) v.e[r] = v.M[0 * 4 + r] * eye[0] + v.M[1 * 4 + r] * eye[1] + v.M[2 * 4 + r] * eye[2] + v.M[3 * 4 + r];
+    v.scale = std::fabs(v.M[3]) + std::fabs(v.M[7]) + std::fabs(v.M[11]) + std::fabs(v.M[15]);
+    // w_N = 1 / (inverse_view_proj (n, 0, 1)).w, affine in n under the division: its range is taken at the frame's corners
+    v.wn_lo = INFINITY; v.wn_hi = 0.0;
+    for (int k = 0; k < 4; ++k) {
+        const double wp = ivp[0 * 4 + 3] * ((k & 1) ? 1.0 : -1.0) + ivp[1 * 4 + 3] * ((k & 2) ? 1.0 : -1.0) + ivp[3 * 4 + 3];
+        if (!(wp > 0.0) || !std::isfinite(1.0 / wp)) return false;     // a near plane that is not in front of the centre: not a view this code reasons about
+        v.wn_lo = std::min(v.wn_lo, 1.0 / wp); v.wn_hi = std::max(v.wn_hi, 1.0 / wp);
+    }
+    return std::isfinite(v.scale) && std::isfinite(v.e[0]) && std::isfinite(v.e[1]) && std::isfinite(v.e[3]);
+}
+
+// The most pixels by which a point with clip w >= w_min on a ray of the frame can project away from the ray's own pixel
+// (w_min <= 0: any point beyond the near plane); +inf where the bound does not hold
+double view_eye_displacement(const ViewCheck& v, uint32_t W, uint32_t H, double w_min)
+{
+    const double ew = std::fabs(v.e[3]);
+    if (!(ew < v.wn_lo)) return INFINITY;
+    double g = 1.0;
+    if (w_min > 0.0) {
+        if (!(ew < w_min)) return INFINITY;
+        g = std::max(1.0, v.wn_hi / w_min - 1.0);
+    }
+    const double k = g / (v.wn_lo - ew);
+    return std::max((std::fabs(v.e[0]) + ew) * k * 0.5 * W, (std::fabs(v.e[1]) + ew) * k * 0.5 * H);
+}
 }  // namespace
+
+extern "C" int volym_view_eye_displacement(const volym_camera_uniforms* camera, uint32_t W, uint32_t H, double w_min, double* pixels)
+{
+    if (!camera || !pixels || W == 0 || H == 0 || !(w_min == w_min)) return VOLYM_E_INVALID;
+    ViewCheck v;
+    if (!view_check(camera->inverse_view_proj, camera->camera_position, v)) return VOLYM_E_INVALID;
+    *pixels = view_eye_displacement(v, W, H, w_min);
+    return VOLYM_OK;
+}
 
 static void compute_culling(const volym_ctx* c, FrameSlot& s)
 {
@@ -186,30 +243,33 @@ static void compute_culling(const volym_ctx* c, FrameSlot& s)
         fp.cull |= CULL_AABB;
     }
     // world -> clip as the exact inverse of the matrix the rays are generated from
-    double ivp[16], M[16];
-    for (int i = 0; i < 16; ++i) ivp[i] = (&c->cam_copy.inverse_view_proj[0][0])[i];
-    if (!invert4d(ivp, M)) return;
+    ViewCheck view;
+    if (!view_check(c->cam_copy.inverse_view_proj, fp.eye, view)) return;
+    const double* M = view.M;
+    const double scale = view.scale;
     auto clip = [&](double x, double y, double z, double out[4]) {
         for (int r = 0; r < 4; ++r) out[r] = M[0 * 4 + r] * x + M[1 * 4 + r] * y + M[2 * 4 + r] * z + M[3 * 4 + r];
     };
-    // the eye must be the centre of projection of that matrix (w == 0), otherwise the hulls say nothing about the rays
-    double ce[4];
-    clip(fp.eye[0], fp.eye[1], fp.eye[2], ce);
-    const double scale = std::fabs(M[3]) + std::fabs(M[7]) + std::fabs(M[11]) + std::fabs(M[15]);
-    if (!(std::fabs(ce[3]) <= 1e-4 * scale)) return;
+    // the eye must be the centre of projection of that matrix (clip x, y and w all 0), otherwise the hulls say nothing about the
+    // rays: no point beyond the near plane may project further than VOLYM_VIEW_EYE_SLACK_PIXELS from the pixel of its ray
+    if (!(view_eye_displacement(view, c->W, c->H, 0.0) <= VOLYM_VIEW_EYE_SLACK_PIXELS)) return;
     double bb[4] = {0, 0, 0, 0};      // bounding rectangle of the last projected box
     auto project_box = [&](const double blo[3], const double bhi[3], float out[8][4]) -> bool {
         P2 pts[8];
+        double w_min = INFINITY;
         for (int k = 0; k < 8; ++k) {
             double q[4];
             clip((k & 1) ? bhi[0] : blo[0], (k & 2) ? bhi[1] : blo[1], (k & 4) ? bhi[2] : blo[2], q);
             if (!(q[3] > 1e-3 * scale)) return false;       // a corner at or behind the eye plane: no hull
+            w_min = std::min(w_min, q[3]);
             pts[k].x = (q[0] / q[3] + 1.0) * 0.5 * c->W;     // wgsl:221-229 inverted: pixel = (ndc + 1)/2 * W
             pts[k].y = (1.0 - q[1] / q[3]) * 0.5 * c->H;
             if (!std::isfinite(pts[k].x) || !std::isfinite(pts[k].y)) return false;
             bb[0] = k ? std::min(bb[0], pts[k].x) : pts[k].x; bb[1] = k ? std::min(bb[1], pts[k].y) : pts[k].y;
             bb[2] = k ? std::max(bb[2], pts[k].x) : pts[k].x; bb[3] = k ? std::max(bb[3], pts[k].y) : pts[k].y;
         }
+        // a box between the eye and the near plane magnifies what the eye is off by: the same bound with this box's nearest corner
+        if (!(view_eye_displacement(view, c->W, c->H, w_min) <= VOLYM_VIEW_EYE_SLACK_PIXELS)) return false;
         return hull_edges(pts, 8, out);
     };
     const double c0[3] = {0, 0, 0}, c1[3] = {1, 1, 1};
