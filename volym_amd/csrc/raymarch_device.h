@@ -121,6 +121,15 @@ struct Counters {
     unsigned long long n_vol, n_imp, n_steps, n_dense, n_hit;
 };
 
+// Lane predicates as wave masks.  A predicate that steers the march is held as the 64-bit mask of the lanes it holds in, in a scalar
+// register pair: lanes_where(<one compare>) is the v_cmp itself, masks combine with & | ^ ~ on the scalar ALU, and lane_of(mask) hands
+// a select or a branch the register pair as its condition.  A bool that is combined, carried round a loop or balloted instead costs a
+// v_cndmask 0/1 and a v_cmp back for nothing.  Rules: ballot single compares only; ~m sets the bits of dead lanes too, so AND it with
+// a mask confined to live lanes before use; inside a divergent region a ballot holds that region's lanes only.
+typedef unsigned long long lanemask;
+__device__ __forceinline__ lanemask lanes_where(bool single_compare) { return __builtin_amdgcn_ballot_w64(single_compare); }
+__device__ __forceinline__ bool lane_of(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
+
 struct V3 {
     float x, y, z;
 };
@@ -766,7 +775,8 @@ __device__ __forceinline__ Ray make_ray_ieee(const FrameParams& fp, uint32_t gx,
 }
 
 // the same values through shared reciprocals; ok: every operand was inside the range in which that is the same arithmetic
-__device__ __forceinline__ Ray make_ray_shared(const FrameParams& fp, uint32_t gx, uint32_t gy, bool& ok)
+// m_ok: the lanes (of those that call) whose operands were all inside the ranges
+__device__ __forceinline__ Ray make_ray_shared(const FrameParams& fp, uint32_t gx, uint32_t gy, lanemask& m_ok)
 {
     Ray r;
     const float scx = div_pixel(static_cast<float>(gx), static_cast<float>(fp.W), fp.rcp_w);
@@ -796,7 +806,14 @@ __device__ __forceinline__ Ray make_ray_shared(const FrameParams& fp, uint32_t g
     const float hi = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(wp[0]), __builtin_fabsf(wp[1])), __builtin_fabsf(wp[2])),
                                      __builtin_fmaxf(__builtin_fabsf(wp[3]), len));
     const float dlo = __builtin_fminf(__builtin_fminf(__builtin_fabsf(r.d.x), __builtin_fabsf(r.d.y)), __builtin_fabsf(r.d.z));
-    ok = lo > fp.setup_lo && hi < 0x1p+40f && dlo > 0x1p-30f;
+    m_ok = lanes_where(lo > fp.setup_lo) & lanes_where(hi < 0x1p+40f) & lanes_where(dlo > 0x1p-30f);
+    return r;
+}
+__device__ __forceinline__ Ray make_ray_shared(const FrameParams& fp, uint32_t gx, uint32_t gy, bool& ok)
+{
+    lanemask m_ok;
+    const Ray r = make_ray_shared(fp, gx, gy, m_ok);
+    ok = lane_of(m_ok);
     return r;
 }
 
@@ -807,9 +824,9 @@ template <bool SHARED = true>
 __device__ __forceinline__ Ray make_ray(const FrameParams& fp, uint32_t gx, uint32_t gy)
 {
     if constexpr (!SHARED) return make_ray_ieee(fp, gx, gy);
-    bool ok;
-    const Ray r = make_ray_shared(fp, gx, gy, ok);
-    if (__builtin_expect(__ballot(!ok) == 0ull, 1)) return r;
+    lanemask m_ok;
+    const Ray r = make_ray_shared(fp, gx, gy, m_ok);
+    if (__builtin_expect((~m_ok & lanes_where(true)) == 0ull, 1)) return r;      // (the calling lanes: a caller may be in a divergent region)
     return make_ray_ieee(fp, gx, gy);
 }
 

@@ -146,6 +146,10 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     constexpr int PQ_QCAP = pq_qcap(K);
     static_assert(K <= 4, "the shading queue of K > 4 does not fit the LDS");
     static_assert(CJ == 0 || IR, "look-ahead jobs belong to the importance-rendering instantiation");
+    // MASKS: the straight-line forms of both march loops (pinned flags: the headline instantiation, its bricked twin, importance
+    // rendering) carry their lane predicates as wave masks in scalar registers; the general forms carry bools
+    constexpr bool MASKS = TABLE && !COUNT && !IMP;
+    static_assert(IMP || MASKS, "the pinned-flag instantiations are table mode and uninstrumented");
     unsigned long long trace_t0 = 0;
     uint32_t trace_iters = 0, trace_flushes = 0, trace_tiles = 0, trace_marched = 0, trace_lanes = 0, trace_accepted = 0, trace_dp_iters = 0;
     unsigned long long tm_leap = 0, tm_samp = 0, tm_flush = 0, tm_mark = 0;
@@ -583,12 +587,45 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             const V3 hvec = ray_half_vector(ray.d);
             hh[lane] = make_float4(hvec.x, hvec.y, hvec.z, 0.0f);     // (a depth-parallel quad: four equal entries, owner = the first)
         }
-        bool active = in_frame && ray.hit;
+        // MASKS: the control predicates of this entry (active, last_dense, leap_ok and what the loops derive from them) are lane
+        // masks in scalar registers from here to the store (raymarch_device.h, lanes_where / lane_of); the general forms keep bools.
+        // A lane out of the frame has t_entry == t_exit == 0: no hit
+        lanemask m_active = lanes_where(gx < fe.W) & lanes_where(gy < fe.H) & lanes_where(!(ray.t_exit <= ray.t_entry));
+        lanemask m_last = 0ull, m_leap_ok = ~0ull;
+        bool active = MASKS ? lane_of(m_active) : in_frame && ray.hit;
         if (COUNT && active) n_hit++;
         float t = active ? ray.t_entry : 0.0f, cur = base, acc_a = active ? 0.0f : 1.0f;   // miss: (0,0,0,1) wgsl:239
         bool last_dense = false;
-        if (culling && tclass == TILE_HIT_TEST) active = false;     // hit rays of this tile see nothing dense: (0,0,0,0)
+        if (culling && tclass == TILE_HIT_TEST) { active = false; m_active = 0ull; }     // hit rays of this tile see nothing dense: (0,0,0,0)
         float t_end = ray.t_exit;                        // samples at t >= t_end cannot be dense
+        if constexpr (MASKS) {
+            if (culling && (fe.cull & CULL_AABB) && m_active != 0ull) {
+                // the slab test of the general form below, on every lane (a dead lane's values are never used) and its verdict as a mask
+                const float rx = __builtin_amdgcn_rcpf(ray.d.x), ry = __builtin_amdgcn_rcpf(ray.d.y), rz = __builtin_amdgcn_rcpf(ray.d.z);
+                const float ax0 = (fe.aabb_lo[0] - ray.o.x) * rx, ax1 = (fe.aabb_hi[0] - ray.o.x) * rx;
+                const float ay0 = (fe.aabb_lo[1] - ray.o.y) * ry, ay1 = (fe.aabb_hi[1] - ray.o.y) * ry;
+                const float az0 = (fe.aabb_lo[2] - ray.o.z) * rz, az1 = (fe.aabb_hi[2] - ray.o.z) * rz;
+                float tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax0, ax1), __builtin_fminf(ay0, ay1)), __builtin_fminf(az0, az1));
+                float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax0, ax1), __builtin_fmaxf(ay0, ay1)), __builtin_fmaxf(az0, az1));
+                tn = tn - 2.0e-5f * __builtin_fabsf(tn) - 1.0e-6f;
+                tf = tf + 2.0e-5f * __builtin_fabsf(tf) + 1.0e-6f;
+                if (fe.cull & CULL_TILE_DEPTH) {
+                    const auto* td = (const __attribute__((address_space(4))) uint32_t*)fe.tile_depth;
+                    const uint32_t t8 = (ty * 2u + (sub >> 1)) * fe.mask_t8x + tx * 2u + (sub & 1u);
+                    tn = __builtin_fmaxf(tn, __uint_as_float(~td[t8]));
+                    tf = __builtin_fminf(tf, __uint_as_float(td[32u * fe.mask_words + t8]));
+                }
+                const lanemask m_static = (lanes_where(ray.d.x == 0.0f) & (lanes_where(ray.o.x < fe.aabb_lo[0]) | lanes_where(ray.o.x > fe.aabb_hi[0]))) |
+                                          (lanes_where(ray.d.y == 0.0f) & (lanes_where(ray.o.y < fe.aabb_lo[1]) | lanes_where(ray.o.y > fe.aabb_hi[1]))) |
+                                          (lanes_where(ray.d.z == 0.0f) & (lanes_where(ray.o.z < fe.aabb_lo[2]) | lanes_where(ray.o.z > fe.aabb_hi[2])));
+                m_active &= ~m_static & lanes_where(tn <= tf);      // the rest is never inside the AABB: nothing dense on those rays
+                if (lane_of(m_active)) {
+                    t_end = __builtin_fminf(t_end, tf);
+                    const float t_first = __builtin_fminf(tn, t_end);
+                    replay_saturated(t, t_first, base);
+                }
+            }
+        } else
         if (culling && (fe.cull & CULL_AABB) && active) {
             // slab test against the AABB of the occupied macro cells (conservative arithmetic)
             // v_rcp_f32 (1 ulp) instead of a division: the slab distances carry a 2e-5 margin
@@ -691,11 +728,11 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         };
 
         // ---- push the samples flagged by `emit` (any subset of lanes), shade when 64 are waiting ----
-        auto append = [&](bool emit, V3 p, float w, uint32_t meta, float rho) __attribute__((always_inline)) {
+        // (the caller's mask: the straight-line forms have it from their compares, the general forms ballot their bool)
+        auto append = [&](lanemask mask, V3 p, float w, uint32_t meta, float rho) __attribute__((always_inline)) {
             if (VOLYM_DEV_SWITCHES && (fp.dev & 128u)) return;              // timing experiment: nothing is queued or shaded
-            const unsigned long long mask = __ballot(emit);
-            if (mask == 0ull) return;
-            if (emit) {
+            if constexpr (!MASKS) if (mask == 0ull) return;
+            if (lane_of(mask)) {                              // (MASKS, no lane: the branch around this is the test for an empty mask)
                 const uint32_t e0 = q_head + q_count + lane_rank_in_mask(mask), e = min(e0, e0 - PQ_QCAP);
                 q4[e] = make_float4(p.x, p.y, p.z, w); qm[e] = meta;
                 if (!TABLE) qr[e] = rho;
@@ -710,7 +747,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         // tiles that queue several batches per iteration: 32.7 us against 32.3 without it; removed)
         auto drain = [&]() __attribute__((always_inline)) { while (q_count >= 64u) flush(64u); };
 
-        if (VOLYM_DEV_SWITCHES && (fp.dev & 256u)) active = false;          // timing experiment: set-up and store only
+        if (VOLYM_DEV_SWITCHES && (fp.dev & 256u)) { active = false; m_active = 0ull; }          // timing experiment: set-up and store only
         if (TRACE) tm_mark = PQ_TICK();
         // ---- at most ONE leap per lane and iteration through provably empty macro cells (both march paths) ----
         // Looking for a leap costs ~100 instructions and an LDS round trip per iteration.  A ray that has just sampled
@@ -722,17 +759,26 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             // raymarch_kernels.h VARIANT 1).  Cells with distance value < PQ_MIN_LEAP_D are simply sampled:
             // a one-cell leap replays ~3 steps, which the K-wide speculation below covers in the same
             // iteration without the ~100 instructions and the LDS round trip of a leap. ----
-            active = active && t < t_end && acc_a < 0.95f;            // wgsl:250 (t_end: nothing dense beyond)
-            const bool want_leap = active && !last_dense && leap_ok;
-            if (__ballot(want_leap) != 0ull) {                          // inside a dense run nobody can leap
+            bool want_leap = false;
+            lanemask m_want = 0ull;
+            if constexpr (MASKS) {
+                m_active &= lanes_where(t < t_end) & lanes_where(acc_a < 0.95f);   // wgsl:250 (t_end: nothing dense beyond)
+                m_want = m_active & ~m_last & m_leap_ok;
+            } else {
+                active = active && t < t_end && acc_a < 0.95f;
+                want_leap = active && !last_dense && leap_ok;
+                m_want = __ballot(want_leap);
+            }
+            if (m_want != 0ull) {                                       // inside a dense run nobody can leap
                 // the cell lookup runs on every lane (clamped index, no branch); only D decides
                 const V3 pos = ray.o + ray.d * t;
                 const float cxf = __builtin_floorf(pos.x * mcf), cyf = __builtin_floorf(pos.y * mcf), czf = __builtin_floorf(pos.z * mcf);
                 const int cx = static_cast<int>(cxf), cy = static_cast<int>(cyf), cz = static_cast<int>(czf);
                 const bool in_range = static_cast<uint32_t>(cx | cy | cz) < fp.mc_n;
+                if constexpr (MASKS) want_leap = lane_of(m_want & lanes_where(static_cast<uint32_t>(cx | cy | cz) < fp.mc_n));
                 const uint32_t ci = in_range ? mad_u24(mad_u24(static_cast<uint32_t>(cz), fp.mc_n, static_cast<uint32_t>(cy)), fp.mc_n, static_cast<uint32_t>(cx)) : 0u;
                 uint32_t D = (static_cast<uint32_t>(VOLYM_DF_IN_LDS(fp) ? s_df[ci >> 1] : df4[ci >> 1]) >> ((ci & 1u) * 4u)) & 15u;
-                if (!(want_leap && in_range)) D = 0u;
+                if (!(MASKS ? want_leap : want_leap && in_range)) D = 0u;
                 if (D >= PQ_MIN_LEAP_D) {
                     // smoothing taps sit up to 2*0.005 along the ray from the sample (wgsl:53-60): keep them inside too
                     const float eps = gauss ? 4.0e-5f + 0.0101f : 4.0e-5f;
@@ -769,8 +815,10 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         cur = __builtin_fminf(base, cur * 1.5f);
                         t += cur;
                     }
-                    if (!(t < t_end)) active = false;             // wgsl:250
+                    if (!MASKS && !(t < t_end)) active = false;   // wgsl:250
                 }
+                // (a lane that did not leap is active only with t < t_end)
+                if constexpr (MASKS) m_active &= lanes_where(t < t_end);
             }
 
         };
@@ -788,10 +836,10 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 // matters for them is samples per iteration, and a long run of one class is exactly what they consist of.
                 constexpr int J = PQ_DP_DEPTH;
                 bool try_leap = true;
-                active = active && t < t_end;
-                while (__ballot(active) != 0ull) {
+                m_active &= lanes_where(t < t_end);
+                while (m_active != 0ull) {
                     tile_iters++;
-                    if (TRACE) { trace_iters++; trace_dp_iters++; trace_lanes += static_cast<uint32_t>(__popcll(__ballot(active))); tm_mark = PQ_TICK(); }
+                    if (TRACE) { trace_iters++; trace_dp_iters++; trace_lanes += static_cast<uint32_t>(__popcll(m_active)); tm_mark = PQ_TICK(); }
                     // a leap is worth looking for only where the march just ran through a whole batch of non-dense samples
                     // (or has not sampled yet); `active` is up to date either way
                     if (try_leap && !(VOLYM_DEV_SWITCHES && (fp.dev & 2u))) leap_phase();
@@ -807,7 +855,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                             ts[sidx] = tt; cb[sidx] = cc;
                             if ((sidx & 3) == 0) my_t[sidx >> 2] = tt;
                             else my_t[sidx >> 2] = kq == static_cast<uint32_t>(sidx & 3) ? tt : my_t[sidx >> 2];
-                            cc = last_dense ? min_step : __builtin_fminf(base, cc * 1.5f);
+                            cc = lane_of(m_last) ? min_step : __builtin_fminf(base, cc * 1.5f);
                             tt += cc;
                         }
                     }
@@ -838,8 +886,13 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     uint32_t sm = 0;
                     if (IR) {
                         bool need[J], ahead[J];
+                        lanemask m_need[J], m_any_need = 0ull;
 #pragma unroll
-                        for (int j = 0; j < J; ++j) { need[j] = active && my_b[j] >= fp.thr_byte && my_ib[j] < 255u; ahead[j] = false; }
+                        for (int j = 0; j < J; ++j) {
+                            m_need[j] = m_active & lanes_where(my_b[j] >= fp.thr_byte) & lanes_where(my_ib[j] < 255u);
+                            m_any_need |= m_need[j];
+                            need[j] = lane_of(m_need[j]); ahead[j] = false;
+                        }
                         if constexpr (CJ != 0) {
                             cj_lookahead(need, my_t, ray.o, ray.d, ray.t_exit, ahead);
                         } else if (flags & F_CONE) {
@@ -849,13 +902,10 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         } else {
                             // (the straight look-ahead through the job ring was measured: 104 us against 66 -- one chain is one lane's work
                             // here, eight lanes' there, and the ring is a window of 32 samples)
-                            bool any_need = false;
-#pragma unroll
-                            for (int j = 0; j < J; ++j) any_need = any_need || need[j];
-                            if (__ballot(any_need) != 0ull) ahead_straight_wave<J>(g, fp_here(), need, my_t, ray.o, ray.d, ray.t_exit, lane, mail, ahead, &la_rounds);
+                            if (m_any_need != 0ull) ahead_straight_wave<J>(g, fp_here(), need, my_t, ray.o, ray.d, ray.t_exit, lane, mail, ahead, &la_rounds);
                         }
 #pragma unroll
-                        for (int j = 0; j < J; ++j) sm |= (static_cast<uint32_t>(__ballot(need[j] && ahead[j]) >> qsh) & 15u) << (4 * j);
+                        for (int j = 0; j < J; ++j) sm |= (static_cast<uint32_t>((m_need[j] & __ballot(ahead[j])) >> qsh) & 15u) << (4 * j);
                     }
                     // How many samples does the sequential march accept?  It stops (wgsl:250) at the first sample with
                     // t >= t_end or alpha >= 0.95, and the predicted positions hold up to and including the first sample
@@ -874,14 +924,14 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         a_after[sidx] = a_run;
                     }
                     const uint32_t full = (1u << N) - 1u;
-                    const uint32_t mism = cm ^ (last_dense ? full : 0u);
+                    const uint32_t mism = cm ^ (lane_of(m_last) ? full : 0u);
                     const uint32_t n_c = min(static_cast<uint32_t>(__builtin_ctz(mism | (1u << N))) + 1u, static_cast<uint32_t>(N));
                     const uint32_t n_acc = min(min(n_t, n_a), n_c);          // >= 1 on an active lane
-                    const uint32_t em = active ? (cm & ~sm & ((1u << n_acc) - 1u)) : 0u;   // accepted dense samples emit, unless suppressed
-                    bool my_emit[J];
+                    const uint32_t em = cm & ~sm & ((1u << n_acc) - 1u);                  // accepted dense samples emit, unless suppressed
+                    lanemask m_emit[J];
 #pragma unroll
-                    for (int j = 0; j < J; ++j) my_emit[j] = ((em >> (4 * j + kq)) & 1u) != 0u;
-                    if (TRACE && kq == 0u && active) trace_accepted += n_acc;
+                    for (int j = 0; j < J; ++j) m_emit[j] = m_active & lanes_where(((em >> (4 * j + kq)) & 1u) != 0u);
+                    if (TRACE && kq == 0u && lane_of(m_active)) trace_accepted += n_acc;
                     // state after the last accepted sample
                     const uint32_t last = n_acc - 1u;
                     float t_sel = ts[0], cb_sel = cb[0], a_sel = a_after[0];
@@ -890,20 +940,19 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         const bool ge = last >= static_cast<uint32_t>(sidx);
                         t_sel = ge ? ts[sidx] : t_sel; cb_sel = ge ? cb[sidx] : cb_sel; a_sel = ge ? a_after[sidx] : a_sel;
                     }
-                    const bool dl = ((cm >> last) & 1u) != 0u;
-                    const bool last_dense_before = last_dense;
-                    const float cur_new = dl ? min_step : __builtin_fminf(base, cb_sel * 1.5f);    // wgsl:263-269 with the real class
-                    if (active) {
+                    const lanemask m_dl = lanes_where(((cm >> last) & 1u) != 0u);
+                    const float cur_new = lane_of(m_dl) ? min_step : __builtin_fminf(base, cb_sel * 1.5f);    // wgsl:263-269 with the real class
+                    if (lane_of(m_active)) {
                         cur = cur_new;
                         t = t_sel + cur_new;                                  // wgsl:272, :325
                         acc_a = a_sel;
-                        last_dense = dl;
                     }
-                    leap_ok = !dl && !last_dense_before && n_acc == static_cast<uint32_t>(N);
-                    try_leap = __ballot(active && leap_ok) != 0ull;
-                    active = active && t < t_end && acc_a < 0.95f;
+                    m_leap_ok = ~m_dl & ~m_last & lanes_where(n_acc == static_cast<uint32_t>(N));      // (m_last: still the class before this batch)
+                    m_last = (m_active & m_dl) | (~m_active & m_last);
+                    try_leap = (m_active & m_leap_ok) != 0ull;
+                    m_active &= lanes_where(t < t_end) & lanes_where(acc_a < 0.95f);
 #pragma unroll
-                    for (int j = 0; j < J; ++j) append(my_emit[j], my_pos[j], my_w[j], own | (my_b[j] << 8), 0.0f);
+                    for (int j = 0; j < J; ++j) append(m_emit[j], my_pos[j], my_w[j], own | (my_b[j] << 8), 0.0f);
                     if (TRACE) tm_samp += PQ_TICK() - tm_mark;
                 }
             } else {
@@ -1007,14 +1056,15 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     acc_a = alpha;
                     if (finished) active = false;
                 }
-                append(my_emit, pos, my_w, own | (b << 8) | (ib << 16), rho_k);
+                append(__ballot(my_emit), pos, my_w, own | (b << 8) | (ib << 16), rho_k);
                 if (TRACE) tm_samp += PQ_TICK() - tm_mark;
             }
             }
         } else {
-        while (__ballot(active) != 0ull) {
+        while ((MASKS ? m_active : __ballot(active)) != 0ull) {
+            if constexpr (MASKS) active = lane_of(m_active);        // (for the development paths below that ask per lane: TRACE, LB)
             tile_iters++;
-            if (TRACE) { trace_iters++; trace_lanes += static_cast<uint32_t>(__popcll(__ballot(active))); tm_mark = PQ_TICK(); if (active) trace_ray_iters++; }
+            if (TRACE) { trace_iters++; trace_lanes += static_cast<uint32_t>(__popcll(MASKS ? m_active : __ballot(active))); tm_mark = PQ_TICK(); if (active) trace_ray_iters++; }
             leap_phase();
             if (TRACE) { const unsigned long long now = PQ_TICK(); tm_leap += now - tm_mark; tm_mark = now; }
             // ---- 2. K speculative samples: positions under the prediction "class stays last_dense" ----
@@ -1027,7 +1077,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     ts[k] = tt;
-                    cc = last_dense ? min_step : __builtin_fminf(base, cc * 1.5f);
+                    cc = (MASKS ? lane_of(m_last) : last_dense) ? min_step : __builtin_fminf(base, cc * 1.5f);
                     tt += cc;
                 }
                 if constexpr (K % 2 == 0) {
@@ -1053,7 +1103,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     // need no guard (a finished lane re-reads its last texels; nothing uses them)
                     if (TABLE && !LB) bs[k] = vol[offs[k]];
                     if (IR) ibs[k] = imp[offs[k]];
-                    if (active) {
+                    if constexpr (!MASKS) if (active) {
                         if (!IR && need_imp) ibs[k] = imp[offs[k]];
                         if (!TABLE) {                                   // wgsl:253-259, all K densities in flight together
                             const V3 p = ray.o + ray.d * ts[k];
@@ -1074,7 +1124,8 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             uint32_t lb_ld[2] = {0u, 0u}, lb_dst = 0xffffu;         // the dwords this lane fetched, and the places they go to
             if constexpr (LB) {
                 const uint32_t* const vol32 = reinterpret_cast<const uint32_t*>(vol);
-                const unsigned long long act = __ballot(active);
+                const unsigned long long act = m_active;
+                if constexpr (MASKS) active = lane_of(m_active);       // (after the leap phase)
                 uint32_t used = 0u, n_new = 0u, lb_b[2] = {0u, 0u};
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
@@ -1143,20 +1194,23 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 float a_tab[K];
 #pragma unroll
                 for (int k = 0; k < K; ++k) a_tab[k] = s_tf_tab[bs[k]].w;
-                const bool predicted = last_dense;
+                const lanemask m_predicted = m_last;
                 // importance rendering (wgsl:283-295): the look-ahead of every sample that can still be accepted as dense,
                 // side by side (straight) or spread over the wave (cone); a suppressed sample only advances
-                bool supp[K];
+                lanemask m_supp[K];
 #pragma unroll
-                for (int k = 0; k < K; ++k) supp[k] = false;
+                for (int k = 0; k < K; ++k) m_supp[k] = 0ull;
                 if (IR) {
-                    bool need[K];
-                    bool chain = active;
+                    bool need[K], supp[K];
+                    lanemask m_need[K], m_any_need = 0ull;
+                    lanemask m_chain = m_active;
 #pragma unroll
                     for (int k = 0; k < K; ++k) {
-                        const bool dense_k = bs[k] >= fp.thr_byte;
-                        need[k] = chain && dense_k && ibs[k] < 255u;
-                        chain = chain && dense_k == predicted;
+                        const lanemask m_dense_k = lanes_where(bs[k] >= fp.thr_byte);
+                        m_need[k] = m_chain & m_dense_k & lanes_where(ibs[k] < 255u);
+                        m_chain &= ~(m_dense_k ^ m_predicted);
+                        m_any_need |= m_need[k];
+                        need[k] = lane_of(m_need[k]); supp[k] = false;
                     }
                     if constexpr (CJ != 0) {
                         cj_lookahead(need, ts, ray.o, ray.d, ray.t_exit, supp);
@@ -1165,33 +1219,32 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                         for (int k = 0; k < K; ++k)
                             supp[k] = ahead_cone_wave(g, fp_here(), need[k], ray.o + ray.d * ts[k], ray.d, ray.t_exit, lane, fp.cone_cos[lane & 7u] * 0.2f, fp.cone_sin[lane & 7u] * 0.2f);
                     } else {
-                        bool any_need = false;
-#pragma unroll
-                        for (int k = 0; k < K; ++k) any_need = any_need || need[k];
-                        if (__ballot(any_need) != 0ull) ahead_straight_wave<K>(g, fp_here(), need, ts, ray.o, ray.d, ray.t_exit, lane, mail, supp, &la_rounds);
+                        if (m_any_need != 0ull) ahead_straight_wave<K>(g, fp_here(), need, ts, ray.o, ray.d, ray.t_exit, lane, mail, supp, &la_rounds);
                     }
 #pragma unroll
-                    for (int k = 0; k < K; ++k) supp[k] = supp[k] && need[k];
+                    for (int k = 0; k < K; ++k) m_supp[k] = m_need[k] & __ballot(supp[k]);
                 }
-                bool valid = active;
+                lanemask m_valid = m_active;
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
-                    const bool go = valid && t < t_end && acc_a < 0.95f;             // wgsl:250
+                    // wgsl:250 (the first sample: the leap phase has just confined m_active to t < t_end and alpha < 0.95)
+                    const lanemask m_go = k == 0 ? m_valid : m_valid & lanes_where(t < t_end) & lanes_where(acc_a < 0.95f);
+                    const lanemask m_dense = lanes_where(bs[k] >= fp.thr_byte);       // <=> b/255 >= thr
+                    const lanemask m_emit = m_go & m_dense & ~m_supp[k];
+                    const bool go = lane_of(m_go);
                     if (TRACE && go) trace_accepted++;
-                    const bool dense = bs[k] >= fp.thr_byte;                          // <=> b/255 >= thr
-                    const bool emit = go && dense && !supp[k];
                     const float w = (1.0f - acc_a) * a_tab[k];                        // wgsl:313-318
                     const V3 pos = ray.o + ray.d * t;                                 // == ps[k] while go
-                    acc_a = emit ? acc_a + w : acc_a;
-                    const float cur_next = dense ? min_step : __builtin_fminf(base, cur * 1.5f);   // wgsl:263-269
+                    acc_a = lane_of(m_emit) ? acc_a + w : acc_a;
+                    const float cur_next = lane_of(m_dense) ? min_step : __builtin_fminf(base, cur * 1.5f);   // wgsl:263-269
                     cur = go ? cur_next : cur;
                     t = go ? t + cur_next : t;                                        // wgsl:272, :325
-                    last_dense = go ? dense : last_dense;
-                    valid = go && dense == predicted;                                 // later speculative positions are off
-                    if (k == K - 1) leap_ok = go && !dense && !predicted;
-                    append(emit, pos, w, own | (bs[k] << 8), 0.0f);
+                    m_last = (m_go & m_dense) | (~m_go & m_last);
+                    m_valid = m_go & ~(m_dense ^ m_predicted);                        // later speculative positions are off
+                    if (k == K - 1) m_leap_ok = m_go & ~m_dense & ~m_predicted;
+                    append(m_emit, pos, w, own | (bs[k] << 8), 0.0f);
                 }
-                active = active && t < t_end && acc_a < 0.95f;                        // wgsl:250, one iteration early
+                m_active &= lanes_where(t < t_end) & lanes_where(acc_a < 0.95f);      // wgsl:250, one iteration early
                 if (TRACE) tm_samp += PQ_TICK() - tm_mark;
                 continue;
             }
@@ -1281,7 +1334,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     }
                     if (advance) t += cur;                        // wgsl:272, :292, :325
                 }
-                append(emit, pos, w, own | (bs[k] << 8) | (ibs[k] << 16), rhos[k]);
+                append(__ballot(emit), pos, w, own | (bs[k] << 8) | (ibs[k] << 16), rhos[k]);
             }
             if (TRACE) tm_samp += PQ_TICK() - tm_mark;
         }
