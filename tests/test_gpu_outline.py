@@ -148,6 +148,44 @@ def test_synthetic_records(oracle, volym_lib):
     assert n == 21 + 6 + 6 + 6 + 2
 
 
+def test_the_own_target_keeps_its_image_while_a_pass_goes_to_a_callers(oracle, volym_lib):
+    """64 x 48: a pass into the context's own target, one into a caller's tensor -- read_outline still returns the first -- and one into
+    the own target again"""
+    from volym_amd import scene
+    W, H = 64, 48
+    rng = np.random.default_rng(5)
+    whole = (0, 0, W, H)
+    sel = scene.selection_mask([1, 3])
+
+    def records():
+        status = np.where(rng.random((H, W)) < 0.1, 2, rng.integers(0, 2, (H, W))).astype(np.uint8)
+        return _records(status, rng.integers(0, 6, (H, W)).astype(np.uint8), rng)
+
+    with _ctx(0, w=W, h=H) as ctx:
+        _scene(ctx, oracle=oracle)
+        ctx.compute_pass()
+        frame = ctx.read_rgba8()
+        first, second, third = records(), records(), records()
+        want = [scene.outline_frame(frame, p, whole, sel, RING, FILL, 2) for p in (first, second, third)]
+        assert (want[0] != want[1]).any() and (want[0] != want[2]).any() and (want[0] != frame).any()
+        dev = [_to_device(p) for p in (first, second, third)]
+        assert ctx.outline_device_ptr() is None
+        ctx.outline_pass(sel, RING, FILL, 2, records_ptr=dev[0].data_ptr(), rect=whole)
+        _same("own target", ctx.read_outline(), want[0])
+        own = ctx.outline_device_ptr()
+        assert own
+        target = torch.zeros(H * W * 4, dtype=torch.uint8, device="cuda")
+        torch.cuda.synchronize()
+        ctx.outline_pass(sel, RING, FILL, 2, records_ptr=dev[1].data_ptr(), rect=whole, target_ptr=target.data_ptr())
+        ctx.sync()
+        _same("caller's tensor", target.cpu().numpy().reshape(H, W, 4), want[1])
+        _same("own target after a pass into a caller's", ctx.read_outline(), want[0])
+        ctx.outline_pass(sel, RING, FILL, 2, records_ptr=dev[2].data_ptr(), rect=whole)
+        _same("own target again", ctx.read_outline(), want[2])
+        assert ctx.outline_device_ptr() == own
+        _same("the frame is untouched", ctx.read_rgba8(), frame)
+
+
 # ---- 2. end to end --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", [0, 1], ids=["linear", "bricked"])
 def test_end_to_end(oracle, volym_lib, layout):

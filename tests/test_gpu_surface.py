@@ -179,6 +179,35 @@ def test_a_callers_buffer_gets_the_same_faces_and_too_small_a_one_is_refused_unt
         assert ctx.surface_device_ptr()
 
 
+def test_the_contexts_own_buffers_grow_and_then_serve_a_smaller_surface(volym_lib):
+    """24^3 built like scene A (random density bytes 1..255, five labels in blocks): a small box, the whole volume, a small box again,
+    each with a surface pass of its own and a faces pass into the context's own buffer.  64, then 576, then 64 rows, so the row offsets
+    and their block sums grow with the face list at the second pass and are all larger than needed at the third"""
+    from volym_amd import scene
+    n = 24
+    dims = (n, n, n)
+    rng = np.random.default_rng(24)
+    vol = rng.integers(1, 256, n ** 3).astype(np.uint8)
+    labels = np.repeat(np.arange(n, dtype=np.uint8) // 5, n * n)              # blocks of five z planes: labels 0..4
+    boxes = [((4, 4, 4), (12, 12, 12)), ((0, 0, 0), dims), ((0, 0, 0), (8, 8, 8))]
+    totals, ptrs = [], []
+    with _ctx(0) as ctx:
+        ctx.set_volume(vol, dims, 0)
+        ctx.set_labels(labels, dims)
+        for box in boxes:
+            s = scene.Surface(box, 0, 128)
+            want = scene.surface_volume(vol, dims, s, labels=labels)
+            got = _run(ctx, s)
+            _same(box, got, want)
+            assert got[1].tobytes() == want[1].tobytes(), box
+            totals.append(int(want[0]["total"]))
+            ptrs.append(ctx.surface_device_ptr())
+    assert totals[0] > 100 and totals[2] > 100 and totals[1] > 8 * max(totals[0], totals[2]), totals
+    assert S.rows(boxes[1]) > 256 > S.rows(boxes[0]) == S.rows(boxes[2])
+    # (the face list's address has no accessor; the summary's is the one the context hands out)
+    assert ptrs[2] and ptrs[2] == ptrs[1], ptrs
+
+
 def test_a_faces_pass_after_an_edit_of_the_scenes_bytes_is_refused(volym_lib):
     from volym_amd import _lib, scene
     host = S.scene_a()

@@ -10,7 +10,7 @@ import re
 
 import pytest
 
-from tests.test_pick_resources import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
 
 OUT = os.path.join(ROOT, "profiles", "outline_kernel_resources.txt")
 KERNELS = ("volym_outline_pack_kernel", "volym_outline_blend_kernel")

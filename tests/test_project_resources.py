@@ -10,7 +10,7 @@ import re
 
 import pytest
 
-from tests.test_pick_resources import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
 
 OUT = os.path.join(ROOT, "profiles", "project_kernel_resources.txt")
 

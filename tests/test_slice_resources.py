@@ -13,7 +13,7 @@ import subprocess
 
 import pytest
 
-from tests.test_pick_resources import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
 
 OUT = os.path.join(ROOT, "profiles", "slice_kernel_resources.txt")
 

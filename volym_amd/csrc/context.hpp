@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI, and the measure pass over them; pick.hip: the pick march; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI, and the measure pass over them; pick.hip: the pick pass and its C ABI; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -21,6 +21,25 @@
 #include "worklist.hpp"
 
 namespace volym {
+
+int ctx_fail(volym_ctx* c, int code, const std::string& msg);
+
+// A device buffer of the context's own: what a pass writes when the caller passes no target.  It grows to the largest size asked
+// for and never shrinks; growing is the one blocking step of a pass.  Freed by hand (release), with the device set and the streams
+// idle: volym_destroy's order says when.  The members are defined below volym_ctx.
+template <class T>
+struct OwnedBuffer {
+    T* ptr = nullptr;
+    size_t capacity = 0;                     // elements ptr holds
+    size_t count = 0;                        // elements the latest pass into it wrote (0: none yet); the pass sets it, growth clears it
+
+    // room for `need` elements.  Nothing when there is; else `stream` (where the earlier passes into it ran) is synchronised and the
+    // buffer replaced.  On failure it is left empty: VOLYM_E_NOMEM, "hipMalloc(<what>): <hip error>"
+    int reserve(volym_ctx* c, hipStream_t stream, size_t need, const char* what);
+    // the first n elements to host memory, blocking (read_back)
+    int read(volym_ctx* c, hipStream_t stream, void* out, size_t n) const;
+    void release() { (void)hipFree(ptr); ptr = nullptr; capacity = count = 0; }
+};
 
 // What a capture hands the feedback thread: written by the caller before FB_CAPTURED, by the worker before FB_READY.
 struct FbJob {
@@ -69,13 +88,11 @@ struct FrameSlot {
     uint32_t* d_shard_own = nullptr;
     uint32_t* d_frame_own = nullptr;
     float4* d_f32 = nullptr;
-    uint32_t* d_blit = nullptr;              // volym_blit target when the caller passes none
-    size_t blit_bytes = 0;
-    uint32_t blit_w = 0, blit_h = 0;
-    uint8_t* d_gather_tmp = nullptr;
+    OwnedBuffer<uint32_t> blit;              // volym_blit target when the caller passes none
+    uint32_t blit_w = 0, blit_h = 0;         // size of the latest blit into it
+    OwnedBuffer<uint8_t> gather_tmp;         // volym_assemble_host's device copy of the gathered shards (count unused)
     uint32_t* d_pack_counters = nullptr;
     uint32_t pack_parity = 0;
-    size_t gather_tmp_bytes = 0;
     Counters* d_counters = nullptr;
     uint4* d_trace = nullptr;
 
@@ -179,57 +196,47 @@ struct volym_ctx {
     hipEvent_t throttle_ev[THROTTLE_RING] = {};
     uint32_t throttle_head = 0;
 
-    // pick passes (volym_pick_pass): the records of the latest pass, in a buffer that grows to the largest rect asked for so far.
-    // Always written on slot 0's stream.
-    volym_pick_record* d_picks = nullptr;
-    size_t pick_capacity = 0;                // records d_picks holds
-    uint32_t pick_w = 0, pick_h = 0;         // rect size of the latest pass (0: none yet)
+    // ---- the read-only passes: each writes a buffer of the context's own when the caller passes no target, always on slot 0's stream
+    // pick passes (volym_pick_pass, pick.hip): the records of the latest pass
+    volym::OwnedBuffer<volym_pick_record> picks;
+    uint32_t pick_w = 0, pick_h = 0;         // rect size of the latest pass
     uint32_t pick_x0 = 0, pick_y0 = 0;       // ... and its origin in the frame (the outline pass places the records by it)
 
-    // outline passes (volym_outline_pass, outline.hip): all allocated on first use, all used on slot 0's stream
-    uint64_t* d_outline_plane = nullptr;     // one bit per frame pixel plus zeroed guards (outline_kernels.h)
+    // outline passes (volym_outline_pass, outline.hip)
+    volym::OwnedBuffer<uint64_t> outline_plane;   // one bit per frame pixel plus zeroed guards (outline_kernels.h), reserved once
     uint32_t outline_stride = 0;             // words per plane row
-    uint32_t* d_outline = nullptr;           // W x H target when the caller passes none
-    bool outline_own_valid = false;          // a pass has written d_outline
+    volym::OwnedBuffer<uint32_t> outline;    // W x H target, reserved once
     hipEvent_t outline_ev[2] = {};           // frame of the other slot -> pass, pass -> the other slot's next work
     bool frame_rendered = false;             // some volym_compute_pass has been enqueued
 
-    // slice passes (volym_slice_pass, slice.hip): the context's own target, grown to the largest slice asked for so far; written on
-    // slot 0's stream
-    uint32_t* d_slice = nullptr;
-    size_t slice_capacity = 0;               // pixels d_slice holds
-    uint32_t slice_w = 0, slice_h = 0;       // size of the latest pass into d_slice (0: none yet)
+    // slice passes (volym_slice_pass, slice.hip)
+    volym::OwnedBuffer<uint32_t> slice;
+    uint32_t slice_w = 0, slice_h = 0;       // size of the latest pass into it
 
-    // projection passes (volym_project_pass, project.hip): the context's own records and image, each grown to the largest rect asked
-    // for so far; written on slot 0's stream
-    volym_projection* d_projection = nullptr;
-    uint32_t* d_projection_image = nullptr;
-    size_t projection_capacity = 0, projection_image_capacity = 0;      // records / pixels they hold
-    uint32_t projection_w = 0, projection_h = 0;                        // rect size of the latest pass into d_projection (0: none yet)
-    uint32_t projection_image_w = 0, projection_image_h = 0;            // ... and into d_projection_image
-    volym_projection* d_projection_at = nullptr;                        // the one record of volym_project_at, allocated on first use
+    // projection passes (volym_project_pass, project.hip): records and image
+    volym::OwnedBuffer<volym_projection> projection;
+    volym::OwnedBuffer<uint32_t> projection_image;
+    uint32_t projection_w = 0, projection_h = 0;                        // rect size of the latest pass into projection
+    uint32_t projection_image_w = 0, projection_image_h = 0;            // ... and into projection_image
+    volym::OwnedBuffer<volym_projection> projection_at;                 // the one record of volym_project_at, reserved once
 
-    // measure passes (volym_measure_pass, scene_bytes.hip): the context's own result, allocated on first use; written on slot 0's stream
-    volym_measurement* d_measure = nullptr;
-    bool measure_valid = false;              // a pass has written d_measure since the latest volym_set_volume
+    // measure passes (volym_measure_pass, scene_bytes.hip): one result, reserved once; count 1: a pass has written it since the latest
+    // volym_set_volume
+    volym::OwnedBuffer<volym_measurement> measure;
 
-    // surface passes (volym_surface_pass / volym_surface_faces_pass, surface.hip): all allocated on first use, all used on slot 0's stream
+    // surface passes (volym_surface_pass / volym_surface_faces_pass, surface.hip)
     uint64_t scene_serial = 0;               // bumped by every set-up call that changes a byte the surface pass reads (density, labels)
-    volym_surface_summary* d_surface = nullptr;
-    uint32_t* d_surface_rows = nullptr;      // per row of the request's box: its face count, scanned in place into the offset of its first face
-    uint32_t* d_surface_sums = nullptr;      // the scan's block sums: one per VOLYM_SURFACE_SCAN_ROWS rows
-    size_t surface_rows_capacity = 0;        // rows d_surface_rows holds
-    bool surface_valid = false;              // a pass has written d_surface since the latest volym_set_volume
+    volym::OwnedBuffer<volym_surface_summary> surface;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> surface_rows;   // per row of the request's box: its face count, scanned in place into the offset of its first face
+    volym::OwnedBuffer<uint32_t> surface_sums;   // the scan's block sums: one per VOLYM_SURFACE_SCAN_ROWS rows; replaced whenever surface_rows is
     uint64_t surface_serial = 0;             // scene_serial at that pass: the offsets describe the scene while it is the current one
     volym_surface surface_request = {};      // what that pass was asked (the emit pass walks it again)
     const uint8_t* surface_vol = nullptr;    // ... and the density it read (d_vol, or d_vol0 under UNCUT)
     bool surface_labels = false;             // ... and whether it read labels
     bool surface_total_known = false;        // surface_total is the pass's total (read back once)
     uint64_t surface_total = 0;
-    volym_surface_face* d_surface_faces = nullptr;   // the context's own face list, grown to the largest total asked for so far
-    size_t surface_faces_capacity = 0;
-    bool surface_faces_valid = false;        // a faces pass has written d_surface_faces since the latest surface pass
-    uint64_t surface_faces_count = 0;        // ... that many records
+    volym::OwnedBuffer<volym_surface_face> surface_faces;   // the context's own face list; count: the faces of the latest faces pass
+    bool surface_faces_valid = false;        // a faces pass has written it since the latest surface pass (a surface may have 0 faces)
 
     bool feedback = true;
     bool feedback_frozen = false;               // dev
@@ -265,7 +272,6 @@ struct volym_ctx {
 
 namespace volym {
 
-int ctx_fail(volym_ctx* c, int code, const std::string& msg);
 // one plain ray-march launch of slot 0 on its stream (what volym_compute_pass enqueues); used by the multi-GPU loop
 int ctx_launch_march(volym_ctx* c);
 
@@ -276,9 +282,8 @@ int quiesce_slots(volym_ctx* c);
 int rebuild_lists(volym_ctx* c);
 // raymarch.hip: the look-ahead's reject box of a frame from imp_box_*
 void set_reject_box(const volym_ctx* c, FrameParams& fp);
-// pick.hip: one pick march of rect {x0, y0, w, h} (inside the frame, not empty) into `out` (w * h records), enqueued on the slot's
-// stream with the slot's frame parameters, tables and -- when it is the one of the current threshold and scene -- distance field
-int launch_pick(volym_ctx* c, FrameSlot& s, const uint32_t rect[4], float alpha_min, void* out);
+// pick.hip: what the context keeps for the pick pass (every stream idle)
+void free_pick(volym_ctx* c);
 // outline.hip: what the context keeps for the outline pass (every stream idle)
 void free_outline(volym_ctx* c);
 // slice.hip: what the context keeps for the slice pass (every stream idle)
@@ -302,3 +307,79 @@ int build_fine_cells(volym_ctx* c);
         if (e_ != hipSuccess)                                                                            \
             return volym::ctx_fail(ctx, VOLYM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// ---- what the read-only passes (pick, outline, slice, projection, measure, surface) and the blit share on the host ----
+namespace volym {
+
+// `bytes` of device memory to host memory behind the work of `stream`, blocking: what every volym_read_* ends in
+inline int read_back(volym_ctx* c, hipStream_t stream, void* out, const void* src, size_t bytes)
+{
+    VOLYM_HIPCHK(c, hipSetDevice(c->device));
+    VOLYM_HIPCHK(c, hipMemcpyAsync(out, src, bytes, hipMemcpyDeviceToHost, stream));
+    VOLYM_HIPCHK(c, hipStreamSynchronize(stream));
+    return VOLYM_OK;
+}
+
+template <class T>
+int OwnedBuffer<T>::reserve(volym_ctx* c, hipStream_t stream, size_t need, const char* what)
+{
+    if (need <= capacity) return VOLYM_OK;
+    VOLYM_HIPCHK(c, hipStreamSynchronize(stream));
+    release();                               // (a failing hipFree follows a sticky error that the next call reports anyway)
+    const hipError_t e = hipMalloc(&ptr, need * sizeof(T));
+    if (e != hipSuccess) { ptr = nullptr; return ctx_fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e)); }
+    capacity = need;
+    return VOLYM_OK;
+}
+
+template <class T>
+int OwnedBuffer<T>::read(volym_ctx* c, hipStream_t stream, void* out, size_t n) const
+{
+    return read_back(c, stream, out, ptr, n * sizeof(T));
+}
+
+inline uint32_t pack_rgba(const uint8_t c[4])
+{
+    return static_cast<uint32_t>(c[0]) | static_cast<uint32_t>(c[1]) << 8 | static_cast<uint32_t>(c[2]) << 16 | static_cast<uint32_t>(c[3]) << 24;
+}
+
+// labels of the volume's dimensions are on the device (labels of any other dimensions count as absent)
+inline bool labels_fit(const volym_ctx* c) { return c->d_labels && c->lnx == c->nx && c->lny == c->ny && c->lnz == c->nz; }
+
+// r = rect, or the whole frame for NULL; a rect that is empty or reaches outside the frame is refused in the name of `who`
+inline int frame_rect(volym_ctx* c, const uint32_t rect[4], const char* who, uint32_t r[4])
+{
+    const uint32_t whole[4] = {0u, 0u, c->W, c->H};
+    for (int k = 0; k < 4; ++k) r[k] = rect ? rect[k] : whole[k];
+    if (r[2] == 0u || r[3] == 0u || r[0] >= c->W || r[1] >= c->H || r[2] > c->W - r[0] || r[3] > c->H - r[1])
+        return ctx_fail(c, VOLYM_E_INVALID, std::string(who) + ": the rect must be non-empty and inside the frame");
+    return VOLYM_OK;
+}
+
+// the 256 + 256 dwords that travel with a slice or projection launch: the request's palette and the context's transfer function
+inline void pack_palette_and_lut(const volym_ctx* c, const uint8_t palette[256][4], uint32_t out_palette[256], uint32_t out_lut[256])
+{
+    for (uint32_t l = 0; l < 256u; ++l) out_palette[l] = pack_rgba(palette[l]);
+    for (uint32_t l = 0; l < 256u; ++l) out_lut[l] = l < c->tf_n ? pack_rgba(c->lut + 4u * l) : 0u;
+}
+
+// The box of a request over the scene's bytes (measure, surface), {lo[3], hi[3]} in texels: the whole volume, and the check
+// lo <= hi <= dims on every axis.  No context: the volym_*_check calls run without a device.
+inline void whole_volume_box(const uint32_t dims[3], uint32_t box[6])
+{
+    for (int a = 0; a < 3; ++a) { box[a] = 0u; box[3 + a] = dims[a]; }
+}
+inline bool box_in_volume(const uint32_t box[6], const uint32_t dims[3])
+{
+    for (int a = 0; a < 3; ++a) if (box[a] > box[3 + a] || box[3 + a] > dims[a]) return false;
+    return true;
+}
+// ... and what such a pass refuses before it reads labels beside the density: the two uploaded under different layouts
+inline int check_labels_layout(volym_ctx* c, const char* who)
+{
+    if (labels_fit(c) && c->labels_bricked != c->bricked)
+        return ctx_fail(c, VOLYM_E_STATE, std::string(who) + ": volume and labels were uploaded under different VOLYM_OPT_VOLUME_LAYOUT settings");
+    return VOLYM_OK;
+}
+
+}  // namespace volym

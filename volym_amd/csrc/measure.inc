@@ -10,18 +10,14 @@ static_assert(sizeof(volym_segment_stats) == 80 && offsetof(volym_segment_stats,
               offsetof(volym_segment_stats, max) == 76, "volym_segment_stats has no padding");
 static_assert(sizeof(volym_measurement) == 36864 && offsetof(volym_measurement, hist) == 20480, "volym_measurement has no padding");
 
-void volym::free_measure(volym_ctx* c)
-{
-    (void)hipFree(c->d_measure); c->d_measure = nullptr;
-    c->measure_valid = false;
-}
+void volym::free_measure(volym_ctx* c) { c->measure.release(); }
 
 extern "C" {
 
 int volym_measure_check(const volym_measure* m, const uint32_t dims[3])
 {
     if (!m || !dims) return VOLYM_E_INVALID;
-    for (int a = 0; a < 3; ++a) if (m->box[a] > m->box[3 + a] || m->box[3 + a] > dims[a]) return VOLYM_E_INVALID;
+    if (!box_in_volume(m->box, dims)) return VOLYM_E_INVALID;
     if (m->flags & ~static_cast<uint32_t>(VOLYM_MEASURE_UNCUT)) return VOLYM_E_INVALID;
     for (int l = 0; l < 256; ++l) if (m->group[l] >= VOLYM_MEASURE_GROUPS && m->group[l] != VOLYM_MEASURE_NO_GROUP) return VOLYM_E_INVALID;
     return VOLYM_OK;
@@ -33,24 +29,22 @@ int volym_measure_pass(volym_ctx* c, const volym_measure* m)
     if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_measure_pass: no volume (volym_set_volume first)");
     const uint32_t dims[3] = {c->nx, c->ny, c->nz};
     volym_measure whole = {};                    // every label in group 0, no flags
-    for (int a = 0; a < 3; ++a) whole.box[3 + a] = dims[a];
+    whole_volume_box(dims, whole.box);
     if (!m) m = &whole;
     if (volym_measure_check(m, dims) != VOLYM_OK)
         return fail(c, VOLYM_E_INVALID, "volym_measure_pass: need lo <= hi <= volume size on every axis, known flags, and groups below 8 or VOLYM_MEASURE_NO_GROUP");
-    const bool labels_fit = c->d_labels && c->lnx == c->nx && c->lny == c->ny && c->lnz == c->nz;
-    if (labels_fit && c->labels_bricked != c->bricked)
-        return fail(c, VOLYM_E_STATE, "volym_measure_pass: volume and labels were uploaded under different VOLYM_OPT_VOLUME_LAYOUT settings");
+    const bool with_labels = labels_fit(c);
+    int rc = check_labels_layout(c, "volym_measure_pass");
+    if (rc != VOLYM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const hipStream_t stream = c->slot0().stream;       // where pick, slice and projection passes go: ordered with them and with itself
-    if (!c->d_measure) {
-        // (a set-up step, once: the one blocking path of a pass)
-        const hipError_t e = hipMalloc(&c->d_measure, sizeof(volym_measurement));
-        if (e != hipSuccess) { c->d_measure = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(measurement): ") + hipGetErrorString(e)); }
-    }
-    const MeasureOut out = {c->d_measure->seg, reinterpret_cast<unsigned long long*>(&c->d_measure->hist[0][0])};
+    // (a set-up step, once: the one blocking path of a pass)
+    rc = c->measure.reserve(c, stream, 1, "measurement");
+    if (rc != VOLYM_OK) return rc;
+    const MeasureOut out = {c->measure.ptr->seg, reinterpret_cast<unsigned long long*>(&c->measure.ptr->hist[0][0])};
     hipLaunchKernelGGL(volym_measure_init_kernel, dim3(1), dim3(256), 0, stream, out);
     HIPCHK(c, hipGetLastError());
-    c->measure_valid = true;
+    c->measure.count = 1;
 
     // the texels that can be in: the request's box, cut to the crop box unless UNCUT
     const bool uncut = (m->flags & VOLYM_MEASURE_UNCUT) != 0u;
@@ -67,7 +61,7 @@ int volym_measure_pass(volym_ctx* c, const volym_measure* m)
     // keep = inside the slab itself: a bricked chunk holds texels of the crop box beside the request's, which must not count
     for (int a = 0; a < 3; ++a) { s.box_lo[a] = box[a]; s.box_hi[a] = box[3 + a]; }
     if (uncut) { s.planes = 0u; s.pn[0] = s.pn[1] = s.pn[2] = s.pd = 0; }
-    const bool masked = !uncut && labels_fit && mask_active(c);
+    const bool masked = !uncut && with_labels && mask_active(c);
     LabelTable group, mask = {};
     std::memcpy(group.v, m->group, 256);
     for (int l = 0; l < 256; ++l) mask.v[l] = c->seg_hidden[l] ? 0u : 1u;
@@ -78,8 +72,8 @@ int volym_measure_pass(volym_ctx* c, const volym_measure* m)
     const uint64_t floor_grid = (items + 256ull * MEASURE_ITEMS_PER_LANE - 1u) / (256ull * MEASURE_ITEMS_PER_LANE);
     const dim3 grid(static_cast<uint32_t>(std::max<uint64_t>(stream_grid(c, (items + 7u) / 8u), floor_grid)));
     const uint4* vol = reinterpret_cast<const uint4*>(uncut && c->d_vol0 ? c->d_vol0 : c->d_vol);
-    const uint4* labels = labels_fit ? reinterpret_cast<const uint4*>(c->d_labels) : nullptr;
-    const auto kernel = labels_fit ? volym_measure_kernel<true> : volym_measure_kernel<false>;
+    const uint4* labels = with_labels ? reinterpret_cast<const uint4*>(c->d_labels) : nullptr;
+    const auto kernel = with_labels ? volym_measure_kernel<true> : volym_measure_kernel<false>;
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, vol, labels, out, group, mask, s, c->nx, c->ny, c->nz, c->bricked ? 1u : 0u, masked ? 1u : 0u,
                        static_cast<uint32_t>(items));
     HIPCHK(c, hipGetLastError());
@@ -90,14 +84,10 @@ int volym_read_measure(volym_ctx* c, struct volym_measurement* out)
 {
     if (!c) return VOLYM_E_INVALID;
     if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_measure: NULL output");
-    if (!c->d_measure || !c->measure_valid) return fail(c, VOLYM_E_STATE, "volym_read_measure: no volym_measure_pass since the volume was set");
-    const hipStream_t stream = c->slot0().stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_measure, sizeof(volym_measurement), hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    return VOLYM_OK;
+    if (c->measure.count == 0u) return fail(c, VOLYM_E_STATE, "volym_read_measure: no volym_measure_pass since the volume was set");
+    return c->measure.read(c, c->slot0().stream, out, 1);
 }
 
-void* volym_measure_device_ptr(volym_ctx* c) { return (c && c->measure_valid) ? c->d_measure : nullptr; }
+void* volym_measure_device_ptr(volym_ctx* c) { return (c && c->measure.count != 0u) ? c->measure.ptr : nullptr; }
 
 }  // extern "C"

@@ -15,36 +15,28 @@ static_assert(offsetof(volym_pick_record, label) == 10 && offsetof(volym_pick_re
 
 namespace volym {
 
-static uint32_t pack_rgba(const uint8_t c[4])
-{
-    return static_cast<uint32_t>(c[0]) | static_cast<uint32_t>(c[1]) << 8 | static_cast<uint32_t>(c[2]) << 16 | static_cast<uint32_t>(c[3]) << 24;
-}
-
 // first use (a set-up step, blocking): the bit plane with its guards zeroed, and the events that order the pass between frame slots
 static int ensure_outline_resources(volym_ctx* c)
 {
-    if (c->d_outline_plane) return VOLYM_OK;
+    if (c->outline_plane.ptr) return VOLYM_OK;
     const uint32_t stride = (c->W + 63u) / 64u + 2u;
-    const size_t bytes = static_cast<size_t>(stride) * (c->H + 2u * OUTLINE_GUARD_ROWS) * sizeof(uint64_t);
+    const size_t words = static_cast<size_t>(stride) * (c->H + 2u * OUTLINE_GUARD_ROWS);
     for (hipEvent_t& ev : c->outline_ev)
         if (!ev) VOLYM_HIPCHK(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    uint64_t* plane = nullptr;
-    hipError_t e = hipMalloc(&plane, bytes);
-    if (e != hipSuccess) return ctx_fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(outline plane): ") + hipGetErrorString(e));
+    const int rc = c->outline_plane.reserve(c, c->slot0().stream, words, "outline plane");
+    if (rc != VOLYM_OK) return rc;
     // on the stream the passes go on: a hipMemset on the null stream is not ordered with a non-blocking stream, and may return
     // before the device has zeroed the plane
-    e = hipMemsetAsync(plane, 0, bytes, c->slot0().stream);
-    if (e != hipSuccess) { (void)hipFree(plane); return ctx_fail(c, VOLYM_E_HIP, std::string("hipMemsetAsync(outline plane): ") + hipGetErrorString(e)); }
-    c->d_outline_plane = plane;
+    const hipError_t e = hipMemsetAsync(c->outline_plane.ptr, 0, words * sizeof(uint64_t), c->slot0().stream);
+    if (e != hipSuccess) { c->outline_plane.release(); return ctx_fail(c, VOLYM_E_HIP, std::string("hipMemsetAsync(outline plane): ") + hipGetErrorString(e)); }
     c->outline_stride = stride;
     return VOLYM_OK;
 }
 
 void free_outline(volym_ctx* c)
 {
-    (void)hipFree(c->d_outline_plane); c->d_outline_plane = nullptr;
-    (void)hipFree(c->d_outline); c->d_outline = nullptr;
-    c->outline_own_valid = false;
+    c->outline_plane.release();
+    c->outline.release();
     for (hipEvent_t& ev : c->outline_ev) { if (ev) (void)hipEventDestroy(ev); ev = nullptr; }
 }
 
@@ -61,11 +53,11 @@ int volym_outline_pass(volym_ctx* c, const volym_outline* o, const void* records
     if (o->radius < 1u || o->radius > OUTLINE_GUARD_ROWS) return ctx_fail(c, VOLYM_E_INVALID, "volym_outline_pass: radius must be 1..8");
     if ((records_device == nullptr) != (rect == nullptr))
         return ctx_fail(c, VOLYM_E_INVALID, "volym_outline_pass: records and rect go together (both NULL: those of the latest volym_pick_pass)");
-    if (rect && (rect[2] == 0u || rect[3] == 0u || rect[0] >= c->W || rect[1] >= c->H || rect[2] > c->W - rect[0] || rect[3] > c->H - rect[1]))
-        return ctx_fail(c, VOLYM_E_INVALID, "volym_outline_pass: the rect must be non-empty and inside the frame");
+    uint32_t r[4] = {c->pick_x0, c->pick_y0, c->pick_w, c->pick_h};      // (those of the latest pick pass, checked by it)
+    if (rect) { const int rc = frame_rect(c, rect, "volym_outline_pass", r); if (rc != VOLYM_OK) return rc; }
     if (c->world != 1u) return ctx_fail(c, VOLYM_E_STATE, "volym_outline_pass: not on a sharded context (its frame buffer holds a picture only on the root, after assembly)");
     if (!c->frame_rendered) return ctx_fail(c, VOLYM_E_STATE, "volym_outline_pass: no volym_compute_pass yet");
-    if (!records_device && (!c->d_picks || c->pick_w == 0u)) return ctx_fail(c, VOLYM_E_STATE, "volym_outline_pass: no volym_pick_pass yet");
+    if (!records_device && c->picks.count == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_outline_pass: no volym_pick_pass yet");
     VOLYM_HIPCHK(c, hipSetDevice(c->device));
     FrameSlot& s0 = c->slot0();                    // the pass runs where the pick passes run: ordered with them and with itself
     FrameSlot& sf = *c->slots[c->last];            // the slot of the frame it reads
@@ -73,25 +65,22 @@ int volym_outline_pass(volym_ctx* c, const volym_outline* o, const void* records
     if (rc != VOLYM_OK) return rc;
     uint32_t* dst = static_cast<uint32_t*>(target_rgba8);
     if (!dst) {
-        if (!c->d_outline) {
-            // our own target, allocated on first use (a set-up step: the one blocking path of the call)
-            hipError_t e = hipMalloc(&c->d_outline, static_cast<size_t>(c->W) * c->H * 4);
-            if (e != hipSuccess) { c->d_outline = nullptr; return ctx_fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(outline target): ") + hipGetErrorString(e)); }
-        }
-        dst = c->d_outline;
+        // our own target, allocated on first use (a set-up step: the one blocking path of the call)
+        rc = c->outline.reserve(c, s0.stream, static_cast<size_t>(c->W) * c->H, "outline target");
+        if (rc != VOLYM_OK) return rc;
+        dst = c->outline.ptr;
     }
 
     OutlineArgs a;
-    a.tails = static_cast<const uint2*>(records_device ? records_device : static_cast<const void*>(c->d_picks));
-    a.plane = c->d_outline_plane;
+    a.tails = static_cast<const uint2*>(records_device ? records_device : static_cast<const void*>(c->picks.ptr));
+    a.plane = c->outline_plane.ptr;
     a.src = c->frame_buf(sf);
     a.dst = dst;
     std::memset(a.sel, 0, sizeof a.sel);
     for (uint32_t l = 0; l < 256u; ++l)
         if (o->selected[l]) a.sel[l >> 6] |= 1ull << (l & 63u);
     a.W = c->W; a.H = c->H; a.stride = c->outline_stride;
-    if (rect) { a.x0 = rect[0]; a.y0 = rect[1]; a.w = rect[2]; a.h = rect[3]; }
-    else { a.x0 = c->pick_x0; a.y0 = c->pick_y0; a.w = c->pick_w; a.h = c->pick_h; }
+    a.x0 = r[0]; a.y0 = r[1]; a.w = r[2]; a.h = r[3];
     a.ring = pack_rgba(o->ring_rgba);
     a.fill = pack_rgba(o->fill_rgba);
 
@@ -114,7 +103,7 @@ int volym_outline_pass(volym_ctx* c, const volym_outline* o, const void* records
         VOLYM_HIPCHK(c, hipEventRecord(c->outline_ev[1], s0.stream));
         VOLYM_HIPCHK(c, hipStreamWaitEvent(other.stream, c->outline_ev[1], 0));
     }
-    if (!target_rgba8) c->outline_own_valid = true;
+    if (!target_rgba8) c->outline.count = static_cast<size_t>(c->W) * c->H;
     return VOLYM_OK;
 }
 
@@ -122,14 +111,10 @@ int volym_read_outline(volym_ctx* c, uint8_t* out)
 {
     if (!c) return VOLYM_E_INVALID;
     if (!out) return ctx_fail(c, VOLYM_E_INVALID, "volym_read_outline: NULL output");
-    if (!c->d_outline || !c->outline_own_valid) return ctx_fail(c, VOLYM_E_STATE, "volym_read_outline: no volym_outline_pass into the context's own target yet");
-    FrameSlot& s = c->slot0();
-    VOLYM_HIPCHK(c, hipSetDevice(c->device));
-    VOLYM_HIPCHK(c, hipMemcpyAsync(out, c->d_outline, static_cast<size_t>(c->W) * c->H * 4, hipMemcpyDeviceToHost, s.stream));
-    VOLYM_HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
+    if (c->outline.count == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_outline: no volym_outline_pass into the context's own target yet");
+    return c->outline.read(c, c->slot0().stream, out, c->outline.count);
 }
 
-void* volym_outline_device_ptr(volym_ctx* c) { return (c && c->outline_own_valid) ? c->d_outline : nullptr; }
+void* volym_outline_device_ptr(volym_ctx* c) { return (c && c->outline.count != 0u) ? c->outline.ptr : nullptr; }
 
 }  // extern "C"

@@ -24,31 +24,12 @@ static_assert(sizeof(volym::ProjectArgs) + sizeof(volym::FrameParams) < 4096, "p
 
 namespace volym {
 
-static uint32_t pack_rgba(const uint8_t c[4])
-{
-    return static_cast<uint32_t>(c[0]) | static_cast<uint32_t>(c[1]) << 8 | static_cast<uint32_t>(c[2]) << 16 | static_cast<uint32_t>(c[3]) << 24;
-}
-
 void free_projection(volym_ctx* c)
 {
-    (void)hipFree(c->d_projection); c->d_projection = nullptr;
-    (void)hipFree(c->d_projection_image); c->d_projection_image = nullptr;
-    (void)hipFree(c->d_projection_at); c->d_projection_at = nullptr;
-    c->projection_capacity = c->projection_image_capacity = 0;
+    c->projection.release();
+    c->projection_image.release();
+    c->projection_at.release();
     c->projection_w = c->projection_h = c->projection_image_w = c->projection_image_h = 0;
-}
-
-// grow one of the context's own buffers to `need` elements of `elem` bytes (a set-up step: the one blocking path of a pass)
-template <class T>
-static int grow(volym_ctx* c, FrameSlot& s0, T*& buf, size_t& capacity, uint32_t& w, uint32_t& h, size_t need, const char* what)
-{
-    if (need <= capacity) return VOLYM_OK;
-    VOLYM_HIPCHK(c, hipStreamSynchronize(s0.stream));      // earlier passes ran on this stream
-    (void)hipFree(buf); buf = nullptr; capacity = 0; w = h = 0;
-    hipError_t e = hipMalloc(&buf, need * sizeof(T));
-    if (e != hipSuccess) { buf = nullptr; return ctx_fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e)); }
-    capacity = need;
-    return VOLYM_OK;
 }
 
 // one validated launch; own_image: the image goes to the context's own target
@@ -59,13 +40,12 @@ static int project_pass(volym_ctx* c, const volym_project* p, const uint32_t rec
     if (!p) return ctx_fail(c, VOLYM_E_INVALID, name + ": NULL volym_project");
     if (volym_project_check(p) != VOLYM_OK)
         return ctx_fail(c, VOLYM_E_INVALID, name + ": a step outside [1e-4, 1], an unknown mode or flag, or LABELS with MEAN");
-    const uint32_t whole[4] = {0u, 0u, c->W, c->H};
-    const uint32_t* r = rect ? rect : whole;
-    if (r[2] == 0u || r[3] == 0u || r[0] >= c->W || r[1] >= c->H || r[2] > c->W - r[0] || r[3] > c->H - r[1])
-        return ctx_fail(c, VOLYM_E_INVALID, name + ": the rect must be non-empty and inside the frame");
+    uint32_t r[4];
+    int rc = frame_rect(c, rect, who, r);
+    if (rc != VOLYM_OK) return rc;
     if (!c->have_vol) return ctx_fail(c, VOLYM_E_STATE, name + ": no volume (volym_set_volume)");
-    const bool labels_fit = c->d_labels && c->lnx == c->nx && c->lny == c->ny && c->lnz == c->nz;
-    if ((p->flags & VOLYM_PROJECT_LABELS) && !labels_fit)
+    const bool with_labels = labels_fit(c);
+    if ((p->flags & VOLYM_PROJECT_LABELS) && !with_labels)
         return ctx_fail(c, VOLYM_E_STATE, name + ": VOLYM_PROJECT_LABELS needs labels of the volume's dimensions on the device (volym_set_labels)");
     if ((p->flags & VOLYM_PROJECT_TF) && !c->have_tf)
         return ctx_fail(c, VOLYM_E_STATE, name + ": VOLYM_PROJECT_TF needs a transfer function (volym_set_transfer_function)");
@@ -75,21 +55,16 @@ static int project_pass(volym_ctx* c, const volym_project* p, const uint32_t rec
         return ctx_fail(c, VOLYM_E_STATE, name + ": the volume changed since the last volym_update");
     VOLYM_HIPCHK(c, hipSetDevice(c->device));
     const size_t need = static_cast<size_t>(r[2]) * r[3];
-    if (!records_device) {
-        const int rc = grow(c, s0, c->d_projection, c->projection_capacity, c->projection_w, c->projection_h, need, "projection records");
-        if (rc != VOLYM_OK) return rc;
-    }
-    if (own_image) {
-        const int rc = grow(c, s0, c->d_projection_image, c->projection_image_capacity, c->projection_image_w, c->projection_image_h, need, "projection image");
-        if (rc != VOLYM_OK) return rc;
-    }
+    // grown on demand (a set-up step: the one blocking path of a pass)
+    if (!records_device && (rc = c->projection.reserve(c, s0.stream, need, "projection records")) != VOLYM_OK) return rc;
+    if (own_image && (rc = c->projection_image.reserve(c, s0.stream, need, "projection image")) != VOLYM_OK) return rc;
 
     ProjectArgs a;
     a.vol = c->d_vol;
-    a.labels = labels_fit ? c->d_labels : nullptr;
+    a.labels = with_labels ? c->d_labels : nullptr;
     a.mc = c->d_mc;
-    a.out = static_cast<uint4*>(records_device ? records_device : static_cast<void*>(c->d_projection));
-    a.image = own_image ? c->d_projection_image : static_cast<uint32_t*>(image_rgba8);
+    a.out = static_cast<uint4*>(records_device ? records_device : static_cast<void*>(c->projection.ptr));
+    a.image = own_image ? c->projection_image.ptr : static_cast<uint32_t*>(image_rgba8);
     a.x0 = r[0]; a.y0 = r[1]; a.w = r[2]; a.h = r[3];
     a.tiles_x = (a.w + 15u) / 16u;
     a.mc_n = c->mc_n;
@@ -98,16 +73,14 @@ static int project_pass(volym_ctx* c, const volym_project* p, const uint32_t rec
     a.tf_n = c->tf_n;
     a.background = pack_rgba(p->background);
     a.step = p->step;
-    for (uint32_t l = 0; l < 256u; ++l) a.palette[l] = pack_rgba(p->palette[l]);
-    std::memset(a.lut, 0, sizeof a.lut);
-    for (uint32_t l = 0; l < c->tf_n && l < 256u; ++l) a.lut[l] = pack_rgba(c->lut + 4u * l);
+    pack_palette_and_lut(c, p->palette, a.palette, a.lut);
 
     const uint32_t grid = a.tiles_x * ((a.h + 15u) / 16u);
     if (c->bricked) hipLaunchKernelGGL((volym_project_kernel<true>), dim3(grid), dim3(256), 0, s0.stream, a, s0.fp);
     else hipLaunchKernelGGL((volym_project_kernel<false>), dim3(grid), dim3(256), 0, s0.stream, a, s0.fp);
     VOLYM_HIPCHK(c, hipGetLastError());
-    if (!records_device) { c->projection_w = r[2]; c->projection_h = r[3]; }
-    if (own_image) { c->projection_image_w = r[2]; c->projection_image_h = r[3]; }
+    if (!records_device) { c->projection_w = r[2]; c->projection_h = r[3]; c->projection.count = need; }
+    if (own_image) { c->projection_image_w = r[2]; c->projection_image_h = r[3]; c->projection_image.count = need; }
     return VOLYM_OK;
 }
 
@@ -160,34 +133,26 @@ int volym_read_projection(volym_ctx* c, struct volym_projection* out)
 {
     if (!c) return VOLYM_E_INVALID;
     if (!out) return ctx_fail(c, VOLYM_E_INVALID, "volym_read_projection: NULL output");
-    if (!c->d_projection || c->projection_w == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_projection: no projection pass into the context's own records yet");
-    FrameSlot& s = c->slot0();
-    VOLYM_HIPCHK(c, hipSetDevice(c->device));
-    VOLYM_HIPCHK(c, hipMemcpyAsync(out, c->d_projection, static_cast<size_t>(c->projection_w) * c->projection_h * sizeof(volym_projection), hipMemcpyDeviceToHost, s.stream));
-    VOLYM_HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
+    if (c->projection.count == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_projection: no projection pass into the context's own records yet");
+    return c->projection.read(c, c->slot0().stream, out, c->projection.count);
 }
 
 int volym_read_projection_image(volym_ctx* c, uint8_t* out)
 {
     if (!c) return VOLYM_E_INVALID;
     if (!out) return ctx_fail(c, VOLYM_E_INVALID, "volym_read_projection_image: NULL output");
-    if (!c->d_projection_image || c->projection_image_w == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_projection_image: no volym_project_image_pass yet");
-    FrameSlot& s = c->slot0();
-    VOLYM_HIPCHK(c, hipSetDevice(c->device));
-    VOLYM_HIPCHK(c, hipMemcpyAsync(out, c->d_projection_image, static_cast<size_t>(c->projection_image_w) * c->projection_image_h * 4u, hipMemcpyDeviceToHost, s.stream));
-    VOLYM_HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
+    if (c->projection_image.count == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_projection_image: no volym_project_image_pass yet");
+    return c->projection_image.read(c, c->slot0().stream, out, c->projection_image.count);
 }
 
-void* volym_projection_device_ptr(volym_ctx* c) { return (c && c->projection_w != 0u) ? c->d_projection : nullptr; }
-void* volym_projection_image_device_ptr(volym_ctx* c) { return (c && c->projection_image_w != 0u) ? c->d_projection_image : nullptr; }
+void* volym_projection_device_ptr(volym_ctx* c) { return (c && c->projection.count != 0u) ? c->projection.ptr : nullptr; }
+void* volym_projection_image_device_ptr(volym_ctx* c) { return (c && c->projection_image.count != 0u) ? c->projection_image.ptr : nullptr; }
 
 int volym_projection_size(volym_ctx* c, uint32_t size[2])
 {
     if (!c) return VOLYM_E_INVALID;
     if (!size) return ctx_fail(c, VOLYM_E_INVALID, "volym_projection_size: NULL output");
-    size[0] = c->d_projection ? c->projection_w : 0u; size[1] = c->d_projection ? c->projection_h : 0u;
+    size[0] = c->projection.count ? c->projection_w : 0u; size[1] = c->projection.count ? c->projection_h : 0u;
     return VOLYM_OK;
 }
 
@@ -195,7 +160,7 @@ int volym_projection_image_size(volym_ctx* c, uint32_t size[2])
 {
     if (!c) return VOLYM_E_INVALID;
     if (!size) return ctx_fail(c, VOLYM_E_INVALID, "volym_projection_image_size: NULL output");
-    size[0] = c->d_projection_image ? c->projection_image_w : 0u; size[1] = c->d_projection_image ? c->projection_image_h : 0u;
+    size[0] = c->projection_image.count ? c->projection_image_w : 0u; size[1] = c->projection_image.count ? c->projection_image_h : 0u;
     return VOLYM_OK;
 }
 
@@ -204,21 +169,16 @@ int volym_project_at(volym_ctx* c, uint32_t x, uint32_t y, float step, struct vo
     if (!c) return VOLYM_E_INVALID;
     if (!out) return ctx_fail(c, VOLYM_E_INVALID, "volym_project_at: NULL output");
     VOLYM_HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_projection_at) {
-        // a record of its own (a set-up step, once): the context's own records keep what the latest pass put there
-        hipError_t e = hipMalloc(&c->d_projection_at, sizeof(volym_projection));
-        if (e != hipSuccess) { c->d_projection_at = nullptr; return ctx_fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(projection record): ") + hipGetErrorString(e)); }
-    }
+    // a record of its own (a set-up step, once): the context's own records keep what the latest pass put there
+    int rc = c->projection_at.reserve(c, c->slot0().stream, 1, "projection record");
+    if (rc != VOLYM_OK) return rc;
     volym_project p;
     std::memset(&p, 0, sizeof p);
     p.step = step;
     const uint32_t rect[4] = {x, y, 1u, 1u};
-    const int rc = project_pass(c, &p, rect, c->d_projection_at, nullptr, false, "volym_project_at");
+    rc = project_pass(c, &p, rect, c->projection_at.ptr, nullptr, false, "volym_project_at");
     if (rc != VOLYM_OK) return rc;
-    FrameSlot& s = c->slot0();
-    VOLYM_HIPCHK(c, hipMemcpyAsync(out, c->d_projection_at, sizeof(volym_projection), hipMemcpyDeviceToHost, s.stream));
-    VOLYM_HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
+    return c->projection_at.read(c, c->slot0().stream, out, 1);
 }
 
 }  // extern "C"

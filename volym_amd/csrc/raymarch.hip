@@ -1,5 +1,6 @@
 // libvolym_hip.so: context, frame loop and their C ABI (include/volym_hip.h) over the gfx950 kernels.  The bytes of the scene
-// (volume, labels, importances, crop box, segment visibility, macro cells) and their C ABI are scene_bytes.hip.
+// (volume, labels, importances, crop box, segment visibility, macro cells) and their C ABI are scene_bytes.hip; the read-only
+// passes over frame and scene (pick, outline, slice, projection, surface) are units of their own, each with its C ABI.
 // Replaces the reference's gpu_context.rs / gpu_resources/* / demos/pipeline.rs for the
 // ray-march path; citations are file:line under /root/reference/.
 //
@@ -520,8 +521,8 @@ static void free_slot(FrameSlot& s)
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.copy_stream) (void)hipStreamSynchronize(s.copy_stream);
     (void)hipFree(s.d_tables); (void)hipFree(s.d_df);
-    (void)hipFree(s.d_shard_own); (void)hipFree(s.d_frame_own); (void)hipFree(s.d_f32); (void)hipFree(s.d_blit);
-    (void)hipFree(s.d_gather_tmp); (void)hipFree(s.d_pack_counters); (void)hipFree(s.d_counters); (void)hipFree(s.d_aabb); (void)hipFree(s.d_tile_mask);
+    (void)hipFree(s.d_shard_own); (void)hipFree(s.d_frame_own); (void)hipFree(s.d_f32); s.blit.release();
+    s.gather_tmp.release(); (void)hipFree(s.d_pack_counters); (void)hipFree(s.d_counters); (void)hipFree(s.d_aabb); (void)hipFree(s.d_tile_mask);
     (void)hipFree(s.d_tile_depth);
     (void)hipFree(s.d_list[0]); (void)hipFree(s.d_list[1]); (void)hipFree(s.d_cost);
     (void)hipFree(s.d_pool_sync); (void)hipFree(s.d_pool_dbg);
@@ -594,7 +595,7 @@ void volym_destroy(volym_ctx* c)
     // (every slot's stream is idle now: nothing reads the scene any more)
     (void)hipFree(c->d_vol); (void)hipFree(c->d_imp); (void)hipFree(c->d_labels); (void)hipFree(c->d_mc); (void)hipFree(c->d_mc_fine);
     (void)hipFree(c->d_vol0); (void)hipFree(c->d_imp0);
-    (void)hipFree(c->d_picks);
+    free_pick(c);
     free_outline(c);
     free_slice(c);
     free_projection(c);
@@ -1285,16 +1286,12 @@ int volym_blit(volym_ctx* c, void* target_rgba8, uint32_t out_w, uint32_t out_h)
     uint32_t* dst = static_cast<uint32_t*>(target_rgba8);
     if (!dst) {
         // our own target: sized on first use / on a size change (a set-up step: this is the one blocking path of the call)
-        const size_t need = static_cast<size_t>(out_w) * out_h * 4;
-        if (need > s.blit_bytes) {
-            HIPCHK(c, hipStreamSynchronize(s.stream));
-            if (s.d_blit) { HIPCHK(c, hipFree(s.d_blit)); s.d_blit = nullptr; s.blit_bytes = 0; }
-            hipError_t e = hipMalloc(&s.d_blit, need);
-            if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(blit target): ") + hipGetErrorString(e));
-            s.blit_bytes = need;
-        }
-        dst = s.d_blit;
+        const size_t need = static_cast<size_t>(out_w) * out_h;
+        const int rc = s.blit.reserve(c, s.stream, need, "blit target");
+        if (rc != VOLYM_OK) return rc;
+        dst = s.blit.ptr;
         s.blit_w = out_w; s.blit_h = out_h;
+        s.blit.count = need;
     }
     hipLaunchKernelGGL(volym_blit_kernel, dim3((out_w + 63u) / 64u, (out_h + 3u) / 4u), dim3(64, 4), 0, s.stream, c->frame_buf(s), c->W, c->H, dst, out_w, out_h);
     HIPCHK(c, hipGetLastError());
@@ -1305,11 +1302,8 @@ int volym_read_blit(volym_ctx* c, uint8_t* out)
 {
     if (!c || !out) return VOLYM_E_INVALID;
     FrameSlot& s = *c->slots[c->last_blit];
-    if (!s.d_blit || s.blit_w == 0) return fail(c, VOLYM_E_STATE, "volym_read_blit: no volym_blit into the context's own target yet");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, s.d_blit, static_cast<size_t>(s.blit_w) * s.blit_h * 4, hipMemcpyDeviceToHost, s.stream));
-    HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
+    if (s.blit.count == 0u) return fail(c, VOLYM_E_STATE, "volym_read_blit: no volym_blit into the context's own target yet");
+    return s.blit.read(c, s.stream, out, s.blit.count);
 }
 
 uint32_t volym_local_tiles(const volym_ctx* c) { return c ? c->n_local : 0u; }
@@ -1411,70 +1405,11 @@ int volym_assemble_host(volym_ctx* c, const uint8_t* gathered_host)
     FrameSlot& s = c->slot0();
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = volym_shard_bytes(c) * c->world;
-    if (s.gather_tmp_bytes < bytes) {
-        HIPCHK(c, hipStreamSynchronize(s.stream));
-        if (s.d_gather_tmp) { HIPCHK(c, hipFree(s.d_gather_tmp)); s.d_gather_tmp = nullptr; s.gather_tmp_bytes = 0; }
-        hipError_t e = hipMalloc(&s.d_gather_tmp, bytes);
-        if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(gather): ") + hipGetErrorString(e));
-        s.gather_tmp_bytes = bytes;
-    }
-    HIPCHK(c, hipMemcpyAsync(s.d_gather_tmp, gathered_host, bytes, hipMemcpyHostToDevice, s.stream));
-    HIPCHK(c, hipStreamSynchronize(s.stream));
-    return volym_assemble(c, s.d_gather_tmp);
-}
-
-// ---- pick: segment, texel and depth under a pixel (the march itself: pick.hip) -----------------------------------------
-int volym_pick_pass(volym_ctx* c, const uint32_t rect[4], float alpha_min)
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!(alpha_min >= 0.0f && alpha_min <= 0.95f)) return fail(c, VOLYM_E_INVALID, "volym_pick_pass: alpha_min must be in [0, 0.95]");
-    const uint32_t whole[4] = {0u, 0u, c->W, c->H};
-    const uint32_t* r = rect ? rect : whole;
-    if (r[2] == 0u || r[3] == 0u || r[0] >= c->W || r[1] >= c->H || r[2] > c->W - r[0] || r[3] > c->H - r[1])
-        return fail(c, VOLYM_E_INVALID, "volym_pick_pass: the rect must be non-empty and inside the frame");
-    if (!c->have_vol || !c->have_imp || !c->have_tf) return fail(c, VOLYM_E_STATE, "volym_pick_pass: set volume, importances and transfer function first");
-    if (!c->have_frame) return fail(c, VOLYM_E_STATE, "volym_pick_pass: call volym_update first");
-    FrameSlot& s = c->slot0();
-    if (s.fp.nx != c->nx || s.fp.ny != c->ny || s.fp.nz != c->nz || c->inx != c->nx || c->iny != c->ny || c->inz != c->nz)
-        return fail(c, VOLYM_E_STATE, "volym_pick_pass: the volume changed since the last volym_update");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t need = static_cast<size_t>(r[2]) * r[3];
-    if (need > c->pick_capacity) {
-        // grown on demand (a set-up step: the one blocking path of the call); earlier passes ran on this stream
-        HIPCHK(c, hipStreamSynchronize(s.stream));
-        if (c->d_picks) { HIPCHK(c, hipFree(c->d_picks)); c->d_picks = nullptr; c->pick_capacity = 0; c->pick_w = c->pick_h = 0; }
-        hipError_t e = hipMalloc(&c->d_picks, need * sizeof(volym_pick_record));
-        if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(pick records): ") + hipGetErrorString(e));
-        c->pick_capacity = need;
-    }
-    const int rc = launch_pick(c, s, r, alpha_min, c->d_picks);
+    const int rc = s.gather_tmp.reserve(c, s.stream, bytes, "gather");
     if (rc != VOLYM_OK) return rc;
-    c->pick_x0 = r[0]; c->pick_y0 = r[1];
-    c->pick_w = r[2]; c->pick_h = r[3];
-    return VOLYM_OK;
-}
-
-int volym_read_picks(volym_ctx* c, volym_pick_record* out)
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_picks: NULL output");
-    if (!c->d_picks || c->pick_w == 0u) return fail(c, VOLYM_E_STATE, "volym_read_picks: no volym_pick_pass yet");
-    FrameSlot& s = c->slot0();
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_picks, static_cast<size_t>(c->pick_w) * c->pick_h * sizeof(volym_pick_record), hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipMemcpyAsync(s.gather_tmp.ptr, gathered_host, bytes, hipMemcpyHostToDevice, s.stream));
     HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
-}
-
-void* volym_pick_device_ptr(volym_ctx* c) { return (c && c->pick_w != 0u) ? c->d_picks : nullptr; }
-
-int volym_pick(volym_ctx* c, uint32_t x, uint32_t y, float alpha_min, volym_pick_record* out)
-{
-    if (!c) return VOLYM_E_INVALID;
-    if (!out) return fail(c, VOLYM_E_INVALID, "volym_pick: NULL output");
-    const uint32_t rect[4] = {x, y, 1u, 1u};
-    const int rc = volym_pick_pass(c, rect, alpha_min);
-    return rc != VOLYM_OK ? rc : volym_read_picks(c, out);
+    return volym_assemble(c, s.gather_tmp.ptr);
 }
 
 int volym_stats_pass(volym_ctx* c, volym_stats* out)

@@ -849,7 +849,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     // (d_imp is uncropped now, and the copies are made again by the next cut: a context that does not cut holds none)
     if (c->d_vol0) { HIPCHK(c, hipFree(c->d_vol0)); c->d_vol0 = nullptr; }
     if (c->d_imp0) { HIPCHK(c, hipFree(c->d_imp0)); c->d_imp0 = nullptr; }
-    c->measure_valid = false;               // (a result describes the volume it was measured in)
+    c->measure.count = 0;                   // (a result describes the volume it was measured in)
     free_surface(c);                        // (and so do a surface's summary, row offsets and faces, which are sized by it)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }

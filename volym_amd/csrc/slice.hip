@@ -17,11 +17,6 @@ static_assert(VOLYM_SLICE_LABELS == static_cast<int>(volym::SLICE_LABELS) && VOL
 
 namespace volym {
 
-static uint32_t pack_rgba(const uint8_t c[4])
-{
-    return static_cast<uint32_t>(c[0]) | static_cast<uint32_t>(c[1]) << 8 | static_cast<uint32_t>(c[2]) << 16 | static_cast<uint32_t>(c[3]) << 24;
-}
-
 // position of pixel (i, j) on axis a, over the integers
 static int64_t slice_pos(const volym_slice* s, int a, uint32_t i, uint32_t j)
 {
@@ -30,8 +25,7 @@ static int64_t slice_pos(const volym_slice* s, int a, uint32_t i, uint32_t j)
 
 void free_slice(volym_ctx* c)
 {
-    (void)hipFree(c->d_slice); c->d_slice = nullptr;
-    c->slice_capacity = 0;
+    c->slice.release();
     c->slice_w = c->slice_h = 0;
 }
 
@@ -90,8 +84,8 @@ int volym_slice_pass(volym_ctx* c, const volym_slice* sl, void* target_rgba8)
     if (volym_slice_check(sl) != VOLYM_OK)
         return ctx_fail(c, VOLYM_E_INVALID, "volym_slice_pass: unknown mode or flag, IMPORTANCE with UNCUT, a size outside 1..8192 or a corner outside [-2^30, 2^30)");
     if (!c->have_vol) return ctx_fail(c, VOLYM_E_STATE, "volym_slice_pass: no volume (volym_set_volume)");
-    const bool labels_fit = c->d_labels && c->lnx == c->nx && c->lny == c->ny && c->lnz == c->nz;
-    if ((sl->flags & VOLYM_SLICE_LABELS) && !labels_fit)
+    const bool with_labels = labels_fit(c);
+    if ((sl->flags & VOLYM_SLICE_LABELS) && !with_labels)
         return ctx_fail(c, VOLYM_E_STATE, "volym_slice_pass: VOLYM_SLICE_LABELS needs labels of the volume's dimensions on the device (volym_set_labels)");
     if (sl->mode == static_cast<uint32_t>(VOLYM_SLICE_IMPORTANCE) && !(c->have_imp && c->d_imp && c->inx == c->nx && c->iny == c->ny && c->inz == c->nz))
         return ctx_fail(c, VOLYM_E_STATE, "volym_slice_pass: VOLYM_SLICE_IMPORTANCE needs importances of the volume's dimensions");
@@ -101,22 +95,16 @@ int volym_slice_pass(volym_ctx* c, const volym_slice* sl, void* target_rgba8)
     FrameSlot& s0 = c->slot0();                    // where the pick passes go: ordered with them and with itself
     uint32_t* dst = static_cast<uint32_t*>(target_rgba8);
     if (!dst) {
-        const size_t need = static_cast<size_t>(sl->width) * sl->height;
-        if (need > c->slice_capacity) {
-            // grown on demand (a set-up step: the one blocking path of the call); earlier passes ran on this stream
-            VOLYM_HIPCHK(c, hipStreamSynchronize(s0.stream));
-            free_slice(c);
-            hipError_t e = hipMalloc(&c->d_slice, need * 4u);
-            if (e != hipSuccess) { c->d_slice = nullptr; return ctx_fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(slice target): ") + hipGetErrorString(e)); }
-            c->slice_capacity = need;
-        }
-        dst = c->d_slice;
+        // grown on demand (a set-up step: the one blocking path of the call)
+        const int rc = c->slice.reserve(c, s0.stream, static_cast<size_t>(sl->width) * sl->height, "slice target");
+        if (rc != VOLYM_OK) return rc;
+        dst = c->slice.ptr;
     }
 
     SliceArgs a;
     a.vol = ((sl->flags & VOLYM_SLICE_UNCUT) && c->d_vol0) ? c->d_vol0 : c->d_vol;
     a.imp = c->d_imp;
-    a.labels = labels_fit ? c->d_labels : nullptr;
+    a.labels = with_labels ? c->d_labels : nullptr;
     a.out = dst;
     for (int k = 0; k < 3; ++k) {
         a.origin[k] = static_cast<uint32_t>(sl->origin[k]); a.du[k] = static_cast<uint32_t>(sl->du[k]); a.dv[k] = static_cast<uint32_t>(sl->dv[k]);
@@ -134,18 +122,16 @@ int volym_slice_pass(volym_ctx* c, const volym_slice* sl, void* target_rgba8)
     a.background = pack_rgba(sl->background);
     a.cut = pack_rgba(sl->cut_rgba);
     std::memset(a.hidden, 0, sizeof a.hidden);
-    if (labels_fit)
+    if (with_labels)
         for (uint32_t l = 0; l < 256u; ++l)
             if (c->seg_hidden[l]) a.hidden[l >> 5] |= 1u << (l & 31u);
-    for (uint32_t l = 0; l < 256u; ++l) a.palette[l] = pack_rgba(sl->palette[l]);
-    std::memset(a.lut, 0, sizeof a.lut);
-    for (uint32_t l = 0; l < c->tf_n && l < 256u; ++l) a.lut[l] = pack_rgba(c->lut + 4u * l);
+    pack_palette_and_lut(c, sl->palette, a.palette, a.lut);
 
     const uint32_t grid = a.tiles_x * ((sl->height + 15u) / 16u);        // <= 512 * 512
     if (c->bricked) hipLaunchKernelGGL((volym_slice_kernel<true>), dim3(grid), dim3(256), 0, s0.stream, a);
     else hipLaunchKernelGGL((volym_slice_kernel<false>), dim3(grid), dim3(256), 0, s0.stream, a);
     VOLYM_HIPCHK(c, hipGetLastError());
-    if (!target_rgba8) { c->slice_w = sl->width; c->slice_h = sl->height; }
+    if (!target_rgba8) { c->slice_w = sl->width; c->slice_h = sl->height; c->slice.count = static_cast<size_t>(sl->width) * sl->height; }
     return VOLYM_OK;
 }
 
@@ -153,14 +139,10 @@ int volym_read_slice(volym_ctx* c, uint8_t* out)
 {
     if (!c) return VOLYM_E_INVALID;
     if (!out) return ctx_fail(c, VOLYM_E_INVALID, "volym_read_slice: NULL output");
-    if (!c->d_slice || c->slice_w == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_slice: no volym_slice_pass into the context's own target yet");
-    FrameSlot& s = c->slot0();
-    VOLYM_HIPCHK(c, hipSetDevice(c->device));
-    VOLYM_HIPCHK(c, hipMemcpyAsync(out, c->d_slice, static_cast<size_t>(c->slice_w) * c->slice_h * 4u, hipMemcpyDeviceToHost, s.stream));
-    VOLYM_HIPCHK(c, hipStreamSynchronize(s.stream));
-    return VOLYM_OK;
+    if (c->slice.count == 0u) return ctx_fail(c, VOLYM_E_STATE, "volym_read_slice: no volym_slice_pass into the context's own target yet");
+    return c->slice.read(c, c->slot0().stream, out, c->slice.count);
 }
 
-void* volym_slice_device_ptr(volym_ctx* c) { return (c && c->slice_w != 0u) ? c->d_slice : nullptr; }
+void* volym_slice_device_ptr(volym_ctx* c) { return (c && c->slice.count != 0u) ? c->slice.ptr : nullptr; }
 
 }  // extern "C"

@@ -25,12 +25,11 @@ static_assert(sizeof(volym_surface_face) == 8 && offsetof(volym_surface_face, di
 
 void volym::free_surface(volym_ctx* c)
 {
-    (void)hipFree(c->d_surface); c->d_surface = nullptr;
-    (void)hipFree(c->d_surface_rows); c->d_surface_rows = nullptr;
-    (void)hipFree(c->d_surface_sums); c->d_surface_sums = nullptr;
-    (void)hipFree(c->d_surface_faces); c->d_surface_faces = nullptr;
-    c->surface_rows_capacity = c->surface_faces_capacity = 0;
-    c->surface_valid = c->surface_faces_valid = c->surface_total_known = false;
+    c->surface.release();
+    c->surface_rows.release();
+    c->surface_sums.release();
+    c->surface_faces.release();
+    c->surface_faces_valid = c->surface_total_known = false;
 }
 
 // the arguments of the walk for request s (checked, box not empty)
@@ -65,7 +64,7 @@ extern "C" {
 int volym_surface_check(const volym_surface* s, const uint32_t dims[3])
 {
     if (!s || !dims) return VOLYM_E_INVALID;
-    for (int a = 0; a < 3; ++a) if (s->box[a] > s->box[3 + a] || s->box[3 + a] > dims[a]) return VOLYM_E_INVALID;
+    if (!box_in_volume(s->box, dims)) return VOLYM_E_INVALID;
     if (s->flags & ~static_cast<uint32_t>(VOLYM_SURFACE_UNCUT)) return VOLYM_E_INVALID;
     if (s->min_byte == 0u || s->min_byte > 255u) return VOLYM_E_INVALID;
     return VOLYM_OK;
@@ -77,70 +76,63 @@ int volym_surface_pass(volym_ctx* c, const volym_surface* s)
     if (!c->have_vol) return fail(c, VOLYM_E_STATE, "volym_surface_pass: no volume (volym_set_volume first)");
     const uint32_t dims[3] = {c->nx, c->ny, c->nz};
     volym_surface whole = {};                    // the whole volume, min_byte 1, every label selected, no flags
-    for (int a = 0; a < 3; ++a) whole.box[3 + a] = dims[a];
+    whole_volume_box(dims, whole.box);
     whole.min_byte = 1u;
     std::memset(whole.select, 1, sizeof whole.select);
     if (!s) s = &whole;
     if (volym_surface_check(s, dims) != VOLYM_OK)
         return fail(c, VOLYM_E_INVALID, "volym_surface_pass: need lo <= hi <= volume size on every axis, known flags and min_byte in 1..255");
-    const bool labels_fit = c->d_labels && c->lnx == c->nx && c->lny == c->ny && c->lnz == c->nz;
-    if (labels_fit && c->labels_bricked != c->bricked)
-        return fail(c, VOLYM_E_STATE, "volym_surface_pass: volume and labels were uploaded under different VOLYM_OPT_VOLUME_LAYOUT settings");
+    const bool with_labels = labels_fit(c);
+    int rc = check_labels_layout(c, "volym_surface_pass");
+    if (rc != VOLYM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const hipStream_t stream = c->slot0().stream;       // where pick, slice, projection and measure passes go
     const bool empty = empty_box(*s);
     const uint32_t n_rows = empty ? 0u : (s->box[4] - s->box[1]) * (s->box[5] - s->box[2]);
-    if (!c->d_surface) {
-        // (a set-up step, once: with the growth below the one blocking path of a pass)
-        const hipError_t e = hipMalloc(&c->d_surface, sizeof(volym_surface_summary));
-        if (e != hipSuccess) { c->d_surface = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(surface summary): ") + hipGetErrorString(e)); }
-    }
-    if (n_rows > c->surface_rows_capacity) {
-        // an earlier pass may still be reading the arrays this replaces
-        HIPCHK(c, hipStreamSynchronize(stream));
-        (void)hipFree(c->d_surface_rows); c->d_surface_rows = nullptr;
-        (void)hipFree(c->d_surface_sums); c->d_surface_sums = nullptr;
-        c->surface_rows_capacity = 0;
-        c->surface_valid = false;
+    // (a set-up step, once: with the growth below the one blocking path of a pass)
+    rc = c->surface.reserve(c, stream, 1, "surface summary");
+    if (rc != VOLYM_OK) return rc;
+    if (n_rows > c->surface_rows.capacity) {
+        // the offsets and the block sums of their scan are replaced together, and the summary they belong to is void from here on;
+        // should either allocation fail neither is kept
+        c->surface.count = 0;
         const size_t n_sums = (static_cast<size_t>(n_rows) + VOLYM_SURFACE_SCAN_ROWS - 1u) / VOLYM_SURFACE_SCAN_ROWS;
-        hipError_t e = hipMalloc(&c->d_surface_rows, static_cast<size_t>(n_rows) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&c->d_surface_sums, n_sums * sizeof(uint32_t));
-        if (e != hipSuccess) {
-            (void)hipFree(c->d_surface_rows); c->d_surface_rows = nullptr; c->d_surface_sums = nullptr;
-            return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(surface row offsets): ") + hipGetErrorString(e));
-        }
-        c->surface_rows_capacity = n_rows;
+        rc = c->surface_rows.reserve(c, stream, n_rows, "surface row offsets");
+        if (rc == VOLYM_OK) { c->surface_sums.release(); rc = c->surface_sums.reserve(c, stream, n_sums, "surface row offsets"); }
+        if (rc != VOLYM_OK) { c->surface_rows.release(); c->surface_sums.release(); return rc; }
     }
-    hipLaunchKernelGGL(volym_surface_init_kernel, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(c->d_surface),
+    hipLaunchKernelGGL(volym_surface_init_kernel, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(c->surface.ptr),
                        static_cast<uint32_t>(sizeof(volym_surface_summary) / 8u));
     HIPCHK(c, hipGetLastError());
     const bool uncut = (s->flags & VOLYM_SURFACE_UNCUT) != 0u;
-    c->surface_valid = true;
+    c->surface.count = 1;
     c->surface_serial = c->scene_serial;
     c->surface_request = *s;
     c->surface_vol = uncut && c->d_vol0 ? c->d_vol0 : c->d_vol;
-    c->surface_labels = labels_fit;
+    c->surface_labels = with_labels;
     c->surface_total_known = empty;                     // (an empty box has no faces: nothing to learn)
     c->surface_total = 0;
     c->surface_faces_valid = false;
     if (empty) return VOLYM_OK;                         // a zero summary, no rows: nothing else is launched
 
-    const SurfaceArgs a = walk_args(c, *s, c->surface_vol, labels_fit);
+    const SurfaceArgs a = walk_args(c, *s, c->surface_vol, with_labels);
     SurfaceSelect select;
     std::memcpy(select.v, s->select, 256);
-    volym_surface_summary* d = c->d_surface;
+    volym_surface_summary* d = c->surface.ptr;
     const SurfaceOut out = {reinterpret_cast<unsigned long long*>(&d->faces[0][0]), reinterpret_cast<unsigned long long*>(&d->total),
                             reinterpret_cast<unsigned long long*>(&d->pos[0][0]), reinterpret_cast<unsigned long long*>(&d->neg[0][0])};
-    const auto count = labels_fit ? volym_surface_count_kernel<true> : volym_surface_count_kernel<false>;
-    hipLaunchKernelGGL(count, dim3(walk_grid(c, n_rows)), dim3(256), 0, stream, a, select, out, c->d_surface_rows);
+    const auto count = with_labels ? volym_surface_count_kernel<true> : volym_surface_count_kernel<false>;
+    uint32_t* const rows = c->surface_rows.ptr;
+    uint32_t* const sums = c->surface_sums.ptr;
+    hipLaunchKernelGGL(count, dim3(walk_grid(c, n_rows)), dim3(256), 0, stream, a, select, out, rows);
     HIPCHK(c, hipGetLastError());
     // the scan: counts -> offsets, in place (a grid of one workgroup runs the same three phases)
     const uint32_t n_blocks = (n_rows + VOLYM_SURFACE_SCAN_ROWS - 1u) / VOLYM_SURFACE_SCAN_ROWS;
-    hipLaunchKernelGGL(volym_surface_scan_sums_kernel, dim3(n_blocks), dim3(256), 0, stream, c->d_surface_rows, c->d_surface_sums, n_rows);
+    hipLaunchKernelGGL(volym_surface_scan_sums_kernel, dim3(n_blocks), dim3(256), 0, stream, rows, sums, n_rows);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(volym_surface_scan_blocks_kernel, dim3(1), dim3(256), 0, stream, c->d_surface_sums, n_blocks);
+    hipLaunchKernelGGL(volym_surface_scan_blocks_kernel, dim3(1), dim3(256), 0, stream, sums, n_blocks);
     HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(volym_surface_scan_rows_kernel, dim3(n_blocks), dim3(256), 0, stream, c->d_surface_rows, c->d_surface_sums, n_rows);
+    hipLaunchKernelGGL(volym_surface_scan_rows_kernel, dim3(n_blocks), dim3(256), 0, stream, rows, sums, n_rows);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
 }
@@ -149,22 +141,20 @@ int volym_read_surface(volym_ctx* c, struct volym_surface_summary* out)
 {
     if (!c) return VOLYM_E_INVALID;
     if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_surface: NULL output");
-    if (!c->d_surface || !c->surface_valid) return fail(c, VOLYM_E_STATE, "volym_read_surface: no volym_surface_pass since the volume was set");
-    const hipStream_t stream = c->slot0().stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_surface, sizeof(volym_surface_summary), hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
+    if (c->surface.count == 0u) return fail(c, VOLYM_E_STATE, "volym_read_surface: no volym_surface_pass since the volume was set");
+    const int rc = c->surface.read(c, c->slot0().stream, out, 1);
+    if (rc != VOLYM_OK) return rc;
     c->surface_total = out->total;
     c->surface_total_known = true;
     return VOLYM_OK;
 }
 
-void* volym_surface_device_ptr(volym_ctx* c) { return (c && c->surface_valid) ? c->d_surface : nullptr; }
+void* volym_surface_device_ptr(volym_ctx* c) { return (c && c->surface.count != 0u) ? c->surface.ptr : nullptr; }
 
 int volym_surface_faces_pass(volym_ctx* c, void* target_device, uint64_t capacity_faces)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (!c->have_vol || !c->d_surface || !c->surface_valid)
+    if (!c->have_vol || c->surface.count == 0u)
         return fail(c, VOLYM_E_STATE, "volym_surface_faces_pass: no volym_surface_pass since the volume was set");
     if (c->surface_serial != c->scene_serial)
         return fail(c, VOLYM_E_STATE, "volym_surface_faces_pass: the scene's bytes changed since the surface pass (run volym_surface_pass again)");
@@ -172,8 +162,8 @@ int volym_surface_faces_pass(volym_ctx* c, void* target_device, uint64_t capacit
     const hipStream_t stream = c->slot0().stream;
     if (!c->surface_total_known) {
         uint64_t total = 0;
-        HIPCHK(c, hipMemcpyAsync(&total, &c->d_surface->total, sizeof total, hipMemcpyDeviceToHost, stream));
-        HIPCHK(c, hipStreamSynchronize(stream));
+        const int rc = read_back(c, stream, &total, &c->surface.ptr->total, sizeof total);
+        if (rc != VOLYM_OK) return rc;
         c->surface_total = total;
         c->surface_total_known = true;
     }
@@ -184,18 +174,12 @@ int volym_surface_faces_pass(volym_ctx* c, void* target_device, uint64_t capacit
         if (capacity_faces < total) return fail(c, VOLYM_E_INVALID, "volym_surface_faces_pass: the target holds fewer faces than the surface has (volym_read_surface: total)");
         if (reinterpret_cast<uintptr_t>(target_device) & 7u) return fail(c, VOLYM_E_INVALID, "volym_surface_faces_pass: the target must be 8-byte aligned");
     } else {
-        if (total > c->surface_faces_capacity) {
-            HIPCHK(c, hipStreamSynchronize(stream));     // an earlier faces pass may still be writing the buffer this replaces
-            (void)hipFree(c->d_surface_faces); c->d_surface_faces = nullptr;
-            c->surface_faces_capacity = 0;
-            c->surface_faces_valid = false;
-            const hipError_t e = hipMalloc(&c->d_surface_faces, static_cast<size_t>(total) * sizeof(volym_surface_face));
-            if (e != hipSuccess) { c->d_surface_faces = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(surface faces): ") + hipGetErrorString(e)); }
-            c->surface_faces_capacity = static_cast<size_t>(total);
-        }
-        target = reinterpret_cast<uint2*>(c->d_surface_faces);
+        c->surface_faces_valid = false;
+        const int rc = c->surface_faces.reserve(c, stream, static_cast<size_t>(total), "surface faces");
+        if (rc != VOLYM_OK) return rc;
+        target = reinterpret_cast<uint2*>(c->surface_faces.ptr);
         c->surface_faces_valid = true;
-        c->surface_faces_count = total;
+        c->surface_faces.count = static_cast<size_t>(total);
     }
     if (total == 0u) return VOLYM_OK;                    // (an empty box has no rows either)
     const volym_surface& s = c->surface_request;
@@ -203,7 +187,7 @@ int volym_surface_faces_pass(volym_ctx* c, void* target_device, uint64_t capacit
     SurfaceSelect select;
     std::memcpy(select.v, s.select, 256);
     const auto emit = c->surface_labels ? volym_surface_emit_kernel<true> : volym_surface_emit_kernel<false>;
-    hipLaunchKernelGGL(emit, dim3(walk_grid(c, a.n_rows)), dim3(256), 0, stream, a, select, c->d_surface_rows, target);
+    hipLaunchKernelGGL(emit, dim3(walk_grid(c, a.n_rows)), dim3(256), 0, stream, a, select, c->surface_rows.ptr, target);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
 }
@@ -211,17 +195,13 @@ int volym_surface_faces_pass(volym_ctx* c, void* target_device, uint64_t capacit
 int volym_read_surface_faces(volym_ctx* c, struct volym_surface_face* out, uint64_t capacity_faces)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (!c->surface_valid || !c->surface_faces_valid)
+    if (c->surface.count == 0u || !c->surface_faces_valid)
         return fail(c, VOLYM_E_STATE, "volym_read_surface_faces: no volym_surface_faces_pass into the context's own buffer since the latest surface pass");
-    const uint64_t n = c->surface_faces_count;
+    const size_t n = c->surface_faces.count;
     if (capacity_faces < n) return fail(c, VOLYM_E_INVALID, "volym_read_surface_faces: the output holds fewer faces than the pass wrote");
     if (n == 0u) return VOLYM_OK;
     if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_surface_faces: NULL output");
-    const hipStream_t stream = c->slot0().stream;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_surface_faces, static_cast<size_t>(n) * sizeof(volym_surface_face), hipMemcpyDeviceToHost, stream));
-    HIPCHK(c, hipStreamSynchronize(stream));
-    return VOLYM_OK;
+    return c->surface_faces.read(c, c->slot0().stream, out, n);
 }
 
 }  // extern "C"

@@ -398,6 +398,16 @@ def outline_frame(frame, picks, rect, selected, ring_rgba, fill_rgba=(0, 0, 0, 0
     return out
 
 
+def _replaced(obj, noun, names, kw):
+    """A copy of request `obj` (a `noun` whose constructor takes `names`) with the fields of kw changed."""
+    fields = {k: getattr(obj, k) for k in names}
+    for k in kw:
+        if k not in fields:
+            raise TypeError("a %s has no field %r" % (noun, k))
+    fields.update(kw)
+    return type(obj)(**fields)
+
+
 SLICE_MAX = 8192                   # largest width and height of a slice
 SLICE_LIMIT = 1 << 30              # every corner position of a slice lies in [-2^30, 2^30), 16.16
 _SLICE_AXES = {"x": 0, "y": 1, "z": 2, 0: 0, 1: 1, 2: 2}
@@ -417,12 +427,7 @@ class Slice:
 
     def replace(self, **kw):
         """A copy with the given fields changed."""
-        fields = {k: getattr(self, k) for k in ("origin", "du", "dv", "width", "height", "mode", "flags", "background", "cut_rgba", "palette")}
-        for k in kw:
-            if k not in fields:
-                raise TypeError("a slice has no field %r" % k)
-        fields.update(kw)
-        return Slice(**fields)
+        return _replaced(self, "slice", ("origin", "du", "dv", "width", "height", "mode", "flags", "background", "cut_rgba", "palette"), kw)
 
     def to_c(self):
         """The _lib.Slice of this slice.  Fields that do not fit their C types raise ValueError."""
@@ -620,12 +625,7 @@ class Measure:
 
     def replace(self, **kw):
         """A copy with the given fields changed."""
-        fields = {k: getattr(self, k) for k in ("box", "flags", "group")}
-        for k in kw:
-            if k not in fields:
-                raise TypeError("a measure has no field %r" % k)
-        fields.update(kw)
-        return Measure(**fields)
+        return _replaced(self, "measure", ("box", "flags", "group"), kw)
 
     def to_c(self):
         """The _lib.Measure of this request.  Fields that do not fit their C types raise ValueError."""
@@ -788,12 +788,7 @@ class Surface:
 
     def replace(self, **kw):
         """A copy with the given fields changed."""
-        fields = {k: getattr(self, k) for k in ("box", "flags", "min_byte", "select")}
-        for k in kw:
-            if k not in fields:
-                raise TypeError("a surface has no field %r" % k)
-        fields.update(kw)
-        return Surface(**fields)
+        return _replaced(self, "surface", ("box", "flags", "min_byte", "select"), kw)
 
     def to_c(self):
         """The _lib.Surface of this request.  Fields that do not fit their C types raise ValueError."""
@@ -974,12 +969,7 @@ class Projection:
 
     def replace(self, **kw):
         """A copy with the given fields changed."""
-        fields = {k: getattr(self, k) for k in ("step", "mode", "flags", "background", "palette")}
-        for k in kw:
-            if k not in fields:
-                raise TypeError("a projection has no field %r" % k)
-        fields.update(kw)
-        return Projection(**fields)
+        return _replaced(self, "projection", ("step", "mode", "flags", "background", "palette"), kw)
 
     def to_c(self):
         """The _lib.Project of this projection.  Fields that do not fit their C types raise ValueError."""
