@@ -24,7 +24,9 @@
  *     Blocking calls: volym_create / volym_destroy, volym_set_* (uploads; they also wait for the frames in flight),
  *     volym_set_option, volym_set_shard, volym_set_stream, volym_sync, volym_settle, volym_read_*, volym_packed_tiles,
  *     volym_assemble_host, volym_stats_pass, volym_time_*; volym_blit blocks only when it has to (re)size its own target, and
- *     volym_surface_faces_pass when it has to learn the face total of its surface pass or grow the context's own face buffer.
+ *     volym_surface_faces_pass when it has to learn the face total of its surface pass or grow the context's own face buffer;
+ *     volym_components_pass blocks only when it has to allocate or grow its buffers; volym_read_components,
+ *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name).
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -777,6 +779,88 @@ int   volym_read_surface_faces(volym_ctx* ctx, struct volym_surface_face* out, u
 /* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
  * bit, min_byte outside 1..255.  An empty box is valid: a zero summary and no faces.  Pure host arithmetic. */
 int   volym_surface_check(const volym_surface* s, const uint32_t dims[3]);
+
+/* --- connected components (new; the reference has none) ------------------------------------------------------------------ */
+/* Is a segment one piece?  The 6-connected components of the solid texels of a request: how many there are, one record per
+ * component and one id per texel of the request's box.  A read-only pass over the bytes of the scene as they stand: it writes no
+ * label and no scene byte.
+ *   The rule (integers only; scene.components_volume of the Python package is its host twin, equal in every byte).  box, flags,
+ * min_byte and select are volym_surface's, and SOLID is the surface pass's predicate: the texel lies in the request's box, its
+ * density byte is >= min_byte and select[label] != 0; UNCUT reads the uncut copy as it does there; the label is 0 everywhere while
+ * the context holds no labels of the volume's dimensions; the cuts are in the bytes for free.  Two solid texels are LINKED iff they
+ * differ by 1 on exactly one axis (the adjacency of the surface pass's faces) and, with SPLIT_LABELS, their label bytes are equal.
+ * A COMPONENT is a class of the transitive closure of "linked"; links never cross the request's box.
+ *   Canonical numbering: a component's ROOT is its first texel in ascending (z, y, x); components are numbered 0, 1, 2, ... in
+ * ascending order of their roots.  The same request on the same scene gives the same bytes in either device layout, every time.
+ *   The id volume: one uint32_t per texel of the box, box-linear with x fastest, (x - x0) + w * ((y - y0) + h * (z - z0)) -- never
+ * the device layout: the component's number, or VOLYM_COMPONENT_NONE for a texel that is not solid.  It lives in a buffer the context
+ * owns, which grows to the largest box asked for so far (4 bytes per texel: 4 GiB for 1024^3); a box of more than 2^31 - 2 texels is
+ * refused.  The table: record k describes component k, for k < max_components; components numbered from max_components on keep
+ * their ids in the id volume and are counted in the summary, but have no record, and nothing is written past that capacity. */
+enum { VOLYM_COMPONENTS_UNCUT = 1, VOLYM_COMPONENTS_SPLIT_LABELS = 2 };                        /* flags */
+#define VOLYM_COMPONENTS_DEFAULT_MAX 65536u         /* max_components == 0 */
+#define VOLYM_COMPONENTS_TABLE_MAX (1u << 24)       /* largest max_components */
+#define VOLYM_COMPONENTS_BOX_MAX 0x7ffffffeu        /* 2^31 - 2: most texels of a request's box */
+#define VOLYM_COMPONENT_NONE 0xffffffffu            /* id of a texel that is not solid */
+typedef struct volym_components {
+    uint32_t box[6];            /* {x0, y0, z0, x1, y1, z1}: lo inclusive, hi exclusive, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint32_t min_byte;          /* 1..255 */
+    uint8_t  select[256];       /* label value -> != 0: its texels can be solid */
+    uint32_t max_components;    /* table records to keep; 0: VOLYM_COMPONENTS_DEFAULT_MAX; at most VOLYM_COMPONENTS_TABLE_MAX */
+} volym_components;             /* 292 bytes */
+struct volym_components_summary {
+    uint64_t n_components;
+    uint64_t n_solid;
+    uint64_t recorded;          /* min(n_components, max_components): the records of the table */
+    uint64_t per_label[256];    /* the components whose root has that label */
+};                              /* 2072 bytes */
+struct volym_component {
+    uint16_t x, y, z;           /* the root texel, the coordinates volym_set_crop_box takes */
+    uint8_t  label;             /* the root's label byte; 0 without labels of the volume's dimensions on the device */
+    uint8_t  flags;             /* bit 0: some texel lies on a face of the request's box: the piece may continue outside */
+    uint32_t count;             /* texels (at most 2^31 - 2) */
+    uint16_t box[6];            /* {x0, y0, z0, x1, y1, z1} of its texels, hi INCLUSIVE (as volym_label_counts' boxes) */
+};                              /* 24 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_components) == 292, "volym_components is 292 bytes");
+static_assert(sizeof(struct volym_components_summary) == 2072, "volym_components_summary is 2072 bytes");
+static_assert(sizeof(struct volym_component) == 24, "volym_component is 24 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_components) == 292, "volym_components is 292 bytes");
+_Static_assert(sizeof(struct volym_components_summary) == 2072, "volym_components_summary is 2072 bytes");
+_Static_assert(sizeof(struct volym_component) == 24, "volym_component is 24 bytes");
+#endif
+/* Enqueue only, on the first slot's stream, where pick, measure and surface passes go: the kernel that zeroes the summary, the row
+ * runs, the merge (a lock-free union-find over the texels of the box, in the id volume itself), the flatten, the numbering with its
+ * scan, the relabel that accumulates the records, and their packing.  c == NULL: the whole volume, min_byte 1, every label, no
+ * flags, the default capacity.  The one blocking path is the first allocation, or a growth, of its buffers.  It needs a volume, but
+ * no volym_update, no frame and no transfer function; it ignores the shard, writes no frame buffer and needs no events with
+ * VOLYM_OPT_FRAMES_IN_FLIGHT = 2: a frame enqueued before or after it is byte for byte the frame without it.  An empty box launches
+ * only the zeroing kernel.  The results are a snapshot: the reads below stay valid after later edits of the scene.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_components_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions
+ * held in the other device layout than the volume (as volym_surface_pass). */
+int   volym_components_pass(volym_ctx* ctx, const volym_components* c);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis or of more than
+ * VOLYM_COMPONENTS_BOX_MAX texels, an unknown flag bit, min_byte outside 1..255, max_components above VOLYM_COMPONENTS_TABLE_MAX.
+ * An empty box is valid: a zero summary, no records, no ids.  Pure host arithmetic. */
+int   volym_components_check(const volym_components* c, const uint32_t dims[3]);
+/* The reads block.  All: VOLYM_E_STATE before any pass, and after volym_set_volume until the next one; VOLYM_E_INVALID for a NULL
+ * ctx or output.
+ *   volym_read_components: the summary of the latest pass.
+ *   volym_read_component_table: its `recorded` records; VOLYM_E_INVALID for a capacity below that.
+ *   volym_read_component_ids: the ids of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi, inside the pass's box; NULL:
+ * the pass's whole box), box-linear in the sub-box; VOLYM_E_INVALID for a sub-box that reaches outside the pass's box.
+ *   volym_component_of: the id of one texel (4 bytes are copied); VOLYM_E_INVALID for a texel outside the pass's box. */
+int   volym_read_components(volym_ctx* ctx, struct volym_components_summary* out);
+int   volym_read_component_table(volym_ctx* ctx, struct volym_component* out, uint64_t capacity);
+int   volym_read_component_ids(volym_ctx* ctx, const uint32_t sub[6], uint32_t* out);
+int   volym_component_of(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, uint32_t* id);
+/* The context's own results in device memory after a pass (NULL before any, and after volym_set_volume): the summary (a struct
+ * volym_components_summary), the id volume of the latest pass's box, the table (struct volym_component records). */
+void* volym_components_device_ptr(volym_ctx* ctx);
+void* volym_component_ids_device_ptr(volym_ctx* ctx);
+void* volym_component_table_device_ptr(volym_ctx* ctx);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

@@ -19,7 +19,8 @@ orthogonal slices through the texel pixel (X, Y) shows.  --project MAX|MEAN[,STE
 intensity along the rays of the same view, STEP apart (default: a quarter of the march step) -- as <screenshot>_project_<mode>.png
 (demo.Simple.project).  --surface [NAME,...][:MIN_BYTE] prints the surface table of the scene in view -- faces per axis, area, enclosed
 texels beside the measured count and sphericity per segment (demo.Simple.surface) -- and --surface-out FILE.stl|.obj writes the mesh of
-those segments together (demo.Simple.export_surface).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
+those segments together (demo.Simple.export_surface).  --components [NAME,...][:MIN_BYTE] prints, per segment in view, its connected
+pieces -- how many, the largest, and the ten largest with root and box (demo.Simple.components).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
 """
@@ -226,13 +227,13 @@ def _measure_table(rows):
     return "\n".join(lines)
 
 
-def _surface_arg(text):
+def _surface_arg(text, option="--surface"):
     """NAME[,NAME...][:MIN_BYTE] -> (names or label values, None for every segment in view; min_byte)"""
     names, _, m = text.rpartition(":") if ":" in text else (text, "", "")
     try:
         min_byte = int(m) if m else 1
     except ValueError:
-        raise SystemExit("--surface: NAME[,NAME...][:MIN_BYTE], MIN_BYTE an integer in 1..255")
+        raise SystemExit("%s: NAME[,NAME...][:MIN_BYTE], MIN_BYTE an integer in 1..255" % option)
     return [int(v) if v.isdigit() else v for v in names.split(",") if v] or None, min_byte
 
 
@@ -242,6 +243,19 @@ def _surface_table(rows):
     for name, s in rows.items():
         lines.append("%-16s %5d %10d %10d %10d %12.1f %12d %12d %10.3f" % ((name, s["label"]) + tuple(s["pairs"]) + (s["area"], s["enclosed"], s["measured"], s["sphericity"])))
     return "\n".join(lines)
+
+
+def _components_table(rows):
+    """what --components prints: per segment of demo.Simple.components' dict its pieces and largest piece, then its ten largest pieces"""
+    lines = []
+    for name, s in rows.items():
+        big = s["largest"]
+        lines.append("%-16s label %3d: %d piece%s in %d solid texels, largest %d texels (%.1f%%), %d smaller than 8 texels" % (
+            name, s["label"], s["pieces"], "" if s["pieces"] == 1 else "s", s["solid"], big["count"] if big else 0, 100.0 * (s["share"] or 0.0), s["small"]["pieces"]))
+        for p in s["top"]:
+            lines.append("  piece %-8d %10d texels  root (%d,%d,%d)  box [%d,%d,%d]..[%d,%d,%d]%s" % (
+                (p["number"], p["count"]) + p["root"] + p["box"][0] + p["box"][1] + (" open" if p["open"] else "",)))
+    return "\n".join(lines) if lines else "components: no solid texel"
 
 
 def run_simple(args):
@@ -315,9 +329,18 @@ def run_simple(args):
                     d.export_surface(ctx, args.surface_out, names, min_byte)
             except ValueError as e:
                 raise SystemExit("--surface: %s" % e)
+        pieces = None
+        if getattr(args, "components", None) is not None:
+            names, min_byte = _surface_arg(args.components, "--components")
+            try:
+                pieces = d.components(ctx, names, min_byte)
+            except ValueError as e:
+                raise SystemExit("--components: %s" % e)
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    if pieces is not None:
+        print(_components_table(pieces))
     if surfaced is not None:
         print(_surface_table(surfaced))
         if args.surface_out:
@@ -455,6 +478,8 @@ def main(argv=None):
     run.add_argument("--surface", nargs="?", const="", metavar="NAME,...[:MIN_BYTE]",
                      help="also print the surface table of the scene in view (all segments, or the named ones; texels with a density byte of at "
                           "least MIN_BYTE, default 1, are solid): faces per axis, area, enclosed texels beside the measured count, sphericity")
+    run.add_argument("--components", nargs="?", const="", metavar="NAME,...[:MIN_BYTE]",
+                     help="also print, per segment (all in view, or the named ones), its connected pieces: how many, the largest, and the ten largest with root and box")
     run.add_argument("--surface-out", metavar="FILE.stl|.obj", help="also write the surface of those segments together as a binary STL or an OBJ mesh")
     run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")

@@ -201,6 +201,40 @@ SURFACE_SUMMARY_DTYPE = np.dtype([("faces", "<u8", (256, 6)), ("total", "<u8"), 
 SURFACE_FACE_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("dir", "u1"), ("label", "u1")])
 
 
+COMPONENTS_UNCUT, COMPONENTS_SPLIT_LABELS = 1, 2               # volym_components.flags
+COMPONENTS_DEFAULT_MAX = 65536                                 # max_components == 0
+COMPONENTS_TABLE_MAX = 1 << 24                                 # largest max_components
+COMPONENTS_BOX_MAX = 2 ** 31 - 2                               # most texels of a request's box
+COMPONENT_NONE = 0xFFFFFFFF                                    # id of a texel that is not solid
+
+
+class Components(C.Structure):
+    """volym_components (include/volym_hip.h): box, flags, min_byte, select table and table capacity of one components pass, 292 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("select", C.c_uint8 * 256),
+        ("max_components", C.c_uint32),
+    ]
+
+
+class ComponentsSummary(C.Structure):
+    """volym_components_summary (include/volym_hip.h): components, solid texels, records kept and components per root label, 2072 bytes"""
+    _fields_ = [("n_components", C.c_uint64), ("n_solid", C.c_uint64), ("recorded", C.c_uint64), ("per_label", C.c_uint64 * 256)]
+
+
+class Component(C.Structure):
+    """volym_component (include/volym_hip.h): the record of one component, 24 bytes"""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("z", C.c_uint16), ("label", C.c_uint8), ("flags", C.c_uint8), ("count", C.c_uint32),
+                ("box", C.c_uint16 * 6)]
+
+
+# the summary and the record as NumPy structured dtypes (GpuContext.read_components / read_component_table, scene.components_volume)
+COMPONENTS_SUMMARY_DTYPE = np.dtype([("n_components", "<u8"), ("n_solid", "<u8"), ("recorded", "<u8"), ("per_label", "<u8", (256,))])
+COMPONENT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("label", "u1"), ("flags", "u1"), ("count", "<u4"), ("box", "<u2", (6,))])
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -348,6 +382,15 @@ SIGNATURES = {
     "volym_surface_faces_pass": (C.c_int, [_ctx, C.c_void_p, C.c_uint64]),
     "volym_read_surface_faces": (C.c_int, [_ctx, C.POINTER(SurfaceFace), C.c_uint64]),
     "volym_surface_check": (C.c_int, [C.POINTER(Surface), C.POINTER(C.c_uint32)]),
+    "volym_components_pass": (C.c_int, [_ctx, C.POINTER(Components)]),
+    "volym_components_check": (C.c_int, [C.POINTER(Components), C.POINTER(C.c_uint32)]),
+    "volym_read_components": (C.c_int, [_ctx, C.POINTER(ComponentsSummary)]),
+    "volym_read_component_table": (C.c_int, [_ctx, C.POINTER(Component), C.c_uint64]),
+    "volym_read_component_ids": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_component_of": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "volym_components_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_component_ids_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_component_table_device_ptr": (C.c_void_p, [_ctx]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI, and the measure pass over them; pick.hip: the pick pass and its C ABI; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI, and the measure pass over them; pick.hip: the pick pass and its C ABI; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI; components.hip: the components pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -238,6 +238,15 @@ struct volym_ctx {
     volym::OwnedBuffer<volym_surface_face> surface_faces;   // the context's own face list; count: the faces of the latest faces pass
     bool surface_faces_valid = false;        // a faces pass has written it since the latest surface pass (a surface may have 0 faces)
 
+    // components passes (volym_components_pass, components.hip): a snapshot, valid until the next volym_set_volume
+    volym::OwnedBuffer<volym_components_summary> components;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> component_ids;      // the id volume of the request's box, box-linear; the union-find forest while the pass runs
+    volym::OwnedBuffer<volym_component> component_table;   // the records: min(max_components, texels of the box) of them at most
+    volym::OwnedBuffer<uint32_t> component_work;     // the working table the records accumulate in (components_kernels.h), sized with the table
+    volym::OwnedBuffer<uint32_t> component_rows;     // per row of the request's box: its roots, scanned in place into the number of its first root
+    volym::OwnedBuffer<uint32_t> component_sums;     // the scan's block sums; replaced whenever component_rows is
+    uint32_t component_box[6] = {};          // the box of the latest pass (the reads address the id volume by it)
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -294,6 +303,8 @@ void free_projection(volym_ctx* c);
 void free_measure(volym_ctx* c);
 // surface.hip: what the context keeps for the surface passes (every stream idle)
 void free_surface(volym_ctx* c);
+// components.hip: what the context keeps for the components pass (every stream idle)
+void free_components(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume
@@ -308,7 +319,7 @@ int build_fine_cells(volym_ctx* c);
             return volym::ctx_fail(ctx, VOLYM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// ---- what the read-only passes (pick, outline, slice, projection, measure, surface) and the blit share on the host ----
+// ---- what the read-only passes (pick, outline, slice, projection, measure, surface, components) and the blit share on the host ----
 namespace volym {
 
 // `bytes` of device memory to host memory behind the work of `stream`, blocking: what every volym_read_* ends in
@@ -363,7 +374,7 @@ inline void pack_palette_and_lut(const volym_ctx* c, const uint8_t palette[256][
     for (uint32_t l = 0; l < 256u; ++l) out_lut[l] = l < c->tf_n ? pack_rgba(c->lut + 4u * l) : 0u;
 }
 
-// The box of a request over the scene's bytes (measure, surface), {lo[3], hi[3]} in texels: the whole volume, and the check
+// The box of a request over the scene's bytes (measure, surface, components), {lo[3], hi[3]} in texels: the whole volume, and the check
 // lo <= hi <= dims on every axis.  No context: the volym_*_check calls run without a device.
 inline void whole_volume_box(const uint32_t dims[3], uint32_t box[6])
 {

@@ -538,6 +538,49 @@ public:
         }
         return out;
     }
+    // New: connected components (volym_components_pass) -- is a segment one piece?  Per segment its pieces, its solid texels and the
+    // ten largest recorded pieces, largest first (of equals the lowest number); `number` is the piece's id in the id volume.
+    struct Piece {
+        uint32_t number;
+        struct volym_component record;
+    };
+    struct Pieces {
+        uint8_t label;
+        std::string segment;
+        uint64_t pieces, solid, recorded, small;        // small: recorded pieces of fewer than 8 texels
+        std::vector<Piece> top;
+    };
+    // One components pass per segment, each selected alone as surface selects them, over the scene as it stands (uncut: as it was
+    // uploaded).  `segments` as measure takes them.  Segments without a solid texel are left out.
+    std::vector<Pieces> components(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {}, uint32_t min_byte = 1u,
+                                   bool uncut = false)
+    {
+        std::vector<Pieces> out;
+        std::vector<struct volym_components_summary> r(1);
+        for (const Measured& m : measure(ctx, a, segments, nullptr, uncut, nullptr)) {
+            volym_components q{};
+            q.box[3] = a.nx; q.box[4] = a.ny; q.box[5] = a.nz;
+            q.flags = uncut ? VOLYM_COMPONENTS_UNCUT : 0u;
+            q.min_byte = min_byte;
+            q.select[m.label] = 1;
+            ctx.check(volym_components_pass(ctx.handle(), &q));
+            ctx.check(volym_read_components(ctx.handle(), r.data()));
+            if (r[0].n_solid == 0u) continue;
+            std::vector<struct volym_component> table(static_cast<size_t>(r[0].recorded));
+            ctx.check(volym_read_component_table(ctx.handle(), table.data(), table.size()));
+            Pieces p{};
+            p.label = m.label; p.segment = m.segment;
+            p.pieces = r[0].n_components; p.solid = r[0].n_solid; p.recorded = r[0].recorded;
+            std::vector<uint32_t> order(table.size());
+            for (size_t k = 0; k < order.size(); ++k) { order[k] = static_cast<uint32_t>(k); if (table[k].count < 8u) ++p.small; }
+            const size_t n_top = std::min<size_t>(10, order.size());
+            std::partial_sort(order.begin(), order.begin() + n_top, order.end(),
+                              [&](uint32_t i, uint32_t j) { return table[i].count != table[j].count ? table[i].count > table[j].count : i < j; });
+            for (size_t k = 0; k < n_top; ++k) p.top.push_back(Piece{order[k], table[order[k]]});
+            out.push_back(p);
+        }
+        return out;
+    }
     // The boundary of the union of `segments` (empty: of every label) as face records in ascending (z, y, x, dir): one surface pass with
     // all of them selected, one emit pass into the context's own buffer, and the read.
     std::vector<struct volym_surface_face> surface_faces(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {},

@@ -10,7 +10,8 @@
 //   slice normal to x, y or z through that texel (Simple::slice) to frame_slice_<axis>.ppm; --project MAX|MEAN[,STEP] the
 //   maximum or mean intensity projection of the view (Simple::project) to frame_project_<mode>.ppm; --measure [NAME,...] prints
 //   the table of segment statistics of the scene in view (Simple::measure); --surface [NAME,...][:MIN_BYTE] prints the surface
-//   table (Simple::surface) and --surface-out FILE.stl writes the mesh of those segments together.
+//   table (Simple::surface) and --surface-out FILE.stl writes the mesh of those segments together; --components [NAME,...][:MIN_BYTE]
+//   prints each segment's connected pieces: how many, the largest, and the ten largest with root and box (Simple::components).
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -59,6 +60,9 @@ struct Options {
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
     std::vector<std::string> surface_names;
     uint32_t surface_min_byte = 1;
+    bool components = false;       // --components [NAME,...][:MIN_BYTE]: also print each segment's connected pieces (run simple)
+    std::vector<std::string> components_names;
+    uint32_t components_min_byte = 1u;
     std::string surface_out;       // --surface-out FILE.stl: also write the mesh of those segments together
 };
 
@@ -247,6 +251,20 @@ int run_simple(const Options& o)
             std::printf("surface: %zu faces -> %s\n", faces.size(), o.surface_out.c_str());
         }
     }
+    if (o.components) {
+        // is each segment one piece: per segment in view, selected alone, its pieces and the ten largest with root and box
+        const std::vector<Simple::Pieces> rows = demo.components(ctx, assets, o.components_names, o.components_min_byte);
+        if (rows.empty()) std::printf("components: no solid texel\n");
+        for (const Simple::Pieces& r : rows) {
+            const uint32_t largest = r.top.empty() ? 0u : r.top.front().record.count;
+            std::printf("%-16s label %3u: %llu piece%s in %llu solid texels, largest %u texels (%.1f%%), %llu smaller than 8 texels\n", r.segment.c_str(), r.label,
+                        static_cast<unsigned long long>(r.pieces), r.pieces == 1u ? "" : "s", static_cast<unsigned long long>(r.solid), largest,
+                        100.0 * static_cast<double>(largest) / static_cast<double>(r.solid), static_cast<unsigned long long>(r.small));
+            for (const Simple::Piece& p : r.top)
+                std::printf("  piece %-8u %10u texels  root (%u,%u,%u)  box [%u,%u,%u]..[%u,%u,%u]%s\n", p.number, p.record.count, p.record.x, p.record.y, p.record.z,
+                            p.record.box[0], p.record.box[1], p.record.box[2], p.record.box[3], p.record.box[4], p.record.box[5], (p.record.flags & 1u) ? " open" : "");
+        }
+    }
     return 0;
 }
 
@@ -342,6 +360,27 @@ int main(int argc, char** argv)
                     }
                 }
             }
+            else if (a == "--components") {
+                o.components = true;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") {
+                    std::string v = next();
+                    const size_t colon = v.rfind(':');
+                    if (colon != std::string::npos) {
+                        size_t used = 0;
+                        unsigned long m = 0;
+                        try { m = std::stoul(v.substr(colon + 1), &used); } catch (const std::exception&) { used = 0; }
+                        if (used == 0 || used != v.size() - colon - 1 || m < 1 || m > 255) throw Error(VOLYM_E_INVALID, "--components: NAME[,NAME...][:MIN_BYTE], MIN_BYTE in 1..255");
+                        o.components_min_byte = static_cast<uint32_t>(m);
+                        v = v.substr(0, colon);
+                    }
+                    size_t pos = 0;
+                    while (pos <= v.size()) {
+                        const size_t comma = std::min(v.find(',', pos), v.size());
+                        if (comma > pos) o.components_names.push_back(v.substr(pos, comma - pos));
+                        pos = comma + 1u;
+                    }
+                }
+            }
             else if (a == "--surface-out") {
                 o.surface_out = next();
                 const size_t n = o.surface_out.size();
@@ -362,7 +401,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

@@ -81,6 +81,7 @@ class GpuContext:
         if v.size != nx * ny * nz:
             raise ValueError("volume has %d bytes, dims say %d" % (v.size, nx * ny * nz))
         self._ck(_lib.lib().volym_set_volume(self.handle, scene._u8p(v), nx, ny, nz, int(filter)))
+        self._volume_dims, self._components_box = (int(nx), int(ny), int(nz)), None      # (read_component_ids shapes its result by them)
 
     def set_importances(self, importances, dims):
         v = np.ascontiguousarray(importances, np.uint8).ravel()
@@ -435,6 +436,62 @@ class GpuContext:
         out = np.zeros(n, _lib.SURFACE_FACE_DTYPE)
         self._ck(_lib.lib().volym_read_surface_faces(self.handle, out.ctypes.data_as(C.POINTER(_lib.SurfaceFace)), n))
         return out
+
+    # ---- connected components ----------------------------------------------------------------
+    def components_pass(self, components=None):
+        """Enqueue one components pass (include/volym_hip.h volym_components_pass; scene.components_volume is its definition): the
+        6-connected pieces of the solid texels of the scene as it stands, numbered in the order of their first texels.
+        `components` is a scene.Components; None: the whole volume, min_byte 1, every label, the default table capacity."""
+        c = None if components is None else C.byref(components.to_c())
+        self._ck(_lib.lib().volym_components_pass(self.handle, c))
+        box = ((0, 0, 0), getattr(self, "_volume_dims", (0, 0, 0))) if components is None else components.box
+        self._components_box = box if all(a < b for a, b in zip(*box)) else None
+
+    def read_components(self):
+        """The summary of the latest components pass: an np.void of _lib.COMPONENTS_SUMMARY_DTYPE (n_components, n_solid, recorded,
+        per_label).  Blocks."""
+        out = np.zeros(1, _lib.COMPONENTS_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_components(self.handle, out.ctypes.data_as(C.POINTER(_lib.ComponentsSummary))))
+        return out[0]
+
+    def read_component_table(self, recorded=None):
+        """The records of the latest components pass (_lib.COMPONENT_DTYPE): record k describes component k.  recorded: how many the
+        pass kept, when the caller has read the summary already (None: it is read here).  Blocks."""
+        n = int(self.read_components()["recorded"]) if recorded is None else int(recorded)
+        out = np.zeros(n, _lib.COMPONENT_DTYPE)
+        self._ck(_lib.lib().volym_read_component_table(self.handle, out.ctypes.data_as(C.POINTER(_lib.Component)), n))
+        return out
+
+    def read_component_ids(self, sub=None):
+        """The ids of the latest components pass as a uint32 array [z, y, x]: of its whole box (None) or of the sub-box (lo, hi) in
+        texels of the volume, which must lie inside the pass's box.  _lib.COMPONENT_NONE marks a texel that is not solid.  Blocks."""
+        box = getattr(self, "_components_box", None) if sub is None else (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        if box is None:                                        # no pass yet (the library refuses), or a pass over an empty box
+            self._ck(_lib.lib().volym_read_component_ids(self.handle, None, None))
+            return np.zeros((0, 0, 0), np.uint32)
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        shape = tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0))
+        out = np.zeros(shape, np.uint32)
+        self._ck(_lib.lib().volym_read_component_ids(self.handle, c, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def component_of(self, x, y, z):
+        """The id of texel (x, y, z) in the latest components pass (_lib.COMPONENT_NONE: not solid).  Blocks; copies 4 bytes."""
+        out = C.c_uint32(0)
+        self._ck(_lib.lib().volym_component_of(self.handle, int(x), int(y), int(z), C.byref(out)))
+        return int(out.value)
+
+    def components_device_ptr(self):
+        """The context's own summary (a volym_components_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_components_device_ptr(self.handle)
+
+    def component_ids_device_ptr(self):
+        """The id volume of the latest components pass in device memory (None before any)."""
+        return _lib.lib().volym_component_ids_device_ptr(self.handle)
+
+    def component_table_device_ptr(self):
+        """The records of the latest components pass in device memory (None before any)."""
+        return _lib.lib().volym_component_table_device_ptr(self.handle)
 
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
@@ -832,6 +889,53 @@ class Simple(ComputeDemo):
         summary, faces = self.surface_faces(ctx, segments, min_byte, box01, uncut)
         mesh.write(path, faces, spacing, origin)
         return scene.surface_summary(summary, None, spacing)
+
+    def components(self, ctx, names=None, min_byte=1, box01=None, uncut=False, spacing=(1, 1, 1), below=8, max_components=0):
+        """Is each segment one piece?  One components pass per segment of `names` (names, ids or label values; None: every label
+        value that has texels in view), each selected alone as surface selects them, in the scene as it stands (uncut=True: as it
+        was uploaded), and the reads of summary and table.  Returns {name: summary} in label order for every segment with a solid
+        texel: {"label", "pieces", "solid" (its solid texels), "recorded", "largest", "share", "small" (scene.components_summary:
+        the pieces of fewer than `below` texels), "top": the ten largest recorded pieces, largest first, as scene.component_dict
+        gives them}.  The labels go to the device first if they are not there yet; without labels everything is label 0."""
+        s = self._surface_request(ctx, None, min_byte, box01, uncut)
+        flags = _lib.COMPONENTS_UNCUT if uncut else 0
+        if names is not None:
+            values = self._label_values(names)
+        else:
+            ctx.measure_pass(scene.Measure(s.box, _lib.MEASURE_UNCUT if uncut else 0, dims=self.dims))
+            values = [int(l) for l in np.flatnonzero(ctx.read_measure()[0]["count"])]
+        out = {}
+        for l in values:
+            ctx.components_pass(scene.check_components(scene.Components(s.box, flags, min_byte, scene.surface_select([l]), max_components), self.dims))
+            summary = ctx.read_components()
+            if not int(summary["n_solid"]):
+                continue
+            table = ctx.read_component_table(summary["recorded"])
+            one = scene.components_summary(summary, table, spacing, below)[l]
+            order = np.argsort(-table["count"].astype(np.int64), kind="stable")[:10]
+            one.update(label=l, solid=int(summary["n_solid"]), top=[scene.component_dict(table[k], k, spacing) for k in order.tolist()])
+            out[self._segment_name(l) or "label %d" % l] = one
+        return out
+
+    def component_at(self, ctx, x, y, alpha_min=0.5, min_byte=1, spacing=(1, 1, 1)):
+        """Click for the piece: pick pixel (x, y), then one components pass for the segment it shows, selected alone, and one measure
+        pass.  Returns the pick with a "component" entry: the record of the piece under the pixel (scene.component_dict) with
+        "pieces" (how many the segment has) and "segment_count" (the segment's texels in view, from the measure pass) added; None
+        when the pixel shows no labelled sample, the picked texel is not solid at min_byte, or the piece has no record."""
+        p = self.pick(ctx, x, y, alpha_min)
+        p["component"] = None
+        if p["status"] == "hit" and p["label"] is not None:
+            l = p["label"]
+            ctx.components_pass(scene.Components(None, 0, min_byte, scene.surface_select([l]), dims=self.dims))
+            number = ctx.component_of(*p["texel"])
+            summary = ctx.read_components()
+            if number != _lib.COMPONENT_NONE and number < int(summary["recorded"]):
+                ctx.measure_pass(scene.Measure(dims=self.dims))
+                rec, _ = ctx.read_measure()
+                one = scene.component_dict(ctx.read_component_table(summary["recorded"])[number], number, spacing)
+                one.update(pieces=int(summary["n_components"]), segment_count=int(rec["count"][l]))
+                p["component"] = one
+        return p
 
     def histogram(self, ctx, segments=None):
         """The density histogram of the visible scene (segments=None), or of the given segments (names, ids or label values) as far

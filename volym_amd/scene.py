@@ -953,6 +953,213 @@ def surface_mesh(faces, spacing=(1, 1, 1), origin=(0, 0, 0)):
     return vertices, inverse.reshape(-1, 4).astype(np.int64)
 
 
+class Components:
+    """volym_components (include/volym_hip.h): what one components pass splits into its pieces.  box, flags, min_byte and select as
+    Surface takes them (flags: _lib.COMPONENTS_UNCUT | _lib.COMPONENTS_SPLIT_LABELS); max_components: the table records to keep
+    (0: _lib.COMPONENTS_DEFAULT_MAX)."""
+
+    def __init__(self, box=None, flags=0, min_byte=1, select=None, max_components=0, dims=None):
+        if box is None:
+            if dims is None:
+                raise ValueError("components without a box need the volume's dims")
+            box = ((0, 0, 0), tuple(int(v) for v in dims))
+        lo, hi = box
+        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.flags = int(flags)
+        self.min_byte = int(min_byte)
+        self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
+        self.max_components = int(max_components)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "components", ("box", "flags", "min_byte", "select", "max_components"), kw)
+
+    def to_c(self):
+        """The _lib.Components of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Components()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("components: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        if not 0 <= self.flags < 2 ** 32 or not 0 <= self.min_byte < 2 ** 32 or not 0 <= self.max_components < 2 ** 32:
+            raise ValueError("components: flags = %d, min_byte = %d and max_components = %d must be u32" % (self.flags, self.min_byte, self.max_components))
+        c.flags, c.min_byte, c.max_components = self.flags, self.min_byte, self.max_components
+        if self.select.size != 256 or not ((self.select >= 0) & (self.select <= 255)).all():
+            raise ValueError("components: the select table is 256 bytes")
+        c.select = (C.c_uint8 * 256)(*[int(g) for g in self.select])
+        return c
+
+
+def check_components(components, dims):
+    """The validity rules of volym_components_check: lo <= hi <= dims on every axis (an empty box is valid), at most
+    _lib.COMPONENTS_BOX_MAX texels in the box, known flag bits, min_byte in 1..255, max_components at most
+    _lib.COMPONENTS_TABLE_MAX.  Returns the request; raises ValueError."""
+    c = components
+    dims = [int(v) for v in dims]
+    lo, hi = c.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("components: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("components box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    if texels > _lib.COMPONENTS_BOX_MAX:
+        raise ValueError("components: the box has %d texels, more than 2^31 - 2" % texels)
+    if c.flags & ~(_lib.COMPONENTS_UNCUT | _lib.COMPONENTS_SPLIT_LABELS) or c.flags < 0:
+        raise ValueError("components: unknown flag bits in %#x" % c.flags)
+    if not 1 <= c.min_byte <= 255:
+        raise ValueError("components: min_byte is 1..255, got %d" % c.min_byte)
+    if not 0 <= c.max_components <= _lib.COMPONENTS_TABLE_MAX:
+        raise ValueError("components: max_components is 0..2^24, got %d" % c.max_components)
+    if np.asarray(c.select).size != 256:
+        raise ValueError("components: the select table has 256 entries")
+    return c
+
+
+def empty_components():
+    """(summary, table, ids) of a pass over an empty box: a zero summary (np.void of _lib.COMPONENTS_SUMMARY_DTYPE), no records
+    (_lib.COMPONENT_DTYPE) and no ids."""
+    return np.zeros(1, _lib.COMPONENTS_SUMMARY_DTYPE)[0], np.zeros(0, _lib.COMPONENT_DTYPE), np.zeros((0, 0, 0), np.uint32)
+
+
+def components_volume(prepared, dims, c, labels=None, cut=None, uncut=None):
+    """The definition of the components pass (include/volym_hip.h volym_components_pass), NumPy and plain Python integers only; equal
+    to the device in every byte.  `prepared`, `uncut`, `labels` and `cut` are what surface_volume takes, and solid is its predicate.
+    A union-find over the x-runs of solid texels (with SPLIT_LABELS: of solid texels of one label), with one union for every pair of
+    runs of adjacent rows that overlap in x; runs are numbered in ascending (z, y, x) of their first texels and the smaller run
+    always becomes the parent, so a component's root run is the one that starts at its root texel.
+    Returns (summary, table, ids): an np.void of _lib.COMPONENTS_SUMMARY_DTYPE, the records (_lib.COMPONENT_DTYPE) of the
+    components numbered below max_components, and the ids as a uint32 array [z, y, x] over the request's box (its bytes are the
+    box-linear id volume), _lib.COMPONENT_NONE where the texel is not solid."""
+    c = check_components(c, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = c.box
+    summary, table, ids = empty_components()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, table, ids
+    whole = bool(c.flags & _lib.COMPONENTS_UNCUT)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("components_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("components_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    split = bool(c.flags & _lib.COMPONENTS_SPLIT_LABELS) and labels is not None
+    solid = (b >= c.min_byte) & (np.asarray(c.select)[l] != 0)
+    d, h, w = solid.shape
+    none = np.uint32(_lib.COMPONENT_NONE)
+    ids = np.full((d, h, w), none, np.uint32)
+    summary["n_solid"] = int(solid.sum())
+    if not solid.any():
+        return summary, table, ids
+
+    def linked(here, there):
+        """texels of `here` linked to their neighbour in `there` (two views of the box, shifted by one texel)"""
+        both = solid[here] & solid[there]
+        return both & (l[here] == l[there]) if split else both
+
+    # the x-runs: a solid texel not linked to its left neighbour starts one
+    start = solid.copy()
+    start[:, :, 1:] &= ~linked((slice(None), slice(None), slice(1, None)), (slice(None), slice(None), slice(0, -1)))
+    run_of = np.cumsum(start.ravel(), dtype=np.int64).reshape(d, h, w) - 1           # of every solid texel: its run, in ascending (z, y, x)
+    first = np.flatnonzero(start.ravel())                                             # of every run: its first texel, box-linear
+    n_runs = first.size
+    # one union per pair of overlapping runs of adjacent rows
+    pairs = []
+    for here, there in (((slice(None), slice(1, None)), (slice(None), slice(0, -1))), ((slice(1, None),), (slice(0, -1),))):
+        at = linked(here, there)
+        pairs.append(np.unique(run_of[here][at] * n_runs + run_of[there][at]))
+    pairs = np.unique(np.concatenate(pairs))
+    parent = list(range(n_runs))
+    for a, r in zip((pairs // n_runs).tolist(), (pairs % n_runs).tolist()):
+        while parent[a] != a:
+            parent[a] = a = parent[parent[a]]
+        while parent[r] != r:
+            parent[r] = r = parent[parent[r]]
+        if a < r:
+            parent[r] = a
+        elif r < a:
+            parent[a] = r
+    parent = np.array(parent, np.int64)
+    while True:                                                                       # every run to its root
+        up = parent[parent]
+        if np.array_equal(up, parent):
+            break
+        parent = up
+    roots = np.flatnonzero(parent == np.arange(n_runs))                               # ascending: the canonical order
+    number = np.zeros(n_runs, np.int64)
+    number[roots] = np.arange(roots.size)
+    of_run = number[parent]                                                           # of every run: its component
+    ids[solid] = of_run[run_of[solid]].astype(np.uint32)
+
+    # the records, from the runs
+    n = roots.size
+    length = np.bincount(run_of[solid], minlength=n_runs)
+    rx, ry, rz = first % w, (first // w) % h, first // (w * h)                         # box coordinates of every run's first texel
+    count = np.zeros(n, np.int64)
+    np.add.at(count, of_run, length)
+    mins = [np.full(n, 1 << 20, np.int64) for _ in range(3)]
+    maxs = [np.full(n, -1, np.int64) for _ in range(3)]
+    for a, (t0, t1) in enumerate(((rx, rx + length - 1), (ry, ry), (rz, rz))):
+        np.minimum.at(mins[a], of_run, t0)
+        np.maximum.at(maxs[a], of_run, t1)
+    edge = (rx == 0) | (rx + length == w) | (ry == 0) | (ry == h - 1) | (rz == 0) | (rz == d - 1)
+    flags = np.zeros(n, np.int64)
+    np.maximum.at(flags, of_run, edge.astype(np.int64))
+    root_label = l.ravel()[first[roots]].astype(np.int64)
+    full = np.zeros(n, _lib.COMPONENT_DTYPE)
+    full["x"], full["y"], full["z"] = rx[roots] + lo[0], ry[roots] + lo[1], rz[roots] + lo[2]
+    full["label"], full["flags"], full["count"] = root_label, flags, count
+    for a in range(3):
+        full["box"][:, a] = mins[a] + lo[a]
+        full["box"][:, 3 + a] = maxs[a] + lo[a]
+    recorded = min(n, c.max_components or _lib.COMPONENTS_DEFAULT_MAX)
+    summary["n_components"], summary["recorded"] = n, recorded
+    summary["per_label"][...] = np.bincount(root_label, minlength=256)
+    return summary, full[:recorded].copy(), ids
+
+
+def components_summary(summary, table, spacing=(1, 1, 1), below=8):
+    """What a user reads off a components pass, per label value that is the root label of some piece: {label: {"pieces": how many
+    pieces have a root of that label (the summary's count, whatever the table kept), "recorded": how many of them the table holds,
+    "largest": the largest recorded piece as a dict (number, root, count, volume = count * the volume of a texel, box with hi
+    inclusive, open: it touches the request's box), "share": the share of ALL solid texels of the request that the largest piece
+    holds (of the segment's own texels when the segment was selected alone), "small": the recorded pieces of fewer than `below`
+    texels as {"pieces", "texels", "numbers"}}}.  Python ints and floats; labels in ascending order."""
+    t = np.asarray(table)
+    n_solid = int(summary["n_solid"])
+    out = {}
+    for label in np.flatnonzero(np.asarray(summary["per_label"])).tolist():
+        mine = np.flatnonzero(t["label"] == label)
+        one = {"pieces": int(summary["per_label"][label]), "recorded": int(mine.size), "largest": None, "share": None,
+               "small": {"pieces": 0, "texels": 0, "numbers": []}}
+        if mine.size:
+            k = int(mine[np.argmax(t["count"][mine])])             # (the first of equals: the lowest number)
+            r = t[k]
+            one["largest"] = component_dict(r, k, spacing)
+            one["share"] = int(r["count"]) / n_solid
+            small = mine[t["count"][mine] < below]
+            one["small"] = {"pieces": int(small.size), "texels": int(t["count"][small].sum()), "numbers": small.tolist()}
+        out[label] = one
+    return out
+
+
+def component_dict(record, number, spacing=(1, 1, 1)):
+    """One record of a components table as a dict of Python values: number, root (x, y, z), label, count, volume, box ((lo), (hi))
+    with hi inclusive, open (the piece touches the request's box and may continue outside)."""
+    sp = [float(v) for v in spacing]
+    box = [int(v) for v in record["box"]]
+    return {"number": int(number), "root": (int(record["x"]), int(record["y"]), int(record["z"])), "label": int(record["label"]),
+            "count": int(record["count"]), "volume": int(record["count"]) * sp[0] * sp[1] * sp[2],
+            "box": (tuple(box[:3]), tuple(box[3:])), "open": bool(int(record["flags"]) & 1)}
+
+
 PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0     # volym_update's range for the march step
 
 
