@@ -26,7 +26,9 @@
  *     volym_assemble_host, volym_stats_pass, volym_time_*; volym_blit blocks only when it has to (re)size its own target, and
  *     volym_surface_faces_pass when it has to learn the face total of its surface pass or grow the context's own face buffer;
  *     volym_components_pass blocks only when it has to allocate or grow its buffers; volym_read_components,
- *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name).
+ *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name);
+ *     volym_distance_pass blocks only when it has to allocate or grow its buffers; volym_read_distance, volym_read_distance_map
+ *     and volym_distance_at block.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -861,6 +863,78 @@ int   volym_component_of(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, uin
 void* volym_components_device_ptr(volym_ctx* ctx);
 void* volym_component_ids_device_ptr(volym_ctx* ctx);
 void* volym_component_table_device_ptr(volym_ctx* ctx);
+
+/* --- distance maps (new; the reference has none) ------------------------------------------------------------------ */
+/* Margins, thickness and clearance: the exact squared Euclidean distance from every texel of a box to the nearest texel of a set.
+ * A read-only pass over the bytes of the scene as they stand: it writes no scene byte.
+ *   The rule (integers only; scene.distance_volume of the Python package is its host twin, equal in every byte).  box, flags,
+ * min_byte and select are volym_surface's.  PRESENT: the texel lies in the box and its density byte is >= min_byte.  SOLID: PRESENT
+ * and select[label] != 0, the surface pass's predicate (UNCUT reads the uncut copy; the label is 0 everywhere while the context holds
+ * no labels of the volume's dimensions).  d2(p, q) = sum over the axes of weight[a] * (p[a] - q[a])^2: anisotropic spacing as
+ * integer weights, 0.5 x 0.5 x 2.5 mm being (1, 1, 25) in units of 0.5 mm.  With 4096 texels per axis d2 <= 3 * 64 * 4095^2 < 2^32.
+ *   The map: one uint32_t per texel of the box, box-linear with x fastest like the component ids, never the device layout.
+ * Without INSIDE, D(t) = min d2(t, s) over the solid texels s of the box: 0 on a solid texel, VOLYM_DISTANCE_NONE everywhere when
+ * the box has none.  With INSIDE, D(t) = min d2(t, u) over the texels u that are not solid, every texel outside the box counting
+ * as not solid (the surface pass's convention: a piece the box cuts is closed along the box); the nearest outside texel is the
+ * axis-aligned one, so D(t) is the minimum of the in-box value and weight[a] * (t[a] - lo[a] + 1)^2 and weight[a] * (hi[a] - t[a])^2
+ * on each axis; 0 on a texel that is not solid, never NONE.
+ *   Ties (max_at, near_at) go to the first texel in ascending (z, y, x): the same request on the same scene gives the same bytes
+ * in either device layout, every time. */
+enum { VOLYM_DISTANCE_UNCUT = 1, VOLYM_DISTANCE_INSIDE = 2 };          /* flags */
+#define VOLYM_DISTANCE_WEIGHT_MAX 64u               /* each weight is 1..64 */
+#define VOLYM_DISTANCE_BOX_MAX 0x7ffffffeu          /* 2^31 - 2: most texels of a request's box */
+#define VOLYM_DISTANCE_NONE 0xffffffffu             /* no seed in the box */
+#define VOLYM_DISTANCE_BINS 256
+typedef struct volym_distance {
+    uint32_t box[6];            /* {x0, y0, z0, x1, y1, z1}: lo inclusive, hi exclusive, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint32_t min_byte;          /* 1..255 */
+    uint8_t  select[256];       /* label value -> != 0: its texels can be solid */
+    uint32_t weight[3];         /* per axis, 1..VOLYM_DISTANCE_WEIGHT_MAX */
+} volym_distance;               /* 300 bytes */
+struct volym_distance_summary {
+    uint64_t n_solid, n_present;
+    uint64_t n_finite;          /* texels of the box with D != NONE */
+    uint32_t max_d2;            /* the largest D != NONE; NONE when n_finite == 0 */
+    uint32_t max_at[3];         /* the first texel that attains it, volume coordinates; {0, 0, 0} when n_finite == 0 */
+    uint32_t near_d2[256];      /* per label byte: the smallest D != NONE over its PRESENT texels, selected or not; NONE: none */
+    uint32_t near_at[256][3];   /* ... and the first such texel; {0, 0, 0}: none */
+    uint64_t hist[VOLYM_DISTANCE_BINS];   /* texels with D != NONE by min(ceil_sqrt(D), 255): sum over k <= r is the texels with D <= r^2 */
+};                              /* 6184 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_distance) == 300, "volym_distance is 300 bytes");
+static_assert(sizeof(struct volym_distance_summary) == 6184, "volym_distance_summary is 6184 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_distance) == 300, "volym_distance is 300 bytes");
+_Static_assert(sizeof(struct volym_distance_summary) == 6184, "volym_distance_summary is 6184 bytes");
+#endif
+/* Enqueue only, on the first slot's stream: the kernel that zeroes the summary, the row sweep, the column sweeps along y and z
+ * (lower envelopes of parabolas, one lane per column), the finish that applies the INSIDE border and accumulates the summary, and
+ * its packing.  d == NULL: the whole volume, min_byte 1, every label, weights 1, no flags.  The one blocking path is the first
+ * allocation, or a growth, of its buffers (4 bytes per texel of the box for the map and 8 for the work arrays).  It needs a volume,
+ * but no volym_update, no frame and no transfer function; it ignores the shard, writes no frame buffer and needs no events with
+ * VOLYM_OPT_FRAMES_IN_FLIGHT = 2.  An empty box launches only the zeroing kernel.  The results are a snapshot: the reads below stay
+ * valid after later edits of the scene.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_distance_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions held
+ * in the other device layout than the volume (as volym_surface_pass). */
+int   volym_distance_pass(volym_ctx* ctx, const volym_distance* d);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis or of more than
+ * VOLYM_DISTANCE_BOX_MAX texels, an unknown flag bit, min_byte outside 1..255, a weight outside 1..VOLYM_DISTANCE_WEIGHT_MAX.  An
+ * empty box is valid.  Pure host arithmetic. */
+int   volym_distance_check(const volym_distance* d, const uint32_t dims[3]);
+/* The reads block.  All: VOLYM_E_STATE before any pass, and after volym_set_volume until the next one; VOLYM_E_INVALID for a NULL
+ * ctx or output.
+ *   volym_read_distance: the summary of the latest pass.
+ *   volym_read_distance_map: the map of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi, inside the pass's box; NULL:
+ * the pass's whole box), box-linear in the sub-box; VOLYM_E_INVALID for a sub-box that reaches outside the pass's box.
+ *   volym_distance_at: D of one texel (4 bytes are copied); VOLYM_E_INVALID for a texel outside the pass's box. */
+int   volym_read_distance(volym_ctx* ctx, struct volym_distance_summary* out);
+int   volym_read_distance_map(volym_ctx* ctx, const uint32_t sub[6], uint32_t* out);
+int   volym_distance_at(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, uint32_t* d2);
+/* The context's own results in device memory after a pass (NULL before any, and after volym_set_volume): the summary (a struct
+ * volym_distance_summary) and the map of the latest pass's box. */
+void* volym_distance_device_ptr(volym_ctx* ctx);
+void* volym_distance_map_device_ptr(volym_ctx* ctx);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

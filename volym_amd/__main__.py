@@ -20,7 +20,10 @@ intensity along the rays of the same view, STEP apart (default: a quarter of the
 (demo.Simple.project).  --surface [NAME,...][:MIN_BYTE] prints the surface table of the scene in view -- faces per axis, area, enclosed
 texels beside the measured count and sphericity per segment (demo.Simple.surface) -- and --surface-out FILE.stl|.obj writes the mesh of
 those segments together (demo.Simple.export_surface).  --components [NAME,...][:MIN_BYTE] prints, per segment in view, its connected
-pieces -- how many, the largest, and the ten largest with root and box (demo.Simple.components).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
+pieces -- how many, the largest, and the ten largest with root and box (demo.Simple.components).  --distance [NAME,...][:MIN_BYTE]
+prints the distance map's summary for the union of those segments (default: every label) -- solid texels, the deepest point and, per
+segment, its nearest texel and the clearance -- and writes the histogram as <screenshot>_distance.json; --distance-inside measures
+inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
 """
@@ -258,6 +261,18 @@ def _components_table(rows):
     return "\n".join(lines) if lines else "components: no solid texel"
 
 
+def _distance_table(s, inside):
+    """what --distance prints: solid texels and the deepest point of demo.Simple.distance's dict, then the nearest texel of every segment"""
+    if s["max_d2"] is None:
+        lines = ["distance: %d solid texels%s, deepest (none): no texel at a finite distance" % (s["n_solid"], " (inside)" if inside else "")]
+    else:
+        lines = ["distance: %d solid texels%s, deepest (%d,%d,%d) d2 %d = %.3f, %d texels at a finite distance" % (
+            (s["n_solid"], " (inside)" if inside else "") + s["max_at"] + (s["max_d2"], s["max"], s["n_finite"]))]
+    for l, c in s["clearance"].items():
+        lines.append("  nearest %-16s label %3d: d2 %10d = %9.3f at (%d,%d,%d)" % ((c["segment"], l, c["d2"], c["distance"]) + c["at"]))
+    return "\n".join(lines)
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -336,9 +351,26 @@ def run_simple(args):
                 pieces = d.components(ctx, names, min_byte)
             except ValueError as e:
                 raise SystemExit("--components: %s" % e)
+        distances = None
+        if getattr(args, "distance", None) is not None:
+            names, min_byte = _surface_arg(args.distance, "--distance")
+            inside = bool(getattr(args, "distance_inside", False))
+            try:
+                distances = d.distance(ctx, names, inside, min_byte)
+                distances["hist"] = [int(v) for v in ctx.read_distance()["hist"]]
+            except ValueError as e:
+                raise SystemExit("--distance: %s" % e)
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    if distances is not None:
+        import json
+        print(_distance_table(distances, inside))
+        stem = path[:-4] if path.lower().endswith(".png") else path
+        with open(stem + "_distance.json", "w") as f:
+            json.dump({"inside": inside, "n_solid": distances["n_solid"], "n_finite": distances["n_finite"], "max_d2": distances["max_d2"],
+                       "max_at": list(distances["max_at"]), "hist": distances["hist"]}, f)
+        print("distance histogram -> %s_distance.json" % stem)
     if pieces is not None:
         print(_components_table(pieces))
     if surfaced is not None:
@@ -480,6 +512,10 @@ def main(argv=None):
                           "least MIN_BYTE, default 1, are solid): faces per axis, area, enclosed texels beside the measured count, sphericity")
     run.add_argument("--components", nargs="?", const="", metavar="NAME,...[:MIN_BYTE]",
                      help="also print, per segment (all in view, or the named ones), its connected pieces: how many, the largest, and the ten largest with root and box")
+    run.add_argument("--distance", nargs="?", const="", metavar="NAME,...[:MIN_BYTE]",
+                     help="also print the distance map's summary for the union of the named segments (default: every label): solid texels, the deepest "
+                          "point, the nearest texel of every segment; and write the histogram as <screenshot>_distance.json")
+    run.add_argument("--distance-inside", action="store_true", help="with --distance: distances inside the set, to its complement (thickness)")
     run.add_argument("--surface-out", metavar="FILE.stl|.obj", help="also write the surface of those segments together as a binary STL or an OBJ mesh")
     run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")

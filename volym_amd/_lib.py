@@ -235,6 +235,35 @@ COMPONENTS_SUMMARY_DTYPE = np.dtype([("n_components", "<u8"), ("n_solid", "<u8")
 COMPONENT_DTYPE = np.dtype([("x", "<u2"), ("y", "<u2"), ("z", "<u2"), ("label", "u1"), ("flags", "u1"), ("count", "<u4"), ("box", "<u2", (6,))])
 
 
+DISTANCE_UNCUT, DISTANCE_INSIDE = 1, 2                          # volym_distance.flags
+DISTANCE_WEIGHT_MAX = 64                                       # each weight is 1..64
+DISTANCE_BOX_MAX = 2 ** 31 - 2                                 # most texels of a request's box
+DISTANCE_NONE = 0xFFFFFFFF                                     # no seed in the box
+DISTANCE_BINS = 256
+
+
+class Distance(C.Structure):
+    """volym_distance (include/volym_hip.h): box, flags, min_byte, select table and axis weights of one distance pass, 300 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("select", C.c_uint8 * 256),
+        ("weight", C.c_uint32 * 3),
+    ]
+
+
+class DistanceSummary(C.Structure):
+    """volym_distance_summary (include/volym_hip.h): counters, the deepest texel, the nearest texel per label and the histogram, 6184 bytes"""
+    _fields_ = [("n_solid", C.c_uint64), ("n_present", C.c_uint64), ("n_finite", C.c_uint64), ("max_d2", C.c_uint32), ("max_at", C.c_uint32 * 3),
+                ("near_d2", C.c_uint32 * 256), ("near_at", (C.c_uint32 * 3) * 256), ("hist", C.c_uint64 * 256)]
+
+
+# the summary as a NumPy structured dtype (GpuContext.read_distance, scene.distance_volume)
+DISTANCE_SUMMARY_DTYPE = np.dtype([("n_solid", "<u8"), ("n_present", "<u8"), ("n_finite", "<u8"), ("max_d2", "<u4"), ("max_at", "<u4", (3,)),
+                                   ("near_d2", "<u4", (256,)), ("near_at", "<u4", (256, 3)), ("hist", "<u8", (256,))])
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -391,6 +420,13 @@ SIGNATURES = {
     "volym_components_device_ptr": (C.c_void_p, [_ctx]),
     "volym_component_ids_device_ptr": (C.c_void_p, [_ctx]),
     "volym_component_table_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_distance_pass": (C.c_int, [_ctx, C.POINTER(Distance)]),
+    "volym_distance_check": (C.c_int, [C.POINTER(Distance), C.POINTER(C.c_uint32)]),
+    "volym_read_distance": (C.c_int, [_ctx, C.POINTER(DistanceSummary)]),
+    "volym_read_distance_map": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_distance_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "volym_distance_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_distance_map_device_ptr": (C.c_void_p, [_ctx]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -1,7 +1,7 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
 // logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
 // capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI, and the measure pass over them; pick.hip: the pick pass and its C ABI; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI; components.hip: the components pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
+// their C ABI, and the measure pass over them; pick.hip: the pick pass and its C ABI; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI; components.hip: the components pass and its C ABI; distance.hip: the distance pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
 // host only, it knows nothing of this header.
 #pragma once
 
@@ -247,6 +247,13 @@ struct volym_ctx {
     volym::OwnedBuffer<uint32_t> component_sums;     // the scan's block sums; replaced whenever component_rows is
     uint32_t component_box[6] = {};          // the box of the latest pass (the reads address the id volume by it)
 
+    // distance passes (volym_distance_pass, distance.hip): a snapshot, valid until the next volym_set_volume
+    volym::OwnedBuffer<volym_distance_summary> distance;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> distance_map;       // D of every texel of the request's box, box-linear
+    volym::OwnedBuffer<uint32_t> distance_work;      // the column sweeps' stacks: two words per texel of the box (distance_kernels.h)
+    volym::OwnedBuffer<unsigned long long> distance_keys;   // the working summary: counters and 64-bit (D, index) keys, packed into `distance`
+    uint32_t distance_box[6] = {};           // the box of the latest pass (the reads address the map by it)
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -305,6 +312,8 @@ void free_measure(volym_ctx* c);
 void free_surface(volym_ctx* c);
 // components.hip: what the context keeps for the components pass (every stream idle)
 void free_components(volym_ctx* c);
+// distance.hip: what the context keeps for the distance pass (every stream idle)
+void free_distance(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume
@@ -319,7 +328,7 @@ int build_fine_cells(volym_ctx* c);
             return volym::ctx_fail(ctx, VOLYM_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
 
-// ---- what the read-only passes (pick, outline, slice, projection, measure, surface, components) and the blit share on the host ----
+// ---- what the read-only passes (pick, outline, slice, projection, measure, surface, components, distance) and the blit share on the host ----
 namespace volym {
 
 // `bytes` of device memory to host memory behind the work of `stream`, blocking: what every volym_read_* ends in
@@ -374,7 +383,7 @@ inline void pack_palette_and_lut(const volym_ctx* c, const uint8_t palette[256][
     for (uint32_t l = 0; l < 256u; ++l) out_lut[l] = l < c->tf_n ? pack_rgba(c->lut + 4u * l) : 0u;
 }
 
-// The box of a request over the scene's bytes (measure, surface, components), {lo[3], hi[3]} in texels: the whole volume, and the check
+// The box of a request over the scene's bytes (measure, surface, components, distance), {lo[3], hi[3]} in texels: the whole volume, and the check
 // lo <= hi <= dims on every axis.  No context: the volym_*_check calls run without a device.
 inline void whole_volume_box(const uint32_t dims[3], uint32_t box[6])
 {

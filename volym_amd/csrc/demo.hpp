@@ -581,6 +581,45 @@ public:
         }
         return out;
     }
+    // New: distance maps (volym_distance_pass) -- margins, thickness and clearance.  One distance pass with the union of `segments`
+    // selected (empty: every label) over the scene as it stands (uncut: as it was uploaded), weights 1, and the read of its summary;
+    // the map stays on the device for volym_read_distance_map and volym_distance_at.  inside: distances to the set's complement
+    // (thickness) instead of to the set (margins, clearance).  `nearest`: per label with a present texel at a finite distance, its
+    // squared distance to the set and the first texel that attains it.
+    struct Nearest {
+        uint8_t label;
+        std::string segment;
+        uint32_t d2, at[3];
+    };
+    struct Distances {
+        struct volym_distance_summary summary;
+        bool finite;                            // some texel has a finite distance: max_d2 and max_at mean something
+        std::vector<Nearest> nearest;
+    };
+    Distances distance(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {}, bool inside = false, uint32_t min_byte = 1u,
+                       bool uncut = false)
+    {
+        if (!labels_on_device_ && !a.labels_raw.empty()) set_labels(ctx, a);
+        volym_distance q{};
+        q.box[3] = a.nx; q.box[4] = a.ny; q.box[5] = a.nz;
+        q.flags = (uncut ? VOLYM_DISTANCE_UNCUT : 0u) | (inside ? VOLYM_DISTANCE_INSIDE : 0u);
+        q.min_byte = min_byte;
+        for (int l = 0; l < 256; ++l) q.select[l] = segments.empty() ? 1 : 0;
+        for (const std::string& name : segments) q.select[label_value_of(a, name)] = 1;
+        q.weight[0] = q.weight[1] = q.weight[2] = 1u;
+        ctx.check(volym_distance_pass(ctx.handle(), &q));
+        std::vector<Distances> r(1);
+        ctx.check(volym_read_distance(ctx.handle(), &r[0].summary));
+        r[0].finite = r[0].summary.n_finite != 0u;
+        for (int l = 0; l < 256; ++l) {
+            if (r[0].summary.near_d2[l] == VOLYM_DISTANCE_NONE) continue;
+            Nearest n{static_cast<uint8_t>(l), "label " + std::to_string(l), r[0].summary.near_d2[l],
+                      {r[0].summary.near_at[l][0], r[0].summary.near_at[l][1], r[0].summary.near_at[l][2]}};
+            for (const SegmentInfo& seg : a.segments) if (seg.label_value == l) { n.segment = seg.name.empty() ? seg.id : seg.name; break; }
+            r[0].nearest.push_back(n);
+        }
+        return r[0];
+    }
     // The boundary of the union of `segments` (empty: of every label) as face records in ascending (z, y, x, dir): one surface pass with
     // all of them selected, one emit pass into the context's own buffer, and the read.
     std::vector<struct volym_surface_face> surface_faces(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& segments = {},

@@ -1,6 +1,6 @@
 // libvolym_hip.so: context, frame loop and their C ABI (include/volym_hip.h) over the gfx950 kernels.  The bytes of the scene
 // (volume, labels, importances, crop box, segment visibility, macro cells) and their C ABI are scene_bytes.hip; the read-only
-// passes over frame and scene (pick, outline, slice, projection, surface, components) are units of their own, each with its C ABI.
+// passes over frame and scene (pick, outline, slice, projection, surface, components, distance) are units of their own, each with its C ABI.
 // Replaces the reference's gpu_context.rs / gpu_resources/* / demos/pipeline.rs for the
 // ray-march path; citations are file:line under /root/reference/.
 //
@@ -602,6 +602,7 @@ void volym_destroy(volym_ctx* c)
     free_measure(c);
     free_surface(c);
     free_components(c);
+    free_distance(c);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);
     delete c;
 }

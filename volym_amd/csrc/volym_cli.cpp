@@ -11,7 +11,9 @@
 //   maximum or mean intensity projection of the view (Simple::project) to frame_project_<mode>.ppm; --measure [NAME,...] prints
 //   the table of segment statistics of the scene in view (Simple::measure); --surface [NAME,...][:MIN_BYTE] prints the surface
 //   table (Simple::surface) and --surface-out FILE.stl writes the mesh of those segments together; --components [NAME,...][:MIN_BYTE]
-//   prints each segment's connected pieces: how many, the largest, and the ten largest with root and box (Simple::components).
+//   prints each segment's connected pieces: how many, the largest, and the ten largest with root and box (Simple::components);
+//   --distance [NAME,...][:MIN_BYTE] prints the distance map's summary for the union of those segments -- solid texels, the deepest
+//   point, the nearest texel of every segment -- and --distance-inside measures inside the set instead (Simple::distance).
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -64,6 +66,10 @@ struct Options {
     std::vector<std::string> components_names;
     uint32_t components_min_byte = 1u;
     std::string surface_out;       // --surface-out FILE.stl: also write the mesh of those segments together
+    bool distance = false;         // --distance [NAME,...][:MIN_BYTE]: also print the distance map's summary (run simple)
+    bool distance_inside = false;  // --distance-inside: distances inside the set, to its complement
+    std::vector<std::string> distance_names;
+    uint32_t distance_min_byte = 1u;
 };
 
 SimpleAssets load_assets(const Options& o, std::string& what)
@@ -265,6 +271,20 @@ int run_simple(const Options& o)
                             p.record.box[0], p.record.box[1], p.record.box[2], p.record.box[3], p.record.box[4], p.record.box[5], (p.record.flags & 1u) ? " open" : "");
         }
     }
+    if (o.distance) {
+        // margins, thickness, clearance: the summary of the distance map of the named segments' union
+        const Simple::Distances r = demo.distance(ctx, assets, o.distance_names, o.distance_inside, o.distance_min_byte);
+        const char* mode = o.distance_inside ? " (inside)" : "";
+        if (!r.finite)
+            std::printf("distance: %llu solid texels%s, deepest (none): no texel at a finite distance\n", static_cast<unsigned long long>(r.summary.n_solid), mode);
+        else
+            std::printf("distance: %llu solid texels%s, deepest (%u,%u,%u) d2 %u = %.3f, %llu texels at a finite distance\n",
+                        static_cast<unsigned long long>(r.summary.n_solid), mode, r.summary.max_at[0], r.summary.max_at[1], r.summary.max_at[2], r.summary.max_d2,
+                        std::sqrt(static_cast<double>(r.summary.max_d2)), static_cast<unsigned long long>(r.summary.n_finite));
+        for (const Simple::Nearest& n : r.nearest)
+            std::printf("  nearest %-16s label %3u: d2 %10u = %9.3f at (%u,%u,%u)\n", n.segment.c_str(), n.label, n.d2, std::sqrt(static_cast<double>(n.d2)), n.at[0], n.at[1],
+                        n.at[2]);
+    }
     return 0;
 }
 
@@ -381,6 +401,28 @@ int main(int argc, char** argv)
                     }
                 }
             }
+            else if (a == "--distance-inside") o.distance_inside = true;
+            else if (a == "--distance") {
+                o.distance = true;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") {
+                    std::string v = next();
+                    const size_t colon = v.rfind(':');
+                    if (colon != std::string::npos) {
+                        size_t used = 0;
+                        unsigned long m = 0;
+                        try { m = std::stoul(v.substr(colon + 1), &used); } catch (const std::exception&) { used = 0; }
+                        if (used == 0 || used != v.size() - colon - 1 || m < 1 || m > 255) throw Error(VOLYM_E_INVALID, "--distance: NAME[,NAME...][:MIN_BYTE], MIN_BYTE in 1..255");
+                        o.distance_min_byte = static_cast<uint32_t>(m);
+                        v = v.substr(0, colon);
+                    }
+                    size_t pos = 0;
+                    while (pos <= v.size()) {
+                        const size_t comma = std::min(v.find(',', pos), v.size());
+                        if (comma > pos) o.distance_names.push_back(v.substr(pos, comma - pos));
+                        pos = comma + 1u;
+                    }
+                }
+            }
             else if (a == "--surface-out") {
                 o.surface_out = next();
                 const size_t n = o.surface_out.size();
@@ -401,7 +443,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

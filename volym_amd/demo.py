@@ -82,6 +82,7 @@ class GpuContext:
             raise ValueError("volume has %d bytes, dims say %d" % (v.size, nx * ny * nz))
         self._ck(_lib.lib().volym_set_volume(self.handle, scene._u8p(v), nx, ny, nz, int(filter)))
         self._volume_dims, self._components_box = (int(nx), int(ny), int(nz)), None      # (read_component_ids shapes its result by them)
+        self._distance_box = None
 
     def set_importances(self, importances, dims):
         v = np.ascontiguousarray(importances, np.uint8).ravel()
@@ -492,6 +493,50 @@ class GpuContext:
     def component_table_device_ptr(self):
         """The records of the latest components pass in device memory (None before any)."""
         return _lib.lib().volym_component_table_device_ptr(self.handle)
+
+    # ---- distance maps ---------------------------------------------------------------------------
+    def distance_pass(self, distance=None):
+        """Enqueue one distance pass (include/volym_hip.h volym_distance_pass; scene.distance_volume is its definition): the exact
+        weighted squared distance from every texel of the request's box to the nearest solid texel (INSIDE: to the nearest texel
+        that is not solid) of the scene as it stands.  `distance` is a scene.Distance; None: the whole volume, min_byte 1, every
+        label, weights 1, no flags."""
+        d = None if distance is None else C.byref(distance.to_c())
+        self._ck(_lib.lib().volym_distance_pass(self.handle, d))
+        box = ((0, 0, 0), getattr(self, "_volume_dims", (0, 0, 0))) if distance is None else distance.box
+        self._distance_box = box if all(a < b for a, b in zip(*box)) else None
+
+    def read_distance(self):
+        """The summary of the latest distance pass: an np.void of _lib.DISTANCE_SUMMARY_DTYPE.  Blocks."""
+        out = np.zeros(1, _lib.DISTANCE_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_distance(self.handle, out.ctypes.data_as(C.POINTER(_lib.DistanceSummary))))
+        return out[0]
+
+    def read_distance_map(self, sub=None):
+        """The map of the latest distance pass as a uint32 array [z, y, x]: of its whole box (None) or of the sub-box (lo, hi) in
+        texels of the volume, which must lie inside the pass's box.  _lib.DISTANCE_NONE: the box holds no seed.  Blocks."""
+        box = getattr(self, "_distance_box", None) if sub is None else (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        if box is None:                                        # no pass yet (the library refuses), or a pass over an empty box
+            self._ck(_lib.lib().volym_read_distance_map(self.handle, None, None))
+            return np.zeros((0, 0, 0), np.uint32)
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        shape = tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0))
+        out = np.zeros(shape, np.uint32)
+        self._ck(_lib.lib().volym_read_distance_map(self.handle, c, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def distance_at(self, x, y, z):
+        """D of texel (x, y, z) in the latest distance pass (_lib.DISTANCE_NONE: no seed).  Blocks; copies 4 bytes."""
+        out = C.c_uint32(0)
+        self._ck(_lib.lib().volym_distance_at(self.handle, int(x), int(y), int(z), C.byref(out)))
+        return int(out.value)
+
+    def distance_device_ptr(self):
+        """The context's own summary (a volym_distance_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_distance_device_ptr(self.handle)
+
+    def distance_map_device_ptr(self):
+        """The map of the latest distance pass in device memory (None before any)."""
+        return _lib.lib().volym_distance_map_device_ptr(self.handle)
 
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
@@ -935,6 +980,66 @@ class Simple(ComputeDemo):
                 one = scene.component_dict(ctx.read_component_table(summary["recorded"])[number], number, spacing)
                 one.update(pieces=int(summary["n_components"]), segment_count=int(rec["count"][l]))
                 p["component"] = one
+        return p
+
+    def _distance_request(self, ctx, values, inside, min_byte, box01, uncut, spacing):
+        s = self._surface_request(ctx, values, min_byte, box01, uncut)
+        weights, unit = scene.distance_weights(spacing)
+        flags = (_lib.DISTANCE_UNCUT if uncut else 0) | (_lib.DISTANCE_INSIDE if inside else 0)
+        return scene.check_distance(scene.Distance(s.box, flags, min_byte, s.select, weights), self.dims), unit
+
+    def distance(self, ctx, names=None, inside=False, min_byte=1, box01=None, uncut=False, spacing=(1, 1, 1)):
+        """The distance map of the union of the segments `names` (names, ids or label values; None: every label) in the scene as it
+        stands (uncut=True: as it was uploaded): one distance pass and the read of its summary; the map stays on the device for
+        ctx.read_distance_map and ctx.distance_at.  inside=False: distances from the set, for margins and clearance; inside=True:
+        distances to the set's complement, for thickness.  spacing: the texel spacing, integer multiples (1..8) of its smallest
+        (scene.distance_weights).  Returns scene.distance_summary's dict -- distances in the units of `spacing` -- with "unit",
+        "weights" and, in "clearance", the segments' names added.  The labels go to the device first if they are not there yet."""
+        values = None if names is None else self._label_values(names)
+        d, unit = self._distance_request(ctx, values, inside, min_byte, box01, uncut, spacing)
+        ctx.distance_pass(d)
+        out = scene.distance_summary(ctx.read_distance(), unit)
+        out.update(unit=unit, weights=d.weight)
+        for l, c in out["clearance"].items():
+            c["segment"] = self._segment_name(l) or "label %d" % l
+        return out
+
+    def thickness(self, ctx, name, min_byte=1, box01=None, uncut=False, spacing=(1, 1, 1)):
+        """Where is segment `name` thickest?  One INSIDE distance pass with the segment selected alone.  Returns {"at": the deepest
+        texel (the first in ascending (z, y, x) of equals), "d2", "radius": the radius of the largest ball round it that fits
+        inside the segment, in the units of `spacing`, "thickness": twice that, "solid": the segment's solid texels}; None when
+        the segment has no solid texel."""
+        out = self.distance(ctx, [name], True, min_byte, box01, uncut, spacing)
+        if not out["n_solid"]:
+            return None
+        return {"at": out["max_at"], "d2": out["max_d2"], "radius": out["max"], "thickness": 2.0 * out["max"], "solid": out["n_solid"]}
+
+    def clearance(self, ctx, a, b, min_byte=1, box01=None, uncut=False, spacing=(1, 1, 1)):
+        """How close does segment `a` come to segment `b`?  Two distance passes: one with `a` selected, whose near_at[b] is the texel
+        of `b` nearest to `a`; one with `b` selected, whose near_at[a] is its partner in `a` (both passes find the same smallest
+        distance, and each texel is the first of equals in ascending (z, y, x) on its side).  Returns {"d2", "distance" (units of
+        `spacing`), "at_a", "at_b"}; None when either segment has no present texel or `a` == `b`."""
+        (la,), (lb,) = self._label_values([a]), self._label_values([b])
+        if la == lb:
+            return None
+        from_a = self.distance(ctx, [la], False, min_byte, box01, uncut, spacing)["clearance"].get(lb)
+        from_b = self.distance(ctx, [lb], False, min_byte, box01, uncut, spacing)["clearance"].get(la)
+        if from_a is None or from_b is None:
+            return None
+        return {"d2": from_a["d2"], "distance": from_a["distance"], "at_a": from_b["at"], "at_b": from_a["at"]}
+
+    def distance_at(self, ctx, x, y, alpha_min=0.5, inside=False, **kw):
+        """Click for the distance map: pick pixel (x, y), then one distance pass for the segment it shows, selected alone.  Returns
+        the pick with a "distance" entry (what distance gives, with "d2_here": D at the picked texel); None when the pixel shows
+        no labelled sample.  Keywords go to distance."""
+        p = self.pick(ctx, x, y, alpha_min)
+        p["distance"] = None
+        if p["status"] == "hit" and p["label"] is not None:
+            one = self.distance(ctx, [p["label"]], inside, **kw)
+            box = ctx._distance_box
+            if box is not None and all(lo <= t < hi for t, lo, hi in zip(p["texel"], *box)):
+                one["d2_here"] = ctx.distance_at(*p["texel"])
+            p["distance"] = one
         return p
 
     def histogram(self, ctx, segments=None):

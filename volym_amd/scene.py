@@ -1160,6 +1160,208 @@ def component_dict(record, number, spacing=(1, 1, 1)):
             "box": (tuple(box[:3]), tuple(box[3:])), "open": bool(int(record["flags"]) & 1)}
 
 
+class Distance:
+    """volym_distance (include/volym_hip.h): what one distance pass maps.  box, flags, min_byte and select as Surface takes them
+    (flags: _lib.DISTANCE_UNCUT | _lib.DISTANCE_INSIDE); weight: the three integer weights of the squared distance, 1..64 each."""
+
+    def __init__(self, box=None, flags=0, min_byte=1, select=None, weight=(1, 1, 1), dims=None):
+        if box is None:
+            if dims is None:
+                raise ValueError("a distance request without a box needs the volume's dims")
+            box = ((0, 0, 0), tuple(int(v) for v in dims))
+        lo, hi = box
+        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.flags = int(flags)
+        self.min_byte = int(min_byte)
+        self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
+        self.weight = tuple(int(v) for v in weight)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "distance", ("box", "flags", "min_byte", "select", "weight"), kw)
+
+    def to_c(self):
+        """The _lib.Distance of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Distance()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("distance: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        if not 0 <= self.flags < 2 ** 32 or not 0 <= self.min_byte < 2 ** 32:
+            raise ValueError("distance: flags = %d and min_byte = %d must be u32" % (self.flags, self.min_byte))
+        c.flags, c.min_byte = self.flags, self.min_byte
+        if self.select.size != 256 or not ((self.select >= 0) & (self.select <= 255)).all():
+            raise ValueError("distance: the select table is 256 bytes")
+        c.select = (C.c_uint8 * 256)(*[int(g) for g in self.select])
+        if len(self.weight) != 3 or not all(0 <= x < 2 ** 32 for x in self.weight):
+            raise ValueError("distance: the weights are three u32")
+        c.weight = (C.c_uint32 * 3)(*self.weight)
+        return c
+
+
+def check_distance(distance, dims):
+    """The validity rules of volym_distance_check: lo <= hi <= dims on every axis (an empty box is valid), at most
+    _lib.DISTANCE_BOX_MAX texels in the box, known flag bits, min_byte in 1..255, every weight in 1.._lib.DISTANCE_WEIGHT_MAX.
+    Returns the request; raises ValueError."""
+    d = distance
+    dims = [int(v) for v in dims]
+    lo, hi = d.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("distance: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("distance box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    if texels > _lib.DISTANCE_BOX_MAX:
+        raise ValueError("distance: the box has %d texels, more than 2^31 - 2" % texels)
+    if d.flags & ~(_lib.DISTANCE_UNCUT | _lib.DISTANCE_INSIDE) or d.flags < 0:
+        raise ValueError("distance: unknown flag bits in %#x" % d.flags)
+    if not 1 <= d.min_byte <= 255:
+        raise ValueError("distance: min_byte is 1..255, got %d" % d.min_byte)
+    if len(d.weight) != 3 or not all(1 <= v <= _lib.DISTANCE_WEIGHT_MAX for v in d.weight):
+        raise ValueError("distance: the weights are three integers in 1..%d, got %r" % (_lib.DISTANCE_WEIGHT_MAX, (d.weight,)))
+    if np.asarray(d.select).size != 256:
+        raise ValueError("distance: the select table has 256 entries")
+    return d
+
+
+def empty_distance():
+    """(summary, map) of a pass over an empty box: no texel is finite (an np.void of _lib.DISTANCE_SUMMARY_DTYPE) and no map."""
+    summary = np.zeros(1, _lib.DISTANCE_SUMMARY_DTYPE)[0]
+    summary["max_d2"] = _lib.DISTANCE_NONE
+    summary["near_d2"][...] = _lib.DISTANCE_NONE
+    return summary, np.zeros((0, 0, 0), np.uint32)
+
+
+def distance_ceil_sqrt(v):
+    """The smallest integer c with c * c >= v, elementwise and exact (the float root proposes, integers settle)."""
+    v = np.asarray(v, np.int64)
+    c = np.sqrt(v.astype(np.float64)).astype(np.int64)
+    c += c * c < v
+    c -= (c > 0) & ((c - 1) * (c - 1) >= v)
+    return c
+
+
+def distance_volume(prepared, dims, d, labels=None, cut=None, uncut=None):
+    """The definition of the distance pass (include/volym_hip.h volym_distance_pass), NumPy integers only; equal to the device in
+    every byte.  `prepared`, `uncut`, `labels` and `cut` are what surface_volume takes, and solid is its predicate.  The transform is
+    separable: per axis one broadcast minimum, f[i] = min_j g[j] + weight * (i - j)^2, taken one j at a time over the whole box.
+    Returns (summary, map): an np.void of _lib.DISTANCE_SUMMARY_DTYPE and D as a uint32 array [z, y, x] over the request's box (its
+    bytes are the box-linear map), _lib.DISTANCE_NONE where the box holds no seed."""
+    d = check_distance(d, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = d.box
+    summary, none = empty_distance()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, none
+    whole = bool(d.flags & _lib.DISTANCE_UNCUT)
+    inside = bool(d.flags & _lib.DISTANCE_INSIDE)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("distance_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("distance_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    present = b >= d.min_byte
+    solid = present & (np.asarray(d.select)[l] != 0)
+    seeds = ~solid if inside else solid
+    far = np.int64(1) << 40                                         # no seed: above every distance, and three of them do not overflow
+    g = np.where(seeds, np.int64(0), far)
+    for axis, weight in ((2, d.weight[0]), (1, d.weight[1]), (0, d.weight[2])):
+        n = g.shape[axis]
+        shape = [1, 1, 1]
+        shape[axis] = n
+        i = np.arange(n, dtype=np.int64).reshape(shape)
+        f = np.full(g.shape, far, np.int64)
+        for j in range(n):
+            at = [slice(None)] * 3
+            at[axis] = slice(j, j + 1)
+            np.minimum(f, g[tuple(at)] + weight * (i - j) ** 2, out=f)
+        g = np.minimum(f, far)
+    if inside:
+        # every texel outside the box is a seed, and the nearest of them is the axis-aligned one
+        for axis, weight in ((2, d.weight[0]), (1, d.weight[1]), (0, d.weight[2])):
+            n = g.shape[axis]
+            shape = [1, 1, 1]
+            shape[axis] = n
+            i = np.arange(n, dtype=np.int64).reshape(shape)
+            g = np.minimum(g, weight * np.minimum(i + 1, n - i) ** 2)
+    finite = g < far
+    out = np.where(finite, g, np.int64(_lib.DISTANCE_NONE)).astype(np.uint32)
+    return distance_map_summary(out, b, l, d), out
+
+
+def distance_map_summary(dmap, density, label, d):
+    """The summary of a distance map, from the map (uint32 [z, y, x] over the request's box) and the density and label bytes of the
+    same box: what the finish of the pass accumulates, by its definition."""
+    summary, _ = empty_distance()
+    lo, _hi = d.box
+    depth, h, w = dmap.shape
+    present = density >= d.min_byte
+    solid = present & (np.asarray(d.select)[label] != 0)
+    finite = dmap != np.uint32(_lib.DISTANCE_NONE)
+    summary["n_solid"], summary["n_present"], summary["n_finite"] = int(solid.sum()), int(present.sum()), int(finite.sum())
+
+    def texel(i):
+        return (lo[0] + i % w, lo[1] + (i // w) % h, lo[2] + i // (w * h))
+
+    flat = dmap.ravel().astype(np.int64)
+    if finite.any():
+        top = int(flat[finite.ravel()].max())
+        summary["max_d2"] = top
+        summary["max_at"][...] = texel(int(np.flatnonzero(finite.ravel() & (flat == top))[0]))
+        bins = np.minimum(distance_ceil_sqrt(flat[finite.ravel()]), 255)
+        summary["hist"][...] = np.bincount(bins, minlength=256)
+    ok = (present & finite).ravel()
+    lab = label.ravel()
+    for v in np.unique(lab[ok]).tolist():
+        mine = ok & (lab == v)
+        best = int(flat[mine].min())
+        summary["near_d2"][v] = best
+        summary["near_at"][v][...] = texel(int(np.flatnonzero(mine & (flat == best))[0]))
+    return summary
+
+
+def distance_weights(spacing):
+    """(weights, unit) for a texel spacing (sx, sy, sz): the squared integer multiples of the smallest spacing, and that smallest
+    spacing -- sqrt(D) * unit is a physical distance.  Raises ValueError where a spacing is no integer multiple (1..8) of the
+    smallest: the device takes integer weights of at most 64 only."""
+    sp = [float(v) for v in spacing]
+    if len(sp) != 3 or not all(v > 0.0 and np.isfinite(v) for v in sp):
+        raise ValueError("distance_weights: three positive spacings, got %r" % (spacing,))
+    unit = min(sp)
+    weights = []
+    for v in sp:
+        m = int(round(v / unit))
+        if not 1 <= m <= 8 or abs(v / unit - m) > 1e-6 * m:
+            raise ValueError("distance_weights: spacing %g is no integer multiple (1..8) of the smallest, %g" % (v, unit))
+        weights.append(m * m)
+    return tuple(weights), unit
+
+
+def distance_summary(summary, unit=1.0):
+    """What a user reads off a distance pass, as Python ints and floats: {"n_solid", "n_present", "n_finite", "max_d2", "max_at",
+    "max" (sqrt(max_d2) * unit; None without a finite texel), "clearance": {label: {"d2", "distance", "at"}} for every label with a
+    present texel at a finite distance, "within": the cumulative histogram -- within[r] texels have a distance of at most r units,
+    for r < 255}."""
+    none = _lib.DISTANCE_NONE
+    top = int(summary["max_d2"])
+    out = {"n_solid": int(summary["n_solid"]), "n_present": int(summary["n_present"]), "n_finite": int(summary["n_finite"]),
+           "max_d2": None if top == none else top, "max_at": tuple(int(v) for v in summary["max_at"]),
+           "max": None if top == none else float(np.sqrt(float(top))) * float(unit), "clearance": {},
+           "within": np.cumsum(np.asarray(summary["hist"], np.uint64)[:255]).tolist()}
+    for l in np.flatnonzero(np.asarray(summary["near_d2"]) != none).tolist():
+        v = int(summary["near_d2"][l])
+        out["clearance"][l] = {"d2": v, "distance": float(np.sqrt(float(v))) * float(unit), "at": tuple(int(x) for x in summary["near_at"][l])}
+    return out
+
+
 PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0     # volym_update's range for the march step
 
 
