@@ -11,6 +11,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from volym_amd import _lib, demo, scene, synth  # noqa: E402
 
+REC = 4         # uint4 records per wave of a variant 2 trace (raymarch_pq.h, the end of the kernel)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -54,7 +56,7 @@ def main():
             t_b = time.perf_counter()
             assert n > 0, n
             if args.kernel == 2:
-                rr = buf[0:2 * 4096:2]
+                rr = buf[0:REC * 4096:REC]
                 t0r = rr[:, 0].astype(np.int64)
                 endr = ((t0r - t0r[rr[:, 1] > 0].min()) & 0xFFFFFFFF) + rr[:, 1].astype(np.int64)
                 wg_ends.append(endr.reshape(-1, 16).max(axis=1) / 100.0)
@@ -75,11 +77,13 @@ def main():
         t_a = time.perf_counter(); ctx.stats_pass(); t_b = time.perf_counter()
         print("host wall of stats_pass: %.1f us ; event-timed plain pass %.1f us" % ((t_b - t_a) * 1e6, 1e3 * float(ctx.time_passes(20).mean())))
     r = buf[:8160 * 4 + 20480]
-    ph = None
+    ph = top = None
     if args.kernel == 2:
-        ph = r[1:2 * 5120 * 2:2]
-        r = r[0:2 * 5120 * 2:2]
+        ph = r[1:REC * 5120 * 2:REC]
+        top = np.concatenate([r[2:REC * 5120 * 2:REC], r[3:REC * 5120 * 2:REC]], axis=1)
+        r = r[0:REC * 5120 * 2:REC]
         ph = ph[r[:, 1] > 0]
+        top = top[r[:, 1] > 0]
     r = r[r[:, 1] > 0]
     t0 = r[:, 0].astype(np.int64)
     t0 = (t0 - t0.min()) & 0xFFFFFFFF
@@ -113,6 +117,22 @@ def main():
         tot = tick.sum(axis=0)
         print("phase shares over all waves (shader ticks): leap %.1f%%  sample %.1f%%  flush %.1f%%  setup+store %.1f%%  ; ticks per us of wave time: %.0f" % (
             *(100.0 * tot / tot.sum()), tot.sum() / (dur[~wrapped].sum() / 100.0)))
+        # The top of an entry and the constant entries (raymarch_pq.h TRACE: from the draw of a ticket to the point where the entry's kind
+        # is known; from there to the issue of a constant entry's last store), against the wave's own time on the same clock
+        ok = ~wrapped & (top[:, 4] > 0) & (top[:, :2] < (1 << 28)).all(axis=1)
+        t_top, t_fill, t_all = (top[ok, k].astype(np.float64) * 16.0 for k in (0, 1, 4))
+        fills, supers = (top[ok, 3] & 0xFFFF).astype(np.float64), (top[ok, 3] >> 16).astype(np.float64)
+        n_entries = tiles[ok].astype(np.float64) + supers      # (8x8 tiles seen by the loop, plus the constant 16x16 entries that leave before it)
+        print("entry tops: %.2f%% of the waves' time (mean per wave %.2f%%), %.0f ticks per entry drawn ; constant entries: %.2f%% of the waves' time, "
+              "%.0f ticks per constant 8x8 or 16x16 entry ; constant 8x8 entries %d, constant 16x16 entries %d ; shader ticks per us %.0f" % (
+                  100.0 * t_top.sum() / t_all.sum(), 100.0 * (t_top / t_all).mean(), t_top.sum() / max(n_entries.sum(), 1.0), 100.0 * t_fill.sum() / t_all.sum(),
+                  t_fill.sum() / max(fills.sum() + supers.sum(), 1.0), int(fills.sum()), int(supers.sum()), t_all.sum() / (dur[ok].sum() / 100.0)))
+        last = top[:, 2].astype(np.int64)
+        tail = np.where(last > 0, dur - last, 0)
+        m = last > 0
+        print("from the end of a wave's last marched entry to its end: mean %.2f us (%.1f%% of the mean wave duration), p50 %.2f p90 %.2f max %.2f ; waves without a "
+              "marched entry: %d, their duration mean %.2f us" % (tail[m].mean() / 100, 100.0 * tail[m].mean() / dur.mean(), np.percentile(tail[m], 50) / 100,
+                                                                 np.percentile(tail[m], 90) / 100, tail[m].max() / 100, int((~m).sum()), (dur[~m].mean() / 100) if (~m).any() else 0.0))
         slow = np.argsort(dur)[-16:]
         ts = tick[slow].sum(axis=0)
         print("slowest 16 waves: leap %.1f%% sample %.1f%% flush %.1f%% setup %.1f%% ; iterations %s ; dur us %s" % (

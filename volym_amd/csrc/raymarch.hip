@@ -1567,8 +1567,8 @@ int volym_dev_read_order(volym_ctx* c, uint32_t* out, uint32_t max_items)
     return static_cast<int>(wl.entries.size());
 }
 
-// One instrumented launch that records, per wave, {start tick, duration ticks (100 MHz), loop iterations, ...} (two
-// uint4 per wave, scripts/wave_trace.py); returns the number of records or a negative error.
+// One instrumented launch that records, per wave, {start tick, duration ticks (100 MHz), loop iterations, ...} (variant 2: four
+// uint4 per wave, the others two; scripts/wave_trace.py); returns the number of records or a negative error.
 int volym_dev_wave_trace(volym_ctx* c, uint32_t* out, uint32_t max_records)
 {
     if (!c || !out) return VOLYM_E_INVALID;
@@ -1580,12 +1580,12 @@ int volym_dev_wave_trace(volym_ctx* c, uint32_t* out, uint32_t max_records)
     for (int i = 0; i < 30 && rc == VOLYM_OK; ++i) rc = launch_march<false, false>(c, s);
     if (rc != VOLYM_OK) return rc;
     feedback_quiesce(s);
-    // records: two per wave of the grid that is really launched (variant 2: the list's grid; variants 0/1: 4 waves per tile)
+    // records: per wave of the grid that is really launched (variant 2: the list's grid, four each; variants 0/1: 4 waves per tile, two each)
     const WorkList& wl = s.lists[s.cur];
     const uint32_t n_items = static_cast<uint32_t>(wl.entries.size());
     const uint32_t pgrid = wl.grid ? wl.grid : std::max(1u, std::min((n_items + PQ_WAVES - 1) / PQ_WAVES, max_grid(c)));
     const uint32_t waves = c->kernel_variant >= 2 ? pgrid * PQ_WAVES : (c->n_local + 64u * 8u) * 4u;   // PQ_WAVES >= every instantiation's WAVES
-    const uint32_t records = waves * 2u;
+    const uint32_t records = waves * (c->kernel_variant >= 2 ? 4u : 2u);
     if (max_records < records) return fail(c, VOLYM_E_INVALID, "volym_dev_wave_trace: buffer too small");
     HIPCHK(c, hipMalloc(&s.d_trace, static_cast<size_t>(records) * sizeof(uint4)));
     HIPCHK(c, hipMemsetAsync(s.d_trace, 0, static_cast<size_t>(records) * sizeof(uint4), s.stream));

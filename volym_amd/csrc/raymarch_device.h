@@ -89,8 +89,32 @@ __device__ __forceinline__ const FrameParams& frame_params_here()
     return *(const FrameParams*)(const char*)p;     // (the address space is inferred back through the cast: s_load, not global_load)
 }
 
+// A buffer that nothing writes while the launch runs (its writers are earlier kernels of the same stream), as a pointer into the constant
+// address space: a read through it at a wave-uniform address is an s_load -- the word arrives in a scalar register through the scalar
+// cache, waits on lgkmcnt only, and never joins the vector-memory queue that the wave's pixel stores are still in.  (A kernel's
+// scalar cache starts out invalidated, so what earlier kernels wrote is seen.)
+template <class T>
+__device__ __forceinline__ const __attribute__((address_space(4))) T* launch_constant(const T* p)
+{
+    return (const __attribute__((address_space(4))) T*)p;
+}
+
+// A word or byte of LDS that other waves of the workgroup write, read or written afresh at the place of the call (volatile), as an
+// LDS access (ds_read / ds_write).  Through a generic pointer the compiler does not always find the address space of a volatile
+// access again and emits a flat one, which waits in the vector-memory queue as well.
+template <class T>
+__device__ __forceinline__ T lds_peek(const T* p)
+{
+    return *(const volatile __attribute__((address_space(3))) T*)p;
+}
+template <class T, class V>
+__device__ __forceinline__ void lds_poke(T* p, V v)
+{
+    *(volatile __attribute__((address_space(3))) T*)p = static_cast<T>(v);
+}
+
 #ifndef VOLYM_DEV_SWITCHES
-#define VOLYM_DEV_SWITCHES 0    // make DEV=1 compiles the FrameParams::dev timing experiments in (scripts/ablate.py --dev)
+#define VOLYM_DEV_SWITCHES 0   // make DEV=1 compiles the FrameParams::dev timing experiments in (scripts/ablate.py --dev)
 #endif
 // The distance field is read from LDS: 32^3 cells of 4 bits are the 16 KB it has there.  A finer grid (64^3, read from global memory
 // through L1 / L2) was measured slower and exists in the development build only: in the product kernels the test

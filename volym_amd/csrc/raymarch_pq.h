@@ -108,11 +108,23 @@ __device__ __forceinline__ uint32_t classify_tile(const FrameParams& fp, const H
     if (out_obj) return in_cube ? TILE_FILL_EMPTY : TILE_HIT_TEST;
     return TILE_MARCH;
 }
-// tile_mask bit of the 8x8 tile (t8x, t8y) (wave-uniform)
+// tile_mask bit of the 8x8 tile (t8x, t8y) (wave-uniform).  The buffer fp.tile_mask names is written by the slot's mask kernel alone,
+// earlier on the slot's own stream (raymarch.hip, ensure_frame_resources: every frame slot has its pair of buffers); a march writes
+// only the other buffer of the pair (tile_mask_spare).  So it is read as tile_depth is: a scalar load
 __device__ __forceinline__ bool tile_mask_bit(const FrameParams& fp, uint32_t t8x, uint32_t t8y)
 {
     const uint32_t bit = t8y * fp.mask_t8x + t8x;
-    return ((fp.tile_mask[bit >> 5] >> (bit & 31u)) & 1u) != 0u;
+    return ((launch_constant(fp.tile_mask)[bit >> 5] >> (bit & 31u)) & 1u) != 0u;
+}
+// whether any of the four 8x8 tiles of the 16x16 tile (tx16, ty16) has its bit set.  A row of the mask is an even number of bits
+// (mask_t8x is twice the frame's 16x16 tiles per row), so each row's pair starts at an even bit and lies in one word: two scalar
+// loads, both issued before either is waited for
+__device__ __forceinline__ bool tile_mask_any16(const FrameParams& fp, uint32_t tx16, uint32_t ty16)
+{
+    const auto* mask = launch_constant(fp.tile_mask);
+    const uint32_t bit0 = ty16 * 2u * fp.mask_t8x + tx16 * 2u, bit1 = bit0 + fp.mask_t8x;
+    const uint32_t w0 = mask[bit0 >> 5], w1 = mask[bit1 >> 5];
+    return (((w0 >> (bit0 & 31u)) | (w1 >> (bit1 & 31u))) & 3u) != 0u;
 }
 // The arguments of volym_raymarch_pq_kernel as the kernel-argument segment lays them out (every argument at its natural alignment, in
 // order: the layout of this struct), for the one thing the kernel needs to know about its own segment: where `fp` sits.
@@ -153,8 +165,14 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     unsigned long long trace_t0 = 0;
     uint32_t trace_iters = 0, trace_flushes = 0, trace_tiles = 0, trace_marched = 0, trace_lanes = 0, trace_accepted = 0, trace_dp_iters = 0;
     unsigned long long tm_leap = 0, tm_samp = 0, tm_flush = 0, tm_mark = 0;
+    // the top of an entry (from the draw of its ticket to the point where its kind -- constant or marched -- is known), the constant
+    // entries themselves (from there to their last store's issue), and when the wave's last marched entry ended
+    unsigned long long tm_grab = 0, tm_kind = 0, tm_top = 0, tm_fill = 0;
+    uint32_t trace_fills = 0, trace_supers = 0, trace_last_march = 0;
+    bool trace_top_open = false;
 #define PQ_TICK() (TRACE ? __builtin_amdgcn_s_memtime() : 0ull)
     if (TRACE) trace_t0 = __builtin_amdgcn_s_memrealtime();
+    const unsigned long long trace_tick0 = PQ_TICK();
 
     __shared__ float4 s_tf_tab[256];
     __shared__ float4 s_lut[TABLE ? 1 : 256];
@@ -206,6 +224,10 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     // time of every workgroup (100 MHz counter).  The host evens out what the counted costs mispredict (worklist.cpp, trim_list).
     uint32_t* const wg_time = reinterpret_cast<uint32_t*>(cost + ((n_items + 1u) & ~1u));
     if (cost && threadIdx.x == 0u) wg_time[gridDim.x * WAVES + blockIdx.x] = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime());
+    // this lane's hull edge: a vector load, the only one of the kernel outside the staging and the marches.  It is issued here and waited
+    // for in front of the barrier, where every wave waits for the staging anyway: behind the barrier no wave waits for ALL its vector
+    // memory again until a march does (the pixel stores of an entry are still under way when the wave starts its next one)
+    const HullEdge hull_edge = load_hull_edge(fp, threadIdx.x & 63u);
     {
         const uint32_t i = threadIdx.x;
         if (i == 0u) s_next_ticket = 0u;
@@ -231,6 +253,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 for (uint32_t k = i; k < n16; k += THREADS) dst[k] = src[k];
         }
     }
+    __builtin_amdgcn_s_waitcnt(0x0f70);                                  // vmcnt(0): the hull edge (above)
     __syncthreads();
     if (VOLYM_DEV_SWITCHES && (fp.dev & 4u)) return;                     // ... + staging
 
@@ -260,11 +283,17 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     const uint32_t n_mine = n_items > blockIdx.x ? (n_items - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u;
     auto grab = [&]() __attribute__((always_inline)) -> uint32_t {
         uint32_t ticket = 0;
+        if (TRACE) { tm_grab = PQ_TICK(); trace_top_open = true; }
         if (lane == 0) ticket = atomicAdd(&s_next_ticket, 1u);
         return __builtin_amdgcn_readfirstlane(ticket);
     };
     const bool culling = !COUNT && fp.cull != 0u;
-    const HullEdge hull_edge = load_hull_edge(fp, lane);
+    auto trace_kind_known = [&]() __attribute__((always_inline)) {
+        if (TRACE) {
+            tm_kind = PQ_TICK();
+            if (trace_top_open) { tm_top += tm_kind - tm_grab; trace_top_open = false; }
+        }
+    };
 
     // ---- cone jobs (IR, use_cone_importance_check): the 8 x N probes of a sample's look-ahead (wgsl:94-139) are the bulk of such a
     // frame, and they sit in the few tiles that show unimportant matter in front of important matter -- one wave per tile walked
@@ -286,8 +315,8 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         uint32_t h = 0, n = 0;
         if (lane == 0u) {
             for (;;) {
-                h = *reinterpret_cast<volatile uint32_t*>(&s_cj_ctl[0]);
-                const uint32_t tl = *reinterpret_cast<volatile uint32_t*>(&s_cj_ctl[1]);
+                h = lds_peek(&s_cj_ctl[0]);
+                const uint32_t tl = lds_peek(&s_cj_ctl[1]);
                 n = min(CJ_RPS, tl - h);
                 if (n == 0u || atomicCAS(&s_cj_ctl[0], h, h + n) == h) break;
             }
@@ -314,7 +343,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 if (st != 0u) {
                     r0 = s_cj[2u * idx]; r1 = s_cj[2u * idx + 1u];
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                    if (lane == glead) *reinterpret_cast<volatile uint32_t*>(&s_cj_flag[idx]) = 0u;
+                    if (lane == glead) lds_poke(&s_cj_flag[idx], 0u);
                     have = true; job_ok = true;
                 } else {
                     __builtin_amdgcn_s_sleep(1);
@@ -386,7 +415,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         const unsigned long long hits = __ballot(hit);
         const bool verdict = CJ == 2 ? hit : ((hits >> (lane & 56u)) & 0xffull) != 0ull;
         if (job_ok && lane == glead)
-            *reinterpret_cast<volatile uint8_t*>(&s_cres[meta & 15u][((meta >> 4) & 3u) * 64u + ((meta >> 6) & 63u)]) = verdict ? 2 : 1;
+            lds_poke(&s_cres[meta & 15u][((meta >> 4) & 3u) * 64u + ((meta >> 6) & 63u)], verdict ? 2 : 1);
         return true;
     };
     // the look-aheads of up to NK samples per lane (sample k at o + d * tsk[k]): submit, serve while waiting, read the verdicts.
@@ -403,7 +432,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         for (int k = 0; k < NK; ++k) {
             const bool nd = need_in[k] && !ahead_cannot_hit(fa, org + dir * tsk[k], dir, t_exit, CJ == 1);   // cannot reach an important voxel: false, unwalked
             need_bits |= nd ? 1u << k : 0u;
-            if (nd) *reinterpret_cast<volatile uint8_t*>(&s_cres[wave][k * 64 + lane]) = 0;
+            if (nd) lds_poke(&s_cres[wave][k * 64 + lane], 0);
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         uint32_t k = 0, todo_bits = need_bits;                                    // todo: not yet in the ring
@@ -415,8 +444,8 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 const uint32_t n = static_cast<uint32_t>(__popcll(m));
                 uint32_t got = 0, tl = 0;
                 if (lane == 0u) {                                                 // as many of the n records as there is room for (serving makes room)
-                    const uint32_t hd = *reinterpret_cast<volatile uint32_t*>(&s_cj_ctl[0]);
-                    tl = *reinterpret_cast<volatile uint32_t*>(&s_cj_ctl[1]);
+                    const uint32_t hd = lds_peek(&s_cj_ctl[0]);
+                    tl = lds_peek(&s_cj_ctl[1]);
                     const uint32_t room = CJ_CAP - min(CJ_CAP, tl - hd);
                     got = min(n, room);
                     if (got != 0u && atomicCAS(&s_cj_ctl[1], tl, tl + got) != tl) got = 0;
@@ -444,12 +473,12 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                                 s_cj[2u * idx] = make_float4(start.x, start.y, start.z, step);
                                 s_cj[2u * idx + 1u] = make_float4(dir.x, dir.y, dir.z, __uint_as_float(wave | (k << 4) | (lane << 6)));
                                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-                                *reinterpret_cast<volatile uint32_t*>(&s_cj_flag[idx]) = 1u;
+                                lds_poke(&s_cj_flag[idx], 1u);
                                 written = true;
                             } else {
                                 __builtin_amdgcn_s_sleep(1);
                                 if (++spins >= (1u << 20)) {                      // cannot happen (see above); never hang: the verdict is "nothing ahead"
-                                    *reinterpret_cast<volatile uint8_t*>(&s_cres[wave][k * 64 + lane]) = 1;
+                                    lds_poke(&s_cres[wave][k * 64 + lane], 1);
                                     written = true;
                                     if (VOLYM_DEV_SWITCHES && (fp.dev & 512u)) atomicAdd(&counters->n_dense, 1ull);
                                 }
@@ -463,14 +492,14 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             } else {
                 bool pending = false;
 #pragma unroll
-                for (int q = 0; q < NK; ++q) pending = pending || (((need_bits >> q) & 1u) != 0u && *reinterpret_cast<volatile uint8_t*>(&s_cres[wave][q * 64 + lane]) == 0);
+                for (int q = 0; q < NK; ++q) pending = pending || (((need_bits >> q) & 1u) != 0u && lds_peek(&s_cres[wave][q * 64 + lane]) == 0);
                 if (__ballot(pending) == 0ull) break;
             }
             if (!cj_serve()) __builtin_amdgcn_s_sleep(1);
             if (VOLYM_DEV_SWITCHES && (fp.dev & 512u) && turns + 1u == (1u << 16) && lane == 0u) atomicAdd(&counters->n_steps, 1ull);       // debug: a look-ahead that gave up
         }
 #pragma unroll
-        for (int q = 0; q < NK; ++q) found[q] = ((need_bits >> q) & 1u) != 0u && *reinterpret_cast<volatile uint8_t*>(&s_cres[wave][q * 64 + lane]) == 2;
+        for (int q = 0; q < NK; ++q) found[q] = ((need_bits >> q) & 1u) != 0u && lds_peek(&s_cres[wave][q * 64 + lane]) == 2;
     };
     // this lane's cone direction (lane & 7) for the wave-wide cone look-ahead, computed where it is used (two gathers
     // from the kernel-argument segment and two multiplies per call: nothing kept live across the march)
@@ -483,11 +512,22 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
       {
         // (the entry's code: worklist_entry.h)
         const size_t list_pos = blockIdx.x + static_cast<size_t>(gridDim.x) * ticket;     // this entry's place in the work list
-        const uint2 entry = ticket < static_cast<uint32_t>(ITEMS_LDS) ? s_items[ticket] : order[list_pos];
-        const uint32_t raw_p = __builtin_amdgcn_readfirstlane(entry.x);
+        // Both words of the entry reach scalar registers without a vector-memory access: a staged entry by one LDS read, an entry
+        // past the staged part (a 4K frame's list) by a scalar load -- the list is read-only for the launch and the place is
+        // wave-uniform.  A branch on the ticket, not a select of two pointers (that was two flat loads, each waited for with
+        // vmcnt(0): the wave's pixel stores of its last entry had to land before it knew what to do next)
+        uint32_t raw_p, entry_xy;
+        if (ticket < static_cast<uint32_t>(ITEMS_LDS)) {
+            const uint2 entry = s_items[ticket];
+            raw_p = __builtin_amdgcn_readfirstlane(entry.x);
+            entry_xy = __builtin_amdgcn_readfirstlane(entry.y);
+        } else {
+            const auto* words = launch_constant(reinterpret_cast<const uint32_t*>(order));      // (one s_load_dwordx2)
+            raw_p = words[2u * list_pos];
+            entry_xy = words[2u * list_pos + 1u];
+        }
         if (raw_p == PQ_NO_ITEM) continue;
-        // the 16x16 tile's position, worked out by the host when it dealt the list (no integer division here)
-        const uint32_t entry_xy = __builtin_amdgcn_readfirstlane(entry.y);
+        // entry_xy: the 16x16 tile's position, worked out by the host when it dealt the list (no integer division here)
         const uint32_t tx = entry_xy & 0xffffu, ty = entry_xy >> 16;
         // counted cost of this list entry, reported by list position (one writer per entry: no atomics, nothing to reset); the
         // host's feedback thread maps positions back to tiles (raymarch.hip, "cost feedback")
@@ -506,9 +546,9 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
             const uint32_t tx16 = tx, ty16 = ty;
             bool masked16 = false;
             if (culling && (fe.cull & CULL_TILE_MASK))
-                masked16 = !(tile_mask_bit(fe, tx16 * 2u, ty16 * 2u) || tile_mask_bit(fe, tx16 * 2u + 1u, ty16 * 2u) ||
-                             tile_mask_bit(fe, tx16 * 2u, ty16 * 2u + 1u) || tile_mask_bit(fe, tx16 * 2u + 1u, ty16 * 2u + 1u));
+                masked16 = !tile_mask_any16(fe, tx16, ty16);
             const uint32_t cls = culling ? classify_tile(fe, hull_edge, lane, static_cast<float>(tx16 * 16u), static_cast<float>(ty16 * 16u), 15.0f, masked16) : TILE_MARCH;
+            trace_kind_known();
             if (cls >= TILE_FILL_EMPTY) {
                 const uint32_t packed = cls == TILE_FILL_MISS ? 0xff000000u : 0u;
                 if (flags & F_RASTER) {
@@ -532,6 +572,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                     }
                 }
                 if (cost && lane == 0) cost[list_pos] = 0;
+                if (TRACE) { tm_fill += PQ_TICK() - tm_kind; trace_supers++; }
                 continue;
             }
             n_sub = 4;
@@ -560,6 +601,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         if (culling && !dp) {
             const bool masked8 = (fe.cull & CULL_TILE_MASK) != 0u && !tile_mask_bit(fe, tx * 2u + (sub & 1u), ty * 2u + (sub >> 1));
             tclass = classify_tile(fe, hull_edge, lane, static_cast<float>(tx * 16u + ((sub & 1u) << 3)), static_cast<float>(ty * 16u + ((sub >> 1) << 3)), 7.0f, masked8);
+            trace_kind_known();
             if (tclass >= TILE_FILL_EMPTY) {            // no ray of this tile can differ from the constant
                 const uint32_t packed = tclass == TILE_FILL_MISS ? 0xff000000u : 0u;     // (0,0,0,1) wgsl:239 / (0,0,0,0) wgsl:328
                 if (flags & F_RASTER) {
@@ -571,9 +613,11 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
                 } else {
                     out_shard[static_cast<size_t>(local_tile) * 256u + sub * 64u + sub_lane] = in_frame ? packed : 0u;
                 }
+                if (TRACE) { tm_fill += PQ_TICK() - tm_kind; trace_fills++; }
                 continue;                                    // a constant tile costs (next to) nothing
             }
         }
+        if (TRACE && trace_top_open) trace_kind_known();     // (a depth-parallel entry is marched: known from its code)
         if (TRACE) trace_marched++;
 
         acc_r[lane] = 0u; acc_g[lane] = 0u; acc_b[lane] = 0u;
@@ -1381,6 +1425,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         if (IR) entry_cost += (la_rounds - la_at_start) * VOLYM_COST_LA;           // a round of 64 chains of N probes
         if (CJ == 1) entry_cost += (cj_count - cj_at_start) * VOLYM_COST_CJ / 8u;   // a cone job of 8 samples is ~14 units of whichever wave walks it
         if (CJ == 2) entry_cost += (cj_count - cj_at_start) * VOLYM_COST_LA / 64u;  // 64 chains: one round
+        if (TRACE) trace_last_march = static_cast<uint32_t>(__builtin_amdgcn_s_memrealtime() - trace_t0);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
       }
@@ -1394,7 +1439,7 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
         if (lane == 0u) atomicSub(&s_cj_ctl[2], 1u);
         for (uint32_t turns = 0; turns < (1u << 20); ++turns) {
             if (cj_serve()) continue;
-            if (*reinterpret_cast<volatile uint32_t*>(&s_cj_ctl[2]) == 0u) break;
+            if (lds_peek(&s_cj_ctl[2]) == 0u) break;
             __builtin_amdgcn_s_sleep(4);
         }
     }
@@ -1402,10 +1447,15 @@ __global__ __launch_bounds__(WAVES * 64) void volym_raymarch_pq_kernel(
     if (TRACE) for (int sft = 32; sft > 0; sft >>= 1) trace_accepted += __shfl_xor(trace_accepted, sft, 64);
     if (TRACE && lane == 0) {
         const unsigned long long t1 = __builtin_amdgcn_s_memrealtime();
-        const size_t rec = (static_cast<size_t>(blockIdx.x) * WAVES + wave) * 2u;
+        const size_t rec = (static_cast<size_t>(blockIdx.x) * WAVES + wave) * 4u;
         trace[rec] = make_uint4(static_cast<uint32_t>(trace_t0), static_cast<uint32_t>(t1 - trace_t0), trace_iters | (trace_tiles << 16), min(trace_flushes, 0xfffu) | (min(trace_marched, 15u) << 12) | (min(trace_dp_iters, 0xffffu) << 16));
         trace[rec + 1] = make_uint4(static_cast<uint32_t>(tm_leap >> 4), static_cast<uint32_t>((tm_samp - tm_flush) >> 4), static_cast<uint32_t>(tm_flush >> 4),
                                     min(trace_lanes, 0xffffu) | (min(trace_accepted, 0xffffu) << 16));   // lanes active at the loop top, samples accepted
+        // entry tops and constant entries (shader ticks / 16), the end of the last marched entry (100 MHz ticks after the wave's start; 0: none),
+        // constant 8x8 entries | constant 16x16 entries << 16
+        trace[rec + 2] = make_uint4(static_cast<uint32_t>(tm_top >> 4), static_cast<uint32_t>(tm_fill >> 4), trace_last_march,
+                                    min(trace_fills, 0xffffu) | (min(trace_supers, 0xffffu) << 16));
+        trace[rec + 3] = make_uint4(static_cast<uint32_t>((PQ_TICK() - trace_tick0) >> 4), 0u, 0u, 0u);     // the wave's whole time on the phases' clock
     }
     if (COUNT) {
         unsigned long long v[5] = {n_vol, n_imp, n_steps, n_dense, n_hit};
