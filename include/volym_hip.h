@@ -28,7 +28,7 @@
  *     volym_components_pass blocks only when it has to allocate or grow its buffers; volym_read_components,
  *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name);
  *     volym_distance_pass blocks only when it has to allocate or grow its buffers; volym_read_distance, volym_read_distance_map
- *     and volym_distance_at block.
+ *     and volym_distance_at block; volym_edit_labels is a set-up call and blocks like volym_set_*.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -935,6 +935,58 @@ int   volym_distance_at(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, uint
  * volym_distance_summary) and the map of the latest pass's box. */
 void* volym_distance_device_ptr(volym_ctx* ctx);
 void* volym_distance_map_device_ptr(volym_ctx* ctx);
+
+/* --- editing labels (new; the reference has none) ------------------------------------------------------------------ */
+/* Acting on what the passes above found: relabel texels on the device by a table, a density window, a piece of the latest
+ * components pass and a band of the latest distance map.  The context ends up byte for byte where a context handed the edited labels
+ * (volym_set_labels, then the same table, mask, box and plane) would be.
+ *   The rule (integers only; scene.relabel_volume of the Python package is its host twin, equal in every byte).  A texel t with label
+ * l becomes to[l] iff all of these hold: t lies in box; to[l] != l; its density byte lies in [min_byte, max_byte] -- the scene byte
+ * as it stands, with UNCUT the uncut copy as volym_measure_pass reads it; with IDS, its id in the id volume of the latest components
+ * pass is not VOLYM_COMPONENT_NONE and lies in [id_lo, id_hi] (with IDS_EXCEPT as well: outside that range); with DISTANCE, its D in
+ * the latest distance map is not VOLYM_DISTANCE_NONE and lies in [d2_lo, d2_hi].  Ids and distances are the snapshots they are: a
+ * snapshot may be applied again after an edit, without a new pass.  Every texel is decided from the bytes before the edit: the result
+ * does not depend on the device layout or on the order of the workgroups.  DRY_RUN fills the result and writes nothing. */
+enum { VOLYM_RELABEL_UNCUT = 1, VOLYM_RELABEL_IDS = 2, VOLYM_RELABEL_IDS_EXCEPT = 4, VOLYM_RELABEL_DISTANCE = 8, VOLYM_RELABEL_DRY_RUN = 16 };   /* flags */
+typedef struct volym_relabel {
+    uint32_t box[6];            /* {x0, y0, z0, x1, y1, z1}: lo inclusive, hi exclusive, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;   /* 0..255, min <= max: the density window; 0..255 = no window */
+    uint8_t  to[256];           /* old label -> new label; to[l] == l: label l is not touched */
+    uint32_t id_lo, id_hi;      /* IDS: lo <= hi */
+    uint32_t d2_lo, d2_hi;      /* DISTANCE: lo <= hi */
+} volym_relabel;                /* 308 bytes */
+struct volym_relabel_result {
+    uint64_t changed;           /* texels whose label changed (with DRY_RUN: would change) */
+    uint64_t left[256];         /* texels that had this label and lost it */
+    uint64_t arrived[256];      /* texels that got this label */
+    uint32_t box[6];            /* hull of the changed texels, lo inclusive, hi exclusive; all 0 when changed == 0 */
+};                              /* 4128 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_relabel) == 308, "volym_relabel is 308 bytes");
+static_assert(sizeof(struct volym_relabel_result) == 4128, "volym_relabel_result is 4128 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_relabel) == 308, "volym_relabel is 308 bytes");
+_Static_assert(sizeof(struct volym_relabel_result) == 4128, "volym_relabel_result is 4128 bytes");
+#endif
+/* The edit: a blocking set-up call, like volym_set_segment_visibility (it waits for the frames in flight; the kernel runs on the
+ * first slot's stream, behind any components or distance pass).  With changed == 0, or DRY_RUN, nothing else is touched: a surface
+ * pass stays valid for volym_surface_faces_pass.  Otherwise the label counts and boxes (volym_label_counts) are those
+ * volym_set_labels of the edited labels leaves, density and importances follow under the mask, box and plane, and a surface pass is
+ * stale.  out may be NULL.  A failure after the kernel has stored leaves the context asking for volym_set_volume.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_relabel_check refuses, IDS or DISTANCE with a box that reaches outside the box
+ * of that pass.  VOLYM_E_STATE: no volume; no labels of the volume's dimensions; labels (or importances of the volume's dimensions)
+ * in the other device layout than the volume; IDS or DISTANCE without such a pass since volym_set_volume.
+ *   Ids and maps belong to one context: the native multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_edit_labels(volym_ctx* ctx, const volym_relabel* r, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, IDS_EXCEPT without IDS, a window without min_byte <= max_byte <= 255, IDS with id_lo > id_hi, DISTANCE with d2_lo > d2_hi.
+ * An empty box is valid: nothing changes.  Pure host arithmetic. */
+int   volym_relabel_check(const volym_relabel* r, const uint32_t dims[3]);
+/* The labels as they stand, blocking: those of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi <= the labels'
+ * dimensions; NULL: the whole label volume), box-linear in the sub-box with x fastest, whatever the device layout.
+ * VOLYM_E_STATE: no labels.  VOLYM_E_INVALID: NULL ctx, a sub-box outside the labels, NULL output for a sub-box with texels. */
+int   volym_read_labels(volym_ctx* ctx, const uint32_t sub[6], uint8_t* out);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

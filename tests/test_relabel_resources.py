@@ -1,0 +1,66 @@
+"""What the compiler made of the relabel kernel (no GPU: any machine with hipcc).
+
+scene_bytes.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
+tests/test_measure_resources.py compiles it.  The four instantiations of volym_relabel_kernel<IDS, DISTANCE> must have no scratch, at
+most 128 VGPRs and at most 64 KB of LDS.  The figures go to profiles/relabel_kernel_resources.txt.
+"""
+import os
+import re
+import subprocess
+
+import pytest
+
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+
+OUT = os.path.join(ROOT, "profiles", "relabel_kernel_resources.txt")
+
+pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not installed")
+
+
+@pytest.fixture(scope="module")
+def scene_unit(tmp_path_factory):
+    out = os.path.join(str(tmp_path_factory.mktemp("relabel")), "scene_bytes.s")
+    cmd = [HIPCC] + makefile_flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", os.path.join(CSRC, "scene_bytes.hip"), "-o", out]
+    p = subprocess.run(cmd, capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return remarks(p.stderr)
+
+
+def instantiations(res):
+    """{(ids, distance): figures} of the volym_relabel_kernel<IDS, DISTANCE> instantiations"""
+    out = {}
+    for name, r in res.items():
+        m = re.search(r"volym_relabel_kernelILb([01])ELb([01])E", name)
+        if m:
+            out[(m.group(1) == "1", m.group(2) == "1")] = r
+    return out
+
+
+def test_the_unit_includes_the_new_header_and_no_other_unit_does():
+    assert os.path.exists(os.path.join(CSRC, "relabel_kernels.h")) and os.path.exists(os.path.join(CSRC, "relabel.inc"))
+    unit = open(os.path.join(CSRC, "scene_bytes.hip")).read()
+    assert unit.index('#include "scene_kernels.h"') < unit.index('#include "relabel_kernels.h"') < unit.index('#include "relabel.inc"')
+    others = [f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".hpp", ".inc", ".cpp")) and f != "scene_bytes.hip"]
+    for f in others:                                                  # scene_bytes.hip stays the only unit with these kernels
+        text = open(os.path.join(CSRC, f)).read()
+        assert '#include "relabel_kernels.h"' not in text and '#include "relabel.inc"' not in text, f
+
+
+def test_the_four_instantiations_have_no_scratch_128_vgprs_and_64_kb_of_lds(scene_unit):
+    inst = instantiations(scene_unit)
+    assert set(inst) == {(False, False), (False, True), (True, False), (True, True)}, list(scene_unit)
+    lines = ["volym_relabel_kernel<IDS, DISTANCE> (scene_bytes.hip), hipcc with the Makefile's flags, -Rpass-analysis=kernel-resource-usage",
+             "written by tests/test_relabel_resources.py; bar for all four: scratch 0, VGPRs <= 128, LDS <= 65536", ""]
+    for (ids, distance), r in sorted(inst.items()):
+        lines.append("relabel_kernel<%-5s, %-5s>  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (
+            str(ids).lower(), str(distance).lower(), r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
+    print("\n".join(lines))
+    try:
+        with open(OUT, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    except OSError:
+        pass                                  # a read-only checkout still checks the bar
+    for key, r in inst.items():
+        assert r["scratch"] == 0, (key, r)
+        assert r["vgpr"] <= 128, (key, r)
+        assert r["lds"] <= 65536, (key, r)

@@ -26,6 +26,10 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
+--relabel FROM[,FROM...]:TO, --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
+each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
+--labels (demo.Simple.save_labels).
 """
 import argparse
 import csv
@@ -273,6 +277,47 @@ def _distance_table(s, inside):
     return "\n".join(lines)
 
 
+def _segment_arg(text):
+    """a segment on the command line: a label value or a name / id of the segments JSON"""
+    return int(text) if text.isdigit() else text
+
+
+def _name_and(text, option, what, number=float):
+    """--grow NAME:R, --split-at X,Y:TO -> (left part, right part)"""
+    left, sep, right = text.rpartition(":")
+    if not sep or not left or not right:
+        raise SystemExit("%s: %s" % (option, what))
+    try:
+        return left, (number(right) if number is not None else right)
+    except ValueError:
+        raise SystemExit("%s: %s" % (option, what))
+
+
+def _label_edits(ctx, d, args):
+    """the label edits of the command line on the scene as it stands (demo.Simple.relabel, split_at, keep_largest, grow, shrink):
+    [(option, result)]"""
+    out = []
+    try:
+        if getattr(args, "relabel", None):
+            froms, to = _name_and(args.relabel, "--relabel", "FROM[,FROM...]:TO -- label values or segment names", None)
+            out.append(("relabel", d.relabel(ctx, {_segment_arg(f): _segment_arg(to) for f in froms.split(",") if f})))
+        if getattr(args, "split_at", None):
+            at, to = _name_and(args.split_at, "--split-at", "X,Y:TO -- a pixel and the segment its piece becomes", None)
+            p = d.split_at(ctx, *_outline_at_arg(at, "--split-at"), _segment_arg(to))
+            out.append(("split_at", p["relabel"]))
+        if getattr(args, "keep_largest", None):
+            out.append(("keep_largest", d.keep_largest(ctx, _segment_arg(args.keep_largest))))
+        if getattr(args, "grow", None):
+            name, r = _name_and(args.grow, "--grow", "NAME:R -- a segment and a margin in texels")
+            out.append(("grow", d.grow(ctx, _segment_arg(name), r)))
+        if getattr(args, "shrink", None):
+            name, r = _name_and(args.shrink, "--shrink", "NAME:R -- a segment and a margin in texels")
+            out.append(("shrink", d.shrink(ctx, _segment_arg(name), r)))
+    except ValueError as e:
+        raise SystemExit("label edit: %s" % e)
+    return out
+
+
 def run_simple(args):
     W, H = args.width, args.height
     raw, labels, segments, what = _load_assets(args)
@@ -294,6 +339,11 @@ def run_simple(args):
             # click to cut: the plane through what the pixel shows, facing the eye; the PNG is the frame after the cut
             plane = d.clip_at(ctx, *_outline_at_arg(args.clip_at, "--clip-at"))
             clipped = {"clip_plane": None if plane is None else {"n": list(plane[0]), "d": plane[1]}}
+            d.compute_pass(ctx)
+            ctx.sync()
+        # label edits, in the order relabel, split, keep the largest, grow, shrink; the PNG is the frame after them
+        edits = _label_edits(ctx, d, args)
+        if edits:
             d.compute_pass(ctx)
             ctx.sync()
         frame = ctx.read_rgba8()
@@ -360,9 +410,15 @@ def run_simple(args):
                 distances["hist"] = [int(v) for v in ctx.read_distance()["hist"]]
             except ValueError as e:
                 raise SystemExit("--distance: %s" % e)
+        labels_out = d.save_labels(ctx, args.labels_out) if getattr(args, "labels_out", None) else None
     path = args.screenshot or ("screenshot_%d.png" % int(time.time()))
     image.write_png(path, frame)
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
+    for option, result in edits:
+        import json
+        print(json.dumps({option: result}))      # one line per label edit: texels changed, per label left and arrived, the hull
+    if labels_out is not None:
+        print("labels: %d bytes -> %s" % (labels_out, args.labels_out))
     if distances is not None:
         import json
         print(_distance_table(distances, inside))
@@ -518,6 +574,12 @@ def main(argv=None):
     run.add_argument("--distance-inside", action="store_true", help="with --distance: distances inside the set, to its complement (thickness)")
     run.add_argument("--surface-out", metavar="FILE.stl|.obj", help="also write the surface of those segments together as a binary STL or an OBJ mesh")
     run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
+    run.add_argument("--relabel", help="FROM[,FROM...]:TO: relabel the segments FROM (label values or names) to TO on the device before the picture")
+    run.add_argument("--split-at", help="X,Y:TO: the piece of the segment pixel (X, Y) shows becomes segment TO (a new name gets an entry)")
+    run.add_argument("--keep-largest", help="NAME: keep the largest piece of the segment, its other pieces become unlabelled")
+    run.add_argument("--grow", help="NAME:R: grow the segment by R texels into the unlabelled texels")
+    run.add_argument("--shrink", help="NAME:R: shrink the segment by R texels")
+    run.add_argument("--labels-out", help="FILE: write the labels as they stand after the edits, raw bytes in the orientation of --labels")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")
     b.add_argument("--width", type=int, default=1024); b.add_argument("--height", type=int, default=768)   # src/main.rs:356-359

@@ -264,6 +264,33 @@ DISTANCE_SUMMARY_DTYPE = np.dtype([("n_solid", "<u8"), ("n_present", "<u8"), ("n
                                    ("near_d2", "<u4", (256,)), ("near_at", "<u4", (256, 3)), ("hist", "<u8", (256,))])
 
 
+RELABEL_UNCUT, RELABEL_IDS, RELABEL_IDS_EXCEPT, RELABEL_DISTANCE, RELABEL_DRY_RUN = 1, 2, 4, 8, 16   # volym_relabel.flags
+
+
+class Relabel(C.Structure):
+    """volym_relabel (include/volym_hip.h): box, flags, density window, label table, id range and distance band of one edit, 308 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("to", C.c_uint8 * 256),
+        ("id_lo", C.c_uint32),
+        ("id_hi", C.c_uint32),
+        ("d2_lo", C.c_uint32),
+        ("d2_hi", C.c_uint32),
+    ]
+
+
+class RelabelResult(C.Structure):
+    """volym_relabel_result (include/volym_hip.h): texels changed, per label those that left and arrived, and their hull, 4128 bytes"""
+    _fields_ = [("changed", C.c_uint64), ("left", C.c_uint64 * 256), ("arrived", C.c_uint64 * 256), ("box", C.c_uint32 * 6)]
+
+
+# the result as a NumPy structured dtype (GpuContext.edit_labels, scene.relabel_volume)
+RELABEL_RESULT_DTYPE = np.dtype([("changed", "<u8"), ("left", "<u8", (256,)), ("arrived", "<u8", (256,)), ("box", "<u4", (6,))])
+
+
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
     _fields_ = [
@@ -427,6 +454,9 @@ SIGNATURES = {
     "volym_distance_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "volym_distance_device_ptr": (C.c_void_p, [_ctx]),
     "volym_distance_map_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_edit_labels": (C.c_int, [_ctx, C.POINTER(Relabel), C.POINTER(RelabelResult)]),
+    "volym_relabel_check": (C.c_int, [C.POINTER(Relabel), C.POINTER(C.c_uint32)]),
+    "volym_read_labels": (C.c_int, [_ctx, C.POINTER(C.c_uint32), _u8p]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

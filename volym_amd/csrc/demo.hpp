@@ -152,6 +152,36 @@ public:
         if (!labels_on_device_) set_labels(ctx, a);
         ctx.check(volym_set_segment_importances(ctx.handle(), table.data()));
     }
+    // New: relabel segments on the device by the table alone (volym_edit_labels): every texel of a segment in `from` (names, ids or
+    // label values as text) gets the label of `to`, which must name a segment of the table or be a label value.  The importances are
+    // mapped from the labels through the segments' table first, so that they follow the edit.
+    volym_relabel_result relabel(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& from, const std::string& to)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "relabel: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        volym_relabel r{};
+        r.box[3] = a.nx; r.box[4] = a.ny; r.box[5] = a.nz;
+        r.max_byte = 255u;
+        for (int l = 0; l < 256; ++l) r.to[l] = static_cast<uint8_t>(l);
+        const uint8_t target = label_value_of(a, to);
+        for (const std::string& s : from) r.to[label_value_of(a, s)] = target;
+        volym_relabel_result out{};
+        ctx.check(volym_edit_labels(ctx.handle(), &r, &out));
+        records_current_ = false;
+        return out;
+    }
+    // New: the labels as they stand on the device, as raw bytes in the orientation prepare_volume read (the y flip undone)
+    std::vector<uint8_t> labels_from_device(const GpuContext& ctx, const SimpleAssets& a)
+    {
+        if (!labels_on_device_) set_labels(ctx, a);
+        std::vector<uint8_t> prepared(static_cast<size_t>(a.nx) * a.ny * a.nz), raw(prepared.size());
+        ctx.check(volym_read_labels(ctx.handle(), nullptr, prepared.data()));
+        const size_t row = a.nx;
+        for (size_t z = 0; z < a.nz; ++z)
+            for (size_t y = 0; y < a.ny; ++y)
+                std::copy(prepared.begin() + (z * a.ny + y) * row, prepared.begin() + (z * a.ny + y + 1) * row, raw.begin() + (z * a.ny + (a.ny - 1 - y)) * row);
+        return raw;
+    }
     // New: axis-aligned crop box in unit-cube coordinates in [0, 1] (the cube the camera orbits; y as the prepared, flipped volume
     // has it): texel = floor(p * n + 0.5) clamped to [0, n].  Density and importances outside it count as 0 (volym_set_crop_box).
     void set_crop(const GpuContext& ctx, const SimpleAssets& a, const float lo01[3], const float hi01[3])

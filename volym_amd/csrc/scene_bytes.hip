@@ -2,7 +2,8 @@
 // one transition (retarget) that keeps density and importances cut to the crop box, the clip plane and the segment mask; the C ABI entry
 // points of all of these.  The frame loop (raymarch.hip) reads what this unit writes; what the two need from each other is
 // declared in context.hpp.  Everything here is blocking set-up path, except the measure pass at the end (measure.inc, measure_kernels.h),
-// which only reads these bytes and is enqueue-only.
+// which only reads these bytes and is enqueue-only, and the label edit after it (relabel.inc, relabel_kernels.h), which rewrites
+// labels in place and carries density and importances along by the same invariant.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 #include "context.hpp"
 #include "scene_kernels.h"
 #include "measure_kernels.h"
+#include "relabel_kernels.h"
 
 using namespace volym;
 
@@ -754,6 +756,35 @@ static void important_texel_box(const uint8_t* imp, uint32_t nx, uint32_t ny, ui
     lo[0] = x0; lo[1] = y0; lo[2] = z0; hi[0] = x1; hi[1] = y1; hi[2] = z1;
 }
 
+// label_count and label_box of the labels on the device: one pass of volym_label_stats_kernel on slot 0's stream, waited for.  On
+// failure the two are left as they were.
+static hipError_t scan_label_stats(volym_ctx* c)
+{
+    const uint64_t n_chunks = (layout_bytes(c->labels_bricked, c->lnx, c->lny, c->lnz) + 15u) / 16u;
+    // counts, then boxes: lo = INT_MAX, hi = -1 until a voxel says otherwise
+    std::vector<unsigned char> init(256 * sizeof(unsigned long long) + 256 * 6 * sizeof(int));
+    int* boxes = reinterpret_cast<int*>(init.data() + 256 * sizeof(unsigned long long));
+    for (int l = 0; l < 256; ++l)
+        for (int i = 0; i < 6; ++i) boxes[l * 6 + i] = i < 3 ? INT32_MAX : -1;
+    unsigned char* d_stats = nullptr;
+    const hipStream_t stream = c->slot0().stream;
+    hipError_t e = hipMalloc(&d_stats, init.size());
+    if (e == hipSuccess) e = hipMemcpy(d_stats, init.data(), init.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(volym_label_stats_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels),
+                           reinterpret_cast<unsigned long long*>(d_stats), reinterpret_cast<int*>(d_stats + 256 * sizeof(unsigned long long)),
+                           c->lnx, c->lny, c->lnz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(init.data(), d_stats, init.size(), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d_stats);
+    if (e != hipSuccess) return e;
+    std::memcpy(c->label_count, init.data(), sizeof c->label_count);
+    std::memcpy(c->label_box, boxes, sizeof c->label_box);
+    return hipSuccess;
+}
+
 // ---- C ABI: what each call makes of the scene's (box, plane, mask) ----------------------------------------------------
 //   volym_set_crop_box(lo, hi)                  current -> (lo, hi), current plane and mask density and importances
 //   volym_set_clip_plane(n, d)                  current -> current box and mask, (n, d)     density and importances
@@ -908,31 +939,11 @@ int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t 
     if (rc != VOLYM_OK) { if (c->d_labels) (void)hipFree(c->d_labels); c->d_labels = nullptr; return rc; }
     c->lnx = nx; c->lny = ny; c->lnz = nz;
     c->labels_bricked = want_bricked(c, nx, ny, nz);
-    const uint64_t n_chunks = (layout_bytes(c->labels_bricked, nx, ny, nz) + 15u) / 16u;
-    // counts, then boxes: lo = INT_MAX, hi = -1 until a voxel says otherwise
-    std::vector<unsigned char> init(256 * sizeof(unsigned long long) + 256 * 6 * sizeof(int));
-    int* boxes = reinterpret_cast<int*>(init.data() + 256 * sizeof(unsigned long long));
-    for (int l = 0; l < 256; ++l)
-        for (int i = 0; i < 6; ++i) boxes[l * 6 + i] = i < 3 ? INT32_MAX : -1;
-    unsigned char* d_stats = nullptr;
-    const hipStream_t stream = c->slot0().stream;
-    hipError_t e = hipMalloc(&d_stats, init.size());
-    if (e == hipSuccess) e = hipMemcpy(d_stats, init.data(), init.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(volym_label_stats_kernel, dim3(stream_grid(c, n_chunks)), dim3(256), 0, stream, reinterpret_cast<const uint4*>(c->d_labels),
-                           reinterpret_cast<unsigned long long*>(d_stats), reinterpret_cast<int*>(d_stats + 256 * sizeof(unsigned long long)),
-                           nx, ny, nz, c->labels_bricked ? 1u : 0u, static_cast<uint32_t>(n_chunks));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(init.data(), d_stats, init.size(), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_stats);
+    const hipError_t e = scan_label_stats(c);
     if (e != hipSuccess) {
         (void)hipFree(c->d_labels); c->d_labels = nullptr;
         return fail(c, VOLYM_E_HIP, std::string("volym_set_labels: ") + hipGetErrorString(e));
     }
-    std::memcpy(c->label_count, init.data(), sizeof c->label_count);
-    std::memcpy(c->label_box, boxes, sizeof c->label_box);
     return VOLYM_OK;
 }
 
@@ -981,3 +992,6 @@ int volym_label_counts(volym_ctx* c, uint64_t counts[256])
 
 // ---- measuring segments ---------------------------------------------------------------------------------------------------
 #include "measure.inc"
+
+// ---- editing labels -------------------------------------------------------------------------------------------------------
+#include "relabel.inc"

@@ -14,6 +14,8 @@
 //   prints each segment's connected pieces: how many, the largest, and the ten largest with root and box (Simple::components);
 //   --distance [NAME,...][:MIN_BYTE] prints the distance map's summary for the union of those segments -- solid texels, the deepest
 //   point, the nearest texel of every segment -- and --distance-inside measures inside the set instead (Simple::distance).
+//   --relabel FROM[,FROM...]:TO relabels those segments on the device before the picture (Simple::relabel) and prints what changed;
+//   --labels-out FILE writes the labels as they stand afterwards, raw bytes in the orientation of --labels.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -59,6 +61,9 @@ struct Options {
     float project_step = 0.0f;     // 0: the march's dense step
     bool measure = false;          // --measure [NAME,...]: also print the table of segment statistics (run simple)
     std::vector<std::string> measure_names;
+    std::vector<std::string> relabel_from;   // --relabel FROM[,FROM...]:TO: relabel segments on the device before the picture (run simple)
+    std::string relabel_to;
+    std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
     std::vector<std::string> surface_names;
     uint32_t surface_min_byte = 1;
@@ -190,6 +195,8 @@ int run_simple(const Options& o)
     if (o.crop) demo.set_crop(ctx, assets, o.crop_lo, o.crop_hi);
     if (o.clip) demo.set_clip_plane(ctx, assets, o.clip_normal, o.clip_point);
     if (!o.hide.empty()) demo.set_hidden(ctx, assets, o.hide);
+    volym_relabel_result relabelled{};
+    if (!o.relabel_to.empty()) relabelled = demo.relabel(ctx, assets, o.relabel_from, o.relabel_to);
     demo.update_gpu_state(ctx, state);
     demo.compute_pass(ctx);
     ctx.check(volym_sync(ctx.handle()));
@@ -200,6 +207,21 @@ int run_simple(const Options& o)
     f << "P6\n" << W << ' ' << H << "\n255\n";
     for (size_t i = 0; i < static_cast<size_t>(W) * H; ++i) f.write(reinterpret_cast<const char*>(&rgba[4 * i]), 3);
     std::printf("run simple: %s, %ux%u -> %s\n", what.c_str(), W, H, path.c_str());
+    if (!o.relabel_to.empty()) {
+        std::printf("relabel: %llu texels changed", static_cast<unsigned long long>(relabelled.changed));
+        if (relabelled.changed != 0u)
+            std::printf(", box [%u,%u,%u)..[%u,%u,%u)", relabelled.box[0], relabelled.box[1], relabelled.box[2], relabelled.box[3], relabelled.box[4], relabelled.box[5]);
+        for (int l = 0; l < 256; ++l)
+            if (relabelled.left[l] != 0u || relabelled.arrived[l] != 0u)
+                std::printf("; label %d: -%llu +%llu", l, static_cast<unsigned long long>(relabelled.left[l]), static_cast<unsigned long long>(relabelled.arrived[l]));
+        std::printf("\n");
+    }
+    if (!o.labels_out.empty()) {
+        const std::vector<uint8_t> raw = demo.labels_from_device(ctx, assets);
+        std::ofstream lf(o.labels_out, std::ios::binary);
+        lf.write(reinterpret_cast<const char*>(raw.data()), static_cast<std::streamsize>(raw.size()));
+        std::printf("labels: %zu bytes -> %s\n", raw.size(), o.labels_out.c_str());
+    }
     if (o.slice_axis >= 0) {
         // the slice view beside the frame: transfer-function colours, segments overlaid, cut texels tinted
         SliceView view;
@@ -347,6 +369,19 @@ int main(int argc, char** argv)
                 o.slice_axis = static_cast<int>(axis);
                 o.slice_index = static_cast<uint32_t>(index);
             }
+            else if (a == "--relabel") {
+                const std::string v = next();
+                const size_t colon = v.rfind(':');
+                if (colon == std::string::npos || colon == 0u || colon + 1u >= v.size()) throw Error(VOLYM_E_INVALID, "--relabel: FROM[,FROM...]:TO -- label values or segment names");
+                o.relabel_to = v.substr(colon + 1u);
+                size_t pos = 0;
+                while (pos < colon) {
+                    const size_t comma = std::min(v.find(',', pos), colon);
+                    if (comma > pos) o.relabel_from.push_back(v.substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+            }
+            else if (a == "--labels-out") o.labels_out = next();
             else if (a == "--measure") {
                 o.measure = true;
                 if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") {
@@ -443,7 +478,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--labels-out file]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

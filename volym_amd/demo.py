@@ -102,6 +102,7 @@ class GpuContext:
         if v.size != nx * ny * nz:
             raise ValueError("labels have %d bytes, dims say %d" % (v.size, nx * ny * nz))
         self._ck(_lib.lib().volym_set_labels(self.handle, scene._u8p(v), nx, ny, nz))
+        self._label_dims = (int(nx), int(ny), int(nz))
 
     def set_segment_importances(self, table):
         """importance = table[label] for every voxel, on the device (table: 256 bytes, scene.segment_table)."""
@@ -537,6 +538,32 @@ class GpuContext:
     def distance_map_device_ptr(self):
         """The map of the latest distance pass in device memory (None before any)."""
         return _lib.lib().volym_distance_map_device_ptr(self.handle)
+
+    # ---- editing labels --------------------------------------------------------------------------
+    def edit_labels(self, relabel):
+        """One edit of the labels on the device (include/volym_hip.h volym_edit_labels; scene.relabel_volume is its definition):
+        texels of the request's box become to[label] where the table, the density window, the ids of the latest components pass
+        and the latest distance map say so.  `relabel` is a scene.Relabel.  Density, importances, label counts and boxes follow,
+        as if the edited labels had been uploaded.  Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_edit_labels(self.handle, C.byref(relabel.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
+    def read_labels(self, sub=None):
+        """The labels on the device as a uint8 array [z, y, x]: the whole label volume (None) or the sub-box (lo, hi) in texels.
+        Blocks."""
+        if sub is None:
+            dims = getattr(self, "_label_dims", None)
+            if dims is None:                                   # no labels yet: the library refuses
+                self._ck(_lib.lib().volym_read_labels(self.handle, None, None))
+                return np.zeros((0, 0, 0), np.uint8)
+            box = ((0, 0, 0), dims)
+        else:
+            box = (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        out = np.zeros(tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0)), np.uint8)
+        self._ck(_lib.lib().volym_read_labels(self.handle, c, scene._u8p(out) if out.size else None))
+        return out
 
     # ---- measurement ------------------------------------------------------------------------
     def stats_pass(self):
@@ -1079,6 +1106,8 @@ class Simple(ComputeDemo):
         self._labels_raw = labels_raw
         self._labels_on_device = True
         self._records_for = None
+        self._segments_on_device = False        # (the table went with the old labels)
+        self._labels_edited = False
 
     def set_segments(self, ctx, segments):
         """New segment importances for the labels of set_labels (an editor's "show me the lobster instead of the cup").
@@ -1090,10 +1119,149 @@ class Simple(ComputeDemo):
         self._records_for = None
         padded = self._labels_raw.size < self.dims[0] * self.dims[1] * self.dims[2]
         if padded and table[0] != 0:
+            if getattr(self, "_labels_edited", False):           # (the host copy predates the edits on the device)
+                self._labels_raw, self._labels_edited = self._labels_from_device(ctx), False
             importances = scene.map_segments_to_importance(self._labels_raw, segments)
             ctx.set_importances(scene.prepare_volume(importances, self.dims, flip_y=True), self.dims)   # (drops the labels)
-            self._labels_on_device = False
+            self._labels_on_device = self._segments_on_device = False
             return
         if not self._labels_on_device:
             self.set_labels(ctx, self._labels_raw)
         ctx.set_segment_importances(table)
+        self._segments_on_device = True
+
+    # ---- editing labels: pick, then the pass, then the edit ---------------------------------------
+    def _labels_from_device(self, ctx):
+        """The labels on the device as raw bytes in the orientation prepare_volume read (the y flip undone)."""
+        return np.ascontiguousarray(ctx.read_labels()[:, ::-1, :]).ravel()
+
+    def _ready_to_edit(self, ctx):
+        """Labels on the device and importances mapped from them through the segments' table, so that they follow an edit."""
+        if not self._labels_raw.size and not self._labels_on_device:
+            raise ValueError("the demo has no labels to edit")
+        if not self._labels_on_device or not getattr(self, "_segments_on_device", False):
+            self.set_segments(ctx, self._segments)
+        if not self._labels_on_device:
+            raise ValueError("the labels are shorter than the volume and label 0 is important: they cannot stay on the device")
+
+    def _edit(self, ctx, relabel):
+        result = ctx.edit_labels(scene.check_relabel(relabel, self.dims))
+        if int(result["changed"]) and not relabel.flags & _lib.RELABEL_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def _new_segment(self, ctx, name, like):
+        """The label value of segment `name`: that of the segments JSON entry of that name or id, or a new entry with the smallest
+        label value that no entry names and no texel carries, and the importance of label `like`.  The table is re-sent."""
+        if not isinstance(name, str):
+            return int(name)
+        for s in self._segments:
+            if name in (s.get("name"), s.get("id")):
+                return int(s["label_value"])
+        used = {int(s["label_value"]) for s in self._segments}
+        counts = ctx.label_counts()
+        value = next((v for v in range(1, 256) if v not in used and not int(counts[v])), None)
+        if value is None:
+            raise ValueError("no label value is free for segment %r" % name)
+        source = next((s for s in self._segments if s["label_value"] == like), None)
+        self._segments = list(self._segments) + [{"id": "Segment_%d" % value, "name": name, "label_value": value,
+                                                  "importance": int(source["importance"]) if source else 0}]
+        self.set_segments(ctx, self._segments)
+        return value
+
+    def relabel(self, ctx, mapping, box01=None, window=(0, 255), uncut=False, dry_run=False):
+        """Merge or swap segments by the table alone, or threshold-paint: every texel of a segment in `mapping` ({from: to}, names,
+        ids or label values; `to` may name a new segment) inside box01 (unit-cube coordinates as set_crop takes them; None: the
+        whole volume) whose density byte lies in `window` gets the new label.  Returns scene.relabel_result_dict's dict."""
+        self._ready_to_edit(ctx)
+        table = {}
+        for old, new in mapping.items():
+            (l,) = self._label_values([old])
+            table[l] = self._new_segment(ctx, new, l)
+        box = None if box01 is None else scene.crop_box_texels(box01[0], box01[1], self.dims)
+        flags = (_lib.RELABEL_UNCUT if uncut else 0) | (_lib.RELABEL_DRY_RUN if dry_run else 0)
+        return self._edit(ctx, scene.Relabel(box, flags, window, table, dims=self.dims))
+
+    def paint(self, ctx, name, window, box01=None, over=(0,), uncut=False):
+        """Threshold-paint: the texels of the segments `over` (default: the unlabelled ones) inside box01 whose density byte lies in
+        `window` = (min_byte, max_byte) join segment `name`."""
+        return self.relabel(ctx, {o: name for o in over}, box01, window, uncut)
+
+    def split_at(self, ctx, x, y, name, alpha_min=0.5, min_byte=1):
+        """Click to split: pick pixel (x, y), one components pass for the segment it shows, selected alone, and the piece under the
+        pixel becomes segment `name` (a name or id of the segments JSON, a label value, or a new name, which gets an entry with
+        the source's importance).  Returns the pick with a "relabel" entry (the result's dict, "label": the piece's new label);
+        None there when the pixel shows no labelled sample or the picked texel is not solid at min_byte."""
+        self._ready_to_edit(ctx)
+        p = self.pick(ctx, x, y, alpha_min)
+        p["relabel"] = None
+        if p["status"] == "hit" and p["label"] is not None:
+            l = p["label"]
+            ctx.components_pass(scene.Components(None, 0, min_byte, scene.surface_select([l]), dims=self.dims))
+            k = ctx.component_of(*p["texel"])
+            if k != _lib.COMPONENT_NONE:
+                value = self._new_segment(ctx, name, l)
+                p["relabel"] = self._edit(ctx, scene.Relabel(None, _lib.RELABEL_IDS, to={l: value}, ids=(k, k), dims=self.dims))
+                p["relabel"]["label"] = value
+        return p
+
+    def keep_largest(self, ctx, name, rest=0, min_byte=1):
+        """Keep the largest piece of segment `name` and send its other pieces to `rest` (a segment, or label 0): one components pass
+        with the segment selected alone, then the edit with IDS_EXCEPT.  Returns the result's dict with "pieces" and "kept" (the
+        largest piece's number) added; None when the segment has no solid texel."""
+        self._ready_to_edit(ctx)
+        (l,) = self._label_values([name])
+        ctx.components_pass(scene.Components(None, 0, min_byte, scene.surface_select([l]), dims=self.dims))
+        summary = ctx.read_components()
+        if not int(summary["recorded"]):
+            return None
+        k = int(np.argmax(ctx.read_component_table(summary["recorded"])["count"]))
+        to = self._new_segment(ctx, rest, l)
+        out = self._edit(ctx, scene.Relabel(None, _lib.RELABEL_IDS | _lib.RELABEL_IDS_EXCEPT, to={l: to}, ids=(k, k), dims=self.dims))
+        out.update(pieces=int(summary["n_components"]), kept=k)
+        return out
+
+    def _band(self, unit, r):
+        """the largest D with sqrt(D) * unit <= r"""
+        return int(np.floor((float(r) / unit) ** 2 + 1e-9))
+
+    def grow(self, ctx, name, r, into=(0,), spacing=(1, 1, 1), min_byte=1):
+        """Grow segment `name` by a margin of r (units of `spacing`) into the segments `into` (default: the unlabelled texels): one
+        distance pass from the segment, then the texels of `into` at a distance of at most r join it."""
+        self._ready_to_edit(ctx)
+        (l,) = self._label_values([name])
+        d, unit = self._distance_request(ctx, [l], False, min_byte, None, False, spacing)
+        ctx.distance_pass(d)
+        table = {v: l for v in self._label_values(into) if v != l}
+        return self._edit(ctx, scene.Relabel(None, _lib.RELABEL_DISTANCE, to=table, d2=(0, self._band(unit, r)), dims=self.dims))
+
+    def shrink(self, ctx, name, r, to=0, spacing=(1, 1, 1), min_byte=1):
+        """Shrink segment `name` by r (units of `spacing`): one INSIDE distance pass, then its texels within r of its outside go to
+        `to` (a segment, or label 0)."""
+        self._ready_to_edit(ctx)
+        (l,) = self._label_values([name])
+        d, unit = self._distance_request(ctx, [l], True, min_byte, None, False, spacing)
+        ctx.distance_pass(d)
+        return self._edit(ctx, scene.Relabel(None, _lib.RELABEL_DISTANCE, to={l: self._new_segment(ctx, to, l)}, d2=(0, self._band(unit, r)), dims=self.dims))
+
+    def core(self, ctx, name, r, to, spacing=(1, 1, 1), min_byte=1):
+        """The thick core of segment `name`: its texels deeper than r (units of `spacing`) inside it become segment `to`."""
+        self._ready_to_edit(ctx)
+        (l,) = self._label_values([name])
+        d, unit = self._distance_request(ctx, [l], True, min_byte, None, False, spacing)
+        ctx.distance_pass(d)
+        return self._edit(ctx, scene.Relabel(None, _lib.RELABEL_DISTANCE, to={l: self._new_segment(ctx, to, l)},
+                                             d2=(self._band(unit, r) + 1, _lib.DISTANCE_NONE - 1), dims=self.dims))
+
+    def save_labels(self, ctx, path):
+        """Write the labels as they stand on the device to `path`: raw bytes in the orientation prepare_volume read, so that the
+        file loads again as labels_raw.  Returns the number of bytes."""
+        if not self._labels_on_device:
+            raw = self._labels_raw
+        else:
+            raw = self._labels_raw = self._labels_from_device(ctx)
+            self._labels_edited = False
+        with open(path, "wb") as f:
+            f.write(raw.tobytes())
+        return int(raw.size)

@@ -1362,6 +1362,150 @@ def distance_summary(summary, unit=1.0):
     return out
 
 
+def relabel_table(mapping=None):
+    """The `to` table of a relabel request from {old label: new label}: the identity everywhere else."""
+    to = np.arange(256, dtype=np.int64)
+    for old, new in (mapping or {}).items():
+        if not (0 <= int(old) <= 255 and 0 <= int(new) <= 255):
+            raise ValueError("relabel_table: labels are bytes, got %r -> %r" % (old, new))
+        to[int(old)] = int(new)
+    return to
+
+
+class Relabel:
+    """volym_relabel (include/volym_hip.h): one edit of the labels.  box as Surface takes it; flags: _lib.RELABEL_UNCUT | RELABEL_IDS |
+    RELABEL_IDS_EXCEPT | RELABEL_DISTANCE | RELABEL_DRY_RUN; window: (min_byte, max_byte) of the density; to: 256 labels (relabel_table);
+    ids: (id_lo, id_hi) in the latest components pass; d2: (d2_lo, d2_hi) in the latest distance map."""
+
+    def __init__(self, box=None, flags=0, window=(0, 255), to=None, ids=(0, 0), d2=(0, 0), dims=None):
+        if box is None:
+            if dims is None:
+                raise ValueError("a relabel request without a box needs the volume's dims")
+            box = ((0, 0, 0), tuple(int(v) for v in dims))
+        lo, hi = box
+        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+        self.ids = tuple(int(v) for v in ids)
+        self.d2 = tuple(int(v) for v in d2)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "relabel", ("box", "flags", "window", "to", "ids", "d2"), kw)
+
+    def to_c(self):
+        """The _lib.Relabel of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Relabel()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("relabel: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        pairs = (self.window, self.ids, self.d2)
+        if not 0 <= self.flags < 2 ** 32 or not all(len(p) == 2 and all(0 <= x < 2 ** 32 for x in p) for p in pairs):
+            raise ValueError("relabel: flags, window, ids and d2 must be u32 (pairs)")
+        c.flags = self.flags
+        c.min_byte, c.max_byte = self.window
+        if self.to.size != 256 or not ((self.to >= 0) & (self.to <= 255)).all():
+            raise ValueError("relabel: the table is 256 bytes")
+        c.to = (C.c_uint8 * 256)(*[int(g) for g in self.to])
+        c.id_lo, c.id_hi = self.ids
+        c.d2_lo, c.d2_hi = self.d2
+        return c
+
+
+def check_relabel(relabel, dims):
+    """The validity rules of volym_relabel_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits, IDS_EXCEPT
+    only with IDS, min_byte <= max_byte <= 255, id_lo <= id_hi with IDS, d2_lo <= d2_hi with DISTANCE.  Returns the request; raises
+    ValueError."""
+    r = relabel
+    dims = [int(v) for v in dims]
+    lo, hi = r.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("relabel: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("relabel box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    known = _lib.RELABEL_UNCUT | _lib.RELABEL_IDS | _lib.RELABEL_IDS_EXCEPT | _lib.RELABEL_DISTANCE | _lib.RELABEL_DRY_RUN
+    if r.flags & ~known or r.flags < 0:
+        raise ValueError("relabel: unknown flag bits in %#x" % r.flags)
+    if r.flags & _lib.RELABEL_IDS_EXCEPT and not r.flags & _lib.RELABEL_IDS:
+        raise ValueError("relabel: IDS_EXCEPT is valid only together with IDS")
+    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
+        raise ValueError("relabel: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (r.window,))
+    if r.flags & _lib.RELABEL_IDS and not (len(r.ids) == 2 and 0 <= r.ids[0] <= r.ids[1]):
+        raise ValueError("relabel: IDS needs id_lo <= id_hi, got %r" % (r.ids,))
+    if r.flags & _lib.RELABEL_DISTANCE and not (len(r.d2) == 2 and 0 <= r.d2[0] <= r.d2[1]):
+        raise ValueError("relabel: DISTANCE needs d2_lo <= d2_hi, got %r" % (r.d2,))
+    if np.asarray(r.to).size != 256:
+        raise ValueError("relabel: the table has 256 entries")
+    return r
+
+
+def _snapshot_in_box(name, snap, snap_box, lo, hi):
+    """The part of a box-linear snapshot (ids, distance map: uint32 [z, y, x] over snap_box) that covers the request's box."""
+    if snap is None or snap_box is None:
+        raise ValueError("relabel_volume: %s and its box are needed" % name)
+    slo, shi = (tuple(int(v) for v in snap_box[0]), tuple(int(v) for v in snap_box[1]))
+    if any(lo[a] < slo[a] or hi[a] > shi[a] for a in range(3)):
+        raise ValueError("relabel_volume: the request's box reaches outside the box of %s" % name)
+    full = np.asarray(snap, np.uint32).reshape(shi[2] - slo[2], shi[1] - slo[1], shi[0] - slo[0])
+    return full[lo[2] - slo[2]:hi[2] - slo[2], lo[1] - slo[1]:hi[1] - slo[1], lo[0] - slo[0]:hi[0] - slo[0]]
+
+
+def relabel_volume(prepared, dims, r, labels, ids=None, ids_box=None, dmap=None, dmap_box=None, uncut=None):
+    """The definition of the label edit (include/volym_hip.h volym_edit_labels), NumPy integers only; equal to the device in every
+    byte.  `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None: prepared),
+    `labels`: the labels before the edit; ids / dmap: the snapshots of the latest components / distance pass as uint32 [z, y, x] over
+    ids_box / dmap_box = ((lo), (hi)).  Returns (new_labels, result): the labels as a uint8 array [z, y, x] of the volume (the input
+    untouched; with DRY_RUN a copy of it) and an np.void of _lib.RELABEL_RESULT_DTYPE."""
+    r = check_relabel(r, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("relabel_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (r.flags & _lib.RELABEL_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("relabel_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    picked_ids = _snapshot_in_box("the component ids", ids, ids_box, lo, hi) if r.flags & _lib.RELABEL_IDS else None
+    picked_map = _snapshot_in_box("the distance map", dmap, dmap_box, lo, hi) if r.flags & _lib.RELABEL_DISTANCE else None
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    old = new[sub]
+    to = np.asarray(r.to, np.int64).astype(np.uint8)
+    b = src.reshape(nz, ny, nx)[sub]
+    hit = (to[old] != old) & (b >= r.window[0]) & (b <= r.window[1])
+    if picked_ids is not None:
+        ranged = (picked_ids >= r.ids[0]) & (picked_ids <= r.ids[1])
+        hit &= (picked_ids != np.uint32(_lib.COMPONENT_NONE)) & (~ranged if r.flags & _lib.RELABEL_IDS_EXCEPT else ranged)
+    if picked_map is not None:
+        hit &= (picked_map != np.uint32(_lib.DISTANCE_NONE)) & (picked_map >= r.d2[0]) & (picked_map <= r.d2[1])
+    n = int(hit.sum())
+    if n == 0:
+        return new, result
+    result["changed"] = n
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not r.flags & _lib.RELABEL_DRY_RUN:
+        new[sub] = np.where(hit, to[old], old)
+    return new, result
+
+
+def relabel_result_dict(result):
+    """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
+    box = [int(v) for v in result["box"]]
+    return {"changed": int(result["changed"]),
+            "left": {int(l): int(result["left"][l]) for l in np.flatnonzero(result["left"])},
+            "arrived": {int(l): int(result["arrived"][l]) for l in np.flatnonzero(result["arrived"])},
+            "box": (tuple(box[:3]), tuple(box[3:])) if int(result["changed"]) else None}
+
+
 PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0     # volym_update's range for the march step
 
 
