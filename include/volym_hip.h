@@ -988,6 +988,44 @@ int   volym_relabel_check(const volym_relabel* r, const uint32_t dims[3]);
  * VOLYM_E_STATE: no labels.  VOLYM_E_INVALID: NULL ctx, a sub-box outside the labels, NULL output for a sub-box with texels. */
 int   volym_read_labels(volym_ctx* ctx, const uint32_t sub[6], uint8_t* out);
 
+/* --- undo and redo of label edits (new; the reference has none) ---------------------------------------------------- */
+/* What an edit destroys is small: the 16-byte label chunks of the device layout in which a byte changed.  While the history is on,
+ * every volym_edit_labels that changes a texel (no DRY_RUN) journals those chunks -- index and the 16 bytes before the edit, 20 bytes
+ * per chunk, each chunk once -- from the kernel that stores them, and the journal becomes a step in device memory of its own.  Undo
+ * swaps the newest undoable step with the labels; redo swaps the newest undone step back; an edit that records drops the redo steps.
+ * scene.LabelHistory of the Python package is the host twin of the bookkeeping, equal in every field of the info.
+ *   budget_bytes > 0: keep a history in at most that much device memory.  0: drop the history and free it.  Off in a new context.
+ * Changing the budget keeps the steps that still fit: the oldest undoable steps are dropped first, then the redo steps that would be
+ * redone last.  An edit journals into a staging area with room for min(items of the request's slab, budget / 20) records; when more
+ * chunks change than that, the edit is carried out and returns VOLYM_OK, the whole history (undo and redo steps) is given up, and
+ * `lost` counts it: undoing older steps across a gap would be wrong.  The same happens when there is no device memory for the step.
+ * After a step that fits, the oldest steps are dropped until used_bytes <= budget_bytes, each adding 1 to dropped_steps.
+ *   volym_set_labels, volym_set_volume and volym_set_importances clear the steps (the budget and the two counters stay). */
+int   volym_label_history(volym_ctx* ctx, uint64_t budget_bytes);
+/* Blocking set-up calls exactly like volym_edit_labels (they wait for the frames in flight and run on the first slot's stream).  The
+ * result is computed on the device from the bytes that were swapped: the texels that differ, per label those that lost it and got
+ * it, and their hull -- for an undo the edit's result with left and arrived exchanged, for a redo the edit's result.  Afterwards the
+ * context is byte for byte where one handed those labels would be, under the box, plane and mask as they stand now (they may have
+ * changed since the edit), and a surface pass is stale.  out may be NULL.
+ *   VOLYM_E_INVALID: NULL ctx.  VOLYM_E_STATE: the history is off; nothing to undo / redo; the states volym_edit_labels refuses.  A
+ * refused call changes nothing.  The native multi-GPU loop has no forward for these calls. */
+int   volym_undo_labels(volym_ctx* ctx, struct volym_relabel_result* out);
+int   volym_redo_labels(volym_ctx* ctx, struct volym_relabel_result* out);
+struct volym_label_history_info {
+    uint64_t budget_bytes, used_bytes;      /* used = 20 * records over all kept steps, <= budget */
+    uint32_t undo_steps, redo_steps;
+    uint64_t next_undo_records, next_redo_records;   /* chunks the next undo / redo would swap; 0: none */
+    uint64_t dropped_steps;                 /* steps evicted to stay in the budget, since the history was switched on */
+    uint64_t lost;                          /* times the whole history was given up because one edit did not fit */
+};                                          /* 56 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(struct volym_label_history_info) == 56, "volym_label_history_info is 56 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(struct volym_label_history_info) == 56, "volym_label_history_info is 56 bytes");
+#endif
+/* VOLYM_E_INVALID: NULL ctx or NULL out.  All 0 while the history is off. */
+int   volym_label_history_info(volym_ctx* ctx, struct volym_label_history_info* out);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

@@ -29,7 +29,8 @@ and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram
 --relabel FROM[,FROM...]:TO, --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
 after the first frame, in that order (demo.Simple.relabel, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
---labels (demo.Simple.save_labels).
+--labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
+back before the picture and --labels-out, one JSON line {"undo": ...} each.
 """
 import argparse
 import csv
@@ -342,7 +343,17 @@ def run_simple(args):
             d.compute_pass(ctx)
             ctx.sync()
         # label edits, in the order relabel, split, keep the largest, grow, shrink; the PNG is the frame after them
+        undo = getattr(args, "undo", None) or 0
+        if undo < 0:
+            raise SystemExit("--undo: N is a number of edits to take back, got %d" % undo)
+        try:
+            if undo:
+                d.history(ctx)              # on before the edits: a step is journalled by the edit it takes back
+        except ValueError as e:
+            raise SystemExit("--undo: %s" % e)
         edits = _label_edits(ctx, d, args)
+        for _ in range(undo):               # the last N edits back; None: nothing (left) to take back
+            edits.append(("undo", d.undo(ctx)))
         if edits:
             d.compute_pass(ctx)
             ctx.sync()
@@ -579,6 +590,8 @@ def main(argv=None):
     run.add_argument("--keep-largest", help="NAME: keep the largest piece of the segment, its other pieces become unlabelled")
     run.add_argument("--grow", help="NAME:R: grow the segment by R texels into the unlabelled texels")
     run.add_argument("--shrink", help="NAME:R: shrink the segment by R texels")
+    run.add_argument("--undo", type=int, metavar="N", help="keep a history of the label edits above on the device and take the last N back, before the "
+                                                           "picture and --labels-out; each prints a JSON line {\"undo\": ...}")
     run.add_argument("--labels-out", help="FILE: write the labels as they stand after the edits, raw bytes in the orientation of --labels")
     run.add_argument("--slice-at", help="X,Y: also write the three orthogonal slices through the texel pixel (X, Y) shows")
     b = sub.add_parser("benchmark", help="run benchmarks on all demos")

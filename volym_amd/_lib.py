@@ -290,6 +290,17 @@ class RelabelResult(C.Structure):
 # the result as a NumPy structured dtype (GpuContext.edit_labels, scene.relabel_volume)
 RELABEL_RESULT_DTYPE = np.dtype([("changed", "<u8"), ("left", "<u8", (256,)), ("arrived", "<u8", (256,)), ("box", "<u4", (6,))])
 
+JOURNAL_RECORD_BYTES = 20        # what one journalled chunk costs of the history's budget: its index and its 16 bytes
+
+
+class LabelHistoryInfo(C.Structure):
+    """volym_label_history_info (include/volym_hip.h): budget and use of the label history, its steps and counters, 56 bytes"""
+    _fields_ = [("budget_bytes", C.c_uint64), ("used_bytes", C.c_uint64), ("undo_steps", C.c_uint32), ("redo_steps", C.c_uint32),
+                ("next_undo_records", C.c_uint64), ("next_redo_records", C.c_uint64), ("dropped_steps", C.c_uint64), ("lost", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
 
 class CCamera(C.Structure):
     """src/camera.rs:5-19"""
@@ -457,6 +468,10 @@ SIGNATURES = {
     "volym_edit_labels": (C.c_int, [_ctx, C.POINTER(Relabel), C.POINTER(RelabelResult)]),
     "volym_relabel_check": (C.c_int, [C.POINTER(Relabel), C.POINTER(C.c_uint32)]),
     "volym_read_labels": (C.c_int, [_ctx, C.POINTER(C.c_uint32), _u8p]),
+    "volym_label_history": (C.c_int, [_ctx, C.c_uint64]),
+    "volym_undo_labels": (C.c_int, [_ctx, C.POINTER(RelabelResult)]),
+    "volym_redo_labels": (C.c_int, [_ctx, C.POINTER(RelabelResult)]),
+    "volym_label_history_info": (C.c_int, [_ctx, C.POINTER(LabelHistoryInfo)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

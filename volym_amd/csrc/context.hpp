@@ -254,6 +254,21 @@ struct volym_ctx {
     volym::OwnedBuffer<unsigned long long> distance_keys;   // the working summary: counters and 64-bit (D, index) keys, packed into `distance`
     uint32_t distance_box[6] = {};           // the box of the latest pass (the reads address the map by it)
 
+    // the history of label edits (volym_label_history, relabel.inc): off (budget 0) in a new context
+    struct LabelStep {
+        uint32_t* index = nullptr;           // the chunks the edit stored ...
+        uint4* old = nullptr;                // ... and the 16 bytes each held on the other side of the step
+        uint64_t records = 0;
+        volym_relabel_result result = {};    // the edit's result: names the labels an undo (left) and a redo (arrived) send texels to
+    };
+    uint64_t history_budget = 0;
+    std::vector<LabelStep> history_steps;    // oldest first: [0, history_cursor) can be undone, the rest redone (the nearest first)
+    size_t history_cursor = 0;
+    uint64_t history_used = 0;               // 20 * records over history_steps
+    uint64_t history_dropped = 0, history_lost = 0;
+    volym::OwnedBuffer<uint32_t> journal_index;   // where an edit journals: room for the worst case of its slab within the budget
+    volym::OwnedBuffer<uint4> journal_old;
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -314,6 +329,10 @@ void free_surface(volym_ctx* c);
 void free_components(volym_ctx* c);
 // distance.hip: what the context keeps for the distance pass (every stream idle)
 void free_distance(volym_ctx* c);
+// scene_bytes.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
+void clear_label_history(volym_ctx* c);
+// scene_bytes.hip: the steps and the staging area of the label history (every stream idle)
+void free_label_history(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume

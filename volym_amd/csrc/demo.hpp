@@ -170,6 +170,24 @@ public:
         records_current_ = false;
         return out;
     }
+    // New: keep a history of the label edits in at most budget_bytes of device memory (volym_label_history), so that undo can take
+    // them back.  The labels go to the device first: handing them to the context clears the history.
+    void history(const GpuContext& ctx, const SimpleAssets& a, uint64_t budget_bytes = 256ull << 20)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "history: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        ctx.check(volym_label_history(ctx.handle(), budget_bytes));
+    }
+    // New: take the latest edit back on the device (volym_undo_labels).  False: there is nothing to take back.
+    bool undo(const GpuContext& ctx, volym_relabel_result& out)
+    {
+        struct volym_label_history_info info{};
+        ctx.check(volym_label_history_info(ctx.handle(), &info));
+        if (info.undo_steps == 0u) return false;
+        ctx.check(volym_undo_labels(ctx.handle(), &out));
+        records_current_ = false;
+        return true;
+    }
     // New: the labels as they stand on the device, as raw bytes in the orientation prepare_volume read (the y flip undone)
     std::vector<uint8_t> labels_from_device(const GpuContext& ctx, const SimpleAssets& a)
     {

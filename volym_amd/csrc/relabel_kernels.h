@@ -1,4 +1,5 @@
-// The kernels of the label edit (volym_edit_labels, volym_read_labels).  Included by scene_bytes.hip alone, after scene_kernels.h,
+// The kernels of the label edit (volym_edit_labels, volym_read_labels) and of its history (volym_label_history: the journalling form
+// of the edit, and the swap of volym_undo_labels and volym_redo_labels).  Included by scene_bytes.hip alone, after scene_kernels.h,
 // whose chunk walk (CropSlab, crop_chunk) and chunk geometry (label_chunk_origin) they read; nothing in that header changes.
 #pragma once
 
@@ -61,6 +62,93 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v)
     return v;
 }
 
+// What a workgroup of the relabel and swap kernels keeps in LDS: the table (relabel only) and its share of the result.
+struct RelabelShared {
+    uint8_t to[256];
+    uint32_t left[256], arrived[256];
+    uint32_t changed, box[6];
+};
+
+// What a lane keeps in registers: its changed texels, their hull, and one run of equal (old label, new label) pairs, keyed
+// old | new << 8, whose length it flushes when the pair changes and once at the end (TALLY_NONE: no run yet).
+constexpr uint32_t TALLY_NONE = 0x10000u;
+struct RelabelTally {
+    uint32_t changed = 0, lo_x = 0xffffffffu, lo_y = 0xffffffffu, lo_z = 0xffffffffu, hi_x = 0, hi_y = 0, hi_z = 0;
+    uint32_t cur = TALLY_NONE, cnt = 0;
+};
+
+__device__ __forceinline__ void tally_init(RelabelShared& sh)
+{
+    const uint32_t l = threadIdx.x;
+    sh.left[l] = sh.arrived[l] = 0u;
+    if (l == 0u) sh.changed = 0u;
+    if (l < 6u) sh.box[l] = l < 3u ? 0xffffffffu : 0u;
+}
+
+__device__ __forceinline__ void tally_flush(RelabelShared& sh, const RelabelTally& t)
+{
+    if (t.cur >= TALLY_NONE) return;
+    atomicAdd(&sh.left[t.cur & 0xffu], t.cnt);
+    atomicAdd(&sh.arrived[t.cur >> 8], t.cnt);
+}
+
+// texel (x, y, z) went from label `from` to label `to`
+__device__ __forceinline__ void tally_texel(RelabelShared& sh, RelabelTally& t, uint32_t from, uint32_t to, uint32_t x, uint32_t y, uint32_t z)
+{
+    const uint32_t key = from | (to << 8);
+    if (key != t.cur) { tally_flush(sh, t); t.cur = key; t.cnt = 0u; }
+    ++t.cnt; ++t.changed;
+    t.lo_x = min(t.lo_x, x); t.lo_y = min(t.lo_y, y); t.lo_z = min(t.lo_z, z);
+    t.hi_x = max(t.hi_x, x); t.hi_y = max(t.hi_y, y); t.hi_z = max(t.hi_z, z);
+}
+
+// The epilogue of both kernels; every lane of the workgroup calls it, after its loop has ended.  The waves add up first: changed
+// and the hull by shuffles, and the runs too where the whole wave carries the same pair (a merge of one segment: every lane) -- one
+// LDS atomic per wave and word instead of 64 on the same word.  After the barrier thread l adds the workgroup's left[l] and
+// arrived[l] to the global result and thread 0 the count and the hull: one global atomic per non-zero word and workgroup.  All
+// integer adds and min/max: the result does not depend on arrival order.  A workgroup holds fewer texels than a layout has bytes
+// (< 2^32): u32 in LDS.
+__device__ __forceinline__ void tally_reduce(RelabelShared& sh, const RelabelTally& t, const RelabelOut& out)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w_changed = wave_sum(t.changed);
+    if (w_changed != 0u) {                                               // (wave-uniform)
+        const uint32_t a = wave_min(t.lo_x), b = wave_min(t.lo_y), c = wave_min(t.lo_z), d = wave_max(t.hi_x), e = wave_max(t.hi_y), f = wave_max(t.hi_z);
+        const unsigned long long have = __ballot(t.cur < TALLY_NONE);
+        const uint32_t first = static_cast<uint32_t>(__ffsll(have)) - 1u;
+        const uint32_t ref = __shfl(t.cur, static_cast<int>(first), 64);
+        if (__all(t.cur >= TALLY_NONE || t.cur == ref)) {
+            const uint32_t total = wave_sum(t.cur < TALLY_NONE ? t.cnt : 0u);
+            if (lane == first) { atomicAdd(&sh.left[ref & 0xffu], total); atomicAdd(&sh.arrived[ref >> 8], total); }
+        } else {
+            tally_flush(sh, t);
+        }
+        if (lane == 0u) {
+            atomicAdd(&sh.changed, w_changed);
+            atomicMin(&sh.box[0], a); atomicMin(&sh.box[1], b); atomicMin(&sh.box[2], c);
+            atomicMax(&sh.box[3], d); atomicMax(&sh.box[4], e); atomicMax(&sh.box[5], f);
+        }
+    }
+    __syncthreads();
+    const uint32_t l = threadIdx.x;
+    if (sh.left[l] != 0u) atomicAdd(&out.left[l], static_cast<unsigned long long>(sh.left[l]));
+    if (sh.arrived[l] != 0u) atomicAdd(&out.arrived[l], static_cast<unsigned long long>(sh.arrived[l]));
+    if (l == 0u && sh.changed != 0u) {
+        atomicAdd(out.changed, static_cast<unsigned long long>(sh.changed));
+        for (int a = 0; a < 3; ++a) atomicMin(&out.box[a], sh.box[a]);
+        for (int a = 3; a < 6; ++a) atomicMax(&out.box[a], sh.box[a]);
+    }
+}
+
+// The journal an edit appends to while the history is on (volym_label_history): per stored chunk its index and its 16 bytes before
+// the edit, as two arrays.  *count runs past capacity when the journal is too small; a record at or past capacity is not written.
+struct LabelJournal {
+    uint32_t* index;
+    uint4* old;
+    uint32_t* count;
+    uint32_t capacity;
+};
+
 // One pass over the items of slab s (make_crop_slab over the request's box, s.box_lo/hi the box itself, no plane: keep names the
 // texels of the box), in either layout.  Per chunk: the 16 labels first; a chunk in which no texel of the box has to[l] != l loads
 // nothing more and stores nothing.  Else the 16 density bytes (vol: the scene bytes, or the uncut copy), then -- IDS, DISTANCE --
@@ -68,38 +156,23 @@ __device__ __forceinline__ uint32_t wave_max(uint32_t v)
 // plain vector store, only if a byte changed and rule.store says so.  Labels are read and written by the chunk's one owner and
 // everything else is only read: every texel is decided from the bytes before the edit.
 //
-// The result.  A lane counts its changed texels and keeps their hull in registers, and carries one run of equal old labels whose
-// length it flushes when the label changes and once at the end.  At the end the waves add up first: changed and the hull by
-// shuffles, and the runs too where the whole wave carries the same label (a merge of one segment: every lane) -- one LDS atomic per
-// wave and word instead of 64 on the same word.  After the barrier thread l adds the workgroup's left[l] and arrived[l] to the
-// global result and thread 0 the count and the hull: one global atomic per non-zero word and workgroup.  All integer adds and
-// min/max: the result does not depend on arrival order.  A workgroup holds fewer texels than a layout has bytes (< 2^32): u32 in LDS.
-template <bool IDS, bool DISTANCE>
-__global__ __launch_bounds__(256) void volym_relabel_kernel(uint4* __restrict__ labels, const uint4* __restrict__ vol, const uint32_t* __restrict__ ids,
-                                                            const uint32_t* __restrict__ dmap, RelabelOut out, LabelTable to, CropSlab s, RelabelRule rule,
-                                                            uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
+// JOURNAL: a chunk that is about to be stored is appended to the journal first, once (its owner is the only lane that gets here):
+// the lanes of a wave that arrive together take one atomicAdd for their number and rank themselves below it.  The loop is divergent,
+// so the ballot is taken inside the predicate, among the lanes that are there.
+//
+// The result: tally_texel per changed texel, tally_reduce at the end.
+template <bool IDS, bool DISTANCE, bool JOURNAL>
+__device__ __forceinline__ void relabel_pass(RelabelShared& sh, uint4* __restrict__ labels, const uint4* __restrict__ vol, const uint32_t* __restrict__ ids,
+                                             const uint32_t* __restrict__ dmap, const RelabelOut& out, const LabelTable& to, const CropSlab& s,
+                                             const RelabelRule& rule, const LabelJournal& journal, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked,
+                                             uint32_t n_items)
 {
-    __shared__ uint8_t s_to[256];
-    __shared__ uint32_t s_left[256], s_arrived[256];
-    __shared__ uint32_t s_changed, s_box[6];
-    {
-        const uint32_t l = threadIdx.x;
-        s_to[l] = to.v[l];
-        s_left[l] = s_arrived[l] = 0u;
-        if (l == 0u) s_changed = 0u;
-        if (l < 6u) s_box[l] = l < 3u ? 0xffffffffu : 0u;
-    }
+    sh.to[threadIdx.x] = to.v[threadIdx.x];
+    tally_init(sh);
     __syncthreads();
     const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
-
-    uint32_t changed = 0, lo_x = 0xffffffffu, lo_y = 0xffffffffu, lo_z = 0xffffffffu, hi_x = 0, hi_y = 0, hi_z = 0;
-    uint32_t cur = 256u, cnt = 0;                    // the run of equal old labels (256: none yet)
-    auto flush = [&]() {
-        if (cur > 255u) return;
-        atomicAdd(&s_left[cur], cnt);
-        atomicAdd(&s_arrived[s_to[cur]], cnt);
-    };
+    RelabelTally t;
 
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_items; i += gridDim.x * 256u) {
         uint64_t k;
@@ -113,7 +186,7 @@ __global__ __launch_bounds__(256) void volym_relabel_kernel(uint4* __restrict__ 
 #pragma unroll
         for (uint32_t j = 0; j < 16u; ++j) {
             const uint32_t l = (lb[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-            if (s_to[l] != l) cand |= 1u << j;
+            if (sh.to[l] != l) cand |= 1u << j;
         }
         cand &= keep;
         if (!cand) continue;                                             // no density, no ids, no store
@@ -143,50 +216,80 @@ __global__ __launch_bounds__(256) void volym_relabel_kernel(uint4* __restrict__ 
                     in = dd != VOLYM_DISTANCE_NONE && dd >= rule.d2_lo && dd <= rule.d2_hi;
                 }
                 if (in) {
-                    const uint32_t sh = 8u * (j & 3u), l = (lb[j >> 2] >> sh) & 0xffu;
-                    lb[j >> 2] = (lb[j >> 2] & ~(0xffu << sh)) | (static_cast<uint32_t>(s_to[l]) << sh);
-                    if (l != cur) { flush(); cur = l; cnt = 0u; }
-                    ++cnt; ++changed;
-                    lo_x = min(lo_x, x); lo_y = min(lo_y, y); lo_z = min(lo_z, z);
-                    hi_x = max(hi_x, x); hi_y = max(hi_y, y); hi_z = max(hi_z, z);
+                    const uint32_t shift = 8u * (j & 3u), l = (lb[j >> 2] >> shift) & 0xffu, becomes = sh.to[l];
+                    lb[j >> 2] = (lb[j >> 2] & ~(0xffu << shift)) | (becomes << shift);
+                    tally_texel(sh, t, l, becomes, x, y, z);
                 } else {
                     cand &= ~(1u << j);
                 }
             }
             if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
         }
-        if (cand && rule.store) labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
+        if (cand && rule.store) {
+            if (JOURNAL) {
+                const unsigned long long here = __ballot(1);             // the lanes that store a chunk in this step
+                const uint32_t lane = threadIdx.x & 63u, leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
+                uint32_t base = 0u;
+                if (lane == leader) base = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
+                base = __shfl(base, static_cast<int>(leader), 64);
+                const uint32_t at = base + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
+                if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = lv; }
+            }
+            labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
+        }
     }
+    tally_reduce(sh, t, out);
+}
 
-    // per wave, before LDS (every lane of the workgroup is here: the loop has ended for all)
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t w_changed = wave_sum(changed);
-    if (w_changed != 0u) {                                               // (wave-uniform)
-        const uint32_t a = wave_min(lo_x), b = wave_min(lo_y), c = wave_min(lo_z), d = wave_max(hi_x), e = wave_max(hi_y), f = wave_max(hi_z);
-        const unsigned long long have = __ballot(cur < 256u);
-        const uint32_t first = static_cast<uint32_t>(__ffsll(have)) - 1u;
-        const uint32_t ref = __shfl(cur, static_cast<int>(first), 64);
-        if (__all(cur > 255u || cur == ref)) {
-            const uint32_t total = wave_sum(cur < 256u ? cnt : 0u);
-            if (lane == first) { atomicAdd(&s_left[ref], total); atomicAdd(&s_arrived[s_to[ref]], total); }
-        } else {
-            flush();
-        }
-        if (lane == 0u) {
-            atomicAdd(&s_changed, w_changed);
-            atomicMin(&s_box[0], a); atomicMin(&s_box[1], b); atomicMin(&s_box[2], c);
-            atomicMax(&s_box[3], d); atomicMax(&s_box[4], e); atomicMax(&s_box[5], f);
-        }
-    }
+template <bool IDS, bool DISTANCE>
+__global__ __launch_bounds__(256) void volym_relabel_kernel(uint4* __restrict__ labels, const uint4* __restrict__ vol, const uint32_t* __restrict__ ids,
+                                                            const uint32_t* __restrict__ dmap, RelabelOut out, LabelTable to, CropSlab s, RelabelRule rule,
+                                                            uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
+{
+    __shared__ RelabelShared sh;
+    relabel_pass<IDS, DISTANCE, false>(sh, labels, vol, ids, dmap, out, to, s, rule, LabelJournal{}, nx, ny, nz, bricked, n_items);
+}
+
+// the same edit while the history is on and the request is no DRY_RUN
+template <bool IDS, bool DISTANCE>
+__global__ __launch_bounds__(256) void volym_relabel_journal_kernel(uint4* __restrict__ labels, const uint4* __restrict__ vol, const uint32_t* __restrict__ ids,
+                                                                    const uint32_t* __restrict__ dmap, RelabelOut out, LabelTable to, CropSlab s, RelabelRule rule,
+                                                                    LabelJournal journal, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
+{
+    __shared__ RelabelShared sh;
+    relabel_pass<IDS, DISTANCE, true>(sh, labels, vol, ids, dmap, out, to, s, rule, journal, nx, ny, nz, bricked, n_items);
+}
+
+// Undo and redo (volym_undo_labels, volym_redo_labels): swap the records of one journal step with the labels, one record per lane and
+// step of the grid.  Chunk index[i] gets the bytes old[i] and old[i] the bytes the chunk held, so that the same launch takes the swap
+// back.  The chunks of a step are distinct: no two lanes touch the same one.  For the bytes that differ (texels of the volume: an edit
+// changes no padding) the lane tallies the label that is there now as left and the one it restores as arrived, and their hull, with
+// coordinates stepped as the relabel kernel steps them: a linear chunk wraps rows and slices.
+__global__ __launch_bounds__(256) void volym_label_swap_kernel(uint4* __restrict__ labels, const uint32_t* __restrict__ index, uint4* __restrict__ old,
+                                                               RelabelOut out, uint32_t nx, uint32_t ny, uint32_t bricked, uint32_t n_records)
+{
+    __shared__ RelabelShared sh;
+    tally_init(sh);
     __syncthreads();
-    const uint32_t l = threadIdx.x;
-    if (s_left[l] != 0u) atomicAdd(&out.left[l], static_cast<unsigned long long>(s_left[l]));
-    if (s_arrived[l] != 0u) atomicAdd(&out.arrived[l], static_cast<unsigned long long>(s_arrived[l]));
-    if (l == 0u && s_changed != 0u) {
-        atomicAdd(out.changed, static_cast<unsigned long long>(s_changed));
-        for (int a = 0; a < 3; ++a) atomicMin(&out.box[a], s_box[a]);
-        for (int a = 3; a < 6; ++a) atomicMax(&out.box[a], s_box[a]);
+    RelabelTally t;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n_records; i += gridDim.x * 256u) {
+        const uint32_t k = index[i];
+        const uint4 now = labels[k], rec = old[i];
+        labels[k] = rec;
+        old[i] = now;
+        const uint32_t a[4] = {now.x, now.y, now.z, now.w}, b[4] = {rec.x, rec.y, rec.z, rec.w};
+        uint32_t x0, y0, z0;
+        label_chunk_origin(bricked != 0u, k, nx, ny, x0, y0, z0);
+        uint32_t x = x0, y = y0, z = z0;
+#pragma unroll
+        for (uint32_t j = 0; j < 16u; ++j) {
+            if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); }
+            const uint32_t shift = 8u * (j & 3u), from = (a[j >> 2] >> shift) & 0xffu, to = (b[j >> 2] >> shift) & 0xffu;
+            if (from != to) tally_texel(sh, t, from, to, x, y, z);
+            if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
+        }
     }
+    tally_reduce(sh, t, out);
 }
 
 // out (box-linear, x fastest) = the labels of box b = {x0, y0, z0, x1, y1, z1}, read from the device layout: one thread per texel

@@ -871,6 +871,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     if (!c) return VOLYM_E_INVALID;
     if (filter != VOLYM_FILTER_NEAREST && filter != VOLYM_FILTER_LINEAR)
         return fail(c, VOLYM_E_INVALID, "volym_set_volume: filter must be VOLYM_FILTER_NEAREST or VOLYM_FILTER_LINEAR");
+    clear_label_history(c);                 // (a step belongs to the scene it was recorded in)
     // The box goes back to the whole volume and the mask to all visible: the importances get their cut texels back (the density
     // is replaced below).  This runs before upload_volume has looked at its arguments: a call that then fails leaves box and mask
     // reset and no volume (have_vol false), which is what a failed volym_set_volume leaves in any case.
@@ -899,6 +900,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
 int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!c) return VOLYM_E_INVALID;
+    clear_label_history(c);
     // the labels go, and the mask with them: density and importances get their hidden texels back (the importances are replaced
     // below).  A call that then fails on its arguments leaves the mask reset.
     int rc = retarget(c, current_cut(c), all_visible(current_cut(c)), true);
@@ -920,6 +922,7 @@ int volym_set_importances(volym_ctx* c, const uint8_t* importances, uint32_t nx,
 int volym_set_labels(volym_ctx* c, const uint8_t* labels, uint32_t nx, uint32_t ny, uint32_t nz)
 {
     if (!c) return VOLYM_E_INVALID;
+    clear_label_history(c);
     // new labels mean new segments: all visible, and density and importances get their hidden texels back while the labels
     // that say which they are still exist
     int rc = retarget(c, current_cut(c), all_visible(current_cut(c)), true);

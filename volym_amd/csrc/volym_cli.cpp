@@ -15,7 +15,8 @@
 //   --distance [NAME,...][:MIN_BYTE] prints the distance map's summary for the union of those segments -- solid texels, the deepest
 //   point, the nearest texel of every segment -- and --distance-inside measures inside the set instead (Simple::distance).
 //   --relabel FROM[,FROM...]:TO relabels those segments on the device before the picture (Simple::relabel) and prints what changed;
-//   --labels-out FILE writes the labels as they stand afterwards, raw bytes in the orientation of --labels.
+//   --labels-out FILE writes the labels as they stand afterwards, raw bytes in the orientation of --labels;
+//   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
@@ -27,6 +28,7 @@
 #include <iterator>
 #include <sstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "demo.hpp"
@@ -63,6 +65,7 @@ struct Options {
     std::vector<std::string> measure_names;
     std::vector<std::string> relabel_from;   // --relabel FROM[,FROM...]:TO: relabel segments on the device before the picture (run simple)
     std::string relabel_to;
+    uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
     std::vector<std::string> surface_names;
@@ -195,8 +198,11 @@ int run_simple(const Options& o)
     if (o.crop) demo.set_crop(ctx, assets, o.crop_lo, o.crop_hi);
     if (o.clip) demo.set_clip_plane(ctx, assets, o.clip_normal, o.clip_point);
     if (!o.hide.empty()) demo.set_hidden(ctx, assets, o.hide);
+    if (o.undo != 0u) demo.history(ctx, assets);                  // on before the edits: a step is journalled by the edit it takes back
     volym_relabel_result relabelled{};
     if (!o.relabel_to.empty()) relabelled = demo.relabel(ctx, assets, o.relabel_from, o.relabel_to);
+    std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
+    for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
     demo.compute_pass(ctx);
     ctx.check(volym_sync(ctx.handle()));
@@ -207,14 +213,18 @@ int run_simple(const Options& o)
     f << "P6\n" << W << ' ' << H << "\n255\n";
     for (size_t i = 0; i < static_cast<size_t>(W) * H; ++i) f.write(reinterpret_cast<const char*>(&rgba[4 * i]), 3);
     std::printf("run simple: %s, %ux%u -> %s\n", what.c_str(), W, H, path.c_str());
-    if (!o.relabel_to.empty()) {
-        std::printf("relabel: %llu texels changed", static_cast<unsigned long long>(relabelled.changed));
-        if (relabelled.changed != 0u)
-            std::printf(", box [%u,%u,%u)..[%u,%u,%u)", relabelled.box[0], relabelled.box[1], relabelled.box[2], relabelled.box[3], relabelled.box[4], relabelled.box[5]);
+    const auto print_result = [](const char* what, const volym_relabel_result& r) {
+        std::printf("%s: %llu texels changed", what, static_cast<unsigned long long>(r.changed));
+        if (r.changed != 0u) std::printf(", box [%u,%u,%u)..[%u,%u,%u)", r.box[0], r.box[1], r.box[2], r.box[3], r.box[4], r.box[5]);
         for (int l = 0; l < 256; ++l)
-            if (relabelled.left[l] != 0u || relabelled.arrived[l] != 0u)
-                std::printf("; label %d: -%llu +%llu", l, static_cast<unsigned long long>(relabelled.left[l]), static_cast<unsigned long long>(relabelled.arrived[l]));
+            if (r.left[l] != 0u || r.arrived[l] != 0u)
+                std::printf("; label %d: -%llu +%llu", l, static_cast<unsigned long long>(r.left[l]), static_cast<unsigned long long>(r.arrived[l]));
         std::printf("\n");
+    };
+    if (!o.relabel_to.empty()) print_result("relabel", relabelled);
+    for (const auto& u : undone) {
+        if (u.first) print_result("undo", u.second);
+        else std::printf("undo: nothing to take back\n");
     }
     if (!o.labels_out.empty()) {
         const std::vector<uint8_t> raw = demo.labels_from_device(ctx, assets);
@@ -382,6 +392,7 @@ int main(int argc, char** argv)
                 }
             }
             else if (a == "--labels-out") o.labels_out = next();
+            else if (a == "--undo") o.undo = static_cast<uint32_t>(std::stoul(next()));
             else if (a == "--measure") {
                 o.measure = true;
                 if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") {
@@ -478,7 +489,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--labels-out file]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--undo n] [--labels-out file]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

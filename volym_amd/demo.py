@@ -549,6 +549,32 @@ class GpuContext:
         self._ck(_lib.lib().volym_edit_labels(self.handle, C.byref(relabel.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
+    def label_history(self, budget_bytes):
+        """Keep a history of label edits in at most `budget_bytes` of device memory (20 bytes per changed 16-byte chunk); 0 drops
+        and frees it (include/volym_hip.h volym_label_history; scene.LabelHistory is the definition of the bookkeeping)."""
+        self._ck(_lib.lib().volym_label_history(self.handle, int(budget_bytes)))
+
+    def _swap_labels(self, call):
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(call(self.handle, out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
+    def undo_labels(self):
+        """Take the newest undoable edit back on the device.  Blocks.  Returns what the swap changed, an np.void of
+        _lib.RELABEL_RESULT_DTYPE: the edit's result with left and arrived exchanged.  E_STATE: nothing to undo, history off."""
+        return self._swap_labels(_lib.lib().volym_undo_labels)
+
+    def redo_labels(self):
+        """Carry the newest undone edit out again on the device.  Blocks.  Returns the edit's result."""
+        return self._swap_labels(_lib.lib().volym_redo_labels)
+
+    def label_history_info(self):
+        """volym_label_history_info as a dict: budget_bytes, used_bytes, undo_steps, redo_steps, next_undo_records,
+        next_redo_records, dropped_steps, lost."""
+        info = _lib.LabelHistoryInfo()
+        self._ck(_lib.lib().volym_label_history_info(self.handle, C.byref(info)))
+        return info.as_dict()
+
     def read_labels(self, sub=None):
         """The labels on the device as a uint8 array [z, y, x]: the whole label volume (None) or the sub-box (lo, hi) in texels.
         Blocks."""
@@ -1150,6 +1176,31 @@ class Simple(ComputeDemo):
             self._labels_edited = True
             self._records_for = None
         return scene.relabel_result_dict(result)
+
+    def history(self, ctx, budget_mb=256):
+        """Switch the history of label edits on (budget_mb megabytes of device memory; 0: off), so that undo and redo can take
+        relabel, paint, split_at, keep_largest, grow, shrink and core back.  The labels go to the device first if they are not
+        there: handing labels to the context clears the history, so this must come after them."""
+        if budget_mb:
+            self._ready_to_edit(ctx)
+        ctx.label_history(int(budget_mb * (1 << 20)))
+
+    def _swap(self, ctx, redo):
+        if not ctx.label_history_info()["redo_steps" if redo else "undo_steps"]:
+            return None
+        result = ctx.redo_labels() if redo else ctx.undo_labels()
+        self._labels_edited = True
+        self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def undo(self, ctx):
+        """Take the latest edit back on the device.  Returns scene.relabel_result_dict's dict of what changed (the edit's with left
+        and arrived exchanged), or None when there is nothing to take back (history off, no step, or the step was evicted)."""
+        return self._swap(ctx, False)
+
+    def redo(self, ctx):
+        """Carry the latest undone edit out again.  Returns its result's dict, or None when there is none."""
+        return self._swap(ctx, True)
 
     def _new_segment(self, ctx, name, like):
         """The label value of segment `name`: that of the segments JSON entry of that name or id, or a new entry with the smallest

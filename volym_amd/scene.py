@@ -1506,6 +1506,139 @@ def relabel_result_dict(result):
             "box": (tuple(box[:3]), tuple(box[3:])) if int(result["changed"]) else None}
 
 
+def label_chunks_changed(dims, old, new, bricked):
+    """The number of 16-byte chunks of the device layout in which the label volumes `old` and `new` differ: what one step of the
+    label history journals.  Linear: 16 consecutive texels of the x-fastest order (a chunk may wrap rows and slices).  Bricked: the
+    4 x 4 patch (x // 4, y // 4) of one z."""
+    nx, ny, nz = (int(v) for v in dims)
+    at = np.flatnonzero(np.asarray(old, np.uint8).ravel() != np.asarray(new, np.uint8).ravel())
+    if not bricked:
+        return int(np.unique(at >> 4).size)
+    x, y, z = at % nx, (at // nx) % ny, at // (nx * ny)
+    bx, by = (nx + 3) // 4, (ny + 3) // 4
+    return int(np.unique((z * by + y // 4) * bx + x // 4).size)
+
+
+def relabel_slab_items(dims, box, bricked):
+    """The items the relabel kernel walks for a request over `box` = ((lo), (hi)) (None: the whole volume): the worst case of the
+    chunks it can store, which sizes the staging area of the label history.  Bricked: four chunks per brick the box touches.
+    Linear: the runs of consecutive bytes the box is made of (rows; whole rows merge into one run per z, whole slices into one
+    run), each covered by the aligned chunks it may touch."""
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = ((0, 0, 0), (nx, ny, nz)) if box is None else (tuple(int(v) for v in box[0]), tuple(int(v) for v in box[1]))
+    if bricked:
+        n = [((hi[a] + 3) >> 2) - (lo[a] >> 2) for a in range(3)]
+        return 4 * n[0] * n[1] * n[2]
+    rows = lo[0] == 0 and hi[0] == nx
+    slices = rows and lo[1] == 0 and hi[1] == ny
+    run, runs_y, runs_z = hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]
+    if rows:
+        run, runs_y = run * runs_y, 1
+    if slices:
+        run, runs_z = run * runs_z, 1
+    return ((run + 15) // 16 + 1) * runs_y * runs_z
+
+
+class LabelHistory:
+    """The definition of the label history's rule (include/volym_hip.h volym_label_history), NumPy only: which steps are kept,
+    evicted and given up, and what undo and redo restore and report.  info() equals the device's volym_label_history_info field for
+    field.  A step keeps the texels that changed with their labels on both sides; what it costs is the device's figure, 20 bytes per
+    16-byte chunk of the layout (`bricked`) in which a byte changed."""
+
+    def __init__(self, budget_bytes, dims, bricked):
+        self.dims, self.bricked = tuple(int(v) for v in dims), bool(bricked)
+        self.budget = 0
+        self.steps, self.cursor = [], 0           # oldest first: [0, cursor) can be undone, the rest redone (the nearest first)
+        self.dropped = self.lost = 0
+        self.set_budget(budget_bytes)
+
+    def set_budget(self, budget_bytes):
+        """volym_label_history: 0 drops everything, counters included; another budget keeps the steps that still fit."""
+        budget_bytes = int(budget_bytes)
+        if budget_bytes == 0:
+            self.budget, self.steps, self.cursor, self.dropped, self.lost = 0, [], 0, 0, 0
+            return
+        if self.budget == 0:
+            self.dropped = self.lost = 0
+        self.budget = budget_bytes
+        self._fit()
+
+    def used(self):
+        return _lib.JOURNAL_RECORD_BYTES * sum(s["records"] for s in self.steps)
+
+    def _fit(self):
+        # the oldest undoable steps go first; when none is left, the redo steps that would be redone last
+        while self.used() > self.budget and self.steps:
+            if self.cursor > 0:
+                self.steps.pop(0)
+                self.cursor -= 1
+            else:
+                self.steps.pop()
+            self.dropped += 1
+
+    def clear(self):
+        """What volym_set_labels, volym_set_volume and volym_set_importances do to the history: the steps go, the rest stays."""
+        self.steps, self.cursor = [], 0
+
+    def record(self, old, new, slab_items=None, box=None):
+        """An edit took the labels from `old` to `new`.  slab_items: the items of the request's slab (relabel_slab_items; default:
+        those of `box`, or of the whole volume).  Returns True when a step was kept."""
+        if self.budget == 0:
+            return False
+        old, new = np.asarray(old, np.uint8).ravel(), np.asarray(new, np.uint8).ravel()
+        at = np.flatnonzero(old != new)
+        if at.size == 0:
+            return False
+        del self.steps[self.cursor:]                                  # a recorded edit drops all redo steps
+        records = label_chunks_changed(self.dims, old, new, self.bricked)
+        items = relabel_slab_items(self.dims, box, self.bricked) if slab_items is None else int(slab_items)
+        if records > min(items, self.budget // _lib.JOURNAL_RECORD_BYTES):
+            self.steps, self.cursor = [], 0                           # the whole history is given up: no undo across a gap
+            self.lost += 1
+            return False
+        self.steps.append({"at": at, "before": old[at].copy(), "after": new[at].copy(), "records": records})
+        self.cursor = len(self.steps)
+        self._fit()
+        return True
+
+    def _swap(self, labels, step, a, b):
+        nx, ny, nz = self.dims
+        out = np.array(labels, np.uint8).ravel()
+        at = step["at"]
+        if not np.array_equal(out[at], step[a]):
+            raise ValueError("LabelHistory: the labels are not those the step left")
+        out[at] = step[b]
+        result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+        result["changed"] = at.size
+        result["left"][...] = np.bincount(step[a], minlength=256)
+        result["arrived"][...] = np.bincount(step[b], minlength=256)
+        x, y, z = at % nx, (at // nx) % ny, at // (nx * ny)
+        result["box"][...] = (x.min(), y.min(), z.min(), x.max() + 1, y.max() + 1, z.max() + 1)
+        return out, result
+
+    def undo(self, labels):
+        """(labels with the newest undoable step taken back [flat], result); ValueError when there is none (the device: E_STATE)."""
+        if self.budget == 0 or self.cursor == 0:
+            raise ValueError("LabelHistory: nothing to undo")
+        self.cursor -= 1
+        return self._swap(labels, self.steps[self.cursor], "after", "before")
+
+    def redo(self, labels):
+        """(labels with the newest undone step carried out again [flat], result); ValueError when there is none."""
+        if self.budget == 0 or self.cursor == len(self.steps):
+            raise ValueError("LabelHistory: nothing to redo")
+        self.cursor += 1
+        return self._swap(labels, self.steps[self.cursor - 1], "before", "after")
+
+    def info(self):
+        """volym_label_history_info as GpuContext.label_history_info returns it."""
+        undo, redo = self.cursor, len(self.steps) - self.cursor
+        return {"budget_bytes": self.budget, "used_bytes": self.used(), "undo_steps": undo, "redo_steps": redo,
+                "next_undo_records": self.steps[self.cursor - 1]["records"] if undo else 0,
+                "next_redo_records": self.steps[self.cursor]["records"] if redo else 0,
+                "dropped_steps": self.dropped, "lost": self.lost}
+
+
 PROJECT_STEP_MIN, PROJECT_STEP_MAX = 1.0e-4, 1.0     # volym_update's range for the march step
 
 
