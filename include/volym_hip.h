@@ -990,7 +990,7 @@ int   volym_read_labels(volym_ctx* ctx, const uint32_t sub[6], uint8_t* out);
 
 /* --- undo and redo of label edits (new; the reference has none) ---------------------------------------------------- */
 /* What an edit destroys is small: the 16-byte label chunks of the device layout in which a byte changed.  While the history is on,
- * every volym_edit_labels that changes a texel (no DRY_RUN) journals those chunks -- index and the 16 bytes before the edit, 20 bytes
+ * every volym_edit_labels and every volym_brush_labels that changes a texel (no DRY_RUN) journals those chunks -- index and the 16 bytes before the edit, 20 bytes
  * per chunk, each chunk once -- from the kernel that stores them, and the journal becomes a step in device memory of its own.  Undo
  * swaps the newest undoable step with the labels; redo swaps the newest undone step back; an edit that records drops the redo steps.
  * scene.LabelHistory of the Python package is the host twin of the bookkeeping, equal in every field of the info.
@@ -1025,6 +1025,69 @@ _Static_assert(sizeof(struct volym_label_history_info) == 56, "volym_label_histo
 #endif
 /* VOLYM_E_INVALID: NULL ctx or NULL out.  All 0 while the history is off. */
 int   volym_label_history_info(volym_ctx* ctx, struct volym_label_history_info* out);
+
+/* --- brush: paint labels along a stroke of picked texels (new; the reference has none) ------------------------------ */
+/* Touching a segmentation up where the user points: the texels within a radius of a polyline of picked texels are relabelled by a
+ * table, under a density window, in one call -- one undo step while the history is on.  The context ends up byte for byte where
+ * volym_edit_labels leaves it: where a context handed the edited labels would be.
+ *   The rule (integers only; scene.brush_volume of the Python package is its host twin, equal in every byte).  The stroke is the
+ * union of n_points segments: point i gives the degenerate segment (p_i, p_i), a ball, when i == 0 or point i carries
+ * VOLYM_BRUSH_LIFT, else the capsule (p_{i-1}, p_i) -- a LIFT in the middle breaks the polyline (a drag over a pixel without a
+ * pick).  With <u, v> = sum over the axes of weight[a] * u[a] * v[a] (the distance pass's metric: a round brush is round in
+ * millimetres), d = b - a and w = t - a, texel t lies within segment (a, b) iff
+ *     <d,d> == 0 or <w,d> <= 0:   <w,w> <= r2;
+ *     else <w,d> >= <d,d>:        <t-b, t-b> <= r2;
+ *     else:                       <w,w> * <d,d> - <w,d>^2 <= r2 * <d,d>.
+ * Points lie inside a volume of at most 4096 texels per axis and the weights are at most 64: every inner product is at most
+ * 3 * 64 * 4095^2 < 2^32, so every product above and r2 * <d,d> is below 2^64, and the difference is non-negative by
+ * Cauchy-Schwarz: the rule is exact in unsigned 64-bit arithmetic.  A texel t with label l becomes to[l] iff t lies in box,
+ * to[l] != l, its density byte lies in [min_byte, max_byte] (the scene byte as it stands; with UNCUT the uncut copy as
+ * volym_measure_pass reads it) and t lies within at least one segment.  Every texel is decided once, from the bytes before the edit:
+ * a texel under two capsules and a table that swaps two labels is swapped once.  DRY_RUN fills the result and writes nothing.
+ * r2 == 0 paints the texels exactly on the segments. */
+#define VOLYM_BRUSH_MAX_POINTS 256u
+enum { VOLYM_BRUSH_UNCUT = 1, VOLYM_BRUSH_DRY_RUN = 16 };      /* flags: the values of their VOLYM_RELABEL counterparts */
+enum { VOLYM_BRUSH_LIFT = 1 };                                 /* volym_brush_point.flags */
+struct volym_brush_point {
+    uint16_t x, y, z;           /* a texel of the volume, in the coordinates of struct volym_pick */
+    uint16_t flags;             /* VOLYM_BRUSH_LIFT: no capsule from the point before */
+};                              /* 8 bytes */
+typedef struct volym_brush {
+    uint32_t box[6];            /* as volym_relabel: {x0, y0, z0, x1, y1, z1}, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;   /* 0..255, min <= max: the density window; 0..255 = no window */
+    uint8_t  to[256];           /* old label -> new label; to[l] == l: label l is not touched */
+    uint32_t weight[3];         /* per axis, 1..VOLYM_DISTANCE_WEIGHT_MAX */
+    uint32_t r2;                /* squared radius in the weighted metric; any value */
+    uint32_t n_points;          /* 1..VOLYM_BRUSH_MAX_POINTS */
+    struct volym_brush_point points[VOLYM_BRUSH_MAX_POINTS];
+} volym_brush;                  /* 2360 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(struct volym_brush_point) == 8, "volym_brush_point is 8 bytes");
+static_assert(sizeof(volym_brush) == 2360, "volym_brush is 2360 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(struct volym_brush_point) == 8, "volym_brush_point is 8 bytes");
+_Static_assert(sizeof(volym_brush) == 2360, "volym_brush is 2360 bytes");
+#endif
+/* The brush: a blocking set-up call with the contract of volym_edit_labels (it waits for the frames in flight; the kernel runs on the
+ * first slot's stream; with changed == 0, or DRY_RUN, nothing else is touched and a surface pass stays valid; otherwise counts, boxes,
+ * density and importances follow and a surface pass is stale; out may be NULL).  The kernel walks the request's box cut to the
+ * stroke's hull (volym_brush_box), not the volume.  While the history is on, a call that changes a texel (no DRY_RUN) is one step of
+ * it, journalled into a staging area with room for min(items of that cut box's slab, budget / 20) records: volym_undo_labels and
+ * volym_redo_labels take it as they take an edit.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_brush_check refuses.  VOLYM_E_STATE: what volym_edit_labels refuses of the
+ * context's state.  The native multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_brush_labels(volym_ctx* ctx, const volym_brush* b, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, a window without min_byte <= max_byte <= 255, a weight outside 1..VOLYM_DISTANCE_WEIGHT_MAX, n_points outside
+ * 1..VOLYM_BRUSH_MAX_POINTS, a point outside [0, dims), a point flag other than LIFT.  An empty box is valid: nothing changes.
+ * Pure host arithmetic. */
+int   volym_brush_check(const volym_brush* b, const uint32_t dims[3]);
+/* The box the brush kernel walks: the request's box cut to the stroke's hull -- the points' box grown on axis a by e - 1, e the
+ * smallest integer with weight[a] * e * e > r2 (no texel further than that from every point on one axis lies within a segment),
+ * clipped to the volume.  box_out = {x0, y0, z0, x1, y1, z1}, hi exclusive; all 0 when the two do not meet.  Pure host arithmetic.
+ * VOLYM_E_INVALID for NULL or what volym_brush_check refuses. */
+int   volym_brush_box(const volym_brush* b, const uint32_t dims[3], uint32_t box_out[6]);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

@@ -26,8 +26,8 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
---relabel FROM[,FROM...]:TO, --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
+--relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -294,14 +294,37 @@ def _name_and(text, option, what, number=float):
         raise SystemExit("%s: %s" % (option, what))
 
 
+def _brush_arg(d, ctx, text):
+    """--brush X,Y,Z[/X,Y,Z...]:TO:R2 -> the scene.Brush that paints segment TO over every label along that polyline of texels"""
+    usage = "X,Y,Z[/X,Y,Z...]:TO:R2 -- texels of the stroke, a label value or segment name, the squared radius"
+    rest, r2 = _name_and(text, "--brush", usage, int)
+    at, to = _name_and(rest, "--brush", usage, None)
+    try:
+        points = [tuple(int(v) for v in p.split(",")) for p in at.split("/")]
+    except ValueError:
+        raise SystemExit("--brush: %s" % usage)
+    if not points or any(len(p) != 3 for p in points):
+        raise SystemExit("--brush: %s" % usage)
+    d._ready_to_edit(ctx)
+    return scene.Brush(points, r2, to=d._brush_table(ctx, _segment_arg(to), None), dims=d.dims)
+
+
 def _label_edits(ctx, d, args):
-    """the label edits of the command line on the scene as it stands (demo.Simple.relabel, split_at, keep_largest, grow, shrink):
+    """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, split_at, keep_largest, grow, shrink):
     [(option, result)]"""
     out = []
     try:
         if getattr(args, "relabel", None):
             froms, to = _name_and(args.relabel, "--relabel", "FROM[,FROM...]:TO -- label values or segment names", None)
             out.append(("relabel", d.relabel(ctx, {_segment_arg(f): _segment_arg(to) for f in froms.split(",") if f})))
+        if getattr(args, "brush", None):
+            out.append(("brush", d._brush(ctx, _brush_arg(d, ctx, args.brush))))
+        if getattr(args, "brush_at", None):
+            usage = "X,Y[/X,Y...]:NAME:R -- pixels of the drag, the segment they paint and the radius in texels"
+            rest, r = _name_and(args.brush_at, "--brush-at", usage)
+            at, name = _name_and(rest, "--brush-at", usage, None)
+            s = d.stroke(ctx, [_outline_at_arg(p, "--brush-at") for p in at.split("/")], _segment_arg(name), r, over=None)
+            out.append(("brush_at", None if s["relabel"] is None else dict(s["relabel"], picked=s["picked"], missed=s["missed"], calls=s["calls"])))
         if getattr(args, "split_at", None):
             at, to = _name_and(args.split_at, "--split-at", "X,Y:TO -- a pixel and the segment its piece becomes", None)
             p = d.split_at(ctx, *_outline_at_arg(at, "--split-at"), _segment_arg(to))
@@ -342,7 +365,7 @@ def run_simple(args):
             clipped = {"clip_plane": None if plane is None else {"n": list(plane[0]), "d": plane[1]}}
             d.compute_pass(ctx)
             ctx.sync()
-        # label edits, in the order relabel, split, keep the largest, grow, shrink; the PNG is the frame after them
+        # label edits, in the order relabel, brush, brush at pixels, split, keep the largest, grow, shrink; the PNG is the frame after them
         undo = getattr(args, "undo", None) or 0
         if undo < 0:
             raise SystemExit("--undo: N is a number of edits to take back, got %d" % undo)
@@ -586,6 +609,10 @@ def main(argv=None):
     run.add_argument("--surface-out", metavar="FILE.stl|.obj", help="also write the surface of those segments together as a binary STL or an OBJ mesh")
     run.add_argument("--project", help="MAX|MEAN[,STEP]: also write the maximum or mean intensity projection of the view as <screenshot>_project_<mode>.png")
     run.add_argument("--relabel", help="FROM[,FROM...]:TO: relabel the segments FROM (label values or names) to TO on the device before the picture")
+    run.add_argument("--brush", help="X,Y,Z[/X,Y,Z...]:TO:R2: paint segment TO (a label value or name) over every label within sqrt(R2) texels of that "
+                                     "polyline of texels of the prepared volume, on the device, after --relabel; one undo step")
+    run.add_argument("--brush-at", help="X,Y[/X,Y...]:NAME:R: drag the brush over those pixels: segment NAME within R texels of the polyline of the picked "
+                                        "texels (a pixel without a pick breaks it)")
     run.add_argument("--split-at", help="X,Y:TO: the piece of the segment pixel (X, Y) shows becomes segment TO (a new name gets an entry)")
     run.add_argument("--keep-largest", help="NAME: keep the largest piece of the segment, its other pieces become unlabelled")
     run.add_argument("--grow", help="NAME:R: grow the segment by R texels into the unlabelled texels")

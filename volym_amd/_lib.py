@@ -290,7 +290,33 @@ class RelabelResult(C.Structure):
 # the result as a NumPy structured dtype (GpuContext.edit_labels, scene.relabel_volume)
 RELABEL_RESULT_DTYPE = np.dtype([("changed", "<u8"), ("left", "<u8", (256,)), ("arrived", "<u8", (256,)), ("box", "<u4", (6,))])
 
-JOURNAL_RECORD_BYTES = 20        # what one journalled chunk costs of the history's budget: its index and its 16 bytes
+BRUSH_UNCUT, BRUSH_DRY_RUN = 1, 16                            # volym_brush.flags: the values of their RELABEL counterparts
+BRUSH_LIFT = 1                                                # volym_brush_point.flags
+BRUSH_MAX_POINTS = 256
+
+
+class BrushPoint(C.Structure):
+    """volym_brush_point (include/volym_hip.h): a texel of the stroke and its flags, 8 bytes"""
+    _fields_ = [("x", C.c_uint16), ("y", C.c_uint16), ("z", C.c_uint16), ("flags", C.c_uint16)]
+
+
+class Brush(C.Structure):
+    """volym_brush (include/volym_hip.h): box, flags, density window, label table, axis weights, squared radius and the points of one
+    stroke, 2360 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("to", C.c_uint8 * 256),
+        ("weight", C.c_uint32 * 3),
+        ("r2", C.c_uint32),
+        ("n_points", C.c_uint32),
+        ("points", BrushPoint * BRUSH_MAX_POINTS),
+    ]
+
+
+JOURNAL_RECORD_BYTES = 20     # what one journalled chunk costs of the history's budget: its index and its 16 bytes
 
 
 class LabelHistoryInfo(C.Structure):
@@ -472,6 +498,9 @@ SIGNATURES = {
     "volym_undo_labels": (C.c_int, [_ctx, C.POINTER(RelabelResult)]),
     "volym_redo_labels": (C.c_int, [_ctx, C.POINTER(RelabelResult)]),
     "volym_label_history_info": (C.c_int, [_ctx, C.POINTER(LabelHistoryInfo)]),
+    "volym_brush_labels": (C.c_int, [_ctx, C.POINTER(Brush), C.POINTER(RelabelResult)]),
+    "volym_brush_check": (C.c_int, [C.POINTER(Brush), C.POINTER(C.c_uint32)]),
+    "volym_brush_box": (C.c_int, [C.POINTER(Brush), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

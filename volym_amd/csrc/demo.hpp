@@ -8,6 +8,7 @@
 #pragma once
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -167,6 +168,31 @@ public:
         for (const std::string& s : from) r.to[label_value_of(a, s)] = target;
         volym_relabel_result out{};
         ctx.check(volym_edit_labels(ctx.handle(), &r, &out));
+        records_current_ = false;
+        return out;
+    }
+    // New: one stroke of the brush on the device (volym_brush_labels): the texels within sqrt(r2) texels of the polyline of `points`
+    // (texels of the prepared volume, as a pick reports them; at most VOLYM_BRUSH_MAX_POINTS), whatever their label, get the label of
+    // `to`, which must name a segment of the table or be a label value.  One call, one step of the history.
+    volym_relabel_result brush(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::array<uint32_t, 3>>& points, const std::string& to, uint32_t r2)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "brush: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        if (points.empty() || points.size() > VOLYM_BRUSH_MAX_POINTS) throw Error(VOLYM_E_INVALID, "brush: 1..256 points");
+        volym_brush b{};
+        b.box[3] = a.nx; b.box[4] = a.ny; b.box[5] = a.nz;
+        b.max_byte = 255u;
+        const uint8_t target = label_value_of(a, to);
+        for (int l = 0; l < 256; ++l) b.to[l] = target;
+        b.weight[0] = b.weight[1] = b.weight[2] = 1u;
+        b.r2 = r2;
+        b.n_points = static_cast<uint32_t>(points.size());
+        for (size_t i = 0; i < points.size(); ++i) {
+            for (int k = 0; k < 3; ++k) if (points[i][k] > 0xffffu) throw Error(VOLYM_E_INVALID, "brush: a point lies outside the volume");
+            b.points[i].x = static_cast<uint16_t>(points[i][0]); b.points[i].y = static_cast<uint16_t>(points[i][1]); b.points[i].z = static_cast<uint16_t>(points[i][2]);
+        }
+        volym_relabel_result out{};
+        ctx.check(volym_brush_labels(ctx.handle(), &b, &out));
         records_current_ = false;
         return out;
     }

@@ -1,7 +1,8 @@
 // The label edit (volym_edit_labels, volym_relabel_check, volym_read_labels): included at the end of scene_bytes.hip, beside the
 // kernels it launches (relabel_kernels.h) and the transition whose pieces it is built from (rewrite, ensure_uncropped_copies,
 // refresh_macro_cells, scan_label_stats), and its history (volym_label_history, volym_undo_labels, volym_redo_labels,
-// volym_label_history_info).  Blocking set-up calls like the other edits of that unit.
+// volym_label_history_info).  Blocking set-up calls like the other edits of that unit.  brush.inc, included after this file, builds
+// the brush on edit_labels, LabelEdit and editable_state.
 
 #include <cstddef>
 
@@ -124,23 +125,34 @@ static void record_step(volym_ctx* c, const volym_relabel_result& res, uint64_t 
 // the working result of an edit, an undo or a redo in device memory: the result, then the journal's counter
 struct DeviceRelabelResult { volym_relabel_result result; uint32_t records, pad; };
 
+// What the edit's transition needs to know of a request, whichever kernel carries it out (volym_edit_labels here, the brush of
+// brush.inc): the box its kernel walks and keeps to, the table, DRY_RUN, and the name errors carry.
+struct LabelEdit {
+    const uint32_t* box;
+    const uint8_t* to;
+    bool dry;
+    const char* who;
+};
+
 // The edit's own transition, the counterpart of retarget for a change of labels under a (box, plane, mask) that stays (follow_labels).
-// With no texel changed (or DRY_RUN) nothing but the result is written.  A failure after the kernel has stored leaves bytes that
-// belong to neither state: the context then asks for volym_set_volume again, as after a failed retarget.
-static int edit_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_result& res)
+// launch(stream, grid, out, to, slab, items, journal) enqueues the request's kernel over the slab of r.box (keep = inside that box);
+// journal is NULL unless the history is on and the request is no DRY_RUN.  With no texel changed (or DRY_RUN) nothing but the result is
+// written.  A failure after the kernel has stored leaves bytes that belong to neither state: the context then asks for
+// volym_set_volume again, as after a failed retarget.
+template <class Launch>
+static int edit_labels(volym_ctx* c, const LabelEdit& r, volym_relabel_result& res, Launch launch)
 {
-    const bool with_ids = (r->flags & VOLYM_RELABEL_IDS) != 0u, with_map = (r->flags & VOLYM_RELABEL_DISTANCE) != 0u;
-    const bool uncut_bytes = (r->flags & VOLYM_RELABEL_UNCUT) != 0u, dry = (r->flags & VOLYM_RELABEL_DRY_RUN) != 0u;
+    const bool dry = r.dry;
     const bool journalled = c->history_budget != 0u && !dry;
     std::memset(&res, 0, sizeof res);
-    for (int a = 0; a < 3; ++a) if (r->box[a] == r->box[3 + a]) return VOLYM_OK;      // an empty box: nothing to walk
+    for (int a = 0; a < 3; ++a) if (r.box[a] == r.box[3 + a]) return VOLYM_OK;        // an empty box: nothing to walk
 
     int rc = quiesce_slots(c);
     if (rc != VOLYM_OK) return rc;
     // A hidden label that has voxels has made the uncut copies already; one without voxels has not (retarget takes the idle path for
     // it), and texels are about to move into it.  The bytes are still uncut then: the precondition of ensure_uncropped_copies.
     bool hidden_target = false;
-    for (int l = 0; l < 256; ++l) hidden_target = hidden_target || (r->to[l] != l && c->seg_hidden[r->to[l]]);
+    for (int l = 0; l < 256; ++l) hidden_target = hidden_target || (r.to[l] != l && c->seg_hidden[r.to[l]]);
     if (hidden_target || mask_active(c)) {
         rc = ensure_uncropped_copies(c, true);                            // in stream order in front of the kernel and the rewrites
         if (rc != VOLYM_OK) return rc;
@@ -148,7 +160,7 @@ static int edit_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_resul
 
     const hipStream_t stream = c->slot0().stream;
     CropSlab s;
-    const uint64_t items = make_crop_slab(c, c->bricked, r->box, nullptr, s);
+    const uint64_t items = make_crop_slab(c, c->bricked, r.box, nullptr, s);
     // the staging area holds the slab's worst case, one record per item, or what the budget holds: past that the kernel only counts
     const uint64_t capacity = journalled ? std::min<uint64_t>(items, c->history_budget / JOURNAL_RECORD_BYTES) : 0u;
     if (journalled) {
@@ -164,36 +176,15 @@ static int edit_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_resul
     e = hipMemcpyAsync(d_res, &init, sizeof init, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) {
         // keep = inside the request's box, whatever the crop box and the plane are: the cuts are in the bytes the window reads
-        for (int a = 0; a < 3; ++a) { s.box_lo[a] = r->box[a]; s.box_hi[a] = r->box[3 + a]; }
+        for (int a = 0; a < 3; ++a) { s.box_lo[a] = r.box[a]; s.box_hi[a] = r.box[3 + a]; }
         s.planes = 0u; s.pn[0] = s.pn[1] = s.pn[2] = s.pd = 0;
-        RelabelRule rule = {};
-        rule.min_byte = r->min_byte; rule.max_byte = r->max_byte;
-        rule.id_lo = r->id_lo; rule.id_hi = r->id_hi; rule.ids_except = (r->flags & VOLYM_RELABEL_IDS_EXCEPT) ? 1u : 0u;
-        rule.d2_lo = r->d2_lo; rule.d2_hi = r->d2_hi;
-        rule.store = dry ? 0u : 1u;
-        std::memcpy(rule.ids_box, c->component_box, sizeof rule.ids_box);
-        std::memcpy(rule.map_box, c->distance_box, sizeof rule.map_box);
         LabelTable to;
-        std::memcpy(to.v, r->to, 256);
+        std::memcpy(to.v, r.to, 256);
         volym_relabel_result* const dr = &d_res->result;
         const RelabelOut out = {reinterpret_cast<unsigned long long*>(&dr->changed), reinterpret_cast<unsigned long long*>(dr->left),
                                 reinterpret_cast<unsigned long long*>(dr->arrived), dr->box};
-        const uint4* vol = reinterpret_cast<const uint4*>(uncut_bytes && c->d_vol0 ? c->d_vol0 : c->d_vol);
-        const uint32_t* ids = with_ids ? c->component_ids.ptr : nullptr;
-        const uint32_t* dmap = with_map ? c->distance_map.ptr : nullptr;
-        const dim3 grid(stream_grid(c, items));
-        if (journalled) {
-            const LabelJournal journal = {c->journal_index.ptr, c->journal_old.ptr, &d_res->records, static_cast<uint32_t>(capacity)};
-            const auto kernel = with_ids ? (with_map ? volym_relabel_journal_kernel<true, true> : volym_relabel_journal_kernel<true, false>)
-                                         : (with_map ? volym_relabel_journal_kernel<false, true> : volym_relabel_journal_kernel<false, false>);
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), vol, ids, dmap, out, to, s, rule, journal, c->nx, c->ny,
-                               c->nz, c->bricked ? 1u : 0u, static_cast<uint32_t>(items));
-        } else {
-            const auto kernel = with_ids ? (with_map ? volym_relabel_kernel<true, true> : volym_relabel_kernel<true, false>)
-                                         : (with_map ? volym_relabel_kernel<false, true> : volym_relabel_kernel<false, false>);
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), vol, ids, dmap, out, to, s, rule, c->nx, c->ny, c->nz,
-                               c->bricked ? 1u : 0u, static_cast<uint32_t>(items));
-        }
+        const LabelJournal journal = {c->journal_index.ptr, c->journal_old.ptr, &d_res->records, static_cast<uint32_t>(capacity)};
+        launch(stream, dim3(stream_grid(c, items)), out, to, s, static_cast<uint32_t>(items), journalled ? &journal : nullptr);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&back, d_res, sizeof back, hipMemcpyDeviceToHost, stream);
@@ -201,7 +192,7 @@ static int edit_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_resul
     (void)hipFree(d_res);
     if (e != hipSuccess) {
         if (!dry) c->have_vol = c->have_frame = false;                    // (the kernel may have stored)
-        return fail(c, VOLYM_E_HIP, std::string("volym_edit_labels: ") + hipGetErrorString(e));
+        return fail(c, VOLYM_E_HIP, std::string(r.who) + ": " + hipGetErrorString(e));
     }
     res = back.result;
     if (res.changed == 0u) { std::memset(res.box, 0, sizeof res.box); return VOLYM_OK; }
@@ -209,9 +200,41 @@ static int edit_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_resul
     if (dry) return VOLYM_OK;
 
     if (journalled) record_step(c, res, back.records, capacity);
-    rc = follow_labels(c, res, "volym_edit_labels");
+    rc = follow_labels(c, res, r.who);
     if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
     return rc;
+}
+
+// volym_edit_labels' request as an edit: the relabel kernel of its flags, plain or journalling
+static int relabel_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_result& res)
+{
+    const bool with_ids = (r->flags & VOLYM_RELABEL_IDS) != 0u, with_map = (r->flags & VOLYM_RELABEL_DISTANCE) != 0u;
+    const bool uncut_bytes = (r->flags & VOLYM_RELABEL_UNCUT) != 0u, dry = (r->flags & VOLYM_RELABEL_DRY_RUN) != 0u;
+    RelabelRule rule = {};
+    rule.min_byte = r->min_byte; rule.max_byte = r->max_byte;
+    rule.id_lo = r->id_lo; rule.id_hi = r->id_hi; rule.ids_except = (r->flags & VOLYM_RELABEL_IDS_EXCEPT) ? 1u : 0u;
+    rule.d2_lo = r->d2_lo; rule.d2_hi = r->d2_hi;
+    rule.store = dry ? 0u : 1u;
+    std::memcpy(rule.ids_box, c->component_box, sizeof rule.ids_box);
+    std::memcpy(rule.map_box, c->distance_box, sizeof rule.map_box);
+    const uint32_t* ids = with_ids ? c->component_ids.ptr : nullptr;
+    const uint32_t* dmap = with_map ? c->distance_map.ptr : nullptr;
+    const LabelEdit edit = {r->box, r->to, dry, "volym_edit_labels"};
+    return edit_labels(c, edit, res, [&](hipStream_t stream, dim3 grid, const RelabelOut& out, const LabelTable& to, const CropSlab& s, uint32_t items,
+                                         const LabelJournal* journal) {
+        const uint4* vol = reinterpret_cast<const uint4*>(uncut_bytes && c->d_vol0 ? c->d_vol0 : c->d_vol);     // (after ensure_uncropped_copies)
+        if (journal) {
+            const auto kernel = with_ids ? (with_map ? volym_relabel_journal_kernel<true, true> : volym_relabel_journal_kernel<true, false>)
+                                         : (with_map ? volym_relabel_journal_kernel<false, true> : volym_relabel_journal_kernel<false, false>);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), vol, ids, dmap, out, to, s, rule, *journal, c->nx, c->ny,
+                               c->nz, c->bricked ? 1u : 0u, items);
+        } else {
+            const auto kernel = with_ids ? (with_map ? volym_relabel_kernel<true, true> : volym_relabel_kernel<true, false>)
+                                         : (with_map ? volym_relabel_kernel<false, true> : volym_relabel_kernel<false, false>);
+            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), vol, ids, dmap, out, to, s, rule, c->nx, c->ny, c->nz,
+                               c->bricked ? 1u : 0u, items);
+        }
+    });
 }
 
 // Undo (redo false) or redo: the step next to the cursor is swapped with the labels, the device counts what the swap changed, and the
@@ -327,7 +350,7 @@ int volym_edit_labels(volym_ctx* c, const volym_relabel* r, struct volym_relabel
     }
     HIPCHK(c, hipSetDevice(c->device));
     volym_relabel_result res;
-    const int rc = edit_labels(c, r, res);
+    const int rc = relabel_labels(c, r, res);
     if (rc == VOLYM_OK && out) *out = res;
     return rc;
 }

@@ -3,7 +3,8 @@
 // points of all of these.  The frame loop (raymarch.hip) reads what this unit writes; what the two need from each other is
 // declared in context.hpp.  Everything here is blocking set-up path, except the measure pass at the end (measure.inc, measure_kernels.h),
 // which only reads these bytes and is enqueue-only, and the label edit after it (relabel.inc, relabel_kernels.h), which rewrites
-// labels in place and carries density and importances along by the same invariant.
+// labels in place and carries density and importances along by the same invariant, and the brush (brush.inc, brush_kernels.h), the
+// same edit decided by a stroke's geometry.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "scene_kernels.h"
 #include "measure_kernels.h"
 #include "relabel_kernels.h"
+#include "brush_kernels.h"
 
 using namespace volym;
 
@@ -998,3 +1000,6 @@ int volym_label_counts(volym_ctx* c, uint64_t counts[256])
 
 // ---- editing labels -------------------------------------------------------------------------------------------------------
 #include "relabel.inc"
+
+// ---- the brush: the edit whose texels a stroke decides ----------------------------------------------------------------------
+#include "brush.inc"

@@ -16,6 +16,7 @@
 //   point, the nearest texel of every segment -- and --distance-inside measures inside the set instead (Simple::distance).
 //   --relabel FROM[,FROM...]:TO relabels those segments on the device before the picture (Simple::relabel) and prints what changed;
 //   --labels-out FILE writes the labels as they stand afterwards, raw bytes in the orientation of --labels;
+//   --brush X,Y,Z[/X,Y,Z...]:TO:R2 paints label TO within sqrt(R2) texels of that polyline of texels (Simple::brush), after --relabel;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
 #include <algorithm>
 #include <cctype>
@@ -65,6 +66,9 @@ struct Options {
     std::vector<std::string> measure_names;
     std::vector<std::string> relabel_from;   // --relabel FROM[,FROM...]:TO: relabel segments on the device before the picture (run simple)
     std::string relabel_to;
+    std::vector<std::array<uint32_t, 3>> brush_points;   // --brush X,Y,Z[/X,Y,Z...]:TO:R2: one stroke of the brush in texel coordinates (run simple)
+    std::string brush_to;
+    uint32_t brush_r2 = 0;
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -201,6 +205,8 @@ int run_simple(const Options& o)
     if (o.undo != 0u) demo.history(ctx, assets);                  // on before the edits: a step is journalled by the edit it takes back
     volym_relabel_result relabelled{};
     if (!o.relabel_to.empty()) relabelled = demo.relabel(ctx, assets, o.relabel_from, o.relabel_to);
+    volym_relabel_result brushed{};
+    if (!o.brush_to.empty()) brushed = demo.brush(ctx, assets, o.brush_points, o.brush_to, o.brush_r2);       // after --relabel, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -222,6 +228,7 @@ int run_simple(const Options& o)
         std::printf("\n");
     };
     if (!o.relabel_to.empty()) print_result("relabel", relabelled);
+    if (!o.brush_to.empty()) print_result("brush", brushed);
     for (const auto& u : undone) {
         if (u.first) print_result("undo", u.second);
         else std::printf("undo: nothing to take back\n");
@@ -391,6 +398,38 @@ int main(int argc, char** argv)
                     pos = comma + 1u;
                 }
             }
+            else if (a == "--brush") {
+                const char* usage = "--brush: X,Y,Z[/X,Y,Z...]:TO:R2 -- texels of the stroke, a label value or segment name, the squared radius";
+                const std::string v = next();
+                const size_t last = v.rfind(':'), first = last == std::string::npos || last == 0u ? std::string::npos : v.rfind(':', last - 1u);
+                if (first == std::string::npos || first == 0u || first + 1u >= last || last + 1u >= v.size()) throw Error(VOLYM_E_INVALID, usage);
+                o.brush_to = v.substr(first + 1u, last - first - 1u);
+                try {
+                    size_t used = 0;
+                    const unsigned long r2 = std::stoul(v.substr(last + 1u), &used);
+                    if (used != v.size() - last - 1u || r2 > 0xffffffffUL) throw Error(VOLYM_E_INVALID, usage);
+                    o.brush_r2 = static_cast<uint32_t>(r2);
+                    size_t pos = 0;
+                    while (pos < first) {
+                        const size_t slash = std::min(v.find('/', pos), first);
+                        std::array<uint32_t, 3> p{};
+                        const std::string one = v.substr(pos, slash - pos);
+                        size_t at = 0;
+                        for (int k = 0; k < 3; ++k) {
+                            if (at >= one.size() || one[at] < '0' || one[at] > '9') throw Error(VOLYM_E_INVALID, usage);
+                            const unsigned long c = std::stoul(one.substr(at), &used);
+                            if (c > 0xffffUL) throw Error(VOLYM_E_INVALID, usage);
+                            p[static_cast<size_t>(k)] = static_cast<uint32_t>(c);
+                            at += used;
+                            if (k < 2) { if (at >= one.size() || one[at] != ',') throw Error(VOLYM_E_INVALID, usage); ++at; }
+                        }
+                        if (at != one.size()) throw Error(VOLYM_E_INVALID, usage);
+                        o.brush_points.push_back(p);
+                        pos = slash + 1u;
+                    }
+                } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
+                if (o.brush_points.empty() || o.brush_points.size() > VOLYM_BRUSH_MAX_POINTS) throw Error(VOLYM_E_INVALID, usage);
+            }
             else if (a == "--labels-out") o.labels_out = next();
             else if (a == "--undo") o.undo = static_cast<uint32_t>(std::stoul(next()));
             else if (a == "--measure") {
@@ -489,7 +528,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--undo n] [--labels-out file]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--brush x,y,z[/x,y,z...]:to:r2] [--undo n] [--labels-out file]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

@@ -549,6 +549,15 @@ class GpuContext:
         self._ck(_lib.lib().volym_edit_labels(self.handle, C.byref(relabel.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
+    def brush_labels(self, brush):
+        """One stroke of the brush on the device (include/volym_hip.h volym_brush_labels; scene.brush_volume is its definition): the
+        texels within the stroke's radius of its polyline become to[label] where the table, the box and the density window say so.
+        `brush` is a scene.Brush.  Everything follows as after edit_labels, and the call is one step of the history.  Blocks.
+        Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_brush_labels(self.handle, C.byref(brush.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
     def label_history(self, budget_bytes):
         """Keep a history of label edits in at most `budget_bytes` of device memory (20 bytes per changed 16-byte chunk); 0 drops
         and frees it (include/volym_hip.h volym_label_history; scene.LabelHistory is the definition of the bookkeeping)."""
@@ -1304,6 +1313,88 @@ class Simple(ComputeDemo):
         ctx.distance_pass(d)
         return self._edit(ctx, scene.Relabel(None, _lib.RELABEL_DISTANCE, to={l: self._new_segment(ctx, to, l)},
                                              d2=(self._band(unit, r) + 1, _lib.DISTANCE_NONE - 1), dims=self.dims))
+
+    def _brush(self, ctx, brush):
+        result = ctx.brush_labels(scene.check_brush(brush, self.dims))
+        if int(result["changed"]) and not brush.flags & _lib.BRUSH_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def _brush_table(self, ctx, name, over):
+        """the table of a stroke that paints segment `name` (None: erases to label 0) over the segments `over` (None: every label)"""
+        sources = list(range(256)) if over is None else self._label_values(over)
+        value = 0 if name is None else self._new_segment(ctx, name, sources[0] if sources else 0)
+        return {l: value for l in sources if l != value}
+
+    def stroke(self, ctx, pixels, name, radius, over=(0,), window=(0, 255), spacing=(1, 1, 1), alpha_min=0.5, uncut=False):
+        """Paint along a drag: one pick pass over the rect of `pixels` [(x, y), ...], then the texels within `radius` (texels of the
+        finest axis of `spacing`) of the polyline of the picked texels, of the segments `over` (names, ids or label values; None:
+        every label) and with a density byte in `window`, join segment `name` (as split_at takes it; None erases to label 0).  A
+        pixel without a pick breaks the polyline: the next picked point starts a new piece of it.  More than 256 picked points
+        become several calls of the brush, the last point of one repeated as the first of the next -- and EACH CALL IS AN UNDO
+        STEP of its own.  Returns {"picked", "missed", "calls", "relabel": the results' dicts summed (changed, left, arrived; box:
+        the hull), None when no pixel picks}."""
+        self._ready_to_edit(ctx)
+        pixels = [(int(x), int(y)) for x, y in pixels]
+        if not pixels:
+            raise ValueError("a stroke needs at least one pixel")
+        for x, y in pixels:
+            if not (0 <= x < ctx.width and 0 <= y < ctx.height):
+                raise ValueError("pixel (%r, %r) is not inside the %d x %d frame" % (x, y, ctx.width, ctx.height))
+        x0, y0 = min(p[0] for p in pixels), min(p[1] for p in pixels)
+        ctx.pick_pass((x0, y0, max(p[0] for p in pixels) - x0 + 1, max(p[1] for p in pixels) - y0 + 1), alpha_min)
+        records = ctx.read_picks()
+        self._records_for = None        # (the rect's pass took the place of a whole frame's records)
+        points, lift = [], False
+        for x, y in pixels:
+            r = records[y - y0, x - x0]
+            if int(r["status"]) != _lib.PICK_HIT:
+                lift = True
+                continue
+            points.append((int(r["x"]), int(r["y"]), int(r["z"]), _lib.BRUSH_LIFT if lift and points else 0))
+            lift = False
+        out = {"picked": len(points), "missed": len(pixels) - len(points), "calls": 0, "relabel": None}
+        if not points:
+            return out
+        weights, unit = scene.distance_weights(spacing)
+        table = self._brush_table(ctx, name, over)
+        flags = _lib.BRUSH_UNCUT if uncut else 0
+        total = None
+        first = 0
+        while first < len(points):
+            part = points[first:first + _lib.BRUSH_MAX_POINTS]
+            part[0] = part[0][:3] + (0,)
+            res = self._brush(ctx, scene.Brush(part, self._band(1.0, radius), None, flags, window, table, weights, dims=self.dims))
+            out["calls"] += 1
+            if total is None:
+                total = res
+            elif res["changed"]:
+                for k in ("left", "arrived"):
+                    for l, v in res[k].items():
+                        total[k][l] = total[k].get(l, 0) + v
+                total["box"] = res["box"] if total["box"] is None else (tuple(min(a, b) for a, b in zip(total["box"][0], res["box"][0])),
+                                                                       tuple(max(a, b) for a, b in zip(total["box"][1], res["box"][1])))
+                total["changed"] += res["changed"]
+            if first + _lib.BRUSH_MAX_POINTS >= len(points):
+                break
+            first += _lib.BRUSH_MAX_POINTS - 1                          # the last point again: the capsule to the next one
+        out["relabel"] = total
+        return out
+
+    def brush_at(self, ctx, x, y, name, radius, over=(0,), window=(0, 255), spacing=(1, 1, 1), alpha_min=0.5):
+        """Click to paint: pick pixel (x, y) and paint a ball of `radius` (texels of the finest axis of `spacing`; round in the units
+        of `spacing`) at the picked texel, as stroke paints: the texels of the segments `over` with a density byte in `window` join
+        segment `name` (None erases to label 0).  One call of the brush, one undo step.  Returns the pick with a "relabel" entry (the
+        result's dict; None when the pixel shows no sample)."""
+        self._ready_to_edit(ctx)
+        p = self.pick(ctx, x, y, alpha_min)
+        p["relabel"] = None
+        if p["status"] == "hit":
+            weights, unit = scene.distance_weights(spacing)
+            table = self._brush_table(ctx, name, over)
+            p["relabel"] = self._brush(ctx, scene.Brush([p["texel"]], self._band(1.0, radius), None, 0, window, table, weights, dims=self.dims))
+        return p
 
     def save_labels(self, ctx, path):
         """Write the labels as they stand on the device to `path`: raw bytes in the orientation prepare_volume read, so that the

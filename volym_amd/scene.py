@@ -1497,6 +1497,202 @@ def relabel_volume(prepared, dims, r, labels, ids=None, ids_box=None, dmap=None,
     return new, result
 
 
+class Brush:
+    """volym_brush (include/volym_hip.h): one stroke of the brush.  box, window and to as Relabel takes them; flags: _lib.BRUSH_UNCUT |
+    BRUSH_DRY_RUN; weight: the distance pass's axis weights (distance_weights); r2: the squared radius in that metric; points: up to
+    _lib.BRUSH_MAX_POINTS texels (x, y, z) or (x, y, z, flags), flags = _lib.BRUSH_LIFT: no capsule from the point before."""
+
+    def __init__(self, points, r2, box=None, flags=0, window=(0, 255), to=None, weight=(1, 1, 1), dims=None):
+        if box is None:
+            if dims is None:
+                raise ValueError("a brush request without a box needs the volume's dims")
+            box = ((0, 0, 0), tuple(int(v) for v in dims))
+        lo, hi = box
+        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+        self.weight = tuple(int(v) for v in weight)
+        self.r2 = int(r2)
+        self.points = [tuple(int(v) for v in p) + ((0,) if len(p) == 3 else ()) for p in points]
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "brush", ("points", "r2", "box", "flags", "window", "to", "weight"), kw)
+
+    def to_c(self):
+        """The _lib.Brush of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Brush()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("brush: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        if not 0 <= self.flags < 2 ** 32 or not 0 <= self.r2 < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("brush: flags, r2 and the window's ends must be u32")
+        if len(self.weight) != 3 or not all(0 <= x < 2 ** 32 for x in self.weight):
+            raise ValueError("brush: three u32 weights")
+        c.flags, c.r2 = self.flags, self.r2
+        c.min_byte, c.max_byte = self.window
+        if self.to.size != 256 or not ((self.to >= 0) & (self.to <= 255)).all():
+            raise ValueError("brush: the table is 256 bytes")
+        c.to = (C.c_uint8 * 256)(*[int(g) for g in self.to])
+        c.weight = (C.c_uint32 * 3)(*self.weight)
+        if len(self.points) > _lib.BRUSH_MAX_POINTS:
+            raise ValueError("brush: at most %d points, got %d" % (_lib.BRUSH_MAX_POINTS, len(self.points)))
+        c.n_points = len(self.points)
+        for i, p in enumerate(self.points):
+            if len(p) != 4 or not all(0 <= x < 2 ** 16 for x in p):
+                raise ValueError("brush: a point is (x, y, z[, flags]) of u16, got %r" % (p,))
+            c.points[i].x, c.points[i].y, c.points[i].z, c.points[i].flags = p
+        return c
+
+
+def check_brush(brush, dims):
+    """The validity rules of volym_brush_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, weights in 1.._lib.DISTANCE_WEIGHT_MAX, 1.._lib.BRUSH_MAX_POINTS points inside the volume, no point
+    flag but LIFT; r2 is any u32.  Returns the request; raises ValueError."""
+    b = brush
+    dims = [int(v) for v in dims]
+    lo, hi = b.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("brush: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("brush box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    if b.flags & ~(_lib.BRUSH_UNCUT | _lib.BRUSH_DRY_RUN) or b.flags < 0:
+        raise ValueError("brush: unknown flag bits in %#x" % b.flags)
+    if len(b.window) != 2 or not 0 <= b.window[0] <= b.window[1] <= 255:
+        raise ValueError("brush: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (b.window,))
+    if len(b.weight) != 3 or not all(1 <= w <= _lib.DISTANCE_WEIGHT_MAX for w in b.weight):
+        raise ValueError("brush: three weights in 1..%d, got %r" % (_lib.DISTANCE_WEIGHT_MAX, b.weight))
+    if not 0 <= b.r2 < 2 ** 32:
+        raise ValueError("brush: r2 is a u32, got %r" % (b.r2,))
+    if not 1 <= len(b.points) <= _lib.BRUSH_MAX_POINTS:
+        raise ValueError("brush: 1..%d points, got %d" % (_lib.BRUSH_MAX_POINTS, len(b.points)))
+    for p in b.points:
+        if len(p) != 4 or not all(0 <= p[a] < dims[a] for a in range(3)):
+            raise ValueError("brush: point %r lies outside the volume %r" % (p, tuple(dims)))
+        if p[3] & ~_lib.BRUSH_LIFT or p[3] < 0:
+            raise ValueError("brush: unknown point flag bits in %#x" % p[3])
+    if np.asarray(b.to).size != 256:
+        raise ValueError("brush: the table has 256 entries")
+    return b
+
+
+def brush_reach(r2, weight):
+    """How far a brush of squared radius r2 reaches along an axis of this weight, in texels: the largest m with weight * m * m <= r2."""
+    import math
+    return math.isqrt(int(r2) // int(weight))
+
+
+def brush_segments(brush):
+    """The segments of the stroke as ((ax, ay, az), (bx, by, bz)): point i gives (p_i, p_i) when i == 0 or it carries LIFT, else
+    (p_{i-1}, p_i)."""
+    out = []
+    for i, p in enumerate(brush.points):
+        q = p if i == 0 or p[3] & _lib.BRUSH_LIFT else brush.points[i - 1]
+        out.append((tuple(q[:3]), tuple(p[:3])))
+    return out
+
+
+def _brush_span(least, most, brush, dims):
+    reach = [brush_reach(brush.r2, w) for w in brush.weight]
+    return (tuple(max(least[a] - reach[a], 0) for a in range(3)), tuple(min(most[a] + reach[a] + 1, int(dims[a])) for a in range(3)))
+
+
+def brush_box(brush, dims):
+    """volym_brush_box: the box the brush kernel walks, ((lo), (hi)) -- the request's box cut to the stroke's hull (the points' box
+    grown per axis by the brush's reach, clipped to the volume); ((0, 0, 0), (0, 0, 0)) when the two do not meet."""
+    b = check_brush(brush, dims)
+    pts = np.array([p[:3] for p in b.points], np.int64)
+    lo, hi = _brush_span(pts.min(axis=0).tolist(), pts.max(axis=0).tolist(), b, dims)
+    lo = tuple(max(lo[a], b.box[0][a]) for a in range(3))
+    hi = tuple(min(hi[a], b.box[1][a]) for a in range(3))
+    if any(lo[a] >= hi[a] for a in range(3)):
+        return ((0, 0, 0), (0, 0, 0))
+    return (lo, hi)
+
+
+def brush_within(t, a, b, weight, r2):
+    """Does texel t lie within segment (a, b)?  The integer rule of include/volym_hip.h, on Python integers."""
+    dot = lambda u, v: sum(int(weight[k]) * int(u[k]) * int(v[k]) for k in range(3))
+    d = [int(b[k]) - int(a[k]) for k in range(3)]
+    w = [int(t[k]) - int(a[k]) for k in range(3)]
+    dd, wd, ww = dot(d, d), dot(w, d), dot(w, w)
+    if dd == 0 or wd <= 0:
+        return ww <= r2
+    if wd >= dd:
+        u = [int(t[k]) - int(b[k]) for k in range(3)]
+        return dot(u, u) <= r2
+    return ww * dd - wd * wd <= r2 * dd
+
+
+def brush_mask(brush, dims):
+    """The texels within at least one segment of the stroke, as a bool array [z, y, x] of the volume: the rule above in NumPy's 64-bit
+    integers (every inner product is below 2^32 and every product below 2^64), segment by segment over the segment's own box."""
+    nx, ny, nz = (int(v) for v in dims)
+    hit = np.zeros((nz, ny, nx), bool)
+    wt = [int(w) for w in brush.weight]
+    r2 = int(brush.r2)
+    for a, b in brush_segments(brush):
+        lo, hi = _brush_span([min(a[k], b[k]) for k in range(3)], [max(a[k], b[k]) for k in range(3)], brush, dims)
+        z, y, x = np.meshgrid(*[np.arange(lo[k], hi[k], dtype=np.int64) for k in (2, 1, 0)], indexing="ij")
+        t = (x, y, z)
+        w = [t[k] - a[k] for k in range(3)]
+        d = [b[k] - a[k] for k in range(3)]
+        ww = sum(wt[k] * w[k] * w[k] for k in range(3))
+        dd = sum(wt[k] * d[k] * d[k] for k in range(3))
+        if dd == 0:
+            inside = ww <= r2
+        else:
+            wd = sum(wt[k] * d[k] * w[k] for k in range(3))
+            u = [t[k] - b[k] for k in range(3)]
+            uu = sum(wt[k] * u[k] * u[k] for k in range(3))
+            mid = (wd > 0) & (wd < dd)
+            p = np.where(mid, wd, 0).astype(np.uint64)
+            perp = ww.astype(np.uint64) * np.uint64(dd) - p * p          # (>= 0 where mid, by Cauchy-Schwarz; unused elsewhere)
+            inside = np.where(wd <= 0, ww <= r2, np.where(wd >= dd, uu <= r2, perp <= np.uint64(r2 * dd)))
+        hit[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]] |= inside
+    return hit
+
+
+def brush_volume(prepared, dims, b, labels, uncut=None):
+    """The definition of the brush (include/volym_hip.h volym_brush_labels), integers only; equal to the device in every byte.
+    `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None: prepared), `labels`:
+    the labels before the stroke.  A texel with label l becomes to[l] iff it lies in the box, to[l] != l, its density byte lies in
+    the window and it lies within at least one segment; every texel is decided once, from the bytes before the edit.  Returns
+    (new_labels, result) as relabel_volume does."""
+    b = check_brush(b, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = b.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("brush_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (b.flags & _lib.BRUSH_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("brush_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    if any(p >= q for p, q in zip(lo, hi)):
+        return new, result
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    to = np.asarray(b.to, np.int64).astype(np.uint8)
+    d = src.reshape(nz, ny, nx)[sub]
+    hit = (to[old] != old) & (d >= b.window[0]) & (d <= b.window[1]) & brush_mask(b, dims)[sub]
+    n = int(hit.sum())
+    if n == 0:
+        return new, result
+    result["changed"] = n
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not b.flags & _lib.BRUSH_DRY_RUN:
+        new[sub] = np.where(hit, to[old], old)
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
