@@ -1,11 +1,15 @@
 """Did a change leave every kernel's machine code alone, wherever the kernel now lives?  No GPU needed.
 
     for u in raymarch scene_bytes; do hipcc <the Makefile's flags> --cuda-device-only -S volym_amd/csrc/$u.hip -o new/$u.s; done   (and before/)
-    python scripts/kernel_asm_equal.py before/*.s -- new/*.s
+    python scripts/kernel_asm_equal.py [--rename OLD=NEW ...] before/*.s -- new/*.s
 
 A kernel's code is the text between its label and its .Lfunc_end, without comments (they carry the function's index in its
 unit) and without the digits of that index in .LBB<n>_, .LJTI<n>_, .Ltmp<n>, .Lfunc_begin<n>, .Lfunc_end<n>.  Prints the kernels
-that differ or exist on one side only; exit status 1 if there are any."""
+that differ or exist on one side only; exit status 1 if there are any.
+
+--rename OLD=NEW: a type or a kernel changed its name.  OLD is replaced by NEW in the names and the code of the kernels before; give
+the mangled spelling with its length, as in 13SurfaceSelect=9BoxSelect.  Kernels before that come to share one name -- copies that
+became one kernel -- must each equal the kernel of that name after."""
 import re
 import sys
 
@@ -25,12 +29,29 @@ def kernels(paths):
 
 
 def main():
-    cut = sys.argv.index("--")
-    a, b = kernels(sys.argv[1:cut]), kernels(sys.argv[cut + 1:])
-    bad = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
-    for k in bad:
-        print("%s: %s" % ("differs" if k in a and k in b else "only before" if k in a else "only after", k))
-    print("%d kernels before, %d after, %d equal" % (len(a), len(b), len(set(a) | set(b)) - len(bad)))
+    args, renames = sys.argv[1:], []
+    while args and args[0] == "--rename":
+        renames.append(args[1].split("=", 1))
+        args = args[2:]
+    cut = args.index("--")
+    b = kernels(args[cut + 1:])
+    a = []                                                  # (name after the renames, code after them, name before)
+    for name, code in kernels(args[:cut]).items():
+        new, was = name, name
+        for old, to in renames:
+            new, code = new.replace(old, to), code.replace(old, to)
+        a.append((new, code, was))
+    bad = 0
+    for new, code, was in sorted(a):
+        if b.get(new) != code:
+            print("%s: %s" % ("differs" if new in b else "only before", was if new == was else "%s -> %s" % (was, new)))
+            bad += 1
+        elif new != was:
+            print("equal: %s -> %s" % (was, new))
+    for k in sorted(set(b) - {new for new, _, _ in a}):
+        print("only after: %s" % k)
+        bad += 1
+    print("%d kernels before, %d after, %d of those before equal" % (len(a), len(b), len(a) - bad))
     return 1 if bad else 0
 
 

@@ -3,6 +3,8 @@ fill and to the closed forms below) and tests/test_gpu_components.py (which comp
 boxes, cut states, select tables and thresholds are those of tests/measure_scenes.py and tests/surface_scenes.py; the constructed
 scenes are built here.
 """
+import functools
+
 import numpy as np
 
 from tests import measure_scenes as M
@@ -33,6 +35,16 @@ def requests(flags=0):
     out += [("whole / %s / 128" % n, scene.Components(BOXES["whole"], flags, 128, sel[n])) for n in sel]
     out += [("whole / all / %d" % m, scene.Components(BOXES["whole"], flags, m, sel["all"])) for m in MIN_BYTES if m != 128]
     return out
+
+
+@functools.lru_cache(None)
+def scan_components(split):
+    """(scene.Components over S.SCAN_BOX, the twin's (summary, table, ids) of S.scan_scene): the surface test's request with
+    SPLIT_LABELS, or no flags and every label selected; computed once, left unchanged"""
+    from volym_amd import scene
+    dims, vol, labels = S.scan_scene()
+    c = scene.Components(S.SCAN_BOX, SPLIT, S.SCAN_MIN_BYTE, scene.surface_select(S.SCAN_LABELS)) if split else scene.Components(S.SCAN_BOX, 0, S.SCAN_MIN_BYTE)
+    return c, scene.components_volume(vol, dims, c, labels=labels)
 
 
 def expect(host, c, labels=True):

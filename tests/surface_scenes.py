@@ -3,6 +3,8 @@ asserts on the host twin the conditions the device tests rely on) and tests/test
 twin).  Scenes, boxes and cut states are those of tests/measure_scenes.py: Scene A is 37 x 22 x 19 with random density bytes 1..255
 and five labels in blocks, Scene B the same density under random labels over all 256 values.
 """
+import functools
+
 import numpy as np
 
 from tests import measure_scenes as M
@@ -27,6 +29,30 @@ LONG_BOXES = {
     "66 from 1": ((1, 2, 0), (67, 79, 71)),
     "94 from 3": ((3, 1, 1), (97, 80, 70)),
 }
+
+# More rows than one workgroup of the offset scan's second phase has threads times the rows of a block: 4 x 257 x 256 of noise, and a
+# box of 257 x 256 = 65792 rows, 257 scan blocks, so that a thread of that one workgroup owns two block sums, not one.
+# The scan is one for the surface and the components pass (box_pass.hip); both walk this box.
+SCAN_DIMS = (4, 257, 256)
+SCAN_BOX = ((1, 0, 0), (3, 257, 256))
+SCAN_MIN_BYTE, SCAN_LABELS = 128, (1, 2)
+
+
+def scan_scene():
+    """(dims, vol, labels): random density bytes 0..255 and, from the same generator next, labels 0..3"""
+    rng = np.random.default_rng(20261020)
+    n = SCAN_DIMS[0] * SCAN_DIMS[1] * SCAN_DIMS[2]
+    vol = rng.integers(0, 256, n, dtype=np.uint8)
+    return SCAN_DIMS, vol, rng.integers(0, 4, n, dtype=np.uint8)
+
+
+@functools.lru_cache(None)
+def scan_surface():
+    """(scene.Surface over SCAN_BOX, the twin's (summary, faces) of scan_scene): computed once, left unchanged"""
+    from volym_amd import scene
+    dims, vol, labels = scan_scene()
+    s = scene.Surface(SCAN_BOX, 0, SCAN_MIN_BYTE, scene.surface_select(SCAN_LABELS))
+    return s, scene.surface_volume(vol, dims, s, labels=labels)
 
 
 def selects():

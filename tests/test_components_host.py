@@ -316,3 +316,17 @@ def test_the_clis_refuse_a_bad_threshold(volym_lib):
     assert "--components" in str(e.value)
     r = subprocess.run([os.path.join(ROOT, "volym_amd", "volym"), "run", "simple", "--components", "Canopy:300"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 2 and "--components" in r.stderr
+
+
+def test_the_scan_scene_has_two_block_sums_per_thread_and_every_piece_recorded():
+    """what tests/test_gpu_components.py test_the_offset_scan_with_two_block_sums_per_thread relies on"""
+    from tests import surface_scenes as S
+    from volym_amd import _lib
+    c, (summary, table, ids) = CS.scan_components(True)
+    assert S.rows(c.box) == 65792 > 256 * _lib.SURFACE_SCAN_ROWS
+    assert int(summary["n_components"]) == int(summary["recorded"]) == len(table) > 10000
+    assert int(ids[ids != _lib.COMPONENT_NONE].max()) == len(table) - 1
+    # without the split and with every label selected pieces merge: another result, so one left over from the first pass would show
+    whole, (summary2, table2, _) = CS.scan_components(False)
+    assert whole.box == c.box and whole.flags == 0 and np.asarray(whole.select).all()
+    assert 1 < int(summary2["n_components"]) == int(summary2["recorded"]) == len(table2) < len(table)

@@ -409,3 +409,18 @@ def test_the_canopy_of_the_bonsai_at_256(volym_lib):
         ctx.set_volume(vol, dims, 0)
         ctx.set_labels(lab, dims)
         _same("canopy", _run(ctx, c), want)
+
+
+# ---- 7. the offset scan's second level: more than 256 blocks of 256 rows ----------------------------------------------------------------
+@pytest.mark.parametrize("layout", [0, 1])
+def test_the_offset_scan_with_two_block_sums_per_thread(volym_lib, layout):
+    """65792 rows are 257 blocks of the scan, so the one workgroup that scans the block sums owns two per thread: the number of every
+    row's first root comes out of it.  The surface test's scene, box and request with SPLIT_LABELS, then no flags and every label."""
+    from tests import surface_scenes as S
+    dims, vol, labels = S.scan_scene()
+    with _ctx(layout) as ctx:
+        ctx.set_volume(vol, dims, 0)
+        ctx.set_labels(labels, dims)
+        for split in (True, False):
+            c, want = CS.scan_components(split)
+            _same(("scan", split), _run(ctx, c), want)

@@ -415,3 +415,16 @@ def test_the_lobster_of_the_teapot(volym_lib, layout):
         solid = int(((vol >= 1) & (lab == 2)).sum())
         for a in range(3):
             assert int(got[0]["pos"][2][a]) - int(got[0]["neg"][2][a]) == solid <= int(rec["count"][2])
+
+
+# ---- 8. the offset scan's second level: more than 256 blocks of 256 rows ----------------------------------------------------------------
+@pytest.mark.parametrize("layout", [0, 1])
+def test_the_offset_scan_with_two_block_sums_per_thread(volym_lib, layout):
+    """65792 rows are 257 blocks of the scan, so the one workgroup that scans the block sums owns two per thread; more than a third of
+    the rows have no face (tests/test_surface_host.py), so a wrong offset lands a row's faces on another's"""
+    dims, vol, labels = S.scan_scene()
+    s, want = S.scan_surface()
+    with _ctx(layout) as ctx:
+        ctx.set_volume(vol, dims, 0)
+        ctx.set_labels(labels, dims)
+        _same("scan", _run(ctx, s), want)

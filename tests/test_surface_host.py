@@ -418,3 +418,15 @@ def test_the_scenes_of_the_device_tests_are_what_those_tests_need():
             assert int((solid[:, :, 63] != solid[:, :, 64]).sum()) > 100, name       # it ends at the border: a face from the carried bit
         summary, faces = scene.surface_volume(vol, dims, scene.Surface((lo, hi), 0, 4), labels=labels)
         assert (summary["faces"].sum(axis=1) > 0).sum() >= 2 and (np.diff(S.face_keys(faces)) > 0).all(), name
+
+
+def test_the_scan_scene_has_two_block_sums_per_thread_and_uneven_rows():
+    """what tests/test_gpu_surface.py test_the_offset_scan_with_two_block_sums_per_thread relies on"""
+    from volym_amd import _lib
+    s, (summary, faces) = S.scan_surface()
+    assert S.rows(s.box) == 65792 > 256 * _lib.SURFACE_SCAN_ROWS                # 257 blocks: ceil(257 / 256) = 2 sums per thread
+    assert int(summary["total"]) == len(faces) > 100000
+    (x0, y0, z0), (x1, y1, z1) = s.box
+    per_row = np.bincount((faces["z"].astype(np.int64) - z0) * (y1 - y0) + (faces["y"] - y0), minlength=S.rows(s.box))
+    assert len(per_row) == S.rows(s.box) and int((per_row == 0).sum()) > S.rows(s.box) // 3      # the offsets are no arithmetic progression
+    assert (np.diff(S.face_keys(faces)) > 0).all()

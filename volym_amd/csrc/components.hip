@@ -32,20 +32,7 @@ void volym::free_components(volym_ctx* c)
     c->component_ids.release();
     c->component_table.release();
     c->component_work.release();
-    c->component_rows.release();
-    c->component_sums.release();
-}
-
-// texels of a box that lies in a volume of at most 4096^3: below 2^36
-static uint64_t box_texels(const uint32_t box[6])
-{
-    return static_cast<uint64_t>(box[3] - box[0]) * (box[4] - box[1]) * (box[5] - box[2]);
-}
-
-// One wave per row and step, four waves per workgroup, at most eight workgroups per CU.
-static uint32_t walk_grid(const volym_ctx* c, uint32_t n_rows)
-{
-    return std::max(std::min((n_rows + 3u) / 4u, static_cast<uint32_t>(c->n_cus) * 8u), 1u);
+    c->component_offsets.release();
 }
 
 extern "C" {
@@ -57,9 +44,7 @@ int volym_components_check(const volym_components* q, const uint32_t dims[3])
     if (q->flags & ~static_cast<uint32_t>(VOLYM_COMPONENTS_UNCUT | VOLYM_COMPONENTS_SPLIT_LABELS)) return VOLYM_E_INVALID;
     if (q->min_byte == 0u || q->min_byte > 255u) return VOLYM_E_INVALID;
     if (q->max_components > VOLYM_COMPONENTS_TABLE_MAX) return VOLYM_E_INVALID;
-    // (the product of three 32-bit extents in two steps: once the first is bounded the second cannot wrap 64 bits; an empty box has 0 texels)
-    const uint64_t w = q->box[3] - q->box[0], h = q->box[4] - q->box[1], d = q->box[5] - q->box[2];
-    if (w != 0u && h != 0u && d != 0u && (w * h > VOLYM_COMPONENTS_BOX_MAX || w * h * d > VOLYM_COMPONENTS_BOX_MAX)) return VOLYM_E_INVALID;
+    if (!box_at_most(q->box, VOLYM_COMPONENTS_BOX_MAX)) return VOLYM_E_INVALID;
     return VOLYM_OK;
 }
 
@@ -83,27 +68,22 @@ int volym_components_pass(volym_ctx* c, const volym_components* q)
     const hipStream_t stream = c->slot0().stream;       // where pick, measure and surface passes go
     const uint32_t n_texels = static_cast<uint32_t>(box_texels(q->box));      // (checked: at most 2^31 - 2)
     const bool empty = n_texels == 0u;
-    const uint32_t w = q->box[3] - q->box[0], h = q->box[4] - q->box[1];
-    const uint32_t n_rows = empty ? 0u : h * (q->box[5] - q->box[2]);
+    const uint32_t n_rows = empty ? 0u : (q->box[4] - q->box[1]) * (q->box[5] - q->box[2]);
     // no more records than the box has texels: a component has at least one
     const uint32_t capacity = std::min(q->max_components ? q->max_components : VOLYM_COMPONENTS_DEFAULT_MAX, n_texels);
 
     // (set-up steps: the one blocking path of a pass.  Whatever grows voids the snapshot first; should an allocation fail none is left)
     const bool grows = c->components.capacity < 1u || n_texels > c->component_ids.capacity || capacity > c->component_table.capacity ||
-                       n_rows > c->component_rows.capacity;
+                       n_rows > c->component_offsets.rows.capacity;
     if (grows) {
         c->components.count = 0;
-        const size_t n_sums = (static_cast<size_t>(n_rows) + COMPONENTS_SCAN_ROWS - 1u) / COMPONENTS_SCAN_ROWS;
         rc = c->components.reserve(c, stream, 1, "components summary");
         if (rc == VOLYM_OK) rc = c->component_ids.reserve(c, stream, n_texels, "component ids");
         if (rc == VOLYM_OK && capacity > c->component_table.capacity) {
             rc = c->component_table.reserve(c, stream, capacity, "component table");
             if (rc == VOLYM_OK) { c->component_work.release(); rc = c->component_work.reserve(c, stream, static_cast<size_t>(capacity) * COMPONENT_WORK_WORDS, "component table"); }
         }
-        if (rc == VOLYM_OK && n_rows > c->component_rows.capacity) {
-            rc = c->component_rows.reserve(c, stream, n_rows, "component row offsets");
-            if (rc == VOLYM_OK) { c->component_sums.release(); rc = c->component_sums.reserve(c, stream, n_sums, "component row offsets"); }
-        }
+        if (rc == VOLYM_OK) rc = c->component_offsets.reserve(c, stream, n_rows, "component row offsets");
         if (rc != VOLYM_OK) { free_components(c); return rc; }
     }
     unsigned long long* const summary = reinterpret_cast<unsigned long long*>(c->components.ptr);
@@ -119,21 +99,11 @@ int volym_components_pass(volym_ctx* c, const volym_components* q)
 
     const bool uncut = (q->flags & VOLYM_COMPONENTS_UNCUT) != 0u;
     const bool split = (q->flags & VOLYM_COMPONENTS_SPLIT_LABELS) != 0u && with_labels;     // (without labels every label is 0: nothing to split)
-    ComponentsArgs a = {};
-    a.vol = uncut && c->d_vol0 ? c->d_vol0 : c->d_vol;
-    a.labels = with_labels ? c->d_labels : nullptr;
-    for (int i = 0; i < 3; ++i) { a.lo[i] = q->box[i]; a.hi[i] = q->box[3 + i]; }
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    a.bricked = c->bricked ? 1u : 0u;
-    a.min_byte = q->min_byte;
-    a.w = w; a.h = h;
-    a.n_rows = n_rows;
-    a.capacity = capacity;
-    ComponentsSelect select;
+    const ComponentsArgs a = {box_walk_args(c, q->box, q->min_byte, uncut && c->d_vol0 ? c->d_vol0 : c->d_vol, with_labels), capacity};
+    BoxSelect select;
     std::memcpy(select.v, q->select, 256);
     uint32_t* const parent = c->component_ids.ptr;
-    uint32_t* const rows = c->component_rows.ptr;
-    uint32_t* const sums = c->component_sums.ptr;
+    uint32_t* const rows = c->component_offsets.rows.ptr;
     const dim3 grid(walk_grid(c, n_rows)), block(256);
 
     const auto rows_kernel = !with_labels ? volym_components_rows_kernel<false, false>
@@ -145,14 +115,8 @@ int volym_components_pass(volym_ctx* c, const volym_components* q)
     HIPCHK(c, hipGetLastError());
     hipLaunchKernelGGL(volym_components_flatten_kernel, grid, block, 0, stream, a, parent, rows);
     HIPCHK(c, hipGetLastError());
-    // the scan: roots per row -> the number of every row's first root, in place (a grid of one workgroup runs the same three phases)
-    const uint32_t n_blocks = (n_rows + COMPONENTS_SCAN_ROWS - 1u) / COMPONENTS_SCAN_ROWS;
-    hipLaunchKernelGGL(volym_components_scan_sums_kernel, dim3(n_blocks), block, 0, stream, rows, sums, n_rows);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(volym_components_scan_blocks_kernel, dim3(1), block, 0, stream, sums, n_blocks);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(volym_components_scan_rows_kernel, dim3(n_blocks), block, 0, stream, rows, sums, n_rows);
-    HIPCHK(c, hipGetLastError());
+    rc = scan_row_offsets(c, stream, c->component_offsets, n_rows);      // roots per row -> the number of every row's first root, in place
+    if (rc != VOLYM_OK) return rc;
     hipLaunchKernelGGL(with_labels ? volym_components_number_kernel<true> : volym_components_number_kernel<false>, grid, block, 0, stream, a, parent, rows,
                        work, summary);
     HIPCHK(c, hipGetLastError());
@@ -188,39 +152,13 @@ int volym_read_component_table(volym_ctx* c, struct volym_component* out, uint64
 int volym_read_component_ids(volym_ctx* c, const uint32_t sub[6], uint32_t* out)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (c->components.count == 0u) return fail(c, VOLYM_E_STATE, "volym_read_component_ids: no volym_components_pass since the volume was set");
-    const uint32_t* box = c->component_box;
-    if (!sub) sub = box;
-    for (int k = 0; k < 3; ++k)
-        if (sub[k] > sub[3 + k] || sub[k] < box[k] || sub[3 + k] > box[3 + k])
-            return fail(c, VOLYM_E_INVALID, "volym_read_component_ids: the sub-box must have lo <= hi and lie inside the box of the pass");
-    if (box_texels(sub) == 0u) return VOLYM_OK;
-    if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_component_ids: NULL output");
-    HIPCHK(c, hipSetDevice(c->device));
-    const hipStream_t stream = c->slot0().stream;
-    const size_t w = box[3] - box[0], h = box[4] - box[1];
-    const size_t sw = sub[3] - sub[0], sh = sub[4] - sub[1], sd = sub[5] - sub[2];
-    const uint32_t* src = c->component_ids.ptr + (sub[0] - box[0]) + w * ((sub[1] - box[1]) + h * static_cast<size_t>(sub[2] - box[2]));
-    if (sw == w && sh == h) {
-        HIPCHK(c, hipMemcpyAsync(out, src, sw * sh * sd * 4u, hipMemcpyDeviceToHost, stream));        // whole slices: one run
-    } else {
-        for (size_t z = 0; z < sd; ++z)                 // one pitched copy per slice of the sub-box
-            HIPCHK(c, hipMemcpy2DAsync(out + z * sw * sh, sw * 4u, src + z * w * h, w * 4u, sw * 4u, sh, hipMemcpyDeviceToHost, stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(stream));
-    return VOLYM_OK;
+    return read_box_volume(c, "volym_read_component_ids", "volym_components_pass", c->components.count != 0u, c->component_box, c->component_ids.ptr, sub, out);
 }
 
 int volym_component_of(volym_ctx* c, uint32_t x, uint32_t y, uint32_t z, uint32_t* id)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (!id) return fail(c, VOLYM_E_INVALID, "volym_component_of: NULL output");
-    if (c->components.count == 0u) return fail(c, VOLYM_E_STATE, "volym_component_of: no volym_components_pass since the volume was set");
-    const uint32_t* box = c->component_box;
-    if (x < box[0] || x >= box[3] || y < box[1] || y >= box[4] || z < box[2] || z >= box[5])
-        return fail(c, VOLYM_E_INVALID, "volym_component_of: the texel lies outside the box of the pass");
-    const size_t w = box[3] - box[0], h = box[4] - box[1];
-    return read_back(c, c->slot0().stream, id, c->component_ids.ptr + (x - box[0]) + w * ((y - box[1]) + h * static_cast<size_t>(z - box[2])), sizeof *id);
+    return read_box_texel(c, "volym_component_of", "volym_components_pass", c->components.count != 0u, c->component_box, c->component_ids.ptr, x, y, z, id);
 }
 
 void* volym_components_device_ptr(volym_ctx* c) { return (c && c->components.count != 0u) ? c->components.ptr : nullptr; }

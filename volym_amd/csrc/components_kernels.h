@@ -4,8 +4,7 @@
 //
 // The work array is the id volume itself, parent[], indexed box-linear: i = (x - x0) + w * row, row = (y - y0) + h * (z - z0).  It is
 // a union-find forest over texels, and the five steps below turn it into the ids in place: no second array of the volume's size.
-//   As in the surface pass a ROW of the box (fixed y, z) belongs to one wave, which walks it in chunks of 64 consecutive x; the scene's
-// bytes are read through layout_offset with byte loads, so odd row lengths and box offsets need no keep mask.  Every load and store is
+//   The rows are walked as box_walk.h says, and a texel is solid by its predicate.  Every load and store is
 // of a texel of the request's box, which volym_components_check puts inside the volume, or of parent[i] with i below the box's
 // texel count.
 //
@@ -19,19 +18,11 @@
 // the flatten kernel because that is a later launch.
 #pragma once
 
-#include "context.hpp"
+#include "box_walk.h"
 
 namespace volym {
 
-struct ComponentsSelect { uint8_t v[256]; };
-
-struct ComponentsArgs {
-    const uint8_t* vol;
-    const uint8_t* labels;              // NULL: every label is 0
-    uint32_t lo[3], hi[3];              // the request's box, not empty
-    uint32_t nx, ny, nz, bricked, min_byte;
-    uint32_t w, h;                      // hi[0] - lo[0], hi[1] - lo[1]
-    uint32_t n_rows;                    // h * (hi[2] - lo[2]) <= 4096^2; w * n_rows <= 2^31 - 2 (volym_components_check)
+struct ComponentsArgs : BoxWalkArgs {   // w * n_rows <= 2^31 - 2 (volym_components_check)
     uint32_t capacity;                  // records kept: components numbered below it
 };
 
@@ -45,11 +36,6 @@ enum { CW_ROOT_XY = 0, CW_ROOT_ZL = 1, CW_COUNT = 2, CW_FLAGS = 3, CW_MIN = 4, C
 
 // summary: struct volym_components_summary as 64-bit words
 enum { CS_N_COMPONENTS = 0, CS_N_SOLID = 1, CS_RECORDED = 2, CS_PER_LABEL = 3, COMPONENT_SUMMARY_WORDS = 3 + 256 };
-
-__device__ __forceinline__ uint32_t components_wave_index()
-{
-    return __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-}
 
 // zero summary (block 0) and an empty working table: counts and flags 0, the box inside out
 __global__ __launch_bounds__(256) void volym_components_init_kernel(unsigned long long* summary, uint32_t* __restrict__ work, uint32_t n_records)
@@ -65,7 +51,7 @@ __global__ __launch_bounds__(256) void volym_components_init_kernel(unsigned lon
 
 // ---- 1. rows: every x-run of solid (and, SPLIT, equally labelled) texels points at its first texel; no atomic ---------------------
 template <bool LABELS, bool SPLIT>
-__global__ __launch_bounds__(256) void volym_components_rows_kernel(ComponentsArgs a, ComponentsSelect select, uint32_t* __restrict__ parent,
+__global__ __launch_bounds__(256) void volym_components_rows_kernel(ComponentsArgs a, BoxSelect select, uint32_t* __restrict__ parent,
                                                                     unsigned long long* __restrict__ summary)
 {
     __shared__ uint8_t s_select[256];
@@ -75,7 +61,7 @@ __global__ __launch_bounds__(256) void volym_components_rows_kernel(ComponentsAr
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t upto = lane == 63u ? ~0ull : ((2ull << lane) - 1ull);        // bits 0..lane
     unsigned long long wave_solid = 0ull;
-    for (uint32_t row = components_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t y = a.lo[1] + row % a.h, z = a.lo[2] + row / a.h;
         const uint32_t base = row * a.w;
         uint64_t carry = 0ull;                                     // bit 0: the last texel of the chunk before is solid
@@ -86,11 +72,7 @@ __global__ __launch_bounds__(256) void volym_components_rows_kernel(ComponentsAr
             uint32_t label = 0u;
             bool solid = false;
             if (in) {
-                const uint32_t o = layout_offset(a.bricked != 0u, bx, bxy, a.lo[0] + xi, y, z);
-                if (a.vol[o] >= a.min_byte) {
-                    if (LABELS) label = a.labels[o];
-                    solid = s_select[label] != 0u;
-                }
+                solid = box_solid<LABELS>(a, s_select, layout_offset(a.bricked != 0u, bx, bxy, a.lo[0] + xi, y, z), label);
             }
             const uint64_t s = __ballot(solid);
             uint64_t link = s & ((s << 1) | carry);                // linked to the texel on the left
@@ -148,7 +130,7 @@ __global__ __launch_bounds__(256) void volym_components_merge_kernel(ComponentsA
     const uint32_t bx = layout_bx(a.bricked != 0u, a.nx), bxy = layout_bxy(a.bricked != 0u, a.nx, a.ny);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t slice = a.w * a.h;
-    for (uint32_t row = components_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t ry = row % a.h, rz = row / a.h;
         if (ry == 0u && rz == 0u) continue;                        // links never cross the request's box
         const uint32_t y = a.lo[1] + ry, z = a.lo[2] + rz;
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(256) void volym_components_merge_kernel(ComponentsA
 __global__ __launch_bounds__(256) void volym_components_flatten_kernel(ComponentsArgs a, uint32_t* parent, uint32_t* __restrict__ rows)
 {
     const uint32_t lane = threadIdx.x & 63u;
-    for (uint32_t row = components_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t base = row * a.w;
         uint32_t n_roots = 0u;                                     // (wave-uniform; below 2^31)
         for (uint32_t x0 = 0u; x0 < a.w; x0 += 64u) {
@@ -194,57 +176,9 @@ __global__ __launch_bounds__(256) void volym_components_flatten_kernel(Component
     }
 }
 
-// ---- the scan of the row counts: three plain phases as in the surface pass, no workgroup waits for another --------------------------
-constexpr uint32_t COMPONENTS_SCAN_ROWS = 256u;                    // one row per thread of a 256-thread workgroup
-
-__device__ __forceinline__ uint32_t components_block_scan(uint32_t v, uint32_t* s_scan, uint32_t* sum)
-{
-    const uint32_t t = threadIdx.x;
-    s_scan[t] = v;
-    __syncthreads();
-    for (uint32_t step = 1u; step < 256u; step <<= 1) {
-        const uint32_t add = t >= step ? s_scan[t - step] : 0u;
-        __syncthreads();
-        s_scan[t] += add;
-        __syncthreads();
-    }
-    const uint32_t inclusive = s_scan[t];
-    if (sum) *sum = s_scan[255];
-    __syncthreads();
-    return inclusive - v;
-}
-
-__global__ __launch_bounds__(256) void volym_components_scan_sums_kernel(const uint32_t* __restrict__ rows, uint32_t* __restrict__ sums, uint32_t n_rows)
-{
-    __shared__ uint32_t s_scan[256];
-    const uint32_t i = blockIdx.x * COMPONENTS_SCAN_ROWS + threadIdx.x;
-    uint32_t sum;
-    (void)components_block_scan(i < n_rows ? rows[i] : 0u, s_scan, &sum);
-    if (threadIdx.x == 0u) sums[blockIdx.x] = sum;
-}
-
-// one workgroup; thread t owns the ceil(n_blocks / 256) consecutive sums from t * per on
-__global__ __launch_bounds__(256) void volym_components_scan_blocks_kernel(uint32_t* __restrict__ sums, uint32_t n_blocks)
-{
-    __shared__ uint32_t s_scan[256];
-    const uint32_t per = (n_blocks + 255u) / 256u;
-    const uint32_t b0 = min(threadIdx.x * per, n_blocks), b1 = min(b0 + per, n_blocks);
-    uint32_t mine = 0u;
-    for (uint32_t b = b0; b < b1; ++b) mine += sums[b];
-    uint32_t run = components_block_scan(mine, s_scan, nullptr);
-    for (uint32_t b = b0; b < b1; ++b) { const uint32_t v = sums[b]; sums[b] = run; run += v; }
-}
-
-__global__ __launch_bounds__(256) void volym_components_scan_rows_kernel(uint32_t* __restrict__ rows, const uint32_t* __restrict__ sums, uint32_t n_rows)
-{
-    __shared__ uint32_t s_scan[256];
-    const uint32_t i = blockIdx.x * COMPONENTS_SCAN_ROWS + threadIdx.x;
-    const uint32_t before = components_block_scan(i < n_rows ? rows[i] : 0u, s_scan, nullptr);
-    if (i < n_rows) rows[i] = sums[blockIdx.x] + before;
-}
-
 // ---- 4. number: a root's number is its row's offset plus the roots before it in the row; no atomic decides a number -----------------
-// rows[row] is now the number of the row's first root.  A root's word becomes TAG | number, and the root texel of a kept component goes
+// Between the flatten and this kernel the host scans rows[] from counts into offsets (scan_row_offsets, box_pass.hip): rows[row] is now
+// the number of the row's first root.  A root's word becomes TAG | number, and the root texel of a kept component goes
 // into the working table.  Only the counters of the summary are atomics (integers: arrival order cannot show).
 template <bool LABELS>
 __global__ __launch_bounds__(256) void volym_components_number_kernel(ComponentsArgs a, uint32_t* parent, const uint32_t* __restrict__ rows,
@@ -258,7 +192,7 @@ __global__ __launch_bounds__(256) void volym_components_number_kernel(Components
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t wave_roots = 0u;
-    for (uint32_t row = components_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t y = a.lo[1] + row % a.h, z = a.lo[2] + row / a.h;
         const uint32_t base = row * a.w;
         uint32_t at = rows[row];                                   // wave-uniform
@@ -308,7 +242,7 @@ __global__ __launch_bounds__(256) void volym_components_relabel_kernel(Component
 #pragma unroll
         for (int k = 0; k < 3; ++k) { atomicMin(&rec[CW_MIN + k], mn[k]); atomicMax(&rec[CW_MAX + k], mx[k]); }
     };
-    for (uint32_t row = components_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t y = a.lo[1] + row % a.h, z = a.lo[2] + row / a.h;
         const uint32_t base = row * a.w;
         const bool edge_yz = y == a.lo[1] || y + 1u == a.hi[1] || z == a.lo[2] || z + 1u == a.hi[2];

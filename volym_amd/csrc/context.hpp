@@ -1,12 +1,18 @@
 // Internal: the context behind include/volym_hip.h (one device, one W x H output, one or two frame slots) and the pieces of host
-// logic that more than one translation unit needs (raymarch.hip: the frame loop and its C ABI, the cost-feedback thread and the
-// capture that feeds it, with mgpu.inc, the native multi-GPU loop, included in it; scene_bytes.hip: the bytes of the scene and
-// their C ABI, and the measure pass over them; pick.hip: the pick pass and its C ABI; outline.hip: the outline pass and its C ABI; slice.hip: the slice pass and its C ABI; project.hip: the projection pass and its C ABI; surface.hip: the surface passes and their C ABI; components.hip: the components pass and its C ABI; distance.hip: the distance pass and its C ABI).  The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp:
-// host only, it knows nothing of this header.
+// logic that more than one translation unit needs.  The units, each with the C ABI of what it holds:
+//   raymarch.hip      the frame loop, the cost-feedback thread and the capture that feeds it; mgpu.inc, the native multi-GPU loop,
+//                     is included in it
+//   scene_bytes.hip   the bytes of the scene, the measure pass over them and the label edits
+//   pick.hip, outline.hip, slice.hip, project.hip, surface.hip, components.hip, distance.hip
+//                     the pass of that name
+//   box_pass.hip      no ABI: what the passes over a request's box share -- the scan of row counts into offsets and the read-back
+//                     of a box-linear volume
+// The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp: host only, it knows nothing of this header.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
@@ -39,6 +45,17 @@ struct OwnedBuffer {
     // the first n elements to host memory, blocking (read_back)
     int read(volym_ctx* c, hipStream_t stream, void* out, size_t n) const;
     void release() { (void)hipFree(ptr); ptr = nullptr; capacity = count = 0; }
+};
+
+// One count per row of a request's box, which scan_row_offsets turns in place into the offset of the row's first item, and the block
+// sums of that scan: one per VOLYM_SURFACE_SCAN_ROWS rows.  The two are replaced together.
+struct RowOffsets {
+    OwnedBuffer<uint32_t> rows, sums;
+
+    // room for n_rows rows.  Nothing when there is; else both are replaced as OwnedBuffer::reserve replaces one, and should either
+    // allocation fail neither is kept
+    int reserve(volym_ctx* c, hipStream_t stream, size_t n_rows, const char* what);
+    void release() { rows.release(); sums.release(); }
 };
 
 // What a capture hands the feedback thread: written by the caller before FB_CAPTURED, by the worker before FB_READY.
@@ -227,8 +244,7 @@ struct volym_ctx {
     // surface passes (volym_surface_pass / volym_surface_faces_pass, surface.hip)
     uint64_t scene_serial = 0;               // bumped by every set-up call that changes a byte the surface pass reads (density, labels)
     volym::OwnedBuffer<volym_surface_summary> surface;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
-    volym::OwnedBuffer<uint32_t> surface_rows;   // per row of the request's box: its face count, scanned in place into the offset of its first face
-    volym::OwnedBuffer<uint32_t> surface_sums;   // the scan's block sums: one per VOLYM_SURFACE_SCAN_ROWS rows; replaced whenever surface_rows is
+    volym::RowOffsets surface_offsets;          // per row of the request's box: its face count, scanned in place into the offset of its first face
     uint64_t surface_serial = 0;             // scene_serial at that pass: the offsets describe the scene while it is the current one
     volym_surface surface_request = {};      // what that pass was asked (the emit pass walks it again)
     const uint8_t* surface_vol = nullptr;    // ... and the density it read (d_vol, or d_vol0 under UNCUT)
@@ -243,8 +259,7 @@ struct volym_ctx {
     volym::OwnedBuffer<uint32_t> component_ids;      // the id volume of the request's box, box-linear; the union-find forest while the pass runs
     volym::OwnedBuffer<volym_component> component_table;   // the records: min(max_components, texels of the box) of them at most
     volym::OwnedBuffer<uint32_t> component_work;     // the working table the records accumulate in (components_kernels.h), sized with the table
-    volym::OwnedBuffer<uint32_t> component_rows;     // per row of the request's box: its roots, scanned in place into the number of its first root
-    volym::OwnedBuffer<uint32_t> component_sums;     // the scan's block sums; replaced whenever component_rows is
+    volym::RowOffsets component_offsets;        // per row of the request's box: its roots, scanned in place into the number of its first root
     uint32_t component_box[6] = {};          // the box of the latest pass (the reads address the id volume by it)
 
     // distance passes (volym_distance_pass, distance.hip): a snapshot, valid until the next volym_set_volume
@@ -377,6 +392,15 @@ int OwnedBuffer<T>::read(volym_ctx* c, hipStream_t stream, void* out, size_t n) 
     return read_back(c, stream, out, ptr, n * sizeof(T));
 }
 
+inline int RowOffsets::reserve(volym_ctx* c, hipStream_t stream, size_t n_rows, const char* what)
+{
+    if (n_rows <= rows.capacity) return VOLYM_OK;
+    int rc = rows.reserve(c, stream, n_rows, what);
+    if (rc == VOLYM_OK) { sums.release(); rc = sums.reserve(c, stream, (n_rows + VOLYM_SURFACE_SCAN_ROWS - 1u) / VOLYM_SURFACE_SCAN_ROWS, what); }
+    if (rc != VOLYM_OK) release();
+    return rc;
+}
+
 inline uint32_t pack_rgba(const uint8_t c[4])
 {
     return static_cast<uint32_t>(c[0]) | static_cast<uint32_t>(c[1]) << 8 | static_cast<uint32_t>(c[2]) << 16 | static_cast<uint32_t>(c[3]) << 24;
@@ -413,6 +437,19 @@ inline bool box_in_volume(const uint32_t box[6], const uint32_t dims[3])
     for (int a = 0; a < 3; ++a) if (box[a] > box[3 + a] || box[3 + a] > dims[a]) return false;
     return true;
 }
+inline bool box_empty(const uint32_t box[6]) { return box[0] >= box[3] || box[1] >= box[4] || box[2] >= box[5]; }
+// texels of a box that lies in a volume of at most 4096^3: below 2^36
+inline uint64_t box_texels(const uint32_t box[6])
+{
+    return static_cast<uint64_t>(box[3] - box[0]) * (box[4] - box[1]) * (box[5] - box[2]);
+}
+// a box with lo <= hi has at most `max` < 2^32 texels: the product of three 32-bit extents in two steps -- once the first is bounded
+// the second cannot wrap 64 bits; an empty box has 0 texels
+inline bool box_at_most(const uint32_t box[6], uint64_t max)
+{
+    const uint64_t w = box[3] - box[0], h = box[4] - box[1], d = box[5] - box[2];
+    return w == 0u || h == 0u || d == 0u || (w * h <= max && w * h * d <= max);
+}
 // ... and what such a pass refuses before it reads labels beside the density: the two uploaded under different layouts
 inline int check_labels_layout(volym_ctx* c, const char* who)
 {
@@ -420,5 +457,28 @@ inline int check_labels_layout(volym_ctx* c, const char* who)
         return ctx_fail(c, VOLYM_E_STATE, std::string(who) + ": volume and labels were uploaded under different VOLYM_OPT_VOLUME_LAYOUT settings");
     return VOLYM_OK;
 }
+
+// ---- the passes that walk a box row by row (box_walk.h: surface, components, distance) ----
+// The workgroups of a walk: one wave per row and step, four waves per workgroup; at most eight workgroups per CU, but at least so
+// many that no wave walks more than WALK_ROWS_PER_WAVE rows (the widths of surface_kernels.h rest on it).  A permitted box has at most
+// 4096^2 = 2^24 rows, so that floor is at most 2^24 / 16384 = 1024 workgroups; on a device of 256 CUs the cap is 2048, and wherever
+// 8 * n_cus >= ceil(n_rows / 16384) the floor changes nothing: the grid is max(min(ceil(n_rows / 4), 8 * n_cus), 1).
+constexpr uint32_t WALK_ROWS_PER_WAVE = 4096u;
+inline uint32_t walk_grid(const volym_ctx* c, uint32_t n_rows)
+{
+    const uint32_t wanted = (n_rows + 3u) / 4u, floor_grid = (n_rows + 4u * WALK_ROWS_PER_WAVE - 1u) / (4u * WALK_ROWS_PER_WAVE);
+    return std::max(std::max(std::min(wanted, static_cast<uint32_t>(c->n_cus) * 8u), floor_grid), 1u);
+}
+// box_pass.hip: rows[0 .. n_rows) from counts into their exclusive prefix sums, in place, on `stream`; sums holds the block sums
+// (RowOffsets).  Sums wrap at 2^32.  Enqueue-only.
+int scan_row_offsets(volym_ctx* c, hipStream_t stream, const RowOffsets& offsets, uint32_t n_rows);
+// box_pass.hip: what volym_read_component_ids and volym_read_distance_map are.  `src` is a uint32 volume over `box`, box-linear; its
+// part over `sub` (NULL: all of it) goes to `out` behind the work of slot 0's stream, blocking.  `have`: the pass `pass` has written
+// it; the messages are in the name of `who`.
+int read_box_volume(volym_ctx* c, const char* who, const char* pass, bool have, const uint32_t box[6], const uint32_t* src, const uint32_t sub[6],
+                    uint32_t* out);
+// box_pass.hip: ... and volym_component_of and volym_distance_at: the one word of texel (x, y, z)
+int read_box_texel(volym_ctx* c, const char* who, const char* pass, bool have, const uint32_t box[6], const uint32_t* src, uint32_t x, uint32_t y,
+                   uint32_t z, uint32_t* out);
 
 }  // namespace volym

@@ -33,18 +33,6 @@ void volym::free_distance(volym_ctx* c)
     c->distance_keys.release();
 }
 
-// texels of a box that lies in a volume of at most 4096^3: below 2^36
-static uint64_t box_texels(const uint32_t box[6])
-{
-    return static_cast<uint64_t>(box[3] - box[0]) * (box[4] - box[1]) * (box[5] - box[2]);
-}
-
-// One wave per row and step, four waves per workgroup, at most eight workgroups per CU.
-static uint32_t walk_grid(const volym_ctx* c, uint32_t n_rows)
-{
-    return std::max(std::min((n_rows + 3u) / 4u, static_cast<uint32_t>(c->n_cus) * 8u), 1u);
-}
-
 extern "C" {
 
 int volym_distance_check(const volym_distance* q, const uint32_t dims[3])
@@ -55,9 +43,7 @@ int volym_distance_check(const volym_distance* q, const uint32_t dims[3])
     if (q->min_byte == 0u || q->min_byte > 255u) return VOLYM_E_INVALID;
     for (int a = 0; a < 3; ++a)
         if (q->weight[a] == 0u || q->weight[a] > VOLYM_DISTANCE_WEIGHT_MAX) return VOLYM_E_INVALID;
-    // (the product of three 32-bit extents in two steps: once the first is bounded the second cannot wrap 64 bits; an empty box has 0 texels)
-    const uint64_t w = q->box[3] - q->box[0], h = q->box[4] - q->box[1], d = q->box[5] - q->box[2];
-    if (w != 0u && h != 0u && d != 0u && (w * h > VOLYM_DISTANCE_BOX_MAX || w * h * d > VOLYM_DISTANCE_BOX_MAX)) return VOLYM_E_INVALID;
+    if (!box_at_most(q->box, VOLYM_DISTANCE_BOX_MAX)) return VOLYM_E_INVALID;
     return VOLYM_OK;
 }
 
@@ -106,17 +92,9 @@ int volym_distance_pass(volym_ctx* c, const volym_distance* q)
     if (empty) return VOLYM_OK;                         // no texel, no seed: the summary of the zeroing kernel, no map
 
     const bool uncut = (q->flags & VOLYM_DISTANCE_UNCUT) != 0u;
-    DistanceArgs a = {};
-    a.vol = uncut && c->d_vol0 ? c->d_vol0 : c->d_vol;
-    a.labels = with_labels ? c->d_labels : nullptr;
-    for (int i = 0; i < 3; ++i) { a.lo[i] = q->box[i]; a.hi[i] = q->box[3 + i]; a.weight[i] = q->weight[i]; }
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    a.bricked = c->bricked ? 1u : 0u;
-    a.min_byte = q->min_byte;
-    a.w = w; a.h = h;
-    a.n_rows = n_rows;
-    a.inside = (q->flags & VOLYM_DISTANCE_INSIDE) ? 1u : 0u;
-    DistanceSelect select;
+    const DistanceArgs a = {box_walk_args(c, q->box, q->min_byte, uncut && c->d_vol0 ? c->d_vol0 : c->d_vol, with_labels),
+                            {q->weight[0], q->weight[1], q->weight[2]}, (q->flags & VOLYM_DISTANCE_INSIDE) ? 1u : 0u};
+    BoxSelect select;
     std::memcpy(select.v, q->select, 256);
     uint32_t* const map = c->distance_map.ptr;
     uint32_t* const stack = c->distance_work.ptr;
@@ -154,39 +132,13 @@ int volym_read_distance(volym_ctx* c, struct volym_distance_summary* out)
 int volym_read_distance_map(volym_ctx* c, const uint32_t sub[6], uint32_t* out)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (c->distance.count == 0u) return fail(c, VOLYM_E_STATE, "volym_read_distance_map: no volym_distance_pass since the volume was set");
-    const uint32_t* box = c->distance_box;
-    if (!sub) sub = box;
-    for (int k = 0; k < 3; ++k)
-        if (sub[k] > sub[3 + k] || sub[k] < box[k] || sub[3 + k] > box[3 + k])
-            return fail(c, VOLYM_E_INVALID, "volym_read_distance_map: the sub-box must have lo <= hi and lie inside the box of the pass");
-    if (box_texels(sub) == 0u) return VOLYM_OK;
-    if (!out) return fail(c, VOLYM_E_INVALID, "volym_read_distance_map: NULL output");
-    HIPCHK(c, hipSetDevice(c->device));
-    const hipStream_t stream = c->slot0().stream;
-    const size_t w = box[3] - box[0], h = box[4] - box[1];
-    const size_t sw = sub[3] - sub[0], sh = sub[4] - sub[1], sd = sub[5] - sub[2];
-    const uint32_t* src = c->distance_map.ptr + (sub[0] - box[0]) + w * ((sub[1] - box[1]) + h * static_cast<size_t>(sub[2] - box[2]));
-    if (sw == w && sh == h) {
-        HIPCHK(c, hipMemcpyAsync(out, src, sw * sh * sd * 4u, hipMemcpyDeviceToHost, stream));        // whole slices: one run
-    } else {
-        for (size_t z = 0; z < sd; ++z)                 // one pitched copy per slice of the sub-box
-            HIPCHK(c, hipMemcpy2DAsync(out + z * sw * sh, sw * 4u, src + z * w * h, w * 4u, sw * 4u, sh, hipMemcpyDeviceToHost, stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(stream));
-    return VOLYM_OK;
+    return read_box_volume(c, "volym_read_distance_map", "volym_distance_pass", c->distance.count != 0u, c->distance_box, c->distance_map.ptr, sub, out);
 }
 
 int volym_distance_at(volym_ctx* c, uint32_t x, uint32_t y, uint32_t z, uint32_t* d2)
 {
     if (!c) return VOLYM_E_INVALID;
-    if (!d2) return fail(c, VOLYM_E_INVALID, "volym_distance_at: NULL output");
-    if (c->distance.count == 0u) return fail(c, VOLYM_E_STATE, "volym_distance_at: no volym_distance_pass since the volume was set");
-    const uint32_t* box = c->distance_box;
-    if (x < box[0] || x >= box[3] || y < box[1] || y >= box[4] || z < box[2] || z >= box[5])
-        return fail(c, VOLYM_E_INVALID, "volym_distance_at: the texel lies outside the box of the pass");
-    const size_t w = box[3] - box[0], h = box[4] - box[1];
-    return read_back(c, c->slot0().stream, d2, c->distance_map.ptr + (x - box[0]) + w * ((y - box[1]) + h * static_cast<size_t>(z - box[2])), sizeof *d2);
+    return read_box_texel(c, "volym_distance_at", "volym_distance_pass", c->distance.count != 0u, c->distance_box, c->distance_map.ptr, x, y, z, d2);
 }
 
 void* volym_distance_device_ptr(volym_ctx* c) { return (c && c->distance.count != 0u) ? c->distance.ptr : nullptr; }

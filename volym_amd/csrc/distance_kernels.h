@@ -4,7 +4,7 @@
 //
 // The transform is separable: D(x, y, z) = min over z' of wz (z - z')^2 + [min over y' of wy (y - y')^2 + [min over x' of
 // wx (x - x')^2 over the seeds of row (y', z')]].  Three sweeps over the map, box-linear (i = (x - x0) + w * ((y - y0) + h * (z - z0))):
-//   rows     one wave per row of the box, 64-texel chunks through layout_offset as the surface and components walks; the nearest seed
+//   rows     one wave per row of the box, 64-texel chunks through layout_offset (the walk and the predicate of box_walk.h); the nearest seed
 //            on either side from one ballot per chunk and two carries; no atomic but the two counters.
 //   columns  along y, then along z, in place: f(i) = min_j g(j) + w (i - j)^2 over the entries with g(j) != NONE, as the lower
 //            envelope of the parabolas (Meijster's two scans).  One lane per column, adjacent lanes on adjacent x, so every load and
@@ -19,19 +19,11 @@
 // volym_distance_check puts inside the volume, or of a word of the map or the work arrays with an index below the box's texel count.
 #pragma once
 
-#include "context.hpp"
+#include "box_walk.h"
 
 namespace volym {
 
-struct DistanceSelect { uint8_t v[256]; };
-
-struct DistanceArgs {
-    const uint8_t* vol;
-    const uint8_t* labels;              // NULL: every label is 0
-    uint32_t lo[3], hi[3];              // the request's box, not empty
-    uint32_t nx, ny, nz, bricked, min_byte;
-    uint32_t w, h;                      // hi[0] - lo[0], hi[1] - lo[1]
-    uint32_t n_rows;                    // h * (hi[2] - lo[2]) <= 4096^2; w * n_rows <= 2^31 - 2 (volym_distance_check)
+struct DistanceArgs : BoxWalkArgs {     // w * n_rows <= 2^31 - 2 (volym_distance_check)
     uint32_t weight[3];
     uint32_t inside;                    // the seeds are the texels that are not solid
 };
@@ -42,11 +34,6 @@ constexpr uint32_t DISTANCE_NONE = VOLYM_DISTANCE_NONE;
 enum { DK_N_SOLID = 0, DK_N_PRESENT = 1, DK_N_FINITE = 2, DK_MAX = 3, DK_NEAR = 4, DK_HIST = 4 + 256, DISTANCE_KEY_WORDS = 4 + 256 + 256 };
 // struct volym_distance_summary as 32-bit words
 enum { DS_MAX_D2 = 6, DS_MAX_AT = 7, DS_NEAR_D2 = 10, DS_NEAR_AT = 10 + 256, DS_HIST = 10 + 256 + 768, DISTANCE_SUMMARY_WORDS = 10 + 256 + 768 + 512 };
-
-__device__ __forceinline__ uint32_t distance_wave_index()
-{
-    return __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-}
 
 // The working summary at rest, and the public summary of a box without texels (what an empty box leaves: the pack kernel, which
 // overwrites it, does not run then).  One workgroup.
@@ -64,7 +51,7 @@ __global__ __launch_bounds__(256) void volym_distance_init_kernel(unsigned long 
 // Left to right the map gets dl, the distance to the nearest seed at or left of the texel (NONE: none); dl == 0 marks the seeds, so
 // the sweep back from the right needs no second look at the scene's bytes.
 template <bool LABELS>
-__global__ __launch_bounds__(256) void volym_distance_rows_kernel(DistanceArgs a, DistanceSelect select, uint32_t* __restrict__ map,
+__global__ __launch_bounds__(256) void volym_distance_rows_kernel(DistanceArgs a, BoxSelect select, uint32_t* __restrict__ map,
                                                                   unsigned long long* __restrict__ keys)
 {
     __shared__ uint8_t s_select[256];
@@ -76,7 +63,7 @@ __global__ __launch_bounds__(256) void volym_distance_rows_kernel(DistanceArgs a
     const uint64_t from = ~0ull << lane;                                        // bits lane..63
     const bool inside = a.inside != 0u;
     unsigned long long wave_solid = 0ull, wave_present = 0ull;
-    for (uint32_t row = distance_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t y = a.lo[1] + row % a.h, z = a.lo[2] + row / a.h;
         const uint32_t base = row * a.w;
         uint32_t carry = DISTANCE_NONE;                             // x of the last seed of the chunks before (wave-uniform)
@@ -85,9 +72,9 @@ __global__ __launch_bounds__(256) void volym_distance_rows_kernel(DistanceArgs a
             const bool in = xi < a.w;
             bool present = false, solid = false;
             if (in) {
-                const uint32_t o = layout_offset(a.bricked != 0u, bx, bxy, a.lo[0] + xi, y, z);
-                present = a.vol[o] >= a.min_byte;
-                if (present) solid = s_select[LABELS ? a.labels[o] : 0u] != 0u;
+                uint32_t label;
+                present = box_present<LABELS>(a, layout_offset(a.bricked != 0u, bx, bxy, a.lo[0] + xi, y, z), label);
+                solid = present && box_selected(s_select, label);
             }
             const uint64_t sol = __ballot(solid);
             const uint64_t s = inside ? __ballot(in && !solid) : sol;
@@ -218,7 +205,7 @@ __global__ __launch_bounds__(256) void volym_distance_finish_kernel(DistanceArgs
     // a lane carries the nearest present texel of one run of equal labels and flushes it when the label changes, and at the end
     uint32_t cur = 256u;
     unsigned long long cur_key = ~0ull;
-    for (uint32_t row = distance_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         const uint32_t ry = row % a.h, rz = row / a.h;
         const uint32_t y = a.lo[1] + ry, z = a.lo[2] + rz;
         const uint32_t base = row * a.w;
@@ -243,9 +230,8 @@ __global__ __launch_bounds__(256) void volym_distance_finish_kernel(DistanceArgs
             if (finite) {
                 const unsigned long long hi = static_cast<unsigned long long>(d) << 32;
                 lane_max = max(lane_max, hi | static_cast<uint32_t>(~i));
-                const uint32_t o = layout_offset(a.bricked != 0u, bx, bxy, a.lo[0] + xi, y, z);
-                if (a.vol[o] >= a.min_byte) {
-                    const uint32_t label = LABELS ? a.labels[o] : 0u;
+                uint32_t label;
+                if (box_present<LABELS>(a, layout_offset(a.bricked != 0u, bx, bxy, a.lo[0] + xi, y, z), label)) {
                     if (label != cur) {
                         if (cur < 256u) atomicMin(&s_near[cur], cur_key);
                         cur = label; cur_key = ~0ull;

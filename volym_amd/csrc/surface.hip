@@ -26,37 +26,9 @@ static_assert(sizeof(volym_surface_face) == 8 && offsetof(volym_surface_face, di
 void volym::free_surface(volym_ctx* c)
 {
     c->surface.release();
-    c->surface_rows.release();
-    c->surface_sums.release();
+    c->surface_offsets.release();
     c->surface_faces.release();
     c->surface_faces_valid = c->surface_total_known = false;
-}
-
-// the arguments of the walk for request s (checked, box not empty)
-static SurfaceArgs walk_args(const volym_ctx* c, const volym_surface& s, const uint8_t* vol, bool labels)
-{
-    SurfaceArgs a = {};
-    a.vol = vol;
-    a.labels = labels ? c->d_labels : nullptr;
-    for (int i = 0; i < 3; ++i) { a.lo[i] = s.box[i]; a.hi[i] = s.box[3 + i]; }
-    a.nx = c->nx; a.ny = c->ny; a.nz = c->nz;
-    a.bricked = c->bricked ? 1u : 0u;
-    a.min_byte = s.min_byte;
-    a.n_rows = (a.hi[1] - a.lo[1]) * (a.hi[2] - a.lo[2]);          // (at most 4096^2 = 2^24)
-    return a;
-}
-
-static bool empty_box(const volym_surface& s)
-{
-    return s.box[0] >= s.box[3] || s.box[1] >= s.box[4] || s.box[2] >= s.box[5];
-}
-
-// One wave per row and step, four waves per workgroup; at least so many workgroups that no wave walks more than
-// SURFACE_ROWS_PER_WAVE rows (the widths of surface_kernels.h rest on it), at most eight per CU beyond that.
-static uint32_t walk_grid(const volym_ctx* c, uint32_t n_rows)
-{
-    const uint32_t wanted = (n_rows + 3u) / 4u, floor_grid = (n_rows + 4u * SURFACE_ROWS_PER_WAVE - 1u) / (4u * SURFACE_ROWS_PER_WAVE);
-    return std::max(std::max(std::min(wanted, static_cast<uint32_t>(c->n_cus) * 8u), floor_grid), 1u);
 }
 
 extern "C" {
@@ -87,20 +59,14 @@ int volym_surface_pass(volym_ctx* c, const volym_surface* s)
     if (rc != VOLYM_OK) return rc;
     HIPCHK(c, hipSetDevice(c->device));
     const hipStream_t stream = c->slot0().stream;       // where pick, slice, projection and measure passes go
-    const bool empty = empty_box(*s);
+    const bool empty = box_empty(s->box);
     const uint32_t n_rows = empty ? 0u : (s->box[4] - s->box[1]) * (s->box[5] - s->box[2]);
     // (a set-up step, once: with the growth below the one blocking path of a pass)
     rc = c->surface.reserve(c, stream, 1, "surface summary");
     if (rc != VOLYM_OK) return rc;
-    if (n_rows > c->surface_rows.capacity) {
-        // the offsets and the block sums of their scan are replaced together, and the summary they belong to is void from here on;
-        // should either allocation fail neither is kept
-        c->surface.count = 0;
-        const size_t n_sums = (static_cast<size_t>(n_rows) + VOLYM_SURFACE_SCAN_ROWS - 1u) / VOLYM_SURFACE_SCAN_ROWS;
-        rc = c->surface_rows.reserve(c, stream, n_rows, "surface row offsets");
-        if (rc == VOLYM_OK) { c->surface_sums.release(); rc = c->surface_sums.reserve(c, stream, n_sums, "surface row offsets"); }
-        if (rc != VOLYM_OK) { c->surface_rows.release(); c->surface_sums.release(); return rc; }
-    }
+    if (n_rows > c->surface_offsets.rows.capacity) c->surface.count = 0;      // the summary the offsets belong to is void from here on
+    rc = c->surface_offsets.reserve(c, stream, n_rows, "surface row offsets");
+    if (rc != VOLYM_OK) return rc;
     hipLaunchKernelGGL(volym_surface_init_kernel, dim3(1), dim3(256), 0, stream, reinterpret_cast<unsigned long long*>(c->surface.ptr),
                        static_cast<uint32_t>(sizeof(volym_surface_summary) / 8u));
     HIPCHK(c, hipGetLastError());
@@ -115,26 +81,16 @@ int volym_surface_pass(volym_ctx* c, const volym_surface* s)
     c->surface_faces_valid = false;
     if (empty) return VOLYM_OK;                         // a zero summary, no rows: nothing else is launched
 
-    const SurfaceArgs a = walk_args(c, *s, c->surface_vol, with_labels);
-    SurfaceSelect select;
+    const SurfaceArgs a = box_walk_args(c, s->box, s->min_byte, c->surface_vol, with_labels);
+    BoxSelect select;
     std::memcpy(select.v, s->select, 256);
     volym_surface_summary* d = c->surface.ptr;
     const SurfaceOut out = {reinterpret_cast<unsigned long long*>(&d->faces[0][0]), reinterpret_cast<unsigned long long*>(&d->total),
                             reinterpret_cast<unsigned long long*>(&d->pos[0][0]), reinterpret_cast<unsigned long long*>(&d->neg[0][0])};
     const auto count = with_labels ? volym_surface_count_kernel<true> : volym_surface_count_kernel<false>;
-    uint32_t* const rows = c->surface_rows.ptr;
-    uint32_t* const sums = c->surface_sums.ptr;
-    hipLaunchKernelGGL(count, dim3(walk_grid(c, n_rows)), dim3(256), 0, stream, a, select, out, rows);
+    hipLaunchKernelGGL(count, dim3(walk_grid(c, n_rows)), dim3(256), 0, stream, a, select, out, c->surface_offsets.rows.ptr);
     HIPCHK(c, hipGetLastError());
-    // the scan: counts -> offsets, in place (a grid of one workgroup runs the same three phases)
-    const uint32_t n_blocks = (n_rows + VOLYM_SURFACE_SCAN_ROWS - 1u) / VOLYM_SURFACE_SCAN_ROWS;
-    hipLaunchKernelGGL(volym_surface_scan_sums_kernel, dim3(n_blocks), dim3(256), 0, stream, rows, sums, n_rows);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(volym_surface_scan_blocks_kernel, dim3(1), dim3(256), 0, stream, sums, n_blocks);
-    HIPCHK(c, hipGetLastError());
-    hipLaunchKernelGGL(volym_surface_scan_rows_kernel, dim3(n_blocks), dim3(256), 0, stream, rows, sums, n_rows);
-    HIPCHK(c, hipGetLastError());
-    return VOLYM_OK;
+    return scan_row_offsets(c, stream, c->surface_offsets, n_rows);      // counts -> offsets, in place
 }
 
 int volym_read_surface(volym_ctx* c, struct volym_surface_summary* out)
@@ -183,11 +139,11 @@ int volym_surface_faces_pass(volym_ctx* c, void* target_device, uint64_t capacit
     }
     if (total == 0u) return VOLYM_OK;                    // (an empty box has no rows either)
     const volym_surface& s = c->surface_request;
-    const SurfaceArgs a = walk_args(c, s, c->surface_vol, c->surface_labels);
-    SurfaceSelect select;
+    const SurfaceArgs a = box_walk_args(c, s.box, s.min_byte, c->surface_vol, c->surface_labels);
+    BoxSelect select;
     std::memcpy(select.v, s.select, 256);
     const auto emit = c->surface_labels ? volym_surface_emit_kernel<true> : volym_surface_emit_kernel<false>;
-    hipLaunchKernelGGL(emit, dim3(walk_grid(c, a.n_rows)), dim3(256), 0, stream, a, select, c->surface_rows.ptr, target);
+    hipLaunchKernelGGL(emit, dim3(walk_grid(c, a.n_rows)), dim3(256), 0, stream, a, select, c->surface_offsets.rows.ptr, target);
     HIPCHK(c, hipGetLastError());
     return VOLYM_OK;
 }

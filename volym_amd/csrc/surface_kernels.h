@@ -2,11 +2,10 @@
 // request, counted per label and direction with their divergence moments, and written out as one list in canonical order.
 // Included by surface.hip alone.
 //
-// The walk both passes share.  A ROW of the request's box (fixed y, z; x ascending) belongs to one wave, which walks it in chunks
-// of 64 consecutive x: lane i of chunk c stands on x = lo_x + 64 * c + i, a run of one texel per step, so that the wave's loads are
-// 64 consecutive bytes of a linear row (16 whole x-runs of a bricked one).  The solidity of the chunk is one 64-bit ballot S.  The
-// x neighbours need no load: they are S shifted by one lane, with bit 63 of the chunk before and bit 0 of the chunk after, which
-// the wave loads one step ahead and which becomes its own S in the next step (every texel of the row is loaded once as "self").
+// The walk both passes share is the row walk of box_walk.h: lane i of chunk c stands on x = lo_x + 64 * c + i, a run of one texel
+// per step, so that the wave's loads are 64 consecutive bytes of a linear row (16 whole x-runs of a bricked one).  The solidity of
+// the chunk is one 64-bit ballot S.  The x neighbours need no load: they are S shifted by one lane, with bit 63 of the chunk
+// before and bit 0 of the chunk after, which the wave loads one step ahead and which becomes its own S in the next step (every texel of the row is loaded once as "self").
 // The y and z neighbours are loaded only by lanes whose own texel is solid -- air asks nothing -- and only where they lie inside
 // the request's box: a neighbour outside the box is not solid by the rule, whatever its bytes, and is never read.  So every load
 // is of a texel inside the request's box, which volym_surface_check puts inside the volume.
@@ -17,19 +16,11 @@
 // a box from x = 5) needs no keep mask -- the trap of measure_own_run does not exist in this form.
 #pragma once
 
-#include "context.hpp"
+#include "box_walk.h"
 
 namespace volym {
 
-struct SurfaceSelect { uint8_t v[256]; };
-
-struct SurfaceArgs {
-    const uint8_t* vol;
-    const uint8_t* labels;              // LABELS only
-    uint32_t lo[3], hi[3];              // the request's box, not empty
-    uint32_t nx, ny, nz, bricked, min_byte;
-    uint32_t n_rows;                    // (hi[1] - lo[1]) * (hi[2] - lo[2]) <= 4096^2
-};
+using SurfaceArgs = BoxWalkArgs;
 
 // the summary in device memory: struct volym_surface_summary, as the arrays the kernels index
 struct SurfaceOut {
@@ -39,29 +30,18 @@ struct SurfaceOut {
     unsigned long long* neg;            // [256][3]
 };
 
-// Widths.  The host launches at least ceil(n_rows / (4 * SURFACE_ROWS_PER_WAVE)) workgroups of four waves (surface.hip), so a wave
+// Widths.  The host launches at least ceil(n_rows / (4 * WALK_ROWS_PER_WAVE)) workgroups of four waves (walk_grid), so a wave
 // walks at most 4096 rows of at most 4096 texels, a lane at most 64 texels of each: 2^18 texels.
 //   lane, u32:       faces of one direction <= 2^18; a moment <= 2^18 * 4096 = 2^30.
 //   workgroup, LDS:  256 lanes: faces of one (label, direction) <= 2^26, u32; a moment <= 2^38: 64-bit.
 //   wave, u64:       the wave's faces (6 * 2^24 at most) are summed in a 64-bit scalar.
 //   row, u32:        at most 6 * 4096 faces.
 //   global:          everything 64-bit; the row offsets are 32-bit, and volym_surface_faces_pass refuses a total beyond them.
-constexpr uint32_t SURFACE_ROWS_PER_WAVE = 4096u;
+static_assert(WALK_ROWS_PER_WAVE == 4096u, "the widths above");
 
 __global__ __launch_bounds__(256) void volym_surface_init_kernel(unsigned long long* summary, uint32_t n_words)
 {
     for (uint32_t i = threadIdx.x; i < n_words; i += 256u) summary[i] = 0ull;
-}
-
-template <bool LABELS>
-__device__ __forceinline__ bool surface_solid(const SurfaceArgs& a, const uint8_t* s_select, uint32_t bx, uint32_t bxy, uint32_t x, uint32_t y,
-                                              uint32_t z, uint32_t& label)
-{
-    const uint32_t o = layout_offset(a.bricked != 0u, bx, bxy, x, y, z);
-    label = 0u;                                                    // no labels held: the constant 0
-    if (a.vol[o] < a.min_byte) return false;
-    if (LABELS) label = a.labels[o];
-    return s_select[label] != 0u;
 }
 
 // One row, chunk by chunk: step(x, label, S, F) is called once per chunk by all 64 lanes with the lane's own x and label (label
@@ -75,12 +55,12 @@ __device__ __forceinline__ void surface_walk_row(const SurfaceArgs& a, const uin
     const bool ym = y > a.lo[1], yp = y + 1u < a.hi[1], zm = z > a.lo[2], zp = z + 1u < a.hi[2];
     uint32_t label_next = 0u;
     uint32_t x = a.lo[0] + lane;
-    uint64_t s_next = __ballot(x < a.hi[0] && surface_solid<LABELS>(a, s_select, bx, bxy, x, y, z, label_next));
+    uint64_t s_next = __ballot(x < a.hi[0] && box_solid<LABELS>(a, s_select, layout_offset(a.bricked != 0u, bx, bxy, x, y, z), label_next));
     uint64_t before = 0ull;                                        // bit 0: the last texel of the chunk before is solid
     for (uint32_t x0 = a.lo[0]; x0 < a.hi[0]; x0 += 64u, x += 64u) {
         const uint64_t s = s_next;
         const uint32_t label = label_next;
-        s_next = __ballot(x + 64u < a.hi[0] && surface_solid<LABELS>(a, s_select, bx, bxy, x + 64u, y, z, label_next));
+        s_next = __ballot(x + 64u < a.hi[0] && box_solid<LABELS>(a, s_select, layout_offset(a.bricked != 0u, bx, bxy, x + 64u, y, z), label_next));
         const bool self = (s >> lane) & 1ull;                      // (a lane beyond the row's end is not solid)
         // the four y and z neighbours together: their density bytes in one round of loads, then their label bytes in one, not eight
         // dependent loads one after the other (the walk waits for memory, not for arithmetic)
@@ -103,15 +83,10 @@ __device__ __forceinline__ void surface_walk_row(const SurfaceArgs& a, const uin
     }
 }
 
-__device__ __forceinline__ uint32_t surface_wave_index()
-{
-    return __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-}
-
 // The count pass: rows[row] = faces of the row; the per-label face counts and moments through LDS into the summary, as
 // volym_measure_kernel accumulates: a lane carries one run of equal labels and flushes it when the label changes and at the end.
 template <bool LABELS>
-__global__ __launch_bounds__(256) void volym_surface_count_kernel(SurfaceArgs a, SurfaceSelect select, SurfaceOut out, uint32_t* __restrict__ rows)
+__global__ __launch_bounds__(256) void volym_surface_count_kernel(SurfaceArgs a, BoxSelect select, SurfaceOut out, uint32_t* __restrict__ rows)
 {
     __shared__ uint32_t s_faces[256 * 6];                          // (widths: see above)
     __shared__ unsigned long long s_pos[256 * 3], s_neg[256 * 3], s_total;
@@ -139,7 +114,7 @@ __global__ __launch_bounds__(256) void volym_surface_count_kernel(SurfaceArgs a,
         }
     };
     unsigned long long wave_total = 0ull;
-    for (uint32_t row = surface_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         uint32_t row_total = 0u;
         surface_walk_row<LABELS>(a, s_select, bx, bxy, row, lane, [&](uint32_t x, uint32_t y, uint32_t z, uint32_t label, uint64_t s, const uint64_t (&f)[6]) {
 #pragma unroll
@@ -182,7 +157,7 @@ __global__ __launch_bounds__(256) void volym_surface_count_kernel(SurfaceArgs a,
 // The emit pass: the same walk; rows[row] is now the offset of the row's first face.  A face record is 8 bytes, stored whole:
 // x | y << 16, z | dir << 16 | label << 24.
 template <bool LABELS>
-__global__ __launch_bounds__(256) void volym_surface_emit_kernel(SurfaceArgs a, SurfaceSelect select, const uint32_t* __restrict__ rows, uint2* __restrict__ faces)
+__global__ __launch_bounds__(256) void volym_surface_emit_kernel(SurfaceArgs a, BoxSelect select, const uint32_t* __restrict__ rows, uint2* __restrict__ faces)
 {
     __shared__ uint8_t s_select[256];
     s_select[threadIdx.x] = select.v[threadIdx.x];
@@ -190,7 +165,7 @@ __global__ __launch_bounds__(256) void volym_surface_emit_kernel(SurfaceArgs a, 
     const uint32_t bx = layout_bx(a.bricked != 0u, a.nx), bxy = layout_bxy(a.bricked != 0u, a.nx, a.ny);
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t below = (1ull << lane) - 1ull;
-    for (uint32_t row = surface_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
+    for (uint32_t row = box_wave_index(); row < a.n_rows; row += gridDim.x * 4u) {
         uint32_t at = rows[row];                                   // wave-uniform: where the chunk's first face goes
         surface_walk_row<LABELS>(a, s_select, bx, bxy, row, lane, [&](uint32_t x, uint32_t y, uint32_t z, uint32_t label, uint64_t s, const uint64_t (&f)[6]) {
             uint32_t mine = at;
@@ -206,60 +181,6 @@ __global__ __launch_bounds__(256) void volym_surface_emit_kernel(SurfaceArgs a, 
                 if ((f[d] >> lane) & 1ull) faces[mine++] = make_uint2(w0, w1 | (d << 16));
         });
     }
-}
-
-// ---- the scan of the row counts: three plain phases, no workgroup waits for another --------------------------------------------
-// rows[] in blocks of VOLYM_SURFACE_SCAN_ROWS = 256: (1) the sum of every block, (2) one workgroup turns the block sums into their
-// exclusive prefix, in place, (3) every block scans its own rows, in place, from its prefix.  Sums wrap at 2^32; a total that does
-// is refused before any offset is used.
-constexpr uint32_t SURFACE_SCAN_ROWS = VOLYM_SURFACE_SCAN_ROWS;
-static_assert(SURFACE_SCAN_ROWS == 256u, "one row per thread of a 256-thread workgroup");
-
-// exclusive prefix of v over the 256 threads of the workgroup; *sum (if not NULL) the total
-__device__ __forceinline__ uint32_t surface_block_scan(uint32_t v, uint32_t* s_scan, uint32_t* sum)
-{
-    const uint32_t t = threadIdx.x;
-    s_scan[t] = v;
-    __syncthreads();
-    for (uint32_t step = 1u; step < 256u; step <<= 1) {
-        const uint32_t add = t >= step ? s_scan[t - step] : 0u;
-        __syncthreads();
-        s_scan[t] += add;
-        __syncthreads();
-    }
-    const uint32_t inclusive = s_scan[t];
-    if (sum) *sum = s_scan[255];
-    __syncthreads();                                               // (s_scan may be used again)
-    return inclusive - v;
-}
-
-__global__ __launch_bounds__(256) void volym_surface_scan_sums_kernel(const uint32_t* __restrict__ rows, uint32_t* __restrict__ sums, uint32_t n_rows)
-{
-    __shared__ uint32_t s_scan[256];
-    const uint32_t i = blockIdx.x * SURFACE_SCAN_ROWS + threadIdx.x;
-    uint32_t sum;
-    (void)surface_block_scan(i < n_rows ? rows[i] : 0u, s_scan, &sum);
-    if (threadIdx.x == 0u) sums[blockIdx.x] = sum;
-}
-
-// one workgroup; thread t owns the ceil(n_blocks / 256) consecutive sums from t * per on
-__global__ __launch_bounds__(256) void volym_surface_scan_blocks_kernel(uint32_t* __restrict__ sums, uint32_t n_blocks)
-{
-    __shared__ uint32_t s_scan[256];
-    const uint32_t per = (n_blocks + 255u) / 256u;
-    const uint32_t b0 = min(threadIdx.x * per, n_blocks), b1 = min(b0 + per, n_blocks);
-    uint32_t mine = 0u;
-    for (uint32_t b = b0; b < b1; ++b) mine += sums[b];
-    uint32_t run = surface_block_scan(mine, s_scan, nullptr);
-    for (uint32_t b = b0; b < b1; ++b) { const uint32_t v = sums[b]; sums[b] = run; run += v; }
-}
-
-__global__ __launch_bounds__(256) void volym_surface_scan_rows_kernel(uint32_t* __restrict__ rows, const uint32_t* __restrict__ sums, uint32_t n_rows)
-{
-    __shared__ uint32_t s_scan[256];
-    const uint32_t i = blockIdx.x * SURFACE_SCAN_ROWS + threadIdx.x;
-    const uint32_t before = surface_block_scan(i < n_rows ? rows[i] : 0u, s_scan, nullptr);
-    if (i < n_rows) rows[i] = sums[blockIdx.x] + before;
 }
 
 }  // namespace volym

@@ -408,6 +408,37 @@ def _replaced(obj, noun, names, kw):
     return type(obj)(**fields)
 
 
+# The box of a request over the scene's bytes (Measure, Surface, Components, Distance, Relabel, Brush): (lo, hi) in texels.
+def _box_or_whole(box, dims, missing):
+    """`box` as two tuples of int; None: the whole volume, which needs dims -- ValueError(missing) without them."""
+    if box is None:
+        if dims is None:
+            raise ValueError(missing)
+        box = ((0, 0, 0), tuple(int(v) for v in dims))
+    lo, hi = box
+    return (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+
+
+def _box_to_c(box, noun):
+    """The six u32 of a request's box; ValueError in the name of `noun` where they are not."""
+    v = list(box[0]) + list(box[1])
+    if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+        raise ValueError("%s: the box is two triples of u32 texel indices" % noun)
+    return (C.c_uint32 * 6)(*v)
+
+
+def _box_in_dims(box, dims, noun):
+    """(lo, hi, dims as a list of int) of a box with 0 <= lo <= hi <= dims on every axis; ValueError in the name of `noun`."""
+    dims = [int(v) for v in dims]
+    lo, hi = box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("%s: the box is two triples of texel indices" % noun)
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("%s box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (noun, a, dims[a], lo[a], hi[a]))
+    return lo, hi, dims
+
+
 SLICE_MAX = 8192                   # largest width and height of a slice
 SLICE_LIMIT = 1 << 30              # every corner position of a slice lies in [-2^30, 2^30), 16.16
 _SLICE_AXES = {"x": 0, "y": 1, "z": 2, 0: 0, 1: 1, 2: 2}
@@ -614,12 +645,7 @@ class Measure:
     -> histogram group 0..7 or _lib.MEASURE_NO_GROUP (None: every label in group 0)."""
 
     def __init__(self, box=None, flags=0, group=None, dims=None):
-        if box is None:
-            if dims is None:
-                raise ValueError("a measure without a box needs the volume's dims")
-            box = ((0, 0, 0), tuple(int(v) for v in dims))
-        lo, hi = box
-        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.box = _box_or_whole(box, dims, "a measure without a box needs the volume's dims")
         self.flags = int(flags)
         self.group = np.zeros(256, np.int64) if group is None else np.array(group, np.int64).ravel()
 
@@ -630,10 +656,7 @@ class Measure:
     def to_c(self):
         """The _lib.Measure of this request.  Fields that do not fit their C types raise ValueError."""
         c = _lib.Measure()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("measure: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
+        c.box = _box_to_c(self.box, "measure")
         if not 0 <= self.flags < 2 ** 32:
             raise ValueError("measure: flags = %d is not a u32" % self.flags)
         c.flags = self.flags
@@ -660,13 +683,7 @@ def check_measure(measure, dims):
     """The validity rules of volym_measure_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits, every
     group entry below 8 or 255.  Returns the measure; raises ValueError."""
     m = measure
-    dims = [int(v) for v in dims]
-    lo, hi = m.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("measure: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("measure box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    _box_in_dims(m.box, dims, "measure")
     if m.flags & ~_lib.MEASURE_UNCUT or m.flags < 0:
         raise ValueError("measure: unknown flag bits in %#x" % m.flags)
     g = np.asarray(m.group)
@@ -776,12 +793,7 @@ class Surface:
     solid (None: every label)."""
 
     def __init__(self, box=None, flags=0, min_byte=1, select=None, dims=None):
-        if box is None:
-            if dims is None:
-                raise ValueError("a surface without a box needs the volume's dims")
-            box = ((0, 0, 0), tuple(int(v) for v in dims))
-        lo, hi = box
-        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.box = _box_or_whole(box, dims, "a surface without a box needs the volume's dims")
         self.flags = int(flags)
         self.min_byte = int(min_byte)
         self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
@@ -793,10 +805,7 @@ class Surface:
     def to_c(self):
         """The _lib.Surface of this request.  Fields that do not fit their C types raise ValueError."""
         c = _lib.Surface()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("surface: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
+        c.box = _box_to_c(self.box, "surface")
         if not 0 <= self.flags < 2 ** 32 or not 0 <= self.min_byte < 2 ** 32:
             raise ValueError("surface: flags = %d and min_byte = %d must be u32" % (self.flags, self.min_byte))
         c.flags, c.min_byte = self.flags, self.min_byte
@@ -820,13 +829,7 @@ def check_surface(surface, dims):
     """The validity rules of volym_surface_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits, min_byte
     in 1..255.  Returns the surface; raises ValueError."""
     s = surface
-    dims = [int(v) for v in dims]
-    lo, hi = s.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("surface: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("surface box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    _box_in_dims(s.box, dims, "surface")
     if s.flags & ~_lib.SURFACE_UNCUT or s.flags < 0:
         raise ValueError("surface: unknown flag bits in %#x" % s.flags)
     if not 1 <= s.min_byte <= 255:
@@ -959,12 +962,7 @@ class Components:
     (0: _lib.COMPONENTS_DEFAULT_MAX)."""
 
     def __init__(self, box=None, flags=0, min_byte=1, select=None, max_components=0, dims=None):
-        if box is None:
-            if dims is None:
-                raise ValueError("components without a box need the volume's dims")
-            box = ((0, 0, 0), tuple(int(v) for v in dims))
-        lo, hi = box
-        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.box = _box_or_whole(box, dims, "components without a box need the volume's dims")
         self.flags = int(flags)
         self.min_byte = int(min_byte)
         self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
@@ -977,10 +975,7 @@ class Components:
     def to_c(self):
         """The _lib.Components of this request.  Fields that do not fit their C types raise ValueError."""
         c = _lib.Components()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("components: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
+        c.box = _box_to_c(self.box, "components")
         if not 0 <= self.flags < 2 ** 32 or not 0 <= self.min_byte < 2 ** 32 or not 0 <= self.max_components < 2 ** 32:
             raise ValueError("components: flags = %d, min_byte = %d and max_components = %d must be u32" % (self.flags, self.min_byte, self.max_components))
         c.flags, c.min_byte, c.max_components = self.flags, self.min_byte, self.max_components
@@ -995,13 +990,7 @@ def check_components(components, dims):
     _lib.COMPONENTS_BOX_MAX texels in the box, known flag bits, min_byte in 1..255, max_components at most
     _lib.COMPONENTS_TABLE_MAX.  Returns the request; raises ValueError."""
     c = components
-    dims = [int(v) for v in dims]
-    lo, hi = c.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("components: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("components box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    lo, hi, dims = _box_in_dims(c.box, dims, "components")
     texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
     if texels > _lib.COMPONENTS_BOX_MAX:
         raise ValueError("components: the box has %d texels, more than 2^31 - 2" % texels)
@@ -1165,12 +1154,7 @@ class Distance:
     (flags: _lib.DISTANCE_UNCUT | _lib.DISTANCE_INSIDE); weight: the three integer weights of the squared distance, 1..64 each."""
 
     def __init__(self, box=None, flags=0, min_byte=1, select=None, weight=(1, 1, 1), dims=None):
-        if box is None:
-            if dims is None:
-                raise ValueError("a distance request without a box needs the volume's dims")
-            box = ((0, 0, 0), tuple(int(v) for v in dims))
-        lo, hi = box
-        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.box = _box_or_whole(box, dims, "a distance request without a box needs the volume's dims")
         self.flags = int(flags)
         self.min_byte = int(min_byte)
         self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
@@ -1183,10 +1167,7 @@ class Distance:
     def to_c(self):
         """The _lib.Distance of this request.  Fields that do not fit their C types raise ValueError."""
         c = _lib.Distance()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("distance: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
+        c.box = _box_to_c(self.box, "distance")
         if not 0 <= self.flags < 2 ** 32 or not 0 <= self.min_byte < 2 ** 32:
             raise ValueError("distance: flags = %d and min_byte = %d must be u32" % (self.flags, self.min_byte))
         c.flags, c.min_byte = self.flags, self.min_byte
@@ -1204,13 +1185,7 @@ def check_distance(distance, dims):
     _lib.DISTANCE_BOX_MAX texels in the box, known flag bits, min_byte in 1..255, every weight in 1.._lib.DISTANCE_WEIGHT_MAX.
     Returns the request; raises ValueError."""
     d = distance
-    dims = [int(v) for v in dims]
-    lo, hi = d.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("distance: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("distance box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    lo, hi, dims = _box_in_dims(d.box, dims, "distance")
     texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
     if texels > _lib.DISTANCE_BOX_MAX:
         raise ValueError("distance: the box has %d texels, more than 2^31 - 2" % texels)
@@ -1378,12 +1353,7 @@ class Relabel:
     ids: (id_lo, id_hi) in the latest components pass; d2: (d2_lo, d2_hi) in the latest distance map."""
 
     def __init__(self, box=None, flags=0, window=(0, 255), to=None, ids=(0, 0), d2=(0, 0), dims=None):
-        if box is None:
-            if dims is None:
-                raise ValueError("a relabel request without a box needs the volume's dims")
-            box = ((0, 0, 0), tuple(int(v) for v in dims))
-        lo, hi = box
-        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.box = _box_or_whole(box, dims, "a relabel request without a box needs the volume's dims")
         self.flags = int(flags)
         self.window = tuple(int(v) for v in window)
         self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
@@ -1397,10 +1367,7 @@ class Relabel:
     def to_c(self):
         """The _lib.Relabel of this request.  Fields that do not fit their C types raise ValueError."""
         c = _lib.Relabel()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("relabel: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
+        c.box = _box_to_c(self.box, "relabel")
         pairs = (self.window, self.ids, self.d2)
         if not 0 <= self.flags < 2 ** 32 or not all(len(p) == 2 and all(0 <= x < 2 ** 32 for x in p) for p in pairs):
             raise ValueError("relabel: flags, window, ids and d2 must be u32 (pairs)")
@@ -1419,13 +1386,7 @@ def check_relabel(relabel, dims):
     only with IDS, min_byte <= max_byte <= 255, id_lo <= id_hi with IDS, d2_lo <= d2_hi with DISTANCE.  Returns the request; raises
     ValueError."""
     r = relabel
-    dims = [int(v) for v in dims]
-    lo, hi = r.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("relabel: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("relabel box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    _box_in_dims(r.box, dims, "relabel")
     known = _lib.RELABEL_UNCUT | _lib.RELABEL_IDS | _lib.RELABEL_IDS_EXCEPT | _lib.RELABEL_DISTANCE | _lib.RELABEL_DRY_RUN
     if r.flags & ~known or r.flags < 0:
         raise ValueError("relabel: unknown flag bits in %#x" % r.flags)
@@ -1503,12 +1464,7 @@ class Brush:
     _lib.BRUSH_MAX_POINTS texels (x, y, z) or (x, y, z, flags), flags = _lib.BRUSH_LIFT: no capsule from the point before."""
 
     def __init__(self, points, r2, box=None, flags=0, window=(0, 255), to=None, weight=(1, 1, 1), dims=None):
-        if box is None:
-            if dims is None:
-                raise ValueError("a brush request without a box needs the volume's dims")
-            box = ((0, 0, 0), tuple(int(v) for v in dims))
-        lo, hi = box
-        self.box = (tuple(int(v) for v in lo), tuple(int(v) for v in hi))
+        self.box = _box_or_whole(box, dims, "a brush request without a box needs the volume's dims")
         self.flags = int(flags)
         self.window = tuple(int(v) for v in window)
         self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
@@ -1523,10 +1479,7 @@ class Brush:
     def to_c(self):
         """The _lib.Brush of this request.  Fields that do not fit their C types raise ValueError."""
         c = _lib.Brush()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("brush: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
+        c.box = _box_to_c(self.box, "brush")
         if not 0 <= self.flags < 2 ** 32 or not 0 <= self.r2 < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
             raise ValueError("brush: flags, r2 and the window's ends must be u32")
         if len(self.weight) != 3 or not all(0 <= x < 2 ** 32 for x in self.weight):
@@ -1552,13 +1505,7 @@ def check_brush(brush, dims):
     min_byte <= max_byte <= 255, weights in 1.._lib.DISTANCE_WEIGHT_MAX, 1.._lib.BRUSH_MAX_POINTS points inside the volume, no point
     flag but LIFT; r2 is any u32.  Returns the request; raises ValueError."""
     b = brush
-    dims = [int(v) for v in dims]
-    lo, hi = b.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("brush: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("brush box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    dims = _box_in_dims(b.box, dims, "brush")[2]
     if b.flags & ~(_lib.BRUSH_UNCUT | _lib.BRUSH_DRY_RUN) or b.flags < 0:
         raise ValueError("brush: unknown flag bits in %#x" % b.flags)
     if len(b.window) != 2 or not 0 <= b.window[0] <= b.window[1] <= 255:
