@@ -1089,6 +1089,99 @@ int   volym_brush_check(const volym_brush* b, const uint32_t dims[3]);
  * VOLYM_E_INVALID for NULL or what volym_brush_check refuses. */
 int   volym_brush_box(const volym_brush* b, const uint32_t dims[3], uint32_t box_out[6]);
 
+/* --- lasso: relabel the texels under a screen polygon (new; the reference has none) --------------------------------- */
+/* Scissors: a polygon drawn over the picture, and every texel that projects into it -- through the whole volume, or through a range
+ * of depths -- is relabelled by a table, under a box and a density window, in one call -- one undo step while the history is on.
+ * With OUTSIDE the texels that do NOT project into it are: "keep only what is under the lasso".  The context ends up byte for byte
+ * where volym_edit_labels leaves it: where a context handed the edited labels would be.
+ *   The rule (integers only; scene.lasso_volume of the Python package is its host twin, equal in every byte).  For texel (x, y, z)
+ * let h = (2x + 1, 2y + 1, 2z + 1), its centre in half-texels, and, in 64-bit integers,
+ *     X = m[0] . h + c[0],   Y = m[1] . h + c[1],   D = m[2] . h + c[2].
+ * With |m| < 2^31, |c| < 2^46 and h < 2^17 (a volume has at most 4096 texels per axis: h < 2^13) no value exceeds 2^51.  The texel
+ * LANDS on pixel (px, py) iff depth[0] <= D <= depth[1] (depth[0] >= 1), 0 <= X < width * D and 0 <= Y < height * D; then
+ * px = floor(X / D), py = floor(Y / D).  It is INSIDE iff it lands on a pixel of the polygon's mask, and SELECTED iff
+ * inside != OUTSIDE: with OUTSIDE everything off screen, behind the eye or outside the depth range is selected.  A selected texel
+ * with label l becomes to[l] iff it lies in box, to[l] != l and its density byte lies in [min_byte, max_byte] (the scene byte as it
+ * stands; with UNCUT the uncut copy as volym_measure_pass reads it).  Every texel is decided once, from the bytes before the edit: a
+ * table that swaps two labels swaps them once.  DRY_RUN fills the result and writes nothing.
+ *   The polygon: n_points vertices, pixel positions in [-2^20, 2^20] that may lie off screen, closed implicitly, filled by the
+ * even-odd rule with a half-open crossing rule: pixel (px, py) is in the mask iff an odd number of edges (x0, y0) -> (x1, y1) satisfy
+ *     (y0 <= py) != (y1 <= py)   and   (px - x0) * (y1 - y0) < (x1 - x0) * (py - y0)  when y1 > y0,  > when y1 < y0
+ * -- exact in 64-bit integers (every factor is below 2^22).  Two polygons that share an edge never both claim a pixel and never both
+ * miss one; the polygon (x0,y0), (x1,y0), (x1,y1), (x0,y1) covers exactly x0 <= px < x1, y0 <= py < y1; the vertex order does not
+ * matter; a bow-tie is empty where it overlaps twice.  The mask's rect is the polygon's bounding box cut to the frame
+ * (volym_lasso_rect); if it is empty nothing is inside. */
+#define VOLYM_LASSO_MAX_POINTS 1024u
+#define VOLYM_LASSO_MAX_FRAME 16384u           /* width and height of the view */
+#define VOLYM_LASSO_VERTEX_MAX 1048576         /* |x|, |y| of a vertex: 2^20 */
+enum { VOLYM_LASSO_UNCUT = 1, VOLYM_LASSO_DRY_RUN = 16, VOLYM_LASSO_OUTSIDE = 32 };   /* flags: UNCUT and DRY_RUN carry the values of their VOLYM_RELABEL counterparts */
+/* The integer view: texel -> (X, Y, D).  volym_lasso_view_from_camera makes one from a frame's camera; any other source (an
+ * orthographic view has m[2] = 0 and c[2] > 0) works as well: the rule reads nothing but these integers. */
+struct volym_lasso_view {
+    int32_t  m[3][3];           /* rows X, Y, D: the coefficients of h; |m| < 2^31 */
+    uint32_t width, height;     /* the frame, 1..VOLYM_LASSO_MAX_FRAME each */
+    int32_t  scale_log2;        /* s of volym_lasso_view_from_camera (0 from any other source): volym_lasso_view_depth reads it, the rule does not */
+    int64_t  c[3];              /* rows X, Y, D: the constant; |c| < 2^46 */
+    int64_t  depth[2];          /* 1 <= depth[0] <= depth[1]: the range of D a texel may land from */
+};                              /* 88 bytes */
+struct volym_lasso_point { int32_t x, y; };     /* a vertex, in pixels */
+typedef struct volym_lasso {
+    uint32_t box[6];            /* as volym_relabel: {x0, y0, z0, x1, y1, z1}, lo <= hi <= volume size on every axis */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;   /* 0..255, min <= max: the density window; 0..255 = no window */
+    uint8_t  to[256];           /* old label -> new label; to[l] == l: label l is not touched */
+    uint32_t n_points;          /* 3..VOLYM_LASSO_MAX_POINTS */
+    struct volym_lasso_view view;
+    struct volym_lasso_point points[VOLYM_LASSO_MAX_POINTS];
+} volym_lasso;                  /* 8576 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(struct volym_lasso_view) == 88, "volym_lasso_view is 88 bytes");
+static_assert(sizeof(struct volym_lasso_point) == 8, "volym_lasso_point is 8 bytes");
+static_assert(sizeof(volym_lasso) == 8576, "volym_lasso is 8576 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(struct volym_lasso_view) == 88, "volym_lasso_view is 88 bytes");
+_Static_assert(sizeof(struct volym_lasso_point) == 8, "volym_lasso_point is 8 bytes");
+_Static_assert(sizeof(volym_lasso) == 8576, "volym_lasso is 8576 bytes");
+#endif
+/* The lasso: a blocking set-up call with the contract of volym_brush_labels (it waits for the frames in flight; the kernels run on
+ * the first slot's stream; with changed == 0, or DRY_RUN, nothing but the mask is touched and a surface pass stays valid; otherwise
+ * counts, boxes, density and importances follow and a surface pass is stale; out may be NULL).  A raster kernel fills the polygon's
+ * bit plane over the mask's rect (volym_read_lasso_mask reads it), then the edit kernel walks the request's box.  While the history
+ * is on, a call that changes a texel (no DRY_RUN) is one step of it, journalled into a staging area with room for min(items of the
+ * box's slab, budget / 20) records: volym_undo_labels and volym_redo_labels take it as they take an edit.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_lasso_check refuses.  VOLYM_E_STATE: what volym_edit_labels refuses of the
+ * context's state.  The native multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_lasso_labels(volym_ctx* ctx, const volym_lasso* lasso, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, a window without min_byte <= max_byte <= 255, n_points outside 3..VOLYM_LASSO_MAX_POINTS, a vertex coordinate outside
+ * [-VOLYM_LASSO_VERTEX_MAX, VOLYM_LASSO_VERTEX_MAX], an entry of m at -2^31, |c| >= 2^46, depth[0] < 1 or depth[0] > depth[1],
+ * width or height outside 1..VOLYM_LASSO_MAX_FRAME.  An empty box is valid: nothing changes.  Pure host arithmetic. */
+int   volym_lasso_check(const volym_lasso* lasso, const uint32_t dims[3]);
+/* The mask's rect: rect_out = {x0, y0, x1, y1}, hi exclusive -- the polygon's bounding box cut to the frame; all 0 when the two do
+ * not meet.  Pure host arithmetic.  VOLYM_E_INVALID for NULL, n_points, a vertex or a frame that volym_lasso_check refuses. */
+int   volym_lasso_rect(const volym_lasso* lasso, uint32_t rect_out[4]);
+/* The polygon's bit plane of the latest volym_lasso_labels that passed its checks: rect_out as volym_lasso_rect gives it, and, words
+ * not NULL, the plane's ceil((x1 - x0) / 32) * (y1 - y0) 32-bit words: pixel (px, py) is bit (px - x0) & 31 of word
+ * (py - y0) * ceil((x1 - x0) / 32) + (px - x0) / 32; the bits past x1 are 0.  For a UI that fills the lasso.  Blocks.
+ * VOLYM_E_INVALID: NULL ctx or rect_out, capacity (in words) too small.  VOLYM_E_STATE: no lasso yet. */
+int   volym_read_lasso_mask(volym_ctx* ctx, uint32_t rect_out[4], uint32_t* words, uint64_t capacity);
+/* The integer view of a frame, in the host part of the library: no context, no GPU.  camera: the frame's uniforms (view_matrix and
+ * projection_matrix are read), width x height: the frame, dims: the volume, near: the near distance along the view axis in the
+ * units of clip w (world units for a perspective projection; <= 0: none).  In double precision
+ *     C = projection * view * diag(1 / (2 nx), 1 / (2 ny), 1 / (2 nz), 1)        (the volume is the unit cube; C acts on (h, 1))
+ *     row X = (W / 2) (C0 + C3) + C3 / 2,   row Y = (H / 2) (C3 - C1) + C3 / 2,   row D = C3,
+ * so that X / D = sx + 1/2 for the texel's screen position sx: the ray of pixel gx passes through the pixel's corner gx / W, and the
+ * nearest ray to the texel is that of floor(sx + 1/2).  The three rows are scaled by the largest 2^s, s <= 40, that keeps every
+ * rounded entry inside the bounds of volym_lasso_check, and depth = [max(1, round(near * 2^s)), INT64_MAX]; out->scale_log2 = s.
+ * VOLYM_E_INVALID: NULL, a frame outside 1..VOLYM_LASSO_MAX_FRAME, a dimension outside 1..4096, a matrix that is
+ * not finite, or no such s >= -40. */
+int   volym_lasso_view_from_camera(const volym_camera_uniforms* camera, uint32_t width, uint32_t height, const uint32_t dims[3], double near,
+                                   struct volym_lasso_view* out);
+/* depth of `view` from two distances along the view axis in the units of volym_lasso_view_from_camera's near (scaled by the view's
+ * scale_log2): depth = [max(1, round(front * 2^s)), round(back * 2^s)], back = +inf: INT64_MAX.  VOLYM_E_INVALID: NULL, a
+ * distance that is not a number, back < front, or a range that rounds to depth[0] > depth[1]. */
+int   volym_lasso_view_depth(struct volym_lasso_view* view, double front, double back);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

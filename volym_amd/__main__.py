@@ -26,8 +26,8 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
---relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
+--relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -310,7 +310,7 @@ def _brush_arg(d, ctx, text):
 
 
 def _label_edits(ctx, d, args):
-    """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, split_at, keep_largest, grow, shrink):
+    """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, lasso, split_at, keep_largest, grow, shrink):
     [(option, result)]"""
     out = []
     try:
@@ -325,6 +325,18 @@ def _label_edits(ctx, d, args):
             at, name = _name_and(rest, "--brush-at", usage, None)
             s = d.stroke(ctx, [_outline_at_arg(p, "--brush-at") for p in at.split("/")], _segment_arg(name), r, over=None)
             out.append(("brush_at", None if s["relabel"] is None else dict(s["relabel"], picked=s["picked"], missed=s["missed"], calls=s["calls"])))
+        if getattr(args, "lasso", None):
+            usage = "X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO -- pixels of the polygon, the segments it cuts and the segment they join (label values or names)"
+            rest, to = _name_and(args.lasso, "--lasso", usage, None)
+            at, froms = _name_and(rest, "--lasso", usage, None)
+            try:
+                pixels = [tuple(int(v) for v in p.split(",")) for p in at.split("/")]
+            except ValueError:
+                raise SystemExit("--lasso: %s" % usage)
+            if len(pixels) < 3 or any(len(p) != 2 for p in pixels):
+                raise SystemExit("--lasso: %s" % usage)
+            out.append(("lasso", d.lasso(ctx, pixels, _segment_arg(to), over=[_segment_arg(f) for f in froms.split(",") if f],
+                                         outside=bool(getattr(args, "lasso_outside", False)))))
         if getattr(args, "split_at", None):
             at, to = _name_and(args.split_at, "--split-at", "X,Y:TO -- a pixel and the segment its piece becomes", None)
             p = d.split_at(ctx, *_outline_at_arg(at, "--split-at"), _segment_arg(to))
@@ -365,7 +377,7 @@ def run_simple(args):
             clipped = {"clip_plane": None if plane is None else {"n": list(plane[0]), "d": plane[1]}}
             d.compute_pass(ctx)
             ctx.sync()
-        # label edits, in the order relabel, brush, brush at pixels, split, keep the largest, grow, shrink; the PNG is the frame after them
+        # label edits, in the order relabel, brush, brush at pixels, lasso, split, keep the largest, grow, shrink; the PNG is the frame after them
         undo = getattr(args, "undo", None) or 0
         if undo < 0:
             raise SystemExit("--undo: N is a number of edits to take back, got %d" % undo)
@@ -613,6 +625,10 @@ def main(argv=None):
                                      "polyline of texels of the prepared volume, on the device, after --relabel; one undo step")
     run.add_argument("--brush-at", help="X,Y[/X,Y...]:NAME:R: drag the brush over those pixels: segment NAME within R texels of the polyline of the picked "
                                         "texels (a pixel without a pick breaks it)")
+    run.add_argument("--lasso", help="X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO: scissors: the texels of the segments FROM that the first frame's view projects into that "
+                                     "polygon of pixels (closed implicitly, even-odd; vertices may lie off screen) join segment TO (0: unlabelled), on the device, "
+                                     "after --brush-at; one undo step")
+    run.add_argument("--lasso-outside", action="store_true", help="with --lasso: the texels that do NOT project into the polygon instead (keep only what is under it)")
     run.add_argument("--split-at", help="X,Y:TO: the piece of the segment pixel (X, Y) shows becomes segment TO (a new name gets an entry)")
     run.add_argument("--keep-largest", help="NAME: keep the largest piece of the segment, its other pieces become unlabelled")
     run.add_argument("--grow", help="NAME:R: grow the segment by R texels into the unlabelled texels")

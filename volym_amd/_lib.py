@@ -316,6 +316,43 @@ class Brush(C.Structure):
     ]
 
 
+LASSO_UNCUT, LASSO_DRY_RUN, LASSO_OUTSIDE = 1, 16, 32         # volym_lasso.flags: UNCUT and DRY_RUN carry the values of their RELABEL counterparts
+LASSO_MAX_POINTS = 1024
+LASSO_MAX_FRAME = 16384
+LASSO_VERTEX_MAX = 1 << 20
+
+
+class LassoView(C.Structure):
+    """volym_lasso_view (include/volym_hip.h): the integer view texel -> (X, Y, D), 88 bytes"""
+    _fields_ = [
+        ("m", (C.c_int32 * 3) * 3),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("scale_log2", C.c_int32),
+        ("c", C.c_int64 * 3),
+        ("depth", C.c_int64 * 2),
+    ]
+
+
+class LassoPoint(C.Structure):
+    """volym_lasso_point (include/volym_hip.h): a vertex of the polygon in pixels, 8 bytes"""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32)]
+
+
+class Lasso(C.Structure):
+    """volym_lasso (include/volym_hip.h): box, flags, density window, label table, the integer view and the polygon, 8576 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("to", C.c_uint8 * 256),
+        ("n_points", C.c_uint32),
+        ("view", LassoView),
+        ("points", LassoPoint * LASSO_MAX_POINTS),
+    ]
+
+
 JOURNAL_RECORD_BYTES = 20     # what one journalled chunk costs of the history's budget: its index and its 16 bytes
 
 
@@ -501,6 +538,12 @@ SIGNATURES = {
     "volym_brush_labels": (C.c_int, [_ctx, C.POINTER(Brush), C.POINTER(RelabelResult)]),
     "volym_brush_check": (C.c_int, [C.POINTER(Brush), C.POINTER(C.c_uint32)]),
     "volym_brush_box": (C.c_int, [C.POINTER(Brush), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_lasso_labels": (C.c_int, [_ctx, C.POINTER(Lasso), C.POINTER(RelabelResult)]),
+    "volym_lasso_check": (C.c_int, [C.POINTER(Lasso), C.POINTER(C.c_uint32)]),
+    "volym_lasso_rect": (C.c_int, [C.POINTER(Lasso), C.POINTER(C.c_uint32)]),
+    "volym_read_lasso_mask": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64]),
+    "volym_lasso_view_from_camera": (C.c_int, [C.POINTER(CameraUniforms), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_double, C.POINTER(LassoView)]),
+    "volym_lasso_view_depth": (C.c_int, [C.POINTER(LassoView), C.c_double, C.c_double]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

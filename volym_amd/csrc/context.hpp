@@ -284,6 +284,11 @@ struct volym_ctx {
     volym::OwnedBuffer<uint32_t> journal_index;   // where an edit journals: room for the worst case of its slab within the budget
     volym::OwnedBuffer<uint4> journal_old;
 
+    // the lasso (volym_lasso_labels, lasso.inc): the polygon's bit plane of the latest call over lasso_rect; count: its words
+    volym::OwnedBuffer<uint32_t> lasso_plane;
+    uint32_t lasso_rect[4] = {};
+    bool lasso_have = false;                 // a call has passed its checks: volym_read_lasso_mask has something to read
+
     bool feedback = true;
     bool feedback_frozen = false;               // dev
     int wide_waves = 0;                         // dev: 0 default choice, 12 or 16 (raymarch.hip launch_march)
@@ -348,6 +353,8 @@ void free_distance(volym_ctx* c);
 void clear_label_history(volym_ctx* c);
 // scene_bytes.hip: the steps and the staging area of the label history (every stream idle)
 void free_label_history(volym_ctx* c);
+// scene_bytes.hip: what the context keeps of the latest lasso (every stream idle)
+void free_lasso(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);
 // scene_bytes.hip: the fine maxima alone, after VOLYM_OPT_BOUNDS_CELLS changed under a volume

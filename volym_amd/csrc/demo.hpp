@@ -118,6 +118,7 @@ public:
         if (!camera_uniforms_from(state.camera, cam)) throw Error(VOLYM_E_INVALID, "inverse_view_proj inversion failed");
         parameter_uniforms_from(state, par);
         ctx.check(volym_update(ctx.handle(), &cam, &par));
+        camera_ = cam;                 // (lasso: the view of the latest frame)
         records_current_ = false;      // (highlight: the pick records of the old view are stale)
         for (int i = 0; i < 3; ++i) eye_[i] = state.camera.position[i];      // (clip_at: the plane faces the eye)
         dense_step_ = 0.25f * par.raymarching_step_size;                     // (project: the march's dense step)
@@ -193,6 +194,31 @@ public:
         }
         volym_relabel_result out{};
         ctx.check(volym_brush_labels(ctx.handle(), &b, &out));
+        records_current_ = false;
+        return out;
+    }
+    // New: scissors on the device (volym_lasso_labels): the texels of the segments `from` (names, ids or label values as text) that the
+    // latest frame's view projects into the polygon `pixels` (3 to VOLYM_LASSO_MAX_POINTS vertices, closed implicitly, even-odd; they
+    // may lie off screen), through the whole volume, get the label of `to`.  One call, one step of the history.
+    volym_relabel_result lasso(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::array<int32_t, 2>>& pixels, const std::vector<std::string>& from,
+                               const std::string& to)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "lasso: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        if (pixels.size() < 3u || pixels.size() > VOLYM_LASSO_MAX_POINTS) throw Error(VOLYM_E_INVALID, "lasso: 3..1024 vertices");
+        std::vector<volym_lasso> request(1);                                 // (8576 bytes: off the stack)
+        volym_lasso& l = request[0];
+        l.box[3] = a.nx; l.box[4] = a.ny; l.box[5] = a.nz;
+        l.max_byte = 255u;
+        for (int k = 0; k < 256; ++k) l.to[k] = static_cast<uint8_t>(k);
+        const uint8_t target = label_value_of(a, to);
+        for (const std::string& s : from) l.to[label_value_of(a, s)] = target;
+        const uint32_t dims[3] = {a.nx, a.ny, a.nz};
+        ctx.check(volym_lasso_view_from_camera(&camera_, ctx.width, ctx.height, dims, 0.0, &l.view));
+        l.n_points = static_cast<uint32_t>(pixels.size());
+        for (size_t i = 0; i < pixels.size(); ++i) { l.points[i].x = pixels[i][0]; l.points[i].y = pixels[i][1]; }
+        volym_relabel_result out{};
+        ctx.check(volym_lasso_labels(ctx.handle(), &l, &out));
         records_current_ = false;
         return out;
     }
@@ -777,6 +803,7 @@ public:
 
 private:
     float eye_[3] = {0.0f, 0.0f, 0.0f};
+    volym_camera_uniforms camera_{};
     float dense_step_ = 0.0025f;
     bool labels_on_device_ = false;
     bool records_current_ = false;             // the device holds the records of a whole-frame pick pass of the current view and scene

@@ -529,4 +529,66 @@ int volym_map_segments_to_importance(uint8_t* data, size_t len, const uint8_t* l
     return VOLYM_OK;
 }
 
+// ---- the lasso's integer view (include/volym_hip.h): the one quantisation of a frame's camera, host arithmetic only ----
+// a distance along the view axis in the view's integers: round(d * 2^s), at least `least`, INT64_MAX past the range
+static bool lasso_depth_of(double d, int s, int64_t least, int64_t* out)
+{
+    if (std::isnan(d)) return false;
+    const double v = std::nearbyint(std::ldexp(d, s));
+    *out = v >= 9223372036854775807.0 ? INT64_MAX : (v <= static_cast<double>(least) ? least : static_cast<int64_t>(v));
+    return true;
+}
+
+int volym_lasso_view_from_camera(const volym_camera_uniforms* camera, uint32_t width, uint32_t height, const uint32_t dims[3], double near,
+                                 struct volym_lasso_view* out)
+{
+    if (!camera || !dims || !out || std::isnan(near)) return VOLYM_E_INVALID;
+    if (width < 1u || width > VOLYM_LASSO_MAX_FRAME || height < 1u || height > VOLYM_LASSO_MAX_FRAME) return VOLYM_E_INVALID;
+    for (int a = 0; a < 3; ++a) if (dims[a] < 1u || dims[a] > 4096u) return VOLYM_E_INVALID;
+    // C = projection * view * diag(1 / (2 nx), 1 / (2 ny), 1 / (2 nz), 1), rows by columns; the uniforms are column-major m[col][row]
+    double Cm[4][4];
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) {
+            double v = 0.0;
+            for (int k = 0; k < 4; ++k) v += static_cast<double>(camera->projection_matrix[k][i]) * static_cast<double>(camera->view_matrix[j][k]);
+            if (!std::isfinite(v)) return VOLYM_E_INVALID;
+            Cm[i][j] = j < 3 ? v / (2.0 * dims[j]) : v;
+        }
+    double rows[3][4];
+    for (int j = 0; j < 4; ++j) {
+        rows[0][j] = 0.5 * width * (Cm[0][j] + Cm[3][j]) + 0.5 * Cm[3][j];
+        rows[1][j] = 0.5 * height * (Cm[3][j] - Cm[1][j]) + 0.5 * Cm[3][j];
+        rows[2][j] = Cm[3][j];
+    }
+    const double m_bound = 2147483648.0, c_bound = 70368744177664.0;      // 2^31, 2^46
+    for (int s = 40; s >= -40; --s) {
+        bool fits = true;
+        for (int r = 0; r < 3 && fits; ++r)
+            for (int j = 0; j < 4 && fits; ++j) fits = std::fabs(std::nearbyint(std::ldexp(rows[r][j], s))) < (j < 3 ? m_bound : c_bound);
+        if (!fits) continue;
+        std::memset(out, 0, sizeof *out);
+        for (int r = 0; r < 3; ++r) {
+            for (int j = 0; j < 3; ++j) out->m[r][j] = static_cast<int32_t>(std::nearbyint(std::ldexp(rows[r][j], s)));
+            out->c[r] = static_cast<int64_t>(std::nearbyint(std::ldexp(rows[r][3], s)));
+        }
+        out->width = width; out->height = height; out->scale_log2 = s;
+        (void)lasso_depth_of(near, s, 1, &out->depth[0]);
+        out->depth[1] = INT64_MAX;
+        return VOLYM_OK;
+    }
+    return VOLYM_E_INVALID;
+}
+
+int volym_lasso_view_depth(struct volym_lasso_view* view, double front, double back)
+{
+    if (!view || std::isnan(front) || std::isnan(back) || back < front) return VOLYM_E_INVALID;
+    if (view->scale_log2 < -40 || view->scale_log2 > 40) return VOLYM_E_INVALID;
+    int64_t lo, hi;
+    (void)lasso_depth_of(front, view->scale_log2, 1, &lo);
+    (void)lasso_depth_of(back, view->scale_log2, INT64_MIN, &hi);
+    if (lo > hi) return VOLYM_E_INVALID;
+    view->depth[0] = lo; view->depth[1] = hi;
+    return VOLYM_OK;
+}
+
 }  // extern "C"

@@ -4,7 +4,7 @@
 // declared in context.hpp.  Everything here is blocking set-up path, except the measure pass at the end (measure.inc, measure_kernels.h),
 // which only reads these bytes and is enqueue-only, and the label edit after it (relabel.inc, relabel_kernels.h), which rewrites
 // labels in place and carries density and importances along by the same invariant, and the brush (brush.inc, brush_kernels.h), the
-// same edit decided by a stroke's geometry.
+// same edit decided by a stroke's geometry, and the lasso (lasso.inc, lasso_kernels.h), the same edit decided by where a texel projects.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,6 +17,7 @@
 #include "measure_kernels.h"
 #include "relabel_kernels.h"
 #include "brush_kernels.h"
+#include "lasso_kernels.h"
 
 using namespace volym;
 
@@ -1003,3 +1004,6 @@ int volym_label_counts(volym_ctx* c, uint64_t counts[256])
 
 // ---- the brush: the edit whose texels a stroke decides ----------------------------------------------------------------------
 #include "brush.inc"
+
+// ---- the lasso: the edit whose texels a screen polygon decides ---------------------------------------------------------------
+#include "lasso.inc"

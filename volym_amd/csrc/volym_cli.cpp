@@ -17,12 +17,15 @@
 //   --relabel FROM[,FROM...]:TO relabels those segments on the device before the picture (Simple::relabel) and prints what changed;
 //   --labels-out FILE writes the labels as they stand afterwards, raw bytes in the orientation of --labels;
 //   --brush X,Y,Z[/X,Y,Z...]:TO:R2 paints label TO within sqrt(R2) texels of that polyline of texels (Simple::brush), after --relabel;
+//   --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO cuts with the scissors: the texels of the segments FROM under that polygon of pixels of
+//   the first frame join TO (Simple::lasso), after --brush;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
 #include <algorithm>
 #include <cctype>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -69,6 +72,9 @@ struct Options {
     std::vector<std::array<uint32_t, 3>> brush_points;   // --brush X,Y,Z[/X,Y,Z...]:TO:R2: one stroke of the brush in texel coordinates (run simple)
     std::string brush_to;
     uint32_t brush_r2 = 0;
+    std::vector<std::array<int32_t, 2>> lasso_pixels;    // --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO: the scissors over a polygon of pixels (run simple)
+    std::vector<std::string> lasso_from;
+    std::string lasso_to;
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -207,6 +213,8 @@ int run_simple(const Options& o)
     if (!o.relabel_to.empty()) relabelled = demo.relabel(ctx, assets, o.relabel_from, o.relabel_to);
     volym_relabel_result brushed{};
     if (!o.brush_to.empty()) brushed = demo.brush(ctx, assets, o.brush_points, o.brush_to, o.brush_r2);       // after --relabel, before --undo
+    volym_relabel_result lassoed{};
+    if (!o.lasso_to.empty()) lassoed = demo.lasso(ctx, assets, o.lasso_pixels, o.lasso_from, o.lasso_to);   // the view of the first frame; after --brush, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -229,6 +237,7 @@ int run_simple(const Options& o)
     };
     if (!o.relabel_to.empty()) print_result("relabel", relabelled);
     if (!o.brush_to.empty()) print_result("brush", brushed);
+    if (!o.lasso_to.empty()) print_result("lasso", lassoed);
     for (const auto& u : undone) {
         if (u.first) print_result("undo", u.second);
         else std::printf("undo: nothing to take back\n");
@@ -430,6 +439,36 @@ int main(int argc, char** argv)
                 } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
                 if (o.brush_points.empty() || o.brush_points.size() > VOLYM_BRUSH_MAX_POINTS) throw Error(VOLYM_E_INVALID, usage);
             }
+            else if (a == "--lasso") {
+                const char* usage = "--lasso: X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO -- pixels of the polygon, the segments it cuts and the segment they join";
+                const std::string v = next();
+                const size_t last = v.rfind(':'), first = last == std::string::npos || last == 0u ? std::string::npos : v.rfind(':', last - 1u);
+                if (first == std::string::npos || first == 0u || first + 1u >= last || last + 1u >= v.size()) throw Error(VOLYM_E_INVALID, usage);
+                o.lasso_to = v.substr(last + 1u);
+                size_t pos = first + 1u;
+                while (pos < last) {
+                    const size_t comma = std::min(v.find(',', pos), last);
+                    if (comma > pos) o.lasso_from.push_back(v.substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+                if (o.lasso_from.empty()) throw Error(VOLYM_E_INVALID, usage);
+                try {
+                    pos = 0;
+                    while (pos < first) {
+                        const size_t slash = std::min(v.find('/', pos), first);
+                        const std::string one = v.substr(pos, slash - pos);
+                        const size_t comma = one.find(',');
+                        if (comma == std::string::npos || comma == 0u || comma + 1u >= one.size()) throw Error(VOLYM_E_INVALID, usage);
+                        size_t used_x = 0, used_y = 0;
+                        const long x = std::stol(one.substr(0, comma), &used_x), y = std::stol(one.substr(comma + 1u), &used_y);
+                        if (used_x != comma || used_y != one.size() - comma - 1u || std::labs(x) > VOLYM_LASSO_VERTEX_MAX || std::labs(y) > VOLYM_LASSO_VERTEX_MAX)
+                            throw Error(VOLYM_E_INVALID, usage);
+                        o.lasso_pixels.push_back({static_cast<int32_t>(x), static_cast<int32_t>(y)});
+                        pos = slash + 1u;
+                    }
+                } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
+                if (o.lasso_pixels.size() < 3u || o.lasso_pixels.size() > VOLYM_LASSO_MAX_POINTS) throw Error(VOLYM_E_INVALID, usage);
+            }
             else if (a == "--labels-out") o.labels_out = next();
             else if (a == "--undo") o.undo = static_cast<uint32_t>(std::stoul(next()));
             else if (a == "--measure") {
@@ -528,7 +567,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--brush x,y,z[/x,y,z...]:to:r2] [--undo n] [--labels-out file]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--brush x,y,z[/x,y,z...]:to:r2] [--lasso x,y/x,y/x,y[/...]:from[,from...]:to] [--undo n] [--labels-out file]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

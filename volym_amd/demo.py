@@ -558,6 +558,26 @@ class GpuContext:
         self._ck(_lib.lib().volym_brush_labels(self.handle, C.byref(brush.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
+    def lasso_labels(self, lasso):
+        """One cut of the scissors on the device (include/volym_hip.h volym_lasso_labels; scene.lasso_volume is its definition): the
+        texels that project into the polygon of `lasso` (a scene.Lasso) -- with LASSO_OUTSIDE, those that do not -- become to[label]
+        where the table, the box and the density window say so.  Everything follows as after edit_labels, and the call is one step of
+        the history.  Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_lasso_labels(self.handle, C.byref(lasso.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
+    def read_lasso_mask(self):
+        """The polygon's bit plane of the latest lasso_labels (include/volym_hip.h volym_read_lasso_mask): (rect, words) -- rect =
+        (x0, y0, x1, y1), hi exclusive, words = np.uint32[(y1 - y0) * ceil((x1 - x0) / 32)], as scene.lasso_mask_words lays them out."""
+        rect = (C.c_uint32 * 4)()
+        self._ck(_lib.lib().volym_read_lasso_mask(self.handle, rect, None, 0))
+        x0, y0, x1, y1 = (int(v) for v in rect)
+        words = np.zeros(((x1 - x0 + 31) // 32) * (y1 - y0), np.uint32)
+        if words.size:
+            self._ck(_lib.lib().volym_read_lasso_mask(self.handle, rect, words.ctypes.data_as(C.POINTER(C.c_uint32)), words.size))
+        return (x0, y0, x1, y1), words
+
     def label_history(self, budget_bytes):
         """Keep a history of label edits in at most `budget_bytes` of device memory (20 bytes per changed 16-byte chunk); 0 drops
         and frees it (include/volym_hip.h volym_label_history; scene.LabelHistory is the definition of the bookkeeping)."""
@@ -675,6 +695,7 @@ class Simple(ComputeDemo):
         """BaseDemo::update_gpu_state (src/demos/pipeline.rs:208-212)"""
         ctx.update(state.camera_uniforms(), state.parameter_uniforms())
         self._records_for = None        # (highlight: the pick records of the old view are stale)
+        self._camera_uniforms = state.camera_uniforms()                 # (lasso: the view of the latest frame)
         self._eye = tuple(float(v) for v in state.camera.position)      # (clip_at: the plane faces the eye)
         self._dense_step = 0.25 * float(state.parameter_uniforms().raymarching_step_size)      # (project: the march's dense step)
 
@@ -1394,6 +1415,52 @@ class Simple(ComputeDemo):
             weights, unit = scene.distance_weights(spacing)
             table = self._brush_table(ctx, name, over)
             p["relabel"] = self._brush(ctx, scene.Brush([p["texel"]], self._band(1.0, radius), None, 0, window, table, weights, dims=self.dims))
+        return p
+
+    def _lasso(self, ctx, lasso):
+        result = ctx.lasso_labels(scene.check_lasso(lasso, self.dims))
+        if int(result["changed"]) and not lasso.flags & _lib.LASSO_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def lasso_view(self, ctx, depth=None):
+        """The integer view of the latest frame's camera (scene.lasso_view); depth: None, or (front, back) along the view axis in the
+        unit cube's units (back None: no far end)."""
+        view = scene.lasso_view(self._camera_uniforms, ctx.width, ctx.height, self.dims)
+        if depth is not None:
+            view = scene.lasso_view_depth(view, depth[0], float("inf") if depth[1] is None else depth[1])
+        return view
+
+    def lasso(self, ctx, pixels, name, over=(0,), window=(0, 255), depth=None, outside=False, uncut=False):
+        """Scissors: the texels that the latest frame's view projects into the polygon `pixels` [(x, y), ...] (3 to 1024 vertices,
+        closed implicitly, even-odd; they may lie off screen), through the whole volume or the range `depth` = (front, back) along the
+        view axis, of the segments `over` (names, ids or label values; None: every label) and with a density byte in `window`, join
+        segment `name` (as split_at takes it; None erases to label 0).  outside: the texels that do NOT project into the polygon
+        instead -- "keep only what is under the lasso".  One call, one undo step.  Returns the result's dict."""
+        self._ready_to_edit(ctx)
+        flags = (_lib.LASSO_OUTSIDE if outside else 0) | (_lib.LASSO_UNCUT if uncut else 0)
+        table = self._brush_table(ctx, name, over)
+        return self._lasso(ctx, scene.Lasso(pixels, self.lasso_view(ctx, depth), None, flags, window, table, dims=self.dims))
+
+    def lasso_erase(self, ctx, pixels, over=None, window=(0, 255), depth=None, outside=False, uncut=False):
+        """lasso with target label 0: what is under the polygon (outside: what is not) becomes unlabelled; over None: every label."""
+        return self.lasso(ctx, pixels, None, over, window, depth, outside, uncut)
+
+    def lasso_to_pick(self, ctx, pixels, name, thickness, over=None, alpha_min=0.5):
+        """Cut only a slab behind the surface the user sees: pick the polygon's first vertex, and lasso from the picked texel's depth
+        to `thickness` texels (of the volume's longest axis) behind it.  Returns the pick with a "relabel" entry (the result's dict;
+        None when the pixel shows no sample)."""
+        self._ready_to_edit(ctx)
+        pixels = [(int(x), int(y)) for x, y in pixels]
+        p = self.pick(ctx, pixels[0][0], pixels[0][1], alpha_min)
+        p["relabel"] = None
+        if p["status"] == "hit":
+            view = self.lasso_view(ctx)
+            t = [2 * v + 1 for v in p["texel"]]
+            front = float(sum(view.m[2][a] * t[a] for a in range(3)) + view.c[2]) * 2.0 ** -view.scale_log2      # the texel's own D, in world units
+            view = scene.lasso_view_depth(view, front, front + float(thickness) / max(self.dims))
+            p["relabel"] = self._lasso(ctx, scene.Lasso(pixels, view, None, 0, (0, 255), self._brush_table(ctx, name, over), dims=self.dims))
         return p
 
     def save_labels(self, ctx, path):

@@ -1640,6 +1640,257 @@ def brush_volume(prepared, dims, b, labels, uncut=None):
     return new, result
 
 
+class LassoView:
+    """volym_lasso_view (include/volym_hip.h): the integer view texel -> (X, Y, D).  m: three rows of three ints, c: three ints,
+    depth: (lo, hi), width x height: the frame, scale_log2: what lasso_view scaled by (lasso_view_depth reads it)."""
+
+    def __init__(self, m, c, depth, width, height, scale_log2=0):
+        self.m = tuple(tuple(int(v) for v in row) for row in m)
+        self.c = tuple(int(v) for v in c)
+        self.depth = tuple(int(v) for v in depth)
+        self.width, self.height, self.scale_log2 = int(width), int(height), int(scale_log2)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "lasso view", ("m", "c", "depth", "width", "height", "scale_log2"), kw)
+
+    @classmethod
+    def from_c(cls, v):
+        return cls([[int(v.m[r][a]) for a in range(3)] for r in range(3)], [int(x) for x in v.c], [int(x) for x in v.depth], v.width, v.height, v.scale_log2)
+
+    def to_c(self):
+        """The _lib.LassoView of this view.  Fields that do not fit their C types raise ValueError."""
+        v = _lib.LassoView()
+        if len(self.m) != 3 or any(len(row) != 3 for row in self.m) or len(self.c) != 3 or len(self.depth) != 2:
+            raise ValueError("lasso view: m is 3 x 3, c has three entries, depth two")
+        if not all(-2 ** 31 <= x < 2 ** 31 for row in self.m for x in row) or not all(-2 ** 63 <= x < 2 ** 63 for x in self.c + self.depth):
+            raise ValueError("lasso view: m is int32, c and depth are int64")
+        if not (0 <= self.width < 2 ** 32 and 0 <= self.height < 2 ** 32 and -2 ** 31 <= self.scale_log2 < 2 ** 31):
+            raise ValueError("lasso view: width and height are u32, scale_log2 is int32")
+        for r in range(3):
+            for a in range(3):
+                v.m[r][a] = self.m[r][a]
+            v.c[r] = self.c[r]
+        v.depth[0], v.depth[1] = self.depth
+        v.width, v.height, v.scale_log2 = self.width, self.height, self.scale_log2
+        return v
+
+
+class Lasso:
+    """volym_lasso (include/volym_hip.h): one cut of the scissors.  points: 3.._lib.LASSO_MAX_POINTS vertices (x, y) in pixels, closed
+    implicitly; view: a LassoView; box, window and to as Relabel takes them; flags: _lib.LASSO_UNCUT | LASSO_DRY_RUN | LASSO_OUTSIDE."""
+
+    def __init__(self, points, view, box=None, flags=0, window=(0, 255), to=None, dims=None):
+        self.box = _box_or_whole(box, dims, "a lasso request without a box needs the volume's dims")
+        self.box = (tuple(int(v) for v in self.box[0]), tuple(int(v) for v in self.box[1]))
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+        self.view = view
+        self.points = [tuple(int(v) for v in p) for p in points]
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "lasso", ("points", "view", "box", "flags", "window", "to"), kw)
+
+    def to_c(self):
+        """The _lib.Lasso of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Lasso()
+        v = list(self.box[0]) + list(self.box[1])
+        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
+            raise ValueError("lasso: the box is two triples of u32 texel indices")
+        c.box = (C.c_uint32 * 6)(*v)
+        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("lasso: flags and the window's ends must be u32")
+        c.flags = self.flags
+        c.min_byte, c.max_byte = self.window
+        if self.to.size != 256 or not ((self.to >= 0) & (self.to <= 255)).all():
+            raise ValueError("lasso: the table is 256 bytes")
+        c.to = (C.c_uint8 * 256)(*[int(g) for g in self.to])
+        c.view = self.view.to_c()
+        if len(self.points) > _lib.LASSO_MAX_POINTS:
+            raise ValueError("lasso: at most %d vertices, got %d" % (_lib.LASSO_MAX_POINTS, len(self.points)))
+        c.n_points = len(self.points)
+        for i, p in enumerate(self.points):
+            if len(p) != 2 or not all(-2 ** 31 <= x < 2 ** 31 for x in p):
+                raise ValueError("lasso: a vertex is (x, y) of int32, got %r" % (p,))
+            c.points[i].x, c.points[i].y = p
+        return c
+
+
+def check_lasso(lasso, dims):
+    """The validity rules of volym_lasso_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, 3.._lib.LASSO_MAX_POINTS vertices within _lib.LASSO_VERTEX_MAX of the origin, |m| < 2^31, |c| < 2^46,
+    1 <= depth[0] <= depth[1], a frame of 1.._lib.LASSO_MAX_FRAME pixels a side.  Returns the request; raises ValueError."""
+    l = lasso
+    dims = [int(v) for v in dims]
+    lo, hi = l.box
+    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
+        raise ValueError("lasso: the box is two triples of texel indices")
+    for a in range(3):
+        if not 0 <= lo[a] <= hi[a] <= dims[a]:
+            raise ValueError("lasso box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
+    if l.flags & ~(_lib.LASSO_UNCUT | _lib.LASSO_DRY_RUN | _lib.LASSO_OUTSIDE) or l.flags < 0:
+        raise ValueError("lasso: unknown flag bits in %#x" % l.flags)
+    if len(l.window) != 2 or not 0 <= l.window[0] <= l.window[1] <= 255:
+        raise ValueError("lasso: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (l.window,))
+    _check_lasso_polygon(l.points, l.view.width, l.view.height)
+    v = l.view
+    if len(v.m) != 3 or any(len(row) != 3 for row in v.m) or len(v.c) != 3 or len(v.depth) != 2:
+        raise ValueError("lasso view: m is 3 x 3, c has three entries, depth two")
+    if not all(abs(x) < 2 ** 31 for row in v.m for x in row):
+        raise ValueError("lasso view: |m| < 2^31")
+    if not all(abs(x) < 2 ** 46 for x in v.c):
+        raise ValueError("lasso view: |c| < 2^46")
+    if not 1 <= v.depth[0] <= v.depth[1] < 2 ** 63:
+        raise ValueError("lasso view: 1 <= depth[0] <= depth[1], got %r" % (v.depth,))
+    if np.asarray(l.to).size != 256:
+        raise ValueError("lasso: the table has 256 entries")
+    return l
+
+
+def _check_lasso_polygon(points, width, height):
+    if not 3 <= len(points) <= _lib.LASSO_MAX_POINTS:
+        raise ValueError("lasso: 3..%d vertices, got %d" % (_lib.LASSO_MAX_POINTS, len(points)))
+    if not (1 <= width <= _lib.LASSO_MAX_FRAME and 1 <= height <= _lib.LASSO_MAX_FRAME):
+        raise ValueError("lasso: a frame of 1..%d pixels a side, got %r x %r" % (_lib.LASSO_MAX_FRAME, width, height))
+    for p in points:
+        if len(p) != 2 or not all(abs(x) <= _lib.LASSO_VERTEX_MAX for x in p):
+            raise ValueError("lasso: vertex %r lies further than 2^20 from the origin" % (p,))
+
+
+def lasso_view(camera_uniforms, width, height, dims, near=0.0):
+    """volym_lasso_view_from_camera: the integer view of a frame -- the ONE quantisation of its camera; the device rule and its twin
+    both start from these integers, and nothing restates it here.  camera_uniforms: a CameraUniforms; near: the near distance along
+    the view axis (<= 0: none).  Returns a LassoView with depth = (max(1, near), INT64_MAX)."""
+    out = _lib.LassoView()
+    d = (C.c_uint32 * 3)(*[int(v) for v in dims])
+    rc = _lib.lib().volym_lasso_view_from_camera(C.byref(camera_uniforms), int(width), int(height), d, float(near), C.byref(out))
+    if rc != _lib.OK:
+        raise ValueError("lasso_view: no integer view of this camera, frame and volume (%d)" % rc)
+    return LassoView.from_c(out)
+
+
+def lasso_view_depth(view, front, back=float("inf")):
+    """volym_lasso_view_depth: a copy of `view` whose depth range is [front, back], two distances along the view axis in world units."""
+    c = view.to_c()
+    rc = _lib.lib().volym_lasso_view_depth(C.byref(c), float(front), float(back))
+    if rc != _lib.OK:
+        raise ValueError("lasso_view_depth: no depth range [%r, %r] (%d)" % (front, back, rc))
+    return LassoView.from_c(c)
+
+
+def lasso_rect(lasso):
+    """volym_lasso_rect: the mask's rect (x0, y0, x1, y1), hi exclusive -- the polygon's bounding box cut to the frame; all 0 when the
+    two do not meet."""
+    _check_lasso_polygon(lasso.points, lasso.view.width, lasso.view.height)
+    return _lasso_rect(lasso.points, lasso.view.width, lasso.view.height)
+
+
+def _lasso_rect(points, width, height):
+    xs, ys = [p[0] for p in points], [p[1] for p in points]
+    x0, y0, x1, y1 = max(min(xs), 0), max(min(ys), 0), min(max(xs), int(width)), min(max(ys), int(height))
+    return (0, 0, 0, 0) if x0 >= x1 or y0 >= y1 else (x0, y0, x1, y1)
+
+
+def lasso_mask(points, width, height):
+    """The polygon's mask over the whole frame, bool [height, width]: pixel (px, py) is in it iff an odd number of edges
+    (x0, y0) -> (x1, y1) satisfy (y0 <= py) != (y1 <= py) and (px - x0) (y1 - y0) < (x1 - x0) (py - y0) when y1 > y0, > when y1 < y0
+    (include/volym_hip.h), in NumPy's 64-bit integers: every factor is below 2^22."""
+    width, height = int(width), int(height)
+    _check_lasso_polygon(points, width, height)
+    mask = np.zeros((height, width), bool)
+    px = np.arange(width, dtype=np.int64)
+    n = len(points)
+    for i in range(n):
+        (x0, y0), (x1, y1) = points[i], points[(i + 1) % n]
+        lo, hi = max(min(y0, y1), 0), min(max(y0, y1), height)     # the rows with (y0 <= py) != (y1 <= py): min <= py < max
+        if lo >= hi:
+            continue
+        py = np.arange(lo, hi, dtype=np.int64)
+        lhs = (px - x0) * (y1 - y0)
+        rhs = (x1 - x0) * (py - y0)
+        mask[lo:hi] ^= (lhs[None, :] < rhs[:, None]) if y1 > y0 else (lhs[None, :] > rhs[:, None])
+    return mask
+
+
+def lasso_mask_words(points, width, height):
+    """(rect, words): the mask as volym_read_lasso_mask returns it -- the rect of lasso_rect and the bit plane over it, uint32
+    [rect_h * ceil(rect_w / 32)]: pixel (px, py) is bit (px - x0) & 31 of word (py - y0) * stride + (px - x0) // 32."""
+    rect = _lasso_rect(points, width, height)
+    x0, y0, x1, y1 = rect
+    if x0 == x1:
+        return rect, np.zeros(0, np.uint32)
+    sub = lasso_mask(points, width, height)[y0:y1, x0:x1]
+    stride = (x1 - x0 + 31) // 32
+    bits = np.zeros((y1 - y0, stride * 32), np.uint8)
+    bits[:, :x1 - x0] = sub
+    return rect, np.packbits(bits, axis=1, bitorder="little").view("<u4").ravel().copy()
+
+
+def _lasso_below(X, r, D):
+    """X < r * D for int64 arrays X, D below 2^62 in size and an int 0 <= r <= 2^14, exact although r * D may not fit 64 bits (the device's
+    lasso_below): D = dh * 2^32 + dl, r * D = hi * 2^32 + lo, compared high word first."""
+    r = int(r)
+    low = r * (D & 0xffffffff)
+    hi = r * (D >> 32) + (low >> 32)
+    xh = X >> 32
+    return (xh < hi) | ((xh == hi) & ((X & 0xffffffff) < (low & 0xffffffff)))
+
+
+def lasso_texels(view, dims):
+    """Which pixel each texel lands on (include/volym_hip.h): (lands, px, py), arrays [z, y, x] of the volume; px and py are 0 where
+    the texel does not land.  X, Y and D in NumPy's 64-bit integers, which hold them (below 2^51)."""
+    nx, ny, nz = (int(v) for v in dims)
+    hx = 2 * np.arange(nx, dtype=np.int64)[None, None, :] + 1
+    hy = 2 * np.arange(ny, dtype=np.int64)[None, :, None] + 1
+    hz = 2 * np.arange(nz, dtype=np.int64)[:, None, None] + 1
+    X, Y, D = (view.m[r][0] * hx + view.m[r][1] * hy + view.m[r][2] * hz + view.c[r] for r in range(3))
+    lands = (D >= view.depth[0]) & (D <= view.depth[1]) & (X >= 0) & (Y >= 0) & _lasso_below(X, view.width, D) & _lasso_below(Y, view.height, D)
+    safe = np.where(lands, D, 1)
+    return lands, np.where(lands, X // safe, 0), np.where(lands, Y // safe, 0)
+
+
+def lasso_volume(prepared, dims, lasso, labels, uncut=None):
+    """The definition of the lasso (include/volym_hip.h volym_lasso_labels), integers only and without any cull; equal to the device
+    in every byte.  `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None:
+    prepared), `labels`: the labels before the cut.  A texel is inside iff it lands on a pixel of the polygon's mask and selected iff
+    inside != OUTSIDE; a selected texel with label l becomes to[l] iff it lies in the box, to[l] != l and its density byte lies in
+    the window; every texel is decided once, from the bytes before the edit.  Returns (new_labels, result) as relabel_volume does."""
+    l = check_lasso(lasso, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = l.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("lasso_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (l.flags & _lib.LASSO_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("lasso_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    if any(p >= q for p, q in zip(lo, hi)):
+        return new, result
+    lands, px, py = lasso_texels(l.view, dims)
+    inside = lands & lasso_mask(l.points, l.view.width, l.view.height)[py, px]
+    selected = inside != bool(l.flags & _lib.LASSO_OUTSIDE)
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    to = np.asarray(l.to, np.int64).astype(np.uint8)
+    d = src.reshape(nz, ny, nx)[sub]
+    hit = (to[old] != old) & (d >= l.window[0]) & (d <= l.window[1]) & selected[sub]
+    n = int(hit.sum())
+    if n == 0:
+        return new, result
+    result["changed"] = n
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not l.flags & _lib.LASSO_DRY_RUN:
+        new[sub] = np.where(hit, to[old], old)
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
