@@ -10,6 +10,10 @@ follow the scene's own width and far corner.
 A Case is a stroke and what the host test asserts about it: `trivial` (it may change fewer than 50 texels), `ragged` (in the ragged
 scene its changed texels share linear chunks across rows), `count` (the texels within the stroke, in scene A's dimensions -- what the
 stroke changes there when its table moves every label).
+
+The small scene is 5 x 3 x 9 with three labels in blocks of three slices: a slice has 15 texels, fewer than a chunk, so every linear
+chunk spans up to four rows and two slices, and the last chunk is partial.  Its strokes (small_cases) are run by the device tests
+with the history off and on; rows_shared says what the host test asserts of them.
 """
 import numpy as np
 
@@ -19,6 +23,7 @@ from tests import relabel_scenes as RS
 DIMS = MS.DIMS
 RAGGED_DIMS = RS.RAGGED_DIMS
 SCENES = {"a": RS.scene_a, "b": RS.scene_b, "ragged": RS.scene_ragged}
+SMALL_DIMS = (5, 3, 9)
 
 
 class Case:
@@ -81,6 +86,34 @@ def cases(dims=DIMS):
         Case("empty box", B([(18, 10, 9)], 30, box=MS.BOXES["empty"]), trivial=True),
         Case("a box the hull misses", B([(3, 3, 3)], 4, box=((20, 10, 10), (30, 20, 18))), trivial=True),
     ]
+
+
+def scene_small():
+    host = RS.Host(SMALL_DIMS)
+    nx, ny, nz = SMALL_DIMS
+    host.labels = np.repeat(np.arange(nz, dtype=np.uint8) // 3, nx * ny)
+    return host
+
+
+def small_cases():
+    """the strokes over the small scene"""
+    from volym_amd import scene
+    nx, ny, nz = SMALL_DIMS
+    mid = (nx // 2, ny // 2, nz // 2)
+    along_z = [(mid[0], mid[1], 0), (mid[0], mid[1], nz - 1)]
+
+    def B(points, r2, **kw):
+        return scene.Brush(points, r2, to=every(7), dims=SMALL_DIMS, **kw)
+
+    return [Case("ball of r2 2 at the centre", B([mid], 2)), Case("capsule along z, r2 1", B(along_z, 1)),
+            Case("capsule along z, r2 1, a window 64..192", B(along_z, 1, window=(64, 192)))]
+
+
+def rows_shared(dims, old, new):
+    """how many changed texels have y > 0 and lie in a 16-byte chunk of the linear layout whose first texel has y = 0"""
+    nx, ny = dims[0], dims[1]
+    at = np.flatnonzero(np.asarray(old).ravel() != np.asarray(new).ravel())
+    return int((((at // nx) % ny > 0) & ((((at >> 4) << 4) // nx) % ny == 0)).sum())
 
 
 def expect(host, case, brush=None):

@@ -10,10 +10,14 @@ The views are integer views of four cameras (scene.lasso_view, the library's one
 inside the volume, with texels behind it and D near 0; fovy 20, which leaves most of the volume off screen; a camera rolled by 30
 degrees.  A Case is a request and what the host test asserts about it: `count` is what the twin changes in scene A (every case has
 one; 0 only where `trivial` says the case is there for its no-op).
+
+The small scene is that of tests/brush_scenes.py, 5 x 3 x 9: every linear chunk spans several rows and two slices.  Its two requests
+(small_cases) are a triangle and its OUTSIDE twin under the default camera at a 64 x 64 frame, which looks along z.
 """
 import numpy as np
 
 from tests import free_camera_cases as FC
+from tests import brush_scenes as BS
 from tests import measure_scenes as MS
 from tests import relabel_scenes as RS
 
@@ -137,6 +141,23 @@ def cases(O, dims=DIMS):
         Case("empty box", L("star", box=MS.BOXES["empty"]), n(0), trivial=True),
     ]
     return out
+
+
+SMALL_DIMS = BS.SMALL_DIMS
+scene_small = BS.scene_small
+rows_shared = BS.rows_shared
+SMALL_FRAME = 64
+SMALL_TRIANGLE = [(12, 8), (50, 30), (20, 56)]
+
+
+def small_cases():
+    """the requests over the small scene: the view is the library's quantisation of the default camera, host arithmetic"""
+    from volym_amd import _lib, scene
+    state = scene.State.with_parameters(1.0, scene.StateParameters())
+    state.update()
+    view = scene.lasso_view(state.camera_uniforms(), SMALL_FRAME, SMALL_FRAME, SMALL_DIMS)
+    inside = scene.Lasso(SMALL_TRIANGLE, view, to=every(7), dims=SMALL_DIMS)
+    return [Case("triangle", inside, None), Case("triangle, outside", inside.replace(flags=_lib.LASSO_OUTSIDE), None)]
 
 
 DEPTH_MID = 1.0                     # the distance of the volume's middle along the view axis of POSE, in world units (the host test checks it)

@@ -314,3 +314,20 @@ def test_the_cases_do_what_the_device_tests_need(which):
         assert under.sum() >= 5
         new, _ = BS.expect(host, case)
         assert np.array_equal(new.reshape(both.shape)[under], 3 - lab[under])
+
+
+def test_the_small_scene_shares_rows_within_chunks():
+    """what tests/test_gpu_brush.py's small-shape test relies on: a slice is smaller than a chunk, every stroke changes a texel but
+    not all, and a changed texel lies in a row above the first of a chunk that starts in row 0"""
+    host = BS.scene_small()
+    nx, ny, nz = host.dims
+    assert host.dims == (5, 3, 9) and nx * ny < 16 and (nx * ny * nz) % 16 != 0
+    assert host.vol.min() >= 1 and sorted(set(host.labels.tolist())) == [0, 1, 2]
+    assert [c.name for c in BS.small_cases()] == ["ball of r2 2 at the centre", "capsule along z, r2 1", "capsule along z, r2 1, a window 64..192"]
+    changed = []
+    for case in BS.small_cases():
+        new, res = BS.expect(host, case)
+        assert 1 <= int(res["changed"]) < nx * ny * nz, case.name
+        assert BS.rows_shared(host.dims, host.labels, new) >= 1, case.name
+        changed.append(int(res["changed"]))
+    assert changed[2] < changed[1]                                      # the window leaves texels of the capsule out

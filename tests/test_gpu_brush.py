@@ -260,6 +260,27 @@ def test_a_budget_one_record_short_of_the_strokes_step_gives_the_history_up(orac
         assert ctx.label_history_info()["lost"] == 0 and ctx.label_history_info()["next_undo_records"] == records
 
 
+@pytest.mark.parametrize("layout", [0, 1])
+def test_a_volume_whose_chunks_span_rows_and_slices(volym_lib, layout):
+    """5 x 3 x 9: a slice is smaller than a chunk, so a linear chunk spans up to four rows and two slices and the last one is partial.
+    Every stroke with the history off and on, then one undo; result and all 135 labels against the twin after each call"""
+    host = BS.scene_small()
+    original = host.labels.copy()
+    with _ctx(layout) as ctx:
+        host.upload(ctx)
+        for budget in (0, LS.BIG):
+            ctx.label_history(budget)
+            for case in BS.small_cases():
+                _hand_labels(ctx, host, original)
+                got = _brush(ctx, host, case)
+                assert 0 < int(got["changed"]) < original.size, case.name
+                assert np.array_equal(ctx.read_labels().ravel(), host.labels), (case.name, budget)
+                if budget:
+                    undone = ctx.undo_labels()
+                    assert undone.tobytes() == LS.swapped(got).tobytes(), case.name
+                    assert np.array_equal(ctx.read_labels().ravel(), original), case.name
+
+
 # ---- 4. frames in flight --------------------------------------------------------------------------------------------------------
 def test_a_brush_between_frames_with_two_frames_in_flight(oracle, volym_lib):
     from volym_amd import _lib

@@ -263,6 +263,28 @@ def test_a_budget_one_record_short_of_the_lassos_step_gives_the_history_up(oracl
         assert ctx.label_history_info()["lost"] == 0 and ctx.label_history_info()["next_undo_records"] == records
 
 
+@pytest.mark.parametrize("layout", [0, 1])
+def test_a_volume_whose_chunks_span_rows_and_slices(volym_lib, layout):
+    """5 x 3 x 9: a slice is smaller than a chunk, so a linear chunk spans up to four rows and two slices and the last one is partial.
+    The triangle and its OUTSIDE twin with the history off and on, then one undo; result, mask and all 135 labels against the twin
+    after each call"""
+    host = LS.scene_small()
+    original = host.labels.copy()
+    with _ctx(layout) as ctx:
+        host.upload(ctx)
+        for budget in (0, LH.BIG):
+            ctx.label_history(budget)
+            for case in LS.small_cases():
+                _hand_labels(ctx, host, original)
+                got = _lasso(ctx, host, case)
+                assert 0 < int(got["changed"]) < original.size, case.name
+                assert np.array_equal(ctx.read_labels().ravel(), host.labels), (case.name, budget)
+                if budget:
+                    undone = ctx.undo_labels()
+                    assert undone.tobytes() == LH.swapped(got).tobytes(), case.name
+                    assert np.array_equal(ctx.read_labels().ravel(), original), case.name
+
+
 # ---- 4. refusals ----------------------------------------------------------------------------------------------------------------
 def test_refusals(oracle, volym_lib):
     from volym_amd import _lib, scene

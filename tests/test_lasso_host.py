@@ -397,3 +397,20 @@ def test_a_picked_texel_lands_on_the_pixel_that_picked_it(oracle, volym_lib):
         assert abs(ex.mean()) < 0.25 and abs(ey.mean()) < 0.25              # no half-pixel bias either way
         seen += int(hit.sum())
     assert seen > 250
+
+
+def test_the_small_scene_shares_rows_within_chunks(volym_lib):
+    """what tests/test_gpu_lasso.py's small-shape test relies on: the triangle and its OUTSIDE twin each change a texel but not all,
+    between them every texel, and a changed texel lies in a row above the first of a chunk that starts in row 0"""
+    host = LS.scene_small()
+    nx, ny, nz = host.dims
+    assert host.dims == (5, 3, 9) and nx * ny < 16
+    inside, outside = LS.small_cases()
+    assert outside.lasso.flags == 32 and inside.lasso.flags == 0 and inside.lasso.view.width == inside.lasso.view.height == 64
+    total = 0
+    for case in (inside, outside):
+        new, res = LS.expect(host, case)
+        assert 1 <= int(res["changed"]) < nx * ny * nz, case.name
+        assert LS.rows_shared(host.dims, host.labels, new) >= 1, case.name
+        total += int(res["changed"])
+    assert total == nx * ny * nz

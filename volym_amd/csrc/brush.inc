@@ -1,6 +1,7 @@
 // The brush (volym_brush_labels, volym_brush_check, volym_brush_box): included at the end of scene_bytes.hip AFTER relabel.inc, which
-// this file does not include itself: it relies on that file's edit_labels (the edit's transition, with the kernel as a parameter),
-// LabelEdit and editable_state, and launches the kernels of brush_kernels.h.  A blocking set-up call like the edit it is a form of.
+// this file does not include itself and whose edit it is a form of: the transition, the launch and the segments' stay on the device
+// are that file's.  Here: the request's checks, the stroke's box and segments, and the rule the kernels of brush_kernels.h read.  A
+// blocking set-up call like that edit.
 
 #include <cmath>
 
@@ -113,12 +114,9 @@ int volym_brush_labels(volym_ctx* c, const volym_brush* b, struct volym_relabel_
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<BrushSegment> segs;
     brush_segments(b, dims, segs);
-    const hipStream_t stream = c->slot0().stream;
-    BrushSegment* d_segs = nullptr;
-    hipError_t e = hipMalloc(&d_segs, segs.size() * sizeof(BrushSegment));
-    if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(brush segments): ") + hipGetErrorString(e));
-    e = hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(BrushSegment), hipMemcpyHostToDevice, stream);      // in stream order in front of the kernel
-    if (e != hipSuccess) { (void)hipFree(d_segs); return fail(c, VOLYM_E_HIP, std::string("volym_brush_labels: ") + hipGetErrorString(e)); }
+    CallArray<BrushSegment> d_segs;
+    int rc = d_segs.upload(c, c->slot0().stream, segs, "brush segments", "volym_brush_labels");
+    if (rc != VOLYM_OK) return rc;
 
     const bool dry = (b->flags & VOLYM_BRUSH_DRY_RUN) != 0u;
     BrushRule rule = {};
@@ -128,18 +126,11 @@ int volym_brush_labels(volym_ctx* c, const volym_brush* b, struct volym_relabel_
     rule.r2 = b->r2;
     for (int a = 0; a < 3; ++a) rule.weight[a] = b->weight[a];
     const LabelEdit edit = {box, b->to, dry, "volym_brush_labels"};
-    const int rc = edit_labels(c, edit, res, [&](hipStream_t s0, dim3 grid, const RelabelOut& o, const LabelTable& to, const CropSlab& s, uint32_t items,
-                                                 const LabelJournal* journal) {
-        const uint4* vol = reinterpret_cast<const uint4*>((b->flags & VOLYM_BRUSH_UNCUT) && c->d_vol0 ? c->d_vol0 : c->d_vol);   // (after ensure_uncropped_copies)
-        if (journal)
-            hipLaunchKernelGGL(volym_brush_journal_kernel, grid, dim3(256), 0, s0, reinterpret_cast<uint4*>(c->d_labels), vol, d_segs, o, to, s, rule, *journal, c->nx,
-                               c->ny, c->nz, c->bricked ? 1u : 0u, items);
-        else
-            hipLaunchKernelGGL(volym_brush_kernel, grid, dim3(256), 0, s0, reinterpret_cast<uint4*>(c->d_labels), vol, d_segs, o, to, s, rule, c->nx, c->ny, c->nz,
-                               c->bricked ? 1u : 0u, items);
+    rc = edit_labels(c, edit, res, [&](hipStream_t stream, dim3 grid, const RelabelOut& o, const LabelTable& to, const CropSlab& s, uint32_t items,
+                                       const LabelJournal* journal) {
+        launch_edit(c, volym_brush_kernel, volym_brush_journal_kernel, stream, grid, o, to, s, rule, items, journal,
+                    edit_density(c, (b->flags & VOLYM_BRUSH_UNCUT) != 0u), d_segs.ptr);
     });
-    (void)hipStreamSynchronize(stream);                                     // (a refusal before the kernel: the copy may still run)
-    (void)hipFree(d_segs);
     if (rc == VOLYM_OK && out) *out = res;
     return rc;
 }

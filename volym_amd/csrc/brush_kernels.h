@@ -1,8 +1,7 @@
 // The kernel of the brush (volym_brush_labels): the label edit whose texels are decided by geometry, not by a snapshot.  Included by
 // scene_bytes.hip alone, AFTER relabel_kernels.h, which this header does not include itself (scene_bytes.hip stays the one place
-// that does): it relies on that header's RelabelShared, RelabelTally, RelabelOut and LabelJournal, on tally_init, tally_texel and
-// tally_reduce, on relabel_owns_chunk and on wave_min / wave_max, and through it on scene_kernels.h (CropSlab, crop_chunk,
-// label_chunk_origin, LabelTable).
+// that does).  Everything but the selection rule is that header's: the walk (wave_chunk_step), the tail (selected_chunk_tail), the
+// prologue, the tally and the journal.  Here: the segment, the rule of one texel against it, and the mask of a chunk.
 #pragma once
 
 #include "scene_kernels.h"
@@ -49,24 +48,16 @@ __device__ __forceinline__ bool brush_within(const BrushSegment& g, const BrushR
 }
 
 // One pass over the items of slab s (make_crop_slab over the request's box cut to the stroke's hull, s.box_lo/hi that box, no plane),
-// in either layout, a wave at a time: the loop's trip count is the wave's, because the segment cull below talks across its lanes.
-// Per chunk, geometry first -- it needs no memory:
-//   1. crop_chunk and, linear, the one-owner test of the relabel kernel;
-//   2. the 16-bit mask of the chunk's texels that lie within some segment.  The box of the wave's 64 chunks (wave_min / wave_max,
-//      then scalar) is held against each segment's box first: a segment that misses it is skipped by a uniform branch.  Then the
-//      lane's chunk box against the segment's, then each texel against it, and only then the 64-bit test;
-//   3. only if that mask is non-zero, the 16 labels and to[l] != l;
-//   4. only then the density, skipped by a uniform test when the window is 0..255;
-//   5. tally_texel, the journal append and the plain 16-byte store exactly as relabel_pass does them.
-// Every texel is decided once, by its chunk's owner, from the bytes before the edit: the mask is the union over the segments.
+// in either layout: the walk and the tail of relabel_kernels.h (wave_chunk_step, selected_chunk_tail) around the brush's selection
+// rule, the 16-bit mask of the chunk's texels that lie within some segment -- their union, so every texel is decided once.  Three
+// levels of cull: the wave's box is held against each segment's box first, and a segment that misses it is skipped by a uniform
+// branch; then the lane's chunk box against the segment's; then each texel against it, and only then the 64-bit test.
 template <bool JOURNAL>
 __device__ __forceinline__ void brush_pass(RelabelShared& sh, uint4* __restrict__ labels, const uint4* __restrict__ vol, const BrushSegment* __restrict__ segs,
                                            const RelabelOut& out, const LabelTable& to, const CropSlab& s, const BrushRule& rule, const LabelJournal& journal,
                                            uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
 {
-    sh.to[threadIdx.x] = to.v[threadIdx.x];
-    tally_init(sh);
-    __syncthreads();
+    edit_prologue(sh, to);
     const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
     const uint32_t lane = threadIdx.x & 63u;
@@ -75,92 +66,26 @@ __device__ __forceinline__ void brush_pass(RelabelShared& sh, uint4* __restrict_
     RelabelTally t;
 
     for (uint32_t base = blockIdx.x * 256u + wave * 64u; base < n_items; base += gridDim.x * 256u) {
-        const uint32_t i = base + lane;
-        uint64_t k = 0;
-        uint32_t keep = 0, moved;
-        bool live = i < n_items && crop_chunk<false>(s, i, nx, ny, n, bricked, bx, by, k, keep, moved);
-        if (live && !bricked && !relabel_owns_chunk(s, i, nx, ny, k)) live = false;
-        if (!keep) live = false;
-        // the chunk's texel box (hi inclusive): a brick's 4 x 4 patch of one z; linear, 16 texels that may wrap rows and slices, whose
-        // box is then taken a little wide (whole rows, whole slices): it only culls
-        uint32_t x0 = 0, y0 = 0, z0 = 0, cl[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, ch[3] = {0u, 0u, 0u};
-        if (live) {
-            label_chunk_origin(bricked != 0u, static_cast<uint32_t>(k), nx, ny, x0, y0, z0);   // (k < 2^28: a layout has fewer than 2^32 bytes)
-            cl[0] = x0; cl[1] = y0; cl[2] = ch[2] = z0;
-            if (bricked) { ch[0] = x0 + 3u; ch[1] = y0 + 3u; }
-            else if (x0 + 15u < nx) { ch[0] = x0 + 15u; ch[1] = y0; }
-            else {
-                const uint32_t rows = (x0 + 15u) / nx;
-                cl[0] = 0u; ch[0] = nx - 1u; ch[1] = y0 + rows;
-                if (ch[1] >= ny) { cl[1] = 0u; ch[1] = ny - 1u; ch[2] = z0 + (y0 + rows) / ny; }
-            }
-        }
-        uint32_t wl[3], wh[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            wl[a] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_min(cl[a]))));
-            wh[a] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_max(ch[a]))));
-        }
-        if (wl[0] > wh[0]) continue;                                     // (uniform: no lane of the wave has a chunk)
+        WaveChunk c;
+        if (!wave_chunk_step(c, s, base, lane, n_items, nx, ny, n, bricked, bx, by)) continue;
         uint32_t mask = 0;
         for (uint32_t g = 0; g < rule.n_segments; ++g) {
             const BrushSegment seg = segs[g];
-            if (seg.lo[0] > wh[0] || seg.hi[0] < wl[0] || seg.lo[1] > wh[1] || seg.hi[1] < wl[1] || seg.lo[2] > wh[2] || seg.hi[2] < wl[2]) continue;   // (uniform)
-            if (!live || seg.lo[0] > ch[0] || seg.hi[0] < cl[0] || seg.lo[1] > ch[1] || seg.hi[1] < cl[1] || seg.lo[2] > ch[2] || seg.hi[2] < cl[2]) continue;
-            uint32_t x = x0, y = y0, z = z0;
+            if (seg.lo[0] > c.wh[0] || seg.hi[0] < c.wl[0] || seg.lo[1] > c.wh[1] || seg.hi[1] < c.wl[1] || seg.lo[2] > c.wh[2] || seg.hi[2] < c.wl[2]) continue;   // (uniform)
+            if (!c.live || seg.lo[0] > c.ch[0] || seg.hi[0] < c.cl[0] || seg.lo[1] > c.ch[1] || seg.hi[1] < c.cl[1] || seg.lo[2] > c.ch[2] || seg.hi[2] < c.cl[2]) continue;
+            // (stepped by hand, not by a ChunkCursor: with one here the compiler spills the segment's scalar registers inside the unrolled loop)
+            uint32_t x = c.x0, y = c.y0, z = c.z0;
 #pragma unroll
             for (uint32_t j = 0; j < 16u; ++j) {
-                if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); }
-                if ((keep & ~mask & (1u << j)) && x >= seg.lo[0] && x <= seg.hi[0] && y >= seg.lo[1] && y <= seg.hi[1] && z >= seg.lo[2] && z <= seg.hi[2] &&
+                if (bricked) { x = c.x0 + (j & 3u); y = c.y0 + (j >> 2); }
+                if ((c.keep & ~mask & (1u << j)) && x >= seg.lo[0] && x <= seg.hi[0] && y >= seg.lo[1] && y <= seg.hi[1] && z >= seg.lo[2] && z <= seg.hi[2] &&
                     brush_within(seg, rule, x, y, z))
                     mask |= 1u << j;
                 if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
             }
         }
         if (!mask) continue;                                             // before any load
-        const uint4 lv = labels[k];
-        uint32_t lb[4] = {lv.x, lv.y, lv.z, lv.w};
-        uint32_t cand = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            const uint32_t l = (lb[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-            if (sh.to[l] != l) cand |= 1u << j;
-        }
-        cand &= mask;
-        if (!cand) continue;                                             // no density, no store
-        if (windowed) {
-            const uint4 dv = vol[k];
-            const uint32_t d[4] = {dv.x, dv.y, dv.z, dv.w};
-#pragma unroll
-            for (uint32_t j = 0; j < 16u; ++j) {
-                const uint32_t b = (d[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-                if (b < rule.min_byte || b > rule.max_byte) cand &= ~(1u << j);
-            }
-            if (!cand) continue;
-        }
-        uint32_t x = x0, y = y0, z = z0;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); }
-            if (cand & (1u << j)) {
-                const uint32_t shift = 8u * (j & 3u), l = (lb[j >> 2] >> shift) & 0xffu, becomes = sh.to[l];
-                lb[j >> 2] = (lb[j >> 2] & ~(0xffu << shift)) | (becomes << shift);
-                tally_texel(sh, t, l, becomes, x, y, z);
-            }
-            if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
-        }
-        if (rule.store) {
-            if (JOURNAL) {
-                const unsigned long long here = __ballot(1);             // the lanes that store a chunk in this step
-                const uint32_t leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
-                uint32_t first = 0u;
-                if (lane == leader) first = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
-                first = __shfl(first, static_cast<int>(leader), 64);
-                const uint32_t at = first + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
-                if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = lv; }
-            }
-            labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
-        }
+        selected_chunk_tail<JOURNAL>(sh, t, labels, vol, c.k, mask, windowed, rule.min_byte, rule.max_byte, rule.store, journal, nx, ny, bricked);
     }
     tally_reduce(sh, t, out);
 }

@@ -1,7 +1,8 @@
 // The lasso (volym_lasso_labels, volym_lasso_check, volym_lasso_rect, volym_read_lasso_mask): included at the end of scene_bytes.hip
-// AFTER relabel.inc and brush.inc, neither of which this file includes itself: it relies on relabel.inc's edit_labels (the edit's
-// transition, with the kernel as a parameter), LabelEdit and editable_state, and launches the kernels of lasso_kernels.h.  A blocking
-// set-up call like the edit it is a form of.  The view's builder (volym_lasso_view_from_camera) is host arithmetic in scene.cpp.
+// AFTER relabel.inc and brush.inc, neither of which this file includes itself.  It is a form of relabel.inc's edit: the transition,
+// the launch and the edges' stay on the device are that file's.  Here: the request's checks, the mask's rect and plane, and the rule
+// the kernels of lasso_kernels.h read.  A blocking set-up call like that edit.  The view's builder (volym_lasso_view_from_camera) is
+// host arithmetic in scene.cpp.
 
 static_assert(sizeof(volym_lasso_view) == 88 && offsetof(volym_lasso_view, width) == 36 && offsetof(volym_lasso_view, height) == 40 &&
               offsetof(volym_lasso_view, scale_log2) == 44 && offsetof(volym_lasso_view, c) == 48 && offsetof(volym_lasso_view, depth) == 72, "volym_lasso_view has no padding");
@@ -98,11 +99,11 @@ int volym_lasso_labels(volym_ctx* c, const volym_lasso* l, struct volym_relabel_
 
     HIPCHK(c, hipSetDevice(c->device));
     const hipStream_t stream = c->slot0().stream;
-    LassoEdge* d_edges = nullptr;
-    std::vector<LassoEdge> edges;
+    std::vector<LassoEdge> edges;                                           // (outlives its copy: declared in front of d_edges)
+    CallArray<LassoEdge> d_edges;
     if (words != 0u) {
         // the polygon's bit plane, in stream order in front of the edit kernel
-        const int rc = c->lasso_plane.reserve(c, stream, words, "lasso plane");
+        int rc = c->lasso_plane.reserve(c, stream, words, "lasso plane");
         if (rc != VOLYM_OK) { c->lasso_have = false; return rc; }
         edges.resize(l->n_points);
         for (uint32_t i = 0; i < l->n_points; ++i) {
@@ -110,21 +111,13 @@ int volym_lasso_labels(volym_ctx* c, const volym_lasso* l, struct volym_relabel_
             const volym_lasso_point& q = l->points[i + 1u == l->n_points ? 0u : i + 1u];
             edges[i] = LassoEdge{p.x, p.y, q.x, q.y};
         }
-        hipError_t e = hipMalloc(&d_edges, edges.size() * sizeof(LassoEdge));
-        if (e != hipSuccess) { c->lasso_have = false; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(lasso edges): ") + hipGetErrorString(e)); }
-        e = hipMemcpyAsync(d_edges, edges.data(), edges.size() * sizeof(LassoEdge), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) {
-            const uint64_t waves = static_cast<uint64_t>((rect_w + 63u) / 64u) * rect_h;
-            hipLaunchKernelGGL(volym_lasso_raster_kernel, dim3(static_cast<uint32_t>((waves + 3u) / 4u)), dim3(256), 0, stream, c->lasso_plane.ptr, d_edges,
-                               l->n_points, rect[0], rect[1], rect[2], rect[3], stride);
-            e = hipGetLastError();
-        }
-        if (e != hipSuccess) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipFree(d_edges);
-            c->lasso_have = false;
-            return fail(c, VOLYM_E_HIP, std::string("volym_lasso_labels: ") + hipGetErrorString(e));
-        }
+        rc = d_edges.upload(c, stream, edges, "lasso edges", "volym_lasso_labels");
+        if (rc != VOLYM_OK) { c->lasso_have = false; return rc; }
+        const uint64_t waves = static_cast<uint64_t>((rect_w + 63u) / 64u) * rect_h;
+        hipLaunchKernelGGL(volym_lasso_raster_kernel, dim3(static_cast<uint32_t>((waves + 3u) / 4u)), dim3(256), 0, stream, c->lasso_plane.ptr, d_edges.ptr,
+                           l->n_points, rect[0], rect[1], rect[2], rect[3], stride);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { c->lasso_have = false; return fail(c, VOLYM_E_HIP, std::string("volym_lasso_labels: ") + hipGetErrorString(e)); }
     }
     std::memcpy(c->lasso_rect, rect, sizeof rect);
     c->lasso_plane.count = words;
@@ -145,17 +138,10 @@ int volym_lasso_labels(volym_ctx* c, const volym_lasso* l, struct volym_relabel_
         const LabelEdit edit = {l->box, l->to, dry, "volym_lasso_labels"};
         rc = edit_labels(c, edit, res, [&](hipStream_t s0, dim3 grid, const RelabelOut& o, const LabelTable& to, const CropSlab& s, uint32_t items,
                                            const LabelJournal* journal) {
-            const uint4* vol = reinterpret_cast<const uint4*>((l->flags & VOLYM_LASSO_UNCUT) && c->d_vol0 ? c->d_vol0 : c->d_vol);   // (after ensure_uncropped_copies)
-            if (journal)
-                hipLaunchKernelGGL(volym_lasso_journal_kernel, grid, dim3(256), 0, s0, reinterpret_cast<uint4*>(c->d_labels), vol, plane, o, to, s, rule, *journal, c->nx,
-                                   c->ny, c->nz, c->bricked ? 1u : 0u, items);
-            else
-                hipLaunchKernelGGL(volym_lasso_kernel, grid, dim3(256), 0, s0, reinterpret_cast<uint4*>(c->d_labels), vol, plane, o, to, s, rule, c->nx, c->ny, c->nz,
-                                   c->bricked ? 1u : 0u, items);
+            launch_edit(c, volym_lasso_kernel, volym_lasso_journal_kernel, s0, grid, o, to, s, rule, items, journal,
+                        edit_density(c, (l->flags & VOLYM_LASSO_UNCUT) != 0u), plane);
         });
     }
-    (void)hipStreamSynchronize(stream);                                     // (the edges' copy and the raster kernel may still run)
-    (void)hipFree(d_edges);
     if (rc == VOLYM_OK && out) *out = res;
     return rc;
 }

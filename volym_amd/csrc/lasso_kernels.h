@@ -1,8 +1,8 @@
 // The kernels of the lasso (volym_lasso_labels): the label edit whose texels are decided by where they project.  Included by
 // scene_bytes.hip alone, AFTER relabel_kernels.h and brush_kernels.h, which this header does not include itself (scene_bytes.hip stays
-// the one place that does): it relies on relabel_kernels.h's RelabelShared, RelabelTally, RelabelOut and LabelJournal, on tally_init,
-// tally_texel and tally_reduce, on relabel_owns_chunk and on wave_min / wave_max, and through it on scene_kernels.h (CropSlab,
-// crop_chunk, label_chunk_origin, LabelTable).
+// the one place that does).  Everything of the edit kernel but the selection rule is relabel_kernels.h's: the walk (wave_chunk_step),
+// the tail (selected_chunk_tail), the prologue, the tally and the journal.  Here: the polygon's bit plane, the integer view, the
+// half-space cull and the mask of a chunk.
 #pragma once
 
 #include "scene_kernels.h"
@@ -119,25 +119,17 @@ __device__ __forceinline__ bool lasso_inside(const LassoRule& v, const uint32_t*
     return ((plane[uy * v.stride + (ux >> 5)] >> (ux & 31u)) & 1u) != 0u;
 }
 
-// One pass over the items of slab s (make_crop_slab over the request's box, s.box_lo/hi that box, no plane), in either layout, a wave
-// at a time: the loop's trip count is the wave's, because the cull below talks across its lanes.  Per chunk, geometry first -- it
-// needs no label and no density:
-//   1. crop_chunk and, linear, the one-owner test of the relabel kernel;
-//   2. the 16-bit mask of the chunk's selected texels.  The box of the wave's 64 chunks (wave_min / wave_max, then scalar) is held
-//      against the six half-spaces first: if it misses, the wave goes on (or, OUTSIDE, selects all it keeps) without a mask read.
-//      Then the lane's own chunk box, then each texel: X, Y and D advance by constants along the chunk;
-//   3. only if that mask is non-zero, the 16 labels and to[l] != l;
-//   4. only then the density, skipped by a uniform test when the window is 0..255;
-//   5. tally_texel, the journal append and the plain 16-byte store exactly as the brush does them.
-// Every texel is decided once, by its chunk's owner, from the bytes before the edit.
+// One pass over the items of slab s (make_crop_slab over the request's box, s.box_lo/hi that box, no plane), in either layout: the
+// walk and the tail of relabel_kernels.h (wave_chunk_step, selected_chunk_tail) around the lasso's selection rule, the 16-bit mask of
+// the chunk's texels that are inside (OUTSIDE: that are not).  The box of the wave's 64 chunks is held against the six half-spaces
+// first: if it misses, the wave goes on (or, OUTSIDE, selects all it keeps) without a mask read.  Then the lane's own chunk box, then
+// each texel: X, Y and D advance by constants along the chunk, beside the coordinates, in a loop of this pass's own.
 template <bool JOURNAL>
 __device__ __forceinline__ void lasso_pass(RelabelShared& sh, uint4* __restrict__ labels, const uint4* __restrict__ vol, const uint32_t* __restrict__ plane,
                                            const RelabelOut& out, const LabelTable& to, const CropSlab& s, const LassoRule& rule, const LabelJournal& journal,
                                            uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked, uint32_t n_items)
 {
-    sh.to[threadIdx.x] = to.v[threadIdx.x];
-    tally_init(sh);
-    __syncthreads();
+    edit_prologue(sh, to);
     const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
     const uint32_t lane = threadIdx.x & 63u;
@@ -147,42 +139,17 @@ __device__ __forceinline__ void lasso_pass(RelabelShared& sh, uint4* __restrict_
     RelabelTally t;
 
     for (uint32_t base = blockIdx.x * 256u + wave * 64u; base < n_items; base += gridDim.x * 256u) {
-        const uint32_t i = base + lane;
-        uint64_t k = 0;
-        uint32_t keep = 0, moved;
-        bool live = i < n_items && crop_chunk<false>(s, i, nx, ny, n, bricked, bx, by, k, keep, moved);
-        if (live && !bricked && !relabel_owns_chunk(s, i, nx, ny, k)) live = false;
-        if (!keep) live = false;
-        // the chunk's texel box (hi inclusive), as the brush takes it: a brick's 4 x 4 patch of one z; linear, 16 texels that may wrap
-        // rows and slices, whose box is then taken a little wide (whole rows, whole slices): it only culls
-        uint32_t x0 = 0, y0 = 0, z0 = 0, cl[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, ch[3] = {0u, 0u, 0u};
-        if (live) {
-            label_chunk_origin(bricked != 0u, static_cast<uint32_t>(k), nx, ny, x0, y0, z0);   // (k < 2^28: a layout has fewer than 2^32 bytes)
-            cl[0] = x0; cl[1] = y0; cl[2] = ch[2] = z0;
-            if (bricked) { ch[0] = x0 + 3u; ch[1] = y0 + 3u; }
-            else if (x0 + 15u < nx) { ch[0] = x0 + 15u; ch[1] = y0; }
-            else {
-                const uint32_t rows = (x0 + 15u) / nx;
-                cl[0] = 0u; ch[0] = nx - 1u; ch[1] = y0 + rows;
-                if (ch[1] >= ny) { cl[1] = 0u; ch[1] = ny - 1u; ch[2] = z0 + (y0 + rows) / ny; }
-            }
-        }
-        uint32_t wl[3], wh[3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            wl[a] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_min(cl[a]))));
-            wh[a] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_max(ch[a]))));
-        }
-        if (wl[0] > wh[0]) continue;                                     // (uniform: no lane of the wave has a chunk)
+        WaveChunk c;
+        if (!wave_chunk_step(c, s, base, lane, n_items, nx, ny, n, bricked, bx, by)) continue;
         uint32_t mask = 0;
-        if (no_rect || lasso_box_misses(rule, wl, wh)) {                 // (uniform) nothing in the wave's box is inside
+        if (no_rect || lasso_box_misses(rule, c.wl, c.wh)) {             // (uniform) nothing in the wave's box is inside
             if (!rule.outside) continue;
-            mask = live ? keep : 0u;
-        } else if (live) {
-            if (lasso_box_misses(rule, cl, ch)) mask = rule.outside ? keep : 0u;
+            mask = c.live ? c.keep : 0u;
+        } else if (c.live) {
+            if (lasso_box_misses(rule, c.cl, c.ch)) mask = rule.outside ? c.keep : 0u;
             else {
-                uint32_t x = x0, y = y0, z = z0;
-                const int64_t X0 = lasso_row(rule, 0, x0, y0, z0), Y0 = lasso_row(rule, 1, x0, y0, z0), D0 = lasso_row(rule, 2, x0, y0, z0);
+                uint32_t x = c.x0, y = c.y0, z = c.z0;
+                const int64_t X0 = lasso_row(rule, 0, x, y, z), Y0 = lasso_row(rule, 1, x, y, z), D0 = lasso_row(rule, 2, x, y, z);
                 int64_t X = X0, Y = Y0, D = D0;
 #pragma unroll 1
                 for (uint32_t j = 0; j < 16u; ++j) {
@@ -192,7 +159,7 @@ __device__ __forceinline__ void lasso_pass(RelabelShared& sh, uint4* __restrict_
                         Y = Y0 + static_cast<int64_t>(rule.m[1][0]) * jx + static_cast<int64_t>(rule.m[1][1]) * jy;
                         D = D0 + static_cast<int64_t>(rule.m[2][0]) * jx + static_cast<int64_t>(rule.m[2][1]) * jy;
                     }
-                    if ((keep & (1u << j)) && lasso_inside(rule, plane, X, Y, D) != (rule.outside != 0u)) mask |= 1u << j;
+                    if ((c.keep & (1u << j)) && lasso_inside(rule, plane, X, Y, D) != (rule.outside != 0u)) mask |= 1u << j;
                     if (!bricked) {
                         if (++x == nx) {
                             x = 0u;
@@ -206,49 +173,7 @@ __device__ __forceinline__ void lasso_pass(RelabelShared& sh, uint4* __restrict_
             }
         }
         if (!mask) continue;                                             // before any load of labels or density
-        const uint4 lv = labels[k];
-        uint32_t lb[4] = {lv.x, lv.y, lv.z, lv.w};
-        uint32_t cand = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            const uint32_t l = (lb[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-            if (sh.to[l] != l) cand |= 1u << j;
-        }
-        cand &= mask;
-        if (!cand) continue;                                             // no density, no store
-        if (windowed) {
-            const uint4 dv = vol[k];
-            const uint32_t d[4] = {dv.x, dv.y, dv.z, dv.w};
-#pragma unroll
-            for (uint32_t j = 0; j < 16u; ++j) {
-                const uint32_t b = (d[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-                if (b < rule.min_byte || b > rule.max_byte) cand &= ~(1u << j);
-            }
-            if (!cand) continue;
-        }
-        uint32_t x = x0, y = y0, z = z0;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); }
-            if (cand & (1u << j)) {
-                const uint32_t shift = 8u * (j & 3u), l = (lb[j >> 2] >> shift) & 0xffu, becomes = sh.to[l];
-                lb[j >> 2] = (lb[j >> 2] & ~(0xffu << shift)) | (becomes << shift);
-                tally_texel(sh, t, l, becomes, x, y, z);
-            }
-            if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
-        }
-        if (rule.store) {
-            if (JOURNAL) {
-                const unsigned long long here = __ballot(1);             // the lanes that store a chunk in this step
-                const uint32_t leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
-                uint32_t first = 0u;
-                if (lane == leader) first = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
-                first = __shfl(first, static_cast<int>(leader), 64);
-                const uint32_t at = first + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
-                if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = lv; }
-            }
-            labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
-        }
+        selected_chunk_tail<JOURNAL>(sh, t, labels, vol, c.k, mask, windowed, rule.min_byte, rule.max_byte, rule.store, journal, nx, ny, bricked);
     }
     tally_reduce(sh, t, out);
 }

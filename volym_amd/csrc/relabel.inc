@@ -1,8 +1,9 @@
 // The label edit (volym_edit_labels, volym_relabel_check, volym_read_labels): included at the end of scene_bytes.hip, beside the
 // kernels it launches (relabel_kernels.h) and the transition whose pieces it is built from (rewrite, ensure_uncropped_copies,
 // refresh_macro_cells, scan_label_stats), and its history (volym_label_history, volym_undo_labels, volym_redo_labels,
-// volym_label_history_info).  Blocking set-up calls like the other edits of that unit.  brush.inc, included after this file, builds
-// the brush on edit_labels, LabelEdit and editable_state.
+// volym_label_history_info).  Blocking set-up calls like the other edits of that unit.  brush.inc and lasso.inc, included after this
+// file, build their edits on what is here: editable_state, LabelEdit and edit_labels (the transition, with the kernel as a parameter),
+// and the three things every launch site needs: edit_density, launch_edit and CallArray.
 
 #include <cstddef>
 
@@ -205,6 +206,44 @@ static int edit_labels(volym_ctx* c, const LabelEdit& r, volym_relabel_result& r
     return rc;
 }
 
+// the density an edit's window reads: the uncut copy with UNCUT, where there is one (call it after ensure_uncropped_copies: inside launch)
+static const uint4* edit_density(const volym_ctx* c, bool uncut) { return reinterpret_cast<const uint4*>(uncut && c->d_vol0 ? c->d_vol0 : c->d_vol); }
+
+// What edit_labels' launch does with what it is handed, for a pair of kernels (plain, journalling) that differ in the journal argument
+// alone: the labels first, then `front` (what the kernel reads beside them), the result, the table, the slab and the rule, the journal
+// where there is one, and the volume's shape.
+template <class Plain, class Journalling, class Rule, class... Front>
+static void launch_edit(const volym_ctx* c, Plain plain, Journalling journalling, hipStream_t stream, dim3 grid, const RelabelOut& out, const LabelTable& to,
+                        const CropSlab& s, const Rule& rule, uint32_t items, const LabelJournal* journal, Front... front)
+{
+    uint4* const labels = reinterpret_cast<uint4*>(c->d_labels);
+    const uint32_t bricked = c->bricked ? 1u : 0u;
+    if (journal) hipLaunchKernelGGL(journalling, grid, dim3(256), 0, stream, labels, front..., out, to, s, rule, *journal, c->nx, c->ny, c->nz, bricked, items);
+    else hipLaunchKernelGGL(plain, grid, dim3(256), 0, stream, labels, front..., out, to, s, rule, c->nx, c->ny, c->nz, bricked, items);
+}
+
+// A small host array on the device for the length of one call (the brush's segments, the lasso's edges): copied on `stream`, in
+// stream order in front of the call's kernels, and freed when the call returns, once the stream is idle (after a refusal the copy or a
+// kernel may still run).
+template <class T>
+struct CallArray {
+    T* ptr = nullptr;
+    hipStream_t stream = nullptr;
+
+    // VOLYM_E_NOMEM "hipMalloc(<what>): <hip error>", or VOLYM_E_HIP "<who>: <hip error>" for the copy
+    int upload(volym_ctx* c, hipStream_t on, const std::vector<T>& host, const char* what, const char* who)
+    {
+        stream = on;
+        hipError_t e = hipMalloc(&ptr, host.size() * sizeof(T));
+        if (e != hipSuccess) { ptr = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e)); }
+        e = hipMemcpyAsync(ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? VOLYM_OK : fail(c, VOLYM_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    CallArray() = default;
+    CallArray(const CallArray&) = delete;
+    ~CallArray() { if (ptr) { (void)hipStreamSynchronize(stream); (void)hipFree(ptr); } }
+};
+
 // volym_edit_labels' request as an edit: the relabel kernel of its flags, plain or journalling
 static int relabel_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_result& res)
 {
@@ -222,18 +261,11 @@ static int relabel_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_re
     const LabelEdit edit = {r->box, r->to, dry, "volym_edit_labels"};
     return edit_labels(c, edit, res, [&](hipStream_t stream, dim3 grid, const RelabelOut& out, const LabelTable& to, const CropSlab& s, uint32_t items,
                                          const LabelJournal* journal) {
-        const uint4* vol = reinterpret_cast<const uint4*>(uncut_bytes && c->d_vol0 ? c->d_vol0 : c->d_vol);     // (after ensure_uncropped_copies)
-        if (journal) {
-            const auto kernel = with_ids ? (with_map ? volym_relabel_journal_kernel<true, true> : volym_relabel_journal_kernel<true, false>)
-                                         : (with_map ? volym_relabel_journal_kernel<false, true> : volym_relabel_journal_kernel<false, false>);
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), vol, ids, dmap, out, to, s, rule, *journal, c->nx, c->ny,
-                               c->nz, c->bricked ? 1u : 0u, items);
-        } else {
-            const auto kernel = with_ids ? (with_map ? volym_relabel_kernel<true, true> : volym_relabel_kernel<true, false>)
-                                         : (with_map ? volym_relabel_kernel<false, true> : volym_relabel_kernel<false, false>);
-            hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), vol, ids, dmap, out, to, s, rule, c->nx, c->ny, c->nz,
-                               c->bricked ? 1u : 0u, items);
-        }
+        const auto plain = with_ids ? (with_map ? volym_relabel_kernel<true, true> : volym_relabel_kernel<true, false>)
+                                    : (with_map ? volym_relabel_kernel<false, true> : volym_relabel_kernel<false, false>);
+        const auto journalling = with_ids ? (with_map ? volym_relabel_journal_kernel<true, true> : volym_relabel_journal_kernel<true, false>)
+                                          : (with_map ? volym_relabel_journal_kernel<false, true> : volym_relabel_journal_kernel<false, false>);
+        launch_edit(c, plain, journalling, stream, grid, out, to, s, rule, items, journal, edit_density(c, uncut_bytes), ids, dmap);
     });
 }
 

@@ -1,6 +1,10 @@
 // The kernels of the label edit (volym_edit_labels, volym_read_labels) and of its history (volym_label_history: the journalling form
 // of the edit, and the swap of volym_undo_labels and volym_redo_labels).  Included by scene_bytes.hip alone, after scene_kernels.h,
 // whose chunk walk (CropSlab, crop_chunk) and chunk geometry (label_chunk_origin) they read; nothing in that header changes.
+// Also what every edit pass is made of, here once for the brush (brush_kernels.h) and the lasso (lasso_kernels.h), which add a
+// selection rule and nothing else: the result's tally, the journal, the pieces of a chunk's edit (edit_prologue, ChunkCursor,
+// chunk_candidates, chunk_in_window, chunk_apply, chunk_store) and the wave-at-a-time walk and tail of the passes that select by
+// geometry (wave_chunk_step, selected_chunk_tail).
 #pragma once
 
 #include "scene_kernels.h"
@@ -149,16 +153,161 @@ struct LabelJournal {
     uint32_t capacity;
 };
 
+// ---- what the edit passes share: relabel_pass below, brush_pass (brush_kernels.h), lasso_pass (lasso_kernels.h) ------------------------
+
+// every pass begins so: the table and an empty tally in LDS
+__device__ __forceinline__ void edit_prologue(RelabelShared& sh, const LabelTable& to)
+{
+    sh.to[threadIdx.x] = to.v[threadIdx.x];
+    tally_init(sh);
+    __syncthreads();
+}
+
+// The texel of byte j of a chunk whose first texel is (x0, y0, z0), in either layout: built at that texel, put at byte j before the
+// byte is looked at (a brick is a 4 x 4 patch of one z) and moved on after it (a linear chunk runs along x and wraps rows and slices).
+struct ChunkCursor {
+    uint32_t x, y, z;
+    __device__ __forceinline__ void at(uint32_t bricked, uint32_t j, uint32_t x0, uint32_t y0) { if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); } }
+    __device__ __forceinline__ void next(uint32_t bricked, uint32_t nx, uint32_t ny) { if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } } }
+};
+
+// the texels of `mask` whose label the table moves: bit j for byte j of the 16 labels lb
+__device__ __forceinline__ uint32_t chunk_candidates(const RelabelShared& sh, const uint32_t lb[4], uint32_t mask)
+{
+    uint32_t cand = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) {
+        const uint32_t l = (lb[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+        if (sh.to[l] != l) cand |= 1u << j;
+    }
+    return cand & mask;
+}
+
+// ... and of those, the ones whose density byte lies in the window
+__device__ __forceinline__ uint32_t chunk_in_window(const uint4& dv, uint32_t min_byte, uint32_t max_byte, uint32_t cand)
+{
+    const uint32_t d[4] = {dv.x, dv.y, dv.z, dv.w};
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) {
+        const uint32_t b = (d[j >> 2] >> (8u * (j & 3u))) & 0xffu;
+        if (b < min_byte || b > max_byte) cand &= ~(1u << j);
+    }
+    return cand;
+}
+
+// Apply and tally: each candidate texel gets its new label in lb and is counted.  The chunk's first texel is (x0, y0, z0).
+__device__ __forceinline__ void chunk_apply(RelabelShared& sh, RelabelTally& t, uint32_t lb[4], uint32_t cand, uint32_t bricked, uint32_t x0, uint32_t y0, uint32_t z0,
+                                            uint32_t nx, uint32_t ny)
+{
+    ChunkCursor c = {x0, y0, z0};
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) {
+        c.at(bricked, j, x0, y0);
+        if (cand & (1u << j)) {
+            const uint32_t shift = 8u * (j & 3u), l = (lb[j >> 2] >> shift) & 0xffu, becomes = sh.to[l];
+            lb[j >> 2] = (lb[j >> 2] & ~(0xffu << shift)) | (becomes << shift);
+            tally_texel(sh, t, l, becomes, c.x, c.y, c.z);
+        }
+        c.next(bricked, nx, ny);
+    }
+}
+
+// Store chunk k, whose bytes were lv and are lb now, by a plain vector store.  JOURNAL: the chunk is appended to the journal first,
+// once (its owner is the only lane that gets here): the lanes of a wave that arrive together take one atomicAdd for their number and
+// rank themselves below it.  The callers' loops are divergent here, so the ballot is taken among the lanes that are there.
+template <bool JOURNAL>
+__device__ __forceinline__ void chunk_store(uint4* __restrict__ labels, uint64_t k, const uint4& lv, const uint32_t lb[4], const LabelJournal& journal)
+{
+    if (JOURNAL) {
+        const unsigned long long here = __ballot(1);                     // the lanes that store a chunk in this step
+        const uint32_t lane = threadIdx.x & 63u, leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
+        uint32_t first = 0u;
+        if (lane == leader) first = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
+        first = __shfl(first, static_cast<int>(leader), 64);
+        const uint32_t at = first + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
+        if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = lv; }
+    }
+    labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
+}
+
+// ---- the walk and the tail of the passes whose texels are selected by geometry (the brush, the lasso) -------------------------------
+// Such a pass goes over its slab a wave at a time -- the loop's trip count is the wave's, because its cull talks across the lanes --
+// and decides per chunk, geometry first: the 16-bit mask of the chunk's selected texels needs no memory.
+
+// One step of that walk: the lane's chunk and the boxes the selection rules cull with.
+struct WaveChunk {
+    uint32_t k, keep;               // the lane's chunk (k < 2^28: a layout has fewer than 2^32 bytes) and the texels of it the slab keeps
+                                    // (live: it has a chunk, owns it, and keeps some)
+    bool live;
+    uint32_t x0, y0, z0;            // the chunk's first texel
+    uint32_t cl[3], ch[3];          // the chunk's texel box, hi INCLUSIVE (no chunk: lo > hi)
+    uint32_t wl[3], wh[3];          // the box of the wave's 64 chunks, in scalar registers
+};
+
+// Item base + lane of slab s: crop_chunk and, linear, the one-owner test.  The chunk's box is a brick's 4 x 4 patch of one z; linear,
+// 16 texels that may wrap rows and slices, whose box is then taken a little wide (whole rows, whole slices): it only culls.  False:
+// no lane of the wave has a chunk (uniform).
+__device__ __forceinline__ bool wave_chunk_step(WaveChunk& c, const CropSlab& s, uint32_t base, uint32_t lane, uint32_t n_items, uint32_t nx, uint32_t ny, uint64_t n,
+                                                uint32_t bricked, uint32_t bx, uint32_t by)
+{
+    const uint32_t i = base + lane;
+    uint64_t k = 0;
+    uint32_t moved;
+    c.keep = 0;
+    c.live = i < n_items && crop_chunk<false>(s, i, nx, ny, n, bricked, bx, by, k, c.keep, moved);
+    if (c.live && !bricked && !relabel_owns_chunk(s, i, nx, ny, k)) c.live = false;
+    if (!c.keep) c.live = false;
+    c.k = static_cast<uint32_t>(k);
+    c.x0 = c.y0 = c.z0 = 0u;
+    for (int a = 0; a < 3; ++a) { c.cl[a] = 0xffffffffu; c.ch[a] = 0u; }
+    if (c.live) {
+        label_chunk_origin(bricked != 0u, c.k, nx, ny, c.x0, c.y0, c.z0);
+        c.cl[0] = c.x0; c.cl[1] = c.y0; c.cl[2] = c.ch[2] = c.z0;
+        if (bricked) { c.ch[0] = c.x0 + 3u; c.ch[1] = c.y0 + 3u; }
+        else if (c.x0 + 15u < nx) { c.ch[0] = c.x0 + 15u; c.ch[1] = c.y0; }
+        else {
+            const uint32_t rows = (c.x0 + 15u) / nx;
+            c.cl[0] = 0u; c.ch[0] = nx - 1u; c.ch[1] = c.y0 + rows;
+            if (c.ch[1] >= ny) { c.cl[1] = 0u; c.ch[1] = ny - 1u; c.ch[2] = c.z0 + (c.y0 + rows) / ny; }
+        }
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        c.wl[a] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_min(c.cl[a]))));
+        c.wh[a] = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(wave_max(c.ch[a]))));
+    }
+    return c.wl[0] <= c.wh[0];
+}
+
+// The tail of a chunk whose mask is not 0: only now the 16 labels and to[l] != l; only if a candidate is left the density, skipped by
+// a uniform test when the window is 0..255; then apply and tally, and the store of chunk_store unless DRY_RUN.  Every texel is decided
+// once, by its chunk's owner, from the bytes before the edit.
+template <bool JOURNAL>
+__device__ __forceinline__ void selected_chunk_tail(RelabelShared& sh, RelabelTally& t, uint4* __restrict__ labels, const uint4* __restrict__ vol, uint64_t k,
+                                                    uint32_t mask, bool windowed, uint32_t min_byte, uint32_t max_byte, uint32_t store, const LabelJournal& journal,
+                                                    uint32_t nx, uint32_t ny, uint32_t bricked)
+{
+    const uint4 lv = labels[k];
+    uint32_t lb[4] = {lv.x, lv.y, lv.z, lv.w};
+    uint32_t cand = chunk_candidates(sh, lb, mask);
+    if (!cand) return;                                                   // no density, no store
+    if (windowed) {                                                      // (uniform)
+        cand = chunk_in_window(vol[k], min_byte, max_byte, cand);
+        if (!cand) return;
+    }
+    uint32_t x0, y0, z0;
+    label_chunk_origin(bricked != 0u, static_cast<uint32_t>(k), nx, ny, x0, y0, z0);
+    chunk_apply(sh, t, lb, cand, bricked, x0, y0, z0, nx, ny);
+    if (store) chunk_store<JOURNAL>(labels, k, lv, lb, journal);
+}
+
+// ---- the edit by table, window, piece and distance ------------------------------------------------------------------------------------
 // One pass over the items of slab s (make_crop_slab over the request's box, s.box_lo/hi the box itself, no plane: keep names the
-// texels of the box), in either layout.  Per chunk: the 16 labels first; a chunk in which no texel of the box has to[l] != l loads
-// nothing more and stores nothing.  Else the 16 density bytes (vol: the scene bytes, or the uncut copy), then -- IDS, DISTANCE --
-// the id and the distance of the texels that are still candidates, from the box-linear snapshots.  The chunk is stored, by a
-// plain vector store, only if a byte changed and rule.store says so.  Labels are read and written by the chunk's one owner and
-// everything else is only read: every texel is decided from the bytes before the edit.
-//
-// JOURNAL: a chunk that is about to be stored is appended to the journal first, once (its owner is the only lane that gets here):
-// the lanes of a wave that arrive together take one atomicAdd for their number and rank themselves below it.  The loop is divergent,
-// so the ballot is taken inside the predicate, among the lanes that are there.
+// texels of the box), in either layout, a lane at a time: the trip count is the item's, and a lane goes on before any load.  Per
+// chunk: the 16 labels first; a chunk in which no texel of the box has to[l] != l loads nothing more and stores nothing.  Else the 16
+// density bytes (vol: the scene bytes, or the uncut copy), then -- IDS, DISTANCE -- the id and the distance of the texels that are
+// still candidates, from the box-linear snapshots.  The chunk is stored only if a byte changed and rule.store says so.  Labels are
+// read and written by the chunk's one owner and everything else is only read: every texel is decided from the bytes before the edit.
 //
 // The result: tally_texel per changed texel, tally_reduce at the end.
 template <bool IDS, bool DISTANCE, bool JOURNAL>
@@ -167,9 +316,7 @@ __device__ __forceinline__ void relabel_pass(RelabelShared& sh, uint4* __restric
                                              const RelabelRule& rule, const LabelJournal& journal, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t bricked,
                                              uint32_t n_items)
 {
-    sh.to[threadIdx.x] = to.v[threadIdx.x];
-    tally_init(sh);
-    __syncthreads();
+    edit_prologue(sh, to);
     const uint64_t n = static_cast<uint64_t>(nx) * ny * nz;
     const uint32_t bx = brick_count(nx), by = brick_count(ny);
     RelabelTally t;
@@ -182,61 +329,36 @@ __device__ __forceinline__ void relabel_pass(RelabelShared& sh, uint4* __restric
         if (!keep) continue;                                             // before any load
         const uint4 lv = labels[k];
         uint32_t lb[4] = {lv.x, lv.y, lv.z, lv.w};
-        uint32_t cand = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            const uint32_t l = (lb[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-            if (sh.to[l] != l) cand |= 1u << j;
-        }
-        cand &= keep;
+        uint32_t cand = chunk_candidates(sh, lb, keep);
         if (!cand) continue;                                             // no density, no ids, no store
-        const uint4 dv = vol[k];
-        const uint32_t d[4] = {dv.x, dv.y, dv.z, dv.w};
-#pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            const uint32_t b = (d[j >> 2] >> (8u * (j & 3u))) & 0xffu;
-            if (b < rule.min_byte || b > rule.max_byte) cand &= ~(1u << j);
-        }
+        cand = chunk_in_window(vol[k], rule.min_byte, rule.max_byte, cand);
         if (!cand) continue;
         uint32_t x0, y0, z0;
         label_chunk_origin(bricked != 0u, static_cast<uint32_t>(k), nx, ny, x0, y0, z0);      // (k < 2^28: a layout has fewer than 2^32 bytes)
-        uint32_t x = x0, y = y0, z = z0;
+        if (IDS || DISTANCE) {                                           // the snapshots, between window and apply
+            ChunkCursor c = {x0, y0, z0};
 #pragma unroll
-        for (uint32_t j = 0; j < 16u; ++j) {
-            if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); }
-            if (cand & (1u << j)) {
-                bool in = true;
-                if (IDS) {
-                    const uint32_t id = ids[box_linear(rule.ids_box, x, y, z)];
-                    const bool ranged = id >= rule.id_lo && id <= rule.id_hi;
-                    in = id != VOLYM_COMPONENT_NONE && (rule.ids_except ? !ranged : ranged);
+            for (uint32_t j = 0; j < 16u; ++j) {
+                c.at(bricked, j, x0, y0);
+                if (cand & (1u << j)) {
+                    bool in = true;
+                    if (IDS) {
+                        const uint32_t id = ids[box_linear(rule.ids_box, c.x, c.y, c.z)];
+                        const bool ranged = id >= rule.id_lo && id <= rule.id_hi;
+                        in = id != VOLYM_COMPONENT_NONE && (rule.ids_except ? !ranged : ranged);
+                    }
+                    if (DISTANCE && in) {
+                        const uint32_t dd = dmap[box_linear(rule.map_box, c.x, c.y, c.z)];
+                        in = dd != VOLYM_DISTANCE_NONE && dd >= rule.d2_lo && dd <= rule.d2_hi;
+                    }
+                    if (!in) cand &= ~(1u << j);
                 }
-                if (DISTANCE && in) {
-                    const uint32_t dd = dmap[box_linear(rule.map_box, x, y, z)];
-                    in = dd != VOLYM_DISTANCE_NONE && dd >= rule.d2_lo && dd <= rule.d2_hi;
-                }
-                if (in) {
-                    const uint32_t shift = 8u * (j & 3u), l = (lb[j >> 2] >> shift) & 0xffu, becomes = sh.to[l];
-                    lb[j >> 2] = (lb[j >> 2] & ~(0xffu << shift)) | (becomes << shift);
-                    tally_texel(sh, t, l, becomes, x, y, z);
-                } else {
-                    cand &= ~(1u << j);
-                }
+                c.next(bricked, nx, ny);
             }
-            if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
+            if (!cand) continue;
         }
-        if (cand && rule.store) {
-            if (JOURNAL) {
-                const unsigned long long here = __ballot(1);             // the lanes that store a chunk in this step
-                const uint32_t lane = threadIdx.x & 63u, leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
-                uint32_t base = 0u;
-                if (lane == leader) base = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
-                base = __shfl(base, static_cast<int>(leader), 64);
-                const uint32_t at = base + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
-                if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = lv; }
-            }
-            labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
-        }
+        chunk_apply(sh, t, lb, cand, bricked, x0, y0, z0, nx, ny);
+        if (rule.store) chunk_store<JOURNAL>(labels, k, lv, lb, journal);
     }
     tally_reduce(sh, t, out);
 }
@@ -264,7 +386,7 @@ __global__ __launch_bounds__(256) void volym_relabel_journal_kernel(uint4* __res
 // step of the grid.  Chunk index[i] gets the bytes old[i] and old[i] the bytes the chunk held, so that the same launch takes the swap
 // back.  The chunks of a step are distinct: no two lanes touch the same one.  For the bytes that differ (texels of the volume: an edit
 // changes no padding) the lane tallies the label that is there now as left and the one it restores as arrived, and their hull, with
-// coordinates stepped as the relabel kernel steps them: a linear chunk wraps rows and slices.
+// coordinates stepped by the edit's ChunkCursor: a linear chunk wraps rows and slices.
 __global__ __launch_bounds__(256) void volym_label_swap_kernel(uint4* __restrict__ labels, const uint32_t* __restrict__ index, uint4* __restrict__ old,
                                                                RelabelOut out, uint32_t nx, uint32_t ny, uint32_t bricked, uint32_t n_records)
 {
@@ -280,13 +402,13 @@ __global__ __launch_bounds__(256) void volym_label_swap_kernel(uint4* __restrict
         const uint32_t a[4] = {now.x, now.y, now.z, now.w}, b[4] = {rec.x, rec.y, rec.z, rec.w};
         uint32_t x0, y0, z0;
         label_chunk_origin(bricked != 0u, k, nx, ny, x0, y0, z0);
-        uint32_t x = x0, y = y0, z = z0;
+        ChunkCursor c = {x0, y0, z0};
 #pragma unroll
         for (uint32_t j = 0; j < 16u; ++j) {
-            if (bricked) { x = x0 + (j & 3u); y = y0 + (j >> 2); }
+            c.at(bricked, j, x0, y0);
             const uint32_t shift = 8u * (j & 3u), from = (a[j >> 2] >> shift) & 0xffu, to = (b[j >> 2] >> shift) & 0xffu;
-            if (from != to) tally_texel(sh, t, from, to, x, y, z);
-            if (!bricked && ++x == nx) { x = 0u; if (++y == ny) { y = 0u; ++z; } }
+            if (from != to) tally_texel(sh, t, from, to, c.x, c.y, c.z);
+            c.next(bricked, nx, ny);
         }
     }
     tally_reduce(sh, t, out);

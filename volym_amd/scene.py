@@ -1347,16 +1347,86 @@ def relabel_table(mapping=None):
     return to
 
 
+# What the three edits of the labels share (Relabel, Brush, Lasso; `noun` names the request in every ValueError): the fields box, flags,
+# window and to, and the tail of their host twins.
+def _edit_fields(r, noun, box, dims, flags, window, to):
+    r.box = _box_or_whole(box, dims, "a %s request without a box needs the volume's dims" % noun)
+    r.flags = int(flags)
+    r.window = tuple(int(v) for v in window)
+    r.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+
+
+def _edit_fields_to_c(r, c, noun, others_fit, others):
+    """box, flags, window and to of request r into its C struct c.  `others_fit`: the request's other u32 fields fit too; `others`:
+    how the ValueError names them all."""
+    c.box = _box_to_c(r.box, noun)
+    if not 0 <= r.flags < 2 ** 32 or len(r.window) != 2 or not all(0 <= x < 2 ** 32 for x in r.window) or not others_fit:
+        raise ValueError("%s: %s" % (noun, others))
+    c.flags = r.flags
+    c.min_byte, c.max_byte = r.window
+    if r.to.size != 256 or not ((r.to >= 0) & (r.to <= 255)).all():
+        raise ValueError("%s: the table is 256 bytes" % noun)
+    c.to = (C.c_uint8 * 256)(*[int(g) for g in r.to])
+    return c
+
+
+def _check_edit_fields(r, dims, noun, known):
+    """The rules every edit shares: lo <= hi <= dims on every axis (an empty box is valid), no flag bit outside `known`,
+    min_byte <= max_byte <= 255, a table of 256 entries.  Returns dims as a list of int."""
+    dims = _box_in_dims(r.box, dims, noun)[2]
+    if r.flags & ~known or r.flags < 0:
+        raise ValueError("%s: unknown flag bits in %#x" % (noun, r.flags))
+    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
+        raise ValueError("%s: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (noun, r.window,))
+    if np.asarray(r.to).size != 256:
+        raise ValueError("%s: the table has 256 entries" % noun)
+    return dims
+
+
+def _edit_volume(noun, prepared, dims, r, labels, uncut, uncut_flag, dry_flag, select):
+    """What relabel_volume, brush_volume and lasso_volume share.  `select(lo, hi)`: the request's own condition as a bool array over
+    its box [z, y, x], or None for none; it is called only for a box that is not empty.  UNCUT and DRY_RUN are the caller's flag
+    values.  Returns (new_labels, result)."""
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("%s: labels have %d bytes, the volume %d" % (noun, lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (r.flags & uncut_flag and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("%s: the density has %d bytes, the volume %d" % (noun, src.size, lab.size))
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    to = np.asarray(r.to, np.int64).astype(np.uint8)
+    d = src.reshape(nz, ny, nx)[sub]
+    hit = (to[old] != old) & (d >= r.window[0]) & (d <= r.window[1])
+    selected = select(lo, hi)
+    if selected is not None:
+        hit &= selected
+    n = int(hit.sum())
+    if n == 0:
+        return new, result
+    result["changed"] = n
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not r.flags & dry_flag:
+        new[sub] = np.where(hit, to[old], old)
+    return new, result
+
+
 class Relabel:
     """volym_relabel (include/volym_hip.h): one edit of the labels.  box as Surface takes it; flags: _lib.RELABEL_UNCUT | RELABEL_IDS |
     RELABEL_IDS_EXCEPT | RELABEL_DISTANCE | RELABEL_DRY_RUN; window: (min_byte, max_byte) of the density; to: 256 labels (relabel_table);
     ids: (id_lo, id_hi) in the latest components pass; d2: (d2_lo, d2_hi) in the latest distance map."""
 
     def __init__(self, box=None, flags=0, window=(0, 255), to=None, ids=(0, 0), d2=(0, 0), dims=None):
-        self.box = _box_or_whole(box, dims, "a relabel request without a box needs the volume's dims")
-        self.flags = int(flags)
-        self.window = tuple(int(v) for v in window)
-        self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+        _edit_fields(self, "relabel", box, dims, flags, window, to)
         self.ids = tuple(int(v) for v in ids)
         self.d2 = tuple(int(v) for v in d2)
 
@@ -1366,16 +1436,8 @@ class Relabel:
 
     def to_c(self):
         """The _lib.Relabel of this request.  Fields that do not fit their C types raise ValueError."""
-        c = _lib.Relabel()
-        c.box = _box_to_c(self.box, "relabel")
-        pairs = (self.window, self.ids, self.d2)
-        if not 0 <= self.flags < 2 ** 32 or not all(len(p) == 2 and all(0 <= x < 2 ** 32 for x in p) for p in pairs):
-            raise ValueError("relabel: flags, window, ids and d2 must be u32 (pairs)")
-        c.flags = self.flags
-        c.min_byte, c.max_byte = self.window
-        if self.to.size != 256 or not ((self.to >= 0) & (self.to <= 255)).all():
-            raise ValueError("relabel: the table is 256 bytes")
-        c.to = (C.c_uint8 * 256)(*[int(g) for g in self.to])
+        pairs_fit = all(len(p) == 2 and all(0 <= x < 2 ** 32 for x in p) for p in (self.ids, self.d2))
+        c = _edit_fields_to_c(self, _lib.Relabel(), "relabel", pairs_fit, "flags, window, ids and d2 must be u32 (pairs)")
         c.id_lo, c.id_hi = self.ids
         c.d2_lo, c.d2_hi = self.d2
         return c
@@ -1386,20 +1448,13 @@ def check_relabel(relabel, dims):
     only with IDS, min_byte <= max_byte <= 255, id_lo <= id_hi with IDS, d2_lo <= d2_hi with DISTANCE.  Returns the request; raises
     ValueError."""
     r = relabel
-    _box_in_dims(r.box, dims, "relabel")
-    known = _lib.RELABEL_UNCUT | _lib.RELABEL_IDS | _lib.RELABEL_IDS_EXCEPT | _lib.RELABEL_DISTANCE | _lib.RELABEL_DRY_RUN
-    if r.flags & ~known or r.flags < 0:
-        raise ValueError("relabel: unknown flag bits in %#x" % r.flags)
+    _check_edit_fields(r, dims, "relabel", _lib.RELABEL_UNCUT | _lib.RELABEL_IDS | _lib.RELABEL_IDS_EXCEPT | _lib.RELABEL_DISTANCE | _lib.RELABEL_DRY_RUN)
     if r.flags & _lib.RELABEL_IDS_EXCEPT and not r.flags & _lib.RELABEL_IDS:
         raise ValueError("relabel: IDS_EXCEPT is valid only together with IDS")
-    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
-        raise ValueError("relabel: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (r.window,))
     if r.flags & _lib.RELABEL_IDS and not (len(r.ids) == 2 and 0 <= r.ids[0] <= r.ids[1]):
         raise ValueError("relabel: IDS needs id_lo <= id_hi, got %r" % (r.ids,))
     if r.flags & _lib.RELABEL_DISTANCE and not (len(r.d2) == 2 and 0 <= r.d2[0] <= r.d2[1]):
         raise ValueError("relabel: DISTANCE needs d2_lo <= d2_hi, got %r" % (r.d2,))
-    if np.asarray(r.to).size != 256:
-        raise ValueError("relabel: the table has 256 entries")
     return r
 
 
@@ -1421,41 +1476,21 @@ def relabel_volume(prepared, dims, r, labels, ids=None, ids_box=None, dmap=None,
     ids_box / dmap_box = ((lo), (hi)).  Returns (new_labels, result): the labels as a uint8 array [z, y, x] of the volume (the input
     untouched; with DRY_RUN a copy of it) and an np.void of _lib.RELABEL_RESULT_DTYPE."""
     r = check_relabel(r, dims)
-    nx, ny, nz = (int(v) for v in dims)
     lo, hi = r.box
-    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
-    lab = np.ascontiguousarray(labels, np.uint8).ravel()
-    if lab.size != nx * ny * nz:
-        raise ValueError("relabel_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
-    new = lab.reshape(nz, ny, nx).copy()
-    src = np.ascontiguousarray(uncut if (r.flags & _lib.RELABEL_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
-    if src.size != lab.size:
-        raise ValueError("relabel_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
-    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
     picked_ids = _snapshot_in_box("the component ids", ids, ids_box, lo, hi) if r.flags & _lib.RELABEL_IDS else None
     picked_map = _snapshot_in_box("the distance map", dmap, dmap_box, lo, hi) if r.flags & _lib.RELABEL_DISTANCE else None
-    if any(a >= b for a, b in zip(lo, hi)):
-        return new, result
-    old = new[sub]
-    to = np.asarray(r.to, np.int64).astype(np.uint8)
-    b = src.reshape(nz, ny, nx)[sub]
-    hit = (to[old] != old) & (b >= r.window[0]) & (b <= r.window[1])
-    if picked_ids is not None:
-        ranged = (picked_ids >= r.ids[0]) & (picked_ids <= r.ids[1])
-        hit &= (picked_ids != np.uint32(_lib.COMPONENT_NONE)) & (~ranged if r.flags & _lib.RELABEL_IDS_EXCEPT else ranged)
-    if picked_map is not None:
-        hit &= (picked_map != np.uint32(_lib.DISTANCE_NONE)) & (picked_map >= r.d2[0]) & (picked_map <= r.d2[1])
-    n = int(hit.sum())
-    if n == 0:
-        return new, result
-    result["changed"] = n
-    result["left"][...] = np.bincount(old[hit], minlength=256)
-    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
-    z, y, x = np.nonzero(hit)
-    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
-    if not r.flags & _lib.RELABEL_DRY_RUN:
-        new[sub] = np.where(hit, to[old], old)
-    return new, result
+
+    def select(lo, hi):
+        hit = None
+        if picked_ids is not None:
+            ranged = (picked_ids >= r.ids[0]) & (picked_ids <= r.ids[1])
+            hit = (picked_ids != np.uint32(_lib.COMPONENT_NONE)) & (~ranged if r.flags & _lib.RELABEL_IDS_EXCEPT else ranged)
+        if picked_map is not None:
+            banded = (picked_map != np.uint32(_lib.DISTANCE_NONE)) & (picked_map >= r.d2[0]) & (picked_map <= r.d2[1])
+            hit = banded if hit is None else hit & banded
+        return hit
+
+    return _edit_volume("relabel_volume", prepared, dims, r, labels, uncut, _lib.RELABEL_UNCUT, _lib.RELABEL_DRY_RUN, select)
 
 
 class Brush:
@@ -1464,10 +1499,7 @@ class Brush:
     _lib.BRUSH_MAX_POINTS texels (x, y, z) or (x, y, z, flags), flags = _lib.BRUSH_LIFT: no capsule from the point before."""
 
     def __init__(self, points, r2, box=None, flags=0, window=(0, 255), to=None, weight=(1, 1, 1), dims=None):
-        self.box = _box_or_whole(box, dims, "a brush request without a box needs the volume's dims")
-        self.flags = int(flags)
-        self.window = tuple(int(v) for v in window)
-        self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+        _edit_fields(self, "brush", box, dims, flags, window, to)
         self.weight = tuple(int(v) for v in weight)
         self.r2 = int(r2)
         self.points = [tuple(int(v) for v in p) + ((0,) if len(p) == 3 else ()) for p in points]
@@ -1478,17 +1510,10 @@ class Brush:
 
     def to_c(self):
         """The _lib.Brush of this request.  Fields that do not fit their C types raise ValueError."""
-        c = _lib.Brush()
-        c.box = _box_to_c(self.box, "brush")
-        if not 0 <= self.flags < 2 ** 32 or not 0 <= self.r2 < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
-            raise ValueError("brush: flags, r2 and the window's ends must be u32")
+        c = _edit_fields_to_c(self, _lib.Brush(), "brush", 0 <= self.r2 < 2 ** 32, "flags, r2 and the window's ends must be u32")
         if len(self.weight) != 3 or not all(0 <= x < 2 ** 32 for x in self.weight):
             raise ValueError("brush: three u32 weights")
-        c.flags, c.r2 = self.flags, self.r2
-        c.min_byte, c.max_byte = self.window
-        if self.to.size != 256 or not ((self.to >= 0) & (self.to <= 255)).all():
-            raise ValueError("brush: the table is 256 bytes")
-        c.to = (C.c_uint8 * 256)(*[int(g) for g in self.to])
+        c.r2 = self.r2
         c.weight = (C.c_uint32 * 3)(*self.weight)
         if len(self.points) > _lib.BRUSH_MAX_POINTS:
             raise ValueError("brush: at most %d points, got %d" % (_lib.BRUSH_MAX_POINTS, len(self.points)))
@@ -1505,11 +1530,7 @@ def check_brush(brush, dims):
     min_byte <= max_byte <= 255, weights in 1.._lib.DISTANCE_WEIGHT_MAX, 1.._lib.BRUSH_MAX_POINTS points inside the volume, no point
     flag but LIFT; r2 is any u32.  Returns the request; raises ValueError."""
     b = brush
-    dims = _box_in_dims(b.box, dims, "brush")[2]
-    if b.flags & ~(_lib.BRUSH_UNCUT | _lib.BRUSH_DRY_RUN) or b.flags < 0:
-        raise ValueError("brush: unknown flag bits in %#x" % b.flags)
-    if len(b.window) != 2 or not 0 <= b.window[0] <= b.window[1] <= 255:
-        raise ValueError("brush: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (b.window,))
+    dims = _check_edit_fields(b, dims, "brush", _lib.BRUSH_UNCUT | _lib.BRUSH_DRY_RUN)
     if len(b.weight) != 3 or not all(1 <= w <= _lib.DISTANCE_WEIGHT_MAX for w in b.weight):
         raise ValueError("brush: three weights in 1..%d, got %r" % (_lib.DISTANCE_WEIGHT_MAX, b.weight))
     if not 0 <= b.r2 < 2 ** 32:
@@ -1521,8 +1542,6 @@ def check_brush(brush, dims):
             raise ValueError("brush: point %r lies outside the volume %r" % (p, tuple(dims)))
         if p[3] & ~_lib.BRUSH_LIFT or p[3] < 0:
             raise ValueError("brush: unknown point flag bits in %#x" % p[3])
-    if np.asarray(b.to).size != 256:
-        raise ValueError("brush: the table has 256 entries")
     return b
 
 
@@ -1610,34 +1629,8 @@ def brush_volume(prepared, dims, b, labels, uncut=None):
     the window and it lies within at least one segment; every texel is decided once, from the bytes before the edit.  Returns
     (new_labels, result) as relabel_volume does."""
     b = check_brush(b, dims)
-    nx, ny, nz = (int(v) for v in dims)
-    lo, hi = b.box
-    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
-    lab = np.ascontiguousarray(labels, np.uint8).ravel()
-    if lab.size != nx * ny * nz:
-        raise ValueError("brush_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
-    new = lab.reshape(nz, ny, nx).copy()
-    src = np.ascontiguousarray(uncut if (b.flags & _lib.BRUSH_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
-    if src.size != lab.size:
-        raise ValueError("brush_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
-    if any(p >= q for p, q in zip(lo, hi)):
-        return new, result
-    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
-    old = new[sub]
-    to = np.asarray(b.to, np.int64).astype(np.uint8)
-    d = src.reshape(nz, ny, nx)[sub]
-    hit = (to[old] != old) & (d >= b.window[0]) & (d <= b.window[1]) & brush_mask(b, dims)[sub]
-    n = int(hit.sum())
-    if n == 0:
-        return new, result
-    result["changed"] = n
-    result["left"][...] = np.bincount(old[hit], minlength=256)
-    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
-    z, y, x = np.nonzero(hit)
-    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
-    if not b.flags & _lib.BRUSH_DRY_RUN:
-        new[sub] = np.where(hit, to[old], old)
-    return new, result
+    select = lambda lo, hi: brush_mask(b, dims)[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+    return _edit_volume("brush_volume", prepared, dims, b, labels, uncut, _lib.BRUSH_UNCUT, _lib.BRUSH_DRY_RUN, select)
 
 
 class LassoView:
@@ -1681,11 +1674,7 @@ class Lasso:
     implicitly; view: a LassoView; box, window and to as Relabel takes them; flags: _lib.LASSO_UNCUT | LASSO_DRY_RUN | LASSO_OUTSIDE."""
 
     def __init__(self, points, view, box=None, flags=0, window=(0, 255), to=None, dims=None):
-        self.box = _box_or_whole(box, dims, "a lasso request without a box needs the volume's dims")
-        self.box = (tuple(int(v) for v in self.box[0]), tuple(int(v) for v in self.box[1]))
-        self.flags = int(flags)
-        self.window = tuple(int(v) for v in window)
-        self.to = relabel_table() if to is None else (relabel_table(to) if isinstance(to, dict) else np.array(to, np.int64).ravel())
+        _edit_fields(self, "lasso", box, dims, flags, window, to)
         self.view = view
         self.points = [tuple(int(v) for v in p) for p in points]
 
@@ -1695,18 +1684,7 @@ class Lasso:
 
     def to_c(self):
         """The _lib.Lasso of this request.  Fields that do not fit their C types raise ValueError."""
-        c = _lib.Lasso()
-        v = list(self.box[0]) + list(self.box[1])
-        if len(v) != 6 or not all(0 <= x < 2 ** 32 for x in v):
-            raise ValueError("lasso: the box is two triples of u32 texel indices")
-        c.box = (C.c_uint32 * 6)(*v)
-        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
-            raise ValueError("lasso: flags and the window's ends must be u32")
-        c.flags = self.flags
-        c.min_byte, c.max_byte = self.window
-        if self.to.size != 256 or not ((self.to >= 0) & (self.to <= 255)).all():
-            raise ValueError("lasso: the table is 256 bytes")
-        c.to = (C.c_uint8 * 256)(*[int(g) for g in self.to])
+        c = _edit_fields_to_c(self, _lib.Lasso(), "lasso", True, "flags and the window's ends must be u32")
         c.view = self.view.to_c()
         if len(self.points) > _lib.LASSO_MAX_POINTS:
             raise ValueError("lasso: at most %d vertices, got %d" % (_lib.LASSO_MAX_POINTS, len(self.points)))
@@ -1723,17 +1701,7 @@ def check_lasso(lasso, dims):
     min_byte <= max_byte <= 255, 3.._lib.LASSO_MAX_POINTS vertices within _lib.LASSO_VERTEX_MAX of the origin, |m| < 2^31, |c| < 2^46,
     1 <= depth[0] <= depth[1], a frame of 1.._lib.LASSO_MAX_FRAME pixels a side.  Returns the request; raises ValueError."""
     l = lasso
-    dims = [int(v) for v in dims]
-    lo, hi = l.box
-    if len(lo) != 3 or len(hi) != 3 or len(dims) != 3:
-        raise ValueError("lasso: the box is two triples of texel indices")
-    for a in range(3):
-        if not 0 <= lo[a] <= hi[a] <= dims[a]:
-            raise ValueError("lasso box axis %d: need 0 <= lo <= hi <= %d, got [%d, %d)" % (a, dims[a], lo[a], hi[a]))
-    if l.flags & ~(_lib.LASSO_UNCUT | _lib.LASSO_DRY_RUN | _lib.LASSO_OUTSIDE) or l.flags < 0:
-        raise ValueError("lasso: unknown flag bits in %#x" % l.flags)
-    if len(l.window) != 2 or not 0 <= l.window[0] <= l.window[1] <= 255:
-        raise ValueError("lasso: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (l.window,))
+    _check_edit_fields(l, dims, "lasso", _lib.LASSO_UNCUT | _lib.LASSO_DRY_RUN | _lib.LASSO_OUTSIDE)
     _check_lasso_polygon(l.points, l.view.width, l.view.height)
     v = l.view
     if len(v.m) != 3 or any(len(row) != 3 for row in v.m) or len(v.c) != 3 or len(v.depth) != 2:
@@ -1744,8 +1712,6 @@ def check_lasso(lasso, dims):
         raise ValueError("lasso view: |c| < 2^46")
     if not 1 <= v.depth[0] <= v.depth[1] < 2 ** 63:
         raise ValueError("lasso view: 1 <= depth[0] <= depth[1], got %r" % (v.depth,))
-    if np.asarray(l.to).size != 256:
-        raise ValueError("lasso: the table has 256 entries")
     return l
 
 
@@ -1858,37 +1824,13 @@ def lasso_volume(prepared, dims, lasso, labels, uncut=None):
     inside != OUTSIDE; a selected texel with label l becomes to[l] iff it lies in the box, to[l] != l and its density byte lies in
     the window; every texel is decided once, from the bytes before the edit.  Returns (new_labels, result) as relabel_volume does."""
     l = check_lasso(lasso, dims)
-    nx, ny, nz = (int(v) for v in dims)
-    lo, hi = l.box
-    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
-    lab = np.ascontiguousarray(labels, np.uint8).ravel()
-    if lab.size != nx * ny * nz:
-        raise ValueError("lasso_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
-    new = lab.reshape(nz, ny, nx).copy()
-    src = np.ascontiguousarray(uncut if (l.flags & _lib.LASSO_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
-    if src.size != lab.size:
-        raise ValueError("lasso_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
-    if any(p >= q for p, q in zip(lo, hi)):
-        return new, result
-    lands, px, py = lasso_texels(l.view, dims)
-    inside = lands & lasso_mask(l.points, l.view.width, l.view.height)[py, px]
-    selected = inside != bool(l.flags & _lib.LASSO_OUTSIDE)
-    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
-    old = new[sub]
-    to = np.asarray(l.to, np.int64).astype(np.uint8)
-    d = src.reshape(nz, ny, nx)[sub]
-    hit = (to[old] != old) & (d >= l.window[0]) & (d <= l.window[1]) & selected[sub]
-    n = int(hit.sum())
-    if n == 0:
-        return new, result
-    result["changed"] = n
-    result["left"][...] = np.bincount(old[hit], minlength=256)
-    result["arrived"][...] = np.bincount(to[old[hit]], minlength=256)
-    z, y, x = np.nonzero(hit)
-    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
-    if not l.flags & _lib.LASSO_DRY_RUN:
-        new[sub] = np.where(hit, to[old], old)
-    return new, result
+
+    def select(lo, hi):
+        lands, px, py = lasso_texels(l.view, dims)
+        inside = lands & lasso_mask(l.points, l.view.width, l.view.height)[py, px]
+        return (inside != bool(l.flags & _lib.LASSO_OUTSIDE))[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]]
+
+    return _edit_volume("lasso_volume", prepared, dims, l, labels, uncut, _lib.LASSO_UNCUT, _lib.LASSO_DRY_RUN, select)
 
 
 def relabel_result_dict(result):
