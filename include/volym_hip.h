@@ -1182,6 +1182,48 @@ int   volym_lasso_view_from_camera(const volym_camera_uniforms* camera, uint32_t
  * distance that is not a number, back < front, or a range that rounds to depth[0] > depth[1]. */
 int   volym_lasso_view_depth(struct volym_lasso_view* view, double front, double back);
 
+/* --- smooth: a majority filter over a box of texels (new; the reference has none) ------------------------------------- */
+/* The first edit that decides a texel from its neighbours' labels: a median filter for one segment, a joint majority filter for all
+ * of them.  It removes threshold speckle, fills pinholes and rounds off the staircase a lasso or a brush leaves.  The context ends up
+ * byte for byte where volym_read_labels, the host filter and volym_set_labels would have left it, and the history survives.
+ *   The rule (integers only; scene.smooth_volume of the Python package is its host twin, equal in every byte).  For texel
+ * t = (x, y, z) with label l, N(t) is the set of texels u OF THE VOLUME (not only of the box) with |u_a - t_a| <= radius[a] on every
+ * axis; texels outside the volume do not exist and cast no vote.  count[m] = the number of u in N(t) that carry m, for the labels as
+ * they stand before the call; hidden, cropped and clipped texels vote like any other (the cuts act through the density window
+ * alone).  The candidates are l itself and every m with take[m] != 0.  The winner w is the candidate with the largest count: l if l
+ * is among those with the largest count, else the smallest such m.  t becomes w iff t lies in the box, give[l] != 0, w != l and the
+ * density byte lies in [min_byte, max_byte] (the scene byte as it stands, or the uncut copy with UNCUT, as volym_edit_labels reads
+ * it).  Every texel is decided from the labels before the call: the result depends neither on the device layout nor on the order of
+ * the workgroups.  DRY_RUN fills the result and writes nothing. */
+#define VOLYM_SMOOTH_MAX_RADIUS 3u
+enum { VOLYM_SMOOTH_UNCUT = 1, VOLYM_SMOOTH_DRY_RUN = 16 };   /* flags: they carry the values of their VOLYM_RELABEL counterparts */
+typedef struct volym_smooth {
+    uint32_t box[6];            /* as in volym_relabel: lo inclusive, hi exclusive, lo <= hi <= dims; an empty box is valid */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window, on the texel that would change */
+    uint32_t radius[3];         /* each 0..VOLYM_SMOOTH_MAX_RADIUS, not all 0; (1, 1, 0) smooths inside slices */
+    uint8_t  give[256];         /* give[l] != 0: texels that carry l may change */
+    uint8_t  take[256];         /* take[m] != 0: label m may receive texels */
+} volym_smooth;                 /* 560 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(volym_smooth) == 560, "volym_smooth is 560 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_smooth) == 560, "volym_smooth is 560 bytes");
+#endif
+/* The smoothing: a blocking set-up call with the contract of volym_brush_labels (it waits for the frames in flight; the kernels run
+ * on the first slot's stream; with changed == 0, or DRY_RUN, no label is touched and a surface pass stays valid; otherwise counts,
+ * boxes, density and importances follow and a surface pass is stale; out may be NULL).  Two phases, because a texel's decision reads
+ * labels another workgroup would overwrite: a vote kernel reads labels and density and leaves the chunks that change, as they will
+ * be, in the journal's staging area; the swap of volym_undo_labels then exchanges them with the labels.  While the history is on, a
+ * call that changes a texel (no DRY_RUN) is one step of it, kept if its records <= min(items of the box's slab, budget / 20).
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_smooth_check refuses.  VOLYM_E_STATE: what volym_edit_labels refuses of the
+ * context's state.  The native multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_smooth_labels(volym_ctx* ctx, const volym_smooth* smooth, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, a window without min_byte <= max_byte <= 255, a radius above VOLYM_SMOOTH_MAX_RADIUS, all radii 0.  An empty box is valid:
+ * nothing changes.  Pure host arithmetic. */
+int   volym_smooth_check(const volym_smooth* smooth, const uint32_t dims[3]);
+
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);
 /* n back-to-back compute passes timed with HIP events on the context's stream;

@@ -26,8 +26,8 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
---relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
+--relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -309,6 +309,19 @@ def _brush_arg(d, ctx, text):
     return scene.Brush(points, r2, to=d._brush_table(ctx, _segment_arg(to), None), dims=d.dims)
 
 
+def _smooth_arg(text):
+    """--smooth [NAME,...][:R[,R,R]] -> (names or None for a joint pass, radius)"""
+    usage = "[NAME,...][:R[,R,R]] -- the segments to smooth against label 0 (none: every label, jointly) and the radius in texels, one or per axis (default 1)"
+    names, sep, r = text.partition(":")
+    try:
+        radius = [int(v) for v in r.split(",")] if sep else [1]
+    except ValueError:
+        raise SystemExit("--smooth: %s" % usage)
+    if len(radius) not in (1, 3) or (sep and not r):
+        raise SystemExit("--smooth: %s" % usage)
+    return ([_segment_arg(n) for n in names.split(",") if n] or None), (radius[0] if len(radius) == 1 else tuple(radius))
+
+
 def _label_edits(ctx, d, args):
     """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, lasso, split_at, keep_largest, grow, shrink):
     [(option, result)]"""
@@ -337,6 +350,12 @@ def _label_edits(ctx, d, args):
                 raise SystemExit("--lasso: %s" % usage)
             out.append(("lasso", d.lasso(ctx, pixels, _segment_arg(to), over=[_segment_arg(f) for f in froms.split(",") if f],
                                          outside=bool(getattr(args, "lasso_outside", False)))))
+        if getattr(args, "smooth", None) is not None:
+            names, radius = _smooth_arg(args.smooth)
+            iterations = getattr(args, "smooth_iterations", None) or 1
+            if iterations < 1:
+                raise SystemExit("--smooth-iterations: N is a number of passes, got %d" % iterations)
+            out.append(("smooth", d.smooth(ctx, names, radius, iterations)))
         if getattr(args, "split_at", None):
             at, to = _name_and(args.split_at, "--split-at", "X,Y:TO -- a pixel and the segment its piece becomes", None)
             p = d.split_at(ctx, *_outline_at_arg(at, "--split-at"), _segment_arg(to))
@@ -377,7 +396,7 @@ def run_simple(args):
             clipped = {"clip_plane": None if plane is None else {"n": list(plane[0]), "d": plane[1]}}
             d.compute_pass(ctx)
             ctx.sync()
-        # label edits, in the order relabel, brush, brush at pixels, lasso, split, keep the largest, grow, shrink; the PNG is the frame after them
+        # label edits, in the order relabel, brush, brush at pixels, lasso, smooth, split, keep the largest, grow, shrink; the PNG is the frame after them
         undo = getattr(args, "undo", None) or 0
         if undo < 0:
             raise SystemExit("--undo: N is a number of edits to take back, got %d" % undo)
@@ -628,6 +647,10 @@ def main(argv=None):
     run.add_argument("--lasso", help="X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO: scissors: the texels of the segments FROM that the first frame's view projects into that "
                                      "polygon of pixels (closed implicitly, even-odd; vertices may lie off screen) join segment TO (0: unlabelled), on the device, "
                                      "after --brush-at; one undo step")
+    run.add_argument("--smooth", nargs="?", const="", help="[NAME,...][:R[,R,R]]: smooth the segmentation on the device after the first frame: a majority filter over "
+                     "R texels (default 1; R,R,R per axis, 1,1,0 inside slices) for the segments NAME against label 0, or jointly for every label without a "
+                     "name (demo.Simple.smooth); prints the passes' results")
+    run.add_argument("--smooth-iterations", type=int, help="with --smooth: N passes, each an undo step of its own (default 1)")
     run.add_argument("--lasso-outside", action="store_true", help="with --lasso: the texels that do NOT project into the polygon instead (keep only what is under it)")
     run.add_argument("--split-at", help="X,Y:TO: the piece of the segment pixel (X, Y) shows becomes segment TO (a new name gets an entry)")
     run.add_argument("--keep-largest", help="NAME: keep the largest piece of the segment, its other pieces become unlabelled")

@@ -322,6 +322,23 @@ LASSO_MAX_FRAME = 16384
 LASSO_VERTEX_MAX = 1 << 20
 
 
+SMOOTH_UNCUT, SMOOTH_DRY_RUN = 1, 16                           # volym_smooth.flags: they carry the values of their RELABEL counterparts
+SMOOTH_MAX_RADIUS = 3
+
+
+class Smooth(C.Structure):
+    """volym_smooth (include/volym_hip.h): box, flags, density window, radii and the give and take tables, 560 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("radius", C.c_uint32 * 3),
+        ("give", C.c_uint8 * 256),
+        ("take", C.c_uint8 * 256),
+    ]
+
+
 class LassoView(C.Structure):
     """volym_lasso_view (include/volym_hip.h): the integer view texel -> (X, Y, D), 88 bytes"""
     _fields_ = [
@@ -544,6 +561,8 @@ SIGNATURES = {
     "volym_read_lasso_mask": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_uint64]),
     "volym_lasso_view_from_camera": (C.c_int, [C.POINTER(CameraUniforms), C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_double, C.POINTER(LassoView)]),
     "volym_lasso_view_depth": (C.c_int, [C.POINTER(LassoView), C.c_double, C.c_double]),
+    "volym_smooth_labels": (C.c_int, [_ctx, C.POINTER(Smooth), C.POINTER(RelabelResult)]),
+    "volym_smooth_check": (C.c_int, [C.POINTER(Smooth), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -282,6 +282,7 @@ struct volym_ctx {
     uint64_t history_used = 0;               // 20 * records over history_steps
     uint64_t history_dropped = 0, history_lost = 0;
     volym::OwnedBuffer<uint32_t> journal_index;   // where an edit journals: room for the worst case of its slab within the budget
+                                                  // (and where the smoothing's vote leaves its records, history on or off: smooth.inc)
     volym::OwnedBuffer<uint4> journal_old;
 
     // the lasso (volym_lasso_labels, lasso.inc): the polygon's bit plane of the latest call over lasso_rect; count: its words

@@ -222,6 +222,25 @@ public:
         records_current_ = false;
         return out;
     }
+    // New: smoothing on the device (volym_smooth_labels): one pass of the majority filter over `radius` texels per axis, through the
+    // whole volume.  names empty: joint, every label gives and takes; else those segments (names, ids or label values as text) and
+    // label 0 give and take.  One call, one step of the history.
+    volym_relabel_result smooth(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& names, const std::array<uint32_t, 3>& radius)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "smooth: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        volym_smooth s{};
+        s.box[3] = a.nx; s.box[4] = a.ny; s.box[5] = a.nz;
+        s.max_byte = 255u;
+        for (int k = 0; k < 3; ++k) s.radius[k] = radius[static_cast<size_t>(k)];
+        for (int k = 0; k < 256; ++k) s.give[k] = s.take[k] = names.empty() ? 1u : 0u;
+        if (!names.empty()) s.give[0] = s.take[0] = 1u;
+        for (const std::string& n : names) { const uint8_t l = label_value_of(a, n); s.give[l] = s.take[l] = 1u; }
+        volym_relabel_result out{};
+        ctx.check(volym_smooth_labels(ctx.handle(), &s, &out));
+        records_current_ = false;
+        return out;
+    }
     // New: keep a history of the label edits in at most budget_bytes of device memory (volym_label_history), so that undo can take
     // them back.  The labels go to the device first: handing them to the context clears the history.
     void history(const GpuContext& ctx, const SimpleAssets& a, uint64_t budget_bytes = 256ull << 20)

@@ -4,6 +4,7 @@
 // volym_label_history_info).  Blocking set-up calls like the other edits of that unit.  brush.inc and lasso.inc, included after this
 // file, build their edits on what is here: editable_state, LabelEdit and edit_labels (the transition, with the kernel as a parameter),
 // and the three things every launch site needs: edit_density, launch_edit and CallArray.
+// smooth.inc, the edit in two phases, takes the pieces instead: editable_state, DeviceRelabelResult, edit_density, record_step, follow_labels.
 
 #include <cstddef>
 

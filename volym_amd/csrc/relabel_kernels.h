@@ -212,21 +212,26 @@ __device__ __forceinline__ void chunk_apply(RelabelShared& sh, RelabelTally& t, 
     }
 }
 
+// One record, chunk k with the 16 bytes `bytes`, appended to the journal: the lanes of a wave that arrive together take one atomicAdd
+// for their number and rank themselves below it.  The callers' loops are divergent here, so the ballot is taken among the lanes that
+// are there.  (The smoothing's vote, smooth_kernels.h, appends the bytes a chunk WILL hold by the same counter.)
+__device__ __forceinline__ void journal_append(const LabelJournal& journal, uint64_t k, const uint4& bytes)
+{
+    const unsigned long long here = __ballot(1);                         // the lanes that store a chunk in this step
+    const uint32_t lane = threadIdx.x & 63u, leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
+    uint32_t first = 0u;
+    if (lane == leader) first = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
+    first = __shfl(first, static_cast<int>(leader), 64);
+    const uint32_t at = first + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
+    if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = bytes; }
+}
+
 // Store chunk k, whose bytes were lv and are lb now, by a plain vector store.  JOURNAL: the chunk is appended to the journal first,
-// once (its owner is the only lane that gets here): the lanes of a wave that arrive together take one atomicAdd for their number and
-// rank themselves below it.  The callers' loops are divergent here, so the ballot is taken among the lanes that are there.
+// once (its owner is the only lane that gets here), by journal_append.
 template <bool JOURNAL>
 __device__ __forceinline__ void chunk_store(uint4* __restrict__ labels, uint64_t k, const uint4& lv, const uint32_t lb[4], const LabelJournal& journal)
 {
-    if (JOURNAL) {
-        const unsigned long long here = __ballot(1);                     // the lanes that store a chunk in this step
-        const uint32_t lane = threadIdx.x & 63u, leader = static_cast<uint32_t>(__ffsll(here)) - 1u;
-        uint32_t first = 0u;
-        if (lane == leader) first = atomicAdd(journal.count, static_cast<uint32_t>(__popcll(here)));
-        first = __shfl(first, static_cast<int>(leader), 64);
-        const uint32_t at = first + static_cast<uint32_t>(__popcll(here & ((1ull << lane) - 1ull)));
-        if (at < journal.capacity) { journal.index[at] = static_cast<uint32_t>(k); journal.old[at] = lv; }
-    }
+    if (JOURNAL) journal_append(journal, k, lv);
     labels[k] = make_uint4(lb[0], lb[1], lb[2], lb[3]);
 }
 

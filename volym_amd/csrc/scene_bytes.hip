@@ -4,7 +4,8 @@
 // declared in context.hpp.  Everything here is blocking set-up path, except the measure pass at the end (measure.inc, measure_kernels.h),
 // which only reads these bytes and is enqueue-only, and the label edit after it (relabel.inc, relabel_kernels.h), which rewrites
 // labels in place and carries density and importances along by the same invariant, and the brush (brush.inc, brush_kernels.h), the
-// same edit decided by a stroke's geometry, and the lasso (lasso.inc, lasso_kernels.h), the same edit decided by where a texel projects.
+// same edit decided by a stroke's geometry, and the lasso (lasso.inc, lasso_kernels.h), the same edit decided by where a texel projects,
+// and the smoothing (smooth.inc, smooth_kernels.h), the edit decided by a texel's neighbours, in two phases.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include "relabel_kernels.h"
 #include "brush_kernels.h"
 #include "lasso_kernels.h"
+#include "smooth_kernels.h"
 
 using namespace volym;
 
@@ -1007,3 +1009,6 @@ int volym_label_counts(volym_ctx* c, uint64_t counts[256])
 
 // ---- the lasso: the edit whose texels a screen polygon decides ---------------------------------------------------------------
 #include "lasso.inc"
+
+// ---- the smoothing: the edit a majority vote of the neighbours decides ----------------------------------------------------------
+#include "smooth.inc"

@@ -19,6 +19,8 @@
 //   --brush X,Y,Z[/X,Y,Z...]:TO:R2 paints label TO within sqrt(R2) texels of that polyline of texels (Simple::brush), after --relabel;
 //   --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO cuts with the scissors: the texels of the segments FROM under that polygon of pixels of
 //   the first frame join TO (Simple::lasso), after --brush;
+//   --smooth [NAME,...][:R[,R,R]] smooths the segmentation: one pass of the majority filter over R texels (default 1) for the segments
+//   NAME against label 0, or jointly for every label without a name (Simple::smooth), after --lasso;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
 #include <algorithm>
 #include <cctype>
@@ -75,6 +77,9 @@ struct Options {
     std::vector<std::array<int32_t, 2>> lasso_pixels;    // --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO: the scissors over a polygon of pixels (run simple)
     std::vector<std::string> lasso_from;
     std::string lasso_to;
+    bool smooth = false;                                 // --smooth [NAME,...][:R[,R,R]]: one pass of the majority filter (run simple)
+    std::vector<std::string> smooth_names;
+    std::array<uint32_t, 3> smooth_radius = {1u, 1u, 1u};
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -215,6 +220,8 @@ int run_simple(const Options& o)
     if (!o.brush_to.empty()) brushed = demo.brush(ctx, assets, o.brush_points, o.brush_to, o.brush_r2);       // after --relabel, before --undo
     volym_relabel_result lassoed{};
     if (!o.lasso_to.empty()) lassoed = demo.lasso(ctx, assets, o.lasso_pixels, o.lasso_from, o.lasso_to);   // the view of the first frame; after --brush, before --undo
+    volym_relabel_result smoothed{};
+    if (o.smooth) smoothed = demo.smooth(ctx, assets, o.smooth_names, o.smooth_radius);                     // after --lasso, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -238,6 +245,7 @@ int run_simple(const Options& o)
     if (!o.relabel_to.empty()) print_result("relabel", relabelled);
     if (!o.brush_to.empty()) print_result("brush", brushed);
     if (!o.lasso_to.empty()) print_result("lasso", lassoed);
+    if (o.smooth) print_result("smooth", smoothed);
     for (const auto& u : undone) {
         if (u.first) print_result("undo", u.second);
         else std::printf("undo: nothing to take back\n");
@@ -469,6 +477,40 @@ int main(int argc, char** argv)
                 } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
                 if (o.lasso_pixels.size() < 3u || o.lasso_pixels.size() > VOLYM_LASSO_MAX_POINTS) throw Error(VOLYM_E_INVALID, usage);
             }
+            else if (a == "--smooth") {
+                const char* usage = "--smooth: [NAME,...][:R[,R,R]] -- the segments to smooth against label 0 (none: every label, jointly) and the radius in texels";
+                o.smooth = true;
+                std::string v;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") v = next();
+                const size_t colon = v.rfind(':');
+                const std::string names = colon == std::string::npos ? v : v.substr(0, colon);
+                size_t pos = 0;
+                while (pos < names.size()) {
+                    const size_t comma = std::min(names.find(',', pos), names.size());
+                    if (comma > pos) o.smooth_names.push_back(names.substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+                if (colon != std::string::npos) {
+                    const std::string r = v.substr(colon + 1u);
+                    std::vector<uint32_t> radii;
+                    try {
+                        pos = 0;
+                        while (pos <= r.size()) {
+                            const size_t comma = std::min(r.find(',', pos), r.size());
+                            const std::string one = r.substr(pos, comma - pos);
+                            size_t used = 0;
+                            if (one.empty() || one[0] < '0' || one[0] > '9') throw Error(VOLYM_E_INVALID, usage);
+                            const unsigned long c = std::stoul(one, &used);
+                            if (used != one.size() || c > VOLYM_SMOOTH_MAX_RADIUS) throw Error(VOLYM_E_INVALID, usage);
+                            radii.push_back(static_cast<uint32_t>(c));
+                            pos = comma + 1u;
+                        }
+                    } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
+                    if (radii.size() == 1u) o.smooth_radius = {radii[0], radii[0], radii[0]};
+                    else if (radii.size() == 3u) o.smooth_radius = {radii[0], radii[1], radii[2]};
+                    else throw Error(VOLYM_E_INVALID, usage);
+                }
+            }
             else if (a == "--labels-out") o.labels_out = next();
             else if (a == "--undo") o.undo = static_cast<uint32_t>(std::stoul(next()));
             else if (a == "--measure") {
@@ -567,7 +609,7 @@ int main(int argc, char** argv)
                 o.project_mode = mode == "MEAN" ? VOLYM_PROJECT_MEAN : VOLYM_PROJECT_MAX;
                 o.project_step = step;
             }
-            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--brush x,y,z[/x,y,z...]:to:r2] [--lasso x,y/x,y/x,y[/...]:from[,from...]:to] [--undo n] [--labels-out file]\n"); return 2; }
+            else { std::fprintf(stderr, "usage: volym [run simple | benchmark] [-d] [--volume f --labels f --segments f] [--width n --height n] [--secs s] [--output f] [--frames-in-flight 1|2] [--crop x0,y0,z0,x1,y1,z1] [--clip-plane nx,ny,nz,px,py,pz] [--hide l,l,...] [--slice x|y|z,index] [--project MAX|MEAN[,step]] [--measure [name,...]] [--surface [name,...][:min_byte]] [--surface-out file.stl] [--components [name,...][:min_byte]] [--distance [name,...][:min_byte]] [--distance-inside] [--relabel from[,from...]:to] [--brush x,y,z[/x,y,z...]:to:r2] [--lasso x,y/x,y/x,y[/...]:from[,from...]:to] [--smooth [name,...][:r[,r,r]]] [--undo n] [--labels-out file]\n"); return 2; }
         } catch (const std::exception& e) { std::fprintf(stderr, "%s\n", e.what()); return 2; }
     }
     try {

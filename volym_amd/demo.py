@@ -567,6 +567,15 @@ class GpuContext:
         self._ck(_lib.lib().volym_lasso_labels(self.handle, C.byref(lasso.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
+    def smooth_labels(self, smooth):
+        """One pass of the majority filter on the device (include/volym_hip.h volym_smooth_labels; scene.smooth_volume is its
+        definition): a texel of the box whose label gives becomes the label that wins the vote of its neighbourhood among its own
+        and those that take, where the density window says so.  `smooth` is a scene.Smooth.  Everything follows as after
+        edit_labels, and the call is one step of the history.  Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_smooth_labels(self.handle, C.byref(smooth.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
     def read_lasso_mask(self):
         """The polygon's bit plane of the latest lasso_labels (include/volym_hip.h volym_read_lasso_mask): (rect, words) -- rect =
         (x0, y0, x1, y1), hi exclusive, words = np.uint32[(y1 - y0) * ceil((x1 - x0) / 32)], as scene.lasso_mask_words lays them out."""
@@ -1461,6 +1470,38 @@ class Simple(ComputeDemo):
             front = float(sum(view.m[2][a] * t[a] for a in range(3)) + view.c[2]) * 2.0 ** -view.scale_log2      # the texel's own D, in world units
             view = scene.lasso_view_depth(view, front, front + float(thickness) / max(self.dims))
             p["relabel"] = self._lasso(ctx, scene.Lasso(pixels, view, None, 0, (0, 255), self._brush_table(ctx, name, over), dims=self.dims))
+        return p
+
+    def _smooth(self, ctx, smooth):
+        result = ctx.smooth_labels(scene.check_smooth(smooth, self.dims))
+        if int(result["changed"]) and not smooth.flags & _lib.SMOOTH_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def smooth(self, ctx, names=None, radius=1, iterations=1, box=None, window=(0, 255), uncut=False):
+        """Smooth the segmentation: a majority filter over the neighbourhood of `radius` texels (an int, or (rx, ry, rz): (1, 1, 0)
+        smooths inside slices).  names None: joint, every label gives and takes; a list (names, ids or label values): those
+        segments and label 0 give and take -- a median filter of one segment against the background.  `iterations` passes, EACH AN
+        UNDO STEP of its own; they stop early once a pass changes nothing.  Returns the list of the results' dicts."""
+        self._ready_to_edit(ctx)
+        table = None if names is None else scene.smooth_table(self._label_values(names) + [0])
+        flags = _lib.SMOOTH_UNCUT if uncut else 0
+        out = []
+        for _ in range(int(iterations)):
+            out.append(self._smooth(ctx, scene.Smooth(radius, box, flags, window, table, table, dims=self.dims)))
+            if not out[-1]["changed"]:
+                break
+        return out
+
+    def smooth_at(self, ctx, x, y, radius=1, iterations=1, alpha_min=0.5):
+        """Click to smooth: pick pixel (x, y) and smooth the segment it shows against label 0.  Returns the pick with a "smooth"
+        entry (the list smooth returns; None when the pixel shows no sample or no label)."""
+        self._ready_to_edit(ctx)
+        p = self.pick(ctx, x, y, alpha_min)
+        p["smooth"] = None
+        if p["status"] == "hit" and p["label"] is not None:
+            p["smooth"] = self.smooth(ctx, [int(p["label"])], radius, iterations)
         return p
 
     def save_labels(self, ctx, path):

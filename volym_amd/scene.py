@@ -1833,6 +1833,137 @@ def lasso_volume(prepared, dims, lasso, labels, uncut=None):
     return _edit_volume("lasso_volume", prepared, dims, l, labels, uncut, _lib.LASSO_UNCUT, _lib.LASSO_DRY_RUN, select)
 
 
+def smooth_table(labels=None):
+    """A give or take table of a smoothing request: 256 bytes, 1 for every label of `labels` (None: for all of them)."""
+    if labels is None:
+        return np.ones(256, np.uint8)
+    t = np.zeros(256, np.uint8)
+    for l in labels:
+        if not 0 <= int(l) <= 255:
+            raise ValueError("smooth_table: labels are bytes, got %r" % (l,))
+        t[int(l)] = 1
+    return t
+
+
+class Smooth:
+    """volym_smooth (include/volym_hip.h): one pass of the majority filter.  box and window as Relabel takes them; flags:
+    _lib.SMOOTH_UNCUT | SMOOTH_DRY_RUN; radius: (rx, ry, rz), each 0.._lib.SMOOTH_MAX_RADIUS and not all 0 (an int: all three);
+    give, take: tables of 256 bytes (smooth_table; None: every label) -- the labels whose texels may change and the labels that may
+    receive texels."""
+
+    def __init__(self, radius=1, box=None, flags=0, window=(0, 255), give=None, take=None, dims=None):
+        self.box = _box_or_whole(box, dims, "a smooth request without a box needs the volume's dims")
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.radius = (int(radius),) * 3 if np.isscalar(radius) else tuple(int(v) for v in radius)
+        self.give = smooth_table() if give is None else np.array(give, np.int64).ravel()
+        self.take = smooth_table() if take is None else np.array(take, np.int64).ravel()
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "smooth", ("radius", "box", "flags", "window", "give", "take"), kw)
+
+    def to_c(self):
+        """The _lib.Smooth of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Smooth()
+        c.box = _box_to_c(self.box, "smooth")
+        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("smooth: flags and the window's ends must be u32")
+        if len(self.radius) != 3 or not all(0 <= x < 2 ** 32 for x in self.radius):
+            raise ValueError("smooth: three u32 radii")
+        c.flags = self.flags
+        c.min_byte, c.max_byte = self.window
+        c.radius = (C.c_uint32 * 3)(*self.radius)
+        for name, t in (("give", self.give), ("take", self.take)):
+            if t.size != 256 or not ((t >= 0) & (t <= 255)).all():
+                raise ValueError("smooth: %s is a table of 256 bytes" % name)
+            setattr(c, name, (C.c_uint8 * 256)(*[int(g) for g in t]))
+        return c
+
+
+def check_smooth(smooth, dims):
+    """The validity rules of volym_smooth_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, radii in 0.._lib.SMOOTH_MAX_RADIUS and not all 0, tables of 256 entries.  Returns the request;
+    raises ValueError."""
+    r = smooth
+    _box_in_dims(r.box, dims, "smooth")
+    if r.flags & ~(_lib.SMOOTH_UNCUT | _lib.SMOOTH_DRY_RUN) or r.flags < 0:
+        raise ValueError("smooth: unknown flag bits in %#x" % r.flags)
+    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
+        raise ValueError("smooth: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (r.window,))
+    if len(r.radius) != 3 or not all(0 <= v <= _lib.SMOOTH_MAX_RADIUS for v in r.radius):
+        raise ValueError("smooth: three radii in 0..%d, got %r" % (_lib.SMOOTH_MAX_RADIUS, r.radius))
+    if not any(r.radius):
+        raise ValueError("smooth: at least one radius above 0")
+    if np.asarray(r.give).size != 256 or np.asarray(r.take).size != 256:
+        raise ValueError("smooth: give and take have 256 entries")
+    return r
+
+
+def _window_sums(a, r, axis):
+    """Sums of int array `a` over [i - r, i + r] along `axis`, cut to the array: differences of one cumulative sum."""
+    if r == 0:
+        return a
+    n = a.shape[axis]
+    shape = list(a.shape)
+    shape[axis] = 1
+    c = np.concatenate([np.zeros(shape, np.int64), np.cumsum(a, axis=axis, dtype=np.int64)], axis=axis)
+    i = np.arange(n)
+    return np.take(c, np.minimum(i + r, n - 1) + 1, axis=axis) - np.take(c, np.maximum(i - r, 0), axis=axis)
+
+
+def smooth_volume(prepared, dims, smooth, labels, uncut=None):
+    """The definition of the smoothing (include/volym_hip.h volym_smooth_labels), integers only and without any cull; equal to the
+    device in every byte.  `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None:
+    prepared), `labels`: the labels before the pass.  Per label of the volume, the votes of every texel are box sums of the label's
+    indicator over the WHOLE volume (x, then y, then z, from cumulative sums); the winner among the own label and the labels that
+    take is the largest count, the own label first and else the smallest label; a texel of the box whose label gives and whose
+    density byte lies in the window becomes the winner.  Returns (new_labels, result) as relabel_volume does."""
+    r = check_smooth(smooth, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("smooth_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    old = lab.reshape(nz, ny, nx)
+    new = old.copy()
+    src = np.ascontiguousarray(uncut if (r.flags & _lib.SMOOTH_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("smooth_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    give, take = np.asarray(r.give) != 0, np.asarray(r.take) != 0
+    own = np.zeros(old.shape, np.int64)
+    best = np.zeros(old.shape, np.int64)
+    best_label = np.zeros(old.shape, np.uint8)
+    for m in np.unique(old).tolist():                               # ascending: a later label must beat the count, not equal it
+        if not (give[m] or take[m]):
+            continue                                                # no candidate of any texel that may change
+        is_m = old == m
+        votes = _window_sums(_window_sums(_window_sums(is_m.astype(np.int64), r.radius[0], 2), r.radius[1], 1), r.radius[2], 0)
+        own[is_m] = votes[is_m]
+        if take[m]:
+            better = ~is_m & (votes > best)
+            best[better] = votes[better]
+            best_label[better] = m
+    d = src.reshape(nz, ny, nx)
+    hit = np.zeros(old.shape, bool)
+    hit[lo[2]:hi[2], lo[1]:hi[1], lo[0]:hi[0]] = True
+    hit &= give[old] & (best > own) & (d >= r.window[0]) & (d <= r.window[1])
+    n = int(hit.sum())
+    if n == 0:
+        return new, result
+    result["changed"] = n
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(best_label[hit], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (x.min(), y.min(), z.min(), x.max() + 1, y.max() + 1, z.max() + 1)
+    if not r.flags & _lib.SMOOTH_DRY_RUN:
+        new[hit] = best_label[hit]
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
