@@ -15,5 +15,5 @@ for blk in txt.split("Function Name: ")[1:]:
     print("%-72s vgpr %3d agpr %3d sgpr %3d scratch %4d lds %6d occ %d%s" % (dem,g("VGPRs"),g("AGPRs"),g("TotalSGPRs"),g(r"ScratchSize \[bytes/lane\]"),g(r"LDS Size \[bytes/block\]"),g(r"Occupancy \[waves/SIMD\]"),tag))
 ' "$1"; }
 /opt/rocm/bin/hipcc $FL $C/raymarch.hip -o /dev/null 2>&1 | fmt ""
-/opt/rocm/bin/hipcc $FL $C/scene_bytes.hip -o /dev/null 2>&1 | fmt "   [scene_bytes.hip]"
+for u in scene_bytes measure relabel brush lasso smooth; do /opt/rocm/bin/hipcc $FL $C/$u.hip -o /dev/null 2>&1 | fmt "   [$u.hip]"; done
 /opt/rocm/bin/hipcc $FL -mllvm -amdgpu-sched-strategy=iterative-ilp -O2 $C/raymarch_common.hip -o /dev/null 2>&1 | fmt "   [raymarch_common.hip: iterative-ilp, -O2]"

@@ -1,17 +1,16 @@
 """What the compiler made of the brush kernels (no GPU: any machine with hipcc).
 
-scene_bytes.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
-tests/test_relabel_resources.py compiles it.  volym_brush_kernel and volym_brush_journal_kernel must have no scratch, at most 128
+brush.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
+tests/test_relabel_resources.py compiles its unit.  volym_brush_kernel and volym_brush_journal_kernel must have no scratch, at most 128
 VGPRs, and no more LDS than the table, the tally and the segments need: the segments are read through the scalar cache, so that is
 sizeof(RelabelShared) = 256 + 2 * 1024 + 4 + 24 bytes.  Only the resource remarks are read, never the instructions.  The figures go
 to profiles/brush_kernel_resources.txt.
 """
 import os
-import subprocess
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import HIPCC, ROOT, compile_unit, makefile_builds, only_unit_including, scene_bytes_holds_no_part_of, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "brush_kernel_resources.txt")
 LDS_BAR = 256 + 2 * 1024 + 4 + 24
@@ -20,12 +19,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not 
 
 
 @pytest.fixture(scope="module")
-def scene_unit(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("brush")), "scene_bytes.s")
-    cmd = [HIPCC] + makefile_flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", os.path.join(CSRC, "scene_bytes.hip"), "-o", out]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return remarks(p.stderr)
+def scene_unit():
+    return compile_unit("brush")
 
 
 def kernels(res):
@@ -39,28 +34,20 @@ def kernels(res):
     return out
 
 
-def test_the_unit_includes_the_brush_after_the_edit_and_no_other_unit_does():
-    unit = open(os.path.join(CSRC, "scene_bytes.hip")).read()
-    assert unit.index('#include "relabel_kernels.h"') < unit.index('#include "brush_kernels.h"') < unit.index('#include "relabel.inc"') < unit.index('#include "brush.inc"')
-    for f in os.listdir(CSRC):
-        if f.endswith((".hip", ".h", ".hpp", ".inc", ".cpp")) and f != "scene_bytes.hip":
-            text = open(os.path.join(CSRC, f)).read()
-            assert '#include "brush_kernels.h"' not in text and '#include "brush.inc"' not in text, f
+def test_the_makefile_builds_the_unit_and_only_it_holds_the_kernels():
+    assert makefile_builds("brush")
+    assert only_unit_including("brush_kernels.h", "brush.hip")
+    assert scene_bytes_holds_no_part_of("brush_kernels.h")
 
 
 def test_both_kernels_have_no_scratch_128_vgprs_and_the_lds_of_table_and_tally(scene_unit):
     found = kernels(scene_unit)
     assert set(found) == {"brush_kernel", "brush_journal_kernel"}, list(scene_unit)
-    lines = ["volym_brush_kernel and volym_brush_journal_kernel (scene_bytes.hip), hipcc with the Makefile's flags, -Rpass-analysis=kernel-resource-usage",
+    lines = ["volym_brush_kernel and volym_brush_journal_kernel (brush.hip), hipcc with the Makefile's flags, -Rpass-analysis=kernel-resource-usage",
              "written by tests/test_brush_resources.py; bar for both: scratch 0, VGPRs <= 128, LDS <= %d" % LDS_BAR, ""]
     for name, r in sorted(found.items()):
         lines.append("%-22s  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (name, r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     for name, r in found.items():
         assert r["scratch"] == 0, (name, r)
         assert r["vgpr"] <= 128, (name, r)

@@ -1,17 +1,16 @@
 """What the compiler made of the kernels of the label history (no GPU: any machine with hipcc).
 
-scene_bytes.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
-tests/test_relabel_resources.py compiles it.  The four instantiations of volym_relabel_journal_kernel<IDS, DISTANCE> and
+relabel.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
+tests/test_relabel_resources.py compiles its unit.  The four instantiations of volym_relabel_journal_kernel<IDS, DISTANCE> and
 volym_label_swap_kernel must have no scratch, at most 128 VGPRs and at most 64 KB of LDS.  Only the resource remarks are read, never
 the instructions.  The figures go to profiles/label_history_kernel_resources.txt.
 """
 import os
 import re
-import subprocess
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import HIPCC, ROOT, compile_unit, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "label_history_kernel_resources.txt")
 
@@ -19,12 +18,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not 
 
 
 @pytest.fixture(scope="module")
-def scene_unit(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("label_history")), "scene_bytes.s")
-    cmd = [HIPCC] + makefile_flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", os.path.join(CSRC, "scene_bytes.hip"), "-o", out]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return remarks(p.stderr)
+def scene_unit():
+    return compile_unit("relabel")
 
 
 def kernels(res):
@@ -42,17 +37,12 @@ def kernels(res):
 def test_the_journalling_instantiations_and_the_swap_kernel_have_no_scratch_128_vgprs_and_64_kb_of_lds(scene_unit):
     found = kernels(scene_unit)
     assert len(found) == 5 and "label_swap_kernel" in found, list(scene_unit)
-    lines = ["volym_relabel_journal_kernel<IDS, DISTANCE> and volym_label_swap_kernel (scene_bytes.hip), hipcc with the Makefile's flags, "
+    lines = ["volym_relabel_journal_kernel<IDS, DISTANCE> and volym_label_swap_kernel (relabel.hip), hipcc with the Makefile's flags, "
              "-Rpass-analysis=kernel-resource-usage",
              "written by tests/test_label_history_resources.py; bar for all five: scratch 0, VGPRs <= 128, LDS <= 65536", ""]
     for name, r in sorted(found.items()):
         lines.append("%-38s  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (name, r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     for name, r in found.items():
         assert r["scratch"] == 0, (name, r)
         assert r["vgpr"] <= 128, (name, r)

@@ -6,11 +6,10 @@ have no scratch and at most 64 VGPRs: a byte test, a ballot and four integer ble
 remarks are read.  The figures go to profiles/outline_kernel_resources.txt.
 """
 import os
-import re
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_builds, makefile_flags, remarks, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "outline_kernel_resources.txt")
 KERNELS = ("volym_outline_pack_kernel", "volym_outline_blend_kernel")
@@ -29,9 +28,7 @@ def outline_unit(tmp_path_factory):
 
 
 def test_the_makefile_builds_and_links_the_unit():
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"outline\$\(SFX\)\.o:.*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c", text)
-    assert re.search(r"^\$\(OUT\):.*outline\$\(SFX\)\.o", text, re.M)
+    assert makefile_builds("outline")
 
 
 def test_both_kernels_have_no_scratch_and_at_most_64_vgprs(outline_unit):
@@ -42,12 +39,7 @@ def test_both_kernels_have_no_scratch_and_at_most_64_vgprs(outline_unit):
              "written by tests/test_outline_resources.py; bar for both: scratch 0, VGPRs <= 64", ""]
     for k, r in by_kernel.items():
         lines.append("%-27s vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (k, r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     for k, r in by_kernel.items():
         assert r["scratch"] == 0, (k, r)
         assert r["vgpr"] <= 64, (k, r)

@@ -13,7 +13,7 @@ import subprocess
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_builds, makefile_flags, remarks, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "pick_kernel_resources.txt")
 
@@ -40,9 +40,7 @@ def instantiations(res):
 
 
 def test_the_makefile_builds_and_links_the_unit():
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"pick\$\(SFX\)\.o:.*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c", text)
-    assert re.search(r"^\$\(OUT\):.*pick\$\(SFX\)\.o", text, re.M)
+    assert makefile_builds("pick")
 
 
 def test_common_instantiation_has_no_scratch_and_fits_four_waves(pick_unit):
@@ -53,12 +51,7 @@ def test_common_instantiation_has_no_scratch_and_fits_four_waves(pick_unit):
     for (brick, general), r in sorted(inst.items()):
         lines.append("pick_kernel<%-5s, %-5s>  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (
             str(brick).lower(), str(general).lower(), r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     common = inst[(False, False)]
     assert common["scratch"] == 0, common
     assert common["vgpr"] <= 128, common

@@ -10,7 +10,7 @@ import re
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_builds, makefile_flags, remarks, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "project_kernel_resources.txt")
 
@@ -38,9 +38,7 @@ def instantiations(res):
 
 
 def test_the_makefile_builds_and_links_the_unit():
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"project\$\(SFX\)\.o:.*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c", text)
-    assert re.search(r"^\$\(OUT\):.*project\$\(SFX\)\.o", text, re.M)
+    assert makefile_builds("project")
 
 
 def test_linear_instantiation_has_no_scratch_and_at_most_128_vgprs(project_unit):
@@ -51,12 +49,7 @@ def test_linear_instantiation_has_no_scratch_and_at_most_128_vgprs(project_unit)
     for brick, r in sorted(inst.items()):
         lines.append("project_kernel<%-5s>  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (
             str(brick).lower(), r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     linear = inst[False]
     assert linear["scratch"] == 0, linear
     assert linear["vgpr"] <= 128, linear

@@ -1,16 +1,15 @@
 """What the compiler made of the relabel kernel (no GPU: any machine with hipcc).
 
-scene_bytes.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
-tests/test_measure_resources.py compiles it.  The four instantiations of volym_relabel_kernel<IDS, DISTANCE> must have no scratch, at
+relabel.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
+tests/test_measure_resources.py compiles its unit.  The four instantiations of volym_relabel_kernel<IDS, DISTANCE> must have no scratch, at
 most 128 VGPRs and at most 64 KB of LDS.  The figures go to profiles/relabel_kernel_resources.txt.
 """
 import os
 import re
-import subprocess
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import HIPCC, ROOT, compile_unit, makefile_builds, only_unit_including, scene_bytes_holds_no_part_of, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "relabel_kernel_resources.txt")
 
@@ -18,12 +17,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not 
 
 
 @pytest.fixture(scope="module")
-def scene_unit(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("relabel")), "scene_bytes.s")
-    cmd = [HIPCC] + makefile_flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", os.path.join(CSRC, "scene_bytes.hip"), "-o", out]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return remarks(p.stderr)
+def scene_unit():
+    return compile_unit("relabel")
 
 
 def instantiations(res):
@@ -37,29 +32,20 @@ def instantiations(res):
 
 
 def test_the_unit_includes_the_new_header_and_no_other_unit_does():
-    assert os.path.exists(os.path.join(CSRC, "relabel_kernels.h")) and os.path.exists(os.path.join(CSRC, "relabel.inc"))
-    unit = open(os.path.join(CSRC, "scene_bytes.hip")).read()
-    assert unit.index('#include "scene_kernels.h"') < unit.index('#include "relabel_kernels.h"') < unit.index('#include "relabel.inc"')
-    others = [f for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".hpp", ".inc", ".cpp")) and f != "scene_bytes.hip"]
-    for f in others:                                                  # scene_bytes.hip stays the only unit with these kernels
-        text = open(os.path.join(CSRC, f)).read()
-        assert '#include "relabel_kernels.h"' not in text and '#include "relabel.inc"' not in text, f
+    assert makefile_builds("relabel")
+    assert only_unit_including("relabel_kernels.h", "relabel.hip")
+    assert scene_bytes_holds_no_part_of("relabel_kernels.h")
 
 
 def test_the_four_instantiations_have_no_scratch_128_vgprs_and_64_kb_of_lds(scene_unit):
     inst = instantiations(scene_unit)
     assert set(inst) == {(False, False), (False, True), (True, False), (True, True)}, list(scene_unit)
-    lines = ["volym_relabel_kernel<IDS, DISTANCE> (scene_bytes.hip), hipcc with the Makefile's flags, -Rpass-analysis=kernel-resource-usage",
+    lines = ["volym_relabel_kernel<IDS, DISTANCE> (relabel.hip), hipcc with the Makefile's flags, -Rpass-analysis=kernel-resource-usage",
              "written by tests/test_relabel_resources.py; bar for all four: scratch 0, VGPRs <= 128, LDS <= 65536", ""]
     for (ids, distance), r in sorted(inst.items()):
         lines.append("relabel_kernel<%-5s, %-5s>  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (
             str(ids).lower(), str(distance).lower(), r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     for key, r in inst.items():
         assert r["scratch"] == 0, (key, r)
         assert r["vgpr"] <= 128, (key, r)

@@ -13,7 +13,7 @@ import subprocess
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_builds, makefile_flags, remarks, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "slice_kernel_resources.txt")
 
@@ -40,9 +40,7 @@ def instantiations(res):
 
 
 def test_the_makefile_builds_and_links_the_unit():
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"slice\$\(SFX\)\.o:.*\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c", text)
-    assert re.search(r"^\$\(OUT\):.*slice\$\(SFX\)\.o", text, re.M)
+    assert makefile_builds("slice")
 
 
 def test_every_instantiation_has_no_scratch_and_at_most_64_vgprs(slice_unit):
@@ -54,12 +52,7 @@ def test_every_instantiation_has_no_scratch_and_at_most_64_vgprs(slice_unit):
     for brick, r in sorted(inst.items()):
         lines.append("slice_kernel<%-5s>  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (
             str(brick).lower(), r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     for brick, r in inst.items():
         assert r["scratch"] == 0, (brick, r)
         assert r["vgpr"] <= 64, (brick, r)

@@ -1,17 +1,16 @@
 """What the compiler made of the surface kernels (no GPU: any machine with hipcc).
 
 surface.hip is compiled device-only with the Makefile's own flags and -Rpass-analysis=kernel-resource-usage, as
-tests/test_measure_resources.py compiles scene_bytes.hip.  Every instantiation of volym_surface_count_kernel<LABELS> and
+tests/test_measure_resources.py compiles measure.hip.  Every instantiation of volym_surface_count_kernel<LABELS> and
 volym_surface_emit_kernel<LABELS>, and the init kernel, must have no scratch, at most 128 VGPRs and at most 64 KB of LDS (the scan of
 the row counts is box_pass.hip's: tests/test_box_pass_resources.py).  The figures go to profiles/surface_kernel_resources.txt.
 """
 import os
 import re
-import subprocess
 
 import pytest
 
-from tests.kernel_listing import CSRC, HIPCC, ROOT, makefile_flags, remarks
+from tests.kernel_listing import CSRC, HIPCC, ROOT, compile_unit, makefile_builds, write_figures
 
 OUT = os.path.join(ROOT, "profiles", "surface_kernel_resources.txt")
 
@@ -19,12 +18,8 @@ pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc is not 
 
 
 @pytest.fixture(scope="module")
-def surface_unit(tmp_path_factory):
-    out = os.path.join(str(tmp_path_factory.mktemp("surface")), "surface.s")
-    cmd = [HIPCC] + makefile_flags() + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-S", os.path.join(CSRC, "surface.hip"), "-o", out]
-    p = subprocess.run(cmd, capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr[-2000:]
-    return remarks(p.stderr)
+def surface_unit():
+    return compile_unit("surface")
 
 
 def kernels(res):
@@ -42,11 +37,7 @@ def kernels(res):
 
 
 def test_the_makefile_builds_the_unit_and_only_it_holds_the_kernels():
-    text = open(os.path.join(CSRC, "Makefile")).read()
-    rule = re.search(r"^\$\(HERE\)surface\$\(SFX\)\.o:(.*)\n\t\$\(HIPCC\) \$\(HIPFLAGS\) -c", text, re.M)
-    assert rule and "$(HDRS)" in rule.group(1)
-    link = re.search(r"^\$\(OUT\):(.*)$", text, re.M).group(1)
-    assert "$(HERE)surface$(SFX).o" in link
+    assert makefile_builds("surface")
     for f in os.listdir(CSRC):
         if f.endswith((".hip", ".h", ".hpp", ".inc", ".cpp")) and f != "surface.hip":
             assert '#include "surface_kernels.h"' not in open(os.path.join(CSRC, f)).read(), f
@@ -59,12 +50,7 @@ def test_every_kernel_has_no_scratch_128_vgprs_and_64_kb_of_lds(surface_unit):
              "written by tests/test_surface_resources.py; bar for all: scratch 0, VGPRs <= 128, LDS <= 65536", ""]
     for name, r in sorted(found.items()):
         lines.append("surface %-13s  vgpr %3d  sgpr %3d  scratch %4d  occupancy %d  lds %5d" % (name, r["vgpr"], r["sgpr"], r["scratch"], r["occ"], r["lds"]))
-    print("\n".join(lines))
-    try:
-        with open(OUT, "w") as f:
-            f.write("\n".join(lines) + "\n")
-    except OSError:
-        pass                                  # a read-only checkout still checks the bar
+    write_figures(OUT, lines)
     for name, r in found.items():
         assert r["scratch"] == 0, (name, r)
         assert r["vgpr"] <= 128, (name, r)

@@ -1,9 +1,18 @@
-// The brush (volym_brush_labels, volym_brush_check, volym_brush_box): included at the end of scene_bytes.hip AFTER relabel.inc, which
-// this file does not include itself and whose edit it is a form of: the transition, the launch and the segments' stay on the device
-// are that file's.  Here: the request's checks, the stroke's box and segments, and the rule the kernels of brush_kernels.h read.  A
-// blocking set-up call like that edit.
+// libvolym_hip.so: the brush (volym_brush_labels, volym_brush_check, volym_brush_box) beside the kernels it launches (brush_kernels.h).
+// A form of relabel.hip's edit: the transition, the launch and the segments' stay on the device are label_edit.hpp's.  Here: the request's
+// checks, the stroke's box and segments, and the rule the kernels read.  A blocking set-up call like that edit.
+#include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
+
+#include "label_edit.hpp"
+#include "brush_kernels.h"
+
+using namespace volym;
+
+static int fail(volym_ctx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
+#define HIPCHK(ctx, expr) VOLYM_HIPCHK(ctx, expr)
 
 static_assert(sizeof(volym_brush_point) == 8 && offsetof(volym_brush_point, flags) == 6, "volym_brush_point has no padding");
 static_assert(sizeof(volym_brush) == 2360 && offsetof(volym_brush, flags) == 24 && offsetof(volym_brush, to) == 36 && offsetof(volym_brush, weight) == 292 &&

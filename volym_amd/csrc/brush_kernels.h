@@ -1,14 +1,13 @@
 // The kernel of the brush (volym_brush_labels): the label edit whose texels are decided by geometry, not by a snapshot.  Included by
-// scene_bytes.hip alone, AFTER relabel_kernels.h, which this header does not include itself (scene_bytes.hip stays the one place
-// that does).  Everything but the selection rule is that header's: the walk (wave_chunk_step), the tail (selected_chunk_tail), the
+// brush.hip alone.  Everything but the selection rule is edit_chunks.h's: the walk (wave_chunk_step), the tail (selected_chunk_tail), the
 // prologue, the tally and the journal.  Here: the segment, the rule of one texel against it, and the mask of a chunk.
 #pragma once
 
-#include "scene_kernels.h"
+#include "edit_chunks.h"
 
 namespace volym {
 
-// One segment of the stroke as the host lays it out (brush.inc): its end points (a == b: a ball), the box of texels that can lie
+// One segment of the stroke as the host lays it out (brush.hip): its end points (a == b: a ball), the box of texels that can lie
 // within it (the end points' box grown by the brush's reach per axis and clipped to the volume; hi INCLUSIVE), <d,d> and r2 * <d,d>.
 // 64 bytes, read by the uniform loop index: one scalar load per segment and wave, no vector register holds any of it.
 struct BrushSegment {
@@ -48,7 +47,7 @@ __device__ __forceinline__ bool brush_within(const BrushSegment& g, const BrushR
 }
 
 // One pass over the items of slab s (make_crop_slab over the request's box cut to the stroke's hull, s.box_lo/hi that box, no plane),
-// in either layout: the walk and the tail of relabel_kernels.h (wave_chunk_step, selected_chunk_tail) around the brush's selection
+// in either layout: the walk and the tail of edit_chunks.h (wave_chunk_step, selected_chunk_tail) around the brush's selection
 // rule, the 16-bit mask of the chunk's texels that lie within some segment -- their union, so every texel is decided once.  Three
 // levels of cull: the wave's box is held against each segment's box first, and a segment that misses it is skipped by a uniform
 // branch; then the lane's chunk box against the segment's; then each texel against it, and only then the 64-bit test.

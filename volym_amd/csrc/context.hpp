@@ -2,9 +2,11 @@
 // logic that more than one translation unit needs.  The units, each with the C ABI of what it holds:
 //   raymarch.hip      the frame loop, the cost-feedback thread and the capture that feeds it; mgpu.inc, the native multi-GPU loop,
 //                     is included in it
-//   scene_bytes.hip   the bytes of the scene, the measure pass over them and the label edits
-//   pick.hip, outline.hip, slice.hip, project.hip, surface.hip, components.hip, distance.hip
+//   scene_bytes.hip   the bytes of the scene; the seam in front of it for the two groups below is scene_bytes.hpp
+//   pick.hip, outline.hip, slice.hip, project.hip, measure.hip, surface.hip, components.hip, distance.hip
 //                     the pass of that name
+//   relabel.hip, brush.hip, lasso.hip, smooth.hip
+//                     the label edit of that name (relabel.hip: and the history); what they share on the host is label_edit.hpp
 //   box_pass.hip      no ABI: what the passes over a request's box share -- the scan of row counts into offsets and the read-back
 //                     of a box-linear volume
 // The work-list scheduler that the feedback thread runs is worklist.hpp / worklist.cpp: host only, it knows nothing of this header.
@@ -237,7 +239,7 @@ struct volym_ctx {
     uint32_t projection_image_w = 0, projection_image_h = 0;            // ... and into projection_image
     volym::OwnedBuffer<volym_projection> projection_at;                 // the one record of volym_project_at, reserved once
 
-    // measure passes (volym_measure_pass, scene_bytes.hip): one result, reserved once; count 1: a pass has written it since the latest
+    // measure passes (volym_measure_pass, measure.hip): one result, reserved once; count 1: a pass has written it since the latest
     // volym_set_volume
     volym::OwnedBuffer<volym_measurement> measure;
 
@@ -269,7 +271,7 @@ struct volym_ctx {
     volym::OwnedBuffer<unsigned long long> distance_keys;   // the working summary: counters and 64-bit (D, index) keys, packed into `distance`
     uint32_t distance_box[6] = {};           // the box of the latest pass (the reads address the map by it)
 
-    // the history of label edits (volym_label_history, relabel.inc): off (budget 0) in a new context
+    // the history of label edits (volym_label_history, relabel.hip): off (budget 0) in a new context
     struct LabelStep {
         uint32_t* index = nullptr;           // the chunks the edit stored ...
         uint4* old = nullptr;                // ... and the 16 bytes each held on the other side of the step
@@ -282,10 +284,10 @@ struct volym_ctx {
     uint64_t history_used = 0;               // 20 * records over history_steps
     uint64_t history_dropped = 0, history_lost = 0;
     volym::OwnedBuffer<uint32_t> journal_index;   // where an edit journals: room for the worst case of its slab within the budget
-                                                  // (and where the smoothing's vote leaves its records, history on or off: smooth.inc)
+                                                  // (and where the smoothing's vote leaves its records, history on or off: smooth.hip)
     volym::OwnedBuffer<uint4> journal_old;
 
-    // the lasso (volym_lasso_labels, lasso.inc): the polygon's bit plane of the latest call over lasso_rect; count: its words
+    // the lasso (volym_lasso_labels, lasso.hip): the polygon's bit plane of the latest call over lasso_rect; count: its words
     volym::OwnedBuffer<uint32_t> lasso_plane;
     uint32_t lasso_rect[4] = {};
     bool lasso_have = false;                 // a call has passed its checks: volym_read_lasso_mask has something to read
@@ -342,7 +344,7 @@ void free_outline(volym_ctx* c);
 void free_slice(volym_ctx* c);
 // project.hip: what the context keeps for the projection pass (every stream idle)
 void free_projection(volym_ctx* c);
-// scene_bytes.hip: what the context keeps for the measure pass (every stream idle)
+// measure.hip: what the context keeps for the measure pass (every stream idle)
 void free_measure(volym_ctx* c);
 // surface.hip: what the context keeps for the surface passes (every stream idle)
 void free_surface(volym_ctx* c);
@@ -350,11 +352,11 @@ void free_surface(volym_ctx* c);
 void free_components(volym_ctx* c);
 // distance.hip: what the context keeps for the distance pass (every stream idle)
 void free_distance(volym_ctx* c);
-// scene_bytes.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
+// relabel.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
 void clear_label_history(volym_ctx* c);
-// scene_bytes.hip: the steps and the staging area of the label history (every stream idle)
+// relabel.hip: the steps and the staging area of the label history (every stream idle)
 void free_label_history(volym_ctx* c);
-// scene_bytes.hip: what the context keeps of the latest lasso (every stream idle)
+// lasso.hip: what the context keeps of the latest lasso (every stream idle)
 void free_lasso(volym_ctx* c);
 // scene_bytes.hip: macro-cell maxima of d_vol for mc_n, their host copy and the occupied-cell boxes, and the fine maxima (sets have_vol)
 int build_macro_cells(volym_ctx* c);

@@ -1,8 +1,18 @@
-// The lasso (volym_lasso_labels, volym_lasso_check, volym_lasso_rect, volym_read_lasso_mask): included at the end of scene_bytes.hip
-// AFTER relabel.inc and brush.inc, neither of which this file includes itself.  It is a form of relabel.inc's edit: the transition,
-// the launch and the edges' stay on the device are that file's.  Here: the request's checks, the mask's rect and plane, and the rule
-// the kernels of lasso_kernels.h read.  A blocking set-up call like that edit.  The view's builder (volym_lasso_view_from_camera) is
-// host arithmetic in scene.cpp.
+// libvolym_hip.so: the lasso (volym_lasso_labels, volym_lasso_check, volym_lasso_rect, volym_read_lasso_mask) beside the kernels it
+// launches (lasso_kernels.h).  A form of relabel.hip's edit: the transition, the launch and the edges' stay on the device are
+// label_edit.hpp's.  Here: the request's checks, the mask's rect and plane, and the rule the kernels read.  A blocking set-up call like
+// that edit.  The view's builder (volym_lasso_view_from_camera) is host arithmetic in scene.cpp.
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+
+#include "label_edit.hpp"
+#include "lasso_kernels.h"
+
+using namespace volym;
+
+static int fail(volym_ctx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
+#define HIPCHK(ctx, expr) VOLYM_HIPCHK(ctx, expr)
 
 static_assert(sizeof(volym_lasso_view) == 88 && offsetof(volym_lasso_view, width) == 36 && offsetof(volym_lasso_view, height) == 40 &&
               offsetof(volym_lasso_view, scale_log2) == 44 && offsetof(volym_lasso_view, c) == 48 && offsetof(volym_lasso_view, depth) == 72, "volym_lasso_view has no padding");

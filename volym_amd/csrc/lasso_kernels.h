@@ -1,15 +1,14 @@
 // The kernels of the lasso (volym_lasso_labels): the label edit whose texels are decided by where they project.  Included by
-// scene_bytes.hip alone, AFTER relabel_kernels.h and brush_kernels.h, which this header does not include itself (scene_bytes.hip stays
-// the one place that does).  Everything of the edit kernel but the selection rule is relabel_kernels.h's: the walk (wave_chunk_step),
+// lasso.hip alone (volym_lasso_raster_kernel is no template).  Everything of the edit kernel but the selection rule is edit_chunks.h's: the walk (wave_chunk_step),
 // the tail (selected_chunk_tail), the prologue, the tally and the journal.  Here: the polygon's bit plane, the integer view, the
 // half-space cull and the mask of a chunk.
 #pragma once
 
-#include "scene_kernels.h"
+#include "edit_chunks.h"
 
 namespace volym {
 
-// One edge of the polygon, vertex i -> vertex (i + 1) % n, as the host lays it out (lasso.inc).  16 bytes, read by the uniform loop
+// One edge of the polygon, vertex i -> vertex (i + 1) % n, as the host lays it out (lasso.hip).  16 bytes, read by the uniform loop
 // index: one scalar load per edge and wave.
 struct LassoEdge { int32_t x0, y0, x1, y1; };
 static_assert(sizeof(LassoEdge) == 16, "LassoEdge is 16 bytes");
@@ -120,7 +119,7 @@ __device__ __forceinline__ bool lasso_inside(const LassoRule& v, const uint32_t*
 }
 
 // One pass over the items of slab s (make_crop_slab over the request's box, s.box_lo/hi that box, no plane), in either layout: the
-// walk and the tail of relabel_kernels.h (wave_chunk_step, selected_chunk_tail) around the lasso's selection rule, the 16-bit mask of
+// walk and the tail of edit_chunks.h (wave_chunk_step, selected_chunk_tail) around the lasso's selection rule, the 16-bit mask of
 // the chunk's texels that are inside (OUTSIDE: that are not).  The box of the wave's 64 chunks is held against the six half-spaces
 // first: if it misses, the wave goes on (or, OUTSIDE, selects all it keeps) without a mask read.  Then the lane's own chunk box, then
 // each texel: X, Y and D advance by constants along the chunk, beside the coordinates, in a loop of this pass's own.

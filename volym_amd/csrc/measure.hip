@@ -1,9 +1,20 @@
-// The measure pass (volym_measure_pass, volym_read_measure, volym_measure_device_ptr, volym_measure_check): included at the end of
-// scene_bytes.hip, beside the kernels it launches (measure_kernels.h) and the walk it shares with the rewrites (make_crop_slab,
-// stream_grid).  Unlike everything above it in that unit the pass is enqueue-only: it reads the scene's bytes and writes the
-// context's own 36 KB result, on slot 0's stream.
+// libvolym_hip.so: the measure pass (volym_measure_pass, volym_read_measure, volym_measure_device_ptr, volym_measure_check) beside the
+// kernels it launches (measure_kernels.h).  It only reads the scene's bytes, over the walk it shares with the rewrites (scene_bytes.hpp:
+// make_crop_slab, stream_grid), and is enqueue-only on slot 0's stream: it writes the context's own 36 KB result.
+#include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
+#include <cstring>
+#include <string>
+
+#include "scene_bytes.hpp"
+#include "measure_kernels.h"
+
+using namespace volym;
+
+static int fail(volym_ctx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
+#define HIPCHK(ctx, expr) VOLYM_HIPCHK(ctx, expr)
 
 static_assert(sizeof(volym_measure) == 284 && offsetof(volym_measure, flags) == 24 && offsetof(volym_measure, group) == 28, "volym_measure has no padding");
 static_assert(sizeof(volym_segment_stats) == 80 && offsetof(volym_segment_stats, box) == 48 && offsetof(volym_segment_stats, min) == 72 &&

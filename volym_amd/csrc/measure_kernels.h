@@ -1,9 +1,8 @@
 // The kernels of the measure pass (volym_measure_pass): per-label statistics and grouped density histograms of the scene under its
-// cuts.  Included by scene_bytes.hip alone, after scene_kernels.h, whose chunk walk (CropSlab, crop_chunk) it reads; nothing in
-// that header changes.
+// cuts.  Included by measure.hip alone; the chunk walk it reads (CropSlab, crop_chunk) is scene_chunks.h's.
 #pragma once
 
-#include "scene_kernels.h"
+#include "scene_chunks.h"
 
 namespace volym {
 
@@ -47,7 +46,7 @@ __device__ __forceinline__ uint32_t measure_own_run(const CropSlab& s, uint32_t 
 // LDS word.  After the barrier thread l adds the workgroup's record of label l and the bins b = l of every group to the global
 // result.  All sums are integers: the result does not depend on arrival order.
 //
-// Widths.  The host launches at least ceil(n_items / (256 * MEASURE_ITEMS_PER_LANE)) workgroups (measure.inc), so a lane walks at
+// Widths.  The host launches at least ceil(n_items / (256 * MEASURE_ITEMS_PER_LANE)) workgroups (measure.hip), so a lane walks at
 // most MEASURE_ITEMS_PER_LANE = 4096 items of at most 16 texels: 2^16 texels.
 //   lane, u32:       count <= 2^16; sum <= 2^16 * 255 < 2^24; sum_sq <= 2^16 * 65025 = 4 261 478 400 < 2^32;
 //                    coordinate sums <= 2^16 * 4095 < 2^28.

@@ -1,12 +1,18 @@
-// The label edit (volym_edit_labels, volym_relabel_check, volym_read_labels): included at the end of scene_bytes.hip, beside the
-// kernels it launches (relabel_kernels.h) and the transition whose pieces it is built from (rewrite, ensure_uncropped_copies,
-// refresh_macro_cells, scan_label_stats), and its history (volym_label_history, volym_undo_labels, volym_redo_labels,
-// volym_label_history_info).  Blocking set-up calls like the other edits of that unit.  brush.inc and lasso.inc, included after this
-// file, build their edits on what is here: editable_state, LabelEdit and edit_labels (the transition, with the kernel as a parameter),
-// and the three things every launch site needs: edit_density, launch_edit and CallArray.
-// smooth.inc, the edit in two phases, takes the pieces instead: editable_state, DeviceRelabelResult, edit_density, record_step, follow_labels.
+// libvolym_hip.so: the label edit (volym_edit_labels, volym_relabel_check, volym_read_labels) beside the kernels it launches
+// (relabel_kernels.h), its history (volym_label_history, volym_undo_labels, volym_redo_labels, volym_label_history_info), and the
+// pieces of the edit's transition that label_edit.hpp declares for this unit, brush.hip, lasso.hip and smooth.hip.  Blocking set-up
+// calls, like the other edits of the scene's bytes.
+#include <hip/hip_runtime.h>
 
 #include <cstddef>
+
+#include "label_edit.hpp"
+#include "relabel_kernels.h"
+
+using namespace volym;
+
+static int fail(volym_ctx* c, int code, const std::string& msg) { return ctx_fail(c, code, msg); }
+#define HIPCHK(ctx, expr) VOLYM_HIPCHK(ctx, expr)
 
 static_assert(sizeof(volym_relabel) == 308 && offsetof(volym_relabel, flags) == 24 && offsetof(volym_relabel, to) == 36 && offsetof(volym_relabel, id_lo) == 292 &&
               offsetof(volym_relabel, d2_lo) == 300, "volym_relabel has no padding");
@@ -17,41 +23,10 @@ static_assert(sizeof(struct volym_label_history_info) == 56 && offsetof(struct v
               offsetof(struct volym_label_history_info, next_undo_records) == 24 && offsetof(struct volym_label_history_info, lost) == 48,
               "volym_label_history_info has no padding");
 
-// What follows a change of labels under a (box, plane, mask) that stays -- an edit, an undo, a redo -- once the labels are stored and
-// `res` names the labels that left and arrived and the hull of the changed texels (changed != 0).
-// Precondition: density and importances held the invariant of context.hpp for the labels as they were.  Postcondition: they hold it
-// for the labels as they are, label_count and label_box describe those, and everything derived from the bytes is up to date.
-static int follow_labels(volym_ctx* c, const volym_relabel_result& res, const char* who)
-{
-    // counts and boxes first: mask_active and volym_visibility_boxes read them
-    const hipError_t es = scan_label_stats(c);
-    if (es != hipSuccess) return fail(c, VOLYM_E_HIP, std::string(who) + " (label statistics): " + hipGetErrorString(es));
-    ++c->scene_serial;                                                    // labels changed: a surface pass is stale
-    // A texel's bytes differ from the rule's only where its old and its new label differ in what they give: visibility for the
-    // density, visibility and the table's byte for importances mapped from the labels.  Every such texel carries a label that
-    // arrived, inside the result's box: the visibility kernel stores the chunks that hold one, whole, by the rule.
-    uint8_t flipped[256];
-    bool hidden_moved = false;
-    for (int l = 0; l < 256; ++l) {
-        flipped[l] = res.left[l] != 0u || res.arrived[l] != 0u;
-        hidden_moved = hidden_moved || (flipped[l] && c->seg_hidden[l]);
-    }
-    int rc = VOLYM_OK;
-    if (hidden_moved) rc = rewrite(c, density_of(c), res.box, flipped, nullptr);
-    if (rc == VOLYM_OK && imp_croppable(c) && (imp_from_labels(c) || hidden_moved)) rc = rewrite(c, importances_of(c), res.box, flipped, nullptr);
-    if (rc == VOLYM_OK && hidden_moved) rc = refresh_macro_cells(c, &res.box, 1u);
-    if (rc != VOLYM_OK) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));                   // every slot's next frame reads the new bytes
-    if (imp_from_labels(c)) segment_important_box(c);
-    crop_important_box(c);
-    return rebuild_lists(c);
-}
-
 // ---- the history of label edits (volym_label_history, volym_undo_labels, volym_redo_labels) ----------------------------------------
-// A step is what one edit destroyed: the chunks it stored, with the bytes they held (relabel_kernels.h LabelJournal), in device
+// A step is what one edit destroyed: the chunks it stored, with the bytes they held (edit_chunks.h LabelJournal), in device
 // memory of its own, sized by its records.  Undo and redo swap a step with the labels (volym_label_swap_kernel) and take the edit's
 // follow-up.  scene.LabelHistory of the Python package is the twin of the bookkeeping below, equal in every field of the info.
-static const uint64_t JOURNAL_RECORD_BYTES = 20u;          // a chunk index and 16 bytes
 
 static void free_step(volym_ctx::LabelStep& s) { (void)hipFree(s.index); (void)hipFree(s.old); s = volym_ctx::LabelStep{}; }
 
@@ -97,7 +72,7 @@ void free_label_history(volym_ctx* c)
 // The journal of the edit that has just stored (records > 0 of them counted, the first min(records, capacity) in the staging area)
 // becomes the newest step, in memory of its own, and every redo step goes.  A journal that ran past its capacity, or one there is no
 // memory for, has a gap: undoing older steps across it would be wrong, so the whole history is given up and `lost` counts it.
-static void record_step(volym_ctx* c, const volym_relabel_result& res, uint64_t records, uint64_t capacity)
+void volym::record_step(volym_ctx* c, const volym_relabel_result& res, uint64_t records, uint64_t capacity)
 {
     drop_steps(c, c->history_cursor, c->history_steps.size());
     volym_ctx::LabelStep step;
@@ -124,126 +99,49 @@ static void record_step(volym_ctx* c, const volym_relabel_result& res, uint64_t 
     fit_history(c);
 }
 
-// the working result of an edit, an undo or a redo in device memory: the result, then the journal's counter
-struct DeviceRelabelResult { volym_relabel_result result; uint32_t records, pad; };
+// ---- the pieces of an edit's transition (label_edit.hpp) -------------------------------------------------------------------------------
 
-// What the edit's transition needs to know of a request, whichever kernel carries it out (volym_edit_labels here, the brush of
-// brush.inc): the box its kernel walks and keeps to, the table, DRY_RUN, and the name errors carry.
-struct LabelEdit {
-    const uint32_t* box;
-    const uint8_t* to;
-    bool dry;
-    const char* who;
-};
-
-// The edit's own transition, the counterpart of retarget for a change of labels under a (box, plane, mask) that stays (follow_labels).
-// launch(stream, grid, out, to, slab, items, journal) enqueues the request's kernel over the slab of r.box (keep = inside that box);
-// journal is NULL unless the history is on and the request is no DRY_RUN.  With no texel changed (or DRY_RUN) nothing but the result is
-// written.  A failure after the kernel has stored leaves bytes that belong to neither state: the context then asks for
-// volym_set_volume again, as after a failed retarget.
-template <class Launch>
-static int edit_labels(volym_ctx* c, const LabelEdit& r, volym_relabel_result& res, Launch launch)
+int volym::begin_edit(volym_ctx* c, const uint8_t receives[256])
 {
-    const bool dry = r.dry;
-    const bool journalled = c->history_budget != 0u && !dry;
-    std::memset(&res, 0, sizeof res);
-    for (int a = 0; a < 3; ++a) if (r.box[a] == r.box[3 + a]) return VOLYM_OK;        // an empty box: nothing to walk
-
     int rc = quiesce_slots(c);
     if (rc != VOLYM_OK) return rc;
-    // A hidden label that has voxels has made the uncut copies already; one without voxels has not (retarget takes the idle path for
-    // it), and texels are about to move into it.  The bytes are still uncut then: the precondition of ensure_uncropped_copies.
     bool hidden_target = false;
-    for (int l = 0; l < 256; ++l) hidden_target = hidden_target || (r.to[l] != l && c->seg_hidden[r.to[l]]);
-    if (hidden_target || mask_active(c)) {
-        rc = ensure_uncropped_copies(c, true);                            // in stream order in front of the kernel and the rewrites
-        if (rc != VOLYM_OK) return rc;
-    }
-
-    const hipStream_t stream = c->slot0().stream;
-    CropSlab s;
-    const uint64_t items = make_crop_slab(c, c->bricked, r.box, nullptr, s);
-    // the staging area holds the slab's worst case, one record per item, or what the budget holds: past that the kernel only counts
-    const uint64_t capacity = journalled ? std::min<uint64_t>(items, c->history_budget / JOURNAL_RECORD_BYTES) : 0u;
-    if (journalled) {
-        rc = c->journal_index.reserve(c, stream, capacity, "label journal");
-        if (rc == VOLYM_OK) rc = c->journal_old.reserve(c, stream, capacity, "label journal");
-        if (rc != VOLYM_OK) return rc;
-    }
-    DeviceRelabelResult init = {}, back = {};
-    for (int a = 0; a < 3; ++a) init.result.box[a] = 0xffffffffu;         // lo = max, hi = 0: the kernel keeps INCLUSIVE maxima
-    DeviceRelabelResult* d_res = nullptr;
-    hipError_t e = hipMalloc(&d_res, sizeof init);
-    if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(relabel result): ") + hipGetErrorString(e));
-    e = hipMemcpyAsync(d_res, &init, sizeof init, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        // keep = inside the request's box, whatever the crop box and the plane are: the cuts are in the bytes the window reads
-        for (int a = 0; a < 3; ++a) { s.box_lo[a] = r.box[a]; s.box_hi[a] = r.box[3 + a]; }
-        s.planes = 0u; s.pn[0] = s.pn[1] = s.pn[2] = s.pd = 0;
-        LabelTable to;
-        std::memcpy(to.v, r.to, 256);
-        volym_relabel_result* const dr = &d_res->result;
-        const RelabelOut out = {reinterpret_cast<unsigned long long*>(&dr->changed), reinterpret_cast<unsigned long long*>(dr->left),
-                                reinterpret_cast<unsigned long long*>(dr->arrived), dr->box};
-        const LabelJournal journal = {c->journal_index.ptr, c->journal_old.ptr, &d_res->records, static_cast<uint32_t>(capacity)};
-        launch(stream, dim3(stream_grid(c, items)), out, to, s, static_cast<uint32_t>(items), journalled ? &journal : nullptr);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&back, d_res, sizeof back, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_res);
-    if (e != hipSuccess) {
-        if (!dry) c->have_vol = c->have_frame = false;                    // (the kernel may have stored)
-        return fail(c, VOLYM_E_HIP, std::string(r.who) + ": " + hipGetErrorString(e));
-    }
-    res = back.result;
-    if (res.changed == 0u) { std::memset(res.box, 0, sizeof res.box); return VOLYM_OK; }
-    for (int a = 3; a < 6; ++a) ++res.box[a];                             // hi exclusive
-    if (dry) return VOLYM_OK;
-
-    if (journalled) record_step(c, res, back.records, capacity);
-    rc = follow_labels(c, res, r.who);
-    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
+    for (int l = 0; l < 256; ++l) hidden_target = hidden_target || (receives[l] && c->seg_hidden[l]);
+    if (hidden_target || mask_active(c)) rc = ensure_uncropped_copies(c, true);
     return rc;
 }
 
-// the density an edit's window reads: the uncut copy with UNCUT, where there is one (call it after ensure_uncropped_copies: inside launch)
-static const uint4* edit_density(const volym_ctx* c, bool uncut) { return reinterpret_cast<const uint4*>(uncut && c->d_vol0 ? c->d_vol0 : c->d_vol); }
-
-// What edit_labels' launch does with what it is handed, for a pair of kernels (plain, journalling) that differ in the journal argument
-// alone: the labels first, then `front` (what the kernel reads beside them), the result, the table, the slab and the rule, the journal
-// where there is one, and the volume's shape.
-template <class Plain, class Journalling, class Rule, class... Front>
-static void launch_edit(const volym_ctx* c, Plain plain, Journalling journalling, hipStream_t stream, dim3 grid, const RelabelOut& out, const LabelTable& to,
-                        const CropSlab& s, const Rule& rule, uint32_t items, const LabelJournal* journal, Front... front)
+uint64_t volym::edit_slab(const volym_ctx* c, const uint32_t box[6], CropSlab& s)
 {
-    uint4* const labels = reinterpret_cast<uint4*>(c->d_labels);
-    const uint32_t bricked = c->bricked ? 1u : 0u;
-    if (journal) hipLaunchKernelGGL(journalling, grid, dim3(256), 0, stream, labels, front..., out, to, s, rule, *journal, c->nx, c->ny, c->nz, bricked, items);
-    else hipLaunchKernelGGL(plain, grid, dim3(256), 0, stream, labels, front..., out, to, s, rule, c->nx, c->ny, c->nz, bricked, items);
+    const uint64_t items = make_crop_slab(c, c->bricked, box, nullptr, s);
+    for (int a = 0; a < 3; ++a) { s.box_lo[a] = box[a]; s.box_hi[a] = box[3 + a]; }
+    s.planes = 0u; s.pn[0] = s.pn[1] = s.pn[2] = s.pd = 0;
+    return items;
 }
 
-// A small host array on the device for the length of one call (the brush's segments, the lasso's edges): copied on `stream`, in
-// stream order in front of the call's kernels, and freed when the call returns, once the stream is idle (after a refusal the copy or a
-// kernel may still run).
-template <class T>
-struct CallArray {
-    T* ptr = nullptr;
-    hipStream_t stream = nullptr;
+int volym::reserve_journal(volym_ctx* c, hipStream_t stream, uint64_t capacity)
+{
+    const int rc = c->journal_index.reserve(c, stream, capacity, "label journal");
+    return rc == VOLYM_OK ? c->journal_old.reserve(c, stream, capacity, "label journal") : rc;
+}
 
-    // VOLYM_E_NOMEM "hipMalloc(<what>): <hip error>", or VOLYM_E_HIP "<who>: <hip error>" for the copy
-    int upload(volym_ctx* c, hipStream_t on, const std::vector<T>& host, const char* what, const char* who)
-    {
-        stream = on;
-        hipError_t e = hipMalloc(&ptr, host.size() * sizeof(T));
-        if (e != hipSuccess) { ptr = nullptr; return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(") + what + "): " + hipGetErrorString(e)); }
-        e = hipMemcpyAsync(ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice, stream);
-        return e == hipSuccess ? VOLYM_OK : fail(c, VOLYM_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    CallArray() = default;
-    CallArray(const CallArray&) = delete;
-    ~CallArray() { if (ptr) { (void)hipStreamSynchronize(stream); (void)hipFree(ptr); } }
-};
+hipError_t volym::launch_label_swap(const volym_ctx* c, hipStream_t stream, const uint32_t* index, uint4* old, uint64_t records, const RelabelOut& out)
+{
+    hipLaunchKernelGGL(volym_label_swap_kernel, dim3(stream_grid(c, records)), dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), index, old, out, c->nx,
+                       c->ny, c->bricked ? 1u : 0u, static_cast<uint32_t>(records));
+    return hipGetLastError();
+}
+
+int volym::finish_edit(volym_ctx* c, volym_relabel_result& res, bool dry, bool journalled, uint64_t records, uint64_t capacity, const char* who)
+{
+    if (res.changed == 0u) { std::memset(res.box, 0, sizeof res.box); return VOLYM_OK; }
+    for (int a = 3; a < 6; ++a) ++res.box[a];                             // hi exclusive
+    if (dry) return VOLYM_OK;
+    if (journalled) record_step(c, res, records, capacity);
+    const int rc = follow_labels(c, res, who);
+    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
+    return rc;
+}
 
 // volym_edit_labels' request as an edit: the relabel kernel of its flags, plain or journalling
 static int relabel_labels(volym_ctx* c, const volym_relabel* r, volym_relabel_result& res)
@@ -277,48 +175,31 @@ static int swap_step(volym_ctx* c, bool redo, volym_relabel_result& res, const c
 {
     volym_ctx::LabelStep& step = c->history_steps[redo ? c->history_cursor : c->history_cursor - 1u];
     std::memset(&res, 0, sizeof res);
-    int rc = quiesce_slots(c);
-    if (rc != VOLYM_OK) return rc;
     const uint64_t* arrives = redo ? step.result.arrived : step.result.left;
-    bool hidden_target = false;
-    for (int l = 0; l < 256; ++l) hidden_target = hidden_target || (arrives[l] != 0u && c->seg_hidden[l]);
-    if (hidden_target || mask_active(c)) {
-        rc = ensure_uncropped_copies(c, true);
+    uint8_t receives[256];
+    for (int l = 0; l < 256; ++l) receives[l] = arrives[l] != 0u;
+    int rc = begin_edit(c, receives);
+    if (rc != VOLYM_OK) return rc;
+    {
+        DeviceResult d;
+        rc = d.alloc(c, c->slot0().stream);
         if (rc != VOLYM_OK) return rc;
-    }
-    const hipStream_t stream = c->slot0().stream;
-    volym_relabel_result init = {};
-    for (int a = 0; a < 3; ++a) init.box[a] = 0xffffffffu;
-    volym_relabel_result* d_res = nullptr;
-    hipError_t e = hipMalloc(&d_res, sizeof init);
-    if (e != hipSuccess) return fail(c, VOLYM_E_NOMEM, std::string("hipMalloc(relabel result): ") + hipGetErrorString(e));
-    e = hipMemcpyAsync(d_res, &init, sizeof init, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) {
-        const RelabelOut out = {reinterpret_cast<unsigned long long*>(&d_res->changed), reinterpret_cast<unsigned long long*>(d_res->left),
-                                reinterpret_cast<unsigned long long*>(d_res->arrived), d_res->box};
-        hipLaunchKernelGGL(volym_label_swap_kernel, dim3(stream_grid(c, step.records)), dim3(256), 0, stream, reinterpret_cast<uint4*>(c->d_labels), step.index,
-                           step.old, out, c->nx, c->ny, c->bricked ? 1u : 0u, static_cast<uint32_t>(step.records));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&res, d_res, sizeof res, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_res);
-    if (e != hipSuccess) {
-        std::memset(&res, 0, sizeof res);
-        c->have_vol = c->have_frame = false;                              // (the kernel may have stored)
-        clear_label_history(c);
-        return fail(c, VOLYM_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        hipError_t e = d.seed<volym_relabel_result>();
+        if (e == hipSuccess) e = launch_label_swap(c, d.stream, step.index, step.old, step.records, d.out());
+        if (e == hipSuccess) e = d.fetch(res);
+        if (e != hipSuccess) {
+            std::memset(&res, 0, sizeof res);
+            c->have_vol = c->have_frame = false;                          // (the kernel may have stored)
+            clear_label_history(c);
+            return fail(c, VOLYM_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+        }
     }
     if (redo) ++c->history_cursor; else --c->history_cursor;
-    if (res.changed == 0u) { std::memset(res.box, 0, sizeof res.box); return VOLYM_OK; }      // (a step holds a changed byte: not reached)
-    for (int a = 3; a < 6; ++a) ++res.box[a];
-    rc = follow_labels(c, res, who);
-    if (rc != VOLYM_OK) c->have_vol = c->have_frame = false;
-    return rc;
+    return finish_edit(c, res, false, false, 0u, 0u, who);                // (a step holds a changed byte: changed != 0)
 }
 
 // what volym_edit_labels refuses of the context's state, in the name of `who`
-static int editable_state(volym_ctx* c, const char* who)
+int volym::editable_state(volym_ctx* c, const char* who)
 {
     const std::string w(who);
     if (!c->have_vol) return fail(c, VOLYM_E_STATE, w + ": no volume (volym_set_volume first)");

@@ -1,11 +1,9 @@
 // libvolym_hip.so: the bytes of the scene.  Volume, label and importance uploads, the device layout, the macro cells, and the
 // one transition (retarget) that keeps density and importances cut to the crop box, the clip plane and the segment mask; the C ABI entry
 // points of all of these.  The frame loop (raymarch.hip) reads what this unit writes; what the two need from each other is
-// declared in context.hpp.  Everything here is blocking set-up path, except the measure pass at the end (measure.inc, measure_kernels.h),
-// which only reads these bytes and is enqueue-only, and the label edit after it (relabel.inc, relabel_kernels.h), which rewrites
-// labels in place and carries density and importances along by the same invariant, and the brush (brush.inc, brush_kernels.h), the
-// same edit decided by a stroke's geometry, and the lasso (lasso.inc, lasso_kernels.h), the same edit decided by where a texel projects,
-// and the smoothing (smooth.inc, smooth_kernels.h), the edit decided by a texel's neighbours, in two phases.
+// declared in context.hpp.  Everything here is blocking set-up path.  The measure pass (measure.hip), which only reads these bytes, and
+// the label edits (relabel.hip, brush.hip, lasso.hip, smooth.hip), which rewrite labels in place and carry density and importances along
+// by the same invariant, are units of their own: the six functions they need of this one are declared in scene_bytes.hpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,13 +11,8 @@
 #include <string>
 #include <vector>
 
-#include "context.hpp"
+#include "scene_bytes.hpp"
 #include "scene_kernels.h"
-#include "measure_kernels.h"
-#include "relabel_kernels.h"
-#include "brush_kernels.h"
-#include "lasso_kernels.h"
-#include "smooth_kernels.h"
 
 using namespace volym;
 
@@ -53,7 +46,7 @@ static hipError_t alloc_layout(uint8_t** p, uint64_t nb)
 }
 
 // grid of the kernels that stream a layout in 16-byte chunks, one chunk per lane and step
-static uint32_t stream_grid(const volym_ctx* c, uint64_t n_chunks)
+uint32_t volym::stream_grid(const volym_ctx* c, uint64_t n_chunks)
 {
     const uint64_t g = std::min<uint64_t>((n_chunks + 255u) / 256u, static_cast<uint64_t>(c->n_cus) * 8u);
     return static_cast<uint32_t>(std::max<uint64_t>(g, 1u));
@@ -437,7 +430,7 @@ static bool crop_active(const volym_ctx* c)
 
 static bool plane_active(const volym_ctx* c) { return c->clip_n[0] != 0 || c->clip_n[1] != 0 || c->clip_n[2] != 0; }
 
-static bool imp_croppable(const volym_ctx* c)
+bool volym::imp_croppable(const volym_ctx* c)
 {
     return c->have_vol && c->have_imp && c->d_imp && c->inx == c->nx && c->iny == c->ny && c->inz == c->nz;
 }
@@ -445,7 +438,7 @@ static bool imp_croppable(const volym_ctx* c)
 static bool imp_from_labels(const volym_ctx* c) { return c->d_labels && c->have_seg_table; }
 
 // a hidden label that has voxels (hiding label values no voxel carries changes no byte)
-static bool mask_active(const volym_ctx* c)
+bool volym::mask_active(const volym_ctx* c)
 {
     for (int l = 0; l < 256; ++l) if (c->seg_hidden[l] && c->label_count[l] != 0u) return true;
     return false;
@@ -465,13 +458,13 @@ static Derived importances_of(const volym_ctx* c)
 
 // The part of the scene state the invariant depends on: crop box [lo, hi), clip plane (kept: n . t <= d) and mask (hidden[l] is
 // 0 or 1).
-struct SceneCut { uint32_t lo[3], hi[3]; int32_t n[3], d; uint8_t hidden[256]; };
+namespace volym { struct SceneCut { uint32_t lo[3], hi[3]; int32_t n[3], d; uint8_t hidden[256]; }; }
 
 static bool same_plane(const SceneCut& a, const SceneCut& b) { return a.d == b.d && a.n[0] == b.n[0] && a.n[1] == b.n[1] && a.n[2] == b.n[2]; }
 
 // the walk of the rewrite kernels over one box [box[0..2], box[3..5]) of a volume in the given layout; returns its items.
 // moved_from: the box is that of a plane edit, and the walk also carries the plane the bytes were clipped to before.
-static uint64_t make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t box[6], const SceneCut* moved_from, CropSlab& s)
+uint64_t volym::make_crop_slab(const volym_ctx* c, bool bricked, const uint32_t box[6], const SceneCut* moved_from, CropSlab& s)
 {
     s = CropSlab{};
     for (int a = 0; a < 3; ++a) { s.lo[a] = box[a]; s.hi[a] = box[3 + a]; s.box_lo[a] = c->crop_lo[a]; s.box_hi[a] = c->crop_hi[a]; }
@@ -536,7 +529,7 @@ static int rewrite(volym_ctx* c, const Derived& d, const uint32_t box[6], const 
 // 0's stream (the slots are at rest): a device-to-device copy is not waited for by the host and the slots' streams do not wait
 // for the NULL stream, so only stream order puts the copy before the kernels that rewrite its source, and the
 // hipStreamSynchronize that ends retarget covers it.
-static int ensure_uncropped_copies(volym_ctx* c, bool vol)
+int volym::ensure_uncropped_copies(volym_ctx* c, bool vol)
 {
     if (vol && !c->d_vol0) {
         const uint64_t nb = layout_bytes(c->bricked, c->nx, c->ny, c->nz) + 16u;
@@ -790,6 +783,36 @@ static hipError_t scan_label_stats(volym_ctx* c)
     return hipSuccess;
 }
 
+// The counterpart of retarget for a change of labels under a (box, plane, mask) that stays -- an edit, an undo, a redo -- once the
+// labels are stored and `res` names the labels that left and arrived and the hull of the changed texels (changed != 0).
+// Precondition: density and importances held the invariant of context.hpp for the labels as they were.  Postcondition: they hold it
+// for the labels as they are, label_count and label_box describe those, and everything derived from the bytes is up to date.
+int volym::follow_labels(volym_ctx* c, const volym_relabel_result& res, const char* who)
+{
+    // counts and boxes first: mask_active and volym_visibility_boxes read them
+    const hipError_t es = scan_label_stats(c);
+    if (es != hipSuccess) return fail(c, VOLYM_E_HIP, std::string(who) + " (label statistics): " + hipGetErrorString(es));
+    ++c->scene_serial;                                                    // labels changed: a surface pass is stale
+    // A texel's bytes differ from the rule's only where its old and its new label differ in what they give: visibility for the
+    // density, visibility and the table's byte for importances mapped from the labels.  Every such texel carries a label that
+    // arrived, inside the result's box: the visibility kernel stores the chunks that hold one, whole, by the rule.
+    uint8_t flipped[256];
+    bool hidden_moved = false;
+    for (int l = 0; l < 256; ++l) {
+        flipped[l] = res.left[l] != 0u || res.arrived[l] != 0u;
+        hidden_moved = hidden_moved || (flipped[l] && c->seg_hidden[l]);
+    }
+    int rc = VOLYM_OK;
+    if (hidden_moved) rc = rewrite(c, density_of(c), res.box, flipped, nullptr);
+    if (rc == VOLYM_OK && imp_croppable(c) && (imp_from_labels(c) || hidden_moved)) rc = rewrite(c, importances_of(c), res.box, flipped, nullptr);
+    if (rc == VOLYM_OK && hidden_moved) rc = refresh_macro_cells(c, &res.box, 1u);
+    if (rc != VOLYM_OK) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->slot0().stream));                   // every slot's next frame reads the new bytes
+    if (imp_from_labels(c)) segment_important_box(c);
+    crop_important_box(c);
+    return rebuild_lists(c);
+}
+
 // ---- C ABI: what each call makes of the scene's (box, plane, mask) ----------------------------------------------------
 //   volym_set_crop_box(lo, hi)                  current -> (lo, hi), current plane and mask density and importances
 //   volym_set_clip_plane(n, d)                  current -> current box and mask, (n, d)     density and importances
@@ -997,18 +1020,3 @@ int volym_label_counts(volym_ctx* c, uint64_t counts[256])
 }
 
 }  // extern "C"
-
-// ---- measuring segments ---------------------------------------------------------------------------------------------------
-#include "measure.inc"
-
-// ---- editing labels -------------------------------------------------------------------------------------------------------
-#include "relabel.inc"
-
-// ---- the brush: the edit whose texels a stroke decides ----------------------------------------------------------------------
-#include "brush.inc"
-
-// ---- the lasso: the edit whose texels a screen polygon decides ---------------------------------------------------------------
-#include "lasso.inc"
-
-// ---- the smoothing: the edit a majority vote of the neighbours decides ----------------------------------------------------------
-#include "smooth.inc"

@@ -1,13 +1,12 @@
-// The kernel of the smoothing (volym_smooth_labels): the vote of a majority filter over a box of texels.  Included by scene_bytes.hip
-// alone, AFTER relabel_kernels.h, brush_kernels.h and lasso_kernels.h, none of which this header includes itself (scene_bytes.hip
-// stays the one place that does).  The vote reads labels and density and writes NO label: for every chunk in which a texel changes
+// The kernel of the smoothing (volym_smooth_labels): the vote of a majority filter over a box of texels.  Included by smooth.hip
+// alone.  The vote reads labels and density and writes NO label: for every chunk in which a texel changes
 // it appends one record -- the chunk's index and its 16 bytes as they will be -- to the journal's staging area (journal_append) and
-// tallies the change (tally_texel, tally_reduce).  volym_label_swap_kernel of relabel_kernels.h applies the records afterwards.
-// From relabel_kernels.h: the one-owner rule (crop_chunk, relabel_owns_chunk, the keep mask), the tally and the journal.  Here: the
+// tallies the change (tally_texel, tally_reduce).  volym_label_swap_kernel of relabel_kernels.h (relabel.hip launches it) applies the records afterwards.
+// From edit_chunks.h: the one-owner rule (crop_chunk, relabel_owns_chunk, the keep mask), the tally and the journal.  Here: the
 // unit a workgroup stages in LDS, in either layout, and the count.
 #pragma once
 
-#include "scene_kernels.h"
+#include "edit_chunks.h"
 
 namespace volym {
 
@@ -27,7 +26,7 @@ namespace volym {
 constexpr uint32_t SMOOTH_LINEAR_CHUNKS = 63u, SMOOTH_LINEAR_BASE = 2u;      // owned chunks of a unit and its first owned dword
 constexpr uint32_t SMOOTH_BRICK_CHUNKS = 56u, SMOOTH_BRICK_BASE = 16u, SMOOTH_BRICKS = 14u;
 
-// the request as the kernel reads it (all of it uniform) and the walk's units (smooth.inc counts them)
+// the request as the kernel reads it (all of it uniform) and the walk's units (smooth.hip counts them)
 struct SmoothRule {
     uint32_t min_byte, max_byte;
     uint32_t store;                 // 0: DRY_RUN
