@@ -28,7 +28,8 @@
  *     volym_components_pass blocks only when it has to allocate or grow its buffers; volym_read_components,
  *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name);
  *     volym_distance_pass blocks only when it has to allocate or grow its buffers; volym_read_distance, volym_read_distance_map
- *     and volym_distance_at block; volym_edit_labels is a set-up call and blocks like volym_set_*.
+ *     and volym_distance_at block; volym_nearest_pass, its reads and volym_nearest_at likewise; volym_edit_labels and the other
+ *     label edits (brush, lasso, smooth, fill) are set-up calls and block like volym_set_*.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -1223,6 +1224,89 @@ int   volym_smooth_labels(volym_ctx* ctx, const volym_smooth* smooth, struct vol
  * bit, a window without min_byte <= max_byte <= 255, a radius above VOLYM_SMOOTH_MAX_RADIUS, all radii 0.  An empty box is valid:
  * nothing changes.  Pure host arithmetic. */
 int   volym_smooth_check(const volym_smooth* smooth, const uint32_t dims[3]);
+
+/* --- nearest segment: feature transform and fill by it (new; the reference has none) ------------------------------------ */
+/* Which seed is nearest: the argmin beside the distance pass's min.  A read-only pass over the bytes of the scene as they stand.
+ *   The rule (integers only; scene.nearest_volume of the Python package is its host twin, equal in every byte).  The request is the
+ * distance pass's struct; PRESENT, SOLID and d2 are that pass's definitions; UNCUT is allowed, INSIDE is refused (the nearest texel
+ * that is not solid may lie outside the box and has no label).  For a texel t of the box, site(t) is the solid texel s of the box
+ * that minimises d2(t, s); ties go to the first s in ascending (z, y, x).  It is stored as the box-linear index of s (x fastest, as
+ * in the distance map), or VOLYM_NEAREST_NONE when the box has no solid texel.  near_label(t) is the label byte of site(t) as the
+ * labels stand at the pass: 0 while the context holds no labels of the volume's dimensions, and 0 where the site is NONE.  The same
+ * request on the same scene gives the same bytes in either device layout, every time.  D is not kept: d2(t, site(t)) is three
+ * multiplications.
+ *   Memory, per texel of the box: 4 + 1 bytes of results (the site map holds the sweeps' g until the sites replace it), 6 of
+ * winners (one uint16_t per axis) and 8 of stacks, for which the distance pass's work arrays serve where the context holds them
+ * large enough (both passes run on the same stream, in stream order; its map, a result, is never used).  At 1024^3: 5 GiB of
+ * results, 6 GiB of winners, 8 GiB of stacks -- 19 GiB, 11 GiB beside a distance pass of the same box. */
+#define VOLYM_NEAREST_NONE 0xffffffffu              /* no solid texel in the box */
+struct volym_nearest_summary {
+    uint64_t n_solid, n_present;
+    uint64_t n_finite;          /* texels of the box with a site */
+    uint64_t cell[256];         /* texels of the box whose near_label is this label and whose site is not NONE */
+    uint64_t cell_present[256]; /* ... those of them that are PRESENT and not SOLID: what a fill of all the matter would hand the label */
+};                              /* 4120 bytes */
+struct volym_nearest_site {
+    uint32_t at[3];             /* the site, volume coordinates; {0, 0, 0}: none */
+    uint32_t d2;                /* d2(t, site(t)) with the weights of the pass; VOLYM_NEAREST_NONE: none */
+    uint32_t label;             /* near_label(t) */
+};                              /* 20 bytes */
+/* The fill: a texel t of box with label l becomes n = near_label(t) of the latest nearest pass iff give[l] != 0, site(t) is not
+ * NONE, take[n] != 0, n != l, its density byte lies in [min_byte, max_byte] (the scene byte as it stands, with UNCUT the uncut copy,
+ * as volym_edit_labels reads it) and d2_lo <= d2(t, site(t)) <= d2_hi with the weights of that pass.  Every texel is decided from the
+ * snapshot and from its own bytes before the edit: the result depends neither on the layout nor on the order of the workgroups.
+ * scene.fill_volume is the host twin. */
+enum { VOLYM_FILL_UNCUT = 1, VOLYM_FILL_DRY_RUN = 2 };   /* flags */
+typedef struct volym_fill {
+    uint32_t box[6];            /* as in volym_relabel; it must lie inside the box of the nearest pass */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window, on the texel that would change */
+    uint8_t  give[256];         /* give[l] != 0: texels that carry l may change */
+    uint8_t  take[256];         /* take[n] != 0: label n may receive texels */
+    uint32_t d2_lo, d2_hi;      /* lo <= hi: the band of d2(t, site(t)); 0 .. 0xffffffff = no band */
+} volym_fill;                   /* 556 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(struct volym_nearest_summary) == 4120, "volym_nearest_summary is 4120 bytes");
+static_assert(sizeof(struct volym_nearest_site) == 20, "volym_nearest_site is 20 bytes");
+static_assert(sizeof(volym_fill) == 556, "volym_fill is 556 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(struct volym_nearest_summary) == 4120, "volym_nearest_summary is 4120 bytes");
+_Static_assert(sizeof(struct volym_nearest_site) == 20, "volym_nearest_site is 20 bytes");
+_Static_assert(sizeof(volym_fill) == 556, "volym_fill is 556 bytes");
+#endif
+/* Enqueue only, on the first slot's stream: the kernel that zeroes the summary, the row sweep, the column sweeps along y and z
+ * (each also stores the entry that wins a position), and the resolve kernel that chains the winners into the site, reads its label
+ * and accumulates the summary.  d == NULL: the whole volume, min_byte 1, every label, weights 1, no flags.  The one blocking path is
+ * the first allocation, or a growth, of its buffers.  It needs what volym_distance_pass needs; an empty box launches only the zeroing
+ * kernel.  The results are a snapshot: the reads below, and volym_fill_labels, stay valid after later edits of the scene.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_nearest_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions held in
+ * the other device layout than the volume. */
+int   volym_nearest_pass(volym_ctx* ctx, const volym_distance* d);
+/* Validity without a context: what volym_distance_check refuses, and the INSIDE flag.  Pure host arithmetic. */
+int   volym_nearest_check(const volym_distance* d, const uint32_t dims[3]);
+/* The reads block.  All: VOLYM_E_STATE before any pass, and after volym_set_volume until the next one; VOLYM_E_INVALID for a NULL
+ * ctx or output.  The maps are of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi, inside the pass's box; NULL: the
+ * pass's whole box), box-linear in the sub-box; the sites they hold stay indices in the pass's box.  volym_nearest_at: the site of one
+ * texel of the pass's box as volume coordinates, with its d2 and label (VOLYM_E_INVALID for a texel outside that box). */
+int   volym_read_nearest(volym_ctx* ctx, struct volym_nearest_summary* out);
+int   volym_read_nearest_sites(volym_ctx* ctx, const uint32_t sub[6], uint32_t* out);
+int   volym_read_nearest_labels(volym_ctx* ctx, const uint32_t sub[6], uint8_t* out);
+int   volym_nearest_at(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, struct volym_nearest_site* out);
+/* The context's own results in device memory after a pass (NULL before any, and after volym_set_volume): the summary (a struct
+ * volym_nearest_summary), the site map and the label map of the latest pass's box. */
+void* volym_nearest_device_ptr(volym_ctx* ctx);
+void* volym_nearest_sites_device_ptr(volym_ctx* ctx);
+void* volym_nearest_labels_device_ptr(volym_ctx* ctx);
+/* The fill: a blocking set-up call with the contract of volym_edit_labels (it waits for the frames in flight; one kernel, in place,
+ * on the first slot's stream; with changed == 0, or DRY_RUN, nothing else is touched; otherwise counts, boxes, density and
+ * importances follow; out may be NULL).  While the history is on, a call that changes a texel (no DRY_RUN) is one step of it.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_fill_check refuses, a box that reaches outside the box of the nearest pass.
+ * VOLYM_E_STATE: what volym_edit_labels refuses of the context's state; no volym_nearest_pass since volym_set_volume.  The native
+ * multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_fill_labels(volym_ctx* ctx, const volym_fill* f, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, a window without min_byte <= max_byte <= 255, d2_lo > d2_hi.  An empty box is valid: nothing changes.  Pure host arithmetic. */
+int   volym_fill_check(const volym_fill* f, const uint32_t dims[3]);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

@@ -26,8 +26,8 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
---relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R and --shrink NAME:R edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink); the PNG is the frame after them and
+--relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R, --shrink NAME:R, --fill [NAME,...][:R] and --separate NAME:R edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -322,6 +322,26 @@ def _smooth_arg(text):
     return ([_segment_arg(n) for n in names.split(",") if n] or None), (radius[0] if len(radius) == 1 else tuple(radius))
 
 
+def _fill_arg(text):
+    """--fill [NAME,...][:R] -> (names or None for every segment, r or None for no limit)"""
+    usage = "[NAME,...][:R] -- the segments that grow into the unlabelled matter (none: every segment) and how far in texels (default: no limit)"
+    names, sep, r = text.partition(":")
+    try:
+        limit = float(r) if sep else None
+    except ValueError:
+        raise SystemExit("--fill: %s" % usage)
+    return ([_segment_arg(n) for n in names.split(",") if n] or None), limit
+
+
+def _fill_table(d, result):
+    """what --fill prints: how many texels joined the nearest segment, then every segment that took some"""
+    took = sorted(result["arrived"].items())
+    lines = ["fill: %d texels joined the nearest of %d segments" % (result["changed"], len(took))]
+    for l, n in took:
+        lines.append("  + %-16s label %3d: %10d" % (d._segment_name(l) or "label %d" % l, l, n))
+    return "\n".join(lines)
+
+
 def _label_edits(ctx, d, args):
     """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, lasso, split_at, keep_largest, grow, shrink):
     [(option, result)]"""
@@ -368,6 +388,12 @@ def _label_edits(ctx, d, args):
         if getattr(args, "shrink", None):
             name, r = _name_and(args.shrink, "--shrink", "NAME:R -- a segment and a margin in texels")
             out.append(("shrink", d.shrink(ctx, _segment_arg(name), r)))
+        if getattr(args, "fill", None) is not None:
+            names, r = _fill_arg(args.fill)
+            out.append(("fill", d.fill(ctx, names, r, window=(1, 255))))
+        if getattr(args, "separate", None):
+            name, r = _name_and(args.separate, "--separate", "NAME:R -- a segment and the depth of its cores in texels")
+            out.append(("separate", d.separate(ctx, _segment_arg(name), r)))
     except ValueError as e:
         raise SystemExit("label edit: %s" % e)
     return out
@@ -481,6 +507,10 @@ def run_simple(args):
     print("run simple: %s, %dx%d -> %s" % (what, W, H, path))
     for option, result in edits:
         import json
+        if option == "fill":
+            print(_fill_table(d, result))
+        elif option == "separate":
+            print("separate: %d pieces%s" % (len(result), "".join(", %s %d texels" % (p["name"], p["texels"]) for p in result)))
         print(json.dumps({option: result}))      # one line per label edit: texels changed, per label left and arrived, the hull
     if labels_out is not None:
         print("labels: %d bytes -> %s" % (labels_out, args.labels_out))
@@ -656,6 +686,11 @@ def main(argv=None):
     run.add_argument("--keep-largest", help="NAME: keep the largest piece of the segment, its other pieces become unlabelled")
     run.add_argument("--grow", help="NAME:R: grow the segment by R texels into the unlabelled texels")
     run.add_argument("--shrink", help="NAME:R: shrink the segment by R texels")
+    run.add_argument("--fill", nargs="?", const="", metavar="NAME,...[:R]",
+                     help="grow the named segments (default: every segment) at once into the unlabelled matter on the device, after --shrink: every unlabelled texel "
+                          "with a density byte above 0 joins the segment it is nearest to, at most R texels away (default: however far) (demo.Simple.fill); one undo step")
+    run.add_argument("--separate", metavar="NAME:R", help="separate touching objects of the segment: its cores at depth R become segments of their own and the rest "
+                                                          "goes to the nearest of them (demo.Simple.separate); after --fill")
     run.add_argument("--undo", type=int, metavar="N", help="keep a history of the label edits above on the device and take the last N back, before the "
                                                            "picture and --labels-out; each prints a JSON line {\"undo\": ...}")
     run.add_argument("--labels-out", help="FILE: write the labels as they stand after the edits, raw bytes in the orientation of --labels")

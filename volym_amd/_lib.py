@@ -339,6 +339,38 @@ class Smooth(C.Structure):
     ]
 
 
+NEAREST_NONE = 0xFFFFFFFF                                      # no solid texel in the box
+FILL_UNCUT, FILL_DRY_RUN = 1, 2                                # volym_fill.flags
+
+
+class NearestSummary(C.Structure):
+    """volym_nearest_summary (include/volym_hip.h): counters and the cells per label, 4120 bytes"""
+    _fields_ = [("n_solid", C.c_uint64), ("n_present", C.c_uint64), ("n_finite", C.c_uint64), ("cell", C.c_uint64 * 256), ("cell_present", C.c_uint64 * 256)]
+
+
+class NearestSite(C.Structure):
+    """volym_nearest_site (include/volym_hip.h): the site of one texel in volume coordinates, its d2 and its label, 20 bytes"""
+    _fields_ = [("at", C.c_uint32 * 3), ("d2", C.c_uint32), ("label", C.c_uint32)]
+
+
+# the summary as a NumPy structured dtype (GpuContext.read_nearest, scene.nearest_volume)
+NEAREST_SUMMARY_DTYPE = np.dtype([("n_solid", "<u8"), ("n_present", "<u8"), ("n_finite", "<u8"), ("cell", "<u8", (256,)), ("cell_present", "<u8", (256,))])
+
+
+class Fill(C.Structure):
+    """volym_fill (include/volym_hip.h): box, flags, density window, the give and take tables and the band of one fill, 556 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("give", C.c_uint8 * 256),
+        ("take", C.c_uint8 * 256),
+        ("d2_lo", C.c_uint32),
+        ("d2_hi", C.c_uint32),
+    ]
+
+
 class LassoView(C.Structure):
     """volym_lasso_view (include/volym_hip.h): the integer view texel -> (X, Y, D), 88 bytes"""
     _fields_ = [
@@ -563,6 +595,17 @@ SIGNATURES = {
     "volym_lasso_view_depth": (C.c_int, [C.POINTER(LassoView), C.c_double, C.c_double]),
     "volym_smooth_labels": (C.c_int, [_ctx, C.POINTER(Smooth), C.POINTER(RelabelResult)]),
     "volym_smooth_check": (C.c_int, [C.POINTER(Smooth), C.POINTER(C.c_uint32)]),
+    "volym_nearest_pass": (C.c_int, [_ctx, C.POINTER(Distance)]),
+    "volym_nearest_check": (C.c_int, [C.POINTER(Distance), C.POINTER(C.c_uint32)]),
+    "volym_read_nearest": (C.c_int, [_ctx, C.POINTER(NearestSummary)]),
+    "volym_read_nearest_sites": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_read_nearest_labels": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+    "volym_nearest_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(NearestSite)]),
+    "volym_nearest_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_nearest_sites_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_nearest_labels_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_fill_labels": (C.c_int, [_ctx, C.POINTER(Fill), C.POINTER(RelabelResult)]),
+    "volym_fill_check": (C.c_int, [C.POINTER(Fill), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -5,6 +5,7 @@
 //   scene_bytes.hip   the bytes of the scene; the seam in front of it for the two groups below is scene_bytes.hpp
 //   pick.hip, outline.hip, slice.hip, project.hip, measure.hip, surface.hip, components.hip, distance.hip
 //                     the pass of that name
+//   nearest.hip       the nearest pass and the fill by it, an edit like those below
 //   relabel.hip, brush.hip, lasso.hip, smooth.hip
 //                     the label edit of that name (relabel.hip: and the history); what they share on the host is label_edit.hpp
 //   box_pass.hip      no ABI: what the passes over a request's box share -- the scan of row counts into offsets and the read-back
@@ -271,6 +272,15 @@ struct volym_ctx {
     volym::OwnedBuffer<unsigned long long> distance_keys;   // the working summary: counters and 64-bit (D, index) keys, packed into `distance`
     uint32_t distance_box[6] = {};           // the box of the latest pass (the reads address the map by it)
 
+    // nearest passes (volym_nearest_pass, nearest.hip): a snapshot, valid until the next volym_set_volume
+    volym::OwnedBuffer<volym_nearest_summary> nearest;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> nearest_sites;      // site of every texel of the request's box, box-linear; the sweeps' g while the pass runs
+    volym::OwnedBuffer<uint8_t> nearest_labels;      // ... and the label byte of that site
+    volym::OwnedBuffer<uint16_t> nearest_winners;    // wx, wy, wz: the winning entry per texel and axis (nearest_kernels.h), three per texel
+    volym::OwnedBuffer<uint32_t> nearest_work;       // the column sweeps' stacks, where the distance pass's work arrays are too small
+    uint32_t nearest_box[6] = {};            // the box of the latest pass (the reads and the fill address the maps by it)
+    uint32_t nearest_weight[3] = {};         // ... and its weights (the fill's band is in its metric)
+
     // the history of label edits (volym_label_history, relabel.hip): off (budget 0) in a new context
     struct LabelStep {
         uint32_t* index = nullptr;           // the chunks the edit stored ...
@@ -352,6 +362,8 @@ void free_surface(volym_ctx* c);
 void free_components(volym_ctx* c);
 // distance.hip: what the context keeps for the distance pass (every stream idle)
 void free_distance(volym_ctx* c);
+// nearest.hip: what the context keeps for the nearest pass (every stream idle)
+void free_nearest(volym_ctx* c);
 // relabel.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
 void clear_label_history(volym_ctx* c);
 // relabel.hip: the steps and the staging area of the label history (every stream idle)

@@ -241,6 +241,33 @@ public:
         records_current_ = false;
         return out;
     }
+    // New: grow several segments at once (volym_nearest_pass, volym_fill_labels): one nearest pass from the union of `names` (names,
+    // ids or label values as text; empty: every label but 0), then one fill -- every unlabelled texel with a density byte above 0
+    // joins the segment it is nearest to, the first in (z, y, x) among equals, if that is at most r texels away (r < 0: however far).
+    // One call, one step of the history.
+    volym_relabel_result fill(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& names, double r)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "fill: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        volym_distance d{};
+        d.box[3] = a.nx; d.box[4] = a.ny; d.box[5] = a.nz;
+        d.min_byte = 1u;
+        d.weight[0] = d.weight[1] = d.weight[2] = 1u;
+        if (names.empty()) std::memset(d.select + 1, 1, 255);
+        for (const std::string& n : names) d.select[label_value_of(a, n)] = 1u;
+        d.select[0] = 0u;
+        ctx.check(volym_nearest_pass(ctx.handle(), &d));
+        volym_fill f{};
+        std::memcpy(f.box, d.box, sizeof f.box);
+        f.min_byte = 1u; f.max_byte = 255u;
+        f.give[0] = 1u;
+        std::memcpy(f.take, d.select, 256);
+        f.d2_hi = r < 0.0 ? 0xffffffffu : static_cast<uint32_t>(std::floor(r * r + 1e-9));
+        volym_relabel_result out{};
+        ctx.check(volym_fill_labels(ctx.handle(), &f, &out));
+        records_current_ = false;
+        return out;
+    }
     // New: keep a history of the label edits in at most budget_bytes of device memory (volym_label_history), so that undo can take
     // them back.  The labels go to the device first: handing them to the context clears the history.
     void history(const GpuContext& ctx, const SimpleAssets& a, uint64_t budget_bytes = 256ull << 20)

@@ -913,6 +913,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     free_surface(c);                        // (and so do a surface's summary, row offsets and faces, which are sized by it)
     free_components(c);                     // (and the components' snapshot: its ids address texels of the old volume)
     free_distance(c);                       // (and the distance map, for the same reason)
+    free_nearest(c);                        // (and the nearest pass's sites)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;

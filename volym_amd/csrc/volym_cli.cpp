@@ -21,6 +21,8 @@
 //   the first frame join TO (Simple::lasso), after --brush;
 //   --smooth [NAME,...][:R[,R,R]] smooths the segmentation: one pass of the majority filter over R texels (default 1) for the segments
 //   NAME against label 0, or jointly for every label without a name (Simple::smooth), after --lasso;
+//   --fill [NAME,...][:R] grows the segments NAME (none: every segment) at once into the unlabelled matter: every unlabelled texel
+//   with a density byte above 0 joins the segment it is nearest to, at most R texels away (Simple::fill), after --smooth;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
 #include <algorithm>
 #include <cctype>
@@ -80,6 +82,9 @@ struct Options {
     bool smooth = false;                                 // --smooth [NAME,...][:R[,R,R]]: one pass of the majority filter (run simple)
     std::vector<std::string> smooth_names;
     std::array<uint32_t, 3> smooth_radius = {1u, 1u, 1u};
+    bool fill = false;                                   // --fill [NAME,...][:R]: the segments grow at once into the unlabelled matter (run simple)
+    std::vector<std::string> fill_names;
+    double fill_r = -1.0;                                // (below 0: however far)
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -222,6 +227,8 @@ int run_simple(const Options& o)
     if (!o.lasso_to.empty()) lassoed = demo.lasso(ctx, assets, o.lasso_pixels, o.lasso_from, o.lasso_to);   // the view of the first frame; after --brush, before --undo
     volym_relabel_result smoothed{};
     if (o.smooth) smoothed = demo.smooth(ctx, assets, o.smooth_names, o.smooth_radius);                     // after --lasso, before --undo
+    volym_relabel_result filled{};
+    if (o.fill) filled = demo.fill(ctx, assets, o.fill_names, o.fill_r);                                    // after --smooth, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -246,6 +253,18 @@ int run_simple(const Options& o)
     if (!o.brush_to.empty()) print_result("brush", brushed);
     if (!o.lasso_to.empty()) print_result("lasso", lassoed);
     if (o.smooth) print_result("smooth", smoothed);
+    if (o.fill) {
+        // how many texels joined the nearest segment, then every segment that took some
+        int took = 0;
+        for (int l = 0; l < 256; ++l) took += filled.arrived[l] != 0u;
+        std::printf("fill: %llu texels joined the nearest of %d segments\n", static_cast<unsigned long long>(filled.changed), took);
+        for (int l = 0; l < 256; ++l) {
+            if (filled.arrived[l] == 0u) continue;
+            std::string name = "label " + std::to_string(l);
+            for (const SegmentInfo& s : assets.segments) if (s.label_value == l) name = s.name.empty() ? s.id : s.name;
+            std::printf("  + %-16s label %3d: %10llu\n", name.c_str(), l, static_cast<unsigned long long>(filled.arrived[l]));
+        }
+    }
     for (const auto& u : undone) {
         if (u.first) print_result("undo", u.second);
         else std::printf("undo: nothing to take back\n");
@@ -509,6 +528,28 @@ int main(int argc, char** argv)
                     if (radii.size() == 1u) o.smooth_radius = {radii[0], radii[0], radii[0]};
                     else if (radii.size() == 3u) o.smooth_radius = {radii[0], radii[1], radii[2]};
                     else throw Error(VOLYM_E_INVALID, usage);
+                }
+            }
+            else if (a == "--fill") {
+                const char* usage = "--fill: [NAME,...][:R] -- the segments that grow into the unlabelled matter (none: every segment) and how far in texels";
+                o.fill = true;
+                std::string v;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") v = next();
+                const size_t colon = v.rfind(':');
+                const std::string names = colon == std::string::npos ? v : v.substr(0, colon);
+                size_t pos = 0;
+                while (pos < names.size()) {
+                    const size_t comma = std::min(names.find(',', pos), names.size());
+                    if (comma > pos) o.fill_names.push_back(names.substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+                if (colon != std::string::npos) {
+                    try {
+                        size_t used = 0;
+                        const std::string r = v.substr(colon + 1u);
+                        o.fill_r = std::stod(r, &used);
+                        if (used != r.size() || !(o.fill_r >= 0.0)) throw Error(VOLYM_E_INVALID, usage);
+                    } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
                 }
             }
             else if (a == "--labels-out") o.labels_out = next();

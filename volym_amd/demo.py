@@ -83,6 +83,7 @@ class GpuContext:
         self._ck(_lib.lib().volym_set_volume(self.handle, scene._u8p(v), nx, ny, nz, int(filter)))
         self._volume_dims, self._components_box = (int(nx), int(ny), int(nz)), None      # (read_component_ids shapes its result by them)
         self._distance_box = None
+        self._nearest_box = None
 
     def set_importances(self, importances, dims):
         v = np.ascontiguousarray(importances, np.uint8).ravel()
@@ -538,6 +539,71 @@ class GpuContext:
     def distance_map_device_ptr(self):
         """The map of the latest distance pass in device memory (None before any)."""
         return _lib.lib().volym_distance_map_device_ptr(self.handle)
+
+    # ---- nearest segment -------------------------------------------------------------------------
+    def nearest_pass(self, distance=None):
+        """Enqueue one nearest pass (include/volym_hip.h volym_nearest_pass; scene.nearest_volume is its definition): for every texel
+        of the request's box the nearest solid texel of the box -- the first in (z, y, x) among equals -- and its label, of the scene
+        as it stands.  `distance` is a scene.Distance without INSIDE; None: the whole volume, min_byte 1, every label, weights 1."""
+        d = None if distance is None else C.byref(distance.to_c())
+        self._ck(_lib.lib().volym_nearest_pass(self.handle, d))
+        box = ((0, 0, 0), getattr(self, "_volume_dims", (0, 0, 0))) if distance is None else distance.box
+        self._nearest_box = box if all(a < b for a, b in zip(*box)) else None
+
+    def read_nearest(self):
+        """The summary of the latest nearest pass: an np.void of _lib.NEAREST_SUMMARY_DTYPE.  Blocks."""
+        out = np.zeros(1, _lib.NEAREST_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_nearest(self.handle, out.ctypes.data_as(C.POINTER(_lib.NearestSummary))))
+        return out[0]
+
+    def _read_nearest_map(self, call, dtype, ctype, sub):
+        box = getattr(self, "_nearest_box", None) if sub is None else (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        if box is None:                                        # no pass yet (the library refuses), or a pass over an empty box
+            self._ck(call(self.handle, None, None))
+            return np.zeros((0, 0, 0), dtype)
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        out = np.zeros(tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0)), dtype)
+        self._ck(call(self.handle, c, out.ctypes.data_as(C.POINTER(ctype))))
+        return out
+
+    def read_nearest_sites(self, sub=None):
+        """The site map of the latest nearest pass as a uint32 array [z, y, x]: of its whole box (None) or of the sub-box (lo, hi) in
+        texels of the volume, which must lie inside the pass's box.  A site is an index in the pass's box, x fastest;
+        _lib.NEAREST_NONE: the box holds no solid texel.  Blocks."""
+        return self._read_nearest_map(_lib.lib().volym_read_nearest_sites, np.uint32, C.c_uint32, sub)
+
+    def read_nearest_labels(self, sub=None):
+        """The label of every texel's site in the latest nearest pass as a uint8 array [z, y, x], as read_nearest_sites.  Blocks."""
+        return self._read_nearest_map(_lib.lib().volym_read_nearest_labels, np.uint8, C.c_uint8, sub)
+
+    def nearest_at(self, x, y, z):
+        """The site of texel (x, y, z) in the latest nearest pass: {"at": its volume coordinates (None: no solid texel in the box),
+        "d2", "label"}.  Blocks."""
+        out = _lib.NearestSite()
+        self._ck(_lib.lib().volym_nearest_at(self.handle, int(x), int(y), int(z), C.byref(out)))
+        none = int(out.d2) == _lib.NEAREST_NONE
+        return {"at": None if none else tuple(int(v) for v in out.at), "d2": None if none else int(out.d2), "label": int(out.label)}
+
+    def nearest_device_ptr(self):
+        """The context's own summary (a volym_nearest_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_nearest_device_ptr(self.handle)
+
+    def nearest_sites_device_ptr(self):
+        """The site map of the latest nearest pass in device memory (None before any)."""
+        return _lib.lib().volym_nearest_sites_device_ptr(self.handle)
+
+    def nearest_labels_device_ptr(self):
+        """The label map of the latest nearest pass in device memory (None before any)."""
+        return _lib.lib().volym_nearest_labels_device_ptr(self.handle)
+
+    def fill_labels(self, fill):
+        """One fill on the device (include/volym_hip.h volym_fill_labels; scene.fill_volume is its definition): a texel of the box
+        whose label gives becomes the label of its site in the latest nearest pass, where the take table, the density window and the
+        band say so.  `fill` is a scene.Fill.  Everything follows as after edit_labels, and the call is one step of the history.
+        Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_fill_labels(self.handle, C.byref(fill.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
 
     # ---- editing labels --------------------------------------------------------------------------
     def edit_labels(self, relabel):
@@ -1343,6 +1409,75 @@ class Simple(ComputeDemo):
         ctx.distance_pass(d)
         return self._edit(ctx, scene.Relabel(None, _lib.RELABEL_DISTANCE, to={l: self._new_segment(ctx, to, l)},
                                              d2=(self._band(unit, r) + 1, _lib.DISTANCE_NONE - 1), dims=self.dims))
+
+    def _nearest_request(self, ctx, values, min_byte, spacing):
+        weights, unit = scene.distance_weights(spacing)
+        return scene.check_nearest(scene.Distance(None, 0, min_byte, scene.surface_select(values), weights, dims=self.dims), self.dims), unit
+
+    def nearest(self, ctx, names=None, min_byte=1, spacing=(1, 1, 1)):
+        """Which segment is nearest?  One nearest pass from the union of the segments `names` (names, ids or label values; None:
+        every label but 0) and the read of its summary; the maps stay on the device for ctx.read_nearest_sites,
+        ctx.read_nearest_labels, ctx.nearest_at and a fill.  Returns scene.nearest_summary's dict, the cells by segment name ("label
+        N" for a value the segments JSON does not list): "texels" of the volume are nearest to the segment, "fill" of them are
+        present and in none of the segments.  The labels go to the device first if they are not there yet."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        values = list(range(1, 256)) if names is None else self._label_values(names)
+        d, unit = self._nearest_request(ctx, values, min_byte, spacing)
+        ctx.nearest_pass(d)
+        out = scene.nearest_summary(ctx.read_nearest(), {l: self._segment_name(l) or "label %d" % l for l in range(256)})
+        out.update(unit=unit, weights=d.weight)
+        return out
+
+    def _fill(self, ctx, fill):
+        result = ctx.fill_labels(scene.check_fill(fill, self.dims))
+        if int(result["changed"]) and not fill.flags & _lib.FILL_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def fill(self, ctx, names=None, r=None, into=(0,), window=(0, 255), spacing=(1, 1, 1), min_byte=1):
+        """Grow several segments at once: one nearest pass from the union of `names` (names, ids or label values; None: every label
+        but those of `into`), then one fill -- every texel of the segments `into` (default: the unlabelled texels) with a density
+        byte in `window` joins the segment it is nearest to, the first in (z, y, x) among equals, if that is at most r away (units of
+        `spacing`; None: however far).  One call, one undo step.  Returns the result's dict."""
+        self._ready_to_edit(ctx)
+        gives = self._label_values(into)
+        seeds = [l for l in (range(256) if names is None else self._label_values(names)) if l not in gives]
+        d, unit = self._nearest_request(ctx, seeds, min_byte, spacing)
+        ctx.nearest_pass(d)
+        band = (0, 0xFFFFFFFF if r is None else self._band(unit, r))
+        return self._fill(ctx, scene.Fill(None, 0, window, scene.smooth_table(gives), scene.smooth_table(seeds), band, dims=self.dims))
+
+    def separate(self, ctx, name, r, most=8, spacing=(1, 1, 1), min_byte=1):
+        """Separate touching objects of segment `name`: its core at depth r (units of `spacing`) falls into pieces, the `most`
+        largest of them become segments "<name> 1", "<name> 2", ... (largest first), the rest of the core goes back, and what is
+        left of `name` goes to the piece it is nearest to.  A composition: core, one components pass, the edits by id, one nearest
+        pass from the new labels and one fill -- each edit an undo step of its own.  Returns [{"name", "label", "texels"}, ...] of the
+        pieces after the fill, largest core first; [] when the segment has no core that deep."""
+        self._ready_to_edit(ctx)
+        (l,) = self._label_values([name])
+        base = self._segment_name(l) or "label %d" % l
+        first = self._new_segment(ctx, "%s 1" % base, l)
+        self.core(ctx, l, r, first, spacing, min_byte)
+        ctx.components_pass(scene.Components(None, 0, min_byte, scene.surface_select([first]), dims=self.dims))
+        summary = ctx.read_components()
+        if not int(summary["recorded"]):
+            return []
+        counts = ctx.read_component_table(summary["recorded"])["count"].astype(np.int64)
+        order = np.argsort(-counts, kind="stable")[:max(int(most), 1)].tolist()
+        pieces = [first]
+        for rank, k in enumerate(order[1:], 2):
+            value = self._new_segment(ctx, "%s %d" % (base, rank), l)
+            self._edit(ctx, scene.Relabel(None, _lib.RELABEL_IDS, to={first: value}, ids=(k, k), dims=self.dims))
+            pieces.append(value)
+        # what still carries the first piece's label and is not that piece: the pieces beyond `most`
+        self._edit(ctx, scene.Relabel(None, _lib.RELABEL_IDS | _lib.RELABEL_IDS_EXCEPT, to={first: l}, ids=(order[0], order[0]), dims=self.dims))
+        d, _unit = self._nearest_request(ctx, pieces, min_byte, spacing)
+        ctx.nearest_pass(d)
+        self._fill(ctx, scene.Fill(None, 0, (0, 255), scene.smooth_table([l]), scene.smooth_table(pieces), dims=self.dims))
+        after = ctx.label_counts()
+        return [{"name": self._segment_name(v), "label": v, "texels": int(after[v])} for v in pieces]
 
     def _brush(self, ctx, brush):
         result = ctx.brush_labels(scene.check_brush(brush, self.dims))

@@ -1964,6 +1964,192 @@ def smooth_volume(prepared, dims, smooth, labels, uncut=None):
     return new, result
 
 
+def check_nearest(distance, dims):
+    """The validity rules of volym_nearest_check: those of check_distance, and no INSIDE (the nearest texel that is not solid may lie
+    outside the box and has no label).  Returns the request; raises ValueError."""
+    d = check_distance(distance, dims)
+    if d.flags & _lib.DISTANCE_INSIDE:
+        raise ValueError("nearest: INSIDE is not valid for a nearest pass")
+    return d
+
+
+def empty_nearest():
+    """(summary, sites, near_labels) of a pass over an empty box: all counters 0 (an np.void of _lib.NEAREST_SUMMARY_DTYPE), no maps."""
+    return np.zeros(1, _lib.NEAREST_SUMMARY_DTYPE)[0], np.zeros((0, 0, 0), np.uint32), np.zeros((0, 0, 0), np.uint8)
+
+
+def nearest_volume(prepared, dims, d, labels=None, cut=None, uncut=None):
+    """The definition of the nearest pass (include/volym_hip.h volym_nearest_pass), NumPy integers only; equal to the device in every
+    byte.  The arguments are distance_volume's.  Every texel carries the 64-bit key d2 << 31 | site, site being the box-linear index
+    of a solid texel (below 2^31, ascending in (z, y, x)); per axis one broadcast minimum of key[j] + (weight * (i - j)^2 << 31), one j
+    at a time over the whole box.  Adding to a key is monotone, so the three minima are the minimum over all solid texels of
+    (d2, site): the nearest one, the first in (z, y, x) among equals.  Returns (summary, sites, near_labels): an np.void of
+    _lib.NEAREST_SUMMARY_DTYPE, the sites as a uint32 array [z, y, x] over the request's box (_lib.NEAREST_NONE: the box holds no solid
+    texel) and the label byte of each site as a uint8 array of the same shape."""
+    d = check_nearest(d, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = d.box
+    summary, no_sites, no_labels = empty_nearest()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, no_sites, no_labels
+    whole = bool(d.flags & _lib.DISTANCE_UNCUT)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("nearest_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("nearest_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    present = b >= d.min_byte
+    solid = present & (np.asarray(d.select)[l] != 0)
+    # d2 < 2^32 and site < 2^31: a key is below 2^63; `far` is above every key, and far + (64 * 4095^2 << 31) is below 2^64
+    far = np.uint64(1) << np.uint64(63)
+    index = np.arange(b.size, dtype=np.uint64).reshape(b.shape)
+    key = np.where(solid, index, far)
+    for axis, weight in ((2, d.weight[0]), (1, d.weight[1]), (0, d.weight[2])):
+        n = key.shape[axis]
+        shape = [1, 1, 1]
+        shape[axis] = n
+        i = np.arange(n, dtype=np.int64).reshape(shape)
+        f = np.full(key.shape, far, np.uint64)
+        for j in range(n):
+            at = [slice(None)] * 3
+            at[axis] = slice(j, j + 1)
+            np.minimum(f, key[tuple(at)] + ((weight * (i - j) ** 2).astype(np.uint64) << np.uint64(31)), out=f)
+        key = np.minimum(f, far)
+    finite = key < far
+    sites = np.where(finite, key & np.uint64(0x7FFFFFFF), np.uint64(_lib.NEAREST_NONE)).astype(np.uint32)
+    near = np.where(finite, l.ravel()[np.where(finite, sites, 0)], 0).astype(np.uint8)
+    summary["n_solid"], summary["n_present"], summary["n_finite"] = int(solid.sum()), int(present.sum()), int(finite.sum())
+    summary["cell"][...] = np.bincount(near[finite], minlength=256)
+    summary["cell_present"][...] = np.bincount(near[finite & present & ~solid], minlength=256)
+    return summary, sites, near
+
+
+def nearest_d2(sites, box, weight):
+    """d2(t, site(t)) of a site map (uint32 [z, y, x] over `box` = ((lo), (hi))) under `weight`, as int64; _lib.NEAREST_NONE where the
+    site is."""
+    sites = np.asarray(sites, np.uint32)
+    depth, h, w = sites.shape
+    s = sites.astype(np.int64)
+    z, y, x = np.meshgrid(np.arange(depth), np.arange(h), np.arange(w), indexing="ij")
+    d2 = weight[0] * (x - s % w) ** 2 + weight[1] * (y - (s // w) % h) ** 2 + weight[2] * (z - s // (w * h)) ** 2
+    return np.where(sites == np.uint32(_lib.NEAREST_NONE), np.int64(_lib.NEAREST_NONE), d2)
+
+
+def nearest_summary(summary, names=None):
+    """What a user reads off a nearest pass, as Python ints: {"n_solid", "n_present", "n_finite", "cells": {label or name: {"texels",
+    "fill"}}} for every label with a cell -- `texels` of the box are nearest to it, `fill` of them are present and not solid.  names:
+    {label: name}."""
+    out = {"n_solid": int(summary["n_solid"]), "n_present": int(summary["n_present"]), "n_finite": int(summary["n_finite"]), "cells": {}}
+    for l in np.flatnonzero(np.asarray(summary["cell"])).tolist():
+        out["cells"][(names or {}).get(l, l)] = {"label": l, "texels": int(summary["cell"][l]), "fill": int(summary["cell_present"][l])}
+    return out
+
+
+class Fill:
+    """volym_fill (include/volym_hip.h): one fill by the latest nearest pass.  box and window as Relabel takes them; flags:
+    _lib.FILL_UNCUT | FILL_DRY_RUN; give, take: tables of 256 bytes (smooth_table; None: every label) -- the labels whose texels may
+    change and the labels that may receive texels; d2: (d2_lo, d2_hi), the band of the squared distance to the site."""
+
+    def __init__(self, box=None, flags=0, window=(0, 255), give=None, take=None, d2=(0, 0xFFFFFFFF), dims=None):
+        self.box = _box_or_whole(box, dims, "a fill request without a box needs the volume's dims")
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.give = smooth_table() if give is None else np.array(give, np.int64).ravel()
+        self.take = smooth_table() if take is None else np.array(take, np.int64).ravel()
+        self.d2 = tuple(int(v) for v in d2)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "fill", ("box", "flags", "window", "give", "take", "d2"), kw)
+
+    def to_c(self):
+        """The _lib.Fill of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Fill()
+        c.box = _box_to_c(self.box, "fill")
+        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("fill: flags and the window's ends must be u32")
+        if len(self.d2) != 2 or not all(0 <= x < 2 ** 32 for x in self.d2):
+            raise ValueError("fill: d2 is a pair of u32")
+        c.flags = self.flags
+        c.min_byte, c.max_byte = self.window
+        c.d2_lo, c.d2_hi = self.d2
+        for name, t in (("give", self.give), ("take", self.take)):
+            if t.size != 256 or not ((t >= 0) & (t <= 255)).all():
+                raise ValueError("fill: %s is a table of 256 bytes" % name)
+            setattr(c, name, (C.c_uint8 * 256)(*[int(g) for g in t]))
+        return c
+
+
+def check_fill(fill, dims):
+    """The validity rules of volym_fill_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, d2_lo <= d2_hi, tables of 256 entries.  Returns the request; raises ValueError."""
+    r = fill
+    _box_in_dims(r.box, dims, "fill")
+    if r.flags & ~(_lib.FILL_UNCUT | _lib.FILL_DRY_RUN) or r.flags < 0:
+        raise ValueError("fill: unknown flag bits in %#x" % r.flags)
+    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
+        raise ValueError("fill: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (r.window,))
+    if len(r.d2) != 2 or not 0 <= r.d2[0] <= r.d2[1]:
+        raise ValueError("fill: the band needs d2_lo <= d2_hi, got %r" % (r.d2,))
+    if np.asarray(r.give).size != 256 or np.asarray(r.take).size != 256:
+        raise ValueError("fill: give and take have 256 entries")
+    return r
+
+
+def fill_volume(prepared, dims, fill, labels, sites, near_labels, pass_box, weight=(1, 1, 1), uncut=None):
+    """The definition of the fill (include/volym_hip.h volym_fill_labels), NumPy integers only; equal to the device in every byte.
+    `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None: prepared), `labels`: the
+    labels before the edit; sites, near_labels: the snapshot of the latest nearest pass (nearest_volume's maps) over pass_box =
+    ((lo), (hi)), and `weight` that pass's weights.  A texel of the box whose label gives becomes its near label n iff it has a site,
+    n takes, n is not its label, its density byte lies in the window and d2(t, site) lies in the band.  Returns (new_labels, result)
+    as relabel_volume does."""
+    r = check_fill(fill, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("fill_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (r.flags & _lib.FILL_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("fill_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    slo, shi = (tuple(int(v) for v in pass_box[0]), tuple(int(v) for v in pass_box[1]))
+    if any(lo[a] < slo[a] or hi[a] > shi[a] for a in range(3)):
+        raise ValueError("fill_volume: the request's box reaches outside the box of the nearest pass")
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    shape = (shi[2] - slo[2], shi[1] - slo[1], shi[0] - slo[0])
+    inner = (slice(lo[2] - slo[2], hi[2] - slo[2]), slice(lo[1] - slo[1], hi[1] - slo[1]), slice(lo[0] - slo[0], hi[0] - slo[0]))
+    site = np.asarray(sites, np.uint32).reshape(shape)
+    d2 = nearest_d2(site, (slo, shi), weight)[inner]
+    site = site[inner]
+    n = np.asarray(near_labels, np.uint8).reshape(shape)[inner]
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    d = src.reshape(nz, ny, nx)[sub]
+    give, take = np.asarray(r.give) != 0, np.asarray(r.take) != 0
+    hit = give[old] & (site != np.uint32(_lib.NEAREST_NONE)) & take[n] & (n != old) & (d >= r.window[0]) & (d <= r.window[1]) & (d2 >= r.d2[0]) & (d2 <= r.d2[1])
+    count = int(hit.sum())
+    if count == 0:
+        return new, result
+    result["changed"] = count
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(n[hit], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not r.flags & _lib.FILL_DRY_RUN:
+        new[sub] = np.where(hit, n, old)
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
