@@ -28,8 +28,9 @@
  *     volym_components_pass blocks only when it has to allocate or grow its buffers; volym_read_components,
  *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name);
  *     volym_distance_pass blocks only when it has to allocate or grow its buffers; volym_read_distance, volym_read_distance_map
- *     and volym_distance_at block; volym_nearest_pass, its reads and volym_nearest_at likewise; volym_edit_labels and the other
- *     label edits (brush, lasso, smooth, fill) are set-up calls and block like volym_set_*.
+ *     and volym_distance_at block; volym_nearest_pass, its reads and volym_nearest_at likewise; volym_geodesic_pass BLOCKS (it
+ *     reads 4 bytes after every batch of its rounds), and so do its reads and volym_geodesic_at; volym_edit_labels and the other
+ *     label edits (brush, lasso, smooth, fill, flood) are set-up calls and block like volym_set_*.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -1307,6 +1308,105 @@ int   volym_fill_labels(volym_ctx* ctx, const volym_fill* f, struct volym_relabe
 /* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
  * bit, a window without min_byte <= max_byte <= 255, d2_lo > d2_hi.  An empty box is valid: nothing changes.  Pure host arithmetic. */
 int   volym_fill_check(const volym_fill* f, const uint32_t dims[3]);
+
+/* --- geodesic growth: steps through the matter, and the flood by them (new; the reference has none) ---------------------- */
+/* How far through the matter, and from which seed: the growth that stays inside a medium, where the distance and nearest passes
+ * measure straight through anything.  A read-only pass over the bytes of the scene as they stand.
+ *   The rule (integers only; scene.geodesic_volume of the Python package is its host twin, equal in every byte).  The density byte
+ * and the label are read as the distance pass reads them: the scene as it stands, the uncut copy with UNCUT, label 0 everywhere
+ * while the context holds no labels of the volume's dimensions.  IN: the density byte lies in [min_byte, max_byte].  SEED(t): t lies
+ * in the box, and either IN and seed[label], or t is one of `points` (a point is a seed unconditionally).  MEDIUM(t): t lies in the
+ * box, IN and through[label].  steps(t) is 0 on a seed; otherwise, for a MEDIUM texel, the length k of the shortest chain
+ * s = p0, p1, ..., pk = t whose consecutive texels differ by 1 on exactly one axis, all in the box, s a seed, p1 .. pk MEDIUM; it is
+ * VOLYM_GEODESIC_NONE if there is no such chain, if k > max_steps, or if t is neither seed nor medium.  geo_label(t) is the smallest
+ * label byte among the seeds that have such a chain of exactly steps(t) to t, with the labels as they stand at the pass: a seed has
+ * its own label, any other reached texel the smallest geo_label among its neighbours that have steps - 1.
+ *   The map holds one key per texel of the box, box-linear with x fastest like the distance map: steps << 8 | geo_label, or
+ * VOLYM_GEODESIC_NONE.  key(t) = min over the neighbours u of key(u) + 256 is monotone and has exactly one fixed point under the
+ * step limit, so the same request on the same scene gives the same bytes in either device layout, whatever ran in which order.
+ *   Memory: 4 bytes per texel of the box for the keys, and 16 bytes per tile of 32 x 8 x 8 texels. */
+enum { VOLYM_GEODESIC_UNCUT = 1 };                  /* flags */
+#define VOLYM_GEODESIC_POINTS_MAX 64u
+#define VOLYM_GEODESIC_STEPS_MAX  0xfffffdu         /* 2^24 - 3: the largest step count a key holds */
+#define VOLYM_GEODESIC_BOX_MAX    0x7ffffffeu       /* texels of a box */
+#define VOLYM_GEODESIC_NONE       0xffffffffu       /* not reached */
+typedef struct volym_geodesic {
+    uint32_t box[6];            /* lo inclusive, hi exclusive, as volym_distance */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window of the medium and of the labelled seeds: min <= max <= 255 */
+    uint8_t  seed[256];         /* label -> != 0: its texels in the window are seeds */
+    uint8_t  through[256];      /* label -> != 0: its texels in the window are medium */
+    uint32_t max_steps;         /* 0: VOLYM_GEODESIC_STEPS_MAX; else 1..VOLYM_GEODESIC_STEPS_MAX */
+    uint32_t n_points;          /* 0..VOLYM_GEODESIC_POINTS_MAX */
+    uint32_t points[VOLYM_GEODESIC_POINTS_MAX][3];  /* seed texels, volume coordinates, inside box; duplicates allowed */
+} volym_geodesic;               /* 1324 bytes */
+struct volym_geodesic_summary {
+    uint64_t n_seed, n_medium, n_reached;   /* n_medium: MEDIUM and not SEED; n_reached: key != NONE, seeds included */
+    uint32_t max_steps;         /* the largest steps reached; VOLYM_GEODESIC_NONE when n_reached == 0 */
+    uint32_t max_at[3];         /* the first texel in ascending (z, y, x) that attains it, volume coordinates; {0, 0, 0}: none */
+    uint64_t cell[256];         /* reached texels by geo_label */
+    uint64_t cell_medium[256];  /* ... those of them that are not seeds: what a flood of everything would hand the label */
+    uint64_t hist[256];         /* reached texels by min(steps, 255) */
+};                              /* 6184 bytes */
+struct volym_geodesic_site { uint32_t steps, label; };   /* VOLYM_GEODESIC_NONE, 0 where not reached */
+/* The flood: a texel t of box with label l becomes n = to[g], g = geo_label(t) of the latest geodesic pass, iff give[l] != 0,
+ * key(t) is not NONE, take[g] != 0, n != l, its density byte lies in [min_byte, max_byte] (the scene byte as it stands, with UNCUT the
+ * uncut copy, as volym_edit_labels reads it) and steps_lo <= steps(t) <= steps_hi.  With `to` the identity it is the geodesic sibling
+ * of volym_fill_labels; `to` lets a wand work from an unlabelled click, where the seed's label is 0 and to[0] the new segment.  Every
+ * texel is decided from the snapshot and from its own bytes before the edit.  scene.flood_volume is the host twin. */
+enum { VOLYM_FLOOD_UNCUT = 1, VOLYM_FLOOD_DRY_RUN = 2 };  /* flags */
+typedef struct volym_flood {
+    uint32_t box[6];            /* as in volym_relabel; it must lie inside the box of the latest geodesic pass */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window, on the texel that would change */
+    uint8_t  give[256];         /* give[l] != 0: texels that carry l may change */
+    uint8_t  take[256];         /* take[g] != 0: texels whose geo_label is g may change */
+    uint8_t  to[256];           /* the label a texel of geo_label g becomes */
+    uint32_t steps_lo, steps_hi;/* lo <= hi: the band of steps(t); 0 .. 0xffffffff = no band */
+} volym_flood;                  /* 812 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_geodesic) == 1324, "volym_geodesic is 1324 bytes");
+static_assert(sizeof(struct volym_geodesic_summary) == 6184, "volym_geodesic_summary is 6184 bytes");
+static_assert(sizeof(struct volym_geodesic_site) == 8, "volym_geodesic_site is 8 bytes");
+static_assert(sizeof(volym_flood) == 812, "volym_flood is 812 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_geodesic) == 1324, "volym_geodesic is 1324 bytes");
+_Static_assert(sizeof(struct volym_geodesic_summary) == 6184, "volym_geodesic_summary is 6184 bytes");
+_Static_assert(sizeof(struct volym_geodesic_site) == 8, "volym_geodesic_site is 8 bytes");
+_Static_assert(sizeof(volym_flood) == 812, "volym_flood is 812 bytes");
+#endif
+/* A BLOCKING call, unlike the other passes: the rounds of its relaxation are enqueued in batches on the first slot's stream, and
+ * after each batch the host reads 4 bytes, the number of tiles still marked, and stops at 0.  g == NULL: the whole volume, window
+ * 1..255, every label but 0 a seed, label 0 the medium, no points.  It needs what volym_distance_pass needs.  The results are a
+ * snapshot: the reads below, and volym_flood_labels, stay valid after later edits of the scene.  No scene byte is written.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_geodesic_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions held
+ * in the other device layout than the volume.  VOLYM_E_HIP: a HIP error, or more rounds than the box has texels (a defect). */
+int   volym_geodesic_pass(volym_ctx* ctx, const volym_geodesic* g);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis or with more
+ * than VOLYM_GEODESIC_BOX_MAX texels, an unknown flag bit, a window without min_byte <= max_byte <= 255, max_steps or n_points above
+ * their maxima, a point outside the box.  An empty box (without points) is valid.  Pure host arithmetic. */
+int   volym_geodesic_check(const volym_geodesic* g, const uint32_t dims[3]);
+/* The reads block.  All: VOLYM_E_STATE before any pass, and after volym_set_volume until the next one; VOLYM_E_INVALID for a NULL
+ * ctx or output.  The map is of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi, inside the pass's box; NULL: the
+ * pass's whole box), box-linear in the sub-box.  volym_geodesic_at: the key of one texel of the pass's box, taken apart
+ * (VOLYM_E_INVALID for a texel outside that box). */
+int   volym_read_geodesic(volym_ctx* ctx, struct volym_geodesic_summary* out);
+int   volym_read_geodesic_map(volym_ctx* ctx, const uint32_t sub[6], uint32_t* out);
+int   volym_geodesic_at(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, struct volym_geodesic_site* out);
+/* The context's own results in device memory after a pass (NULL before any, and after volym_set_volume): the summary (a struct
+ * volym_geodesic_summary) and the key map of the latest pass's box. */
+void* volym_geodesic_device_ptr(volym_ctx* ctx);
+void* volym_geodesic_map_device_ptr(volym_ctx* ctx);
+/* The flood: a blocking set-up call with the contract of volym_edit_labels and volym_fill_labels (one kernel, in place, on the first
+ * slot's stream; with changed == 0, or DRY_RUN, nothing else is touched; out may be NULL).  While the history is on, a call that
+ * changes a texel (no DRY_RUN) is one step of it.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_flood_check refuses, a box that reaches outside the box of the geodesic pass.
+ * VOLYM_E_STATE: what volym_edit_labels refuses of the context's state; no volym_geodesic_pass since volym_set_volume.  The native
+ * multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_flood_labels(volym_ctx* ctx, const volym_flood* f, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
+ * bit, a window without min_byte <= max_byte <= 255, steps_lo > steps_hi.  An empty box is valid.  Pure host arithmetic. */
+int   volym_flood_check(const volym_flood* f, const uint32_t dims[3]);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

@@ -26,8 +26,8 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
---relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R, --shrink NAME:R, --fill [NAME,...][:R] and --separate NAME:R edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate); the PNG is the frame after them and
+--relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R, --shrink NAME:R, --fill [NAME,...][:R], --separate NAME:R, --flood [NAME,...][:R] and --wand-at X,Y:NAME:TOL[:R] edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate, grow_through, wand_at); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -342,6 +342,30 @@ def _fill_table(d, result):
     return "\n".join(lines)
 
 
+def _flood_table(d, result):
+    """what --flood prints: how many texels joined a segment through the matter, then every segment that took some"""
+    took = sorted(result["arrived"].items())
+    lines = ["flood: %d texels joined %d segments through the matter" % (result["changed"], len(took))]
+    for l, n in took:
+        lines.append("  + %-16s label %3d: %10d" % (d._segment_name(l) or "label %d" % l, l, n))
+    return "\n".join(lines)
+
+
+def _wand_arg(text):
+    """--wand-at X,Y:NAME:TOL[:R] -> (x, y, name, tolerance, r or None)"""
+    usage = "X,Y:NAME:TOL[:R] -- a pixel, the segment that takes what the wand reaches, the tolerance in density bytes and the reach in steps (default: no limit)"
+    parts = text.split(":")
+    try:
+        x, y = (int(v) for v in parts[0].split(","))
+        name, tol = parts[1], int(parts[2])
+        r = int(parts[3]) if len(parts) > 3 else None
+        if len(parts) > 4 or not name:
+            raise ValueError
+    except (ValueError, IndexError):
+        raise SystemExit("--wand-at: %s" % usage)
+    return x, y, name, tol, r
+
+
 def _label_edits(ctx, d, args):
     """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, lasso, split_at, keep_largest, grow, shrink):
     [(option, result)]"""
@@ -394,6 +418,12 @@ def _label_edits(ctx, d, args):
         if getattr(args, "separate", None):
             name, r = _name_and(args.separate, "--separate", "NAME:R -- a segment and the depth of its cores in texels")
             out.append(("separate", d.separate(ctx, _segment_arg(name), r)))
+        if getattr(args, "flood", None) is not None:
+            names, r = _fill_arg(args.flood)
+            out.append(("flood", d.grow_through(ctx, names, None if r is None else int(r), window=(1, 255))))
+        if getattr(args, "wand_at", None):
+            x, y, name, tol, r = _wand_arg(args.wand_at)
+            out.append(("wand", d.wand_at(ctx, x, y, _segment_arg(name), tol, r)))
     except ValueError as e:
         raise SystemExit("label edit: %s" % e)
     return out
@@ -509,6 +539,11 @@ def run_simple(args):
         import json
         if option == "fill":
             print(_fill_table(d, result))
+        elif option == "flood":
+            print(_flood_table(d, result))
+        elif option == "wand":
+            print("wand: %s" % ("nothing under the pixel" if result["relabel"] is None else "%d texels joined label %d, density %d..%d" % (
+                result["relabel"]["changed"], result["relabel"]["label"], result["relabel"]["window"][0], result["relabel"]["window"][1])))
         elif option == "separate":
             print("separate: %d pieces%s" % (len(result), "".join(", %s %d texels" % (p["name"], p["texels"]) for p in result)))
         print(json.dumps({option: result}))      # one line per label edit: texels changed, per label left and arrived, the hull
@@ -691,6 +726,12 @@ def main(argv=None):
                           "with a density byte above 0 joins the segment it is nearest to, at most R texels away (default: however far) (demo.Simple.fill); one undo step")
     run.add_argument("--separate", metavar="NAME:R", help="separate touching objects of the segment: its cores at depth R become segments of their own and the rest "
                                                           "goes to the nearest of them (demo.Simple.separate); after --fill")
+    run.add_argument("--flood", nargs="?", const="", metavar="NAME,...[:R]",
+                     help="grow the named segments (default: every segment) at once THROUGH the unlabelled matter of density above 0 on the device, after --separate: "
+                          "a texel joins the segment whose seed is the fewest 6-connected steps away, at most R (default: however far); gaps of air are no "
+                          "bridge (demo.Simple.grow_through); one undo step")
+    run.add_argument("--wand-at", metavar="X,Y:NAME:TOL[:R]", help="the magic wand: from the texel under pixel (X, Y) through the unlabelled matter whose density is within "
+                                                                    "TOL of that texel's, at most R steps, into segment NAME (demo.Simple.wand_at); after --flood")
     run.add_argument("--undo", type=int, metavar="N", help="keep a history of the label edits above on the device and take the last N back, before the "
                                                            "picture and --labels-out; each prints a JSON line {\"undo\": ...}")
     run.add_argument("--labels-out", help="FILE: write the labels as they stand after the edits, raw bytes in the orientation of --labels")

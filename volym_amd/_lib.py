@@ -371,6 +371,60 @@ class Fill(C.Structure):
     ]
 
 
+GEODESIC_UNCUT = 1                                             # volym_geodesic.flags
+GEODESIC_POINTS_MAX = 64
+GEODESIC_STEPS_MAX = 0xFFFFFD                                  # 2^24 - 3: the largest step count a key holds
+GEODESIC_BOX_MAX = 0x7FFFFFFE
+GEODESIC_NONE = 0xFFFFFFFF                                     # not reached
+FLOOD_UNCUT, FLOOD_DRY_RUN = 1, 2                              # volym_flood.flags
+
+
+class Geodesic(C.Structure):
+    """volym_geodesic (include/volym_hip.h): box, flags, window, the seed and through tables, the step limit and the points, 1324 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("seed", C.c_uint8 * 256),
+        ("through", C.c_uint8 * 256),
+        ("max_steps", C.c_uint32),
+        ("n_points", C.c_uint32),
+        ("points", (C.c_uint32 * 3) * GEODESIC_POINTS_MAX),
+    ]
+
+
+class GeodesicSummary(C.Structure):
+    """volym_geodesic_summary (include/volym_hip.h): counters, the maximum, the cells per label and the histogram of steps, 6184 bytes"""
+    _fields_ = [("n_seed", C.c_uint64), ("n_medium", C.c_uint64), ("n_reached", C.c_uint64), ("max_steps", C.c_uint32), ("max_at", C.c_uint32 * 3),
+                ("cell", C.c_uint64 * 256), ("cell_medium", C.c_uint64 * 256), ("hist", C.c_uint64 * 256)]
+
+
+class GeodesicSite(C.Structure):
+    """volym_geodesic_site (include/volym_hip.h): the key of one texel taken apart, 8 bytes"""
+    _fields_ = [("steps", C.c_uint32), ("label", C.c_uint32)]
+
+
+# the summary as a NumPy structured dtype (GpuContext.read_geodesic, scene.geodesic_volume)
+GEODESIC_SUMMARY_DTYPE = np.dtype([("n_seed", "<u8"), ("n_medium", "<u8"), ("n_reached", "<u8"), ("max_steps", "<u4"), ("max_at", "<u4", (3,)),
+                                   ("cell", "<u8", (256,)), ("cell_medium", "<u8", (256,)), ("hist", "<u8", (256,))])
+
+
+class Flood(C.Structure):
+    """volym_flood (include/volym_hip.h): box, flags, density window, the give, take and to tables and the band of one flood, 812 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("give", C.c_uint8 * 256),
+        ("take", C.c_uint8 * 256),
+        ("to", C.c_uint8 * 256),
+        ("steps_lo", C.c_uint32),
+        ("steps_hi", C.c_uint32),
+    ]
+
+
 class LassoView(C.Structure):
     """volym_lasso_view (include/volym_hip.h): the integer view texel -> (X, Y, D), 88 bytes"""
     _fields_ = [
@@ -606,6 +660,15 @@ SIGNATURES = {
     "volym_nearest_labels_device_ptr": (C.c_void_p, [_ctx]),
     "volym_fill_labels": (C.c_int, [_ctx, C.POINTER(Fill), C.POINTER(RelabelResult)]),
     "volym_fill_check": (C.c_int, [C.POINTER(Fill), C.POINTER(C.c_uint32)]),
+    "volym_geodesic_pass": (C.c_int, [_ctx, C.POINTER(Geodesic)]),
+    "volym_geodesic_check": (C.c_int, [C.POINTER(Geodesic), C.POINTER(C.c_uint32)]),
+    "volym_read_geodesic": (C.c_int, [_ctx, C.POINTER(GeodesicSummary)]),
+    "volym_read_geodesic_map": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_geodesic_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(GeodesicSite)]),
+    "volym_geodesic_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_geodesic_map_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_flood_labels": (C.c_int, [_ctx, C.POINTER(Flood), C.POINTER(RelabelResult)]),
+    "volym_flood_check": (C.c_int, [C.POINTER(Flood), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

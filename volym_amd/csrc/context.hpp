@@ -6,6 +6,7 @@
 //   pick.hip, outline.hip, slice.hip, project.hip, measure.hip, surface.hip, components.hip, distance.hip
 //                     the pass of that name
 //   nearest.hip       the nearest pass and the fill by it, an edit like those below
+//   geodesic.hip      the geodesic pass and the flood by it, an edit like those below
 //   relabel.hip, brush.hip, lasso.hip, smooth.hip
 //                     the label edit of that name (relabel.hip: and the history); what they share on the host is label_edit.hpp
 //   box_pass.hip      no ABI: what the passes over a request's box share -- the scan of row counts into offsets and the read-back
@@ -281,6 +282,13 @@ struct volym_ctx {
     uint32_t nearest_box[6] = {};            // the box of the latest pass (the reads and the fill address the maps by it)
     uint32_t nearest_weight[3] = {};         // ... and its weights (the fill's band is in its metric)
 
+    // geodesic passes (volym_geodesic_pass, geodesic.hip): a snapshot, valid until the next volym_set_volume
+    volym::OwnedBuffer<volym_geodesic_summary> geodesic;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> geodesic_map;       // the key of every texel of the request's box, box-linear; aliases no other pass's result
+    volym::OwnedBuffer<uint32_t> geodesic_tiles;     // the relaxation's state: a header, then per tile two round flags and two list entries (geodesic_kernels.h)
+    uint32_t geodesic_box[6] = {};           // the box of the latest pass (the reads and the flood address the map by it)
+    uint64_t geodesic_rounds = 0;            // the rounds the latest pass enqueued, those past the last active one included
+
     // the history of label edits (volym_label_history, relabel.hip): off (budget 0) in a new context
     struct LabelStep {
         uint32_t* index = nullptr;           // the chunks the edit stored ...
@@ -364,6 +372,8 @@ void free_components(volym_ctx* c);
 void free_distance(volym_ctx* c);
 // nearest.hip: what the context keeps for the nearest pass (every stream idle)
 void free_nearest(volym_ctx* c);
+// geodesic.hip: what the context keeps for the geodesic pass (every stream idle)
+void free_geodesic(volym_ctx* c);
 // relabel.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
 void clear_label_history(volym_ctx* c);
 // relabel.hip: the steps and the staging area of the label history (every stream idle)

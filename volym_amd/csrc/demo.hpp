@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstring>
 #include <fstream>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -265,6 +266,36 @@ public:
         f.d2_hi = r < 0.0 ? 0xffffffffu : static_cast<uint32_t>(std::floor(r * r + 1e-9));
         volym_relabel_result out{};
         ctx.check(volym_fill_labels(ctx.handle(), &f, &out));
+        records_current_ = false;
+        return out;
+    }
+    // New: grow several segments at once through the matter alone (volym_geodesic_pass, volym_flood_labels): one geodesic pass from
+    // the union of `names` (names, ids or label values as text; empty: every label but 0) through the unlabelled texels with a
+    // density byte above 0, at most r steps (r < 0: however far), then one flood -- every texel reached joins the segment whose seed
+    // is the fewest 6-connected steps away, the smallest label among equals.  A gap of air is no bridge.  One step of the history.
+    volym_relabel_result flood(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& names, double r)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "flood: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        if (r >= 0.0 && (r < 1.0 || r > static_cast<double>(VOLYM_GEODESIC_STEPS_MAX))) throw Error(VOLYM_E_INVALID, "flood: R is a number of steps, 1 at least");
+        auto g = std::make_unique<volym_geodesic>();       // (1324 bytes, zeroed)
+        g->box[3] = a.nx; g->box[4] = a.ny; g->box[5] = a.nz;
+        g->min_byte = 1u; g->max_byte = 255u;
+        if (names.empty()) std::memset(g->seed + 1, 1, 255);
+        for (const std::string& n : names) g->seed[label_value_of(a, n)] = 1u;
+        g->seed[0] = 0u;
+        g->through[0] = 1u;
+        g->max_steps = r < 0.0 ? 0u : static_cast<uint32_t>(r);
+        ctx.check(volym_geodesic_pass(ctx.handle(), g.get()));
+        volym_flood f{};
+        std::memcpy(f.box, g->box, sizeof f.box);
+        f.max_byte = 255u;
+        f.give[0] = 1u;
+        std::memcpy(f.take, g->seed, 256);
+        for (int l = 0; l < 256; ++l) f.to[l] = static_cast<uint8_t>(l);
+        f.steps_lo = 1u; f.steps_hi = 0xffffffffu;
+        volym_relabel_result out{};
+        ctx.check(volym_flood_labels(ctx.handle(), &f, &out));
         records_current_ = false;
         return out;
     }

@@ -1,5 +1,5 @@
 // What every label-edit kernel is made of, here once for the relabel (relabel_kernels.h), the brush (brush_kernels.h), the lasso
-// (lasso_kernels.h), the smoothing's vote (smooth_kernels.h) and the fill (nearest_kernels.h): the result's tally, the journal, the pieces of a chunk's edit
+// (lasso_kernels.h), the smoothing's vote (smooth_kernels.h), the fill (nearest_kernels.h) and the flood (geodesic_kernels.h): the result's tally, the journal, the pieces of a chunk's edit
 // (edit_prologue, ChunkCursor, chunk_candidates, chunk_in_window, chunk_apply, chunk_store) and the wave-at-a-time walk and tail of
 // the passes that select by geometry (wave_chunk_step, selected_chunk_tail), over the chunk walk of scene_chunks.h.  Device functions
 // and the structs they read only: no __global__ function, so every edit's unit includes it.

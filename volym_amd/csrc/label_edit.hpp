@@ -1,5 +1,5 @@
 // Internal: what the label edits share on the host -- relabel.hip (volym_edit_labels, the history, undo and redo), brush.hip, lasso.hip,
-// smooth.hip and nearest.hip (the fill).  The edit's transition as named pieces (begin_edit, edit_slab, DeviceResult, launch_label_swap, finish_edit), the
+// smooth.hip, nearest.hip (the fill) and geodesic.hip (the flood).  The edit's transition as named pieces (begin_edit, edit_slab, DeviceResult, launch_label_swap, finish_edit), the
 // transition of an edit in one kernel built from them (edit_labels, with the kernel as a parameter), and the three things every launch
 // site needs: edit_density, launch_edit and CallArray.  The pieces that are plain functions are defined once, in relabel.hip.  All of it
 // is blocking set-up path, like the other edits of the scene's bytes (scene_bytes.hip), whose seam (scene_bytes.hpp) it is built on.
@@ -19,7 +19,7 @@ constexpr uint64_t JOURNAL_RECORD_BYTES = 20u;          // a chunk index and 16 
 
 // What the edit's transition needs to know of a request, whichever kernel carries it out: the box its kernel walks and keeps to, the
 // table, DRY_RUN, the name errors carry, and the labels that may receive texels (begin_edit's receives[256]; NULL: those the table
-// moves texels to -- an edit whose new label does not come from the table, the fill, names its own).
+// moves texels to -- an edit whose new label does not come from the table, the fill or the flood, names its own).
 struct LabelEdit { const uint32_t* box; const uint8_t* to; bool dry; const char* who; const uint8_t* receives = nullptr; };
 
 // the working result of an edit, an undo or a redo in device memory: the result, then the journal's counter

@@ -914,6 +914,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     free_components(c);                     // (and the components' snapshot: its ids address texels of the old volume)
     free_distance(c);                       // (and the distance map, for the same reason)
     free_nearest(c);                        // (and the nearest pass's sites)
+    free_geodesic(c);                       // (and the geodesic pass's keys)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;

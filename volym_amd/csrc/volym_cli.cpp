@@ -21,6 +21,8 @@
 //   the first frame join TO (Simple::lasso), after --brush;
 //   --smooth [NAME,...][:R[,R,R]] smooths the segmentation: one pass of the majority filter over R texels (default 1) for the segments
 //   NAME against label 0, or jointly for every label without a name (Simple::smooth), after --lasso;
+//   --flood [NAME,...][:R] grows the segments NAME (none: every segment) at once THROUGH the unlabelled matter of density above 0: a
+//   texel joins the segment whose seed is the fewest 6-connected steps away, at most R steps (Simple::flood), after --fill;
 //   --fill [NAME,...][:R] grows the segments NAME (none: every segment) at once into the unlabelled matter: every unlabelled texel
 //   with a density byte above 0 joins the segment it is nearest to, at most R texels away (Simple::fill), after --smooth;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
@@ -85,6 +87,9 @@ struct Options {
     bool fill = false;                                   // --fill [NAME,...][:R]: the segments grow at once into the unlabelled matter (run simple)
     std::vector<std::string> fill_names;
     double fill_r = -1.0;                                // (below 0: however far)
+    bool flood = false;                                  // --flood [NAME,...][:R]: the segments grow at once through the unlabelled matter (run simple)
+    std::vector<std::string> flood_names;
+    double flood_r = -1.0;                               // (below 0: however far)
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -229,6 +234,8 @@ int run_simple(const Options& o)
     if (o.smooth) smoothed = demo.smooth(ctx, assets, o.smooth_names, o.smooth_radius);                     // after --lasso, before --undo
     volym_relabel_result filled{};
     if (o.fill) filled = demo.fill(ctx, assets, o.fill_names, o.fill_r);                                    // after --smooth, before --undo
+    volym_relabel_result flooded{};
+    if (o.flood) flooded = demo.flood(ctx, assets, o.flood_names, o.flood_r);                               // after --fill, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -263,6 +270,18 @@ int run_simple(const Options& o)
             std::string name = "label " + std::to_string(l);
             for (const SegmentInfo& s : assets.segments) if (s.label_value == l) name = s.name.empty() ? s.id : s.name;
             std::printf("  + %-16s label %3d: %10llu\n", name.c_str(), l, static_cast<unsigned long long>(filled.arrived[l]));
+        }
+    }
+    if (o.flood) {
+        // how many texels joined a segment through the matter, then every segment that took some
+        int took = 0;
+        for (int l = 0; l < 256; ++l) took += flooded.arrived[l] != 0u;
+        std::printf("flood: %llu texels joined %d segments through the matter\n", static_cast<unsigned long long>(flooded.changed), took);
+        for (int l = 0; l < 256; ++l) {
+            if (flooded.arrived[l] == 0u) continue;
+            std::string name = "label " + std::to_string(l);
+            for (const SegmentInfo& s : assets.segments) if (s.label_value == l) name = s.name.empty() ? s.id : s.name;
+            std::printf("  + %-16s label %3d: %10llu\n", name.c_str(), l, static_cast<unsigned long long>(flooded.arrived[l]));
         }
     }
     for (const auto& u : undone) {
@@ -549,6 +568,28 @@ int main(int argc, char** argv)
                         const std::string r = v.substr(colon + 1u);
                         o.fill_r = std::stod(r, &used);
                         if (used != r.size() || !(o.fill_r >= 0.0)) throw Error(VOLYM_E_INVALID, usage);
+                    } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
+                }
+            }
+            else if (a == "--flood") {
+                const char* usage = "--flood: [NAME,...][:R] -- the segments that grow through the unlabelled matter (none: every segment) and how many steps";
+                o.flood = true;
+                std::string v;
+                if (i + 1 < argc && argv[i + 1][0] != '-' && std::string(argv[i + 1]) != "run" && std::string(argv[i + 1]) != "benchmark") v = next();
+                const size_t colon = v.rfind(':');
+                const std::string names = colon == std::string::npos ? v : v.substr(0, colon);
+                size_t pos = 0;
+                while (pos < names.size()) {
+                    const size_t comma = std::min(names.find(',', pos), names.size());
+                    if (comma > pos) o.flood_names.push_back(names.substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+                if (colon != std::string::npos) {
+                    try {
+                        size_t used = 0;
+                        const std::string r = v.substr(colon + 1u);
+                        o.flood_r = std::stod(r, &used);
+                        if (used != r.size() || !(o.flood_r >= 1.0)) throw Error(VOLYM_E_INVALID, usage);
                     } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
                 }
             }

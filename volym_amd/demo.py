@@ -84,6 +84,7 @@ class GpuContext:
         self._volume_dims, self._components_box = (int(nx), int(ny), int(nz)), None      # (read_component_ids shapes its result by them)
         self._distance_box = None
         self._nearest_box = None
+        self._geodesic_box = None
 
     def set_importances(self, importances, dims):
         v = np.ascontiguousarray(importances, np.uint8).ravel()
@@ -603,6 +604,61 @@ class GpuContext:
         Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
         out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
         self._ck(_lib.lib().volym_fill_labels(self.handle, C.byref(fill.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
+    # ---- geodesic growth -------------------------------------------------------------------------
+    def geodesic_pass(self, geodesic=None):
+        """One geodesic pass (include/volym_hip.h volym_geodesic_pass; scene.geodesic_volume is its definition): for every texel of
+        the request's box the number of 6-connected steps through the medium to the nearest seed, and the smallest label among the
+        seeds that near, of the scene as it stands.  `geodesic` is a scene.Geodesic; None: the whole volume, window 1..255, every
+        label but 0 a seed, label 0 the medium.  Blocks, unlike the other passes: the host counts the rounds."""
+        g = None if geodesic is None else C.byref(geodesic.to_c())
+        self._ck(_lib.lib().volym_geodesic_pass(self.handle, g))
+        box = ((0, 0, 0), getattr(self, "_volume_dims", (0, 0, 0))) if geodesic is None else geodesic.box
+        self._geodesic_box = box if all(a < b for a, b in zip(*box)) else None
+
+    def read_geodesic(self):
+        """The summary of the latest geodesic pass: an np.void of _lib.GEODESIC_SUMMARY_DTYPE.  Blocks."""
+        out = np.zeros(1, _lib.GEODESIC_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_geodesic(self.handle, out.ctypes.data_as(C.POINTER(_lib.GeodesicSummary))))
+        return out[0]
+
+    def read_geodesic_map(self, sub=None):
+        """The keys of the latest geodesic pass (steps << 8 | geo_label; _lib.GEODESIC_NONE: not reached) as a uint32 array
+        [z, y, x]: of its whole box (None) or of the sub-box (lo, hi) in texels of the volume, which must lie inside the pass's
+        box.  Blocks."""
+        box = getattr(self, "_geodesic_box", None) if sub is None else (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        call = _lib.lib().volym_read_geodesic_map
+        if box is None:                                        # no pass yet (the library refuses), or a pass over an empty box
+            self._ck(call(self.handle, None, None))
+            return np.zeros((0, 0, 0), np.uint32)
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        out = np.zeros(tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0)), np.uint32)
+        self._ck(call(self.handle, c, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def geodesic_at(self, x, y, z):
+        """The key of texel (x, y, z) in the latest geodesic pass, taken apart: {"steps" (None: not reached), "label"}.  Blocks."""
+        out = _lib.GeodesicSite()
+        self._ck(_lib.lib().volym_geodesic_at(self.handle, int(x), int(y), int(z), C.byref(out)))
+        none = int(out.steps) == _lib.GEODESIC_NONE
+        return {"steps": None if none else int(out.steps), "label": int(out.label)}
+
+    def geodesic_device_ptr(self):
+        """The context's own summary (a volym_geodesic_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_geodesic_device_ptr(self.handle)
+
+    def geodesic_map_device_ptr(self):
+        """The key map of the latest geodesic pass in device memory (None before any)."""
+        return _lib.lib().volym_geodesic_map_device_ptr(self.handle)
+
+    def flood_labels(self, flood):
+        """One flood on the device (include/volym_hip.h volym_flood_labels; scene.flood_volume is its definition): a texel of the
+        box whose label gives becomes to[g], g its geo label in the latest geodesic pass, where the take table, the density window
+        and the band of steps say so.  `flood` is a scene.Flood.  Everything follows as after edit_labels, and the call is one step
+        of the history.  Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_flood_labels(self.handle, C.byref(flood.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
     # ---- editing labels --------------------------------------------------------------------------
@@ -1478,6 +1534,63 @@ class Simple(ComputeDemo):
         self._fill(ctx, scene.Fill(None, 0, (0, 255), scene.smooth_table([l]), scene.smooth_table(pieces), dims=self.dims))
         after = ctx.label_counts()
         return [{"name": self._segment_name(v), "label": v, "texels": int(after[v])} for v in pieces]
+
+    # ---- geodesic growth: steps through the matter ------------------------------------------------
+    def _flood(self, ctx, flood):
+        result = ctx.flood_labels(scene.check_flood(flood, self.dims))
+        if int(result["changed"]) and not flood.flags & _lib.FLOOD_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def reach(self, ctx, names, through=(0,), window=(1, 255), r=None):
+        """How far through the matter?  One geodesic pass from the union of the segments `names` (names, ids or label values; None:
+        every label but those of `through`) through the segments `through` (default: the unlabelled texels) with a density byte in
+        `window`, at most r steps (None: however far), and the read of its summary; the map stays on the device for
+        ctx.read_geodesic_map, ctx.geodesic_at and a flood.  Returns scene.geodesic_summary's dict, the cells by segment name.  The
+        labels go to the device first if they are not there yet."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        medium = self._label_values(through)
+        seeds = [l for l in (range(256) if names is None else self._label_values(names)) if l not in medium]
+        g = scene.check_geodesic(scene.Geodesic(None, 0, window, scene.smooth_table(seeds), scene.smooth_table(medium), 0 if r is None else int(r), dims=self.dims), self.dims)
+        ctx.geodesic_pass(g)
+        return scene.geodesic_summary(ctx.read_geodesic(), {l: self._segment_name(l) or "label %d" % l for l in range(256)})
+
+    def grow_through(self, ctx, names, r, into=(0,), window=(1, 255)):
+        """Grow several segments at once, each only through matter it touches: one geodesic pass from the union of `names` (None:
+        every label but those of `into`) through the segments `into` with a density byte in `window`, at most r steps (None:
+        however far), then one flood -- every texel reached joins the segment whose seed is the fewest steps away, the smallest label
+        among equals.  Where Simple.fill measures straight through anything, this stays inside the matter: an air gap is no
+        bridge.  One undo step.  Returns the result's dict."""
+        self._ready_to_edit(ctx)
+        gives = self._label_values(into)
+        seeds = [l for l in (range(256) if names is None else self._label_values(names)) if l not in gives]
+        limit = 0 if r is None else int(r)
+        if limit < 0 or (r is not None and limit == 0):
+            raise ValueError("grow_through: r is at least 1 step, or None")
+        ctx.geodesic_pass(scene.check_geodesic(scene.Geodesic(None, 0, window, scene.smooth_table(seeds), scene.smooth_table(gives), limit, dims=self.dims), self.dims))
+        return self._flood(ctx, scene.Flood(None, 0, (0, 255), scene.smooth_table(gives), scene.smooth_table(seeds), None, (1, 0xFFFFFFFF), dims=self.dims))
+
+    def wand_at(self, ctx, x, y, name, tolerance, r=None, over=(0,), alpha_min=0.5):
+        """The magic wand: pick pixel (x, y); the texel it shows is the one seed of a geodesic pass through the segments `over`
+        (default: the unlabelled texels) whose density byte lies within `tolerance` of the picked texel's, at most r steps (None:
+        however far); everything reached joins segment `name` (a name or id of the segments JSON, a label value, or a new name, as
+        in split_at), the picked texel included where its label is one of `over`.  Returns the pick with a "relabel" entry (the
+        result's dict, "label": the segment's label, "window"); None there when the pixel shows nothing."""
+        self._ready_to_edit(ctx)
+        p = self.pick(ctx, x, y, alpha_min)
+        p["relabel"] = None
+        if p["status"] == "hit" and p["texel"] is not None:
+            medium = self._label_values(over)
+            window = (max(int(p["density"]) - int(tolerance), 0), min(int(p["density"]) + int(tolerance), 255))
+            value = self._new_segment(ctx, name, p["label"] or 0)
+            ctx.geodesic_pass(scene.check_geodesic(scene.Geodesic(None, 0, window, scene.smooth_table([]), scene.smooth_table(medium), 0 if r is None else int(r),
+                                                                  [p["texel"]], dims=self.dims), self.dims))
+            # the seed carries the picked texel's label, whatever it is: every geo label takes, and all of them become `value`
+            p["relabel"] = self._flood(ctx, scene.Flood(None, 0, (0, 255), scene.smooth_table(medium), None, np.full(256, value, np.int64), dims=self.dims))
+            p["relabel"].update(label=value, window=window)
+        return p
 
     def _brush(self, ctx, brush):
         result = ctx.brush_labels(scene.check_brush(brush, self.dims))

@@ -2150,6 +2150,261 @@ def fill_volume(prepared, dims, fill, labels, sites, near_labels, pass_box, weig
     return new, result
 
 
+class Geodesic:
+    """volym_geodesic (include/volym_hip.h): what one geodesic pass maps.  box as Distance takes it; flags: _lib.GEODESIC_UNCUT;
+    window: (min_byte, max_byte) of the medium and of the labelled seeds; seed, through: tables of 256 bytes (smooth_table; None:
+    every label but 0 seeds, label 0 the medium); max_steps: 0 for no limit; points: seed texels (x, y, z) in volume coordinates."""
+
+    def __init__(self, box=None, flags=0, window=(1, 255), seed=None, through=None, max_steps=0, points=(), dims=None):
+        self.box = _box_or_whole(box, dims, "a geodesic request without a box needs the volume's dims")
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.seed = smooth_table(range(1, 256)) if seed is None else np.array(seed, np.int64).ravel()
+        self.through = smooth_table([0]) if through is None else np.array(through, np.int64).ravel()
+        self.max_steps = int(max_steps)
+        self.points = tuple(tuple(int(v) for v in p) for p in points)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "geodesic", ("box", "flags", "window", "seed", "through", "max_steps", "points"), kw)
+
+    def to_c(self):
+        """The _lib.Geodesic of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Geodesic()
+        c.box = _box_to_c(self.box, "geodesic")
+        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window) or not 0 <= self.max_steps < 2 ** 32:
+            raise ValueError("geodesic: flags, the window's ends and max_steps must be u32")
+        c.flags, c.max_steps = self.flags, self.max_steps
+        c.min_byte, c.max_byte = self.window
+        for name, t in (("seed", self.seed), ("through", self.through)):
+            if t.size != 256 or not ((t >= 0) & (t <= 255)).all():
+                raise ValueError("geodesic: %s is a table of 256 bytes" % name)
+            setattr(c, name, (C.c_uint8 * 256)(*[int(g) for g in t]))
+        if not all(len(p) == 3 and all(0 <= x < 2 ** 32 for x in p) for p in self.points):
+            raise ValueError("geodesic: a point is three u32")
+        c.n_points = len(self.points)                      # (the check refuses more than the struct holds; only those are copied)
+        for i, p in enumerate(self.points[:_lib.GEODESIC_POINTS_MAX]):
+            c.points[i] = (C.c_uint32 * 3)(*p)
+        return c
+
+
+def check_geodesic(geodesic, dims):
+    """The validity rules of volym_geodesic_check: lo <= hi <= dims on every axis (an empty box is valid), at most
+    _lib.GEODESIC_BOX_MAX texels, no flag but UNCUT, min_byte <= max_byte <= 255, max_steps <= _lib.GEODESIC_STEPS_MAX, at most
+    _lib.GEODESIC_POINTS_MAX points, every point inside the box.  Returns the request; raises ValueError."""
+    g = geodesic
+    lo, hi, dims = _box_in_dims(g.box, dims, "geodesic")
+    texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    if texels > _lib.GEODESIC_BOX_MAX:
+        raise ValueError("geodesic: the box has %d texels, more than 2^31 - 2" % texels)
+    if g.flags & ~_lib.GEODESIC_UNCUT or g.flags < 0:
+        raise ValueError("geodesic: unknown flag bits in %#x" % g.flags)
+    if len(g.window) != 2 or not 0 <= g.window[0] <= g.window[1] <= 255:
+        raise ValueError("geodesic: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (g.window,))
+    if not 0 <= g.max_steps <= _lib.GEODESIC_STEPS_MAX:
+        raise ValueError("geodesic: max_steps is 0 (no limit) or 1..%d, got %d" % (_lib.GEODESIC_STEPS_MAX, g.max_steps))
+    if len(g.points) > _lib.GEODESIC_POINTS_MAX:
+        raise ValueError("geodesic: %d points, more than %d" % (len(g.points), _lib.GEODESIC_POINTS_MAX))
+    for p in g.points:
+        if len(p) != 3 or not all(lo[a] <= p[a] < hi[a] for a in range(3)):
+            raise ValueError("geodesic: the point %r lies outside the box" % (p,))
+    if np.asarray(g.seed).size != 256 or np.asarray(g.through).size != 256:
+        raise ValueError("geodesic: seed and through have 256 entries")
+    return g
+
+
+def empty_geodesic():
+    """(summary, keys) of a pass over an empty box: nothing reached (an np.void of _lib.GEODESIC_SUMMARY_DTYPE) and no map."""
+    summary = np.zeros(1, _lib.GEODESIC_SUMMARY_DTYPE)[0]
+    summary["max_steps"] = _lib.GEODESIC_NONE
+    return summary, np.zeros((0, 0, 0), np.uint32)
+
+
+def geodesic_volume(prepared, dims, g, labels=None, cut=None, uncut=None):
+    """The definition of the geodesic pass (include/volym_hip.h volym_geodesic_pass), NumPy integers only; equal to the device in
+    every byte.  The arguments are distance_volume's.  Layer by layer: the seeds carry their label as layer 0; layer k is every
+    medium texel not reached yet that has a neighbour (one step along one axis, inside the box) in layer k - 1, and it takes the
+    smallest label among those neighbours; it ends with an empty layer or at max_steps.  Returns (summary, keys): an np.void of
+    _lib.GEODESIC_SUMMARY_DTYPE and the keys steps << 8 | geo_label (_lib.GEODESIC_NONE: not reached) as a uint32 array [z, y, x] over
+    the request's box."""
+    g = check_geodesic(g, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = g.box
+    summary, no_keys = empty_geodesic()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, no_keys
+    whole = bool(g.flags & _lib.GEODESIC_UNCUT)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("geodesic_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("geodesic_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    window = (b >= g.window[0]) & (b <= g.window[1])
+    seed = window & (np.asarray(g.seed)[l] != 0)
+    for p in g.points:
+        seed[p[2] - lo[2], p[1] - lo[1], p[0] - lo[0]] = True
+    medium = window & (np.asarray(g.through)[l] != 0)
+    far = np.int64(1) << np.int64(40)                          # above every key
+    key = np.where(seed, l.astype(np.int64), far)
+    layer = key.copy()                                         # the keys of the latest layer, `far` elsewhere
+    waiting = medium & ~seed
+    limit = g.max_steps or _lib.GEODESIC_STEPS_MAX
+    for _k in range(1, limit + 1):
+        if not waiting.any():
+            break
+        m = np.full(key.shape, far, np.int64)
+        for axis in range(3):
+            n = key.shape[axis]
+            if n < 2:
+                continue
+            a, c = [slice(None)] * 3, [slice(None)] * 3
+            a[axis], c[axis] = slice(1, n), slice(0, n - 1)
+            a, c = tuple(a), tuple(c)
+            np.minimum(m[a], layer[c], out=m[a])
+            np.minimum(m[c], layer[a], out=m[c])
+        new = waiting & (m < far)
+        if not new.any():
+            break
+        key[new] = m[new] + 256
+        waiting &= ~new
+        layer = np.where(new, key, far)
+    reached = key < far
+    keys = np.where(reached, key, np.int64(_lib.GEODESIC_NONE)).astype(np.uint32)
+    summary["n_seed"], summary["n_medium"], summary["n_reached"] = int(seed.sum()), int((medium & ~seed).sum()), int(reached.sum())
+    if reached.any():
+        steps = np.where(reached, key >> 8, -1)
+        at = int(np.argmax(steps))                              # (the first of the largest, in (z, y, x))
+        d, h, w = key.shape
+        summary["max_steps"] = int(steps.ravel()[at])
+        summary["max_at"][...] = (lo[0] + at % w, lo[1] + (at // w) % h, lo[2] + at // (w * h))
+        summary["cell"][...] = np.bincount((key[reached] & 0xFF), minlength=256)
+        summary["cell_medium"][...] = np.bincount((key[reached & ~seed] & 0xFF), minlength=256)
+        summary["hist"][...] = np.bincount(np.minimum(key[reached] >> 8, 255), minlength=256)
+    return summary, keys
+
+
+def geodesic_summary(summary, names=None):
+    """What a user reads off a geodesic pass, as Python ints: {"n_seed", "n_medium", "n_reached", "max_steps" (None: nothing
+    reached), "max_at", "cells": {label or name: {"label", "texels", "grown"}}} for every label with a cell -- `texels` of the box
+    were reached from it, `grown` of them are no seeds.  names: {label: name}."""
+    none = int(summary["n_reached"]) == 0
+    out = {"n_seed": int(summary["n_seed"]), "n_medium": int(summary["n_medium"]), "n_reached": int(summary["n_reached"]),
+           "max_steps": None if none else int(summary["max_steps"]), "max_at": None if none else tuple(int(v) for v in summary["max_at"]), "cells": {}}
+    for l in np.flatnonzero(np.asarray(summary["cell"])).tolist():
+        out["cells"][(names or {}).get(l, l)] = {"label": l, "texels": int(summary["cell"][l]), "grown": int(summary["cell_medium"][l])}
+    return out
+
+
+class Flood:
+    """volym_flood (include/volym_hip.h): one flood by the latest geodesic pass.  box and window as Relabel takes them; flags:
+    _lib.FLOOD_UNCUT | FLOOD_DRY_RUN; give, take: tables of 256 bytes (smooth_table; None: every label) -- the labels whose texels
+    may change and the geo labels whose texels may change; to: the label a texel of geo label g becomes (None: g itself; a dict
+    {g: label} changes the identity there); steps: (steps_lo, steps_hi), the band of the steps."""
+
+    def __init__(self, box=None, flags=0, window=(0, 255), give=None, take=None, to=None, steps=(0, 0xFFFFFFFF), dims=None):
+        self.box = _box_or_whole(box, dims, "a flood request without a box needs the volume's dims")
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.give = smooth_table() if give is None else np.array(give, np.int64).ravel()
+        self.take = smooth_table() if take is None else np.array(take, np.int64).ravel()
+        if to is None or isinstance(to, dict):
+            table = np.arange(256, dtype=np.int64)
+            for k, v in (to or {}).items():
+                table[int(k)] = int(v)
+            to = table
+        self.to = np.array(to, np.int64).ravel()
+        self.steps = tuple(int(v) for v in steps)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "flood", ("box", "flags", "window", "give", "take", "to", "steps"), kw)
+
+    def to_c(self):
+        """The _lib.Flood of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Flood()
+        c.box = _box_to_c(self.box, "flood")
+        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("flood: flags and the window's ends must be u32")
+        if len(self.steps) != 2 or not all(0 <= x < 2 ** 32 for x in self.steps):
+            raise ValueError("flood: steps is a pair of u32")
+        c.flags = self.flags
+        c.min_byte, c.max_byte = self.window
+        c.steps_lo, c.steps_hi = self.steps
+        for name, t in (("give", self.give), ("take", self.take), ("to", self.to)):
+            if t.size != 256 or not ((t >= 0) & (t <= 255)).all():
+                raise ValueError("flood: %s is a table of 256 bytes" % name)
+            setattr(c, name, (C.c_uint8 * 256)(*[int(g) for g in t]))
+        return c
+
+
+def check_flood(flood, dims):
+    """The validity rules of volym_flood_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, steps_lo <= steps_hi, tables of 256 entries.  Returns the request; raises ValueError."""
+    r = flood
+    _box_in_dims(r.box, dims, "flood")
+    if r.flags & ~(_lib.FLOOD_UNCUT | _lib.FLOOD_DRY_RUN) or r.flags < 0:
+        raise ValueError("flood: unknown flag bits in %#x" % r.flags)
+    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
+        raise ValueError("flood: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (r.window,))
+    if len(r.steps) != 2 or not 0 <= r.steps[0] <= r.steps[1]:
+        raise ValueError("flood: the band needs steps_lo <= steps_hi, got %r" % (r.steps,))
+    if np.asarray(r.give).size != 256 or np.asarray(r.take).size != 256 or np.asarray(r.to).size != 256:
+        raise ValueError("flood: give, take and to have 256 entries")
+    return r
+
+
+def flood_volume(prepared, dims, flood, labels, keys, pass_box, uncut=None):
+    """The definition of the flood (include/volym_hip.h volym_flood_labels), NumPy integers only; equal to the device in every byte.
+    `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None: prepared), `labels`: the
+    labels before the edit; keys: the snapshot of the latest geodesic pass (geodesic_volume's map) over pass_box = ((lo), (hi)).  A
+    texel of the box whose label gives becomes to[g], g its geo label, iff its key is not NONE, g takes, to[g] is not its label, its
+    density byte lies in the window and its steps lie in the band.  Returns (new_labels, result) as relabel_volume does."""
+    r = check_flood(flood, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("flood_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (r.flags & _lib.FLOOD_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("flood_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    slo, shi = (tuple(int(v) for v in pass_box[0]), tuple(int(v) for v in pass_box[1]))
+    if any(lo[a] < slo[a] or hi[a] > shi[a] for a in range(3)):
+        raise ValueError("flood_volume: the request's box reaches outside the box of the geodesic pass")
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    shape = (shi[2] - slo[2], shi[1] - slo[1], shi[0] - slo[0])
+    inner = (slice(lo[2] - slo[2], hi[2] - slo[2]), slice(lo[1] - slo[1], hi[1] - slo[1]), slice(lo[0] - slo[0], hi[0] - slo[0]))
+    key = np.asarray(keys, np.uint32).reshape(shape)[inner]
+    g, steps = (key & np.uint32(0xFF)).astype(np.int64), (key >> np.uint32(8)).astype(np.int64)
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    d = src.reshape(nz, ny, nx)[sub]
+    give, take = np.asarray(r.give) != 0, np.asarray(r.take) != 0
+    n = np.asarray(r.to).astype(np.uint8)[g]
+    hit = give[old] & (key != np.uint32(_lib.GEODESIC_NONE)) & take[g] & (n != old) & (d >= r.window[0]) & (d <= r.window[1]) & (steps >= r.steps[0]) & (steps <= r.steps[1])
+    count = int(hit.sum())
+    if count == 0:
+        return new, result
+    result["changed"] = count
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(n[hit], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not r.flags & _lib.FLOOD_DRY_RUN:
+        new[sub] = np.where(hit, n, old)
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
