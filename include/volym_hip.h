@@ -104,6 +104,12 @@ enum {
                                   and more of the empty ends of the rays.  The march loop does not read the grid.  A view with the
                                   cone look-ahead (use_importance_rendering and use_cone_importance_check) keeps the macro cells.  Blocking; with a
                                   volume on the device it rebuilds the grid, and every view gets a new mask. */
+    VOLYM_OPT_TEXEL_BYTES = 13, /* 1 (default) = a volume of 256 x 256 x 256 texels in the linear layout, marched by kernel 2 with opacity
+                                  on, the nearest filter and no importance mode, runs volym_raymarch_cube256_kernel: the texel address
+                                  is the three clamped coordinates as bytes side by side, one saturating conversion each
+                                  (raymarch_device.h texel256_insert; volym_selftest_texel256).  0 = the general kernel.  Same
+                                  pixels for either value; every other volume, flag set and the instrumented launch run the general
+                                  kernels whatever it is.  Takes effect with the next pass. */
     VOLYM_OPT_SETUP_IEEE = 10  /* 1 = the ray set-up (wgsl:221-241) runs its 14 divisions as 14 plain IEEE divisions; default 0: the
                                   divisions that share a denominator share its refined reciprocal -- the same instructions on the
                                   same values, so the same bits (raymarch_device.h make_ray; volym_selftest_ray_setup).  Takes
@@ -1420,6 +1426,16 @@ int volym_time_batch(volym_ctx* ctx, uint32_t n, float* ms_total);
  * for every pixel, compared bit for bit on the device.  out[0] = rays that differ in any bit of direction, entry, exit or hit
  * (must be 0), out[1] = rays of waves that fell back to the plain divisions, out[2] = rays.  Blocks. */
 int volym_selftest_ray_setup(volym_ctx* ctx, unsigned long long out[3]);
+/* Self-test of the texel selection of VOLYM_OPT_TEXEL_BYTES: clamp(floor(x), 0, 255) as the general kernels compute it
+ * (v_cvt_flr_i32_f32, v_med3_i32) against the saturating byte conversion (v_cvt_pk_u8_f32), on the device, for every float x of
+ * magnitude in [2^-10, 512) with both signs, +-0, the smallest and largest denormals, +-2^40, +-inf and four NaNs.
+ * out[0] = values other than NaN on which the form the library is built with differs (must be 0), out[1] = NaNs on which it differs,
+ * out[2], out[3] = the same two counts for the conversion with no floor in front of it, out[4] = values compared.  Needs no volume
+ * and no frame.  Blocks. */
+int volym_selftest_texel256(volym_ctx* ctx, unsigned long long out[5]);
+/* 1 when the latest compute pass ran volym_raymarch_cube256_kernel (VOLYM_OPT_TEXEL_BYTES), 0 when it ran a general kernel or
+ * there has been none. */
+int volym_texel_bytes_in_use(volym_ctx* ctx);
 
 #ifdef __cplusplus
 }

@@ -66,6 +66,9 @@
 #define OP_X46(i) "v_add_co_u32 %" #i ", vcc, %" #i ", %8\n"
 #define OP_X47(i) "v_mad_u32_u24 %" #i ", %" #i ", %8, %9\n"
 #define OP_X48(i) "v_mul_f32 %" #i ", %" #i ", %8\nv_and_b32 %" #i ", %" #i ", %9\n"
+// float -> u8 with saturation, inserted into one byte of the destination dword (the texel addresses of 256-cubed volumes)
+#define OP_X49(i) "v_cvt_pk_u8_f32 %" #i ", %8, 1, %" #i "\n"
+#define OP_X50(i) "v_floor_f32 %" #i ", %" #i "\nv_cvt_pk_u8_f32 %" #i ", %" #i ", 2, %9\n"
 template <int KIND>
 __global__ __launch_bounds__(1024) void rate_kernel(uint32_t* out, float x, float y, uint32_t sc)
 {
@@ -131,6 +134,8 @@ __global__ __launch_bounds__(1024) void rate_kernel(uint32_t* out, float x, floa
             if (KIND == 46) BODY8(OP_X46)
             if (KIND == 47) BODY8(OP_X47)
             if (KIND == 48) BODY8(OP_X48)
+            if (KIND == 49) BODY8(OP_X49)
+            if (KIND == 50) BODY8(OP_X50)
 
         }
     }
@@ -258,6 +263,8 @@ int main()
     RUN("v_add_co_u32", 46);
     RUN("v_mad_u32_u24 vgpr", 47);
     RUN("v_mul_f32+v_and mix", 48);
+    RUN("v_cvt_pk_u8_f32", 49);
+    RUN("floor+cvt_pk_u8 (x2)", 50);
 
 #define RUNPK(NAME, K) run(NAME, [&](int g, int T) { hipLaunchKernelGGL(rate_pk_kernel<K>, dim3(g), dim3(T), 0, 0, d_out, 1.0001f, 0.5f); }, d_out, n_cus)
     RUNPK("v_pk_mul_f32", 0);

@@ -17,6 +17,7 @@ OPT_VOLUME_LAYOUT, OPT_CULLING, OPT_COST_FEEDBACK, OPT_DEPTH_PARALLEL, OPT_XCD_B
 OPT_SETUP_IEEE = 10
 OPT_FRAMES_IN_FLIGHT = 11
 OPT_BOUNDS_CELLS = 12
+OPT_TEXEL_BYTES = 13
 
 
 class VolymError(RuntimeError):
@@ -673,6 +674,8 @@ SIGNATURES = {
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_selftest_ray_setup": (C.c_int, [_ctx, C.POINTER(C.c_ulonglong)]),
+    "volym_selftest_texel256": (C.c_int, [_ctx, C.POINTER(C.c_ulonglong)]),
+    "volym_texel_bytes_in_use": (C.c_int, [_ctx]),
     # include/volym_host.h
     "volym_camera_default_with_aspect_and_pos": (None, [C.POINTER(CCamera), C.c_float, _f32p]),
     "volym_camera_orbit": (None, [C.POINTER(CCamera), C.c_float, C.c_float, C.c_float]),

@@ -321,6 +321,8 @@ struct volym_ctx {
     uint32_t wgs_per_cu = 1;
     bool culling = true;
     bool setup_ieee = false;                    // VOLYM_OPT_SETUP_IEEE: make_ray with plain divisions (FrameParams::setup_lo = +inf)
+    bool texel_bytes = true;                    // VOLYM_OPT_TEXEL_BYTES: 256-cubed linear volumes march in volym_raymarch_cube256_kernel
+    bool last_march_cube256 = false;            // ... and whether the latest plain launch of kernel 2 was that kernel (volym_texel_bytes_in_use)
     bool straight_jobs = false;                 // dev switch (option 121): CJ = 2 instantiation for the straight look-ahead
     bool lds_bricks = false;        // dev option 122: LDS-staged bricks in the common instantiation (bricked layout)
     volym_camera_uniforms cam_copy;

@@ -32,6 +32,9 @@ namespace volym {
 extern template __global__ void volym_raymarch_pq_kernel<true, false, false, 4, false, false, false, PQ_WAVES, 0, false, true>(
     const uint8_t* __restrict__, const uint8_t* __restrict__, const FrameTables* __restrict__, const uint8_t* __restrict__, const uint2* __restrict__, uint32_t,
     uint16_t* __restrict__, uint32_t* __restrict__, uint32_t* __restrict__, float4* __restrict__, Counters* __restrict__, uint4* __restrict__, const FrameParams);
+extern template __global__ void volym_raymarch_cube256_kernel<true, false, false, 4, false, false, false, PQ_WAVES, 0, false, true>(
+    const uint8_t* __restrict__, const uint8_t* __restrict__, const FrameTables* __restrict__, const uint8_t* __restrict__, const uint2* __restrict__, uint32_t,
+    uint16_t* __restrict__, uint32_t* __restrict__, uint32_t* __restrict__, float4* __restrict__, Counters* __restrict__, uint4* __restrict__, const FrameParams);
 }  // namespace volym
 
 using namespace volym;
@@ -713,6 +716,10 @@ int volym_set_option(volym_ctx* c, int key, int value)
         if (value != 0 && value != 1) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_SETUP_IEEE: 0 or 1");
         c->setup_ieee = value == 1;       // read by the next volym_update
         return VOLYM_OK;
+    case VOLYM_OPT_TEXEL_BYTES:
+        if (value != 0 && value != 1) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_TEXEL_BYTES: 0 or 1");
+        c->texel_bytes = value == 1;      // read by the next launch
+        return VOLYM_OK;
     case VOLYM_OPT_XCD_BANDS:
         if (value < 0 || value > 64) return fail(c, VOLYM_E_INVALID, "VOLYM_OPT_XCD_BANDS: 0..64");
         c->xcd_bands = static_cast<uint32_t>(value);
@@ -1084,7 +1091,13 @@ static int launch_march(volym_ctx* c, FrameSlot& s)
             else if (table) VOLYM_PQ_LAUNCH_W(true, 4, true, true, false);
             else VOLYM_PQ_LAUNCH_W(false, 1, true, true, false);
         } else {
-            if (table && no_imp) VOLYM_PQ_LAUNCH(true, 4, false, false, false, PQ_WAVES);
+            // the headline instantiation's twin for 256 texels on every axis (raymarch_pq.h CUBE256): plain launches only
+            const bool cube256 = table && no_imp && plain && c->texel_bytes && fp.nx == 256u && fp.ny == 256u && fp.nz == 256u;
+            if (plain) c->last_march_cube256 = cube256;
+            if (cube256)
+                hipLaunchKernelGGL((volym_raymarch_cube256_kernel<true, false, false, 4, false, false, false, PQ_WAVES, 0, false, true>), dim3(pgrid), dim3(PQ_WAVES * 64), 0, s.stream, c->d_vol, c->d_imp, s.d_tables, s.d_df,
+                                   reinterpret_cast<const uint2*>(s.d_list[s.cur]), n_items, cost_out, d_shard, d_frame, s.d_f32, cnt, trace, fp);
+            else if (table && no_imp) VOLYM_PQ_LAUNCH(true, 4, false, false, false, PQ_WAVES);
             else if (table && ir && cone_jobs) VOLYM_PQ_LAUNCH_J(true, 4, false, false, true, PQ_WAVES, 1);
 #if VOLYM_DEV_SWITCHES
             else if (table && ir && straight_jobs) VOLYM_PQ_LAUNCH_J(true, 4, false, false, true, PQ_WAVES, 2);
@@ -1461,6 +1474,29 @@ int volym_selftest_ray_setup(volym_ctx* c, unsigned long long out[3])
     HIPCHK(c, hipStreamSynchronize(s.stream));
     out[0] = h.n_vol; out[1] = h.n_imp; out[2] = h.n_steps;
     return VOLYM_OK;
+}
+
+// Both forms of the texel selection of a 256-texel axis (raymarch_device.h texel256_insert), compared on the device over every float
+// of magnitude in [2^-10, 512) and the special values.  out: volym_texel256_selftest_kernel's five counts.
+int volym_selftest_texel256(volym_ctx* c, unsigned long long out[5])
+{
+    if (!c || !out) return VOLYM_E_INVALID;
+    FrameSlot& s = c->slot0();
+    HIPCHK(c, hipSetDevice(c->device));
+    static_assert(sizeof(Counters) == 5 * sizeof(unsigned long long), "counters");
+    HIPCHK(c, hipMemsetAsync(s.d_counters, 0, sizeof(Counters), s.stream));
+    volym_texel256_selftest_kernel<<<4096, 256, 0, s.stream>>>(reinterpret_cast<unsigned long long*>(s.d_counters));
+    HIPCHK(c, hipGetLastError());
+    Counters h;
+    HIPCHK(c, hipMemcpyAsync(&h, s.d_counters, sizeof h, hipMemcpyDeviceToHost, s.stream));
+    HIPCHK(c, hipStreamSynchronize(s.stream));
+    out[0] = h.n_vol; out[1] = h.n_imp; out[2] = h.n_steps; out[3] = h.n_dense; out[4] = h.n_hit;
+    return VOLYM_OK;
+}
+
+int volym_texel_bytes_in_use(volym_ctx* c)
+{
+    return c && c->last_march_cube256 ? 1 : 0;
 }
 
 int volym_time_batch(volym_ctx* c, uint32_t n, float* ms_total)

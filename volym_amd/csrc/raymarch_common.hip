@@ -18,4 +18,9 @@ template __global__ void volym_raymarch_pq_kernel<true, false, false, 4, false, 
     const uint8_t* __restrict__, const uint8_t* __restrict__, const FrameTables* __restrict__, const uint8_t* __restrict__, const uint2* __restrict__, uint32_t,
     uint16_t* __restrict__, uint32_t* __restrict__, uint32_t* __restrict__, float4* __restrict__, Counters* __restrict__, uint4* __restrict__, const FrameParams);
 
+// its twin for volumes of 256 texels on every axis (raymarch_pq.h, CUBE256): the same flags, the same scheduler
+template __global__ void volym_raymarch_cube256_kernel<true, false, false, 4, false, false, false, PQ_WAVES, 0, false, true>(
+    const uint8_t* __restrict__, const uint8_t* __restrict__, const FrameTables* __restrict__, const uint8_t* __restrict__, const uint2* __restrict__, uint32_t,
+    uint16_t* __restrict__, uint32_t* __restrict__, uint32_t* __restrict__, float4* __restrict__, Counters* __restrict__, uint4* __restrict__, const FrameParams);
+
 }  // namespace volym

@@ -187,9 +187,12 @@ __device__ __forceinline__ float dot_fast(V3 a, V3 b)
 //            the importance volume beside it, BASELINE configs[4] on one GPU, 584 -> 284 us).
 __host__ __device__ inline uint32_t brick_count(uint32_t n) { return (n + 3u) >> 2; }
 
-template <bool BRICK>
+// CUBE256: the compile-time tag "linear layout, 256 texels on every axis" (texel256_* below)
+template <bool BRICK, bool CUBE256 = false>
 struct GridT {
     static constexpr bool bricked = BRICK;
+    static constexpr bool cube256 = CUBE256;
+    static_assert(!(BRICK && CUBE256), "the packed texel address is the linear layout's");
     const uint8_t* __restrict__ vol;
     const uint8_t* __restrict__ imp;
     int nx, ny, nz;
@@ -263,9 +266,31 @@ __device__ __forceinline__ uint32_t voxel_offset(const G& g, int ix, int iy, int
     }
 }
 
+// 256 texels on an axis (G::cube256): the clamp range 0..255 is a byte's range and the linear offset x + 256*(y + 256*z) is the
+// three bytes side by side.  v_cvt_pk_u8_f32 converts a float to u8 with saturation and inserts it into byte BYTE of `old`:
+// convert, clamp and pack of one coordinate in one instruction, where the general form needs v_cvt_flr_i32_f32, v_med3_i32 and a
+// share of two v_mad_u32_u24.  `scaled` is u * fn as texel_nearest forms it (EXACT, unchanged).  The floor in front of it is
+// needed: the conversion rounds to nearest (volym_selftest_texel256, FLOOR = false: 41.9 M of 3.2e8 values differ).  With it, floor
+// of a float is exact, the conversion of an integer-valued float is exact under any rounding and saturation to 0..255 is the
+// clamp: the same texel as texel_nearest for every input but NaN (the self-test: no difference; no position is NaN).
+template <int BYTE, bool FLOOR = true>
+__device__ __forceinline__ uint32_t texel256_insert(float scaled, uint32_t old)
+{
+    static_assert(BYTE >= 0 && BYTE <= 2, "x in byte 0, y in byte 1, z in byte 2");
+    return __builtin_amdgcn_cvt_pk_u8_f32(FLOOR ? __builtin_floorf(scaled) : scaled, static_cast<uint32_t>(BYTE), old);
+}
+// the offset of the texel of the scaled position (sx, sy, sz)
+template <bool FLOOR = true>
+__device__ __forceinline__ uint32_t texel256_offset(float sx, float sy, float sz)
+{
+    return texel256_insert<2, FLOOR>(sz, texel256_insert<1, FLOOR>(sy, texel256_insert<0, FLOOR>(sx, 0u)));
+}
+
 template <class G>
 __device__ __forceinline__ uint32_t nearest_offset(const G& g, V3 p)
 {
+    if constexpr (G::cube256) return texel256_offset(p.x * g.fnx, p.y * g.fny, p.z * g.fnz);
+    else
     return voxel_offset(g, texel_nearest(p.x, g.fnx, g.hix), texel_nearest(p.y, g.fny, g.hiy),
                         texel_nearest(p.z, g.fnz, g.hiz));
 }

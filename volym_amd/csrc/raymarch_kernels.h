@@ -469,6 +469,49 @@ __global__ __launch_bounds__(256) void volym_ray_setup_selftest_kernel(FramePara
     }
 }
 
+// volym_selftest_texel256: the texel of a scaled coordinate x = u * 256 in both forms -- v_cvt_flr_i32_f32 + v_med3_i32 0..255 as
+// texel_nearest has it, and the saturating byte conversion of texel256_insert -- for every float of magnitude in [2^-10, 512), both
+// signs, and a handful of special values.  One value per thread and round.
+// out[0] / out[1]: values that are not / are NaN on which the form the march kernel uses (a floor in front of the conversion) differs,
+// out[2] / out[3]: the same for the conversion without a floor in front of it, out[4]: values.
+constexpr uint32_t TEXEL256_SWEEP_LO = 0x3a800000u, TEXEL256_SWEEP_HI = 0x44000000u;        // 2^-10, 512
+constexpr uint32_t TEXEL256_SWEEP_N = TEXEL256_SWEEP_HI - TEXEL256_SWEEP_LO;
+constexpr uint32_t TEXEL256_N_SPECIAL = 16u;
+__global__ __launch_bounds__(256) void volym_texel256_selftest_kernel(unsigned long long* __restrict__ out)
+{
+    const uint32_t special[TEXEL256_N_SPECIAL] = {0x00000000u, 0x80000000u, 0x00000001u, 0x80000001u, 0x007fffffu, 0x807fffffu, 0x53800000u, 0xd3800000u,   // +-0, denormal ends, +-2^40
+                                                  0x7f800000u, 0xff800000u, 0x7fc00000u, 0xffc00000u, 0x7f800001u, 0xff800001u, 0x7fffffffu, 0xffffffffu};   // +-inf, NaNs
+    const unsigned long long total = 2ull * TEXEL256_SWEEP_N + TEXEL256_N_SPECIAL;
+    uint32_t bad[4] = {0u, 0u, 0u, 0u}, seen = 0u;
+    for (unsigned long long i = static_cast<unsigned long long>(blockIdx.x) * 256u + threadIdx.x; i < total; i += static_cast<unsigned long long>(gridDim.x) * 256u) {
+        uint32_t bits;
+        if (i < 2ull * TEXEL256_SWEEP_N) {
+            const uint32_t k = static_cast<uint32_t>(i);
+            bits = k < TEXEL256_SWEEP_N ? TEXEL256_SWEEP_LO + k : (TEXEL256_SWEEP_LO + (k - TEXEL256_SWEEP_N)) | 0x80000000u;
+        } else {
+            bits = special[0];
+#pragma unroll
+            for (uint32_t j = 1; j < TEXEL256_N_SPECIAL; ++j) bits = i - 2ull * TEXEL256_SWEEP_N == j ? special[j] : bits;
+        }
+        const float x = __uint_as_float(bits);
+        const uint32_t r = static_cast<uint32_t>(clamp_texel(floor_to_int(x), 255));
+        const uint32_t ref = r | (r << 8) | (r << 16);
+        // the form in use: the three bytes of an offset, and an insert into a dword whose other bytes are set
+        const bool same_used = texel256_offset(x, x, x) == ref && texel256_insert<1>(x, 0x00a5005au) == (0x00a5005au | (r << 8));
+        const bool same_bare = texel256_offset<false>(x, x, x) == ref;
+        const bool nan = x != x;
+        bad[0] += !same_used && !nan ? 1u : 0u; bad[1] += !same_used && nan ? 1u : 0u;
+        bad[2] += !same_bare && !nan ? 1u : 0u; bad[3] += !same_bare && nan ? 1u : 0u;
+        seen++;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (bad[k]) atomicAdd(&out[k], static_cast<unsigned long long>(bad[k]));
+    unsigned long long n = seen;
+    for (int s = 32; s > 0; s >>= 1) n += __shfl_xor(n, s, 64);
+    if ((threadIdx.x & 63u) == 0u) atomicAdd(&out[4], n);
+}
+
 __global__ __launch_bounds__(256) void volym_tile_mask_kernel(const uint8_t* __restrict__ mc_max, uint32_t mc_n, uint32_t thr_byte, ClipMatrix M,
                                                               float margin, uint32_t W, uint32_t H, uint32_t t8x, uint32_t n_words,
                                                               uint32_t* __restrict__ out)

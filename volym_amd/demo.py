@@ -763,6 +763,17 @@ class GpuContext:
         self._ck(_lib.lib().volym_selftest_ray_setup(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def selftest_texel256(self):
+        """(values on which the byte conversion in use differs from clamp(floor(x), 0, 255), NaNs on which it does, the same two counts
+        for the conversion without a floor, values compared)."""
+        out = (C.c_ulonglong * 5)()
+        self._ck(_lib.lib().volym_selftest_texel256(self.handle, out))
+        return tuple(int(v) for v in out)
+
+    def texel_bytes_in_use(self):
+        """whether the latest compute pass ran the kernel of 256-cubed volumes (VOLYM_OPT_TEXEL_BYTES)"""
+        return bool(_lib.lib().volym_texel_bytes_in_use(self.handle))
+
     def time_batch(self, n):
         """n back-to-back passes between one pair of HIP events: total milliseconds."""
         ms = C.c_float(0.0)
