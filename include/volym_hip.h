@@ -29,8 +29,9 @@
  *     volym_read_component_table, volym_read_component_ids and volym_component_of block (they are volym_read_* in all but name);
  *     volym_distance_pass blocks only when it has to allocate or grow its buffers; volym_read_distance, volym_read_distance_map
  *     and volym_distance_at block; volym_nearest_pass, its reads and volym_nearest_at likewise; volym_geodesic_pass BLOCKS (it
- *     reads 4 bytes after every batch of its rounds), and so do its reads and volym_geodesic_at; volym_edit_labels and the other
- *     label edits (brush, lasso, smooth, fill, flood) are set-up calls and block like volym_set_*.
+ *     reads 4 bytes after every batch of its rounds), and so do its reads and volym_geodesic_at; volym_cost_pass BLOCKS in the
+ *     same way, and so do its reads and volym_cost_at; volym_edit_labels and the other
+ *     label edits (brush, lasso, smooth, fill, flood, spread) are set-up calls and block like volym_set_*.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -1413,6 +1414,118 @@ int   volym_flood_labels(volym_ctx* ctx, const volym_flood* f, struct volym_rela
 /* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, an unknown flag
  * bit, a window without min_byte <= max_byte <= 255, steps_lo > steps_hi.  An empty box is valid.  Pure host arithmetic. */
 int   volym_flood_check(const volym_flood* f, const uint32_t dims[3]);
+
+/* --- grow from seeds: cost-weighted growth through the matter, and the spread by it (new; the reference has none) -------- */
+/* Where two growing segments meet is for the image to say: a step through the medium costs more the more the density changes
+ * across it, and each texel goes to the seed it can be reached from most cheaply.  A read-only pass over the bytes of the scene
+ * as they stand, the sibling of volym_geodesic_pass, whose steps all cost the same.
+ *   The rule (integers only; scene.cost_volume of the Python package is its host twin, equal in every byte).  IN, SEED(t) and
+ * MEDIUM(t) are exactly those of volym_geodesic above -- the box, the window [min_byte, max_byte], the seed and through tables, the
+ * points (seeds unconditionally), UNCUT -- and the density byte b(t) and the label are read as that pass reads them.  A step from
+ * a texel u to a texel t that differs from it by 1 on exactly one axis, both in the box, costs
+ *     step(u, t) = step_cost + contrast_cost * |b(t) - b(u)|        (1 <= step_cost <= 255, 0 <= contrast_cost <= 255),
+ * at most 255 + 255 * 255 = 65 280, and the same in either direction.  cost(t) is 0 on a seed; otherwise, for a MEDIUM texel, the
+ * smallest sum of step costs over the chains s = p0, p1, ..., pk = t of such steps, s a seed, p1 .. pk MEDIUM.  cost_label(t) is
+ * the smallest label byte among the seeds that have a chain of exactly cost(t) to t, with the labels as they stand at the pass.
+ * The key is cost << 8 | cost_label; it is VOLYM_COST_NONE if there is no chain, if t is neither seed nor medium, or if
+ * cost(t) > max_cost (0: VOLYM_COST_MAX).  A chain within the limit has only prefixes within it (costs are not negative), so the
+ * map under a limit is the map without one, cut off.
+ *   The map holds one key per texel of the box, box-linear with x fastest.  key(t) = min over the neighbours u of
+ * key(u) + (step(u, t) << 8) is monotone, and because every step costs at least 1 it has exactly one fixed point under the limit:
+ * the same request on the same scene gives the same bytes in either device layout, whatever ran in which order.  The sum can pass
+ * 2^32 where key + 256 could not: it is formed saturating at 2^32 - 1 = VOLYM_COST_NONE, which is above every admitted key.
+ *   Memory: 5 bytes per texel of the box (the keys, and the density bytes the relaxation reads), and 16 bytes per tile of
+ * 32 x 8 x 8 texels. */
+enum { VOLYM_COST_UNCUT = 1 };                      /* flags */
+#define VOLYM_COST_POINTS_MAX 64u
+#define VOLYM_COST_MAX        0xfffffdu             /* 2^24 - 3: the largest cost a key holds */
+#define VOLYM_COST_STEP_MAX   65280u                /* 255 + 255 * 255: the most one step costs */
+#define VOLYM_COST_BOX_MAX    0x7ffffffeu           /* texels of a box */
+#define VOLYM_COST_NONE       0xffffffffu           /* not reached */
+#define VOLYM_COST_HIST_SHIFT_MAX 16u
+typedef struct volym_cost {
+    uint32_t box[6];            /* lo inclusive, hi exclusive, as volym_geodesic */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window of the medium and of the labelled seeds: min <= max <= 255 */
+    uint8_t  seed[256];         /* label -> != 0: its texels in the window are seeds */
+    uint8_t  through[256];      /* label -> != 0: its texels in the window are medium */
+    uint32_t max_cost;          /* 0: VOLYM_COST_MAX; else 1..VOLYM_COST_MAX */
+    uint32_t n_points;          /* 0..VOLYM_COST_POINTS_MAX */
+    uint32_t points[VOLYM_COST_POINTS_MAX][3];      /* seed texels, volume coordinates, inside box; duplicates allowed */
+    uint32_t step_cost;         /* 1..255: what every step costs */
+    uint32_t contrast_cost;     /* 0..255: what every unit of |b(t) - b(u)| adds; 0 with step_cost 1 is the geodesic pass */
+    uint32_t hist_shift;        /* 0..16: the summary's histogram bins by min(cost >> hist_shift, 255) */
+} volym_cost;                   /* 1336 bytes */
+struct volym_cost_summary {
+    uint64_t n_seed, n_medium, n_reached;   /* n_medium: MEDIUM and not SEED; n_reached: key != NONE, seeds included */
+    uint32_t max_cost;          /* the largest cost reached; VOLYM_COST_NONE when n_reached == 0 */
+    uint32_t max_at[3];         /* the first texel in ascending (z, y, x) that attains it, volume coordinates; {0, 0, 0}: none */
+    uint64_t cell[256];         /* reached texels by cost_label */
+    uint64_t cell_medium[256];  /* ... those of them that are not seeds: what a spread of everything would hand the label */
+    uint64_t hist[256];         /* reached texels by min(cost >> hist_shift, 255) */
+};                              /* 6184 bytes */
+struct volym_cost_site { uint32_t cost, label; };    /* VOLYM_COST_NONE, 0 where not reached */
+/* The spread: volym_flood_labels' rule read from the cost snapshot.  A texel t of box with label l becomes n = to[g],
+ * g = cost_label(t) of the latest cost pass, iff give[l] != 0, key(t) is not NONE, take[g] != 0, n != l, its density byte lies in
+ * [min_byte, max_byte] (the scene byte as it stands, with UNCUT the uncut copy) and cost_lo <= cost(t) <= cost_hi.  Every texel is
+ * decided from the snapshot and from its own bytes before the edit.  scene.spread_volume is the host twin. */
+enum { VOLYM_SPREAD_UNCUT = 1, VOLYM_SPREAD_DRY_RUN = 2 };  /* flags */
+typedef struct volym_spread {
+    uint32_t box[6];            /* as in volym_relabel; it must lie inside the box of the latest cost pass */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window, on the texel that would change */
+    uint8_t  give[256];         /* give[l] != 0: texels that carry l may change */
+    uint8_t  take[256];         /* take[g] != 0: texels whose cost_label is g may change */
+    uint8_t  to[256];           /* the label a texel of cost_label g becomes */
+    uint32_t cost_lo, cost_hi;  /* lo <= hi: the band of cost(t); 0 .. 0xffffffff = no band */
+} volym_spread;                 /* 812 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_cost) == 1336, "volym_cost is 1336 bytes");
+static_assert(sizeof(struct volym_cost_summary) == 6184, "volym_cost_summary is 6184 bytes");
+static_assert(sizeof(struct volym_cost_site) == 8, "volym_cost_site is 8 bytes");
+static_assert(sizeof(volym_spread) == 812, "volym_spread is 812 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_cost) == 1336, "volym_cost is 1336 bytes");
+_Static_assert(sizeof(struct volym_cost_summary) == 6184, "volym_cost_summary is 6184 bytes");
+_Static_assert(sizeof(struct volym_cost_site) == 8, "volym_cost_site is 8 bytes");
+_Static_assert(sizeof(volym_spread) == 812, "volym_spread is 812 bytes");
+#endif
+/* A BLOCKING call, as volym_geodesic_pass is: the rounds of its relaxation are enqueued in batches on the first slot's stream, and
+ * after each batch the host reads 4 bytes, the number of tiles still marked, and stops at 0.  q == NULL: the whole volume, window
+ * 1..255, every label but 0 a seed, label 0 the medium, no points, step_cost 1, contrast_cost 16, no limit, hist_shift 4.  It needs
+ * what volym_distance_pass needs.  The results are a snapshot of the pass's own -- summary, key map, the density bytes of the box
+ * as the pass read them, tile state and box; it aliases no other pass's buffers -- so the reads below, and volym_spread_labels,
+ * stay valid after later edits, tables, cuts and volym_set_labels; volym_set_volume drops it.  No scene byte is written.
+ *   VOLYM_E_INVALID: NULL ctx, what volym_cost_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's dimensions held in
+ * the other device layout than the volume.  VOLYM_E_HIP: a HIP error, or more rounds than the box has texels (a defect). */
+int   volym_cost_pass(volym_ctx* ctx, const volym_cost* q);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for: NULL; a box without lo <= hi <= dims on every axis; a box with
+ * more than VOLYM_COST_BOX_MAX texels; a flag bit other than UNCUT; a window without min_byte <= max_byte <= 255; step_cost
+ * outside 1..255; contrast_cost above 255; max_cost above VOLYM_COST_MAX; hist_shift above 16; n_points above
+ * VOLYM_COST_POINTS_MAX; a point outside the box.  An empty box (without points) is valid.  Pure host arithmetic. */
+int   volym_cost_check(const volym_cost* q, const uint32_t dims[3]);
+/* The reads block.  All: VOLYM_E_STATE before any pass, and after volym_set_volume until the next one; VOLYM_E_INVALID for a NULL
+ * ctx or output.  The map is of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi, inside the pass's box; NULL: the
+ * pass's whole box), box-linear in the sub-box.  volym_cost_at: the key of one texel of the pass's box, taken apart
+ * (VOLYM_E_INVALID for a texel outside that box). */
+int   volym_read_cost(volym_ctx* ctx, struct volym_cost_summary* out);
+int   volym_read_cost_map(volym_ctx* ctx, const uint32_t sub[6], uint32_t* out);
+int   volym_cost_at(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, struct volym_cost_site* out);
+/* The context's own results in device memory after a pass (NULL before any, and after volym_set_volume): the summary (a struct
+ * volym_cost_summary) and the key map of the latest pass's box. */
+void* volym_cost_device_ptr(volym_ctx* ctx);
+void* volym_cost_map_device_ptr(volym_ctx* ctx);
+/* The spread: a blocking set-up call with the contract of volym_flood_labels (one kernel, in place, on the first slot's stream;
+ * with changed == 0, or DRY_RUN, nothing else is touched; out may be NULL; the labels that may receive texels are
+ * {to[g] : take[g]}).  While the history is on, a call that changes a texel (no DRY_RUN) is one step of it.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_spread_check refuses, a box that reaches outside the box of the cost pass.
+ * VOLYM_E_STATE: what volym_edit_labels refuses of the context's state; no volym_cost_pass since volym_set_volume.  The native
+ * multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_spread_labels(volym_ctx* ctx, const volym_spread* s, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, a flag bit
+ * other than UNCUT and DRY_RUN, a window without min_byte <= max_byte <= 255, cost_lo > cost_hi.  An empty box is valid.  Pure
+ * host arithmetic. */
+int   volym_spread_check(const volym_spread* s, const uint32_t dims[3]);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

@@ -26,8 +26,8 @@ segment, its nearest texel and the clearance -- and writes the histogram as <scr
 inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] prints the table of segment statistics of the scene in view -- texels, share in view,
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
---relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R, --shrink NAME:R, --fill [NAME,...][:R], --separate NAME:R, --flood [NAME,...][:R] and --wand-at X,Y:NAME:TOL[:R] edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate, grow_through, wand_at); the PNG is the frame after them and
+--relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R, --shrink NAME:R, --fill [NAME,...][:R], --separate NAME:R, --flood [NAME,...][:R], --wand-at X,Y:NAME:TOL[:R], --grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]] and --smart-wand-at X,Y:NAME:CONTRAST:MAX_COST edit the labels on the device
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate, grow_through, wand_at, grow_from_seeds, smart_wand_at); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -366,6 +366,45 @@ def _wand_arg(text):
     return x, y, name, tol, r
 
 
+def _grow_arg(text):
+    """--grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]] -> (names, contrast, max_cost)"""
+    usage = ("NAME[,NAME...][:CONTRAST[:MAX_COST]] -- the segments that grow, what a byte of density change across a step costs beside the step's own 1 "
+             "(0..255, default 16) and the most a texel may cost (default: no limit)")
+    parts = text.split(":")
+    try:
+        names = [_segment_arg(n) for n in parts[0].split(",") if n]
+        contrast = int(parts[1]) if len(parts) > 1 else 16
+        max_cost = int(parts[2]) if len(parts) > 2 else 0
+        if len(parts) > 3 or not names or not 0 <= contrast <= 255 or max_cost < 0:
+            raise ValueError
+    except ValueError:
+        raise SystemExit("--grow-from-seeds: %s" % usage)
+    return names, contrast, max_cost
+
+
+def _grow_table(d, result):
+    """what --grow-from-seeds prints: how many texels joined the segment that reaches them most cheaply, then every segment that took some"""
+    took = sorted(result["arrived"].items())
+    lines = ["grow from seeds: %d texels joined the cheapest of %d segments" % (result["changed"], len(took))]
+    for l, n in took:
+        lines.append("  + %-16s label %3d: %10d" % (d._segment_name(l) or "label %d" % l, l, n))
+    return "\n".join(lines)
+
+
+def _smart_wand_arg(text):
+    """--smart-wand-at X,Y:NAME:CONTRAST:MAX_COST -> (x, y, name, contrast, max_cost)"""
+    usage = "X,Y:NAME:CONTRAST:MAX_COST -- a pixel, the segment that takes what the wand reaches, the cost of a byte of density change and the most a texel may cost"
+    parts = text.split(":")
+    try:
+        x, y = (int(v) for v in parts[0].split(","))
+        name, contrast, max_cost = parts[1], int(parts[2]), int(parts[3])
+        if len(parts) != 4 or not name:
+            raise ValueError
+    except (ValueError, IndexError):
+        raise SystemExit("--smart-wand-at: %s" % usage)
+    return x, y, name, contrast, max_cost
+
+
 def _label_edits(ctx, d, args):
     """the label edits of the command line on the scene as it stands (demo.Simple.relabel, the brush, stroke, lasso, split_at, keep_largest, grow, shrink):
     [(option, result)]"""
@@ -424,6 +463,12 @@ def _label_edits(ctx, d, args):
         if getattr(args, "wand_at", None):
             x, y, name, tol, r = _wand_arg(args.wand_at)
             out.append(("wand", d.wand_at(ctx, x, y, _segment_arg(name), tol, r)))
+        if getattr(args, "grow_from_seeds", None):
+            names, contrast, max_cost = _grow_arg(args.grow_from_seeds)
+            out.append(("grow_from_seeds", d.grow_from_seeds(ctx, names, contrast=contrast, max_cost=max_cost)))
+        if getattr(args, "smart_wand_at", None):
+            x, y, name, contrast, max_cost = _smart_wand_arg(args.smart_wand_at)
+            out.append(("smart_wand", d.smart_wand_at(ctx, x, y, _segment_arg(name), contrast, max_cost)))
     except ValueError as e:
         raise SystemExit("label edit: %s" % e)
     return out
@@ -544,6 +589,11 @@ def run_simple(args):
         elif option == "wand":
             print("wand: %s" % ("nothing under the pixel" if result["relabel"] is None else "%d texels joined label %d, density %d..%d" % (
                 result["relabel"]["changed"], result["relabel"]["label"], result["relabel"]["window"][0], result["relabel"]["window"][1])))
+        elif option == "grow_from_seeds":
+            print(_grow_table(d, result))
+        elif option == "smart_wand":
+            print("smart wand: %s" % ("nothing under the pixel" if result["relabel"] is None else "%d texels joined label %d" % (
+                result["relabel"]["changed"], result["relabel"]["label"])))
         elif option == "separate":
             print("separate: %d pieces%s" % (len(result), "".join(", %s %d texels" % (p["name"], p["texels"]) for p in result)))
         print(json.dumps({option: result}))      # one line per label edit: texels changed, per label left and arrived, the hull
@@ -732,6 +782,13 @@ def main(argv=None):
                           "bridge (demo.Simple.grow_through); one undo step")
     run.add_argument("--wand-at", metavar="X,Y:NAME:TOL[:R]", help="the magic wand: from the texel under pixel (X, Y) through the unlabelled matter whose density is within "
                                                                     "TOL of that texel's, at most R steps, into segment NAME (demo.Simple.wand_at); after --flood")
+    run.add_argument("--grow-from-seeds", metavar="NAME[,NAME...][:CONTRAST[:MAX_COST]]",
+                     help="grow from seeds on the device, after --wand-at: the named segments grow at once through the unlabelled matter of density above 0, where a "
+                          "step costs 1 and CONTRAST (default 16) per byte of density change across it; a texel joins the segment that reaches it most cheaply, for "
+                          "at most MAX_COST (default: however much) (demo.Simple.grow_from_seeds); one undo step")
+    run.add_argument("--smart-wand-at", metavar="X,Y:NAME:CONTRAST:MAX_COST",
+                     help="the wand that stops at edges: from the texel under pixel (X, Y) through the unlabelled matter, a step costing 1 and CONTRAST per byte of "
+                          "density change, for at most MAX_COST, into segment NAME (demo.Simple.smart_wand_at); after --grow-from-seeds")
     run.add_argument("--undo", type=int, metavar="N", help="keep a history of the label edits above on the device and take the last N back, before the "
                                                            "picture and --labels-out; each prints a JSON line {\"undo\": ...}")
     run.add_argument("--labels-out", help="FILE: write the labels as they stand after the edits, raw bytes in the orientation of --labels")

@@ -426,6 +426,66 @@ class Flood(C.Structure):
     ]
 
 
+COST_UNCUT = 1                                                 # volym_cost.flags
+COST_POINTS_MAX = 64
+COST_MAX = 0xFFFFFD                                            # 2^24 - 3: the largest cost a key holds
+COST_STEP_MAX = 65280                                          # 255 + 255 * 255: the most one step costs
+COST_BOX_MAX = 0x7FFFFFFE
+COST_NONE = 0xFFFFFFFF                                         # not reached
+COST_HIST_SHIFT_MAX = 16
+SPREAD_UNCUT, SPREAD_DRY_RUN = 1, 2                            # volym_spread.flags
+
+
+class Cost(C.Structure):
+    """volym_cost (include/volym_hip.h): box, flags, window, the seed and through tables, the cost limit, the points, the two weights
+    and the histogram's shift, 1336 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("seed", C.c_uint8 * 256),
+        ("through", C.c_uint8 * 256),
+        ("max_cost", C.c_uint32),
+        ("n_points", C.c_uint32),
+        ("points", (C.c_uint32 * 3) * COST_POINTS_MAX),
+        ("step_cost", C.c_uint32),
+        ("contrast_cost", C.c_uint32),
+        ("hist_shift", C.c_uint32),
+    ]
+
+
+class CostSummary(C.Structure):
+    """volym_cost_summary (include/volym_hip.h): counters, the maximum, the cells per label and the histogram of costs, 6184 bytes"""
+    _fields_ = [("n_seed", C.c_uint64), ("n_medium", C.c_uint64), ("n_reached", C.c_uint64), ("max_cost", C.c_uint32), ("max_at", C.c_uint32 * 3),
+                ("cell", C.c_uint64 * 256), ("cell_medium", C.c_uint64 * 256), ("hist", C.c_uint64 * 256)]
+
+
+class CostSite(C.Structure):
+    """volym_cost_site (include/volym_hip.h): the key of one texel taken apart, 8 bytes"""
+    _fields_ = [("cost", C.c_uint32), ("label", C.c_uint32)]
+
+
+# the summary as a NumPy structured dtype (GpuContext.read_cost, scene.cost_volume)
+COST_SUMMARY_DTYPE = np.dtype([("n_seed", "<u8"), ("n_medium", "<u8"), ("n_reached", "<u8"), ("max_cost", "<u4"), ("max_at", "<u4", (3,)),
+                               ("cell", "<u8", (256,)), ("cell_medium", "<u8", (256,)), ("hist", "<u8", (256,))])
+
+
+class Spread(C.Structure):
+    """volym_spread (include/volym_hip.h): box, flags, density window, the give, take and to tables and the band of one spread, 812 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("give", C.c_uint8 * 256),
+        ("take", C.c_uint8 * 256),
+        ("to", C.c_uint8 * 256),
+        ("cost_lo", C.c_uint32),
+        ("cost_hi", C.c_uint32),
+    ]
+
+
 class LassoView(C.Structure):
     """volym_lasso_view (include/volym_hip.h): the integer view texel -> (X, Y, D), 88 bytes"""
     _fields_ = [
@@ -670,6 +730,15 @@ SIGNATURES = {
     "volym_geodesic_map_device_ptr": (C.c_void_p, [_ctx]),
     "volym_flood_labels": (C.c_int, [_ctx, C.POINTER(Flood), C.POINTER(RelabelResult)]),
     "volym_flood_check": (C.c_int, [C.POINTER(Flood), C.POINTER(C.c_uint32)]),
+    "volym_cost_pass": (C.c_int, [_ctx, C.POINTER(Cost)]),
+    "volym_cost_check": (C.c_int, [C.POINTER(Cost), C.POINTER(C.c_uint32)]),
+    "volym_read_cost": (C.c_int, [_ctx, C.POINTER(CostSummary)]),
+    "volym_read_cost_map": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_cost_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(CostSite)]),
+    "volym_cost_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_cost_map_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_spread_labels": (C.c_int, [_ctx, C.POINTER(Spread), C.POINTER(RelabelResult)]),
+    "volym_spread_check": (C.c_int, [C.POINTER(Spread), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

@@ -7,6 +7,7 @@
 //                     the pass of that name
 //   nearest.hip       the nearest pass and the fill by it, an edit like those below
 //   geodesic.hip      the geodesic pass and the flood by it, an edit like those below
+//   cost.hip          the cost pass; the spread by it is the flood's kernel, launched by geodesic.hip's flood_by_map
 //   relabel.hip, brush.hip, lasso.hip, smooth.hip
 //                     the label edit of that name (relabel.hip: and the history); what they share on the host is label_edit.hpp
 //   box_pass.hip      no ABI: what the passes over a request's box share -- the scan of row counts into offsets and the read-back
@@ -289,6 +290,14 @@ struct volym_ctx {
     uint32_t geodesic_box[6] = {};           // the box of the latest pass (the reads and the flood address the map by it)
     uint64_t geodesic_rounds = 0;            // the rounds the latest pass enqueued, those past the last active one included
 
+    // cost passes (volym_cost_pass, cost.hip): a snapshot of its own, valid until the next volym_set_volume
+    volym::OwnedBuffer<volym_cost_summary> cost;     // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> cost_map;           // the key of every texel of the request's box, box-linear; aliases no other pass's result
+    volym::OwnedBuffer<uint8_t> cost_bytes;          // the density byte of every texel of that box as the pass read it, box-linear
+    volym::OwnedBuffer<uint32_t> cost_tiles;         // the relaxation's state, laid out as geodesic_tiles is (cost_kernels.h)
+    uint32_t cost_box[6] = {};               // the box of the latest pass (the reads and the spread address the map by it)
+    uint64_t cost_rounds = 0;                // the rounds the latest pass enqueued, those past the last active one included
+
     // the history of label edits (volym_label_history, relabel.hip): off (budget 0) in a new context
     struct LabelStep {
         uint32_t* index = nullptr;           // the chunks the edit stored ...
@@ -376,6 +385,12 @@ void free_distance(volym_ctx* c);
 void free_nearest(volym_ctx* c);
 // geodesic.hip: what the context keeps for the geodesic pass (every stream idle)
 void free_geodesic(volym_ctx* c);
+// geodesic.hip: the flood's edit by any key map of the flood's format (key >> 8 in the band, key & 0xff the label that takes), box-linear
+// over pass_box, which holds f->box: volym_flood_labels by the geodesic map, volym_spread_labels (cost.hip) by the cost map.  `who` names
+// the call in errors.  The request and the context's state are checked by the caller.
+int flood_by_map(volym_ctx* c, const volym_flood* f, const uint32_t* keys, const uint32_t pass_box[6], const char* who, volym_relabel_result& res);
+// cost.hip: what the context keeps for the cost pass (every stream idle)
+void free_cost(volym_ctx* c);
 // relabel.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
 void clear_label_history(volym_ctx* c);
 // relabel.hip: the steps and the staging area of the label history (every stream idle)

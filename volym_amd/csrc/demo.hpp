@@ -299,6 +299,35 @@ public:
         records_current_ = false;
         return out;
     }
+    // New: grow from seeds (volym_cost_pass, volym_spread_labels): one cost pass from the union of `names` (names, ids or label values
+    // as text; at least one) through the unlabelled texels with a density byte above 0, where a step costs 1 and `contrast` per byte of
+    // density change across it, at most max_cost in all (0: however much), then one spread -- every texel reached joins the segment
+    // that reaches it most cheaply, the smallest label among equals.  One step of the history.
+    volym_relabel_result grow_from_seeds(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& names, uint32_t contrast, uint32_t max_cost)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "grow from seeds: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        if (names.empty()) throw Error(VOLYM_E_INVALID, "grow from seeds: name the segments that grow");
+        auto q = std::make_unique<volym_cost>();           // (1336 bytes, zeroed)
+        q->box[3] = a.nx; q->box[4] = a.ny; q->box[5] = a.nz;
+        q->min_byte = 1u; q->max_byte = 255u;
+        for (const std::string& n : names) q->seed[label_value_of(a, n)] = 1u;
+        q->seed[0] = 0u;
+        q->through[0] = 1u;
+        q->step_cost = 1u; q->contrast_cost = contrast; q->max_cost = max_cost; q->hist_shift = 8u;
+        ctx.check(volym_cost_pass(ctx.handle(), q.get()));
+        volym_spread s{};
+        std::memcpy(s.box, q->box, sizeof s.box);
+        s.max_byte = 255u;
+        s.give[0] = 1u;
+        std::memcpy(s.take, q->seed, 256);
+        for (int l = 0; l < 256; ++l) s.to[l] = static_cast<uint8_t>(l);
+        s.cost_lo = 1u; s.cost_hi = 0xffffffffu;
+        volym_relabel_result out{};
+        ctx.check(volym_spread_labels(ctx.handle(), &s, &out));
+        records_current_ = false;
+        return out;
+    }
     // New: keep a history of the label edits in at most budget_bytes of device memory (volym_label_history), so that undo can take
     // them back.  The labels go to the device first: handing them to the context clears the history.
     void history(const GpuContext& ctx, const SimpleAssets& a, uint64_t budget_bytes = 256ull << 20)

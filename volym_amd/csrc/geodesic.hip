@@ -1,5 +1,6 @@
 // libvolym_hip.so: the geodesic pass (volym_geodesic_pass, volym_geodesic_check, the reads, volym_geodesic_at and the two device
-// pointers) and the flood by it (volym_flood_labels, volym_flood_check), beside the kernels they launch (geodesic_kernels.h).  The pass
+// pointers) and the flood by it (volym_flood_labels, volym_flood_check; flood_by_map, which cost.hip calls with its own map), beside
+// the kernels they launch (geodesic_kernels.h).  The pass
 // is a read-only pass like the distance pass, its results a snapshot that later edits of the scene leave valid -- but it BLOCKS: the
 // host enqueues the rounds of the relaxation in batches on slot 0's stream and reads 4 bytes after each, the tiles still marked.
 // The flood is an edit like the others and goes through label_edit.hpp's transition.
@@ -50,21 +51,21 @@ void volym::free_geodesic(volym_ctx* c)
 
 static bool have_pass(const volym_ctx* c) { return c->geodesic.count != 0u; }
 
-// volym_flood_labels' request as an edit: the table only marks the labels that give, the receiving labels are {to[g] : take[g]}
-static int flood_labels(volym_ctx* c, const volym_flood* f, volym_relabel_result& res)
+// A flood request as an edit: the table only marks the labels that give, the receiving labels are {to[g] : take[g]}.  The map is
+// volym_flood_labels' own or, for volym_spread_labels (cost.hip), the cost pass's: the same format, so the same kernel.
+int volym::flood_by_map(volym_ctx* c, const volym_flood* f, const uint32_t* keys, const uint32_t pass_box[6], const char* who, volym_relabel_result& res)
 {
     const bool dry = (f->flags & VOLYM_FLOOD_DRY_RUN) != 0u, uncut_bytes = (f->flags & VOLYM_FLOOD_UNCUT) != 0u;
     FloodRule rule = {};
     rule.min_byte = f->min_byte; rule.max_byte = f->max_byte;
     rule.steps_lo = f->steps_lo; rule.steps_hi = f->steps_hi;
     rule.store = dry ? 0u : 1u;
-    std::memcpy(rule.box, c->geodesic_box, sizeof rule.box);
+    std::memcpy(rule.box, pass_box, sizeof rule.box);
     std::memcpy(rule.take, f->take, 256);
     std::memcpy(rule.to, f->to, 256);
     uint8_t marks[256], receives[256] = {};
     for (int l = 0; l < 256; ++l) { marks[l] = static_cast<uint8_t>(f->give[l] ? l ^ 1 : l); if (f->take[l]) receives[f->to[l]] = 1u; }
-    const uint32_t* keys = c->geodesic_map.ptr;
-    const LabelEdit edit = {f->box, marks, dry, "volym_flood_labels", receives};
+    const LabelEdit edit = {f->box, marks, dry, who, receives};
     return edit_labels(c, edit, res, [&](hipStream_t stream, dim3 grid, const RelabelOut& out, const LabelTable& to, const CropSlab& s, uint32_t items,
                                          const LabelJournal* journal) {
         launch_edit(c, volym_geodesic_flood_kernel, volym_geodesic_flood_journal_kernel, stream, grid, out, to, s, rule, items, journal, edit_density(c, uncut_bytes), keys);
@@ -225,7 +226,7 @@ int volym_flood_labels(volym_ctx* c, const volym_flood* f, struct volym_relabel_
             return fail(c, VOLYM_E_INVALID, "volym_flood_labels: a box that reaches outside the box of the geodesic pass");
     HIPCHK(c, hipSetDevice(c->device));
     volym_relabel_result res;
-    const int rc = flood_labels(c, f, res);
+    const int rc = flood_by_map(c, f, c->geodesic_map.ptr, c->geodesic_box, "volym_flood_labels", res);
     if (rc == VOLYM_OK && out) *out = res;
     return rc;
 }

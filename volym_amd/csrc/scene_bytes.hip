@@ -915,6 +915,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     free_distance(c);                       // (and the distance map, for the same reason)
     free_nearest(c);                        // (and the nearest pass's sites)
     free_geodesic(c);                       // (and the geodesic pass's keys)
+    free_cost(c);                           // (and the cost pass's keys and bytes)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;

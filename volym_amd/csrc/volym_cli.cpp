@@ -23,6 +23,9 @@
 //   NAME against label 0, or jointly for every label without a name (Simple::smooth), after --lasso;
 //   --flood [NAME,...][:R] grows the segments NAME (none: every segment) at once THROUGH the unlabelled matter of density above 0: a
 //   texel joins the segment whose seed is the fewest 6-connected steps away, at most R steps (Simple::flood), after --fill;
+//   --grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]] grows the segments NAME at once through the unlabelled matter of density
+//   above 0, a step costing 1 and CONTRAST (default 16) per byte of density change across it: a texel joins the segment that reaches
+//   it most cheaply, for at most MAX_COST (Simple::grow_from_seeds), after --flood;
 //   --fill [NAME,...][:R] grows the segments NAME (none: every segment) at once into the unlabelled matter: every unlabelled texel
 //   with a density byte above 0 joins the segment it is nearest to, at most R texels away (Simple::fill), after --smooth;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
@@ -90,6 +93,9 @@ struct Options {
     bool flood = false;                                  // --flood [NAME,...][:R]: the segments grow at once through the unlabelled matter (run simple)
     std::vector<std::string> flood_names;
     double flood_r = -1.0;                               // (below 0: however far)
+    bool grow = false;                                   // --grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]]: the segments grow by cost (run simple)
+    std::vector<std::string> grow_names;
+    uint32_t grow_contrast = 16u, grow_max_cost = 0u;    // (0: however much)
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -236,6 +242,8 @@ int run_simple(const Options& o)
     if (o.fill) filled = demo.fill(ctx, assets, o.fill_names, o.fill_r);                                    // after --smooth, before --undo
     volym_relabel_result flooded{};
     if (o.flood) flooded = demo.flood(ctx, assets, o.flood_names, o.flood_r);                               // after --fill, before --undo
+    volym_relabel_result grown{};
+    if (o.grow) grown = demo.grow_from_seeds(ctx, assets, o.grow_names, o.grow_contrast, o.grow_max_cost);   // after --flood, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -282,6 +290,18 @@ int run_simple(const Options& o)
             std::string name = "label " + std::to_string(l);
             for (const SegmentInfo& s : assets.segments) if (s.label_value == l) name = s.name.empty() ? s.id : s.name;
             std::printf("  + %-16s label %3d: %10llu\n", name.c_str(), l, static_cast<unsigned long long>(flooded.arrived[l]));
+        }
+    }
+    if (o.grow) {
+        // how many texels joined the segment that reaches them most cheaply, then every segment that took some
+        int took = 0;
+        for (int l = 0; l < 256; ++l) took += grown.arrived[l] != 0u;
+        std::printf("grow from seeds: %llu texels joined the cheapest of %d segments\n", static_cast<unsigned long long>(grown.changed), took);
+        for (int l = 0; l < 256; ++l) {
+            if (grown.arrived[l] == 0u) continue;
+            std::string name = "label " + std::to_string(l);
+            for (const SegmentInfo& s : assets.segments) if (s.label_value == l) name = s.name.empty() ? s.id : s.name;
+            std::printf("  + %-16s label %3d: %10llu\n", name.c_str(), l, static_cast<unsigned long long>(grown.arrived[l]));
         }
     }
     for (const auto& u : undone) {
@@ -592,6 +612,40 @@ int main(int argc, char** argv)
                         if (used != r.size() || !(o.flood_r >= 1.0)) throw Error(VOLYM_E_INVALID, usage);
                     } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
                 }
+            }
+            else if (a == "--grow-from-seeds") {
+                const char* usage = "--grow-from-seeds: NAME[,NAME...][:CONTRAST[:MAX_COST]] -- the segments that grow, the cost of a byte of density change (0..255) "
+                                    "and the most a texel may cost";
+                o.grow = true;
+                const std::string v = next();
+                std::vector<std::string> parts;
+                size_t pos = 0;
+                while (pos <= v.size()) {
+                    const size_t colon = std::min(v.find(':', pos), v.size());
+                    parts.push_back(v.substr(pos, colon - pos));
+                    pos = colon + 1u;
+                }
+                if (parts.empty() || parts.size() > 3u) throw Error(VOLYM_E_INVALID, usage);
+                pos = 0;
+                while (pos < parts[0].size()) {
+                    const size_t comma = std::min(parts[0].find(',', pos), parts[0].size());
+                    if (comma > pos) o.grow_names.push_back(parts[0].substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+                try {
+                    size_t used = 0;
+                    if (parts.size() > 1u) {
+                        const unsigned long c = std::stoul(parts[1], &used);
+                        if (used != parts[1].size() || c > 255ul) throw Error(VOLYM_E_INVALID, usage);
+                        o.grow_contrast = static_cast<uint32_t>(c);
+                    }
+                    if (parts.size() > 2u) {
+                        const unsigned long m = std::stoul(parts[2], &used);
+                        if (used != parts[2].size() || m > VOLYM_COST_MAX) throw Error(VOLYM_E_INVALID, usage);
+                        o.grow_max_cost = static_cast<uint32_t>(m);
+                    }
+                } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
+                if (o.grow_names.empty()) throw Error(VOLYM_E_INVALID, usage);
             }
             else if (a == "--labels-out") o.labels_out = next();
             else if (a == "--undo") o.undo = static_cast<uint32_t>(std::stoul(next()));

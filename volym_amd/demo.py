@@ -85,6 +85,7 @@ class GpuContext:
         self._distance_box = None
         self._nearest_box = None
         self._geodesic_box = None
+        self._cost_box = None
 
     def set_importances(self, importances, dims):
         v = np.ascontiguousarray(importances, np.uint8).ravel()
@@ -659,6 +660,61 @@ class GpuContext:
         of the history.  Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
         out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
         self._ck(_lib.lib().volym_flood_labels(self.handle, C.byref(flood.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
+    # ---- grow from seeds: cost-weighted growth -----------------------------------------------------
+    def cost_pass(self, cost=None):
+        """One cost pass (include/volym_hip.h volym_cost_pass; scene.cost_volume is its definition): for every texel of the request's
+        box the cost of the cheapest chain of 6-connected steps through the medium from a seed, where a step costs more the more the
+        density changes across it, and the smallest label among the seeds that attain it, of the scene as it stands.  `cost` is a
+        scene.Cost; None: the whole volume, window 1..255, every label but 0 a seed, label 0 the medium, step 1, contrast 16.  Blocks,
+        as geodesic_pass does: the host counts the rounds."""
+        q = None if cost is None else C.byref(cost.to_c())
+        self._ck(_lib.lib().volym_cost_pass(self.handle, q))
+        box = ((0, 0, 0), getattr(self, "_volume_dims", (0, 0, 0))) if cost is None else cost.box
+        self._cost_box = box if all(a < b for a, b in zip(*box)) else None
+
+    def read_cost(self):
+        """The summary of the latest cost pass: an np.void of _lib.COST_SUMMARY_DTYPE.  Blocks."""
+        out = np.zeros(1, _lib.COST_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_cost(self.handle, out.ctypes.data_as(C.POINTER(_lib.CostSummary))))
+        return out[0]
+
+    def read_cost_map(self, sub=None):
+        """The keys of the latest cost pass (cost << 8 | cost_label; _lib.COST_NONE: not reached) as a uint32 array [z, y, x]: of its
+        whole box (None) or of the sub-box (lo, hi) in texels of the volume, which must lie inside the pass's box.  Blocks."""
+        box = getattr(self, "_cost_box", None) if sub is None else (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        call = _lib.lib().volym_read_cost_map
+        if box is None:                                        # no pass yet (the library refuses), or a pass over an empty box
+            self._ck(call(self.handle, None, None))
+            return np.zeros((0, 0, 0), np.uint32)
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        out = np.zeros(tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0)), np.uint32)
+        self._ck(call(self.handle, c, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def cost_at(self, x, y, z):
+        """The key of texel (x, y, z) in the latest cost pass, taken apart: {"cost" (None: not reached), "label"}.  Blocks."""
+        out = _lib.CostSite()
+        self._ck(_lib.lib().volym_cost_at(self.handle, int(x), int(y), int(z), C.byref(out)))
+        none = int(out.cost) == _lib.COST_NONE
+        return {"cost": None if none else int(out.cost), "label": int(out.label)}
+
+    def cost_device_ptr(self):
+        """The context's own summary (a volym_cost_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_cost_device_ptr(self.handle)
+
+    def cost_map_device_ptr(self):
+        """The key map of the latest cost pass in device memory (None before any)."""
+        return _lib.lib().volym_cost_map_device_ptr(self.handle)
+
+    def spread_labels(self, spread):
+        """One spread on the device (include/volym_hip.h volym_spread_labels; scene.spread_volume is its definition): a texel of the
+        box whose label gives becomes to[g], g its cost label in the latest cost pass, where the take table, the density window and
+        the band of cost say so.  `spread` is a scene.Spread.  Everything follows as after edit_labels, and the call is one step of
+        the history.  Blocks.  Returns the result: an np.void of _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_spread_labels(self.handle, C.byref(spread.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
     # ---- editing labels --------------------------------------------------------------------------
@@ -1601,6 +1657,61 @@ class Simple(ComputeDemo):
             # the seed carries the picked texel's label, whatever it is: every geo label takes, and all of them become `value`
             p["relabel"] = self._flood(ctx, scene.Flood(None, 0, (0, 255), scene.smooth_table(medium), None, np.full(256, value, np.int64), dims=self.dims))
             p["relabel"].update(label=value, window=window)
+        return p
+
+    # ---- grow from seeds: cost-weighted growth ------------------------------------------------------
+    def _spread(self, ctx, spread):
+        result = ctx.spread_labels(scene.check_spread(spread, self.dims))
+        if int(result["changed"]) and not spread.flags & _lib.SPREAD_DRY_RUN:
+            self._labels_edited = True
+            self._records_for = None
+        return scene.relabel_result_dict(result)
+
+    def _cost_request(self, seeds, medium, contrast, step, window, max_cost, points=()):
+        limit = 0 if max_cost is None else int(max_cost)
+        return scene.check_cost(scene.Cost(None, 0, window, scene.smooth_table(seeds), scene.smooth_table(medium), step, contrast, limit, points, 8, dims=self.dims), self.dims)
+
+    def cost_reach(self, ctx, names, through=(0,), contrast=16, step=1, window=(1, 255), max_cost=0):
+        """How cheaply through the matter?  One cost pass from the union of the segments `names` (names, ids or label values; None:
+        every label but those of `through`) through the segments `through` (default: the unlabelled texels) with a density byte in
+        `window`, where a step costs step + contrast * |change of density byte|, at most max_cost in all (0: however much), and the
+        read of its summary; the map stays on the device for ctx.read_cost_map, ctx.cost_at and a spread.  Returns
+        scene.cost_summary's dict, the cells by segment name.  The labels go to the device first if they are not there yet."""
+        if not self._labels_on_device and self._labels_raw.size:
+            self.set_labels(ctx, self._labels_raw)
+        medium = self._label_values(through)
+        seeds = [l for l in (range(256) if names is None else self._label_values(names)) if l not in medium]
+        ctx.cost_pass(self._cost_request(seeds, medium, contrast, step, window, max_cost))
+        return scene.cost_summary(ctx.read_cost(), {l: self._segment_name(l) or "label %d" % l for l in range(256)})
+
+    def grow_from_seeds(self, ctx, names, into=(0,), contrast=16, step=1, window=(1, 255), max_cost=0):
+        """Grow from seeds: one cost pass from the union of `names` (None: every label but those of `into`) through the segments
+        `into` with a density byte in `window`, then one spread -- every texel of `into` that is reached goes to the segment that
+        reaches it most cheaply, the smallest label among equals.  Where grow_through lets two segments meet halfway in steps, here
+        they meet where the density changes: crossing a boundary costs contrast per byte of change.  One undo step.  Returns the
+        result's dict."""
+        self._ready_to_edit(ctx)
+        gives = self._label_values(into)
+        seeds = [l for l in (range(256) if names is None else self._label_values(names)) if l not in gives]
+        ctx.cost_pass(self._cost_request(seeds, gives, contrast, step, window, max_cost))
+        return self._spread(ctx, scene.Spread(None, 0, (0, 255), scene.smooth_table(gives), scene.smooth_table(seeds), None, (1, 0xFFFFFFFF), dims=self.dims))
+
+    def smart_wand_at(self, ctx, x, y, name, contrast, max_cost, step=1, over=(0,), window=(1, 255), alpha_min=0.5):
+        """The wand that stops at edges rather than at a tolerance: pick pixel (x, y); the texel it shows is the one seed of a cost
+        pass through the segments `over` (default: the unlabelled texels) in `window`, and everything it reaches for at most max_cost
+        joins segment `name` (a name or id of the segments JSON, a label value, or a new name, as in split_at), the picked texel
+        included where its label is one of `over`.  Returns the pick with a "relabel" entry (the result's dict and "label": the
+        segment's label); None there when the pixel shows nothing."""
+        self._ready_to_edit(ctx)
+        p = self.pick(ctx, x, y, alpha_min)
+        p["relabel"] = None
+        if p["status"] == "hit" and p["texel"] is not None:
+            medium = self._label_values(over)
+            value = self._new_segment(ctx, name, p["label"] or 0)
+            ctx.cost_pass(self._cost_request([], medium, contrast, step, window, max_cost, [p["texel"]]))
+            # the seed carries the picked texel's label, whatever it is: every cost label takes, and all of them become `value`
+            p["relabel"] = self._spread(ctx, scene.Spread(None, 0, (0, 255), scene.smooth_table(medium), None, np.full(256, value, np.int64), dims=self.dims))
+            p["relabel"].update(label=value)
         return p
 
     def _brush(self, ctx, brush):

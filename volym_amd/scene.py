@@ -2405,6 +2405,258 @@ def flood_volume(prepared, dims, flood, labels, keys, pass_box, uncut=None):
     return new, result
 
 
+class Cost:
+    """volym_cost (include/volym_hip.h): what one cost pass maps.  box, flags (_lib.COST_UNCUT), window, seed, through and points as
+    Geodesic takes them; step: what every step costs, 1..255; contrast: what every unit of density change across a step adds, 0..255;
+    max_cost: 0 for no limit; hist_shift: the summary's histogram bins by min(cost >> hist_shift, 255)."""
+
+    def __init__(self, box=None, flags=0, window=(1, 255), seed=None, through=None, step=1, contrast=16, max_cost=0, points=(), hist_shift=0, dims=None):
+        self.box = _box_or_whole(box, dims, "a cost request without a box needs the volume's dims")
+        self.flags = int(flags)
+        self.window = tuple(int(v) for v in window)
+        self.seed = smooth_table(range(1, 256)) if seed is None else np.array(seed, np.int64).ravel()
+        self.through = smooth_table([0]) if through is None else np.array(through, np.int64).ravel()
+        self.step, self.contrast, self.max_cost, self.hist_shift = int(step), int(contrast), int(max_cost), int(hist_shift)
+        self.points = tuple(tuple(int(v) for v in p) for p in points)
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "cost", ("box", "flags", "window", "seed", "through", "step", "contrast", "max_cost", "points", "hist_shift"), kw)
+
+    def to_c(self):
+        """The _lib.Cost of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Cost()
+        c.box = _box_to_c(self.box, "cost")
+        scalars = (self.flags, self.step, self.contrast, self.max_cost, self.hist_shift)
+        if not all(0 <= x < 2 ** 32 for x in scalars) or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("cost: flags, the window's ends, step, contrast, max_cost and hist_shift must be u32")
+        c.flags, c.step_cost, c.contrast_cost, c.max_cost, c.hist_shift = scalars
+        c.min_byte, c.max_byte = self.window
+        for name, t in (("seed", self.seed), ("through", self.through)):
+            if t.size != 256 or not ((t >= 0) & (t <= 255)).all():
+                raise ValueError("cost: %s is a table of 256 bytes" % name)
+            setattr(c, name, (C.c_uint8 * 256)(*[int(g) for g in t]))
+        if not all(len(p) == 3 and all(0 <= x < 2 ** 32 for x in p) for p in self.points):
+            raise ValueError("cost: a point is three u32")
+        c.n_points = len(self.points)                      # (the check refuses more than the struct holds; only those are copied)
+        for i, p in enumerate(self.points[:_lib.COST_POINTS_MAX]):
+            c.points[i] = (C.c_uint32 * 3)(*p)
+        return c
+
+
+def check_cost(cost, dims):
+    """The validity rules of volym_cost_check: lo <= hi <= dims on every axis (an empty box is valid), at most _lib.COST_BOX_MAX
+    texels, no flag but UNCUT, min_byte <= max_byte <= 255, step in 1..255, contrast in 0..255, max_cost <= _lib.COST_MAX,
+    hist_shift <= 16, at most _lib.COST_POINTS_MAX points, every point inside the box.  Returns the request; raises ValueError."""
+    q = cost
+    lo, hi, dims = _box_in_dims(q.box, dims, "cost")
+    texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    if texels > _lib.COST_BOX_MAX:
+        raise ValueError("cost: the box has %d texels, more than 2^31 - 2" % texels)
+    if q.flags & ~_lib.COST_UNCUT or q.flags < 0:
+        raise ValueError("cost: unknown flag bits in %#x" % q.flags)
+    if len(q.window) != 2 or not 0 <= q.window[0] <= q.window[1] <= 255:
+        raise ValueError("cost: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (q.window,))
+    if not 1 <= q.step <= 255:
+        raise ValueError("cost: step is 1..255, got %d" % q.step)
+    if not 0 <= q.contrast <= 255:
+        raise ValueError("cost: contrast is 0..255, got %d" % q.contrast)
+    if not 0 <= q.max_cost <= _lib.COST_MAX:
+        raise ValueError("cost: max_cost is 0 (no limit) or 1..%d, got %d" % (_lib.COST_MAX, q.max_cost))
+    if not 0 <= q.hist_shift <= _lib.COST_HIST_SHIFT_MAX:
+        raise ValueError("cost: hist_shift is 0..%d, got %d" % (_lib.COST_HIST_SHIFT_MAX, q.hist_shift))
+    if len(q.points) > _lib.COST_POINTS_MAX:
+        raise ValueError("cost: %d points, more than %d" % (len(q.points), _lib.COST_POINTS_MAX))
+    for p in q.points:
+        if len(p) != 3 or not all(lo[a] <= p[a] < hi[a] for a in range(3)):
+            raise ValueError("cost: the point %r lies outside the box" % (p,))
+    if np.asarray(q.seed).size != 256 or np.asarray(q.through).size != 256:
+        raise ValueError("cost: seed and through have 256 entries")
+    return q
+
+
+def empty_cost():
+    """(summary, keys) of a pass over an empty box: nothing reached (an np.void of _lib.COST_SUMMARY_DTYPE) and no map."""
+    summary = np.zeros(1, _lib.COST_SUMMARY_DTYPE)[0]
+    summary["max_cost"] = _lib.COST_NONE
+    return summary, np.zeros((0, 0, 0), np.uint32)
+
+
+def cost_volume(prepared, dims, c, labels=None, cut=None, uncut=None):
+    """The definition of the cost pass (include/volym_hip.h volym_cost_pass), NumPy integers only; equal to the device in every byte.
+    The arguments are geodesic_volume's.  The seeds carry their label as key; then whole-array sweeps: every medium texel that is no
+    seed takes the smallest key(u) + (step(u, t) << 8) over its six neighbours u in the box, where that is below its own and its cost
+    within the limit, until a sweep lowers nothing -- the one fixed point, since every step costs at least 1.  Returns
+    (summary, keys): an np.void of _lib.COST_SUMMARY_DTYPE and the keys cost << 8 | cost_label (_lib.COST_NONE: not reached) as a
+    uint32 array [z, y, x] over the request's box."""
+    q = check_cost(c, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = q.box
+    summary, no_keys = empty_cost()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, no_keys
+    whole = bool(q.flags & _lib.COST_UNCUT)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("cost_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("cost_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    window = (b >= q.window[0]) & (b <= q.window[1])
+    seed = window & (np.asarray(q.seed)[l] != 0)
+    for p in q.points:
+        seed[p[2] - lo[2], p[1] - lo[1], p[0] - lo[0]] = True
+    medium = window & (np.asarray(q.through)[l] != 0)
+    far = np.int64(1) << np.int64(40)                          # above every key and every key + step
+    limit = np.int64(((q.max_cost or _lib.COST_MAX) << 8) | 0xFF)  # the largest key the limit admits
+    key = np.where(seed, l.astype(np.int64), far)
+    open_ = medium & ~seed
+    bi = b.astype(np.int64)
+    pairs = []                                                 # per axis with two texels or more: the two slices and step << 8 between them
+    for axis in range(3):
+        n = key.shape[axis]
+        if n < 2:
+            continue
+        a, d = [slice(None)] * 3, [slice(None)] * 3
+        a[axis], d[axis] = slice(1, n), slice(0, n - 1)
+        a, d = tuple(a), tuple(d)
+        pairs.append((a, d, (q.step + q.contrast * np.abs(bi[a] - bi[d])) << 8))
+    while open_.any():
+        m = np.full(key.shape, far, np.int64)
+        for a, d, step8 in pairs:
+            np.minimum(m[a], key[d] + step8, out=m[a])
+            np.minimum(m[d], key[a] + step8, out=m[d])
+        lower = open_ & (m <= limit) & (m < key)
+        if not lower.any():
+            break
+        key[lower] = m[lower]
+    reached = key < far
+    keys = np.where(reached, key, np.int64(_lib.COST_NONE)).astype(np.uint32)
+    summary["n_seed"], summary["n_medium"], summary["n_reached"] = int(seed.sum()), int(open_.sum()), int(reached.sum())
+    if reached.any():
+        cost = np.where(reached, key >> 8, -1)
+        at = int(np.argmax(cost))                               # (the first of the largest, in (z, y, x))
+        d, h, w = key.shape
+        summary["max_cost"] = int(cost.ravel()[at])
+        summary["max_at"][...] = (lo[0] + at % w, lo[1] + (at // w) % h, lo[2] + at // (w * h))
+        summary["cell"][...] = np.bincount((key[reached] & 0xFF), minlength=256)
+        summary["cell_medium"][...] = np.bincount((key[reached & ~seed] & 0xFF), minlength=256)
+        summary["hist"][...] = np.bincount(np.minimum((key[reached] >> 8) >> q.hist_shift, 255), minlength=256)
+    return summary, keys
+
+
+def cost_summary(summary, names=None):
+    """What a user reads off a cost pass, as Python ints: {"n_seed", "n_medium", "n_reached", "max_cost" (None: nothing reached),
+    "max_at", "cells": {label or name: {"label", "texels", "grown"}}} for every label with a cell -- `texels` of the box are reached
+    most cheaply from it, `grown` of them are no seeds.  names: {label: name}."""
+    none = int(summary["n_reached"]) == 0
+    out = {"n_seed": int(summary["n_seed"]), "n_medium": int(summary["n_medium"]), "n_reached": int(summary["n_reached"]),
+           "max_cost": None if none else int(summary["max_cost"]), "max_at": None if none else tuple(int(v) for v in summary["max_at"]), "cells": {}}
+    for l in np.flatnonzero(np.asarray(summary["cell"])).tolist():
+        out["cells"][(names or {}).get(l, l)] = {"label": l, "texels": int(summary["cell"][l]), "grown": int(summary["cell_medium"][l])}
+    return out
+
+
+class Spread:
+    """volym_spread (include/volym_hip.h): one spread by the latest cost pass.  Everything as Flood takes it -- box, window, flags
+    (_lib.SPREAD_UNCUT | SPREAD_DRY_RUN), give, take, to -- with cost: (cost_lo, cost_hi), the band of the cost."""
+
+    def __init__(self, box=None, flags=0, window=(0, 255), give=None, take=None, to=None, cost=(0, 0xFFFFFFFF), dims=None):
+        f = Flood(box, flags, window, give, take, to, cost, dims=dims)
+        self.box, self.flags, self.window, self.give, self.take, self.to, self.cost = f.box, f.flags, f.window, f.give, f.take, f.to, f.steps
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "spread", ("box", "flags", "window", "give", "take", "to", "cost"), kw)
+
+    def as_flood(self):
+        """The Flood with the same fields, its band of steps this band of cost: flood_volume by a cost map is spread_volume."""
+        return Flood(self.box, self.flags, self.window, self.give, self.take, self.to, self.cost)
+
+    def to_c(self):
+        """The _lib.Spread of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Spread()
+        c.box = _box_to_c(self.box, "spread")
+        if not 0 <= self.flags < 2 ** 32 or len(self.window) != 2 or not all(0 <= x < 2 ** 32 for x in self.window):
+            raise ValueError("spread: flags and the window's ends must be u32")
+        if len(self.cost) != 2 or not all(0 <= x < 2 ** 32 for x in self.cost):
+            raise ValueError("spread: cost is a pair of u32")
+        c.flags = self.flags
+        c.min_byte, c.max_byte = self.window
+        c.cost_lo, c.cost_hi = self.cost
+        for name, t in (("give", self.give), ("take", self.take), ("to", self.to)):
+            if t.size != 256 or not ((t >= 0) & (t <= 255)).all():
+                raise ValueError("spread: %s is a table of 256 bytes" % name)
+            setattr(c, name, (C.c_uint8 * 256)(*[int(g) for g in t]))
+        return c
+
+
+def check_spread(spread, dims):
+    """The validity rules of volym_spread_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, cost_lo <= cost_hi, tables of 256 entries.  Returns the request; raises ValueError."""
+    r = spread
+    _box_in_dims(r.box, dims, "spread")
+    if r.flags & ~(_lib.SPREAD_UNCUT | _lib.SPREAD_DRY_RUN) or r.flags < 0:
+        raise ValueError("spread: unknown flag bits in %#x" % r.flags)
+    if len(r.window) != 2 or not 0 <= r.window[0] <= r.window[1] <= 255:
+        raise ValueError("spread: the window is 0 <= min_byte <= max_byte <= 255, got %r" % (r.window,))
+    if len(r.cost) != 2 or not 0 <= r.cost[0] <= r.cost[1]:
+        raise ValueError("spread: the band needs cost_lo <= cost_hi, got %r" % (r.cost,))
+    if np.asarray(r.give).size != 256 or np.asarray(r.take).size != 256 or np.asarray(r.to).size != 256:
+        raise ValueError("spread: give, take and to have 256 entries")
+    return r
+
+
+def spread_volume(prepared, dims, spread, labels, keys, pass_box, uncut=None):
+    """The definition of the spread (include/volym_hip.h volym_spread_labels), NumPy integers only; equal to the device in every byte.
+    The arguments are flood_volume's, keys the snapshot of the latest cost pass (cost_volume's map) over pass_box.  A texel of the
+    box whose label gives becomes to[g], g its cost label, iff its key is not NONE, g takes, to[g] is not its label, its density byte
+    lies in the window and its cost lies in the band.  Returns (new_labels, result) as relabel_volume does."""
+    r = check_spread(spread, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("spread_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (r.flags & _lib.SPREAD_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("spread_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    slo, shi = (tuple(int(v) for v in pass_box[0]), tuple(int(v) for v in pass_box[1]))
+    if any(lo[a] < slo[a] or hi[a] > shi[a] for a in range(3)):
+        raise ValueError("spread_volume: the request's box reaches outside the box of the cost pass")
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    shape = (shi[2] - slo[2], shi[1] - slo[1], shi[0] - slo[0])
+    inner = (slice(lo[2] - slo[2], hi[2] - slo[2]), slice(lo[1] - slo[1], hi[1] - slo[1]), slice(lo[0] - slo[0], hi[0] - slo[0]))
+    key = np.asarray(keys, np.uint32).reshape(shape)[inner]
+    g, cost = (key & np.uint32(0xFF)).astype(np.int64), (key >> np.uint32(8)).astype(np.int64)
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    d = src.reshape(nz, ny, nx)[sub]
+    give, take = np.asarray(r.give) != 0, np.asarray(r.take) != 0
+    n = np.asarray(r.to).astype(np.uint8)[g]
+    hit = give[old] & (key != np.uint32(_lib.COST_NONE)) & take[g] & (n != old) & (d >= r.window[0]) & (d <= r.window[1]) & (cost >= r.cost[0]) & (cost <= r.cost[1])
+    count = int(hit.sum())
+    if count == 0:
+        return new, result
+    result["changed"] = count
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(n[hit], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not r.flags & _lib.SPREAD_DRY_RUN:
+        new[sub] = np.where(hit, n, old)
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
