@@ -30,8 +30,9 @@
  *     volym_distance_pass blocks only when it has to allocate or grow its buffers; volym_read_distance, volym_read_distance_map
  *     and volym_distance_at block; volym_nearest_pass, its reads and volym_nearest_at likewise; volym_geodesic_pass BLOCKS (it
  *     reads 4 bytes after every batch of its rounds), and so do its reads and volym_geodesic_at; volym_cost_pass BLOCKS in the
- *     same way, and so do its reads and volym_cost_at; volym_edit_labels and the other
- *     label edits (brush, lasso, smooth, fill, flood, spread) are set-up calls and block like volym_set_*.
+ *     same way, and so do its reads and volym_cost_at; volym_interpolate_pass blocks only when it has to allocate or grow its
+ *     buffers, its reads and volym_interpolate_at block; volym_edit_labels and the other
+ *     label edits (brush, lasso, smooth, fill, flood, spread, interpolate) are set-up calls and block like volym_set_*.
  *   - the default kernel schedules its work from lists that a feedback thread inside the library re-deals from the
  *     counted cost of earlier frames (asynchronously: a frame never waits for it, and every list renders the same
  *     pixels); volym_settle runs that loop to its fixed point for the current view.
@@ -1526,6 +1527,122 @@ int   volym_spread_labels(volym_ctx* ctx, const volym_spread* s, struct volym_re
  * other than UNCUT and DRY_RUN, a window without min_byte <= max_byte <= 255, cost_lo > cost_hi.  An empty box is valid.  Pure
  * host arithmetic. */
 int   volym_spread_check(const volym_spread* s, const uint32_t dims[3]);
+
+/* --- fill between slices: interpolate a segment across gaps (new; the reference has none) ------------------------------ */
+/* A segment painted on some slices is filled in on the slices between them: shape-based interpolation (Raya and Udupa) with the
+ * distance pass's exact metric, decided by comparing squares.  A read-only pass over the bytes of the scene as they stand, and an
+ * edit by its snapshot.
+ *   The rule (integers only; scene.interpolate_volume of the Python package is its host twin, equal in every byte).  The SLICES are
+ * the planes of box perpendicular to `axis`.  A texel of box is SHAPE when its density byte (the scene byte as it stands, with UNCUT
+ * the uncut copy) is >= min_byte and select[label] != 0; min_byte may be 0 here -- labels alone decide -- and the label is 0
+ * everywhere while the context holds no labels of the volume's dimensions.  Without KEYS the KEY slices are the slices that hold a
+ * SHAPE texel; with KEYS they are the slices whose bit is set (bit c & 31 of keys[c >> 5], c the slice's volume coordinate along
+ * axis), whether they hold a SHAPE texel or not.  A GAP is a maximal run of slices that are no keys between two keys z0 < z1; it is
+ * fillable unless max_gap != 0 and the run is longer than max_gap.  Slices before the first key, after the last, or in a refused
+ * gap are left alone.
+ *   The signed planar map holds one uint32_t per texel of box, box-linear with x fastest: VOLYM_INTERPOLATE_NONE on a slice that is
+ * no key.  On a key slice a SHAPE texel holds Din << 1 | 1, Din the smallest weighted squared distance within the slice (the two
+ * weights of the in-plane axes; weight[axis] is not read) to a texel of the slice that is not SHAPE, texels outside box counting as
+ * not SHAPE; a texel that is not SHAPE holds Dout << 1, Dout the distance to the nearest SHAPE texel of the slice, or NONE when the
+ * slice has none (a KEYS slice without SHAPE: infinitely far outside).  D <= 2 * 64 * 4095^2 < 2^31.
+ *   A texel of slice z of a fillable gap, with a = z1 - z, b = z - z0 and m0, m1 the words at its in-plane position in z0 and z1, is
+ * INSIDE iff both words are SHAPE; or m0 is SHAPE, m1 is neither SHAPE nor NONE and a^2 D0 > b^2 D1; or m1 is SHAPE, m0 is neither
+ * SHAPE nor NONE and b^2 D1 > a^2 D0 (D = m >> 1).  Equality is outside; the products are below 2^24 * 2^31, exact in 64 bits.
+ * Nothing joins shapes that do not overlap in projection: each only shrinks towards the other key inside its own projection, and
+ * the texels between them stay outside.  That is the method's known limit.
+ *   The state map holds one byte per texel of box, box-linear: SHAPE (the texel was SHAPE at the pass) | INSIDE (on a key slice
+ * equal to SHAPE, on a slice of a fillable gap the decision, else 0) | GAP (the slice belongs to a fillable gap).
+ *   Memory: 17 bytes per texel of box (the two maps, and 12 bytes of work arrays), 17 GiB at 1024^3. */
+enum { VOLYM_INTERPOLATE_UNCUT = 1, VOLYM_INTERPOLATE_KEYS = 2 };          /* volym_interpolate.flags */
+enum { VOLYM_INTERPOLATE_SHAPE = 1, VOLYM_INTERPOLATE_INSIDE = 2, VOLYM_INTERPOLATE_GAP = 4 };   /* bits of a state byte */
+enum { VOLYM_INTERPOLATE_SLICE_OUTSIDE = 0, VOLYM_INTERPOLATE_SLICE_KEY = 1, VOLYM_INTERPOLATE_SLICE_GAP = 2, VOLYM_INTERPOLATE_SLICE_REFUSED = 3 };
+#define VOLYM_INTERPOLATE_NONE 0xffffffffu          /* no key slice, or a key slice without SHAPE */
+#define VOLYM_INTERPOLATE_SLICES 4096
+typedef struct volym_interpolate {
+    uint32_t box[6];            /* lo inclusive, hi exclusive, as volym_distance */
+    uint32_t flags;
+    uint32_t min_byte;          /* 0..255 */
+    uint8_t  select[256];
+    uint32_t weight[3];         /* per axis, 1..VOLYM_DISTANCE_WEIGHT_MAX; the two in-plane ones are used */
+    uint32_t axis;              /* 0, 1 or 2: x, y or z */
+    uint32_t max_gap;           /* 0: no limit; else a gap of more slices is refused */
+    uint32_t keys[VOLYM_INTERPOLATE_SLICES / 32];   /* KEYS only */
+} volym_interpolate;            /* 820 bytes */
+struct volym_interpolate_slice {
+    uint32_t kind;              /* VOLYM_INTERPOLATE_SLICE_* */
+    uint32_t key_lo, key_hi;    /* volume coordinates along axis: of the two keys about a GAP or REFUSED slice, of a KEY slice
+                                 * itself; VOLYM_INTERPOLATE_NONE on an OUTSIDE slice */
+    uint32_t count;             /* KEY: the slice's SHAPE texels; GAP: its INSIDE texels; else 0 */
+};
+struct volym_interpolate_summary {
+    uint32_t n_slices;          /* the box's extent along axis (0: an empty box) */
+    uint32_t n_keys;
+    uint32_t n_gaps, n_gap_slices;      /* the fillable gaps and their slices */
+    uint32_t n_refused;         /* the gaps max_gap refused */
+    uint32_t reserved;          /* 0 */
+    uint64_t n_shape;           /* SHAPE texels of the box */
+    uint64_t n_inside;          /* INSIDE texels on gap slices */
+    uint64_t n_new;             /* ... of them not SHAPE: what a fill adds */
+    uint64_t n_stale;           /* SHAPE and not INSIDE on gap slices: what `out` erases */
+    struct volym_interpolate_slice slice[VOLYM_INTERPOLATE_SLICES];   /* slice k of the box (coordinate box[axis] + k); 0 past n_slices */
+};                              /* 65592 bytes */
+/* The edit: a texel of box is considered when its state has GAP and its density byte lies in [min_byte, max_byte]; with label l it
+ * becomes to[l] when its state has INSIDE and out[l] otherwise.  Identity tables touch nothing; `out` is what erases a stale earlier
+ * fill.  It reads only the snapshot and the labels as they stand.  scene.interpolate_labels_volume is the host twin. */
+enum { VOLYM_INTERPOLATE_EDIT_UNCUT = 1, VOLYM_INTERPOLATE_EDIT_DRY_RUN = 2 };      /* volym_interpolate_edit.flags */
+typedef struct volym_interpolate_edit {
+    uint32_t box[6];            /* as in volym_relabel; it must lie inside the box of the latest interpolate pass */
+    uint32_t flags;
+    uint32_t min_byte, max_byte;/* the density window, on the texel that would change */
+    uint8_t  to[256];           /* the label an INSIDE texel of label l becomes */
+    uint8_t  out[256];          /* ... and a texel of a gap slice that is not INSIDE */
+} volym_interpolate_edit;       /* 548 bytes */
+#if defined(__cplusplus)
+static_assert(sizeof(volym_interpolate) == 820, "volym_interpolate is 820 bytes");
+static_assert(sizeof(struct volym_interpolate_slice) == 16, "volym_interpolate_slice is 16 bytes");
+static_assert(sizeof(struct volym_interpolate_summary) == 65592, "volym_interpolate_summary is 65592 bytes");
+static_assert(sizeof(volym_interpolate_edit) == 548, "volym_interpolate_edit is 548 bytes");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(volym_interpolate) == 820, "volym_interpolate is 820 bytes");
+_Static_assert(sizeof(struct volym_interpolate_slice) == 16, "volym_interpolate_slice is 16 bytes");
+_Static_assert(sizeof(struct volym_interpolate_summary) == 65592, "volym_interpolate_summary is 65592 bytes");
+_Static_assert(sizeof(volym_interpolate_edit) == 548, "volym_interpolate_edit is 548 bytes");
+#endif
+/* Enqueue one pass on the first slot's stream, as volym_distance_pass does: a handful of launches; it blocks only for the first
+ * allocation, or a growth, of its buffers.  q must not be NULL.  It needs what volym_distance_pass needs; an empty box launches only
+ * the zeroing kernel.  The results are a snapshot of the pass's own -- summary, signed map, state map and box; it aliases no other
+ * pass's buffers -- so the reads below, and volym_interpolate_labels, stay valid after later edits, cuts and volym_set_labels;
+ * volym_set_volume drops it.  No scene byte is written.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_interpolate_check refuses.  VOLYM_E_STATE: no volume; labels of the volume's
+ * dimensions held in the other device layout than the volume.  VOLYM_E_NOMEM: an allocation failed (no snapshot is left). */
+int   volym_interpolate_pass(volym_ctx* ctx, const volym_interpolate* q);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for: NULL; a box without lo <= hi <= dims on every axis; a box with more
+ * than VOLYM_DISTANCE_BOX_MAX texels; an unknown flag bit; min_byte above 255; a weight outside 1..VOLYM_DISTANCE_WEIGHT_MAX; an
+ * axis above 2; an extent above VOLYM_INTERPOLATE_SLICES.  An empty box is valid.  Pure host arithmetic. */
+int   volym_interpolate_check(const volym_interpolate* q, const uint32_t dims[3]);
+/* The reads block.  All: VOLYM_E_STATE before any pass, and after volym_set_volume until the next one; VOLYM_E_INVALID for a NULL
+ * ctx or output.  The maps are of sub = {x0, y0, z0, x1, y1, z1} (volume coordinates, lo <= hi, inside the pass's box; NULL: the
+ * pass's whole box), box-linear in the sub-box.  volym_interpolate_at: the signed word and the state byte of one texel of the
+ * pass's box (VOLYM_E_INVALID for a texel outside it); either output may be NULL, not both. */
+int   volym_read_interpolate(volym_ctx* ctx, struct volym_interpolate_summary* out);
+int   volym_read_interpolate_map(volym_ctx* ctx, const uint32_t sub[6], uint32_t* out);
+int   volym_read_interpolate_state(volym_ctx* ctx, const uint32_t sub[6], uint8_t* out);
+int   volym_interpolate_at(volym_ctx* ctx, uint32_t x, uint32_t y, uint32_t z, uint32_t* word, uint8_t* state);
+/* The context's own results in device memory after a pass (NULL before any, and after volym_set_volume): the summary (a struct
+ * volym_interpolate_summary), the signed map and the state map of the latest pass's box. */
+void* volym_interpolate_device_ptr(volym_ctx* ctx);
+void* volym_interpolate_map_device_ptr(volym_ctx* ctx);
+void* volym_interpolate_state_device_ptr(volym_ctx* ctx);
+/* The edit: a blocking set-up call with the contract of volym_edit_labels (one kernel, in place, on the first slot's stream; with
+ * changed == 0, or DRY_RUN, nothing else is touched; out may be NULL; the labels that may receive texels are those either table
+ * moves a label to).  While the history is on, a call that changes a texel (no DRY_RUN) is one step of it.
+ *   VOLYM_E_INVALID: NULL ctx or request, what volym_interpolate_labels_check refuses, a box that reaches outside the box of the
+ * interpolate pass.  VOLYM_E_STATE: what volym_edit_labels refuses of the context's state; no volym_interpolate_pass since
+ * volym_set_volume.  The native multi-GPU loop (volym_mgpu_*) has no forward for this call. */
+int   volym_interpolate_labels(volym_ctx* ctx, const volym_interpolate_edit* e, struct volym_relabel_result* out);
+/* Validity without a context: VOLYM_OK, or VOLYM_E_INVALID for NULL, a box without lo <= hi <= dims on every axis, a flag bit other
+ * than UNCUT and DRY_RUN, a window without min_byte <= max_byte <= 255.  An empty box is valid.  Pure host arithmetic. */
+int   volym_interpolate_labels_check(const volym_interpolate_edit* e, const uint32_t dims[3]);
 
 /* --- measurement ------------------------------------------------------------------ */
 int volym_stats_pass(volym_ctx* ctx, volym_stats* out);

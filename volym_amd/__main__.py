@@ -27,7 +27,7 @@ inside the set instead: thickness (demo.Simple.distance).  --measure [NAME,...] 
 mean, deviation, range, centroid and box per segment (demo.Simple.measure) -- and writes the density histogram of the visible scene
 and of each listed segment as <screenshot>_histogram.json (demo.Simple.histogram).
 --relabel FROM[,FROM...]:TO, --brush X,Y,Z[/X,Y,Z...]:TO:R2, --brush-at X,Y[/X,Y...]:NAME:R, --lasso X,Y/X,Y/X,Y[/...]:FROM[,FROM...]:TO (--lasso-outside), --smooth [NAME,...][:R[,R,R]] (--smooth-iterations N), --split-at X,Y:TO, --keep-largest NAME, --grow NAME:R, --shrink NAME:R, --fill [NAME,...][:R], --separate NAME:R, --flood [NAME,...][:R], --wand-at X,Y:NAME:TOL[:R], --grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]] and --smart-wand-at X,Y:NAME:CONTRAST:MAX_COST edit the labels on the device
-after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate, grow_through, wand_at, grow_from_seeds, smart_wand_at); the PNG is the frame after them and
+after the first frame, in that order (demo.Simple.relabel, GpuContext.brush_labels, Simple.stroke, lasso, smooth, split_at, keep_largest, grow, shrink, fill, separate, grow_through, wand_at, grow_from_seeds, smart_wand_at, fill_between); the PNG is the frame after them and
 each prints its result as one JSON line.  --labels-out FILE writes the labels as they then stand, raw bytes in the orientation of
 --labels (demo.Simple.save_labels).  --undo N keeps a history of those edits on the device (demo.Simple.history) and takes the last N
 back before the picture and --labels-out, one JSON line {"undo": ...} each.
@@ -391,6 +391,44 @@ def _grow_table(d, result):
     return "\n".join(lines)
 
 
+def _fill_between_arg(text):
+    """--fill-between NAME[,NAME...]:AXIS[:MAX_GAP] -> (names, axis, max_gap)"""
+    usage = ("NAME[,NAME...]:AXIS[:MAX_GAP] -- the segments to interpolate, the axis their painted slices are perpendicular to (x, y or z) and the most "
+             "slices a gap may have (default: no limit)")
+    parts = text.split(":")
+    try:
+        names = [_segment_arg(n) for n in parts[0].split(",") if n]
+        axis = parts[1] if len(parts) > 1 else ""
+        max_gap = int(parts[2]) if len(parts) > 2 else 0
+        if len(parts) > 3 or not names or axis not in ("x", "y", "z") or max_gap < 0:
+            raise ValueError
+    except ValueError:
+        raise SystemExit("--fill-between: %s" % usage)
+    return names, axis, max_gap
+
+
+def _fill_between_keys_arg(text):
+    """--fill-between-keys Z,Z,... -> the key slices"""
+    try:
+        keys = [int(v) for v in text.split(",") if v]
+        if not keys or min(keys) < 0:
+            raise ValueError
+    except ValueError:
+        raise SystemExit("--fill-between-keys: Z,Z,... -- the slices (coordinates along the axis of --fill-between) that count as painted")
+    return keys
+
+
+def _fill_between_table(result):
+    """what --fill-between prints: per segment the keys, the gaps filled and refused and the texels that joined and left"""
+    lines = []
+    for r in result:
+        s = r["summary"]
+        lines.append("fill between: %s label %d, %d key slices, %d gaps of %d slices filled, %d refused: %d texels joined, %d left" % (
+            r["name"], r["label"], s["n_keys"], s["n_gaps"], s["n_gap_slices"], s["n_refused"], r["relabel"]["arrived"].get(r["label"], 0),
+            r["relabel"]["left"].get(r["label"], 0)))
+    return "\n".join(lines)
+
+
 def _smart_wand_arg(text):
     """--smart-wand-at X,Y:NAME:CONTRAST:MAX_COST -> (x, y, name, contrast, max_cost)"""
     usage = "X,Y:NAME:CONTRAST:MAX_COST -- a pixel, the segment that takes what the wand reaches, the cost of a byte of density change and the most a texel may cost"
@@ -469,6 +507,10 @@ def _label_edits(ctx, d, args):
         if getattr(args, "smart_wand_at", None):
             x, y, name, contrast, max_cost = _smart_wand_arg(args.smart_wand_at)
             out.append(("smart_wand", d.smart_wand_at(ctx, x, y, _segment_arg(name), contrast, max_cost)))
+        if getattr(args, "fill_between", None):
+            names, axis, max_gap = _fill_between_arg(args.fill_between)
+            keys = _fill_between_keys_arg(args.fill_between_keys) if getattr(args, "fill_between_keys", None) else None
+            out.append(("fill_between", d.fill_between(ctx, names, axis, max_gap, keys, replace=keys is not None)))
     except ValueError as e:
         raise SystemExit("label edit: %s" % e)
     return out
@@ -594,6 +636,8 @@ def run_simple(args):
         elif option == "smart_wand":
             print("smart wand: %s" % ("nothing under the pixel" if result["relabel"] is None else "%d texels joined label %d" % (
                 result["relabel"]["changed"], result["relabel"]["label"])))
+        elif option == "fill_between":
+            print(_fill_between_table(result))
         elif option == "separate":
             print("separate: %d pieces%s" % (len(result), "".join(", %s %d texels" % (p["name"], p["texels"]) for p in result)))
         print(json.dumps({option: result}))      # one line per label edit: texels changed, per label left and arrived, the hull
@@ -789,6 +833,13 @@ def main(argv=None):
     run.add_argument("--smart-wand-at", metavar="X,Y:NAME:CONTRAST:MAX_COST",
                      help="the wand that stops at edges: from the texel under pixel (X, Y) through the unlabelled matter, a step costing 1 and CONTRAST per byte of "
                           "density change, for at most MAX_COST, into segment NAME (demo.Simple.smart_wand_at); after --grow-from-seeds")
+    run.add_argument("--fill-between", metavar="NAME[,NAME...]:AXIS[:MAX_GAP]",
+                     help="fill between slices on the device, after --smart-wand-at: each named segment, painted on some slices perpendicular to AXIS (x, y or z), is "
+                          "interpolated across the slices between them; gaps of more than MAX_GAP slices are left alone (default: no limit) "
+                          "(demo.Simple.fill_between); one undo step per segment")
+    run.add_argument("--fill-between-keys", metavar="Z,Z,...", help="with --fill-between: only these slices count as painted, and what the segment holds on the "
+                                                                     "slices between them outside the interpolated shape goes back to label 0 -- the way to fill again "
+                                                                     "after a key slice was repainted")
     run.add_argument("--undo", type=int, metavar="N", help="keep a history of the label edits above on the device and take the last N back, before the "
                                                            "picture and --labels-out; each prints a JSON line {\"undo\": ...}")
     run.add_argument("--labels-out", help="FILE: write the labels as they stand after the edits, raw bytes in the orientation of --labels")

@@ -372,6 +372,59 @@ class Fill(C.Structure):
     ]
 
 
+INTERPOLATE_UNCUT, INTERPOLATE_KEYS = 1, 2                      # volym_interpolate.flags
+INTERPOLATE_SHAPE, INTERPOLATE_INSIDE, INTERPOLATE_GAP = 1, 2, 4   # bits of a state byte
+INTERPOLATE_SLICE_OUTSIDE, INTERPOLATE_SLICE_KEY, INTERPOLATE_SLICE_GAP, INTERPOLATE_SLICE_REFUSED = 0, 1, 2, 3
+INTERPOLATE_NONE = 0xFFFFFFFF                                  # no key slice, or a key slice without SHAPE
+INTERPOLATE_SLICES = 4096
+INTERPOLATE_EDIT_UNCUT, INTERPOLATE_EDIT_DRY_RUN = 1, 2        # volym_interpolate_edit.flags
+
+
+class Interpolate(C.Structure):
+    """volym_interpolate (include/volym_hip.h): box, flags, min_byte, select, weights, axis, max_gap and the key bits, 820 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("select", C.c_uint8 * 256),
+        ("weight", C.c_uint32 * 3),
+        ("axis", C.c_uint32),
+        ("max_gap", C.c_uint32),
+        ("keys", C.c_uint32 * (INTERPOLATE_SLICES // 32)),
+    ]
+
+
+class InterpolateSlice(C.Structure):
+    """volym_interpolate_slice (include/volym_hip.h): the kind of one slice, the keys about it and its count, 16 bytes"""
+    _fields_ = [("kind", C.c_uint32), ("key_lo", C.c_uint32), ("key_hi", C.c_uint32), ("count", C.c_uint32)]
+
+
+class InterpolateSummary(C.Structure):
+    """volym_interpolate_summary (include/volym_hip.h): the slice and gap counts, the texel counts and the slice records, 65592 bytes"""
+    _fields_ = [("n_slices", C.c_uint32), ("n_keys", C.c_uint32), ("n_gaps", C.c_uint32), ("n_gap_slices", C.c_uint32), ("n_refused", C.c_uint32),
+                ("reserved", C.c_uint32), ("n_shape", C.c_uint64), ("n_inside", C.c_uint64), ("n_new", C.c_uint64), ("n_stale", C.c_uint64),
+                ("slice", InterpolateSlice * INTERPOLATE_SLICES)]
+
+
+# the summary as a NumPy structured dtype (GpuContext.read_interpolate, scene.interpolate_volume)
+INTERPOLATE_SLICE_DTYPE = np.dtype([("kind", "<u4"), ("key_lo", "<u4"), ("key_hi", "<u4"), ("count", "<u4")])
+INTERPOLATE_SUMMARY_DTYPE = np.dtype([("n_slices", "<u4"), ("n_keys", "<u4"), ("n_gaps", "<u4"), ("n_gap_slices", "<u4"), ("n_refused", "<u4"), ("reserved", "<u4"),
+                                      ("n_shape", "<u8"), ("n_inside", "<u8"), ("n_new", "<u8"), ("n_stale", "<u8"),
+                                      ("slice", INTERPOLATE_SLICE_DTYPE, (INTERPOLATE_SLICES,))])
+
+
+class InterpolateEdit(C.Structure):
+    """volym_interpolate_edit (include/volym_hip.h): box, flags, density window and the to and out tables of one edit, 548 bytes"""
+    _fields_ = [
+        ("box", C.c_uint32 * 6),
+        ("flags", C.c_uint32),
+        ("min_byte", C.c_uint32),
+        ("max_byte", C.c_uint32),
+        ("to", C.c_uint8 * 256),
+        ("out", C.c_uint8 * 256),
+    ]
+
+
 GEODESIC_UNCUT = 1                                             # volym_geodesic.flags
 GEODESIC_POINTS_MAX = 64
 GEODESIC_STEPS_MAX = 0xFFFFFD                                  # 2^24 - 3: the largest step count a key holds
@@ -739,6 +792,17 @@ SIGNATURES = {
     "volym_cost_map_device_ptr": (C.c_void_p, [_ctx]),
     "volym_spread_labels": (C.c_int, [_ctx, C.POINTER(Spread), C.POINTER(RelabelResult)]),
     "volym_spread_check": (C.c_int, [C.POINTER(Spread), C.POINTER(C.c_uint32)]),
+    "volym_interpolate_pass": (C.c_int, [_ctx, C.POINTER(Interpolate)]),
+    "volym_interpolate_check": (C.c_int, [C.POINTER(Interpolate), C.POINTER(C.c_uint32)]),
+    "volym_read_interpolate": (C.c_int, [_ctx, C.POINTER(InterpolateSummary)]),
+    "volym_read_interpolate_map": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "volym_read_interpolate_state": (C.c_int, [_ctx, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+    "volym_interpolate_at": (C.c_int, [_ctx, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]),
+    "volym_interpolate_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_interpolate_map_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_interpolate_state_device_ptr": (C.c_void_p, [_ctx]),
+    "volym_interpolate_labels": (C.c_int, [_ctx, C.POINTER(InterpolateEdit), C.POINTER(RelabelResult)]),
+    "volym_interpolate_labels_check": (C.c_int, [C.POINTER(InterpolateEdit), C.POINTER(C.c_uint32)]),
     "volym_stats_pass": (C.c_int, [_ctx, C.POINTER(Stats)]),
     "volym_time_passes": (C.c_int, [_ctx, C.c_uint32, _f32p]),
     "volym_time_batch": (C.c_int, [_ctx, C.c_uint32, _f32p]),

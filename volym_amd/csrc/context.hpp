@@ -8,6 +8,7 @@
 //   nearest.hip       the nearest pass and the fill by it, an edit like those below
 //   geodesic.hip      the geodesic pass and the flood by it, an edit like those below
 //   cost.hip          the cost pass; the spread by it is the flood's kernel, launched by geodesic.hip's flood_by_map
+//   interpolate.hip   the interpolate pass (fill between slices) and the edit by it, an edit like those below
 //   relabel.hip, brush.hip, lasso.hip, smooth.hip
 //                     the label edit of that name (relabel.hip: and the history); what they share on the host is label_edit.hpp
 //   box_pass.hip      no ABI: what the passes over a request's box share -- the scan of row counts into offsets and the read-back
@@ -298,6 +299,15 @@ struct volym_ctx {
     uint32_t cost_box[6] = {};               // the box of the latest pass (the reads and the spread address the map by it)
     uint64_t cost_rounds = 0;                // the rounds the latest pass enqueued, those past the last active one included
 
+    // interpolate passes (volym_interpolate_pass, interpolate.hip): a snapshot of its own, valid until the next volym_set_volume
+    volym::OwnedBuffer<volym_interpolate_summary> interpolate;   // one summary, reserved once; count 1: a pass has written it since the latest volym_set_volume
+    volym::OwnedBuffer<uint32_t> interpolate_work;   // four words per texel of the request's box: Dout, Din and the two stacks of the column sweeps; the signed
+                                                     // map is stored over the first stack (interpolate_kernels.h)
+    volym::OwnedBuffer<uint8_t> interpolate_state;   // the state byte of every texel of that box, box-linear
+    volym::OwnedBuffer<uint32_t> interpolate_counts; // the SHAPE texels per slice, VOLYM_INTERPOLATE_SLICES words
+    uint32_t interpolate_box[6] = {};        // the box of the latest pass (the reads and the edit address the maps by it)
+    uint32_t interpolate_texels = 0;         // ... and its texels: the signed map starts at word 2 * interpolate_texels of the work array
+
     // the history of label edits (volym_label_history, relabel.hip): off (budget 0) in a new context
     struct LabelStep {
         uint32_t* index = nullptr;           // the chunks the edit stored ...
@@ -391,6 +401,8 @@ void free_geodesic(volym_ctx* c);
 int flood_by_map(volym_ctx* c, const volym_flood* f, const uint32_t* keys, const uint32_t pass_box[6], const char* who, volym_relabel_result& res);
 // cost.hip: what the context keeps for the cost pass (every stream idle)
 void free_cost(volym_ctx* c);
+// interpolate.hip: what the context keeps for the interpolate pass (every stream idle)
+void free_interpolate(volym_ctx* c);
 // relabel.hip: the steps of the label history, when the labels they belong to are replaced or dropped (the budget stays)
 void clear_label_history(volym_ctx* c);
 // relabel.hip: the steps and the staging area of the label history (every stream idle)

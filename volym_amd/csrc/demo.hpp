@@ -328,6 +328,41 @@ public:
         records_current_ = false;
         return out;
     }
+    // New: fill between slices (volym_interpolate_pass, volym_interpolate_labels): each segment of `names` (names, ids or label values
+    // as text; at least one), painted on some slices perpendicular to `axis` (0, 1, 2), is interpolated across the slices between them
+    // -- one pass and one edit per segment, each one step of the history.  The unlabelled texels the interpolated shape holds join the
+    // segment; gaps of more than max_gap slices are left alone (0: no limit).  Returns per segment its label, the summary's counts and the
+    // edit's result.
+    struct FilledBetween { uint32_t label, n_keys, n_gaps, n_gap_slices, n_refused; volym_relabel_result result; };
+    std::vector<FilledBetween> fill_between(const GpuContext& ctx, const SimpleAssets& a, const std::vector<std::string>& names, uint32_t axis, uint32_t max_gap)
+    {
+        set_segments(ctx, a, a.segments);
+        if (!labels_on_device_) throw Error(VOLYM_E_STATE, "fill between: the labels are shorter than the volume and label 0 is important: they cannot stay on the device");
+        if (names.empty()) throw Error(VOLYM_E_INVALID, "fill between: name the segments to interpolate");
+        std::vector<FilledBetween> out;
+        auto summary = std::make_unique<volym_interpolate_summary>();      // (65592 bytes)
+        for (const std::string& n : names) {
+            const uint32_t l = label_value_of(a, n);
+            volym_interpolate q{};
+            q.box[3] = a.nx; q.box[4] = a.ny; q.box[5] = a.nz;
+            q.select[l] = 1u;
+            q.weight[0] = q.weight[1] = q.weight[2] = 1u;
+            q.axis = axis; q.max_gap = max_gap;
+            ctx.check(volym_interpolate_pass(ctx.handle(), &q));
+            volym_interpolate_edit e{};
+            std::memcpy(e.box, q.box, sizeof e.box);
+            e.max_byte = 255u;
+            for (int k = 0; k < 256; ++k) e.to[k] = e.out[k] = static_cast<uint8_t>(k);
+            e.to[0] = static_cast<uint8_t>(l);
+            FilledBetween f{};
+            ctx.check(volym_interpolate_labels(ctx.handle(), &e, &f.result));
+            ctx.check(volym_read_interpolate(ctx.handle(), summary.get()));
+            f.label = l; f.n_keys = summary->n_keys; f.n_gaps = summary->n_gaps; f.n_gap_slices = summary->n_gap_slices; f.n_refused = summary->n_refused;
+            out.push_back(f);
+        }
+        records_current_ = false;
+        return out;
+    }
     // New: keep a history of the label edits in at most budget_bytes of device memory (volym_label_history), so that undo can take
     // them back.  The labels go to the device first: handing them to the context clears the history.
     void history(const GpuContext& ctx, const SimpleAssets& a, uint64_t budget_bytes = 256ull << 20)

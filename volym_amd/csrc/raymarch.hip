@@ -609,6 +609,7 @@ void volym_destroy(volym_ctx* c)
     free_nearest(c);
     free_geodesic(c);
     free_cost(c);
+    free_interpolate(c);
     free_label_history(c);
     free_lasso(c);
     for (uint32_t i = 0; i < volym_ctx::THROTTLE_RING; ++i) if (c->throttle_ev[i]) (void)hipEventDestroy(c->throttle_ev[i]);

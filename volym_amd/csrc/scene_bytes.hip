@@ -916,6 +916,7 @@ int volym_set_volume(volym_ctx* c, const uint8_t* voxels, uint32_t nx, uint32_t 
     free_nearest(c);                        // (and the nearest pass's sites)
     free_geodesic(c);                       // (and the geodesic pass's keys)
     free_cost(c);                           // (and the cost pass's keys and bytes)
+    free_interpolate(c);                    // (and the interpolate pass's maps)
     rc = upload_volume(c, &c->d_vol, voxels, nx, ny, nz);
     if (rc != VOLYM_OK) { c->have_vol = false; return rc; }
     c->nx = nx; c->ny = ny; c->nz = nz; c->filter = filter;

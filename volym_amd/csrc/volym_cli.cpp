@@ -26,6 +26,8 @@
 //   --grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]] grows the segments NAME at once through the unlabelled matter of density
 //   above 0, a step costing 1 and CONTRAST (default 16) per byte of density change across it: a texel joins the segment that reaches
 //   it most cheaply, for at most MAX_COST (Simple::grow_from_seeds), after --flood;
+//   --fill-between NAME[,NAME...]:AXIS[:MAX_GAP] interpolates each segment NAME, painted on some slices perpendicular to AXIS (x, y or z),
+//   across the slices between them; gaps of more than MAX_GAP slices are left alone (Simple::fill_between), after --grow-from-seeds;
 //   --fill [NAME,...][:R] grows the segments NAME (none: every segment) at once into the unlabelled matter: every unlabelled texel
 //   with a density byte above 0 joins the segment it is nearest to, at most R texels away (Simple::fill), after --smooth;
 //   --undo N keeps a history of the edits on the device (Simple::history) and takes the last N back before both, printing each.
@@ -96,6 +98,9 @@ struct Options {
     bool grow = false;                                   // --grow-from-seeds NAME[,NAME...][:CONTRAST[:MAX_COST]]: the segments grow by cost (run simple)
     std::vector<std::string> grow_names;
     uint32_t grow_contrast = 16u, grow_max_cost = 0u;    // (0: however much)
+    bool between = false;                                // --fill-between NAME[,NAME...]:AXIS[:MAX_GAP]: the segments are interpolated across gaps (run simple)
+    std::vector<std::string> between_names;
+    uint32_t between_axis = 2u, between_max_gap = 0u;    // (0: no limit)
     uint32_t undo = 0;             // --undo N: keep a history of the label edits on the device and take the last N back (run simple)
     std::string labels_out;        // --labels-out FILE: the labels as they stand after the edits, raw bytes (run simple)
     bool surface = false;          // --surface [NAME,...][:MIN_BYTE]: also print the surface table (run simple)
@@ -244,6 +249,8 @@ int run_simple(const Options& o)
     if (o.flood) flooded = demo.flood(ctx, assets, o.flood_names, o.flood_r);                               // after --fill, before --undo
     volym_relabel_result grown{};
     if (o.grow) grown = demo.grow_from_seeds(ctx, assets, o.grow_names, o.grow_contrast, o.grow_max_cost);   // after --flood, before --undo
+    std::vector<Simple::FilledBetween> between;
+    if (o.between) between = demo.fill_between(ctx, assets, o.between_names, o.between_axis, o.between_max_gap);   // after --grow-from-seeds, before --undo
     std::vector<std::pair<bool, volym_relabel_result>> undone(o.undo);       // the last N edits back, before the picture and --labels-out
     for (auto& u : undone) u.first = demo.undo(ctx, u.second);
     demo.update_gpu_state(ctx, state);
@@ -303,6 +310,14 @@ int run_simple(const Options& o)
             for (const SegmentInfo& s : assets.segments) if (s.label_value == l) name = s.name.empty() ? s.id : s.name;
             std::printf("  + %-16s label %3d: %10llu\n", name.c_str(), l, static_cast<unsigned long long>(grown.arrived[l]));
         }
+    }
+    for (const auto& f : between) {
+        // per segment the keys, the gaps filled and refused and the texels that joined and left
+        std::string name = "label " + std::to_string(f.label);
+        for (const SegmentInfo& s : assets.segments) if (s.label_value == static_cast<int>(f.label)) name = s.name.empty() ? s.id : s.name;
+        std::printf("fill between: %s label %u, %u key slices, %u gaps of %u slices filled, %u refused: %llu texels joined, %llu left\n", name.c_str(), f.label, f.n_keys,
+                    f.n_gaps, f.n_gap_slices, f.n_refused, static_cast<unsigned long long>(f.result.arrived[f.label]),
+                    static_cast<unsigned long long>(f.result.left[f.label]));
     }
     for (const auto& u : undone) {
         if (u.first) print_result("undo", u.second);
@@ -646,6 +661,36 @@ int main(int argc, char** argv)
                     }
                 } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
                 if (o.grow_names.empty()) throw Error(VOLYM_E_INVALID, usage);
+            }
+            else if (a == "--fill-between") {
+                const char* usage = "--fill-between: NAME[,NAME...]:AXIS[:MAX_GAP] -- the segments to interpolate, the axis their painted slices are perpendicular to "
+                                    "(x, y or z) and the most slices a gap may have";
+                o.between = true;
+                const std::string v = next();
+                std::vector<std::string> parts;
+                size_t pos = 0;
+                while (pos <= v.size()) {
+                    const size_t colon = std::min(v.find(':', pos), v.size());
+                    parts.push_back(v.substr(pos, colon - pos));
+                    pos = colon + 1u;
+                }
+                if (parts.size() < 2u || parts.size() > 3u || parts[1].size() != 1u || parts[1][0] < 'x' || parts[1][0] > 'z') throw Error(VOLYM_E_INVALID, usage);
+                o.between_axis = static_cast<uint32_t>(parts[1][0] - 'x');
+                pos = 0;
+                while (pos < parts[0].size()) {
+                    const size_t comma = std::min(parts[0].find(',', pos), parts[0].size());
+                    if (comma > pos) o.between_names.push_back(parts[0].substr(pos, comma - pos));
+                    pos = comma + 1u;
+                }
+                try {
+                    size_t used = 0;
+                    if (parts.size() > 2u) {
+                        const unsigned long g = std::stoul(parts[2], &used);
+                        if (used != parts[2].size() || g > 4096ul) throw Error(VOLYM_E_INVALID, usage);
+                        o.between_max_gap = static_cast<uint32_t>(g);
+                    }
+                } catch (const std::logic_error&) { throw Error(VOLYM_E_INVALID, usage); }
+                if (o.between_names.empty()) throw Error(VOLYM_E_INVALID, usage);
             }
             else if (a == "--labels-out") o.labels_out = next();
             else if (a == "--undo") o.undo = static_cast<uint32_t>(std::stoul(next()));

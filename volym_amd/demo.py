@@ -717,6 +717,70 @@ class GpuContext:
         self._ck(_lib.lib().volym_spread_labels(self.handle, C.byref(spread.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
         return out[0]
 
+    # ---- fill between slices ----------------------------------------------------------------------
+    def interpolate_pass(self, interpolate):
+        """Enqueue one interpolate pass (include/volym_hip.h volym_interpolate_pass; scene.interpolate_volume is its definition): the
+        key slices of the request's box along its axis, the signed planar distance of the selected shape on each of them, and for
+        every texel of the slices between two keys whether the interpolated shape holds it.  `interpolate` is a scene.Interpolate."""
+        self._ck(_lib.lib().volym_interpolate_pass(self.handle, C.byref(interpolate.to_c())))
+        box = interpolate.box
+        self._interpolate_box = box if all(a < b for a, b in zip(*box)) else None
+
+    def read_interpolate(self):
+        """The summary of the latest interpolate pass: an np.void of _lib.INTERPOLATE_SUMMARY_DTYPE.  Blocks."""
+        out = np.zeros(1, _lib.INTERPOLATE_SUMMARY_DTYPE)
+        self._ck(_lib.lib().volym_read_interpolate(self.handle, out.ctypes.data_as(C.POINTER(_lib.InterpolateSummary))))
+        return out[0]
+
+    def _read_interpolate_map(self, call, dtype, ctype, sub):
+        box = getattr(self, "_interpolate_box", None) if sub is None else (tuple(int(v) for v in sub[0]), tuple(int(v) for v in sub[1]))
+        if box is None:                                        # no pass yet (the library refuses), or a pass over an empty box
+            self._ck(call(self.handle, None, None))
+            return np.zeros((0, 0, 0), dtype)
+        c = None if sub is None else (C.c_uint32 * 6)(*(list(box[0]) + list(box[1])))
+        out = np.zeros(tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0)), dtype)
+        self._ck(call(self.handle, c, out.ctypes.data_as(C.POINTER(ctype))))
+        return out
+
+    def read_interpolate_map(self, sub=None):
+        """The signed planar map of the latest interpolate pass as a uint32 array [z, y, x]: of its whole box (None) or of the sub-box
+        (lo, hi) in texels of the volume, which must lie inside the pass's box.  On a key slice D << 1 | 1 inside the shape and
+        D << 1 outside it; _lib.INTERPOLATE_NONE elsewhere.  Blocks."""
+        return self._read_interpolate_map(_lib.lib().volym_read_interpolate_map, np.uint32, C.c_uint32, sub)
+
+    def read_interpolate_state(self, sub=None):
+        """The state bytes of the latest interpolate pass (_lib.INTERPOLATE_SHAPE | INSIDE | GAP) as a uint8 array [z, y, x], as
+        read_interpolate_map.  Blocks."""
+        return self._read_interpolate_map(_lib.lib().volym_read_interpolate_state, np.uint8, C.c_uint8, sub)
+
+    def interpolate_at(self, x, y, z):
+        """The signed word and the state byte of texel (x, y, z) in the latest interpolate pass: {"word", "state"}.  Blocks."""
+        word, state = C.c_uint32(0), C.c_uint8(0)
+        self._ck(_lib.lib().volym_interpolate_at(self.handle, int(x), int(y), int(z), C.byref(word), C.byref(state)))
+        return {"word": int(word.value), "state": int(state.value)}
+
+    def interpolate_device_ptr(self):
+        """The context's own summary (a volym_interpolate_summary in device memory) after a pass (None before any)."""
+        return _lib.lib().volym_interpolate_device_ptr(self.handle)
+
+    def interpolate_map_device_ptr(self):
+        """The signed map of the latest interpolate pass in device memory (None before any)."""
+        return _lib.lib().volym_interpolate_map_device_ptr(self.handle)
+
+    def interpolate_state_device_ptr(self):
+        """The state map of the latest interpolate pass in device memory (None before any)."""
+        return _lib.lib().volym_interpolate_state_device_ptr(self.handle)
+
+    def interpolate_labels(self, edit):
+        """One edit by the latest interpolate pass on the device (include/volym_hip.h volym_interpolate_labels;
+        scene.interpolate_labels_volume is its definition): a texel of a gap slice in the box becomes to[label] where the interpolated
+        shape holds it and out[label] where it does not, within the density window.  `edit` is a scene.InterpolateEdit.  Everything
+        follows as after edit_labels, and the call is one step of the history.  Blocks.  Returns the result: an np.void of
+        _lib.RELABEL_RESULT_DTYPE."""
+        out = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)
+        self._ck(_lib.lib().volym_interpolate_labels(self.handle, C.byref(edit.to_c()), out.ctypes.data_as(C.POINTER(_lib.RelabelResult))))
+        return out[0]
+
     # ---- editing labels --------------------------------------------------------------------------
     def edit_labels(self, relabel):
         """One edit of the labels on the device (include/volym_hip.h volym_edit_labels; scene.relabel_volume is its definition):
@@ -1712,6 +1776,42 @@ class Simple(ComputeDemo):
             # the seed carries the picked texel's label, whatever it is: every cost label takes, and all of them become `value`
             p["relabel"] = self._spread(ctx, scene.Spread(None, 0, (0, 255), scene.smooth_table(medium), None, np.full(256, value, np.int64), dims=self.dims))
             p["relabel"].update(label=value)
+        return p
+
+    # ---- fill between slices ----------------------------------------------------------------------
+    def fill_between(self, ctx, names, axis, max_gap=0, keys=None, replace=False, min_byte=0, spacing=(1, 1, 1)):
+        """Fill between slices: each segment of `names` (names, ids or label values), painted on some slices perpendicular to `axis`
+        ("x", "y", "z" or 0, 1, 2), is interpolated across the slices between them -- one interpolate pass and one edit per segment,
+        each one undo step.  The unlabelled texels the interpolated shape holds join the segment.  max_gap: gaps of more slices are
+        left alone (0: no limit); keys: the slices (volume coordinates along axis) that count as painted -- the way to redo a fill
+        after a key slice was repainted, when the slices filled last time must not count; None: every slice that holds the segment;
+        replace: texels of the segment on the filled slices that the shape does not hold go back to label 0.  Nothing joins shapes that
+        do not overlap when seen along the axis: each only shrinks towards the other key inside its own outline.  Returns [{"name", "label", "summary", "relabel"}] per segment."""
+        self._ready_to_edit(ctx)
+        weights, _unit = scene.distance_weights(spacing)
+        flags = 0 if keys is None else _lib.INTERPOLATE_KEYS
+        out = []
+        for l in self._label_values(names):
+            q = scene.check_interpolate(scene.Interpolate(None, flags, min_byte, scene.surface_select([l]), weights, axis, max_gap, keys or (), dims=self.dims), self.dims)
+            ctx.interpolate_pass(q)
+            edit = scene.check_interpolate_edit(scene.InterpolateEdit(None, 0, (0, 255), {0: l}, {l: 0} if replace else None, dims=self.dims), self.dims)
+            result = ctx.interpolate_labels(edit)
+            if int(result["changed"]):
+                self._labels_edited = True
+                self._records_for = None
+            out.append({"name": self._segment_name(l) or "label %d" % l, "label": l, "summary": scene.interpolate_summary(ctx.read_interpolate()),
+                        "relabel": scene.relabel_result_dict(result)})
+        return out
+
+    def fill_between_at(self, ctx, x, y, axis, max_gap=0, alpha_min=0.5):
+        """Fill between slices for the segment under pixel (x, y): pick, then fill_between of the label the pixel shows.  Returns the
+        pick with a "fill_between" entry (fill_between's entry for the segment); None there when the pixel shows nothing or an
+        unlabelled texel."""
+        self._ready_to_edit(ctx)
+        p = self.pick(ctx, x, y, alpha_min)
+        p["fill_between"] = None
+        if p["status"] == "hit" and p["texel"] is not None and p["label"]:
+            p["fill_between"] = self.fill_between(ctx, [int(p["label"])], axis, max_gap)[0]
         return p
 
     def _brush(self, ctx, brush):

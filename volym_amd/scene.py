@@ -2657,6 +2657,273 @@ def spread_volume(prepared, dims, spread, labels, keys, pass_box, uncut=None):
     return new, result
 
 
+class Interpolate:
+    """volym_interpolate (include/volym_hip.h): what one interpolate pass (fill between slices) maps.  box, min_byte, select and weight
+    as Distance takes them, but min_byte may be 0 (labels alone decide); flags: _lib.INTERPOLATE_UNCUT | INTERPOLATE_KEYS; axis: 0, 1 or
+    2 (or "x", "y", "z"), the slices are the planes perpendicular to it; max_gap: 0 for no limit, else a gap of more slices is not
+    filled; keys: the volume coordinates along axis of the key slices, read with KEYS only."""
+
+    def __init__(self, box=None, flags=0, min_byte=1, select=None, weight=(1, 1, 1), axis=2, max_gap=0, keys=(), dims=None):
+        self.box = _box_or_whole(box, dims, "an interpolate request without a box needs the volume's dims")
+        self.flags = int(flags)
+        self.min_byte = int(min_byte)
+        self.select = np.ones(256, np.int64) if select is None else np.array(select, np.int64).ravel()
+        self.weight = tuple(int(v) for v in weight)
+        self.axis = "xyz".index(axis) if isinstance(axis, str) and axis in ("x", "y", "z") else int(axis)
+        self.max_gap = int(max_gap)
+        self.keys = tuple(sorted(set(int(k) for k in keys)))
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "interpolate", ("box", "flags", "min_byte", "select", "weight", "axis", "max_gap", "keys"), kw)
+
+    def key_words(self):
+        """The 128 words of the request's key bits; ValueError for a key outside 0..4095."""
+        words = [0] * (_lib.INTERPOLATE_SLICES // 32)
+        for k in self.keys:
+            if not 0 <= k < _lib.INTERPOLATE_SLICES:
+                raise ValueError("interpolate: a key slice is 0..%d, got %d" % (_lib.INTERPOLATE_SLICES - 1, k))
+            words[k >> 5] |= 1 << (k & 31)
+        return words
+
+    def to_c(self):
+        """The _lib.Interpolate of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _lib.Interpolate()
+        c.box = _box_to_c(self.box, "interpolate")
+        if not all(0 <= v < 2 ** 32 for v in (self.flags, self.min_byte, self.axis, self.max_gap)):
+            raise ValueError("interpolate: flags, min_byte, axis and max_gap must be u32")
+        c.flags, c.min_byte, c.axis, c.max_gap = self.flags, self.min_byte, self.axis, self.max_gap
+        if self.select.size != 256 or not ((self.select >= 0) & (self.select <= 255)).all():
+            raise ValueError("interpolate: the select table is 256 bytes")
+        c.select = (C.c_uint8 * 256)(*[int(g) for g in self.select])
+        if len(self.weight) != 3 or not all(0 <= x < 2 ** 32 for x in self.weight):
+            raise ValueError("interpolate: the weights are three u32")
+        c.weight = (C.c_uint32 * 3)(*self.weight)
+        c.keys = (C.c_uint32 * (_lib.INTERPOLATE_SLICES // 32))(*self.key_words())
+        return c
+
+
+def check_interpolate(interpolate, dims):
+    """The validity rules of volym_interpolate_check: lo <= hi <= dims on every axis (an empty box is valid), at most
+    _lib.DISTANCE_BOX_MAX texels in the box and _lib.INTERPOLATE_SLICES along an axis, known flag bits, min_byte in 0..255, every
+    weight in 1.._lib.DISTANCE_WEIGHT_MAX, an axis in 0..2.  Returns the request; raises ValueError."""
+    q = interpolate
+    lo, hi, dims = _box_in_dims(q.box, dims, "interpolate")
+    texels = (hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2])
+    if texels > _lib.DISTANCE_BOX_MAX or any(hi[a] - lo[a] > _lib.INTERPOLATE_SLICES for a in range(3)):
+        raise ValueError("interpolate: the box has %d texels, more than 2^31 - 2, or more than %d along an axis" % (texels, _lib.INTERPOLATE_SLICES))
+    if q.flags & ~(_lib.INTERPOLATE_UNCUT | _lib.INTERPOLATE_KEYS) or q.flags < 0:
+        raise ValueError("interpolate: unknown flag bits in %#x" % q.flags)
+    if not 0 <= q.min_byte <= 255:
+        raise ValueError("interpolate: min_byte is 0..255, got %d" % q.min_byte)
+    if len(q.weight) != 3 or not all(1 <= v <= _lib.DISTANCE_WEIGHT_MAX for v in q.weight):
+        raise ValueError("interpolate: the weights are three integers in 1..%d, got %r" % (_lib.DISTANCE_WEIGHT_MAX, (q.weight,)))
+    if q.axis not in (0, 1, 2):
+        raise ValueError("interpolate: the axis is 0, 1 or 2, got %r" % (q.axis,))
+    if q.max_gap < 0:
+        raise ValueError("interpolate: max_gap is 0 (no limit) or a number of slices, got %d" % q.max_gap)
+    if np.asarray(q.select).size != 256:
+        raise ValueError("interpolate: the select table has 256 entries")
+    q.key_words()
+    return q
+
+
+def empty_interpolate():
+    """(summary, map, state) of a pass over an empty box: no slice (an np.void of _lib.INTERPOLATE_SUMMARY_DTYPE) and no maps."""
+    return np.zeros(1, _lib.INTERPOLATE_SUMMARY_DTYPE)[0], np.zeros((0, 0, 0), np.uint32), np.zeros((0, 0, 0), np.uint8)
+
+
+def _planar_d2(seeds, weights):
+    """Per plane seeds[k] (bool [k, u, v]): the smallest weights[0] * du^2 + weights[1] * dv^2 to a seed of the plane, int64; `far`
+    (2^40) in a plane without seeds.  One broadcast minimum per axis, as distance_volume takes it."""
+    far = np.int64(1) << 40
+    g = np.where(seeds, np.int64(0), far)
+    for axis, weight in ((2, weights[1]), (1, weights[0])):
+        n = g.shape[axis]
+        shape = [1, 1, 1]
+        shape[axis] = n
+        i = np.arange(n, dtype=np.int64).reshape(shape)
+        f = np.full(g.shape, far, np.int64)
+        for j in range(n):
+            at = [slice(None)] * 3
+            at[axis] = slice(j, j + 1)
+            np.minimum(f, g[tuple(at)] + weight * (i - j) ** 2, out=f)
+        g = np.minimum(f, far)
+    return g
+
+
+def interpolate_volume(prepared, dims, q, labels=None, cut=None, uncut=None):
+    """The definition of the interpolate pass (include/volym_hip.h volym_interpolate_pass), NumPy integers only; equal to the device in
+    every byte.  `prepared`, `uncut`, `labels` and `cut` are what distance_volume takes.  Returns (summary, map, state): an np.void of
+    _lib.INTERPOLATE_SUMMARY_DTYPE, the signed planar map as a uint32 array [z, y, x] over the request's box and the state bytes as a
+    uint8 array of the same shape (their bytes are the box-linear maps)."""
+    q = check_interpolate(q, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = q.box
+    summary, no_map, no_state = empty_interpolate()
+    if any(a >= b for a, b in zip(lo, hi)):
+        return summary, no_map, no_state
+    whole = bool(q.flags & _lib.INTERPOLATE_UNCUT)
+    src = np.ascontiguousarray(uncut if (whole and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != nx * ny * nz:
+        raise ValueError("interpolate_volume: the density has %d bytes, the volume %d" % (src.size, nx * ny * nz))
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    b = src.reshape(nz, ny, nx)[sub]
+    if labels is None:
+        l = np.zeros(b.shape, np.uint8)
+    else:
+        lab = np.ascontiguousarray(labels, np.uint8).ravel()
+        if lab.size != src.size:
+            raise ValueError("interpolate_volume: labels have %d bytes, the volume %d" % (lab.size, src.size))
+        l = lab.reshape(nz, ny, nx)[sub]
+    none = np.int64(_lib.INTERPOLATE_NONE)
+    # slices first: [k, u, v] with (u, v) the two in-plane axes in the order (z, y, x) keeps them
+    np_axis = 2 - q.axis
+    shape = np.moveaxis((b >= q.min_byte) & (np.asarray(q.select)[l] != 0), np_axis, 0)
+    weights = [q.weight[a] for a in (2, 1, 0) if a != q.axis]
+    n = shape.shape[0]
+    counts = shape.reshape(n, -1).sum(axis=1)
+    first = lo[q.axis]
+    if q.flags & _lib.INTERPOLATE_KEYS:
+        is_key = np.array([(first + k) in set(q.keys) for k in range(n)], bool)
+    else:
+        is_key = counts > 0
+    keys = np.flatnonzero(is_key).tolist()
+    word = np.full(shape.shape, none, np.int64)
+    state = np.where(shape, _lib.INTERPOLATE_SHAPE, 0).astype(np.uint8)
+    if keys:
+        s = shape[keys]
+        far = np.int64(1) << 40
+        d_out, d_in = _planar_d2(s, weights), _planar_d2(~s, weights)
+        for axis, weight in ((1, weights[0]), (2, weights[1])):        # texels outside the box are not SHAPE
+            m = s.shape[axis]
+            at = [1, 1, 1]
+            at[axis] = m
+            i = np.arange(m, dtype=np.int64).reshape(at)
+            d_in = np.minimum(d_in, weight * np.minimum(i + 1, m - i) ** 2)
+        word[keys] = np.where(s, d_in << 1 | 1, np.where(d_out < far, d_out << 1, none))
+        state[keys] |= np.where(s, _lib.INTERPOLATE_INSIDE, 0).astype(np.uint8)
+    rec = summary["slice"]
+    rec["key_lo"][:n] = rec["key_hi"][:n] = _lib.INTERPOLATE_NONE
+    for k in keys:
+        rec[k] = (_lib.INTERPOLATE_SLICE_KEY, first + k, first + k, counts[k])
+    n_gaps = n_gap_slices = n_refused = n_inside = n_new = n_stale = 0
+    for z0, z1 in zip(keys, keys[1:]):
+        if z1 - z0 < 2:
+            continue
+        if q.max_gap and z1 - z0 - 1 > q.max_gap:
+            n_refused += 1
+            for z in range(z0 + 1, z1):
+                rec[z] = (_lib.INTERPOLATE_SLICE_REFUSED, first + z0, first + z1, 0)
+            continue
+        n_gaps += 1
+        m0, m1 = word[z0], word[z1]
+        sh0, sh1 = (m0 != none) & ((m0 & 1) == 1), (m1 != none) & ((m1 & 1) == 1)
+        out0, out1 = (m0 != none) & ~sh0, (m1 != none) & ~sh1
+        d0, d1 = m0 >> 1, m1 >> 1
+        for z in range(z0 + 1, z1):
+            a2, b2 = np.int64((z1 - z) ** 2), np.int64((z - z0) ** 2)
+            inside = (sh0 & sh1) | (sh0 & out1 & (a2 * d0 > b2 * d1)) | (sh1 & out0 & (b2 * d1 > a2 * d0))
+            was = shape[z]
+            state[z] |= np.where(inside, _lib.INTERPOLATE_GAP | _lib.INTERPOLATE_INSIDE, _lib.INTERPOLATE_GAP).astype(np.uint8)
+            count = int(inside.sum())
+            rec[z] = (_lib.INTERPOLATE_SLICE_GAP, first + z0, first + z1, count)
+            n_gap_slices += 1
+            n_inside += count
+            n_new += int((inside & ~was).sum())
+            n_stale += int((was & ~inside).sum())
+    summary["n_slices"], summary["n_keys"], summary["n_gaps"], summary["n_gap_slices"], summary["n_refused"] = n, len(keys), n_gaps, n_gap_slices, n_refused
+    summary["n_shape"], summary["n_inside"], summary["n_new"], summary["n_stale"] = int(counts.sum()), n_inside, n_new, n_stale
+    return (summary, np.ascontiguousarray(np.moveaxis(word, 0, np_axis)).astype(np.uint32), np.ascontiguousarray(np.moveaxis(state, 0, np_axis)))
+
+
+def interpolate_summary(summary):
+    """What a user reads off an interpolate pass, as Python ints: the counters of the summary, "keys": the volume coordinates of the
+    key slices, "gaps": [(key_lo, key_hi)] of the fillable gaps and "refused": the same of those max_gap refused."""
+    n = int(summary["n_slices"])
+    rec = summary["slice"][:n]
+    out = {k: int(summary[k]) for k in ("n_slices", "n_keys", "n_gaps", "n_gap_slices", "n_refused", "n_shape", "n_inside", "n_new", "n_stale")}
+    out["keys"] = [int(r["key_lo"]) for r in rec if int(r["kind"]) == _lib.INTERPOLATE_SLICE_KEY]
+    for name, kind in (("gaps", _lib.INTERPOLATE_SLICE_GAP), ("refused", _lib.INTERPOLATE_SLICE_REFUSED)):
+        out[name] = sorted(set((int(r["key_lo"]), int(r["key_hi"])) for r in rec if int(r["kind"]) == kind))
+    return out
+
+
+class InterpolateEdit:
+    """volym_interpolate_edit (include/volym_hip.h): one edit by the latest interpolate pass.  box and window as Relabel takes them;
+    flags: _lib.INTERPOLATE_EDIT_UNCUT | INTERPOLATE_EDIT_DRY_RUN; to: the label an INSIDE texel of a gap slice becomes, out: the label
+    every other texel of a gap slice becomes (relabel_table's dicts or 256 labels; None: the identity)."""
+
+    def __init__(self, box=None, flags=0, window=(0, 255), to=None, out=None, dims=None):
+        _edit_fields(self, "interpolate edit", box, dims, flags, window, to)
+        self.out = relabel_table() if out is None else (relabel_table(out) if isinstance(out, dict) else np.array(out, np.int64).ravel())
+
+    def replace(self, **kw):
+        """A copy with the given fields changed."""
+        return _replaced(self, "interpolate edit", ("box", "flags", "window", "to", "out"), kw)
+
+    def to_c(self):
+        """The _lib.InterpolateEdit of this request.  Fields that do not fit their C types raise ValueError."""
+        c = _edit_fields_to_c(self, _lib.InterpolateEdit(), "interpolate edit", True, "flags and the window's ends must be u32")
+        if self.out.size != 256 or not ((self.out >= 0) & (self.out <= 255)).all():
+            raise ValueError("interpolate edit: the out table is 256 bytes")
+        c.out = (C.c_uint8 * 256)(*[int(g) for g in self.out])
+        return c
+
+
+def check_interpolate_edit(edit, dims):
+    """The validity rules of volym_interpolate_labels_check: lo <= hi <= dims on every axis (an empty box is valid), known flag bits,
+    min_byte <= max_byte <= 255, tables of 256 entries.  Returns the request; raises ValueError."""
+    _check_edit_fields(edit, dims, "interpolate edit", _lib.INTERPOLATE_EDIT_UNCUT | _lib.INTERPOLATE_EDIT_DRY_RUN)
+    if np.asarray(edit.out).size != 256:
+        raise ValueError("interpolate edit: the out table has 256 entries")
+    return edit
+
+
+def interpolate_labels_volume(prepared, dims, edit, labels, state, pass_box, uncut=None):
+    """The definition of the edit (include/volym_hip.h volym_interpolate_labels), NumPy integers only; equal to the device in every
+    byte.  `prepared`: the scene bytes as they stand (cuts applied), `uncut`: the uncut copy (read with UNCUT; None: prepared),
+    `labels`: the labels before the edit; state: the state map of the latest interpolate pass (interpolate_volume's) over pass_box =
+    ((lo), (hi)).  A texel of the box whose state has GAP and whose density byte lies in the window becomes to[l] where its state has
+    INSIDE and out[l] where it has not.  Returns (new_labels, result) as relabel_volume does."""
+    r = check_interpolate_edit(edit, dims)
+    nx, ny, nz = (int(v) for v in dims)
+    lo, hi = r.box
+    result = np.zeros(1, _lib.RELABEL_RESULT_DTYPE)[0]
+    lab = np.ascontiguousarray(labels, np.uint8).ravel()
+    if lab.size != nx * ny * nz:
+        raise ValueError("interpolate_labels_volume: labels have %d bytes, the volume %d" % (lab.size, nx * ny * nz))
+    new = lab.reshape(nz, ny, nx).copy()
+    src = np.ascontiguousarray(uncut if (r.flags & _lib.INTERPOLATE_EDIT_UNCUT and uncut is not None) else prepared, np.uint8).ravel()
+    if src.size != lab.size:
+        raise ValueError("interpolate_labels_volume: the density has %d bytes, the volume %d" % (src.size, lab.size))
+    slo, shi = (tuple(int(v) for v in pass_box[0]), tuple(int(v) for v in pass_box[1]))
+    if any(lo[a] < slo[a] or hi[a] > shi[a] for a in range(3)):
+        raise ValueError("interpolate_labels_volume: the request's box reaches outside the box of the interpolate pass")
+    if any(a >= b for a, b in zip(lo, hi)):
+        return new, result
+    shape = (shi[2] - slo[2], shi[1] - slo[1], shi[0] - slo[0])
+    inner = (slice(lo[2] - slo[2], hi[2] - slo[2]), slice(lo[1] - slo[1], hi[1] - slo[1]), slice(lo[0] - slo[0], hi[0] - slo[0]))
+    st = np.asarray(state, np.uint8).reshape(shape)[inner]
+    sub = (slice(lo[2], hi[2]), slice(lo[1], hi[1]), slice(lo[0], hi[0]))
+    old = new[sub]
+    d = src.reshape(nz, ny, nx)[sub]
+    to, out = np.asarray(r.to, np.int64).astype(np.uint8), np.asarray(r.out, np.int64).astype(np.uint8)
+    becomes = np.where((st & _lib.INTERPOLATE_INSIDE) != 0, to[old], out[old])
+    hit = ((st & _lib.INTERPOLATE_GAP) != 0) & (d >= r.window[0]) & (d <= r.window[1]) & (becomes != old)
+    count = int(hit.sum())
+    if count == 0:
+        return new, result
+    result["changed"] = count
+    result["left"][...] = np.bincount(old[hit], minlength=256)
+    result["arrived"][...] = np.bincount(becomes[hit], minlength=256)
+    z, y, x = np.nonzero(hit)
+    result["box"][...] = (lo[0] + x.min(), lo[1] + y.min(), lo[2] + z.min(), lo[0] + x.max() + 1, lo[1] + y.max() + 1, lo[2] + z.max() + 1)
+    if not r.flags & _lib.INTERPOLATE_EDIT_DRY_RUN:
+        new[sub] = np.where(hit, becomes, old)
+    return new, result
+
+
 def relabel_result_dict(result):
     """A relabel result as Python values: {"changed", "left": {label: n}, "arrived": {label: n}, "box": ((lo), (hi)) or None}."""
     box = [int(v) for v in result["box"]]
